@@ -508,6 +508,32 @@ def collective_probe(n_points, dev, iters=200):
             "launcher": "bench.py (self-launched ranks)" if os.environ.get("FFX_BENCH_LAUNCHED") else "torchrun"}
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(outdir, arrays, limit=DUMP_LIMIT_BYTES):
+    """writes {name: array} as outdir/<name>.npy in float32 (float64 stays float64).  If they come to more than `limit` bytes
+    together, each is cut to the same fraction of its elements, a sample drawn with a fixed seed from its flat index, so the
+    files of two builds hold the same elements in the same order.  Returns {name: [shape written, shape computed]}."""
+    import numpy as np
+
+    os.makedirs(outdir, exist_ok=True)
+    arrays = {k: np.asarray(v) for k, v in arrays.items()}
+    arrays = {k: v if v.dtype == np.float64 else v.astype(np.float32) for k, v in arrays.items()}
+    total = sum(v.nbytes for v in arrays.values())
+    budget = limit - 4096 * len(arrays)  # (room for the .npy headers)
+    written = {}
+    for name, a in arrays.items():
+        out = a
+        if total > budget:
+            n = max(1, int(a.size * budget / total))
+            idx = np.sort(np.random.default_rng(0).choice(a.size, size=n, replace=False))
+            out = a.reshape(-1)[idx]
+        np.save(os.path.join(outdir, f"{name}.npy"), np.ascontiguousarray(out))
+        written[name] = [list(out.shape), list(a.shape)]
+    return written
+
+
 def _gather_floats(x, dev):
     """[x of rank 0, x of rank 1, ...] on every rank"""
     import torch.distributed as td
@@ -546,6 +572,9 @@ def main():
                     help="the film's reconstruction filter: box (the headline workload of every round) or Mitsuba's gaussian, hdrfilm's default, which a scene "
                          "FILE without <rfilter> gets (ffx_render_fwd_filtered; the gradient step then re-traces: ffx_render_bwd_filtered)")
     ap.add_argument("--entity-device", default="cuda", help="device argument of ff.Scene (where the sampler bounds live and whose generator is used): cuda (the reference default) or cpu")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step of the headline bracket returned (the rendered image, float32) as DIR/image.npy, "
+                         "at most 64 MB (a fixed, seeded sample beyond that); the inputs are seeded, so two builds can be compared output for output")
     args = ap.parse_args()
 
     if args.gpus < 1:
@@ -612,9 +641,15 @@ def main():
     w_render = 0 if args.no_render_steps else args.warmup
     n_render = args.steps if not args.no_render_steps else 1
 
+    # --dump-outputs: the image of the bracket's last timed step, held by reference (no copy, no sync inside the timed region)
+    last_outputs = {}
+
     def timed_render_step(i):
         geom.timing = events if _timed(i, w_render, n_render) else None
-        return render_step(i)
+        img = render_step(i)
+        if args.dump_outputs and i == w_render + n_render - 1:
+            last_outputs["image"] = img
+        return img
 
     # Preflight (FFX_BENCH_PREFLIGHT=0: off): before anything is timed on this box, the kernel about to be timed must agree with the library's
     # OTHER implementation of the same render — the per-lane kernels (one ray per lane, LDS stack, binary BVH: FFX_TRAVERSAL=lane; ~20x
@@ -642,7 +677,9 @@ def main():
     t_render = _bracket(timed_render_step, n_render, w_render, dev, preflight_render if do_preflight else None, settle_render)
     geom.timing = None
     torch.cuda.synchronize()
-    renders_per_sec = world * args.steps / t_render
+    # to the host before any later render can reuse the image's buffer
+    last_outputs = {k: v.float().cpu().numpy() for k, v in last_outputs.items()}
+    renders_per_sec = world * n_render / t_render
     per_rank_t = _gather_floats(_bracket.local_s, dev)
     rccl = collective_probe(args.grad_grid**2, dev)
     k8_ms, k8_n = _kernel_ms(events, "render_fwd")
@@ -1003,7 +1040,7 @@ def main():
         "n_gpus": world,
         "steps": args.steps,
         "warmup": args.warmup,
-        "ms_per_step": 1e3 * t_render / args.steps,
+        "ms_per_step": 1e3 * t_render / n_render,  # (= --steps unless --no-render-steps)
         "higher_is_better": True,
         "scaling": "weak",
         "vs_baseline": None,
@@ -1030,7 +1067,7 @@ def main():
             "rfilter": args.rfilter,
             "material": ("principled BSDF (Mitsuba's model, reflection side), parameters randomised as the reference's scripts do" if args.material == "principled"
                          else "diffuse (Lambert)"),
-            "primary_rays_per_sec": world * args.steps * W * H * args.spp / t_render,
+            "primary_rays_per_sec": world * n_render * W * H * args.spp / t_render,
             "parallelism": f"dp{world}: independent scene samples per rank, no collective in the render loop",
             "render_paths": dict(wl.mi_scene.render_paths),
             # how the scene samples reached the device: "native" = one ffx_scene_step_h call each (ABI 8, the native params.update()), "python" = key writes + params.update()
@@ -1078,6 +1115,8 @@ def main():
     else:
         out["cpu_baseline"] = None
     out["evidence"] = cited_profiles(pkey) + ([f for f in cited_profiles("colon") if "colon" in f] if "colon_roofline" in cfg34 else [])
+    if args.dump_outputs:
+        out["dumped_outputs"] = {"dir": args.dump_outputs, "step": w_render + n_render - 1, "arrays": dump_outputs(args.dump_outputs, last_outputs)}
     print(json.dumps(out))
 
 

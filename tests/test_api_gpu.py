@@ -978,6 +978,31 @@ def test_filtered_cache_overflow_grows_to_the_dense_layout_before_it_re_traces(m
     assert not getattr(opt2, "_cache_overflowed", False) and opt2.step_paths["cache_k9"] == 6
 
 
+def test_bench_dumps_the_last_timed_image_and_repeats_it(tmp_path):
+    """`bench.py --dump-outputs DIR` writes the image the last of the K timed steps returned (DIR/image.npy, float32, H x W x 3); the inputs are
+    seeded, so a second run with the same arguments renders the same image; the line reports K and the milliseconds of one timed step."""
+    import json
+    import subprocess
+    import sys
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "FFX_DIST_BACKEND")}
+    env["FFX_BENCH_EXTRA_BRACKETS"] = "0"
+    imgs = []
+    for run in ("a", "b"):
+        res = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "5", "--warmup", "2", "--res", "128", "--no-cpu-baseline",
+                              "--no-grad-steps", "--dump-outputs", str(tmp_path / run)], env=env, cwd=root, capture_output=True, text=True, timeout=600)
+        assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-3000:]
+        (line,) = [ln for ln in res.stdout.splitlines() if ln.startswith("{")]
+        out = json.loads(line)
+        assert out["steps"] == 5 and out["ms_per_step"] == pytest.approx(1e3 / out["value"], rel=1e-9)
+        assert out["dumped_outputs"]["step"] == 2 + 5 - 1 and out["dumped_outputs"]["arrays"]["image"] == [[128, 128, 3], [128, 128, 3]]
+        img = np.load(tmp_path / run / "image.npy")
+        assert img.dtype == np.float32 and img.shape == (128, 128, 3) and np.isfinite(img).all() and img.max() > 0
+        imgs.append(img)
+    assert_image_close(imgs[1], imgs[0], 64, what="the dumped image of two identical runs")
+
+
 def test_bench_self_launches_its_ranks():
     """`python bench.py --gpus 2` with no torchrun environment: the launcher starts two fresh rank processes (here both on
     the one device, transport gloo — FFX_DIST_BACKEND=gloo is the explicit opt-in for that; on a node with >= 2 GPUs the

@@ -211,3 +211,27 @@ def test_committed_driver_line_carries_configs_3_and_4(bench):
     if tr is not None and r["traffic"] is not None and os.path.basename(tr["source"]) == os.path.basename(r["traffic_source"]):
         assert r["traffic"] == pytest.approx(tr["bytes"], rel=1e-12) and r["traffic_ratio"] == pytest.approx(tr["bytes"] / r["algorithmic_bytes_per_launch"], rel=1e-12)
     assert any("colon" in f for f in d["evidence"])
+
+
+def test_dump_outputs_writes_float_arrays_and_samples_the_same_elements_beyond_the_limit(bench, tmp_path):
+    """`bench.py --dump-outputs DIR`: every array lands as DIR/<name>.npy in float32 (float64 kept); past the size limit each is cut to a
+    fixed, seeded sample of its elements — the same elements in the same order on every run, so two builds compare output for output."""
+    import numpy as np
+
+    rng = np.random.default_rng(3)
+    img = rng.random((64, 48, 3)).astype(np.float16)
+    f64 = rng.random(100)
+    w = bench.dump_outputs(str(tmp_path / "a"), {"image": img, "loss": f64})
+    a = np.load(tmp_path / "a" / "image.npy")
+    assert a.dtype == np.float32 and a.shape == img.shape and np.array_equal(a, img.astype(np.float32))
+    assert np.load(tmp_path / "a" / "loss.npy").dtype == np.float64
+    assert w == {"image": [[64, 48, 3], [64, 48, 3]], "loss": [[100], [100]]}
+    limit = 3 * 4096
+    for d in ("b", "c"):
+        w = bench.dump_outputs(str(tmp_path / d), {"image": img, "loss": f64}, limit=limit)
+    b, c = (np.load(tmp_path / d / "image.npy") for d in ("b", "c"))
+    assert np.array_equal(b, c) and b.ndim == 1
+    assert sum(os.path.getsize(tmp_path / "b" / f) for f in os.listdir(tmp_path / "b")) <= limit
+    assert np.isin(b, img.astype(np.float32).reshape(-1)).all()
+    assert w["image"][1] == [64, 48, 3]
+    assert bench.DUMP_LIMIT_BYTES == 64 << 20
