@@ -115,8 +115,7 @@ __device__ void bin_scan_one(char *base, int nt, uint32_t cap, bool env) {
 }
 
 // apex records of the pre-pass (k_apex_records of ffx_trace.hip, same arithmetic): what to write for apex a
-struct BinApex { float o[FFX_N_APEX][3]; int on[FFX_N_APEX]; TriApex *out; uint32_t astride; uint32_t *cache_hdr; uint32_t cap_stray;
-                 uint32_t *gnw; int clear_on; }; // gnw: the per-slot normals as words (word 4 k + 3: shape / smooth / clear bits); clear_on: k_bin_clear will run
+struct BinApex { float o[FFX_N_APEX][3]; int on[FFX_N_APEX]; TriApex *out; uint32_t astride; uint32_t *cache_hdr; uint32_t cap_stray; };
 
 // One wave per workgroup whose registers fit the hole ONE retired render wave leaves: these launches run beside a render whose one-wave
 // workgroups refill every slot the moment it frees.  A four-wave workgroup of 96-VGPR waves waited for four slots and enough registers on ONE
@@ -156,16 +155,6 @@ __global__ void __launch_bounds__(BIN_BLOCK) __attribute__((amdgpu_waves_per_eu(
     }
   }
   const bool grid_on = bb.g[a].on != 0 && bb.base[a] != nullptr;
-  if (!FILL && a >= 1 && ba.gnw && ba.clear_on && k < n_tris) { // (clear_on == 0: the render kernels do not look at the bits)
-    // the emitter's "clear" bit of this triangle (ffx_common.h FFX_GN_CLEAR_BIT): set here for every triangle when the proof will run,
-    // taken back by k_bin_clear where it fails; cleared otherwise (a blob whose pre-pass ran before with other emitter positions).  A
-    // degenerate triangle's word stays 0 — that IS its flag.
-    uint32_t *w = ba.gnw + 4 * (size_t)k + 3;
-    if ((*w & FFX_GN_SHAPE_MASK) != 0u) {
-      if (grid_on && ((ba.clear_on >> (a - 1)) & 1) && ba.on[a]) atomicOr(w, FFX_GN_CLEAR_BIT(a));
-      else atomicAnd(w, ~FFX_GN_CLEAR_BIT(a));
-    }
-  }
   char *base = bb.base[a];
   uint32_t *starts = (uint32_t *)(base + ffx_bin_off_starts());
   uint32_t *cursors = (uint32_t *)(base + ffx_bin_off_cursors());
@@ -225,10 +214,6 @@ __global__ void __launch_bounds__(BIN_BLOCK) __attribute__((amdgpu_waves_per_eu(
       cls = (oL || oR || oT || oB) ? 0 : 3;
     }
   }
-#ifdef FFX_BINPROBE // timing experiments (tools/binprobe.py): 1 = no wave-cooperative path, 2 = no per-lane path, 3 = neither
-  if (FFX_BINPROBE & 2) { if (cls == 1) cls = 0; }
-  if (FFX_BINPROBE & 1) { if (cls >= 2) cls = 0; }
-#endif
   {
     // ---- triangles that touch at most sixteen tiles, a lane each.  Which tiles: a bit mask over the lane's own window (no atomics
     // yet).  Then the wave walks its lanes' masks in rounds, every lane offering its next tile, and lanes that offer the SAME tile —
@@ -365,97 +350,8 @@ __global__ void __launch_bounds__(64) k_bin_scan(BinBuild bb) {
   if (bb.g[g].on && bb.base[g]) bin_scan_one(bb.base[g], bb.g[g].nx * bb.g[g].ny, bb.cap, g >= 1 && ((bb.env_mask >> (g - 1)) & 1));
 }
 
-// ---- "clear" triangles (ffx_common.h FFX_GN_CLEAR_BIT): the proof that nothing can shadow a triangle from an emitter.
-// Shadow segments run from the emitter E to Po = P + off n_k, P on triangle k, n_k its unit normal on the viewer's side — which is E's
-// side for every sample E lights — off = (1 + max|P|) 8.9e-5 >= 8.9e-5; hits at t >= 1 - 8.9e-4 do not count.  Triangle j cannot
-// intersect the counted part of ANY such segment if
-//   (H0) its projection from E is apart from k's (padded boxes in the grid: a segment is a POINT of E's image plane), or
-//   (H1) all of j lies behind k's plane or within 2e-5 above it: the counted part of the segment stays >= 8.9e-5 (1 - 8.9e-4) above, or
-//   (H2) j faces E, the two E-side normals agree (cos >= 0.5) and all of k lies in front of j's plane or within 2e-5 behind it: then
-//        Po (lifted by >= 8.9e-5 x 0.5) and E are both strictly in front of j's plane, and so is the whole segment.
-// The tolerances shrink by the rounding of the plane evaluations (3e-7 of the coordinates' magnitude: scenes beyond ~60 units lose them and
-// keep the strict tests).  Two triangles whose projections overlap share a tile of E's grid, so testing k against the entries of its
-// tiles is complete.  Unsafe projections (a vertex behind / beside the apex) have infinite boxes: H0 never holds for them, H1 / H2 are 3-D.
-// A wave per (tile, chunk of 64 entries k): lanes on k, the tile's entries j one after the other (uniform: scalar loads).
-// The entries j are walked 64 at a time: every lane loads ONE of them and derives its plane (normal towards the emitter, its length, the
-// facing test, the coordinate magnitude) — one memory round trip per 64 entries — and the inner loop broadcasts entry after entry with
-// v_readlane.  (First version: entry j and its record fetched inside the loop, two dependent loads per iteration: 357 us beside a render
-// for 9 M instructions' worth of work, the loop's period.)
-#define CLEAR_SPLIT 4
-struct ClearTri { v3 a, b, c, n; float len, s, M; float4 bb; int slot; };
-__device__ __forceinline__ ClearTri clear_load(const char *__restrict__ ents, const TriRec *__restrict__ recs, uint32_t i, v3 E) {
-  ClearTri t;
-  const float4 *e4 = reinterpret_cast<const float4 *>(ents + ((size_t)i << 6));
-  t.bb = e4[0];
-  t.slot = __float_as_int(e4[3].y);
-  const float4 *r4 = reinterpret_cast<const float4 *>(recs + t.slot);
-  const float4 ra = r4[0], rb = r4[1], rc = r4[2];
-  const v3 e1 = V3(ra.w, rb.x, rb.y), e2 = V3(rb.z, rb.w, rc.x);
-  t.a = V3(ra.x, ra.y, ra.z);
-  t.b = V3(t.a.x + e1.x, t.a.y + e1.y, t.a.z + e1.z);
-  t.c = V3(t.a.x + e2.x, t.a.y + e2.y, t.a.z + e2.z);
-  t.n = vcross(e1, e2);
-  t.s = vdot(t.n, vsub(E, t.a));
-  if (t.s < 0.f) { t.n = V3(-t.n.x, -t.n.y, -t.n.z); t.s = -t.s; } // towards the emitter
-  t.len = sqrtf(vdot(t.n, t.n));
-  t.M = fmaxf(fmaxf(fmaxf(fabsf(t.a.x), fabsf(t.a.y)), fabsf(t.a.z)), fmaxf(fmaxf(fabsf(e1.x) + fabsf(e2.x), fabsf(e1.y) + fabsf(e2.y)), fabsf(e1.z) + fabsf(e2.z)));
-  return t;
-}
-template <int WPE>
-__global__ void __launch_bounds__(BIN_BLOCK) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) k_bin_clear(const TriRec *__restrict__ recs, BinBuild bb, BinApex ba) {
-  FFX_SIDE_PRIO();
-  const int a = 1 + (int)blockIdx.y;
-  if (!bb.g[a].on || !bb.base[a] || !ba.on[a] || !ba.gnw || !((ba.clear_on >> (a - 1)) & 1)) return;
-  const char *base = bb.base[a];
-  if (((const BinHdr *)base)->ok == 0u) return; // (lists incomplete: the render kernels do not look at the bits then, bins_ready)
-  const int tile = (int)blockIdx.x / CLEAR_SPLIT, part = (int)blockIdx.x % CLEAR_SPLIT;
-  if (tile >= bb.g[a].nx * bb.g[a].ny) return;
-  const uint32_t *starts = (const uint32_t *)(base + ffx_bin_off_starts());
-  const uint32_t beg = starts[tile], n = starts[tile + 1] - beg;
-  if (n < 2u) return; // alone in its tile
-  const char *ents = base + ffx_bin_off_entries() + ((size_t)beg << 6);
-  const uint32_t lane = threadIdx.x & 63u;
-  const v3 E = V3(ba.o[a][0], ba.o[a][1], ba.o[a][2]);
-  const uint32_t bit = FFX_GN_CLEAR_BIT(a);
-  auto bc = [](float v, uint32_t l) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), (int)l)); };
-  for (uint32_t k0 = (uint32_t)part * 64u; k0 < n; k0 += 64u * CLEAR_SPLIT) {
-    const uint32_t ki = k0 + lane;
-    const bool valid = ki < n;
-    const ClearTri K = clear_load(ents, recs, valid ? ki : n - 1u, E);
-    // (already refuted in another tile: nothing to prove.  The emitter must stand clearly off k's plane — 1e-4: above the tolerances — or the
-    // first part of a segment is no higher above it than j may be)
-    bool open = valid && (ba.gnw[4 * (size_t)K.slot + 3] & bit) != 0u;
-    bool unclear = open && !(K.len > 0.f && K.s > 1e-4f * K.len);
-    open = open && !unclear;
-    for (uint32_t j0 = 0; j0 < n && __ballot(open) != 0ull; j0 += 64u) { // (uniform)
-      const uint32_t m = min(64u, n - j0);
-      const ClearTri J = clear_load(ents, recs, j0 + lane < n ? j0 + lane : n - 1u, E); // this lane's entry of the chunk
-      for (uint32_t t = 0; t < m && __ballot(open) != 0ull; ++t) { // (uniform) entry j0 + t, broadcast
-        const int slot_j = __builtin_amdgcn_readlane(J.slot, (int)t);
-        const float bx0 = bc(J.bb.x, t), by0 = bc(J.bb.y, t), bx1 = bc(J.bb.z, t), by1 = bc(J.bb.w, t);
-        const bool other = open && slot_j != K.slot;
-        const bool apart = K.bb.x > bx1 || K.bb.z < bx0 || K.bb.y > by1 || K.bb.w < by0; // (H0; an unsafe entry's infinite box is never apart)
-        if (__ballot(other && !apart) == 0ull) continue;
-        const v3 ja = V3(bc(J.a.x, t), bc(J.a.y, t), bc(J.a.z, t)), jb = V3(bc(J.b.x, t), bc(J.b.y, t), bc(J.b.z, t)), jc = V3(bc(J.c.x, t), bc(J.c.y, t), bc(J.c.z, t));
-        const v3 nj = V3(bc(J.n.x, t), bc(J.n.y, t), bc(J.n.z, t));
-        const float lenj = bc(J.len, t), sj = bc(J.s, t), Mj = bc(J.M, t);
-        const float tol = 2e-5f - 3e-7f * (K.M + Mj); // world units; <= 0 for large coordinates: the strict tests remain
-        // H1: j behind k's plane
-        // (differences first: a neighbour's vertex minus k's is exact in float, Sterbenz — the products then carry no cancellation)
-        const float tk = tol * K.len;
-        const bool h1 = vdot(K.n, vsub(ja, K.a)) <= tk && vdot(K.n, vsub(jb, K.a)) <= tk && vdot(K.n, vsub(jc, K.a)) <= tk;
-        // H2: j faces the emitter, the emitter-side normals agree, k in front of j's plane
-        const float tj = -tol * lenj;
-        const bool h2 = sj > 1e-5f * lenj && vdot(K.n, nj) >= 0.5f * K.len * lenj && vdot(nj, vsub(K.a, ja)) >= tj && vdot(nj, vsub(K.b, ja)) >= tj && vdot(nj, vsub(K.c, ja)) >= tj;
-        if (other && !apart && !h1 && !h2) { unclear = true; open = false; }
-      }
-    }
-    if (valid && unclear) atomicAnd(ba.gnw + 4 * (size_t)K.slot + 3, ~bit);
-  }
-}
-
 // ---- the ENVELOPE of an emitter's grid (ffx_common.h FFX_ENV_SUB; round 6).  The spot's any-hit stage is a quarter of the render kernel for an
-// emitter next to the camera that hardly anything shadows, and a per-triangle proof (k_bin_clear) settles a third of the
+// emitter next to the camera that hardly anything shadows, and a per-triangle proof (round 5) settled a third of the
 // triangles at best: the neighbours of a triangle on a curved surface do come within the shadow ray's ignored tail of it.  What CAN be stated
 // cheaply is where the front of everything a tile lists lies.  Seen from the emitter E a triangle's plane is affine in 1 / depth:
 //     1 / t_j(d) = d . n_j,  n_j = A_j / T_j  (the apex record's own numbers),      d = Z Minv (x, y, 1)   =>   1 / (t_j Z) = m_j . (x, y, 1)
@@ -556,12 +452,11 @@ __global__ void __launch_bounds__(BIN_BLOCK) __attribute__((amdgpu_waves_per_eu(
 }
 
 void ffx_bins_launch(const TriRec *recs, int n_tris, const BinBuild &bb, const void *apex_out, const float (*apex_o)[3], const int *apex_on, uint32_t astride,
-                     uint32_t *cache_hdr, uint32_t cap_stray, hipStream_t s, int beside_lambert, uint32_t *gn_words, int clear_on, const EnvBuild *env) {
+                     uint32_t *cache_hdr, uint32_t cap_stray, hipStream_t s, int beside_lambert, const EnvBuild *env) {
   BinApex ba;
   memset(&ba, 0, sizeof ba);
   for (int a = 0; a < FFX_N_APEX; ++a) { ba.on[a] = apex_on[a]; ba.o[a][0] = apex_o[a][0]; ba.o[a][1] = apex_o[a][1]; ba.o[a][2] = apex_o[a][2]; }
   ba.out = (TriApex *)apex_out; ba.astride = astride; ba.cache_hdr = cache_hdr; ba.cap_stray = cap_stray;
-  ba.gnw = gn_words; ba.clear_on = clear_on;
   const dim3 grid(ffx_cdiv(n_tris, BIN_BLOCK), FFX_N_APEX);
   if (beside_lambert) hipLaunchKernelGGL((k_bin<false, 8>), grid, dim3(BIN_BLOCK), 0, s, recs, n_tris, bb, ba);
   else hipLaunchKernelGGL((k_bin<false, 7>), grid, dim3(BIN_BLOCK), 0, s, recs, n_tris, bb, ba);
@@ -569,13 +464,6 @@ void ffx_bins_launch(const TriRec *recs, int n_tris, const BinBuild &bb, const v
     hipLaunchKernelGGL(k_bin_scan, dim3(FFX_N_APEX), dim3(64), 0, s, bb);
     if (beside_lambert) hipLaunchKernelGGL((k_bin<true, 8>), grid, dim3(BIN_BLOCK), 0, s, recs, n_tris, bb, ba);
     else hipLaunchKernelGGL((k_bin<true, 7>), grid, dim3(BIN_BLOCK), 0, s, recs, n_tris, bb, ba);
-    if (gn_words && clear_on && (((clear_on & 1) && bb.g[1].on && apex_on[1]) || ((clear_on & 2) && bb.g[2].on && apex_on[2]))) { // the emitters' grids: which triangles nothing can shadow
-      int nt = 0;
-      for (int a = 1; a < FFX_N_APEX; ++a) if (((clear_on >> (a - 1)) & 1) && bb.g[a].on && apex_on[a]) nt = nt > bb.g[a].nx * bb.g[a].ny ? nt : bb.g[a].nx * bb.g[a].ny;
-      const dim3 cgrid(nt * CLEAR_SPLIT, FFX_N_APEX - 1);
-      if (beside_lambert) hipLaunchKernelGGL((k_bin_clear<8>), cgrid, dim3(BIN_BLOCK), 0, s, recs, bb, ba);
-      else hipLaunchKernelGGL((k_bin_clear<7>), cgrid, dim3(BIN_BLOCK), 0, s, recs, bb, ba);
-    }
     if (env && apex_out) { // the emitters' envelopes (ffx_common.h FFX_ENV_SUB): a wave per tile
       int nt[FFX_N_APEX] = {0, 0, 0};
       for (int a = 1; a < FFX_N_APEX; ++a) if (env->on[a] && bb.g[a].on && bb.base[a] && apex_on[a]) nt[a] = bb.g[a].nx * bb.g[a].ny;

@@ -186,7 +186,7 @@ inline int32_t leaf_code(int first, int count) { return ~(int32_t)(((uint32_t)fi
 // node of its own.  A wide node of layer k is a maximal subtree that contains at most FFX_WIDE items of
 // layer k-1 (clusters for k = 1; items that stay alone simply move up a layer), and those items are its
 // children.  Every child's box is the box of ONE binary node, which the binary refit already maintains
-// (in that node's parent): the overlay only re-quantises them, and it inherits the SAH quality of the
+// (in that node's parent): the overlay only copies them, and it inherits the SAH quality of the
 // binary tree.  Typical fill: ~45 of 64 (53 k triangles: 1 198 clusters, 27 + 1 wide nodes).
 struct WideNode { std::vector<int> kids; int bnode = -1; };
 
@@ -251,14 +251,10 @@ void build_wide(const std::vector<BuildNode> &bn, int root, std::vector<WideNode
 // FFX_WIDE_MAX_DEPTH): split the child with the most triangles instead, which bounds the depth by log32.
 void build_wide_topdown(const std::vector<BuildNode> &bn, const std::vector<float> &area, int root, bool by_count, std::vector<WideNode> &wide,
                         std::vector<int> &wide_of, int &depth_out) {
-  // experiment knobs (host side, read at build time): largest cluster, priority = area * count^FFX_WIDE_COST_EXP
-  const int CL = getenv("FFX_WIDE_CLUSTER") ? std::max(4, std::min(FFX_WIDE, atoi(getenv("FFX_WIDE_CLUSTER")))) : FFX_WIDE;
-  const float cexp = getenv("FFX_WIDE_COST_EXP") ? (float)atof(getenv("FFX_WIDE_COST_EXP")) : 0.f;
-  auto prio = [&](int id) { return cexp == 0.f ? area[id] : area[id] * std::pow((float)bn[id].scount, cexp); };
   wide.clear();
   wide_of.assign(bn.size(), -1);
   depth_out = 0;
-  if (bn[root].scount <= CL) return; // the whole scene is one cluster
+  if (bn[root].scount <= FFX_WIDE) return; // the whole scene is one cluster
   std::vector<std::pair<int, int>> queue{{root, 1}};
   for (size_t qi = 0; qi < queue.size(); ++qi) {
     const int b = queue[qi].first, depth = queue[qi].second;
@@ -269,10 +265,10 @@ void build_wide_topdown(const std::vector<BuildNode> &bn, const std::vector<floa
       int best = -1;
       for (int k = 0; k < (int)w.kids.size(); ++k) {
         const int id = w.kids[k];
-        if (bn[id].scount <= CL) continue; // a cluster stays whole
+        if (bn[id].scount <= FFX_WIDE) continue; // a cluster stays whole
         if (best < 0) { best = k; continue; }
         const int bid = w.kids[best];
-        const bool better = by_count ? (bn[id].scount > bn[bid].scount) : (prio(id) > prio(bid) || (prio(id) == prio(bid) && bn[id].scount > bn[bid].scount));
+        const bool better = by_count ? (bn[id].scount > bn[bid].scount) : (area[id] > area[bid] || (area[id] == area[bid] && bn[id].scount > bn[bid].scount));
         if (better) best = k;
       }
       if (best < 0) break;
@@ -283,7 +279,7 @@ void build_wide_topdown(const std::vector<BuildNode> &bn, const std::vector<floa
     std::sort(w.kids.begin(), w.kids.end(), [&](int a, int c) { return bn[a].sfirst < bn[c].sfirst; });
     wide_of[b] = (int)wide.size();
     for (int id : w.kids)
-      if (bn[id].scount > CL) queue.push_back({id, depth + 1});
+      if (bn[id].scount > FFX_WIDE) queue.push_back({id, depth + 1});
     wide.push_back(std::move(w));
     depth_out = std::max(depth_out, depth);
   }
@@ -589,14 +585,9 @@ int ffx_bvh_build_host(const float *verts, int n_verts, const int32_t *tris, int
       const std::vector<int> &kids = wide[w].kids;
       for (int j = 0; j < FFX_WIDE; ++j) {
         WideChild &c = wn[w * FFX_WIDE + j];
-#if FFX_WIDE_F32
         c.lo[0] = c.lo[1] = c.lo[2] = 3.0e38f; // inverted box: lanes beyond the child count are masked off anyway
         c.hi0 = c.hi12[0] = c.hi12[1] = -3.0e38f;
         c.pad = 0;
-#else
-        c.q[0] = c.q[1] = c.q[2] = 0xffff; // inverted box: lanes beyond the child count are masked off anyway
-        c.q[3] = c.q[4] = c.q[5] = 0;
-#endif
         c.ref = 0;
         wsrc[w * FFX_WIDE + j] = -1;
         if (j >= (int)kids.size()) continue;

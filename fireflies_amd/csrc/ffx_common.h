@@ -26,12 +26,8 @@ static inline int ffx_cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 // quarter of a million one-wave workgroups keep every SIMD's issue port busy: a wave of these latency-bound kernels then gets one issue
 // slot in eight, and their dependent chain — which the next render waits for — took 0.46 ms instead of 0.12 (tools/steptrace.py: the
 // step's period WAS that chain).  s_setprio raises the wave's priority at the SIMD's arbiter: their few instructions go first, the
-// render loses nothing measurable.  -DFFX_NO_SIDE_PRIO switches it off (A/B).
-#ifdef FFX_NO_SIDE_PRIO
-#define FFX_SIDE_PRIO() do { } while (0)
-#else
+// render loses nothing measurable.
 #define FFX_SIDE_PRIO() __builtin_amdgcn_s_setprio(3)
-#endif
 
 // ------------------------------------------------------------------ small POD blocks passed by value
 struct Mat4 { float m[16]; };
@@ -108,18 +104,12 @@ static inline uint64_t ffx_apex_stride(int n_tris) { return ((((uint64_t)n_tris 
 static inline uint64_t ffx_apex_offset(const ffx_bvh_info *info, int k) { return info->total_bytes - (uint64_t)(FFX_N_APEX - k) * ffx_apex_stride(info->n_tris); }
 
 // ------------------------------------------------------------------ 64-wide overlay
-// One child of a wide node, or one triangle of a cluster: a box on the 16-bit grid of the current pose
-// (x = org + q * step per axis; q[0..2] round down, q[3..5] round up, one extra cell of slack each) and
-// a reference: cluster << 31 | element << 6 | (count - 1), where `element` indexes the ONE array of 16-byte
-// elements formed by the wide nodes (64 each) followed by the triangle boxes in leaf-slot order.  In the
-// triangle part `ref` is unused.
-#ifndef FFX_WIDE_F32
-#define FFX_WIDE_F32 1
-#endif
-#if FFX_WIDE_F32
-// float32 boxes (32-byte elements): the 16-bit grid cost six integer-to-float conversions per step of the walk —
-// conversions issue at the 4-cycle rate, a third of the box test's issue time (tools/ubench/issue_rates.hip) — for
-// half the bytes of a structure that lives in L2 anyway.  WideHdr then holds the identity grid (org 0, step 1).
+// One child of a wide node, or one triangle of a cluster: a float32 box of the current pose and a reference:
+// cluster << 31 | element << 6 | (count - 1), where `element` indexes the ONE array of 32-byte elements formed by
+// the wide nodes (64 each) followed by the triangle boxes in leaf-slot order.  In the triangle part `ref` is unused.
+// (Float boxes, not a 16-bit grid: the grid cost six integer-to-float conversions per step of the walk — conversions
+// issue at the 4-cycle rate, a third of the box test's issue time (tools/ubench/issue_rates.hip) — for half the bytes
+// of a structure that lives in L2 anyway.)
 struct __attribute__((aligned(16))) WideChild {
   float lo[3];
   float hi0;   // hi[0]
@@ -129,17 +119,9 @@ struct __attribute__((aligned(16))) WideChild {
 };
 static_assert(sizeof(WideChild) == 32, "wide child must be 32 bytes");
 #define FFX_WIDE_ELEM_SHIFT 5
-#else
-struct __attribute__((aligned(16))) WideChild {
-  uint16_t q[6];
-  int32_t ref;
-};
-static_assert(sizeof(WideChild) == 16, "wide child must be 16 bytes");
-#define FFX_WIDE_ELEM_SHIFT 4
-#endif
 #define FFX_WIDE 64
 #define FFX_WIDE_MAX_DEPTH 6
-// grid header written by the refit: org[3], step[3] (floats)
+// grid header written by the refit: org[3], step[3] (floats) — the identity grid (org 0, step 1) of the float boxes
 struct WideHdr { float org[3]; float step[3]; float pad[10]; };
 static_assert(sizeof(WideHdr) == 64, "wide header must be 64 bytes");
 
@@ -187,19 +169,12 @@ struct BinsK {
   const char *base[3]; // per apex: BinHdr, list starts, cursors, entries
   BinGrid g[3];
   float cam_inv_ts_x, cam_inv_ts_y; // camera pixels -> tile units
-  int clear_on;                     // the emitters' "nothing can shadow this triangle" bits of the per-slot normals are valid (FFX_GN_CLEAR_BIT)
   int env_on;                       // mask over the emitters (bit 0 projector, bit 1 spot): the pre-pass built that grid's envelope
   uint32_t env_off;                 // ffx_bin_off_env(n_tris): the envelope's offset inside an apex's bins area
 };
-// Round 5: "clear" triangles.  The spot's any-hit stage was a quarter of the render kernel (K8 0.400 -> 0.302 ms without it, tools/k8ab.py) for an
-// emitter next to the camera that hardly anything shadows.  The pre-pass (k_bin_clear, ffx_bins.hip) proves per triangle k and emitter E that
-// NO other triangle can intersect a shadow segment from E to a lifted point of k — every triangle j listed in a tile of E's grid with k is
-// (H0) apart from k in E's image plane, or (H1) wholly behind k's plane, or (H2) front-facing to E with k wholly in front of ITS plane (the
-// concave neighbours of a tube seen from inside) — and leaves bit 27 + a (a = 1 projector, 2 spot) of the fourth word of the triangle's
-// per-slot normal (ffx_bvh_info.off_gn) set.  A packet all of whose samples that need emitter a lie on such triangles skips the walk.
+// the fourth word of a triangle's per-slot normal (ffx_bvh_info.off_gn): shape + 1 (0: a degenerate triangle), and the smooth-shading bit
 #define FFX_GN_SHAPE_MASK 0x0fffffff
 #define FFX_GN_SMOOTH_BIT 0x40000000
-#define FFX_GN_CLEAR_BIT(a) (1u << (27 + (a)))
 // the pre-pass of a packet render on `s` (ffx_bins.hip): apex records + the bins of the enabled grids — three launches (count, scan,
 // fill); with every grid off it is the apex records alone (one launch)
 struct BinBuild { BinGrid g[3]; char *base[3]; uint32_t cap; uint32_t *arrive; /* [dev] one word, zero between builds: BinHdr.pad0 of apex 0 */
@@ -208,8 +183,7 @@ struct BinBuild { BinGrid g[3]; char *base[3]; uint32_t cap; uint32_t *arrive; /
 // over the grid) / 40 — a listed triangle whose plane is steeper than 1 : 40 against a cell's rays poisons the cell —, kap = (1 - 10 eps)(1 + 6e-5)
 struct EnvBuild { float Minv[FFX_N_APEX][9]; float graz[FFX_N_APEX]; int on[FFX_N_APEX]; uint32_t env_off; float kap; };
 void ffx_bins_launch(const TriRec *recs, int n_tris, const BinBuild &bb, const void *apex_out, const float (*apex_o)[3], const int *apex_on, uint32_t astride,
-                     uint32_t *cache_hdr, uint32_t cap_stray, hipStream_t s, int beside_lambert = 0, uint32_t *gn_words = nullptr, int clear_on = 0,
-                     const EnvBuild *env = nullptr);
+                     uint32_t *cache_hdr, uint32_t cap_stray, hipStream_t s, int beside_lambert = 0, const EnvBuild *env = nullptr);
 
 // top bit of the `cap_stray` argument of the launches that reset an adjoint cache's header (k_bin<false>, k_apex_records, k_cache_reset):
 // FFX_RENDER_CACHE_KEEP_DROPPED — empty the arena, keep the `dropped` count of the step's earlier scene samples

@@ -219,68 +219,29 @@ __global__ void __launch_bounds__(TAIL_BLOCK) k_refit_tail(BvhNode *nodes, const
   }
 }
 
-// ---- 64-wide overlay (ffx_common.h): after the binary refit, every box the wave-packet kernels test is
-// re-expressed on a 16-bit grid spanning the scene's bounding box of THIS pose (the root box the refit
-// just produced): triangle boxes in leaf-slot order and the children of the wide inner nodes, each of which
-// is the box of one binary node (wsrc: binary node * 2 + side).  q_lo = floor - 1, q_hi = ceil + 1: the
-// extra cell (1.5e-5 of the scene extent) absorbs every rounding of the de-quantisation in the kernels.
-__device__ __forceinline__ void grid_of_root(const BvhNode *__restrict__ nodes, float org[3], float step[3], float inv[3]) {
-  const BvhNode &n = nodes[0];
-  float ext[3], emax = 0.f;
-#pragma unroll
-  for (int a = 0; a < 3; ++a) {
-    const float lo = fminf(n.lo0[a], n.lo1[a]), hi = fmaxf(n.hi0[a], n.hi1[a]);
-    org[a] = lo;
-    ext[a] = hi - lo;
-    emax = fmaxf(emax, ext[a]);
-  }
-#pragma unroll
-  for (int a = 0; a < 3; ++a) {
-    const float e = fmaxf(ext[a], fmaxf(emax * 1e-6f, 1e-30f)); // a flat scene still gets a non-degenerate grid
-    step[a] = e * (1.0f / 65533.0f);                            // cells 1 .. 65534 span the box: the slack cell never clips
-    inv[a] = 65533.0f / e;
-    org[a] -= step[a];
-  }
-}
-__device__ __forceinline__ void quantise_box(const float lo[3], const float hi[3], const float org[3], const float inv[3], WideChild &c) {
-#if FFX_WIDE_F32
-  // the boxes as they are (leaf boxes carry the refit's relative padding; the walk's packet constants carry the
-  // padding for its own roundings, make_widepk)
+// ---- 64-wide overlay (ffx_common.h): after the binary refit, every box the wave-packet kernels test is copied
+// into the overlay as it is: triangle boxes in leaf-slot order and the children of the wide inner nodes, each of which
+// is the box of one binary node (wsrc: binary node * 2 + side).  Leaf boxes carry the refit's relative padding; the
+// walk's packet constants carry the padding for its own roundings (make_widepk).
+__device__ __forceinline__ void wide_box(const float lo[3], const float hi[3], WideChild &c) {
   c.lo[0] = lo[0]; c.lo[1] = lo[1]; c.lo[2] = lo[2];
   c.hi0 = hi[0]; c.hi12[0] = hi[1]; c.hi12[1] = hi[2];
-#else
-#pragma unroll
-  for (int a = 0; a < 3; ++a) {
-    const float ql = floorf((lo[a] - org[a]) * inv[a]) - 1.0f, qh = ceilf((hi[a] - org[a]) * inv[a]) + 1.0f;
-    c.q[a] = (uint16_t)fminf(fmaxf(ql, 0.f), 65535.f);
-    c.q[3 + a] = (uint16_t)fminf(fmaxf(qh, 0.f), 65535.f);
-  }
-#endif
 }
 __global__ void __launch_bounds__(UPD_BLOCK)
     k_wide_quant(const BvhNode *__restrict__ nodes, const TriRec *__restrict__ recs, int n_tris, WideChild *__restrict__ tq, WideChild *__restrict__ wn,
                  const int32_t *__restrict__ wsrc, int n_wchild, WideHdr *__restrict__ hdr) {
   const int i = blockIdx.x * UPD_BLOCK + threadIdx.x;
-  float org[3], step[3], inv[3];
-#if FFX_WIDE_F32
-#pragma unroll
-  for (int a = 0; a < 3; ++a) { org[a] = 0.f; step[a] = 1.f; inv[a] = 1.f; }
-#else
-  grid_of_root(nodes, org, step, inv);
-#endif
   if (i == 0) {
 #pragma unroll
-    for (int a = 0; a < 3; ++a) { hdr->org[a] = org[a]; hdr->step[a] = step[a]; }
+    for (int a = 0; a < 3; ++a) { hdr->org[a] = 0.f; hdr->step[a] = 1.f; }
   }
   if (i < n_tris) {
     float lo[3], hi[3];
     leaf_box(recs, ~(int32_t)((uint32_t)i << 3), lo, hi); // the padded box of the single triangle in slot i
     WideChild c;
-    quantise_box(lo, hi, org, inv, c);
+    wide_box(lo, hi, c);
     c.ref = 0;
-#if FFX_WIDE_F32
     c.pad = 0;
-#endif
     tq[i] = c;
   } else if (i < n_tris + n_wchild) {
     const int k = i - n_tris;
@@ -288,8 +249,8 @@ __global__ void __launch_bounds__(UPD_BLOCK)
     if (src < 0) return;
     const BvhNode &n = nodes[src >> 1];
     WideChild c = wn[k];
-    if (src & 1) quantise_box(n.lo1, n.hi1, org, inv, c);
-    else quantise_box(n.lo0, n.hi0, org, inv, c);
+    if (src & 1) wide_box(n.lo1, n.hi1, c);
+    else wide_box(n.lo0, n.hi0, c);
     wn[k] = c;
   }
 }
@@ -432,7 +393,6 @@ static int scene_update_impl(void *bvh, const ffx_bvh_info *info, const float *s
                              const int32_t *vert_off, const float *xform, int n_shapes, const ffx_smooth *smooth, ffx_stream s, bool host_tab, int top = 0) {
   if (top == 2) {
     if (!bvh || !info) FFX_FAIL(FFX_ERR_ARG, "scene_refit_top: bad argument");
-#if FFX_WIDE_F32
     if (refit_fused_enabled() && refit_split_enabled() && info->off_plan != 0 && info->n_treelets > 0 && info->off_tq != 0) {
       char *b = (char *)bvh;
       SmoothTab sm0;
@@ -444,7 +404,6 @@ static int scene_update_impl(void *bvh, const ffx_bvh_info *info, const float *s
                          (const int32_t *)nullptr, (const float *)nullptr, 1, tab0, sm0, 2);
       FFX_CHECK_LAUNCH("scene_refit_top");
     }
-#endif
     return FFX_OK;
   }
   if (!bvh || !info || !src_verts || !tris || !tri_shape || !vert_off || !xform || n_shapes < 1) FFX_FAIL(FFX_ERR_ARG, "scene_update: bad argument");
@@ -489,7 +448,6 @@ static int scene_update_impl(void *bvh, const ffx_bvh_info *info, const float *s
       FFX_CHECK_LAUNCH("scene_update/vertex_normals");
     }
   }
-#if FFX_WIDE_F32
   if (info->off_plan != 0 && info->n_treelets > 0 && info->off_tq != 0 && refit_fused_enabled()) {
     if (info->plan_ints < 8 * (info->n_treelets + 1) + 1 || info->off_plan + 4ull * (uint64_t)info->plan_ints > info->total_bytes)
       FFX_FAIL(FFX_ERR_ARG, "scene_update: bad refit plan");
@@ -510,7 +468,6 @@ static int scene_update_impl(void *bvh, const ffx_bvh_info *info, const float *s
     FFX_CHECK_LAUNCH("scene_update/fused");
     return FFX_OK;
   }
-#endif
   if (host_tab) {
     hipLaunchKernelGGL(k_build_records<true>, dim3(ffx_cdiv(info->n_tris, UPD_BLOCK)), dim3(UPD_BLOCK), 0, st, order, recs, info->n_tris, src_verts, tris,
                        tri_shape, (const int32_t *)nullptr, (const float *)nullptr, n_shapes, tab, sm);

@@ -1152,7 +1152,7 @@ struct PatSync {
 };
 static_assert(sizeof(PatSync) == FFX_PATTERN_SYNC_BYTES && offsetof(PatSync, stale) == 16 && offsetof(PatSync, timeout) == 20 && offsetof(PatSync, hdr) == 72,
               "ffx.h: FFX_PATTERN_SYNC_BYTES and the documented offsets");
-struct FwdK { float *pts, *tsum, *tsor, *ws, *zero, *tex, *kept_new; const float *kept_old; long n_zero; int want_softor, nbx, nby, check_kept, pow_cache; unsigned int epoch; };
+struct FwdK { float *pts, *tsum, *tsor, *ws, *zero, *tex, *kept_new; const float *kept_old; long n_zero; int want_softor, nbx, nby, check_kept; unsigned int epoch; };
 // the data term is complete when its slices AND the regulariser's value (point 0's workgroup) are: whoever of the slice helpers and the updating
 // workgroup gets here last adds the slices up
 __device__ __forceinline__ void pattern_step_fin(PatSync *sy, unsigned int participants, int n, const AdamK &adam, float *reg_value, float loss_div) {
@@ -1224,7 +1224,7 @@ __global__ void __launch_bounds__(SPLAT_BLOCK)
       // beta^t: the running products of the last launch when they belong to step t - 1 and to these betas (one multiply instead of two
       // double-precision pow() in this workgroup's serial tail); pow() otherwise
       double p1, p2;
-      if (fw.pow_cache && sy->pw_t == (double)t - 1.0 && sy->pw_b1 == adam.beta1 && sy->pw_b2 == adam.beta2 && t > 1.0f) { p1 = sy->pw1 * adam.beta1; p2 = sy->pw2 * adam.beta2; }
+      if (sy->pw_t == (double)t - 1.0 && sy->pw_b1 == adam.beta1 && sy->pw_b2 == adam.beta2 && t > 1.0f) { p1 = sy->pw1 * adam.beta1; p2 = sy->pw2 * adam.beta2; }
       else { p1 = pow(adam.beta1, (double)t); p2 = pow(adam.beta2, (double)t); }
       for (int i = tid; i < n; i += SPLAT_BLOCK) {
         AdamIn in = in0;
@@ -1642,8 +1642,6 @@ int ffx_pattern_step(float *rays, int n, const float *KF, float sigma, int size0
   fw.pts = pts; fw.tsum = tsum; fw.tsor = fw.want_softor ? tsor : nullptr; fw.ws = fw.want_softor ? ws : nullptr; fw.zero = zero; fw.n_zero = zero ? n_zero : 0L; fw.tex = tex;
   fw.kept_new = rays_kept + (size_t)(epoch & 1u) * 3 * (size_t)n; fw.kept_old = rays_kept + (size_t)((epoch & 1u) ^ 1u) * 3 * (size_t)n; fw.check_kept = check_kept ? 1 : 0;
   fw.nbx = ffx_cdiv(size0, TILE_W); fw.nby = ffx_cdiv(size1, TILE_H);
-  static const int pow_cache = [] { const char *e = getenv("FFX_ADAM_POW_CACHE"); return e ? atoi(e) : 1; }();
-  fw.pow_cache = pow_cache;
   fw.epoch = epoch;
   // one helper per forward tile up to 1024 (5 workgroups of this kernel fit a CU by LDS: 1280 at a time; beyond that helpers take several tiles
   // each); the gradient's n workgroups in front

@@ -47,7 +47,7 @@ struct CamK {
 // the factor exp(2 alpha x0) stays inside float's range — narrower filters keep the five exponentials).  Every kernel that forms weights
 // calls rf_weights, so forward, adjoint and cache agree bit for bit; the oracle's five expf differ in the last bits (1e-6 of a weight).
 struct RfC { float alpha, bias, aL, aL2, k[4]; int rec; };
-#define FFX_MAT_PRE 12 // floats per pre-row: eta, 1/eta^2, a2, 1/a2, metallic, c_sw, c_fd, brdf, 2 roughness, lobe flags (bits), roughness^2, tint term
+#define FFX_PRE_FLOATS 12 // floats per pre-row: eta, 1/eta^2, a2, 1/a2, metallic, c_sw, c_fd, brdf, 2 roughness, lobe flags (bits), roughness^2, tint term
 #define FFX_PRE_ANISO 1u
 #define FFX_PRE_TINT 2u
 #define FFX_PRE_CLEARCOAT 4u
@@ -78,7 +78,7 @@ struct ShadeK {
   // per-row constants of the inline material rows (round 5; shade_prepare -> mat_pre_row): what every BSDF evaluation of a row re-derived from its
   // parameters — alpha^2 and its reciprocal, 1 / eta^2, the Fresnel mix's coefficients, the diffuse weight, which optional lobes are on
   int mat_pre_on;
-  float mat_pre[8 * FFX_MAT_PRE];
+  float mat_pre[8 * FFX_PRE_FLOATS];
   // tile bins of the three apexes (ffx_common.h BinsK): the packet kernels try them before the tree walks
   BinsK bins;
   // reconstruction filter (ffx_scene_desc.rfilter = gaussian; the *_filtered entry points only): g(x) = max(0, exp(rf_alpha x^2) - rf_bias)
@@ -316,11 +316,6 @@ __global__ void __launch_bounds__(TR_BLOCK)
 // compiler's IEEE expansions (which also cover denormal and overflow ranges that cannot occur here:
 // arguments are lengths and depths of visible surface points).  Ray generation and the triangle test
 // keep the IEEE forms: they decide WHICH primitive is hit.
-#ifdef FFX_EXP_SEED_LIGHT // timing experiment: the light terms on the bare hardware seeds (1 ulp), like the BSDF
-__device__ __forceinline__ float rcp_nr(float x) { return __builtin_amdgcn_rcpf(x); }
-__device__ __forceinline__ float div_nr(float a, float b) { return a * __builtin_amdgcn_rcpf(b); }
-__device__ __forceinline__ float sqrt_nr(float x) { return __builtin_amdgcn_sqrtf(x); }
-#else
 __device__ __forceinline__ float rcp_nr(float x) {
   const float r = __builtin_amdgcn_rcpf(x);
   return fmaf(r, fmaf(-x, r, 1.0f), r);
@@ -336,7 +331,6 @@ __device__ __forceinline__ float sqrt_nr(float x) {
   const float s1 = fmaf(fmaf(-s, s, x), h, s);
   return x > 0.f ? s1 : s; // sqrt(0) = 0 (rsq(0) = inf would give NaN)
 }
-#endif
 // 1 / sqrt(x) of a squared emitter distance (x > 0): the hardware seed plus one Newton step — five instructions where rcp_nr(sqrt_nr(x)) took ten
 // (two transcendental seeds, two refinements), the same value to the last bit or two
 __device__ __forceinline__ float rsqrt_nr(float x) {
@@ -542,7 +536,7 @@ __device__ __forceinline__ void material_terms(const float *__restrict__ m, cons
   B = b * FFX_PI_F;
 }
 
-// ---- the same two functions on a row whose constants the host has derived once (ShadeK.mat_pre, FFX_MAT_PRE floats per row): no squares, clamps
+// ---- the same two functions on a row whose constants the host has derived once (ShadeK.mat_pre, FFX_PRE_FLOATS floats per row): no squares, clamps
 // and reciprocals of parameters per evaluation, one flag word instead of five parameter loads and compares.  The arithmetic of the lobes is
 // material_terms', with the host's IEEE values where that one forms hardware seeds (a last-bit difference, inside the parity tolerance).
 __device__ __forceinline__ void material_geometry_p(const float *__restrict__ m, const float *__restrict__ p, v3 n, v3 wv, v3 wl, MatGeo &g) {
@@ -1395,11 +1389,10 @@ __device__ __forceinline__ void traverse_packet_oct(const BvhNode *__restrict__ 
 // boxes).  Triangles sit in clusters of up to 64 consecutive leaf slots whose boxes are tested the same way;
 // only the triangles that survive are tested exactly, with the lanes back on the rays (same apex test, same
 // acceptance rule: results are identical to the binary walk, closest hit with the primitive-id tie-break
-// is order independent).  Boxes live on a 16-bit grid (ffx_common.h: WideChild, 16 B per child: a node is one
-// coalesced 1 KB load); the grid is folded into the packet constants once per walk, so de-quantisation is
-// six integer-to-float conversions per step.  The traversal stack (reference, entry distance) is in LDS.
+// is order independent).  Boxes are float32 (ffx_common.h: WideChild, 32 B per child: a node is one
+// coalesced 2 KB load).  The traversal stack (reference, entry distance) is in LDS.
 // `elems`: the wide nodes (64 children each) followed by the triangle boxes in leaf-slot order — ONE array of
-// 16-byte elements, so that a reference (cluster << 31 | element << 6 | count - 1) addresses both kinds alike;
+// 32-byte elements, so that a reference (cluster << 31 | element << 6 | count - 1) addresses both kinds alike;
 // `tq0` = element index of leaf slot 0.
 struct WideScene { const WideChild *elems; const WideHdr *hdr; int32_t root; uint32_t tq0; };
 #define FFX_WSTACK (63 * FFX_WIDE_MAX_DEPTH + 6)
@@ -1462,11 +1455,7 @@ template <int R>
 __device__ __forceinline__ WidePk make_widepk(const WideHdr *__restrict__ hdr, v3 o, const v3 (&aid)[R], const uint32_t (&oct)[R], const wmask (&active)[R],
                                               uint32_t oct0, uint32_t mixed, float &spread) {
   float dmax_all = 0.f, dspread = 0.f; // largest |d_a| and largest (max |d_a| - min |d_a|) over the axes, in units of 1/scale
-#if FFX_WIDE_F32
   const float org[3] = {0.f, 0.f, 0.f}, step[3] = {1.f, 1.f, 1.f}; // float boxes: no grid to fold in
-#else
-  const float org[3] = {hdr->org[0], hdr->org[1], hdr->org[2]}, step[3] = {hdr->step[0], hdr->step[1], hdr->step[2]};
-#endif
   const float oo[3] = {o.x, o.y, o.z};
   float mN[3], kN[3], mF[3], kF[3], mG[3], kG[3];
   const float k22 = 2.384185791015625e-07f, k21 = 4.76837158203125e-07f, kw = 1.0000004f;
@@ -1494,7 +1483,6 @@ __device__ __forceinline__ WidePk make_widepk(const WideHdr *__restrict__ hdr, v
   if (mixed == 0u) { // (a compile-time constant at the call sites) the three axes in interleaved chains
     wave_reduce3_nn<false>(lo);
     wave_reduce3_nn<true>(hi);
-#if FFX_WIDE_F32
     // Everything from here on is wave-uniform float arithmetic, which this machine can only do on the vector ALU at the
     // 4-cycle rate of scalar-operand instructions: it is written to be short.  Signs are applied to the bit patterns
     // (scalar ALU); the two paddings of each side are one fma (2^-20 >= 2^-22 + 2^-21 + the roundings they cover:
@@ -1524,7 +1512,6 @@ __device__ __forceinline__ WidePk make_widepk(const WideHdr *__restrict__ hdr, v
     pk.mG = V3(mG[0], mG[1], mG[2]); pk.kG = V3(kG[0], kG[1], kG[2]);
     spread = fat ? 1.0f : 0.0f;
     return pk;
-#endif
   } else {
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
@@ -1636,7 +1623,6 @@ __device__ __forceinline__ bool traverse_wide_oct(const WideScene &ws, const Tri
     // divergence (lanes beyond the count re-read the last element and are masked out of the result)
     const uint32_t cnt1 = (uint32_t)cur & 63u;
     const uint32_t eoff = ((uint32_t)cur & 0x7fffffc0u) >> (6 - FFX_WIDE_ELEM_SHIFT); // element index * element size
-#if FFX_WIDE_F32
     // lane j reads element j whatever the count: the unused children of a wide node hold inverted boxes (never hit), a
     // cluster's run is followed by other triangles' boxes (masked below; the array is padded by 64 elements) — so the
     // scalar side of the step is three instructions: the lane's byte offset is ONE vector add on a loop-invariant base.
@@ -1645,14 +1631,6 @@ __device__ __forceinline__ bool traverse_wide_oct(const WideScene &ws, const Tri
     const uint4 q = *reinterpret_cast<const uint4 *>(ebase + voff + 16); // hi.y, hi.z, ref, pad  (q.z = ref)
     const float lx = qa.x, ly = qa.y, lz = qa.z, hx = qa.w, hy = __uint_as_float(q.x), hz = __uint_as_float(q.y);
 #define FFX_QREF q.z
-#else
-    const uint32_t lo16 = lane16 < (cnt1 << FFX_WIDE_ELEM_SHIFT) ? lane16 : (cnt1 << FFX_WIDE_ELEM_SHIFT);
-    const wmask lanes = ~0ull >> (63u - cnt1);
-    const uint4 q = *reinterpret_cast<const uint4 *>(ebase + eoff + lo16);
-    const float lx = (float)(q.x & 0xffffu), ly = (float)(q.x >> 16), lz = (float)(q.y & 0xffffu);
-    const float hx = (float)(q.y >> 16), hy = (float)(q.z & 0xffffu), hz = (float)(q.z >> 16);
-#define FFX_QREF q.w
-#endif
     float nx, ny, nz, fx, fy, fz, tn;
     if constexpr (OCT < 8) { // which plane is entered first is known at compile time
       nx = (OCT & 1) ? hx : lx; fx = (OCT & 1) ? lx : hx;
@@ -1668,22 +1646,13 @@ __device__ __forceinline__ bool traverse_wide_oct(const WideScene &ws, const Tri
       tn = vmax3_sat(t1, t2, t2);
     }
     const float tf = vmin2_s(vmin3(fmaf(fx, pk.mF.x, -pk.kF.x), fmaf(fy, pk.mF.y, -pk.kF.y), fmaf(fz, pk.mF.z, -pk.kF.z)), hb);
-#if FFX_WIDE_F32
     wmask hit = m_le(tn, tf);
-#else
-    wmask hit = m_le(tn, tf) & lanes;
-#endif
     FFX_TSTOP(tw, ANY ? 8 : 0);
     if (cur < 0) {
-#if FFX_WIDE_F32
       hit &= ~0ull >> (63u - cnt1); // only the cluster's own triangles
-#endif
       // ---- cluster: the surviving triangles are tested exactly, lanes back on the rays
       FFX_STAT(ANY ? 12 : 8);
       const uint32_t slot0 = (eoff >> FFX_WIDE_ELEM_SHIFT) - ws.tq0;
-#ifdef FFX_EXP_ANY_NOTRIS // timing experiment: any-hit walks without the exact triangle tests
-      if (ANY) hit = 0ull;
-#endif
       while (hit != 0ull) {
         const uint32_t j = (uint32_t)wff1(hit);
         asm("s_bitset0_b64 %0, %1" : "+s"(hit) : "s"(j)); // hit &= hit - 1 in one scalar instruction instead of three
@@ -1759,9 +1728,7 @@ __device__ __forceinline__ bool traverse_wide_oct(const WideScene &ws, const Tri
       const uint32_t key = (__float_as_uint(tn) & ~63u) | (threadIdx.x & 63u);
       uint32_t near_lane = (uint32_t)wff1(hit);
       if (wpop(hit) != 1) { // several children: nearest first, the others onto the stack
-#ifndef FFX_EXP_LANE_ORDER // (experiment: descend in lane order instead of nearest-first)
         near_lane = wave_reduce_nn<false>(msel(hit, key, 0xffffffffu)) & 63u;
-#endif
         const wmask others = hit & ~(1ull << near_lane);
         if (__builtin_amdgcn_inverse_ballot_w64(others)) stack[sp + (int)mbcnt64(others)] = make_uint2(FFX_QREF, key);
         sp += wpop(others);
@@ -1898,11 +1865,6 @@ template <bool ANY, int R, bool WIDE>
 __device__ __forceinline__ void traverse_packet_any(const BvhNode *__restrict__ nodes, const TriApex *__restrict__ arecs, const WideScene &ws, uint2 *__restrict__ stack,
                                                     const v3 (&o)[R], const v3 (&d)[R], const float (&tmin)[R], const float (&tmax)[R], const bool (&active)[R],
                                                     Hit (&h)[R], bool (&found)[R]) {
-#ifdef FFX_EXP_NOWALK // timing experiment: every ray "hits" leaf slot 0 half-way along its range — what everything but the walks costs
-#pragma unroll
-  for (int r = 0; r < R; ++r) { h[r].t = ANY ? -INFINITY : 0.5f * (tmin[r] + tmax[r]); h[r].prim = ANY ? -1 : 0; h[r].shape = -1; h[r].slot = ANY ? -1 : 0; found[r] = false; }
-  return;
-#endif
   if constexpr (WIDE) traverse_wide<ANY, R>(ws, nodes, arecs, o, d, tmin, tmax, active, h, found, stack);
   else if constexpr (R == 1 && octant_loops()) traverse_packet1<ANY>(nodes, arecs, o, d, tmin, tmax, active, h, found);
   else traverse_packet<ANY, R>(nodes, arecs, o, d, tmin, tmax, active, h, found);
@@ -2103,9 +2065,6 @@ __device__ __forceinline__ bool bins_shadow(const BinsK &bk, const int a, const 
     const float v = fmaf(Nc.x, sdir.x, fmaf(Nc.y, sdir.y, Nc.z * sdir.z));
     if ((active & ~m_le(v, 1.0f)) == 0ull) { occluded = 0ull; FFX_STAT(a == 1 ? 37 : 47); return true; }
   }
-#ifdef FFX_EXP_NO_SPOT_WALK // timing experiment: what the any-hit stage of the packets the envelope does NOT settle costs (they count as unoccluded)
-  if (a == 2) { occluded = 0ull; return true; }
-#endif
   uint32_t mnx = msel(active, __float_as_uint(fx), 0x7f800000u), mny = msel(active, __float_as_uint(fy), 0x7f800000u);
   uint32_t mxx = msel(active, __float_as_uint(fx), 0u), mxy = msel(active, __float_as_uint(fy), 0u);
   wave_reduce_minmax4(mnx, mny, mxx, mxy);
@@ -2191,9 +2150,6 @@ __device__ __forceinline__ void shade_sample_pk(const BvhNode *__restrict__ node
   FFX_TSTOP(tp, 22);
   const ShadeK &c = kernarg_shade(); // phase: light terms at the hit point
   ShadePre pre[R];
-  int cbits[R]; // the hit triangle's flag word (per-slot normal, word 3): the emitters' "clear" bits (ffx_common.h FFX_GN_CLEAR_BIT)
-#pragma unroll
-  for (int r = 0; r < R; ++r) cbits[r] = 0;
   bool any_p = false, any_s = false;
 #pragma unroll
   for (int r = 0; r < R; ++r) {
@@ -2212,9 +2168,6 @@ __device__ __forceinline__ void shade_sample_pk(const BvhNode *__restrict__ node
     q.ng = V3(0.f, 0.f, 1.f);
     q.Po = V3(0.f, 0.f, 0.f);
     q.ok = st[r].hit != 0;
-#ifdef FFX_EXPERIMENT_PRIMARY_ONLY // timing experiment: ray generation + primary walk only
-    q.ok = false;
-#endif
     if (q.ok) {
       const float4 *r4 = reinterpret_cast<const float4 *>(recs + h[r].slot);
       // the unit geometric normal comes from the update (ffx_bvh_info.off_gn: IEEE, the oracle's bits) — re-deriving it from the
@@ -2223,7 +2176,6 @@ __device__ __forceinline__ void shade_sample_pk(const BvhNode *__restrict__ node
       const float4 gq = gn[h[r].slot];
       const int gbits = __float_as_int(gq.w); // 0: degenerate triangle; else (shape + 1) | smooth << 30
       st[r].shape = (gbits & FFX_GN_SHAPE_MASK) - 1;
-      cbits[r] = gbits;
       q.P = V3(fmaf(h[r].t, d[r].x, o[r].x), fmaf(h[r].t, d[r].y, o[r].y), fmaf(h[r].t, d[r].z, o[r].z));
       v3 ng = V3(gq.x, gq.y, gq.z);
       q.ok = (gbits & FFX_GN_SHAPE_MASK) != 0;
@@ -2341,16 +2293,7 @@ __device__ __forceinline__ void shade_sample_pk(const BvhNode *__restrict__ node
 #pragma unroll
   for (int r = 0; r < R; ++r) occ_p[r] = occ_s[r] = false;
   FFX_TSTOP(tp, 18);
-  // (round 5) a packet all of whose samples that need an emitter lie on triangles NOTHING can shadow from it (k_bin_clear's proof, the bit in
-  // the per-slot normal's flag word; valid while that emitter's lists are: bins_ready) skips that emitter's any-hit stage altogether
-  bool walk_p = c.shadows && wballot(any_p) != 0ull, walk_s = c.shadows && wballot(any_s) != 0ull;
-  if constexpr (R == 1) {
-    const BinsK &bkc = kernarg_shade().bins;
-    if (bkc.clear_on) {
-      if ((bkc.clear_on & 1) && walk_p && wballot(pre[0].need_p && !((uint32_t)cbits[0] & FFX_GN_CLEAR_BIT(1))) == 0ull && bins_ready(bkc, 1)) { walk_p = false; FFX_STAT(38); }
-      if ((bkc.clear_on & 2) && walk_s && wballot(pre[0].need_s && !((uint32_t)cbits[0] & FFX_GN_CLEAR_BIT(2))) == 0ull && bins_ready(bkc, 2)) { walk_s = false; FFX_STAT(39); }
-    }
-  }
+  const bool walk_p = c.shadows && wballot(any_p) != 0ull, walk_s = c.shadows && wballot(any_s) != 0ull;
   if (walk_p) {
     const v3 ppos = V3(c.p_pos[0], c.p_pos[1], c.p_pos[2]);
     v3 so[R], sdir[R];
@@ -2386,11 +2329,7 @@ __device__ __forceinline__ void shade_sample_pk(const BvhNode *__restrict__ node
 #endif
   }
   FFX_TSTOP(tp, 19);
-#ifdef FFX_EXP_NO_SPOT_SHADOW // timing experiment: what the spot's any-hit stage costs (every spot sample counts as unoccluded)
-  if (false) {
-#else
   if (walk_s) {
-#endif
     const v3 spos = V3(c.s_pos[0], c.s_pos[1], c.s_pos[2]);
     v3 so[R], sdir[R];
     float s0[R], s1[R];
@@ -2436,8 +2375,8 @@ __device__ __forceinline__ void shade_sample_pk(const BvhNode *__restrict__ node
       if (lit_p || lit_s) {
         const float *mrow = mat_table(c2) + (size_t)FFX_MAT_STRIDE * st[r].shape;
         const bool mat_on = mrow[FFX_MAT_MODEL] != 0.f;
-        // (wave-uniform: the rows travel with the call and the host derived their constants — FFX_MAT_PRE=0 in the environment keeps the on-the-fly form)
-        const float *prow = c2.mat_pre_on ? c2.mat_pre + FFX_MAT_PRE * st[r].shape : nullptr;
+        // (wave-uniform: the rows travel with the call and the host derived their constants — other tables take the on-the-fly form)
+        const float *prow = c2.mat_pre_on ? c2.mat_pre + FFX_PRE_FLOATS * st[r].shape : nullptr;
         const v3 wv = V3(-d[r].x, -d[r].y, -d[r].z);
         if constexpr (TEX) { // base colour of this sample: the row's, or its texture at the hit (only lit samples need one)
           st[r].base[0] = mrow[0]; st[r].base[1] = mrow[1]; st[r].base[2] = mrow[2];
@@ -2696,8 +2635,7 @@ static void rf_constants(float stddev, RfC &c) { // [EXT Mitsuba src/rfilters/ga
   c.aL = c.alpha * 1.4426950408889634f;
   c.aL2 = 2.0f * c.aL;
   for (int n = 0; n < 4; ++n) c.k[n] = (float)exp((double)c.alpha * (2 * n + 1));
-  const char *e = getenv("FFX_RF_RECURRENCE");
-  c.rec = (c.alpha >= -8.0f && !(e && strcmp(e, "0") == 0)) ? 1 : 0;
+  c.rec = c.alpha >= -8.0f ? 1 : 0;
 }
 // acc[ch] of lane l += sum over the samples 32 (l / 32) .. + 31 of this pass of  gx[a] gy[b] L[ch]  for window entry n = 5 b + a = l % 32 (< 25)
 __device__ __forceinline__ void rf_fold(float *__restrict__ s_rf, int lane, const float (&gx)[5], const float (&gy)[5], float l0, float l1, float l2, float l3,
@@ -4066,12 +4004,11 @@ static int shade_prepare(const ffx_scene_desc *sd, ShadeK &c) {
     if (sd->n_mat_h > FFX_MAX_MAT_H || sd->n_mat_h != sd->n_shapes * c.mat_stride) return 0;
     c.mat_inline = 1;
     for (int i = 0; i < sd->n_mat_h; ++i) c.mat_h[i] = sd->mat_h[i];
-    const char *pe = getenv("FFX_MAT_PRE");
-    if (c.mat_stride == FFX_MAT_STRIDE && sd->n_shapes <= 8 && !(pe && strcmp(pe, "0") == 0)) { // per-row constants of the principled rows (ShadeK.mat_pre)
+    if (c.mat_stride == FFX_MAT_STRIDE && sd->n_shapes <= 8) { // per-row constants of the principled rows (ShadeK.mat_pre)
       c.mat_pre_on = 1;
       for (int k = 0; k < sd->n_shapes; ++k) {
         const float *m = sd->mat_h + k * FFX_MAT_STRIDE;
-        float *p = c.mat_pre + k * FFX_MAT_PRE;
+        float *p = c.mat_pre + k * FFX_PRE_FLOATS;
         const float eta = m[FFX_MAT_ETA], r2 = m[FFX_MAT_ROUGHNESS] * m[FFX_MAT_ROUGHNESS], a = r2 > 0.001f ? r2 : 0.001f, a2 = a * a;
         const float metallic = m[FFX_MAT_METALLIC], m1 = 1.0f - metallic, tint = m[FFX_MAT_SPEC_TINT];
         const float r0 = (eta - 1.0f) / (eta + 1.0f);
@@ -4172,12 +4109,6 @@ static int use_packet() {
   return (e && strcmp(e, "lane") == 0) ? 0 : 1;
 }
 
-// independent waves per workgroup of the packet kernels: FFX_PACKET_WAVES = 1 (default), 2 or 4.
-// The waves of a workgroup never cooperate, so the smallest workgroup gives the dispatcher the finest
-// grain (measured 1 / 2 / 4 waves: 0.882 / 0.891 / 0.951 ms per step on the vocal fold, 16.2 / 16.5 /
-// 17.4 ms on the colon).
-static int packet_waves() { return 1; }
-
 // FFX_WIDE=0 selects the binary packet walks (A/B baseline); default: the 64-wide walk
 static int use_wide(const ffx_bvh_info *info) {
   const char *e = getenv("FFX_WIDE");
@@ -4227,16 +4158,10 @@ static int pixels_per_wave(bool with_cache, long pixels = 0) {
   return (w == 1 || w == 2 || w == 4) ? w : dflt;
 }
 
-// experiment knob: dynamic LDS bytes per workgroup of the packet kernels (unused by the kernel; it only
-// lowers occupancy so that latency- and throughput-bound behaviour can be told apart)
 // renders below 33 samples per pixel take k_render_fwd_blk (several pixels per wave); FFX_RENDER_BLOCKS=0: a pixel per wave whatever the count
 static bool lowspp_blocks() {
   const char *e = getenv("FFX_RENDER_BLOCKS");
   return !(e && strcmp(e, "0") == 0);
-}
-static size_t dummy_lds() {
-  const char *e = getenv("FFX_DUMMY_LDS");
-  return e ? (size_t)atol(e) : 0;
 }
 
 // ---- tile bins: the three grids of a scene description (ffx_common.h BinGrid).  A pure function of sd (and the environment), so that
@@ -4309,21 +4234,6 @@ static void bins_grids(const ffx_scene_desc *sd, BinGrid (&g)[FFX_N_APEX], float
     }
   }
 }
-// FFX_SHADOW_CLEAR=0: the render kernels walk every shadow packet (A/B and the tests' reference for the skip; the pre-pass then leaves the
-// bits cleared).  A pure function of (sd, info, environment), like the grids: ffx_apex_prepare and the renders behind it agree.
-// -> a mask over the emitters: bit 0 projector, bit 1 spot.  DEFAULT 0 (off) — a measured negative result, kept as an opt-in because it is
-// exact and tested: without the spot's any-hit stage K8 runs 0.400 -> 0.302 ms (-DFFX_EXP_NO_SPOT_SHADOW), but the proof only succeeds for
-// 22 - 36 % of the vocal fold's triangles (a smooth surface is half saddle: there a triangle's vertex neighbours straddle its plane and it
-// theirs — neither H1 nor H2 — and the margin between the lift of a shadow ray's end point, 8.9e-5 (1 + |P|), and the ignored tail of the
-// ray, 8.9e-4 |d|, is too small to settle them by distance), so ~20 % of the pixels skip the stage: K8 0.400 -> 0.381 ms (tools/k8ab.py),
-// while the pairwise proof adds ~10 M instructions to the pre-pass on the side stream, 280 us elapsed beside a render (rocprofv3): the loop
-// fell from 2 400 to 1 810 renders/s (spot only; 1 580 with the projector's 68-entry tiles too).  FFX_SHADOW_CLEAR=2 / 3 switches it on.
-static int clear_enabled(const ffx_scene_desc *sd, const ffx_bvh_info *info) {
-  const char *e = getenv("FFX_SHADOW_CLEAR");
-  if (!(sd && (sd->shadows & FFX_SHADOWS_ON) && info->off_gn != 0 && bins_enabled())) return 0;
-  const int m = e ? atoi(e) : 0;
-  return (m < 0 || m > 3) ? 0 : m;
-}
 // FFX_ENVELOPE=0: no envelopes (every shadow packet runs its any-hit stage: the A/B baseline and the tests' reference).  -> a mask over the
 // emitters (bit 0 projector, bit 1 spot).  A pure function of (sd, info, environment), like the grids: the pre-pass and the renders behind it agree.
 static int env_enabled(const ffx_scene_desc *sd, const ffx_bvh_info *info) {
@@ -4368,7 +4278,6 @@ static void bins_k(const void *bvh, const ffx_bvh_info *info, const ffx_scene_de
   if (!info->off_bins || !info->bins_stride) return;
   bins_grids(sd, bk.g, bk.cam_inv_ts_x, bk.cam_inv_ts_y);
   for (int a = 0; a < FFX_N_APEX; ++a) bk.base[a] = (const char *)bvh + info->off_bins + (uint64_t)a * info->bins_stride;
-  bk.clear_on = clear_enabled(sd, info);
   EnvBuild eb;
   bk.env_on = env_build(bk.g, env_enabled(sd, info), info->n_tris, eb);
   bk.env_off = eb.env_off;
@@ -4430,7 +4339,7 @@ static int launch_apex(const void *bvh, const ffx_bvh_info *info, const float *c
       const int env_mask = env_build(bb.g, env_enabled(sd, info), info->n_tris, eb);
       bb.env_mask = env_mask;
       ffx_bins_launch(recs, info->n_tris, bb, out, ak.o, ak.on, (uint32_t)stride, (uint32_t *)cache, cap_stray, s, sd && sd->mat_stride != FFX_MAT_STRIDE,
-                      info->off_gn ? (uint32_t *)((char *)bvh + info->off_gn) : nullptr, clear_enabled(sd, info), env_mask ? &eb : nullptr);
+                      env_mask ? &eb : nullptr);
     }
   } else if (cache)
     hipLaunchKernelGGL(k_cache_reset, dim3(1), dim3(1), 0, s, (uint32_t *)cache, cap_stray);
@@ -4521,19 +4430,15 @@ int ffx_trace_primary(const void *bvh, const ffx_bvh_info *info, const ffx_camer
     if (spp < 64 && 64 % spp == 0)
       while ((spp << (ppw_log2 + 1)) <= 64) ++ppw_log2;
     {
-      // ... but never more than 16 pixels (1 spp) / 8 pixels per wave: a smaller block leaves lanes idle, yet it makes
+      // ... but never more than 8 pixels per wave: a smaller block leaves lanes idle, yet it makes
       // more and thinner packets — fewer exact tests per walk (24 per walk with 8x8-pixel packets) and enough waves to
       // hide the walk's latency (4096 waves of 64 pixels do not fill the GPU).  Measured at 512^2 (tools/k7time.py):
       // 1 / 2 / 4 spp 0.118 / 0.105 / 0.095 ms with full waves, 0.071 / 0.056 / 0.057 ms capped; >= 8 spp unchanged.
-      // FFX_K7_PPW_LOG2 overrides the cap (experiment knob).
-      static const int env_cap = getenv("FFX_K7_PPW_LOG2") ? atoi(getenv("FFX_K7_PPW_LOG2")) : -1;
       // (tools/lowspp.py, 512^2: 4 / 8 / 16 / 32 / 64 pixels per wave at 1 spp = 0.174 / 0.160 / 0.169 / 0.192 / 0.239 ms; at 4 spp 0.193 / 0.175 / 0.185)
-      const int cap = env_cap >= 0 ? env_cap : 3;
-      if (ppw_log2 > cap) ppw_log2 = cap;
+      if (ppw_log2 > 3) ppw_log2 = 3;
     }
     const int bw_log2 = (ppw_log2 + 1) / 2, bh_log2 = ppw_log2 / 2;
     const int blocks_x = ffx_cdiv(k.W, 1 << bw_log2), n_blocks = blocks_x * ffx_cdiv(k.H, 1 << bh_log2);
-    const int wpb = packet_waves();
     const TriApex *arecs;
     uint32_t astride;
     // the pre-pass of a camera-only scene: apex records and (round 4) the camera's tile bins; with FFX_RENDER_APEX_READY in `jitter` the
@@ -4547,10 +4452,10 @@ int ffx_trace_primary(const void *bvh, const ffx_bvh_info *info, const ffx_camer
     const int jit = jitter & 1;
     const WideScene ws = wide_scene(bvh, info);
     if (use_wide(info))
-      hipLaunchKernelGGL(k_trace_primary_pk<true>, dim3(ffx_cdiv(n_blocks, wpb)), dim3(64 * wpb), 0, (hipStream_t)s, k, nodes, recs, arecs, ws, spp, jit,
+      hipLaunchKernelGGL(k_trace_primary_pk<true>, dim3(n_blocks), dim3(64), 0, (hipStream_t)s, k, nodes, recs, arecs, ws, spp, jit,
                          seed_key_of(seed), bw_log2, bh_log2, blocks_x, n_blocks, t_out, shape_out, prim_out, bk);
     else
-      hipLaunchKernelGGL(k_trace_primary_pk<false>, dim3(ffx_cdiv(n_blocks, wpb)), dim3(64 * wpb), 0, (hipStream_t)s, k, nodes, recs, arecs, ws, spp, jit,
+      hipLaunchKernelGGL(k_trace_primary_pk<false>, dim3(n_blocks), dim3(64), 0, (hipStream_t)s, k, nodes, recs, arecs, ws, spp, jit,
                          seed_key_of(seed), bw_log2, bh_log2, blocks_x, n_blocks, t_out, shape_out, prim_out, bk);
     FFX_CHECK_LAUNCH("trace_primary");
     return FFX_OK;
@@ -4606,9 +4511,8 @@ static int render_fwd_impl(const void *bvh, const ffx_bvh_info *info, const ffx_
     int ptx = ffx_cdiv(c.cam.W, 2), pty = ffx_cdiv(c.cam.H, 2);
     int pn = (ffx_cdiv(ptx, 1 << tb) * ffx_cdiv(pty, 1 << tb)) << (2 * tb); // whole blocks; tiles outside the image are skipped
     ptx |= tb << 24;
-    const int wpb = packet_waves();
     const int ppw = pixels_per_wave(cache != nullptr || adj_gtex != nullptr || rf_cache != nullptr, (long)c.cam.W * c.cam.H);
-    int pgrid = ((ffx_cdiv((long)pn * (4 / ppw), wpb) + 7) / 8) * 8; // multiple of 8 so the XCD remap is a bijection onto [0, grid)
+    int pgrid = ((pn * (4 / ppw) + 7) / 8) * 8; // multiple of 8 so the XCD remap is a bijection onto [0, grid)
     const TriApex *arecs;
     uint32_t astride;
     // (capacity of the cache's arena: single-sample records of the box film's footprint cache / 64-sample blocks of the filtered film's record cache)
@@ -4625,7 +4529,7 @@ static int render_fwd_impl(const void *bvh, const ffx_bvh_info *info, const ffx_
     const uint32_t foot_off = (uint32_t)(cache_off_foot((size_t)c.cam.W * c.cam.H) >> 7), arena_off = (uint32_t)(cache_off_arena((size_t)c.cam.W * c.cam.H) >> 7);
     const uint32_t foot_b_off = (uint32_t)(cache_off_foot_b((size_t)c.cam.W * c.cam.H, cache_stray_capacity(c.cam.W, c.cam.H, spp)) >> 7);
 #define FFX_LAUNCH_FWD_(WIDE_, MAT_, ADJ_)                                                                                                               \
-  hipLaunchKernelGGL((k_render_fwd_pk<1, WIDE_, MAT_, ADJ_>), dim3(pgrid), dim3(64 * wpb), dummy_lds(), (hipStream_t)s, c, nodes, recs, arecs, astride, ws, \
+  hipLaunchKernelGGL((k_render_fwd_pk<1, WIDE_, MAT_, ADJ_>), dim3(pgrid), dim3(64), 0, (hipStream_t)s, c, nodes, recs, arecs, astride, ws, \
                      shape_albedo, tex, spp, seed_key_of(seed), ptx, pn, xcd_mode((long)c.cam.W * c.cam.H), img_fp16, img, (char *)cache, ppw, 1.0f / (float)spp, foot_off,     \
                      arena_off, foot_b_off, nrec, gn, cap_stray, adj_gimg, adj_gtex, adj_dot)
 #define FFX_LAUNCH_FWD(WIDE_, MAT_) do { if (adj_gtex) FFX_LAUNCH_FWD_(WIDE_, MAT_, true); else FFX_LAUNCH_FWD_(WIDE_, MAT_, false); } while (0)
@@ -4643,7 +4547,7 @@ static int render_fwd_impl(const void *bvh, const ffx_bvh_info *info, const ffx_
                          c.cam.H, 0, (void *)nullptr, adj_gimg, G);
       FFX_CHECK_LAUNCH("render_fwd_adjoint_filtered/gather G");
 #define FFX_LAUNCH_RFA(MAT_)                                                                                                                             \
-  hipLaunchKernelGGL((k_render_fwd_pk<1, true, MAT_, true, true>), dim3(pgrid), dim3(64 * wpb), dummy_lds(), (hipStream_t)s, c, nodes, recs, arecs, astride, ws, \
+  hipLaunchKernelGGL((k_render_fwd_pk<1, true, MAT_, true, true>), dim3(pgrid), dim3(64), 0, (hipStream_t)s, c, nodes, recs, arecs, astride, ws, \
                      shape_albedo, tex, spp, seed_key_of(seed), ptx, pn, xcd_mode((long)c.cam.W * c.cam.H), img_fp16, img, (char *)rf_scratch, ppw,          \
                      1.0f / (float)spp, foot_off, arena_off, foot_b_off, nrec, gn, cap_stray, (const float *)G, adj_gtex, (float *)nullptr)
       if (matm == 1) FFX_LAUNCH_RFA(1); else FFX_LAUNCH_RFA(0);
@@ -4661,7 +4565,7 @@ static int render_fwd_impl(const void *bvh, const ffx_bvh_info *info, const ffx_
       const size_t n_pix = (size_t)c.cam.W * c.cam.H;
       const uint32_t recs_off = (uint32_t)(rfc_off_recs(n_pix) >> 7), facb_off = (uint32_t)(rfc_off_facb(n_pix, (size_t)spp, rfc_all(sd)) >> 7);
 #define FFX_LAUNCH_RFC(MAT_)                                                                                                                              \
-  hipLaunchKernelGGL((k_render_fwd_pk<1, true, MAT_, false, true, true>), dim3(pgrid), dim3(64 * wpb), dummy_lds(), (hipStream_t)s, c, nodes, recs, arecs, astride, ws, \
+  hipLaunchKernelGGL((k_render_fwd_pk<1, true, MAT_, false, true, true>), dim3(pgrid), dim3(64), 0, (hipStream_t)s, c, nodes, recs, arecs, astride, ws, \
                      shape_albedo, tex, spp, seed_key_of(seed), ptx, pn, xcd_mode((long)c.cam.W * c.cam.H), img_fp16, img, (char *)rf_scratch, ppw,       \
                      1.0f / (float)spp, recs_off, arena_off, facb_off, nrec, gn, cap_stray, (const float *)nullptr, (float *)rf_cache, (float *)nullptr)
       if (matm == 1) FFX_LAUNCH_RFC(1); else FFX_LAUNCH_RFC(0);
@@ -4680,7 +4584,7 @@ static int render_fwd_impl(const void *bvh, const ffx_bvh_info *info, const ffx_
       const int bw_log2 = (ppw_log2 + 1) / 2, bh_log2 = ppw_log2 / 2;
       const int blocks_x = ffx_cdiv(c.cam.W, 1 << bw_log2), n_blocks = 64 * ffx_cdiv(blocks_x, 8) * ffx_cdiv(ffx_cdiv(c.cam.H, 1 << bh_log2), 8); // (whole 8 x 8 patches)
 #define FFX_LAUNCH_BLKF(MAT_)                                                                                                                            \
-  hipLaunchKernelGGL((k_render_fwd_blk<true, MAT_, true>), dim3(ffx_cdiv(n_blocks, wpb)), dim3(64 * wpb), 0, (hipStream_t)s, c, nodes, recs, arecs, astride, ws, \
+  hipLaunchKernelGGL((k_render_fwd_blk<true, MAT_, true>), dim3(n_blocks), dim3(64), 0, (hipStream_t)s, c, nodes, recs, arecs, astride, ws, \
                      shape_albedo, tex, spp, seed_key_of(seed), bw_log2, bh_log2, blocks_x, n_blocks, img_fp16 & 1, rf_scratch, 1.0f / (float)spp, nrec, gn)
       if (matm == 2) FFX_LAUNCH_BLKF(2); else if (matm == 1) FFX_LAUNCH_BLKF(1); else FFX_LAUNCH_BLKF(0);
 #undef FFX_LAUNCH_BLKF
@@ -4692,7 +4596,7 @@ static int render_fwd_impl(const void *bvh, const ffx_bvh_info *info, const ffx_
     }
     if (rf_scratch) { // the filtered render: the kernel leaves every pixel's 25 x 4 outgoing sums in the scratch area, the gather forms the image
 #define FFX_LAUNCH_RF(MAT_)                                                                                                                               \
-  hipLaunchKernelGGL((k_render_fwd_pk<1, true, MAT_, false, true>), dim3(pgrid), dim3(64 * wpb), dummy_lds(), (hipStream_t)s, c, nodes, recs, arecs, astride, ws, \
+  hipLaunchKernelGGL((k_render_fwd_pk<1, true, MAT_, false, true>), dim3(pgrid), dim3(64), 0, (hipStream_t)s, c, nodes, recs, arecs, astride, ws, \
                      shape_albedo, tex, spp, seed_key_of(seed), ptx, pn, xcd_mode((long)c.cam.W * c.cam.H), img_fp16 & 1, img, (char *)rf_scratch, ppw,       \
                      1.0f / (float)spp, foot_off, arena_off, foot_b_off, nrec, gn, cap_stray, adj_gimg, adj_gtex, adj_dot)
       if (matm == 2) FFX_LAUNCH_RF(2); else if (matm == 1) FFX_LAUNCH_RF(1); else FFX_LAUNCH_RF(0);
@@ -4710,13 +4614,12 @@ static int render_fwd_impl(const void *bvh, const ffx_bvh_info *info, const ffx_
       while (slots < spp) slots <<= 1;
       int ppw_log2 = 0;
       while ((slots << (ppw_log2 + 1)) <= 64) ++ppw_log2;
-      static const int env_cap = getenv("FFX_RENDER_BLK_LOG2") ? atoi(getenv("FFX_RENDER_BLK_LOG2")) : -1; // (experiment knob: pixels per wave, log2)
-      const int cap = env_cap >= 0 ? env_cap : (spp == 1 ? 4 : 3);
+      const int cap = spp == 1 ? 4 : 3;
       if (ppw_log2 > cap) ppw_log2 = cap;
       const int bw_log2 = (ppw_log2 + 1) / 2, bh_log2 = ppw_log2 / 2;
       const int blocks_x = ffx_cdiv(c.cam.W, 1 << bw_log2), n_blocks = 64 * ffx_cdiv(blocks_x, 8) * ffx_cdiv(ffx_cdiv(c.cam.H, 1 << bh_log2), 8); // (whole 8 x 8 patches)
 #define FFX_LAUNCH_BLK(WIDE_, MAT_)                                                                                                                     \
-  hipLaunchKernelGGL((k_render_fwd_blk<WIDE_, MAT_>), dim3(ffx_cdiv(n_blocks, wpb)), dim3(64 * wpb), 0, (hipStream_t)s, c, nodes, recs, arecs, astride, ws, \
+  hipLaunchKernelGGL((k_render_fwd_blk<WIDE_, MAT_>), dim3(n_blocks), dim3(64), 0, (hipStream_t)s, c, nodes, recs, arecs, astride, ws, \
                      shape_albedo, tex, spp, seed_key_of(seed), bw_log2, bh_log2, blocks_x, n_blocks, img_fp16, img, 1.0f / (float)spp, nrec, gn)
       if (use_wide(info)) { if (matm == 2) FFX_LAUNCH_BLK(true, 2); else if (matm == 1) FFX_LAUNCH_BLK(true, 1); else FFX_LAUNCH_BLK(true, 0); }
       else { if (matm == 2) FFX_LAUNCH_BLK(false, 2); else if (matm == 1) FFX_LAUNCH_BLK(false, 1); else FFX_LAUNCH_BLK(false, 0); }
@@ -4898,8 +4801,7 @@ static int render_bwd_impl(const void *bvh, const ffx_bvh_info *info, const ffx_
     int ptx = ffx_cdiv(c.cam.W, 2), pty = ffx_cdiv(c.cam.H, 2);
     int pn = (ffx_cdiv(ptx, 1 << tb) * ffx_cdiv(pty, 1 << tb)) << (2 * tb);
     ptx |= tb << 24;
-    const int wpb = packet_waves();
-    int pgrid = ((ffx_cdiv(pn, wpb) + 7) / 8) * 8;
+    int pgrid = ((pn + 7) / 8) * 8;
     const TriApex *arecs;
     uint32_t astride;
     if (!launch_apex(bvh, info, sd->cam.to_world, sd, &arecs, &astride, (hipStream_t)s, nullptr, 0, flags & FFX_RENDER_APEX_READY)) return FFX_ERR_ARG;
@@ -4923,7 +4825,7 @@ static int render_bwd_impl(const void *bvh, const ffx_bvh_info *info, const ffx_
     }
     const bool wide = use_wide(info) != 0;
 #define FFX_LAUNCH_BWD(WIDE_, MAT_, RF_)                                                                                                                  \
-  hipLaunchKernelGGL((k_render_bwd_pk<1, WIDE_, MAT_, RF_>), dim3(pgrid), dim3(64 * wpb), 0, (hipStream_t)s, c, nodes, recs, arecs, astride, ws, shape_albedo, \
+  hipLaunchKernelGGL((k_render_bwd_pk<1, WIDE_, MAT_, RF_>), dim3(pgrid), dim3(64), 0, (hipStream_t)s, c, nodes, recs, arecs, astride, ws, shape_albedo, \
                      spp, seed_key_of(seed), ptx, pn, xcd_mode((long)c.cam.W * c.cam.H), gsrc, gtex, nrec, gn, det)
     auto launch = [&]() {
       if (rf_scratch) { if (matm == 2) FFX_LAUNCH_BWD(true, 2, true); else if (matm == 1) FFX_LAUNCH_BWD(true, 1, true); else FFX_LAUNCH_BWD(true, 0, true); }

@@ -521,7 +521,6 @@ class Scene:
         # up to 8 material rows (42 albedos) travel inside the scene description as kernel arguments: a randomisation of the
         # material then costs no host-to-device copy at all (it was the one copyBuffer launch of every step)
         self._mats_in_sd = alb.size <= 128 and os.environ.get("FFX_HOST_MATERIALS", "1") != "0"
-        self._apex_ahead = os.environ.get("FFX_APEX_AHEAD", "1") != "0"  # apex records written with the re-fit instead of in front of the render
         # Two render streams, used in turn (FFX_RENDER_STREAMS=1: the caller's stream, as before): consecutive renders are independent of
         # each other — each reads its own blob copy, the texture and kernel arguments — and back to back on ONE stream they leave the tail
         # of every launch (the last of 262 144 one-wave workgroups draining) and the dependency gap behind it unused: tools/overlapprobe.py,
@@ -792,7 +791,7 @@ class Scene:
             # the update has been applied above): their apex records are written behind the re-fit, on its side stream, and the
             # render launches without a pre-pass (ops.DeviceGeometry.update; the description is built here instead of in render())
             self.update_paths["python"] += 1
-            self.geom.update(self._xforms, self._offs, apex_sd=self.scene_desc(tex_channels=ch) if self._apex_ahead else None)
+            self.geom.update(self._xforms, self._offs, apex_sd=self.scene_desc(tex_channels=ch))
 
     # ------------------------------------------------------------------ the native params.update() (include/ffx.h ffx_scene_step_h)
     # A scene sample drawn by the native randomiser (ffx_scene_randomize_h) reaches the device in ONE call: its key writes — poses into
@@ -804,7 +803,7 @@ class Scene:
         """poses: [(entity row, parameter key)], values: [(draw row, values per draw, repeat, parameter key)], meshes: [(entity row, mesh
         name)] — the writes of Scene._apply_native.  -> the compiled plan, or None (not compilable, or not yet: a key never pushed before)"""
         g = self.geom
-        if not (self._apex_ahead and g._async and g.n_shapes <= 32 and self.device.type == "cuda") or ops._lane_kernels():
+        if not (g._async and g.n_shapes <= 32 and self.device.type == "cuda") or ops._lane_kernels():
             return None
         d, stride = self.data, self._mat_stride
         sd_pose = {d.camera.name + ".to_world": _SD_CAM_TW}

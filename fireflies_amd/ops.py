@@ -187,13 +187,13 @@ _pattern_epochs = {}
 _SHARED_STREAMS = {}
 
 
-def shared_streams(device, role, n, priority=0):
+def shared_streams(device, role, n):
     """the process's n streams of `role` on `device` (created on first use): every scene / geometry of the device takes the same ones"""
     dev = torch.device(device)
-    key = (dev.type, dev.index if dev.index is not None else torch.cuda.current_device(), role, int(priority))
+    key = (dev.type, dev.index if dev.index is not None else torch.cuda.current_device(), role)
     got = _SHARED_STREAMS.setdefault(key, [])
     while len(got) < n:
-        got.append(torch.cuda.Stream(dev, priority=int(priority)))
+        got.append(torch.cuda.Stream(dev))
     return got[:n]
 
 
@@ -457,7 +457,7 @@ class _EventPair:
 # the pre-pass knobs are read per call (a test flips them mid-process) — straight from os.environ's own dict where it has one (posix: bytes -> bytes;
 # os.environ.get's encode + KeyError path was 0.6 us a look-up, fourteen of them per loop step: a tenth of the host's time at 4 spp)
 _ENV_DATA = getattr(os.environ, "_data", None)
-_ENV_NAMES = ("FFX_BINS", "FFX_BIN_TILE", "FFX_BIN_TILE_PROJ", "FFX_BIN_SPOT_N", "FFX_BIN_CAP", "FFX_SHADOW_CLEAR", "FFX_ENVELOPE")
+_ENV_NAMES = ("FFX_BINS", "FFX_BIN_TILE", "FFX_BIN_TILE_PROJ", "FFX_BIN_SPOT_N", "FFX_BIN_CAP", "FFX_ENVELOPE")
 if isinstance(_ENV_DATA, dict) and os.name == "posix":
     _ENV_KEYS = tuple(n.encode() for n in _ENV_NAMES)
 
@@ -483,7 +483,7 @@ def apex_key(sd=None, cam=None):
     key = [C.string_at(C.addressof(c), C.sizeof(c))]
     if sd is not None:
         key += [C.string_at(C.addressof(sd.proj), C.sizeof(sd.proj)) if sd.proj.enabled else None]
-        # (not the spot's intensity: randomised per step, no part of the pre-pass; `shadows`: the pre-pass proves the "clear" triangles only for a scene that traces shadow rays)
+        # (not the spot's intensity: randomised per step, no part of the pre-pass; `shadows`: the pre-pass builds the envelopes only for a scene that traces shadow rays)
         key += [(C.string_at(C.addressof(sd.spot), 64), sd.spot.cutoff_deg, int(sd.shadows)) if sd.spot.enabled else (None, int(sd.shadows))]
     else:
         key += [None, None]
@@ -586,25 +586,16 @@ class DeviceGeometry:
         b0 = torch.zeros(int(self.info.total_bytes), dtype=torch.uint8, device=self.device)
         b0[:static].copy_(torch.from_numpy(blob[:static]))
         self._async = self.device.type == "cuda" and os.environ.get("FFX_ASYNC_UPDATE", "1") != "0"
-        # (FFX_BLOB_COPIES >= 2: measured 2 / 3 / 4 copies = 2 050 / 2 043 / 2 038 renders/s — a longer window for the side stream's work buys
-        # nothing: the GPU is busy either way, the re-fit and the pre-pass cost what they cost)
         # (round 5: four copies, of which renders at 33 samples per pixel and more use two — see _ring)
-        n_copies = max(2, int(os.environ.get("FFX_BLOB_COPIES", "4"))) if self._async else 1
+        n_copies = 4 if self._async else 1
         self._blobs = [b0] + [b0.clone() for _ in range(n_copies - 1)]
         self._cur = 0
-        # (FFX_SIDE_PRIORITY: -1 = a high-priority queue for the side stream; measured: renders/s unchanged, gradient steps 2 130 -> 1 540 per
-        # second — the step's small launches on the main stream then wait behind it.  0 = default)
+        # (the side stream has the default priority: a high-priority queue left renders/s unchanged and took gradient steps 2 130 -> 1 540 per
+        # second — the step's small launches on the main stream then wait behind it)
         # (round 6: ONE side stream — and one pair of render streams, shared_streams below — per device and process, not per geometry: the streams of a
         # scene that was used a moment ago keep their hardware queues, and a second scene's own streams then share what is left — its consecutive renders
         # lost their overlap: configs[4] behind a two-stream bracket of the vocal fold, 125 -> 118 renders/s, K8 alone unchanged)
-        self._side = shared_streams(self.device, "side", 1, int(os.environ.get("FFX_SIDE_PRIORITY", "0")))[0] if self._async else None
-        # (round 6, a measured negative result kept as a knob) FFX_SIDE_STREAMS=n: a side stream per blob copy, so that the chains of consecutive
-        # poses — re-fit -> count -> scan -> fill [-> envelopes], five or six dependent launches of mostly latency — overlap each other instead of
-        # queueing on one stream (each writes its own copy; what they share is read-only).  With 4 streams the loops LOSE a quarter (principled
-        # 64 spp 2 890 -> 2 208 renders/s, diffuse 3 406 -> 2 506, 16 spp 5 516 -> 3 849): more side work in flight only takes issue slots and
-        # dispatch turns from the render that the chain then waits for.  Default 1: the one stream of rounds 1-5.
-        n_side = max(1, min(n_copies, int(os.environ.get("FFX_SIDE_STREAMS", "1")))) if self._async else 0
-        self._sides = [self._side] + [torch.cuda.Stream(self.device, priority=int(os.environ.get("FFX_SIDE_PRIORITY", "0"))) for _ in range(n_side - 1)] if self._async else []
+        self._side = shared_streams(self.device, "side", 1)[0] if self._async else None
         self._side_handles = {}
         self._last_spp = 64  # samples per pixel of the last render call (how deep update() lets the poses run ahead: _ring)
         self._upd_done = [None] * n_copies   # event: the refit of blob i has been enqueued up to here (side stream)
@@ -643,10 +634,7 @@ class DeviceGeometry:
             self._smooth = (sm, keep)
         self.smooth = [bool(f) for f in smooth] if smooth is not None else [False] * S
         if self._async:  # blob copies / uploads above were enqueued on the caller's stream
-            if self._smooth is not None:
-                self._sides = self._sides[:1]
-            for s_ in self._sides:
-                s_.wait_stream(_stream_obj(self._didx))
+            self._side.wait_stream(_stream_obj(self._didx))
         self.update(torch.eye(4, dtype=torch.float32).repeat(S, 1, 1) if build_xforms is None else torch.from_numpy(np.asarray(build_xforms, np.float32)))
 
     @property
@@ -696,8 +684,6 @@ class DeviceGeometry:
         Below 33 spp the render is as short as the chain, and with two copies the chain of pose i + 2 has to wait for the render of pose i: 5 435 /
         5 735 / 6 002 renders/s at 1 spp, 5 107 / 5 384 / 5 602 at 10 spp with 2 / 3 / 4 copies."""
         n = len(self._blobs)
-        if len(self._sides) > 1:  # (FFX_SIDE_STREAMS > 1: the chains of up to n - 1 poses ahead may overlap each other and the renders)
-            return n if self._last_spp <= 32 else min(n, max(2, int(os.environ.get("FFX_RING_LONG", "3"))))
         return n if self._last_spp <= 32 else min(n, 2)
 
     def _wait_readers(self, i, stream_obj):
@@ -757,7 +743,7 @@ class DeviceGeometry:
             return
         nxt = (self._cur + 1) % self._ring()
         main = _stream_obj(self._didx)
-        side = self._side_of(nxt)
+        side = self._side
         self._wait_readers(nxt, side)  # its readers must be done before it is overwritten
         if self._pool_written is not None:
             side.wait_event(self._pool_written)  # caller-supplied vertices must have landed in the pool
@@ -782,10 +768,6 @@ class DeviceGeometry:
                 ev.record(side)
         self._cur = nxt
 
-    def _side_of(self, i):
-        """the side stream that re-fits blob copy i (one per copy: the poses' chains overlap; a copy is always written from the same stream)"""
-        return self._sides[i % len(self._sides)]
-
     def _side_handle_of(self, side):
         h = self._side_handles.get(side.cuda_stream)
         if h is None:
@@ -798,7 +780,7 @@ class DeviceGeometry:
         tile bins the blob then holds; vert_off: the frame offsets [S] the call used (host int32, already checked by it)."""
         self.version += 1
         nxt = (self._cur + 1) % self._ring()
-        side = self._side_of(nxt)
+        side = self._side
         self._wait_readers(nxt, side)
         if self._pool_written is not None:
             side.wait_event(self._pool_written)

@@ -20,23 +20,30 @@
  *   - all calls are asynchronous on `stream` (a hipStream_t; the oracle ignores it).
  *   - arrays are dense, row-major, C order.  float = IEEE binary32.
  *   - no global state besides the error string; calls on distinct streams are re-entrant.
- *   - process environment read by libffx_hip.so at every ffx_trace_primary / ffx_render_* call.  None of these
- *     changes a result (tests/test_hip_parity.py runs every variant against the oracle); they select between
- *     equivalent kernels / launch shapes and exist for A/B measurements:
- *       FFX_TRAVERSAL=lane       per-lane kernels (LDS stack, apex vectors per ray) instead of the wave-packet kernels
+ *   - process environment: every FFX_* variable the package reads (libffx_hip.so and fireflies_amd/ both), one entry
+ *     each, with the default the code uses (tests/test_abi_cpu.py keeps this list exact).  None of them changes a result
+ *     (tests/test_hip_parity.py runs the variants against the oracle); they select between equivalent kernels, launch
+ *     shapes and host paths for A/B measurements and tests.  "Large films" below are those of more than 2 x 512^2 pixels.
+ *     Read by libffx_hip.so at every ffx_trace_primary / ffx_render_* call:
+ *       FFX_TRAVERSAL=lane       per-lane kernels (LDS stack, apex vectors per ray) instead of the wave-packet kernels (the Python
+ *                                layer reads it too: the per-lane kernels neither read nor write apex records)
  *       FFX_WIDE=0               wave-packet kernels on the binary walk only (default: 64-wide walk with binary fallback)
- *       FFX_PIXELS_PER_WAVE=1|2|4  pixels of a 2x2 tile one wavefront renders (default 1; 2 when the adjoint cache is written)
- *       FFX_TILE_BLOCK=0..8      log2 side of the square blocks in which tiles are enumerated (default 3)
+ *       FFX_PIXELS_PER_WAVE=1|2|4  pixels of a 2x2 tile one wavefront renders (default 2; 1 on large films, except for the forwards
+ *                                that write an adjoint cache or fold the adjoint, which keep 2)
+ *       FFX_TILE_BLOCK=0..8      log2 side of the square blocks in which tiles are enumerated (default 5; on large films 3, and 4 for
+ *                                the forwards that write an adjoint cache or fold the adjoint)
  *       FFX_XCD_REMAP=0|1|B      workgroup -> tile mapping across the 8 XCDs: 0 round-robin, 1 one image band per XCD,
- *                                B >= 2: each XCD takes B consecutive work items of every 8 B (default 128)
- *       FFX_DUMMY_LDS=bytes      extra dynamic LDS per workgroup (occupancy experiments)
- *       FFX_K7_PPW_LOG2=0..6     cap on log2(pixels per wavefront) of ffx_trace_primary (default 4 at 1 spp, else 3)
+ *                                B >= 2: each XCD takes B consecutive work items of every 8 B (default 1024; 256 on large films)
+ *       FFX_RENDER_BLOCKS=0      ffx_render_fwd / ffx_render_fwd_filtered below 33 samples per pixel: a pixel per wave whatever the count, as
+ *                                at 64 (default: compact blocks of up to 8 pixels per wave, 16 at 1 spp, k_render_fwd_blk — the same image
+ *                                bit for bit, 1.5 - 2.3x faster)
  *       FFX_BINS=0               the packet render kernels walk the tree for every packet (default: tile bins first, ffx_bvh_info.off_bins)
- *       FFX_BIN_TILE=4..32       side of a camera tile of the bins in pixels (default 8)
- *       FFX_SHADOW_CLEAR=1|2|3   (off by default) the pre-pass also proves per triangle that nothing can shadow it from the projector (1) / the
- *                                spot (2) and marks it in its per-slot normal's flag word (ffx_bvh_info.off_gn); a pixel whose samples all
- *                                lie on such triangles skips that emitter's shadow stage — exact, tested, but the proof costs the loop more
- *                                than the skip gains on the default workload (fireflies_amd/csrc/ffx_trace.hip clear_enabled)
+ *       FFX_BIN_TILE=4..32       side of a camera tile of the bins in pixels, a power of two (default 8)
+ *       FFX_BIN_TILE_PROJ=4..64  side of a projector tile of the bins in texels, a power of two (default twice FFX_BIN_TILE)
+ *       FFX_BIN_SPOT_N=8..128    tiles across the spot's square grid (default 2 per degree of the cone's cutoff angle; 1.2 under the
+ *                                caller's hint FFX_SHADOWS_PLAIN)
+ *       FFX_BIN_CAP=n            capacity of each grid's entry list, at most the default 2 F + 16384 (a test knob: a grid whose lists do
+ *                                not fit is marked not-ok by the pre-pass and its packets take the tree walks — the overflow path)
  *       FFX_ENVELOPE=0|1|2|3     (round 6; default 3) the emitters whose tile grid also gets an ENVELOPE from the pre-pass — bit 0 projector, bit 1
  *                                spot: per cell of the grid (7 x 7 per tile) one plane in front of every triangle the tile lists there; a shadow
  *                                packet whose segments all end in front of their cells' planes skips that emitter's any-hit stage (exact: the
@@ -44,22 +51,36 @@
  *                                baseline).  A caller's hint in ffx_scene_desc.shadows (FFX_SHADOWS_PLAIN) leaves them out per pose.
  *       FFX_RFC_CAP=n            blocks of the filtered film's adjoint cache a forward may take, at most what the cache holds (a test knob: pixels
  *                                that find the arena full keep no records and are counted in `dropped` — the overflow path)
- *       FFX_BIN_CAP=n            capacity of each grid's entry list, at most the default 2 F + 16384 (a test knob: a grid whose lists do
- *                                not fit is marked not-ok by the pre-pass and its packets take the tree walks — the overflow path)
- *       FFX_RENDER_BLOCKS=0      ffx_render_fwd / ffx_render_fwd_filtered below 33 samples per pixel: a pixel per wave whatever the count, as
- *                                at 64 (default: compact blocks of up to 8 pixels per wave, k_render_fwd_blk — the same image bit for bit,
- *                                1.5 - 2.3x faster; FFX_RENDER_BLK_LOG2=n: at most 2^n pixels per wave of the box film, an experiment knob)
- *     ffx_bvh_build_host additionally reads, once per build (host side; the renders do not depend on them —
+ *       FFX_K9_BLOCK=8           ffx_render_bwd_cached on the round-2 kernel (default 16: footprints by 16x16-pixel blocks through LDS);
+ *                                ffx_render_bwd_cached_l1 then declines
+ *     Read by ffx_scene_update:
+ *       FFX_REFIT=fused|levels   fused: the fused re-fit as one launch; levels: the level-by-level re-fit (default: the fused re-fit's
+ *                                treelets and the top of the tree as two launches)
+ *     Read by ffx_bvh_build_host, once per build (host side; the renders do not depend on them —
  *     tests/test_hip_parity.py::test_wide_overlay_builders_give_identical_images):
  *       FFX_WIDE_BUILD=area|count|layers   builder of the 64-wide overlay (default area: greedy SAH cut)
- *       FFX_WIDE_CLUSTER=4..64, FFX_WIDE_COST_EXP=x   experiment knobs of that builder (largest cluster; priority area * count^x)
- *     The Python host layer reads FFX_LIB (alternative BUILD of this library), FFX_ASYNC_UPDATE=0 (single BVH blob,
- *     refit on the caller's stream), FFX_CACHE_LIMIT_GB (adjoint cache budget), FFX_HOST_PHILOX=0 (sampler draws on the
- *     device instead of ffx_torch_rand_h) and then FFX_PREDRAW=0, FFX_SIDE_STREAMS=n (a side stream per BVH blob copy: a measured loss, default 1),
- *     FFX_PATTERN_STEP=0 (the optimiser's step with ffx_pattern_bwd_blur + ffx_pattern_fwd_blur instead of ffx_pattern_step), FFX_K9_L1=0 (ffx_l1_value_grad +
- *     ffx_render_bwd_cached instead of ffx_render_bwd_cached_l1), FFX_STEP_STREAMS=1 (the fused renders of a multi-sample step one after the other on the
- *     caller's stream instead of in turn on the scene's two render streams), FFX_DEFER_TOP=n (FFX_STEP_DEFER_TOP while the last render had at most n samples
- *     per pixel; default 8, 0: never); ffx_pattern_step itself reads FFX_ADAM_POW_CACHE=0 (pow() every step);
+ *       FFX_TREELET_TRIS=n       triangles per treelet of the fused re-fit, at least FFX_LEAF_MAX (default 512)
+ *     Read by the Python layer (fireflies_amd/):
+ *       FFX_LIB=path             an alternative BUILD of this library (default fireflies_amd/csrc/libffx_hip.so)
+ *       FFX_ASYNC_UPDATE=0       a single BVH blob, re-fit on the caller's stream (default: four copies, re-fit on a side stream)
+ *       FFX_DEFER_TOP=n          FFX_STEP_DEFER_TOP while the last render had at most n samples per pixel (default 8; 0: never)
+ *       FFX_RENDER_STREAMS=1     mi.Scene renders on the caller's stream (default 2: the process's two render streams, in turn)
+ *       FFX_STEP_STREAMS=1       the fused renders of a multi-sample step one after the other on the caller's stream (default 2: in turn
+ *                                on the scene's two render streams)
+ *       FFX_HOST_MATERIALS=0     material rows stay in device memory (default: tables of up to 128 floats travel inside the scene description)
+ *       FFX_CACHE_LIMIT_GB=x     adjoint cache budget: larger renders take the re-tracing adjoint (default 32)
+ *       FFX_CACHE_MAX_TEXELS_PER_PIXEL=x   expected projector texels per camera pixel beyond which the cache is refused (default 6.0)
+ *       FFX_FUSED_ADJOINT=0      PatternOptimizer: no fused forward + adjoint launch for a linear loss (default 1)
+ *       FFX_FUSED_ADJOINT_FILTERED=1   ... and the fused launch under a gaussian film too (default 0: the filtered forward's per-sample records
+ *                                and the adjoint from them)
+ *       FFX_K9_L1=0              ffx_l1_value_grad + ffx_render_bwd_cached instead of ffx_render_bwd_cached_l1 (default 1)
+ *       FFX_PATTERN_STEP=0       the optimiser's step with ffx_pattern_bwd_blur + ffx_pattern_fwd_blur instead of ffx_pattern_step (default 1)
+ *       FFX_DETERMINISTIC=1      every texture gradient from ffx_render_bwd_det (default 0: the float-atomic adjoints)
+ *       FFX_HOST_PHILOX=0        sampler draws on the device instead of ffx_torch_rand_h (default 1)
+ *       FFX_PREDRAW=0            no draws of the next randomisation ahead of the render (default 1)
+ *       FFX_NATIVE_RANDOMIZE=0   randomize() on the Python path instead of ffx_scene_randomize_h (default 1)
+ *       FFX_NATIVE_UPDATE=0      params.update() on the Python path instead of ffx_scene_step_h (default 1)
+ *       FFX_DIST_FORCE=1         torch.distributed and the gradient exchange even for a single process (default 0)
  *     bench.py reads FFX_DIST_BACKEND and FFX_BENCH_TIMED_STEPS.
  */
 #ifndef FFX_H
@@ -429,7 +450,7 @@ typedef struct ffx_bvh_info {
   int32_t level_start[FFX_MAX_LEVELS + 1]; /* ranges into the refit list, leaves-first */
   /* 64-wide overlay of the same tree for the wave-packet kernels: inner nodes of up to
    * 64 children, triangles grouped in clusters of up to 64 consecutive leaf slots; ONE array of 32-byte
-   * elements {f32 lo[3], f32 hi[3], i32 ref, pad} (16 bytes with 16-bit boxes in a -DFFX_WIDE_F32=0 build).
+   * elements {f32 lo[3], f32 hi[3], i32 ref, pad}.
    * All zero in a blob written by the oracle (which walks its own binary tree). */
   int32_t n_wide;     /* wide inner nodes (0: the whole scene is one cluster) */
   int32_t wide_depth; /* wide inner levels above the clusters */
@@ -453,8 +474,7 @@ typedef struct ffx_bvh_info {
   uint64_t off_gn;    /* (n_tris + 4) x 16 B: per leaf slot the unit geometric normal {nx, ny, nz, bits}, written by ffx_scene_update with
                          IEEE cross / sqrt / divide in the oracle's order; the packet render kernels read it instead of re-deriving it
                          per sample.  The fourth word is NOT a float: raw bits 0 for a degenerate triangle (the normal is then
-                         {0,0,0}), else (shape + 1) | smooth << 30 (smooth: the record is flagged by ffx_smooth; bits 28 / 29: scratch of the
-                         render calls' pre-pass under FFX_SHADOW_CLEAR — "nothing can shadow this triangle from the projector / spot") — the kernels take
+                         {0,0,0}), else (shape + 1) | smooth << 30 (smooth: the record is flagged by ffx_smooth) — the kernels take
                          the hit's shape id and smooth flag from it, so a blob written to any other encoding renders with a wrong
                          material row.  0 in the oracle's blob (it has no such area). */
   /* tile bins (ABI 5, DESIGN.md 5.1 "round 4"): for each of the three ray origins of a render (camera, projector, spot) a

@@ -24,6 +24,26 @@ def test_header_and_python_abi_agree():
     assert _header_symbols() == sorted(_abi.PROTOTYPES)
 
 
+def test_header_lists_exactly_the_environment_knobs_the_package_reads():
+    """include/ffx.h's knob block (one entry per knob, its name first) names every FFX_* variable fireflies_amd/ reads — getenv and
+    env_pow2 in the native sources, os.environ.get / os.environ[...] and ops._ENV_NAMES in Python — and nothing else"""
+    pkg = os.path.join(ROOT, "fireflies_amd")
+    read = set(ops._ENV_NAMES)
+    for d, _, files in os.walk(pkg):
+        for f in files:
+            if f.endswith((".hip", ".cpp", ".h")):
+                pat = r'\b(?:getenv|env_pow2)\(\s*"(FFX_\w+)"'
+            elif f.endswith(".py"):
+                pat = r'\bos\.environ(?:\.get\(|\[)\s*"(FFX_\w+)"'
+            else:
+                continue
+            read.update(re.findall(pat, open(os.path.join(d, f)).read()))
+    block = open(os.path.join(ROOT, "include", "ffx.h")).read().split("*/", 1)[0]
+    listed = re.findall(r"^ \* {7}(FFX_\w+)", block, flags=re.M)
+    assert len(listed) == len(set(listed)), sorted(n for n in listed if listed.count(n) > 1)
+    assert set(listed) == read, {"read, not listed": sorted(read - set(listed)), "listed, not read": sorted(set(listed) - read)}
+
+
 @pytest.mark.parametrize("which", ["hip", "oracle"])
 def test_library_exports_every_symbol(which, oracle):
     path = _lib.LIB_PATH if which == "hip" else oracle.LIB_PATH

@@ -1,4 +1,4 @@
-"""K7 (ffx_trace_primary) time per call for a range of samples per pixel: python tools/k7time.py  (FFX_K7_PPW_LOG2 caps the pixels per wave)"""
+"""K7 (ffx_trace_primary) time per call for a range of samples per pixel: python tools/k7time.py [vocalfold|colon]"""
 import os
 import sys
 
@@ -26,4 +26,4 @@ def t(spp, jit):
     return a.elapsed_time(b) / 20
 
 
-print(which, "cap", os.environ.get("FFX_K7_PPW_LOG2"), " ".join(f"{s}spp {t(s, 1 if s > 1 else 0):.4f}" for s in (1, 2, 4, 8, 16, 32, 64)))
+print(which, " ".join(f"{s}spp {t(s, 1 if s > 1 else 0):.4f}" for s in (1, 2, 4, 8, 16, 32, 64)))
