@@ -4,7 +4,7 @@ The reference is a serial loop (examples/vocalfold_scene.py:100-102); this layer
 One process per GPU.  A step of S samples is split as {k : k mod world == rank}; every sample's
 RNG seed depends only on (base_seed, step, k) — never on the world size — so 1/2/4/8-GPU runs
 sum the same set of per-sample gradients.  The only exchange is ONE all-reduce(sum) of a flat
-fp32 buffer [3N + 1] (pattern gradient + loss; 0.8-12 KB, latency-bound), RCCL over xGMI on GPUs
+fp32 buffer [3N + 2] (pattern gradient + loss + dropped count, exchange_step; 0.8-12 KB, latency-bound), RCCL over xGMI on GPUs
 (`backend="nccl"` is RCCL on ROCm), gloo in the CPU tests.
 """
 import os
@@ -91,17 +91,11 @@ def exchanging():
     return td.is_initialized() and (td.get_world_size() > 1 or force_exchange())
 
 
-def accumulate_step(sample_fn, n_values: int, step: int, n_samples: int, base_seed: int = 0, device="cpu"):
-    """Runs this rank's samples of one step and returns the all-reduced flat buffer
-    [n_values + 1] = (sum of per-sample gradients, sum of per-sample losses), both divided by
-    n_samples.  `sample_fn(seed) -> (grad [n_values], loss scalar)` is the per-sample work
-    (randomise + render + adjoint); it never communicates."""
-    r, w = rank(), world_size()
-    flat = torch.zeros(n_values + 1, dtype=torch.float32, device=device)
-    for k in sample_ids(n_samples, r, w):
-        g, loss = sample_fn(sample_seed(base_seed, step, n_samples, k))
-        flat[:n_values] += g.reshape(-1).to(flat.dtype)
-        flat[n_values] += float(loss) if not isinstance(loss, torch.Tensor) else loss.detach().to(flat.dtype).reshape(())
+def exchange_step(grad: torch.Tensor, loss: torch.Tensor, dropped: torch.Tensor = None):
+    """An optimisation step's ONE exchange: all-reduce(sum) of the fp32 buffer [grad (3N), loss, dropped (PatternOptimizer.step: the adjoint cache's
+    count of dropped samples)].  -> (flat, summed gradient [grad's shape], summed loss [0-dim], guard): `guard` views flat from the gradient's last
+    float, so that its word at byte 8 is the summed count — ffx_adam_clamp_step's guard: no rank updates when any dropped (None without `dropped`)."""
+    n = grad.numel()
+    flat = torch.cat([grad.reshape(-1), loss.reshape(-1)] + ([dropped.reshape(-1)] if dropped is not None else []))
     allreduce_sum_(flat)
-    flat /= float(n_samples)
-    return flat
+    return flat, flat[:n].view(grad.shape), flat[n], (flat[n - 1:] if dropped is not None else None)

@@ -1,5 +1,5 @@
 """Multi-process (gloo, world_size 2) tests of the data-parallel layer: sample sharding, seeds that
-do not depend on the world size, and the single all-reduce of the flat [3N+1] buffer.  The
+do not depend on the world size, and the optimisation step's single all-reduce of the flat [3N+2] buffer (dist.exchange_step).  The
 per-sample work is injected: a closed-form stand-in and the CPU oracle (test infrastructure)."""
 import os
 import socket
@@ -61,6 +61,19 @@ def _oracle_sample_factory():
     return sample, pts.size
 
 
+def _step(fn, n, step, dropped=0.0):
+    """one step's exchange as PatternOptimizer.step composes it: this rank's samples (sample_ids, sample_seed), their gradient and loss summed,
+    the cache's dropped count behind them, ONE dist.exchange_step -> (the buffer / S, the guard word the update launch reads)"""
+    g, loss = torch.zeros(n), torch.zeros(())
+    for k in dist.sample_ids(4, dist.rank(), dist.world_size()):
+        gk, lk = fn(dist.sample_seed(50, step, 4, k))
+        g += gk.reshape(-1).to(g.dtype)
+        loss += float(lk)
+    flat, gsum, lsum, guard = dist.exchange_step(g, loss, torch.tensor([dropped]))
+    assert gsum.data_ptr() == flat.data_ptr() and lsum.data_ptr() == flat[n:].data_ptr()
+    return flat / 4.0, int(guard.view(torch.int32)[2])
+
+
 def _worker(rank, world, port, kind, out):
     os.environ.update(RANK=str(rank), WORLD_SIZE=str(world), LOCAL_RANK=str(rank), MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
     dist.init(backend="gloo")
@@ -68,21 +81,24 @@ def _worker(rank, world, port, kind, out):
         fn, n = _analytic_sample, 12
     else:
         fn, n = _oracle_sample_factory()
-    res = [dist.accumulate_step(fn, n, step, 4, base_seed=50) for step in range(2)]
-    torch.save(torch.stack(res), os.path.join(out, f"r{rank}.pt"))
+    res = [_step(fn, n, step)[0] for step in range(2)]
+    guard = _step(fn, n, 0, dropped=5.0 if rank == 1 else 0.0)[1]  # (only rank 1's cache dropped samples)
+    torch.save({"res": torch.stack(res), "guard": guard}, os.path.join(out, f"r{rank}.pt"))
     torch.distributed.destroy_process_group()
 
 
 @pytest.mark.parametrize("kind", ["analytic", "oracle"])
-def test_two_ranks_match_one_process(tmp_path, kind):
+def test_two_ranks_step_exchange_matches_one_process(tmp_path, kind):
     port = _free_port()
     mp.spawn(_worker, args=(2, port, kind, str(tmp_path)), nprocs=2, join=True)
-    r0, r1 = torch.load(tmp_path / "r0.pt"), torch.load(tmp_path / "r1.pt")
+    o0, o1 = torch.load(tmp_path / "r0.pt"), torch.load(tmp_path / "r1.pt")
+    r0, r1 = o0["res"], o1["res"]
     torch.testing.assert_close(r0, r1, rtol=0, atol=0)  # every rank holds the reduced buffer
+    assert o0["guard"] != 0 and o1["guard"] != 0  # one rank's dropped samples reach every rank's update guard
     # single process reference (no process group)
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
         os.environ.pop(k, None)
     fn, n = (_analytic_sample, 12) if kind == "analytic" else _oracle_sample_factory()
-    ref = torch.stack([dist.accumulate_step(fn, n, step, 4, base_seed=50) for step in range(2)])
+    ref = torch.stack([_step(fn, n, step)[0] for step in range(2)])
     torch.testing.assert_close(r0, ref, rtol=1e-5, atol=1e-7)  # same samples, different summation order
     assert float(ref.abs().sum()) > 0
