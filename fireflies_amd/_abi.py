@@ -7,7 +7,7 @@ shared library (oracle/oracle.py) — both libraries implement the same header.
 import ctypes as C
 
 FFX_MAX_LEVELS = 96
-FFX_ABI_VERSION = 10
+FFX_ABI_VERSION = 11
 PATTERN_SYNC_BYTES = 35840  # FFX_PATTERN_SYNC_BYTES
 FFX_ERR_UNSUPPORTED = -3
 REDUCE_SUM = 0
@@ -177,6 +177,15 @@ MAT_MODEL, MAT_ROUGHNESS, MAT_ANISOTROPIC, MAT_METALLIC, MAT_SPEC_TRANS, MAT_ETA
 MAT_SPEC_TINT, MAT_SHEEN, MAT_SHEEN_TINT, MAT_FLATNESS, MAT_CLEARCOAT, MAT_CLEARCOAT_GLOSS = 9, 10, 11, 12, 13, 14
 MAT_BASE_TEX = 15
 RENDER_FP16, RENDER_SPARSE_ADJOINT, RENDER_APEX_READY, RENDER_CACHE_ZEROED, RENDER_CACHE_KEEP_DROPPED = 1, 2, 4, 8, 16  # flags in the img_fp16 argument of the render calls
+# the path integrator's depths in bits 8..15 of the flags word of ffx_render_fwd[_filtered] / ffx_render_bwd[_filtered] (ABI 11)
+RENDER_MAX_DEPTH_SHIFT, RENDER_RR_DEPTH_SHIFT, RENDER_PATH_MASK, RENDER_MAX_DEPTH_LIMIT = 8, 12, 0xFF00, 8
+
+
+def render_path(max_depth, rr_depth):
+    """FFX_RENDER_PATH(max_depth, rr_depth): the flags bits of a path render (0 for max_depth 2: the direct-light kernels)"""
+    return 0 if max_depth == 2 else ((max_depth & 15) << RENDER_MAX_DEPTH_SHIFT) | ((rr_depth & 15) << RENDER_RR_DEPTH_SHIFT)
+
+
 MAX_BASE_TEX = 4
 RFILTER_BOX, RFILTER_GAUSSIAN = 0, 1
 MAX_MAT_H = 128

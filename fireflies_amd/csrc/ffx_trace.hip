@@ -657,10 +657,18 @@ struct SampleTerms {
 
 __device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
+// what a path vertex needs beyond the emitters' terms: the lifted origin of its secondary ray, its normals, whether the row's base
+// colour came from a texture.  ok = 0: no vertex (a miss, a degenerate triangle)
+struct PathVtx { v3 Po, ng, ns; int textured, ok; };
+
+// the sample's hit in (nt, ft] and next-event estimation there: projector and spot terms, shadow rays, base colour.  PATH (the path kernels):
+// the ray has an arbitrary origin (no apex form) and *pv receives the vertex
+template <bool PATH = false>
 __device__ __forceinline__ void shade_sample(const ShadeK &c, const BvhNode *__restrict__ nodes, const TriRec *__restrict__ recs, const float4 *__restrict__ nrec, v3 o,
-                                             v3 d, float nt, float ft, SampleTerms &st, int *stack, int stride) {
+                                             v3 d, float nt, float ft, SampleTerms &st, int *stack, int stride, PathVtx *pv = nullptr) {
   Hit h;
-  st.hit = traverse<false, true>(nodes, recs, o, d, nt, ft, h, stack, stride);
+  st.hit = traverse<false, !PATH>(nodes, recs, o, d, nt, ft, h, stack, stride);
+  if (PATH) pv->ok = 0;
   st.has_proj = 0;
   st.proj_fac = 0.f; st.proj_fac_b = 0.f;
   st.spot[0] = st.spot[1] = st.spot[2] = 0.f;
@@ -696,6 +704,7 @@ __device__ __forceinline__ void shade_sample(const ShadeK &c, const BvhNode *__r
       textured = true;
     }
   }
+  if (PATH) { pv->Po = Po; pv->ng = ng; pv->ns = ns; pv->textured = textured ? 1 : 0; pv->ok = 1; }
 
   if (c.proj_on) {
     v3 pl = xf_point(c.p_w2l, P);
@@ -3976,6 +3985,216 @@ __global__ void __launch_bounds__(64)
   }
 }
 
+// ------------------------------------------------------------------------------------------ path integrator
+// max_depth > 2 (include/ffx.h FFX_RENDER_PATH): Mitsuba's `path` with cosine-weighted bounces and next-event estimation to the two delta emitters
+// at every vertex.  Per-lane kernels: one wave = one pixel, lane l takes samples l, l + 64, ... (the layout rf_fold needs), one lane walks one path
+// with shade_sample's arbitrary-ray form.  The adjoint replays the same paths: the texture enters through the emitters' terms only.
+// The counter-based stream of the path's random numbers: vertex v (1 = the primary hit), dimension dim (0, 1: the bounce direction, 2: roulette)
+__device__ __forceinline__ float path_u(uint32_t path_key, uint32_t idx, int v, int dim) {
+  const uint32_t r = hash32(hash32(idx ^ path_key) + (uint32_t)(4 * v + dim));
+  return (float)(r >> 8) * (1.0f / 16777216.0f);
+}
+// cosine-weighted direction about the unit normal n: (sqrt(u0) cos(2 pi u1), sqrt(u0) sin(2 pi u1), sqrt(1 - u0)) in the frame of Duff et al. 2017
+__device__ __forceinline__ v3 cosine_dir(v3 n, float u0, float u1) {
+  const float sg = copysignf(1.0f, n.z), a = -1.0f / (sg + n.z), b = n.x * n.y * a;
+  const v3 s = V3(1.0f + sg * n.x * n.x * a, sg * b, -sg * n.x), t = V3(b, sg + n.y * n.y * a, -n.y);
+  const float r = sqrtf(u0), ph = 2.0f * FFX_PI_F * u1, z = sqrtf(fmaxf(1.0f - u0, 0.f));
+  const float x = r * cosf(ph), y = r * sinf(ph);
+  return V3(fmaf(x, s.x, fmaf(y, t.x, z * n.x)), fmaf(x, s.y, fmaf(y, t.y, z * n.y)), fmaf(x, s.z, fmaf(y, t.z, z * n.z)));
+}
+// the projector's texture value at a vertex, per colour channel (1-channel textures: times the projector's colour)
+__device__ __forceinline__ void path_tex(const ShadeK &c, const SampleTerms &st, const float *__restrict__ tex, float (&tv)[3]) {
+  const int tc = c.tc;
+  const size_t o00 = ((size_t)st.iy0 * c.tw + st.ix0) * tc, o01 = ((size_t)st.iy0 * c.tw + st.ix1) * tc;
+  const size_t o10 = ((size_t)st.iy1 * c.tw + st.ix0) * tc, o11 = ((size_t)st.iy1 * c.tw + st.ix1) * tc;
+  if (tc == 1) {
+    const float v = st.wy0 * (st.wx0 * tex[o00] + st.wx1 * tex[o01]) + st.wy1 * (st.wx0 * tex[o10] + st.wx1 * tex[o11]);
+    tv[0] = v * c.p_color[0]; tv[1] = v * c.p_color[1]; tv[2] = v * c.p_color[2];
+  } else {
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) tv[ch] = st.wy0 * (st.wx0 * tex[o00 + ch] + st.wx1 * tex[o01 + ch]) + st.wy1 * (st.wx0 * tex[o10 + ch] + st.wx1 * tex[o11 + ch]);
+  }
+}
+// the bounce at vertex pv towards wo: throughput *= pi f = (base A + B) / cos_o (Lambert rows: base)
+__device__ __forceinline__ void path_bounce_weight(const ShadeK &c, const SampleTerms &st, const PathVtx &pv, v3 d, v3 wo, float (&f)[3]) {
+  const float *mt = mat_table(c);
+  f[0] = st.base[0]; f[1] = st.base[1]; f[2] = st.base[2];
+  if (c.mat_stride == FFX_MAT_STRIDE && mt[(size_t)FFX_MAT_STRIDE * st.shape + FFX_MAT_MODEL] != 0.f) {
+    const float *mrow = mt + (size_t)FFX_MAT_STRIDE * st.shape;
+    MatGeo mg;
+    material_geometry(mrow, pv.ns, V3(-d.x, -d.y, -d.z), wo, mg);
+    float A, B;
+    if (pv.textured) material_terms<true>(mrow, mg, A, B, st.base[0], st.base[1], st.base[2]);
+    else material_terms(mrow, mg, A, B);
+    const float ic = mg.cos_o > 0.f ? 1.0f / mg.cos_o : 0.f;
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) f[ch] = (st.base[ch] * A + B) * ic;
+  }
+}
+struct PathArgs { const BvhNode *nodes; const TriRec *recs; const float4 *nrec; int spp, max_depth, rr_depth; uint32_t seed_key, path_key; };
+// one path of sample idx whose camera ray is (o, d) in (nt, ft].  At every vertex visit(st, beta) sees the emitters' terms and the throughput;
+// then the bounce (vertex v < max_depth - 1), the roulette (v >= rr_depth) and the secondary ray from the lifted point
+template <typename F>
+__device__ __forceinline__ void path_walk(const PathArgs &a, uint32_t idx, v3 o, v3 d, float nt, float ft, int *stack, F &&visit) {
+  const ShadeK &c = kernarg_shade();
+  SampleTerms st;
+  PathVtx pv;
+  shade_sample<true>(c, a.nodes, a.recs, a.nrec, o, d, nt, ft, st, stack, 64, &pv);
+  float beta[3] = {1.f, 1.f, 1.f};
+  for (int v = 1; st.hit && pv.ok; ++v) {
+    visit(st, beta);
+    if (v + 1 >= a.max_depth) break;
+    const v3 wo = cosine_dir(pv.ns, path_u(a.path_key, idx, v, 0), path_u(a.path_key, idx, v, 1));
+    if (!(vdot(pv.ng, wo) > 0.f)) break;
+    float f[3];
+    path_bounce_weight(c, st, pv, d, wo, f);
+    beta[0] *= f[0]; beta[1] *= f[1]; beta[2] *= f[2];
+    const float bmax = fmaxf(beta[0], fmaxf(beta[1], beta[2]));
+    if (!(bmax > 0.f)) break;
+    if (v >= a.rr_depth) { // Mitsuba's roulette: survive with q = min(max beta, 0.95), then beta /= q
+      const float q = fminf(bmax, 0.95f);
+      if (path_u(a.path_key, idx, v, 2) >= q) break;
+      const float iq = 1.0f / q;
+      beta[0] *= iq; beta[1] *= iq; beta[2] *= iq;
+    }
+    o = pv.Po;
+    d = wo;
+    shade_sample<true>(c, a.nodes, a.recs, a.nrec, o, d, 0.f, 3.0e38f, st, stack, 64, &pv);
+  }
+}
+__device__ __forceinline__ float wave_sum_tree(float v) { // (fixed order: the same bits on every run)
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+  return v;
+}
+// RF: the gaussian film — the pixel's 25 x 4 outgoing sums into `part` ([pixel][25][4], k_rf_gather forms the image); else the pixel's mean into img
+template <bool RF>
+__global__ void __launch_bounds__(64)
+    k_path_fwd(ShadeK c, PathArgs a, const float *__restrict__ tex, int fp16, void *__restrict__ img, float *__restrict__ part) {
+  extern __shared__ int s_dyn[];
+  __shared__ __attribute__((aligned(16))) float s_rf[RF ? FFX_RF_FLOATS : 4];
+  const int lane = threadIdx.x;
+  const uint32_t pix = blockIdx.x;
+  const int W = c.cam.W, px = (int)(pix % (uint32_t)W), py = (int)(pix / (uint32_t)W);
+  float acc[4] = {0.f, 0.f, 0.f, 0.f};
+  for (int pass = 0; pass < (a.spp + 63) >> 6; ++pass) {
+    const int s = pass * 64 + lane;
+    const uint32_t idx = pix * (uint32_t)a.spp + (uint32_t)s;
+    float jx, jy;
+    sample_jitter(a.seed_key, idx, jx, jy);
+    float L[3] = {0.f, 0.f, 0.f};
+    if (s < a.spp) {
+      v3 o, d;
+      float nt, ft;
+      cam_ray(c.cam, ((float)px + jx) * c.cam.inv_w, ((float)py + jy) * c.cam.inv_h, o, d, nt, ft);
+      path_walk(a, idx, o, d, nt, ft, s_dyn + lane, [&](const SampleTerms &st, const float (&beta)[3]) {
+        const ShadeK &k = kernarg_shade();
+        float r[3] = {st.spot[0], st.spot[1], st.spot[2]}, b[3] = {st.spot_b[0], st.spot_b[1], st.spot_b[2]};
+        if (st.has_proj) {
+          float tv[3];
+          path_tex(k, st, tex, tv);
+#pragma unroll
+          for (int ch = 0; ch < 3; ++ch) { r[ch] += tv[ch] * st.proj_fac; b[ch] += tv[ch] * st.proj_fac_b; }
+        }
+#pragma unroll
+        for (int ch = 0; ch < 3; ++ch) L[ch] += beta[ch] * (k.mat_stride == 3 ? st.base[ch] * r[ch] : st.base[ch] * r[ch] + b[ch]);
+      });
+    }
+    if (RF) {
+      float gx[5], gy[5];
+      rf_weights(c.rf, jx, gx);
+      rf_weights(c.rf, jy, gy);
+      rf_fold(s_rf, lane, gx, gy, L[0], L[1], L[2], s < a.spp ? 1.f : 0.f, acc);
+    } else {
+      acc[0] += L[0]; acc[1] += L[1]; acc[2] += L[2];
+    }
+  }
+  if (RF) {
+    rf_store(part, pix, lane, acc);
+    return;
+  }
+  const float inv_spp = 1.0f / (float)a.spp;
+  const float m0 = wave_sum_tree(acc[0]) * inv_spp, m1 = wave_sum_tree(acc[1]) * inv_spp, m2 = wave_sum_tree(acc[2]) * inv_spp;
+  if (lane == 0) {
+    if (fp16 & 1) {
+      _Float16 *p = (_Float16 *)img + (size_t)pix * 3;
+      p[0] = (_Float16)m0; p[1] = (_Float16)m1; p[2] = (_Float16)m2;
+    } else {
+      float *p = (float *)img + (size_t)pix * 3;
+      p[0] = m0; p[1] = m1; p[2] = m2;
+    }
+  }
+}
+// the adjoint: replays k_path_fwd's paths and scatters every vertex's projector term, weighted by the sample's d loss / d radiance, through its four
+// bilinear taps.  Box film: gimg[pixel] / spp; RF: sum over the sample's 5x5 window of filter weight x G (G = gimg / weight, float4 per pixel)
+template <bool RF>
+__global__ void __launch_bounds__(64)
+    k_path_bwd(ShadeK c, PathArgs a, const float *__restrict__ gsrc, float *__restrict__ gtex) {
+  extern __shared__ int s_dyn[];
+  const int lane = threadIdx.x;
+  const uint32_t pix = blockIdx.x;
+  const int W = c.cam.W, H = c.cam.H, px = (int)(pix % (uint32_t)W), py = (int)(pix / (uint32_t)W);
+  float g0 = 0.f, g1 = 0.f, g2 = 0.f; // box: the pixel's gradient / spp; RF: lanes 0..24 hold G of window pixel `lane`
+  if (RF) {
+    const float4 gw = rf_window_g(reinterpret_cast<const float4 *>(gsrc), px, py, W, H, lane, true);
+    g0 = gw.x; g1 = gw.y; g2 = gw.z;
+    if (wballot(g0 != 0.f || g1 != 0.f || g2 != 0.f) == 0ull) return;
+  } else {
+    const float inv_spp = 1.0f / (float)a.spp;
+    g0 = gsrc[(size_t)pix * 3] * inv_spp; g1 = gsrc[(size_t)pix * 3 + 1] * inv_spp; g2 = gsrc[(size_t)pix * 3 + 2] * inv_spp;
+    if (g0 == 0.f && g1 == 0.f && g2 == 0.f) return; // (block-uniform)
+  }
+  for (int pass = 0; pass < (a.spp + 63) >> 6; ++pass) {
+    const int s = pass * 64 + lane;
+    const uint32_t idx = pix * (uint32_t)a.spp + (uint32_t)s;
+    float jx, jy;
+    sample_jitter(a.seed_key, idx, jx, jy);
+    float q[3] = {g0, g1, g2};
+    if (RF) { // (all lanes: the readlanes need the whole wave)
+      float gx[5], gy[5];
+      rf_weights(c.rf, jx, gx);
+      rf_weights(c.rf, jy, gy);
+      q[0] = q[1] = q[2] = 0.f;
+#pragma unroll
+      for (int n = 0; n < 25; ++n) {
+        const float w = gx[n % 5] * gy[n / 5];
+        q[0] = __builtin_fmaf(w, __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(g0), n)), q[0]);
+        q[1] = __builtin_fmaf(w, __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(g1), n)), q[1]);
+        q[2] = __builtin_fmaf(w, __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(g2), n)), q[2]);
+      }
+    }
+    if (s >= a.spp || (q[0] == 0.f && q[1] == 0.f && q[2] == 0.f)) continue;
+    v3 o, d;
+    float nt, ft;
+    cam_ray(c.cam, ((float)px + jx) * c.cam.inv_w, ((float)py + jy) * c.cam.inv_h, o, d, nt, ft);
+    path_walk(a, idx, o, d, nt, ft, s_dyn + lane, [&](const SampleTerms &st, const float (&beta)[3]) {
+      if (!st.has_proj) return;
+      const ShadeK &k = kernarg_shade();
+      float cw[3]; // d radiance / d (texture value) per channel, times the sample's gradient
+#pragma unroll
+      for (int ch = 0; ch < 3; ++ch) cw[ch] = q[ch] * beta[ch] * (st.base[ch] * st.proj_fac + st.proj_fac_b);
+      const int tc = k.tc;
+      const size_t o00 = ((size_t)st.iy0 * k.tw + st.ix0) * tc, o01 = ((size_t)st.iy0 * k.tw + st.ix1) * tc;
+      const size_t o10 = ((size_t)st.iy1 * k.tw + st.ix0) * tc, o11 = ((size_t)st.iy1 * k.tw + st.ix1) * tc;
+      if (tc == 1) {
+        const float ws = cw[0] * k.p_color[0] + cw[1] * k.p_color[1] + cw[2] * k.p_color[2];
+        atomicAdd(gtex + o00, ws * st.wy0 * st.wx0);
+        atomicAdd(gtex + o01, ws * st.wy0 * st.wx1);
+        atomicAdd(gtex + o10, ws * st.wy1 * st.wx0);
+        atomicAdd(gtex + o11, ws * st.wy1 * st.wx1);
+      } else {
+#pragma unroll
+        for (int ch = 0; ch < 3; ++ch) {
+          atomicAdd(gtex + o00 + ch, cw[ch] * st.wy0 * st.wx0);
+          atomicAdd(gtex + o01 + ch, cw[ch] * st.wy0 * st.wx1);
+          atomicAdd(gtex + o10 + ch, cw[ch] * st.wy1 * st.wx0);
+          atomicAdd(gtex + o11 + ch, cw[ch] * st.wy1 * st.wx1);
+        }
+      }
+    });
+  }
+}
+
 // ------------------------------------------------------------------------------------------ host side
 static int cam_prepare(const ffx_camera *c, CamK &k) {
   if (c->width < 1 || c->height < 1) return 0;
@@ -4480,6 +4699,26 @@ int ffx_trace_rays(const void *bvh, const ffx_bvh_info *info, const float *origi
   return FFX_OK;
 }
 
+// the path integrator's depths from a flags word (include/ffx.h FFX_RENDER_PATH): 0 = a bad field, else 1 with max_depth (2: direct light only, the
+// existing kernels) and rr_depth
+static int path_depths(int flags, int &max_depth, int &rr_depth) {
+  const int md = (flags >> FFX_RENDER_MAX_DEPTH_SHIFT) & 15, rr = (flags >> FFX_RENDER_RR_DEPTH_SHIFT) & 15;
+  max_depth = md == 0 ? 2 : md;
+  rr_depth = rr == 0 ? 5 : rr;
+  return max_depth >= 2 && max_depth <= FFX_RENDER_MAX_DEPTH_LIMIT;
+}
+static PathArgs path_args(const void *bvh, const ffx_bvh_info *info, int spp, uint32_t seed, int max_depth, int rr_depth) {
+  PathArgs a;
+  a.nodes = (const BvhNode *)((const char *)bvh + info->off_nodes);
+  a.recs = (const TriRec *)((const char *)bvh + info->off_recs);
+  a.nrec = info->off_nrec ? (const float4 *)((const char *)bvh + info->off_nrec) : nullptr;
+  a.spp = spp; a.max_depth = max_depth; a.rr_depth = rr_depth;
+  a.seed_key = seed_key_of(seed);
+  a.path_key = hash32(a.seed_key ^ 0x5bd1e995U);
+  return a;
+}
+static inline size_t path_stack_bytes(const ffx_bvh_info *info) { return (size_t)(info->max_depth < 8 ? 8 : info->max_depth) * 64 * sizeof(int); }
+
 static int render_fwd_impl(const void *bvh, const ffx_bvh_info *info, const ffx_scene_desc *sd, const float *shape_albedo, const float *tex, int spp,
                            uint32_t seed, int call_flags, void *img, void *cache, ffx_stream s, const float *adj_gimg = nullptr, float *adj_gtex = nullptr,
                            float *adj_dot = nullptr, void *rf_scratch = nullptr, void *rf_cache = nullptr) {
@@ -4501,6 +4740,25 @@ static int render_fwd_impl(const void *bvh, const ffx_bvh_info *info, const ffx_
   const TriRec *recs = (const TriRec *)((const char *)bvh + info->off_recs);
   const float4 *nrec = info->off_nrec ? (const float4 *)((const char *)bvh + info->off_nrec) : nullptr; // vertex normals per slot (ffx_smooth)
   const float4 *gn = info->off_gn ? (const float4 *)((const char *)bvh + info->off_gn) : nullptr;         // unit geometric normals per slot
+  int max_depth, rr_depth;
+  if (!path_depths(call_flags, max_depth, rr_depth)) FFX_FAIL(FFX_ERR_ARG, "render_fwd: max_depth must be 2 .. %d", FFX_RENDER_MAX_DEPTH_LIMIT);
+  if (max_depth > 2) { // the path integrator: one wave per pixel; no apex records, no tile bins
+    if (cache || adj_gtex) FFX_FAIL(FFX_ERR_UNSUPPORTED, "render_fwd: max_depth > 2 has neither an adjoint cache nor a fused adjoint (use ffx_render_bwd)");
+    const long n_pix = (long)c.cam.W * c.cam.H;
+    if (n_pix >= (1L << 31)) FFX_FAIL(FFX_ERR_UNSUPPORTED, "render_fwd: more than 2^31 pixels");
+    const PathArgs pa = path_args(bvh, info, spp, seed, max_depth, rr_depth);
+    if (rf_scratch) {
+      hipLaunchKernelGGL(k_path_fwd<true>, dim3((unsigned)n_pix), dim3(64), path_stack_bytes(info), (hipStream_t)s, c, pa, tex, 0, (void *)nullptr, (float *)rf_scratch);
+      FFX_CHECK_LAUNCH("render_fwd_filtered (path)");
+      hipLaunchKernelGGL(k_rf_gather, dim3(ffx_cdiv(c.cam.W, 64), ffx_cdiv(c.cam.H, FFX_RFG_WAVES)), dim3(64 * FFX_RFG_WAVES), 0, (hipStream_t)s, (const float4 *)rf_scratch, c.cam.W,
+                         c.cam.H, img_fp16 & 1, img, (const float *)nullptr, (float4 *)nullptr);
+      FFX_CHECK_LAUNCH("render_fwd_filtered (path)/gather");
+      return FFX_OK;
+    }
+    hipLaunchKernelGGL(k_path_fwd<false>, dim3((unsigned)n_pix), dim3(64), path_stack_bytes(info), (hipStream_t)s, c, pa, tex, img_fp16 & 1, img, (float *)nullptr);
+    FFX_CHECK_LAUNCH("render_fwd (path)");
+    return FFX_OK;
+  }
   if (cache && sd->n_base_tex > 0) FFX_FAIL(FFX_ERR_UNSUPPORTED, "render_fwd_cache: textured base colours (the footprint folds one base colour per shape): use ffx_render_bwd");
   if (cache && sd->proj.enabled && (sd->proj.tex_w > 4094 || sd->proj.tex_h > 4094 || sd->n_shapes > 255))
     FFX_FAIL(FFX_ERR_UNSUPPORTED, "render_fwd_cache: texture larger than 4094^2 or more than 255 shapes");
@@ -4645,8 +4903,11 @@ static int render_fwd_impl(const void *bvh, const ffx_bvh_info *info, const ffx_
 
 int ffx_render_fwd(const void *bvh, const ffx_bvh_info *info, const ffx_scene_desc *sd, const float *shape_albedo, const float *tex, int spp,
                    uint32_t seed, int img_fp16, void *img, ffx_stream s) {
-  return render_fwd_impl(bvh, info, sd, shape_albedo, tex, spp, seed, img_fp16 & (FFX_RENDER_FP16 | FFX_RENDER_APEX_READY), img, nullptr, s);
+  return render_fwd_impl(bvh, info, sd, shape_albedo, tex, spp, seed, img_fp16 & (FFX_RENDER_FP16 | FFX_RENDER_APEX_READY | FFX_RENDER_PATH_MASK), img, nullptr, s);
 }
+// the entry points without the path integrator refuse its bits rather than render direct light only
+#define FFX_NO_PATH(flags_, what_) \
+  do { if ((flags_) & FFX_RENDER_PATH_MASK) FFX_FAIL(FFX_ERR_UNSUPPORTED, "%s: max_depth > 2 is served by ffx_render_fwd[_filtered] / ffx_render_bwd[_filtered] only", what_); } while (0)
 
 size_t ffx_render_cache_bytes(int width, int height, int spp) {
   if (width < 1 || height < 1 || spp < 1) return 0;
@@ -4665,6 +4926,7 @@ int ffx_render_fwd_cache(const void *bvh, const ffx_bvh_info *info, const ffx_sc
                          uint32_t seed, int img_fp16, void *img, void *cache, ffx_stream s) {
   if (!cache) FFX_FAIL(FFX_ERR_ARG, "render_fwd_cache: cache is NULL");
   if (((uintptr_t)cache & 15) != 0) FFX_FAIL(FFX_ERR_ARG, "render_fwd_cache: cache must be 16-byte aligned");
+  FFX_NO_PATH(img_fp16, "render_fwd_cache");
   return render_fwd_impl(bvh, info, sd, shape_albedo, tex, spp, seed, img_fp16 & 31, img, cache, s);
 }
 
@@ -4682,6 +4944,7 @@ int ffx_render_fwd_adjoint(const void *bvh, const ffx_bvh_info *info, const ffx_
                            uint32_t seed, int img_fp16, void *img, const float *gimg, float *gtex, float *dot_out, ffx_stream s) {
   if (!gimg || !gtex) FFX_FAIL(FFX_ERR_ARG, "render_fwd_adjoint: gimg / gtex is NULL");
   if (sd && !sd->proj.enabled) FFX_FAIL(FFX_ERR_ARG, "render_fwd_adjoint: the scene has no projector (nothing to differentiate)");
+  FFX_NO_PATH(img_fp16, "render_fwd_adjoint");
   return render_fwd_impl(bvh, info, sd, shape_albedo, tex, spp, seed, img_fp16 & (FFX_RENDER_FP16 | FFX_RENDER_SPARSE_ADJOINT | FFX_RENDER_APEX_READY), img, nullptr, s, gimg,
                          gtex, dot_out);
 }
@@ -4709,6 +4972,7 @@ static int render_bwd_cached_impl(const ffx_scene_desc *sd, const float *shape_a
 int ffx_render_bwd_cached(const ffx_scene_desc *sd, const float *shape_albedo, const void *cache, int spp, const float *gimg, float *gtex, const void *img,
                           int img_fp16, float *dot_out, ffx_stream s) {
   if (!gimg) FFX_FAIL(FFX_ERR_ARG, "render_bwd_cached: bad argument");
+  FFX_NO_PATH(img_fp16, "render_bwd_cached");
   return render_bwd_cached_impl(sd, shape_albedo, cache, spp, gimg, gtex, img, img_fp16, dot_out, nullptr, 0.f, s);
 }
 // K9 under an L1 loss against a target image (include/ffx.h): the loss launch (ffx_l1_value_grad) and its gradient image are folded into the scatter
@@ -4795,6 +5059,29 @@ static int render_bwd_impl(const void *bvh, const ffx_bvh_info *info, const ffx_
   const TriRec *recs = (const TriRec *)((const char *)bvh + info->off_recs);
   const float4 *nrec = info->off_nrec ? (const float4 *)((const char *)bvh + info->off_nrec) : nullptr;
   const float4 *gn = info->off_gn ? (const float4 *)((const char *)bvh + info->off_gn) : nullptr;
+  int max_depth, rr_depth;
+  if (!path_depths(flags, max_depth, rr_depth)) FFX_FAIL(FFX_ERR_ARG, "render_bwd: max_depth must be 2 .. %d", FFX_RENDER_MAX_DEPTH_LIMIT);
+  if (max_depth > 2) { // the path integrator's adjoint: replays the forward's paths
+    if (det_ws || det_part) FFX_FAIL(FFX_ERR_UNSUPPORTED, "render_bwd_det: max_depth > 2 has no deterministic adjoint");
+    const long n_pix = (long)c.cam.W * c.cam.H;
+    if (n_pix >= (1L << 31)) FFX_FAIL(FFX_ERR_UNSUPPORTED, "render_bwd: more than 2^31 pixels");
+    const PathArgs pa = path_args(bvh, info, spp, seed, max_depth, rr_depth);
+    if (rf_scratch) { // G = gimg / weight as in the re-tracing filtered adjoint below
+      float *part = (float *)rf_scratch;
+      float4 *G = (float4 *)(part + (size_t)n_pix * 100);
+      hipLaunchKernelGGL(k_rf_weights, dim3((unsigned)n_pix), dim3(64), 0, (hipStream_t)s, c.rf, (int)n_pix, spp, seed_key_of(seed), part);
+      FFX_CHECK_LAUNCH("render_bwd_filtered (path)/weights");
+      hipLaunchKernelGGL(k_rf_gather, dim3(ffx_cdiv(c.cam.W, 64), ffx_cdiv(c.cam.H, FFX_RFG_WAVES)), dim3(64 * FFX_RFG_WAVES), 0, (hipStream_t)s, (const float4 *)part, c.cam.W, c.cam.H, 0,
+                         (void *)nullptr, gimg, G);
+      FFX_CHECK_LAUNCH("render_bwd_filtered (path)/gather");
+      hipLaunchKernelGGL(k_path_bwd<true>, dim3((unsigned)n_pix), dim3(64), path_stack_bytes(info), (hipStream_t)s, c, pa, (const float *)G, gtex);
+      FFX_CHECK_LAUNCH("render_bwd_filtered (path)");
+      return FFX_OK;
+    }
+    hipLaunchKernelGGL(k_path_bwd<false>, dim3((unsigned)n_pix), dim3(64), path_stack_bytes(info), (hipStream_t)s, c, pa, gimg, gtex);
+    FFX_CHECK_LAUNCH("render_bwd (path)");
+    return FFX_OK;
+  }
   if (use_packet() && !gn) FFX_FAIL(FFX_ERR_ARG, "render_bwd: blob without per-slot normals (built by another library version?)");
   if (use_packet()) {
     const int tb = tile_block_log2((long)c.cam.W * c.cam.H);
@@ -4903,6 +5190,7 @@ int ffx_render_bwd_det(const void *bvh, const ffx_bvh_info *info, const ffx_scen
                        const float *gimg, float *gtex, void *workspace, ffx_stream s) {
   if (!workspace || ((uintptr_t)workspace & 15) != 0) FFX_FAIL(FFX_ERR_ARG, "render_bwd_det: workspace is NULL or not 16-byte aligned");
   if (!sd) FFX_FAIL(FFX_ERR_ARG, "render_bwd_det: bad argument");
+  FFX_NO_PATH(flags, "render_bwd_det");
   // workspace: [the filtered film's scratch (16-byte multiple)] [one 64-bit sum per texel and channel] [the largest tap]
   void *rf = sd->rfilter != FFX_RFILTER_BOX ? workspace : nullptr;
   void *det = (char *)workspace + (rf ? ffx_render_filter_bytes(sd) : 0);
@@ -4913,6 +5201,7 @@ int ffx_render_bwd_det_part(const void *bvh, const ffx_bvh_info *info, const ffx
                             const float *gimg, int part, int scale_log2, void *acc, void *workspace, ffx_stream s) {
   if (!sd || !acc || (part != 1 && part != 2) || ((uintptr_t)acc & (part == 1 ? 3 : 7)) != 0) FFX_FAIL(FFX_ERR_ARG, "render_bwd_det_part: bad argument");
   if (scale_log2 < -126 || scale_log2 > 126) FFX_FAIL(FFX_ERR_ARG, "render_bwd_det_part: scale_log2 out of range");
+  FFX_NO_PATH(flags, "render_bwd_det_part");
   void *rf = nullptr;
   if (sd->rfilter != FFX_RFILTER_BOX) {
     if (!workspace || ((uintptr_t)workspace & 15) != 0) FFX_FAIL(FFX_ERR_ARG, "render_bwd_det_part: a filtered film needs its scratch (ffx_render_filter_bytes), 16-byte aligned");
@@ -4941,8 +5230,8 @@ size_t ffx_render_filter_bytes(const ffx_scene_desc *sd) {
 int ffx_render_fwd_filtered(const void *bvh, const ffx_bvh_info *info, const ffx_scene_desc *sd, const float *shape_albedo, const float *tex, int spp,
                             uint32_t seed, int img_fp16, void *img, void *scratch, ffx_stream s) {
   if (!scratch || ((uintptr_t)scratch & 15) != 0) FFX_FAIL(FFX_ERR_ARG, "render_fwd_filtered: scratch is NULL or not 16-byte aligned");
-  return render_fwd_impl(bvh, info, sd, shape_albedo, tex, spp, seed, img_fp16 & (FFX_RENDER_FP16 | FFX_RENDER_APEX_READY), img, nullptr, s, nullptr, nullptr, nullptr,
-                         scratch);
+  return render_fwd_impl(bvh, info, sd, shape_albedo, tex, spp, seed, img_fp16 & (FFX_RENDER_FP16 | FFX_RENDER_APEX_READY | FFX_RENDER_PATH_MASK), img, nullptr, s, nullptr,
+                         nullptr, nullptr, scratch);
 }
 
 int ffx_render_fwd_adjoint_filtered(const void *bvh, const ffx_bvh_info *info, const ffx_scene_desc *sd, const float *shape_albedo, const float *tex, int spp,
@@ -4950,6 +5239,7 @@ int ffx_render_fwd_adjoint_filtered(const void *bvh, const ffx_bvh_info *info, c
   if (!gimg || !gtex) FFX_FAIL(FFX_ERR_ARG, "render_fwd_adjoint_filtered: gimg / gtex is NULL");
   if (!scratch || ((uintptr_t)scratch & 15) != 0) FFX_FAIL(FFX_ERR_ARG, "render_fwd_adjoint_filtered: scratch is NULL or not 16-byte aligned");
   if (sd && !sd->proj.enabled) FFX_FAIL(FFX_ERR_ARG, "render_fwd_adjoint_filtered: the scene has no projector (nothing to differentiate)");
+  FFX_NO_PATH(img_fp16, "render_fwd_adjoint_filtered");
   return render_fwd_impl(bvh, info, sd, shape_albedo, tex, spp, seed, img_fp16 & (FFX_RENDER_FP16 | FFX_RENDER_SPARSE_ADJOINT | FFX_RENDER_APEX_READY), img, nullptr, s, gimg,
                          gtex, nullptr, scratch);
 }
@@ -4964,6 +5254,7 @@ int ffx_render_fwd_cache_filtered(const void *bvh, const ffx_bvh_info *info, con
                                   uint32_t seed, int img_fp16, void *img, void *cache, void *scratch, ffx_stream s) {
   if (!cache || ((uintptr_t)cache & 15) != 0) FFX_FAIL(FFX_ERR_ARG, "render_fwd_cache_filtered: cache is NULL or not 16-byte aligned");
   if (!scratch || ((uintptr_t)scratch & 15) != 0) FFX_FAIL(FFX_ERR_ARG, "render_fwd_cache_filtered: scratch is NULL or not 16-byte aligned");
+  FFX_NO_PATH(img_fp16, "render_fwd_cache_filtered");
   return render_fwd_impl(bvh, info, sd, shape_albedo, tex, spp, seed,
                          img_fp16 & (FFX_RENDER_FP16 | FFX_RENDER_SPARSE_ADJOINT | FFX_RENDER_APEX_READY | FFX_RENDER_CACHE_ZEROED | FFX_RENDER_CACHE_KEEP_DROPPED), img, nullptr, s,
                          nullptr, nullptr, nullptr, scratch, cache);

@@ -163,8 +163,9 @@ class CacheOverflowError(RuntimeError):
 
 class _Render(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, tex, geom, sd, albedo, spp, seed, fp16):
+    def forward(ctx, tex, geom, sd, albedo, spp, seed, fp16, max_depth=2, rr_depth=5):
         ctx.geom, ctx.sd, ctx.spp, ctx.seed = geom, sd, spp, seed
+        ctx.depths = (max_depth, rr_depth)
         ctx.tex_shape = tex.shape
         t = _c(tex)
         if t.dim() == 2:
@@ -176,11 +177,11 @@ class _Render(torch.autograd.Function):
             # tensor in place on the next randomisation): keep a private copy (3 or 16 floats per shape) — unless the scene
             # description carries the rows itself (sd.n_mat_h: a value, already a snapshot)
             ctx.albedo = albedo.clone() if albedo is not None and sd.n_mat_h == 0 else None
-            if cache_supported(sd, spp):
+            if max_depth == 2 and cache_supported(sd, spp):  # (the path integrator's adjoint replays its paths: no cache)
                 # store a texture footprint per pixel now instead of re-tracing the scene in backward
                 ctx.cache = torch.empty(ops.render_cache_bytes_sd(sd, spp), dtype=torch.uint8, device=t.device)
         ctx.pose_version = geom.version
-        return geom.render_fwd(sd, albedo, t, spp, seed, fp16, cache=ctx.cache)
+        return geom.render_fwd(sd, albedo, t, spp, seed, fp16, cache=ctx.cache, max_depth=max_depth, rr_depth=rr_depth)
 
     @staticmethod
     def backward(ctx, g):
@@ -204,14 +205,20 @@ class _Render(torch.autograd.Function):
                     "uses the re-tracing adjoint (cache over FFX_CACHE_LIMIT_GB, texture > 4094^2 or > 255 shapes): call backward "
                     "before the next randomisation"
                 )
-            gtex = ctx.geom.render_bwd(ctx.sd, ctx.albedo, ctx.spp, ctx.seed, g)
-        return gtex.reshape(ctx.tex_shape), None, None, None, None, None, None
+            gtex = ctx.geom.render_bwd(ctx.sd, ctx.albedo, ctx.spp, ctx.seed, g, max_depth=ctx.depths[0], rr_depth=ctx.depths[1])
+        return gtex.reshape(ctx.tex_shape), None, None, None, None, None, None, None, None
 
 
-def render(tex, geom, sd, albedo, spp, seed=0, fp16=False):
+def render(tex, geom, sd, albedo, spp, seed=0, fp16=False, max_depth=2, rr_depth=5):
     """K8/K9: image [H,W,3], differentiable w.r.t. the projector texture ([h,w] or [h,w,c]).
     When the texture requires grad the forward kernel also stores each pixel's footprint in the texture
     (128 B per pixel + a small arena: 40 MB at 512x512x64; under a gaussian film an arena of per-sample records — 16 / 20 bytes per sample
     of the pixels that have a lit sample, room for every pixel up to 344 MB, a quarter of them beyond) and the adjoint scatters those footprints; beyond FFX_CACHE_LIMIT_GB the adjoint re-traces instead (then the geometry must not be re-fitted between
-    forward and backward)."""
-    return _Render.apply(tex, geom, sd, albedo, int(spp), int(seed), bool(fp16))
+    forward and backward).
+    max_depth > 2: Mitsuba's `path` integrator; no cache — the adjoint replays the forward's paths, so the geometry must not be
+    re-fitted between forward and backward."""
+    if max_depth != 2:
+        ops.path_flags(max_depth, rr_depth)  # (the range check before any launch)
+        if ops.deterministic_mode() and tex.requires_grad:
+            raise ValueError("render: max_depth > 2 has no deterministic adjoint (FFX_DETERMINISTIC=1)")
+    return _Render.apply(tex, geom, sd, albedo, int(spp), int(seed), bool(fp16), int(max_depth), int(rr_depth))

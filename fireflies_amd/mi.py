@@ -1141,11 +1141,49 @@ def traverse(scene: Scene) -> SceneParameters:
     return scene._params
 
 
-def render(scene: Scene, params: SceneParameters = None, spp: int = 16, seed: int = 0, sensor: int = 0, fp16: bool = False):
+class Integrator:
+    """what `mi.load_dict({"type": "path" | "direct", ...})` returns and `mi.render(..., integrator=)` / `PatternOptimizer(..., integrator=)` take:
+    Mitsuba's `path` with max_depth in 2 .. 8 (2: direct light at the primary hit, what every render without an integrator computes; k: k - 2
+    indirect bounces) and Russian roulette from depth rr_depth on (default 5), or `direct` (= max_depth 2).  DESIGN.md 4.4."""
+
+    def __init__(self, type_="path", max_depth=-1, rr_depth=5):
+        if type_ not in ("path", "direct"):
+            raise ValueError(f"integrator type {type_!r}: only 'path' and 'direct' are served")
+        if type_ == "direct":
+            max_depth = 2
+        ops.path_flags(max_depth, rr_depth)  # (ValueError outside 2 .. 8: Mitsuba's default -1, unbounded, included)
+        self.type, self.max_depth, self.rr_depth = type_, int(max_depth), int(rr_depth)
+
+    def __repr__(self):
+        return f"Integrator(type={self.type!r}, max_depth={self.max_depth}, rr_depth={self.rr_depth})"
+
+
+def load_dict(d: dict):
+    """mi.load_dict for integrator dictionaries: {"type": "path", "max_depth": k, "rr_depth": r} or {"type": "direct"} -> Integrator.
+    Scenes come from load_file / load_scene_data."""
+    if not isinstance(d, dict) or "type" not in d:
+        raise ValueError("load_dict: a dictionary with a 'type'")
+    t = d["type"]
+    if t not in ("path", "direct"):
+        raise NotImplementedError(f"load_dict: type {t!r} — only the integrators 'path' and 'direct' (scenes: mi.load_file / mi.load_scene_data)")
+    extra = set(d) - ({"type", "max_depth", "rr_depth"} if t == "path" else {"type"})
+    if extra:
+        raise ValueError(f"load_dict: {t!r} integrator properties {sorted(extra)} are not served")
+    if t == "direct":
+        return Integrator("direct")
+    return Integrator("path", d.get("max_depth", -1), d.get("rr_depth", 5))
+
+
+def render(scene: Scene, params: SceneParameters = None, spp: int = 16, seed: int = 0, sensor: int = 0, fp16: bool = False, integrator: Integrator = None):
     """mi.render(scene, spp=...) -> [H,W,3] (wrapped; `.torch()` as in examples/vocalfold_scene.py:14).
-    Differentiable w.r.t. `tex.data` when that parameter is a tensor that requires grad."""
+    Differentiable w.r.t. `tex.data` when that parameter is a tensor that requires grad.
+    integrator (mi.load_dict): None or max_depth 2 renders direct light at the primary hit, as always; deeper paths run on the caller's stream."""
     if sensor != 0:
         raise NotImplementedError("only sensor 0 renders; further sensors are projector proxies")
+    if integrator is not None and not isinstance(integrator, Integrator):
+        raise TypeError("render: integrator must come from mi.load_dict")
+    if integrator is not None and integrator.max_depth > 2:
+        return _render_path(scene, spp, seed, fp16, integrator)
     p = scene._params
     tex = tex_in = None
     ch = 3
@@ -1180,3 +1218,32 @@ def render(scene: Scene, params: SceneParameters = None, spp: int = 16, seed: in
         t = tex if tex.is_contiguous() else tex.contiguous()
         img = scene.geom.render_fwd(sd, mats, t.unsqueeze(-1) if t.dim() == 2 else t, int(spp), int(seed), bool(fp16))
     return TensorXf(img)
+
+
+def _render_path(scene, spp, seed, fp16, integrator):
+    """mi.render with max_depth > 2: the path integrator on the caller's stream (the live texture, the scene's material table)"""
+    p = scene._params
+    tex = None
+    ch = 3
+    if scene.data.projector is not None:
+        tex = p["tex.data"]
+        tex = tex.t if isinstance(tex, _ArrayBase) else tex
+        if not isinstance(tex, torch.Tensor):
+            tex = torch.as_tensor(np.asarray(tex, np.float32))
+        if tex.device != scene.device:
+            tex = tex.to(scene.device)
+        ch = 1 if tex.dim() == 2 else int(tex.shape[-1])
+    scene.note_spp(spp)
+    sd = scene.scene_desc(tex_channels=ch)
+    if tex is None:
+        tex = torch.zeros((1, 1, 1), device=scene.device)
+    elif tex.dtype != torch.float32:
+        tex = tex.float()
+    mats = scene.materials_arg(sd)
+    md, rr = integrator.max_depth, integrator.rr_depth
+    if tex.requires_grad and torch.is_grad_enabled():
+        scene.render_paths["autograd"] += 1
+        return TensorXf(Fn.render(tex, scene.geom, sd, mats, spp, seed, fp16, max_depth=md, rr_depth=rr))
+    scene.render_paths["caller_stream"] += 1
+    t = tex if tex.is_contiguous() else tex.contiguous()
+    return TensorXf(scene.geom.render_fwd(sd, mats, t.unsqueeze(-1) if t.dim() == 2 else t, int(spp), int(seed), bool(fp16), max_depth=md, rr_depth=rr))

@@ -521,6 +521,22 @@ def det_finish_(acc: torch.Tensor, scale_log2: int, gtex: torch.Tensor):
     return gtex
 
 
+def path_flags(max_depth=2, rr_depth=5):
+    """the flags bits (include/ffx.h FFX_RENDER_PATH) of a render with Mitsuba's `path` integrator at `max_depth` (2: direct light at the primary hit,
+    0 bits — the kernels of every other call; up to 8) with Russian roulette from vertex `rr_depth` on"""
+    if isinstance(max_depth, bool) or not isinstance(max_depth, (int, np.integer)) or not 2 <= int(max_depth) <= _abi.RENDER_MAX_DEPTH_LIMIT:
+        raise ValueError(f"max_depth must be an integer in 2 .. {_abi.RENDER_MAX_DEPTH_LIMIT} (-1, unbounded, is not served), got {max_depth!r}")
+    if isinstance(rr_depth, bool) or not isinstance(rr_depth, (int, np.integer)) or int(rr_depth) < 1:
+        raise ValueError(f"rr_depth must be a positive integer, got {rr_depth!r}")
+    return _abi.render_path(int(max_depth), min(int(rr_depth), 15))  # (a roulette from vertex 15 on never runs: max_depth <= 8)
+
+
+def _no_path(max_depth, what):
+    if max_depth != 2:
+        path_flags(max_depth)  # (the range check's message first)
+        raise ValueError(f"{what}: max_depth > 2 renders through render_fwd / render_bwd only (no adjoint cache, fused or deterministic adjoint)")
+
+
 def _lane_kernels():
     return os.environ.get("FFX_TRAVERSAL") == "lane"  # (the per-lane A/B kernels neither read nor write apex records)
 
@@ -910,14 +926,19 @@ class DeviceGeometry:
     def _timed(self, name):
         return _EventPair(self.timing, name)
 
-    def render_fwd(self, sd, albedo, tex, spp, seed=0, fp16=False, cache=None, sparse_adjoint=False, cache_zeroed=False, keep_dropped=False, img_out=None):
+    def render_fwd(self, sd, albedo, tex, spp, seed=0, fp16=False, cache=None, sparse_adjoint=False, cache_zeroed=False, keep_dropped=False, img_out=None,
+                   max_depth=2, rr_depth=5):
         """K8.  With `cache` (a uint8 tensor of render_cache_bytes(...) bytes) the kernel also stores one
         footprint of every pixel in the projector texture for render_bwd_cached (opaque layout, ffx.h).
         sparse_adjoint (with a cache): FFX_RENDER_SPARSE_ADJOINT — gradients are only wanted at texels whose value is
         not zero (a pattern optimiser's case), dark footprints are skipped.  cache_zeroed: FFX_RENDER_CACHE_ZEROED — the caller has
         cleared the first 64 bytes of `cache` on this stream.  keep_dropped: FFX_RENDER_CACHE_KEEP_DROPPED — the header's count of dropped
         samples survives this call's reset (the later scene samples of a step that reuses one cache).
-        A filtered film (sd.rfilter) with a cache: ffx_render_fwd_cache_filtered (per-sample records; render_bwd_cached needs the seed)."""
+        A filtered film (sd.rfilter) with a cache: ffx_render_fwd_cache_filtered (per-sample records; render_bwd_cached needs the seed).
+        max_depth > 2: Mitsuba's `path` integrator — no cache; its adjoint is render_bwd with the same max_depth / rr_depth / seed."""
+        path = path_flags(max_depth, rr_depth) if max_depth != 2 else 0
+        if path and cache is not None:
+            raise ValueError("render_fwd: max_depth > 2 has no adjoint cache (its adjoint is render_bwd with the same max_depth)")
         H, W = sd.cam.height, sd.cam.width
         self._last_spp = spp
         mats_arg = _check_materials(sd, albedo)
@@ -925,6 +946,8 @@ class DeviceGeometry:
         if tuple(img.shape) != (H, W, 3) or img.dtype != (torch.float16 if fp16 else torch.float32) or not img.is_contiguous():
             raise ValueError("img_out must be a contiguous [H, W, 3] tensor of the film's type")
         blob = self.blob  # (acquire first: the flag below speaks about the blob this call reads)
+        if path:
+            return self._render_path_fwd(blob, sd, mats_arg, tex, spp, seed, fp16, img, path)
         flags = int(bool(fp16)) | self._apex_flag(apex_key(sd))
         if sd.rfilter:  # a reconstruction filter that spreads samples over neighbouring pixels: its own entry point and a scratch area
             scratch = torch.empty(render_filter_bytes(sd), dtype=torch.uint8, device=self.device)  # (caching allocator, stream-ordered: renders on two streams never share one)
@@ -964,7 +987,22 @@ class DeviceGeometry:
         self._release()
         return img
 
-    def render_fwd_adjoint(self, sd, albedo, tex, spp, seed, gimg, out=None, dot_out=None, fp16=False, sparse_adjoint=False, img_out=None):
+    def _render_path_fwd(self, blob, sd, mats_arg, tex, spp, seed, fp16, img, path):
+        """the path integrator's forward (ffx_render_fwd[_filtered] with FFX_RENDER_PATH bits): per-lane walks that read neither apex records nor
+        tile bins — nothing is claimed about the blob's apex areas, and none is rewritten"""
+        tex_arg = _dev(tex, name="tex") if tex is not None else None
+        with self._timed("render_fwd"):
+            if sd.rfilter:
+                scratch = torch.empty(render_filter_bytes(sd), dtype=torch.uint8, device=self.device)
+                self._call("ffx_render_fwd_filtered", _dev(blob, torch.uint8), C.byref(self.info), C.byref(sd), mats_arg, tex_arg, int(spp), int(seed) & 0xFFFFFFFF,
+                           int(bool(fp16)) | path, _dev(img, img.dtype), _dev(scratch, torch.uint8), _stream(self._didx))
+            else:
+                self._call("ffx_render_fwd", _dev(blob, torch.uint8), C.byref(self.info), C.byref(sd), mats_arg, tex_arg, int(spp), int(seed) & 0xFFFFFFFF,
+                           int(bool(fp16)) | path, _dev(img, img.dtype), _stream(self._didx))
+        self._release()
+        return img
+
+    def render_fwd_adjoint(self, sd, albedo, tex, spp, seed, gimg, out=None, dot_out=None, fp16=False, sparse_adjoint=False, img_out=None, max_depth=2):
         """K8 with the adjoint folded in (ffx_render_fwd_adjoint): for a loss whose gradient `gimg` [H,W,3] does not depend on the image.
         -> (img, gtex): the render, and gtex (+)= its adjoint applied to gimg — `out`: accumulate into this [tex_h, tex_w, channels]
         tensor instead of a fresh zeroed one.  dot_out: _abi.ADJOINT_DOT_SLOTS float32 partial sums that <gimg, img> is added to."""
@@ -972,6 +1010,7 @@ class DeviceGeometry:
         if sd.rfilter and (dot_out is not None or sd.proj.tex_channels != 1 or sd.n_base_tex > 0):
             raise ValueError("render_fwd_adjoint with a reconstruction filter: 1-channel projector textures, no textured base colours, no dot_out "
                              "(the image forms behind the render launch) — box-filtered pixels are what the general call folds; use render_fwd + render_bwd")
+        _no_path(max_depth, "render_fwd_adjoint")
         mats_arg = _check_materials(sd, albedo)
         img = torch.empty((H, W, 3), dtype=torch.float16 if fp16 else torch.float32, device=self.device) if img_out is None else img_out
         if tuple(img.shape) != (H, W, 3) or img.dtype != (torch.float16 if fp16 else torch.float32):
@@ -997,11 +1036,12 @@ class DeviceGeometry:
         self._release()
         return img, gtex
 
-    def render_bwd_cached(self, sd, albedo, cache, spp, gimg, out=None, img=None, dot_out=None, seed=None):
+    def render_bwd_cached(self, sd, albedo, cache, spp, gimg, out=None, img=None, dot_out=None, seed=None, max_depth=2):
         """K9 from the adjoint cache written by render_fwd(..., cache=...): scatters per-pixel footprints, no BVH.
         `out`: accumulate into this [tex_h, tex_w, channels] tensor instead of a fresh zeroed one.
         `img` + `dot_out` (render_dot_slots(W, H) float32 partial sums, one per 8x8-pixel block): the same launch adds
         <gimg, img> to them — their sum is the value of a loss that is linear in the image, whose gradient gimg is."""
+        _no_path(max_depth, "render_bwd_cached")
         gtex = torch.zeros((sd.proj.tex_h, sd.proj.tex_w, sd.proj.tex_channels), dtype=torch.float32, device=self.device) if out is None else out
         mats_arg = _check_materials(sd, albedo)
         if (img is None) != (dot_out is None):
@@ -1037,11 +1077,12 @@ class DeviceGeometry:
                                float(weight), _dev(out), _dev(loss_slots), _stream(self._didx), allow=(_abi.FFX_ERR_UNSUPPORTED,))
         return out if rc == 0 else None
 
-    def render_bwd_det_part(self, sd, albedo, spp, seed, gimg, part, acc, scale_log2=0):
+    def render_bwd_det_part(self, sd, albedo, spp, seed, gimg, part, acc, scale_log2=0, max_depth=2):
         """ONE pass of the deterministic re-tracing adjoint (ffx_render_bwd_det_part): part 1 — the largest |tap| of this render into the int32
         word `acc` (the float's bits; maximum over calls); part 2 — every tap as a 64-bit fixed-point integer at 2^scale_log2 into the int64
         tensor `acc` [tex_h, tex_w, channels] (sum over calls).  The caller clears `acc`, reduces it over samples and ranks, and converts
         (det_scale_log2, det_finish_): sums that come out bitwise equal whatever the order or the number of ranks."""
+        _no_path(max_depth, "render_bwd_det_part")
         if _lane_kernels():
             raise ValueError("the per-lane kernels (FFX_TRAVERSAL=lane) have no deterministic adjoint")
         want = torch.int32 if part == 1 else torch.int64
@@ -1057,14 +1098,29 @@ class DeviceGeometry:
                        _stream(self._didx))
         self._release()
 
-    def render_bwd(self, sd, albedo, spp, seed, gimg, deterministic=None):
+    def render_bwd(self, sd, albedo, spp, seed, gimg, deterministic=None, max_depth=2, rr_depth=5):
         """the re-tracing adjoint.  deterministic (default: FFX_DETERMINISTIC=1 in the environment): ffx_render_bwd_det — bitwise
-        reproducible accumulation (64-bit fixed point instead of float atomics; two re-traces and one host synchronisation)."""
+        reproducible accumulation (64-bit fixed point instead of float atomics; two re-traces and one host synchronisation).
+        max_depth > 2: the path integrator's adjoint — replays render_fwd's paths of the same max_depth, rr_depth, spp and seed (float atomics only)."""
+        path = path_flags(max_depth, rr_depth) if max_depth != 2 else 0
+        if deterministic is None:
+            deterministic = deterministic_mode()
+        if path and deterministic:
+            raise ValueError("render_bwd: max_depth > 2 has no deterministic adjoint (FFX_DETERMINISTIC / deterministic=True)")
         gtex = torch.zeros((sd.proj.tex_h, sd.proj.tex_w, sd.proj.tex_channels), dtype=torch.float32, device=self.device)
         mats_arg = _check_materials(sd, albedo)
         blob = self.blob
-        if deterministic is None:
-            deterministic = deterministic_mode()
+        if path:  # (per-lane walks: no apex records are read or written)
+            scratch = torch.empty(render_filter_bytes(sd), dtype=torch.uint8, device=self.device) if sd.rfilter else None
+            with self._timed("render_bwd"):
+                if scratch is not None:
+                    self._call("ffx_render_bwd_filtered", _dev(blob, torch.uint8), C.byref(self.info), C.byref(sd), mats_arg, int(spp), int(seed) & 0xFFFFFFFF, path,
+                               _dev(gimg, name="gimg"), _dev(gtex), _dev(scratch, torch.uint8), _stream(self._didx))
+                else:
+                    self._call("ffx_render_bwd", _dev(blob, torch.uint8), C.byref(self.info), C.byref(sd), mats_arg, int(spp), int(seed) & 0xFFFFFFFF, path,
+                               _dev(gimg, name="gimg"), _dev(gtex), _stream(self._didx))
+            self._release()
+            return gtex
         if deterministic:
             if _lane_kernels():
                 raise ValueError("the per-lane kernels (FFX_TRAVERSAL=lane) have no deterministic adjoint")

@@ -99,8 +99,12 @@ def image_l1_loss(target):
 
 class PatternOptimizer:
     def __init__(self, mi_scene, ff_scene, laser, sigma=10.0, tex_size=(500, 500), spp=64, lr=1e-3, reg_weight=0.1, samples_per_step=1,
-                 base_seed=0, loss_fn=coverage_loss, blur=(5, 3.0)):
+                 base_seed=0, loss_fn=coverage_loss, blur=(5, 3.0), integrator=None):
         self.mi_scene, self.ff_scene, self.laser = mi_scene, ff_scene, laser
+        # mi.load_dict's integrator: max_depth > 2 renders paths; its adjoint replays them (the "retrace" route)
+        self.max_depth, self.rr_depth = (2, 5) if integrator is None else (int(integrator.max_depth), int(integrator.rr_depth))
+        if self.max_depth > 2 and ops.deterministic_mode():
+            raise ValueError("PatternOptimizer: max_depth > 2 has no deterministic adjoint (FFX_DETERMINISTIC=1)")
         self.sigma, self.tex_size, self.spp = float(sigma), (int(tex_size[0]), int(tex_size[1])), int(spp)
         mi_scene.note_spp(self.spp)  # (the pre-pass of the poses to come: with or without the emitters' envelopes, mi.Scene.note_spp)
         self.reg_weight, self.samples_per_step, self.base_seed = float(reg_weight), int(samples_per_step), int(base_seed)
@@ -150,7 +154,7 @@ class PatternOptimizer:
         self.ff_scene.randomize()
         leaf = tex_value.detach().clone().requires_grad_(True)
         sd = self.mi_scene.scene_desc(tex_channels=1)
-        img = Fn.render(leaf, self.mi_scene.geom, sd, self.mi_scene.materials_arg(sd), self.spp, seed)
+        img = Fn.render(leaf, self.mi_scene.geom, sd, self.mi_scene.materials_arg(sd), self.spp, seed, max_depth=self.max_depth, rr_depth=self.rr_depth)
         loss = self.loss_fn(img)
         (g,) = torch.autograd.grad(loss, leaf)
         return g, loss.detach()
@@ -251,7 +255,11 @@ class PatternOptimizer:
         - "fused": a loss linear in the image — forward and adjoint in ONE launch (ffx_render_fwd_adjoint[_filtered]), no cache, no K9;
         - "lin_rf": the same loss under a filtered film — the filtered forward stores its per-sample records, K9 applies the constant gradient to them;
         - "cache": any other loss — cache-writing forward + K9 (its linear / L1 / general sub-cases: _samples_cached);
-        - "retrace": no cache possible — forward, the loss's gradient image, ffx_render_bwd."""
+        - "retrace": no cache possible — forward, the loss's gradient image, ffx_render_bwd (always with max_depth > 2: the replay of the paths)."""
+        if self.max_depth > 2:
+            if ops.deterministic_mode():
+                raise ValueError("PatternOptimizer.step: max_depth > 2 has no deterministic adjoint (FFX_DETERMINISTIC=1)")
+            return "retrace"
         if ops.deterministic_mode() and sd0.proj.enabled:
             return "det"
         # a linear loss: <gimg, img> is evaluated in the gradient launch from the step's renders (the fused launch's own partial sums would cost more)
@@ -404,10 +412,11 @@ class PatternOptimizer:
             apply_sample()
             sd = ms.scene_desc(tex_channels=1)
             mats = ms.materials_arg(sd)
-            img = geom.render_fwd(sd, mats, tex3, self.spp, seed, False, cache=None, sparse_adjoint=False, cache_zeroed=k == 0, keep_dropped=k != 0)
+            img = geom.render_fwd(sd, mats, tex3, self.spp, seed, False, cache=None, sparse_adjoint=False, cache_zeroed=k == 0, keep_dropped=k != 0,
+                                  max_depth=self.max_depth, rr_depth=self.rr_depth)
             self.step_paths["retrace"] += 1
             gimg = self._image_loss(img, loss_sum)
-            gtex += geom.render_bwd(sd, mats, self.spp, seed, gimg).reshape(gtex.shape)
+            gtex += geom.render_bwd(sd, mats, self.spp, seed, gimg, max_depth=self.max_depth, rr_depth=self.rr_depth).reshape(gtex.shape)
 
     def _pattern_bwd_args(self):
         """rays, KF, texture size, the pattern launch's buffers, blur taps and regulariser weight of the gradient launches"""

@@ -93,7 +93,7 @@
 extern "C" {
 #endif
 
-#define FFX_ABI_VERSION 10
+#define FFX_ABI_VERSION 11
 #define FFX_MAX_LEVELS 96
 
 typedef void *ffx_stream; /* hipStream_t */
@@ -752,6 +752,17 @@ int ffx_det_finish(const void *acc /*[dev] int64 [n]*/, int scale_log2, size_t n
                                        other, then finds at its end whether ANY of them overflowed (ffx_adam_args.guard, ffx_render_cache_status):
                                        the first sample of the step clears the word (FFX_RENDER_CACHE_ZEROED or a plain call), the others keep it.
                                        The oracle ignores the bit (its cache never drops). */
+/* The path integrator (ABI 11): bits 8..11 and 12..15 of the flags word of ffx_render_fwd, ffx_render_fwd_filtered (img_fp16),
+ * ffx_render_bwd and ffx_render_bwd_filtered (flags) carry Mitsuba's `path` max_depth and rr_depth.  max_depth 0 (the field unset) or 2: direct
+ * light at the primary hit, the kernels of every earlier version; 3 .. FFX_RENDER_MAX_DEPTH_LIMIT: max_depth - 2 cosine-weighted bounces with
+ * next-event estimation at every vertex, Russian roulette from vertex rr_depth on (0: 5); any other value: FFX_ERR_ARG.  The adjoint replays the
+ * forward's paths: pass the same flags, seed and spp to both.  Every other render entry point answers FFX_ERR_UNSUPPORTED when these bits are set.
+ * The oracle ignores the bits (it renders direct light only). */
+#define FFX_RENDER_MAX_DEPTH_SHIFT 8
+#define FFX_RENDER_RR_DEPTH_SHIFT 12
+#define FFX_RENDER_PATH_MASK 0xff00
+#define FFX_RENDER_MAX_DEPTH_LIMIT 8
+#define FFX_RENDER_PATH(max_depth, rr_depth) ((((max_depth) & 15) << FFX_RENDER_MAX_DEPTH_SHIFT) | (((rr_depth) & 15) << FFX_RENDER_RR_DEPTH_SHIFT))
 /* Writes the apex records (the triangles as seen from a fixed ray origin) of sd's camera and enabled emitters into
  * the blob's apex areas — what every packet render does in front of its kernel unless told FFX_RENDER_APEX_READY.  Only
  * sd->cam.to_world, sd->proj.{enabled,to_world} and sd->spot.{enabled,to_world} are read.  No reference counterpart (Mitsuba
