@@ -186,6 +186,15 @@ def render_path(max_depth, rr_depth):
     return 0 if max_depth == 2 else ((max_depth & 15) << RENDER_MAX_DEPTH_SHIFT) | ((rr_depth & 15) << RENDER_RR_DEPTH_SHIFT)
 
 
+# the appearance adjoint's bit in the flags word of ffx_render_bwd[_filtered] (ABI 11, include/ffx.h FFX_RENDER_GRAD_APPEARANCE)
+RENDER_GRAD_APPEARANCE = 0x10000
+
+
+def appearance_floats(n_shapes, base_tex_hw=()):
+    """FFX_RENDER_APPEARANCE_FLOATS: the floats of the appearance block behind gtex — [n_shapes][3] rows, [3] spot, [h][w][3] per base-colour texture"""
+    return 3 * int(n_shapes) + 3 + 3 * sum(int(h) * int(w) for h, w in base_tex_hw)
+
+
 MAX_BASE_TEX = 4
 RFILTER_BOX, RFILTER_GAUSSIAN = 0, 1
 MAX_MAT_H = 128

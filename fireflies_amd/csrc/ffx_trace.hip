@@ -462,13 +462,17 @@ __device__ __forceinline__ float ggx1_cc(float c, float c_dot_h) { // smith_ggx1
 // the lobes, one after the other, each reading the material values it needs from the row when it needs them (the row is
 // 64 bytes in the vector L1; holding all of it plus the directions in registers cost the kernel two waves of occupancy)
 // TEX: the base colour is (b0, b1, b2) — the row's texture sampled at the hit — instead of the row's own m[0..2]
-template <bool TEX = false>
-__device__ __forceinline__ void material_terms(const float *__restrict__ m, const MatGeo &g, float &A, float &B, float b0 = 0.f, float b1 = 0.f, float b2 = 0.f) {
+// TAU (the appearance adjoint): *tau receives pi tau, the numerators of the tint terms that A divides by lum (A = A0 + pi tau / lum;
+// 0 when lum <= 0, where the tints went to B)
+template <bool TEX = false, bool TAU = false>
+__device__ __forceinline__ void material_terms(const float *__restrict__ m, const MatGeo &g, float &A, float &B, float b0 = 0.f, float b1 = 0.f, float b2 = 0.f,
+                                               float *tau = nullptr) {
   const float cos_i = g.cos_i, cos_o = g.cos_o, ch = g.ch, ci_h = g.ci_h, co_h = g.co_h;
   A = 0.f; B = 0.f;
+  if (TAU) *tau = 0.f;
   if (!(cos_i > 0.f && cos_o > 0.f)) return;
   const bool facing = ci_h > 0.f && co_h > 0.f; // (cos_i, cos_o > 0)
-  float a = 0.f, b = 0.f;
+  float a = 0.f, b = 0.f, tu = 0.f;
   const float eta = m[FFX_MAT_ETA];
   const float ct2 = 1.0f - (1.0f - ci_h * ci_h) * sqrf(brcp(eta));
   const float ct = ct2 > 0.f ? bsqrt(ct2) : 0.f; // cosine of the transmitted direction
@@ -494,7 +498,7 @@ __device__ __forceinline__ void material_terms(const float *__restrict__ m, cons
     if (spec_tint != 0.f) {
       const float lum = TEX ? 0.212671f * b0 + 0.715160f * b1 + 0.072169f * b2 : 0.212671f * m[0] + 0.715160f * m[1] + 0.072169f * m[2];
       const float t = m1 * spec_tint * sqrf((eta - 1.0f) * brcp(eta + 1.0f)) * (1.0f - sw);
-      if (lum > 0.f) Fa += bdiv(t, lum);
+      if (lum > 0.f) { Fa += bdiv(t, lum); if (TAU) tu += t * common; }
       else Fb += t;
     }
     a += Fa * common;
@@ -529,11 +533,12 @@ __device__ __forceinline__ void material_terms(const float *__restrict__ m, cons
   if (sheen > 0.f && 1.0f - metallic > 0.f) {
     const float sv = sheen * (1.0f - metallic) * schlick_weight(fabsf(co_h)) * cos_o;
     const float lum = TEX ? 0.212671f * b0 + 0.715160f * b1 + 0.072169f * b2 : 0.212671f * m[0] + 0.715160f * m[1] + 0.072169f * m[2], sheen_tint = m[FFX_MAT_SHEEN_TINT];
-    if (lum > 0.f) { a += bdiv(sv * sheen_tint, lum); b += sv * (1.0f - sheen_tint); }
+    if (lum > 0.f) { a += bdiv(sv * sheen_tint, lum); b += sv * (1.0f - sheen_tint); if (TAU) tu += sv * sheen_tint; }
     else b += sv;
   }
   A = a * FFX_PI_F;
   B = b * FFX_PI_F;
+  if (TAU) *tau = tu * FFX_PI_F;
 }
 
 // ---- the same two functions on a row whose constants the host has derived once (ShadeK.mat_pre, FFX_PRE_FLOATS floats per row): no squares, clamps
@@ -660,15 +665,19 @@ __device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? l
 // what a path vertex needs beyond the emitters' terms: the lifted origin of its secondary ray, its normals, whether the row's base
 // colour came from a texture.  ok = 0: no vertex (a miss, a degenerate triangle)
 struct PathVtx { v3 Po, ng, ns; int textured, ok; };
+// what the appearance adjoint needs beyond the emitters' terms: the tint parts pi tau of both emitters' factors (proj_t scales like
+// proj_fac, spot_t like s_f), the spot's factors at unit intensity (spot = s_int s_f, spot_b = s_int s_fb), and where a textured base colour was read
+struct AppTerms { float proj_t, spot_t, s_f, s_fb; int tix, slot; float bu, bv; };
 
 // the sample's hit in (nt, ft] and next-event estimation there: projector and spot terms, shadow rays, base colour.  PATH (the path kernels):
-// the ray has an arbitrary origin (no apex form) and *pv receives the vertex
-template <bool PATH = false>
+// the ray has an arbitrary origin (no apex form) and *pv receives the vertex.  APP (k_render_bwd_appearance): *ap receives AppTerms
+template <bool PATH = false, bool APP = false>
 __device__ __forceinline__ void shade_sample(const ShadeK &c, const BvhNode *__restrict__ nodes, const TriRec *__restrict__ recs, const float4 *__restrict__ nrec, v3 o,
-                                             v3 d, float nt, float ft, SampleTerms &st, int *stack, int stride, PathVtx *pv = nullptr) {
+                                             v3 d, float nt, float ft, SampleTerms &st, int *stack, int stride, PathVtx *pv = nullptr, AppTerms *ap = nullptr) {
   Hit h;
   st.hit = traverse<false, !PATH>(nodes, recs, o, d, nt, ft, h, stack, stride);
   if (PATH) pv->ok = 0;
+  if (APP) { ap->proj_t = ap->spot_t = ap->s_f = ap->s_fb = 0.f; ap->tix = 0; }
   st.has_proj = 0;
   st.proj_fac = 0.f; st.proj_fac_b = 0.f;
   st.spot[0] = st.spot[1] = st.spot[2] = 0.f;
@@ -702,6 +711,7 @@ __device__ __forceinline__ void shade_sample(const ShadeK &c, const BvhNode *__r
       hit_barycentrics<false>(ra, rb, rc, o, d, bu, bv);
       base_tex_sample(c, tix - 1, h.slot, bu, bv, st.base);
       textured = true;
+      if (APP) { ap->tix = tix; ap->slot = h.slot; ap->bu = bu; ap->bv = bv; }
     }
   }
   if (PATH) { pv->Po = Po; pv->ng = ng; pv->ns = ns; pv->textured = textured ? 1 : 0; pv->ok = 1; }
@@ -730,16 +740,17 @@ __device__ __forceinline__ void shade_sample(const ShadeK &c, const BvhNode *__r
             vis = !traverse<true, true>(nodes, recs, ppos, vsub(Po, ppos), 0.f, 1.0f - SHADOW_EPS, hs, stack, stride);
           }
           if (vis) {
-            float bA = cos_s, bB = 0.f; // Lambert; material rows: pi f cos = base_color * bA + bB
+            float bA = cos_s, bB = 0.f, bT = 0.f; // Lambert; material rows: pi f cos = base_color * bA + bB
             if (c.mat_stride == FFX_MAT_STRIDE && mt[(size_t)FFX_MAT_STRIDE * h.shape + FFX_MAT_MODEL] != 0.f) {
               const float *mrow = mt + (size_t)FFX_MAT_STRIDE * h.shape;
               MatGeo mg;
               material_geometry(mrow, ns, V3(-d.x, -d.y, -d.z), wi, mg);
-              if (textured) material_terms<true>(mrow, mg, bA, bB, st.base[0], st.base[1], st.base[2]);
-              else material_terms(mrow, mg, bA, bB);
+              if (textured) material_terms<true, APP>(mrow, mg, bA, bB, st.base[0], st.base[1], st.base[2], &bT);
+              else material_terms<false, APP>(mrow, mg, bA, bB, 0.f, 0.f, 0.f, &bT);
             }
             st.proj_fac = (c.p_scale / (pl.z * pl.z * cos_p)) * bA;
             st.proj_fac_b = (c.p_scale / (pl.z * pl.z * cos_p)) * bB;
+            if (APP) ap->proj_t = (c.p_scale / (pl.z * pl.z * cos_p)) * bT;
             float fx = fmaf(u, (float)c.tw, -0.5f), fy = fmaf(v, (float)c.th, -0.5f);
             float x0 = floorf(fx), y0 = floorf(fy);
             float ax = fx - x0, ay = fy - y0;
@@ -778,15 +789,16 @@ __device__ __forceinline__ void shade_sample(const ShadeK &c, const BvhNode *__r
           vis = !traverse<true, true>(nodes, recs, spos, vsub(Po, spos), 0.f, 1.0f - SHADOW_EPS, hs, stack, stride);
         }
         if (vis) {
-          float bA = cos_s, bB = 0.f;
+          float bA = cos_s, bB = 0.f, bT = 0.f;
           if (c.mat_stride == FFX_MAT_STRIDE && mt[(size_t)FFX_MAT_STRIDE * h.shape + FFX_MAT_MODEL] != 0.f) {
             const float *mrow = mt + (size_t)FFX_MAT_STRIDE * h.shape;
             MatGeo mg;
             material_geometry(mrow, ns, V3(-d.x, -d.y, -d.z), wi, mg);
-            if (textured) material_terms<true>(mrow, mg, bA, bB, st.base[0], st.base[1], st.base[2]);
-            else material_terms(mrow, mg, bA, bB);
+            if (textured) material_terms<true, APP>(mrow, mg, bA, bB, st.base[0], st.base[1], st.base[2], &bT);
+            else material_terms<false, APP>(mrow, mg, bA, bB, 0.f, 0.f, 0.f, &bT);
           }
           float f = fall * bA / d2 * 0.3183098861837907f, fb = fall * bB / d2 * 0.3183098861837907f;
+          if (APP) { ap->s_f = f; ap->s_fb = fb; ap->spot_t = fall * bT / d2 * 0.3183098861837907f; }
           st.spot[0] = c.s_int[0] * f;
           st.spot[1] = c.s_int[1] * f;
           st.spot[2] = c.s_int[2] * f;
@@ -4195,6 +4207,146 @@ __global__ void __launch_bounds__(64)
   }
 }
 
+// ------------------------------------------------------------------------------------------ appearance adjoint
+// FFX_RENDER_GRAD_APPEARANCE (include/ffx.h): d loss / d (the rows' base colours, the spot's intensity, base-colour textures) at max_depth 2.  Per sample
+// and channel L_c = b_c E_c + F_c with E_c = spot_c + tex_c proj_fac (the parts scaled by the base colour b, the tint terms pi tau / lum(b) included)
+// and F_c their b-free parts.  With T_c the tint parts' numerators (s_int_c spot_t + tex_c proj_t) and the sample's adjoint weight q_c:
+//   d/db_k sum_c q_c L_c = q_k E_k - (sum_c q_c b_c T_c) w_k / lum^2        (w = the luminance weights; T = 0 where lum <= 0)
+//   d/dI_c              = q_c (b_c s_f + s_fb)                              (the spot's factors at unit intensity)
+// Samples replay the forward's (same jitter and seed) with shade_sample's per-lane walk.  One wave = one pixel at a time, a workgroup of four waves
+// strides over the film; row sums go through LDS (one global atomic per non-zero entry and workgroup), the spot's through a wave sum (one atomic per
+// wave), a textured base colour's through its four bilinear taps (global atomics).
+#define FFX_APP_WAVES 4
+#define FFX_APP_LDS_ROWS 255
+static_assert(64 * FFX_APP_WAVES == TR_BLOCK, "k_render_bwd_appearance takes the per-lane kernels' traversal stack (stack_bytes)");
+struct AppArgs {
+  const BvhNode *nodes; const TriRec *recs; const float4 *nrec;
+  const float *tex; // the projector texture [tex_h, tex_w, tex_channels] (NULL without a projector)
+  int spp, n_pix, n_shapes;
+  uint32_t seed_key;
+  float *grow, *gspot, *gbt[FFX_MAX_BASE_TEX]; // [n_shapes][3], [3], [h][w][3] per base-colour texture
+};
+// the four texels (float offsets) and weights of base_tex_sample's bilinear lookup, by the same arithmetic
+__device__ __forceinline__ void base_tex_taps(const ShadeK &c, int k, int slot, float bu, float bv, size_t (&o)[4], float (&w)[4]) {
+  const float *uv = c.slot_uv + 6 * (size_t)slot;
+  const float bw = (1.0f - bu) - bv;
+  float u = fmaf(bw, uv[0], fmaf(bu, uv[2], bv * uv[4])), v = fmaf(bw, uv[1], fmaf(bu, uv[3], bv * uv[5]));
+  u = u - floorf(u);
+  v = v - floorf(v);
+  const int tw = c.btw[k], th = c.bth[k];
+  const float fx = fmaf(u, (float)tw, -0.5f), fy = fmaf(v, (float)th, -0.5f);
+  const float x0f = floorf(fx), y0f = floorf(fy);
+  const float ax = fx - x0f, ay = fy - y0f;
+  int x0 = (int)x0f, y0 = (int)y0f, x1 = x0 + 1, y1 = y0 + 1;
+  x0 = x0 < 0 ? x0 + tw : x0; x1 = x1 >= tw ? x1 - tw : x1; y0 = y0 < 0 ? y0 + th : y0; y1 = y1 >= th ? y1 - th : y1;
+  x0 = x0 >= tw ? x0 - tw : x0; y0 = y0 >= th ? y0 - th : y0; x1 = x1 < 0 ? x1 + tw : x1; y1 = y1 < 0 ? y1 + th : y1;
+  o[0] = ((size_t)y0 * tw + x0) * 3; o[1] = ((size_t)y0 * tw + x1) * 3; o[2] = ((size_t)y1 * tw + x0) * 3; o[3] = ((size_t)y1 * tw + x1) * 3;
+  w[0] = (1.0f - ay) * (1.0f - ax); w[1] = (1.0f - ay) * ax; w[2] = ay * (1.0f - ax); w[3] = ay * ax;
+}
+// RF: gsrc is G = gimg / weight as float4 per pixel (k_rf_gather) and a sample's weight is sum_n w_n G[p + n]; else gsrc = gimg, weight gimg / spp
+template <bool RF>
+__global__ void __launch_bounds__(64 * FFX_APP_WAVES)
+    k_render_bwd_appearance(ShadeK c, AppArgs a, const float *__restrict__ gsrc) {
+  extern __shared__ int s_dyn[];
+  __shared__ float s_rows[FFX_APP_LDS_ROWS * 3];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const bool lds = a.n_shapes <= FFX_APP_LDS_ROWS;
+  if (lds)
+    for (int i = threadIdx.x; i < a.n_shapes * 3; i += 64 * FFX_APP_WAVES) s_rows[i] = 0.f;
+  __syncthreads();
+  const int W = c.cam.W, H = c.cam.H;
+  const float wl[3] = {0.212671f, 0.715160f, 0.072169f};
+  float gs[3] = {0.f, 0.f, 0.f}; // this lane's share of d loss / d spot intensity
+  for (long pl = (long)blockIdx.x * FFX_APP_WAVES + wave; pl < a.n_pix; pl += (long)gridDim.x * FFX_APP_WAVES) { // (wave-uniform)
+    const uint32_t pix = (uint32_t)pl;
+    const int px = (int)(pix % (uint32_t)W), py = (int)(pix / (uint32_t)W);
+    float g0, g1, g2; // box: the pixel's gradient / spp; RF: lanes 0..24 hold G of window pixel `lane`
+    if (RF) {
+      const float4 gw = rf_window_g(reinterpret_cast<const float4 *>(gsrc), px, py, W, H, lane, true);
+      g0 = gw.x; g1 = gw.y; g2 = gw.z;
+      if (wballot(g0 != 0.f || g1 != 0.f || g2 != 0.f) == 0ull) continue;
+    } else {
+      const float inv_spp = 1.0f / (float)a.spp;
+      g0 = gsrc[(size_t)pix * 3] * inv_spp; g1 = gsrc[(size_t)pix * 3 + 1] * inv_spp; g2 = gsrc[(size_t)pix * 3 + 2] * inv_spp;
+      if (g0 == 0.f && g1 == 0.f && g2 == 0.f) continue;
+    }
+    for (int pass = 0; pass < (a.spp + 63) >> 6; ++pass) {
+      const int s = pass * 64 + lane;
+      const uint32_t idx = pix * (uint32_t)a.spp + (uint32_t)s;
+      float jx, jy;
+      sample_jitter(a.seed_key, idx, jx, jy);
+      float q[3] = {g0, g1, g2};
+      if (RF) { // (all lanes: the readlanes need the whole wave)
+        float gx[5], gy[5];
+        rf_weights(c.rf, jx, gx);
+        rf_weights(c.rf, jy, gy);
+        q[0] = q[1] = q[2] = 0.f;
+#pragma unroll
+        for (int n = 0; n < 25; ++n) {
+          const float w = gx[n % 5] * gy[n / 5];
+          q[0] = __builtin_fmaf(w, __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(g0), n)), q[0]);
+          q[1] = __builtin_fmaf(w, __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(g1), n)), q[1]);
+          q[2] = __builtin_fmaf(w, __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(g2), n)), q[2]);
+        }
+      }
+      if (s >= a.spp || (q[0] == 0.f && q[1] == 0.f && q[2] == 0.f)) continue;
+      v3 o, d;
+      float nt, ft;
+      cam_ray(c.cam, ((float)px + jx) * c.cam.inv_w, ((float)py + jy) * c.cam.inv_h, o, d, nt, ft);
+      SampleTerms st;
+      AppTerms ap;
+      shade_sample<false, true>(kernarg_shade(), a.nodes, a.recs, a.nrec, o, d, nt, ft, st, s_dyn + threadIdx.x, 64 * FFX_APP_WAVES, nullptr, &ap);
+      if (!st.hit) continue;
+      const ShadeK &k = kernarg_shade();
+      float tv[3] = {0.f, 0.f, 0.f};
+      if (st.has_proj) path_tex(k, st, a.tex, tv);
+      float E[3], qbt = 0.f;
+#pragma unroll
+      for (int ch = 0; ch < 3; ++ch) {
+        E[ch] = st.spot[ch] + tv[ch] * st.proj_fac;
+        qbt += q[ch] * st.base[ch] * (k.s_int[ch] * ap.spot_t + tv[ch] * ap.proj_t);
+        gs[ch] += q[ch] * (st.base[ch] * ap.s_f + ap.s_fb);
+      }
+      const float lum = wl[0] * st.base[0] + wl[1] * st.base[1] + wl[2] * st.base[2];
+      const float r = lum > 0.f ? qbt / (lum * lum) : 0.f;
+      float gb[3];
+#pragma unroll
+      for (int ch = 0; ch < 3; ++ch) gb[ch] = q[ch] * E[ch] - r * wl[ch];
+      if (gb[0] == 0.f && gb[1] == 0.f && gb[2] == 0.f) continue;
+      if (ap.tix == 0) { // the row's own base colour
+        if (lds) {
+#pragma unroll
+          for (int ch = 0; ch < 3; ++ch) atomicAdd(&s_rows[st.shape * 3 + ch], gb[ch]);
+        } else {
+#pragma unroll
+          for (int ch = 0; ch < 3; ++ch) atomicAdd(a.grow + (size_t)st.shape * 3 + ch, gb[ch]);
+        }
+      } else { // a base-colour texture: through the lookup's four taps
+        float *gt = ap.tix == 1 ? a.gbt[0] : ap.tix == 2 ? a.gbt[1] : ap.tix == 3 ? a.gbt[2] : a.gbt[3];
+        size_t to[4];
+        float tw4[4];
+        base_tex_taps(k, ap.tix - 1, ap.slot, ap.bu, ap.bv, to, tw4);
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+#pragma unroll
+          for (int ch = 0; ch < 3; ++ch) atomicAdd(gt + to[t] + ch, gb[ch] * tw4[t]);
+        }
+      }
+    }
+  }
+#pragma unroll
+  for (int ch = 0; ch < 3; ++ch) {
+    const float v = wave_sum_tree(gs[ch]);
+    if (lane == 0 && v != 0.f) atomicAdd(a.gspot + ch, v);
+  }
+  __syncthreads();
+  if (lds)
+    for (int i = threadIdx.x; i < a.n_shapes * 3; i += 64 * FFX_APP_WAVES) {
+      const float v = s_rows[i];
+      if (v != 0.f) atomicAdd(a.grow + i, v);
+    }
+}
+
 // ------------------------------------------------------------------------------------------ host side
 static int cam_prepare(const ffx_camera *c, CamK &k) {
   if (c->width < 1 || c->height < 1) return 0;
@@ -4901,8 +5053,12 @@ static int render_fwd_impl(const void *bvh, const ffx_bvh_info *info, const ffx_
   return FFX_OK;
 }
 
+// the appearance adjoint's bit belongs to ffx_render_bwd[_filtered]: every other render entry point refuses it
+#define FFX_NO_APPEARANCE(flags_, what_) \
+  do { if ((flags_) & FFX_RENDER_GRAD_APPEARANCE) FFX_FAIL(FFX_ERR_UNSUPPORTED, "%s: FFX_RENDER_GRAD_APPEARANCE is served by ffx_render_bwd[_filtered] only", what_); } while (0)
 int ffx_render_fwd(const void *bvh, const ffx_bvh_info *info, const ffx_scene_desc *sd, const float *shape_albedo, const float *tex, int spp,
                    uint32_t seed, int img_fp16, void *img, ffx_stream s) {
+  FFX_NO_APPEARANCE(img_fp16, "render_fwd");
   return render_fwd_impl(bvh, info, sd, shape_albedo, tex, spp, seed, img_fp16 & (FFX_RENDER_FP16 | FFX_RENDER_APEX_READY | FFX_RENDER_PATH_MASK), img, nullptr, s);
 }
 // the entry points without the path integrator refuse its bits rather than render direct light only
@@ -4927,6 +5083,7 @@ int ffx_render_fwd_cache(const void *bvh, const ffx_bvh_info *info, const ffx_sc
   if (!cache) FFX_FAIL(FFX_ERR_ARG, "render_fwd_cache: cache is NULL");
   if (((uintptr_t)cache & 15) != 0) FFX_FAIL(FFX_ERR_ARG, "render_fwd_cache: cache must be 16-byte aligned");
   FFX_NO_PATH(img_fp16, "render_fwd_cache");
+  FFX_NO_APPEARANCE(img_fp16, "render_fwd_cache");
   return render_fwd_impl(bvh, info, sd, shape_albedo, tex, spp, seed, img_fp16 & 31, img, cache, s);
 }
 
@@ -4945,6 +5102,7 @@ int ffx_render_fwd_adjoint(const void *bvh, const ffx_bvh_info *info, const ffx_
   if (!gimg || !gtex) FFX_FAIL(FFX_ERR_ARG, "render_fwd_adjoint: gimg / gtex is NULL");
   if (sd && !sd->proj.enabled) FFX_FAIL(FFX_ERR_ARG, "render_fwd_adjoint: the scene has no projector (nothing to differentiate)");
   FFX_NO_PATH(img_fp16, "render_fwd_adjoint");
+  FFX_NO_APPEARANCE(img_fp16, "render_fwd_adjoint");
   return render_fwd_impl(bvh, info, sd, shape_albedo, tex, spp, seed, img_fp16 & (FFX_RENDER_FP16 | FFX_RENDER_SPARSE_ADJOINT | FFX_RENDER_APEX_READY), img, nullptr, s, gimg,
                          gtex, dot_out);
 }
@@ -4973,6 +5131,7 @@ int ffx_render_bwd_cached(const ffx_scene_desc *sd, const float *shape_albedo, c
                           int img_fp16, float *dot_out, ffx_stream s) {
   if (!gimg) FFX_FAIL(FFX_ERR_ARG, "render_bwd_cached: bad argument");
   FFX_NO_PATH(img_fp16, "render_bwd_cached");
+  FFX_NO_APPEARANCE(img_fp16, "render_bwd_cached");
   return render_bwd_cached_impl(sd, shape_albedo, cache, spp, gimg, gtex, img, img_fp16, dot_out, nullptr, 0.f, s);
 }
 // K9 under an L1 loss against a target image (include/ffx.h): the loss launch (ffx_l1_value_grad) and its gradient image are folded into the scatter
@@ -5176,8 +5335,63 @@ static int render_bwd_impl(const void *bvh, const ffx_bvh_info *info, const ffx_
   return FFX_OK;
 }
 
+// FFX_RENDER_GRAD_APPEARANCE (include/ffx.h): after the texture part — the launches of a call without the bit, which leave G = gimg / weight
+// in the filtered film's scratch when the scene has a projector — one launch of k_render_bwd_appearance into the block behind gtex
+static int render_bwd_appearance(const void *bvh, const ffx_bvh_info *info, const ffx_scene_desc *sd, const float *shape_albedo, int spp, uint32_t seed, int flags,
+                                 const float *gimg, float *gtex, ffx_stream s, void *rf_scratch) {
+  if (!bvh || !info || !sd || (!shape_albedo && sd->n_mat_h <= 0) || !gimg || !gtex || spp < 1) FFX_FAIL(FFX_ERR_ARG, "render_bwd: bad argument");
+  if (flags & FFX_RENDER_PATH_MASK) FFX_FAIL(FFX_ERR_UNSUPPORTED, "render_bwd: FFX_RENDER_GRAD_APPEARANCE is served at max_depth 2 only");
+  const int rc = render_bwd_impl(bvh, info, sd, shape_albedo, spp, seed, flags & ~FFX_RENDER_GRAD_APPEARANCE, gimg, gtex, s, rf_scratch);
+  if (rc != FFX_OK) return rc;
+  if (!check_info(info, "render_bwd")) return FFX_ERR_ARG;
+  ShadeK c;
+  if (!shade_prepare(sd, c)) FFX_FAIL(rf_scratch ? FFX_ERR_UNSUPPORTED : FFX_ERR_ARG, "render_bwd: bad scene description%s", rf_scratch ? " (gaussian filter: stddev <= 0.5)" : "");
+  c.mats = shape_albedo;
+  if (c.mat_stride == FFX_MAT_STRIDE && !c.mat_inline && ((uintptr_t)shape_albedo & 15) != 0) FFX_FAIL(FFX_ERR_ARG, "render_bwd: material rows must be 16-byte aligned");
+  const long n_pix = (long)c.cam.W * c.cam.H;
+  if (n_pix * spp >= (1L << 32)) FFX_FAIL(FFX_ERR_UNSUPPORTED, "render_bwd: more than 2^32 samples");
+  if (sd->n_shapes < 1) FFX_FAIL(FFX_ERR_ARG, "render_bwd: n_shapes < 1");
+  const long n_tex = (long)sd->proj.tex_w * sd->proj.tex_h * sd->proj.tex_channels;
+  if (n_tex < 0) FFX_FAIL(FFX_ERR_ARG, "render_bwd: bad projector texture size");
+  AppArgs a;
+  memset(&a, 0, sizeof a);
+  a.nodes = (const BvhNode *)((const char *)bvh + info->off_nodes);
+  a.recs = (const TriRec *)((const char *)bvh + info->off_recs);
+  a.nrec = info->off_nrec ? (const float4 *)((const char *)bvh + info->off_nrec) : nullptr;
+  a.tex = sd->proj.enabled ? gimg + (size_t)n_pix * 3 : nullptr; // (the input half of the layout: the forward's texture behind gimg)
+  a.spp = spp; a.n_pix = (int)n_pix; a.n_shapes = sd->n_shapes;
+  a.seed_key = seed_key_of(seed);
+  a.grow = gtex + n_tex;
+  a.gspot = a.grow + (size_t)3 * sd->n_shapes;
+  float *bt = a.gspot + 3;
+  for (int k = 0; k < c.n_base_tex; ++k) {
+    a.gbt[k] = bt;
+    bt += (size_t)3 * c.btw[k] * c.bth[k];
+  }
+  const float *gsrc = gimg;
+  if (rf_scratch) {
+    float *part = (float *)rf_scratch;
+    float4 *G = (float4 *)(part + (size_t)n_pix * 100);
+    if (!sd->proj.enabled) { // (the texture part launched nothing: G as it forms it)
+      hipLaunchKernelGGL(k_rf_weights, dim3((unsigned)n_pix), dim3(64), 0, (hipStream_t)s, c.rf, (int)n_pix, spp, seed_key_of(seed), part);
+      FFX_CHECK_LAUNCH("render_bwd_filtered (appearance)/weights");
+      hipLaunchKernelGGL(k_rf_gather, dim3(ffx_cdiv(c.cam.W, 64), ffx_cdiv(c.cam.H, FFX_RFG_WAVES)), dim3(64 * FFX_RFG_WAVES), 0, (hipStream_t)s, (const float4 *)part, c.cam.W,
+                         c.cam.H, 0, (void *)nullptr, gimg, G);
+      FFX_CHECK_LAUNCH("render_bwd_filtered (appearance)/gather");
+    }
+    gsrc = (const float *)G;
+  }
+  const long blocks = ffx_cdiv(n_pix, (long)FFX_APP_WAVES);
+  const unsigned grid = (unsigned)(blocks < 2048 ? blocks : 2048); // (every workgroup strides over the film: 2048 x 4 waves fill the device)
+  if (rf_scratch) hipLaunchKernelGGL(k_render_bwd_appearance<true>, dim3(grid), dim3(64 * FFX_APP_WAVES), stack_bytes(info), (hipStream_t)s, c, a, gsrc);
+  else hipLaunchKernelGGL(k_render_bwd_appearance<false>, dim3(grid), dim3(64 * FFX_APP_WAVES), stack_bytes(info), (hipStream_t)s, c, a, gsrc);
+  FFX_CHECK_LAUNCH(rf_scratch ? "render_bwd_filtered (appearance)" : "render_bwd (appearance)");
+  return FFX_OK;
+}
+
 int ffx_render_bwd(const void *bvh, const ffx_bvh_info *info, const ffx_scene_desc *sd, const float *shape_albedo, int spp, uint32_t seed, int flags,
                    const float *gimg, float *gtex, ffx_stream s) {
+  if (flags & FFX_RENDER_GRAD_APPEARANCE) return render_bwd_appearance(bvh, info, sd, shape_albedo, spp, seed, flags, gimg, gtex, s, nullptr);
   return render_bwd_impl(bvh, info, sd, shape_albedo, spp, seed, flags, gimg, gtex, s, nullptr);
 }
 
@@ -5191,6 +5405,7 @@ int ffx_render_bwd_det(const void *bvh, const ffx_bvh_info *info, const ffx_scen
   if (!workspace || ((uintptr_t)workspace & 15) != 0) FFX_FAIL(FFX_ERR_ARG, "render_bwd_det: workspace is NULL or not 16-byte aligned");
   if (!sd) FFX_FAIL(FFX_ERR_ARG, "render_bwd_det: bad argument");
   FFX_NO_PATH(flags, "render_bwd_det");
+  FFX_NO_APPEARANCE(flags, "render_bwd_det");
   // workspace: [the filtered film's scratch (16-byte multiple)] [one 64-bit sum per texel and channel] [the largest tap]
   void *rf = sd->rfilter != FFX_RFILTER_BOX ? workspace : nullptr;
   void *det = (char *)workspace + (rf ? ffx_render_filter_bytes(sd) : 0);
@@ -5202,6 +5417,7 @@ int ffx_render_bwd_det_part(const void *bvh, const ffx_bvh_info *info, const ffx
   if (!sd || !acc || (part != 1 && part != 2) || ((uintptr_t)acc & (part == 1 ? 3 : 7)) != 0) FFX_FAIL(FFX_ERR_ARG, "render_bwd_det_part: bad argument");
   if (scale_log2 < -126 || scale_log2 > 126) FFX_FAIL(FFX_ERR_ARG, "render_bwd_det_part: scale_log2 out of range");
   FFX_NO_PATH(flags, "render_bwd_det_part");
+  FFX_NO_APPEARANCE(flags, "render_bwd_det_part");
   void *rf = nullptr;
   if (sd->rfilter != FFX_RFILTER_BOX) {
     if (!workspace || ((uintptr_t)workspace & 15) != 0) FFX_FAIL(FFX_ERR_ARG, "render_bwd_det_part: a filtered film needs its scratch (ffx_render_filter_bytes), 16-byte aligned");
@@ -5230,6 +5446,7 @@ size_t ffx_render_filter_bytes(const ffx_scene_desc *sd) {
 int ffx_render_fwd_filtered(const void *bvh, const ffx_bvh_info *info, const ffx_scene_desc *sd, const float *shape_albedo, const float *tex, int spp,
                             uint32_t seed, int img_fp16, void *img, void *scratch, ffx_stream s) {
   if (!scratch || ((uintptr_t)scratch & 15) != 0) FFX_FAIL(FFX_ERR_ARG, "render_fwd_filtered: scratch is NULL or not 16-byte aligned");
+  FFX_NO_APPEARANCE(img_fp16, "render_fwd_filtered");
   return render_fwd_impl(bvh, info, sd, shape_albedo, tex, spp, seed, img_fp16 & (FFX_RENDER_FP16 | FFX_RENDER_APEX_READY | FFX_RENDER_PATH_MASK), img, nullptr, s, nullptr,
                          nullptr, nullptr, scratch);
 }
@@ -5240,6 +5457,7 @@ int ffx_render_fwd_adjoint_filtered(const void *bvh, const ffx_bvh_info *info, c
   if (!scratch || ((uintptr_t)scratch & 15) != 0) FFX_FAIL(FFX_ERR_ARG, "render_fwd_adjoint_filtered: scratch is NULL or not 16-byte aligned");
   if (sd && !sd->proj.enabled) FFX_FAIL(FFX_ERR_ARG, "render_fwd_adjoint_filtered: the scene has no projector (nothing to differentiate)");
   FFX_NO_PATH(img_fp16, "render_fwd_adjoint_filtered");
+  FFX_NO_APPEARANCE(img_fp16, "render_fwd_adjoint_filtered");
   return render_fwd_impl(bvh, info, sd, shape_albedo, tex, spp, seed, img_fp16 & (FFX_RENDER_FP16 | FFX_RENDER_SPARSE_ADJOINT | FFX_RENDER_APEX_READY), img, nullptr, s, gimg,
                          gtex, nullptr, scratch);
 }
@@ -5247,6 +5465,7 @@ int ffx_render_fwd_adjoint_filtered(const void *bvh, const ffx_bvh_info *info, c
 int ffx_render_bwd_filtered(const void *bvh, const ffx_bvh_info *info, const ffx_scene_desc *sd, const float *shape_albedo, int spp, uint32_t seed, int flags,
                             const float *gimg, float *gtex, void *scratch, ffx_stream s) {
   if (!scratch || ((uintptr_t)scratch & 15) != 0) FFX_FAIL(FFX_ERR_ARG, "render_bwd_filtered: scratch is NULL or not 16-byte aligned");
+  if (flags & FFX_RENDER_GRAD_APPEARANCE) return render_bwd_appearance(bvh, info, sd, shape_albedo, spp, seed, flags, gimg, gtex, s, scratch);
   return render_bwd_impl(bvh, info, sd, shape_albedo, spp, seed, flags, gimg, gtex, s, scratch);
 }
 
@@ -5255,6 +5474,7 @@ int ffx_render_fwd_cache_filtered(const void *bvh, const ffx_bvh_info *info, con
   if (!cache || ((uintptr_t)cache & 15) != 0) FFX_FAIL(FFX_ERR_ARG, "render_fwd_cache_filtered: cache is NULL or not 16-byte aligned");
   if (!scratch || ((uintptr_t)scratch & 15) != 0) FFX_FAIL(FFX_ERR_ARG, "render_fwd_cache_filtered: scratch is NULL or not 16-byte aligned");
   FFX_NO_PATH(img_fp16, "render_fwd_cache_filtered");
+  FFX_NO_APPEARANCE(img_fp16, "render_fwd_cache_filtered");
   return render_fwd_impl(bvh, info, sd, shape_albedo, tex, spp, seed,
                          img_fp16 & (FFX_RENDER_FP16 | FFX_RENDER_SPARSE_ADJOINT | FFX_RENDER_APEX_READY | FFX_RENDER_CACHE_ZEROED | FFX_RENDER_CACHE_KEEP_DROPPED), img, nullptr, s,
                          nullptr, nullptr, nullptr, scratch, cache);

@@ -428,6 +428,10 @@ class SceneParameters:
         self._d = {}
         self._dirty = set()
         self._pending = None  # a callable: values of a natively pushed scene sample not yet written into the map (fireflies_amd/scene.py Scene._materialise)
+        # the appearance parameters (Scene._build_params) and those of them assigned a tensor that requires grad: mi.render differentiates with respect
+        # to these leaves until the key is assigned again
+        self._leaf_keys = frozenset()
+        self._leaves = {}
 
     def keys(self):
         return self._d.keys()
@@ -460,6 +464,12 @@ class SceneParameters:
         self._dirty.add(k)
         if k == "tex.data":
             self._scene._note_texture(v)
+        elif k in self._leaf_keys:
+            t = v.t if isinstance(v, _ArrayBase) else v
+            if isinstance(t, torch.Tensor) and t.requires_grad:
+                self._leaves[k] = t
+            else:
+                self._leaves.pop(k, None)
 
     def _init(self, k, v):
         self._d[k] = v
@@ -615,6 +625,8 @@ class Scene:
             p._init(s.name + ".intensity.value", Color3f(torch.tensor(s.intensity, dtype=torch.float32)))
             p._init(s.name + ".cutoff_angle", Float(s.cutoff_angle))
             p._init(s.name + ".beam_width", Float(s.beam_width))
+        p._leaf_keys = frozenset([m + ".brdf_0.base_color.value" for m in mats] + [n + ".brdf_0.base_color.data" for n, _ in self._base_tex]
+                                 + ([d.spot.name + ".intensity.value"] if d.spot is not None else []))
 
     def sensors(self):
         return self._sensors
@@ -868,6 +880,7 @@ class Scene:
         sp.frames = (C.c_int32 * S)(*([-1] * S))
         sp.mesh_shapes = [self._mesh_index[name] for _, name in meshes]
         sp.eta, sp.has_mat, sp.warn = eta, has_mat, warn
+        sp.keys = frozenset([key for _, key in poses] + [key for _, _, _, key in values])  # (what a push writes: step_native forgets their leaves)
         sp.geoms = []
         for b in g._blobs:
             gs = _abi.StepGeom()
@@ -927,6 +940,9 @@ class Scene:
                 if values[drow, 0] > 0.0:
                     self._warn_spec_trans(key)
         p._dirty = set()
+        if p._leaves:
+            for k in sp.keys:
+                p._leaves.pop(k, None)
         if sp.has_mat:
             self._albedo_stale = True
         self._sd_cache = (ch, sd)
@@ -1049,7 +1065,7 @@ class Scene:
         if d.spot is not None:
             f[_SD_SPOT_TW:_SD_SPOT_TW + 16] = self._mat(d.spot.name + ".to_world").reshape(-1)
             inten = p[d.spot.name + ".intensity.value"]
-            f[_SD_SPOT_INT:_SD_SPOT_INT + 3] = inten.t.reshape(-1)[:3].tolist() if isinstance(inten, _ArrayBase) else [float(v) for v in inten]
+            f[_SD_SPOT_INT:_SD_SPOT_INT + 3] = inten.t.reshape(-1)[:3].tolist() if isinstance(inten, _ArrayBase) else [float(v) for v in (inten.detach() if isinstance(inten, torch.Tensor) else inten)]
             f[_SD_SPOT_INT + 3], f[_SD_SPOT_INT + 4] = float(p[d.spot.name + ".cutoff_angle"]), float(p[d.spot.name + ".beam_width"])
 
     def scene_desc(self, tex_channels=3):
@@ -1081,7 +1097,7 @@ class Scene:
         if d.spot is not None:
             s = d.spot
             inten = p[s.name + ".intensity.value"]
-            inten = inten.t.reshape(-1).tolist() if isinstance(inten, _ArrayBase) else list(inten)
+            inten = inten.t.reshape(-1).tolist() if isinstance(inten, _ArrayBase) else list(inten.detach() if isinstance(inten, torch.Tensor) else inten)
             spot = scenes.SpotData(s.name, self._mat(s.name + ".to_world"), tuple(float(v) for v in inten), float(p[s.name + ".cutoff_angle"]),
                                    float(p[s.name + ".beam_width"]))
         tmp = scenes.SceneData(d.meshes, sensor, proj, spot, float(p["Projector.scale"]) if proj is not None else 1.0)
@@ -1176,12 +1192,15 @@ def load_dict(d: dict):
 
 def render(scene: Scene, params: SceneParameters = None, spp: int = 16, seed: int = 0, sensor: int = 0, fp16: bool = False, integrator: Integrator = None):
     """mi.render(scene, spp=...) -> [H,W,3] (wrapped; `.torch()` as in examples/vocalfold_scene.py:14).
-    Differentiable w.r.t. `tex.data` when that parameter is a tensor that requires grad.
+    Differentiable w.r.t. `tex.data` when that parameter is a tensor that requires grad — and w.r.t. `<mat>.brdf_0.base_color.value`,
+    `<spot>.intensity.value` and `<mat>.brdf_0.base_color.data` when such a tensor was assigned to them (direct light only).
     integrator (mi.load_dict): None or max_depth 2 renders direct light at the primary hit, as always; deeper paths run on the caller's stream."""
     if sensor != 0:
         raise NotImplementedError("only sensor 0 renders; further sensors are projector proxies")
     if integrator is not None and not isinstance(integrator, Integrator):
         raise TypeError("render: integrator must come from mi.load_dict")
+    if scene._params._leaves and torch.is_grad_enabled():
+        return _render_appearance(scene, spp, seed, fp16, integrator)
     if integrator is not None and integrator.max_depth > 2:
         return _render_path(scene, spp, seed, fp16, integrator)
     p = scene._params
@@ -1247,3 +1266,82 @@ def _render_path(scene, spp, seed, fp16, integrator):
     scene.render_paths["caller_stream"] += 1
     t = tex if tex.is_contiguous() else tex.contiguous()
     return TensorXf(scene.geom.render_fwd(sd, mats, t.unsqueeze(-1) if t.dim() == 2 else t, int(spp), int(seed), bool(fp16), max_depth=md, rr_depth=rr))
+
+
+class _AppearanceRender(torch.autograd.Function):
+    """mi.render with appearance leaves: the plain forward; the backward is ONE ffx_render_bwd[_filtered] call with
+    FFX_RENDER_GRAD_APPEARANCE, which yields the texture gradient and the appearance block together"""
+
+    @staticmethod
+    def forward(ctx, tex, scene, sd, mats, spp, seed, fp16, kinds, *leaves):
+        geom = scene.geom
+        t = tex.detach()
+        t = (t if t.is_contiguous() else t.contiguous())
+        t = t.unsqueeze(-1) if t.dim() == 2 else t
+        ctx.geom, ctx.sd, ctx.spp, ctx.seed, ctx.kinds = geom, sd, spp, seed, kinds
+        ctx.tex, ctx.tex_shape = t, tex.shape
+        ctx.mats = mats.clone() if mats is not None else None  # (the scene's table is rewritten in place by the next randomisation)
+        ctx.keep = [bt for _, bt in scene._base_tex]  # (the description points at them)
+        ctx.leaf_meta = [(x.shape, x.dtype, x.device) for x in leaves]
+        ctx.pose_version = geom.version
+        return geom.render_fwd(sd, mats, t, spp, seed, fp16)
+
+    @staticmethod
+    def backward(ctx, g):
+        if ctx.geom.version != ctx.pose_version:
+            raise RuntimeError("mi.render: the scene was updated between the render and its backward — the appearance adjoint re-traces the render's pose: "
+                               "call backward before the next params.update()")
+        gtex, app = ctx.geom.render_bwd(ctx.sd, ctx.mats, ctx.spp, ctx.seed, g.float().contiguous(), appearance=True, tex=ctx.tex)
+        grads = []
+        for (kind, arg), (shape, dtype, device) in zip(ctx.kinds, ctx.leaf_meta):
+            if kind == "mat":
+                v = app.rows[list(arg)].sum(0)
+            elif kind == "spot":
+                v = app.spot
+            else:
+                v = app.base_tex[arg]
+            n = 1
+            for e in shape:
+                n *= int(e)
+            v = v.sum().reshape(shape) if n == 1 else v.reshape(shape)  # (a scalar assigned to a colour is broadcast to its three channels)
+            grads.append(v.to(device=device, dtype=dtype))
+        gt = gtex.reshape(ctx.tex_shape) if ctx.needs_input_grad[0] else None
+        return (gt, None, None, None, None, None, None, None, *grads)
+
+
+def _render_appearance(scene, spp, seed, fp16, integrator):
+    """mi.render while appearance leaves are assigned and grad is enabled: through _AppearanceRender on the caller's stream"""
+    if integrator is not None and integrator.max_depth > 2:
+        raise ValueError("mi.render: the gradients of base colours and spot intensity are served for direct light only (max_depth 2); "
+                         "the scene holds parameters that require grad: " + ", ".join(sorted(scene._params._leaves)))
+    if ops.deterministic_mode():
+        raise ValueError("mi.render: the gradients of base colours and spot intensity have no deterministic adjoint (FFX_DETERMINISTIC=1)")
+    p = scene._params
+    tex = None
+    ch = 3
+    if scene.data.projector is not None:
+        tex = p["tex.data"]
+        tex = tex.t if isinstance(tex, _ArrayBase) else tex
+        if not isinstance(tex, torch.Tensor):
+            tex = torch.as_tensor(np.asarray(tex, np.float32))
+        if tex.device != scene.device:
+            tex = tex.to(scene.device)
+        ch = 1 if tex.dim() == 2 else int(tex.shape[-1])
+    scene.note_spp(spp)
+    sd = scene.scene_desc(tex_channels=ch)
+    if tex is None:
+        tex = torch.zeros((1, 1, 1), device=scene.device)
+    elif tex.dtype != torch.float32:
+        tex = tex.float()
+    names = [n for n, _ in scene._base_tex]
+    kinds, leaves = [], []
+    for k, leaf in p._leaves.items():
+        base, _, rest = k.partition(".")
+        if rest == "brdf_0.base_color.value":
+            kinds.append(("mat", tuple(scene._material_meshes[base])))
+        elif rest == "brdf_0.base_color.data":
+            kinds.append(("base_tex", names.index(base)))
+        else:
+            kinds.append(("spot", None))
+        leaves.append(leaf)
+    return TensorXf(_AppearanceRender.apply(tex, scene, sd, scene.materials_arg(sd), int(spp), int(seed), bool(fp16), kinds, *leaves))

@@ -5,6 +5,7 @@ libffx_hip.so.  All functions require contiguous tensors on a HIP device and rai
 """
 import ctypes as C
 import os
+from typing import NamedTuple
 
 import numpy as np
 import torch
@@ -535,6 +536,14 @@ def _no_path(max_depth, what):
     if max_depth != 2:
         path_flags(max_depth)  # (the range check's message first)
         raise ValueError(f"{what}: max_depth > 2 renders through render_fwd / render_bwd only (no adjoint cache, fused or deterministic adjoint)")
+
+
+class AppearanceGrad(NamedTuple):
+    """what render_bwd(..., appearance=True) adds to the texture gradient: d loss / d base colour per material row [n_shapes, 3] (zero on
+    rows whose base colour is a texture), d loss / d spot intensity [3], d loss / d base-colour texture [h, w, 3] per texture of the scene description"""
+    rows: torch.Tensor
+    spot: torch.Tensor
+    base_tex: list
 
 
 def _lane_kernels():
@@ -1098,10 +1107,15 @@ class DeviceGeometry:
                        _stream(self._didx))
         self._release()
 
-    def render_bwd(self, sd, albedo, spp, seed, gimg, deterministic=None, max_depth=2, rr_depth=5):
+    def render_bwd(self, sd, albedo, spp, seed, gimg, deterministic=None, max_depth=2, rr_depth=5, appearance=False, tex=None):
         """the re-tracing adjoint.  deterministic (default: FFX_DETERMINISTIC=1 in the environment): ffx_render_bwd_det — bitwise
         reproducible accumulation (64-bit fixed point instead of float atomics; two re-traces and one host synchronisation).
-        max_depth > 2: the path integrator's adjoint — replays render_fwd's paths of the same max_depth, rr_depth, spp and seed (float atomics only)."""
+        max_depth > 2: the path integrator's adjoint — replays render_fwd's paths of the same max_depth, rr_depth, spp and seed (float atomics only).
+        appearance=True (FFX_RENDER_GRAD_APPEARANCE): -> (gtex, AppearanceGrad) — also d loss / d base colour per material row, d loss /
+        d spot intensity and d loss / d base-colour texture; `tex` is the forward's projector texture (needed when the scene has a projector).
+        Direct light (max_depth 2) and the float-atomic adjoint only."""
+        if appearance:
+            return self._render_bwd_appearance(sd, albedo, spp, seed, gimg, deterministic, max_depth, tex)
         path = path_flags(max_depth, rr_depth) if max_depth != 2 else 0
         if deterministic is None:
             deterministic = deterministic_mode()
@@ -1149,3 +1163,47 @@ class DeviceGeometry:
             )
         self._release()
         return gtex
+
+    def _render_bwd_appearance(self, sd, albedo, spp, seed, gimg, deterministic, max_depth, tex):
+        """render_bwd(..., appearance=True): one ffx_render_bwd[_filtered] call with FFX_RENDER_GRAD_APPEARANCE; gimg and the texture travel in one
+        buffer, gtex and the appearance block in another (include/ffx.h)"""
+        if max_depth != 2:
+            path_flags(max_depth)  # (the range check's message first)
+            raise ValueError("render_bwd(appearance=True): the appearance gradients are served at max_depth 2 (direct light) only")
+        if deterministic is None:
+            deterministic = deterministic_mode()
+        if deterministic:
+            raise ValueError("render_bwd(appearance=True) has no deterministic adjoint (FFX_DETERMINISTIC / deterministic=True)")
+        H, W = sd.cam.height, sd.cam.width
+        n_tex = sd.proj.tex_h * sd.proj.tex_w * sd.proj.tex_channels
+        bt = [(int(sd.base_tex_h[k]), int(sd.base_tex_w[k])) for k in range(sd.n_base_tex)]
+        n_app = _abi.appearance_floats(sd.n_shapes, bt)
+        src = gimg.reshape(-1)
+        if sd.proj.enabled:
+            if tex is None or tex.numel() != n_tex:
+                raise ValueError(f"render_bwd(appearance=True): the forward's projector texture ({n_tex} floats) is needed")
+            src = torch.cat([gimg.reshape(-1).float(), tex.detach().reshape(-1).to(device=self.device, dtype=torch.float32)])
+        if src.numel() < H * W * 3:
+            raise ValueError("gimg must hold [H, W, 3] floats")
+        out = torch.zeros(n_tex + n_app, dtype=torch.float32, device=self.device)
+        mats_arg = _check_materials(sd, albedo)
+        blob = self.blob
+        flags = self._apex_flag(apex_key(sd)) | _abi.RENDER_GRAD_APPEARANCE
+        with self._timed("render_bwd"):
+            if sd.rfilter:
+                scratch = torch.empty(render_filter_bytes(sd), dtype=torch.uint8, device=self.device)
+                self._call("ffx_render_bwd_filtered", _dev(blob, torch.uint8), C.byref(self.info), C.byref(sd), mats_arg, int(spp), int(seed) & 0xFFFFFFFF, flags,
+                           _dev(src, name="gimg"), _dev(out), _dev(scratch, torch.uint8), _stream(self._didx))
+            else:
+                self._call("ffx_render_bwd", _dev(blob, torch.uint8), C.byref(self.info), C.byref(sd), mats_arg, int(spp), int(seed) & 0xFFFFFFFF, flags,
+                           _dev(src, name="gimg"), _dev(out), _stream(self._didx))
+        self._release()
+        gtex = out[:n_tex].view(sd.proj.tex_h, sd.proj.tex_w, sd.proj.tex_channels)
+        S = sd.n_shapes
+        rows = out[n_tex:n_tex + 3 * S].view(S, 3)
+        spot = out[n_tex + 3 * S:n_tex + 3 * S + 3]
+        base_tex, o = [], n_tex + 3 * S + 3
+        for h, w in bt:
+            base_tex.append(out[o:o + 3 * h * w].view(h, w, 3))
+            o += 3 * h * w
+        return gtex, AppearanceGrad(rows, spot, base_tex)

@@ -763,6 +763,22 @@ int ffx_det_finish(const void *acc /*[dev] int64 [n]*/, int scale_log2, size_t n
 #define FFX_RENDER_PATH_MASK 0xff00
 #define FFX_RENDER_MAX_DEPTH_LIMIT 8
 #define FFX_RENDER_PATH(max_depth, rr_depth) ((((max_depth) & 15) << FFX_RENDER_MAX_DEPTH_SHIFT) | (((rr_depth) & 15) << FFX_RENDER_RR_DEPTH_SHIFT))
+/* The appearance adjoint (ABI 11): FFX_RENDER_GRAD_APPEARANCE in the flags word of ffx_render_bwd / ffx_render_bwd_filtered adds
+ * d loss / d base colour, d loss / d spot intensity and d loss / d base-colour texture to the texture gradient (Mitsuba's `<mat>.brdf_0.base_color.value`,
+ * `<spot>.intensity.value`, `<mat>.brdf_0.base_color.data`, examples/vocalfold_scene.py:80-90, main.py:123,151).  Direct light only: with path bits the
+ * call answers FFX_ERR_UNSUPPORTED, and so does every other render entry point when the bit is set.  With the bit:
+ *   input  — when sd->proj.enabled, gimg is followed in the same buffer by the forward's projector texture [tex_h][tex_w][tex_channels] (the base
+ *            colour's derivative needs the light that arrived: gimg then holds H x W x 3 + tex_h x tex_w x tex_channels floats);
+ *   output — gtex [tex_h][tex_w][tex_channels] is followed in the same buffer by FFX_RENDER_APPEARANCE_FLOATS(sd) floats:
+ *            [n_shapes][3] per material row d loss / d base_color (0 for rows whose FFX_MAT_BASE_TEX != 0), [3] d loss / d spot intensity, then per
+ *            k < n_base_tex [base_tex_h[k]][base_tex_w[k]][3] d loss / d base_tex[k].  Accumulated into: the caller zeroes the whole buffer.
+ * The texture gradient comes from the same launches as without the bit; one launch follows them.  The oracle ignores the bit (it writes gtex only). */
+#define FFX_RENDER_GRAD_APPEARANCE 0x10000
+#define FFX_RENDER_APPEARANCE_BASE_TEX_TEXELS(sd, k) ((sd)->n_base_tex > (k) ? (size_t)(sd)->base_tex_w[k] * (size_t)(sd)->base_tex_h[k] : (size_t)0)
+#define FFX_RENDER_APPEARANCE_FLOATS(sd)                                                                                                         \
+  (3 * (size_t)(sd)->n_shapes + 3 +                                                                                                             \
+   3 * (FFX_RENDER_APPEARANCE_BASE_TEX_TEXELS(sd, 0) + FFX_RENDER_APPEARANCE_BASE_TEX_TEXELS(sd, 1) + FFX_RENDER_APPEARANCE_BASE_TEX_TEXELS(sd, 2) + \
+        FFX_RENDER_APPEARANCE_BASE_TEX_TEXELS(sd, 3)))
 /* Writes the apex records (the triangles as seen from a fixed ray origin) of sd's camera and enabled emitters into
  * the blob's apex areas — what every packet render does in front of its kernel unless told FFX_RENDER_APEX_READY.  Only
  * sd->cam.to_world, sd->proj.{enabled,to_world} and sd->spot.{enabled,to_world} are read.  No reference counterpart (Mitsuba

@@ -1,0 +1,47 @@
+"""The appearance adjoint's cost: ms per 512^2 x 64-spp vocal-fold adjoint with FFX_RENDER_GRAD_APPEARANCE (the texture gradient's
+launches + k_render_bwd_appearance), next to the same render_bwd without it, box and gaussian film.  HIP events around repeated calls of one pose on
+one stream, after a warm-up.  Prints one JSON line.
+
+    python tools/appearancebench.py [reps]
+"""
+import json
+import os
+import sys
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from fireflies_amd import workloads  # noqa: E402
+
+
+def _ms(fn, reps):
+    fn()
+    torch.cuda.synchronize()
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for _ in range(reps):
+        fn()
+    b.record()
+    torch.cuda.synchronize()
+    return a.elapsed_time(b) / reps
+
+
+def main():
+    reps = int(sys.argv[1]) if len(sys.argv) > 1 else 5
+    wl = workloads.vocalfold(device="cuda", width=512, height=512, grid=16)
+    torch.manual_seed(0)
+    wl.ff_scene.randomize()
+    tex = workloads.build_texture(wl).detach().unsqueeze(-1).contiguous()
+    geom, out = wl.mi_scene.geom, {"res": 512, "spp": 64, "reps": reps}
+    for film in ("box", "gaussian"):
+        wl.mi_scene.rfilter = film
+        sd = wl.mi_scene.scene_desc(tex_channels=1)
+        mats = wl.mi_scene.materials_arg(sd)
+        gimg = torch.full((sd.cam.height, sd.cam.width, 3), -1.0 / (sd.cam.height * sd.cam.width), device="cuda")
+        out[f"render_bwd_ms_{film}"] = round(_ms(lambda: geom.render_bwd(sd, mats, 64, 1, gimg), reps), 3)
+        out[f"appearance_bwd_ms_{film}"] = round(_ms(lambda: geom.render_bwd(sd, mats, 64, 1, gimg, appearance=True, tex=tex), reps), 3)
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()
