@@ -4363,6 +4363,16 @@ static int cam_prepare(const ffx_camera *c, CamK &k) {
   return 1;
 }
 
+// the material table that travels with the call (ffx_scene_desc.mat_h: n_shapes rows of `ms` floats) into a kernel argument (ShadeK / BwdP / BwdF);
+// 0: the table's size is wrong
+template <class K> static int copy_mat_h(const ffx_scene_desc *sd, int ms, K &k) {
+  if (sd->n_mat_h <= 0) return 1;
+  if (sd->n_mat_h > FFX_MAX_MAT_H || sd->n_mat_h != sd->n_shapes * ms) return 0;
+  k.mat_inline = 1;
+  for (int i = 0; i < sd->n_mat_h; ++i) k.mat_h[i] = sd->mat_h[i];
+  return 1;
+}
+
 static int shade_prepare(const ffx_scene_desc *sd, ShadeK &c) {
   memset(&c, 0, sizeof c);
   if (!cam_prepare(&sd->cam, c.cam)) return 0;
@@ -4371,28 +4381,24 @@ static int shade_prepare(const ffx_scene_desc *sd, ShadeK &c) {
   c.shadows = sd->shadows & FFX_SHADOWS_ON; // (the word's other bits are hints to the pre-pass and the caches)
   c.mat_stride = sd->mat_stride ? sd->mat_stride : 3;
   if (c.mat_stride != 3 && c.mat_stride != FFX_MAT_STRIDE) return 0;
-  if (sd->n_mat_h > 0) { // the material table travels with the call (ffx_scene_desc.mat_h)
-    if (sd->n_mat_h > FFX_MAX_MAT_H || sd->n_mat_h != sd->n_shapes * c.mat_stride) return 0;
-    c.mat_inline = 1;
-    for (int i = 0; i < sd->n_mat_h; ++i) c.mat_h[i] = sd->mat_h[i];
-    if (c.mat_stride == FFX_MAT_STRIDE && sd->n_shapes <= 8) { // per-row constants of the principled rows (ShadeK.mat_pre)
-      c.mat_pre_on = 1;
-      for (int k = 0; k < sd->n_shapes; ++k) {
-        const float *m = sd->mat_h + k * FFX_MAT_STRIDE;
-        float *p = c.mat_pre + k * FFX_PRE_FLOATS;
-        const float eta = m[FFX_MAT_ETA], r2 = m[FFX_MAT_ROUGHNESS] * m[FFX_MAT_ROUGHNESS], a = r2 > 0.001f ? r2 : 0.001f, a2 = a * a;
-        const float metallic = m[FFX_MAT_METALLIC], m1 = 1.0f - metallic, tint = m[FFX_MAT_SPEC_TINT];
-        const float r0 = (eta - 1.0f) / (eta + 1.0f);
-        uint32_t flags = 0;
-        if (m[FFX_MAT_ANISOTROPIC] != 0.f) flags |= FFX_PRE_ANISO;
-        if (tint != 0.f) flags |= FFX_PRE_TINT;
-        if (m[FFX_MAT_CLEARCOAT] > 0.f) flags |= FFX_PRE_CLEARCOAT;
-        if (m[FFX_MAT_FLATNESS] > 0.f) flags |= FFX_PRE_FLAT;
-        if (m[FFX_MAT_SHEEN] > 0.f && m1 > 0.f) flags |= FFX_PRE_SHEEN;
-        p[0] = eta; p[1] = 1.0f / (eta * eta); p[2] = a2; p[3] = 1.0f / a2;
-        p[4] = metallic; p[5] = metallic + m1 * tint; p[6] = m1 * (1.0f - tint); p[7] = m1 * (1.0f - m[FFX_MAT_SPEC_TRANS]);
-        p[8] = 2.0f * m[FFX_MAT_ROUGHNESS]; memcpy(&p[9], &flags, 4); p[10] = r2; p[11] = m1 * tint * r0 * r0;
-      }
+  if (!copy_mat_h(sd, c.mat_stride, c)) return 0;
+  if (c.mat_inline && c.mat_stride == FFX_MAT_STRIDE && sd->n_shapes <= 8) { // per-row constants of the principled rows (ShadeK.mat_pre)
+    c.mat_pre_on = 1;
+    for (int k = 0; k < sd->n_shapes; ++k) {
+      const float *m = sd->mat_h + k * FFX_MAT_STRIDE;
+      float *p = c.mat_pre + k * FFX_PRE_FLOATS;
+      const float eta = m[FFX_MAT_ETA], r2 = m[FFX_MAT_ROUGHNESS] * m[FFX_MAT_ROUGHNESS], a = r2 > 0.001f ? r2 : 0.001f, a2 = a * a;
+      const float metallic = m[FFX_MAT_METALLIC], m1 = 1.0f - metallic, tint = m[FFX_MAT_SPEC_TINT];
+      const float r0 = (eta - 1.0f) / (eta + 1.0f);
+      uint32_t flags = 0;
+      if (m[FFX_MAT_ANISOTROPIC] != 0.f) flags |= FFX_PRE_ANISO;
+      if (tint != 0.f) flags |= FFX_PRE_TINT;
+      if (m[FFX_MAT_CLEARCOAT] > 0.f) flags |= FFX_PRE_CLEARCOAT;
+      if (m[FFX_MAT_FLATNESS] > 0.f) flags |= FFX_PRE_FLAT;
+      if (m[FFX_MAT_SHEEN] > 0.f && m1 > 0.f) flags |= FFX_PRE_SHEEN;
+      p[0] = eta; p[1] = 1.0f / (eta * eta); p[2] = a2; p[3] = 1.0f / a2;
+      p[4] = metallic; p[5] = metallic + m1 * tint; p[6] = m1 * (1.0f - tint); p[7] = m1 * (1.0f - m[FFX_MAT_SPEC_TRANS]);
+      p[8] = 2.0f * m[FFX_MAT_ROUGHNESS]; memcpy(&p[9], &flags, 4); p[10] = r2; p[11] = m1 * tint * r0 * r0;
     }
   }
   if (sd->rfilter == FFX_RFILTER_GAUSSIAN) { // [EXT Mitsuba src/rfilters/gaussian.cpp] radius 4 stddev; the 5x5 window holds radius <= 2
@@ -4783,6 +4789,150 @@ extern "C" int ffx_debug_stats48(unsigned long long *out48, int reset) { // ... 
   return 0;
 }
 #endif
+
+// ---- what the render calls share: the blob's areas, one setup per call, the grids, the gaussian film's steps, one launcher per kernel family
+struct BlobView { const BvhNode *nodes; const TriRec *recs; const float4 *nrec, *gn; }; // nrec: vertex normals per slot (ffx_smooth), gn: unit geometric normals per slot
+static BlobView blob_view(const void *bvh, const ffx_bvh_info *info) {
+  const char *b = (const char *)bvh;
+  return {(const BvhNode *)(b + info->off_nodes), (const TriRec *)(b + info->off_recs), info->off_nrec ? (const float4 *)(b + info->off_nrec) : nullptr,
+          info->off_gn ? (const float4 *)(b + info->off_gn) : nullptr};
+}
+
+// the path integrator's depths from a flags word (include/ffx.h FFX_RENDER_PATH): 0 = a bad field, else 1 with max_depth (2: direct light only, the
+// existing kernels) and rr_depth
+static int path_depths(int flags, int &max_depth, int &rr_depth) {
+  const int md = (flags >> FFX_RENDER_MAX_DEPTH_SHIFT) & 15, rr = (flags >> FFX_RENDER_RR_DEPTH_SHIFT) & 15;
+  max_depth = md == 0 ? 2 : md;
+  rr_depth = rr == 0 ? 5 : rr;
+  return max_depth >= 2 && max_depth <= FFX_RENDER_MAX_DEPTH_LIMIT;
+}
+static inline size_t path_stack_bytes(const ffx_bvh_info *info) { return (size_t)(info->max_depth < 8 ? 8 : info->max_depth) * 64 * sizeof(int); }
+
+// the scene's reconstruction filter against the entry point (`what`: "render_fwd" / "render_bwd"): the gaussian film's calls take a scratch and the wide packet kernels
+static int check_filter(const char *what, const ffx_scene_desc *sd, const ffx_bvh_info *info, const void *rf_scratch) {
+  if (rf_scratch && sd->rfilter == FFX_RFILTER_BOX) FFX_FAIL(FFX_ERR_UNSUPPORTED, "%s_filtered: rfilter must be FFX_RFILTER_GAUSSIAN", what);
+  if (!rf_scratch && sd->rfilter != FFX_RFILTER_BOX) FFX_FAIL(FFX_ERR_UNSUPPORTED, "%s: the scene's reconstruction filter is not the box (use ffx_%s_filtered)", what, what);
+  if (rf_scratch && (!use_packet() || !use_wide(info))) FFX_FAIL(FFX_ERR_UNSUPPORTED, "%s_filtered: only the default (wide packet) kernels carry the filter", what);
+  return FFX_OK;
+}
+
+// what a render call derives from its arguments before it picks a route; c.mats is the caller's material table (shape_albedo).  matm: 0 Lambert,
+// 1 material rows, 2 material rows with textured base colours (their own instantiation — the default kernels pay nothing)
+struct RenderSetup { ShadeK c; BlobView b; long n_pix; int spp, matm; uint32_t seed_key; int max_depth, rr_depth; };
+// the bvh info, the filter, the scene description, the rows' alignment, the 2^32-samples limit and the path depths of `flags`, refused in this order
+// with messages that begin with `what`
+static int render_setup(const char *what, const void *bvh, const ffx_bvh_info *info, const ffx_scene_desc *sd, const float *shape_albedo, int spp, uint32_t seed,
+                        int flags, const void *rf_scratch, RenderSetup &r) {
+  if (!check_info(info, what)) return FFX_ERR_ARG;
+  if (const int rc = check_filter(what, sd, info, rf_scratch)) return rc;
+  if (!shade_prepare(sd, r.c)) FFX_FAIL(rf_scratch ? FFX_ERR_UNSUPPORTED : FFX_ERR_ARG, "%s: bad scene description%s", what, rf_scratch ? " (gaussian filter: stddev <= 0.5)" : "");
+  r.c.mats = shape_albedo;
+  const bool mat = r.c.mat_stride == FFX_MAT_STRIDE;
+  if (mat && !r.c.mat_inline && ((uintptr_t)shape_albedo & 15) != 0) FFX_FAIL(FFX_ERR_ARG, "%s: material rows must be 16-byte aligned", what);
+  r.n_pix = (long)r.c.cam.W * r.c.cam.H;
+  if (r.n_pix * spp >= (1L << 32)) FFX_FAIL(FFX_ERR_UNSUPPORTED, "%s: more than 2^32 samples", what);
+  r.b = blob_view(bvh, info);
+  r.spp = spp;
+  r.matm = !mat ? 0 : (r.c.n_base_tex > 0 ? 2 : 1);
+  r.seed_key = seed_key_of(seed);
+  if (!path_depths(flags, r.max_depth, r.rr_depth)) FFX_FAIL(FFX_ERR_ARG, "%s: max_depth must be 2 .. %d", what, FFX_RENDER_MAX_DEPTH_LIMIT);
+  return FFX_OK;
+}
+static PathArgs path_args(const RenderSetup &r) {
+  return {r.b.nodes, r.b.recs, r.b.nrec, r.spp, r.max_depth, r.rr_depth, r.seed_key, hash32(r.seed_key ^ 0x5bd1e995U)};
+}
+
+// what the packet kernels read besides the setup: the pre-pass's apex records (launch_apex), the wide tree and the grid — the film's 2x2-pixel tiles
+// enumerated in square blocks of 2^tb x 2^tb tiles (ptx carries tb in its top byte; pn counts the tiles of whole blocks, those outside the image are
+// skipped) at ppw pixels per wave (k_render_fwd_pk; the adjoint's 4 = a tile per wave)
+struct Packets { const TriApex *arecs; uint32_t astride; WideScene ws; int ptx, pn, pgrid, ppw; };
+static void packet_grid(Packets &p, const CamK &cam, int tb, int ppw) {
+  const int ptx = ffx_cdiv(cam.W, 2), pty = ffx_cdiv(cam.H, 2);
+  p.pn = (ffx_cdiv(ptx, 1 << tb) * ffx_cdiv(pty, 1 << tb)) << (2 * tb);
+  p.ptx = ptx | tb << 24;
+  p.pgrid = ((p.pn * (4 / ppw) + 7) / 8) * 8; // multiple of 8 so the XCD remap is a bijection onto [0, grid)
+  p.ppw = ppw;
+}
+// k_render_fwd_blk's pixel blocks: sample slots per pixel = the next power of two >= spp (at least min_slots), 64 / slots pixels per wave but at most
+// 2^cap, the blocks enumerated in whole 8 x 8 patches
+struct PixBlocks { int bw_log2, bh_log2, blocks_x, n_blocks; };
+static PixBlocks pixel_blocks(const CamK &cam, int spp, int min_slots, int cap) {
+  int slots = min_slots, ppw_log2 = 0;
+  while (slots < spp) slots <<= 1;
+  while ((slots << (ppw_log2 + 1)) <= 64) ++ppw_log2;
+  if (ppw_log2 > cap) ppw_log2 = cap;
+  const int bw_log2 = (ppw_log2 + 1) / 2, bh_log2 = ppw_log2 / 2, blocks_x = ffx_cdiv(cam.W, 1 << bw_log2);
+  return {bw_log2, bh_log2, blocks_x, 64 * ffx_cdiv(blocks_x, 8) * ffx_cdiv(ffx_cdiv(cam.H, 1 << bh_log2), 8)};
+}
+
+static int check_launch(const char *what) { FFX_CHECK_LAUNCH(what); return FFX_OK; }
+// the filtered calls' scratch: [pixel][25][4] partial sums, then G = gimg / weight as float4 per pixel (ffx_render_filter_bytes)
+static float4 *rf_G_area(void *rf_scratch, long n_pix) { return (float4 *)((float *)rf_scratch + (size_t)n_pix * 100); }
+// G = gimg / weight: the weight every pixel receives (the jitter alone decides it) into the partial sums, then the gather into G; NULL if a launch fails
+static float4 *rf_G(const RenderSetup &r, const float *gimg, void *rf_scratch, hipStream_t s, const char *what_weights, const char *what_gather) {
+  hipLaunchKernelGGL(k_rf_weights, dim3((unsigned)r.n_pix), dim3(64), 0, s, r.c.rf, (int)r.n_pix, r.spp, r.seed_key, (float *)rf_scratch);
+  if (check_launch(what_weights) != FFX_OK) return nullptr;
+  hipLaunchKernelGGL(k_rf_gather, dim3(ffx_cdiv(r.c.cam.W, 64), ffx_cdiv(r.c.cam.H, FFX_RFG_WAVES)), dim3(64 * FFX_RFG_WAVES), 0, s, (const float4 *)rf_scratch,
+                     r.c.cam.W, r.c.cam.H, 0, (void *)nullptr, gimg, rf_G_area(rf_scratch, r.n_pix));
+  return check_launch(what_gather) == FFX_OK ? rf_G_area(rf_scratch, r.n_pix) : nullptr;
+}
+// the image from the partial sums (and, if wsum is given, the weight every pixel received: ffx_render_fwd_cache_filtered)
+static int rf_develop(const RenderSetup &r, int fp16, void *img, void *rf_scratch, hipStream_t s, const char *what, float *wsum = nullptr) {
+  hipLaunchKernelGGL(k_rf_gather, dim3(ffx_cdiv(r.c.cam.W, 64), ffx_cdiv(r.c.cam.H, FFX_RFG_WAVES)), dim3(64 * FFX_RFG_WAVES), 0, s, (const float4 *)rf_scratch,
+                     r.c.cam.W, r.c.cam.H, fp16 & 1, img, (const float *)nullptr, (float4 *)nullptr, wsum);
+  FFX_CHECK_LAUNCH(what);
+  return FFX_OK;
+}
+
+// (wide, matm) as template arguments: f(std::bool_constant<WIDE>, std::integral_constant<int, MATM>).  The launchers instantiate only the kernels that
+// exist (`if constexpr`): the host refuses the other combinations first — a filtered film off the wide walk, textured base colours with an adjoint
+// cache or the fused adjoint.  (The order of the references is the order of the kernels in the code object.)
+template <class F> static void dispatch_wm(bool wide, int matm, F &&f) {
+  auto by_matm = [&](auto w) {
+    if (matm == 2) f(w, std::integral_constant<int, 2>());
+    else if (matm == 1) f(w, std::integral_constant<int, 1>());
+    else f(w, std::integral_constant<int, 0>());
+  };
+  if (wide) by_matm(std::true_type());
+  else by_matm(std::false_type());
+}
+// a k_render_fwd_pk launch's own arguments (the kernel's parameters: fp16, img, cache, cache_foot_off / cache_arena_off / cache_foot_b_off, ...)
+struct FwdPkArgs { int fp16; void *img; char *cache; uint32_t off[3], cap_stray; const float *adj_gimg; float *adj_gtex, *adj_dot; };
+// ADJ: k_render_fwd_pk's ADJ (0 / 1), or 2 for the box film's route, which takes the fused adjoint iff a.adj_gtex
+template <int ADJ, bool RF = false, bool RFC = false>
+static void launch_fwd_pk(bool wide, const RenderSetup &r, const Packets &p, const float *tex, const FwdPkArgs &a, hipStream_t s) {
+  dispatch_wm(wide, r.matm, [&](auto w, auto m) {
+    auto launch = [&](auto adj) {
+      constexpr bool WIDE = decltype(w)::value, A = decltype(adj)::value;
+      constexpr int MATM = decltype(m)::value;
+      if constexpr ((WIDE || !RF) && (MATM < 2 || (!A && !RFC)))
+        hipLaunchKernelGGL((k_render_fwd_pk<1, WIDE, MATM, A, RF, RFC>), dim3(p.pgrid), dim3(64), 0, s, r.c, r.b.nodes, r.b.recs, p.arecs, p.astride, p.ws,
+                           r.c.mats, tex, r.spp, r.seed_key, p.ptx, p.pn, xcd_mode(r.n_pix), a.fp16, a.img, a.cache, p.ppw, 1.0f / (float)r.spp, a.off[0],
+                           a.off[1], a.off[2], r.b.nrec, r.b.gn, a.cap_stray, a.adj_gimg, a.adj_gtex, a.adj_dot);
+    };
+    if constexpr (ADJ != 2) launch(std::bool_constant<ADJ == 1>());
+    else if (a.adj_gtex) launch(std::true_type());
+    else launch(std::false_type());
+  });
+}
+template <bool RF = false>
+static void launch_fwd_blk(bool wide, const RenderSetup &r, const Packets &p, const PixBlocks &pb, const float *tex, int fp16, void *img, hipStream_t s) {
+  dispatch_wm(wide, r.matm, [&](auto w, auto m) {
+    if constexpr (decltype(w)::value || !RF)
+      hipLaunchKernelGGL((k_render_fwd_blk<decltype(w)::value, decltype(m)::value, RF>), dim3(pb.n_blocks), dim3(64), 0, s, r.c, r.b.nodes, r.b.recs, p.arecs,
+                         p.astride, p.ws, r.c.mats, tex, r.spp, r.seed_key, pb.bw_log2, pb.bh_log2, pb.blocks_x, pb.n_blocks, fp16, img, 1.0f / (float)r.spp,
+                         r.b.nrec, r.b.gn);
+  });
+}
+template <bool RF>
+static void launch_bwd_pk(bool wide, const RenderSetup &r, const Packets &p, const float *gsrc, float *gtex, const DetK &det, hipStream_t s) {
+  dispatch_wm(wide, r.matm, [&](auto w, auto m) {
+    if constexpr (decltype(w)::value || !RF)
+      hipLaunchKernelGGL((k_render_bwd_pk<1, decltype(w)::value, decltype(m)::value, RF>), dim3(p.pgrid), dim3(64), 0, s, r.c, r.b.nodes, r.b.recs, p.arecs,
+                         p.astride, p.ws, r.c.mats, r.spp, r.seed_key, p.ptx, p.pn, xcd_mode(r.n_pix), gsrc, gtex, r.b.nrec, r.b.gn, det);
+  });
+}
+
 extern "C" {
 
 int ffx_trace_primary(const void *bvh, const ffx_bvh_info *info, const ffx_camera *cam, int spp, int jitter, uint32_t seed, float *t_out,
@@ -4793,8 +4943,7 @@ int ffx_trace_primary(const void *bvh, const ffx_bvh_info *info, const ffx_camer
   if (!cam_prepare(cam, k)) FFX_FAIL(FFX_ERR_ARG, "trace_primary: bad camera");
   long total = (long)k.W * k.H * spp;
   if (total >= (1L << 32)) FFX_FAIL(FFX_ERR_UNSUPPORTED, "trace_primary: more than 2^32 samples");
-  const BvhNode *nodes = (const BvhNode *)((const char *)bvh + info->off_nodes);
-  const TriRec *recs = (const TriRec *)((const char *)bvh + info->off_recs);
+  const BlobView b = blob_view(bvh, info);
   if (use_packet()) {
     // pixels per wave: 64 / spp when spp divides 64 (a compact bw x bh block), else one pixel per wave
     int ppw_log2 = 0;
@@ -4823,15 +4972,15 @@ int ffx_trace_primary(const void *bvh, const ffx_bvh_info *info, const ffx_camer
     const int jit = jitter & 1;
     const WideScene ws = wide_scene(bvh, info);
     if (use_wide(info))
-      hipLaunchKernelGGL(k_trace_primary_pk<true>, dim3(n_blocks), dim3(64), 0, (hipStream_t)s, k, nodes, recs, arecs, ws, spp, jit,
+      hipLaunchKernelGGL(k_trace_primary_pk<true>, dim3(n_blocks), dim3(64), 0, (hipStream_t)s, k, b.nodes, b.recs, arecs, ws, spp, jit,
                          seed_key_of(seed), bw_log2, bh_log2, blocks_x, n_blocks, t_out, shape_out, prim_out, bk);
     else
-      hipLaunchKernelGGL(k_trace_primary_pk<false>, dim3(n_blocks), dim3(64), 0, (hipStream_t)s, k, nodes, recs, arecs, ws, spp, jit,
+      hipLaunchKernelGGL(k_trace_primary_pk<false>, dim3(n_blocks), dim3(64), 0, (hipStream_t)s, k, b.nodes, b.recs, arecs, ws, spp, jit,
                          seed_key_of(seed), bw_log2, bh_log2, blocks_x, n_blocks, t_out, shape_out, prim_out, bk);
     FFX_CHECK_LAUNCH("trace_primary");
     return FFX_OK;
   }
-  hipLaunchKernelGGL(k_trace_primary, dim3(ffx_cdiv(total, TR_BLOCK)), dim3(TR_BLOCK), stack_bytes(info), (hipStream_t)s, k, nodes, recs, spp, jitter & 1,
+  hipLaunchKernelGGL(k_trace_primary, dim3(ffx_cdiv(total, TR_BLOCK)), dim3(TR_BLOCK), stack_bytes(info), (hipStream_t)s, k, b.nodes, b.recs, spp, jitter & 1,
                      seed_key_of(seed), total, t_out, shape_out, prim_out);
   FFX_CHECK_LAUNCH("trace_primary");
   return FFX_OK;
@@ -4843,33 +4992,12 @@ int ffx_trace_rays(const void *bvh, const ffx_bvh_info *info, const float *origi
   if (!bvh || !info || !origins || !dirs || !t_out || n < 0) FFX_FAIL(FFX_ERR_ARG, "trace_rays: bad argument");
   if (!check_info(info, "trace_rays")) return FFX_ERR_ARG;
   if (n == 0) return FFX_OK;
-  const BvhNode *nodes = (const BvhNode *)((const char *)bvh + info->off_nodes);
-  const TriRec *recs = (const TriRec *)((const char *)bvh + info->off_recs);
-  hipLaunchKernelGGL(k_trace_rays, dim3(ffx_cdiv(n, TR_BLOCK)), dim3(TR_BLOCK), stack_bytes(info), (hipStream_t)s, nodes, recs, origins, dirs, n, tmax,
+  const BlobView b = blob_view(bvh, info);
+  hipLaunchKernelGGL(k_trace_rays, dim3(ffx_cdiv(n, TR_BLOCK)), dim3(TR_BLOCK), stack_bytes(info), (hipStream_t)s, b.nodes, b.recs, origins, dirs, n, tmax,
                      t_out, shape_out, prim_out);
   FFX_CHECK_LAUNCH("trace_rays");
   return FFX_OK;
 }
-
-// the path integrator's depths from a flags word (include/ffx.h FFX_RENDER_PATH): 0 = a bad field, else 1 with max_depth (2: direct light only, the
-// existing kernels) and rr_depth
-static int path_depths(int flags, int &max_depth, int &rr_depth) {
-  const int md = (flags >> FFX_RENDER_MAX_DEPTH_SHIFT) & 15, rr = (flags >> FFX_RENDER_RR_DEPTH_SHIFT) & 15;
-  max_depth = md == 0 ? 2 : md;
-  rr_depth = rr == 0 ? 5 : rr;
-  return max_depth >= 2 && max_depth <= FFX_RENDER_MAX_DEPTH_LIMIT;
-}
-static PathArgs path_args(const void *bvh, const ffx_bvh_info *info, int spp, uint32_t seed, int max_depth, int rr_depth) {
-  PathArgs a;
-  a.nodes = (const BvhNode *)((const char *)bvh + info->off_nodes);
-  a.recs = (const TriRec *)((const char *)bvh + info->off_recs);
-  a.nrec = info->off_nrec ? (const float4 *)((const char *)bvh + info->off_nrec) : nullptr;
-  a.spp = spp; a.max_depth = max_depth; a.rr_depth = rr_depth;
-  a.seed_key = seed_key_of(seed);
-  a.path_key = hash32(a.seed_key ^ 0x5bd1e995U);
-  return a;
-}
-static inline size_t path_stack_bytes(const ffx_bvh_info *info) { return (size_t)(info->max_depth < 8 ? 8 : info->max_depth) * 64 * sizeof(int); }
 
 static int render_fwd_impl(const void *bvh, const ffx_bvh_info *info, const ffx_scene_desc *sd, const float *shape_albedo, const float *tex, int spp,
                            uint32_t seed, int call_flags, void *img, void *cache, ffx_stream s, const float *adj_gimg = nullptr, float *adj_gtex = nullptr,
@@ -4877,37 +5005,19 @@ static int render_fwd_impl(const void *bvh, const ffx_bvh_info *info, const ffx_
   const int img_fp16 = call_flags & (FFX_RENDER_FP16 | FFX_RENDER_SPARSE_ADJOINT); // what the kernels see; the other bits steer the pre-pass
   if (!bvh || !info || !sd || (!shape_albedo && sd->n_mat_h <= 0) || !img || spp < 1) FFX_FAIL(FFX_ERR_ARG, "render_fwd: bad argument");
   if (sd->proj.enabled && !tex) FFX_FAIL(FFX_ERR_ARG, "render_fwd: projector enabled but tex is NULL");
-  if (!check_info(info, "render_fwd")) return FFX_ERR_ARG;
-  if ((sd->rfilter != FFX_RFILTER_BOX) != (rf_scratch != nullptr))
-    FFX_FAIL(FFX_ERR_UNSUPPORTED, rf_scratch ? "render_fwd_filtered: rfilter must be FFX_RFILTER_GAUSSIAN"
-                                             : "render_fwd: the scene's reconstruction filter is not the box (use ffx_render_fwd_filtered)");
-  if (rf_scratch && (!use_packet() || !use_wide(info))) FFX_FAIL(FFX_ERR_UNSUPPORTED, "render_fwd_filtered: only the default (wide packet) kernels carry the filter");
-  ShadeK c;
-  if (!shade_prepare(sd, c)) FFX_FAIL(rf_scratch ? FFX_ERR_UNSUPPORTED : FFX_ERR_ARG, "render_fwd: bad scene description%s", rf_scratch ? " (gaussian filter: stddev <= 0.5)" : "");
-  c.mats = shape_albedo;
-  const bool mat = c.mat_stride == FFX_MAT_STRIDE;
-  if (mat && !c.mat_inline && ((uintptr_t)shape_albedo & 15) != 0) FFX_FAIL(FFX_ERR_ARG, "render_fwd: material rows must be 16-byte aligned");
-  if ((long)c.cam.W * c.cam.H * spp >= (1L << 32)) FFX_FAIL(FFX_ERR_UNSUPPORTED, "render_fwd: more than 2^32 samples");
-  const BvhNode *nodes = (const BvhNode *)((const char *)bvh + info->off_nodes);
-  const TriRec *recs = (const TriRec *)((const char *)bvh + info->off_recs);
-  const float4 *nrec = info->off_nrec ? (const float4 *)((const char *)bvh + info->off_nrec) : nullptr; // vertex normals per slot (ffx_smooth)
-  const float4 *gn = info->off_gn ? (const float4 *)((const char *)bvh + info->off_gn) : nullptr;         // unit geometric normals per slot
-  int max_depth, rr_depth;
-  if (!path_depths(call_flags, max_depth, rr_depth)) FFX_FAIL(FFX_ERR_ARG, "render_fwd: max_depth must be 2 .. %d", FFX_RENDER_MAX_DEPTH_LIMIT);
-  if (max_depth > 2) { // the path integrator: one wave per pixel; no apex records, no tile bins
+  RenderSetup r;
+  if (const int rc = render_setup("render_fwd", bvh, info, sd, shape_albedo, spp, seed, call_flags, rf_scratch, r)) return rc;
+  const hipStream_t st = (hipStream_t)s;
+  if (r.max_depth > 2) { // the path integrator: one wave per pixel; no apex records, no tile bins
     if (cache || adj_gtex) FFX_FAIL(FFX_ERR_UNSUPPORTED, "render_fwd: max_depth > 2 has neither an adjoint cache nor a fused adjoint (use ffx_render_bwd)");
-    const long n_pix = (long)c.cam.W * c.cam.H;
-    if (n_pix >= (1L << 31)) FFX_FAIL(FFX_ERR_UNSUPPORTED, "render_fwd: more than 2^31 pixels");
-    const PathArgs pa = path_args(bvh, info, spp, seed, max_depth, rr_depth);
+    if (r.n_pix >= (1L << 31)) FFX_FAIL(FFX_ERR_UNSUPPORTED, "render_fwd: more than 2^31 pixels");
+    const PathArgs pa = path_args(r);
     if (rf_scratch) {
-      hipLaunchKernelGGL(k_path_fwd<true>, dim3((unsigned)n_pix), dim3(64), path_stack_bytes(info), (hipStream_t)s, c, pa, tex, 0, (void *)nullptr, (float *)rf_scratch);
+      hipLaunchKernelGGL(k_path_fwd<true>, dim3((unsigned)r.n_pix), dim3(64), path_stack_bytes(info), st, r.c, pa, tex, 0, (void *)nullptr, (float *)rf_scratch);
       FFX_CHECK_LAUNCH("render_fwd_filtered (path)");
-      hipLaunchKernelGGL(k_rf_gather, dim3(ffx_cdiv(c.cam.W, 64), ffx_cdiv(c.cam.H, FFX_RFG_WAVES)), dim3(64 * FFX_RFG_WAVES), 0, (hipStream_t)s, (const float4 *)rf_scratch, c.cam.W,
-                         c.cam.H, img_fp16 & 1, img, (const float *)nullptr, (float4 *)nullptr);
-      FFX_CHECK_LAUNCH("render_fwd_filtered (path)/gather");
-      return FFX_OK;
+      return rf_develop(r, img_fp16, img, rf_scratch, st, "render_fwd_filtered (path)/gather");
     }
-    hipLaunchKernelGGL(k_path_fwd<false>, dim3((unsigned)n_pix), dim3(64), path_stack_bytes(info), (hipStream_t)s, c, pa, tex, img_fp16 & 1, img, (float *)nullptr);
+    hipLaunchKernelGGL(k_path_fwd<false>, dim3((unsigned)r.n_pix), dim3(64), path_stack_bytes(info), st, r.c, pa, tex, img_fp16 & 1, img, (float *)nullptr);
     FFX_CHECK_LAUNCH("render_fwd (path)");
     return FFX_OK;
   }
@@ -4915,140 +5025,71 @@ static int render_fwd_impl(const void *bvh, const ffx_bvh_info *info, const ffx_
   if (cache && sd->proj.enabled && (sd->proj.tex_w > 4094 || sd->proj.tex_h > 4094 || sd->n_shapes > 255))
     FFX_FAIL(FFX_ERR_UNSUPPORTED, "render_fwd_cache: texture larger than 4094^2 or more than 255 shapes");
   if (adj_gtex && sd->n_base_tex > 0) FFX_FAIL(FFX_ERR_UNSUPPORTED, "render_fwd_adjoint: textured base colours (the footprint folds one base colour per shape): use ffx_render_bwd");
-  if ((use_packet() || cache || adj_gtex) && !gn) FFX_FAIL(FFX_ERR_ARG, "render_fwd: blob without per-slot normals (built by another library version?)");
-  if (use_packet() || cache || adj_gtex) { // the per-sample cache / the fused adjoint are the packet kernels' 
-    const int tb = tile_block_log2((long)c.cam.W * c.cam.H, cache != nullptr || adj_gtex != nullptr || rf_cache != nullptr);
-    int ptx = ffx_cdiv(c.cam.W, 2), pty = ffx_cdiv(c.cam.H, 2);
-    int pn = (ffx_cdiv(ptx, 1 << tb) * ffx_cdiv(pty, 1 << tb)) << (2 * tb); // whole blocks; tiles outside the image are skipped
-    ptx |= tb << 24;
-    const int ppw = pixels_per_wave(cache != nullptr || adj_gtex != nullptr || rf_cache != nullptr, (long)c.cam.W * c.cam.H);
-    int pgrid = ((pn * (4 / ppw) + 7) / 8) * 8; // multiple of 8 so the XCD remap is a bijection onto [0, grid)
-    const TriApex *arecs;
-    uint32_t astride;
+  const bool packet = use_packet() || cache || adj_gtex; // the per-sample cache / the fused adjoint are the packet kernels'
+  if (packet && !r.b.gn) FFX_FAIL(FFX_ERR_ARG, "render_fwd: blob without per-slot normals (built by another library version?)");
+  if (packet) {
+    const bool folds = cache != nullptr || adj_gtex != nullptr || rf_cache != nullptr;
+    Packets p;
+    packet_grid(p, r.c.cam, tile_block_log2(r.n_pix, folds), pixels_per_wave(folds, r.n_pix));
     // (capacity of the cache's arena: single-sample records of the box film's footprint cache / 64-sample blocks of the filtered film's record cache)
-    uint32_t cap_stray = cache ? (uint32_t)cache_stray_capacity(c.cam.W, c.cam.H, spp) : (rf_cache ? (uint32_t)rfc_cap_blocks((size_t)c.cam.W * c.cam.H, (size_t)spp, rfc_all(sd)) : 0u);
+    uint32_t cap_stray = cache ? (uint32_t)cache_stray_capacity(r.c.cam.W, r.c.cam.H, spp) : (rf_cache ? (uint32_t)rfc_cap_blocks((size_t)r.n_pix, (size_t)spp, rfc_all(sd)) : 0u);
     if (rf_cache)
       if (const char *ce = getenv("FFX_RFC_CAP")) { // (test knob, include/ffx.h: fewer blocks than the cache has room for — the overflow path)
         const long cv = atol(ce);
         if (cv >= 0 && (unsigned long)cv < cap_stray) cap_stray = (uint32_t)cv;
       }
-    if (!launch_apex(bvh, info, sd->cam.to_world, sd, &arecs, &astride, (hipStream_t)s, cache ? cache : rf_cache, cap_stray, call_flags)) return FFX_ERR_ARG;
-    const WideScene ws = wide_scene(bvh, info);
-    bins_k(bvh, info, sd, c.bins);
+    if (!launch_apex(bvh, info, sd->cam.to_world, sd, &p.arecs, &p.astride, st, cache ? cache : rf_cache, cap_stray, call_flags)) return FFX_ERR_ARG;
+    p.ws = wide_scene(bvh, info);
+    bins_k(bvh, info, sd, r.c.bins);
     // offsets of the cache areas in units of 128 bytes (both are multiples of 128; a 1024^2 x 256-spp cache is 160 MB)
-    const uint32_t foot_off = (uint32_t)(cache_off_foot((size_t)c.cam.W * c.cam.H) >> 7), arena_off = (uint32_t)(cache_off_arena((size_t)c.cam.W * c.cam.H) >> 7);
-    const uint32_t foot_b_off = (uint32_t)(cache_off_foot_b((size_t)c.cam.W * c.cam.H, cache_stray_capacity(c.cam.W, c.cam.H, spp)) >> 7);
-#define FFX_LAUNCH_FWD_(WIDE_, MAT_, ADJ_)                                                                                                               \
-  hipLaunchKernelGGL((k_render_fwd_pk<1, WIDE_, MAT_, ADJ_>), dim3(pgrid), dim3(64), 0, (hipStream_t)s, c, nodes, recs, arecs, astride, ws, \
-                     shape_albedo, tex, spp, seed_key_of(seed), ptx, pn, xcd_mode((long)c.cam.W * c.cam.H), img_fp16, img, (char *)cache, ppw, 1.0f / (float)spp, foot_off,     \
-                     arena_off, foot_b_off, nrec, gn, cap_stray, adj_gimg, adj_gtex, adj_dot)
-#define FFX_LAUNCH_FWD(WIDE_, MAT_) do { if (adj_gtex) FFX_LAUNCH_FWD_(WIDE_, MAT_, true); else FFX_LAUNCH_FWD_(WIDE_, MAT_, false); } while (0)
-    const int matm = !mat ? 0 : (c.n_base_tex > 0 ? 2 : 1); // (textured base colours: their own instantiation — the default kernels pay nothing)
+    const uint32_t foot_off = (uint32_t)(cache_off_foot((size_t)r.n_pix) >> 7), arena_off = (uint32_t)(cache_off_arena((size_t)r.n_pix) >> 7);
+    const uint32_t foot_b_off = (uint32_t)(cache_off_foot_b((size_t)r.n_pix, cache_stray_capacity(r.c.cam.W, r.c.cam.H, spp)) >> 7);
     if (rf_scratch && adj_gtex) { // ... with the adjoint of a loss that is linear in the image folded in (ffx_render_fwd_adjoint_filtered)
-      if (sd->proj.tex_channels != 1 || matm == 2) FFX_FAIL(FFX_ERR_UNSUPPORTED, "render_fwd_adjoint_filtered: 1-channel projector textures without textured base colours (use ffx_render_fwd_filtered + ffx_render_bwd_filtered)");
-      // the weight every pixel will receive (the jitter alone decides it) -> G = gimg / weight behind the partial sums; then the render, whose
-      // footprints take every sample's own gradient from G; then the image
-      const int n_pix = c.cam.W * c.cam.H;
-      float *part = (float *)rf_scratch;
-      float4 *G = (float4 *)(part + (size_t)n_pix * 100);
-      hipLaunchKernelGGL(k_rf_weights, dim3(n_pix), dim3(64), 0, (hipStream_t)s, c.rf, n_pix, spp, seed_key_of(seed), part);
-      FFX_CHECK_LAUNCH("render_fwd_adjoint_filtered/weights");
-      hipLaunchKernelGGL(k_rf_gather, dim3(ffx_cdiv(c.cam.W, 64), ffx_cdiv(c.cam.H, FFX_RFG_WAVES)), dim3(64 * FFX_RFG_WAVES), 0, (hipStream_t)s, (const float4 *)part, c.cam.W,
-                         c.cam.H, 0, (void *)nullptr, adj_gimg, G);
-      FFX_CHECK_LAUNCH("render_fwd_adjoint_filtered/gather G");
-#define FFX_LAUNCH_RFA(MAT_)                                                                                                                             \
-  hipLaunchKernelGGL((k_render_fwd_pk<1, true, MAT_, true, true>), dim3(pgrid), dim3(64), 0, (hipStream_t)s, c, nodes, recs, arecs, astride, ws, \
-                     shape_albedo, tex, spp, seed_key_of(seed), ptx, pn, xcd_mode((long)c.cam.W * c.cam.H), img_fp16, img, (char *)rf_scratch, ppw,          \
-                     1.0f / (float)spp, foot_off, arena_off, foot_b_off, nrec, gn, cap_stray, (const float *)G, adj_gtex, (float *)nullptr)
-      if (matm == 1) FFX_LAUNCH_RFA(1); else FFX_LAUNCH_RFA(0);
-#undef FFX_LAUNCH_RFA
+      if (sd->proj.tex_channels != 1 || r.matm == 2) FFX_FAIL(FFX_ERR_UNSUPPORTED, "render_fwd_adjoint_filtered: 1-channel projector textures without textured base colours (use ffx_render_fwd_filtered + ffx_render_bwd_filtered)");
+      // G = gimg / weight behind the partial sums; then the render, whose footprints take every sample's own gradient from G; then the image
+      const float4 *G = rf_G(r, adj_gimg, rf_scratch, st, "render_fwd_adjoint_filtered/weights", "render_fwd_adjoint_filtered/gather G");
+      if (!G) return FFX_ERR_LAUNCH;
+      launch_fwd_pk<1, true>(true, r, p, tex, {img_fp16, img, (char *)rf_scratch, {foot_off, arena_off, foot_b_off}, cap_stray, (const float *)G, adj_gtex, nullptr}, st);
       FFX_CHECK_LAUNCH("render_fwd_adjoint_filtered");
-      hipLaunchKernelGGL(k_rf_gather, dim3(ffx_cdiv(c.cam.W, 64), ffx_cdiv(c.cam.H, FFX_RFG_WAVES)), dim3(64 * FFX_RFG_WAVES), 0, (hipStream_t)s, (const float4 *)rf_scratch, c.cam.W,
-                         c.cam.H, img_fp16 & 1, img, (const float *)nullptr, (float4 *)nullptr);
-      FFX_CHECK_LAUNCH("render_fwd_adjoint_filtered/gather");
-      return FFX_OK;
+      return rf_develop(r, img_fp16, img, rf_scratch, st, "render_fwd_adjoint_filtered/gather");
     }
     if (rf_scratch && rf_cache) { // ... that also stores its adjoint's per-sample records (ffx_render_fwd_cache_filtered; rfc_off_* above)
-      if (matm == 2) FFX_FAIL(FFX_ERR_UNSUPPORTED, "render_fwd_cache_filtered: textured base colours (the records carry one base colour per shape): use ffx_render_bwd_filtered");
+      if (r.matm == 2) FFX_FAIL(FFX_ERR_UNSUPPORTED, "render_fwd_cache_filtered: textured base colours (the records carry one base colour per shape): use ffx_render_bwd_filtered");
       if (sd->proj.enabled && (sd->proj.tex_w > 4094 || sd->proj.tex_h > 4094 || sd->n_shapes > 255)) FFX_FAIL(FFX_ERR_UNSUPPORTED, "render_fwd_cache_filtered: texture larger than 4094^2 or more than 255 shapes");
       if (spp > 1024) FFX_FAIL(FFX_ERR_UNSUPPORTED, "render_fwd_cache_filtered: more than 1024 samples per pixel (16 passes)");
-      const size_t n_pix = (size_t)c.cam.W * c.cam.H;
+      const size_t n_pix = (size_t)r.n_pix;
       const uint32_t recs_off = (uint32_t)(rfc_off_recs(n_pix) >> 7), facb_off = (uint32_t)(rfc_off_facb(n_pix, (size_t)spp, rfc_all(sd)) >> 7);
-#define FFX_LAUNCH_RFC(MAT_)                                                                                                                              \
-  hipLaunchKernelGGL((k_render_fwd_pk<1, true, MAT_, false, true, true>), dim3(pgrid), dim3(64), 0, (hipStream_t)s, c, nodes, recs, arecs, astride, ws, \
-                     shape_albedo, tex, spp, seed_key_of(seed), ptx, pn, xcd_mode((long)c.cam.W * c.cam.H), img_fp16, img, (char *)rf_scratch, ppw,       \
-                     1.0f / (float)spp, recs_off, arena_off, facb_off, nrec, gn, cap_stray, (const float *)nullptr, (float *)rf_cache, (float *)nullptr)
-      if (matm == 1) FFX_LAUNCH_RFC(1); else FFX_LAUNCH_RFC(0);
-#undef FFX_LAUNCH_RFC
+      launch_fwd_pk<0, true, true>(true, r, p, tex, {img_fp16, img, (char *)rf_scratch, {recs_off, arena_off, facb_off}, cap_stray, nullptr, (float *)rf_cache, nullptr}, st);
       FFX_CHECK_LAUNCH("render_fwd_cache_filtered");
-      hipLaunchKernelGGL(k_rf_gather, dim3(ffx_cdiv(c.cam.W, 64), ffx_cdiv(c.cam.H, FFX_RFG_WAVES)), dim3(64 * FFX_RFG_WAVES), 0, (hipStream_t)s, (const float4 *)rf_scratch, c.cam.W, c.cam.H,
-                         img_fp16 & 1, img, (const float *)nullptr, (float4 *)nullptr, (float *)((char *)rf_cache + rfc_off_wsum(n_pix)));
-      FFX_CHECK_LAUNCH("render_fwd_cache_filtered/gather");
-      return FFX_OK;
+      return rf_develop(r, img_fp16, img, rf_scratch, st, "render_fwd_cache_filtered/gather", (float *)((char *)rf_cache + rfc_off_wsum(n_pix)));
     }
     if (rf_scratch && spp <= 32 && lowspp_blocks()) { // ... below 33 samples per pixel: several pixels per wave, the same scratch contents (k_render_fwd_blk<..., RF>)
-      int slots = 8; // (at least 8 sample slots per pixel: rf_fold_blk reads them in groups of four, two pixels per round)
-      while (slots < spp) slots <<= 1;
-      int ppw_log2 = 0;
-      while ((slots << (ppw_log2 + 1)) <= 64) ++ppw_log2; // 8 / 4 / 2 pixels per wave at <= 8 / 16 / 32 spp
-      const int bw_log2 = (ppw_log2 + 1) / 2, bh_log2 = ppw_log2 / 2;
-      const int blocks_x = ffx_cdiv(c.cam.W, 1 << bw_log2), n_blocks = 64 * ffx_cdiv(blocks_x, 8) * ffx_cdiv(ffx_cdiv(c.cam.H, 1 << bh_log2), 8); // (whole 8 x 8 patches)
-#define FFX_LAUNCH_BLKF(MAT_)                                                                                                                            \
-  hipLaunchKernelGGL((k_render_fwd_blk<true, MAT_, true>), dim3(n_blocks), dim3(64), 0, (hipStream_t)s, c, nodes, recs, arecs, astride, ws, \
-                     shape_albedo, tex, spp, seed_key_of(seed), bw_log2, bh_log2, blocks_x, n_blocks, img_fp16 & 1, rf_scratch, 1.0f / (float)spp, nrec, gn)
-      if (matm == 2) FFX_LAUNCH_BLKF(2); else if (matm == 1) FFX_LAUNCH_BLKF(1); else FFX_LAUNCH_BLKF(0);
-#undef FFX_LAUNCH_BLKF
+      // (at least 8 sample slots per pixel: rf_fold_blk reads them in groups of four, two pixels per round -> 8 / 4 / 2 pixels per wave at <= 8 / 16 / 32 spp)
+      launch_fwd_blk<true>(true, r, p, pixel_blocks(r.c.cam, spp, 8, 3), tex, img_fp16 & 1, rf_scratch, st);
       FFX_CHECK_LAUNCH("render_fwd_filtered (pixel blocks)");
-      hipLaunchKernelGGL(k_rf_gather, dim3(ffx_cdiv(c.cam.W, 64), ffx_cdiv(c.cam.H, FFX_RFG_WAVES)), dim3(64 * FFX_RFG_WAVES), 0, (hipStream_t)s, (const float4 *)rf_scratch, c.cam.W, c.cam.H,
-                         img_fp16 & 1, img, (const float *)nullptr, (float4 *)nullptr);
-      FFX_CHECK_LAUNCH("render_fwd_filtered/gather");
-      return FFX_OK;
+      return rf_develop(r, img_fp16, img, rf_scratch, st, "render_fwd_filtered/gather");
     }
     if (rf_scratch) { // the filtered render: the kernel leaves every pixel's 25 x 4 outgoing sums in the scratch area, the gather forms the image
-#define FFX_LAUNCH_RF(MAT_)                                                                                                                               \
-  hipLaunchKernelGGL((k_render_fwd_pk<1, true, MAT_, false, true>), dim3(pgrid), dim3(64), 0, (hipStream_t)s, c, nodes, recs, arecs, astride, ws, \
-                     shape_albedo, tex, spp, seed_key_of(seed), ptx, pn, xcd_mode((long)c.cam.W * c.cam.H), img_fp16 & 1, img, (char *)rf_scratch, ppw,       \
-                     1.0f / (float)spp, foot_off, arena_off, foot_b_off, nrec, gn, cap_stray, adj_gimg, adj_gtex, adj_dot)
-      if (matm == 2) FFX_LAUNCH_RF(2); else if (matm == 1) FFX_LAUNCH_RF(1); else FFX_LAUNCH_RF(0);
-#undef FFX_LAUNCH_RF
+      launch_fwd_pk<0, true>(true, r, p, tex, {img_fp16 & 1, img, (char *)rf_scratch, {foot_off, arena_off, foot_b_off}, cap_stray, adj_gimg, adj_gtex, adj_dot}, st);
       FFX_CHECK_LAUNCH("render_fwd_filtered");
-      hipLaunchKernelGGL(k_rf_gather, dim3(ffx_cdiv(c.cam.W, 64), ffx_cdiv(c.cam.H, FFX_RFG_WAVES)), dim3(64 * FFX_RFG_WAVES), 0, (hipStream_t)s, (const float4 *)rf_scratch, c.cam.W, c.cam.H,
-                         img_fp16 & 1, img, (const float *)nullptr, (float4 *)nullptr);
-      FFX_CHECK_LAUNCH("render_fwd_filtered/gather");
-      return FFX_OK;
+      return rf_develop(r, img_fp16, img, rf_scratch, st, "render_fwd_filtered/gather");
     }
     if (!cache && !adj_gtex && spp <= 32 && lowspp_blocks()) {
       // fewer than 64 samples per pixel: several pixels per wave (k_render_fwd_blk).  Sample slots per pixel = the next power of two >= spp; the
       // block never exceeds 8 pixels (K7's reason, ffx_trace_primary: thinner packets, fewer exact tests per walk, more waves)
-      int slots = 1;
-      while (slots < spp) slots <<= 1;
-      int ppw_log2 = 0;
-      while ((slots << (ppw_log2 + 1)) <= 64) ++ppw_log2;
-      const int cap = spp == 1 ? 4 : 3;
-      if (ppw_log2 > cap) ppw_log2 = cap;
-      const int bw_log2 = (ppw_log2 + 1) / 2, bh_log2 = ppw_log2 / 2;
-      const int blocks_x = ffx_cdiv(c.cam.W, 1 << bw_log2), n_blocks = 64 * ffx_cdiv(blocks_x, 8) * ffx_cdiv(ffx_cdiv(c.cam.H, 1 << bh_log2), 8); // (whole 8 x 8 patches)
-#define FFX_LAUNCH_BLK(WIDE_, MAT_)                                                                                                                     \
-  hipLaunchKernelGGL((k_render_fwd_blk<WIDE_, MAT_>), dim3(n_blocks), dim3(64), 0, (hipStream_t)s, c, nodes, recs, arecs, astride, ws, \
-                     shape_albedo, tex, spp, seed_key_of(seed), bw_log2, bh_log2, blocks_x, n_blocks, img_fp16, img, 1.0f / (float)spp, nrec, gn)
-      if (use_wide(info)) { if (matm == 2) FFX_LAUNCH_BLK(true, 2); else if (matm == 1) FFX_LAUNCH_BLK(true, 1); else FFX_LAUNCH_BLK(true, 0); }
-      else { if (matm == 2) FFX_LAUNCH_BLK(false, 2); else if (matm == 1) FFX_LAUNCH_BLK(false, 1); else FFX_LAUNCH_BLK(false, 0); }
-#undef FFX_LAUNCH_BLK
+      launch_fwd_blk(use_wide(info), r, p, pixel_blocks(r.c.cam, spp, 1, spp == 1 ? 4 : 3), tex, img_fp16, img, st);
       FFX_CHECK_LAUNCH("render_fwd (pixel blocks)");
       return FFX_OK;
     }
-    if (use_wide(info)) { if (matm == 2) FFX_LAUNCH_FWD_(true, 2, false); else if (matm == 1) FFX_LAUNCH_FWD(true, 1); else FFX_LAUNCH_FWD(true, 0); }
-    else { if (matm == 2) FFX_LAUNCH_FWD_(false, 2, false); else if (matm == 1) FFX_LAUNCH_FWD(false, 1); else FFX_LAUNCH_FWD(false, 0); }
-#undef FFX_LAUNCH_FWD
-#undef FFX_LAUNCH_FWD_
+    launch_fwd_pk<2>(use_wide(info), r, p, tex, {img_fp16, img, (char *)cache, {foot_off, arena_off, foot_b_off}, cap_stray, adj_gimg, adj_gtex, adj_dot}, st);
     FFX_CHECK_LAUNCH("render_fwd");
     return FFX_OK;
   }
-  int tiles_x = ffx_cdiv(c.cam.W, 8), tiles_y = ffx_cdiv(c.cam.H, 8);
+  int tiles_x = ffx_cdiv(r.c.cam.W, 8), tiles_y = ffx_cdiv(r.c.cam.H, 8);
   int n_tiles = tiles_x * tiles_y;
   int grid = ((n_tiles + 7) / 8) * 8;
-  hipLaunchKernelGGL(k_render_fwd, dim3(grid), dim3(TR_BLOCK), stack_bytes(info), (hipStream_t)s, c, nodes, recs, nrec, shape_albedo, tex, spp,
-                     seed_key_of(seed), tiles_x, n_tiles, xcd_mode(), img_fp16, img);
+  hipLaunchKernelGGL(k_render_fwd, dim3(grid), dim3(TR_BLOCK), stack_bytes(info), st, r.c, r.b.nodes, r.b.recs, r.b.nrec, shape_albedo, tex, spp,
+                     r.seed_key, tiles_x, n_tiles, xcd_mode(), img_fp16, img);
   FFX_CHECK_LAUNCH("render_fwd");
   return FFX_OK;
 }
@@ -5154,12 +5195,7 @@ static int render_bwd_cached_impl(const ffx_scene_desc *sd, const float *shape_a
   BwdP p;
   memset(&p, 0, sizeof p);
   p.mats = shape_albedo;
-  if (sd->n_mat_h > 0) {
-    const int ms_ = sd->mat_stride ? sd->mat_stride : 3;
-    if (sd->n_mat_h > FFX_MAX_MAT_H || sd->n_mat_h != sd->n_shapes * ms_) FFX_FAIL(FFX_ERR_ARG, "render_bwd_cached: n_mat_h must be n_shapes x stride (<= %d)", FFX_MAX_MAT_H);
-    p.mat_inline = 1;
-    for (int i = 0; i < sd->n_mat_h; ++i) p.mat_h[i] = sd->mat_h[i];
-  }
+  if (!copy_mat_h(sd, sd->mat_stride ? sd->mat_stride : 3, p)) FFX_FAIL(FFX_ERR_ARG, "render_bwd_cached: n_mat_h must be n_shapes x stride (<= %d)", FFX_MAX_MAT_H);
   p.img = dot_out ? img : nullptr; p.img_fp16 = img_fp16 & 1; p.dot_out = dot_out;
   p.dot_slots = (int)ffx_render_dot_slots(sd->cam.width, sd->cam.height);
   if (l1_target) { // (sign(img - target) * weight / n per element; value weight / n * sum |img - target|: ffx_l1_value_grad's)
@@ -5202,83 +5238,47 @@ static int render_bwd_cached_impl(const ffx_scene_desc *sd, const float *shape_a
 static int render_bwd_impl(const void *bvh, const ffx_bvh_info *info, const ffx_scene_desc *sd, const float *shape_albedo, int spp, uint32_t seed, int flags,
                            const float *gimg, float *gtex, ffx_stream s, void *rf_scratch, void *det_ws = nullptr, const DetPart *det_part = nullptr) {
   if (!bvh || !info || !sd || (!shape_albedo && sd->n_mat_h <= 0) || !gimg || (!gtex && !det_part) || spp < 1) FFX_FAIL(FFX_ERR_ARG, "render_bwd: bad argument");
-  if ((sd->rfilter != FFX_RFILTER_BOX) != (rf_scratch != nullptr))
-    FFX_FAIL(FFX_ERR_UNSUPPORTED, rf_scratch ? "render_bwd_filtered: rfilter must be FFX_RFILTER_GAUSSIAN"
-                                             : "render_bwd: the scene's reconstruction filter is not the box (use ffx_render_bwd_filtered)");
-  if (rf_scratch && (!use_packet() || !use_wide(info))) FFX_FAIL(FFX_ERR_UNSUPPORTED, "render_bwd_filtered: only the default (wide packet) kernels carry the filter");
+  // (the filter is refused before a scene without projector returns, and that before the bvh info is looked at; render_setup's repeat then passes)
+  if (const int rc = check_filter("render_bwd", sd, info, rf_scratch)) return rc;
   if (!sd->proj.enabled) return FFX_OK;
-  if (!check_info(info, "render_bwd")) return FFX_ERR_ARG;
-  ShadeK c;
-  if (!shade_prepare(sd, c)) FFX_FAIL(rf_scratch ? FFX_ERR_UNSUPPORTED : FFX_ERR_ARG, "render_bwd: bad scene description%s", rf_scratch ? " (gaussian filter: stddev <= 0.5)" : "");
-  c.mats = shape_albedo;
-  const bool mat = c.mat_stride == FFX_MAT_STRIDE;
-  if (mat && !c.mat_inline && ((uintptr_t)shape_albedo & 15) != 0) FFX_FAIL(FFX_ERR_ARG, "render_bwd: material rows must be 16-byte aligned");
-  if ((long)c.cam.W * c.cam.H * spp >= (1L << 32)) FFX_FAIL(FFX_ERR_UNSUPPORTED, "render_bwd: more than 2^32 samples");
-  const BvhNode *nodes = (const BvhNode *)((const char *)bvh + info->off_nodes);
-  const TriRec *recs = (const TriRec *)((const char *)bvh + info->off_recs);
-  const float4 *nrec = info->off_nrec ? (const float4 *)((const char *)bvh + info->off_nrec) : nullptr;
-  const float4 *gn = info->off_gn ? (const float4 *)((const char *)bvh + info->off_gn) : nullptr;
-  int max_depth, rr_depth;
-  if (!path_depths(flags, max_depth, rr_depth)) FFX_FAIL(FFX_ERR_ARG, "render_bwd: max_depth must be 2 .. %d", FFX_RENDER_MAX_DEPTH_LIMIT);
-  if (max_depth > 2) { // the path integrator's adjoint: replays the forward's paths
+  RenderSetup r;
+  if (const int rc = render_setup("render_bwd", bvh, info, sd, shape_albedo, spp, seed, flags, rf_scratch, r)) return rc;
+  const hipStream_t st = (hipStream_t)s;
+  if (r.max_depth > 2) { // the path integrator's adjoint: replays the forward's paths
     if (det_ws || det_part) FFX_FAIL(FFX_ERR_UNSUPPORTED, "render_bwd_det: max_depth > 2 has no deterministic adjoint");
-    const long n_pix = (long)c.cam.W * c.cam.H;
-    if (n_pix >= (1L << 31)) FFX_FAIL(FFX_ERR_UNSUPPORTED, "render_bwd: more than 2^31 pixels");
-    const PathArgs pa = path_args(bvh, info, spp, seed, max_depth, rr_depth);
+    if (r.n_pix >= (1L << 31)) FFX_FAIL(FFX_ERR_UNSUPPORTED, "render_bwd: more than 2^31 pixels");
+    const PathArgs pa = path_args(r);
     if (rf_scratch) { // G = gimg / weight as in the re-tracing filtered adjoint below
-      float *part = (float *)rf_scratch;
-      float4 *G = (float4 *)(part + (size_t)n_pix * 100);
-      hipLaunchKernelGGL(k_rf_weights, dim3((unsigned)n_pix), dim3(64), 0, (hipStream_t)s, c.rf, (int)n_pix, spp, seed_key_of(seed), part);
-      FFX_CHECK_LAUNCH("render_bwd_filtered (path)/weights");
-      hipLaunchKernelGGL(k_rf_gather, dim3(ffx_cdiv(c.cam.W, 64), ffx_cdiv(c.cam.H, FFX_RFG_WAVES)), dim3(64 * FFX_RFG_WAVES), 0, (hipStream_t)s, (const float4 *)part, c.cam.W, c.cam.H, 0,
-                         (void *)nullptr, gimg, G);
-      FFX_CHECK_LAUNCH("render_bwd_filtered (path)/gather");
-      hipLaunchKernelGGL(k_path_bwd<true>, dim3((unsigned)n_pix), dim3(64), path_stack_bytes(info), (hipStream_t)s, c, pa, (const float *)G, gtex);
+      const float4 *G = rf_G(r, gimg, rf_scratch, st, "render_bwd_filtered (path)/weights", "render_bwd_filtered (path)/gather");
+      if (!G) return FFX_ERR_LAUNCH;
+      hipLaunchKernelGGL(k_path_bwd<true>, dim3((unsigned)r.n_pix), dim3(64), path_stack_bytes(info), st, r.c, pa, (const float *)G, gtex);
       FFX_CHECK_LAUNCH("render_bwd_filtered (path)");
       return FFX_OK;
     }
-    hipLaunchKernelGGL(k_path_bwd<false>, dim3((unsigned)n_pix), dim3(64), path_stack_bytes(info), (hipStream_t)s, c, pa, gimg, gtex);
+    hipLaunchKernelGGL(k_path_bwd<false>, dim3((unsigned)r.n_pix), dim3(64), path_stack_bytes(info), st, r.c, pa, gimg, gtex);
     FFX_CHECK_LAUNCH("render_bwd (path)");
     return FFX_OK;
   }
-  if (use_packet() && !gn) FFX_FAIL(FFX_ERR_ARG, "render_bwd: blob without per-slot normals (built by another library version?)");
+  if (use_packet() && !r.b.gn) FFX_FAIL(FFX_ERR_ARG, "render_bwd: blob without per-slot normals (built by another library version?)");
   if (use_packet()) {
-    const int tb = tile_block_log2((long)c.cam.W * c.cam.H);
-    int ptx = ffx_cdiv(c.cam.W, 2), pty = ffx_cdiv(c.cam.H, 2);
-    int pn = (ffx_cdiv(ptx, 1 << tb) * ffx_cdiv(pty, 1 << tb)) << (2 * tb);
-    ptx |= tb << 24;
-    int pgrid = ((pn + 7) / 8) * 8;
-    const TriApex *arecs;
-    uint32_t astride;
-    if (!launch_apex(bvh, info, sd->cam.to_world, sd, &arecs, &astride, (hipStream_t)s, nullptr, 0, flags & FFX_RENDER_APEX_READY)) return FFX_ERR_ARG;
-    const WideScene ws = wide_scene(bvh, info);
-    bins_k(bvh, info, sd, c.bins);
+    Packets p;
+    packet_grid(p, r.c.cam, tile_block_log2(r.n_pix), 4);
+    if (!launch_apex(bvh, info, sd->cam.to_world, sd, &p.arecs, &p.astride, st, nullptr, 0, flags & FFX_RENDER_APEX_READY)) return FFX_ERR_ARG;
+    p.ws = wide_scene(bvh, info);
+    bins_k(bvh, info, sd, r.c.bins);
     DetK det;
     memset(&det, 0, sizeof det);
-    const int matm = !mat ? 0 : (c.n_base_tex > 0 ? 2 : 1);
     const float *gsrc = gimg; // what the kernel gathers from: gimg, or (filtered film) G = gimg / weight as float4 per pixel
     if (rf_scratch) {
       // 1. the weight every pixel received (jitter only) -> G = gimg / weight behind the partial sums; 2. the re-trace gathers through the filter
-      const int n_pix = c.cam.W * c.cam.H;
-      float *part = (float *)rf_scratch;
-      float4 *G = (float4 *)(part + (size_t)n_pix * 100);
-      hipLaunchKernelGGL(k_rf_weights, dim3(n_pix), dim3(64), 0, (hipStream_t)s, c.rf, n_pix, spp, seed_key_of(seed), part);
-      FFX_CHECK_LAUNCH("render_bwd_filtered/weights");
-      hipLaunchKernelGGL(k_rf_gather, dim3(ffx_cdiv(c.cam.W, 64), ffx_cdiv(c.cam.H, FFX_RFG_WAVES)), dim3(64 * FFX_RFG_WAVES), 0, (hipStream_t)s, (const float4 *)part, c.cam.W, c.cam.H, 0,
-                         (void *)nullptr, gimg, G);
-      FFX_CHECK_LAUNCH("render_bwd_filtered/gather");
-      gsrc = (const float *)G;
+      gsrc = (const float *)rf_G(r, gimg, rf_scratch, st, "render_bwd_filtered/weights", "render_bwd_filtered/gather");
+      if (!gsrc) return FFX_ERR_LAUNCH;
     }
     const bool wide = use_wide(info) != 0;
-#define FFX_LAUNCH_BWD(WIDE_, MAT_, RF_)                                                                                                                  \
-  hipLaunchKernelGGL((k_render_bwd_pk<1, WIDE_, MAT_, RF_>), dim3(pgrid), dim3(64), 0, (hipStream_t)s, c, nodes, recs, arecs, astride, ws, shape_albedo, \
-                     spp, seed_key_of(seed), ptx, pn, xcd_mode((long)c.cam.W * c.cam.H), gsrc, gtex, nrec, gn, det)
     auto launch = [&]() {
-      if (rf_scratch) { if (matm == 2) FFX_LAUNCH_BWD(true, 2, true); else if (matm == 1) FFX_LAUNCH_BWD(true, 1, true); else FFX_LAUNCH_BWD(true, 0, true); }
-      else if (wide) { if (matm == 2) FFX_LAUNCH_BWD(true, 2, false); else if (matm == 1) FFX_LAUNCH_BWD(true, 1, false); else FFX_LAUNCH_BWD(true, 0, false); }
-      else { if (matm == 2) FFX_LAUNCH_BWD(false, 2, false); else if (matm == 1) FFX_LAUNCH_BWD(false, 1, false); else FFX_LAUNCH_BWD(false, 0, false); }
+      if (rf_scratch) launch_bwd_pk<true>(true, r, p, gsrc, gtex, det, st);
+      else launch_bwd_pk<false>(wide, r, p, gsrc, gtex, det, st);
     };
-#undef FFX_LAUNCH_BWD
     if (det_part) { // one pass of the deterministic accumulation alone: the caller owns the accumulators and the scale (ffx_render_bwd_det_part)
       det.mode = det_part->part;
       det.vmax = det_part->vmax;
@@ -5291,15 +5291,15 @@ static int render_bwd_impl(const void *bvh, const ffx_bvh_info *info, const ffx_
     if (det_ws) {
       // deterministic accumulation (DetK above): the largest tap of the launch -> a power-of-two scale -> 64-bit fixed-point sums -> gtex.  The
       // scale needs the first pass's result on the host: ONE 4-byte read and a stream synchronisation per call (a debugging / cross-checking mode)
-      const long n_t = (long)c.tw * c.th * c.tc;
+      const long n_t = (long)r.c.tw * r.c.th * r.c.tc;
       det.fix = (unsigned long long *)det_ws;
       det.vmax = (unsigned int *)(det.fix + n_t);
-      if (hipMemsetAsync(det_ws, 0, (size_t)n_t * 8 + 8, (hipStream_t)s) != hipSuccess) FFX_FAIL(FFX_ERR_LAUNCH, "render_bwd_det: clearing the workspace failed");
+      if (hipMemsetAsync(det_ws, 0, (size_t)n_t * 8 + 8, st) != hipSuccess) FFX_FAIL(FFX_ERR_LAUNCH, "render_bwd_det: clearing the workspace failed");
       det.mode = 1;
       launch();
       FFX_CHECK_LAUNCH("render_bwd_det/max");
       unsigned int vbits = 0;
-      if (hipMemcpyAsync(&vbits, det.vmax, 4, hipMemcpyDeviceToHost, (hipStream_t)s) != hipSuccess || hipStreamSynchronize((hipStream_t)s) != hipSuccess)
+      if (hipMemcpyAsync(&vbits, det.vmax, 4, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
         FFX_FAIL(FFX_ERR_LAUNCH, "render_bwd_det: reading the largest tap failed");
       float vmax;
       memcpy(&vmax, &vbits, 4);
@@ -5312,12 +5312,12 @@ static int render_bwd_impl(const void *bvh, const ffx_bvh_info *info, const ffx_
       }
       // (b = bits of this launch's tap count — 4 taps per sample: 2^-36 of the largest tap at 512 x 512 x 64 spp; a fixed b = 34 — room for 2^32
       // samples — had left 2^-28, round-5 advisor)
-      const int sh = det_scale_log2(vbits, 4ull * (unsigned long long)c.cam.W * (unsigned long long)c.cam.H * (unsigned long long)(spp > 0 ? spp : 1));
+      const int sh = det_scale_log2(vbits, 4ull * (unsigned long long)r.c.cam.W * (unsigned long long)r.c.cam.H * (unsigned long long)(spp > 0 ? spp : 1));
       det.scale = ldexpf(1.0f, sh);
       det.mode = 2;
       launch();
       FFX_CHECK_LAUNCH("render_bwd_det/sum");
-      hipLaunchKernelGGL(k_det_finish, dim3(ffx_cdiv(n_t, 256)), dim3(256), 0, (hipStream_t)s, det.fix, 1.0f / det.scale, n_t, gtex);
+      hipLaunchKernelGGL(k_det_finish, dim3(ffx_cdiv(n_t, 256)), dim3(256), 0, st, det.fix, 1.0f / det.scale, n_t, gtex);
       FFX_CHECK_LAUNCH("render_bwd_det/finish");
       return FFX_OK;
     }
@@ -5326,10 +5326,10 @@ static int render_bwd_impl(const void *bvh, const ffx_bvh_info *info, const ffx_
     return FFX_OK;
   }
   if (det_ws || det_part) FFX_FAIL(FFX_ERR_UNSUPPORTED, "render_bwd_det: the per-lane kernels (FFX_TRAVERSAL=lane) have no deterministic mode");
-  int tiles_x = ffx_cdiv(c.cam.W, 8), tiles_y = ffx_cdiv(c.cam.H, 8);
+  int tiles_x = ffx_cdiv(r.c.cam.W, 8), tiles_y = ffx_cdiv(r.c.cam.H, 8);
   int n_tiles = tiles_x * tiles_y;
   int grid = ((n_tiles + 7) / 8) * 8;
-  hipLaunchKernelGGL(k_render_bwd, dim3(grid), dim3(TR_BLOCK), stack_bytes(info), (hipStream_t)s, c, nodes, recs, nrec, shape_albedo, spp, seed_key_of(seed),
+  hipLaunchKernelGGL(k_render_bwd, dim3(grid), dim3(TR_BLOCK), stack_bytes(info), st, r.c, r.b.nodes, r.b.recs, r.b.nrec, shape_albedo, spp, r.seed_key,
                      tiles_x, n_tiles, xcd_mode(), gimg, gtex);
   FFX_CHECK_LAUNCH("render_bwd");
   return FFX_OK;
@@ -5341,50 +5341,34 @@ static int render_bwd_appearance(const void *bvh, const ffx_bvh_info *info, cons
                                  const float *gimg, float *gtex, ffx_stream s, void *rf_scratch) {
   if (!bvh || !info || !sd || (!shape_albedo && sd->n_mat_h <= 0) || !gimg || !gtex || spp < 1) FFX_FAIL(FFX_ERR_ARG, "render_bwd: bad argument");
   if (flags & FFX_RENDER_PATH_MASK) FFX_FAIL(FFX_ERR_UNSUPPORTED, "render_bwd: FFX_RENDER_GRAD_APPEARANCE is served at max_depth 2 only");
-  const int rc = render_bwd_impl(bvh, info, sd, shape_albedo, spp, seed, flags & ~FFX_RENDER_GRAD_APPEARANCE, gimg, gtex, s, rf_scratch);
-  if (rc != FFX_OK) return rc;
-  if (!check_info(info, "render_bwd")) return FFX_ERR_ARG;
-  ShadeK c;
-  if (!shade_prepare(sd, c)) FFX_FAIL(rf_scratch ? FFX_ERR_UNSUPPORTED : FFX_ERR_ARG, "render_bwd: bad scene description%s", rf_scratch ? " (gaussian filter: stddev <= 0.5)" : "");
-  c.mats = shape_albedo;
-  if (c.mat_stride == FFX_MAT_STRIDE && !c.mat_inline && ((uintptr_t)shape_albedo & 15) != 0) FFX_FAIL(FFX_ERR_ARG, "render_bwd: material rows must be 16-byte aligned");
-  const long n_pix = (long)c.cam.W * c.cam.H;
-  if (n_pix * spp >= (1L << 32)) FFX_FAIL(FFX_ERR_UNSUPPORTED, "render_bwd: more than 2^32 samples");
+  if (const int rc = render_bwd_impl(bvh, info, sd, shape_albedo, spp, seed, flags & ~FFX_RENDER_GRAD_APPEARANCE, gimg, gtex, s, rf_scratch)) return rc;
+  RenderSetup r;
+  if (const int rc = render_setup("render_bwd", bvh, info, sd, shape_albedo, spp, seed, flags, rf_scratch, r)) return rc;
   if (sd->n_shapes < 1) FFX_FAIL(FFX_ERR_ARG, "render_bwd: n_shapes < 1");
   const long n_tex = (long)sd->proj.tex_w * sd->proj.tex_h * sd->proj.tex_channels;
   if (n_tex < 0) FFX_FAIL(FFX_ERR_ARG, "render_bwd: bad projector texture size");
+  const hipStream_t st = (hipStream_t)s;
   AppArgs a;
   memset(&a, 0, sizeof a);
-  a.nodes = (const BvhNode *)((const char *)bvh + info->off_nodes);
-  a.recs = (const TriRec *)((const char *)bvh + info->off_recs);
-  a.nrec = info->off_nrec ? (const float4 *)((const char *)bvh + info->off_nrec) : nullptr;
-  a.tex = sd->proj.enabled ? gimg + (size_t)n_pix * 3 : nullptr; // (the input half of the layout: the forward's texture behind gimg)
-  a.spp = spp; a.n_pix = (int)n_pix; a.n_shapes = sd->n_shapes;
-  a.seed_key = seed_key_of(seed);
-  a.grow = gtex + n_tex;
-  a.gspot = a.grow + (size_t)3 * sd->n_shapes;
+  a.nodes = r.b.nodes; a.recs = r.b.recs; a.nrec = r.b.nrec;
+  a.tex = sd->proj.enabled ? gimg + (size_t)r.n_pix * 3 : nullptr; // (the input half of the layout: the forward's texture behind gimg)
+  a.spp = spp; a.n_pix = (int)r.n_pix; a.n_shapes = sd->n_shapes; a.seed_key = r.seed_key;
+  a.grow = gtex + n_tex; a.gspot = a.grow + (size_t)3 * sd->n_shapes;
   float *bt = a.gspot + 3;
-  for (int k = 0; k < c.n_base_tex; ++k) {
+  for (int k = 0; k < r.c.n_base_tex; ++k) {
     a.gbt[k] = bt;
-    bt += (size_t)3 * c.btw[k] * c.bth[k];
+    bt += (size_t)3 * r.c.btw[k] * r.c.bth[k];
   }
   const float *gsrc = gimg;
-  if (rf_scratch) {
-    float *part = (float *)rf_scratch;
-    float4 *G = (float4 *)(part + (size_t)n_pix * 100);
-    if (!sd->proj.enabled) { // (the texture part launched nothing: G as it forms it)
-      hipLaunchKernelGGL(k_rf_weights, dim3((unsigned)n_pix), dim3(64), 0, (hipStream_t)s, c.rf, (int)n_pix, spp, seed_key_of(seed), part);
-      FFX_CHECK_LAUNCH("render_bwd_filtered (appearance)/weights");
-      hipLaunchKernelGGL(k_rf_gather, dim3(ffx_cdiv(c.cam.W, 64), ffx_cdiv(c.cam.H, FFX_RFG_WAVES)), dim3(64 * FFX_RFG_WAVES), 0, (hipStream_t)s, (const float4 *)part, c.cam.W,
-                         c.cam.H, 0, (void *)nullptr, gimg, G);
-      FFX_CHECK_LAUNCH("render_bwd_filtered (appearance)/gather");
-    }
-    gsrc = (const float *)G;
+  if (rf_scratch) { // G = gimg / weight: the texture part left it in the scratch, or (no projector) launched nothing and it is formed here
+    gsrc = (const float *)(sd->proj.enabled ? rf_G_area(rf_scratch, r.n_pix)
+                                            : rf_G(r, gimg, rf_scratch, st, "render_bwd_filtered (appearance)/weights", "render_bwd_filtered (appearance)/gather"));
+    if (!gsrc) return FFX_ERR_LAUNCH;
   }
-  const long blocks = ffx_cdiv(n_pix, (long)FFX_APP_WAVES);
+  const long blocks = ffx_cdiv(r.n_pix, (long)FFX_APP_WAVES);
   const unsigned grid = (unsigned)(blocks < 2048 ? blocks : 2048); // (every workgroup strides over the film: 2048 x 4 waves fill the device)
-  if (rf_scratch) hipLaunchKernelGGL(k_render_bwd_appearance<true>, dim3(grid), dim3(64 * FFX_APP_WAVES), stack_bytes(info), (hipStream_t)s, c, a, gsrc);
-  else hipLaunchKernelGGL(k_render_bwd_appearance<false>, dim3(grid), dim3(64 * FFX_APP_WAVES), stack_bytes(info), (hipStream_t)s, c, a, gsrc);
+  if (rf_scratch) hipLaunchKernelGGL(k_render_bwd_appearance<true>, dim3(grid), dim3(64 * FFX_APP_WAVES), stack_bytes(info), st, r.c, a, gsrc);
+  else hipLaunchKernelGGL(k_render_bwd_appearance<false>, dim3(grid), dim3(64 * FFX_APP_WAVES), stack_bytes(info), st, r.c, a, gsrc);
   FFX_CHECK_LAUNCH(rf_scratch ? "render_bwd_filtered (appearance)" : "render_bwd (appearance)");
   return FFX_OK;
 }
@@ -5491,11 +5475,7 @@ int ffx_render_bwd_cached_filtered(const ffx_scene_desc *sd, const float *shape_
   p.mats = shape_albedo;
   p.ms = sd->mat_stride ? sd->mat_stride : 3;
   if (p.ms != 3 && p.ms != FFX_MAT_STRIDE) FFX_FAIL(FFX_ERR_ARG, "render_bwd_cached_filtered: bad material stride");
-  if (sd->n_mat_h > 0) {
-    if (sd->n_mat_h > FFX_MAX_MAT_H || sd->n_mat_h != sd->n_shapes * p.ms) FFX_FAIL(FFX_ERR_ARG, "render_bwd_cached_filtered: n_mat_h must be n_shapes x stride (<= %d)", FFX_MAX_MAT_H);
-    p.mat_inline = 1;
-    for (int i = 0; i < sd->n_mat_h; ++i) p.mat_h[i] = sd->mat_h[i];
-  }
+  if (!copy_mat_h(sd, p.ms, p)) FFX_FAIL(FFX_ERR_ARG, "render_bwd_cached_filtered: n_mat_h must be n_shapes x stride (<= %d)", FFX_MAX_MAT_H);
   p.tw = sd->proj.tex_w; p.th = sd->proj.tex_h; p.tc = sd->proj.tex_channels; p.spp = spp;
   p.W = sd->cam.width; p.H = sd->cam.height;
   if (p.tw < 1 || p.th < 1 || (p.tc != 1 && p.tc != 3) || p.W < 1 || p.H < 1) FFX_FAIL(FFX_ERR_ARG, "render_bwd_cached_filtered: bad scene description");

@@ -338,3 +338,165 @@ def test_ctypes_mirrors_have_the_compilers_layout(tmp_path):
         assert int(got[cname]) == C.sizeof(cls), cname
         for fname, _ in cls._fields_:
             assert int(got[f"{cname}.{fname}"]) == getattr(cls, fname).offset, f"{cname}.{fname}"
+
+
+# the parameters of every render entry point, in order (include/ffx.h); `s` is the stream
+_RENDER_PARAMS = {
+    "ffx_render_fwd": "bvh info sd mats tex spp seed flags img s",
+    "ffx_render_fwd_cache": "bvh info sd mats tex spp seed flags img cache s",
+    "ffx_render_fwd_adjoint": "bvh info sd mats tex spp seed flags img gimg gtex dot s",
+    "ffx_render_fwd_filtered": "bvh info sd mats tex spp seed flags img scratch s",
+    "ffx_render_fwd_adjoint_filtered": "bvh info sd mats tex spp seed flags img gimg gtex scratch s",
+    "ffx_render_fwd_cache_filtered": "bvh info sd mats tex spp seed flags img cache scratch s",
+    "ffx_render_bwd": "bvh info sd mats spp seed flags gimg gtex s",
+    "ffx_render_bwd_filtered": "bvh info sd mats spp seed flags gimg gtex scratch s",
+    "ffx_render_bwd_det": "bvh info sd mats spp seed flags gimg gtex workspace s",
+    "ffx_render_bwd_det_part": "bvh info sd mats spp seed flags gimg part scale_log2 acc workspace s",
+    "ffx_render_bwd_cached": "sd mats cache spp gimg gtex img flags dot s",
+    "ffx_render_bwd_cached_l1": "sd mats cache spp img target weight gtex dot s",
+    "ffx_render_bwd_cached_filtered": "sd mats cache spp seed gimg gtex s",
+    "ffx_trace_primary": "bvh info cam spp flags seed t_out shape_out prim_out s",
+}
+_P3 = _abi.render_path(3, 5)
+_APP = _abi.RENDER_GRAD_APPEARANCE
+_GAUSS = {"rfilter": _abi.RFILTER_GAUSSIAN}
+_MISALIGNED = "misaligned"  # stands for a host address 4 bytes off a 16-byte boundary
+_BASE_TEX = {"mat_stride": _abi.MAT_STRIDE, "n_base_tex": 1, "base_tex_w": (4,), "base_tex_h": (4,), "base_tex": ("buf",), "slot_uv": "buf"}
+_ARG, _UNS = _abi_err("FFX_ERR_ARG"), _abi_err("FFX_ERR_UNSUPPORTED")
+# (entry point, scene / bvh info changes, argument changes, return code, message substring)
+_REFUSALS = [
+    # NULL buffers and counts
+    ("ffx_render_fwd", {}, {"img": None}, _ARG, "render_fwd: bad argument"),
+    ("ffx_render_fwd", {}, {"bvh": None}, _ARG, "render_fwd: bad argument"),
+    ("ffx_render_fwd", {}, {"mats": None}, _ARG, "render_fwd: bad argument"),
+    ("ffx_render_fwd", {}, {"spp": 0}, _ARG, "render_fwd: bad argument"),
+    ("ffx_render_fwd", {}, {"tex": None}, _ARG, "render_fwd: projector enabled but tex is NULL"),
+    ("ffx_render_fwd_cache", {}, {"cache": None}, _ARG, "render_fwd_cache: cache is NULL"),
+    ("ffx_render_fwd_adjoint", {}, {"gtex": None}, _ARG, "render_fwd_adjoint: gimg / gtex is NULL"),
+    ("ffx_render_fwd_adjoint", {"proj.enabled": 0}, {}, _ARG, "render_fwd_adjoint: the scene has no projector"),
+    ("ffx_render_fwd_filtered", _GAUSS, {"scratch": None}, _ARG, "render_fwd_filtered: scratch is NULL or not 16-byte aligned"),
+    ("ffx_render_fwd_adjoint_filtered", _GAUSS, {"gimg": None}, _ARG, "render_fwd_adjoint_filtered: gimg / gtex is NULL"),
+    ("ffx_render_fwd_cache_filtered", _GAUSS, {"cache": None}, _ARG, "render_fwd_cache_filtered: cache is NULL or not 16-byte aligned"),
+    ("ffx_render_bwd", {}, {"gimg": None}, _ARG, "render_bwd: bad argument"),
+    ("ffx_render_bwd", {}, {"flags": _APP, "gtex": None}, _ARG, "render_bwd: bad argument"),
+    ("ffx_render_bwd_filtered", _GAUSS, {"scratch": None}, _ARG, "render_bwd_filtered: scratch is NULL or not 16-byte aligned"),
+    ("ffx_render_bwd_det", {}, {"workspace": None}, _ARG, "render_bwd_det: workspace is NULL or not 16-byte aligned"),
+    ("ffx_render_bwd_det_part", {}, {"acc": None}, _ARG, "render_bwd_det_part: bad argument"),
+    ("ffx_render_bwd_det_part", {}, {"scale_log2": 127}, _ARG, "render_bwd_det_part: scale_log2 out of range"),
+    ("ffx_render_bwd_cached", {}, {"gimg": None}, _ARG, "render_bwd_cached: bad argument"),
+    ("ffx_render_bwd_cached_l1", {}, {"target": None}, _ARG, "render_bwd_cached_l1: bad argument"),
+    ("ffx_render_bwd_cached_filtered", _GAUSS, {"cache": None}, _ARG, "render_bwd_cached_filtered: bad argument"),
+    ("ffx_trace_primary", {}, {"t_out": None}, _ARG, "trace_primary: bad argument"),
+    # the bvh info, and what is checked before it
+    ("ffx_render_fwd", {"info.n_tris": 0}, {}, _ARG, "render_fwd: bad bvh info"),
+    ("ffx_render_fwd", {"info.n_tris": 0, **_GAUSS}, {}, _ARG, "render_fwd: bad bvh info"),
+    ("ffx_render_bwd", {"info.n_tris": 0}, {}, _ARG, "render_bwd: bad bvh info"),
+    ("ffx_render_bwd", {"info.n_tris": 0, **_GAUSS}, {}, _UNS, "render_bwd: the scene's reconstruction filter is not the box"),
+    ("ffx_render_bwd", {"info.n_tris": 0, "proj.enabled": 0}, {}, 0, None),  # nothing to differentiate: done before the info is looked at
+    ("ffx_trace_primary", {"info.n_tris": 0}, {}, _ARG, "trace_primary: bad bvh info"),
+    # the reconstruction filter against the entry point
+    ("ffx_render_fwd", _GAUSS, {}, _UNS, "render_fwd: the scene's reconstruction filter is not the box (use ffx_render_fwd_filtered)"),
+    ("ffx_render_fwd_filtered", {}, {}, _UNS, "render_fwd_filtered: rfilter must be FFX_RFILTER_GAUSSIAN"),
+    ("ffx_render_fwd_adjoint_filtered", {}, {}, _UNS, "render_fwd_filtered: rfilter must be FFX_RFILTER_GAUSSIAN"),
+    ("ffx_render_bwd", _GAUSS, {}, _UNS, "render_bwd: the scene's reconstruction filter is not the box (use ffx_render_bwd_filtered)"),
+    ("ffx_render_bwd_filtered", {}, {}, _UNS, "render_bwd_filtered: rfilter must be FFX_RFILTER_GAUSSIAN"),
+    ("ffx_render_bwd_filtered", {"proj.enabled": 0}, {}, _UNS, "render_bwd_filtered: rfilter must be FFX_RFILTER_GAUSSIAN"),
+    ("ffx_render_bwd_det", {"info.off_tq": 0, **_GAUSS}, {}, _UNS, "render_bwd_filtered: only the default (wide packet) kernels carry the filter"),
+    ("ffx_render_bwd_cached", _GAUSS, {}, _UNS, "render_bwd_cached: the scene's reconstruction filter is not the box (use ffx_render_bwd_filtered)"),
+    ("ffx_render_bwd_cached_filtered", {}, {}, _UNS, "render_bwd_cached_filtered: rfilter must be FFX_RFILTER_GAUSSIAN"),
+    ("ffx_render_fwd_filtered", {"info.off_tq": 0, **_GAUSS}, {}, _UNS, "render_fwd_filtered: only the default (wide packet) kernels carry the filter"),
+    ("ffx_render_bwd_filtered", {"info.off_tq": 0, **_GAUSS}, {}, _UNS, "render_bwd_filtered: only the default (wide packet) kernels carry the filter"),
+    ("ffx_render_fwd_filtered", {"rfilter_stddev": 0.75, **_GAUSS}, {}, _UNS, "render_fwd: bad scene description (gaussian filter: stddev <= 0.5)"),
+    ("ffx_render_bwd_filtered", {"rfilter_stddev": 0.75, **_GAUSS}, {}, _UNS, "render_bwd: bad scene description (gaussian filter: stddev <= 0.5)"),
+    ("ffx_render_bwd_cached_filtered", {"rfilter_stddev": 0.75, **_GAUSS}, {}, _UNS, "render_bwd_cached_filtered: gaussian filter: stddev <= 0.5"),
+    # the material table
+    ("ffx_render_fwd", {"mat_stride": 5}, {}, _ARG, "render_fwd: bad scene description"),
+    ("ffx_render_fwd", {"n_mat_h": 5}, {"mats": None}, _ARG, "render_fwd: bad scene description"),
+    ("ffx_render_bwd", {"mat_stride": 5}, {}, _ARG, "render_bwd: bad scene description"),
+    ("ffx_render_bwd", {"mat_stride": 5}, {"flags": _APP}, _ARG, "render_bwd: bad scene description"),
+    ("ffx_render_bwd_filtered", {"mat_stride": 5, **_GAUSS}, {}, _UNS, "render_bwd: bad scene description (gaussian filter"),
+    ("ffx_render_bwd_cached", {"mat_stride": 5}, {}, _ARG, "render_bwd_cached: bad material stride"),
+    ("ffx_render_bwd_cached", {"n_mat_h": 5}, {}, _ARG, "render_bwd_cached: n_mat_h must be n_shapes x stride (<= 128)"),
+    ("ffx_render_bwd_cached", {"n_mat_h": 3, "proj.tex_w": 0}, {}, _ARG, "render_bwd_cached: bad scene description"),
+    ("ffx_render_bwd_cached_filtered", {"mat_stride": 5, **_GAUSS}, {}, _ARG, "render_bwd_cached_filtered: bad material stride"),
+    ("ffx_render_bwd_cached_filtered", {"n_mat_h": 5, **_GAUSS}, {}, _ARG, "render_bwd_cached_filtered: n_mat_h must be n_shapes x stride (<= 128)"),
+    ("ffx_render_bwd_cached_filtered", {"n_shapes": 256, **_GAUSS}, {}, _UNS, "render_bwd_cached_filtered: 1 .. 255 shapes"),
+    # misaligned rows, caches and scratch
+    ("ffx_render_fwd", {"mat_stride": _abi.MAT_STRIDE}, {"mats": _MISALIGNED}, _ARG, "render_fwd: material rows must be 16-byte aligned"),
+    ("ffx_render_bwd", {"mat_stride": _abi.MAT_STRIDE}, {"mats": _MISALIGNED}, _ARG, "render_bwd: material rows must be 16-byte aligned"),
+    ("ffx_render_bwd", {"mat_stride": _abi.MAT_STRIDE, "proj.enabled": 0}, {"mats": _MISALIGNED, "flags": _APP}, _ARG,
+     "render_bwd: material rows must be 16-byte aligned"),
+    ("ffx_render_fwd_cache", {}, {"cache": _MISALIGNED}, _ARG, "render_fwd_cache: cache must be 16-byte aligned"),
+    ("ffx_render_fwd_filtered", _GAUSS, {"scratch": _MISALIGNED}, _ARG, "render_fwd_filtered: scratch is NULL or not 16-byte aligned"),
+    ("ffx_render_fwd_adjoint_filtered", _GAUSS, {"scratch": _MISALIGNED}, _ARG, "render_fwd_adjoint_filtered: scratch is NULL or not 16-byte aligned"),
+    ("ffx_render_fwd_cache_filtered", _GAUSS, {"scratch": _MISALIGNED}, _ARG, "render_fwd_cache_filtered: scratch is NULL or not 16-byte aligned"),
+    ("ffx_render_bwd_filtered", _GAUSS, {"scratch": _MISALIGNED}, _ARG, "render_bwd_filtered: scratch is NULL or not 16-byte aligned"),
+    ("ffx_render_bwd_det", {}, {"workspace": _MISALIGNED}, _ARG, "render_bwd_det: workspace is NULL or not 16-byte aligned"),
+    ("ffx_render_bwd_det_part", _GAUSS, {"workspace": _MISALIGNED}, _ARG, "render_bwd_det_part: a filtered film needs its scratch"),
+    ("ffx_render_bwd_det_part", {}, {"part": 2, "acc": _MISALIGNED}, _ARG, "render_bwd_det_part: bad argument"),
+    # the path integrator's bits and the appearance adjoint's bit on the entry points that refuse them
+    *[(f, _GAUSS if "filtered" in f else {}, {"flags": _P3}, _UNS, f"{f[4:]}: max_depth > 2 is served by ffx_render_fwd[_filtered] / ffx_render_bwd[_filtered] only")
+      for f in ("ffx_render_fwd_cache", "ffx_render_fwd_adjoint", "ffx_render_fwd_adjoint_filtered", "ffx_render_fwd_cache_filtered", "ffx_render_bwd_cached",
+                "ffx_render_bwd_det", "ffx_render_bwd_det_part")],
+    *[(f, _GAUSS if "filtered" in f else {}, {"flags": _APP}, _UNS, f"{f[4:]}: FFX_RENDER_GRAD_APPEARANCE is served by ffx_render_bwd[_filtered] only")
+      for f in ("ffx_render_fwd", "ffx_render_fwd_cache", "ffx_render_fwd_adjoint", "ffx_render_fwd_filtered", "ffx_render_fwd_adjoint_filtered",
+                "ffx_render_fwd_cache_filtered", "ffx_render_bwd_cached", "ffx_render_bwd_det", "ffx_render_bwd_det_part")],
+    ("ffx_render_bwd", {}, {"flags": _APP | _P3}, _UNS, "render_bwd: FFX_RENDER_GRAD_APPEARANCE is served at max_depth 2 only"),
+    ("ffx_render_bwd_filtered", _GAUSS, {"flags": _APP | _P3}, _UNS, "render_bwd: FFX_RENDER_GRAD_APPEARANCE is served at max_depth 2 only"),
+    ("ffx_render_bwd", {"proj.enabled": 0, "n_shapes": 0}, {"flags": _APP}, _ARG, "render_bwd: n_shapes < 1"),
+    # sample counts and film sizes
+    ("ffx_render_bwd_cached_filtered", _GAUSS, {"spp": 2048}, _UNS, "render_bwd_cached_filtered: more than 1024 samples per pixel"),
+    ("ffx_render_fwd", {"cam.width": 65536, "cam.height": 65536}, {"spp": 1}, _UNS, "render_fwd: more than 2^32 samples"),
+    ("ffx_render_bwd", {"cam.width": 65536, "cam.height": 65536}, {"spp": 1}, _UNS, "render_bwd: more than 2^32 samples"),
+    ("ffx_render_bwd", {"cam.width": 65536, "cam.height": 65536}, {"spp": 1, "flags": _APP}, _UNS, "render_bwd: more than 2^32 samples"),
+    ("ffx_trace_primary", {"cam.width": 65536, "cam.height": 65536}, {"spp": 1}, _UNS, "trace_primary: more than 2^32 samples"),
+    ("ffx_render_fwd", {"cam.width": 65536, "cam.height": 32768}, {"spp": 1, "flags": _P3}, _UNS, "render_fwd: more than 2^31 pixels"),
+    ("ffx_render_bwd", {"cam.width": 65536, "cam.height": 32768}, {"spp": 1, "flags": _P3}, _UNS, "render_bwd: more than 2^31 pixels"),
+    # textured base colours and large textures on the footprint-folding routes
+    ("ffx_render_fwd_cache", {"proj.enabled": 0, **_BASE_TEX}, {}, _UNS, "render_fwd_cache: textured base colours"),
+    ("ffx_render_fwd_adjoint", _BASE_TEX, {}, _UNS, "render_fwd_adjoint: textured base colours"),
+    ("ffx_render_fwd_cache", {"proj.tex_w": 5000}, {}, _UNS, "render_fwd_cache: texture larger than 4094^2 or more than 255 shapes"),
+    # max_depth out of range
+    *[(f, _GAUSS if "filtered" in f else {}, {"flags": md << _abi.RENDER_MAX_DEPTH_SHIFT}, _ARG, f"{f[4:14]}: max_depth must be 2 .. 8")
+      for f in ("ffx_render_fwd", "ffx_render_fwd_filtered", "ffx_render_bwd", "ffx_render_bwd_filtered") for md in (1, 9)],
+    # the last refusal in front of the launches: a blob without the per-slot normals the packet kernels read
+    ("ffx_render_fwd", {}, {}, _ARG, "render_fwd: blob without per-slot normals"),
+    ("ffx_render_bwd", {}, {}, _ARG, "render_bwd: blob without per-slot normals"),
+]
+
+
+@pytest.mark.parametrize("case", _REFUSALS, ids=lambda c: f"{c[0][4:]}-{c[4] or 'ok'}")
+def test_render_entry_points_refuse_before_any_launch(case, monkeypatch):
+    """every render entry point's refusals that come before its first launch, in the order the host code checks them: host dummy
+    pointers that the library never dereferences, a one-triangle bvh info without normals or apex areas (so that nothing can launch)"""
+    name, sd_changes, arg_changes, rc, msg = case
+    for knob in ("FFX_TRAVERSAL", "FFX_WIDE"):
+        monkeypatch.delenv(knob, raising=False)
+    lib = _lib.api().lib
+    buf = np.zeros(64, np.float32)
+    addr = (buf.ctypes.data + 15) & ~15
+    eye = _abi.mat16(np.eye(4))
+    sd = _abi.SceneDesc()
+    sd.cam.to_world, sd.cam.camera_to_sample, sd.cam.width, sd.cam.height = eye, eye, 4, 4
+    sd.proj.to_world, sd.proj.camera_to_sample, sd.proj.tex_w, sd.proj.tex_h, sd.proj.tex_channels, sd.proj.enabled = eye, eye, 4, 4, 1, 1
+    sd.n_shapes = 1
+    info = _abi.BvhInfo(n_tris=1, n_nodes=1, max_depth=1, off_tq=64)
+    val = lambda v: addr if v == "buf" else (addr + 4 if v == _MISALIGNED else v)  # noqa: E731
+    for key, v in sd_changes.items():
+        obj, attr = (info, key[5:]) if key.startswith("info.") else (sd, key)
+        while "." in attr:
+            head, attr = attr.split(".", 1)
+            obj = getattr(obj, head)
+        if isinstance(v, tuple):
+            getattr(obj, attr)[: len(v)] = [val(x) for x in v]
+        else:
+            setattr(obj, attr, val(v))
+    args = dict(bvh=addr, info=C.byref(info), sd=C.byref(sd), cam=C.byref(sd.cam), mats=addr, tex=addr, spp=4, seed=1, flags=0, img=addr, cache=addr,
+                scratch=addr, gimg=addr, gtex=addr, dot=addr, target=addr, weight=1.0, workspace=addr, part=1, scale_log2=0, acc=addr, t_out=addr,
+                shape_out=addr, prim_out=addr, s=None)
+    args.update({k: val(v) for k, v in arg_changes.items()})
+    got = getattr(lib, name)(*[args[p] for p in _RENDER_PARAMS[name].split()])
+    err = (lib.ffx_last_error() or b"").decode()
+    assert got == rc, (got, err)
+    if msg:
+        assert msg in err, err
