@@ -195,6 +195,17 @@ def appearance_floats(n_shapes, base_tex_hw=()):
     return 3 * int(n_shapes) + 3 + 3 * sum(int(h) * int(w) for h, w in base_tex_hw)
 
 
+# the BSDF's adjoint (include/ffx.h FFX_RENDER_GRAD_MATERIAL): with RENDER_GRAD_APPEARANCE only; [n_shapes][11] behind the appearance block, columns
+# FFX_MAT_ROUGHNESS .. FFX_MAT_CLEARCOAT_GLOSS (scenes.MAT_COLUMN) in order
+RENDER_GRAD_MATERIAL = 0x20000
+RENDER_MATERIAL_COLS = 11
+
+
+def material_floats(n_shapes):
+    """FFX_RENDER_MATERIAL_FLOATS: the floats of the material block behind the appearance block — [n_shapes][11]"""
+    return RENDER_MATERIAL_COLS * int(n_shapes)
+
+
 MAX_BASE_TEX = 4
 RFILTER_BOX, RFILTER_GAUSSIAN = 0, 1
 MAX_MAT_H = 128

@@ -541,6 +541,136 @@ __device__ __forceinline__ void material_terms(const float *__restrict__ m, cons
   if (TAU) *tau = tu * FFX_PI_F;
 }
 
+// ---- the BSDF's adjoint (FFX_RENDER_GRAD_MATERIAL): d (uA A + uB B) / d (the row's eleven parameters FFX_MAT_ROUGHNESS ..
+// FFX_MAT_CLEARCOAT_GLOSS), A and B as material_terms forms them, by one hand-derived reverse pass.  The geometry keeps the frame projections of
+// the anisotropic form for every row: d/d anisotropic at 0 needs them although the isotropic forward never forms the frame.  One-sided derivatives
+// into [0, 1] where the forward skips a lobe whose parameter is 0 (clearcoat, sheen, flatness, spec_tint, anisotropic; the diffuse and sheen lobes
+// at metallic = 1, the diffuse lobe at spec_trans = 1); active fmaxf(0.001, .) clamps give 0.  The eta column is d/d eta, except at eta = 1
+// where the forward skips the specular lobe and d/d eta vanishes: there it holds the limit of (d/d eta) / (eta - 1) as eta -> 1+, the factor
+// that a `specular` leaf at 0 chains with the finite limit of (eta - 1) d eta / d specular (mi.py, scenes.specular_to_eta_grad).
+#define FFX_MAT_GRAD_COLS FFX_RENDER_MATERIAL_COLS // columns FFX_MAT_ROUGHNESS .. FFX_MAT_CLEARCOAT_GLOSS (include/ffx.h FFX_RENDER_MATERIAL_FLOATS)
+static_assert(FFX_MAT_CLEARCOAT_GLOSS - FFX_MAT_ROUGHNESS + 1 == FFX_MAT_GRAD_COLS, "the material block's columns are the row's parameters in order");
+struct MatGeoD {
+  float cos_i, cos_o, ch, ci_h, co_h, s2; // as MatGeo
+  float hx, hy, vx, vy, lx, ly;           // the half vector, wv and wl in the shading frame coordinate_system(n)
+};
+__device__ __forceinline__ void material_geometry_d(v3 n, v3 wv, v3 wl, MatGeoD &g) {
+  g.cos_i = vdot(n, wv);
+  g.cos_o = vdot(n, wl);
+  v3 wh = V3(wv.x + wl.x, wv.y + wl.y, wv.z + wl.z);
+  const float ihl = __builtin_amdgcn_rsqf(vdot(wh, wh));
+  wh = V3(wh.x * ihl, wh.y * ihl, wh.z * ihl);
+  g.ci_h = vdot(wv, wh);
+  g.co_h = vdot(wl, wh);
+  g.ch = vdot(n, wh);
+  const float sg = copysignf(1.0f, n.z), ca = -brcp(sg + n.z), cb = n.x * n.y * ca;
+  const v3 fs = V3(sg * (sqrf(n.x) * ca) + 1.0f, sg * cb, -sg * n.x), ft = V3(cb, fmaf(n.y, n.y * ca, sg), -n.y);
+  g.hx = vdot(wh, fs); g.hy = vdot(wh, ft);
+  g.vx = vdot(wv, fs); g.vy = vdot(wv, ft);
+  g.lx = vdot(wl, fs); g.ly = vdot(wl, ft);
+  g.s2 = sqrf(g.hx) + sqrf(g.hy);
+}
+// lum: the luminance of the sample's base colour (the tint terms divide by it).  gr[j] += d (uA A + uB B) / d m[FFX_MAT_ROUGHNESS + j]
+__device__ __forceinline__ void material_terms_vjp(const float *__restrict__ m, const MatGeoD &g, float lum, float uA, float uB, float (&gr)[FFX_MAT_GRAD_COLS]) {
+  enum { R = 0, AN, ME, STR, ETA, STI, SH, SHT, FL, CC, CCG };
+  const float cos_i = g.cos_i, cos_o = g.cos_o, ch = g.ch, ci_h = g.ci_h, co_h = g.co_h;
+  if (!(cos_i > 0.f && cos_o > 0.f)) return;
+  const bool facing = ci_h > 0.f && co_h > 0.f;
+  const float wa = uA * FFX_PI_F, wb = uB * FFX_PI_F; // (A = pi a, B = pi b)
+  const float eta = m[FFX_MAT_ETA];
+  const float ct2 = 1.0f - (1.0f - ci_h * ci_h) * sqrf(brcp(eta));
+  const float ct = ct2 > 0.f ? bsqrt(ct2) : 0.f;
+  const float sw = schlick_weight(eta > 1.0f ? fabsf(ci_h) : ct);
+  const float c = fabsf(ci_h);
+  const float dct = ct2 > 0.f ? bdiv(1.0f - c * c, eta * eta * eta * ct) : 0.f; // d ct / d eta
+  const float ds = c + eta * ct, dp = ct + eta * c, ir = brcp(ds * dp);
+  const float a_s = (c - eta * ct) * dp * ir, a_p = (ct - eta * c) * ds * ir;
+  float F_d = 0.5f * (a_s * a_s + a_p * a_p), dFd = a_s * (-2.0f * c * (ct + eta * dct) * sqrf(brcp(ds))) + a_p * (2.0f * c * (eta * dct - ct) * sqrf(brcp(dp)));
+  if (eta == 1.0f) F_d = 0.f;
+  else if (c == 0.f) { F_d = 1.f; dFd = 0.f; }
+  const float metallic = m[FFX_MAT_METALLIC], m1 = 1.0f - metallic, spec_tint = m[FFX_MAT_SPEC_TINT];
+  // roughness, anisotropic -> ax, ay (calc_dist_params; aspect = 1 and ax = ay = max(0.001, roughness^2) for an isotropic row)
+  const float rough = m[FFX_MAT_ROUGHNESS], r2 = sqrf(rough), aspect = bsqrt(1.0f - 0.9f * m[FFX_MAT_ANISOTROPIC]);
+  const float axr = bdiv(r2, aspect), ayr = r2 * aspect, ax = fmaxf(0.001f, axr), ay = fmaxf(0.001f, ayr);
+  float d_sw = 0.f, d_eta = 0.f, d_ax = 0.f, d_ay = 0.f;
+  if (facing && (F_d > 0.f || eta == 1.0f)) { // main specular lobe: F D G / (4 cos_i) = F P
+    const float tmp = sqrf(bdiv(g.hx, ax)) + sqrf(bdiv(g.hy, ay)) + sqrf(ch);
+    const float xy_i = sqrf(ax * g.vx) + sqrf(ay * g.vy), xy_o = sqrf(ax * g.lx) + sqrf(ay * g.ly), axay = ax * ay;
+    const float dden = FFX_PI_F * axay * sqrf(tmp);
+    const float s_i = bsqrt(sqrf(cos_i) + xy_i), s_o = bsqrt(sqrf(cos_o) + xy_o);
+    float P = bdiv(cos_o, dden * ((cos_i + s_i) * (cos_o + s_o)));
+    if (!(ch > 1e-20f * dden)) P = 0.f;
+    const float ga = wa * P, gb = wb * P, gt = lum > 0.f ? bdiv(ga, lum) : gb; // (gt: the tint term t goes to a / lum, or to b when lum <= 0)
+    if (eta == 1.0f) { // the lobe is skipped; (d F_d / d eta) / (eta - 1) -> a_s'^2 + a_p'^2 = (1 + (1 - 2c^2)^2) / (4 c^4), (d R0 / d eta) / (eta - 1) -> 1/2
+      const float c2 = c * c;
+      const float dF1 = c > 0.f ? bdiv(1.0f + sqrf(1.0f - 2.0f * c2), 4.0f * c2 * c2) : 0.f;
+      d_eta = gb * m1 * (1.0f - spec_tint) * dF1 + gt * m1 * spec_tint * (1.0f - sw) * 0.5f;
+    } else {
+      const float R0 = sqrf((eta - 1.0f) * brcp(eta + 1.0f)), t = m1 * spec_tint * R0 * (1.0f - sw);
+      const float Fa = metallic * (1.0f - sw) + (lum > 0.f ? bdiv(t, lum) : 0.f);
+      const float Fb = metallic * sw + m1 * spec_tint * sw + m1 * (1.0f - spec_tint) * F_d + (lum > 0.f ? 0.f : t);
+      gr[ME] += ga * (1.0f - sw) + gb * (sw - spec_tint * sw - (1.0f - spec_tint) * F_d) - gt * spec_tint * R0 * (1.0f - sw);
+      gr[STI] += gb * m1 * (sw - F_d) + gt * m1 * R0 * (1.0f - sw);
+      d_sw += -ga * metallic + gb * (metallic + m1 * spec_tint) - gt * m1 * spec_tint * R0;
+      d_eta = gb * m1 * (1.0f - spec_tint) * dFd + gt * m1 * spec_tint * (1.0f - sw) * (4.0f * (eta - 1.0f) * brcp(sqrf(eta + 1.0f) * (eta + 1.0f)));
+      // P = cos_o / (pi axay tmp^2 (cos_i + s_i)(cos_o + s_o)) -> axay, tmp, xy_i, xy_o -> ax, ay
+      const float k = (wa * Fa + wb * Fb) * P;
+      const float d_axay = -bdiv(k, axay), d_tmp = -2.0f * bdiv(k, tmp);
+      const float d_xyi = -bdiv(k, 2.0f * s_i * (cos_i + s_i)), d_xyo = -bdiv(k, 2.0f * s_o * (cos_o + s_o));
+      d_ax = d_axay * ay - 2.0f * d_tmp * bdiv(sqrf(g.hx), ax * ax * ax) + 2.0f * ax * (d_xyi * sqrf(g.vx) + d_xyo * sqrf(g.lx));
+      d_ay = d_axay * ax - 2.0f * d_tmp * bdiv(sqrf(g.hy), ay * ay * ay) + 2.0f * ay * (d_xyi * sqrf(g.vy) + d_xyo * sqrf(g.ly));
+    }
+  }
+  const float cc = m[FFX_MAT_CLEARCOAT];
+  if (cc >= 0.f && facing) { // clearcoat: b += cc / 4 Fcc Dcc Gcc cos_o
+    const float Fcc = sw + (1.0f - sw) * 0.04f;
+    const float alpha = 0.1f + (0.001f - 0.1f) * m[FFX_MAT_CLEARCOAT_GLOSS], a2 = sqrf(alpha), c2 = sqrf(ch);
+    const float L = logf(a2), Q = g.s2 + a2 * c2;
+    float Dcc = bdiv(a2 - 1.0f, FFX_PI_F * L * Q);
+    if (!(Dcc * ch > 1e-20f)) Dcc = 0.f;
+    const float k = wb * 0.25f * ggx1_cc(cos_i, ci_h) * ggx1_cc(cos_o, co_h) * cos_o;
+    gr[CC] += k * Fcc * Dcc;
+    d_sw += k * cc * 0.96f * Dcc;
+    const float dD = Dcc * (brcp(a2 - 1.0f) - brcp(a2 * L) - bdiv(c2, Q)); // d Dcc / d a2
+    gr[CCG] += k * cc * Fcc * dD * 2.0f * alpha * (0.001f - 0.1f);
+  }
+  const float str = m[FFX_MAT_SPEC_TRANS];
+  if (m1 >= 0.f && 1.0f - str >= 0.f) { // diffuse + retro-reflection (+ fake subsurface): a += (1 - metallic)(1 - spec_trans) cos_o / pi dterm
+    const float Fo = schlick_weight(cos_o), Fi = schlick_weight(cos_i);
+    const float f_diff = (1.0f - 0.5f * Fi) * (1.0f - 0.5f * Fo);
+    const float Rr = 2.0f * rough * sqrf(co_h);
+    const float d0 = f_diff + Rr * (Fo + Fi + Fo * Fi * (Rr - 1.0f));
+    const float flat = m[FFX_MAT_FLATNESS];
+    const float Fss90 = Rr * 0.5f;
+    const float Fss = (1.0f + (Fss90 - 1.0f) * Fo) * (1.0f + (Fss90 - 1.0f) * Fi);
+    const float iso = brcp(cos_o + cos_i) - 0.5f;
+    const float f_ss = 1.25f * (Fss * iso + 0.5f);
+    const float dterm = flat > 0.f ? d0 + (f_ss - d0) * flat : d0;
+    const float dretro = Fo + Fi + Fo * Fi * (2.0f * Rr - 1.0f);
+    const float dss = 1.25f * iso * 0.5f * (Fo * (1.0f + (Fss90 - 1.0f) * Fi) + Fi * (1.0f + (Fss90 - 1.0f) * Fo));
+    const float k = wa * cos_o * 0.3183098861837907f, brdf = m1 * (1.0f - str);
+    gr[ME] -= (1.0f - str) * k * dterm;
+    gr[STR] -= m1 * k * dterm;
+    if (flat >= 0.f) gr[FL] += k * brdf * (f_ss - d0);
+    gr[R] += k * brdf * (flat > 0.f ? (1.0f - flat) * dretro + flat * dss : dretro) * 2.0f * sqrf(co_h);
+  }
+  const float sheen = m[FFX_MAT_SHEEN];
+  if (sheen >= 0.f && m1 >= 0.f) { // sheen: sv = sheen (1 - metallic) schlick(|co_h|) cos_o, to a (tint / lum) and b (1 - tint)
+    const float sh = schlick_weight(fabsf(co_h)) * cos_o, stt = m[FFX_MAT_SHEEN_TINT];
+    const float gsv = lum > 0.f ? wa * bdiv(stt, lum) + wb * (1.0f - stt) : wb;
+    gr[SH] += gsv * m1 * sh;
+    gr[ME] -= gsv * sheen * sh;
+    if (lum > 0.f) gr[SHT] += sheen * m1 * sh * (bdiv(wa, lum) - wb);
+  }
+  // eta: through F_d and R0 (d_eta), and through sw when eta < 1 (sw = schlick(ct))
+  if (eta < 1.0f && ct2 > 0.f && ct < 1.0f) d_eta += d_sw * (-5.0f * sqrf(sqrf(1.0f - ct))) * dct;
+  gr[ETA] += d_eta;
+  // ax = max(0.001, roughness^2 / aspect), ay = max(0.001, roughness^2 aspect), aspect = sqrt(1 - 0.9 anisotropic)
+  const float dx = axr > 0.001f ? d_ax : 0.f, dy = ayr > 0.001f ? d_ay : 0.f;
+  gr[R] += 2.0f * rough * (bdiv(dx, aspect) + dy * aspect);
+  gr[AN] += 0.45f * r2 * (bdiv(dx, aspect * aspect * aspect) - bdiv(dy, aspect));
+}
+
 // ---- the same two functions on a row whose constants the host has derived once (ShadeK.mat_pre, FFX_PRE_FLOATS floats per row): no squares, clamps
 // and reciprocals of parameters per evaluation, one flag word instead of five parameter loads and compares.  The arithmetic of the lobes is
 // material_terms', with the host's IEEE values where that one forms hardware seeds (a last-bit difference, inside the parity tolerance).
@@ -668,16 +798,22 @@ struct PathVtx { v3 Po, ng, ns; int textured, ok; };
 // what the appearance adjoint needs beyond the emitters' terms: the tint parts pi tau of both emitters' factors (proj_t scales like
 // proj_fac, spot_t like s_f), the spot's factors at unit intensity (spot = s_int s_f, spot_b = s_int s_fb), and where a textured base colour was read
 struct AppTerms { float proj_t, spot_t, s_f, s_fb; int tix, slot; float bu, bv; };
+// what the BSDF's adjoint needs (FFX_RENDER_GRAD_MATERIAL): the shading normal, both emitters' directions and the factors that multiply
+// pi f cos into their terms (proj_fac = kp bA, spot's f = ks bA; 0: the emitter does not light the sample)
+struct MatVtx { v3 ns, wp, ws; float kp, ks; };
 
 // the sample's hit in (nt, ft] and next-event estimation there: projector and spot terms, shadow rays, base colour.  PATH (the path kernels):
-// the ray has an arbitrary origin (no apex form) and *pv receives the vertex.  APP (k_render_bwd_appearance): *ap receives AppTerms
-template <bool PATH = false, bool APP = false>
+// the ray has an arbitrary origin (no apex form) and *pv receives the vertex.  APP (k_render_bwd_appearance): *ap receives AppTerms.  MAT
+// (k_render_bwd_material): *mv receives MatVtx
+template <bool PATH = false, bool APP = false, bool MAT = false>
 __device__ __forceinline__ void shade_sample(const ShadeK &c, const BvhNode *__restrict__ nodes, const TriRec *__restrict__ recs, const float4 *__restrict__ nrec, v3 o,
-                                             v3 d, float nt, float ft, SampleTerms &st, int *stack, int stride, PathVtx *pv = nullptr, AppTerms *ap = nullptr) {
+                                             v3 d, float nt, float ft, SampleTerms &st, int *stack, int stride, PathVtx *pv = nullptr, AppTerms *ap = nullptr,
+                                             MatVtx *mv = nullptr) {
   Hit h;
   st.hit = traverse<false, !PATH>(nodes, recs, o, d, nt, ft, h, stack, stride);
   if (PATH) pv->ok = 0;
   if (APP) { ap->proj_t = ap->spot_t = ap->s_f = ap->s_fb = 0.f; ap->tix = 0; }
+  if (MAT) { mv->kp = mv->ks = 0.f; }
   st.has_proj = 0;
   st.proj_fac = 0.f; st.proj_fac_b = 0.f;
   st.spot[0] = st.spot[1] = st.spot[2] = 0.f;
@@ -715,6 +851,7 @@ __device__ __forceinline__ void shade_sample(const ShadeK &c, const BvhNode *__r
     }
   }
   if (PATH) { pv->Po = Po; pv->ng = ng; pv->ns = ns; pv->textured = textured ? 1 : 0; pv->ok = 1; }
+  if (MAT) mv->ns = ns;
 
   if (c.proj_on) {
     v3 pl = xf_point(c.p_w2l, P);
@@ -751,6 +888,7 @@ __device__ __forceinline__ void shade_sample(const ShadeK &c, const BvhNode *__r
             st.proj_fac = (c.p_scale / (pl.z * pl.z * cos_p)) * bA;
             st.proj_fac_b = (c.p_scale / (pl.z * pl.z * cos_p)) * bB;
             if (APP) ap->proj_t = (c.p_scale / (pl.z * pl.z * cos_p)) * bT;
+            if (MAT) { mv->kp = c.p_scale / (pl.z * pl.z * cos_p); mv->wp = wi; }
             float fx = fmaf(u, (float)c.tw, -0.5f), fy = fmaf(v, (float)c.th, -0.5f);
             float x0 = floorf(fx), y0 = floorf(fy);
             float ax = fx - x0, ay = fy - y0;
@@ -799,6 +937,7 @@ __device__ __forceinline__ void shade_sample(const ShadeK &c, const BvhNode *__r
           }
           float f = fall * bA / d2 * 0.3183098861837907f, fb = fall * bB / d2 * 0.3183098861837907f;
           if (APP) { ap->s_f = f; ap->s_fb = fb; ap->spot_t = fall * bT / d2 * 0.3183098861837907f; }
+          if (MAT) { mv->ks = fall / d2 * 0.3183098861837907f; mv->ws = wi; }
           st.spot[0] = c.s_int[0] * f;
           st.spot[1] = c.s_int[1] * f;
           st.spot[2] = c.s_int[2] * f;
@@ -4218,6 +4357,7 @@ __global__ void __launch_bounds__(64)
 // wave), a textured base colour's through its four bilinear taps (global atomics).
 #define FFX_APP_WAVES 4
 #define FFX_APP_LDS_ROWS 255
+#define FFX_MAT_LDS_ROWS 64 // (k_render_bwd_material: rows of [FFX_MAT_GRAD_COLS] sums in LDS; more shapes go straight to global atomics)
 static_assert(64 * FFX_APP_WAVES == TR_BLOCK, "k_render_bwd_appearance takes the per-lane kernels' traversal stack (stack_bytes)");
 struct AppArgs {
   const BvhNode *nodes; const TriRec *recs; const float4 *nrec;
@@ -4344,6 +4484,152 @@ __global__ void __launch_bounds__(64 * FFX_APP_WAVES)
     for (int i = threadIdx.x; i < a.n_shapes * 3; i += 64 * FFX_APP_WAVES) {
       const float v = s_rows[i];
       if (v != 0.f) atomicAdd(a.grow + i, v);
+    }
+}
+// FFX_RENDER_GRAD_MATERIAL (include/ffx.h): k_render_bwd_appearance's replay (the same text, the appearance block included) plus,
+// per sample and lit emitter, the BSDF's adjoint (material_terms_vjp) into gmat [n_shapes][FFX_MAT_GRAD_COLS] — row sums through LDS (s_mat) when
+// n_shapes <= FFX_MAT_LDS_ROWS, global atomics otherwise, then one global atomic per non-zero entry and workgroup.  A sibling kernel rather than a
+// template flag on k_render_bwd_appearance: sharing one body changed the appearance kernel's code.
+template <bool RF>
+__global__ void __launch_bounds__(64 * FFX_APP_WAVES)
+    k_render_bwd_material(ShadeK c, AppArgs a, const float *__restrict__ gsrc, float *__restrict__ gmat) {
+  extern __shared__ int s_dyn[];
+  __shared__ float s_rows[FFX_APP_LDS_ROWS * 3];
+  __shared__ float s_mat[FFX_MAT_LDS_ROWS * FFX_MAT_GRAD_COLS];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const bool lds = a.n_shapes <= FFX_APP_LDS_ROWS;
+  if (lds)
+    for (int i = threadIdx.x; i < a.n_shapes * 3; i += 64 * FFX_APP_WAVES) s_rows[i] = 0.f;
+  const bool lds_m = a.n_shapes <= FFX_MAT_LDS_ROWS;
+  if (lds_m)
+    for (int i = threadIdx.x; i < a.n_shapes * FFX_MAT_GRAD_COLS; i += 64 * FFX_APP_WAVES) s_mat[i] = 0.f;
+  __syncthreads();
+  const int W = c.cam.W, H = c.cam.H;
+  const float wl[3] = {0.212671f, 0.715160f, 0.072169f};
+  float gs[3] = {0.f, 0.f, 0.f}; // this lane's share of d loss / d spot intensity
+  for (long pl = (long)blockIdx.x * FFX_APP_WAVES + wave; pl < a.n_pix; pl += (long)gridDim.x * FFX_APP_WAVES) { // (wave-uniform)
+    const uint32_t pix = (uint32_t)pl;
+    const int px = (int)(pix % (uint32_t)W), py = (int)(pix / (uint32_t)W);
+    float g0, g1, g2; // box: the pixel's gradient / spp; RF: lanes 0..24 hold G of window pixel `lane`
+    if (RF) {
+      const float4 gw = rf_window_g(reinterpret_cast<const float4 *>(gsrc), px, py, W, H, lane, true);
+      g0 = gw.x; g1 = gw.y; g2 = gw.z;
+      if (wballot(g0 != 0.f || g1 != 0.f || g2 != 0.f) == 0ull) continue;
+    } else {
+      const float inv_spp = 1.0f / (float)a.spp;
+      g0 = gsrc[(size_t)pix * 3] * inv_spp; g1 = gsrc[(size_t)pix * 3 + 1] * inv_spp; g2 = gsrc[(size_t)pix * 3 + 2] * inv_spp;
+      if (g0 == 0.f && g1 == 0.f && g2 == 0.f) continue;
+    }
+    for (int pass = 0; pass < (a.spp + 63) >> 6; ++pass) {
+      const int s = pass * 64 + lane;
+      const uint32_t idx = pix * (uint32_t)a.spp + (uint32_t)s;
+      float jx, jy;
+      sample_jitter(a.seed_key, idx, jx, jy);
+      float q[3] = {g0, g1, g2};
+      if (RF) { // (all lanes: the readlanes need the whole wave)
+        float gx[5], gy[5];
+        rf_weights(c.rf, jx, gx);
+        rf_weights(c.rf, jy, gy);
+        q[0] = q[1] = q[2] = 0.f;
+#pragma unroll
+        for (int n = 0; n < 25; ++n) {
+          const float w = gx[n % 5] * gy[n / 5];
+          q[0] = __builtin_fmaf(w, __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(g0), n)), q[0]);
+          q[1] = __builtin_fmaf(w, __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(g1), n)), q[1]);
+          q[2] = __builtin_fmaf(w, __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(g2), n)), q[2]);
+        }
+      }
+      if (s >= a.spp || (q[0] == 0.f && q[1] == 0.f && q[2] == 0.f)) continue;
+      v3 o, d;
+      float nt, ft;
+      cam_ray(c.cam, ((float)px + jx) * c.cam.inv_w, ((float)py + jy) * c.cam.inv_h, o, d, nt, ft);
+      SampleTerms st;
+      AppTerms ap;
+      MatVtx mv;
+      shade_sample<false, true, true>(kernarg_shade(), a.nodes, a.recs, a.nrec, o, d, nt, ft, st, s_dyn + threadIdx.x, 64 * FFX_APP_WAVES, nullptr, &ap, &mv);
+      if (!st.hit) continue;
+      const ShadeK &k = kernarg_shade();
+      float tv[3] = {0.f, 0.f, 0.f};
+      if (st.has_proj) path_tex(k, st, a.tex, tv);
+      { // L_c = sum_e (b_c A_e + B_e) E_ec: one reverse pass per emitter with uA_e = sum_c q_c b_c E_ec, uB_e = sum_c q_c E_ec
+        const float *mt = mat_table(k);
+        if (k.mat_stride == FFX_MAT_STRIDE && mt[(size_t)FFX_MAT_STRIDE * st.shape + FFX_MAT_MODEL] != 0.f && (mv.kp != 0.f || mv.ks != 0.f)) {
+          const float *mrow = mt + (size_t)FFX_MAT_STRIDE * st.shape;
+          const float lum = wl[0] * st.base[0] + wl[1] * st.base[1] + wl[2] * st.base[2];
+          const v3 wv = V3(-d.x, -d.y, -d.z);
+          float gm[FFX_MAT_GRAD_COLS];
+#pragma unroll
+          for (int j = 0; j < FFX_MAT_GRAD_COLS; ++j) gm[j] = 0.f;
+          MatGeoD mg;
+          if (mv.kp != 0.f) {
+            float uA = 0.f, uB = 0.f;
+#pragma unroll
+            for (int ch = 0; ch < 3; ++ch) { const float e = q[ch] * tv[ch] * mv.kp; uA += e * st.base[ch]; uB += e; }
+            material_geometry_d(mv.ns, wv, mv.wp, mg);
+            material_terms_vjp(mrow, mg, lum, uA, uB, gm);
+          }
+          if (mv.ks != 0.f) {
+            float uA = 0.f, uB = 0.f;
+#pragma unroll
+            for (int ch = 0; ch < 3; ++ch) { const float e = q[ch] * k.s_int[ch] * mv.ks; uA += e * st.base[ch]; uB += e; }
+            material_geometry_d(mv.ns, wv, mv.ws, mg);
+            material_terms_vjp(mrow, mg, lum, uA, uB, gm);
+          }
+          float *dst = lds_m ? s_mat + st.shape * FFX_MAT_GRAD_COLS : gmat + (size_t)st.shape * FFX_MAT_GRAD_COLS;
+#pragma unroll
+          for (int j = 0; j < FFX_MAT_GRAD_COLS; ++j)
+            if (gm[j] != 0.f) atomicAdd(dst + j, gm[j]);
+        }
+      }
+      float E[3], qbt = 0.f;
+#pragma unroll
+      for (int ch = 0; ch < 3; ++ch) {
+        E[ch] = st.spot[ch] + tv[ch] * st.proj_fac;
+        qbt += q[ch] * st.base[ch] * (k.s_int[ch] * ap.spot_t + tv[ch] * ap.proj_t);
+        gs[ch] += q[ch] * (st.base[ch] * ap.s_f + ap.s_fb);
+      }
+      const float lum = wl[0] * st.base[0] + wl[1] * st.base[1] + wl[2] * st.base[2];
+      const float r = lum > 0.f ? qbt / (lum * lum) : 0.f;
+      float gb[3];
+#pragma unroll
+      for (int ch = 0; ch < 3; ++ch) gb[ch] = q[ch] * E[ch] - r * wl[ch];
+      if (gb[0] == 0.f && gb[1] == 0.f && gb[2] == 0.f) continue;
+      if (ap.tix == 0) { // the row's own base colour
+        if (lds) {
+#pragma unroll
+          for (int ch = 0; ch < 3; ++ch) atomicAdd(&s_rows[st.shape * 3 + ch], gb[ch]);
+        } else {
+#pragma unroll
+          for (int ch = 0; ch < 3; ++ch) atomicAdd(a.grow + (size_t)st.shape * 3 + ch, gb[ch]);
+        }
+      } else { // a base-colour texture: through the lookup's four taps
+        float *gt = ap.tix == 1 ? a.gbt[0] : ap.tix == 2 ? a.gbt[1] : ap.tix == 3 ? a.gbt[2] : a.gbt[3];
+        size_t to[4];
+        float tw4[4];
+        base_tex_taps(k, ap.tix - 1, ap.slot, ap.bu, ap.bv, to, tw4);
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+#pragma unroll
+          for (int ch = 0; ch < 3; ++ch) atomicAdd(gt + to[t] + ch, gb[ch] * tw4[t]);
+        }
+      }
+    }
+  }
+#pragma unroll
+  for (int ch = 0; ch < 3; ++ch) {
+    const float v = wave_sum_tree(gs[ch]);
+    if (lane == 0 && v != 0.f) atomicAdd(a.gspot + ch, v);
+  }
+  __syncthreads();
+  if (lds)
+    for (int i = threadIdx.x; i < a.n_shapes * 3; i += 64 * FFX_APP_WAVES) {
+      const float v = s_rows[i];
+      if (v != 0.f) atomicAdd(a.grow + i, v);
+    }
+  if (lds_m)
+    for (int i = threadIdx.x; i < a.n_shapes * FFX_MAT_GRAD_COLS; i += 64 * FFX_APP_WAVES) {
+      const float v = s_mat[i];
+      if (v != 0.f) atomicAdd(gmat + i, v);
     }
 }
 
@@ -5094,9 +5380,12 @@ static int render_fwd_impl(const void *bvh, const ffx_bvh_info *info, const ffx_
   return FFX_OK;
 }
 
-// the appearance adjoint's bit belongs to ffx_render_bwd[_filtered]: every other render entry point refuses it
-#define FFX_NO_APPEARANCE(flags_, what_) \
-  do { if ((flags_) & FFX_RENDER_GRAD_APPEARANCE) FFX_FAIL(FFX_ERR_UNSUPPORTED, "%s: FFX_RENDER_GRAD_APPEARANCE is served by ffx_render_bwd[_filtered] only", what_); } while (0)
+// the appearance adjoint's bits belong to ffx_render_bwd[_filtered]: every other render entry point refuses them
+#define FFX_NO_APPEARANCE(flags_, what_)                                                                                                                  \
+  do {                                                                                                                                                    \
+    if ((flags_) & FFX_RENDER_GRAD_APPEARANCE) FFX_FAIL(FFX_ERR_UNSUPPORTED, "%s: FFX_RENDER_GRAD_APPEARANCE is served by ffx_render_bwd[_filtered] only", what_); \
+    if ((flags_) & FFX_RENDER_GRAD_MATERIAL) FFX_FAIL(FFX_ERR_UNSUPPORTED, "%s: FFX_RENDER_GRAD_MATERIAL is served by ffx_render_bwd[_filtered] only", what_);     \
+  } while (0)
 int ffx_render_fwd(const void *bvh, const ffx_bvh_info *info, const ffx_scene_desc *sd, const float *shape_albedo, const float *tex, int spp,
                    uint32_t seed, int img_fp16, void *img, ffx_stream s) {
   FFX_NO_APPEARANCE(img_fp16, "render_fwd");
@@ -5341,7 +5630,8 @@ static int render_bwd_appearance(const void *bvh, const ffx_bvh_info *info, cons
                                  const float *gimg, float *gtex, ffx_stream s, void *rf_scratch) {
   if (!bvh || !info || !sd || (!shape_albedo && sd->n_mat_h <= 0) || !gimg || !gtex || spp < 1) FFX_FAIL(FFX_ERR_ARG, "render_bwd: bad argument");
   if (flags & FFX_RENDER_PATH_MASK) FFX_FAIL(FFX_ERR_UNSUPPORTED, "render_bwd: FFX_RENDER_GRAD_APPEARANCE is served at max_depth 2 only");
-  if (const int rc = render_bwd_impl(bvh, info, sd, shape_albedo, spp, seed, flags & ~FFX_RENDER_GRAD_APPEARANCE, gimg, gtex, s, rf_scratch)) return rc;
+  if (const int rc = render_bwd_impl(bvh, info, sd, shape_albedo, spp, seed, flags & ~(FFX_RENDER_GRAD_APPEARANCE | FFX_RENDER_GRAD_MATERIAL), gimg, gtex, s, rf_scratch))
+    return rc;
   RenderSetup r;
   if (const int rc = render_setup("render_bwd", bvh, info, sd, shape_albedo, spp, seed, flags, rf_scratch, r)) return rc;
   if (sd->n_shapes < 1) FFX_FAIL(FFX_ERR_ARG, "render_bwd: n_shapes < 1");
@@ -5367,14 +5657,28 @@ static int render_bwd_appearance(const void *bvh, const ffx_bvh_info *info, cons
   }
   const long blocks = ffx_cdiv(r.n_pix, (long)FFX_APP_WAVES);
   const unsigned grid = (unsigned)(blocks < 2048 ? blocks : 2048); // (every workgroup strides over the film: 2048 x 4 waves fill the device)
+  if (flags & FFX_RENDER_GRAD_MATERIAL) { // (FFX_RENDER_MATERIAL_FLOATS(sd) floats behind the appearance block)
+    float *gmat = gtex + n_tex + FFX_RENDER_APPEARANCE_FLOATS(sd);
+    if (rf_scratch) hipLaunchKernelGGL(k_render_bwd_material<true>, dim3(grid), dim3(64 * FFX_APP_WAVES), stack_bytes(info), st, r.c, a, gsrc, gmat);
+    else hipLaunchKernelGGL(k_render_bwd_material<false>, dim3(grid), dim3(64 * FFX_APP_WAVES), stack_bytes(info), st, r.c, a, gsrc, gmat);
+    FFX_CHECK_LAUNCH(rf_scratch ? "render_bwd_filtered (material)" : "render_bwd (material)");
+    return FFX_OK;
+  }
   if (rf_scratch) hipLaunchKernelGGL(k_render_bwd_appearance<true>, dim3(grid), dim3(64 * FFX_APP_WAVES), stack_bytes(info), st, r.c, a, gsrc);
   else hipLaunchKernelGGL(k_render_bwd_appearance<false>, dim3(grid), dim3(64 * FFX_APP_WAVES), stack_bytes(info), st, r.c, a, gsrc);
   FFX_CHECK_LAUNCH(rf_scratch ? "render_bwd_filtered (appearance)" : "render_bwd (appearance)");
   return FFX_OK;
 }
+// FFX_RENDER_GRAD_MATERIAL extends FFX_RENDER_GRAD_APPEARANCE: alone it is an argument error
+#define FFX_MATERIAL_NEEDS_APPEARANCE(flags_, what_)                                                                                      \
+  do {                                                                                                                                    \
+    if (((flags_) & (FFX_RENDER_GRAD_MATERIAL | FFX_RENDER_GRAD_APPEARANCE)) == FFX_RENDER_GRAD_MATERIAL)                                 \
+      FFX_FAIL(FFX_ERR_ARG, "%s: FFX_RENDER_GRAD_MATERIAL needs FFX_RENDER_GRAD_APPEARANCE", what_);                                      \
+  } while (0)
 
 int ffx_render_bwd(const void *bvh, const ffx_bvh_info *info, const ffx_scene_desc *sd, const float *shape_albedo, int spp, uint32_t seed, int flags,
                    const float *gimg, float *gtex, ffx_stream s) {
+  FFX_MATERIAL_NEEDS_APPEARANCE(flags, "render_bwd");
   if (flags & FFX_RENDER_GRAD_APPEARANCE) return render_bwd_appearance(bvh, info, sd, shape_albedo, spp, seed, flags, gimg, gtex, s, nullptr);
   return render_bwd_impl(bvh, info, sd, shape_albedo, spp, seed, flags, gimg, gtex, s, nullptr);
 }
@@ -5449,6 +5753,7 @@ int ffx_render_fwd_adjoint_filtered(const void *bvh, const ffx_bvh_info *info, c
 int ffx_render_bwd_filtered(const void *bvh, const ffx_bvh_info *info, const ffx_scene_desc *sd, const float *shape_albedo, int spp, uint32_t seed, int flags,
                             const float *gimg, float *gtex, void *scratch, ffx_stream s) {
   if (!scratch || ((uintptr_t)scratch & 15) != 0) FFX_FAIL(FFX_ERR_ARG, "render_bwd_filtered: scratch is NULL or not 16-byte aligned");
+  FFX_MATERIAL_NEEDS_APPEARANCE(flags, "render_bwd_filtered");
   if (flags & FFX_RENDER_GRAD_APPEARANCE) return render_bwd_appearance(bvh, info, sd, shape_albedo, spp, seed, flags, gimg, gtex, s, scratch);
   return render_bwd_impl(bvh, info, sd, shape_albedo, spp, seed, flags, gimg, gtex, s, scratch);
 }

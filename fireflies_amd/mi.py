@@ -625,8 +625,15 @@ class Scene:
             p._init(s.name + ".intensity.value", Color3f(torch.tensor(s.intensity, dtype=torch.float32)))
             p._init(s.name + ".cutoff_angle", Float(s.cutoff_angle))
             p._init(s.name + ".beam_width", Float(s.beam_width))
+        # (the BSDF parameters: every key a principled material exposes, and the `specular` / `roughness` that diffuse ones keep, whose gradient is 0)
+        bsdf = [m + ".brdf_0.specular" for m in mats] + [m + ".brdf_0.roughness.value" for m in mats]
+        bsdf += [m + f".brdf_0.{k}.value" for m, ms in mats.items() if ms[0].bsdf is not None for k in scenes.PRINCIPLED_DEFAULTS if k not in ("specular", "roughness")]
+        bsdf += [m + ".brdf_0.eta" for m, ms in mats.items() if ms[0].bsdf is not None]
         p._leaf_keys = frozenset([m + ".brdf_0.base_color.value" for m in mats] + [n + ".brdf_0.base_color.data" for n, _ in self._base_tex]
-                                 + ([d.spot.name + ".intensity.value"] if d.spot is not None else []))
+                                 + ([d.spot.name + ".intensity.value"] if d.spot is not None else []) + bsdf)
+        # which key last wrote each principled material's eta (`<mat>.brdf_0.eta` -> its own key or the material's `specular`): a specular leaf and an
+        # eta leaf get d loss / d eta only while the row's eta is theirs (specular wins within one update, as _apply orders it)
+        self._eta_src = {}
 
     def sensors(self):
         return self._sensors
@@ -699,10 +706,12 @@ class Scene:
                             late.append(k)
                             continue
                         v = self._params._d[k]
-                        v = float(v) if isinstance(v, float) else float((v.t if isinstance(v, _ArrayBase) else torch.as_tensor(v, dtype=torch.float32)).reshape(-1)[0])
+                        v = float(v) if isinstance(v, float) else float((v.t if isinstance(v, _ArrayBase) else torch.as_tensor(v, dtype=torch.float32)).detach().reshape(-1)[0])
                         if conv:  # `specular`: the plugin re-derives eta from it
                             v = scenes.specular_to_eta(v)
                             self._params._d[eta_key] = Float(v)
+                        if conv or k == eta_key:
+                            self._eta_src[eta_key] = k
                         if warn_st and v > 0.0:
                             self._warn_spec_trans(k)
                         for i in rows:
@@ -739,7 +748,9 @@ class Scene:
                         plan[k] = _PLAIN_KEY  # (no part of anything the device sees)
                         continue
                     v = self._params._d[k]
-                    v = float(v) if isinstance(v, float) else float((v.t if isinstance(v, _ArrayBase) else torch.as_tensor(v, dtype=torch.float32)).reshape(-1)[0])
+                    v = float(v) if isinstance(v, float) else float((v.t if isinstance(v, _ArrayBase) else torch.as_tensor(v, dtype=torch.float32)).detach().reshape(-1)[0])
+                    if name in ("specular", "eta"):
+                        self._eta_src[base + ".brdf_0.eta"] = k
                     if name == "specular":  # the plugin re-derives eta from it (principled.cpp parameters_changed)
                         col, v = scenes.MAT_COLUMN["eta"], scenes.specular_to_eta(v)
                         self._params._d[base + ".brdf_0.eta"] = Float(v)
@@ -943,6 +954,8 @@ class Scene:
         if p._leaves:
             for k in sp.keys:
                 p._leaves.pop(k, None)
+            for eta_key, _ in sp.eta:  # (a drawn `specular` wrote the row's eta)
+                self._eta_src.pop(eta_key, None)
         if sp.has_mat:
             self._albedo_stale = True
         self._sd_cache = (ch, sd)
@@ -1193,7 +1206,9 @@ def load_dict(d: dict):
 def render(scene: Scene, params: SceneParameters = None, spp: int = 16, seed: int = 0, sensor: int = 0, fp16: bool = False, integrator: Integrator = None):
     """mi.render(scene, spp=...) -> [H,W,3] (wrapped; `.torch()` as in examples/vocalfold_scene.py:14).
     Differentiable w.r.t. `tex.data` when that parameter is a tensor that requires grad — and w.r.t. `<mat>.brdf_0.base_color.value`,
-    `<spot>.intensity.value` and `<mat>.brdf_0.base_color.data` when such a tensor was assigned to them (direct light only).
+    `<spot>.intensity.value`, `<mat>.brdf_0.base_color.data` and the principled BSDF's parameters (`<mat>.brdf_0.{roughness, anisotropic, metallic,
+    spec_trans, spec_tint, sheen, sheen_tint, flatness, clearcoat, clearcoat_gloss}.value`, `.specular`, `.eta`) when such a tensor was assigned to
+    them (direct light only; each BSDF leaf's gradient is summed over the material's shapes).
     integrator (mi.load_dict): None or max_depth 2 renders direct light at the primary hit, as always; deeper paths run on the caller's stream."""
     if sensor != 0:
         raise NotImplementedError("only sensor 0 renders; further sensors are projector proxies")
@@ -1270,7 +1285,8 @@ def _render_path(scene, spp, seed, fp16, integrator):
 
 class _AppearanceRender(torch.autograd.Function):
     """mi.render with appearance leaves: the plain forward; the backward is ONE ffx_render_bwd[_filtered] call with
-    FFX_RENDER_GRAD_APPEARANCE, which yields the texture gradient and the appearance block together"""
+    FFX_RENDER_GRAD_APPEARANCE, which yields the texture gradient and the appearance block together (and, with BSDF leaves, FFX_RENDER_GRAD_MATERIAL's
+    block: kind "bsdf" = (rows, column of the block, factor) — the factor chains `specular` to eta, or is 0 for a leaf that does not drive the row)"""
 
     @staticmethod
     def forward(ctx, tex, scene, sd, mats, spp, seed, fp16, kinds, *leaves):
@@ -1291,13 +1307,17 @@ class _AppearanceRender(torch.autograd.Function):
         if ctx.geom.version != ctx.pose_version:
             raise RuntimeError("mi.render: the scene was updated between the render and its backward — the appearance adjoint re-traces the render's pose: "
                                "call backward before the next params.update()")
-        gtex, app = ctx.geom.render_bwd(ctx.sd, ctx.mats, ctx.spp, ctx.seed, g.float().contiguous(), appearance=True, tex=ctx.tex)
+        material = any(kind == "bsdf" for kind, _ in ctx.kinds)
+        gtex, app = ctx.geom.render_bwd(ctx.sd, ctx.mats, ctx.spp, ctx.seed, g.float().contiguous(), appearance=True, tex=ctx.tex, material=material)
         grads = []
         for (kind, arg), (shape, dtype, device) in zip(ctx.kinds, ctx.leaf_meta):
             if kind == "mat":
                 v = app.rows[list(arg)].sum(0)
             elif kind == "spot":
                 v = app.spot
+            elif kind == "bsdf":
+                rows, col, fac = arg
+                v = app.material[list(rows), col].sum() * fac
             else:
                 v = app.base_tex[arg]
             n = 1
@@ -1312,10 +1332,10 @@ class _AppearanceRender(torch.autograd.Function):
 def _render_appearance(scene, spp, seed, fp16, integrator):
     """mi.render while appearance leaves are assigned and grad is enabled: through _AppearanceRender on the caller's stream"""
     if integrator is not None and integrator.max_depth > 2:
-        raise ValueError("mi.render: the gradients of base colours and spot intensity are served for direct light only (max_depth 2); "
+        raise ValueError("mi.render: the gradients of base colours, spot intensity and BSDF parameters are served for direct light only (max_depth 2); "
                          "the scene holds parameters that require grad: " + ", ".join(sorted(scene._params._leaves)))
     if ops.deterministic_mode():
-        raise ValueError("mi.render: the gradients of base colours and spot intensity have no deterministic adjoint (FFX_DETERMINISTIC=1)")
+        raise ValueError("mi.render: the gradients of base colours, spot intensity and BSDF parameters have no deterministic adjoint (FFX_DETERMINISTIC=1)")
     p = scene._params
     tex = None
     ch = 3
@@ -1341,6 +1361,21 @@ def _render_appearance(scene, spp, seed, fp16, integrator):
             kinds.append(("mat", tuple(scene._material_meshes[base])))
         elif rest == "brdf_0.base_color.data":
             kinds.append(("base_tex", names.index(base)))
+        elif rest.startswith("brdf_0."):  # a BSDF parameter: its column of the material block (scenes.MAT_COLUMN, from roughness on)
+            rows = tuple(scene._material_meshes[base])
+            name = rest[len("brdf_0."):]
+            name = name[:-len(".value")] if name.endswith(".value") else name
+            fac = 1.0
+            if name in ("specular", "eta"):
+                eta_key = base + ".brdf_0.eta"
+                if scene._eta_src.get(eta_key) != k:
+                    fac = 0.0  # (the row's eta came from the other key, or a diffuse material's `specular`: no part of the render)
+                elif name == "specular":
+                    fac = scenes.specular_to_eta_grad(float(leaf.detach().reshape(-1)[0]))
+                elif float(scene._albedo_host[rows[0], scenes.MAT_COLUMN["eta"]]) == 1.0:
+                    fac = 0.0  # (at eta = 1 the column holds the limit a `specular` of 0 chains with; d loss / d eta itself is 0 there)
+            col = scenes.MAT_COLUMN["eta" if name == "specular" else name] - scenes.MAT_COLUMN["roughness"]
+            kinds.append(("bsdf", (rows, col, fac)))
         else:
             kinds.append(("spot", None))
         leaves.append(leaf)

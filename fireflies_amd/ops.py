@@ -540,10 +540,13 @@ def _no_path(max_depth, what):
 
 class AppearanceGrad(NamedTuple):
     """what render_bwd(..., appearance=True) adds to the texture gradient: d loss / d base colour per material row [n_shapes, 3] (zero on
-    rows whose base colour is a texture), d loss / d spot intensity [3], d loss / d base-colour texture [h, w, 3] per texture of the scene description"""
+    rows whose base colour is a texture), d loss / d spot intensity [3], d loss / d base-colour texture [h, w, 3] per texture of the scene description.
+    material (render_bwd(..., material=True), FFX_RENDER_GRAD_MATERIAL): d loss / d the BSDF parameters per material row [n_shapes, 11], columns
+    roughness .. clearcoat_gloss in scenes.MAT_COLUMN order (the eta column: d loss / d eta; at eta = 1 the limit include/ffx.h describes); else None"""
     rows: torch.Tensor
     spot: torch.Tensor
     base_tex: list
+    material: torch.Tensor = None
 
 
 def _lane_kernels():
@@ -1107,15 +1110,19 @@ class DeviceGeometry:
                        _stream(self._didx))
         self._release()
 
-    def render_bwd(self, sd, albedo, spp, seed, gimg, deterministic=None, max_depth=2, rr_depth=5, appearance=False, tex=None):
+    def render_bwd(self, sd, albedo, spp, seed, gimg, deterministic=None, max_depth=2, rr_depth=5, appearance=False, tex=None, material=False):
         """the re-tracing adjoint.  deterministic (default: FFX_DETERMINISTIC=1 in the environment): ffx_render_bwd_det — bitwise
         reproducible accumulation (64-bit fixed point instead of float atomics; two re-traces and one host synchronisation).
         max_depth > 2: the path integrator's adjoint — replays render_fwd's paths of the same max_depth, rr_depth, spp and seed (float atomics only).
         appearance=True (FFX_RENDER_GRAD_APPEARANCE): -> (gtex, AppearanceGrad) — also d loss / d base colour per material row, d loss /
         d spot intensity and d loss / d base-colour texture; `tex` is the forward's projector texture (needed when the scene has a projector).
-        Direct light (max_depth 2) and the float-atomic adjoint only."""
+        Direct light (max_depth 2) and the float-atomic adjoint only.
+        material=True (with appearance=True; FFX_RENDER_GRAD_MATERIAL): AppearanceGrad.material also holds d loss / d the principled BSDF's
+        parameters per material row [n_shapes, 11]."""
+        if material and not appearance:
+            raise ValueError("render_bwd(material=True) needs appearance=True (the material block extends the appearance adjoint)")
         if appearance:
-            return self._render_bwd_appearance(sd, albedo, spp, seed, gimg, deterministic, max_depth, tex)
+            return self._render_bwd_appearance(sd, albedo, spp, seed, gimg, deterministic, max_depth, tex, material)
         path = path_flags(max_depth, rr_depth) if max_depth != 2 else 0
         if deterministic is None:
             deterministic = deterministic_mode()
@@ -1164,7 +1171,7 @@ class DeviceGeometry:
         self._release()
         return gtex
 
-    def _render_bwd_appearance(self, sd, albedo, spp, seed, gimg, deterministic, max_depth, tex):
+    def _render_bwd_appearance(self, sd, albedo, spp, seed, gimg, deterministic, max_depth, tex, material=False):
         """render_bwd(..., appearance=True): one ffx_render_bwd[_filtered] call with FFX_RENDER_GRAD_APPEARANCE; gimg and the texture travel in one
         buffer, gtex and the appearance block in another (include/ffx.h)"""
         if max_depth != 2:
@@ -1185,10 +1192,11 @@ class DeviceGeometry:
             src = torch.cat([gimg.reshape(-1).float(), tex.detach().reshape(-1).to(device=self.device, dtype=torch.float32)])
         if src.numel() < H * W * 3:
             raise ValueError("gimg must hold [H, W, 3] floats")
-        out = torch.zeros(n_tex + n_app, dtype=torch.float32, device=self.device)
+        n_mat = _abi.material_floats(sd.n_shapes) if material else 0
+        out = torch.zeros(n_tex + n_app + n_mat, dtype=torch.float32, device=self.device)
         mats_arg = _check_materials(sd, albedo)
         blob = self.blob
-        flags = self._apex_flag(apex_key(sd)) | _abi.RENDER_GRAD_APPEARANCE
+        flags = self._apex_flag(apex_key(sd)) | _abi.RENDER_GRAD_APPEARANCE | (_abi.RENDER_GRAD_MATERIAL if material else 0)
         with self._timed("render_bwd"):
             if sd.rfilter:
                 scratch = torch.empty(render_filter_bytes(sd), dtype=torch.uint8, device=self.device)
@@ -1206,4 +1214,5 @@ class DeviceGeometry:
         for h, w in bt:
             base_tex.append(out[o:o + 3 * h * w].view(h, w, 3))
             o += 3 * h * w
-        return gtex, AppearanceGrad(rows, spot, base_tex)
+        mat = out[n_tex + n_app:].view(S, _abi.RENDER_MATERIAL_COLS) if material else None
+        return gtex, AppearanceGrad(rows, spot, base_tex, mat)

@@ -261,6 +261,17 @@ def specular_to_eta(specular):
     return 2.0 / (1.0 - float(np.sqrt(0.08 * float(specular)))) - 1.0
 
 
+def specular_to_eta_grad(specular):
+    """d eta / d specular of specular_to_eta: 0.08 / (x (1 - x)^2) with x = sqrt(0.08 specular), for specular > 0.  At specular = 0 the derivative is
+    infinite; there the value is the finite limit of (eta - 1) d eta / d specular = 0.16 / (1 - x)^3 -> 0.16, the factor that the material adjoint's eta
+    column chains with at eta = 1, where it holds the limit of (d loss / d eta) / (eta - 1) (include/ffx.h FFX_RENDER_GRAD_MATERIAL)"""
+    s = float(specular)
+    if s <= 0.0:
+        return 0.16
+    x = float(np.sqrt(0.08 * s))
+    return 0.08 / (x * (1.0 - x) ** 2)
+
+
 def material_row(albedo, bsdf):
     """one row of the material table (include/ffx.h): [base_color(3), model, roughness, ..., clearcoat_gloss, 0]"""
     row = np.zeros(MAT_STRIDE, np.float32)

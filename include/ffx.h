@@ -779,6 +779,21 @@ int ffx_det_finish(const void *acc /*[dev] int64 [n]*/, int scale_log2, size_t n
   (3 * (size_t)(sd)->n_shapes + 3 +                                                                                                             \
    3 * (FFX_RENDER_APPEARANCE_BASE_TEX_TEXELS(sd, 0) + FFX_RENDER_APPEARANCE_BASE_TEX_TEXELS(sd, 1) + FFX_RENDER_APPEARANCE_BASE_TEX_TEXELS(sd, 2) + \
         FFX_RENDER_APPEARANCE_BASE_TEX_TEXELS(sd, 3)))
+/* The BSDF's adjoint: FFX_RENDER_GRAD_MATERIAL, together with FFX_RENDER_GRAD_APPEARANCE in the flags word of ffx_render_bwd /
+ * ffx_render_bwd_filtered, adds d loss / d the principled parameters of every material row (Mitsuba's `<mat>.brdf_0.{roughness, anisotropic, metallic,
+ * spec_trans, spec_tint, sheen, sheen_tint, flatness, clearcoat, clearcoat_gloss}.value`, `.specular`, `.eta`; main.py:97-107 randomises nine).  An
+ * additive extension of ABI 11 (FFX_ABI_VERSION is unchanged: old callers never set the bit).  The bit alone answers FFX_ERR_ARG; with path bits
+ * FFX_ERR_UNSUPPORTED, and so does every other render entry point when it is set.  With it:
+ *   output — the appearance block behind gtex is followed in the same buffer by FFX_RENDER_MATERIAL_FLOATS(sd) floats: [n_shapes][11] per material
+ *            row, columns FFX_MAT_ROUGHNESS .. FFX_MAT_CLEARCOAT_GLOSS in order (column j holds d loss / d row[FFX_MAT_ROUGHNESS + j]); 0 for Lambert
+ *            rows (model 0) and for a table of Lambert albedos (mat_stride 3).  The eta column holds d loss / d eta, except at eta = 1 exactly, where
+ *            the derivative vanishes and the column holds the limit of (d loss / d eta) / (eta - 1) as eta -> 1+ (what a `specular`
+ *            of 0 chains with).  Direct light, the reflection side the forward evaluates; one-sided derivatives into [0, 1] where a lobe is skipped
+ *            at a parameter's bound.  Accumulated into: the caller zeroes the whole buffer.
+ * The texture gradient and the appearance block are those of a call without the bit.  The oracle ignores the bit. */
+#define FFX_RENDER_GRAD_MATERIAL 0x20000
+#define FFX_RENDER_MATERIAL_COLS 11
+#define FFX_RENDER_MATERIAL_FLOATS(sd) ((size_t)FFX_RENDER_MATERIAL_COLS * (size_t)(sd)->n_shapes)
 /* Writes the apex records (the triangles as seen from a fixed ray origin) of sd's camera and enabled emitters into
  * the blob's apex areas — what every packet render does in front of its kernel unless told FFX_RENDER_APEX_READY.  Only
  * sd->cam.to_world, sd->proj.{enabled,to_world} and sd->spot.{enabled,to_world} are read.  No reference counterpart (Mitsuba

@@ -1,5 +1,6 @@
 """The appearance adjoint's cost: ms per 512^2 x 64-spp vocal-fold adjoint with FFX_RENDER_GRAD_APPEARANCE (the texture gradient's
-launches + k_render_bwd_appearance), next to the same render_bwd without it, box and gaussian film.  HIP events around repeated calls of one pose on
+launches + k_render_bwd_appearance), next to the same render_bwd without it, and with FFX_RENDER_GRAD_MATERIAL as well (k_render_bwd_material: the
+BSDF parameters' adjoint), box and gaussian film.  HIP events around repeated calls of one pose on
 one stream, after a warm-up.  Prints one JSON line.
 
     python tools/appearancebench.py [reps]
@@ -40,6 +41,7 @@ def main():
         gimg = torch.full((sd.cam.height, sd.cam.width, 3), -1.0 / (sd.cam.height * sd.cam.width), device="cuda")
         out[f"render_bwd_ms_{film}"] = round(_ms(lambda: geom.render_bwd(sd, mats, 64, 1, gimg), reps), 3)
         out[f"appearance_bwd_ms_{film}"] = round(_ms(lambda: geom.render_bwd(sd, mats, 64, 1, gimg, appearance=True, tex=tex), reps), 3)
+        out[f"material_bwd_ms_{film}"] = round(_ms(lambda: geom.render_bwd(sd, mats, 64, 1, gimg, appearance=True, tex=tex, material=True), reps), 3)
     print(json.dumps(out))
 
 
