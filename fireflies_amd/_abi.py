@@ -206,6 +206,11 @@ def material_floats(n_shapes):
     return RENDER_MATERIAL_COLS * int(n_shapes)
 
 
+# path replay backpropagation (include/ffx.h FFX_RENDER_GRAD_PRB): with RENDER_GRAD_APPEARANCE [| RENDER_GRAD_MATERIAL] and path bits, the two blocks
+# at max_depth > 2
+RENDER_GRAD_PRB = 0x40000
+
+
 MAX_BASE_TEX = 4
 RFILTER_BOX, RFILTER_GAUSSIAN = 0, 1
 MAX_MAT_H = 128

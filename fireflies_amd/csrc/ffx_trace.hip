@@ -4633,6 +4633,315 @@ __global__ void __launch_bounds__(64 * FFX_APP_WAVES)
     }
 }
 
+// ------------------------------------------------------------------------------------------ prb: the appearance and BSDF adjoints through bounces
+// FFX_RENDER_GRAD_PRB (include/ffx.h): the blocks of FFX_RENDER_GRAD_APPEARANCE / FFX_RENDER_GRAD_MATERIAL at max_depth > 2, by path replay with the
+// sampling decisions detached (Mitsuba's `prb`).  Per sample, with vertices v = 1 .. n, throughput beta_v, next-event term N_v = b R_v + F_v, bounce
+// weight f_v = (b A_v + B_v) / cos_o (Lambert: b) and the roulette's q_v (1 where it does not run):
+//   L = sum_v beta_v N_v,   S_v = N_v + (f_v / q_v) S_v+1,   dL/dtheta = sum_v beta_v [ dN_v/dtheta + (df_v/dtheta / q_v) S_v+1 ]
+// Bounces are cosine-weighted, so no parameter moves a path; q_v and the survival tests are constants of the replay.  Two walks per sample: the first
+// leaves N_v and f_v / q_v in LDS ([vertex][6][thread]), the lane folds them into the suffix radiances S_v, the second accumulates — at every vertex
+// what k_render_bwd_appearance / k_render_bwd_material form per sample (weight q beta_v) and what k_path_bwd scatters into gtex, at every bounce the
+// derivative of f_v.  Workgroups of 1, 2 or 4 waves (the host picks what fits 64 KB of LDS) stride over the film.
+struct PrbArgs { int max_depth, rr_depth; uint32_t path_key; float *gtex, *gmat; };
+// the bounce weight of path_bounce_weight with what its derivative needs: model (0: a Lambert row, f = base), A (the tint parts pi tau / lum included),
+// pi tau and 1 / cos_o
+struct PrbBounce { int model; float A, tau, ic; };
+__device__ __forceinline__ void prb_bounce_weight(const ShadeK &c, const SampleTerms &st, const PathVtx &pv, v3 d, v3 wo, float (&f)[3], PrbBounce &pb) {
+  const float *mt = mat_table(c);
+  f[0] = st.base[0]; f[1] = st.base[1]; f[2] = st.base[2];
+  pb.model = 0; pb.A = 1.f; pb.tau = 0.f; pb.ic = 1.f;
+  if (c.mat_stride == FFX_MAT_STRIDE && mt[(size_t)FFX_MAT_STRIDE * st.shape + FFX_MAT_MODEL] != 0.f) {
+    const float *mrow = mt + (size_t)FFX_MAT_STRIDE * st.shape;
+    MatGeo mg;
+    material_geometry(mrow, pv.ns, V3(-d.x, -d.y, -d.z), wo, mg);
+    float A, B, T;
+    if (pv.textured) material_terms<true, true>(mrow, mg, A, B, st.base[0], st.base[1], st.base[2], &T);
+    else material_terms<false, true>(mrow, mg, A, B, 0.f, 0.f, 0.f, &T);
+    const float ic = mg.cos_o > 0.f ? 1.0f / mg.cos_o : 0.f;
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) f[ch] = (st.base[ch] * A + B) * ic;
+    pb.model = 1; pb.A = A; pb.tau = T; pb.ic = ic;
+  }
+}
+// path_walk (the same paths: the same arithmetic in the same order) with two callbacks: visit(v, st, ap, mv, d, beta) at every vertex, bounce(v, st,
+// pv, ap, d, wo, beta, iq, f, pb) after a bounce that survived — beta is the throughput in front of the bounce, iq = 1 / q_v
+template <bool APP, bool MAT, typename V, typename B>
+__device__ __forceinline__ void path_walk_prb(const AppArgs &a, const PrbArgs &p, uint32_t idx, v3 o, v3 d, float nt, float ft, int *stack, int stride, V &&visit,
+                                              B &&bounce) {
+  const ShadeK &c = kernarg_shade();
+  SampleTerms st;
+  PathVtx pv;
+  AppTerms ap;
+  MatVtx mv;
+  shade_sample<true, APP, MAT>(c, a.nodes, a.recs, a.nrec, o, d, nt, ft, st, stack, stride, &pv, &ap, &mv);
+  float beta[3] = {1.f, 1.f, 1.f};
+  for (int v = 1; st.hit && pv.ok; ++v) {
+    visit(v, st, ap, mv, d, beta);
+    if (v + 1 >= p.max_depth) break;
+    const v3 wo = cosine_dir(pv.ns, path_u(p.path_key, idx, v, 0), path_u(p.path_key, idx, v, 1));
+    if (!(vdot(pv.ng, wo) > 0.f)) break;
+    float f[3], nb[3];
+    PrbBounce pb;
+    prb_bounce_weight(c, st, pv, d, wo, f, pb);
+    nb[0] = beta[0] * f[0]; nb[1] = beta[1] * f[1]; nb[2] = beta[2] * f[2];
+    const float bmax = fmaxf(nb[0], fmaxf(nb[1], nb[2]));
+    if (!(bmax > 0.f)) break;
+    float iq = 1.0f;
+    if (v >= p.rr_depth) { // (detached: q and the survival test are constants of the replay)
+      const float q = fminf(bmax, 0.95f);
+      if (path_u(p.path_key, idx, v, 2) >= q) break;
+      iq = 1.0f / q;
+      nb[0] *= iq; nb[1] *= iq; nb[2] *= iq;
+    }
+    bounce(v, st, pv, ap, d, wo, beta, iq, f, pb);
+    beta[0] = nb[0]; beta[1] = nb[1]; beta[2] = nb[2];
+    o = pv.Po;
+    d = wo;
+    shade_sample<true, APP, MAT>(c, a.nodes, a.recs, a.nrec, o, d, 0.f, 3.0e38f, st, stack, stride, &pv, &ap, &mv);
+  }
+}
+// s_dyn: the traversal stack [stack_ints / threads][threads] followed by the path records [max_depth - 1][6][threads]
+template <bool RF, bool MAT>
+__device__ __forceinline__ void path_bwd_prb(const ShadeK &c, const AppArgs &a, const PrbArgs &p, const float *__restrict__ gsrc, int *s_dyn, int stack_ints,
+                                             float *s_rows, float *s_mat) {
+  const int nthr = blockDim.x, waves = nthr >> 6;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  float *s_path = reinterpret_cast<float *>(s_dyn + stack_ints) + threadIdx.x;
+  const int pstride = 6 * nthr; // floats per vertex
+  const bool lds = a.n_shapes <= FFX_APP_LDS_ROWS;
+  if (lds)
+    for (int i = threadIdx.x; i < a.n_shapes * 3; i += nthr) s_rows[i] = 0.f;
+  const bool lds_m = MAT && a.n_shapes <= FFX_MAT_LDS_ROWS;
+  if (lds_m)
+    for (int i = threadIdx.x; i < a.n_shapes * FFX_MAT_GRAD_COLS; i += nthr) s_mat[i] = 0.f;
+  __syncthreads();
+  const int W = c.cam.W, H = c.cam.H;
+  const float wl[3] = {0.212671f, 0.715160f, 0.072169f};
+  float gs[3] = {0.f, 0.f, 0.f}; // this lane's share of d loss / d spot intensity
+  // d loss / d base colour at a vertex: into the row's sum, or through a base-colour texture's four taps
+  auto emit_base = [&](int shape, const AppTerms &ap, const float (&gb)[3]) {
+    if (gb[0] == 0.f && gb[1] == 0.f && gb[2] == 0.f) return;
+    if (ap.tix == 0) {
+      float *dst = lds ? s_rows + shape * 3 : a.grow + (size_t)shape * 3;
+#pragma unroll
+      for (int ch = 0; ch < 3; ++ch) atomicAdd(dst + ch, gb[ch]);
+    } else {
+      float *gt = ap.tix == 1 ? a.gbt[0] : ap.tix == 2 ? a.gbt[1] : ap.tix == 3 ? a.gbt[2] : a.gbt[3];
+      size_t to[4];
+      float tw4[4];
+      base_tex_taps(kernarg_shade(), ap.tix - 1, ap.slot, ap.bu, ap.bv, to, tw4);
+#pragma unroll
+      for (int t = 0; t < 4; ++t) {
+#pragma unroll
+        for (int ch = 0; ch < 3; ++ch) atomicAdd(gt + to[t] + ch, gb[ch] * tw4[t]);
+      }
+    }
+  };
+  auto emit_mat = [&](int shape, const float (&gm)[FFX_MAT_GRAD_COLS]) {
+    float *dst = lds_m ? s_mat + shape * FFX_MAT_GRAD_COLS : p.gmat + (size_t)shape * FFX_MAT_GRAD_COLS;
+#pragma unroll
+    for (int j = 0; j < FFX_MAT_GRAD_COLS; ++j)
+      if (gm[j] != 0.f) atomicAdd(dst + j, gm[j]);
+  };
+  for (long pl = (long)blockIdx.x * waves + wave; pl < a.n_pix; pl += (long)gridDim.x * waves) { // (wave-uniform)
+    const uint32_t pix = (uint32_t)pl;
+    const int px = (int)(pix % (uint32_t)W), py = (int)(pix / (uint32_t)W);
+    float g0, g1, g2; // box: the pixel's gradient / spp; RF: lanes 0..24 hold G of window pixel `lane`
+    if (RF) {
+      const float4 gw = rf_window_g(reinterpret_cast<const float4 *>(gsrc), px, py, W, H, lane, true);
+      g0 = gw.x; g1 = gw.y; g2 = gw.z;
+      if (wballot(g0 != 0.f || g1 != 0.f || g2 != 0.f) == 0ull) continue;
+    } else {
+      const float inv_spp = 1.0f / (float)a.spp;
+      g0 = gsrc[(size_t)pix * 3] * inv_spp; g1 = gsrc[(size_t)pix * 3 + 1] * inv_spp; g2 = gsrc[(size_t)pix * 3 + 2] * inv_spp;
+      if (g0 == 0.f && g1 == 0.f && g2 == 0.f) continue;
+    }
+    for (int pass = 0; pass < (a.spp + 63) >> 6; ++pass) {
+      const int s = pass * 64 + lane;
+      const uint32_t idx = pix * (uint32_t)a.spp + (uint32_t)s;
+      float jx, jy;
+      sample_jitter(a.seed_key, idx, jx, jy);
+      float q[3] = {g0, g1, g2};
+      if (RF) { // (all lanes: the readlanes need the whole wave)
+        float gx[5], gy[5];
+        rf_weights(c.rf, jx, gx);
+        rf_weights(c.rf, jy, gy);
+        q[0] = q[1] = q[2] = 0.f;
+#pragma unroll
+        for (int n = 0; n < 25; ++n) {
+          const float w = gx[n % 5] * gy[n / 5];
+          q[0] = __builtin_fmaf(w, __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(g0), n)), q[0]);
+          q[1] = __builtin_fmaf(w, __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(g1), n)), q[1]);
+          q[2] = __builtin_fmaf(w, __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(g2), n)), q[2]);
+        }
+      }
+      if (s >= a.spp || (q[0] == 0.f && q[1] == 0.f && q[2] == 0.f)) continue;
+      v3 o, d;
+      float nt, ft;
+      cam_ray(c.cam, ((float)px + jx) * c.cam.inv_w, ((float)py + jy) * c.cam.inv_h, o, d, nt, ft);
+      // first walk: N_v into floats 0..2 of vertex v's record, f_v / q_v into 3..5
+      int n = 0;
+      path_walk_prb<false, false>(
+          a, p, idx, o, d, nt, ft, s_dyn + threadIdx.x, nthr,
+          [&](int v, const SampleTerms &st, const AppTerms &, const MatVtx &, v3, const float (&)[3]) {
+            float tv[3] = {0.f, 0.f, 0.f};
+            if (st.has_proj) path_tex(kernarg_shade(), st, a.tex, tv);
+            float *rec = s_path + (size_t)(v - 1) * pstride;
+#pragma unroll
+            for (int ch = 0; ch < 3; ++ch) rec[ch * nthr] = st.base[ch] * (st.spot[ch] + tv[ch] * st.proj_fac) + (st.spot_b[ch] + tv[ch] * st.proj_fac_b);
+            n = v;
+          },
+          [&](int v, const SampleTerms &, const PathVtx &, const AppTerms &, v3, v3, const float (&)[3], float iq, const float (&f)[3], const PrbBounce &) {
+            float *rec = s_path + (size_t)(v - 1) * pstride;
+#pragma unroll
+            for (int ch = 0; ch < 3; ++ch) rec[(3 + ch) * nthr] = f[ch] * iq;
+          });
+      if (n == 0) continue;
+      { // the suffix radiances S_v over the N_v (S_n = N_n: the last vertex's f / q may be stale and is not read)
+        float S[3] = {0.f, 0.f, 0.f};
+        for (int v = n; v >= 1; --v) {
+          float *rec = s_path + (size_t)(v - 1) * pstride;
+#pragma unroll
+          for (int ch = 0; ch < 3; ++ch) {
+            S[ch] = v < n ? __builtin_fmaf(rec[(3 + ch) * nthr], S[ch], rec[ch * nthr]) : rec[ch * nthr];
+            rec[ch * nthr] = S[ch];
+          }
+        }
+      }
+      // second walk: the derivatives
+      path_walk_prb<true, MAT>(
+          a, p, idx, o, d, nt, ft, s_dyn + threadIdx.x, nthr,
+          [&](int, const SampleTerms &st, const AppTerms &ap, const MatVtx &mv, v3 dv, const float (&beta)[3]) {
+            const ShadeK &k = kernarg_shade();
+            const float w[3] = {q[0] * beta[0], q[1] * beta[1], q[2] * beta[2]};
+            float tv[3] = {0.f, 0.f, 0.f};
+            if (st.has_proj) {
+              path_tex(k, st, a.tex, tv);
+              float cw[3]; // d radiance / d (texture value) per channel, times the sample's gradient: k_path_bwd's sum
+#pragma unroll
+              for (int ch = 0; ch < 3; ++ch) cw[ch] = w[ch] * (st.base[ch] * st.proj_fac + st.proj_fac_b);
+              const int tc = k.tc;
+              const size_t o00 = ((size_t)st.iy0 * k.tw + st.ix0) * tc, o01 = ((size_t)st.iy0 * k.tw + st.ix1) * tc;
+              const size_t o10 = ((size_t)st.iy1 * k.tw + st.ix0) * tc, o11 = ((size_t)st.iy1 * k.tw + st.ix1) * tc;
+              if (tc == 1) {
+                const float ws = cw[0] * k.p_color[0] + cw[1] * k.p_color[1] + cw[2] * k.p_color[2];
+                atomicAdd(p.gtex + o00, ws * st.wy0 * st.wx0);
+                atomicAdd(p.gtex + o01, ws * st.wy0 * st.wx1);
+                atomicAdd(p.gtex + o10, ws * st.wy1 * st.wx0);
+                atomicAdd(p.gtex + o11, ws * st.wy1 * st.wx1);
+              } else {
+#pragma unroll
+                for (int ch = 0; ch < 3; ++ch) {
+                  atomicAdd(p.gtex + o00 + ch, cw[ch] * st.wy0 * st.wx0);
+                  atomicAdd(p.gtex + o01 + ch, cw[ch] * st.wy0 * st.wx1);
+                  atomicAdd(p.gtex + o10 + ch, cw[ch] * st.wy1 * st.wx0);
+                  atomicAdd(p.gtex + o11 + ch, cw[ch] * st.wy1 * st.wx1);
+                }
+              }
+            }
+            const float lum = wl[0] * st.base[0] + wl[1] * st.base[1] + wl[2] * st.base[2];
+            if (MAT) { // N_c = sum_e (b_c A_e + B_e) E_ec: one reverse pass per emitter, as k_render_bwd_material with the weight q beta
+              const float *mt = mat_table(k);
+              if (k.mat_stride == FFX_MAT_STRIDE && mt[(size_t)FFX_MAT_STRIDE * st.shape + FFX_MAT_MODEL] != 0.f && (mv.kp != 0.f || mv.ks != 0.f)) {
+                const float *mrow = mt + (size_t)FFX_MAT_STRIDE * st.shape;
+                const v3 wv = V3(-dv.x, -dv.y, -dv.z);
+                float gm[FFX_MAT_GRAD_COLS];
+#pragma unroll
+                for (int j = 0; j < FFX_MAT_GRAD_COLS; ++j) gm[j] = 0.f;
+                MatGeoD mg;
+                if (mv.kp != 0.f) {
+                  float uA = 0.f, uB = 0.f;
+#pragma unroll
+                  for (int ch = 0; ch < 3; ++ch) { const float e = w[ch] * tv[ch] * mv.kp; uA += e * st.base[ch]; uB += e; }
+                  material_geometry_d(mv.ns, wv, mv.wp, mg);
+                  material_terms_vjp(mrow, mg, lum, uA, uB, gm);
+                }
+                if (mv.ks != 0.f) {
+                  float uA = 0.f, uB = 0.f;
+#pragma unroll
+                  for (int ch = 0; ch < 3; ++ch) { const float e = w[ch] * k.s_int[ch] * mv.ks; uA += e * st.base[ch]; uB += e; }
+                  material_geometry_d(mv.ns, wv, mv.ws, mg);
+                  material_terms_vjp(mrow, mg, lum, uA, uB, gm);
+                }
+                emit_mat(st.shape, gm);
+              }
+            }
+            float qbt = 0.f, gb[3];
+#pragma unroll
+            for (int ch = 0; ch < 3; ++ch) {
+              qbt += w[ch] * st.base[ch] * (k.s_int[ch] * ap.spot_t + tv[ch] * ap.proj_t);
+              gs[ch] += w[ch] * (st.base[ch] * ap.s_f + ap.s_fb);
+            }
+            const float r = lum > 0.f ? qbt / (lum * lum) : 0.f;
+#pragma unroll
+            for (int ch = 0; ch < 3; ++ch) gb[ch] = w[ch] * (st.spot[ch] + tv[ch] * st.proj_fac) - r * wl[ch];
+            emit_base(st.shape, ap, gb);
+          },
+          [&](int v, const SampleTerms &st, const PathVtx &pv, const AppTerms &ap, v3 dv, v3 wo, const float (&beta)[3], float iq, const float (&)[3],
+              const PrbBounce &pb) {
+            if (v >= n) return; // (no vertex behind this bounce: S_v+1 = 0)
+            const float *rec = s_path + (size_t)v * pstride; // vertex v + 1
+            float h[3], hb = 0.f; // h_c = q_c beta_v,c S_v+1,c / q_v
+#pragma unroll
+            for (int ch = 0; ch < 3; ++ch) {
+              h[ch] = q[ch] * beta[ch] * iq * rec[ch * nthr];
+              hb += h[ch] * st.base[ch];
+            }
+            if (h[0] == 0.f && h[1] == 0.f && h[2] == 0.f) return;
+            float gb[3] = {h[0], h[1], h[2]}; // Lambert rows: f = b
+            if (pb.model) { // f_c = (b_c A + B) / cos_o, A = A0 + pi tau / lum(b)
+              const float lum = wl[0] * st.base[0] + wl[1] * st.base[1] + wl[2] * st.base[2];
+              const float r = lum > 0.f ? hb * pb.tau / (lum * lum) : 0.f;
+#pragma unroll
+              for (int ch = 0; ch < 3; ++ch) gb[ch] = (h[ch] * pb.A - r * wl[ch]) * pb.ic;
+              if (MAT) {
+                const float *mrow = mat_table(kernarg_shade()) + (size_t)FFX_MAT_STRIDE * st.shape;
+                float gm[FFX_MAT_GRAD_COLS];
+#pragma unroll
+                for (int j = 0; j < FFX_MAT_GRAD_COLS; ++j) gm[j] = 0.f;
+                MatGeoD mg;
+                material_geometry_d(pv.ns, V3(-dv.x, -dv.y, -dv.z), wo, mg);
+                material_terms_vjp(mrow, mg, lum, hb * pb.ic, (h[0] + h[1] + h[2]) * pb.ic, gm);
+                emit_mat(st.shape, gm);
+              }
+            }
+            emit_base(st.shape, ap, gb);
+          });
+    }
+  }
+#pragma unroll
+  for (int ch = 0; ch < 3; ++ch) {
+    const float v = wave_sum_tree(gs[ch]);
+    if (lane == 0 && v != 0.f) atomicAdd(a.gspot + ch, v);
+  }
+  __syncthreads();
+  if (lds)
+    for (int i = threadIdx.x; i < a.n_shapes * 3; i += nthr) {
+      const float v = s_rows[i];
+      if (v != 0.f) atomicAdd(a.grow + i, v);
+    }
+  if (lds_m)
+    for (int i = threadIdx.x; i < a.n_shapes * FFX_MAT_GRAD_COLS; i += nthr) {
+      const float v = s_mat[i];
+      if (v != 0.f) atomicAdd(p.gmat + i, v);
+    }
+}
+template <bool RF>
+__global__ void __launch_bounds__(64 * FFX_APP_WAVES)
+    k_path_bwd_prb(ShadeK c, AppArgs a, PrbArgs p, const float *__restrict__ gsrc, int stack_ints) {
+  extern __shared__ int s_dyn[];
+  __shared__ float s_rows[FFX_APP_LDS_ROWS * 3];
+  path_bwd_prb<RF, false>(c, a, p, gsrc, s_dyn, stack_ints, s_rows, nullptr);
+}
+template <bool RF>
+__global__ void __launch_bounds__(64 * FFX_APP_WAVES)
+    k_path_bwd_prb_material(ShadeK c, AppArgs a, PrbArgs p, const float *__restrict__ gsrc, int stack_ints) {
+  extern __shared__ int s_dyn[];
+  __shared__ float s_rows[FFX_APP_LDS_ROWS * 3];
+  __shared__ float s_mat[FFX_MAT_LDS_ROWS * FFX_MAT_GRAD_COLS];
+  path_bwd_prb<RF, true>(c, a, p, gsrc, s_dyn, stack_ints, s_rows, s_mat);
+}
+
 // ------------------------------------------------------------------------------------------ host side
 static int cam_prepare(const ffx_camera *c, CamK &k) {
   if (c->width < 1 || c->height < 1) return 0;
@@ -5385,6 +5694,7 @@ static int render_fwd_impl(const void *bvh, const ffx_bvh_info *info, const ffx_
   do {                                                                                                                                                    \
     if ((flags_) & FFX_RENDER_GRAD_APPEARANCE) FFX_FAIL(FFX_ERR_UNSUPPORTED, "%s: FFX_RENDER_GRAD_APPEARANCE is served by ffx_render_bwd[_filtered] only", what_); \
     if ((flags_) & FFX_RENDER_GRAD_MATERIAL) FFX_FAIL(FFX_ERR_UNSUPPORTED, "%s: FFX_RENDER_GRAD_MATERIAL is served by ffx_render_bwd[_filtered] only", what_);     \
+    if ((flags_) & FFX_RENDER_GRAD_PRB) FFX_FAIL(FFX_ERR_UNSUPPORTED, "%s: FFX_RENDER_GRAD_PRB is served by ffx_render_bwd[_filtered] only", what_);               \
   } while (0)
 int ffx_render_fwd(const void *bvh, const ffx_bvh_info *info, const ffx_scene_desc *sd, const float *shape_albedo, const float *tex, int spp,
                    uint32_t seed, int img_fp16, void *img, ffx_stream s) {
@@ -5669,17 +5979,83 @@ static int render_bwd_appearance(const void *bvh, const ffx_bvh_info *info, cons
   FFX_CHECK_LAUNCH(rf_scratch ? "render_bwd_filtered (appearance)" : "render_bwd (appearance)");
   return FFX_OK;
 }
-// FFX_RENDER_GRAD_MATERIAL extends FFX_RENDER_GRAD_APPEARANCE: alone it is an argument error
+// FFX_RENDER_GRAD_PRB (include/ffx.h): the appearance (and material) blocks at max_depth > 2 — ONE launch of k_path_bwd_prb[_material],
+// which also forms the texture part (k_path_bwd's sum) while it replays the paths
+#define FFX_PRB_STATIC_LDS ((FFX_APP_LDS_ROWS * 3 + FFX_MAT_LDS_ROWS * FFX_MAT_GRAD_COLS) * sizeof(float))
+static int render_bwd_prb(const void *bvh, const ffx_bvh_info *info, const ffx_scene_desc *sd, const float *shape_albedo, int spp, uint32_t seed, int flags,
+                          const float *gimg, float *gtex, ffx_stream s, void *rf_scratch) {
+  if (!bvh || !info || !sd || (!shape_albedo && sd->n_mat_h <= 0) || !gimg || !gtex || spp < 1) FFX_FAIL(FFX_ERR_ARG, "render_bwd: bad argument");
+  RenderSetup r;
+  if (const int rc = render_setup("render_bwd", bvh, info, sd, shape_albedo, spp, seed, flags, rf_scratch, r)) return rc;
+  if (sd->n_shapes < 1) FFX_FAIL(FFX_ERR_ARG, "render_bwd: n_shapes < 1");
+  const long n_tex = (long)sd->proj.tex_w * sd->proj.tex_h * sd->proj.tex_channels;
+  if (n_tex < 0) FFX_FAIL(FFX_ERR_ARG, "render_bwd: bad projector texture size");
+  if (r.n_pix >= (1L << 31)) FFX_FAIL(FFX_ERR_UNSUPPORTED, "render_bwd: more than 2^31 pixels");
+  const hipStream_t st = (hipStream_t)s;
+  AppArgs a;
+  memset(&a, 0, sizeof a);
+  a.nodes = r.b.nodes; a.recs = r.b.recs; a.nrec = r.b.nrec;
+  a.tex = sd->proj.enabled ? gimg + (size_t)r.n_pix * 3 : nullptr; // (the forward's texture behind gimg, as for the direct-light blocks)
+  a.spp = spp; a.n_pix = (int)r.n_pix; a.n_shapes = sd->n_shapes; a.seed_key = r.seed_key;
+  a.grow = gtex + n_tex; a.gspot = a.grow + (size_t)3 * sd->n_shapes;
+  float *bt = a.gspot + 3;
+  for (int k = 0; k < r.c.n_base_tex; ++k) {
+    a.gbt[k] = bt;
+    bt += (size_t)3 * r.c.btw[k] * r.c.bth[k];
+  }
+  const bool material = (flags & FFX_RENDER_GRAD_MATERIAL) != 0;
+  PrbArgs p;
+  p.max_depth = r.max_depth; p.rr_depth = r.rr_depth; p.path_key = path_args(r).path_key;
+  p.gtex = gtex; p.gmat = material ? gtex + n_tex + FFX_RENDER_APPEARANCE_FLOATS(sd) : nullptr;
+  const float *gsrc = gimg;
+  if (rf_scratch) {
+    gsrc = (const float *)rf_G(r, gimg, rf_scratch, st, "render_bwd_filtered (prb)/weights", "render_bwd_filtered (prb)/gather");
+    if (!gsrc) return FFX_ERR_LAUNCH;
+  }
+  // LDS per wave: the traversal stack and the path records [max_depth - 1][6] per lane; the widest workgroup (4, 2, 1 waves) that stays inside 64 KB
+  const int depth = info->max_depth < 8 ? 8 : info->max_depth;
+  const size_t wave_stack = (size_t)depth * 64 * sizeof(int), wave_path = (size_t)(r.max_depth - 1) * 6 * 64 * sizeof(float);
+  int waves = FFX_APP_WAVES;
+  while (waves > 1 && waves * (wave_stack + wave_path) + FFX_PRB_STATIC_LDS > 65536) waves >>= 1;
+  const size_t dyn = waves * (wave_stack + wave_path);
+  const int stack_ints = depth * 64 * waves;
+  const long blocks = ffx_cdiv(r.n_pix, (long)waves), cap = 8192 / waves; // (every workgroup strides over the film, as k_render_bwd_appearance's)
+  const unsigned grid = (unsigned)(blocks < cap ? blocks : cap);
+  if (material) {
+    if (rf_scratch) hipLaunchKernelGGL(k_path_bwd_prb_material<true>, dim3(grid), dim3(64 * waves), dyn, st, r.c, a, p, gsrc, stack_ints);
+    else hipLaunchKernelGGL(k_path_bwd_prb_material<false>, dim3(grid), dim3(64 * waves), dyn, st, r.c, a, p, gsrc, stack_ints);
+    FFX_CHECK_LAUNCH(rf_scratch ? "render_bwd_filtered (prb, material)" : "render_bwd (prb, material)");
+    return FFX_OK;
+  }
+  if (rf_scratch) hipLaunchKernelGGL(k_path_bwd_prb<true>, dim3(grid), dim3(64 * waves), dyn, st, r.c, a, p, gsrc, stack_ints);
+  else hipLaunchKernelGGL(k_path_bwd_prb<false>, dim3(grid), dim3(64 * waves), dyn, st, r.c, a, p, gsrc, stack_ints);
+  FFX_CHECK_LAUNCH(rf_scratch ? "render_bwd_filtered (prb)" : "render_bwd (prb)");
+  return FFX_OK;
+}
+// FFX_RENDER_GRAD_MATERIAL and FFX_RENDER_GRAD_PRB extend FFX_RENDER_GRAD_APPEARANCE: alone each is an argument error
 #define FFX_MATERIAL_NEEDS_APPEARANCE(flags_, what_)                                                                                      \
   do {                                                                                                                                    \
     if (((flags_) & (FFX_RENDER_GRAD_MATERIAL | FFX_RENDER_GRAD_APPEARANCE)) == FFX_RENDER_GRAD_MATERIAL)                                 \
       FFX_FAIL(FFX_ERR_ARG, "%s: FFX_RENDER_GRAD_MATERIAL needs FFX_RENDER_GRAD_APPEARANCE", what_);                                      \
+    if (((flags_) & FFX_RENDER_GRAD_PRB) && !((flags_) & FFX_RENDER_GRAD_APPEARANCE))                                                     \
+      FFX_FAIL(FFX_ERR_ARG, "%s: FFX_RENDER_GRAD_PRB needs FFX_RENDER_GRAD_APPEARANCE", what_);                                           \
   } while (0)
+// the appearance route of a flags word: with FFX_RENDER_GRAD_PRB and max_depth > 2 (or a bad depth field, which render_setup reports) the path replay;
+// else the direct-light kernels, which ignore the bit (and refuse path bits without it, as before)
+static int render_bwd_leaves(const void *bvh, const ffx_bvh_info *info, const ffx_scene_desc *sd, const float *shape_albedo, int spp, uint32_t seed, int flags,
+                             const float *gimg, float *gtex, ffx_stream s, void *rf_scratch) {
+  if (flags & FFX_RENDER_GRAD_PRB) {
+    int md, rr;
+    if (!path_depths(flags, md, rr) || md > 2) return render_bwd_prb(bvh, info, sd, shape_albedo, spp, seed, flags, gimg, gtex, s, rf_scratch);
+    flags &= ~(FFX_RENDER_GRAD_PRB | FFX_RENDER_PATH_MASK); // (max_depth 2: direct light, whatever rr_depth says)
+  }
+  return render_bwd_appearance(bvh, info, sd, shape_albedo, spp, seed, flags, gimg, gtex, s, rf_scratch);
+}
 
 int ffx_render_bwd(const void *bvh, const ffx_bvh_info *info, const ffx_scene_desc *sd, const float *shape_albedo, int spp, uint32_t seed, int flags,
                    const float *gimg, float *gtex, ffx_stream s) {
   FFX_MATERIAL_NEEDS_APPEARANCE(flags, "render_bwd");
-  if (flags & FFX_RENDER_GRAD_APPEARANCE) return render_bwd_appearance(bvh, info, sd, shape_albedo, spp, seed, flags, gimg, gtex, s, nullptr);
+  if (flags & FFX_RENDER_GRAD_APPEARANCE) return render_bwd_leaves(bvh, info, sd, shape_albedo, spp, seed, flags, gimg, gtex, s, nullptr);
   return render_bwd_impl(bvh, info, sd, shape_albedo, spp, seed, flags, gimg, gtex, s, nullptr);
 }
 
@@ -5754,7 +6130,7 @@ int ffx_render_bwd_filtered(const void *bvh, const ffx_bvh_info *info, const ffx
                             const float *gimg, float *gtex, void *scratch, ffx_stream s) {
   if (!scratch || ((uintptr_t)scratch & 15) != 0) FFX_FAIL(FFX_ERR_ARG, "render_bwd_filtered: scratch is NULL or not 16-byte aligned");
   FFX_MATERIAL_NEEDS_APPEARANCE(flags, "render_bwd_filtered");
-  if (flags & FFX_RENDER_GRAD_APPEARANCE) return render_bwd_appearance(bvh, info, sd, shape_albedo, spp, seed, flags, gimg, gtex, s, scratch);
+  if (flags & FFX_RENDER_GRAD_APPEARANCE) return render_bwd_leaves(bvh, info, sd, shape_albedo, spp, seed, flags, gimg, gtex, s, scratch);
   return render_bwd_impl(bvh, info, sd, shape_albedo, spp, seed, flags, gimg, gtex, s, scratch);
 }
 

@@ -215,7 +215,7 @@ def render(tex, geom, sd, albedo, spp, seed=0, fp16=False, max_depth=2, rr_depth
     (128 B per pixel + a small arena: 40 MB at 512x512x64; under a gaussian film an arena of per-sample records — 16 / 20 bytes per sample
     of the pixels that have a lit sample, room for every pixel up to 344 MB, a quarter of them beyond) and the adjoint scatters those footprints; beyond FFX_CACHE_LIMIT_GB the adjoint re-traces instead (then the geometry must not be re-fitted between
     forward and backward).
-    max_depth > 2: Mitsuba's `path` integrator; no cache — the adjoint replays the forward's paths, so the geometry must not be
+    max_depth > 2: Mitsuba's `path` integrator (a `prb` integrator renders the same image and, for `tex.data`, is `path`); no cache — the adjoint replays the forward's paths, so the geometry must not be
     re-fitted between forward and backward."""
     if max_depth != 2:
         ops.path_flags(max_depth, rr_depth)  # (the range check before any launch)

@@ -1171,13 +1171,15 @@ def traverse(scene: Scene) -> SceneParameters:
 
 
 class Integrator:
-    """what `mi.load_dict({"type": "path" | "direct", ...})` returns and `mi.render(..., integrator=)` / `PatternOptimizer(..., integrator=)` take:
-    Mitsuba's `path` with max_depth in 2 .. 8 (2: direct light at the primary hit, what every render without an integrator computes; k: k - 2
-    indirect bounces) and Russian roulette from depth rr_depth on (default 5), or `direct` (= max_depth 2).  DESIGN.md 4.4."""
+    """what `mi.load_dict({"type": "path" | "prb" | "direct", ...})` returns and `mi.render(..., integrator=)` / `PatternOptimizer(..., integrator=)`
+    take: Mitsuba's `path` with max_depth in 2 .. 8 (2: direct light at the primary hit, what every render without an integrator computes; k: k - 2
+    indirect bounces) and Russian roulette from depth rr_depth on (default 5), or `direct` (= max_depth 2).  DESIGN.md 4.4.  `prb` (path replay
+    backpropagation) renders what `path` renders, bit for bit; under it mi.render also differentiates the base colours, the spot's
+    intensity, base-colour textures and the BSDF parameters through the bounces."""
 
     def __init__(self, type_="path", max_depth=-1, rr_depth=5):
-        if type_ not in ("path", "direct"):
-            raise ValueError(f"integrator type {type_!r}: only 'path' and 'direct' are served")
+        if type_ not in ("path", "prb", "direct"):
+            raise ValueError(f"integrator type {type_!r}: only 'path', 'prb' and 'direct' are served")
         if type_ == "direct":
             max_depth = 2
         ops.path_flags(max_depth, rr_depth)  # (ValueError outside 2 .. 8: Mitsuba's default -1, unbounded, included)
@@ -1188,19 +1190,19 @@ class Integrator:
 
 
 def load_dict(d: dict):
-    """mi.load_dict for integrator dictionaries: {"type": "path", "max_depth": k, "rr_depth": r} or {"type": "direct"} -> Integrator.
+    """mi.load_dict for integrator dictionaries: {"type": "path" | "prb", "max_depth": k, "rr_depth": r} or {"type": "direct"} -> Integrator.
     Scenes come from load_file / load_scene_data."""
     if not isinstance(d, dict) or "type" not in d:
         raise ValueError("load_dict: a dictionary with a 'type'")
     t = d["type"]
-    if t not in ("path", "direct"):
-        raise NotImplementedError(f"load_dict: type {t!r} — only the integrators 'path' and 'direct' (scenes: mi.load_file / mi.load_scene_data)")
-    extra = set(d) - ({"type", "max_depth", "rr_depth"} if t == "path" else {"type"})
+    if t not in ("path", "prb", "direct"):
+        raise NotImplementedError(f"load_dict: type {t!r} — only the integrators 'path', 'prb' and 'direct' (scenes: mi.load_file / mi.load_scene_data)")
+    extra = set(d) - ({"type", "max_depth", "rr_depth"} if t != "direct" else {"type"})
     if extra:
         raise ValueError(f"load_dict: {t!r} integrator properties {sorted(extra)} are not served")
     if t == "direct":
         return Integrator("direct")
-    return Integrator("path", d.get("max_depth", -1), d.get("rr_depth", 5))
+    return Integrator(t, d.get("max_depth", -1), d.get("rr_depth", 5))
 
 
 def render(scene: Scene, params: SceneParameters = None, spp: int = 16, seed: int = 0, sensor: int = 0, fp16: bool = False, integrator: Integrator = None):
@@ -1208,7 +1210,8 @@ def render(scene: Scene, params: SceneParameters = None, spp: int = 16, seed: in
     Differentiable w.r.t. `tex.data` when that parameter is a tensor that requires grad — and w.r.t. `<mat>.brdf_0.base_color.value`,
     `<spot>.intensity.value`, `<mat>.brdf_0.base_color.data` and the principled BSDF's parameters (`<mat>.brdf_0.{roughness, anisotropic, metallic,
     spec_trans, spec_tint, sheen, sheen_tint, flatness, clearcoat, clearcoat_gloss}.value`, `.specular`, `.eta`) when such a tensor was assigned to
-    them (direct light only; each BSDF leaf's gradient is summed over the material's shapes).
+    them (each BSDF leaf's gradient is summed over the material's shapes).  Those leaves need direct light (max_depth 2) or the `prb`
+    integrator, which carries them through the bounces; `path` with max_depth > 2 refuses them.
     integrator (mi.load_dict): None or max_depth 2 renders direct light at the primary hit, as always; deeper paths run on the caller's stream."""
     if sensor != 0:
         raise NotImplementedError("only sensor 0 renders; further sensors are projector proxies")
@@ -1289,17 +1292,19 @@ class _AppearanceRender(torch.autograd.Function):
     block: kind "bsdf" = (rows, column of the block, factor) — the factor chains `specular` to eta, or is 0 for a leaf that does not drive the row)"""
 
     @staticmethod
-    def forward(ctx, tex, scene, sd, mats, spp, seed, fp16, kinds, *leaves):
+    def forward(ctx, tex, scene, sd, mats, spp, seed, fp16, kinds, depths, *leaves):
         geom = scene.geom
         t = tex.detach()
         t = (t if t.is_contiguous() else t.contiguous())
         t = t.unsqueeze(-1) if t.dim() == 2 else t
-        ctx.geom, ctx.sd, ctx.spp, ctx.seed, ctx.kinds = geom, sd, spp, seed, kinds
+        ctx.geom, ctx.sd, ctx.spp, ctx.seed, ctx.kinds, ctx.depths = geom, sd, spp, seed, kinds, depths
         ctx.tex, ctx.tex_shape = t, tex.shape
         ctx.mats = mats.clone() if mats is not None else None  # (the scene's table is rewritten in place by the next randomisation)
         ctx.keep = [bt for _, bt in scene._base_tex]  # (the description points at them)
         ctx.leaf_meta = [(x.shape, x.dtype, x.device) for x in leaves]
         ctx.pose_version = geom.version
+        if depths[0] > 2:  # (`prb`: the path integrator's image)
+            return geom.render_fwd(sd, mats, t, spp, seed, fp16, max_depth=depths[0], rr_depth=depths[1])
         return geom.render_fwd(sd, mats, t, spp, seed, fp16)
 
     @staticmethod
@@ -1308,7 +1313,10 @@ class _AppearanceRender(torch.autograd.Function):
             raise RuntimeError("mi.render: the scene was updated between the render and its backward — the appearance adjoint re-traces the render's pose: "
                                "call backward before the next params.update()")
         material = any(kind == "bsdf" for kind, _ in ctx.kinds)
-        gtex, app = ctx.geom.render_bwd(ctx.sd, ctx.mats, ctx.spp, ctx.seed, g.float().contiguous(), appearance=True, tex=ctx.tex, material=material)
+        if ctx.depths[0] > 2:  # (`prb`: FFX_RENDER_GRAD_PRB's replay of the paths yields the same blocks)
+            gtex, app = ctx.geom.render_bwd_prb(ctx.sd, ctx.mats, ctx.spp, ctx.seed, g.float().contiguous(), ctx.tex, ctx.depths[0], ctx.depths[1], material=material)
+        else:
+            gtex, app = ctx.geom.render_bwd(ctx.sd, ctx.mats, ctx.spp, ctx.seed, g.float().contiguous(), appearance=True, tex=ctx.tex, material=material)
         grads = []
         for (kind, arg), (shape, dtype, device) in zip(ctx.kinds, ctx.leaf_meta):
             if kind == "mat":
@@ -1326,14 +1334,15 @@ class _AppearanceRender(torch.autograd.Function):
             v = v.sum().reshape(shape) if n == 1 else v.reshape(shape)  # (a scalar assigned to a colour is broadcast to its three channels)
             grads.append(v.to(device=device, dtype=dtype))
         gt = gtex.reshape(ctx.tex_shape) if ctx.needs_input_grad[0] else None
-        return (gt, None, None, None, None, None, None, None, *grads)
+        return (gt, None, None, None, None, None, None, None, None, *grads)
 
 
 def _render_appearance(scene, spp, seed, fp16, integrator):
     """mi.render while appearance leaves are assigned and grad is enabled: through _AppearanceRender on the caller's stream"""
-    if integrator is not None and integrator.max_depth > 2:
-        raise ValueError("mi.render: the gradients of base colours, spot intensity and BSDF parameters are served for direct light only (max_depth 2); "
-                         "the scene holds parameters that require grad: " + ", ".join(sorted(scene._params._leaves)))
+    if integrator is not None and integrator.max_depth > 2 and integrator.type != "prb":
+        raise ValueError("mi.render: under the 'path' integrator the gradients of base colours, spot intensity and BSDF parameters are served for direct "
+                         "light only (max_depth 2); use the 'prb' integrator (mi.load_dict({'type': 'prb', ...})) for max_depth > 2.  "
+                         "The scene holds parameters that require grad: " + ", ".join(sorted(scene._params._leaves)))
     if ops.deterministic_mode():
         raise ValueError("mi.render: the gradients of base colours, spot intensity and BSDF parameters have no deterministic adjoint (FFX_DETERMINISTIC=1)")
     p = scene._params
@@ -1379,4 +1388,5 @@ def _render_appearance(scene, spp, seed, fp16, integrator):
         else:
             kinds.append(("spot", None))
         leaves.append(leaf)
-    return TensorXf(_AppearanceRender.apply(tex, scene, sd, scene.materials_arg(sd), int(spp), int(seed), bool(fp16), kinds, *leaves))
+    depths = (2, 5) if integrator is None else (int(integrator.max_depth), int(integrator.rr_depth))
+    return TensorXf(_AppearanceRender.apply(tex, scene, sd, scene.materials_arg(sd), int(spp), int(seed), bool(fp16), kinds, depths, *leaves))

@@ -1181,6 +1181,22 @@ class DeviceGeometry:
             deterministic = deterministic_mode()
         if deterministic:
             raise ValueError("render_bwd(appearance=True) has no deterministic adjoint (FFX_DETERMINISTIC / deterministic=True)")
+        return self._render_bwd_leaves(sd, albedo, spp, seed, gimg, tex, material, 0, "render_bwd(appearance=True)")
+
+    def render_bwd_prb(self, sd, albedo, spp, seed, gimg, tex, max_depth, rr_depth=5, material=False, deterministic=None):
+        """path replay backpropagation (Mitsuba's `prb`, FFX_RENDER_GRAD_PRB): -> (gtex, AppearanceGrad) of a render_fwd with the same
+        max_depth, rr_depth, spp and seed — render_bwd(appearance=True[, material=True])'s blocks through every bounce, with the texture gradient of
+        render_bwd(max_depth=...) from the same launch.  The roulette's decisions and survival probabilities are constants of the replay.  max_depth 2
+        is render_bwd(appearance=True).  `tex`: the forward's projector texture (None without a projector).  Float atomics only."""
+        path = path_flags(max_depth, rr_depth)
+        if deterministic is None:
+            deterministic = deterministic_mode()
+        if deterministic:
+            raise ValueError("render_bwd_prb has no deterministic adjoint (FFX_DETERMINISTIC / deterministic=True)")
+        return self._render_bwd_leaves(sd, albedo, spp, seed, gimg, tex, material, (path | _abi.RENDER_GRAD_PRB) if path else 0, "render_bwd_prb")
+
+    def _render_bwd_leaves(self, sd, albedo, spp, seed, gimg, tex, material, path, what):
+        """the call behind render_bwd(appearance=True) (path 0) and render_bwd_prb (the path bits | FFX_RENDER_GRAD_PRB)"""
         H, W = sd.cam.height, sd.cam.width
         n_tex = sd.proj.tex_h * sd.proj.tex_w * sd.proj.tex_channels
         bt = [(int(sd.base_tex_h[k]), int(sd.base_tex_w[k])) for k in range(sd.n_base_tex)]
@@ -1188,7 +1204,7 @@ class DeviceGeometry:
         src = gimg.reshape(-1)
         if sd.proj.enabled:
             if tex is None or tex.numel() != n_tex:
-                raise ValueError(f"render_bwd(appearance=True): the forward's projector texture ({n_tex} floats) is needed")
+                raise ValueError(f"{what}: the forward's projector texture ({n_tex} floats) is needed")
             src = torch.cat([gimg.reshape(-1).float(), tex.detach().reshape(-1).to(device=self.device, dtype=torch.float32)])
         if src.numel() < H * W * 3:
             raise ValueError("gimg must hold [H, W, 3] floats")
@@ -1196,7 +1212,8 @@ class DeviceGeometry:
         out = torch.zeros(n_tex + n_app + n_mat, dtype=torch.float32, device=self.device)
         mats_arg = _check_materials(sd, albedo)
         blob = self.blob
-        flags = self._apex_flag(apex_key(sd)) | _abi.RENDER_GRAD_APPEARANCE | (_abi.RENDER_GRAD_MATERIAL if material else 0)
+        # (the path replay walks per lane: no apex records are read or written)
+        flags = (path if path else self._apex_flag(apex_key(sd))) | _abi.RENDER_GRAD_APPEARANCE | (_abi.RENDER_GRAD_MATERIAL if material else 0)
         with self._timed("render_bwd"):
             if sd.rfilter:
                 scratch = torch.empty(render_filter_bytes(sd), dtype=torch.uint8, device=self.device)

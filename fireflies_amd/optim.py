@@ -101,7 +101,8 @@ class PatternOptimizer:
     def __init__(self, mi_scene, ff_scene, laser, sigma=10.0, tex_size=(500, 500), spp=64, lr=1e-3, reg_weight=0.1, samples_per_step=1,
                  base_seed=0, loss_fn=coverage_loss, blur=(5, 3.0), integrator=None):
         self.mi_scene, self.ff_scene, self.laser = mi_scene, ff_scene, laser
-        # mi.load_dict's integrator: max_depth > 2 renders paths; its adjoint replays them (the "retrace" route)
+        # mi.load_dict's integrator: max_depth > 2 renders paths; its adjoint replays them (the "retrace" route).  `prb` is `path`
+        # here: the optimiser differentiates tex.data only
         self.max_depth, self.rr_depth = (2, 5) if integrator is None else (int(integrator.max_depth), int(integrator.rr_depth))
         if self.max_depth > 2 and ops.deterministic_mode():
             raise ValueError("PatternOptimizer: max_depth > 2 has no deterministic adjoint (FFX_DETERMINISTIC=1)")

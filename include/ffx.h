@@ -794,6 +794,17 @@ int ffx_det_finish(const void *acc /*[dev] int64 [n]*/, int scale_log2, size_t n
 #define FFX_RENDER_GRAD_MATERIAL 0x20000
 #define FFX_RENDER_MATERIAL_COLS 11
 #define FFX_RENDER_MATERIAL_FLOATS(sd) ((size_t)FFX_RENDER_MATERIAL_COLS * (size_t)(sd)->n_shapes)
+/* Path replay backpropagation (Mitsuba's `prb` integrator): FFX_RENDER_GRAD_PRB, together with FFX_RENDER_GRAD_APPEARANCE
+ * (and optionally FFX_RENDER_GRAD_MATERIAL) and FFX_RENDER_PATH(max_depth, rr_depth) in the flags word of ffx_render_bwd / ffx_render_bwd_filtered,
+ * serves the appearance and material blocks at max_depth 3 .. FFX_RENDER_MAX_DEPTH_LIMIT: the gradients of a ffx_render_fwd[_filtered] with the same
+ * path bits, seed and spp, through every bounce.  An additive extension of ABI 11 (FFX_ABI_VERSION is unchanged).  Input and output buffers exactly
+ * as for the two blocks at direct light; gtex receives the texture gradient of a call with the path bits alone (up to the order of the float
+ * atomics) from the same single launch.  The roulette's survival probabilities and decisions are constants of the replay (detached): the blocks are
+ * an unbiased gradient of the expected image, not the derivative of the fixed-seed image once the roulette runs.  Without
+ * FFX_RENDER_GRAD_APPEARANCE the bit answers FFX_ERR_ARG; every other render entry point answers FFX_ERR_UNSUPPORTED when it is set; at max_depth 2
+ * (the field unset or 2) the bit is ignored and the direct-light kernels run.  FFX_RENDER_GRAD_APPEARANCE with path bits but without this bit is
+ * refused as before.  The oracle ignores the bit. */
+#define FFX_RENDER_GRAD_PRB 0x40000
 /* Writes the apex records (the triangles as seen from a fixed ray origin) of sd's camera and enabled emitters into
  * the blob's apex areas — what every packet render does in front of its kernel unless told FFX_RENDER_APEX_READY.  Only
  * sd->cam.to_world, sd->proj.{enabled,to_world} and sd->spot.{enabled,to_world} are read.  No reference counterpart (Mitsuba

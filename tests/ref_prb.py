@@ -1,0 +1,70 @@
+"""Float64 restatement for the `prb` adjoint: tests/ref_path.py's path integrator with the roulette detached.
+
+ref_path.render_fwd recomputes the roulette's survival probability q_v = min(max beta, 0.95) and its decision from the material rows it is given, so
+central differences of it over a row differentiate q_v too (and meet a jump wherever a decision flips).  `prb` treats q_v, the survival test and the
+"max beta = 0 ends the path" test as constants of the replay.  render_fwd_frozen walks the same paths with two throughputs: the one of the rows under
+test, which the image uses, and the one of the unperturbed rows `mats0`, which alone decides survival and supplies q_v.  Central differences of it over
+`mats` (and over the spot's intensity in `sd`) are the detached gradient; with the roulette off it equals ref_path.render_fwd.
+Bounces are cosine-weighted, so no row moves a path: both throughputs belong to the same vertices."""
+import numpy as np
+
+from tests import ref_bruteforce as bf
+from tests import ref_path as rp
+
+
+def path_vertices_frozen(verts, tri_idx, tri_shape, sd, mats, mats0, spp, seed, max_depth, rr_depth=5):
+    """ref_path.path_vertices with survival and q_v from mats0: a list of (sample indices, throughput under mats [n, 3], emitters' terms under mats)"""
+    mats, mats0 = np.asarray(mats, np.float64), np.asarray(mats0, np.float64)
+    tris = bf.world_triangles(verts, tri_idx)
+    v0, e1, e2 = tris
+    key = rp.path_key(seed)
+    o, d, nt, ft = bf.camera_rays(sd.cam, spp, True, seed)
+    idx = np.arange(len(d), dtype=np.uint64)
+    beta, beta0 = np.ones((len(d), 3)), np.ones((len(d), 3))
+    out = []
+    for v in range(1, max_depth):
+        t, prim = bf.intersect(o, d, tris, nt, ft)
+        hit = prim >= 0
+        idx, o, d, beta, beta0, t, prim = idx[hit], o[hit], d[hit], beta[hit], beta0[hit], t[hit], prim[hit]
+        if len(idx) == 0:
+            break
+        P = o + t[:, None] * d
+        n = np.cross(e1[prim], e2[prim])
+        n = n / np.linalg.norm(n, axis=1, keepdims=True)
+        n = np.where(((n * d).sum(1) > 0)[:, None], -n, n)
+        Po = P + n * ((1.0 + np.abs(P).max(1)) * rp.EPS)[:, None]
+        shape = np.asarray(tri_shape)[prim]
+        out.append((idx, beta.copy(), rp._emitters(sd, tris, mats[shape], P, n, Po, d)))
+        if v + 1 >= max_depth:
+            break
+        wo = rp.cosine_dir(n, rp.path_u(key, idx, v, 0), rp.path_u(key, idx, v, 1))
+        with np.errstate(divide="ignore", invalid="ignore"):
+            cos_o = (n * wo).sum(1)[:, None]
+            f = np.pi * bf.bsdf_cos(mats[shape], n, -d, wo) / cos_o
+            f0 = np.pi * bf.bsdf_cos(mats0[shape], n, -d, wo) / cos_o
+        beta, beta0 = beta * f, beta0 * f0
+        bmax0 = beta0.max(1)
+        keep = bmax0 > 0
+        if v >= rr_depth:
+            q = np.minimum(bmax0, 0.95)
+            keep &= rp.path_u(key, idx, v, 2) < q
+            qs = np.where(keep, q, 1.0)[:, None]
+            beta, beta0 = beta / qs, beta0 / qs
+        idx, o, d, beta, beta0 = idx[keep], Po[keep], wo[keep], beta[keep], beta0[keep]
+        nt, ft = np.zeros(len(idx)), np.full(len(idx), np.inf)
+    return out
+
+
+def render_fwd_frozen(verts, tri_idx, tri_shape, sd, mats, mats0, tex, spp, seed, max_depth, rr_depth=5, gaussian_stddev=None):
+    """ref_path.render_fwd of `mats` on the paths, survival decisions and q_v of `mats0`"""
+    W, H = sd.cam.width, sd.cam.height
+    L = np.zeros((W * H * spp, 3))
+    for idx, beta, e in path_vertices_frozen(verts, tri_idx, tri_shape, sd, mats, mats0, spp, seed, max_depth, rr_depth):
+        rad = e["spot"].copy()
+        if sd.proj.enabled:
+            rad += rp._tex_value(sd, tex, e) * e["pfac"]
+        L[idx.astype(np.int64)] += beta * rad
+    if gaussian_stddev is not None:
+        num, den, _ = bf._film_splat(W, H, spp, seed, gaussian_stddev, values=L)
+        return np.where(den[..., None] > 0, num / np.where(den > 0, den, 1.0)[..., None], 0.0)
+    return L.reshape(H, W, spp, 3).mean(2)

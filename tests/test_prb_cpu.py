@@ -1,0 +1,179 @@
+"""The `prb` integrator without a GPU: mi.load_dict, the FFX_RENDER_GRAD_PRB bit in the header and in _abi and its place among the
+flags, the refusals that come before any launch (host dummy pointers, as tests/test_abi_cpu.py's), and the float64 restatement's detached roulette
+(tests/ref_prb.py) against tests/ref_path.py."""
+import ctypes as C
+import os
+import re
+
+import numpy as np
+import pytest
+
+from fireflies_amd import _abi, _lib, mi, scene_desc, scenes
+from tests import ref_path as rp
+from tests import ref_prb
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+FFX_ERR_ARG, FFX_ERR_UNSUPPORTED = -1, -3  # (include/ffx.h; checked below)
+APP, MAT, PRB = _abi.RENDER_GRAD_APPEARANCE, _abi.RENDER_GRAD_MATERIAL, _abi.RENDER_GRAD_PRB
+P3 = _abi.render_path(3, 5)
+GAUSS = {"rfilter": _abi.RFILTER_GAUSSIAN}
+
+
+def _header():
+    with open(os.path.join(ROOT, "include", "ffx.h")) as f:
+        return f.read()
+
+
+def _define(name):
+    m = re.search(r"^#define\s+" + name + r"\s+(\S+)", _header(), re.M)
+    assert m, name
+    return int(m.group(1), 0)
+
+
+def test_load_dict_prb():
+    it = mi.load_dict({"type": "prb", "max_depth": 4, "rr_depth": 3})
+    assert isinstance(it, mi.Integrator) and (it.type, it.max_depth, it.rr_depth) == ("prb", 4, 3)
+    assert mi.load_dict({"type": "prb", "max_depth": 3}).rr_depth == 5
+    assert mi.load_dict({"type": "prb", "max_depth": 2}).max_depth == 2
+    for bad in ({"type": "prb"}, {"type": "prb", "max_depth": -1}, {"type": "prb", "max_depth": 9}, {"type": "prb", "max_depth": 1},
+                {"type": "prb", "max_depth": 3, "hide_emitters": True}, {"type": "prb", "max_depth": 3, "rr_depth": 0}):
+        with pytest.raises(ValueError):
+            mi.load_dict(bad)
+    for t in ("volpath", "prbvolpath", "prb_reparam", "prb_basic"):
+        with pytest.raises(NotImplementedError):
+            mi.load_dict({"type": t, "max_depth": 3})
+    # `path` is what it was
+    it = mi.load_dict({"type": "path", "max_depth": 4, "rr_depth": 3})
+    assert (it.type, it.max_depth, it.rr_depth) == ("path", 4, 3)
+
+
+def test_bit_in_header_and_abi_agree():
+    assert _define("FFX_RENDER_GRAD_PRB") == _abi.RENDER_GRAD_PRB == 0x40000
+    assert _define("FFX_ABI_VERSION") == _abi.FFX_ABI_VERSION == 11
+    for name, val in (("FFX_ERR_ARG", FFX_ERR_ARG), ("FFX_ERR_UNSUPPORTED", FFX_ERR_UNSUPPORTED)):
+        assert int(re.search(r"^\s*" + name + r"\s*=\s*(-?\d+)", _header(), re.M).group(1)) == val
+
+
+def test_bit_is_clear_of_the_other_flags():
+    m = _abi.RENDER_GRAD_PRB
+    assert m & (m - 1) == 0
+    for name in ("FFX_RENDER_FP16", "FFX_RENDER_SPARSE_ADJOINT", "FFX_RENDER_APEX_READY", "FFX_RENDER_CACHE_ZEROED", "FFX_RENDER_CACHE_KEEP_DROPPED",
+                 "FFX_RENDER_GRAD_APPEARANCE", "FFX_RENDER_GRAD_MATERIAL", "FFX_RENDER_PATH_MASK"):
+        assert m & _define(name) == 0, name
+    # every other FFX_RENDER_* flag the header defines as a plain number that could share the word
+    for name, val in re.findall(r"^#define\s+(FFX_RENDER_[A-Z_0-9]+)\s+(0x[0-9a-fA-F]+|\d+)\s", _header(), re.M):
+        if name in ("FFX_RENDER_GRAD_PRB", "FFX_RENDER_MAX_DEPTH_SHIFT", "FFX_RENDER_RR_DEPTH_SHIFT", "FFX_RENDER_MAX_DEPTH_LIMIT", "FFX_RENDER_MATERIAL_COLS"):
+            continue
+        assert m & int(val, 0) == 0, name
+    for f in (_abi.RENDER_FP16, _abi.RENDER_SPARSE_ADJOINT, _abi.RENDER_APEX_READY, _abi.RENDER_CACHE_ZEROED, _abi.RENDER_CACHE_KEEP_DROPPED,
+              _abi.RENDER_GRAD_APPEARANCE, _abi.RENDER_GRAD_MATERIAL, _abi.RENDER_PATH_MASK):
+        assert m & f == 0, f
+    for md in range(2, _abi.RENDER_MAX_DEPTH_LIMIT + 1):
+        for rr in range(1, 16):
+            assert _abi.render_path(md, rr) & m == 0
+
+
+# the parameters of the render entry points, in order (include/ffx.h); `s` is the stream
+_PARAMS = {
+    "ffx_render_fwd": "bvh info sd mats tex spp seed flags img s",
+    "ffx_render_fwd_cache": "bvh info sd mats tex spp seed flags img cache s",
+    "ffx_render_fwd_adjoint": "bvh info sd mats tex spp seed flags img gimg gtex dot s",
+    "ffx_render_fwd_filtered": "bvh info sd mats tex spp seed flags img scratch s",
+    "ffx_render_fwd_adjoint_filtered": "bvh info sd mats tex spp seed flags img gimg gtex scratch s",
+    "ffx_render_fwd_cache_filtered": "bvh info sd mats tex spp seed flags img cache scratch s",
+    "ffx_render_bwd": "bvh info sd mats spp seed flags gimg gtex s",
+    "ffx_render_bwd_filtered": "bvh info sd mats spp seed flags gimg gtex scratch s",
+    "ffx_render_bwd_det": "bvh info sd mats spp seed flags gimg gtex workspace s",
+    "ffx_render_bwd_det_part": "bvh info sd mats spp seed flags gimg part scale_log2 acc workspace s",
+    "ffx_render_bwd_cached": "sd mats cache spp gimg gtex img flags dot s",
+}
+# the entry points that refuse FFX_RENDER_GRAD_APPEARANCE (tests/test_abi_cpu.py _REFUSALS) refuse FFX_RENDER_GRAD_PRB the same way
+_OTHERS = ("ffx_render_fwd", "ffx_render_fwd_cache", "ffx_render_fwd_adjoint", "ffx_render_fwd_filtered", "ffx_render_fwd_adjoint_filtered",
+           "ffx_render_fwd_cache_filtered", "ffx_render_bwd_cached", "ffx_render_bwd_det", "ffx_render_bwd_det_part")
+_CASES = [
+    # the bit extends FFX_RENDER_GRAD_APPEARANCE: without it an argument error, whatever else is set
+    ("ffx_render_bwd", {}, PRB, FFX_ERR_ARG, "render_bwd: FFX_RENDER_GRAD_PRB needs FFX_RENDER_GRAD_APPEARANCE"),
+    ("ffx_render_bwd", {}, PRB | P3, FFX_ERR_ARG, "render_bwd: FFX_RENDER_GRAD_PRB needs FFX_RENDER_GRAD_APPEARANCE"),
+    ("ffx_render_bwd", {}, PRB | MAT | P3, FFX_ERR_ARG, "render_bwd: FFX_RENDER_GRAD_MATERIAL needs FFX_RENDER_GRAD_APPEARANCE"),
+    ("ffx_render_bwd_filtered", GAUSS, PRB | P3, FFX_ERR_ARG, "render_bwd_filtered: FFX_RENDER_GRAD_PRB needs FFX_RENDER_GRAD_APPEARANCE"),
+    *[(f, GAUSS if "filtered" in f else {}, PRB, FFX_ERR_UNSUPPORTED, f"{f[4:]}: FFX_RENDER_GRAD_PRB is served by ffx_render_bwd[_filtered] only") for f in _OTHERS],
+    # without the bit the appearance adjoint refuses path bits as before, with the same message
+    ("ffx_render_bwd", {}, APP | P3, FFX_ERR_UNSUPPORTED, "render_bwd: FFX_RENDER_GRAD_APPEARANCE is served at max_depth 2 only"),
+    ("ffx_render_bwd_filtered", GAUSS, APP | MAT | P3, FFX_ERR_UNSUPPORTED, "render_bwd: FFX_RENDER_GRAD_APPEARANCE is served at max_depth 2 only"),
+    # with it the call reaches the scene checks of the served route (nothing launches: the bvh info is refused first)
+    ("ffx_render_bwd", {"info.n_tris": 0}, APP | PRB | P3, FFX_ERR_ARG, "render_bwd: bad bvh info"),
+    ("ffx_render_bwd", {"info.n_tris": 0}, APP | MAT | PRB | P3, FFX_ERR_ARG, "render_bwd: bad bvh info"),
+    ("ffx_render_bwd_filtered", {"info.n_tris": 0, **GAUSS}, APP | PRB | P3, FFX_ERR_ARG, "render_bwd: bad bvh info"),
+    ("ffx_render_bwd", {"info.n_tris": 0}, APP | PRB | _abi.render_path(9, 5), FFX_ERR_ARG, "render_bwd: bad bvh info"),
+    ("ffx_render_bwd", {"n_shapes": 0, "proj.enabled": 0}, APP | PRB | P3, FFX_ERR_ARG, "render_bwd: n_shapes < 1"),
+    ("ffx_render_bwd", {}, APP | PRB | (1 << _abi.RENDER_MAX_DEPTH_SHIFT), FFX_ERR_ARG, "render_bwd: max_depth must be 2 .. 8"),
+]
+
+
+@pytest.mark.parametrize("case", _CASES, ids=lambda c: f"{c[0][4:]}-{c[2]:#x}-{c[3]}")
+def test_refusals_before_any_launch(case, monkeypatch):
+    name, changes, flags, rc, msg = case
+    for knob in ("FFX_TRAVERSAL", "FFX_WIDE"):
+        monkeypatch.delenv(knob, raising=False)
+    lib = _lib.api().lib
+    buf = np.zeros(64, np.float32)
+    addr = (buf.ctypes.data + 15) & ~15
+    eye = _abi.mat16(np.eye(4))
+    sd = _abi.SceneDesc()
+    sd.cam.to_world, sd.cam.camera_to_sample, sd.cam.width, sd.cam.height = eye, eye, 4, 4
+    sd.proj.to_world, sd.proj.camera_to_sample, sd.proj.tex_w, sd.proj.tex_h, sd.proj.tex_channels, sd.proj.enabled = eye, eye, 4, 4, 1, 1
+    sd.n_shapes = 1
+    info = _abi.BvhInfo(n_tris=1, n_nodes=1, max_depth=1, off_tq=64)
+    for key, v in changes.items():
+        obj, attr = (info, key[5:]) if key.startswith("info.") else (sd, key)
+        while "." in attr:
+            head, attr = attr.split(".", 1)
+            obj = getattr(obj, head)
+        setattr(obj, attr, v)
+    args = dict(bvh=addr, info=C.byref(info), sd=C.byref(sd), mats=addr, tex=addr, spp=4, seed=1, flags=flags, img=addr, cache=addr, scratch=addr, gimg=addr,
+                gtex=addr, dot=addr, workspace=addr, part=1, scale_log2=0, acc=addr, s=None)
+    got = getattr(lib, name)(*[args[p] for p in _PARAMS[name].split()])
+    err = (lib.ffx_last_error() or b"").decode()
+    assert got == rc, (got, err)
+    assert msg in err, err
+
+
+def _corner():
+    quad = np.array([[0, 1, 2], [0, 2, 3]], np.int32)
+    floor = np.array([[0, 0, 0], [2, 0, 0], [2, 2, 0], [0, 2, 0]], np.float32)[None]
+    wall = np.array([[0, 0, 0], [0, 2, 0], [0, 2, 2], [0, 0, 2]], np.float32)[None]
+    meshes = [scenes.MeshData("mesh-Floor", floor, quad, (0.6, 0.55, 0.5), bsdf={"roughness": 0.35, "metallic": 0.2, "specular": 0.6}),
+              scenes.MeshData("mesh-Wall", wall, quad, (0.7, 0.7, 0.75))]
+    cam = scenes.SensorData("PerspectiveCamera", scenes.look_at((3.2, 3.0, 2.4), (0.6, 0.6, 0.5), up=(0, 0, 1)), 50.0, 0.01, 100.0, 6, 6)
+    spot = scenes.SpotData("emit-Spot", scenes.look_at((1.8, 2.6, 2.5), (0.5, 0.5, 0.0), up=(0, 0, 1)), (8.0, 8.0, 8.0), 30.0, 20.0)
+    return scenes.SceneData(meshes, cam, None, spot)
+
+
+def test_frozen_roulette_restatement():
+    """ref_prb.render_fwd_frozen is ref_path.render_fwd when the rows are the frozen ones; under a perturbed row it keeps the unperturbed paths'
+    survivors and q, so it is smooth in the row where ref_path's image differentiates q (and may jump)"""
+    sc = _corner()
+    pool, tris, shape, off, stride, nfr, alb = scenes.flatten(sc)
+    world = (pool.astype(np.float64), tris + off[shape][:, None], shape)
+    sd = scene_desc.scene_desc(sc, tex_channels=1, shadows=True)
+    rows = np.asarray(alb, np.float64)
+    spp, seed = 8, 3
+    for rr in (1, 5):
+        a = rp.render_fwd(*world, sd, rows, None, spp, seed, 4, rr)
+        b = ref_prb.render_fwd_frozen(*world, sd, rows, rows, None, spp, seed, 4, rr)
+        assert a.max() > 0 and np.array_equal(a, b)
+    # the image under rr_depth 1 is linear in one bounce's base colour on frozen paths when max_depth is 3 and that row is seen only once per path:
+    # check the weaker, always-true property — second differences of the frozen image in a Lambert row's colour over max_depth 3 are those of a
+    # polynomial of degree <= 2 (one factor per vertex), i.e. third differences vanish
+    r = rows.copy()
+    f = lambda x: float(ref_prb.render_fwd_frozen(*world, sd, np.where(np.arange(r.shape[1])[None] == 0, np.where(np.arange(r.shape[0])[:, None] == 1, x, r), r),
+                                                  rows, None, spp, seed, 3, 1).sum())  # noqa: E731
+    x0, h = float(rows[1, 0]), 0.05
+    v = [f(x0 + k * h) for k in range(-2, 3)]
+    third = v[4] - 2 * v[3] + 2 * v[1] - v[0]
+    assert abs(third) <= 1e-9 * abs(v[2]), (third, v)
+    # the undetached image is not such a polynomial here: q depends on the colour
+    g = lambda x: float(rp.render_fwd(*world, sd, np.where(np.arange(r.shape[1])[None] == 0, np.where(np.arange(r.shape[0])[:, None] == 1, x, r), r),
+                                      None, spp, seed, 3, 1).sum())  # noqa: E731
+    w = [g(x0 + k * h) for k in range(-2, 3)]
+    assert w[2] == v[2]

@@ -1,6 +1,8 @@
 """The path integrator's cost: ms per 512^2 x 64-spp vocal-fold render at max_depth 2 (the packet kernels), 3 and 4 (the per-lane
 path kernel), box and gaussian film, and ms per gradient sample (forward + loss gradient image + replay adjoint) at max_depth 3.  HIP events
-around repeated calls of one pose on one stream, after a warm-up.  Prints one JSON line.
+around repeated calls of one pose on one stream, after a warm-up.  Then the `prb` adjoint at max_depth 3 and 4:
+render_bwd_prb with and without the material block next to render_bwd (k_path_bwd) at the same depth, the three alternating in one loop, median
+of the repetitions after two warm-up rounds.  Prints one JSON line.
 
     python tools/pathbench.py [reps]
 """
@@ -46,6 +48,22 @@ def main():
             geom.render_bwd(sd, mats, 64, 1, gimg, max_depth=3)
 
         out[f"grad_sample_ms_{film}_d3"] = round(_ms(grad_sample, reps), 3)
+        for depth in (3, 4):
+            calls = {"path_bwd": lambda: geom.render_bwd(sd, mats, 64, 1, gimg, max_depth=depth),
+                     "prb_bwd": lambda: geom.render_bwd_prb(sd, mats, 64, 1, gimg, tex, depth),
+                     "prb_material_bwd": lambda: geom.render_bwd_prb(sd, mats, 64, 1, gimg, tex, depth, material=True)}
+            times = {k: [] for k in calls}
+            for rep in range(reps + 2):
+                for k, fn in calls.items():
+                    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    a.record()
+                    fn()
+                    b.record()
+                    torch.cuda.synchronize()
+                    if rep >= 2:
+                        times[k].append(a.elapsed_time(b))
+            for k, v in times.items():
+                out[f"{k}_ms_{film}_d{depth}"] = round(sorted(v)[len(v) // 2], 3)
     print(json.dumps(out))
 
 
