@@ -4166,51 +4166,68 @@ __device__ __forceinline__ void path_tex(const ShadeK &c, const SampleTerms &st,
     for (int ch = 0; ch < 3; ++ch) tv[ch] = st.wy0 * (st.wx0 * tex[o00 + ch] + st.wx1 * tex[o01 + ch]) + st.wy1 * (st.wx0 * tex[o10 + ch] + st.wx1 * tex[o11 + ch]);
   }
 }
-// the bounce at vertex pv towards wo: throughput *= pi f = (base A + B) / cos_o (Lambert rows: base)
-__device__ __forceinline__ void path_bounce_weight(const ShadeK &c, const SampleTerms &st, const PathVtx &pv, v3 d, v3 wo, float (&f)[3]) {
+// the bounce at vertex pv towards wo: throughput *= pi f = (base A + B) / cos_o (Lambert rows: base).  pb receives what the derivative of f needs
+// (prb): model (0: a Lambert row, f = base), A (the tint parts pi tau / lum included), 1 / cos_o and — TAU only — pi tau
+struct PrbBounce { int model; float A, tau, ic; };
+template <bool TAU>
+__device__ __forceinline__ void path_bounce_weight(const ShadeK &c, const SampleTerms &st, const PathVtx &pv, v3 d, v3 wo, float (&f)[3], PrbBounce &pb) {
   const float *mt = mat_table(c);
   f[0] = st.base[0]; f[1] = st.base[1]; f[2] = st.base[2];
+  pb.model = 0; pb.A = 1.f; pb.tau = 0.f; pb.ic = 1.f;
   if (c.mat_stride == FFX_MAT_STRIDE && mt[(size_t)FFX_MAT_STRIDE * st.shape + FFX_MAT_MODEL] != 0.f) {
     const float *mrow = mt + (size_t)FFX_MAT_STRIDE * st.shape;
     MatGeo mg;
     material_geometry(mrow, pv.ns, V3(-d.x, -d.y, -d.z), wo, mg);
-    float A, B;
-    if (pv.textured) material_terms<true>(mrow, mg, A, B, st.base[0], st.base[1], st.base[2]);
-    else material_terms(mrow, mg, A, B);
+    float A, B, T = 0.f;
+    if (pv.textured) material_terms<true, TAU>(mrow, mg, A, B, st.base[0], st.base[1], st.base[2], &T);
+    else material_terms<false, TAU>(mrow, mg, A, B, 0.f, 0.f, 0.f, &T);
     const float ic = mg.cos_o > 0.f ? 1.0f / mg.cos_o : 0.f;
 #pragma unroll
     for (int ch = 0; ch < 3; ++ch) f[ch] = (st.base[ch] * A + B) * ic;
+    pb.model = 1; pb.A = A; pb.tau = T; pb.ic = ic;
   }
 }
 struct PathArgs { const BvhNode *nodes; const TriRec *recs; const float4 *nrec; int spp, max_depth, rr_depth; uint32_t seed_key, path_key; };
-// one path of sample idx whose camera ray is (o, d) in (nt, ft].  At every vertex visit(st, beta) sees the emitters' terms and the throughput;
-// then the bounce (vertex v < max_depth - 1), the roulette (v >= rr_depth) and the secondary ray from the lifted point
-template <typename F>
-__device__ __forceinline__ void path_walk(const PathArgs &a, uint32_t idx, v3 o, v3 d, float nt, float ft, int *stack, F &&visit) {
+struct NoBounce {
+  template <typename... T> __device__ __forceinline__ void operator()(T &&...) const {}
+};
+// one path of sample idx whose camera ray is (o, d) in (nt, ft], every caller's by the same arithmetic in the same order.  At every vertex
+// visit(v, st, ap, mv, d, beta) sees the emitters' terms and the throughput (ap with APP, mv with MAT: shade_sample's); then the bounce (vertex
+// v < max_depth - 1), the roulette (v >= rr_depth: q and the survival test are constants of a replay) and, after a bounce that survived,
+// bounce(v, st, pv, ap, d, wo, beta, iq, f, pb) — beta is the throughput in front of the bounce, iq = 1 / q_v, pb.tau is formed with APP only —
+// and the secondary ray from the lifted point
+template <bool APP = false, bool MAT = false, typename V, typename B = NoBounce>
+__device__ __forceinline__ void path_walk(const PathArgs &a, uint32_t idx, v3 o, v3 d, float nt, float ft, int *stack, int stride, V &&visit, B &&bounce = B()) {
   const ShadeK &c = kernarg_shade();
   SampleTerms st;
   PathVtx pv;
-  shade_sample<true>(c, a.nodes, a.recs, a.nrec, o, d, nt, ft, st, stack, 64, &pv);
+  AppTerms ap;
+  MatVtx mv;
+  shade_sample<true, APP, MAT>(c, a.nodes, a.recs, a.nrec, o, d, nt, ft, st, stack, stride, &pv, &ap, &mv);
   float beta[3] = {1.f, 1.f, 1.f};
   for (int v = 1; st.hit && pv.ok; ++v) {
-    visit(st, beta);
+    visit(v, st, ap, mv, d, beta);
     if (v + 1 >= a.max_depth) break;
     const v3 wo = cosine_dir(pv.ns, path_u(a.path_key, idx, v, 0), path_u(a.path_key, idx, v, 1));
     if (!(vdot(pv.ng, wo) > 0.f)) break;
-    float f[3];
-    path_bounce_weight(c, st, pv, d, wo, f);
-    beta[0] *= f[0]; beta[1] *= f[1]; beta[2] *= f[2];
-    const float bmax = fmaxf(beta[0], fmaxf(beta[1], beta[2]));
+    float f[3], nb[3];
+    PrbBounce pb;
+    path_bounce_weight<APP>(c, st, pv, d, wo, f, pb);
+    nb[0] = beta[0] * f[0]; nb[1] = beta[1] * f[1]; nb[2] = beta[2] * f[2];
+    const float bmax = fmaxf(nb[0], fmaxf(nb[1], nb[2]));
     if (!(bmax > 0.f)) break;
+    float iq = 1.0f;
     if (v >= a.rr_depth) { // Mitsuba's roulette: survive with q = min(max beta, 0.95), then beta /= q
       const float q = fminf(bmax, 0.95f);
       if (path_u(a.path_key, idx, v, 2) >= q) break;
-      const float iq = 1.0f / q;
-      beta[0] *= iq; beta[1] *= iq; beta[2] *= iq;
+      iq = 1.0f / q;
+      nb[0] *= iq; nb[1] *= iq; nb[2] *= iq;
     }
+    bounce(v, st, pv, ap, d, wo, beta, iq, f, pb);
+    beta[0] = nb[0]; beta[1] = nb[1]; beta[2] = nb[2];
     o = pv.Po;
     d = wo;
-    shade_sample<true>(c, a.nodes, a.recs, a.nrec, o, d, 0.f, 3.0e38f, st, stack, 64, &pv);
+    shade_sample<true, APP, MAT>(c, a.nodes, a.recs, a.nrec, o, d, 0.f, 3.0e38f, st, stack, stride, &pv, &ap, &mv);
   }
 }
 __device__ __forceinline__ float wave_sum_tree(float v) { // (fixed order: the same bits on every run)
@@ -4238,7 +4255,7 @@ __global__ void __launch_bounds__(64)
       v3 o, d;
       float nt, ft;
       cam_ray(c.cam, ((float)px + jx) * c.cam.inv_w, ((float)py + jy) * c.cam.inv_h, o, d, nt, ft);
-      path_walk(a, idx, o, d, nt, ft, s_dyn + lane, [&](const SampleTerms &st, const float (&beta)[3]) {
+      path_walk(a, idx, o, d, nt, ft, s_dyn + lane, 64, [&](int, const SampleTerms &st, const AppTerms &, const MatVtx &, v3, const float (&beta)[3]) {
         const ShadeK &k = kernarg_shade();
         float r[3] = {st.spot[0], st.spot[1], st.spot[2]}, b[3] = {st.spot_b[0], st.spot_b[1], st.spot_b[2]};
         if (st.has_proj) {
@@ -4276,8 +4293,61 @@ __global__ void __launch_bounds__(64)
     }
   }
 }
+// ---- the pieces of the per-lane replay adjoints (k_path_bwd, the direct-light leaves of 4.5 / 4.5.1, prb of 4.5.2): one wave = one pixel ----
+// the adjoint of a pixel.  Box film: g = gimg[pixel] / spp; RF: gsrc is G = gimg / weight as float4 per pixel (k_rf_gather) and lanes 0..24 hold G of
+// window pixel `lane`.  false: nothing flows into this pixel's samples (wave-uniform; box: block-uniform)
+template <bool RF>
+__device__ __forceinline__ bool pixel_adjoint(const float *__restrict__ gsrc, uint32_t pix, int px, int py, int W, int H, int lane, int spp, float (&g)[3]) {
+  if (RF) {
+    const float4 gw = rf_window_g(reinterpret_cast<const float4 *>(gsrc), px, py, W, H, lane, true);
+    g[0] = gw.x; g[1] = gw.y; g[2] = gw.z;
+    return wballot(g[0] != 0.f || g[1] != 0.f || g[2] != 0.f) != 0ull;
+  }
+  const float inv_spp = 1.0f / (float)spp;
+  g[0] = gsrc[(size_t)pix * 3] * inv_spp; g[1] = gsrc[(size_t)pix * 3 + 1] * inv_spp; g[2] = gsrc[(size_t)pix * 3 + 2] * inv_spp;
+  return !(g[0] == 0.f && g[1] == 0.f && g[2] == 0.f);
+}
+// the adjoint weight of a sample with jitter (jx, jy): box: g; RF: sum over the sample's 5x5 window of filter weight x G
+template <bool RF>
+__device__ __forceinline__ void sample_adjoint(const RfC &rf, float jx, float jy, const float (&g)[3], float (&q)[3]) {
+  q[0] = g[0]; q[1] = g[1]; q[2] = g[2];
+  if (RF) { // (all lanes: the readlanes need the whole wave)
+    float gx[5], gy[5];
+    rf_weights(rf, jx, gx);
+    rf_weights(rf, jy, gy);
+    q[0] = q[1] = q[2] = 0.f;
+#pragma unroll
+    for (int n = 0; n < 25; ++n) {
+      const float w = gx[n % 5] * gy[n / 5];
+      q[0] = __builtin_fmaf(w, __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(g[0]), n)), q[0]);
+      q[1] = __builtin_fmaf(w, __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(g[1]), n)), q[1]);
+      q[2] = __builtin_fmaf(w, __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(g[2]), n)), q[2]);
+    }
+  }
+}
+// cw (d loss / d texture value per channel at a vertex) into the projector texture's gradient through the vertex's four bilinear taps: path_tex's adjoint
+__device__ __forceinline__ void proj_tex_scatter(const ShadeK &k, const SampleTerms &st, const float (&cw)[3], float *__restrict__ gtex) {
+  const int tc = k.tc;
+  const size_t o00 = ((size_t)st.iy0 * k.tw + st.ix0) * tc, o01 = ((size_t)st.iy0 * k.tw + st.ix1) * tc;
+  const size_t o10 = ((size_t)st.iy1 * k.tw + st.ix0) * tc, o11 = ((size_t)st.iy1 * k.tw + st.ix1) * tc;
+  if (tc == 1) {
+    const float ws = cw[0] * k.p_color[0] + cw[1] * k.p_color[1] + cw[2] * k.p_color[2];
+    atomicAdd(gtex + o00, ws * st.wy0 * st.wx0);
+    atomicAdd(gtex + o01, ws * st.wy0 * st.wx1);
+    atomicAdd(gtex + o10, ws * st.wy1 * st.wx0);
+    atomicAdd(gtex + o11, ws * st.wy1 * st.wx1);
+  } else {
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) {
+      atomicAdd(gtex + o00 + ch, cw[ch] * st.wy0 * st.wx0);
+      atomicAdd(gtex + o01 + ch, cw[ch] * st.wy0 * st.wx1);
+      atomicAdd(gtex + o10 + ch, cw[ch] * st.wy1 * st.wx0);
+      atomicAdd(gtex + o11 + ch, cw[ch] * st.wy1 * st.wx1);
+    }
+  }
+}
 // the adjoint: replays k_path_fwd's paths and scatters every vertex's projector term, weighted by the sample's d loss / d radiance, through its four
-// bilinear taps.  Box film: gimg[pixel] / spp; RF: sum over the sample's 5x5 window of filter weight x G (G = gimg / weight, float4 per pixel)
+// bilinear taps
 template <bool RF>
 __global__ void __launch_bounds__(64)
     k_path_bwd(ShadeK c, PathArgs a, const float *__restrict__ gsrc, float *__restrict__ gtex) {
@@ -4285,63 +4355,24 @@ __global__ void __launch_bounds__(64)
   const int lane = threadIdx.x;
   const uint32_t pix = blockIdx.x;
   const int W = c.cam.W, H = c.cam.H, px = (int)(pix % (uint32_t)W), py = (int)(pix / (uint32_t)W);
-  float g0 = 0.f, g1 = 0.f, g2 = 0.f; // box: the pixel's gradient / spp; RF: lanes 0..24 hold G of window pixel `lane`
-  if (RF) {
-    const float4 gw = rf_window_g(reinterpret_cast<const float4 *>(gsrc), px, py, W, H, lane, true);
-    g0 = gw.x; g1 = gw.y; g2 = gw.z;
-    if (wballot(g0 != 0.f || g1 != 0.f || g2 != 0.f) == 0ull) return;
-  } else {
-    const float inv_spp = 1.0f / (float)a.spp;
-    g0 = gsrc[(size_t)pix * 3] * inv_spp; g1 = gsrc[(size_t)pix * 3 + 1] * inv_spp; g2 = gsrc[(size_t)pix * 3 + 2] * inv_spp;
-    if (g0 == 0.f && g1 == 0.f && g2 == 0.f) return; // (block-uniform)
-  }
+  float g[3];
+  if (!pixel_adjoint<RF>(gsrc, pix, px, py, W, H, lane, a.spp, g)) return;
   for (int pass = 0; pass < (a.spp + 63) >> 6; ++pass) {
     const int s = pass * 64 + lane;
     const uint32_t idx = pix * (uint32_t)a.spp + (uint32_t)s;
-    float jx, jy;
+    float jx, jy, q[3];
     sample_jitter(a.seed_key, idx, jx, jy);
-    float q[3] = {g0, g1, g2};
-    if (RF) { // (all lanes: the readlanes need the whole wave)
-      float gx[5], gy[5];
-      rf_weights(c.rf, jx, gx);
-      rf_weights(c.rf, jy, gy);
-      q[0] = q[1] = q[2] = 0.f;
-#pragma unroll
-      for (int n = 0; n < 25; ++n) {
-        const float w = gx[n % 5] * gy[n / 5];
-        q[0] = __builtin_fmaf(w, __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(g0), n)), q[0]);
-        q[1] = __builtin_fmaf(w, __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(g1), n)), q[1]);
-        q[2] = __builtin_fmaf(w, __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(g2), n)), q[2]);
-      }
-    }
+    sample_adjoint<RF>(c.rf, jx, jy, g, q);
     if (s >= a.spp || (q[0] == 0.f && q[1] == 0.f && q[2] == 0.f)) continue;
     v3 o, d;
     float nt, ft;
     cam_ray(c.cam, ((float)px + jx) * c.cam.inv_w, ((float)py + jy) * c.cam.inv_h, o, d, nt, ft);
-    path_walk(a, idx, o, d, nt, ft, s_dyn + lane, [&](const SampleTerms &st, const float (&beta)[3]) {
+    path_walk(a, idx, o, d, nt, ft, s_dyn + lane, 64, [&](int, const SampleTerms &st, const AppTerms &, const MatVtx &, v3, const float (&beta)[3]) {
       if (!st.has_proj) return;
-      const ShadeK &k = kernarg_shade();
       float cw[3]; // d radiance / d (texture value) per channel, times the sample's gradient
 #pragma unroll
       for (int ch = 0; ch < 3; ++ch) cw[ch] = q[ch] * beta[ch] * (st.base[ch] * st.proj_fac + st.proj_fac_b);
-      const int tc = k.tc;
-      const size_t o00 = ((size_t)st.iy0 * k.tw + st.ix0) * tc, o01 = ((size_t)st.iy0 * k.tw + st.ix1) * tc;
-      const size_t o10 = ((size_t)st.iy1 * k.tw + st.ix0) * tc, o11 = ((size_t)st.iy1 * k.tw + st.ix1) * tc;
-      if (tc == 1) {
-        const float ws = cw[0] * k.p_color[0] + cw[1] * k.p_color[1] + cw[2] * k.p_color[2];
-        atomicAdd(gtex + o00, ws * st.wy0 * st.wx0);
-        atomicAdd(gtex + o01, ws * st.wy0 * st.wx1);
-        atomicAdd(gtex + o10, ws * st.wy1 * st.wx0);
-        atomicAdd(gtex + o11, ws * st.wy1 * st.wx1);
-      } else {
-#pragma unroll
-        for (int ch = 0; ch < 3; ++ch) {
-          atomicAdd(gtex + o00 + ch, cw[ch] * st.wy0 * st.wx0);
-          atomicAdd(gtex + o01 + ch, cw[ch] * st.wy0 * st.wx1);
-          atomicAdd(gtex + o10 + ch, cw[ch] * st.wy1 * st.wx0);
-          atomicAdd(gtex + o11 + ch, cw[ch] * st.wy1 * st.wx1);
-        }
-      }
+      proj_tex_scatter(kernarg_shade(), st, cw, gtex);
     });
   }
 }
@@ -4383,162 +4414,138 @@ __device__ __forceinline__ void base_tex_taps(const ShadeK &c, int k, int slot, 
   o[0] = ((size_t)y0 * tw + x0) * 3; o[1] = ((size_t)y0 * tw + x1) * 3; o[2] = ((size_t)y1 * tw + x0) * 3; o[3] = ((size_t)y1 * tw + x1) * 3;
   w[0] = (1.0f - ay) * (1.0f - ax); w[1] = (1.0f - ay) * ax; w[2] = ay * (1.0f - ax); w[3] = ay * ax;
 }
-// RF: gsrc is G = gimg / weight as float4 per pixel (k_rf_gather) and a sample's weight is sum_n w_n G[p + n]; else gsrc = gimg, weight gimg / spp
-template <bool RF>
-__global__ void __launch_bounds__(64 * FFX_APP_WAVES)
-    k_render_bwd_appearance(ShadeK c, AppArgs a, const float *__restrict__ gsrc) {
-  extern __shared__ int s_dyn[];
-  __shared__ float s_rows[FFX_APP_LDS_ROWS * 3];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const bool lds = a.n_shapes <= FFX_APP_LDS_ROWS;
-  if (lds)
-    for (int i = threadIdx.x; i < a.n_shapes * 3; i += 64 * FFX_APP_WAVES) s_rows[i] = 0.f;
-  __syncthreads();
-  const int W = c.cam.W, H = c.cam.H;
-  const float wl[3] = {0.212671f, 0.715160f, 0.072169f};
-  float gs[3] = {0.f, 0.f, 0.f}; // this lane's share of d loss / d spot intensity
-  for (long pl = (long)blockIdx.x * FFX_APP_WAVES + wave; pl < a.n_pix; pl += (long)gridDim.x * FFX_APP_WAVES) { // (wave-uniform)
-    const uint32_t pix = (uint32_t)pl;
-    const int px = (int)(pix % (uint32_t)W), py = (int)(pix / (uint32_t)W);
-    float g0, g1, g2; // box: the pixel's gradient / spp; RF: lanes 0..24 hold G of window pixel `lane`
-    if (RF) {
-      const float4 gw = rf_window_g(reinterpret_cast<const float4 *>(gsrc), px, py, W, H, lane, true);
-      g0 = gw.x; g1 = gw.y; g2 = gw.z;
-      if (wballot(g0 != 0.f || g1 != 0.f || g2 != 0.f) == 0ull) continue;
-    } else {
-      const float inv_spp = 1.0f / (float)a.spp;
-      g0 = gsrc[(size_t)pix * 3] * inv_spp; g1 = gsrc[(size_t)pix * 3 + 1] * inv_spp; g2 = gsrc[(size_t)pix * 3 + 2] * inv_spp;
-      if (g0 == 0.f && g1 == 0.f && g2 == 0.f) continue;
-    }
-    for (int pass = 0; pass < (a.spp + 63) >> 6; ++pass) {
-      const int s = pass * 64 + lane;
-      const uint32_t idx = pix * (uint32_t)a.spp + (uint32_t)s;
-      float jx, jy;
-      sample_jitter(a.seed_key, idx, jx, jy);
-      float q[3] = {g0, g1, g2};
-      if (RF) { // (all lanes: the readlanes need the whole wave)
-        float gx[5], gy[5];
-        rf_weights(c.rf, jx, gx);
-        rf_weights(c.rf, jy, gy);
-        q[0] = q[1] = q[2] = 0.f;
-#pragma unroll
-        for (int n = 0; n < 25; ++n) {
-          const float w = gx[n % 5] * gy[n / 5];
-          q[0] = __builtin_fmaf(w, __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(g0), n)), q[0]);
-          q[1] = __builtin_fmaf(w, __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(g1), n)), q[1]);
-          q[2] = __builtin_fmaf(w, __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(g2), n)), q[2]);
-        }
-      }
-      if (s >= a.spp || (q[0] == 0.f && q[1] == 0.f && q[2] == 0.f)) continue;
-      v3 o, d;
-      float nt, ft;
-      cam_ray(c.cam, ((float)px + jx) * c.cam.inv_w, ((float)py + jy) * c.cam.inv_h, o, d, nt, ft);
-      SampleTerms st;
-      AppTerms ap;
-      shade_sample<false, true>(kernarg_shade(), a.nodes, a.recs, a.nrec, o, d, nt, ft, st, s_dyn + threadIdx.x, 64 * FFX_APP_WAVES, nullptr, &ap);
-      if (!st.hit) continue;
-      const ShadeK &k = kernarg_shade();
-      float tv[3] = {0.f, 0.f, 0.f};
-      if (st.has_proj) path_tex(k, st, a.tex, tv);
-      float E[3], qbt = 0.f;
-#pragma unroll
-      for (int ch = 0; ch < 3; ++ch) {
-        E[ch] = st.spot[ch] + tv[ch] * st.proj_fac;
-        qbt += q[ch] * st.base[ch] * (k.s_int[ch] * ap.spot_t + tv[ch] * ap.proj_t);
-        gs[ch] += q[ch] * (st.base[ch] * ap.s_f + ap.s_fb);
-      }
-      const float lum = wl[0] * st.base[0] + wl[1] * st.base[1] + wl[2] * st.base[2];
-      const float r = lum > 0.f ? qbt / (lum * lum) : 0.f;
-      float gb[3];
-#pragma unroll
-      for (int ch = 0; ch < 3; ++ch) gb[ch] = q[ch] * E[ch] - r * wl[ch];
-      if (gb[0] == 0.f && gb[1] == 0.f && gb[2] == 0.f) continue;
-      if (ap.tix == 0) { // the row's own base colour
-        if (lds) {
-#pragma unroll
-          for (int ch = 0; ch < 3; ++ch) atomicAdd(&s_rows[st.shape * 3 + ch], gb[ch]);
-        } else {
-#pragma unroll
-          for (int ch = 0; ch < 3; ++ch) atomicAdd(a.grow + (size_t)st.shape * 3 + ch, gb[ch]);
-        }
-      } else { // a base-colour texture: through the lookup's four taps
-        float *gt = ap.tix == 1 ? a.gbt[0] : ap.tix == 2 ? a.gbt[1] : ap.tix == 3 ? a.gbt[2] : a.gbt[3];
-        size_t to[4];
-        float tw4[4];
-        base_tex_taps(k, ap.tix - 1, ap.slot, ap.bu, ap.bv, to, tw4);
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-#pragma unroll
-          for (int ch = 0; ch < 3; ++ch) atomicAdd(gt + to[t] + ch, gb[ch] * tw4[t]);
-        }
-      }
-    }
-  }
+static __constant__ constexpr float FFX_LUM_W[3] = {0.212671f, 0.715160f, 0.072169f}; // the luminance weights w of the tint terms
+__device__ __forceinline__ float base_lum(const SampleTerms &st) { return FFX_LUM_W[0] * st.base[0] + FFX_LUM_W[1] * st.base[1] + FFX_LUM_W[2] * st.base[2]; }
+// the appearance block at a vertex whose radiance carries the weight w (q at direct light, q beta in prb), tv = the projector's texture value there:
+// gs += d/d (spot intensity), gb = d/d (base colour) = w E - r w_lum
+__device__ __forceinline__ void base_colour_vjp(const ShadeK &k, const SampleTerms &st, const AppTerms &ap, const float (&tv)[3], const float (&w)[3], float (&gs)[3],
+                                                float (&gb)[3]) {
+  float E[3], qbt = 0.f;
 #pragma unroll
   for (int ch = 0; ch < 3; ++ch) {
-    const float v = wave_sum_tree(gs[ch]);
-    if (lane == 0 && v != 0.f) atomicAdd(a.gspot + ch, v);
+    E[ch] = st.spot[ch] + tv[ch] * st.proj_fac;
+    qbt += w[ch] * st.base[ch] * (k.s_int[ch] * ap.spot_t + tv[ch] * ap.proj_t);
+    gs[ch] += w[ch] * (st.base[ch] * ap.s_f + ap.s_fb);
   }
-  __syncthreads();
-  if (lds)
-    for (int i = threadIdx.x; i < a.n_shapes * 3; i += 64 * FFX_APP_WAVES) {
-      const float v = s_rows[i];
-      if (v != 0.f) atomicAdd(a.grow + i, v);
-    }
+  const float lum = base_lum(st);
+  const float r = lum > 0.f ? qbt / (lum * lum) : 0.f;
+#pragma unroll
+  for (int ch = 0; ch < 3; ++ch) gb[ch] = w[ch] * E[ch] - r * FFX_LUM_W[ch];
 }
-// FFX_RENDER_GRAD_MATERIAL (include/ffx.h): k_render_bwd_appearance's replay (the same text, the appearance block included) plus,
-// per sample and lit emitter, the BSDF's adjoint (material_terms_vjp) into gmat [n_shapes][FFX_MAT_GRAD_COLS] — row sums through LDS (s_mat) when
-// n_shapes <= FFX_MAT_LDS_ROWS, global atomics otherwise, then one global atomic per non-zero entry and workgroup.  A sibling kernel rather than a
-// template flag on k_render_bwd_appearance: sharing one body changed the appearance kernel's code.
-template <bool RF>
-__global__ void __launch_bounds__(64 * FFX_APP_WAVES)
-    k_render_bwd_material(ShadeK c, AppArgs a, const float *__restrict__ gsrc, float *__restrict__ gmat) {
-  extern __shared__ int s_dyn[];
-  __shared__ float s_rows[FFX_APP_LDS_ROWS * 3];
-  __shared__ float s_mat[FFX_MAT_LDS_ROWS * FFX_MAT_GRAD_COLS];
+// the BSDF's adjoint at a vertex lit by the two emitters (FFX_RENDER_GRAD_MATERIAL): L_c = sum_e (b_c A_e + B_e) E_ec, one reverse pass per emitter —
+// the projector's, then the spot's — with uA_e = sum_c w_c b_c E_ec, uB_e = sum_c w_c E_ec (wv: towards the viewer).  false: the row has no BSDF
+// parameters or no emitter lights the vertex, gm is not formed
+__device__ __forceinline__ bool emitters_material_vjp(const ShadeK &k, const SampleTerms &st, const MatVtx &mv, v3 wv, const float (&w)[3], const float (&tv)[3],
+                                                      float (&gm)[FFX_MAT_GRAD_COLS]) {
+  const float *mt = mat_table(k);
+  if (!(k.mat_stride == FFX_MAT_STRIDE && mt[(size_t)FFX_MAT_STRIDE * st.shape + FFX_MAT_MODEL] != 0.f && (mv.kp != 0.f || mv.ks != 0.f))) return false;
+  const float *mrow = mt + (size_t)FFX_MAT_STRIDE * st.shape;
+  const float lum = base_lum(st);
+#pragma unroll
+  for (int j = 0; j < FFX_MAT_GRAD_COLS; ++j) gm[j] = 0.f;
+  MatGeoD mg;
+  if (mv.kp != 0.f) {
+    float uA = 0.f, uB = 0.f;
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) { const float e = w[ch] * tv[ch] * mv.kp; uA += e * st.base[ch]; uB += e; }
+    material_geometry_d(mv.ns, wv, mv.wp, mg);
+    material_terms_vjp(mrow, mg, lum, uA, uB, gm);
+  }
+  if (mv.ks != 0.f) {
+    float uA = 0.f, uB = 0.f;
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) { const float e = w[ch] * k.s_int[ch] * mv.ks; uA += e * st.base[ch]; uB += e; }
+    material_geometry_d(mv.ns, wv, mv.ws, mg);
+    material_terms_vjp(mrow, mg, lum, uA, uB, gm);
+  }
+  return true;
+}
+// a workgroup's sums per material row: base colours in s_rows when n_shapes <= FFX_APP_LDS_ROWS, BSDF parameters (MAT) in s_mat when n_shapes <=
+// FFX_MAT_LDS_ROWS, global atomics otherwise; flush() leaves one global atomic per non-zero entry and workgroup.  nthr = the workgroup's threads
+template <bool MAT>
+struct RowSums {
+  const AppArgs &a;
+  float *s_rows, *s_mat, *gmat;
+  bool lds, lds_m;
+  __device__ __forceinline__ void init(int nthr) {
+    lds = a.n_shapes <= FFX_APP_LDS_ROWS;
+    if (lds)
+      for (int i = threadIdx.x; i < a.n_shapes * 3; i += nthr) s_rows[i] = 0.f;
+    lds_m = MAT && a.n_shapes <= FFX_MAT_LDS_ROWS;
+    if (lds_m)
+      for (int i = threadIdx.x; i < a.n_shapes * FFX_MAT_GRAD_COLS; i += nthr) s_mat[i] = 0.f;
+    __syncthreads();
+  }
+  // d loss / d base colour at a vertex: into the row's sum, or through a base-colour texture's four taps
+  __device__ __forceinline__ void add_base(int shape, const AppTerms &ap, const float (&gb)[3]) const {
+    if (gb[0] == 0.f && gb[1] == 0.f && gb[2] == 0.f) return;
+    if (ap.tix == 0) { // the row's own base colour
+      if (lds) {
+#pragma unroll
+        for (int ch = 0; ch < 3; ++ch) atomicAdd(&s_rows[shape * 3 + ch], gb[ch]);
+      } else {
+#pragma unroll
+        for (int ch = 0; ch < 3; ++ch) atomicAdd(a.grow + (size_t)shape * 3 + ch, gb[ch]);
+      }
+    } else { // a base-colour texture: through the lookup's four taps
+      float *gt = ap.tix == 1 ? a.gbt[0] : ap.tix == 2 ? a.gbt[1] : ap.tix == 3 ? a.gbt[2] : a.gbt[3];
+      size_t to[4];
+      float tw4[4];
+      base_tex_taps(kernarg_shade(), ap.tix - 1, ap.slot, ap.bu, ap.bv, to, tw4);
+#pragma unroll
+      for (int t = 0; t < 4; ++t) {
+#pragma unroll
+        for (int ch = 0; ch < 3; ++ch) atomicAdd(gt + to[t] + ch, gb[ch] * tw4[t]);
+      }
+    }
+  }
+  __device__ __forceinline__ void add_mat(int shape, const float (&gm)[FFX_MAT_GRAD_COLS]) const {
+    float *dst = lds_m ? s_mat + shape * FFX_MAT_GRAD_COLS : gmat + (size_t)shape * FFX_MAT_GRAD_COLS;
+#pragma unroll
+    for (int j = 0; j < FFX_MAT_GRAD_COLS; ++j)
+      if (gm[j] != 0.f) atomicAdd(dst + j, gm[j]);
+  }
+  // gs: this lane's share of d loss / d spot intensity (a wave sum, one atomic per wave)
+  __device__ __forceinline__ void flush(const float (&gs)[3], int lane, int nthr) const {
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) {
+      const float v = wave_sum_tree(gs[ch]);
+      if (lane == 0 && v != 0.f) atomicAdd(a.gspot + ch, v);
+    }
+    __syncthreads();
+    if (lds)
+      for (int i = threadIdx.x; i < a.n_shapes * 3; i += nthr) {
+        const float v = s_rows[i];
+        if (v != 0.f) atomicAdd(a.grow + i, v);
+      }
+    if (lds_m)
+      for (int i = threadIdx.x; i < a.n_shapes * FFX_MAT_GRAD_COLS; i += nthr) {
+        const float v = s_mat[i];
+        if (v != 0.f) atomicAdd(gmat + i, v);
+      }
+  }
+};
+// the direct-light leaves: per sample the appearance block and — MAT (FFX_RENDER_GRAD_MATERIAL) — per lit emitter the BSDF's adjoint
+// (material_terms_vjp) into gmat [n_shapes][FFX_MAT_GRAD_COLS].  One body for both kernels; each owns its static LDS
+template <bool RF, bool MAT>
+__device__ __forceinline__ void bwd_leaves(const ShadeK &c, const AppArgs &a, const float *__restrict__ gsrc, float *__restrict__ gmat, int *s_dyn, float *s_rows,
+                                           float *s_mat) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const bool lds = a.n_shapes <= FFX_APP_LDS_ROWS;
-  if (lds)
-    for (int i = threadIdx.x; i < a.n_shapes * 3; i += 64 * FFX_APP_WAVES) s_rows[i] = 0.f;
-  const bool lds_m = a.n_shapes <= FFX_MAT_LDS_ROWS;
-  if (lds_m)
-    for (int i = threadIdx.x; i < a.n_shapes * FFX_MAT_GRAD_COLS; i += 64 * FFX_APP_WAVES) s_mat[i] = 0.f;
-  __syncthreads();
+  RowSums<MAT> rs{a, s_rows, s_mat, gmat};
+  rs.init(64 * FFX_APP_WAVES);
   const int W = c.cam.W, H = c.cam.H;
-  const float wl[3] = {0.212671f, 0.715160f, 0.072169f};
-  float gs[3] = {0.f, 0.f, 0.f}; // this lane's share of d loss / d spot intensity
+  float gs[3] = {0.f, 0.f, 0.f};
   for (long pl = (long)blockIdx.x * FFX_APP_WAVES + wave; pl < a.n_pix; pl += (long)gridDim.x * FFX_APP_WAVES) { // (wave-uniform)
     const uint32_t pix = (uint32_t)pl;
     const int px = (int)(pix % (uint32_t)W), py = (int)(pix / (uint32_t)W);
-    float g0, g1, g2; // box: the pixel's gradient / spp; RF: lanes 0..24 hold G of window pixel `lane`
-    if (RF) {
-      const float4 gw = rf_window_g(reinterpret_cast<const float4 *>(gsrc), px, py, W, H, lane, true);
-      g0 = gw.x; g1 = gw.y; g2 = gw.z;
-      if (wballot(g0 != 0.f || g1 != 0.f || g2 != 0.f) == 0ull) continue;
-    } else {
-      const float inv_spp = 1.0f / (float)a.spp;
-      g0 = gsrc[(size_t)pix * 3] * inv_spp; g1 = gsrc[(size_t)pix * 3 + 1] * inv_spp; g2 = gsrc[(size_t)pix * 3 + 2] * inv_spp;
-      if (g0 == 0.f && g1 == 0.f && g2 == 0.f) continue;
-    }
+    float g[3];
+    if (!pixel_adjoint<RF>(gsrc, pix, px, py, W, H, lane, a.spp, g)) continue;
     for (int pass = 0; pass < (a.spp + 63) >> 6; ++pass) {
       const int s = pass * 64 + lane;
       const uint32_t idx = pix * (uint32_t)a.spp + (uint32_t)s;
-      float jx, jy;
+      float jx, jy, q[3];
       sample_jitter(a.seed_key, idx, jx, jy);
-      float q[3] = {g0, g1, g2};
-      if (RF) { // (all lanes: the readlanes need the whole wave)
-        float gx[5], gy[5];
-        rf_weights(c.rf, jx, gx);
-        rf_weights(c.rf, jy, gy);
-        q[0] = q[1] = q[2] = 0.f;
-#pragma unroll
-        for (int n = 0; n < 25; ++n) {
-          const float w = gx[n % 5] * gy[n / 5];
-          q[0] = __builtin_fmaf(w, __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(g0), n)), q[0]);
-          q[1] = __builtin_fmaf(w, __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(g1), n)), q[1]);
-          q[2] = __builtin_fmaf(w, __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(g2), n)), q[2]);
-        }
-      }
+      sample_adjoint<RF>(c.rf, jx, jy, g, q);
       if (s >= a.spp || (q[0] == 0.f && q[1] == 0.f && q[2] == 0.f)) continue;
       v3 o, d;
       float nt, ft;
@@ -4546,91 +4553,37 @@ __global__ void __launch_bounds__(64 * FFX_APP_WAVES)
       SampleTerms st;
       AppTerms ap;
       MatVtx mv;
-      shade_sample<false, true, true>(kernarg_shade(), a.nodes, a.recs, a.nrec, o, d, nt, ft, st, s_dyn + threadIdx.x, 64 * FFX_APP_WAVES, nullptr, &ap, &mv);
+      shade_sample<false, true, MAT>(kernarg_shade(), a.nodes, a.recs, a.nrec, o, d, nt, ft, st, s_dyn + threadIdx.x, 64 * FFX_APP_WAVES, nullptr, &ap, &mv);
       if (!st.hit) continue;
       const ShadeK &k = kernarg_shade();
       float tv[3] = {0.f, 0.f, 0.f};
       if (st.has_proj) path_tex(k, st, a.tex, tv);
-      { // L_c = sum_e (b_c A_e + B_e) E_ec: one reverse pass per emitter with uA_e = sum_c q_c b_c E_ec, uB_e = sum_c q_c E_ec
-        const float *mt = mat_table(k);
-        if (k.mat_stride == FFX_MAT_STRIDE && mt[(size_t)FFX_MAT_STRIDE * st.shape + FFX_MAT_MODEL] != 0.f && (mv.kp != 0.f || mv.ks != 0.f)) {
-          const float *mrow = mt + (size_t)FFX_MAT_STRIDE * st.shape;
-          const float lum = wl[0] * st.base[0] + wl[1] * st.base[1] + wl[2] * st.base[2];
-          const v3 wv = V3(-d.x, -d.y, -d.z);
-          float gm[FFX_MAT_GRAD_COLS];
-#pragma unroll
-          for (int j = 0; j < FFX_MAT_GRAD_COLS; ++j) gm[j] = 0.f;
-          MatGeoD mg;
-          if (mv.kp != 0.f) {
-            float uA = 0.f, uB = 0.f;
-#pragma unroll
-            for (int ch = 0; ch < 3; ++ch) { const float e = q[ch] * tv[ch] * mv.kp; uA += e * st.base[ch]; uB += e; }
-            material_geometry_d(mv.ns, wv, mv.wp, mg);
-            material_terms_vjp(mrow, mg, lum, uA, uB, gm);
-          }
-          if (mv.ks != 0.f) {
-            float uA = 0.f, uB = 0.f;
-#pragma unroll
-            for (int ch = 0; ch < 3; ++ch) { const float e = q[ch] * k.s_int[ch] * mv.ks; uA += e * st.base[ch]; uB += e; }
-            material_geometry_d(mv.ns, wv, mv.ws, mg);
-            material_terms_vjp(mrow, mg, lum, uA, uB, gm);
-          }
-          float *dst = lds_m ? s_mat + st.shape * FFX_MAT_GRAD_COLS : gmat + (size_t)st.shape * FFX_MAT_GRAD_COLS;
-#pragma unroll
-          for (int j = 0; j < FFX_MAT_GRAD_COLS; ++j)
-            if (gm[j] != 0.f) atomicAdd(dst + j, gm[j]);
-        }
+      if (MAT) {
+        float gm[FFX_MAT_GRAD_COLS];
+        if (emitters_material_vjp(k, st, mv, V3(-d.x, -d.y, -d.z), q, tv, gm)) rs.add_mat(st.shape, gm);
       }
-      float E[3], qbt = 0.f;
-#pragma unroll
-      for (int ch = 0; ch < 3; ++ch) {
-        E[ch] = st.spot[ch] + tv[ch] * st.proj_fac;
-        qbt += q[ch] * st.base[ch] * (k.s_int[ch] * ap.spot_t + tv[ch] * ap.proj_t);
-        gs[ch] += q[ch] * (st.base[ch] * ap.s_f + ap.s_fb);
-      }
-      const float lum = wl[0] * st.base[0] + wl[1] * st.base[1] + wl[2] * st.base[2];
-      const float r = lum > 0.f ? qbt / (lum * lum) : 0.f;
       float gb[3];
-#pragma unroll
-      for (int ch = 0; ch < 3; ++ch) gb[ch] = q[ch] * E[ch] - r * wl[ch];
-      if (gb[0] == 0.f && gb[1] == 0.f && gb[2] == 0.f) continue;
-      if (ap.tix == 0) { // the row's own base colour
-        if (lds) {
-#pragma unroll
-          for (int ch = 0; ch < 3; ++ch) atomicAdd(&s_rows[st.shape * 3 + ch], gb[ch]);
-        } else {
-#pragma unroll
-          for (int ch = 0; ch < 3; ++ch) atomicAdd(a.grow + (size_t)st.shape * 3 + ch, gb[ch]);
-        }
-      } else { // a base-colour texture: through the lookup's four taps
-        float *gt = ap.tix == 1 ? a.gbt[0] : ap.tix == 2 ? a.gbt[1] : ap.tix == 3 ? a.gbt[2] : a.gbt[3];
-        size_t to[4];
-        float tw4[4];
-        base_tex_taps(k, ap.tix - 1, ap.slot, ap.bu, ap.bv, to, tw4);
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-#pragma unroll
-          for (int ch = 0; ch < 3; ++ch) atomicAdd(gt + to[t] + ch, gb[ch] * tw4[t]);
-        }
-      }
+      base_colour_vjp(k, st, ap, tv, q, gs, gb);
+      rs.add_base(st.shape, ap, gb);
     }
   }
-#pragma unroll
-  for (int ch = 0; ch < 3; ++ch) {
-    const float v = wave_sum_tree(gs[ch]);
-    if (lane == 0 && v != 0.f) atomicAdd(a.gspot + ch, v);
-  }
-  __syncthreads();
-  if (lds)
-    for (int i = threadIdx.x; i < a.n_shapes * 3; i += 64 * FFX_APP_WAVES) {
-      const float v = s_rows[i];
-      if (v != 0.f) atomicAdd(a.grow + i, v);
-    }
-  if (lds_m)
-    for (int i = threadIdx.x; i < a.n_shapes * FFX_MAT_GRAD_COLS; i += 64 * FFX_APP_WAVES) {
-      const float v = s_mat[i];
-      if (v != 0.f) atomicAdd(gmat + i, v);
-    }
+  rs.flush(gs, lane, 64 * FFX_APP_WAVES);
+}
+// RF: gsrc is G = gimg / weight as float4 per pixel (k_rf_gather) and a sample's weight is sum_n w_n G[p + n]; else gsrc = gimg, weight gimg / spp
+template <bool RF>
+__global__ void __launch_bounds__(64 * FFX_APP_WAVES)
+    k_render_bwd_appearance(ShadeK c, AppArgs a, const float *__restrict__ gsrc) {
+  extern __shared__ int s_dyn[];
+  __shared__ float s_rows[FFX_APP_LDS_ROWS * 3];
+  bwd_leaves<RF, false>(c, a, gsrc, nullptr, s_dyn, s_rows, nullptr);
+}
+template <bool RF>
+__global__ void __launch_bounds__(64 * FFX_APP_WAVES)
+    k_render_bwd_material(ShadeK c, AppArgs a, const float *__restrict__ gsrc, float *__restrict__ gmat) {
+  extern __shared__ int s_dyn[];
+  __shared__ float s_rows[FFX_APP_LDS_ROWS * 3];
+  __shared__ float s_mat[FFX_MAT_LDS_ROWS * FFX_MAT_GRAD_COLS];
+  bwd_leaves<RF, true>(c, a, gsrc, gmat, s_dyn, s_rows, s_mat);
 }
 
 // ------------------------------------------------------------------------------------------ prb: the appearance and BSDF adjoints through bounces
@@ -4643,63 +4596,6 @@ __global__ void __launch_bounds__(64 * FFX_APP_WAVES)
 // what k_render_bwd_appearance / k_render_bwd_material form per sample (weight q beta_v) and what k_path_bwd scatters into gtex, at every bounce the
 // derivative of f_v.  Workgroups of 1, 2 or 4 waves (the host picks what fits 64 KB of LDS) stride over the film.
 struct PrbArgs { int max_depth, rr_depth; uint32_t path_key; float *gtex, *gmat; };
-// the bounce weight of path_bounce_weight with what its derivative needs: model (0: a Lambert row, f = base), A (the tint parts pi tau / lum included),
-// pi tau and 1 / cos_o
-struct PrbBounce { int model; float A, tau, ic; };
-__device__ __forceinline__ void prb_bounce_weight(const ShadeK &c, const SampleTerms &st, const PathVtx &pv, v3 d, v3 wo, float (&f)[3], PrbBounce &pb) {
-  const float *mt = mat_table(c);
-  f[0] = st.base[0]; f[1] = st.base[1]; f[2] = st.base[2];
-  pb.model = 0; pb.A = 1.f; pb.tau = 0.f; pb.ic = 1.f;
-  if (c.mat_stride == FFX_MAT_STRIDE && mt[(size_t)FFX_MAT_STRIDE * st.shape + FFX_MAT_MODEL] != 0.f) {
-    const float *mrow = mt + (size_t)FFX_MAT_STRIDE * st.shape;
-    MatGeo mg;
-    material_geometry(mrow, pv.ns, V3(-d.x, -d.y, -d.z), wo, mg);
-    float A, B, T;
-    if (pv.textured) material_terms<true, true>(mrow, mg, A, B, st.base[0], st.base[1], st.base[2], &T);
-    else material_terms<false, true>(mrow, mg, A, B, 0.f, 0.f, 0.f, &T);
-    const float ic = mg.cos_o > 0.f ? 1.0f / mg.cos_o : 0.f;
-#pragma unroll
-    for (int ch = 0; ch < 3; ++ch) f[ch] = (st.base[ch] * A + B) * ic;
-    pb.model = 1; pb.A = A; pb.tau = T; pb.ic = ic;
-  }
-}
-// path_walk (the same paths: the same arithmetic in the same order) with two callbacks: visit(v, st, ap, mv, d, beta) at every vertex, bounce(v, st,
-// pv, ap, d, wo, beta, iq, f, pb) after a bounce that survived — beta is the throughput in front of the bounce, iq = 1 / q_v
-template <bool APP, bool MAT, typename V, typename B>
-__device__ __forceinline__ void path_walk_prb(const AppArgs &a, const PrbArgs &p, uint32_t idx, v3 o, v3 d, float nt, float ft, int *stack, int stride, V &&visit,
-                                              B &&bounce) {
-  const ShadeK &c = kernarg_shade();
-  SampleTerms st;
-  PathVtx pv;
-  AppTerms ap;
-  MatVtx mv;
-  shade_sample<true, APP, MAT>(c, a.nodes, a.recs, a.nrec, o, d, nt, ft, st, stack, stride, &pv, &ap, &mv);
-  float beta[3] = {1.f, 1.f, 1.f};
-  for (int v = 1; st.hit && pv.ok; ++v) {
-    visit(v, st, ap, mv, d, beta);
-    if (v + 1 >= p.max_depth) break;
-    const v3 wo = cosine_dir(pv.ns, path_u(p.path_key, idx, v, 0), path_u(p.path_key, idx, v, 1));
-    if (!(vdot(pv.ng, wo) > 0.f)) break;
-    float f[3], nb[3];
-    PrbBounce pb;
-    prb_bounce_weight(c, st, pv, d, wo, f, pb);
-    nb[0] = beta[0] * f[0]; nb[1] = beta[1] * f[1]; nb[2] = beta[2] * f[2];
-    const float bmax = fmaxf(nb[0], fmaxf(nb[1], nb[2]));
-    if (!(bmax > 0.f)) break;
-    float iq = 1.0f;
-    if (v >= p.rr_depth) { // (detached: q and the survival test are constants of the replay)
-      const float q = fminf(bmax, 0.95f);
-      if (path_u(p.path_key, idx, v, 2) >= q) break;
-      iq = 1.0f / q;
-      nb[0] *= iq; nb[1] *= iq; nb[2] *= iq;
-    }
-    bounce(v, st, pv, ap, d, wo, beta, iq, f, pb);
-    beta[0] = nb[0]; beta[1] = nb[1]; beta[2] = nb[2];
-    o = pv.Po;
-    d = wo;
-    shade_sample<true, APP, MAT>(c, a.nodes, a.recs, a.nrec, o, d, 0.f, 3.0e38f, st, stack, stride, &pv, &ap, &mv);
-  }
-}
 // s_dyn: the traversal stack [stack_ints / threads][threads] followed by the path records [max_depth - 1][6][threads]
 template <bool RF, bool MAT>
 __device__ __forceinline__ void path_bwd_prb(const ShadeK &c, const AppArgs &a, const PrbArgs &p, const float *__restrict__ gsrc, int *s_dyn, int stack_ints,
@@ -4708,81 +4604,30 @@ __device__ __forceinline__ void path_bwd_prb(const ShadeK &c, const AppArgs &a, 
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   float *s_path = reinterpret_cast<float *>(s_dyn + stack_ints) + threadIdx.x;
   const int pstride = 6 * nthr; // floats per vertex
-  const bool lds = a.n_shapes <= FFX_APP_LDS_ROWS;
-  if (lds)
-    for (int i = threadIdx.x; i < a.n_shapes * 3; i += nthr) s_rows[i] = 0.f;
-  const bool lds_m = MAT && a.n_shapes <= FFX_MAT_LDS_ROWS;
-  if (lds_m)
-    for (int i = threadIdx.x; i < a.n_shapes * FFX_MAT_GRAD_COLS; i += nthr) s_mat[i] = 0.f;
-  __syncthreads();
+  const PathArgs pa = {a.nodes, a.recs, a.nrec, a.spp, p.max_depth, p.rr_depth, a.seed_key, p.path_key};
+  RowSums<MAT> rs{a, s_rows, s_mat, p.gmat};
+  rs.init(nthr);
   const int W = c.cam.W, H = c.cam.H;
-  const float wl[3] = {0.212671f, 0.715160f, 0.072169f};
-  float gs[3] = {0.f, 0.f, 0.f}; // this lane's share of d loss / d spot intensity
-  // d loss / d base colour at a vertex: into the row's sum, or through a base-colour texture's four taps
-  auto emit_base = [&](int shape, const AppTerms &ap, const float (&gb)[3]) {
-    if (gb[0] == 0.f && gb[1] == 0.f && gb[2] == 0.f) return;
-    if (ap.tix == 0) {
-      float *dst = lds ? s_rows + shape * 3 : a.grow + (size_t)shape * 3;
-#pragma unroll
-      for (int ch = 0; ch < 3; ++ch) atomicAdd(dst + ch, gb[ch]);
-    } else {
-      float *gt = ap.tix == 1 ? a.gbt[0] : ap.tix == 2 ? a.gbt[1] : ap.tix == 3 ? a.gbt[2] : a.gbt[3];
-      size_t to[4];
-      float tw4[4];
-      base_tex_taps(kernarg_shade(), ap.tix - 1, ap.slot, ap.bu, ap.bv, to, tw4);
-#pragma unroll
-      for (int t = 0; t < 4; ++t) {
-#pragma unroll
-        for (int ch = 0; ch < 3; ++ch) atomicAdd(gt + to[t] + ch, gb[ch] * tw4[t]);
-      }
-    }
-  };
-  auto emit_mat = [&](int shape, const float (&gm)[FFX_MAT_GRAD_COLS]) {
-    float *dst = lds_m ? s_mat + shape * FFX_MAT_GRAD_COLS : p.gmat + (size_t)shape * FFX_MAT_GRAD_COLS;
-#pragma unroll
-    for (int j = 0; j < FFX_MAT_GRAD_COLS; ++j)
-      if (gm[j] != 0.f) atomicAdd(dst + j, gm[j]);
-  };
+  float gs[3] = {0.f, 0.f, 0.f};
   for (long pl = (long)blockIdx.x * waves + wave; pl < a.n_pix; pl += (long)gridDim.x * waves) { // (wave-uniform)
     const uint32_t pix = (uint32_t)pl;
     const int px = (int)(pix % (uint32_t)W), py = (int)(pix / (uint32_t)W);
-    float g0, g1, g2; // box: the pixel's gradient / spp; RF: lanes 0..24 hold G of window pixel `lane`
-    if (RF) {
-      const float4 gw = rf_window_g(reinterpret_cast<const float4 *>(gsrc), px, py, W, H, lane, true);
-      g0 = gw.x; g1 = gw.y; g2 = gw.z;
-      if (wballot(g0 != 0.f || g1 != 0.f || g2 != 0.f) == 0ull) continue;
-    } else {
-      const float inv_spp = 1.0f / (float)a.spp;
-      g0 = gsrc[(size_t)pix * 3] * inv_spp; g1 = gsrc[(size_t)pix * 3 + 1] * inv_spp; g2 = gsrc[(size_t)pix * 3 + 2] * inv_spp;
-      if (g0 == 0.f && g1 == 0.f && g2 == 0.f) continue;
-    }
+    float g[3];
+    if (!pixel_adjoint<RF>(gsrc, pix, px, py, W, H, lane, a.spp, g)) continue;
     for (int pass = 0; pass < (a.spp + 63) >> 6; ++pass) {
       const int s = pass * 64 + lane;
       const uint32_t idx = pix * (uint32_t)a.spp + (uint32_t)s;
-      float jx, jy;
+      float jx, jy, q[3];
       sample_jitter(a.seed_key, idx, jx, jy);
-      float q[3] = {g0, g1, g2};
-      if (RF) { // (all lanes: the readlanes need the whole wave)
-        float gx[5], gy[5];
-        rf_weights(c.rf, jx, gx);
-        rf_weights(c.rf, jy, gy);
-        q[0] = q[1] = q[2] = 0.f;
-#pragma unroll
-        for (int n = 0; n < 25; ++n) {
-          const float w = gx[n % 5] * gy[n / 5];
-          q[0] = __builtin_fmaf(w, __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(g0), n)), q[0]);
-          q[1] = __builtin_fmaf(w, __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(g1), n)), q[1]);
-          q[2] = __builtin_fmaf(w, __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(g2), n)), q[2]);
-        }
-      }
+      sample_adjoint<RF>(c.rf, jx, jy, g, q);
       if (s >= a.spp || (q[0] == 0.f && q[1] == 0.f && q[2] == 0.f)) continue;
       v3 o, d;
       float nt, ft;
       cam_ray(c.cam, ((float)px + jx) * c.cam.inv_w, ((float)py + jy) * c.cam.inv_h, o, d, nt, ft);
       // first walk: N_v into floats 0..2 of vertex v's record, f_v / q_v into 3..5
       int n = 0;
-      path_walk_prb<false, false>(
-          a, p, idx, o, d, nt, ft, s_dyn + threadIdx.x, nthr,
+      path_walk(
+          pa, idx, o, d, nt, ft, s_dyn + threadIdx.x, nthr,
           [&](int v, const SampleTerms &st, const AppTerms &, const MatVtx &, v3, const float (&)[3]) {
             float tv[3] = {0.f, 0.f, 0.f};
             if (st.has_proj) path_tex(kernarg_shade(), st, a.tex, tv);
@@ -4809,8 +4654,8 @@ __device__ __forceinline__ void path_bwd_prb(const ShadeK &c, const AppArgs &a, 
         }
       }
       // second walk: the derivatives
-      path_walk_prb<true, MAT>(
-          a, p, idx, o, d, nt, ft, s_dyn + threadIdx.x, nthr,
+      path_walk<true, MAT>(
+          pa, idx, o, d, nt, ft, s_dyn + threadIdx.x, nthr,
           [&](int, const SampleTerms &st, const AppTerms &ap, const MatVtx &mv, v3 dv, const float (&beta)[3]) {
             const ShadeK &k = kernarg_shade();
             const float w[3] = {q[0] * beta[0], q[1] * beta[1], q[2] * beta[2]};
@@ -4820,62 +4665,15 @@ __device__ __forceinline__ void path_bwd_prb(const ShadeK &c, const AppArgs &a, 
               float cw[3]; // d radiance / d (texture value) per channel, times the sample's gradient: k_path_bwd's sum
 #pragma unroll
               for (int ch = 0; ch < 3; ++ch) cw[ch] = w[ch] * (st.base[ch] * st.proj_fac + st.proj_fac_b);
-              const int tc = k.tc;
-              const size_t o00 = ((size_t)st.iy0 * k.tw + st.ix0) * tc, o01 = ((size_t)st.iy0 * k.tw + st.ix1) * tc;
-              const size_t o10 = ((size_t)st.iy1 * k.tw + st.ix0) * tc, o11 = ((size_t)st.iy1 * k.tw + st.ix1) * tc;
-              if (tc == 1) {
-                const float ws = cw[0] * k.p_color[0] + cw[1] * k.p_color[1] + cw[2] * k.p_color[2];
-                atomicAdd(p.gtex + o00, ws * st.wy0 * st.wx0);
-                atomicAdd(p.gtex + o01, ws * st.wy0 * st.wx1);
-                atomicAdd(p.gtex + o10, ws * st.wy1 * st.wx0);
-                atomicAdd(p.gtex + o11, ws * st.wy1 * st.wx1);
-              } else {
-#pragma unroll
-                for (int ch = 0; ch < 3; ++ch) {
-                  atomicAdd(p.gtex + o00 + ch, cw[ch] * st.wy0 * st.wx0);
-                  atomicAdd(p.gtex + o01 + ch, cw[ch] * st.wy0 * st.wx1);
-                  atomicAdd(p.gtex + o10 + ch, cw[ch] * st.wy1 * st.wx0);
-                  atomicAdd(p.gtex + o11 + ch, cw[ch] * st.wy1 * st.wx1);
-                }
-              }
+              proj_tex_scatter(k, st, cw, p.gtex);
             }
-            const float lum = wl[0] * st.base[0] + wl[1] * st.base[1] + wl[2] * st.base[2];
-            if (MAT) { // N_c = sum_e (b_c A_e + B_e) E_ec: one reverse pass per emitter, as k_render_bwd_material with the weight q beta
-              const float *mt = mat_table(k);
-              if (k.mat_stride == FFX_MAT_STRIDE && mt[(size_t)FFX_MAT_STRIDE * st.shape + FFX_MAT_MODEL] != 0.f && (mv.kp != 0.f || mv.ks != 0.f)) {
-                const float *mrow = mt + (size_t)FFX_MAT_STRIDE * st.shape;
-                const v3 wv = V3(-dv.x, -dv.y, -dv.z);
-                float gm[FFX_MAT_GRAD_COLS];
-#pragma unroll
-                for (int j = 0; j < FFX_MAT_GRAD_COLS; ++j) gm[j] = 0.f;
-                MatGeoD mg;
-                if (mv.kp != 0.f) {
-                  float uA = 0.f, uB = 0.f;
-#pragma unroll
-                  for (int ch = 0; ch < 3; ++ch) { const float e = w[ch] * tv[ch] * mv.kp; uA += e * st.base[ch]; uB += e; }
-                  material_geometry_d(mv.ns, wv, mv.wp, mg);
-                  material_terms_vjp(mrow, mg, lum, uA, uB, gm);
-                }
-                if (mv.ks != 0.f) {
-                  float uA = 0.f, uB = 0.f;
-#pragma unroll
-                  for (int ch = 0; ch < 3; ++ch) { const float e = w[ch] * k.s_int[ch] * mv.ks; uA += e * st.base[ch]; uB += e; }
-                  material_geometry_d(mv.ns, wv, mv.ws, mg);
-                  material_terms_vjp(mrow, mg, lum, uA, uB, gm);
-                }
-                emit_mat(st.shape, gm);
-              }
+            if (MAT) { // N_c = sum_e (b_c A_e + B_e) E_ec: the direct-light leaves' reverse passes with the weight q beta
+              float gm[FFX_MAT_GRAD_COLS];
+              if (emitters_material_vjp(k, st, mv, V3(-dv.x, -dv.y, -dv.z), w, tv, gm)) rs.add_mat(st.shape, gm);
             }
-            float qbt = 0.f, gb[3];
-#pragma unroll
-            for (int ch = 0; ch < 3; ++ch) {
-              qbt += w[ch] * st.base[ch] * (k.s_int[ch] * ap.spot_t + tv[ch] * ap.proj_t);
-              gs[ch] += w[ch] * (st.base[ch] * ap.s_f + ap.s_fb);
-            }
-            const float r = lum > 0.f ? qbt / (lum * lum) : 0.f;
-#pragma unroll
-            for (int ch = 0; ch < 3; ++ch) gb[ch] = w[ch] * (st.spot[ch] + tv[ch] * st.proj_fac) - r * wl[ch];
-            emit_base(st.shape, ap, gb);
+            float gb[3];
+            base_colour_vjp(k, st, ap, tv, w, gs, gb);
+            rs.add_base(st.shape, ap, gb);
           },
           [&](int v, const SampleTerms &st, const PathVtx &pv, const AppTerms &ap, v3 dv, v3 wo, const float (&beta)[3], float iq, const float (&)[3],
               const PrbBounce &pb) {
@@ -4890,10 +4688,10 @@ __device__ __forceinline__ void path_bwd_prb(const ShadeK &c, const AppArgs &a, 
             if (h[0] == 0.f && h[1] == 0.f && h[2] == 0.f) return;
             float gb[3] = {h[0], h[1], h[2]}; // Lambert rows: f = b
             if (pb.model) { // f_c = (b_c A + B) / cos_o, A = A0 + pi tau / lum(b)
-              const float lum = wl[0] * st.base[0] + wl[1] * st.base[1] + wl[2] * st.base[2];
+              const float lum = base_lum(st);
               const float r = lum > 0.f ? hb * pb.tau / (lum * lum) : 0.f;
 #pragma unroll
-              for (int ch = 0; ch < 3; ++ch) gb[ch] = (h[ch] * pb.A - r * wl[ch]) * pb.ic;
+              for (int ch = 0; ch < 3; ++ch) gb[ch] = (h[ch] * pb.A - r * FFX_LUM_W[ch]) * pb.ic;
               if (MAT) {
                 const float *mrow = mat_table(kernarg_shade()) + (size_t)FFX_MAT_STRIDE * st.shape;
                 float gm[FFX_MAT_GRAD_COLS];
@@ -4902,29 +4700,14 @@ __device__ __forceinline__ void path_bwd_prb(const ShadeK &c, const AppArgs &a, 
                 MatGeoD mg;
                 material_geometry_d(pv.ns, V3(-dv.x, -dv.y, -dv.z), wo, mg);
                 material_terms_vjp(mrow, mg, lum, hb * pb.ic, (h[0] + h[1] + h[2]) * pb.ic, gm);
-                emit_mat(st.shape, gm);
+                rs.add_mat(st.shape, gm);
               }
             }
-            emit_base(st.shape, ap, gb);
+            rs.add_base(st.shape, ap, gb);
           });
     }
   }
-#pragma unroll
-  for (int ch = 0; ch < 3; ++ch) {
-    const float v = wave_sum_tree(gs[ch]);
-    if (lane == 0 && v != 0.f) atomicAdd(a.gspot + ch, v);
-  }
-  __syncthreads();
-  if (lds)
-    for (int i = threadIdx.x; i < a.n_shapes * 3; i += nthr) {
-      const float v = s_rows[i];
-      if (v != 0.f) atomicAdd(a.grow + i, v);
-    }
-  if (lds_m)
-    for (int i = threadIdx.x; i < a.n_shapes * FFX_MAT_GRAD_COLS; i += nthr) {
-      const float v = s_mat[i];
-      if (v != 0.f) atomicAdd(p.gmat + i, v);
-    }
+  rs.flush(gs, lane, nthr);
 }
 template <bool RF>
 __global__ void __launch_bounds__(64 * FFX_APP_WAVES)
@@ -5491,6 +5274,15 @@ template <class F> static void dispatch_wm(bool wide, int matm, F &&f) {
   if (wide) by_matm(std::true_type());
   else by_matm(std::false_type());
 }
+// (filtered film, material block) as template arguments, for the per-lane appearance kernels: f(std::bool_constant<RF>, std::bool_constant<MAT>)
+template <class F> static void dispatch_rf_mat(bool rf, bool mat, F &&f) {
+  auto by_mat = [&](auto r) {
+    if (mat) f(r, std::true_type());
+    else f(r, std::false_type());
+  };
+  if (rf) by_mat(std::true_type());
+  else by_mat(std::false_type());
+}
 // a k_render_fwd_pk launch's own arguments (the kernel's parameters: fp16, img, cache, cache_foot_off / cache_arena_off / cache_foot_b_off, ...)
 struct FwdPkArgs { int fp16; void *img; char *cache; uint32_t off[3], cap_stray; const float *adj_gimg; float *adj_gtex, *adj_dot; };
 // ADJ: k_render_fwd_pk's ADJ (0 / 1), or 2 for the box film's route, which takes the fused adjoint iff a.adj_gtex
@@ -5934,24 +5726,17 @@ static int render_bwd_impl(const void *bvh, const ffx_bvh_info *info, const ffx_
   return FFX_OK;
 }
 
-// FFX_RENDER_GRAD_APPEARANCE (include/ffx.h, DESIGN.md 4.5): after the texture part — the launches of a call without the bit, which leave G = gimg / weight
-// in the filtered film's scratch when the scene has a projector — one launch of k_render_bwd_appearance into the block behind gtex
-static int render_bwd_appearance(const void *bvh, const ffx_bvh_info *info, const ffx_scene_desc *sd, const float *shape_albedo, int spp, uint32_t seed, int flags,
-                                 const float *gimg, float *gtex, ffx_stream s, void *rf_scratch) {
-  if (!bvh || !info || !sd || (!shape_albedo && sd->n_mat_h <= 0) || !gimg || !gtex || spp < 1) FFX_FAIL(FFX_ERR_ARG, "render_bwd: bad argument");
-  if (flags & FFX_RENDER_PATH_MASK) FFX_FAIL(FFX_ERR_UNSUPPORTED, "render_bwd: FFX_RENDER_GRAD_APPEARANCE is served at max_depth 2 only");
-  if (const int rc = render_bwd_impl(bvh, info, sd, shape_albedo, spp, seed, flags & ~(FFX_RENDER_GRAD_APPEARANCE | FFX_RENDER_GRAD_MATERIAL), gimg, gtex, s, rf_scratch))
-    return rc;
-  RenderSetup r;
+// what both appearance routes set up after their own refusals: render_setup, the n_shapes / texture-size checks and the kernels' AppArgs over the layout
+// of gimg (the forward's texture behind the image gradient) and gtex (the appearance block behind the texture's n_tex floats)
+static int app_args(const void *bvh, const ffx_bvh_info *info, const ffx_scene_desc *sd, const float *shape_albedo, int spp, uint32_t seed, int flags,
+                    const float *gimg, float *gtex, void *rf_scratch, RenderSetup &r, AppArgs &a, long &n_tex) {
   if (const int rc = render_setup("render_bwd", bvh, info, sd, shape_albedo, spp, seed, flags, rf_scratch, r)) return rc;
   if (sd->n_shapes < 1) FFX_FAIL(FFX_ERR_ARG, "render_bwd: n_shapes < 1");
-  const long n_tex = (long)sd->proj.tex_w * sd->proj.tex_h * sd->proj.tex_channels;
+  n_tex = (long)sd->proj.tex_w * sd->proj.tex_h * sd->proj.tex_channels;
   if (n_tex < 0) FFX_FAIL(FFX_ERR_ARG, "render_bwd: bad projector texture size");
-  const hipStream_t st = (hipStream_t)s;
-  AppArgs a;
   memset(&a, 0, sizeof a);
   a.nodes = r.b.nodes; a.recs = r.b.recs; a.nrec = r.b.nrec;
-  a.tex = sd->proj.enabled ? gimg + (size_t)r.n_pix * 3 : nullptr; // (the input half of the layout: the forward's texture behind gimg)
+  a.tex = sd->proj.enabled ? gimg + (size_t)r.n_pix * 3 : nullptr;
   a.spp = spp; a.n_pix = (int)r.n_pix; a.n_shapes = sd->n_shapes; a.seed_key = r.seed_key;
   a.grow = gtex + n_tex; a.gspot = a.grow + (size_t)3 * sd->n_shapes;
   float *bt = a.gspot + 3;
@@ -5959,6 +5744,21 @@ static int render_bwd_appearance(const void *bvh, const ffx_bvh_info *info, cons
     a.gbt[k] = bt;
     bt += (size_t)3 * r.c.btw[k] * r.c.bth[k];
   }
+  return FFX_OK;
+}
+// FFX_RENDER_GRAD_APPEARANCE (include/ffx.h, DESIGN.md 4.5): after the texture part — the launches of a call without the bit, which leave G = gimg / weight
+// in the filtered film's scratch when the scene has a projector — one launch of k_render_bwd_appearance (with FFX_RENDER_GRAD_MATERIAL:
+// k_render_bwd_material, FFX_RENDER_MATERIAL_FLOATS(sd) more floats) into the block behind gtex
+static int render_bwd_appearance(const void *bvh, const ffx_bvh_info *info, const ffx_scene_desc *sd, const float *shape_albedo, int spp, uint32_t seed, int flags,
+                                 const float *gimg, float *gtex, ffx_stream s, void *rf_scratch) {
+  if (flags & FFX_RENDER_PATH_MASK) FFX_FAIL(FFX_ERR_UNSUPPORTED, "render_bwd: FFX_RENDER_GRAD_APPEARANCE is served at max_depth 2 only");
+  if (const int rc = render_bwd_impl(bvh, info, sd, shape_albedo, spp, seed, flags & ~(FFX_RENDER_GRAD_APPEARANCE | FFX_RENDER_GRAD_MATERIAL), gimg, gtex, s, rf_scratch))
+    return rc;
+  RenderSetup r;
+  AppArgs a;
+  long n_tex;
+  if (const int rc = app_args(bvh, info, sd, shape_albedo, spp, seed, flags, gimg, gtex, rf_scratch, r, a, n_tex)) return rc;
+  const hipStream_t st = (hipStream_t)s;
   const float *gsrc = gimg;
   if (rf_scratch) { // G = gimg / weight: the texture part left it in the scratch, or (no projector) launched nothing and it is formed here
     gsrc = (const float *)(sd->proj.enabled ? rf_G_area(rf_scratch, r.n_pix)
@@ -5967,16 +5767,15 @@ static int render_bwd_appearance(const void *bvh, const ffx_bvh_info *info, cons
   }
   const long blocks = ffx_cdiv(r.n_pix, (long)FFX_APP_WAVES);
   const unsigned grid = (unsigned)(blocks < 2048 ? blocks : 2048); // (every workgroup strides over the film: 2048 x 4 waves fill the device)
-  if (flags & FFX_RENDER_GRAD_MATERIAL) { // (FFX_RENDER_MATERIAL_FLOATS(sd) floats behind the appearance block)
-    float *gmat = gtex + n_tex + FFX_RENDER_APPEARANCE_FLOATS(sd);
-    if (rf_scratch) hipLaunchKernelGGL(k_render_bwd_material<true>, dim3(grid), dim3(64 * FFX_APP_WAVES), stack_bytes(info), st, r.c, a, gsrc, gmat);
-    else hipLaunchKernelGGL(k_render_bwd_material<false>, dim3(grid), dim3(64 * FFX_APP_WAVES), stack_bytes(info), st, r.c, a, gsrc, gmat);
-    FFX_CHECK_LAUNCH(rf_scratch ? "render_bwd_filtered (material)" : "render_bwd (material)");
-    return FFX_OK;
-  }
-  if (rf_scratch) hipLaunchKernelGGL(k_render_bwd_appearance<true>, dim3(grid), dim3(64 * FFX_APP_WAVES), stack_bytes(info), st, r.c, a, gsrc);
-  else hipLaunchKernelGGL(k_render_bwd_appearance<false>, dim3(grid), dim3(64 * FFX_APP_WAVES), stack_bytes(info), st, r.c, a, gsrc);
-  FFX_CHECK_LAUNCH(rf_scratch ? "render_bwd_filtered (appearance)" : "render_bwd (appearance)");
+  const bool material = (flags & FFX_RENDER_GRAD_MATERIAL) != 0;
+  float *gmat = gtex + n_tex + FFX_RENDER_APPEARANCE_FLOATS(sd);
+  dispatch_rf_mat(rf_scratch != nullptr, material, [&](auto rf, auto m) {
+    constexpr bool RF = decltype(rf)::value;
+    if constexpr (decltype(m)::value) hipLaunchKernelGGL(k_render_bwd_material<RF>, dim3(grid), dim3(64 * FFX_APP_WAVES), stack_bytes(info), st, r.c, a, gsrc, gmat);
+    else hipLaunchKernelGGL(k_render_bwd_appearance<RF>, dim3(grid), dim3(64 * FFX_APP_WAVES), stack_bytes(info), st, r.c, a, gsrc);
+  });
+  FFX_CHECK_LAUNCH(material ? (rf_scratch ? "render_bwd_filtered (material)" : "render_bwd (material)")
+                            : (rf_scratch ? "render_bwd_filtered (appearance)" : "render_bwd (appearance)"));
   return FFX_OK;
 }
 // FFX_RENDER_GRAD_PRB (include/ffx.h): the appearance (and material) blocks at max_depth > 2 — ONE launch of k_path_bwd_prb[_material],
@@ -5984,25 +5783,12 @@ static int render_bwd_appearance(const void *bvh, const ffx_bvh_info *info, cons
 #define FFX_PRB_STATIC_LDS ((FFX_APP_LDS_ROWS * 3 + FFX_MAT_LDS_ROWS * FFX_MAT_GRAD_COLS) * sizeof(float))
 static int render_bwd_prb(const void *bvh, const ffx_bvh_info *info, const ffx_scene_desc *sd, const float *shape_albedo, int spp, uint32_t seed, int flags,
                           const float *gimg, float *gtex, ffx_stream s, void *rf_scratch) {
-  if (!bvh || !info || !sd || (!shape_albedo && sd->n_mat_h <= 0) || !gimg || !gtex || spp < 1) FFX_FAIL(FFX_ERR_ARG, "render_bwd: bad argument");
   RenderSetup r;
-  if (const int rc = render_setup("render_bwd", bvh, info, sd, shape_albedo, spp, seed, flags, rf_scratch, r)) return rc;
-  if (sd->n_shapes < 1) FFX_FAIL(FFX_ERR_ARG, "render_bwd: n_shapes < 1");
-  const long n_tex = (long)sd->proj.tex_w * sd->proj.tex_h * sd->proj.tex_channels;
-  if (n_tex < 0) FFX_FAIL(FFX_ERR_ARG, "render_bwd: bad projector texture size");
+  AppArgs a;
+  long n_tex;
+  if (const int rc = app_args(bvh, info, sd, shape_albedo, spp, seed, flags, gimg, gtex, rf_scratch, r, a, n_tex)) return rc;
   if (r.n_pix >= (1L << 31)) FFX_FAIL(FFX_ERR_UNSUPPORTED, "render_bwd: more than 2^31 pixels");
   const hipStream_t st = (hipStream_t)s;
-  AppArgs a;
-  memset(&a, 0, sizeof a);
-  a.nodes = r.b.nodes; a.recs = r.b.recs; a.nrec = r.b.nrec;
-  a.tex = sd->proj.enabled ? gimg + (size_t)r.n_pix * 3 : nullptr; // (the forward's texture behind gimg, as for the direct-light blocks)
-  a.spp = spp; a.n_pix = (int)r.n_pix; a.n_shapes = sd->n_shapes; a.seed_key = r.seed_key;
-  a.grow = gtex + n_tex; a.gspot = a.grow + (size_t)3 * sd->n_shapes;
-  float *bt = a.gspot + 3;
-  for (int k = 0; k < r.c.n_base_tex; ++k) {
-    a.gbt[k] = bt;
-    bt += (size_t)3 * r.c.btw[k] * r.c.bth[k];
-  }
   const bool material = (flags & FFX_RENDER_GRAD_MATERIAL) != 0;
   PrbArgs p;
   p.max_depth = r.max_depth; p.rr_depth = r.rr_depth; p.path_key = path_args(r).path_key;
@@ -6021,15 +5807,13 @@ static int render_bwd_prb(const void *bvh, const ffx_bvh_info *info, const ffx_s
   const int stack_ints = depth * 64 * waves;
   const long blocks = ffx_cdiv(r.n_pix, (long)waves), cap = 8192 / waves; // (every workgroup strides over the film, as k_render_bwd_appearance's)
   const unsigned grid = (unsigned)(blocks < cap ? blocks : cap);
-  if (material) {
-    if (rf_scratch) hipLaunchKernelGGL(k_path_bwd_prb_material<true>, dim3(grid), dim3(64 * waves), dyn, st, r.c, a, p, gsrc, stack_ints);
-    else hipLaunchKernelGGL(k_path_bwd_prb_material<false>, dim3(grid), dim3(64 * waves), dyn, st, r.c, a, p, gsrc, stack_ints);
-    FFX_CHECK_LAUNCH(rf_scratch ? "render_bwd_filtered (prb, material)" : "render_bwd (prb, material)");
-    return FFX_OK;
-  }
-  if (rf_scratch) hipLaunchKernelGGL(k_path_bwd_prb<true>, dim3(grid), dim3(64 * waves), dyn, st, r.c, a, p, gsrc, stack_ints);
-  else hipLaunchKernelGGL(k_path_bwd_prb<false>, dim3(grid), dim3(64 * waves), dyn, st, r.c, a, p, gsrc, stack_ints);
-  FFX_CHECK_LAUNCH(rf_scratch ? "render_bwd_filtered (prb)" : "render_bwd (prb)");
+  dispatch_rf_mat(rf_scratch != nullptr, material, [&](auto rf, auto m) {
+    constexpr bool RF = decltype(rf)::value;
+    if constexpr (decltype(m)::value) hipLaunchKernelGGL(k_path_bwd_prb_material<RF>, dim3(grid), dim3(64 * waves), dyn, st, r.c, a, p, gsrc, stack_ints);
+    else hipLaunchKernelGGL(k_path_bwd_prb<RF>, dim3(grid), dim3(64 * waves), dyn, st, r.c, a, p, gsrc, stack_ints);
+  });
+  FFX_CHECK_LAUNCH(material ? (rf_scratch ? "render_bwd_filtered (prb, material)" : "render_bwd (prb, material)")
+                            : (rf_scratch ? "render_bwd_filtered (prb)" : "render_bwd (prb)"));
   return FFX_OK;
 }
 // FFX_RENDER_GRAD_MATERIAL and FFX_RENDER_GRAD_PRB extend FFX_RENDER_GRAD_APPEARANCE: alone each is an argument error
@@ -6044,6 +5828,7 @@ static int render_bwd_prb(const void *bvh, const ffx_bvh_info *info, const ffx_s
 // else the direct-light kernels, which ignore the bit (and refuse path bits without it, as before)
 static int render_bwd_leaves(const void *bvh, const ffx_bvh_info *info, const ffx_scene_desc *sd, const float *shape_albedo, int spp, uint32_t seed, int flags,
                              const float *gimg, float *gtex, ffx_stream s, void *rf_scratch) {
+  if (!bvh || !info || !sd || (!shape_albedo && sd->n_mat_h <= 0) || !gimg || !gtex || spp < 1) FFX_FAIL(FFX_ERR_ARG, "render_bwd: bad argument");
   if (flags & FFX_RENDER_GRAD_PRB) {
     int md, rr;
     if (!path_depths(flags, md, rr) || md > 2) return render_bwd_prb(bvh, info, sd, shape_albedo, spp, seed, flags, gimg, gtex, s, rf_scratch);
