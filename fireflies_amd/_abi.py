@@ -209,6 +209,9 @@ def material_floats(n_shapes):
 # path replay backpropagation (include/ffx.h FFX_RENDER_GRAD_PRB): with RENDER_GRAD_APPEARANCE [| RENDER_GRAD_MATERIAL] and path bits, the two blocks
 # at max_depth > 2
 RENDER_GRAD_PRB = 0x40000
+# forward mode (include/ffx.h FFX_RENDER_TANGENT): in the img_fp16 word of ffx_render_fwd[_filtered]; the tangent blocks travel behind the texture in
+# the layout of the gradient blocks, the tangent image comes back behind the primal
+RENDER_TANGENT = 0x80000
 
 
 MAX_BASE_TEX = 4

@@ -4725,6 +4725,191 @@ __global__ void __launch_bounds__(64 * FFX_APP_WAVES)
   path_bwd_prb<RF, true>(c, a, p, gsrc, s_dyn, stack_ints, s_rows, s_mat);
 }
 
+// ------------------------------------------------------------------------------------------ forward mode: the tangent image
+// FFX_RENDER_TANGENT (include/ffx.h): d image / d theta . dtheta for a tangent dtheta of everything the adjoints above differentiate — the projector's
+// texture, the rows' base colours, the spot's intensity, base-colour textures, the BSDF columns.  Every piece is the transpose of the adjoint piece it
+// stands next to: vertex_tangent of base_colour_vjp + emitters_material_vjp + proj_tex_scatter, bounce_tangent of path_bwd_prb's bounce.  One wave =
+// one pixel (k_path_fwd's layout), one walk per sample that carries the throughput and its tangent; no atomics: the box film takes the fixed-order
+// wave sum, the gaussian film rf_fold's sums and k_rf_gather, so two runs give the same bits.
+struct JvpArgs {
+  const float *tex, *dtex;                           // the projector's texture and its tangent (NULL without a projector)
+  const float *drow, *dspot, *dbt[FFX_MAX_BASE_TEX]; // the tangents in the appearance block's layout: [n_shapes][3], [3], [h][w][3] per base-colour texture
+  const float *dmat;                                 // [n_shapes][FFX_MAT_GRAD_COLS], or NULL: a table without material columns
+  float *dimg, *part;                                // the tangent image (box film) / the pixels' [25][4] outgoing sums (gaussian film)
+};
+// (kernels <RF, MAT>: the BSDF's reverse passes cost registers — 2 waves per SIMD through the bounces against 4 without them)
+// what a vertex's bounce needs of its tangents: the base colour's, its luminance-weighted sum, the row's material tangent (NULL: a Lambert row)
+struct VtxTan { float db[3], lum, wdb; const float *md; };
+// the tangent of (A, B) of material_terms along the row's tangent md: the reverse pass seeded with (1, 0) and with (0, 1), dotted with md
+__device__ __forceinline__ void material_terms_jvp(const float *__restrict__ mrow, const MatGeoD &mg, float lum, const float *__restrict__ md, float &dA, float &dB) {
+  float gA[FFX_MAT_GRAD_COLS], gB[FFX_MAT_GRAD_COLS];
+#pragma unroll
+  for (int j = 0; j < FFX_MAT_GRAD_COLS; ++j) gA[j] = gB[j] = 0.f;
+  material_terms_vjp(mrow, mg, lum, 1.f, 0.f, gA);
+  material_terms_vjp(mrow, mg, lum, 0.f, 1.f, gB);
+  dA = dB = 0.f;
+#pragma unroll
+  for (int j = 0; j < FFX_MAT_GRAD_COLS; ++j) {
+    const float t = md[j];
+    dA = __builtin_fmaf(gA[j], t, dA);
+    dB = __builtin_fmaf(gB[j], t, dB);
+  }
+}
+// the next-event term N_c = b_c E_c + F_c of a vertex and its tangent (wv: towards the viewer):
+//   dN_c = db_c E_c - b_c T_c (w . db) / lum^2 + dI_c (b_c s_f + s_fb) + dtex_c (b_c proj_fac + proj_fac_b) + sum_e (b_c dA_e + dB_e) E_ec
+// (E, T, s_f: base_colour_vjp's; E_ec: emitters_material_vjp's; the last sum with MAT only).  vt receives what bounce_tangent needs
+template <bool MAT>
+__device__ __forceinline__ void vertex_tangent(const ShadeK &k, const JvpArgs &j, const SampleTerms &st, const AppTerms &ap, const MatVtx &mv, v3 wv, VtxTan &vt,
+                                               float (&N)[3], float (&dN)[3]) {
+  if (ap.tix == 0) { // the row's own base colour
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) vt.db[ch] = j.drow[(size_t)st.shape * 3 + ch];
+  } else { // a base-colour texture: the tangent texture through the lookup's four taps
+    const float *dt = ap.tix == 1 ? j.dbt[0] : ap.tix == 2 ? j.dbt[1] : ap.tix == 3 ? j.dbt[2] : j.dbt[3];
+    size_t to[4];
+    float tw4[4];
+    base_tex_taps(k, ap.tix - 1, ap.slot, ap.bu, ap.bv, to, tw4);
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) vt.db[ch] = tw4[0] * dt[to[0] + ch] + tw4[1] * dt[to[1] + ch] + tw4[2] * dt[to[2] + ch] + tw4[3] * dt[to[3] + ch];
+  }
+  const float *mt = mat_table(k);
+  const bool model = k.mat_stride == FFX_MAT_STRIDE && mt[(size_t)FFX_MAT_STRIDE * st.shape + FFX_MAT_MODEL] != 0.f;
+  vt.md = MAT && model ? j.dmat + (size_t)st.shape * FFX_MAT_GRAD_COLS : nullptr;
+  vt.lum = base_lum(st);
+  vt.wdb = FFX_LUM_W[0] * vt.db[0] + FFX_LUM_W[1] * vt.db[1] + FFX_LUM_W[2] * vt.db[2];
+  N[0] = N[1] = N[2] = 0.f;
+  dN[0] = dN[1] = dN[2] = 0.f;
+  // no emitter lights the vertex.  (MAT: by the emitters' own factors — a row whose A and B both vanish, as at spec_trans = 1 with eta = 1, still has
+  // one-sided BSDF tangents)
+  if (!st.has_proj && (MAT ? mv.ks == 0.f : ap.s_f == 0.f && ap.s_fb == 0.f)) return;
+  float tv[3] = {0.f, 0.f, 0.f}, dtv[3] = {0.f, 0.f, 0.f};
+  if (st.has_proj) {
+    path_tex(k, st, j.tex, tv);
+    path_tex(k, st, j.dtex, dtv);
+  }
+  const float r = vt.lum > 0.f ? vt.wdb / (vt.lum * vt.lum) : 0.f;
+#pragma unroll
+  for (int ch = 0; ch < 3; ++ch) {
+    const float E = st.spot[ch] + tv[ch] * st.proj_fac, T = k.s_int[ch] * ap.spot_t + tv[ch] * ap.proj_t;
+    N[ch] = st.base[ch] * E + (st.spot_b[ch] + tv[ch] * st.proj_fac_b);
+    dN[ch] = vt.db[ch] * E - st.base[ch] * T * r + j.dspot[ch] * (st.base[ch] * ap.s_f + ap.s_fb) + dtv[ch] * (st.base[ch] * st.proj_fac + st.proj_fac_b);
+  }
+  if (!MAT || !vt.md) return;
+  const float *mrow = mt + (size_t)FFX_MAT_STRIDE * st.shape;
+  MatGeoD mg;
+  float dA, dB;
+  if (mv.kp != 0.f) {
+    material_geometry_d(mv.ns, wv, mv.wp, mg);
+    material_terms_jvp(mrow, mg, vt.lum, vt.md, dA, dB);
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) dN[ch] += (st.base[ch] * dA + dB) * (tv[ch] * mv.kp);
+  }
+  if (mv.ks != 0.f) {
+    material_geometry_d(mv.ns, wv, mv.ws, mg);
+    material_terms_jvp(mrow, mg, vt.lum, vt.md, dA, dB);
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) dN[ch] += (st.base[ch] * dA + dB) * (k.s_int[ch] * mv.ks);
+  }
+}
+// the tangent of the bounce weight f_c = (b_c A + B) / cos_o, A = A0 + pi tau / lum(b) (Lambert rows: f = b) at vertex pv towards wo
+__device__ __forceinline__ void bounce_tangent(const ShadeK &k, const SampleTerms &st, const PathVtx &pv, v3 wv, v3 wo, const PrbBounce &pb, const VtxTan &vt,
+                                               float (&df)[3]) {
+  df[0] = vt.db[0]; df[1] = vt.db[1]; df[2] = vt.db[2];
+  if (!pb.model) return;
+  const float r = vt.lum > 0.f ? vt.wdb * pb.tau / (vt.lum * vt.lum) : 0.f;
+  float dA = 0.f, dB = 0.f;
+  if (vt.md) {
+    MatGeoD mg;
+    material_geometry_d(pv.ns, wv, wo, mg);
+    material_terms_jvp(mat_table(k) + (size_t)FFX_MAT_STRIDE * st.shape, mg, vt.lum, vt.md, dA, dB);
+  }
+#pragma unroll
+  for (int ch = 0; ch < 3; ++ch) df[ch] = (vt.db[ch] * pb.A + st.base[ch] * (dA - r) + dB) * pb.ic;
+}
+// one pixel's tangent.  PATH: through the bounces, dL += dbeta_v N_v + beta_v dN_v, dbeta_v+1 = (dbeta_v f_v + beta_v df_v) / q_v with the roulette's
+// q_v and both termination tests constants (prb's detached roulette); else direct light at the primary hit, by bwd_leaves' walk
+// MAT: the table has material columns (the material block is there); else the BSDF's tangents are not formed
+template <bool RF, bool PATH, bool MAT>
+__device__ __forceinline__ void jvp_pixel(const ShadeK &c, const PathArgs &a, const JvpArgs &j, int *s_dyn, float *s_rf) {
+  const int lane = threadIdx.x;
+  const uint32_t pix = blockIdx.x;
+  const int W = c.cam.W, px = (int)(pix % (uint32_t)W), py = (int)(pix / (uint32_t)W);
+  float acc[4] = {0.f, 0.f, 0.f, 0.f};
+  for (int pass = 0; pass < (a.spp + 63) >> 6; ++pass) {
+    const int s = pass * 64 + lane;
+    const uint32_t idx = pix * (uint32_t)a.spp + (uint32_t)s;
+    float jx, jy;
+    sample_jitter(a.seed_key, idx, jx, jy);
+    float dL[3] = {0.f, 0.f, 0.f};
+    if (s < a.spp) {
+      v3 o, d;
+      float nt, ft;
+      cam_ray(c.cam, ((float)px + jx) * c.cam.inv_w, ((float)py + jy) * c.cam.inv_h, o, d, nt, ft);
+      VtxTan vt;
+      float N[3], dN[3];
+      if (PATH) {
+        float bd[3] = {0.f, 0.f, 0.f}; // the throughput's tangent
+        path_walk<true, MAT>(
+            a, idx, o, d, nt, ft, s_dyn + lane, 64,
+            [&](int, const SampleTerms &st, const AppTerms &ap, const MatVtx &mv, v3 dv, const float (&beta)[3]) {
+              vertex_tangent<MAT>(kernarg_shade(), j, st, ap, mv, V3(-dv.x, -dv.y, -dv.z), vt, N, dN);
+#pragma unroll
+              for (int ch = 0; ch < 3; ++ch) dL[ch] += bd[ch] * N[ch] + beta[ch] * dN[ch];
+            },
+            [&](int, const SampleTerms &st, const PathVtx &pv, const AppTerms &, v3 dv, v3 wo, const float (&beta)[3], float iq, const float (&f)[3],
+                const PrbBounce &pb) {
+              float df[3];
+              bounce_tangent(kernarg_shade(), st, pv, V3(-dv.x, -dv.y, -dv.z), wo, pb, vt, df);
+#pragma unroll
+              for (int ch = 0; ch < 3; ++ch) bd[ch] = (bd[ch] * f[ch] + beta[ch] * df[ch]) * iq;
+            });
+      } else {
+        SampleTerms st;
+        AppTerms ap;
+        MatVtx mv;
+        shade_sample<false, true, MAT>(kernarg_shade(), a.nodes, a.recs, a.nrec, o, d, nt, ft, st, s_dyn + lane, 64, nullptr, &ap, &mv);
+        if (st.hit && (st.has_proj || (MAT ? mv.ks != 0.f : ap.s_f != 0.f || ap.s_fb != 0.f))) { // (lit: st.base is then the row's)
+          vertex_tangent<MAT>(kernarg_shade(), j, st, ap, mv, V3(-d.x, -d.y, -d.z), vt, N, dN);
+          dL[0] = dN[0]; dL[1] = dN[1]; dL[2] = dN[2];
+        }
+      }
+    }
+    if (RF) {
+      float gx[5], gy[5];
+      rf_weights(c.rf, jx, gx);
+      rf_weights(c.rf, jy, gy);
+      rf_fold(s_rf, lane, gx, gy, dL[0], dL[1], dL[2], s < a.spp ? 1.f : 0.f, acc);
+    } else {
+      acc[0] += dL[0]; acc[1] += dL[1]; acc[2] += dL[2];
+    }
+  }
+  if (RF) {
+    rf_store(j.part, pix, lane, acc);
+    return;
+  }
+  const float inv_spp = 1.0f / (float)a.spp;
+  const float m0 = wave_sum_tree(acc[0]) * inv_spp, m1 = wave_sum_tree(acc[1]) * inv_spp, m2 = wave_sum_tree(acc[2]) * inv_spp;
+  if (lane == 0) {
+    float *p = j.dimg + (size_t)pix * 3;
+    p[0] = m0; p[1] = m1; p[2] = m2;
+  }
+}
+// RF: the gaussian film — the tangent's sums into j.part, k_rf_gather forms the tangent image (the weights carry no tangent: dI = sum w dL / sum w)
+template <bool RF, bool MAT>
+__global__ void __launch_bounds__(64)
+    k_render_jvp(ShadeK c, PathArgs a, JvpArgs j) {
+  extern __shared__ int s_dyn[];
+  __shared__ __attribute__((aligned(16))) float s_rf[RF ? FFX_RF_FLOATS : 4];
+  jvp_pixel<RF, false, MAT>(c, a, j, s_dyn, s_rf);
+}
+template <bool RF, bool MAT>
+__global__ void __launch_bounds__(64)
+    k_path_jvp(ShadeK c, PathArgs a, JvpArgs j) {
+  extern __shared__ int s_dyn[];
+  __shared__ __attribute__((aligned(16))) float s_rf[RF ? FFX_RF_FLOATS : 4];
+  jvp_pixel<RF, true, MAT>(c, a, j, s_dyn, s_rf);
+}
+
 // ------------------------------------------------------------------------------------------ host side
 static int cam_prepare(const ffx_camera *c, CamK &k) {
   if (c->width < 1 || c->height < 1) return 0;
@@ -5488,9 +5673,56 @@ static int render_fwd_impl(const void *bvh, const ffx_bvh_info *info, const ffx_
     if ((flags_) & FFX_RENDER_GRAD_MATERIAL) FFX_FAIL(FFX_ERR_UNSUPPORTED, "%s: FFX_RENDER_GRAD_MATERIAL is served by ffx_render_bwd[_filtered] only", what_);     \
     if ((flags_) & FFX_RENDER_GRAD_PRB) FFX_FAIL(FFX_ERR_UNSUPPORTED, "%s: FFX_RENDER_GRAD_PRB is served by ffx_render_bwd[_filtered] only", what_);               \
   } while (0)
+// the tangent image's bit belongs to ffx_render_fwd[_filtered]: every other render entry point refuses it
+#define FFX_NO_TANGENT(flags_, what_) \
+  do { if ((flags_) & FFX_RENDER_TANGENT) FFX_FAIL(FFX_ERR_UNSUPPORTED, "%s: FFX_RENDER_TANGENT is served by ffx_render_fwd[_filtered] only", what_); } while (0)
+// FFX_RENDER_TANGENT (include/ffx.h): the primal by the launches of a call without the bit, then one launch of k_render_jvp (max_depth 2)
+// or k_path_jvp into the tangent image behind it (the gaussian film: into the scratch, which the primal's gather has read by then, and a second gather)
+static int render_jvp(const void *bvh, const ffx_bvh_info *info, const ffx_scene_desc *sd, const float *shape_albedo, const float *tex, int spp, uint32_t seed,
+                      int img_fp16, void *img, ffx_stream s, void *rf_scratch) {
+  const char *what = rf_scratch ? "render_fwd_filtered" : "render_fwd";
+  if (img_fp16 & FFX_RENDER_FP16) FFX_FAIL(FFX_ERR_UNSUPPORTED, "%s: FFX_RENDER_TANGENT has no fp16 film", what);
+  if (!shape_albedo) FFX_FAIL(FFX_ERR_ARG, "%s: FFX_RENDER_TANGENT needs the device material table (shape_albedo is NULL)", what);
+  if (!bvh || !info || !sd || !img || spp < 1) FFX_FAIL(FFX_ERR_ARG, "render_fwd: bad argument");
+  if (!tex) FFX_FAIL(FFX_ERR_ARG, "render_fwd: FFX_RENDER_TANGENT but tex (the tangent blocks) is NULL");
+  RenderSetup r;
+  if (const int rc = render_setup("render_fwd", bvh, info, sd, shape_albedo, spp, seed, img_fp16, rf_scratch, r)) return rc;
+  if (sd->n_shapes < 1) FFX_FAIL(FFX_ERR_ARG, "render_fwd: n_shapes < 1");
+  const long n_tex = sd->proj.enabled ? (long)sd->proj.tex_w * sd->proj.tex_h * sd->proj.tex_channels : 0;
+  if (n_tex < 0) FFX_FAIL(FFX_ERR_ARG, "render_fwd: bad projector texture size");
+  if (r.n_pix >= (1L << 31)) FFX_FAIL(FFX_ERR_UNSUPPORTED, "render_fwd: more than 2^31 pixels");
+  if (const int rc = render_fwd_impl(bvh, info, sd, shape_albedo, tex, spp, seed, img_fp16 & (FFX_RENDER_APEX_READY | FFX_RENDER_PATH_MASK), img, nullptr, s, nullptr,
+                                     nullptr, nullptr, rf_scratch))
+    return rc;
+  JvpArgs j;
+  memset(&j, 0, sizeof j);
+  if (sd->proj.enabled) { j.tex = tex; j.dtex = tex + n_tex; }
+  j.drow = tex + 2 * n_tex; j.dspot = j.drow + (size_t)3 * sd->n_shapes;
+  const float *bt = j.dspot + 3;
+  for (int k = 0; k < r.c.n_base_tex; ++k) {
+    j.dbt[k] = bt;
+    bt += (size_t)3 * r.c.btw[k] * r.c.bth[k];
+  }
+  // (a table of stride 3 has no material columns: the block is not there)
+  j.dmat = r.c.mat_stride == FFX_MAT_STRIDE ? tex + 2 * n_tex + FFX_RENDER_APPEARANCE_FLOATS(sd) : nullptr;
+  j.dimg = (float *)img + (size_t)r.n_pix * 3;
+  j.part = (float *)rf_scratch;
+  const hipStream_t st = (hipStream_t)s;
+  const PathArgs pa = path_args(r);
+  const bool path = r.max_depth > 2;
+  dispatch_rf_mat(rf_scratch != nullptr, j.dmat != nullptr, [&](auto rf, auto m) {
+    constexpr bool RF = decltype(rf)::value, MAT = decltype(m)::value;
+    if (path) hipLaunchKernelGGL((k_path_jvp<RF, MAT>), dim3((unsigned)r.n_pix), dim3(64), path_stack_bytes(info), st, r.c, pa, j);
+    else hipLaunchKernelGGL((k_render_jvp<RF, MAT>), dim3((unsigned)r.n_pix), dim3(64), path_stack_bytes(info), st, r.c, pa, j);
+  });
+  FFX_CHECK_LAUNCH(path ? (rf_scratch ? "render_fwd_filtered (path, tangent)" : "render_fwd (path, tangent)") : (rf_scratch ? "render_fwd_filtered (tangent)" : "render_fwd (tangent)"));
+  if (rf_scratch) return rf_develop(r, 0, j.dimg, rf_scratch, st, "render_fwd_filtered (tangent)/gather");
+  return FFX_OK;
+}
 int ffx_render_fwd(const void *bvh, const ffx_bvh_info *info, const ffx_scene_desc *sd, const float *shape_albedo, const float *tex, int spp,
                    uint32_t seed, int img_fp16, void *img, ffx_stream s) {
   FFX_NO_APPEARANCE(img_fp16, "render_fwd");
+  if (img_fp16 & FFX_RENDER_TANGENT) return render_jvp(bvh, info, sd, shape_albedo, tex, spp, seed, img_fp16, img, s, nullptr);
   return render_fwd_impl(bvh, info, sd, shape_albedo, tex, spp, seed, img_fp16 & (FFX_RENDER_FP16 | FFX_RENDER_APEX_READY | FFX_RENDER_PATH_MASK), img, nullptr, s);
 }
 // the entry points without the path integrator refuse its bits rather than render direct light only
@@ -5516,6 +5748,7 @@ int ffx_render_fwd_cache(const void *bvh, const ffx_bvh_info *info, const ffx_sc
   if (((uintptr_t)cache & 15) != 0) FFX_FAIL(FFX_ERR_ARG, "render_fwd_cache: cache must be 16-byte aligned");
   FFX_NO_PATH(img_fp16, "render_fwd_cache");
   FFX_NO_APPEARANCE(img_fp16, "render_fwd_cache");
+  FFX_NO_TANGENT(img_fp16, "render_fwd_cache");
   return render_fwd_impl(bvh, info, sd, shape_albedo, tex, spp, seed, img_fp16 & 31, img, cache, s);
 }
 
@@ -5535,6 +5768,7 @@ int ffx_render_fwd_adjoint(const void *bvh, const ffx_bvh_info *info, const ffx_
   if (sd && !sd->proj.enabled) FFX_FAIL(FFX_ERR_ARG, "render_fwd_adjoint: the scene has no projector (nothing to differentiate)");
   FFX_NO_PATH(img_fp16, "render_fwd_adjoint");
   FFX_NO_APPEARANCE(img_fp16, "render_fwd_adjoint");
+  FFX_NO_TANGENT(img_fp16, "render_fwd_adjoint");
   return render_fwd_impl(bvh, info, sd, shape_albedo, tex, spp, seed, img_fp16 & (FFX_RENDER_FP16 | FFX_RENDER_SPARSE_ADJOINT | FFX_RENDER_APEX_READY), img, nullptr, s, gimg,
                          gtex, dot_out);
 }
@@ -5564,6 +5798,7 @@ int ffx_render_bwd_cached(const ffx_scene_desc *sd, const float *shape_albedo, c
   if (!gimg) FFX_FAIL(FFX_ERR_ARG, "render_bwd_cached: bad argument");
   FFX_NO_PATH(img_fp16, "render_bwd_cached");
   FFX_NO_APPEARANCE(img_fp16, "render_bwd_cached");
+  FFX_NO_TANGENT(img_fp16, "render_bwd_cached");
   return render_bwd_cached_impl(sd, shape_albedo, cache, spp, gimg, gtex, img, img_fp16, dot_out, nullptr, 0.f, s);
 }
 // K9 under an L1 loss against a target image (include/ffx.h): the loss launch (ffx_l1_value_grad) and its gradient image are folded into the scatter
@@ -5839,6 +6074,7 @@ static int render_bwd_leaves(const void *bvh, const ffx_bvh_info *info, const ff
 
 int ffx_render_bwd(const void *bvh, const ffx_bvh_info *info, const ffx_scene_desc *sd, const float *shape_albedo, int spp, uint32_t seed, int flags,
                    const float *gimg, float *gtex, ffx_stream s) {
+  FFX_NO_TANGENT(flags, "render_bwd");
   FFX_MATERIAL_NEEDS_APPEARANCE(flags, "render_bwd");
   if (flags & FFX_RENDER_GRAD_APPEARANCE) return render_bwd_leaves(bvh, info, sd, shape_albedo, spp, seed, flags, gimg, gtex, s, nullptr);
   return render_bwd_impl(bvh, info, sd, shape_albedo, spp, seed, flags, gimg, gtex, s, nullptr);
@@ -5855,6 +6091,7 @@ int ffx_render_bwd_det(const void *bvh, const ffx_bvh_info *info, const ffx_scen
   if (!sd) FFX_FAIL(FFX_ERR_ARG, "render_bwd_det: bad argument");
   FFX_NO_PATH(flags, "render_bwd_det");
   FFX_NO_APPEARANCE(flags, "render_bwd_det");
+  FFX_NO_TANGENT(flags, "render_bwd_det");
   // workspace: [the filtered film's scratch (16-byte multiple)] [one 64-bit sum per texel and channel] [the largest tap]
   void *rf = sd->rfilter != FFX_RFILTER_BOX ? workspace : nullptr;
   void *det = (char *)workspace + (rf ? ffx_render_filter_bytes(sd) : 0);
@@ -5867,6 +6104,7 @@ int ffx_render_bwd_det_part(const void *bvh, const ffx_bvh_info *info, const ffx
   if (scale_log2 < -126 || scale_log2 > 126) FFX_FAIL(FFX_ERR_ARG, "render_bwd_det_part: scale_log2 out of range");
   FFX_NO_PATH(flags, "render_bwd_det_part");
   FFX_NO_APPEARANCE(flags, "render_bwd_det_part");
+  FFX_NO_TANGENT(flags, "render_bwd_det_part");
   void *rf = nullptr;
   if (sd->rfilter != FFX_RFILTER_BOX) {
     if (!workspace || ((uintptr_t)workspace & 15) != 0) FFX_FAIL(FFX_ERR_ARG, "render_bwd_det_part: a filtered film needs its scratch (ffx_render_filter_bytes), 16-byte aligned");
@@ -5896,6 +6134,7 @@ int ffx_render_fwd_filtered(const void *bvh, const ffx_bvh_info *info, const ffx
                             uint32_t seed, int img_fp16, void *img, void *scratch, ffx_stream s) {
   if (!scratch || ((uintptr_t)scratch & 15) != 0) FFX_FAIL(FFX_ERR_ARG, "render_fwd_filtered: scratch is NULL or not 16-byte aligned");
   FFX_NO_APPEARANCE(img_fp16, "render_fwd_filtered");
+  if (img_fp16 & FFX_RENDER_TANGENT) return render_jvp(bvh, info, sd, shape_albedo, tex, spp, seed, img_fp16, img, s, scratch);
   return render_fwd_impl(bvh, info, sd, shape_albedo, tex, spp, seed, img_fp16 & (FFX_RENDER_FP16 | FFX_RENDER_APEX_READY | FFX_RENDER_PATH_MASK), img, nullptr, s, nullptr,
                          nullptr, nullptr, scratch);
 }
@@ -5907,6 +6146,7 @@ int ffx_render_fwd_adjoint_filtered(const void *bvh, const ffx_bvh_info *info, c
   if (sd && !sd->proj.enabled) FFX_FAIL(FFX_ERR_ARG, "render_fwd_adjoint_filtered: the scene has no projector (nothing to differentiate)");
   FFX_NO_PATH(img_fp16, "render_fwd_adjoint_filtered");
   FFX_NO_APPEARANCE(img_fp16, "render_fwd_adjoint_filtered");
+  FFX_NO_TANGENT(img_fp16, "render_fwd_adjoint_filtered");
   return render_fwd_impl(bvh, info, sd, shape_albedo, tex, spp, seed, img_fp16 & (FFX_RENDER_FP16 | FFX_RENDER_SPARSE_ADJOINT | FFX_RENDER_APEX_READY), img, nullptr, s, gimg,
                          gtex, nullptr, scratch);
 }
@@ -5914,6 +6154,7 @@ int ffx_render_fwd_adjoint_filtered(const void *bvh, const ffx_bvh_info *info, c
 int ffx_render_bwd_filtered(const void *bvh, const ffx_bvh_info *info, const ffx_scene_desc *sd, const float *shape_albedo, int spp, uint32_t seed, int flags,
                             const float *gimg, float *gtex, void *scratch, ffx_stream s) {
   if (!scratch || ((uintptr_t)scratch & 15) != 0) FFX_FAIL(FFX_ERR_ARG, "render_bwd_filtered: scratch is NULL or not 16-byte aligned");
+  FFX_NO_TANGENT(flags, "render_bwd_filtered");
   FFX_MATERIAL_NEEDS_APPEARANCE(flags, "render_bwd_filtered");
   if (flags & FFX_RENDER_GRAD_APPEARANCE) return render_bwd_leaves(bvh, info, sd, shape_albedo, spp, seed, flags, gimg, gtex, s, scratch);
   return render_bwd_impl(bvh, info, sd, shape_albedo, spp, seed, flags, gimg, gtex, s, scratch);
@@ -5925,6 +6166,7 @@ int ffx_render_fwd_cache_filtered(const void *bvh, const ffx_bvh_info *info, con
   if (!scratch || ((uintptr_t)scratch & 15) != 0) FFX_FAIL(FFX_ERR_ARG, "render_fwd_cache_filtered: scratch is NULL or not 16-byte aligned");
   FFX_NO_PATH(img_fp16, "render_fwd_cache_filtered");
   FFX_NO_APPEARANCE(img_fp16, "render_fwd_cache_filtered");
+  FFX_NO_TANGENT(img_fp16, "render_fwd_cache_filtered");
   return render_fwd_impl(bvh, info, sd, shape_albedo, tex, spp, seed,
                          img_fp16 & (FFX_RENDER_FP16 | FFX_RENDER_SPARSE_ADJOINT | FFX_RENDER_APEX_READY | FFX_RENDER_CACHE_ZEROED | FFX_RENDER_CACHE_KEEP_DROPPED), img, nullptr, s,
                          nullptr, nullptr, nullptr, scratch, cache);

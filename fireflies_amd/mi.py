@@ -1188,6 +1188,10 @@ class Integrator:
     def __repr__(self):
         return f"Integrator(type={self.type!r}, max_depth={self.max_depth}, rr_depth={self.rr_depth})"
 
+    def render_forward(self, scene, params, tangents, sensor=0, seed=0, spp=0):
+        """Mitsuba's Integrator.render_forward, with the tangents given per key: mi.render_forward(..., integrator=self) (spp 0: the default 16)"""
+        return render_forward(scene, params, tangents, spp=int(spp) if spp else 16, seed=seed, sensor=sensor, integrator=self)
+
 
 def load_dict(d: dict):
     """mi.load_dict for integrator dictionaries: {"type": "path" | "prb", "max_depth": k, "rr_depth": r} or {"type": "direct"} -> Integrator.
@@ -1286,6 +1290,121 @@ def _render_path(scene, spp, seed, fp16, integrator):
     return TensorXf(scene.geom.render_fwd(sd, mats, t.unsqueeze(-1) if t.dim() == 2 else t, int(spp), int(seed), bool(fp16), max_depth=md, rr_depth=rr))
 
 
+def _forward_keys(scene):
+    """the keys mi.render_forward takes tangents for: `tex.data` and the leaf keys of mi.render's appearance and BSDF gradients"""
+    return sorted(scene._params._leaf_keys | ({"tex.data"} if scene.data.projector is not None else set()))
+
+
+def _eta_owner(scene, mat):
+    """the key that drives a principled material's eta: the one that wrote it last (Scene._eta_src), else what the scene file gave"""
+    eta_key = mat + ".brdf_0.eta"
+    src = scene._eta_src.get(eta_key)
+    if src is None:
+        bsdf = next((m.bsdf for m in scene.data.meshes if m.material == mat), None) or {}
+        src = eta_key if "eta" in bsdf and "specular" not in bsdf else mat + ".brdf_0.specular"  # (scenes.material_row's rule)
+    return src
+
+
+def _eta_factor(scene, k, base, name, value, rows, owner):
+    """what a `specular` / `eta` key `k` of material `base` contributes to the eta column of its rows — one rule for mi.render's backward and for
+    mi.render_forward.  owner: the key that drives the rows' eta.  0 when that is the other key; `specular` chains with
+    scenes.specular_to_eta_grad(value) (at 0: the finite limit the column's own limit at eta = 1 pairs with); `eta` counts 1, except at eta = 1,
+    where the column holds that limit and d / d eta itself is 0"""
+    if owner != k:
+        return 0.0
+    if name == "specular":
+        return scenes.specular_to_eta_grad(float(value))
+    return 0.0 if float(scene._albedo_host[rows[0], scenes.MAT_COLUMN["eta"]]) == 1.0 else 1.0
+
+
+def render_forward(scene: Scene, params: SceneParameters = None, tangents: dict = None, spp: int = 16, seed: int = 0, sensor: int = 0,
+                   integrator: Integrator = None):
+    """forward-mode derivative of mi.render: -> (image, d image / d theta . dtheta), both [H,W,3] TensorXf.  `tangents` maps
+    parameter keys to tensors shaped like the parameter (a scalar for a scalar): `tex.data`, `<mat>.brdf_0.base_color.value`, `<spot>.intensity.value`,
+    `<mat>.brdf_0.base_color.data` and the principled BSDF's keys — any other key is a KeyError.  The keys need not hold tensors that require grad.  A
+    material's tangent acts on every shape of the material; `specular` is chained to eta (scenes.specular_to_eta_grad) while it drives the row's eta,
+    `eta` while it does.  integrator: None, `direct` or max_depth 2: direct light; `prb`: through the bounces with the roulette detached; `path` with
+    max_depth > 2 only for a tangent of `tex.data` alone (the image is linear in the texture and no path depends on it)."""
+    if sensor != 0:
+        raise NotImplementedError("only sensor 0 renders; further sensors are projector proxies")
+    if integrator is not None and not isinstance(integrator, Integrator):
+        raise TypeError("render_forward: integrator must come from mi.load_dict")
+    if not isinstance(tangents, dict):
+        raise TypeError("render_forward: tangents must be a dict of parameter key -> tensor")
+    allowed = _forward_keys(scene)
+    bad = sorted(k for k in tangents if k not in allowed)
+    if bad:
+        raise KeyError(f"render_forward: no tangent is served for {bad}; the allowed keys are {allowed}")
+    md, rr = (2, 5) if integrator is None else (int(integrator.max_depth), int(integrator.rr_depth))
+    if md > 2 and integrator.type != "prb" and set(tangents) - {"tex.data"}:
+        raise ValueError("render_forward: under the 'path' integrator with max_depth > 2 only a tangent of tex.data is served; use the 'prb' integrator "
+                         "(mi.load_dict({'type': 'prb', ...})) for " + ", ".join(sorted(set(tangents) - {"tex.data"})))
+    p = scene._params
+    tex = None
+    ch = 3
+    if scene.data.projector is not None:
+        tex = p["tex.data"]
+        tex = tex.t if isinstance(tex, _ArrayBase) else tex
+        if not isinstance(tex, torch.Tensor):
+            tex = torch.as_tensor(np.asarray(tex, np.float32))
+        tex = tex.detach().to(device=scene.device, dtype=torch.float32)
+        ch = 1 if tex.dim() == 2 else int(tex.shape[-1])
+    scene.note_spp(spp)
+    sd = scene.scene_desc(tex_channels=ch)
+    S = int(sd.n_shapes)
+    dev = scene.device
+
+    def as_t(v, n, key):
+        v = v.t if isinstance(v, _ArrayBase) else v
+        v = torch.as_tensor(v).detach().to(device=dev, dtype=torch.float32).reshape(-1)
+        if v.numel() == 1 and n == 3:
+            v = v.expand(3)  # (a scalar assigned to a colour is broadcast to its three channels)
+        if v.numel() != n:
+            raise ValueError(f"render_forward: the tangent of {key} must be shaped like the parameter ({n} values), got {v.numel()}")
+        return v
+
+    rows = torch.zeros((S, 3), device=dev)
+    spot = torch.zeros(3, device=dev)
+    names = [n for n, _ in scene._base_tex]
+    base_tex = [None] * len(names)
+    principled = int(sd.mat_stride) == scenes.MAT_STRIDE
+    material = torch.zeros((S, 11), device=dev) if principled else None
+    dtex = None
+    for k, v in tangents.items():
+        base, _, rest = k.partition(".")
+        if k == "tex.data":
+            dtex = as_t(v, tex.numel(), k)
+        elif rest == "brdf_0.base_color.value":
+            rows[list(scene._material_meshes[base])] += as_t(v, 3, k)
+        elif rest == "brdf_0.base_color.data":
+            i = names.index(base)
+            base_tex[i] = as_t(v, scene._base_tex[i][1].numel(), k)
+        elif rest.startswith("brdf_0."):
+            name = rest[len("brdf_0."):]
+            name = name[:-len(".value")] if name.endswith(".value") else name
+            if not principled or not scene._material_principled.get(base, False):
+                continue  # (a diffuse material's `specular` / `roughness`: no part of the render)
+            fac = 1.0
+            mrows = list(scene._material_meshes[base])
+            if name in ("specular", "eta"):
+                sv = p[k]
+                sv = float(torch.as_tensor(sv.t if isinstance(sv, _ArrayBase) else sv).detach().reshape(-1)[0])
+                # (the owner: Scene._eta_src, or — nothing assigned yet, which a leaf of the backward never is — what the scene file gave)
+                fac = _eta_factor(scene, k, base, name, sv, mrows, _eta_owner(scene, base))
+            col = scenes.MAT_COLUMN["eta" if name == "specular" else name] - scenes.MAT_COLUMN["roughness"]
+            material[mrows, col] += as_t(v, 1, k)[0] * fac
+        else:
+            spot += as_t(v, 3, k)
+    t3 = None
+    if tex is not None:
+        t3 = (tex if tex.is_contiguous() else tex.contiguous())
+        t3 = t3.unsqueeze(-1) if t3.dim() == 2 else t3
+    scene.render_paths["caller_stream"] += 1
+    img, dimg = scene.geom.render_jvp(sd, scene.albedo, t3, int(spp), int(seed), dtex=dtex, tangent=ops.AppearanceGrad(rows, spot, base_tex, material),
+                                      max_depth=md, rr_depth=rr)
+    return TensorXf(img), TensorXf(dimg)
+
+
 class _AppearanceRender(torch.autograd.Function):
     """mi.render with appearance leaves: the plain forward; the backward is ONE ffx_render_bwd[_filtered] call with
     FFX_RENDER_GRAD_APPEARANCE, which yields the texture gradient and the appearance block together (and, with BSDF leaves, FFX_RENDER_GRAD_MATERIAL's
@@ -1376,13 +1495,8 @@ def _render_appearance(scene, spp, seed, fp16, integrator):
             name = name[:-len(".value")] if name.endswith(".value") else name
             fac = 1.0
             if name in ("specular", "eta"):
-                eta_key = base + ".brdf_0.eta"
-                if scene._eta_src.get(eta_key) != k:
-                    fac = 0.0  # (the row's eta came from the other key, or a diffuse material's `specular`: no part of the render)
-                elif name == "specular":
-                    fac = scenes.specular_to_eta_grad(float(leaf.detach().reshape(-1)[0]))
-                elif float(scene._albedo_host[rows[0], scenes.MAT_COLUMN["eta"]]) == 1.0:
-                    fac = 0.0  # (at eta = 1 the column holds the limit a `specular` of 0 chains with; d loss / d eta itself is 0 there)
+                # (the owner is the key that wrote the row's eta last; the other key, or a diffuse material's `specular`, is no part of the render)
+                fac = _eta_factor(scene, k, base, name, leaf.detach().reshape(-1)[0], rows, scene._eta_src.get(base + ".brdf_0.eta"))
             col = scenes.MAT_COLUMN["eta" if name == "specular" else name] - scenes.MAT_COLUMN["roughness"]
             kinds.append(("bsdf", (rows, col, fac)))
         else:

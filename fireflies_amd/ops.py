@@ -1195,6 +1195,77 @@ class DeviceGeometry:
             raise ValueError("render_bwd_prb has no deterministic adjoint (FFX_DETERMINISTIC / deterministic=True)")
         return self._render_bwd_leaves(sd, albedo, spp, seed, gimg, tex, material, (path | _abi.RENDER_GRAD_PRB) if path else 0, "render_bwd_prb")
 
+    def render_jvp(self, sd, albedo, tex, spp, seed=0, *, dtex=None, tangent=None, max_depth=2, rr_depth=5):
+        """forward mode (FFX_RENDER_TANGENT): -> (img, dimg), img the image of render_fwd with the same arguments bit for bit and dimg =
+        d img / d theta . dtheta.  dtex: the tangent of the projector's texture (shaped like tex); tangent: an AppearanceGrad whose fields hold tangents
+        where render_bwd(appearance=True, material=True) returns gradients — rows [n_shapes, 3], spot [3], base_tex [h, w, 3] per texture, material
+        [n_shapes, 11] (the eta column: a tangent of eta).  None anywhere is a zero tangent.  albedo: the device material table (needed even when the
+        scene description carries the rows).  max_depth > 2: through the bounces with prb's detached roulette.  fp32 film; two calls give the same bits."""
+        path = path_flags(max_depth, rr_depth) if max_depth != 2 else 0
+        H, W = sd.cam.height, sd.cam.width
+        if albedo is None:
+            raise ValueError("render_jvp: the device material table is needed")
+        ms = int(sd.mat_stride) or 3
+        if albedo.dim() != 2 or albedo.shape[1] != ms or albedo.shape[0] < sd.n_shapes:
+            raise ValueError(f"material table {tuple(albedo.shape)} does not match the scene description (n_shapes {sd.n_shapes}, mat_stride {ms})")
+        buf = self.pack_tangent(sd, tex, dtex, tangent).to(self.device)
+        out = torch.empty((2, H, W, 3), dtype=torch.float32, device=self.device)
+        blob = self.blob
+        # (direct light: the primal is the packet kernels' and takes the apex flag render_fwd takes; deeper paths walk per lane)
+        flags = (path if path else self._apex_flag(apex_key(sd))) | _abi.RENDER_TANGENT
+        with self._timed("render_jvp"):
+            if sd.rfilter:
+                scratch = torch.empty(render_filter_bytes(sd), dtype=torch.uint8, device=self.device)
+                self._call("ffx_render_fwd_filtered", _dev(blob, torch.uint8), C.byref(self.info), C.byref(sd), _dev(albedo, name="albedo"), _dev(buf, name="tex"), int(spp),
+                           int(seed) & 0xFFFFFFFF, flags, _dev(out), _dev(scratch, torch.uint8), _stream(self._didx))
+            else:
+                self._call("ffx_render_fwd", _dev(blob, torch.uint8), C.byref(self.info), C.byref(sd), _dev(albedo, name="albedo"), _dev(buf, name="tex"), int(spp),
+                           int(seed) & 0xFFFFFFFF, flags, _dev(out), _stream(self._didx))
+        self._release()
+        return out[0], out[1]
+
+    @staticmethod
+    def pack_tangent(sd, tex, dtex, tangent):
+        """the `tex` buffer of a FFX_RENDER_TANGENT call (include/ffx.h): [texture, its tangent] with a projector, then the appearance block's
+        _abi.appearance_floats floats of tangent, then — a table with material columns — _abi.material_floats floats.  On the device of `tex` (or of the
+        first tangent given, else the host)"""
+        S = int(sd.n_shapes)
+        bt = [(int(sd.base_tex_h[k]), int(sd.base_tex_w[k])) for k in range(sd.n_base_tex)]
+        n_tex = sd.proj.tex_h * sd.proj.tex_w * sd.proj.tex_channels if sd.proj.enabled else 0
+        n_app = _abi.appearance_floats(S, bt)
+        n_mat = _abi.material_floats(S) if int(sd.mat_stride) == _abi.MAT_STRIDE else 0
+        t = tangent if tangent is not None else AppearanceGrad(None, None, None, None)
+        given = [x for x in (tex, dtex, t.rows, t.spot, t.material, *(t.base_tex or [])) if isinstance(x, torch.Tensor)]
+        device = given[0].device if given else torch.device("cpu")
+        buf = torch.zeros(2 * n_tex + n_app + n_mat, dtype=torch.float32, device=device)
+
+        def put(o, v, n, what):
+            if v is None:
+                return
+            v = torch.as_tensor(v).detach().to(device=device, dtype=torch.float32).reshape(-1)
+            if v.numel() != n:
+                raise ValueError(f"render_jvp: {what} must hold {n} floats, got {v.numel()}")
+            buf[o:o + n] = v
+
+        if n_tex:
+            if tex is None:
+                raise ValueError(f"render_jvp: the projector's texture ({n_tex} floats) is needed")
+            put(0, tex, n_tex, "tex")
+            put(n_tex, dtex, n_tex, "dtex")
+        o = 2 * n_tex
+        put(o, t.rows, 3 * S, "tangent.rows")
+        put(o + 3 * S, t.spot, 3, "tangent.spot")
+        o += 3 * S + 3
+        if t.base_tex is not None and len(t.base_tex) != len(bt):
+            raise ValueError(f"render_jvp: tangent.base_tex must list {len(bt)} textures (None for a zero tangent)")
+        for k, (h, w) in enumerate(bt):
+            put(o, t.base_tex[k] if t.base_tex is not None else None, 3 * h * w, f"tangent.base_tex[{k}]")
+            o += 3 * h * w
+        if t.material is not None and not n_mat:
+            raise ValueError("render_jvp: tangent.material on a table without material columns")
+        put(o, t.material, n_mat, "tangent.material")
+        return buf
+
     def _render_bwd_leaves(self, sd, albedo, spp, seed, gimg, tex, material, path, what):
         """the call behind render_bwd(appearance=True) (path 0) and render_bwd_prb (the path bits | FFX_RENDER_GRAD_PRB)"""
         H, W = sd.cam.height, sd.cam.width

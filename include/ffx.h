@@ -805,6 +805,23 @@ int ffx_det_finish(const void *acc /*[dev] int64 [n]*/, int scale_log2, size_t n
  * (the field unset or 2) the bit is ignored and the direct-light kernels run.  FFX_RENDER_GRAD_APPEARANCE with path bits but without this bit is
  * refused as before.  The oracle ignores the bit. */
 #define FFX_RENDER_GRAD_PRB 0x40000
+/* Forward mode (Mitsuba's render_forward): FFX_RENDER_TANGENT in the img_fp16 word of ffx_render_fwd / ffx_render_fwd_filtered adds the
+ * tangent image d image / d theta . dtheta for a tangent dtheta of everything the three adjoint bits above differentiate.  An additive extension of
+ * ABI 11 (FFX_ABI_VERSION is unchanged).
+ *   input  — tex [tex_h][tex_w][tex_channels] is followed in the same buffer by the texture's tangent of the same shape (a scene without a projector
+ *            has neither), then by FFX_RENDER_APPEARANCE_FLOATS(sd) floats of tangent in the layout of the appearance GRADIENT block ([n_shapes][3]
+ *            base-colour rows, [3] spot intensity, [h_k][w_k][3] per base-colour texture), then by FFX_RENDER_MATERIAL_FLOATS(sd) floats ([n_shapes][11],
+ *            columns FFX_MAT_ROUGHNESS .. FFX_MAT_CLEARCOAT_GLOSS; the eta column is a tangent of eta): <tangent, gradient> is a plain inner product of
+ *            the buffers.  A table of stride 3 has no material columns and the material block is then not there.  The base-colour tangent of a row with
+ *            FFX_MAT_BASE_TEX != 0 and the material tangent of a Lambert row are ignored (the adjoints write zeros there).
+ *   output — img: [H][W][3] fp32 primal, exactly the image of the call without the bit (its launches, bit for bit), followed by the [H][W][3] fp32
+ *            tangent image, written by further launches on the same stream.  The gaussian film's weights carry no tangent: dI = sum w dL / sum w; its
+ *            scratch keeps its size and is reused in stream order.
+ * With FFX_RENDER_PATH(k, r), k in 3 .. FFX_RENDER_MAX_DEPTH_LIMIT, the tangent runs through the bounces with prb's detached roulette (the survival
+ * probabilities and both termination tests are constants).  No atomics: two calls give the same bits.  FFX_ERR_UNSUPPORTED together with
+ * FFX_RENDER_FP16 and on every other render entry point; FFX_ERR_ARG with a NULL shape_albedo (the rows of sd->mat_h do not stand in for it here).
+ * The oracle ignores the bit. */
+#define FFX_RENDER_TANGENT 0x80000
 /* Writes the apex records (the triangles as seen from a fixed ray origin) of sd's camera and enabled emitters into
  * the blob's apex areas — what every packet render does in front of its kernel unless told FFX_RENDER_APEX_READY.  Only
  * sd->cam.to_world, sd->proj.{enabled,to_world} and sd->spot.{enabled,to_world} are read.  No reference counterpart (Mitsuba

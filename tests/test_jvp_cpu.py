@@ -1,0 +1,294 @@
+"""Forward mode (FFX_RENDER_TANGENT) without a GPU: the bit in the header and in _abi, the refusals that come before any launch (host
+dummy pointers, as tests/test_abi_cpu.py's), the packing of the tangent blocks behind the texture, mi.render_forward's key and integrator rules (on a
+stand-in for the scene: they are decided before the geometry is touched) and the float64 tangent that tests/test_jvp_gpu.py compares to — central
+differences of tests/ref_prb.render_fwd_frozen along the tangent, with the linear parts (texture, spot intensity) taken exactly."""
+import ctypes as C
+import os
+import re
+import types
+
+import numpy as np
+import pytest
+import torch
+
+from fireflies_amd import _abi, _lib, mi, ops, scene_desc, scenes
+from tests import ref_prb
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+FFX_ERR_ARG, FFX_ERR_UNSUPPORTED = -1, -3  # (include/ffx.h)
+TAN = 0x80000
+GAUSS = {"rfilter": _abi.RFILTER_GAUSSIAN}
+R0 = scenes.MAT_COLUMN["roughness"]
+
+
+def _header():
+    with open(os.path.join(ROOT, "include", "ffx.h")) as f:
+        return f.read()
+
+
+def test_bit_in_header_and_abi_agree_and_the_abi_is_frozen():
+    h = _header()
+    assert int(re.search(r"^#define\s+FFX_RENDER_TANGENT\s+(\S+)", h, re.M).group(1), 0) == _abi.RENDER_TANGENT == TAN
+    assert int(re.search(r"^#define\s+FFX_ABI_VERSION\s+(\S+)", h, re.M).group(1), 0) == _abi.FFX_ABI_VERSION == 11
+    for name, val in re.findall(r"^#define\s+(FFX_RENDER_[A-Z_0-9]+)\s+(0x[0-9a-fA-F]+|\d+)\s", h, re.M):
+        if name in ("FFX_RENDER_TANGENT", "FFX_RENDER_MAX_DEPTH_SHIFT", "FFX_RENDER_RR_DEPTH_SHIFT", "FFX_RENDER_MAX_DEPTH_LIMIT", "FFX_RENDER_MATERIAL_COLS"):
+            continue
+        assert TAN & int(val, 0) == 0, name
+    assert "render_jvp" not in h and "ffx_render_forward" not in h  # (no new entry point: the bit rides on ffx_render_fwd[_filtered])
+
+
+_PARAMS = {
+    "ffx_render_fwd": "bvh info sd mats tex spp seed flags img s",
+    "ffx_render_fwd_cache": "bvh info sd mats tex spp seed flags img cache s",
+    "ffx_render_fwd_adjoint": "bvh info sd mats tex spp seed flags img gimg gtex dot s",
+    "ffx_render_fwd_filtered": "bvh info sd mats tex spp seed flags img scratch s",
+    "ffx_render_fwd_adjoint_filtered": "bvh info sd mats tex spp seed flags img gimg gtex scratch s",
+    "ffx_render_fwd_cache_filtered": "bvh info sd mats tex spp seed flags img cache scratch s",
+    "ffx_render_bwd": "bvh info sd mats spp seed flags gimg gtex s",
+    "ffx_render_bwd_filtered": "bvh info sd mats spp seed flags gimg gtex scratch s",
+    "ffx_render_bwd_det": "bvh info sd mats spp seed flags gimg gtex workspace s",
+    "ffx_render_bwd_det_part": "bvh info sd mats spp seed flags gimg part scale_log2 acc workspace s",
+    "ffx_render_bwd_cached": "sd mats cache spp gimg gtex img flags dot s",
+}
+_OTHERS = ("ffx_render_fwd_cache", "ffx_render_fwd_adjoint", "ffx_render_fwd_adjoint_filtered", "ffx_render_fwd_cache_filtered", "ffx_render_bwd",
+           "ffx_render_bwd_filtered", "ffx_render_bwd_det", "ffx_render_bwd_det_part", "ffx_render_bwd_cached")
+_P3 = _abi.render_path(3, 5)
+# (entry point, scene / bvh info changes, argument changes, return code, message)
+_CASES = [
+    ("ffx_render_fwd", {}, {"flags": TAN | _abi.RENDER_FP16}, FFX_ERR_UNSUPPORTED, "render_fwd: FFX_RENDER_TANGENT has no fp16 film"),
+    ("ffx_render_fwd", {}, {"flags": TAN | _abi.RENDER_FP16 | _P3}, FFX_ERR_UNSUPPORTED, "render_fwd: FFX_RENDER_TANGENT has no fp16 film"),
+    ("ffx_render_fwd_filtered", GAUSS, {"flags": TAN | _abi.RENDER_FP16}, FFX_ERR_UNSUPPORTED, "render_fwd_filtered: FFX_RENDER_TANGENT has no fp16 film"),
+    ("ffx_render_fwd", {}, {"flags": TAN, "mats": None}, FFX_ERR_ARG, "render_fwd: FFX_RENDER_TANGENT needs the device material table"),
+    ("ffx_render_fwd", {"n_mat_h": 3}, {"flags": TAN | _P3, "mats": None}, FFX_ERR_ARG, "render_fwd: FFX_RENDER_TANGENT needs the device material table"),
+    ("ffx_render_fwd_filtered", GAUSS, {"flags": TAN, "mats": None}, FFX_ERR_ARG, "render_fwd_filtered: FFX_RENDER_TANGENT needs the device material table"),
+    *[(f, GAUSS if "filtered" in f else {}, {"flags": TAN}, FFX_ERR_UNSUPPORTED, f"{f[4:]}: FFX_RENDER_TANGENT is served by ffx_render_fwd[_filtered] only")
+      for f in _OTHERS],
+    ("ffx_render_bwd", {}, {"flags": TAN | _abi.RENDER_GRAD_APPEARANCE | _abi.RENDER_GRAD_PRB | _P3}, FFX_ERR_UNSUPPORTED,
+     "render_bwd: FFX_RENDER_TANGENT is served by ffx_render_fwd[_filtered] only"),
+    # the other refusals of the served route still come first or in their order (nothing launches: the bvh info is refused)
+    ("ffx_render_fwd", {}, {"flags": TAN | _abi.RENDER_GRAD_APPEARANCE}, FFX_ERR_UNSUPPORTED, "render_fwd: FFX_RENDER_GRAD_APPEARANCE is served by"),
+    ("ffx_render_fwd", {}, {"flags": TAN, "tex": None}, FFX_ERR_ARG, "render_fwd: FFX_RENDER_TANGENT but tex (the tangent blocks) is NULL"),
+    ("ffx_render_fwd", {"proj.enabled": 0}, {"flags": TAN, "tex": None}, FFX_ERR_ARG, "render_fwd: FFX_RENDER_TANGENT but tex (the tangent blocks) is NULL"),
+    ("ffx_render_fwd", {}, {"flags": TAN, "img": None}, FFX_ERR_ARG, "render_fwd: bad argument"),
+    ("ffx_render_fwd", {"info.n_tris": 0}, {"flags": TAN}, FFX_ERR_ARG, "render_fwd: bad bvh info"),
+    ("ffx_render_fwd", {"info.n_tris": 0}, {"flags": TAN | _P3}, FFX_ERR_ARG, "render_fwd: bad bvh info"),
+    ("ffx_render_fwd_filtered", {"info.n_tris": 0, **GAUSS}, {"flags": TAN | _P3}, FFX_ERR_ARG, "render_fwd: bad bvh info"),
+    ("ffx_render_fwd", GAUSS, {"flags": TAN}, FFX_ERR_UNSUPPORTED, "render_fwd: the scene's reconstruction filter is not the box"),
+    ("ffx_render_fwd_filtered", {}, {"flags": TAN}, FFX_ERR_UNSUPPORTED, "render_fwd_filtered: rfilter must be FFX_RFILTER_GAUSSIAN"),
+    ("ffx_render_fwd", {}, {"flags": TAN | _abi.render_path(9, 5)}, FFX_ERR_ARG, "render_fwd: max_depth must be 2 .. 8"),
+    ("ffx_render_fwd", {"n_shapes": 0}, {"flags": TAN}, FFX_ERR_ARG, "render_fwd: n_shapes < 1"),
+    ("ffx_render_fwd", {"cam.width": 65536, "cam.height": 32768}, {"flags": TAN, "spp": 1}, FFX_ERR_UNSUPPORTED, "render_fwd: more than 2^31 pixels"),
+    # the last refusal in front of the primal's launches, as without the bit
+    ("ffx_render_fwd", {}, {"flags": TAN}, FFX_ERR_ARG, "render_fwd: blob without per-slot normals"),
+]
+
+
+@pytest.mark.parametrize("case", _CASES, ids=lambda c: f"{c[0][4:]}-{c[3]}-{c[4][:48]}")
+def test_refusals_before_any_launch(case, monkeypatch):
+    name, changes, arg_changes, rc, msg = case
+    for knob in ("FFX_TRAVERSAL", "FFX_WIDE"):
+        monkeypatch.delenv(knob, raising=False)
+    lib = _lib.api().lib
+    buf = np.zeros(64, np.float32)
+    addr = (buf.ctypes.data + 15) & ~15
+    eye = _abi.mat16(np.eye(4))
+    sd = _abi.SceneDesc()
+    sd.cam.to_world, sd.cam.camera_to_sample, sd.cam.width, sd.cam.height = eye, eye, 4, 4
+    sd.proj.to_world, sd.proj.camera_to_sample, sd.proj.tex_w, sd.proj.tex_h, sd.proj.tex_channels, sd.proj.enabled = eye, eye, 4, 4, 1, 1
+    sd.n_shapes = 1
+    info = _abi.BvhInfo(n_tris=1, n_nodes=1, max_depth=1, off_tq=64)
+    for key, v in changes.items():
+        obj, attr = (info, key[5:]) if key.startswith("info.") else (sd, key)
+        while "." in attr:
+            head, attr = attr.split(".", 1)
+            obj = getattr(obj, head)
+        setattr(obj, attr, v)
+    args = dict(bvh=addr, info=C.byref(info), sd=C.byref(sd), mats=addr, tex=addr, spp=4, seed=1, flags=0, img=addr, cache=addr, scratch=addr, gimg=addr,
+                gtex=addr, dot=addr, workspace=addr, part=1, scale_log2=0, acc=addr, s=None)
+    args.update(arg_changes)
+    got = getattr(lib, name)(*[args[p] for p in _PARAMS[name].split()])
+    err = (lib.ffx_last_error() or b"").decode()
+    assert got == rc, (got, err)
+    assert msg in err, err
+
+
+def _sd(S, stride, proj, bt=()):
+    sd = _abi.SceneDesc()
+    sd.n_shapes, sd.mat_stride = S, stride
+    sd.proj.enabled, sd.proj.tex_w, sd.proj.tex_h, sd.proj.tex_channels = int(proj), 5, 4, 1
+    sd.n_base_tex = len(bt)
+    for k, (h, w) in enumerate(bt):
+        sd.base_tex_h[k], sd.base_tex_w[k] = h, w
+    return sd
+
+
+def test_packing_of_the_tangent_blocks():
+    """[texture, tangent texture] (with a projector), then _abi.appearance_floats in the gradient block's layout, then the material block iff the
+    table has material columns"""
+    S, bt = 3, [(2, 3), (1, 2)]
+    sd = _sd(S, _abi.MAT_STRIDE, True, bt)
+    n_tex, n_app, n_mat = 20, _abi.appearance_floats(S, bt), _abi.material_floats(S)
+    assert n_app == 3 * S + 3 + 3 * (6 + 2) and n_mat == 11 * S
+    tex, dtex = torch.arange(20.0).reshape(4, 5, 1), 100 + torch.arange(20.0).reshape(4, 5, 1)
+    rows, spot = 200 + torch.arange(9.0).reshape(3, 3), torch.tensor([301.0, 302.0, 303.0])
+    b0, b1 = 400 + torch.arange(18.0).reshape(2, 3, 3), 500 + torch.arange(6.0).reshape(1, 2, 3)
+    mat = 600 + torch.arange(33.0).reshape(3, 11)
+    buf = ops.DeviceGeometry.pack_tangent(sd, tex, dtex, ops.AppearanceGrad(rows, spot, [b0, b1], mat))
+    assert buf.dtype == torch.float32 and buf.numel() == 2 * n_tex + n_app + n_mat
+    want = torch.cat([x.reshape(-1) for x in (tex, dtex, rows, spot, b0, b1, mat)])
+    assert torch.equal(buf, want)
+    # None is a zero tangent, field by field
+    buf = ops.DeviceGeometry.pack_tangent(sd, tex, None, ops.AppearanceGrad(None, spot, [None, b1], None))
+    want = torch.cat([tex.reshape(-1), torch.zeros(20 + 9), spot, torch.zeros(18), b1.reshape(-1), torch.zeros(33)])
+    assert torch.equal(buf, want)
+    assert torch.equal(ops.DeviceGeometry.pack_tangent(sd, tex, None, None)[n_tex:], torch.zeros(n_tex + n_app + n_mat))
+    # no projector: neither texture; a table of stride 3: no material block
+    sd = _sd(2, 3, False)
+    buf = ops.DeviceGeometry.pack_tangent(sd, None, None, ops.AppearanceGrad(torch.ones(2, 3), None, [], None))
+    assert buf.numel() == _abi.appearance_floats(2) == 9 and torch.equal(buf, torch.tensor([1.0] * 6 + [0.0] * 3))
+    with pytest.raises(ValueError):
+        ops.DeviceGeometry.pack_tangent(sd, None, None, ops.AppearanceGrad(None, None, [], torch.ones(2, 11)))
+    with pytest.raises(ValueError):
+        ops.DeviceGeometry.pack_tangent(_sd(2, 3, True), None, None, None)  # (the projector's texture is needed)
+    with pytest.raises(ValueError):
+        ops.DeviceGeometry.pack_tangent(_sd(2, 3, False), None, None, ops.AppearanceGrad(torch.ones(3, 3), None, [], None))
+
+
+class _NoGeometry:
+    def __getattr__(self, name):
+        raise AssertionError(f"the rule must be decided before the geometry is touched (geom.{name})")
+
+
+class _Served(Exception):
+    """the rules let the call through: it went on to read the scene's parameters"""
+
+
+class _Params:
+    _leaf_keys = frozenset(["mat-A.brdf_0.base_color.value", "mat-A.brdf_0.roughness.value", "mat-A.brdf_0.specular", "emit-Spot.intensity.value"])
+
+    def __getitem__(self, k):
+        raise _Served(k)
+
+
+def _stand_in(projector=True):
+    return types.SimpleNamespace(_params=_Params(), data=types.SimpleNamespace(projector=object() if projector else None), geom=_NoGeometry())
+
+
+def test_render_forward_refuses_unknown_keys_and_path_with_appearance_tangents():
+    sc = _stand_in()
+    with pytest.raises(KeyError) as e:
+        mi.render_forward(sc, None, {"mat-A.brdf_0.base_color.value": torch.ones(3), "PerspectiveCamera.to_world": torch.eye(4)})
+    msg = str(e.value)
+    assert "PerspectiveCamera.to_world" in msg and all(k in msg for k in sorted(sc._params._leaf_keys) + ["tex.data"])
+    with pytest.raises(KeyError) as e:
+        mi.render_forward(_stand_in(projector=False), None, {"tex.data": torch.ones(2, 2)})
+    assert "tex.data" in str(e.value)
+    path3 = mi.load_dict({"type": "path", "max_depth": 3})
+    with pytest.raises(ValueError, match="prb") as e:
+        mi.render_forward(sc, None, {"tex.data": torch.ones(2, 2), "mat-A.brdf_0.roughness.value": 1.0}, integrator=path3)
+    assert "mat-A.brdf_0.roughness.value" in str(e.value)
+    with pytest.raises(ValueError, match="prb"):
+        path3.render_forward(sc, None, {"emit-Spot.intensity.value": torch.ones(3)})
+    with pytest.raises(TypeError):
+        mi.render_forward(sc, None, {"tex.data": torch.ones(2, 2)}, integrator="prb")
+    with pytest.raises(TypeError):
+        mi.render_forward(sc, None, ["tex.data"])
+    with pytest.raises(NotImplementedError):
+        mi.render_forward(sc, None, {}, sensor=1)
+    # what is served goes on to the geometry: path + tex.data alone, prb, direct, max_depth 2
+    for it, tan in ((path3, {"tex.data": 0}), (mi.load_dict({"type": "prb", "max_depth": 3}), {"mat-A.brdf_0.specular": 0}),
+                    (mi.load_dict({"type": "direct"}), {"mat-A.brdf_0.specular": 0}), (mi.load_dict({"type": "path", "max_depth": 2}), {"mat-A.brdf_0.specular": 0})):
+        with pytest.raises(_Served):
+            mi.render_forward(sc, None, tan, integrator=it)
+
+
+# ---------------------------------------------------------------------------------------------- the float64 tangent
+def _copy(sd):
+    out = _abi.SceneDesc()
+    C.memmove(C.addressof(out), C.addressof(sd), C.sizeof(out))
+    return out
+
+
+def interior_material_tangent(rows, rng):
+    """a random tangent of the BSDF columns of the principled rows that central differences can follow: zero where the parameter sits at a bound of
+    [0, 1] (the forward skips the lobe there; the one-sided values are the dot-product identity's business) and on the eta column at eta = 1"""
+    rows = np.asarray(rows, np.float64)
+    d = np.zeros_like(rows)
+    if rows.shape[1] <= 3:
+        return d
+    pr = rows[:, scenes.MAT_COLUMN["model"]] != 0
+    for j in range(11):
+        col = rows[:, R0 + j]
+        ok = pr & ((col > 0.05) & (col < 0.95) if R0 + j != scenes.MAT_COLUMN["eta"] else col > 1.05)
+        d[ok, R0 + j] = rng.uniform(0.5, 1.5, int(ok.sum()))
+    return d
+
+
+def float64_tangent(world, sd, rows, tex, spp, seed, depth, rr, stddev, drows=None, dtex=None, dspot=None, h=5e-4):
+    """d image / d theta . dtheta in float64 on the paths, survival decisions and q_v of `rows` (prb's detached roulette): the five-point central
+    difference of ref_prb.render_fwd_frozen along drows (base colours and BSDF columns, [n_shapes, stride]) plus — the image is linear in both —
+    the image of the texture dtex with a dark spot and of the spot intensity dspot (float32 values) with a dark texture"""
+    rows = np.asarray(rows, np.float64)
+    tex = None if tex is None else np.asarray(tex, np.float64)
+
+    def img(r, s, t):
+        return ref_prb.render_fwd_frozen(*world, s, r, rows, t, spp, seed, depth, rr, gaussian_stddev=stddev)
+
+    out = np.zeros((sd.cam.height, sd.cam.width, 3))
+    if drows is not None and np.abs(drows).max() > 0:
+        d = np.asarray(drows, np.float64)
+        out += (-img(rows + 2 * h * d, sd, tex) + 8 * img(rows + h * d, sd, tex) - 8 * img(rows - h * d, sd, tex) + img(rows - 2 * h * d, sd, tex)) / (12 * h)
+    dark = _copy(sd)
+    for c in range(3):
+        dark.spot.intensity[c] = 0.0
+    if dtex is not None and tex is not None:
+        out += img(rows, dark, np.asarray(dtex, np.float64))
+    if dspot is not None:
+        lit = _copy(sd)
+        for c in range(3):
+            lit.spot.intensity[c] = float(dspot[c])
+            assert float(lit.spot.intensity[c]) == float(dspot[c]), "dspot must hold float32 values"
+        out += img(rows, lit, None if tex is None else np.zeros_like(tex))
+    return out
+
+
+def small_corner(W=6, H=6, tex=8):
+    """tests/test_material_grad_gpu.py's corner with every lobe of the floor active, small enough for the float64 restatement on the host"""
+    from tests import test_material_grad_gpu as tm
+
+    fb, wb, _ = tm.CASES["every_lobe"]
+    return tm.corner_scene(fb, wb, W=W, H=H, tex=tex)
+
+
+@pytest.mark.parametrize("depth,rr,stddev", [(2, 5, None), (3, 1, None), (3, 1, 0.5)])
+def test_float64_tangent_is_converged_in_h(depth, rr, stddev):
+    """halving h changes the reference by less than 1e-6 of its scale (the stencil's h^4 term and the differences' rounding are both below it), and the
+    exact linear parts are what differences of the texture and the intensity give"""
+    sc = small_corner()
+    pool, tris, shape, off, stride, nfr, alb = scenes.flatten(sc)
+    world = (pool.astype(np.float64), tris + off[shape][:, None], shape)
+    sd = scene_desc.scene_desc(sc, tex_channels=1, shadows=True)
+    if stddev is not None:
+        sd.rfilter = _abi.RFILTER_GAUSSIAN
+    rows = scenes.material_rows(sc).astype(np.float64)
+    rng = np.random.default_rng(1)
+    tex = rng.uniform(0, 1, (8, 8, 1))
+    drows = interior_material_tangent(rows, rng)
+    drows[:, :3] = rng.uniform(0.5, 1.5, (rows.shape[0], 3))
+    assert (drows[:, R0:R0 + 11] != 0).sum() >= 12
+    spp, seed = 4, 3
+    a = float64_tangent(world, sd, rows, tex, spp, seed, depth, rr, stddev, drows=drows, h=5e-4)
+    b = float64_tangent(world, sd, rows, tex, spp, seed, depth, rr, stddev, drows=drows, h=2.5e-4)
+    scale = np.abs(a).max()
+    print("depth", depth, "rr", rr, "stddev", stddev, ": max |T(h) - T(h/2)|", np.abs(a - b).max(), "scale", scale)
+    assert scale > 0 and np.abs(a - b).max() <= 1e-6 * scale
+    dtex = rng.uniform(-1, 1, (8, 8, 1))
+    dspot = np.array([0.5, 2.0, 1.25], np.float32)
+    lin = float64_tangent(world, sd, rows, tex, spp, seed, depth, rr, stddev, dtex=dtex, dspot=dspot)
+    hi = _copy(sd)
+    for c in range(3):
+        hi.spot.intensity[c] = float(sd.spot.intensity[c]) + float(dspot[c])
+    fd = (ref_prb.render_fwd_frozen(*world, hi, rows, rows, tex + dtex, spp, seed, depth, rr, gaussian_stddev=stddev)
+          - ref_prb.render_fwd_frozen(*world, sd, rows, rows, tex, spp, seed, depth, rr, gaussian_stddev=stddev))
+    print("linear parts: max |exact - difference|", np.abs(lin - fd).max(), "scale", np.abs(fd).max())
+    assert np.abs(fd).max() > 0 and np.abs(lin - fd).max() <= 1e-9 * np.abs(fd).max()

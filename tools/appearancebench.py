@@ -1,6 +1,7 @@
 """The appearance adjoint's cost: ms per 512^2 x 64-spp vocal-fold adjoint with FFX_RENDER_GRAD_APPEARANCE (the texture gradient's
 launches + k_render_bwd_appearance), next to the same render_bwd without it, and with FFX_RENDER_GRAD_MATERIAL as well (k_render_bwd_material: the
-BSDF parameters' adjoint), box and gaussian film.  HIP events around repeated calls of one pose on
+BSDF parameters' adjoint), box and gaussian film; beside them forward mode (render_jvp, DESIGN.md 4.5.3: primal + tangent image) and the render
+alone.  HIP events around repeated calls of one pose on
 one stream, after a warm-up.  Prints one JSON line.
 
     python tools/appearancebench.py [reps]
@@ -12,7 +13,7 @@ import sys
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from fireflies_amd import workloads  # noqa: E402
+from fireflies_amd import ops, workloads  # noqa: E402
 
 
 def _ms(fn, reps):
@@ -42,6 +43,13 @@ def main():
         out[f"render_bwd_ms_{film}"] = round(_ms(lambda: geom.render_bwd(sd, mats, 64, 1, gimg), reps), 3)
         out[f"appearance_bwd_ms_{film}"] = round(_ms(lambda: geom.render_bwd(sd, mats, 64, 1, gimg, appearance=True, tex=tex), reps), 3)
         out[f"material_bwd_ms_{film}"] = round(_ms(lambda: geom.render_bwd(sd, mats, 64, 1, gimg, appearance=True, tex=tex, material=True), reps), 3)
+        # forward mode: the whole call — the primal render and the tangent image — and the render alone, in the same run
+        S = sd.n_shapes
+        tan = ops.AppearanceGrad(torch.rand((S, 3), device="cuda"), torch.rand(3, device="cuda"), [torch.rand_like(t) for _, t in wl.mi_scene._base_tex],
+                                 torch.rand((S, 11), device="cuda") if sd.mat_stride == 16 else None)
+        dtex = torch.rand_like(tex)
+        out[f"render_fwd_ms_{film}"] = round(_ms(lambda: geom.render_fwd(sd, mats, tex, 64, 1), reps), 3)
+        out[f"jvp_ms_{film}"] = round(_ms(lambda: geom.render_jvp(sd, wl.mi_scene.albedo, tex, 64, 1, dtex=dtex, tangent=tan), reps), 3)
     print(json.dumps(out))
 
 
