@@ -17,6 +17,12 @@ def _c(t):
     return t if t.is_contiguous() else t.contiguous()
 
 
+def _tex3(t):
+    """a projector texture as the render calls take it: contiguous, [h, w] as [h, w, 1]"""
+    t = t if t.is_contiguous() else t.contiguous()
+    return t.unsqueeze(-1) if t.dim() == 2 else t
+
+
 class _ProjectRays(torch.autograd.Function):
     @staticmethod
     def forward(ctx, rays, KF):
@@ -167,9 +173,7 @@ class _Render(torch.autograd.Function):
         ctx.geom, ctx.sd, ctx.spp, ctx.seed = geom, sd, spp, seed
         ctx.depths = (max_depth, rr_depth)
         ctx.tex_shape = tex.shape
-        t = _c(tex)
-        if t.dim() == 2:
-            t = t.unsqueeze(-1)
+        t = _tex3(tex)
         ctx.cache = None
         ctx.albedo = albedo
         if tex.requires_grad and sd.proj.enabled:

@@ -1223,71 +1223,64 @@ def render(scene: Scene, params: SceneParameters = None, spp: int = 16, seed: in
         raise TypeError("render: integrator must come from mi.load_dict")
     if scene._params._leaves and torch.is_grad_enabled():
         return _render_appearance(scene, spp, seed, fp16, integrator)
-    if integrator is not None and integrator.max_depth > 2:
-        return _render_path(scene, spp, seed, fp16, integrator)
-    p = scene._params
-    tex = tex_in = None
-    ch = 3
-    if scene.data.projector is not None:
-        tex = p["tex.data"]
-        tex = tex_in = tex.t if isinstance(tex, _ArrayBase) else tex  # (tex_in: the tensor as assigned, before any conversion below)
-        if not isinstance(tex, torch.Tensor):
-            tex = torch.as_tensor(np.asarray(tex, np.float32))
-        if tex.device != scene.device:
-            tex = tex.to(scene.device)  # the reference uploads through numpy (vocalfold_scene.py:69)
-        ch = 1 if tex.dim() == 2 else int(tex.shape[-1])
-    scene.note_spp(spp)
-    sd = scene.scene_desc(tex_channels=ch)
+    sd, tex_in, tex = _scene_texture(scene, spp)
     if tex is None:
         tex = torch.zeros((1, 1, 1), device=scene.device)
-    elif tex.dtype != torch.float32:
-        tex = tex.float()
+    # max_depth > 2: the path integrator, on the caller's stream (the live texture, the scene's material table)
+    deep = integrator is not None and integrator.max_depth > 2
+    md, rr = (integrator.max_depth, integrator.rr_depth) if deep else (2, 5)
     if tex.requires_grad and torch.is_grad_enabled():
         scene.render_paths["autograd"] += 1
-        img = Fn.render(tex, scene.geom, sd, scene.materials_arg(sd), spp, seed, fp16)
+        img = Fn.render(tex, scene.geom, sd, scene.materials_arg(sd), spp, seed, fp16, md, rr)
     else:  # nothing to differentiate: straight to the kernel (autograd.Function.apply costs ~80 us of host time per call)
         mats = scene.materials_arg(sd)
-        slot = scene._render_stream(tex_in, mats) if tex_in is not None else None
+        slot = scene._render_stream(tex_in, mats) if tex_in is not None and not deep else None
         if slot is not None:  # beside the previous render, on the scene's other render stream
             rs, done, priv = slot
             scene.render_paths["two_stream"] += 1
             with torch.cuda.stream(rs):
-                img = scene.geom.render_fwd(sd, mats, priv.unsqueeze(-1) if priv.dim() == 2 else priv, int(spp), int(seed), bool(fp16))
+                img = scene.geom.render_fwd(sd, mats, Fn._tex3(priv), int(spp), int(seed), bool(fp16))
                 done.record(rs)
             return _RenderedXf(img, done)
         scene.render_paths["caller_stream"] += 1
-        t = tex if tex.is_contiguous() else tex.contiguous()
-        img = scene.geom.render_fwd(sd, mats, t.unsqueeze(-1) if t.dim() == 2 else t, int(spp), int(seed), bool(fp16))
+        img = scene.geom.render_fwd(sd, mats, Fn._tex3(tex), int(spp), int(seed), bool(fp16), max_depth=md, rr_depth=rr)
     return TensorXf(img)
 
 
-def _render_path(scene, spp, seed, fp16, integrator):
-    """mi.render with max_depth > 2: the path integrator on the caller's stream (the live texture, the scene's material table)"""
-    p = scene._params
-    tex = None
+def _scene_texture(scene, spp):
+    """what every render entry point starts with -> (the scene description of a render at `spp`, the projector's texture as assigned — what
+    Scene._render_stream knows it by —, and as a float32 tensor on the scene's device); None, None without a projector"""
+    tex = tex_in = None
     ch = 3
     if scene.data.projector is not None:
-        tex = p["tex.data"]
-        tex = tex.t if isinstance(tex, _ArrayBase) else tex
+        tex = scene._params["tex.data"]
+        tex = tex_in = tex.t if isinstance(tex, _ArrayBase) else tex  # (tex_in: before any conversion below)
         if not isinstance(tex, torch.Tensor):
             tex = torch.as_tensor(np.asarray(tex, np.float32))
         if tex.device != scene.device:
-            tex = tex.to(scene.device)
+            tex = tex.to(scene.device)  # the reference uploads through numpy (vocalfold_scene.py:69)
+        if tex.dtype != torch.float32:
+            tex = tex.float()
         ch = 1 if tex.dim() == 2 else int(tex.shape[-1])
     scene.note_spp(spp)
-    sd = scene.scene_desc(tex_channels=ch)
-    if tex is None:
-        tex = torch.zeros((1, 1, 1), device=scene.device)
-    elif tex.dtype != torch.float32:
-        tex = tex.float()
-    mats = scene.materials_arg(sd)
-    md, rr = integrator.max_depth, integrator.rr_depth
-    if tex.requires_grad and torch.is_grad_enabled():
-        scene.render_paths["autograd"] += 1
-        return TensorXf(Fn.render(tex, scene.geom, sd, mats, spp, seed, fp16, max_depth=md, rr_depth=rr))
-    scene.render_paths["caller_stream"] += 1
-    t = tex if tex.is_contiguous() else tex.contiguous()
-    return TensorXf(scene.geom.render_fwd(sd, mats, t.unsqueeze(-1) if t.dim() == 2 else t, int(spp), int(seed), bool(fp16), max_depth=md, rr_depth=rr))
+    return scene.scene_desc(tex_channels=ch), tex_in, tex
+
+
+def _leaf_kind(scene, k):
+    """a key of mi.render's appearance and BSDF gradients (SceneParameters._leaf_keys) -> ("mat", rows) | ("base_tex", index) |
+    ("bsdf", rows, column of the material block, parameter name) | ("spot",); rows: the material's shapes.  A `specular` key has eta's column:
+    what it contributes there is _eta_factor's business"""
+    base, _, rest = k.partition(".")
+    if rest == "brdf_0.base_color.value":
+        return ("mat", tuple(scene._material_meshes[base]))
+    if rest == "brdf_0.base_color.data":
+        return ("base_tex", [n for n, _ in scene._base_tex].index(base))
+    if rest.startswith("brdf_0."):  # a BSDF parameter: its column of the material block (scenes.MAT_COLUMN, from roughness on)
+        name = rest[len("brdf_0."):]
+        name = name[:-len(".value")] if name.endswith(".value") else name
+        col = scenes.MAT_COLUMN["eta" if name == "specular" else name] - scenes.MAT_COLUMN["roughness"]
+        return ("bsdf", tuple(scene._material_meshes[base]), col, name)
+    return ("spot",)
 
 
 def _forward_keys(scene):
@@ -1305,8 +1298,8 @@ def _eta_owner(scene, mat):
     return src
 
 
-def _eta_factor(scene, k, base, name, value, rows, owner):
-    """what a `specular` / `eta` key `k` of material `base` contributes to the eta column of its rows — one rule for mi.render's backward and for
+def _eta_factor(scene, k, name, value, rows, owner):
+    """what a `specular` / `eta` key `k` contributes to the eta column of its rows — one rule for mi.render's backward and for
     mi.render_forward.  owner: the key that drives the rows' eta.  0 when that is the other key; `specular` chains with
     scenes.specular_to_eta_grad(value) (at 0: the finite limit the column's own limit at eta = 1 pairs with); `eta` counts 1, except at eta = 1,
     where the column holds that limit and d / d eta itself is 0"""
@@ -1339,18 +1332,8 @@ def render_forward(scene: Scene, params: SceneParameters = None, tangents: dict 
     if md > 2 and integrator.type != "prb" and set(tangents) - {"tex.data"}:
         raise ValueError("render_forward: under the 'path' integrator with max_depth > 2 only a tangent of tex.data is served; use the 'prb' integrator "
                          "(mi.load_dict({'type': 'prb', ...})) for " + ", ".join(sorted(set(tangents) - {"tex.data"})))
-    p = scene._params
-    tex = None
-    ch = 3
-    if scene.data.projector is not None:
-        tex = p["tex.data"]
-        tex = tex.t if isinstance(tex, _ArrayBase) else tex
-        if not isinstance(tex, torch.Tensor):
-            tex = torch.as_tensor(np.asarray(tex, np.float32))
-        tex = tex.detach().to(device=scene.device, dtype=torch.float32)
-        ch = 1 if tex.dim() == 2 else int(tex.shape[-1])
-    scene.note_spp(spp)
-    sd = scene.scene_desc(tex_channels=ch)
+    sd, _, tex = _scene_texture(scene, spp)
+    tex = tex.detach() if tex is not None else None  # (no 1 x 1 x 1 stand-in: render_jvp packs no texture without a projector)
     S = int(sd.n_shapes)
     dev = scene.device
 
@@ -1365,42 +1348,35 @@ def render_forward(scene: Scene, params: SceneParameters = None, tangents: dict 
 
     rows = torch.zeros((S, 3), device=dev)
     spot = torch.zeros(3, device=dev)
-    names = [n for n, _ in scene._base_tex]
-    base_tex = [None] * len(names)
+    base_tex = [None] * len(scene._base_tex)
     principled = int(sd.mat_stride) == scenes.MAT_STRIDE
     material = torch.zeros((S, 11), device=dev) if principled else None
     dtex = None
     for k, v in tangents.items():
-        base, _, rest = k.partition(".")
         if k == "tex.data":
             dtex = as_t(v, tex.numel(), k)
-        elif rest == "brdf_0.base_color.value":
-            rows[list(scene._material_meshes[base])] += as_t(v, 3, k)
-        elif rest == "brdf_0.base_color.data":
-            i = names.index(base)
-            base_tex[i] = as_t(v, scene._base_tex[i][1].numel(), k)
-        elif rest.startswith("brdf_0."):
-            name = rest[len("brdf_0."):]
-            name = name[:-len(".value")] if name.endswith(".value") else name
+            continue
+        kind = _leaf_kind(scene, k)
+        if kind[0] == "mat":
+            rows[list(kind[1])] += as_t(v, 3, k)
+        elif kind[0] == "base_tex":
+            base_tex[kind[1]] = as_t(v, scene._base_tex[kind[1]][1].numel(), k)
+        elif kind[0] == "bsdf":
+            _, mrows, col, name = kind
+            base = k.partition(".")[0]
             if not principled or not scene._material_principled.get(base, False):
                 continue  # (a diffuse material's `specular` / `roughness`: no part of the render)
             fac = 1.0
-            mrows = list(scene._material_meshes[base])
             if name in ("specular", "eta"):
-                sv = p[k]
+                sv = scene._params[k]
                 sv = float(torch.as_tensor(sv.t if isinstance(sv, _ArrayBase) else sv).detach().reshape(-1)[0])
                 # (the owner: Scene._eta_src, or — nothing assigned yet, which a leaf of the backward never is — what the scene file gave)
-                fac = _eta_factor(scene, k, base, name, sv, mrows, _eta_owner(scene, base))
-            col = scenes.MAT_COLUMN["eta" if name == "specular" else name] - scenes.MAT_COLUMN["roughness"]
-            material[mrows, col] += as_t(v, 1, k)[0] * fac
+                fac = _eta_factor(scene, k, name, sv, mrows, _eta_owner(scene, base))
+            material[list(mrows), col] += as_t(v, 1, k)[0] * fac
         else:
             spot += as_t(v, 3, k)
-    t3 = None
-    if tex is not None:
-        t3 = (tex if tex.is_contiguous() else tex.contiguous())
-        t3 = t3.unsqueeze(-1) if t3.dim() == 2 else t3
     scene.render_paths["caller_stream"] += 1
-    img, dimg = scene.geom.render_jvp(sd, scene.albedo, t3, int(spp), int(seed), dtex=dtex, tangent=ops.AppearanceGrad(rows, spot, base_tex, material),
+    img, dimg = scene.geom.render_jvp(sd, scene.albedo, Fn._tex3(tex) if tex is not None else None, int(spp), int(seed), dtex=dtex, tangent=ops.AppearanceGrad(rows, spot, base_tex, material),
                                       max_depth=md, rr_depth=rr)
     return TensorXf(img), TensorXf(dimg)
 
@@ -1413,9 +1389,7 @@ class _AppearanceRender(torch.autograd.Function):
     @staticmethod
     def forward(ctx, tex, scene, sd, mats, spp, seed, fp16, kinds, depths, *leaves):
         geom = scene.geom
-        t = tex.detach()
-        t = (t if t.is_contiguous() else t.contiguous())
-        t = t.unsqueeze(-1) if t.dim() == 2 else t
+        t = Fn._tex3(tex.detach())
         ctx.geom, ctx.sd, ctx.spp, ctx.seed, ctx.kinds, ctx.depths = geom, sd, spp, seed, kinds, depths
         ctx.tex, ctx.tex_shape = t, tex.shape
         ctx.mats = mats.clone() if mats is not None else None  # (the scene's table is rewritten in place by the next randomisation)
@@ -1464,43 +1438,21 @@ def _render_appearance(scene, spp, seed, fp16, integrator):
                          "The scene holds parameters that require grad: " + ", ".join(sorted(scene._params._leaves)))
     if ops.deterministic_mode():
         raise ValueError("mi.render: the gradients of base colours, spot intensity and BSDF parameters have no deterministic adjoint (FFX_DETERMINISTIC=1)")
-    p = scene._params
-    tex = None
-    ch = 3
-    if scene.data.projector is not None:
-        tex = p["tex.data"]
-        tex = tex.t if isinstance(tex, _ArrayBase) else tex
-        if not isinstance(tex, torch.Tensor):
-            tex = torch.as_tensor(np.asarray(tex, np.float32))
-        if tex.device != scene.device:
-            tex = tex.to(scene.device)
-        ch = 1 if tex.dim() == 2 else int(tex.shape[-1])
-    scene.note_spp(spp)
-    sd = scene.scene_desc(tex_channels=ch)
+    sd, _, tex = _scene_texture(scene, spp)
     if tex is None:
         tex = torch.zeros((1, 1, 1), device=scene.device)
-    elif tex.dtype != torch.float32:
-        tex = tex.float()
-    names = [n for n, _ in scene._base_tex]
     kinds, leaves = [], []
-    for k, leaf in p._leaves.items():
-        base, _, rest = k.partition(".")
-        if rest == "brdf_0.base_color.value":
-            kinds.append(("mat", tuple(scene._material_meshes[base])))
-        elif rest == "brdf_0.base_color.data":
-            kinds.append(("base_tex", names.index(base)))
-        elif rest.startswith("brdf_0."):  # a BSDF parameter: its column of the material block (scenes.MAT_COLUMN, from roughness on)
-            rows = tuple(scene._material_meshes[base])
-            name = rest[len("brdf_0."):]
-            name = name[:-len(".value")] if name.endswith(".value") else name
+    for k, leaf in scene._params._leaves.items():
+        kind = _leaf_kind(scene, k)
+        if kind[0] == "bsdf":
+            _, rows, col, name = kind
             fac = 1.0
             if name in ("specular", "eta"):
                 # (the owner is the key that wrote the row's eta last; the other key, or a diffuse material's `specular`, is no part of the render)
-                fac = _eta_factor(scene, k, base, name, leaf.detach().reshape(-1)[0], rows, scene._eta_src.get(base + ".brdf_0.eta"))
-            col = scenes.MAT_COLUMN["eta" if name == "specular" else name] - scenes.MAT_COLUMN["roughness"]
+                fac = _eta_factor(scene, k, name, leaf.detach().reshape(-1)[0], rows, scene._eta_src.get(k.partition(".")[0] + ".brdf_0.eta"))
             kinds.append(("bsdf", (rows, col, fac)))
         else:
-            kinds.append(("spot", None))
+            kinds.append((kind[0], kind[1] if len(kind) > 1 else None))
         leaves.append(leaf)
     depths = (2, 5) if integrator is None else (int(integrator.max_depth), int(integrator.rr_depth))
     return TensorXf(_AppearanceRender.apply(tex, scene, sd, scene.materials_arg(sd), int(spp), int(seed), bool(fp16), kinds, depths, *leaves))

@@ -4,6 +4,7 @@ PyTorch is used for device memory and the current HIP stream; every arithmetic s
 libffx_hip.so.  All functions require contiguous tensors on a HIP device and raise otherwise.
 """
 import ctypes as C
+import math
 import os
 from typing import NamedTuple
 
@@ -419,10 +420,14 @@ def _check_materials(sd, albedo):
         return None
     if albedo is None:
         raise ValueError("no material table: pass the device tensor or put the rows into the scene description (scene_desc.set_host_materials)")
+    _check_table(sd, albedo)
+    return _dev(albedo, name="albedo")
+
+
+def _check_table(sd, albedo):
     ms = int(sd.mat_stride) or 3
     if albedo.dim() != 2 or albedo.shape[1] != ms or albedo.shape[0] < sd.n_shapes:
         raise ValueError(f"material table {tuple(albedo.shape)} does not match the scene description (n_shapes {sd.n_shapes}, mat_stride {ms})")
-    return _dev(albedo, name="albedo")
 
 
 # ------------------------------------------------------------------ K5..K9
@@ -547,6 +552,25 @@ class AppearanceGrad(NamedTuple):
     spot: torch.Tensor
     base_tex: list
     material: torch.Tensor = None
+
+
+def appearance_blocks(sd, material, buf, start):
+    """the gradient / tangent blocks of a render of `sd` (include/ffx.h: [n_shapes][3] rows, [3] spot, [h][w][3] per base-colour texture, then — with
+    `material` — [n_shapes][11]) as views into the flat float buffer `buf` from float `start` on: the one place that knows their order and offsets
+    -> (an AppearanceGrad of the views, the floats they cover: _abi.appearance_floats [+ _abi.material_floats])"""
+    S, o = int(sd.n_shapes), int(start)
+    shapes = [(S, 3), (3,)] + [(int(sd.base_tex_h[k]), int(sd.base_tex_w[k]), 3) for k in range(sd.n_base_tex)] + [(S, _abi.RENDER_MATERIAL_COLS)] * bool(material)
+    views = []
+    for shape in shapes:
+        n = math.prod(shape)
+        views.append(buf[o:o + n].view(shape))
+        o += n
+    mat = views.pop() if material else None
+    return AppearanceGrad(views[0], views[1], views[2:], mat), o - int(start)
+
+
+# what a render entry point does about a film with a reconstruction filter (sd.rfilter): DeviceGeometry._launch
+_TWIN, _SLOT, _OWN = 0, 1, 2
 
 
 def _lane_kernels():
@@ -938,6 +962,31 @@ class DeviceGeometry:
     def _timed(self, name):
         return _EventPair(self.timing, name)
 
+    def _launch(self, timer, name, film, blob, sd, lead, spp, seed, flags, *rest):
+        """every render call that reads a blob: `name`(blob, info, sd, *lead, spp, seed, flags, *rest, [scratch,] stream) inside the `timer` bracket, then
+        the release.  lead: (materials,) for the adjoints, (materials, texture) for the forwards.  film: what `name` does about a film with a
+        reconstruction filter (sd.rfilter) — _TWIN: name + "_filtered" serves it and takes a scratch tensor in front of the stream; _SLOT: `name`
+        serves both films and always has that argument, None for a box film; _OWN: `name` serves both films from the arguments the caller gives"""
+        if film != _OWN and sd.rfilter:
+            if film == _TWIN:
+                name += "_filtered"
+            # (caching allocator, stream-ordered: renders on two streams never share one)
+            rest += (_dev(torch.empty(render_filter_bytes(sd), dtype=torch.uint8, device=self.device), torch.uint8),)
+        elif film == _SLOT:
+            rest += (None,)
+        with self._timed(timer):
+            self._call(name, _dev(blob, torch.uint8), C.byref(self.info), C.byref(sd), *lead, int(spp), int(seed) & 0xFFFFFFFF, flags, *rest, _stream(self._didx))
+        self._release()
+
+    def _launch_fwd(self, timer, blob, sd, mats_arg, tex_arg, spp, seed, flags, img_arg):
+        """ffx_render_fwd[_filtered]: the render (render_fwd: direct light or path bits) and, with FFX_RENDER_TANGENT, the forward mode (render_jvp)"""
+        self._launch(timer, "ffx_render_fwd", _TWIN, blob, sd, (mats_arg, tex_arg), spp, seed, flags, img_arg)
+
+    def _launch_bwd(self, blob, sd, mats_arg, spp, seed, flags, gimg_arg, gtex_arg):
+        """ffx_render_bwd[_filtered]: the re-tracing adjoint (render_bwd: direct light or path bits) and, with FFX_RENDER_GRAD_APPEARANCE, the one that
+        also yields the appearance blocks (_render_bwd_leaves)"""
+        self._launch("render_bwd", "ffx_render_bwd", _TWIN, blob, sd, (mats_arg,), spp, seed, flags, gimg_arg, gtex_arg)
+
     def render_fwd(self, sd, albedo, tex, spp, seed=0, fp16=False, cache=None, sparse_adjoint=False, cache_zeroed=False, keep_dropped=False, img_out=None,
                    max_depth=2, rr_depth=5):
         """K8.  With `cache` (a uint8 tensor of render_cache_bytes(...) bytes) the kernel also stores one
@@ -958,60 +1007,17 @@ class DeviceGeometry:
         if tuple(img.shape) != (H, W, 3) or img.dtype != (torch.float16 if fp16 else torch.float32) or not img.is_contiguous():
             raise ValueError("img_out must be a contiguous [H, W, 3] tensor of the film's type")
         blob = self.blob  # (acquire first: the flag below speaks about the blob this call reads)
-        if path:
-            return self._render_path_fwd(blob, sd, mats_arg, tex, spp, seed, fp16, img, path)
-        flags = int(bool(fp16)) | self._apex_flag(apex_key(sd))
-        if sd.rfilter:  # a reconstruction filter that spreads samples over neighbouring pixels: its own entry point and a scratch area
-            scratch = torch.empty(render_filter_bytes(sd), dtype=torch.uint8, device=self.device)  # (caching allocator, stream-ordered: renders on two streams never share one)
-            if cache is not None:  # ... and the per-sample records of its adjoint (ABI 7)
-                if cache.numel() < render_cache_bytes_sd(sd, spp):
-                    raise ValueError("cache tensor too small")
-                flags |= (_abi.RENDER_SPARSE_ADJOINT if sparse_adjoint else 0) | (_abi.RENDER_CACHE_ZEROED if cache_zeroed else 0) | (_abi.RENDER_CACHE_KEEP_DROPPED if keep_dropped else 0)
-                with self._timed("render_fwd"):
-                    self._call("ffx_render_fwd_cache_filtered", _dev(blob, torch.uint8), C.byref(self.info), C.byref(sd), mats_arg,
-                               _dev(tex, name="tex") if tex is not None else None, int(spp), int(seed) & 0xFFFFFFFF, flags, _dev(img, img.dtype),
-                               _dev(cache, torch.uint8, "cache"), _dev(scratch, torch.uint8), _stream(self._didx))
-                self._release()
-                return img
-            with self._timed("render_fwd"):
-                self._call("ffx_render_fwd_filtered", _dev(blob, torch.uint8), C.byref(self.info), C.byref(sd), mats_arg,
-                           _dev(tex, name="tex") if tex is not None else None, int(spp), int(seed) & 0xFFFFFFFF, flags, _dev(img, img.dtype), _dev(scratch, torch.uint8),
-                           _stream(self._didx))
-            self._release()
+        # (the path integrator walks per lane and reads neither apex records nor tile bins: it claims nothing about the blob's apex areas, and rewrites none)
+        flags = int(bool(fp16)) | (path if path else self._apex_flag(apex_key(sd)))
+        if cache is None:
+            self._launch_fwd("render_fwd", blob, sd, mats_arg, _dev(tex, name="tex") if tex is not None else None, spp, seed, flags, _dev(img, img.dtype))
             return img
-        if cache is not None:
-            if cache.numel() < render_cache_bytes_sd(sd, spp):
-                raise ValueError("cache tensor too small")
-            flags |= (_abi.RENDER_SPARSE_ADJOINT if sparse_adjoint else 0) | (_abi.RENDER_CACHE_ZEROED if cache_zeroed else 0) | (_abi.RENDER_CACHE_KEEP_DROPPED if keep_dropped else 0)
-            with self._timed("render_fwd"):
-                self._call(
-                    "ffx_render_fwd_cache", _dev(blob, torch.uint8), C.byref(self.info), C.byref(sd), mats_arg,
-                    _dev(tex, name="tex") if tex is not None else None, int(spp), int(seed) & 0xFFFFFFFF, flags,
-                    _dev(img, img.dtype), _dev(cache, torch.uint8, "cache"), _stream(self._didx),
-                )
-            self._release()
-            return img
-        with self._timed("render_fwd"):
-          self._call(
-            "ffx_render_fwd", _dev(blob, torch.uint8), C.byref(self.info), C.byref(sd), mats_arg,
-            _dev(tex, name="tex") if tex is not None else None, int(spp), int(seed) & 0xFFFFFFFF, flags, _dev(img, img.dtype), _stream(self._didx),
-          )
-        self._release()
-        return img
-
-    def _render_path_fwd(self, blob, sd, mats_arg, tex, spp, seed, fp16, img, path):
-        """the path integrator's forward (ffx_render_fwd[_filtered] with FFX_RENDER_PATH bits): per-lane walks that read neither apex records nor
-        tile bins — nothing is claimed about the blob's apex areas, and none is rewritten"""
-        tex_arg = _dev(tex, name="tex") if tex is not None else None
-        with self._timed("render_fwd"):
-            if sd.rfilter:
-                scratch = torch.empty(render_filter_bytes(sd), dtype=torch.uint8, device=self.device)
-                self._call("ffx_render_fwd_filtered", _dev(blob, torch.uint8), C.byref(self.info), C.byref(sd), mats_arg, tex_arg, int(spp), int(seed) & 0xFFFFFFFF,
-                           int(bool(fp16)) | path, _dev(img, img.dtype), _dev(scratch, torch.uint8), _stream(self._didx))
-            else:
-                self._call("ffx_render_fwd", _dev(blob, torch.uint8), C.byref(self.info), C.byref(sd), mats_arg, tex_arg, int(spp), int(seed) & 0xFFFFFFFF,
-                           int(bool(fp16)) | path, _dev(img, img.dtype), _stream(self._didx))
-        self._release()
+        # ... and the records of the adjoint: one footprint per pixel, under a filtered film every sample's (ABI 7)
+        if cache.numel() < render_cache_bytes_sd(sd, spp):
+            raise ValueError("cache tensor too small")
+        flags |= (_abi.RENDER_SPARSE_ADJOINT if sparse_adjoint else 0) | (_abi.RENDER_CACHE_ZEROED if cache_zeroed else 0) | (_abi.RENDER_CACHE_KEEP_DROPPED if keep_dropped else 0)
+        self._launch("render_fwd", "ffx_render_fwd_cache", _TWIN, blob, sd, (mats_arg, _dev(tex, name="tex") if tex is not None else None), spp, seed, flags,
+                     _dev(img, img.dtype), _dev(cache, torch.uint8, "cache"))
         return img
 
     def render_fwd_adjoint(self, sd, albedo, tex, spp, seed, gimg, out=None, dot_out=None, fp16=False, sparse_adjoint=False, img_out=None, max_depth=2):
@@ -1034,18 +1040,9 @@ class DeviceGeometry:
             raise ValueError(f"dot_out must hold {_abi.ADJOINT_DOT_SLOTS} float32 partial sums (the caller zeroes and sums them)")
         blob = self.blob
         flags = int(bool(fp16)) | (_abi.RENDER_SPARSE_ADJOINT if sparse_adjoint else 0) | self._apex_flag(apex_key(sd))
-        if sd.rfilter:  # the filtered film: weights -> G, ONE render launch with the adjoint folded in, gather (ffx_render_fwd_adjoint_filtered)
-            scratch = torch.empty(render_filter_bytes(sd), dtype=torch.uint8, device=self.device)
-            with self._timed("render_fwd"):
-                self._call("ffx_render_fwd_adjoint_filtered", _dev(blob, torch.uint8), C.byref(self.info), C.byref(sd), mats_arg, _dev(tex, name="tex"), int(spp),
-                           int(seed) & 0xFFFFFFFF, flags, _dev(img, img.dtype), _dev(gimg, name="gimg"), _dev(gtex), _dev(scratch, torch.uint8), _stream(self._didx))
-            self._release()
-            return img, gtex
-        with self._timed("render_fwd"):
-            self._call("ffx_render_fwd_adjoint", _dev(blob, torch.uint8), C.byref(self.info), C.byref(sd), mats_arg, _dev(tex, name="tex"), int(spp),
-                       int(seed) & 0xFFFFFFFF, flags, _dev(img, img.dtype), _dev(gimg, name="gimg"), _dev(gtex), _dev(dot_out) if dot_out is not None else None,
-                       _stream(self._didx))
-        self._release()
+        # (the filtered film — weights -> G, ONE render launch with the adjoint folded in, gather — has its scratch where the box film has dot_out)
+        self._launch("render_fwd", "ffx_render_fwd_adjoint", _TWIN, blob, sd, (mats_arg, _dev(tex, name="tex")), spp, seed, flags,
+                     _dev(img, img.dtype), _dev(gimg, name="gimg"), _dev(gtex), *(() if sd.rfilter else (_dev(dot_out) if dot_out is not None else None,)))
         return img, gtex
 
     def render_bwd_cached(self, sd, albedo, cache, spp, gimg, out=None, img=None, dot_out=None, seed=None, max_depth=2):
@@ -1103,12 +1100,8 @@ class DeviceGeometry:
         mats_arg = _check_materials(sd, albedo)
         blob = self.blob
         flags = self._apex_flag(apex_key(sd))
-        scratch = torch.empty(render_filter_bytes(sd), dtype=torch.uint8, device=self.device) if sd.rfilter else None
-        with self._timed("render_bwd"):
-            self._call("ffx_render_bwd_det_part", _dev(blob, torch.uint8), C.byref(self.info), C.byref(sd), mats_arg, int(spp), int(seed) & 0xFFFFFFFF, flags,
-                       _dev(gimg, name="gimg"), int(part), int(scale_log2), C.c_void_p(acc.data_ptr()), _dev(scratch, torch.uint8) if scratch is not None else None,
-                       _stream(self._didx))
-        self._release()
+        self._launch("render_bwd", "ffx_render_bwd_det_part", _SLOT, blob, sd, (mats_arg,), spp, seed, flags,
+                     _dev(gimg, name="gimg"), int(part), int(scale_log2), C.c_void_p(acc.data_ptr()))
 
     def render_bwd(self, sd, albedo, spp, seed, gimg, deterministic=None, max_depth=2, rr_depth=5, appearance=False, tex=None, material=False):
         """the re-tracing adjoint.  deterministic (default: FFX_DETERMINISTIC=1 in the environment): ffx_render_bwd_det — bitwise
@@ -1122,7 +1115,14 @@ class DeviceGeometry:
         if material and not appearance:
             raise ValueError("render_bwd(material=True) needs appearance=True (the material block extends the appearance adjoint)")
         if appearance:
-            return self._render_bwd_appearance(sd, albedo, spp, seed, gimg, deterministic, max_depth, tex, material)
+            if max_depth != 2:
+                path_flags(max_depth)  # (the range check's message first)
+                raise ValueError("render_bwd(appearance=True): the appearance gradients are served at max_depth 2 (direct light) only")
+            if deterministic is None:
+                deterministic = deterministic_mode()
+            if deterministic:
+                raise ValueError("render_bwd(appearance=True) has no deterministic adjoint (FFX_DETERMINISTIC / deterministic=True)")
+            return self._render_bwd_leaves(sd, albedo, spp, seed, gimg, tex, material, 0, "render_bwd(appearance=True)")
         path = path_flags(max_depth, rr_depth) if max_depth != 2 else 0
         if deterministic is None:
             deterministic = deterministic_mode()
@@ -1131,57 +1131,19 @@ class DeviceGeometry:
         gtex = torch.zeros((sd.proj.tex_h, sd.proj.tex_w, sd.proj.tex_channels), dtype=torch.float32, device=self.device)
         mats_arg = _check_materials(sd, albedo)
         blob = self.blob
-        if path:  # (per-lane walks: no apex records are read or written)
-            scratch = torch.empty(render_filter_bytes(sd), dtype=torch.uint8, device=self.device) if sd.rfilter else None
-            with self._timed("render_bwd"):
-                if scratch is not None:
-                    self._call("ffx_render_bwd_filtered", _dev(blob, torch.uint8), C.byref(self.info), C.byref(sd), mats_arg, int(spp), int(seed) & 0xFFFFFFFF, path,
-                               _dev(gimg, name="gimg"), _dev(gtex), _dev(scratch, torch.uint8), _stream(self._didx))
-                else:
-                    self._call("ffx_render_bwd", _dev(blob, torch.uint8), C.byref(self.info), C.byref(sd), mats_arg, int(spp), int(seed) & 0xFFFFFFFF, path,
-                               _dev(gimg, name="gimg"), _dev(gtex), _stream(self._didx))
-            self._release()
-            return gtex
         if deterministic:
             if _lane_kernels():
                 raise ValueError("the per-lane kernels (FFX_TRAVERSAL=lane) have no deterministic adjoint")
             flags = self._apex_flag(apex_key(sd))
-            wsb = api().lib.ffx_render_bwd_det_bytes(C.byref(sd))
-            work = torch.empty(wsb, dtype=torch.uint8, device=self.device)
-            with self._timed("render_bwd"):
-                self._call("ffx_render_bwd_det", _dev(blob, torch.uint8), C.byref(self.info), C.byref(sd), mats_arg, int(spp), int(seed) & 0xFFFFFFFF, flags,
-                           _dev(gimg, name="gimg"), _dev(gtex), _dev(work, torch.uint8), _stream(self._didx))
-            self._release()
+            work = torch.empty(api().lib.ffx_render_bwd_det_bytes(C.byref(sd)), dtype=torch.uint8, device=self.device)  # (a filtered film's scratch is part of it)
+            self._launch("render_bwd", "ffx_render_bwd_det", _OWN, blob, sd, (mats_arg,), spp, seed, flags, _dev(gimg, name="gimg"), _dev(gtex), _dev(work, torch.uint8))
             return gtex
-        # (ABI 7: the re-tracing adjoints take FFX_RENDER_APEX_READY like the renders.  Before, they always re-ran the pre-pass — and rewrote the
-        # tile bins under the eyes of renders of the same pose on the scene's other render stream)
-        flags = self._apex_flag(apex_key(sd))
-        if sd.rfilter:
-            scratch = torch.empty(render_filter_bytes(sd), dtype=torch.uint8, device=self.device)
-            with self._timed("render_bwd"):
-                self._call("ffx_render_bwd_filtered", _dev(blob, torch.uint8), C.byref(self.info), C.byref(sd), mats_arg, int(spp), int(seed) & 0xFFFFFFFF, flags,
-                           _dev(gimg, name="gimg"), _dev(gtex), _dev(scratch, torch.uint8), _stream(self._didx))
-            self._release()
-            return gtex
-        with self._timed("render_bwd"):
-            self._call(
-                "ffx_render_bwd", _dev(blob, torch.uint8), C.byref(self.info), C.byref(sd), mats_arg, int(spp),
-                int(seed) & 0xFFFFFFFF, flags, _dev(gimg, name="gimg"), _dev(gtex), _stream(self._didx),
-            )
-        self._release()
+        # (the path replay walks per lane: no apex records are read or written.  ABI 7: the direct-light adjoints take FFX_RENDER_APEX_READY like the
+        # renders.  Before, they always re-ran the pre-pass — and rewrote the tile bins under the eyes of renders of the same pose on the scene's other
+        # render stream)
+        flags = path if path else self._apex_flag(apex_key(sd))
+        self._launch_bwd(blob, sd, mats_arg, spp, seed, flags, _dev(gimg, name="gimg"), _dev(gtex))
         return gtex
-
-    def _render_bwd_appearance(self, sd, albedo, spp, seed, gimg, deterministic, max_depth, tex, material=False):
-        """render_bwd(..., appearance=True): one ffx_render_bwd[_filtered] call with FFX_RENDER_GRAD_APPEARANCE; gimg and the texture travel in one
-        buffer, gtex and the appearance block in another (include/ffx.h)"""
-        if max_depth != 2:
-            path_flags(max_depth)  # (the range check's message first)
-            raise ValueError("render_bwd(appearance=True): the appearance gradients are served at max_depth 2 (direct light) only")
-        if deterministic is None:
-            deterministic = deterministic_mode()
-        if deterministic:
-            raise ValueError("render_bwd(appearance=True) has no deterministic adjoint (FFX_DETERMINISTIC / deterministic=True)")
-        return self._render_bwd_leaves(sd, albedo, spp, seed, gimg, tex, material, 0, "render_bwd(appearance=True)")
 
     def render_bwd_prb(self, sd, albedo, spp, seed, gimg, tex, max_depth, rr_depth=5, material=False, deterministic=None):
         """path replay backpropagation (Mitsuba's `prb`, FFX_RENDER_GRAD_PRB): -> (gtex, AppearanceGrad) of a render_fwd with the same
@@ -1205,23 +1167,13 @@ class DeviceGeometry:
         H, W = sd.cam.height, sd.cam.width
         if albedo is None:
             raise ValueError("render_jvp: the device material table is needed")
-        ms = int(sd.mat_stride) or 3
-        if albedo.dim() != 2 or albedo.shape[1] != ms or albedo.shape[0] < sd.n_shapes:
-            raise ValueError(f"material table {tuple(albedo.shape)} does not match the scene description (n_shapes {sd.n_shapes}, mat_stride {ms})")
+        _check_table(sd, albedo)
         buf = self.pack_tangent(sd, tex, dtex, tangent).to(self.device)
         out = torch.empty((2, H, W, 3), dtype=torch.float32, device=self.device)
         blob = self.blob
         # (direct light: the primal is the packet kernels' and takes the apex flag render_fwd takes; deeper paths walk per lane)
         flags = (path if path else self._apex_flag(apex_key(sd))) | _abi.RENDER_TANGENT
-        with self._timed("render_jvp"):
-            if sd.rfilter:
-                scratch = torch.empty(render_filter_bytes(sd), dtype=torch.uint8, device=self.device)
-                self._call("ffx_render_fwd_filtered", _dev(blob, torch.uint8), C.byref(self.info), C.byref(sd), _dev(albedo, name="albedo"), _dev(buf, name="tex"), int(spp),
-                           int(seed) & 0xFFFFFFFF, flags, _dev(out), _dev(scratch, torch.uint8), _stream(self._didx))
-            else:
-                self._call("ffx_render_fwd", _dev(blob, torch.uint8), C.byref(self.info), C.byref(sd), _dev(albedo, name="albedo"), _dev(buf, name="tex"), int(spp),
-                           int(seed) & 0xFFFFFFFF, flags, _dev(out), _stream(self._didx))
-        self._release()
+        self._launch_fwd("render_jvp", blob, sd, _dev(albedo, name="albedo"), _dev(buf, name="tex"), spp, seed, flags, _dev(out))
         return out[0], out[1]
 
     @staticmethod
@@ -1232,46 +1184,44 @@ class DeviceGeometry:
         S = int(sd.n_shapes)
         bt = [(int(sd.base_tex_h[k]), int(sd.base_tex_w[k])) for k in range(sd.n_base_tex)]
         n_tex = sd.proj.tex_h * sd.proj.tex_w * sd.proj.tex_channels if sd.proj.enabled else 0
-        n_app = _abi.appearance_floats(S, bt)
         n_mat = _abi.material_floats(S) if int(sd.mat_stride) == _abi.MAT_STRIDE else 0
         t = tangent if tangent is not None else AppearanceGrad(None, None, None, None)
         given = [x for x in (tex, dtex, t.rows, t.spot, t.material, *(t.base_tex or [])) if isinstance(x, torch.Tensor)]
         device = given[0].device if given else torch.device("cpu")
-        buf = torch.zeros(2 * n_tex + n_app + n_mat, dtype=torch.float32, device=device)
+        buf = torch.zeros(2 * n_tex + _abi.appearance_floats(S, bt) + n_mat, dtype=torch.float32, device=device)
+        both = buf[:2 * n_tex].view(2, n_tex)
+        dst, _ = appearance_blocks(sd, n_mat > 0, buf, 2 * n_tex)
 
-        def put(o, v, n, what):
+        def put(view, v, what):
             if v is None:
                 return
             v = torch.as_tensor(v).detach().to(device=device, dtype=torch.float32).reshape(-1)
-            if v.numel() != n:
-                raise ValueError(f"render_jvp: {what} must hold {n} floats, got {v.numel()}")
-            buf[o:o + n] = v
+            if v.numel() != view.numel():
+                raise ValueError(f"render_jvp: {what} must hold {view.numel()} floats, got {v.numel()}")
+            view.copy_(v.view(view.shape))
 
         if n_tex:
             if tex is None:
                 raise ValueError(f"render_jvp: the projector's texture ({n_tex} floats) is needed")
-            put(0, tex, n_tex, "tex")
-            put(n_tex, dtex, n_tex, "dtex")
-        o = 2 * n_tex
-        put(o, t.rows, 3 * S, "tangent.rows")
-        put(o + 3 * S, t.spot, 3, "tangent.spot")
-        o += 3 * S + 3
+            put(both[0], tex, "tex")
+            put(both[1], dtex, "dtex")
+        put(dst.rows, t.rows, "tangent.rows")
+        put(dst.spot, t.spot, "tangent.spot")
         if t.base_tex is not None and len(t.base_tex) != len(bt):
             raise ValueError(f"render_jvp: tangent.base_tex must list {len(bt)} textures (None for a zero tangent)")
-        for k, (h, w) in enumerate(bt):
-            put(o, t.base_tex[k] if t.base_tex is not None else None, 3 * h * w, f"tangent.base_tex[{k}]")
-            o += 3 * h * w
+        for k, view in enumerate(dst.base_tex):
+            put(view, t.base_tex[k] if t.base_tex is not None else None, f"tangent.base_tex[{k}]")
         if t.material is not None and not n_mat:
             raise ValueError("render_jvp: tangent.material on a table without material columns")
-        put(o, t.material, n_mat, "tangent.material")
+        put(dst.material, t.material, "tangent.material")
         return buf
 
     def _render_bwd_leaves(self, sd, albedo, spp, seed, gimg, tex, material, path, what):
-        """the call behind render_bwd(appearance=True) (path 0) and render_bwd_prb (the path bits | FFX_RENDER_GRAD_PRB)"""
+        """the call behind render_bwd(appearance=True) (path 0) and render_bwd_prb (the path bits | FFX_RENDER_GRAD_PRB): gimg and the texture travel in one
+        buffer, gtex and the blocks in another (include/ffx.h)"""
         H, W = sd.cam.height, sd.cam.width
         n_tex = sd.proj.tex_h * sd.proj.tex_w * sd.proj.tex_channels
         bt = [(int(sd.base_tex_h[k]), int(sd.base_tex_w[k])) for k in range(sd.n_base_tex)]
-        n_app = _abi.appearance_floats(sd.n_shapes, bt)
         src = gimg.reshape(-1)
         if sd.proj.enabled:
             if tex is None or tex.numel() != n_tex:
@@ -1280,27 +1230,10 @@ class DeviceGeometry:
         if src.numel() < H * W * 3:
             raise ValueError("gimg must hold [H, W, 3] floats")
         n_mat = _abi.material_floats(sd.n_shapes) if material else 0
-        out = torch.zeros(n_tex + n_app + n_mat, dtype=torch.float32, device=self.device)
+        out = torch.zeros(n_tex + _abi.appearance_floats(sd.n_shapes, bt) + n_mat, dtype=torch.float32, device=self.device)
         mats_arg = _check_materials(sd, albedo)
         blob = self.blob
         # (the path replay walks per lane: no apex records are read or written)
         flags = (path if path else self._apex_flag(apex_key(sd))) | _abi.RENDER_GRAD_APPEARANCE | (_abi.RENDER_GRAD_MATERIAL if material else 0)
-        with self._timed("render_bwd"):
-            if sd.rfilter:
-                scratch = torch.empty(render_filter_bytes(sd), dtype=torch.uint8, device=self.device)
-                self._call("ffx_render_bwd_filtered", _dev(blob, torch.uint8), C.byref(self.info), C.byref(sd), mats_arg, int(spp), int(seed) & 0xFFFFFFFF, flags,
-                           _dev(src, name="gimg"), _dev(out), _dev(scratch, torch.uint8), _stream(self._didx))
-            else:
-                self._call("ffx_render_bwd", _dev(blob, torch.uint8), C.byref(self.info), C.byref(sd), mats_arg, int(spp), int(seed) & 0xFFFFFFFF, flags,
-                           _dev(src, name="gimg"), _dev(out), _stream(self._didx))
-        self._release()
-        gtex = out[:n_tex].view(sd.proj.tex_h, sd.proj.tex_w, sd.proj.tex_channels)
-        S = sd.n_shapes
-        rows = out[n_tex:n_tex + 3 * S].view(S, 3)
-        spot = out[n_tex + 3 * S:n_tex + 3 * S + 3]
-        base_tex, o = [], n_tex + 3 * S + 3
-        for h, w in bt:
-            base_tex.append(out[o:o + 3 * h * w].view(h, w, 3))
-            o += 3 * h * w
-        mat = out[n_tex + n_app:].view(S, _abi.RENDER_MATERIAL_COLS) if material else None
-        return gtex, AppearanceGrad(rows, spot, base_tex, mat)
+        self._launch_bwd(blob, sd, mats_arg, spp, seed, flags, _dev(src, name="gimg"), _dev(out))
+        return out[:n_tex].view(sd.proj.tex_h, sd.proj.tex_w, sd.proj.tex_channels), appearance_blocks(sd, material, out, n_tex)[0]

@@ -2315,6 +2315,39 @@ def test_deterministic_adjoint_is_bitwise_reproducible_and_cross_checks_the_atom
     assert float(gd2.render_bwd(sd0, dev(alb2), 9, 3, torch.zeros(44, 52, 3, device="cuda"), deterministic=True).abs().max()) == 0.0
 
 
+def test_deterministic_adjoint_in_two_parts_under_the_gaussian_film():
+    """ffx_render_bwd_det_part with a filtered film (the scratch argument that is None for a box film) through ops.render_bwd_det_part: the largest tap,
+    the scale derived from it, the fixed-point sums and their conversion give the gradient of the one-call deterministic adjoint and of the float-atomic
+    re-trace within the tolerance of the test above (1e-3 of the gradient's scale on all but 1e-3 of the texels, 0.05 of it anywhere), and the same
+    bits when repeated.  48 x 40 film at 4 spp: a partly filled last packet and pixel block, several pixels per wave; two shapes; 16 x 16 texels."""
+    sc = scenes.vocalfold(width=48, height=40, tex=16, frames=3, n_fold=20, tube=(20, 24))
+    pool, tris, shape, off, stride, nfr, alb = scenes.flatten(sc)
+    assert len(sc.meshes) == 2
+    gd = ops.DeviceGeometry(pool, tris, shape, off)
+    gd.update(_rand_xforms(2, 5), (off + stride).astype(np.int32))
+    sd = scene_desc.scene_desc(sc, tex_channels=1, shadows=True, rfilter="gaussian")
+    spp, seed = 4, 7
+    gimg = dev(np.random.default_rng(3).standard_normal((40, 48, 3)).astype(np.float32))
+
+    def in_two_parts():
+        vmax = torch.zeros(1, dtype=torch.int32, device="cuda")
+        gd.render_bwd_det_part(sd, dev(alb), spp, seed, gimg, 1, vmax)
+        sh = ops.det_scale_log2(int(vmax.item()), 4 * 48 * 40 * spp)
+        assert sh is not None
+        fix = torch.zeros((16, 16, 1), dtype=torch.int64, device="cuda")
+        gd.render_bwd_det_part(sd, dev(alb), spp, seed, gimg, 2, fix, scale_log2=sh)
+        return ops.det_finish_(fix, sh, torch.zeros((16, 16, 1), device="cuda"))
+
+    g = in_two_parts()
+    assert torch.equal(g, in_two_parts())
+    gs = float(g.abs().max())
+    assert gs > 0 and bool(torch.isfinite(g).all())
+    for what, other in (("one call", gd.render_bwd(sd, dev(alb), spp, seed, gimg, deterministic=True)), ("float atomics", gd.render_bwd(sd, dev(alb), spp, seed, gimg, deterministic=False))):
+        err = (other - g).abs()
+        print(f"{what}: max |difference| {float(err.max()):.3e} of scale {gs:.3e}")
+        assert float((err > 1e-3 * gs).float().mean()) <= 1e-3 and float(err.max()) <= 0.05 * gs, (what, float(err.max()) / gs)
+
+
 def test_per_slot_normal_area_holds_what_the_header_says():
     """include/ffx.h ffx_bvh_info.off_gn: per leaf slot the unit geometric normal and, in the fourth word, the BITS (shape + 1) | smooth << 30
     (0: degenerate triangle) — the render kernels take a hit's shape and smooth flag from that word.  The records of the same blob give the

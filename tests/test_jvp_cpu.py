@@ -154,6 +154,41 @@ def test_packing_of_the_tangent_blocks():
         ops.DeviceGeometry.pack_tangent(_sd(2, 3, False), None, None, ops.AppearanceGrad(torch.ones(3, 3), None, [], None))
 
 
+@pytest.mark.parametrize("material", [False, True])
+@pytest.mark.parametrize("bt", [[], [(2, 3), (1, 4)]])
+@pytest.mark.parametrize("proj", [False, True])
+@pytest.mark.parametrize("S", [2, 3])
+def test_one_layout_of_the_gradient_and_tangent_blocks(S, proj, bt, material):
+    """ops.appearance_blocks is the one place that knows the blocks' order and offsets: its views tile the buffer behind the start offset — rows, spot,
+    the base textures in index order, the material block — without a gap or an overlap, they cover what _abi's totals say, and what pack_tangent
+    writes is what they read (behind the texture and its tangent)"""
+    sd = _sd(S, _abi.MAT_STRIDE if material else 3, proj, bt)
+    total = _abi.appearance_floats(S, bt) + (_abi.material_floats(S) if material else 0)
+    start = 7
+    buf = torch.arange(float(start + total))
+    blocks, n = ops.appearance_blocks(sd, material, buf, start)
+    assert n == total
+    assert tuple(blocks.rows.shape) == (S, 3) and tuple(blocks.spot.shape) == (3,) and [tuple(b.shape) for b in blocks.base_tex] == [(h, w, 3) for h, w in bt]
+    assert (blocks.material is None) == (not material) and (not material or tuple(blocks.material.shape) == (S, 11))
+    parts = [blocks.rows, blocks.spot, *blocks.base_tex] + ([blocks.material] if material else [])
+    assert torch.equal(torch.cat([x.reshape(-1) for x in parts]), buf[start:])  # every float behind `start` once, in this order
+    assert all(x.data_ptr() == buf.data_ptr() + 4 * int(x.reshape(-1)[0]) for x in parts)  # ... as views, not copies
+    # distinct inputs through pack_tangent, read back through the same views
+    n_tex = 20 if proj else 0
+    g = torch.Generator().manual_seed(S + 10 * len(bt))
+    tex, dtex = (torch.rand(4, 5, 1, generator=g), torch.rand(4, 5, 1, generator=g)) if proj else (None, None)
+    tan = ops.AppearanceGrad(torch.rand(S, 3, generator=g), torch.rand(3, generator=g), [torch.rand(h, w, 3, generator=g) for h, w in bt],
+                             torch.rand(S, 11, generator=g) if material else None)
+    packed = ops.DeviceGeometry.pack_tangent(sd, tex, dtex, tan)
+    assert packed.numel() == 2 * n_tex + total
+    back, _ = ops.appearance_blocks(sd, material, packed, 2 * n_tex)
+    assert torch.equal(back.rows, tan.rows) and torch.equal(back.spot, tan.spot) and len(back.base_tex) == len(bt)
+    assert all(torch.equal(a, b) for a, b in zip(back.base_tex, tan.base_tex))
+    assert back.material is None if not material else torch.equal(back.material, tan.material)
+    if proj:
+        assert torch.equal(packed[:2 * n_tex], torch.cat([tex.reshape(-1), dtex.reshape(-1)]))
+
+
 class _NoGeometry:
     def __getattr__(self, name):
         raise AssertionError(f"the rule must be decided before the geometry is touched (geom.{name})")
