@@ -212,6 +212,10 @@ RENDER_GRAD_PRB = 0x40000
 # forward mode (include/ffx.h FFX_RENDER_TANGENT): in the img_fp16 word of ffx_render_fwd[_filtered]; the tangent blocks travel behind the texture in
 # the layout of the gradient blocks, the tangent image comes back behind the primal
 RENDER_TANGENT = 0x80000
+# arbitrary output variables (include/ffx.h FFX_RENDER_AOV): in the img_fp16 word of ffx_render_fwd[_filtered]; [H][W][RENDER_AOV_FLOATS] floats come
+# back behind the image
+RENDER_AOV = 0x100000
+RENDER_AOV_FLOATS = 17
 
 
 MAX_BASE_TEX = 4

@@ -4910,6 +4910,235 @@ __global__ void __launch_bounds__(64)
   jvp_pixel<RF, true, MAT>(c, a, j, s_dyn, s_rf);
 }
 
+// ------------------------------------------------------------------------------------------ FFX_RENDER_AOV
+// FFX_RENDER_AOV (include/ffx.h): what the camera sees at the primary hit, through the render's film over the render's samples.  The
+// block's 17 floats are handled in GROUPS of three channels (the last holds two) — what rf_fold carries beside the weight, and what keeps a group's
+// values, not the block's, live beside the walk.
+#define FFX_AOV_GROUPS ((FFX_RENDER_AOV_FLOATS + 2) / 3)
+#define FFX_AOV_PITCH (3 * FFX_AOV_GROUPS) // floats per pixel of the box film's sums in LDS (the block, padded to whole groups)
+// channels 3 g .. 3 g + 2 of a sample that hit slot `slot` at distance t along (o, d); g is wave-uniform.  Barycentrics from the camera's apex record
+// (u = d . B / d . A, v = d . C / d . A), normals from the update's per-slot records, texture coordinates, material row and base-colour lookup as
+// shade_sample reads them
+__device__ __forceinline__ void aov_group(const ShadeK &c, const int g, const TriRec *__restrict__ recs, const TriApex *__restrict__ arecs, const float4 *__restrict__ nrec,
+                                          const float4 *__restrict__ gn, const Hit &h, const float nt, const v3 o, const v3 d, float (&v)[3]) {
+  const int slot = h.slot;
+  if (g == 0) {
+    v[0] = h.t - nt;
+    v[1] = fmaf(h.t, d.x, o.x);
+    v[2] = fmaf(h.t, d.y, o.y);
+    return;
+  }
+  if (g == 5) {
+    v[0] = (float)recs[slot].shape;
+    v[1] = (float)h.prim;
+    return;
+  }
+  const float4 gq = g < 4 ? gn[slot] : make_float4(0.f, 0.f, 0.f, 0.f);
+  if (g == 1) {
+    v[0] = fmaf(h.t, d.z, o.z);
+    v[1] = gq.x;
+    v[2] = gq.y;
+    return;
+  }
+  const TriApex &ar = arecs[slot];
+  const float det = d.x * ar.A[0] + d.y * ar.A[1] + d.z * ar.A[2];
+  const float bu = (d.x * ar.B[0] + d.y * ar.B[1] + d.z * ar.B[2]) / det, bv = (d.x * ar.C[0] + d.y * ar.C[1] + d.z * ar.C[2]) / det;
+  const float bw = (1.0f - bu) - bv;
+  if (g == 2 || g == 3) {
+    v3 ns = V3(gq.x, gq.y, gq.z);
+    if ((__float_as_int(gq.w) & FFX_GN_SMOOTH_BIT) != 0 && nrec) {
+      const float4 n0 = nrec[3 * (size_t)slot], n1 = nrec[3 * (size_t)slot + 1], n2 = nrec[3 * (size_t)slot + 2];
+      const v3 ni = V3(fmaf(bw, n0.x, fmaf(bu, n1.x, bv * n2.x)), fmaf(bw, n0.y, fmaf(bu, n1.y, bv * n2.y)), fmaf(bw, n0.z, fmaf(bu, n1.z, bv * n2.z)));
+      const float l2 = vdot(ni, ni);
+      if (l2 > 0.f) {
+        const float il = 1.0f / sqrtf(l2);
+        ns = V3(ni.x * il, ni.y * il, ni.z * il);
+      }
+    }
+    if (g == 2) {
+      v[0] = gq.z;
+      v[1] = ns.x;
+      v[2] = ns.y;
+      return;
+    }
+    v[0] = ns.z;
+    if (c.slot_uv) {
+      const float *uv = c.slot_uv + 6 * (size_t)slot;
+      v[1] = fmaf(bw, uv[0], fmaf(bu, uv[2], bv * uv[4]));
+      v[2] = fmaf(bw, uv[1], fmaf(bu, uv[3], bv * uv[5]));
+    }
+    return;
+  }
+  // g == 4: the base colour
+  const float *row = mat_table(c) + (size_t)c.mat_stride * recs[slot].shape;
+  v[0] = row[0]; v[1] = row[1]; v[2] = row[2];
+  if (c.mat_stride == FFX_MAT_STRIDE && c.n_base_tex > 0) {
+    const int tix = (int)row[FFX_MAT_BASE_TEX];
+    if (tix > 0 && tix <= c.n_base_tex) base_tex_sample(c, tix - 1, slot, bu, bv, v);
+  }
+}
+
+// K7's packet form (k_trace_primary_pk: a wave owns a compact block of bw x bh pixels with spp_w sample slots each, one pixel and 64 samples per pass from
+// 33 samples per pixel up; candidates from the camera's tile bins, the tree walk when there are none) with the film behind it.
+//   box film (RF = false): every group of every pass, one launch.  A pixel's samples sit in spp_w neighbouring lanes: an xor butterfly inside the group
+//     (fixed order), the passes' sums added in order in LDS, the means stored as whole blocks — no atomics, the same bits on every run.
+//   gaussian film (RF = true): group `group` alone — its three values and the weight through rf_fold / rf_fold_blk into `out` = the film's scratch
+//     ([pixel][25][4]), as the render kernels leave the radiance there; k_aov_gather forms the channels.  One launch per group: the scratch holds one.
+// The kernel's ONE argument, read in place like ShadeK (kernarg_first): a phase takes a fresh view of it and re-reads what it needs with scalar
+// loads, so the walk's scalar registers do not also carry the pointers and counts of the phases around it (as by-value arguments they did: 29
+// scalars spilled into vector lanes, and those vectors into scratch)
+struct AovK {
+  ShadeK c;
+  const BvhNode *nodes; const TriRec *recs; const TriApex *arecs; WideScene ws;
+  int spp; uint32_t seed_key; int bw_log2, bh_log2, blocks_x, n_blocks;
+  const float4 *nrec, *gn;
+  float *out; int group;
+};
+template <bool WIDE, bool RF>
+__global__ void __launch_bounds__(PK_BLOCK) __attribute__((amdgpu_waves_per_eu(FFX_PK_MAT_WAVES, FFX_PK_MAT_WAVES)))
+    k_render_aov(AovK args) {
+  constexpr int WSTACK_N = WIDE ? FFX_WSTACK : 1, RF_N = (FFX_RF_FLOATS * 4 + 7) / 8;
+  __shared__ __attribute__((aligned(16))) uint2 s_wstack[RF ? (WSTACK_N > RF_N ? WSTACK_N : RF_N) : WSTACK_N]; // (RF: the filter's rows alias the walk's stack)
+  __shared__ float s_acc[RF ? 4 * 64 : 8 * FFX_AOV_PITCH]; // (box film: up to 8 pixels' sums; gaussian film: rf_fold's four sums per lane between the passes)
+  const int blk = __builtin_amdgcn_readfirstlane(blockIdx.x);
+  // what a lane derives from its number — its pixel of the block, its sample slot, the sample's jitter and ray — is formed in front of the walk and
+  // AGAIN behind it, from a copy of the lane number the compiler cannot see through (the same instructions: the same bits): nothing per-lane stays
+  // live across the walk, which takes every register of the budget
+  struct Sample { int pl, sl, x, y, bx0, by0; bool active; uint32_t pix; float jx, jy, nt, ft; v3 o, d; };
+  auto sample_of = [&](const AovK &a, int lane_, int pass) {
+    Sample q;
+    const int ppw_log2 = a.bw_log2 + a.bh_log2, spp_w = 64 >> ppw_log2;
+    q.bx0 = (blk % a.blocks_x) << a.bw_log2;
+    q.by0 = (blk / a.blocks_x) << a.bh_log2;
+    q.pl = lane_ >> (6 - ppw_log2);
+    q.sl = lane_ & (spp_w - 1);
+    q.x = q.bx0 + (q.pl & ((1 << a.bw_log2) - 1));
+    q.y = q.by0 + (q.pl >> a.bw_log2);
+    q.pix = (uint32_t)q.y * (uint32_t)a.c.cam.W + (uint32_t)q.x;
+    const int sidx = pass * spp_w + q.sl;
+    q.active = q.x < a.c.cam.W && q.y < a.c.cam.H && sidx < a.spp;
+    sample_jitter(a.seed_key, q.pix * (uint32_t)a.spp + (uint32_t)sidx, q.jx, q.jy);
+    cam_ray(a.c.cam, ((float)q.x + q.jx) * a.c.cam.inv_w, ((float)q.y + q.jy) * a.c.cam.inv_h, q.o, q.d, q.nt, q.ft);
+    return q;
+  };
+  auto lane_again = [] {
+    int l = threadIdx.x & 63;
+    asm volatile("" : "+v"(l));
+    return l;
+  };
+  int passes;
+  {
+    const AovK &a = kernarg_first<AovK>();
+    if (blk >= a.n_blocks) return; // whole wave
+    const int spp_w = 64 >> (a.bw_log2 + a.bh_log2); // sample slots of one pixel per pass
+    passes = (a.spp + spp_w - 1) / spp_w; // (more than one only for a wave that owns ONE pixel: the host gives a block's pixels >= spp slots)
+  }
+  for (int i = threadIdx.x & 63; i < (RF ? 4 * 64 : 8 * FFX_AOV_PITCH); i += 64) s_acc[i] = 0.f;
+  __builtin_amdgcn_wave_barrier();
+  for (int pass = 0; pass < passes; ++pass) {
+    Hit h[1];
+    bool hit;
+    {
+      const AovK &a = kernarg_first<AovK>();
+      const Sample q = sample_of(a, threadIdx.x & 63, pass);
+      const v3 o[1] = {q.o}, d[1] = {q.d};
+      const float nt[1] = {q.nt}, ft[1] = {q.ft};
+      const bool active[1] = {q.active};
+      bool fnd[1];
+      bool binned = false;
+      if (a.c.bins.g[0].on) binned = bins_block(a.c.bins, q.bx0, q.by0, 1 << a.bw_log2, 1 << a.bh_log2, a.arecs, d[0], nt[0], ft[0], wballot(active[0]), h[0]);
+      if (!binned) traverse_packet_any<false, 1, WIDE>(a.nodes, a.arecs, a.ws, s_wstack, o, d, nt, ft, active, h, fnd);
+      hit = active[0] && h[0].prim >= 0;
+    }
+    const AovK &a = kernarg_first<AovK>();
+    const int lane = lane_again();
+    const Sample q = sample_of(a, lane, pass);
+    const int ppw_log2 = a.bw_log2 + a.bh_log2;
+    if constexpr (RF) {
+      float v[3] = {0.f, 0.f, 0.f};
+      if (hit) aov_group(a.c, a.group, a.recs, a.arecs, a.nrec, a.gn, h[0], q.nt, q.o, q.d, v);
+      float gx[5], gy[5];
+      rf_weights(a.c.rf, q.jx, gx);
+      rf_weights(a.c.rf, q.jy, gy);
+      if (ppw_log2 > 0) { // (a single pass)
+        rf_fold_blk(reinterpret_cast<float *>(s_wstack), lane, gx, gy, v[0], v[1], v[2], q.active ? 1.f : 0.f, ppw_log2, a.bw_log2, q.bx0, q.by0, a.c.cam.W, a.c.cam.H,
+                    a.out);
+        return;
+      }
+      // (one pixel per wave: rf_fold's sums over the passes wait in LDS, four floats per lane)
+      float acc[4] = {s_acc[lane], s_acc[64 + lane], s_acc[128 + lane], s_acc[192 + lane]};
+      rf_fold(reinterpret_cast<float *>(s_wstack), lane, gx, gy, v[0], v[1], v[2], q.active ? 1.f : 0.f, acc);
+      if (pass + 1 == passes) {
+        rf_store(a.out, q.pix, lane, acc);
+      } else {
+        s_acc[lane] = acc[0]; s_acc[64 + lane] = acc[1]; s_acc[128 + lane] = acc[2]; s_acc[192 + lane] = acc[3];
+      }
+    } else {
+      const int spp_w = 64 >> ppw_log2;
+#pragma unroll 1
+      for (int g = 0; g < FFX_AOV_GROUPS; ++g) {
+        float v[3] = {0.f, 0.f, 0.f};
+        if (hit) aov_group(a.c, g, a.recs, a.arecs, a.nrec, a.gn, h[0], q.nt, q.o, q.d, v);
+        for (int m = 1; m < spp_w; m <<= 1) {
+          v[0] += __shfl_xor(v[0], m, 64);
+          v[1] += __shfl_xor(v[1], m, 64);
+          v[2] += __shfl_xor(v[2], m, 64);
+        }
+        if (q.sl == 0) {
+          float *s = s_acc + q.pl * FFX_AOV_PITCH + 3 * g;
+          s[0] += v[0]; s[1] += v[1]; s[2] += v[2];
+        }
+      }
+    }
+  }
+  if constexpr (!RF) {
+    __builtin_amdgcn_wave_barrier();
+    const AovK &a = kernarg_first<AovK>();
+    const int ppw_log2 = a.bw_log2 + a.bh_log2, W = a.c.cam.W, H = a.c.cam.H;
+    const int bx0 = (blk % a.blocks_x) << a.bw_log2, by0 = (blk / a.blocks_x) << a.bh_log2;
+    const float fspp = (float)a.spp;
+    for (int i = lane_again(); i < (FFX_RENDER_AOV_FLOATS << ppw_log2); i += 64) { // the block's pixels, 17 consecutive floats each
+      const int q = i / FFX_RENDER_AOV_FLOATS, ch = i - q * FFX_RENDER_AOV_FLOATS;
+      const int qx = bx0 + (q & ((1 << a.bw_log2) - 1)), qy = by0 + (q >> a.bw_log2);
+      if (qx < W && qy < H) a.out[((size_t)qy * W + qx) * FFX_RENDER_AOV_FLOATS + ch] = s_acc[q * FFX_AOV_PITCH + ch] / fspp;
+    }
+  }
+}
+// k_rf_gather for three (n_ch < 3: fewer) channels of the block: a pixel's 25 incoming sums, the same staging through LDS and the same order of
+// additions; what differs is the store — channels ch0 .. ch0 + n_ch - 1 of a 17-float pixel instead of the film's 3-float pixel
+__global__ void __launch_bounds__(64) k_aov_gather(const float4 *__restrict__ part, int W, int H, float *__restrict__ aov, int ch0, int n_ch) {
+  __shared__ float4 seg[68 * 5];
+  const int lane = threadIdx.x;
+  const int x0 = blockIdx.x * 64, y = blockIdx.y;
+  float r = 0.f, g = 0.f, b = 0.f, w = 0.f;
+  for (int wb = 0; wb < 5; ++wb) {
+    const int qy = y - (wb - 2);
+    if (qy < 0 || qy >= H) continue; // (wave-uniform)
+    __builtin_amdgcn_wave_barrier();
+#pragma unroll
+    for (int kk = 0; kk < 6; ++kk) {
+      const int e = lane + 64 * kk; // element (record e / 5, entry e % 5) of the 68 x 5 segment table
+      if (e < 340) {
+        const int rec = e / 5, wa = e - 5 * rec;
+        const int qx = x0 - 2 + rec;
+        seg[e] = (qx >= 0 && qx < W) ? part[((size_t)qy * W + qx) * 25 + (wb * 5 + wa)] : make_float4(0.f, 0.f, 0.f, 0.f);
+      }
+    }
+    __builtin_amdgcn_wave_barrier();
+#pragma unroll
+    for (int wa = 0; wa < 5; ++wa) {
+      const float4 v = seg[(lane + 4 - wa) * 5 + wa];
+      r += v.x; g += v.y; b += v.z; w += v.w;
+    }
+  }
+  const int x = x0 + lane;
+  if (x >= W) return;
+  float *p = aov + ((size_t)y * W + x) * FFX_RENDER_AOV_FLOATS + ch0;
+  p[0] = w > 0.f ? r / w : 0.f;
+  if (n_ch > 1) p[1] = w > 0.f ? g / w : 0.f;
+  if (n_ch > 2) p[2] = w > 0.f ? b / w : 0.f;
+}
+
 // ------------------------------------------------------------------------------------------ host side
 static int cam_prepare(const ffx_camera *c, CamK &k) {
   if (c->width < 1 || c->height < 1) return 0;
@@ -5719,9 +5948,71 @@ static int render_jvp(const void *bvh, const ffx_bvh_info *info, const ffx_scene
   if (rf_scratch) return rf_develop(r, 0, j.dimg, rf_scratch, st, "render_fwd_filtered (tangent)/gather");
   return FFX_OK;
 }
+// the AOV block's bit belongs to ffx_render_fwd[_filtered]: every other render entry point refuses it
+#define FFX_NO_AOV(flags_, what_) \
+  do { if ((flags_) & FFX_RENDER_AOV) FFX_FAIL(FFX_ERR_UNSUPPORTED, "%s: FFX_RENDER_AOV is served by ffx_render_fwd[_filtered] only", what_); } while (0)
+// FFX_RENDER_AOV (include/ffx.h): the image by the launches of a call without the bit, then k_render_aov into the block behind it — one
+// launch under the box film; under the gaussian film one launch into the scratch (which the image's gather has read by then) and one gather per group
+static int render_aov(const void *bvh, const ffx_bvh_info *info, const ffx_scene_desc *sd, const float *shape_albedo, const float *tex, int spp, uint32_t seed,
+                      int img_fp16, void *img, ffx_stream s, void *rf_scratch) {
+  const char *what = rf_scratch ? "render_fwd_filtered" : "render_fwd";
+  if (img_fp16 & FFX_RENDER_FP16) FFX_FAIL(FFX_ERR_UNSUPPORTED, "%s: FFX_RENDER_AOV has no fp16 film", what);
+  if (img_fp16 & FFX_RENDER_TANGENT) FFX_FAIL(FFX_ERR_UNSUPPORTED, "%s: FFX_RENDER_AOV is not served together with FFX_RENDER_TANGENT", what);
+  if (sd && !shape_albedo && sd->n_mat_h <= 0) FFX_FAIL(FFX_ERR_ARG, "%s: FFX_RENDER_AOV needs a material table (shape_albedo is NULL and sd->mat_h is empty)", what);
+  if (!bvh || !info || !sd || !img || spp < 1) FFX_FAIL(FFX_ERR_ARG, "render_fwd: bad argument");
+  RenderSetup r;
+  if (const int rc = render_setup("render_fwd", bvh, info, sd, shape_albedo, spp, seed, img_fp16, rf_scratch, r)) return rc;
+  if (r.n_pix >= (1L << 31)) FFX_FAIL(FFX_ERR_UNSUPPORTED, "render_fwd: more than 2^31 pixels");
+  if (!r.b.gn) FFX_FAIL(FFX_ERR_ARG, "render_fwd: blob without per-slot normals (built by another library version?)");
+  if (const int rc = render_fwd_impl(bvh, info, sd, shape_albedo, tex, spp, seed, img_fp16 & (FFX_RENDER_APEX_READY | FFX_RENDER_PATH_MASK), img, nullptr, s, nullptr,
+                                     nullptr, nullptr, rf_scratch))
+    return rc;
+  const hipStream_t st = (hipStream_t)s;
+  // the camera's apex records and bins: a packet render at direct light has just written them; the path kernels and the per-lane kernels write none,
+  // and the caller's FFX_RENDER_APEX_READY then says whether the blob holds them (as for ffx_trace_primary)
+  const bool fresh = use_packet() && r.max_depth == 2;
+  const TriApex *arecs;
+  uint32_t astride;
+  if (!launch_apex(bvh, info, sd->cam.to_world, sd, &arecs, &astride, st, nullptr, 0, fresh ? FFX_RENDER_APEX_READY : (img_fp16 & FFX_RENDER_APEX_READY))) return FFX_ERR_ARG;
+  bins_k(bvh, info, sd, r.c.bins);
+  // below 33 samples per pixel a compact block of pixels per wave (at least 8 sample slots per pixel under the gaussian film: rf_fold_blk), else one
+  // pixel — and one pixel whatever the count under FFX_RENDER_BLOCKS=0, as the render beside it
+  int bw_log2 = 0, bh_log2 = 0;
+  if (spp <= 32 && lowspp_blocks()) {
+    const PixBlocks pb = pixel_blocks(r.c.cam, spp, rf_scratch ? 8 : 1, 3);
+    bw_log2 = pb.bw_log2; bh_log2 = pb.bh_log2;
+  }
+  AovK a;
+  a.c = r.c;
+  a.nodes = r.b.nodes; a.recs = r.b.recs; a.arecs = arecs; a.ws = wide_scene(bvh, info);
+  a.spp = spp; a.seed_key = r.seed_key; a.bw_log2 = bw_log2; a.bh_log2 = bh_log2;
+  a.blocks_x = ffx_cdiv(r.c.cam.W, 1 << bw_log2);
+  a.n_blocks = a.blocks_x * ffx_cdiv(r.c.cam.H, 1 << bh_log2);
+  a.nrec = r.b.nrec; a.gn = r.b.gn;
+  a.out = (float *)img + (size_t)r.n_pix * 3;
+  a.group = 0;
+  if (!rf_scratch) {
+    if (use_wide(info)) hipLaunchKernelGGL((k_render_aov<true, false>), dim3(a.n_blocks), dim3(64), 0, st, a);
+    else hipLaunchKernelGGL((k_render_aov<false, false>), dim3(a.n_blocks), dim3(64), 0, st, a);
+    FFX_CHECK_LAUNCH("render_fwd (aov)");
+    return FFX_OK;
+  }
+  float *aov = a.out;
+  a.out = (float *)rf_scratch;
+  for (int g = 0; g < FFX_AOV_GROUPS; ++g) { // (check_filter: the filtered film runs on the wide walk)
+    a.group = g;
+    hipLaunchKernelGGL((k_render_aov<true, true>), dim3(a.n_blocks), dim3(64), 0, st, a);
+    FFX_CHECK_LAUNCH("render_fwd_filtered (aov)");
+    const int n_ch = FFX_RENDER_AOV_FLOATS - 3 * g < 3 ? FFX_RENDER_AOV_FLOATS - 3 * g : 3;
+    hipLaunchKernelGGL(k_aov_gather, dim3(ffx_cdiv(r.c.cam.W, 64), r.c.cam.H), dim3(64), 0, st, (const float4 *)rf_scratch, r.c.cam.W, r.c.cam.H, aov, 3 * g, n_ch);
+    FFX_CHECK_LAUNCH("render_fwd_filtered (aov)/gather");
+  }
+  return FFX_OK;
+}
 int ffx_render_fwd(const void *bvh, const ffx_bvh_info *info, const ffx_scene_desc *sd, const float *shape_albedo, const float *tex, int spp,
                    uint32_t seed, int img_fp16, void *img, ffx_stream s) {
   FFX_NO_APPEARANCE(img_fp16, "render_fwd");
+  if (img_fp16 & FFX_RENDER_AOV) return render_aov(bvh, info, sd, shape_albedo, tex, spp, seed, img_fp16, img, s, nullptr);
   if (img_fp16 & FFX_RENDER_TANGENT) return render_jvp(bvh, info, sd, shape_albedo, tex, spp, seed, img_fp16, img, s, nullptr);
   return render_fwd_impl(bvh, info, sd, shape_albedo, tex, spp, seed, img_fp16 & (FFX_RENDER_FP16 | FFX_RENDER_APEX_READY | FFX_RENDER_PATH_MASK), img, nullptr, s);
 }
@@ -5749,6 +6040,7 @@ int ffx_render_fwd_cache(const void *bvh, const ffx_bvh_info *info, const ffx_sc
   FFX_NO_PATH(img_fp16, "render_fwd_cache");
   FFX_NO_APPEARANCE(img_fp16, "render_fwd_cache");
   FFX_NO_TANGENT(img_fp16, "render_fwd_cache");
+  FFX_NO_AOV(img_fp16, "render_fwd_cache");
   return render_fwd_impl(bvh, info, sd, shape_albedo, tex, spp, seed, img_fp16 & 31, img, cache, s);
 }
 
@@ -5769,6 +6061,7 @@ int ffx_render_fwd_adjoint(const void *bvh, const ffx_bvh_info *info, const ffx_
   FFX_NO_PATH(img_fp16, "render_fwd_adjoint");
   FFX_NO_APPEARANCE(img_fp16, "render_fwd_adjoint");
   FFX_NO_TANGENT(img_fp16, "render_fwd_adjoint");
+  FFX_NO_AOV(img_fp16, "render_fwd_adjoint");
   return render_fwd_impl(bvh, info, sd, shape_albedo, tex, spp, seed, img_fp16 & (FFX_RENDER_FP16 | FFX_RENDER_SPARSE_ADJOINT | FFX_RENDER_APEX_READY), img, nullptr, s, gimg,
                          gtex, dot_out);
 }
@@ -5799,6 +6092,7 @@ int ffx_render_bwd_cached(const ffx_scene_desc *sd, const float *shape_albedo, c
   FFX_NO_PATH(img_fp16, "render_bwd_cached");
   FFX_NO_APPEARANCE(img_fp16, "render_bwd_cached");
   FFX_NO_TANGENT(img_fp16, "render_bwd_cached");
+  FFX_NO_AOV(img_fp16, "render_bwd_cached");
   return render_bwd_cached_impl(sd, shape_albedo, cache, spp, gimg, gtex, img, img_fp16, dot_out, nullptr, 0.f, s);
 }
 // K9 under an L1 loss against a target image (include/ffx.h): the loss launch (ffx_l1_value_grad) and its gradient image are folded into the scatter
@@ -6075,6 +6369,7 @@ static int render_bwd_leaves(const void *bvh, const ffx_bvh_info *info, const ff
 int ffx_render_bwd(const void *bvh, const ffx_bvh_info *info, const ffx_scene_desc *sd, const float *shape_albedo, int spp, uint32_t seed, int flags,
                    const float *gimg, float *gtex, ffx_stream s) {
   FFX_NO_TANGENT(flags, "render_bwd");
+  FFX_NO_AOV(flags, "render_bwd");
   FFX_MATERIAL_NEEDS_APPEARANCE(flags, "render_bwd");
   if (flags & FFX_RENDER_GRAD_APPEARANCE) return render_bwd_leaves(bvh, info, sd, shape_albedo, spp, seed, flags, gimg, gtex, s, nullptr);
   return render_bwd_impl(bvh, info, sd, shape_albedo, spp, seed, flags, gimg, gtex, s, nullptr);
@@ -6092,6 +6387,7 @@ int ffx_render_bwd_det(const void *bvh, const ffx_bvh_info *info, const ffx_scen
   FFX_NO_PATH(flags, "render_bwd_det");
   FFX_NO_APPEARANCE(flags, "render_bwd_det");
   FFX_NO_TANGENT(flags, "render_bwd_det");
+  FFX_NO_AOV(flags, "render_bwd_det");
   // workspace: [the filtered film's scratch (16-byte multiple)] [one 64-bit sum per texel and channel] [the largest tap]
   void *rf = sd->rfilter != FFX_RFILTER_BOX ? workspace : nullptr;
   void *det = (char *)workspace + (rf ? ffx_render_filter_bytes(sd) : 0);
@@ -6105,6 +6401,7 @@ int ffx_render_bwd_det_part(const void *bvh, const ffx_bvh_info *info, const ffx
   FFX_NO_PATH(flags, "render_bwd_det_part");
   FFX_NO_APPEARANCE(flags, "render_bwd_det_part");
   FFX_NO_TANGENT(flags, "render_bwd_det_part");
+  FFX_NO_AOV(flags, "render_bwd_det_part");
   void *rf = nullptr;
   if (sd->rfilter != FFX_RFILTER_BOX) {
     if (!workspace || ((uintptr_t)workspace & 15) != 0) FFX_FAIL(FFX_ERR_ARG, "render_bwd_det_part: a filtered film needs its scratch (ffx_render_filter_bytes), 16-byte aligned");
@@ -6134,6 +6431,7 @@ int ffx_render_fwd_filtered(const void *bvh, const ffx_bvh_info *info, const ffx
                             uint32_t seed, int img_fp16, void *img, void *scratch, ffx_stream s) {
   if (!scratch || ((uintptr_t)scratch & 15) != 0) FFX_FAIL(FFX_ERR_ARG, "render_fwd_filtered: scratch is NULL or not 16-byte aligned");
   FFX_NO_APPEARANCE(img_fp16, "render_fwd_filtered");
+  if (img_fp16 & FFX_RENDER_AOV) return render_aov(bvh, info, sd, shape_albedo, tex, spp, seed, img_fp16, img, s, scratch);
   if (img_fp16 & FFX_RENDER_TANGENT) return render_jvp(bvh, info, sd, shape_albedo, tex, spp, seed, img_fp16, img, s, scratch);
   return render_fwd_impl(bvh, info, sd, shape_albedo, tex, spp, seed, img_fp16 & (FFX_RENDER_FP16 | FFX_RENDER_APEX_READY | FFX_RENDER_PATH_MASK), img, nullptr, s, nullptr,
                          nullptr, nullptr, scratch);
@@ -6147,6 +6445,7 @@ int ffx_render_fwd_adjoint_filtered(const void *bvh, const ffx_bvh_info *info, c
   FFX_NO_PATH(img_fp16, "render_fwd_adjoint_filtered");
   FFX_NO_APPEARANCE(img_fp16, "render_fwd_adjoint_filtered");
   FFX_NO_TANGENT(img_fp16, "render_fwd_adjoint_filtered");
+  FFX_NO_AOV(img_fp16, "render_fwd_adjoint_filtered");
   return render_fwd_impl(bvh, info, sd, shape_albedo, tex, spp, seed, img_fp16 & (FFX_RENDER_FP16 | FFX_RENDER_SPARSE_ADJOINT | FFX_RENDER_APEX_READY), img, nullptr, s, gimg,
                          gtex, nullptr, scratch);
 }
@@ -6155,6 +6454,7 @@ int ffx_render_bwd_filtered(const void *bvh, const ffx_bvh_info *info, const ffx
                             const float *gimg, float *gtex, void *scratch, ffx_stream s) {
   if (!scratch || ((uintptr_t)scratch & 15) != 0) FFX_FAIL(FFX_ERR_ARG, "render_bwd_filtered: scratch is NULL or not 16-byte aligned");
   FFX_NO_TANGENT(flags, "render_bwd_filtered");
+  FFX_NO_AOV(flags, "render_bwd_filtered");
   FFX_MATERIAL_NEEDS_APPEARANCE(flags, "render_bwd_filtered");
   if (flags & FFX_RENDER_GRAD_APPEARANCE) return render_bwd_leaves(bvh, info, sd, shape_albedo, spp, seed, flags, gimg, gtex, s, scratch);
   return render_bwd_impl(bvh, info, sd, shape_albedo, spp, seed, flags, gimg, gtex, s, scratch);
@@ -6167,6 +6467,7 @@ int ffx_render_fwd_cache_filtered(const void *bvh, const ffx_bvh_info *info, con
   FFX_NO_PATH(img_fp16, "render_fwd_cache_filtered");
   FFX_NO_APPEARANCE(img_fp16, "render_fwd_cache_filtered");
   FFX_NO_TANGENT(img_fp16, "render_fwd_cache_filtered");
+  FFX_NO_AOV(img_fp16, "render_fwd_cache_filtered");
   return render_fwd_impl(bvh, info, sd, shape_albedo, tex, spp, seed,
                          img_fp16 & (FFX_RENDER_FP16 | FFX_RENDER_SPARSE_ADJOINT | FFX_RENDER_APEX_READY | FFX_RENDER_CACHE_ZEROED | FFX_RENDER_CACHE_KEEP_DROPPED), img, nullptr, s,
                          nullptr, nullptr, nullptr, scratch, cache);

@@ -213,14 +213,19 @@ class _Render(torch.autograd.Function):
         return gtex.reshape(ctx.tex_shape), None, None, None, None, None, None, None, None
 
 
-def render(tex, geom, sd, albedo, spp, seed=0, fp16=False, max_depth=2, rr_depth=5):
+def render(tex, geom, sd, albedo, spp, seed=0, fp16=False, max_depth=2, rr_depth=5, integrator=None):
     """K8/K9: image [H,W,3], differentiable w.r.t. the projector texture ([h,w] or [h,w,c]).
     When the texture requires grad the forward kernel also stores each pixel's footprint in the texture
     (128 B per pixel + a small arena: 40 MB at 512x512x64; under a gaussian film an arena of per-sample records — 16 / 20 bytes per sample
     of the pixels that have a lit sample, room for every pixel up to 344 MB, a quarter of them beyond) and the adjoint scatters those footprints; beyond FFX_CACHE_LIMIT_GB the adjoint re-traces instead (then the geometry must not be re-fitted between
     forward and backward).
     max_depth > 2: Mitsuba's `path` integrator (a `prb` integrator renders the same image and, for `tex.data`, is `path`); no cache — the adjoint replays the forward's paths, so the geometry must not be
-    re-fitted between forward and backward."""
+    re-fitted between forward and backward.
+    integrator (mi.load_dict's): its max_depth / rr_depth instead of the two arguments; an `aov` integrator is refused (mi.render serves it)."""
+    if integrator is not None:
+        if getattr(integrator, "type", None) == "aov":
+            raise ValueError("render: an 'aov' integrator is served by mi.render only (its channels carry no derivatives); pass its nested integrator")
+        max_depth, rr_depth = int(integrator.max_depth), int(integrator.rr_depth)
     if max_depth != 2:
         ops.path_flags(max_depth, rr_depth)  # (the range check before any launch)
         if ops.deterministic_mode() and tex.requires_grad:

@@ -1193,14 +1193,77 @@ class Integrator:
         return render_forward(scene, params, tangents, spp=int(spp) if spp else 16, seed=seed, sensor=sensor, integrator=self)
 
 
+# the types of Mitsuba's `aov` integrator that are served -> (channel of ops.AOV_CHANNELS, suffixes of its components in aov_names())
+AOV_TYPES = {"depth": ("",), "position": (".X", ".Y", ".Z"), "geo_normal": (".X", ".Y", ".Z"), "sh_normal": (".X", ".Y", ".Z"), "uv": (".U", ".V"),
+             "albedo": (".R", ".G", ".B"), "shape_index": ("",), "prim_index": ("",)}
+
+
+class AovIntegrator(Integrator):
+    """Mitsuba's `aov` integrator: mi.load_dict({"type": "aov", "aovs": "<name>:<type>,...", "<key>": {<a path / prb / direct
+    integrator>}}).  mi.render(..., integrator=this) returns [H, W, C]: the channels of `aovs` in order — what the camera sees at the primary hit,
+    through the render's film over the render's samples — then the nested integrator's RGB, if there is one.  max_depth / rr_depth are the nested
+    integrator's (direct light without one)."""
+
+    def __init__(self, aovs, nested=None):
+        self.aovs = self.parse(aovs)
+        if nested is not None and (not isinstance(nested, tuple) or len(nested) != 2 or not isinstance(nested[1], Integrator)):
+            raise TypeError("aov: nested must be (key, Integrator)")
+        if nested is not None and nested[1].type == "aov":
+            raise ValueError("aov: an 'aov' integrator cannot be nested in another one")
+        self.nested = nested
+        inner = nested[1] if nested is not None else None
+        self.type, self.max_depth, self.rr_depth = "aov", inner.max_depth if inner else 2, inner.rr_depth if inner else 5
+
+    @staticmethod
+    def parse(aovs):
+        """'dd.y:depth,nn:sh_normal' -> [('dd.y', 'depth'), ('nn', 'sh_normal')]"""
+        if not isinstance(aovs, str) or not aovs.strip():
+            raise ValueError("aov: 'aovs' must be a string '<name>:<type>,<name>:<type>,...'")
+        out = []
+        for item in aovs.split(","):
+            name, sep, type_ = (x.strip() for x in item.partition(":"))
+            if not sep or not name or not type_:
+                raise ValueError(f"aov: {item.strip()!r} is not '<name>:<type>'")
+            if type_ not in AOV_TYPES:
+                raise ValueError(f"aov: type {type_!r} is not served; the served types are {sorted(AOV_TYPES)}")
+            out.append((name, type_))
+        return out
+
+    def aov_names(self):
+        """the channel names of mi.render's output, in order: a scalar type keeps its name, vectors get .X .Y .Z, uv .U .V, albedo .R .G .B; the nested
+        integrator's <key>.R .G .B come last"""
+        names = [name + suffix for name, type_ in self.aovs for suffix in AOV_TYPES[type_]]
+        return names + ([self.nested[0] + c for c in (".R", ".G", ".B")] if self.nested is not None else [])
+
+    def __repr__(self):
+        return f"AovIntegrator(aovs={','.join(n + ':' + t for n, t in self.aovs)!r}, nested={self.nested!r})"
+
+
+def _no_aov(integrator, what):
+    if integrator is not None and getattr(integrator, "type", None) == "aov":
+        raise ValueError(f"{what}: an 'aov' integrator is served by mi.render only (its channels carry no derivatives); pass its nested integrator")
+
+
 def load_dict(d: dict):
-    """mi.load_dict for integrator dictionaries: {"type": "path" | "prb", "max_depth": k, "rr_depth": r} or {"type": "direct"} -> Integrator.
-    Scenes come from load_file / load_scene_data."""
+    """mi.load_dict for integrator dictionaries: {"type": "path" | "prb", "max_depth": k, "rr_depth": r} or {"type": "direct"} -> Integrator;
+    {"type": "aov", "aovs": "<name>:<type>,...", "<any key>": {one of the former}} -> AovIntegrator.  Scenes come from load_file / load_scene_data."""
     if not isinstance(d, dict) or "type" not in d:
         raise ValueError("load_dict: a dictionary with a 'type'")
     t = d["type"]
+    if t == "aov":
+        nested = [(k, v) for k, v in d.items() if isinstance(v, dict)]
+        extra = sorted(k for k, v in d.items() if k not in ("type", "aovs") and not isinstance(v, dict))
+        if extra:
+            raise ValueError(f"load_dict: 'aov' integrator properties {extra} are not served")
+        if len(nested) > 1:
+            raise ValueError(f"load_dict: an 'aov' integrator takes at most one nested integrator, got {[k for k, _ in nested]}")
+        if nested and nested[0][1].get("type") == "aov":
+            raise ValueError("load_dict: an 'aov' integrator cannot be nested in another one")
+        if "aovs" not in d:
+            raise ValueError("load_dict: an 'aov' integrator needs 'aovs'")
+        return AovIntegrator(d["aovs"], (nested[0][0], load_dict(nested[0][1])) if nested else None)
     if t not in ("path", "prb", "direct"):
-        raise NotImplementedError(f"load_dict: type {t!r} — only the integrators 'path', 'prb' and 'direct' (scenes: mi.load_file / mi.load_scene_data)")
+        raise NotImplementedError(f"load_dict: type {t!r} — only the integrators 'path', 'prb', 'direct' and 'aov' (scenes: mi.load_file / mi.load_scene_data)")
     extra = set(d) - ({"type", "max_depth", "rr_depth"} if t != "direct" else {"type"})
     if extra:
         raise ValueError(f"load_dict: {t!r} integrator properties {sorted(extra)} are not served")
@@ -1221,6 +1284,8 @@ def render(scene: Scene, params: SceneParameters = None, spp: int = 16, seed: in
         raise NotImplementedError("only sensor 0 renders; further sensors are projector proxies")
     if integrator is not None and not isinstance(integrator, Integrator):
         raise TypeError("render: integrator must come from mi.load_dict")
+    if integrator is not None and integrator.type == "aov":
+        return _render_aov(scene, params, spp, seed, fp16, integrator)
     if scene._params._leaves and torch.is_grad_enabled():
         return _render_appearance(scene, spp, seed, fp16, integrator)
     sd, tex_in, tex = _scene_texture(scene, spp)
@@ -1245,6 +1310,30 @@ def render(scene: Scene, params: SceneParameters = None, spp: int = 16, seed: in
         scene.render_paths["caller_stream"] += 1
         img = scene.geom.render_fwd(sd, mats, Fn._tex3(tex), int(spp), int(seed), bool(fp16), max_depth=md, rr_depth=rr)
     return TensorXf(img)
+
+
+def _render_aov(scene, params, spp, seed, fp16, integrator):
+    """mi.render under an `aov` integrator -> [H, W, C]: the block's channels in the order of `aovs` (constants for autograd), then the nested integrator's
+    RGB.  While anything can take a gradient the RGB goes through mi.render's own routes with the nested integrator — the same image bit for bit, with
+    its autograd; otherwise it is the image the block's call renders anyway (the same bits again).  In the first case the image is rendered twice:
+    FFX_RENDER_AOV has no form that launches the block alone, so the block's call renders a direct-light image that is dropped (cost)"""
+    if fp16:
+        raise ValueError("mi.render: an 'aov' integrator has no fp16 film")
+    inner = integrator.nested[1] if integrator.nested is not None else None
+    sd, _, tex = _scene_texture(scene, spp)
+    if tex is None:
+        tex = torch.zeros((1, 1, 1), device=scene.device)
+    grad = inner is not None and torch.is_grad_enabled() and (tex.requires_grad or bool(scene._params._leaves))
+    rgb = render(scene, params, spp, seed, 0, False, inner).torch() if grad else None
+    md, rr = (inner.max_depth, inner.rr_depth) if inner is not None and not grad else (2, 5)
+    img, block = scene.geom.render_aov(sd, scene.materials_arg(sd), Fn._tex3(tex.detach()), int(spp), int(seed), max_depth=md, rr_depth=rr)
+    parts = []
+    for _, type_ in integrator.aovs:
+        first, n = ops.AOV_CHANNELS[type_]
+        parts.append(block[..., first:first + n])
+    if inner is not None:
+        parts.append(rgb if grad else img)
+    return TensorXf(torch.cat(parts, dim=-1))
 
 
 def _scene_texture(scene, spp):
@@ -1322,6 +1411,7 @@ def render_forward(scene: Scene, params: SceneParameters = None, tangents: dict 
         raise NotImplementedError("only sensor 0 renders; further sensors are projector proxies")
     if integrator is not None and not isinstance(integrator, Integrator):
         raise TypeError("render_forward: integrator must come from mi.load_dict")
+    _no_aov(integrator, "render_forward")
     if not isinstance(tangents, dict):
         raise TypeError("render_forward: tangents must be a dict of parameter key -> tensor")
     allowed = _forward_keys(scene)

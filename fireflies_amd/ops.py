@@ -543,6 +543,12 @@ def _no_path(max_depth, what):
         raise ValueError(f"{what}: max_depth > 2 renders through render_fwd / render_bwd only (no adjoint cache, fused or deterministic adjoint)")
 
 
+# the block of render_aov (include/ffx.h FFX_RENDER_AOV): channel -> (first float, floats), in the block's order
+AOV_CHANNELS = {"depth": (0, 1), "position": (1, 3), "geo_normal": (4, 3), "sh_normal": (7, 3), "uv": (10, 2), "albedo": (12, 3), "shape_index": (15, 1),
+                "prim_index": (16, 1)}
+assert sum(n for _, n in AOV_CHANNELS.values()) == _abi.RENDER_AOV_FLOATS
+
+
 class AppearanceGrad(NamedTuple):
     """what render_bwd(..., appearance=True) adds to the texture gradient: d loss / d base colour per material row [n_shapes, 3] (zero on
     rows whose base colour is a texture), d loss / d spot intensity [3], d loss / d base-colour texture [h, w, 3] per texture of the scene description.
@@ -1175,6 +1181,21 @@ class DeviceGeometry:
         flags = (path if path else self._apex_flag(apex_key(sd))) | _abi.RENDER_TANGENT
         self._launch_fwd("render_jvp", blob, sd, _dev(albedo, name="albedo"), _dev(buf, name="tex"), spp, seed, flags, _dev(out))
         return out[0], out[1]
+
+    def render_aov(self, sd, albedo, tex, spp, seed=0, *, max_depth=2, rr_depth=5):
+        """the render and its ground truth (FFX_RENDER_AOV): -> (img [H, W, 3], aov [H, W, 17]), img the image of render_fwd with the
+        same arguments bit for bit, aov the primary hit's depth, position, normals, uv, base colour and ids (AOV_CHANNELS names the offsets) through the
+        same film over the same samples.  max_depth > 2 chooses the image only.  fp32 film; two calls give the same bits."""
+        path = path_flags(max_depth, rr_depth) if max_depth != 2 else 0
+        H, W = sd.cam.height, sd.cam.width
+        mats_arg = _check_materials(sd, albedo)
+        out = torch.empty(H * W * (3 + _abi.RENDER_AOV_FLOATS), dtype=torch.float32, device=self.device)
+        blob = self.blob
+        # (the block's launch reads the camera's apex records and bins: behind a path render, which writes none, the call runs the pre-pass itself unless
+        # the blob already holds this pose's)
+        flags = path | self._apex_flag(apex_key(sd)) | _abi.RENDER_AOV
+        self._launch_fwd("render_aov", blob, sd, mats_arg, _dev(tex, name="tex") if tex is not None else None, spp, seed, flags, _dev(out))
+        return out[:H * W * 3].view(H, W, 3), out[H * W * 3:].view(H, W, _abi.RENDER_AOV_FLOATS)
 
     @staticmethod
     def pack_tangent(sd, tex, dtex, tangent):

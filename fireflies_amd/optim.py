@@ -103,6 +103,8 @@ class PatternOptimizer:
         self.mi_scene, self.ff_scene, self.laser = mi_scene, ff_scene, laser
         # mi.load_dict's integrator: max_depth > 2 renders paths; its adjoint replays them (the "retrace" route).  `prb` is `path`
         # here: the optimiser differentiates tex.data only
+        if getattr(integrator, "type", None) == "aov":
+            raise ValueError("PatternOptimizer: an 'aov' integrator is served by mi.render only (its channels carry no derivatives); pass its nested integrator")
         self.max_depth, self.rr_depth = (2, 5) if integrator is None else (int(integrator.max_depth), int(integrator.rr_depth))
         if self.max_depth > 2 and ops.deterministic_mode():
             raise ValueError("PatternOptimizer: max_depth > 2 has no deterministic adjoint (FFX_DETERMINISTIC=1)")

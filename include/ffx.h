@@ -36,7 +36,7 @@
  *                                B >= 2: each XCD takes B consecutive work items of every 8 B (default 1024; 256 on large films)
  *       FFX_RENDER_BLOCKS=0      ffx_render_fwd / ffx_render_fwd_filtered below 33 samples per pixel: a pixel per wave whatever the count, as
  *                                at 64 (default: compact blocks of up to 8 pixels per wave, 16 at 1 spp, k_render_fwd_blk — the same image
- *                                bit for bit, 1.5 - 2.3x faster)
+ *                                bit for bit, 1.5 - 2.3x faster); the FFX_RENDER_AOV launches of such a call follow it
  *       FFX_BINS=0               the packet render kernels walk the tree for every packet (default: tile bins first, ffx_bvh_info.off_bins)
  *       FFX_BIN_TILE=4..32       side of a camera tile of the bins in pixels, a power of two (default 8)
  *       FFX_BIN_TILE_PROJ=4..64  side of a projector tile of the bins in texels, a power of two (default twice FFX_BIN_TILE)
@@ -822,6 +822,30 @@ int ffx_det_finish(const void *acc /*[dev] int64 [n]*/, int scale_log2, size_t n
  * FFX_RENDER_FP16 and on every other render entry point; FFX_ERR_ARG with a NULL shape_albedo (the rows of sd->mat_h do not stand in for it here).
  * The oracle ignores the bit. */
 #define FFX_RENDER_TANGENT 0x80000
+/* Arbitrary output variables (Mitsuba's `aov` integrator): FFX_RENDER_AOV in the img_fp16 word of ffx_render_fwd / ffx_render_fwd_filtered adds,
+ * behind the image, what the camera sees at the primary hit — the ground truth of a dataset sample, through the render's own film and samples.  An additive
+ * extension of ABI 11 (FFX_ABI_VERSION is unchanged).
+ *   output — img: [H][W][3] fp32 image, exactly the image of the call without the bit (its launches, bit for bit), followed by [H][W][FFX_RENDER_AOV_FLOATS]
+ *            fp32, per pixel in this order (per-sample value; 0 for a sample that misses):
+ *              0       depth        t of K7 (ffx_trace_primary): distance along the unit ray from the near-plane origin
+ *              1..3    position     world-space hit point o + t d
+ *              4..6    geo_normal   unit e1 x e2 of the hit triangle in its stored winding, NOT faced to the viewer
+ *              7..9    sh_normal    the interpolated vertex normal of a shape flagged by ffx_smooth, normalised, NOT faced; the geometric normal for a
+ *                                   flat shape and for a zero-length interpolant
+ *              10..11  uv           ffx_scene_desc.slot_uv interpolated at the hit, NOT wrapped (0 when slot_uv is NULL)
+ *              12..14  albedo       the row's base colour: FFX_MAT_BASE_TEX != 0 -> the base-colour texture's repeat + bilinear lookup; a table of
+ *                                   stride 3 -> its Lambert albedo
+ *              15      shape_index  the hit's shape row as a float (K7's shape_out)
+ *              16      prim_index   the hit's triangle id as a float (K7's prim_out)
+ *            Every channel goes through the film as the radiance does, over the image's own samples (same idx, jitter and seed): the box film's mean over
+ *            the pixel's spp samples (misses count as 0), the gaussian film's sum(w a) / sum(w) (0 where no weight arrived).  The index channels are
+ *            averaged like the rest [EXT Mitsuba's aov does the same]; they are exact at 1 spp.  The path bits choose the image only: the block always
+ *            describes the primary hit.
+ * Written by further launches on the same stream (the gaussian film: one pass over its scratch per three channels, the scratch keeps its size).  No
+ * atomics: two calls give the same bits.  FFX_ERR_UNSUPPORTED together with FFX_RENDER_FP16, FFX_RENDER_TANGENT or a FFX_RENDER_GRAD_* bit and on every
+ * other render entry point; FFX_ERR_ARG without a material table (shape_albedo NULL and no rows in sd->mat_h).  The oracle ignores the bit. */
+#define FFX_RENDER_AOV 0x100000
+#define FFX_RENDER_AOV_FLOATS 17
 /* Writes the apex records (the triangles as seen from a fixed ray origin) of sd's camera and enabled emitters into
  * the blob's apex areas — what every packet render does in front of its kernel unless told FFX_RENDER_APEX_READY.  Only
  * sd->cam.to_world, sd->proj.{enabled,to_world} and sd->spot.{enabled,to_world} are read.  No reference counterpart (Mitsuba
