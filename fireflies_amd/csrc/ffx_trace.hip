@@ -109,6 +109,12 @@ struct Hit { float t; int prim, shape, slot; };
 // rejected).  With 1/0 = inf the products 0*inf = NaN would silently drop the axis and such rays
 // (every pixel-corner ray of the centre row / column when jitter is off) would walk the whole tree.
 struct RayBox { v3 o, id; };
+// The walks that use this test (the per-lane walk and the generic packet walk) cull a box against the current hit distance WIDENED by 3 ulp,
+// like the octant and wide walks (their `sw`): a box that ends exactly on the hit — a flat box in a coordinate plane, which the refit's
+// relative pad leaves as it is — has the entry distance (plane - o) * rcp(d), rounded up to three times where t = T/det is rounded once, and
+// may hold a triangle at the same t with a smaller id.  Against the bare distance the tie was dropped on one such ray in five
+// (tests/tie_scenes.py: sheets_far_from_their_plane).
+#define FFX_TIE_WIDEN 1.0000004f
 __device__ __forceinline__ float safe_rcp_dir(float d) {
   float a = fabsf(d) < 1e-20f ? copysignf(1e-20f, d) : d;
   return __builtin_amdgcn_rcpf(a);
@@ -202,8 +208,8 @@ __device__ __forceinline__ bool traverse(const BvhNode *__restrict__ nodes, cons
     float lo0[3] = {q0.x, q0.y, q0.z}, hi0[3] = {q0.w, q1.x, q1.y};
     float lo1[3] = {q1.z, q1.w, q2.x}, hi1[3] = {q2.y, q2.z, q2.w};
     float t0, t1;
-    bool h0 = (ch.x != FFX_EMPTY_CHILD) && slab(lo0, hi0, rb, tmin, h.t, t0);
-    bool h1 = (ch.y != FFX_EMPTY_CHILD) && slab(lo1, hi1, rb, tmin, h.t, t1);
+    bool h0 = (ch.x != FFX_EMPTY_CHILD) && slab(lo0, hi0, rb, tmin, h.t * FFX_TIE_WIDEN, t0);
+    bool h1 = (ch.y != FFX_EMPTY_CHILD) && slab(lo1, hi1, rb, tmin, h.t * FFX_TIE_WIDEN, t1);
 #pragma unroll
     for (int side = 0; side < 2; ++side) {
       int c = side ? ch.y : ch.x;
@@ -226,8 +232,8 @@ __device__ __forceinline__ bool traverse(const BvhNode *__restrict__ nodes, cons
       }
     }
     // a leaf may have shortened the ray: drop inner children that now start behind the hit
-    if (h0 && t0 > h.t) h0 = false;
-    if (h1 && t1 > h.t) h1 = false;
+    if (h0 && t0 > h.t * FFX_TIE_WIDEN) h0 = false;
+    if (h1 && t1 > h.t * FFX_TIE_WIDEN) h1 = false;
     if (h0 && h1) {
       int nearc = ch.x, farc = ch.y;
       if (t1 < t0) { nearc = ch.y; farc = ch.x; }
@@ -1185,8 +1191,8 @@ __device__ __forceinline__ void traverse_packet(const BvhNode *__restrict__ node
     bool any0 = false, any1 = false;
 #pragma unroll
     for (int r = 0; r < R; ++r) {
-      h0[r] = slab(lo0, hi0, rb[r], tmin[r], h[r].t, t0[r]) & (c0 != FFX_EMPTY_CHILD);
-      h1[r] = slab(lo1, hi1, rb[r], tmin[r], h[r].t, t1[r]) & (c1 != FFX_EMPTY_CHILD);
+      h0[r] = slab(lo0, hi0, rb[r], tmin[r], h[r].t * FFX_TIE_WIDEN, t0[r]) & (c0 != FFX_EMPTY_CHILD);
+      h1[r] = slab(lo1, hi1, rb[r], tmin[r], h[r].t * FFX_TIE_WIDEN, t1[r]) & (c1 != FFX_EMPTY_CHILD);
       any0 |= h0[r];
       any1 |= h1[r];
     }
@@ -1257,7 +1263,8 @@ __device__ __forceinline__ void traverse_packet(const BvhNode *__restrict__ node
     bool g0 = false, g1 = false, first1 = false, first0 = false;
 #pragma unroll
     for (int r = 0; r < R; ++r) {
-      const bool a0 = h0[r] & (c0 >= 0) & (t0[r] <= h[r].t), a1 = h1[r] & (c1 >= 0) & (t1[r] <= h[r].t);
+      const float hw = h[r].t * FFX_TIE_WIDEN;
+      const bool a0 = h0[r] & (c0 >= 0) & (t0[r] <= hw), a1 = h1[r] & (c1 >= 0) & (t1[r] <= hw);
       g0 |= a0;
       g1 |= a1;
       first1 |= a1 & (!a0 | (t1[r] < t0[r]));

@@ -1026,7 +1026,10 @@ static void closest_hit(const onode *nodes, const orec *recs, v3 o, v3 d, float 
   stack[sp++] = 0;
   while (sp) {
     const onode *nd = &nodes[stack[--sp]];
-    if (!box_hit(nd, o, id, tmin, h->t)) continue;
+    /* boxes are culled against the hit distance WIDENED by 3 ulp: a box that ends exactly on the hit (a flat box in a coordinate plane, which
+     * refit_rec's relative pad leaves as it is) has the entry distance (plane - o) * (1/d), rounded up to three times where t = T/det is rounded
+     * once, and may hold a triangle at the same t with a smaller id (tests/tie_scenes.py: sheets_far_from_their_plane) */
+    if (!box_hit(nd, o, id, tmin, h->t * 1.0000004f)) continue;
     if (nd->left < 0) {
       for (int i = 0; i < nd->count; ++i) {
         const orec *r = &recs[nd->first + i];
