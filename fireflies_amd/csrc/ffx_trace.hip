@@ -1157,16 +1157,31 @@ __device__ __forceinline__ void msel_into(int &dst, unsigned long long mask, int
   asm("v_cndmask_b32_e64 %0, %0, %1, %2" : "+v"(dst) : "v"(v), "s"(mask));
 }
 
-// Generic packet walk (min/max slab test, no assumption on direction signs) for R rays per lane.  The
-// kernels instantiate R = 1 only — a packed two-rays-per-lane variant was measured slower and removed —
-// and reach this loop for the rare packets whose rays disagree on a direction sign; everything else
-// takes the octant loops below.  Same apex triangle test, same results.
-template <bool ANY, int R>
-__device__ __forceinline__ void traverse_packet(const BvhNode *__restrict__ nodes, const TriApex *__restrict__ recs, const v3 (&o)[R], const v3 (&d)[R],
-                                                const float (&tmin)[R], const float (&tmax)[R], const bool (&active)[R], Hit (&h)[R], bool (&found)[R]) {
-  RayBox rb[R];
+// A scalar seen as an array of one.  The generic packet walk, shade_sample_pk and the two tile kernels were written for R rays
+// per lane and still run their single-trip loops over one-element arrays: the compiler turns such an array into registers only
+// after it has unrolled the loop, late in its pipeline, and with the same statements written straight-line every render kernel
+// that reaches them comes out different (other registers, spills moved both ways: tools/isa_same.py).  They keep that form
+// behind one-ray signatures until a change to these kernels is measured anyway.  For the same reason the walks take their ray
+// by const reference: by value the render kernels came out different too.
+template <typename T> __device__ __forceinline__ const T (&as1(const T &x))[1] { return reinterpret_cast<const T (&)[1]>(x); }
+template <typename T> __device__ __forceinline__ T (&as1(T &x))[1] { return reinterpret_cast<T (&)[1]>(x); }
+
+// Generic packet walk (min/max slab test, no assumption on direction signs), one ray per lane — a packed
+// two-rays-per-lane variant was measured slower and removed.  The kernels reach this loop for the rare
+// packets whose rays disagree on a direction sign and for the packets the 64-wide walk hands back;
+// everything else takes the octant loops below.  Same apex triangle test, same results.
+// (The body's one-element arrays and single-trip loops: see as1.)
+template <bool ANY>
+__device__ __forceinline__ void traverse_packet(const BvhNode *__restrict__ nodes, const TriApex *__restrict__ recs, const v3 &o_, const v3 &d_, const float &tmin_,
+                                                const float &tmax_, const bool &active_, Hit &h_, bool &found_) {
+  const v3 (&o)[1] = as1(o_), (&d)[1] = as1(d_);
+  const float (&tmin)[1] = as1(tmin_), (&tmax)[1] = as1(tmax_);
+  const bool (&active)[1] = as1(active_);
+  Hit (&h)[1] = as1(h_);
+  bool (&found)[1] = as1(found_);
+  RayBox rb[1];
 #pragma unroll
-  for (int r = 0; r < R; ++r) {
+  for (int r = 0; r < 1; ++r) {
     h[r].t = active[r] ? tmax[r] : -INFINITY; // an inactive ray fails every slab test
     h[r].prim = -1;
     h[r].shape = -1;
@@ -1186,11 +1201,11 @@ __device__ __forceinline__ void traverse_packet(const BvhNode *__restrict__ node
     const int c0 = ch.x, c1 = ch.y;
     const float lo0[3] = {q0.x, q0.y, q0.z}, hi0[3] = {q0.w, q1.x, q1.y};
     const float lo1[3] = {q1.z, q1.w, q2.x}, hi1[3] = {q2.y, q2.z, q2.w};
-    float t0[R], t1[R];
-    bool h0[R], h1[R];
+    float t0[1], t1[1];
+    bool h0[1], h1[1];
     bool any0 = false, any1 = false;
 #pragma unroll
-    for (int r = 0; r < R; ++r) {
+    for (int r = 0; r < 1; ++r) {
       h0[r] = slab(lo0, hi0, rb[r], tmin[r], h[r].t * FFX_TIE_WIDEN, t0[r]) & (c0 != FFX_EMPTY_CHILD);
       h1[r] = slab(lo1, hi1, rb[r], tmin[r], h[r].t * FFX_TIE_WIDEN, t1[r]) & (c1 != FFX_EMPTY_CHILD);
       any0 |= h0[r];
@@ -1213,10 +1228,10 @@ __device__ __forceinline__ void traverse_packet(const BvhNode *__restrict__ node
           // tri_hit_apex): the rays of a packet nearly always fail together at the first barycentric
           // test, so the remaining dot product and the IEEE division are skipped for the whole wave.
           // (U <= det is implied by V >= 0 and U + V <= det.)
-          bool p1[R], neg[R], any1 = false;
-          float detA[R], Us[R];
+          bool p1[1], neg[1], any1 = false;
+          float detA[1], Us[1];
 #pragma unroll
-          for (int r = 0; r < R; ++r) {
+          for (int r = 0; r < 1; ++r) {
             const float det = vdot(d[r], A);
             const float U = vdot(d[r], B);
             neg[r] = det < 0.f;
@@ -1226,9 +1241,9 @@ __device__ __forceinline__ void traverse_packet(const BvhNode *__restrict__ node
             any1 |= p1[r];
           }
           if (wballot(any1) == 0ull) continue;
-          bool p2[R], any2 = false;
+          bool p2[1], any2 = false;
 #pragma unroll
-          for (int r = 0; r < R; ++r) {
+          for (int r = 0; r < 1; ++r) {
             const float Vv = vdot(d[r], C);
             const float Vs = neg[r] ? -Vv : Vv;
             p2[r] = p1[r] & (Vs >= 0.f) & (Us[r] + Vs <= detA[r]);
@@ -1236,7 +1251,7 @@ __device__ __forceinline__ void traverse_packet(const BvhNode *__restrict__ node
           }
           if (wballot(any2) == 0ull) continue;
 #pragma unroll
-          for (int r = 0; r < R; ++r) {
+          for (int r = 0; r < 1; ++r) {
             const float t = (neg[r] ? -Tq : Tq) / detA[r];
             const bool hit = p2[r] & (t > tmin[r]);
             if (ANY) {
@@ -1257,12 +1272,12 @@ __device__ __forceinline__ void traverse_packet(const BvhNode *__restrict__ node
     if (ANY) {
       bool undecided = false;
 #pragma unroll
-      for (int r = 0; r < R; ++r) undecided |= active[r] & !found[r];
+      for (int r = 0; r < 1; ++r) undecided |= active[r] & !found[r];
       if (wballot(undecided) == 0ull) break; // every ray of the packet is decided
     }
     bool g0 = false, g1 = false, first1 = false, first0 = false;
 #pragma unroll
-    for (int r = 0; r < R; ++r) {
+    for (int r = 0; r < 1; ++r) {
       const float hw = h[r].t * FFX_TIE_WIDEN;
       const bool a0 = h0[r] & (c0 >= 0) & (t0[r] <= hw), a1 = h1[r] & (c1 >= 0) & (t1[r] <= hw);
       g0 |= a0;
@@ -1302,9 +1317,6 @@ __device__ __forceinline__ void traverse_packet(const BvhNode *__restrict__ node
 // alone decides the result — is unchanged.  The loop is compiled once per octant (OCT bit a set =
 // direction component a negative) and selected per walk by a wave-uniform switch; packets with mixed
 // signs take the generic loop.
-#ifndef FFX_OCTANT_LOOPS
-#define FFX_OCTANT_LOOPS 1
-#endif
 #ifndef FFX_PK1_WAVES
 // resident waves per SIMD the 1-ray packet kernels are register-budgeted for.  8 -> 64 VGPRs / 78 SGPRs.  With
 // the 64-wide walk the hot loops fit: what spills (9 dwords) are loop-invariant addresses and pixel indices,
@@ -1313,7 +1325,6 @@ __device__ __forceinline__ void traverse_packet(const BvhNode *__restrict__ node
 // resident waves hide it.  (The binary walk preferred 7: its spills were inside the node loop.)
 #define FFX_PK1_WAVES 8
 #endif
-__device__ __forceinline__ constexpr bool octant_loops() { return FFX_OCTANT_LOOPS != 0; }
 // `scale` = 1/tmax of the ray: the octant box test works in units of the ray's own parameter range, so
 // every distance it compares lies in [0, 1] (see slab_oct).  The scale multiplies 1/d once, hence enters
 // plane*m and o*m alike: a purely relative change of the results, no new cancellation error.
@@ -1563,22 +1574,21 @@ __device__ __forceinline__ void traverse_packet_oct(const BvhNode *__restrict__ 
 // `tq0` = element index of leaf slot 0.
 struct WideScene { const WideChild *elems; const WideHdr *hdr; int32_t root; uint32_t tq0; };
 #define FFX_WSTACK (63 * FFX_WIDE_MAX_DEPTH + 6)
-// per-walk constants, uniform across the wave: tn_a = fma(q_near_a, mN_a, -kN_a), tf_a = fma(q_far_a, mF_a, -kF_a)
-// (GEN walks only) a second entry term per axis from the FAR plane, tg_a = fma(q_far_a, mG_a, -kG_a): an axis on
-// which the packet's rays disagree in sign has two entry bounds and no exit bound (see make_widepk).
-struct WidePk { v3 mN, kN, mF, kF, mG, kG; wmask neg[3]; };
+// per-walk constants, uniform across the wave: tn_a = fma(q_near_a, mN_a, -kN_a), tf_a = fma(q_far_a, mF_a, -kF_a).
+// Packets whose rays disagree on a direction sign go to the binary walk (`dis != 0` in traverse_wide).  A wide
+// walk for them was tried — a mixed axis as a wedge with two entry bounds and no exit bound — and removed; dropping
+// the axis instead is conservative too, but a packet with two mixed axes — a pixel next to the image centre — then
+// walks every box in its depth range: one such wave took 7 ms.
+struct WidePk { v3 mN, kN, mF, kF; };
 
 // wave-wide min / max of the bit patterns of NON-NEGATIVE floats (they order like unsigned integers): four
 // fused DPP steps inside each row of 16 lanes (quad swap, quad-pair swap, half-row mirror, row mirror: one
 // VALU instruction each; the s_nop covers the "VALU wrote the VGPR a DPP op reads" hazard the compiler
-// cannot see inside an asm statement), then the four row results are combined on the scalar ALU.
-#define FFX_DPP_STEP(OP, CTRL) asm("s_nop 1\n\t" OP " %0, %0, %0 " CTRL " row_mask:0xf bank_mask:0xf" : "+v"(v))
-__device__ __forceinline__ uint32_t smin_u32(uint32_t a, uint32_t b) { uint32_t r; asm("s_min_u32 %0, %1, %2" : "=s"(r) : "s"(a), "s"(b) : "scc"); return r; }
-__device__ __forceinline__ uint32_t smax_u32(uint32_t a, uint32_t b) { uint32_t r; asm("s_max_u32 %0, %1, %2" : "=s"(r) : "s"(a), "s"(b) : "scc"); return r; }
+// cannot see inside an asm statement), then row_bcast:15 / :31 carry the row results to lane 63 (see
+// wave_reduce3_nn) — one readlane, no scalar min/max.
 template <bool MAX>
 __device__ __forceinline__ uint32_t wave_reduce_nn(uint32_t v) {
-  // ONE asm block (the compiler pads every asm statement with its own hazard nop): four butterfly steps inside the rows,
-  // row_bcast:15 / :31 carry the row results to lane 63 (see wave_reduce3_nn) — one readlane, no scalar min/max
+  // ONE asm block (the compiler pads every asm statement with its own hazard nop)
 #define FFX_R1(OP, CTRL, MASK) "s_nop 1\n\t" OP " %0, %0, %0 " CTRL " row_mask:" MASK " bank_mask:0xf\n\t"
 #define FFX_R1_ALL(OP) FFX_R1(OP, "quad_perm:[1,0,3,2]", "0xf") FFX_R1(OP, "quad_perm:[2,3,0,1]", "0xf") FFX_R1(OP, "row_half_mirror", "0xf") \
     FFX_R1(OP, "row_mirror", "0xf") FFX_R1(OP, "row_bcast:15", "0xa") FFX_R1(OP, "row_bcast:31", "0xc")
@@ -1611,121 +1621,47 @@ __device__ __forceinline__ void wave_reduce3_nn(uint32_t (&v)[3]) {
 __device__ __forceinline__ uint32_t mbcnt64(wmask m) { return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u)); }
 __device__ __forceinline__ int wff1(wmask m) { return __builtin_ctzll(m); }
 
-// the packet constants of one walk.  `aid[r]` = |scaled 1/d| of ray r per axis, `oct[r]` its direction signs,
-// `oct0` the packet's octant (signs of its first active ray), `mixed` the axes on which the active rays
-// disagree in sign.  On a mixed axis the packet is a wedge that opens both ways: it reaches a box beyond
-// `lo` no earlier than (lo - o) * min(1/d+) and a box before `hi` no earlier than (o - hi) * min(1/|d-|), and
-// it never leaves the slab for good — two entry bounds, no exit bound.  (Dropping the axis instead is
-// conservative too, but a packet with two mixed axes — a pixel next to the image centre — then walks every
-// box in its depth range: one such wave took 7 ms.)
-template <int R>
-__device__ __forceinline__ WidePk make_widepk(const WideHdr *__restrict__ hdr, v3 o, const v3 (&aid)[R], const uint32_t (&oct)[R], const wmask (&active)[R],
-                                              uint32_t oct0, uint32_t mixed, float &spread) {
-  float dmax_all = 0.f, dspread = 0.f; // largest |d_a| and largest (max |d_a| - min |d_a|) over the axes, in units of 1/scale
-  const float org[3] = {0.f, 0.f, 0.f}, step[3] = {1.f, 1.f, 1.f}; // float boxes: no grid to fold in
+// the packet constants of one walk.  `aid` = |scaled 1/d| of the lane's ray per axis, `oct0` the packet's octant
+// (the direction signs its active rays share); `spread` > FFX_WIDE_FAT: a fat packet (see traverse_wide).
+__device__ __forceinline__ WidePk make_widepk(const v3 &o, const v3 &aid, const wmask &active, uint32_t oct0, float &spread) {
   const float oo[3] = {o.x, o.y, o.z};
-  float mN[3], kN[3], mF[3], kF[3], mG[3], kG[3];
-  const float k22 = 2.384185791015625e-07f, k21 = 4.76837158203125e-07f, kw = 1.0000004f;
+  float mN[3], kN[3], mF[3], kF[3];
+  const float kw = 1.0000004f;
   WidePk pk;
-  // smallest / largest |1/d_a| over the active rays; on a mixed axis: the smallest of each sign
-  uint32_t lo[3], hi[3], lo2[3];
+  // smallest / largest |1/d_a| over the active rays, the three axes in interleaved chains
+  uint32_t lo[3], hi[3];
 #pragma unroll
   for (int a = 0; a < 3; ++a) {
-    const bool is_mixed = (mixed >> a) & 1u;
-    lo[a] = 0x7f800000u; hi[a] = 0u; lo2[a] = 0x7f800000u; // +inf, 0, +inf
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-      const uint32_t v = __float_as_uint(a == 0 ? aid[r].x : (a == 1 ? aid[r].y : aid[r].z));
-      const wmask negr = __builtin_amdgcn_uicmp((oct[r] >> a) & 1u, 0u, 33);
-      const wmask first = is_mixed ? (active[r] & ~negr) : active[r];
-      const uint32_t vl = msel(first, v, 0x7f800000u), vh = msel(active[r], v, 0u), vl2 = msel(active[r] & negr, v, 0x7f800000u);
-      if (R == 1) { lo[a] = vl; hi[a] = vh; lo2[a] = vl2; } // (aid is finite: safe_rcp_dir clamps tiny components)
-      else {
-        lo[a] = lo[a] < vl ? lo[a] : vl;
-        hi[a] = hi[a] > vh ? hi[a] : vh;
-        lo2[a] = lo2[a] < vl2 ? lo2[a] : vl2;
-      }
-    }
+    const uint32_t v = __float_as_uint(a == 0 ? aid.x : (a == 1 ? aid.y : aid.z));
+    lo[a] = msel(active, v, 0x7f800000u); // +inf  (aid is finite: safe_rcp_dir clamps tiny components)
+    hi[a] = msel(active, v, 0u);
   }
-  if (mixed == 0u) { // (a compile-time constant at the call sites) the three axes in interleaved chains
-    wave_reduce3_nn<false>(lo);
-    wave_reduce3_nn<true>(hi);
-    // Everything from here on is wave-uniform float arithmetic, which this machine can only do on the vector ALU at the
-    // 4-cycle rate of scalar-operand instructions: it is written to be short.  Signs are applied to the bit patterns
-    // (scalar ALU); the two paddings of each side are one fma (2^-20 >= 2^-22 + 2^-21 + the roundings they cover:
-    // of o * m, of m * k and of the box test's own fma); the fat-packet measure
-    //     max_a (1/mn_a - 1/mx_a) / max_a (1/mn_a) <= FAT   <=>   for all a:  M (mx_a - mn_a) <= FAT mn_a mx_a,  M = min_a mn_a
-    // needs no reciprocal.
-    const float PAD = 9.5367431640625e-07f; // 2^-20
-    const float M = fminf(__uint_as_float(lo[0]), fminf(__uint_as_float(lo[1]), __uint_as_float(lo[2])));
-    bool fat = false;
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-      const uint32_t sgn = ((oct0 >> a) & 1u) << 31;
-      pk.neg[a] = sgn ? ~0ull : 0ull;
-      const float mn = __uint_as_float(lo[a]), mx = __uint_as_float(hi[a]);
-      fat |= M * (mx - mn) > FFX_WIDE_FAT * (mn * mx);
-      const float sN = __uint_as_float(lo[a] ^ sgn), sFk = __uint_as_float(hi[a] ^ sgn) * kw;
-      const float oidn = oo[a] * sN, oidf = oo[a] * sFk;
-      mN[a] = sN;
-      kN[a] = fmaf(fabsf(oidn), PAD, oidn);   // the entry can only move earlier
-      mF[a] = sFk;
-      kF[a] = fmaf(-fabsf(oidf), PAD, oidf);  // the exit only later (on top of the far-side widening kw)
-      mG[a] = 0.f;
-      kG[a] = 1e30f;
-    }
-    pk.mN = V3(mN[0], mN[1], mN[2]); pk.kN = V3(kN[0], kN[1], kN[2]);
-    pk.mF = V3(mF[0], mF[1], mF[2]); pk.kF = V3(kF[0], kF[1], kF[2]);
-    pk.mG = V3(mG[0], mG[1], mG[2]); pk.kG = V3(kG[0], kG[1], kG[2]);
-    spread = fat ? 1.0f : 0.0f;
-    return pk;
-  } else {
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-      lo[a] = wave_reduce_nn<false>(lo[a]);
-      if ((mixed >> a) & 1u) lo2[a] = wave_reduce_nn<false>(lo2[a]);
-      else hi[a] = wave_reduce_nn<true>(hi[a]);
-    }
-  }
+  wave_reduce3_nn<false>(lo);
+  wave_reduce3_nn<true>(hi);
+  // Everything from here on is wave-uniform float arithmetic, which this machine can only do on the vector ALU at the
+  // 4-cycle rate of scalar-operand instructions: it is written to be short.  Signs are applied to the bit patterns
+  // (scalar ALU); the two paddings of each side are one fma (2^-20 >= 2^-22 + 2^-21 + the roundings they cover:
+  // of o * m, of m * k and of the box test's own fma); the fat-packet measure
+  //     max_a (1/mn_a - 1/mx_a) / max_a (1/mn_a) <= FAT   <=>   for all a:  M (mx_a - mn_a) <= FAT mn_a mx_a,  M = min_a mn_a
+  // needs no reciprocal.
+  const float PAD = 9.5367431640625e-07f; // 2^-20
+  const float M = fminf(__uint_as_float(lo[0]), fminf(__uint_as_float(lo[1]), __uint_as_float(lo[2])));
+  bool fat = false;
 #pragma unroll
   for (int a = 0; a < 3; ++a) {
-    const bool is_mixed = (mixed >> a) & 1u;
-    const float mn = __uint_as_float(lo[a]);
-    const bool negd = !is_mixed && ((oct0 >> a) & 1u);
-    pk.neg[a] = negd ? ~0ull : 0ull;
-    const float sN = negd ? -mn : mn;
-    // near side (same padding as make_rayoct: the entry can only move earlier)
-    const float oidn = oo[a] * sN, cN = oidn + fabsf(oidn) * k22;
-    const float gn = org[a] * sN;
-    mN[a] = step[a] * sN;
-    kN[a] = (cN - gn) + (fabsf(cN) + fabsf(gn)) * k21;
-    if (!is_mixed) {
-      // far side, widened (make_rayslab)
-      const float mx = __uint_as_float(hi[a]);
-      const float dhi = __builtin_amdgcn_rcpf(mn), dlo = __builtin_amdgcn_rcpf(mx); // |d_a| range of the packet
-      dmax_all = fmaxf(dmax_all, dhi);
-      dspread = fmaxf(dspread, dhi - dlo);
-      const float sF = negd ? -mx : mx;
-      const float oidf = oo[a] * sF, cF = (oidf - fabsf(oidf) * k22) * kw;
-      const float sFk = sF * kw, gf = org[a] * sFk;
-      mF[a] = step[a] * sFk;
-      kF[a] = (cF - gf) - (fabsf(cF) + fabsf(gf)) * k21;
-      mG[a] = 0.f;
-      kG[a] = 1e30f; // tg_a = -1e30
-    } else {
-      // second entry bound from the far (= hi) plane: (o - x) * m2 = fma(q, -step * m2, -(org * m2 - o * m2))
-      const float m2 = __uint_as_float(lo2[a]);
-      const float og = oo[a] * m2, gg = org[a] * m2;
-      mG[a] = -(step[a] * m2);
-      kG[a] = (gg - og) + (fabsf(gg) + fabsf(og)) * k21;
-      mF[a] = 0.f;
-      kF[a] = -1e30f; // tf_a = +1e30
-    }
+    const uint32_t sgn = ((oct0 >> a) & 1u) << 31;
+    const float mn = __uint_as_float(lo[a]), mx = __uint_as_float(hi[a]);
+    fat |= M * (mx - mn) > FFX_WIDE_FAT * (mn * mx);
+    const float sN = __uint_as_float(lo[a] ^ sgn), sFk = __uint_as_float(hi[a] ^ sgn) * kw;
+    const float oidn = oo[a] * sN, oidf = oo[a] * sFk;
+    mN[a] = sN;
+    kN[a] = fmaf(fabsf(oidn), PAD, oidn);   // the entry can only move earlier
+    mF[a] = sFk;
+    kF[a] = fmaf(-fabsf(oidf), PAD, oidf);  // the exit only later (on top of the far-side widening kw)
   }
   pk.mN = V3(mN[0], mN[1], mN[2]); pk.kN = V3(kN[0], kN[1], kN[2]);
   pk.mF = V3(mF[0], mF[1], mF[2]); pk.kF = V3(kF[0], kF[1], kF[2]);
-  pk.mG = V3(mG[0], mG[1], mG[2]); pk.kG = V3(kG[0], kG[1], kG[2]);
-  spread = dspread * __builtin_amdgcn_rcpf(dmax_all);
+  spread = fat ? 1.0f : 0.0f;
   return pk;
 }
 
@@ -1734,27 +1670,20 @@ __device__ __forceinline__ WidePk make_widepk(const WideHdr *__restrict__ hdr, v
 #ifndef FFX_WIDE_MAX_WORK
 #define FFX_WIDE_MAX_WORK 96 // steps + exact triangle tests of one walk (typical: 7 + 7; measured 24 / 48 / 64 / 96 / 192: 0.77 / 0.70 / 0.65 / 0.65 / 0.65 ms vocal fold, 4.2 / 3.5 / 3.4 / 3.3 / 3.3 ms colon)
 #endif
-template <bool ANY, int OCT, int R>
-__device__ __forceinline__ bool traverse_wide_oct(const WideScene &ws, const TriApex *__restrict__ recs, const WidePk &pk, const v3 (&d)[R], const float (&tmin)[R],
-                                                  const float (&tmax)[R], const float (&sw)[R], const wmask (&active)[R], Hit (&h)[R], wmask (&occluded)[R],
-                                                  uint2 *__restrict__ stack) {
+template <bool ANY, int OCT>
+__device__ __forceinline__ bool traverse_wide_oct(const WideScene &ws, const TriApex *__restrict__ recs, const WidePk &pk, const v3 &d, const float &tmin, const float &tmax,
+                                                  const float &sw, const wmask &active, Hit &h, wmask &occluded, uint2 *__restrict__ stack) {
   const uint32_t lane16 = (threadIdx.x & 63u) << FFX_WIDE_ELEM_SHIFT; // byte offset of this lane's element within a node / cluster
   int budget = FFX_WIDE_MAX_WORK;
-#pragma unroll
-  for (int r = 0; r < R; ++r) {
-    h[r].t = msel(active[r], tmax[r], -INFINITY);
-    h[r].prim = -1;
-    h[r].shape = -1;
-    h[r].slot = -1;
-    occluded[r] = 0ull;
-  }
+  h.t = msel(active, tmax, -INFINITY);
+  h.prim = -1;
+  h.shape = -1;
+  h.slot = -1;
+  occluded = 0ull;
   // the packet's hit distance in box-test units (the largest over its rays: a box matters while ANY ray can
   // still reach it), as the bit pattern of a non-negative float; refreshed whenever a ray's hit improves
   auto packet_hts = [&]() -> uint32_t {
-    float m = 0.f;
-#pragma unroll
-    for (int r = 0; r < R; ++r) m = fmaxf(m, h[r].t * sw[r]); // -inf (inactive / occluded) drops out against 0
-    return wave_reduce_nn<true>(__float_as_uint(m));
+    return wave_reduce_nn<true>(__float_as_uint(fmaxf(0.f, h.t * sw))); // -inf (inactive / occluded) drops out against 0
   };
   // before any hit every active ray's distance is its tmax, which the unit of the box test maps to 0.999 * (1 + a few
   // ulp) by construction (sw = 0.999 / tmax * 1.0000002): a constant just above that is a valid (conservative) packet
@@ -1798,20 +1727,11 @@ __device__ __forceinline__ bool traverse_wide_oct(const WideScene &ws, const Tri
     const uint4 q = *reinterpret_cast<const uint4 *>(ebase + voff + 16); // hi.y, hi.z, ref, pad  (q.z = ref)
     const float lx = qa.x, ly = qa.y, lz = qa.z, hx = qa.w, hy = __uint_as_float(q.x), hz = __uint_as_float(q.y);
 #define FFX_QREF q.z
-    float nx, ny, nz, fx, fy, fz, tn;
-    if constexpr (OCT < 8) { // which plane is entered first is known at compile time
-      nx = (OCT & 1) ? hx : lx; fx = (OCT & 1) ? lx : hx;
-      ny = (OCT & 2) ? hy : ly; fy = (OCT & 2) ? ly : hy;
-      nz = (OCT & 4) ? hz : lz; fz = (OCT & 4) ? lz : hz;
-      tn = vmax3_sat(fmaf(nx, pk.mN.x, -pk.kN.x), fmaf(ny, pk.mN.y, -pk.kN.y), fmaf(nz, pk.mN.z, -pk.kN.z));
-    } else { // generic instance (packets with mixed direction signs): run-time plane choice, second entry terms
-      nx = msel(pk.neg[0], hx, lx); fx = msel(pk.neg[0], lx, hx);
-      ny = msel(pk.neg[1], hy, ly); fy = msel(pk.neg[1], ly, hy);
-      nz = msel(pk.neg[2], hz, lz); fz = msel(pk.neg[2], lz, hz);
-      const float t1 = fmaxf(fmaxf(fmaf(nx, pk.mN.x, -pk.kN.x), fmaf(ny, pk.mN.y, -pk.kN.y)), fmaf(nz, pk.mN.z, -pk.kN.z));
-      const float t2 = fmaxf(fmaxf(fmaf(fx, pk.mG.x, -pk.kG.x), fmaf(fy, pk.mG.y, -pk.kG.y)), fmaf(fz, pk.mG.z, -pk.kG.z));
-      tn = vmax3_sat(t1, t2, t2);
-    }
+    // which plane is entered first is known at compile time
+    const float nx = (OCT & 1) ? hx : lx, fx = (OCT & 1) ? lx : hx;
+    const float ny = (OCT & 2) ? hy : ly, fy = (OCT & 2) ? ly : hy;
+    const float nz = (OCT & 4) ? hz : lz, fz = (OCT & 4) ? lz : hz;
+    const float tn = vmax3_sat(fmaf(nx, pk.mN.x, -pk.kN.x), fmaf(ny, pk.mN.y, -pk.kN.y), fmaf(nz, pk.mN.z, -pk.kN.z));
     const float tf = vmin2_s(vmin3(fmaf(fx, pk.mF.x, -pk.kF.x), fmaf(fy, pk.mF.y, -pk.kF.y), fmaf(fz, pk.mF.z, -pk.kF.z)), hb);
     wmask hit = m_le(tn, tf);
     FFX_TSTOP(tw, ANY ? 8 : 0);
@@ -1842,46 +1762,35 @@ __device__ __forceinline__ bool traverse_wide_oct(const WideScene &ws, const Tri
         const v3 B = V3(__int_as_float(r8.s3), __int_as_float(r8.s4), __int_as_float(r8.s5));
         const v3 C = V3(__int_as_float(r8.s6), __int_as_float(r8.s7), __int_as_float(r4.x));
         const float T = __int_as_float(r4.y);
-        wmask improved = 0ull;
-#pragma unroll
-        for (int r = 0; r < R; ++r) {
-          // apex test, staged with wave-uniform early-outs (identical arithmetic to traverse_packet_oct)
-          const float det = vdot(d[r], A);
-          const float U = vdot(d[r], B);
-          const wmask neg = m_lt(det, 0.f);
-          const float detA = fabsf(det);
-          const float Us = msel(neg, -U, U);
-          const wmask alive = ANY ? (active[r] & ~occluded[r]) : active[r];
-          const wmask p1 = alive & m_gt(detA, 0.f) & m_ge(Us, 0.f) & m_le(Us, detA);
-          if (p1 == 0ull) continue;
-          FFX_STAT(ANY ? 7 : 3);
-          const float Vv = vdot(d[r], C);
-          const float Vs = msel(neg, -Vv, Vv);
-          const wmask p2 = p1 & m_ge(Vs, 0.f) & m_le(Us + Vs, detA);
-          if (p2 == 0ull) continue;
-          const float t = msel(neg, -T, T) / detA;
-          const wmask hitm = p2 & m_gt(t, tmin[r]);
-          if (ANY) {
-            const wmask occ = hitm & m_lt(t, tmax[r]);
-            occluded[r] |= occ;
-            msel_into(h[r].t, occ, -INFINITY);
-            improved |= occ;
-          } else {
-            const wmask better = hitm & (m_lt(t, h[r].t) | (m_eq(t, h[r].t) & m_ult((uint32_t)prim, (uint32_t)h[r].prim)));
-            msel_into(h[r].t, better, t);
-            msel_into(h[r].prim, better, prim);
-            msel_into(h[r].slot, better, (int)slot);
-            improved |= better;
-          }
-        }
-        if (improved != 0ull) {
-          if (ANY) {
-            wmask left = 0ull;
-#pragma unroll
-            for (int r = 0; r < R; ++r) left |= active[r] & ~occluded[r];
-            if (left == 0ull) { go = false; hit = 0ull; } // every ray of the packet is decided: leave the cluster, end the walk
-            // (the undecided rays keep their full length: the packet's hit distance does not change)
-          } else {
+        // apex test, staged with wave-uniform early-outs (identical arithmetic to traverse_packet_oct)
+        const float det = vdot(d, A);
+        const float U = vdot(d, B);
+        const wmask neg = m_lt(det, 0.f);
+        const float detA = fabsf(det);
+        const float Us = msel(neg, -U, U);
+        const wmask alive = ANY ? (active & ~occluded) : active;
+        const wmask p1 = alive & m_gt(detA, 0.f) & m_ge(Us, 0.f) & m_le(Us, detA);
+        if (p1 == 0ull) continue;
+        FFX_STAT(ANY ? 7 : 3);
+        const float Vv = vdot(d, C);
+        const float Vs = msel(neg, -Vv, Vv);
+        const wmask p2 = p1 & m_ge(Vs, 0.f) & m_le(Us + Vs, detA);
+        if (p2 == 0ull) continue;
+        const float t = msel(neg, -T, T) / detA;
+        const wmask hitm = p2 & m_gt(t, tmin);
+        if (ANY) {
+          const wmask occ = hitm & m_lt(t, tmax);
+          occluded |= occ;
+          msel_into(h.t, occ, -INFINITY);
+          // every ray of the packet decided: leave the cluster, end the walk (else the undecided rays keep their full
+          // length: the packet's hit distance does not change)
+          if (occ != 0ull && (active & ~occluded) == 0ull) { go = false; hit = 0ull; }
+        } else {
+          const wmask better = hitm & (m_lt(t, h.t) | (m_eq(t, h.t) & m_ult((uint32_t)prim, (uint32_t)h.prim)));
+          msel_into(h.t, better, t);
+          msel_into(h.prim, better, prim);
+          msel_into(h.slot, better, (int)slot);
+          if (better != 0ull) {
             hb = packet_hts();
             hit &= m_le(tn, __uint_as_float(hb)); // the remaining triangles of this cluster against the shorter rays
           }
@@ -1923,118 +1832,93 @@ __device__ __forceinline__ bool traverse_wide_oct(const WideScene &ws, const Tri
 }
 
 #undef FFX_QREF
-// wide walk of R rays per lane that share their origin `o` (the apex the records `recs` were prepared for).
+// wide walk of a packet whose rays share their origin `o` (the apex the records `recs` were prepared for).
 // Packets the interval test is bad at go to the binary walk instead (its box tests are per ray): packets whose
 // rays disagree on a direction sign, packets whose directions spread more than FFX_WIDE_FAT of their length
 // (the samples of a pixel on a depth discontinuity, seen from an emitter: a fan whose bounding wedge
 // contains hundreds of boxes no ray comes near — colon, 1024^2: 15.9 ms with every packet on the wide walk,
 // 4.2 ms on the binary walk), and walks that exceed FFX_WIDE_MAX_WORK.  Results are identical either way.
-template <bool ANY, int R>
-__device__ __forceinline__ void traverse_wide(const WideScene &ws, const BvhNode *__restrict__ nodes, const TriApex *__restrict__ recs, const v3 (&o)[R],
-                                              const v3 (&d)[R], const float (&tmin)[R], const float (&tmax)[R], const bool (&act)[R], Hit (&h)[R], bool (&found)[R],
-                                              uint2 *__restrict__ stack) {
+template <bool ANY>
+__device__ __forceinline__ void traverse_wide(const WideScene &ws, const BvhNode *__restrict__ nodes, const TriApex *__restrict__ recs, const v3 &o, const v3 &d,
+                                              const float &tmin, const float &tmax, const bool &act, Hit &h, bool &found, uint2 *__restrict__ stack) {
   FFX_TSTART(ts);
-  wmask active[R], any_active = 0ull;
-#pragma unroll
-  for (int r = 0; r < R; ++r) { active[r] = wballot(act[r]); any_active |= active[r]; }
-  if (any_active == 0ull) {
-#pragma unroll
-    for (int r = 0; r < R; ++r) { h[r].t = -INFINITY; h[r].prim = -1; h[r].shape = -1; h[r].slot = -1; found[r] = false; }
+  const wmask active = wballot(act);
+  if (active == 0ull) {
+    h.t = -INFINITY; h.prim = -1; h.shape = -1; h.slot = -1; found = false;
     return;
   }
-  v3 aid[R];
-  float sw[R];
-  uint32_t oct[R];
-#pragma unroll
-  for (int r = 0; r < R; ++r) {
-    // unit of the box test: tmax maps to 0.999 (traverse_packet1)
-    const float scale = 0.999f * __builtin_amdgcn_rcpf(tmax[r]);
-    const v3 id = V3(safe_rcp_dir(d[r].x) * scale, safe_rcp_dir(d[r].y) * scale, safe_rcp_dir(d[r].z) * scale);
-    oct[r] = (__float_as_uint(id.x) >> 31) | ((__float_as_uint(id.y) >> 31) << 1) | ((__float_as_uint(id.z) >> 31) << 2);
-    aid[r] = V3(fabsf(id.x), fabsf(id.y), fabsf(id.z));
-    sw[r] = scale * 1.0000002f;
-  }
+  // unit of the box test: tmax maps to 0.999 (traverse_packet_any)
+  const float scale = 0.999f * __builtin_amdgcn_rcpf(tmax);
+  const v3 id = V3(safe_rcp_dir(d.x) * scale, safe_rcp_dir(d.y) * scale, safe_rcp_dir(d.z) * scale);
+  const uint32_t oct = (__float_as_uint(id.x) >> 31) | ((__float_as_uint(id.y) >> 31) << 1) | ((__float_as_uint(id.z) >> 31) << 2);
+  const v3 aid = V3(fabsf(id.x), fabsf(id.y), fabsf(id.z));
+  const float sw = scale * 1.0000002f;
   // the packet's octant: that of its first active ray
-  uint32_t oct0 = 0;
-  {
-    bool got = false;
-#pragma unroll
-    for (int r = 0; r < R; ++r)
-      if (!got && active[r] != 0ull) { oct0 = (uint32_t)__builtin_amdgcn_readlane((int)oct[r], wff1(active[r])); got = true; }
-  }
-  wmask dis = 0ull;
-#pragma unroll
-  for (int r = 0; r < R; ++r) dis |= active[r] & __builtin_amdgcn_uicmp(oct[r], oct0, 33);
+  const uint32_t oct0 = (uint32_t)__builtin_amdgcn_readlane((int)oct, wff1(active));
+  const wmask dis = active & __builtin_amdgcn_uicmp(oct, oct0, 33);
   bool done = false;
   if (dis == 0ull) {
     float spread;
-    const WidePk pk = make_widepk<R>(ws.hdr, o[0], aid, oct, active, oct0, 0u, spread);
+    const WidePk pk = make_widepk(o, aid, active, oct0, spread);
     FFX_TSTOP(ts, ANY ? 12 : 4);
     if (spread <= FFX_WIDE_FAT) {
-      wmask occ[R];
+      wmask occ;
       switch (oct0) { // wave-uniform
-        case 0: done = traverse_wide_oct<ANY, 0, R>(ws, recs, pk, d, tmin, tmax, sw, active, h, occ, stack); break;
-        case 1: done = traverse_wide_oct<ANY, 1, R>(ws, recs, pk, d, tmin, tmax, sw, active, h, occ, stack); break;
-        case 2: done = traverse_wide_oct<ANY, 2, R>(ws, recs, pk, d, tmin, tmax, sw, active, h, occ, stack); break;
-        case 3: done = traverse_wide_oct<ANY, 3, R>(ws, recs, pk, d, tmin, tmax, sw, active, h, occ, stack); break;
-        case 4: done = traverse_wide_oct<ANY, 4, R>(ws, recs, pk, d, tmin, tmax, sw, active, h, occ, stack); break;
-        case 5: done = traverse_wide_oct<ANY, 5, R>(ws, recs, pk, d, tmin, tmax, sw, active, h, occ, stack); break;
-        case 6: done = traverse_wide_oct<ANY, 6, R>(ws, recs, pk, d, tmin, tmax, sw, active, h, occ, stack); break;
-        default: done = traverse_wide_oct<ANY, 7, R>(ws, recs, pk, d, tmin, tmax, sw, active, h, occ, stack); break;
+        case 0: done = traverse_wide_oct<ANY, 0>(ws, recs, pk, d, tmin, tmax, sw, active, h, occ, stack); break;
+        case 1: done = traverse_wide_oct<ANY, 1>(ws, recs, pk, d, tmin, tmax, sw, active, h, occ, stack); break;
+        case 2: done = traverse_wide_oct<ANY, 2>(ws, recs, pk, d, tmin, tmax, sw, active, h, occ, stack); break;
+        case 3: done = traverse_wide_oct<ANY, 3>(ws, recs, pk, d, tmin, tmax, sw, active, h, occ, stack); break;
+        case 4: done = traverse_wide_oct<ANY, 4>(ws, recs, pk, d, tmin, tmax, sw, active, h, occ, stack); break;
+        case 5: done = traverse_wide_oct<ANY, 5>(ws, recs, pk, d, tmin, tmax, sw, active, h, occ, stack); break;
+        case 6: done = traverse_wide_oct<ANY, 6>(ws, recs, pk, d, tmin, tmax, sw, active, h, occ, stack); break;
+        default: done = traverse_wide_oct<ANY, 7>(ws, recs, pk, d, tmin, tmax, sw, active, h, occ, stack); break;
       }
-#pragma unroll
-      for (int r = 0; r < R; ++r) found[r] = __builtin_amdgcn_inverse_ballot_w64(occ[r]);
+      found = __builtin_amdgcn_inverse_ballot_w64(occ);
     }
   }
   if (!done) {
     FFX_STAT(ANY ? 30 : 26);
-    traverse_packet<ANY, R>(nodes, recs, o, d, tmin, tmax, act, h, found); // binary walk, per-ray box tests
+    traverse_packet<ANY>(nodes, recs, o, d, tmin, tmax, act, h, found); // binary walk, per-ray box tests
   }
 }
 
-// one ray per lane: pick the octant loop if the packet's active rays agree on their direction signs
-template <bool ANY>
-__device__ __forceinline__ void traverse_packet1(const BvhNode *__restrict__ nodes, const TriApex *__restrict__ recs, const v3 (&o)[1], const v3 (&d)[1],
-                                                 const float (&tmin)[1], const float (&tmax)[1], const bool (&active)[1], Hit (&h)[1], bool (&found)[1]) {
-  const wmask am = wballot(active[0]);
+// dispatch: WIDE — the 64-wide walk (default); otherwise the binary walks: the octant loop if the packet's
+// active rays agree on their direction signs, else the generic loop.  All packet walks are APEX walks (their
+// rays share the origin `o` whose records `arecs` were written by k_apex_records).
+template <bool ANY, bool WIDE>
+__device__ __forceinline__ void traverse_packet_any(const BvhNode *__restrict__ nodes, const TriApex *__restrict__ arecs, const WideScene &ws, uint2 *__restrict__ stack,
+                                                    const v3 &o, const v3 &d, const float &tmin, const float &tmax, const bool &active, Hit &h, bool &found) {
+  if constexpr (WIDE) {
+    traverse_wide<ANY>(ws, nodes, arecs, o, d, tmin, tmax, active, h, found, stack);
+    return;
+  }
+  const wmask am = wballot(active);
   if (am == 0ull) { // nothing to trace
-    h[0].t = -INFINITY; h[0].prim = -1; h[0].shape = -1; h[0].slot = -1; found[0] = false;
+    h.t = -INFINITY; h.prim = -1; h.shape = -1; h.slot = -1; found = false;
     return;
   }
   // unit of the box test: tmax maps to 0.999, so an entry distance beyond the ray's range — which the
   // clamp turns into exactly 1 — stays above the scaled hit distance and the box is rejected
-  const float scale = 0.999f * __builtin_amdgcn_rcpf(tmax[0]);
-  const RayOct rb = make_rayoct(o[0], d[0], scale);
+  const float scale = 0.999f * __builtin_amdgcn_rcpf(tmax);
+  const RayOct rb = make_rayoct(o, d, scale);
   // octant from the reciprocals actually used (a clamped -0.0 component counts as negative)
   const uint32_t oct = (__float_as_uint(rb.id.x) >> 31) | ((__float_as_uint(rb.id.y) >> 31) << 1) | ((__float_as_uint(rb.id.z) >> 31) << 2);
   const uint32_t oct0 = (uint32_t)__builtin_amdgcn_readlane((int)oct, __builtin_ctzll(am)); // octant of the first active lane
   const bool uniform = (am & __builtin_amdgcn_uicmp(oct, oct0, 33)) == 0ull;
   if (uniform) {
     switch (oct0) { // wave-uniform
-      case 0: traverse_packet_oct<ANY, 0>(nodes, recs, rb, scale, d[0], tmin[0], tmax[0], am, h[0], found[0]); break;
-      case 1: traverse_packet_oct<ANY, 1>(nodes, recs, rb, scale, d[0], tmin[0], tmax[0], am, h[0], found[0]); break;
-      case 2: traverse_packet_oct<ANY, 2>(nodes, recs, rb, scale, d[0], tmin[0], tmax[0], am, h[0], found[0]); break;
-      case 3: traverse_packet_oct<ANY, 3>(nodes, recs, rb, scale, d[0], tmin[0], tmax[0], am, h[0], found[0]); break;
-      case 4: traverse_packet_oct<ANY, 4>(nodes, recs, rb, scale, d[0], tmin[0], tmax[0], am, h[0], found[0]); break;
-      case 5: traverse_packet_oct<ANY, 5>(nodes, recs, rb, scale, d[0], tmin[0], tmax[0], am, h[0], found[0]); break;
-      case 6: traverse_packet_oct<ANY, 6>(nodes, recs, rb, scale, d[0], tmin[0], tmax[0], am, h[0], found[0]); break;
-      default: traverse_packet_oct<ANY, 7>(nodes, recs, rb, scale, d[0], tmin[0], tmax[0], am, h[0], found[0]); break;
+      case 0: traverse_packet_oct<ANY, 0>(nodes, arecs, rb, scale, d, tmin, tmax, am, h, found); break;
+      case 1: traverse_packet_oct<ANY, 1>(nodes, arecs, rb, scale, d, tmin, tmax, am, h, found); break;
+      case 2: traverse_packet_oct<ANY, 2>(nodes, arecs, rb, scale, d, tmin, tmax, am, h, found); break;
+      case 3: traverse_packet_oct<ANY, 3>(nodes, arecs, rb, scale, d, tmin, tmax, am, h, found); break;
+      case 4: traverse_packet_oct<ANY, 4>(nodes, arecs, rb, scale, d, tmin, tmax, am, h, found); break;
+      case 5: traverse_packet_oct<ANY, 5>(nodes, arecs, rb, scale, d, tmin, tmax, am, h, found); break;
+      case 6: traverse_packet_oct<ANY, 6>(nodes, arecs, rb, scale, d, tmin, tmax, am, h, found); break;
+      default: traverse_packet_oct<ANY, 7>(nodes, arecs, rb, scale, d, tmin, tmax, am, h, found); break;
     }
   } else {
-    traverse_packet<ANY, 1>(nodes, recs, o, d, tmin, tmax, active, h, found);
+    traverse_packet<ANY>(nodes, arecs, o, d, tmin, tmax, active, h, found);
   }
-}
-
-// dispatch: WIDE — the 64-wide walk (default); otherwise the binary walks: octant loops for one ray per
-// lane, the generic loop for more.  All packet walks are APEX walks (their rays share the origin o[0] whose
-// records `arecs` were written by k_apex_records).
-template <bool ANY, int R, bool WIDE>
-__device__ __forceinline__ void traverse_packet_any(const BvhNode *__restrict__ nodes, const TriApex *__restrict__ arecs, const WideScene &ws, uint2 *__restrict__ stack,
-                                                    const v3 (&o)[R], const v3 (&d)[R], const float (&tmin)[R], const float (&tmax)[R], const bool (&active)[R],
-                                                    Hit (&h)[R], bool (&found)[R]) {
-  if constexpr (WIDE) traverse_wide<ANY, R>(ws, nodes, arecs, o, d, tmin, tmax, active, h, found, stack);
-  else if constexpr (R == 1 && octant_loops()) traverse_packet1<ANY>(nodes, arecs, o, d, tmin, tmax, active, h, found);
-  else traverse_packet<ANY, R>(nodes, arecs, o, d, tmin, tmax, active, h, found);
 }
 
 // ------------------------------------------------------------------------------------------ tile bins instead of a tree walk
@@ -2256,7 +2140,7 @@ struct ShadePre {
   float pfac_b, sfac_b; // material rows only
 };
 
-// packet version of shade_sample for R samples per lane: every lane of the wave reaches every walk
+// packet version of shade_sample, one sample per lane: every lane of the wave reaches every walk
 // The scene constants (ShadeK, ~100 dwords) are the first kernel argument of the render kernels.  Read
 // through `c` the compiler loads them all up front and, out of SGPRs, parks them in VGPR lanes
 // (v_writelane / v_readlane: ~480 spill instructions on the VALU, the unit that bounds these kernels).
@@ -2276,50 +2160,50 @@ __device__ __forceinline__ bool tex_footprint_lit(const float *__restrict__ tex,
 }
 
 // MATM: 0 = [S,3] Lambert albedos, 1 = material rows, 2 = material rows some of which take their base colour from a texture
-// px, py (wave-uniform): the pixel the packet's primary rays belong to — the tile bins are tried first (R == 1), the tree walks serve
-// what they cannot
-template <int R, bool WIDE, int MATM = 0>
+// px, py (wave-uniform): the pixel the packet's primary rays belong to — the tile bins are tried first, the tree walks serve
+// what they cannot.  (The body's one-element arrays and single-trip loops: see as1.)
+template <bool WIDE, int MATM = 0>
 __device__ __forceinline__ void shade_sample_pk(const BvhNode *__restrict__ nodes, const TriRec *__restrict__ recs, const TriApex *__restrict__ arecs,
-                                                uint32_t astride, const WideScene &ws, uint2 *__restrict__ stack, const bool (&active)[R], const v3 (&o)[R],
-                                                const v3 (&d)[R], const float (&nt)[R], const float (&ft)[R], SampleTerms (&st)[R],
+                                                uint32_t astride, const WideScene &ws, uint2 *__restrict__ stack, const bool &active_, const v3 &o_,
+                                                const v3 &d_, const float &nt_, const float &ft_, SampleTerms &st_,
                                                 const float4 *__restrict__ nrec, const float4 *__restrict__ gn, const int px, const int py,
                                                 const float *__restrict__ tex_probe = nullptr, const int blk_w = 1, const int blk_h = 1) {
   constexpr bool MAT = MATM != 0, TEX = MATM == 2;
-  Hit h[R];
-  bool fnd[R];
+  const bool (&active)[1] = as1(active_);
+  const v3 (&o)[1] = as1(o_), (&d)[1] = as1(d_);
+  const float (&nt)[1] = as1(nt_), (&ft)[1] = as1(ft_);
+  SampleTerms (&st)[1] = as1(st_);
+  Hit h[1];
+  bool fnd[1];
   FFX_TSTART(tp);
   bool binned = false;
   // (blk_w x blk_h > 1: the packet's primary rays belong to a compact block of pixels whose first is (px, py) — k_render_fwd_blk, renders at
   // fewer than 64 samples per pixel; the default arguments are constants of every other caller)
-  if constexpr (R == 1) {
-    if (blk_w * blk_h == 1) binned = bins_primary(kernarg_shade().bins, px, py, arecs, d[0], nt[0], ft[0], wballot(active[0]), h[0]);
-    else binned = bins_block(kernarg_shade().bins, px, py, blk_w, blk_h, arecs, d[0], nt[0], ft[0], wballot(active[0]), h[0]);
-  }
+  if (blk_w * blk_h == 1) binned = bins_primary(kernarg_shade().bins, px, py, arecs, d[0], nt[0], ft[0], wballot(active[0]), h[0]);
+  else binned = bins_block(kernarg_shade().bins, px, py, blk_w, blk_h, arecs, d[0], nt[0], ft[0], wballot(active[0]), h[0]);
   if (!binned) {
-    if constexpr (R == 1) FFX_STAT(36);
-    traverse_packet_any<false, R, WIDE>(nodes, arecs, ws, stack, o, d, nt, ft, active, h, fnd); // apex 0: the camera
+    FFX_STAT(36);
+    traverse_packet_any<false, WIDE>(nodes, arecs, ws, stack, o[0], d[0], nt[0], ft[0], active[0], h[0], fnd[0]); // apex 0: the camera
   }
 #ifdef FFX_BINCHECK // self-check build: every binned walk is repeated on the tree and compared lane by lane (tools/bincheck.py)
-  if constexpr (R == 1) {
-    if (binned) {
-      Hit h2[R];
-      traverse_packet_any<false, R, WIDE>(nodes, arecs, ws, stack, o, d, nt, ft, active, h2, fnd);
-      const bool bad = active[0] && (h2[0].prim != h[0].prim || (h2[0].prim >= 0 && h2[0].t != h[0].t));
-      const wmask bm = wballot(bad);
-      if (bm != 0ull && (threadIdx.x & 63) == (unsigned)wff1(bm)) {
-        atomicAdd(&g_ffx_chk[0], 1ull);
-        if (atomicAdd(&g_ffx_chk[1], 1ull) == 0ull) { g_ffx_chk[2] = (unsigned long long)px | ((unsigned long long)py << 16) | ((unsigned long long)(threadIdx.x & 63) << 32); g_ffx_chk[3] = (unsigned long long)(uint32_t)h[0].prim | ((unsigned long long)(uint32_t)h2[0].prim << 32); g_ffx_chk[4] = (unsigned long long)(uint32_t)h[0].slot | ((unsigned long long)(uint32_t)h2[0].slot << 32); g_ffx_chk[5] = (unsigned long long)__float_as_uint(h[0].t) | ((unsigned long long)__float_as_uint(h2[0].t) << 32); }
-      }
-      h[0] = h2[0];
+  if (binned) {
+    Hit h2[1];
+    traverse_packet_any<false, WIDE>(nodes, arecs, ws, stack, o[0], d[0], nt[0], ft[0], active[0], h2[0], fnd[0]);
+    const bool bad = active[0] && (h2[0].prim != h[0].prim || (h2[0].prim >= 0 && h2[0].t != h[0].t));
+    const wmask bm = wballot(bad);
+    if (bm != 0ull && (threadIdx.x & 63) == (unsigned)wff1(bm)) {
+      atomicAdd(&g_ffx_chk[0], 1ull);
+      if (atomicAdd(&g_ffx_chk[1], 1ull) == 0ull) { g_ffx_chk[2] = (unsigned long long)px | ((unsigned long long)py << 16) | ((unsigned long long)(threadIdx.x & 63) << 32); g_ffx_chk[3] = (unsigned long long)(uint32_t)h[0].prim | ((unsigned long long)(uint32_t)h2[0].prim << 32); g_ffx_chk[4] = (unsigned long long)(uint32_t)h[0].slot | ((unsigned long long)(uint32_t)h2[0].slot << 32); g_ffx_chk[5] = (unsigned long long)__float_as_uint(h[0].t) | ((unsigned long long)__float_as_uint(h2[0].t) << 32); }
     }
+    h[0] = h2[0];
   }
 #endif
   FFX_TSTOP(tp, 22);
   const ShadeK &c = kernarg_shade(); // phase: light terms at the hit point
-  ShadePre pre[R];
+  ShadePre pre[1];
   bool any_p = false, any_s = false;
 #pragma unroll
-  for (int r = 0; r < R; ++r) {
+  for (int r = 0; r < 1; ++r) {
     ShadePre &q = pre[r];
     // shading normal of this sample (ffx_smooth): equal to the geometric one unless the hit record is flagged.  It takes the
     // geometric normal's place in q.ng once the geometric side tests below are done (one normal stays live across the walks).
@@ -2456,84 +2340,75 @@ __device__ __forceinline__ void shade_sample_pk(const BvhNode *__restrict__ node
   // triangle records were prepared for — to the lifted surface point: o = emitter, d = Po - emitter,
   // occluded iff some triangle is hit at 0 < t < 1 - eps.  No normalisation, and the packet's rays share
   // their origin exactly.
-  bool occ_p[R], occ_s[R];
-#pragma unroll
-  for (int r = 0; r < R; ++r) occ_p[r] = occ_s[r] = false;
+  bool occ_p[1], occ_s[1];
+  occ_p[0] = occ_s[0] = false;
   FFX_TSTOP(tp, 18);
   const bool walk_p = c.shadows && wballot(any_p) != 0ull, walk_s = c.shadows && wballot(any_s) != 0ull;
   if (walk_p) {
     const v3 ppos = V3(c.p_pos[0], c.p_pos[1], c.p_pos[2]);
-    v3 so[R], sdir[R];
-    float s0[R], s1[R];
-    bool act[R];
-    Hit hs[R];
+    v3 so[1], sdir[1];
+    float s0[1], s1[1];
+    bool act[1];
+    Hit hs[1];
 #pragma unroll
-    for (int r = 0; r < R; ++r) { so[r] = ppos; sdir[r] = vsub(pre[r].Po, ppos); s0[r] = 0.f; s1[r] = 1.0f - SHADOW_EPS; act[r] = pre[r].need_p; }
+    for (int r = 0; r < 1; ++r) { so[r] = ppos; sdir[r] = vsub(pre[r].Po, ppos); s0[r] = 0.f; s1[r] = 1.0f - SHADOW_EPS; act[r] = pre[r].need_p; }
     const TriApex *arecs_p = reinterpret_cast<const TriApex *>(reinterpret_cast<const char *>(arecs) + astride);
     bool binned_p = false;
-    if constexpr (R == 1) {
-      wmask occm;
-      binned_p = bins_shadow(kernarg_shade().bins, 1, arecs_p, sdir[0], wballot(act[0]), occm);
-      if (binned_p) occ_p[0] = __builtin_amdgcn_inverse_ballot_w64(occm);
-    }
+    wmask occm;
+    binned_p = bins_shadow(kernarg_shade().bins, 1, arecs_p, sdir[0], wballot(act[0]), occm);
+    if (binned_p) occ_p[0] = __builtin_amdgcn_inverse_ballot_w64(occm);
     if (!binned_p) {
-      if constexpr (R == 1) FFX_STAT(44);
-      traverse_packet_any<true, R, WIDE>(nodes, arecs_p, ws, stack, so, sdir, s0, s1, act, hs, occ_p);
+      FFX_STAT(44);
+      traverse_packet_any<true, WIDE>(nodes, arecs_p, ws, stack, so[0], sdir[0], s0[0], s1[0], act[0], hs[0], occ_p[0]);
     }
 #ifdef FFX_BINCHECK
-    if constexpr (R == 1) {
-      if (binned_p) {
-        bool occ2[R];
-        traverse_packet_any<true, R, WIDE>(nodes, arecs_p, ws, stack, so, sdir, s0, s1, act, hs, occ2);
-        const wmask bm = wballot(act[0] && occ2[0] != occ_p[0]);
-        if (bm != 0ull && (threadIdx.x & 63) == (unsigned)wff1(bm)) {
-          atomicAdd(&g_ffx_chk[8], 1ull);
-          if (atomicAdd(&g_ffx_chk[9], 1ull) == 0ull) { g_ffx_chk[10] = (unsigned long long)px | ((unsigned long long)py << 16) | ((unsigned long long)(threadIdx.x & 63) << 32) | ((unsigned long long)occ2[0] << 40); g_ffx_chk[11] = (unsigned long long)(uint32_t)hs[0].slot; }
-        }
-        occ_p[0] = occ2[0];
+    if (binned_p) {
+      bool occ2[1];
+      traverse_packet_any<true, WIDE>(nodes, arecs_p, ws, stack, so[0], sdir[0], s0[0], s1[0], act[0], hs[0], occ2[0]);
+      const wmask bm = wballot(act[0] && occ2[0] != occ_p[0]);
+      if (bm != 0ull && (threadIdx.x & 63) == (unsigned)wff1(bm)) {
+        atomicAdd(&g_ffx_chk[8], 1ull);
+        if (atomicAdd(&g_ffx_chk[9], 1ull) == 0ull) { g_ffx_chk[10] = (unsigned long long)px | ((unsigned long long)py << 16) | ((unsigned long long)(threadIdx.x & 63) << 32) | ((unsigned long long)occ2[0] << 40); g_ffx_chk[11] = (unsigned long long)(uint32_t)hs[0].slot; }
       }
+      occ_p[0] = occ2[0];
     }
 #endif
   }
   FFX_TSTOP(tp, 19);
   if (walk_s) {
     const v3 spos = V3(c.s_pos[0], c.s_pos[1], c.s_pos[2]);
-    v3 so[R], sdir[R];
-    float s0[R], s1[R];
-    bool act[R];
-    Hit hs[R];
+    v3 so[1], sdir[1];
+    float s0[1], s1[1];
+    bool act[1];
+    Hit hs[1];
 #pragma unroll
-    for (int r = 0; r < R; ++r) { so[r] = spos; sdir[r] = vsub(pre[r].Po, spos); s0[r] = 0.f; s1[r] = 1.0f - SHADOW_EPS; act[r] = pre[r].need_s; }
+    for (int r = 0; r < 1; ++r) { so[r] = spos; sdir[r] = vsub(pre[r].Po, spos); s0[r] = 0.f; s1[r] = 1.0f - SHADOW_EPS; act[r] = pre[r].need_s; }
     const TriApex *arecs_s = reinterpret_cast<const TriApex *>(reinterpret_cast<const char *>(arecs) + 2u * astride);
     bool binned_s = false;
-    if constexpr (R == 1) {
-      wmask occm;
-      binned_s = bins_shadow(kernarg_shade().bins, 2, arecs_s, sdir[0], wballot(act[0]), occm);
-      if (binned_s) occ_s[0] = __builtin_amdgcn_inverse_ballot_w64(occm);
-    }
+    wmask occm;
+    binned_s = bins_shadow(kernarg_shade().bins, 2, arecs_s, sdir[0], wballot(act[0]), occm);
+    if (binned_s) occ_s[0] = __builtin_amdgcn_inverse_ballot_w64(occm);
     if (!binned_s) {
-      if constexpr (R == 1) FFX_STAT(45);
-      traverse_packet_any<true, R, WIDE>(nodes, arecs_s, ws, stack, so, sdir, s0, s1, act, hs, occ_s);
+      FFX_STAT(45);
+      traverse_packet_any<true, WIDE>(nodes, arecs_s, ws, stack, so[0], sdir[0], s0[0], s1[0], act[0], hs[0], occ_s[0]);
     }
 #ifdef FFX_BINCHECK
-    if constexpr (R == 1) {
-      if (binned_s) {
-        bool occ2[R];
-        traverse_packet_any<true, R, WIDE>(nodes, arecs_s, ws, stack, so, sdir, s0, s1, act, hs, occ2);
-        const wmask bm = wballot(act[0] && occ2[0] != occ_s[0]);
-        if (bm != 0ull && (threadIdx.x & 63) == (unsigned)wff1(bm)) {
-          atomicAdd(&g_ffx_chk[16], 1ull);
-          if (atomicAdd(&g_ffx_chk[17], 1ull) == 0ull) { g_ffx_chk[18] = (unsigned long long)px | ((unsigned long long)py << 16) | ((unsigned long long)(threadIdx.x & 63) << 32) | ((unsigned long long)occ2[0] << 40); g_ffx_chk[19] = (unsigned long long)(uint32_t)hs[0].slot; }
-        }
-        occ_s[0] = occ2[0];
+    if (binned_s) {
+      bool occ2[1];
+      traverse_packet_any<true, WIDE>(nodes, arecs_s, ws, stack, so[0], sdir[0], s0[0], s1[0], act[0], hs[0], occ2[0]);
+      const wmask bm = wballot(act[0] && occ2[0] != occ_s[0]);
+      if (bm != 0ull && (threadIdx.x & 63) == (unsigned)wff1(bm)) {
+        atomicAdd(&g_ffx_chk[16], 1ull);
+        if (atomicAdd(&g_ffx_chk[17], 1ull) == 0ull) { g_ffx_chk[18] = (unsigned long long)px | ((unsigned long long)py << 16) | ((unsigned long long)(threadIdx.x & 63) << 32) | ((unsigned long long)occ2[0] << 40); g_ffx_chk[19] = (unsigned long long)(uint32_t)hs[0].slot; }
       }
+      occ_s[0] = occ2[0];
     }
 #endif
   }
   FFX_TSTOP(tp, 20);
   const ShadeK &c2 = kernarg_shade(); // phase: texture footprint and light intensities
 #pragma unroll
-  for (int r = 0; r < R; ++r) {
+  for (int r = 0; r < 1; ++r) {
     ShadePre &q = pre[r];
     if constexpr (MAT) {
       // BSDF of the samples an emitter reaches: pi f cos = base_color * bA + bB (material_eval); Lambert rows: bA = cos_s
@@ -2617,8 +2492,8 @@ __device__ __forceinline__ void shade_sample_pk(const BvhNode *__restrict__ node
 // Packet kernels.  A wavefront owns one 2x2-pixel tile (65,536 work items at 512x512): tile costs vary
 // by an order of magnitude (rays along the tube vs. rays that leave it), so fine-grained, independent
 // waves let the hardware dispatcher keep every SIMD busy to the end.  The 64 lanes are the 64 samples
-// of a pixel and the tile is walked as four single pixels (R = 1; the template parameter remains from
-// a two-pixels-per-lane experiment).  All 64 rays of a packet are within a one-pixel frustum, so the
+// of a pixel and the tile is walked as four single pixels: one ray per lane (two pixels per lane were measured slower and
+// removed; the two tile kernels keep R = 1 in their template heads and their [R] arrays, see there).  All 64 rays of a packet are within a one-pixel frustum, so the
 // union of their paths is practically one ray's path.
 #define PK_BLOCK 64 // one independent wave per workgroup: the finest grain for the dispatcher (2 / 4 waves measured +1 % / +8 % time)
 
@@ -2652,26 +2527,26 @@ __global__ void __launch_bounds__(PK_BLOCK) __attribute__((amdgpu_waves_per_eu(F
   const int passes = (spp + spp_w - 1) / spp_w;
   for (int pass = 0; pass < passes; ++pass) {
     const int sidx = pass * spp_w + sl;
-    const bool active[1] = {in_img && sidx < spp};
+    const bool active = in_img && sidx < spp;
     const uint32_t idx = pix * (uint32_t)spp + (uint32_t)sidx;
     float jx = 0.f, jy = 0.f;
     if (jitter) sample_jitter(seed_key, idx, jx, jy);
-    v3 o[1], d[1];
-    float nt[1], ft[1];
-    cam_ray(cam, ((float)x + jx) * cam.inv_w, ((float)y + jy) * cam.inv_h, o[0], d[0], nt[0], ft[0]);
-    Hit h[1];
-    bool fnd[1];
+    v3 o, d;
+    float nt, ft;
+    cam_ray(cam, ((float)x + jx) * cam.inv_w, ((float)y + jy) * cam.inv_h, o, d, nt, ft);
+    Hit h;
+    bool fnd;
     // round 4: the block's candidates from the camera's tile bins (as K8's primary rays) — the tree walk when there are none
     // (no bins area, a grid that is off or overflowed)
     bool binned = false;
     if (bins.g[0].on)
-      binned = bins_block(bins, (blk % blocks_x) << bw_log2, (blk / blocks_x) << bh_log2, 1 << bw_log2, 1 << bh_log2, arecs, d[0], nt[0], ft[0], wballot(active[0]), h[0]);
-    if (!binned) traverse_packet_any<false, 1, WIDE>(nodes, arecs, ws, s_wstack, o, d, nt, ft, active, h, fnd);
-    if (active[0]) {
-      const bool hit = h[0].prim >= 0;
-      t_out[idx] = hit ? (h[0].t - nt[0]) : 0.f;
-      if (shape_out) shape_out[idx] = hit ? recs[h[0].slot].shape : -1;
-      if (prim_out) prim_out[idx] = h[0].prim;
+      binned = bins_block(bins, (blk % blocks_x) << bw_log2, (blk / blocks_x) << bh_log2, 1 << bw_log2, 1 << bh_log2, arecs, d, nt, ft, wballot(active), h);
+    if (!binned) traverse_packet_any<false, WIDE>(nodes, arecs, ws, s_wstack, o, d, nt, ft, active, h, fnd);
+    if (active) {
+      const bool hit = h.prim >= 0;
+      t_out[idx] = hit ? (h.t - nt) : 0.f;
+      if (shape_out) shape_out[idx] = hit ? recs[h.slot].shape : -1;
+      if (prim_out) prim_out[idx] = h.prim;
     }
   }
 }
@@ -2696,10 +2571,7 @@ __device__ __forceinline__ void packet_pixels(int tile, int tiles_x_tb, int sub,
   const int tx = (rem << tb) + (within & bt1), ty = ((int)by_ << tb) + (within >> tb);
   const int bx = tx * 2, by = ty * 2;
 #pragma unroll
-  for (int r = 0; r < R; ++r) {
-    if (R == 2) { px[r] = bx + r; py[r] = by + sub; }
-    else { px[r] = bx + (sub & 1); py[r] = by + (sub >> 1); }
-  }
+  for (int r = 0; r < R; ++r) { px[r] = bx + (sub & 1); py[r] = by + (sub >> 1); }
 }
 
 // ---- adjoint cache (store instead of re-trace): what K9 needs of a pixel, written by K8.
@@ -2977,14 +2849,15 @@ __device__ __forceinline__ float4 rf_window_g(const float4 *__restrict__ G, int 
 // (here: the scratch area, [pixel][25][4] floats; no adjoint cache in this mode) — see rf_fold above.
 // RFC (ffx_render_fwd_cache_filtered; RF && !ADJ): additionally the per-sample records of the filtered film's adjoint cache (rfc_off_* above);
 // its base travels in `adj_gtex`, the record areas' offsets (128-byte units) in cache_foot_off / cache_foot_b_off.
+// R (rays per lane) is 1 and stays in the template head: the benchmark and the committed profiles read ADJ and RF by their position
+// in the instance name as the profiler prints it, k_render_fwd_pk<1, true, 1, false, false, false>.  (Its [R] arrays and loops: see as1.)
 template <int R, bool WIDE, int MATM, bool ADJ = false, bool RF = false, bool RFC = false>
-__global__ void __launch_bounds__(PK_BLOCK) __attribute__((amdgpu_waves_per_eu(MATM ? FFX_PK_MAT_WAVES : (R == 1 ? FFX_PK1_WAVES : 3), MATM ? FFX_PK_MAT_WAVES : (R == 1 ? FFX_PK1_WAVES : 4))))
+__global__ void __launch_bounds__(PK_BLOCK) __attribute__((amdgpu_waves_per_eu(MATM ? FFX_PK_MAT_WAVES : FFX_PK1_WAVES, MATM ? FFX_PK_MAT_WAVES : FFX_PK1_WAVES)))
     k_render_fwd_pk(ShadeK c, const BvhNode *__restrict__ nodes, const TriRec *__restrict__ recs, const TriApex *__restrict__ arecs, uint32_t astride,
                     WideScene ws, const float *__restrict__ albedo, const float *__restrict__ tex, int spp, uint32_t seed_key, int tiles_x, int n_tiles, int remap,
                     int fp16, void *__restrict__ img, char *__restrict__ cache, int ppw, float inv_spp_arg, uint32_t cache_foot_off, uint32_t cache_arena_off,
                     uint32_t cache_foot_b_off, const float4 *__restrict__ nrec, const float4 *__restrict__ gn, uint32_t cap_stray,
                     const float *__restrict__ adj_gimg, float *__restrict__ adj_gtex, float *__restrict__ adj_dot) {
-  constexpr int NSUB = 4 / R;
   constexpr bool MAT = MATM != 0, TEX = MATM == 2;
   constexpr int MS = MAT ? FFX_MAT_STRIDE : 3; // floats per material row
   // adj_gtex (ffx_render_fwd_adjoint): the adjoint of a loss whose gradient gimg does not depend on the image (a loss linear in it) needs
@@ -2999,7 +2872,7 @@ __global__ void __launch_bounds__(PK_BLOCK) __attribute__((amdgpu_waves_per_eu(M
   __shared__ __attribute__((aligned(16))) uint2 s_wstack[RF ? (WSTACK_N > RF_N ? WSTACK_N : RF_N) : WSTACK_N]; // (RF: the filter's rows alias the walk's stack and are read in 16-byte units)
   __shared__ float s_foot[32]; // the pixel's 5x5 texture footprint (adjoint cache)
   __shared__ float s_foot_b[MAT ? 32 : 1]; // material rows: the footprint of the base_color-independent part
-  static_assert(R == 1, "the adjoint cache is written one pixel at a time");
+  static_assert(R == 1, "one ray per lane: the adjoint cache is written one pixel at a time");
   static_assert(!RFC || (RF && !ADJ), "RFC: the filtered forward that writes the per-sample adjoint records");
   FFX_TINIT();
   FFX_TSTART(twave);
@@ -3011,8 +2884,8 @@ __global__ void __launch_bounds__(PK_BLOCK) __attribute__((amdgpu_waves_per_eu(M
   // each wave of the workgroup owns its own tile; the waves never synchronise
   // a wave walks `ppw` (1, 2 or 4) of its tile's four pixels; 4 / ppw waves share a tile
   const int wv = __builtin_amdgcn_readfirstlane(xcd_remap(blockIdx.x, gridDim.x, remap) * (blockDim.x >> 6) + (threadIdx.x >> 6)); // wave-uniform: say so
-  const int wpt_log2 = (R == 1) ? (ppw == 1 ? 2 : (ppw == 2 ? 1 : 0)) : 0; // waves per tile = NSUB / ppw, a power of two: shifts, not divisions
-  const int tile = (R == 1) ? (wv >> wpt_log2) : wv / (NSUB / ppw), sub0 = (R == 1) ? (wv & ((1 << wpt_log2) - 1)) * ppw : (wv % (NSUB / ppw)) * ppw;
+  const int wpt_log2 = ppw == 1 ? 2 : (ppw == 2 ? 1 : 0); // waves per tile = 4 / ppw, a power of two: shifts, not divisions
+  const int tile = wv >> wpt_log2, sub0 = (wv & ((1 << wpt_log2) - 1)) * ppw;
   const int lane = threadIdx.x & 63;
   const int W = c.cam.W, H = c.cam.H; // (the only direct use of the by-value copy)
   const int passes = (spp + 63) >> 6;
@@ -3062,7 +2935,7 @@ __global__ void __launch_bounds__(PK_BLOCK) __attribute__((amdgpu_waves_per_eu(M
       SampleTerms st[R];
       // (fp16 carries the call's flags: bit 0 fp16 film, bit 1 FFX_RENDER_SPARSE_ADJOINT — then the cache-writing forward may
       // skip dark footprints too: the caller only wants gradients of texels whose value is not zero)
-      shade_sample_pk<R, WIDE, MATM>(nodes, recs, arecs, astride, ws, s_wstack, active, o, d, nt, ft, st, nrec, gn, px[0], py[0], ((fold || RFC) && !(fp16 & 2)) ? nullptr : tex);
+      shade_sample_pk<WIDE, MATM>(nodes, recs, arecs, astride, ws, s_wstack, active[0], o[0], d[0], nt[0], ft[0], st[0], nrec, gn, px[0], py[0], ((fold || RFC) && !(fp16 & 2)) ? nullptr : tex);
       FFX_TSTOP(tk, 17);
       if constexpr (RFC) {
         // ---- the filtered film's adjoint cache: this pass's 64 records, if any of its samples is lit (one 1 KB store per wave)
@@ -3438,27 +3311,27 @@ __global__ void __launch_bounds__(PK_BLOCK) __attribute__((amdgpu_waves_per_eu(M
   const int W = c.cam.W, H = c.cam.H; // (the only direct use of the by-value copy)
   const bool in_img = x < W && y < H;
   const uint32_t pix = (uint32_t)y * (uint32_t)W + (uint32_t)x;
-  const bool active[1] = {in_img && sl < spp};
-  v3 o[1], d[1];
-  float nt[1], ft[1];
+  const bool active = in_img && sl < spp;
+  v3 o, d;
+  float nt, ft;
   {
     const CamK &cam = kernarg_shade().cam;
     float jx, jy;
     sample_jitter(seed_key, pix * (uint32_t)spp + (uint32_t)sl, jx, jy);
-    cam_ray(cam, ((float)x + jx) * cam.inv_w, ((float)y + jy) * cam.inv_h, o[0], d[0], nt[0], ft[0]);
+    cam_ray(cam, ((float)x + jx) * cam.inv_w, ((float)y + jy) * cam.inv_h, o, d, nt, ft);
   }
-  SampleTerms st[1];
-  shade_sample_pk<1, WIDE, MATM>(nodes, recs, arecs, astride, ws, s_wstack, active, o, d, nt, ft, st, nrec, gn, bx0, by0, tex, 1 << bw_log2, 1 << bh_log2);
+  SampleTerms st;
+  shade_sample_pk<WIDE, MATM>(nodes, recs, arecs, astride, ws, s_wstack, active, o, d, nt, ft, st, nrec, gn, bx0, by0, tex, 1 << bw_log2, 1 << bh_log2);
   const ShadeK &ct = kernarg_shade(); // texture gather and the sample's colour: k_render_fwd_pk's arithmetic
   float c0 = 0.f, c1 = 0.f, c2 = 0.f;
-  if (st[0].hit) {
-    float r0 = st[0].spot[0], r1 = st[0].spot[1], r2 = st[0].spot[2];
-    float b0 = st[0].spot_b[0], b1 = st[0].spot_b[1], b2 = st[0].spot_b[2]; // (MAT only: dead otherwise)
-    if (st[0].has_proj) {
+  if (st.hit) {
+    float r0 = st.spot[0], r1 = st.spot[1], r2 = st.spot[2];
+    float b0 = st.spot_b[0], b1 = st.spot_b[1], b2 = st.spot_b[2]; // (MAT only: dead otherwise)
+    if (st.has_proj) {
       const int tc = ct.tc;
-      const size_t o00 = ((size_t)st[0].iy0 * ct.tw + st[0].ix0) * tc, o01 = ((size_t)st[0].iy0 * ct.tw + st[0].ix1) * tc;
-      const size_t o10 = ((size_t)st[0].iy1 * ct.tw + st[0].ix0) * tc, o11 = ((size_t)st[0].iy1 * ct.tw + st[0].ix1) * tc;
-      const float wx0 = st[0].wx0, wx1 = st[0].wx1, wy0 = st[0].wy0, wy1 = st[0].wy1, pf = st[0].proj_fac, pb = st[0].proj_fac_b;
+      const size_t o00 = ((size_t)st.iy0 * ct.tw + st.ix0) * tc, o01 = ((size_t)st.iy0 * ct.tw + st.ix1) * tc;
+      const size_t o10 = ((size_t)st.iy1 * ct.tw + st.ix0) * tc, o11 = ((size_t)st.iy1 * ct.tw + st.ix1) * tc;
+      const float wx0 = st.wx0, wx1 = st.wx1, wy0 = st.wy0, wy1 = st.wy1, pf = st.proj_fac, pb = st.proj_fac_b;
       if (tc == 1) {
         const float tv = wy0 * (wx0 * tex[o00] + wx1 * tex[o01]) + wy1 * (wx0 * tex[o10] + wx1 * tex[o11]);
         r0 += tv * ct.p_color[0] * pf;
@@ -3484,11 +3357,11 @@ __global__ void __launch_bounds__(PK_BLOCK) __attribute__((amdgpu_waves_per_eu(M
       }
     }
     if constexpr (TEX) {
-      c0 = st[0].base[0] * r0;
-      c1 = st[0].base[1] * r1;
-      c2 = st[0].base[2] * r2;
+      c0 = st.base[0] * r0;
+      c1 = st.base[1] * r1;
+      c2 = st.base[2] * r2;
     } else {
-      const float *alb = mat_table(ct) + MS * st[0].shape;
+      const float *alb = mat_table(ct) + MS * st.shape;
       c0 = alb[0] * r0;
       c1 = alb[1] * r1;
       c2 = alb[2] * r2;
@@ -3500,7 +3373,7 @@ __global__ void __launch_bounds__(PK_BLOCK) __attribute__((amdgpu_waves_per_eu(M
     sample_jitter(seed_key, pix * (uint32_t)spp + (uint32_t)sl, jx, jy);
     rf_weights(ct.rf, jx, gx);
     rf_weights(ct.rf, jy, gy);
-    rf_fold_blk(reinterpret_cast<float *>(s_wstack), lane, gx, gy, c0, c1, c2, active[0] ? 1.f : 0.f, ppw_log2, bw_log2, bx0, by0, W, H, reinterpret_cast<float *>(img));
+    rf_fold_blk(reinterpret_cast<float *>(s_wstack), lane, gx, gy, c0, c1, c2, active ? 1.f : 0.f, ppw_log2, bw_log2, bx0, by0, W, H, reinterpret_cast<float *>(img));
     return;
   }
   // the pixel's samples sit in spp_w neighbouring lanes: a butterfly inside the group, nearest partners first — the tree of k_render_fwd_pk's DPP
@@ -3560,12 +3433,12 @@ __global__ void __launch_bounds__(256) k_det_finish(const unsigned long long *__
 }
 // RF (ffx_render_bwd_filtered): `gimg` is then G = gimg / weight as float4 per pixel (k_rf_gather) and a sample's radiance receives
 // sum over its 5x5 window of  w_n G[pixel + n]  — the transpose of the filter — in place of gimg[pixel] / spp.
+// (R = 1 stays in the template head as in k_render_fwd_pk: the instance names k_render_bwd_pk<1, ...> are what profiles and tools key on)
 template <int R, bool WIDE, int MATM, bool RF = false>
-__global__ void __launch_bounds__(PK_BLOCK) __attribute__((amdgpu_waves_per_eu(MATM ? FFX_PK_MAT_WAVES : (R == 1 ? FFX_PK1_WAVES : 3), MATM ? FFX_PK_MAT_WAVES : (R == 1 ? FFX_PK1_WAVES : 4))))
+__global__ void __launch_bounds__(PK_BLOCK) __attribute__((amdgpu_waves_per_eu(MATM ? FFX_PK_MAT_WAVES : FFX_PK1_WAVES, MATM ? FFX_PK_MAT_WAVES : FFX_PK1_WAVES)))
     k_render_bwd_pk(ShadeK c, const BvhNode *__restrict__ nodes, const TriRec *__restrict__ recs, const TriApex *__restrict__ arecs, uint32_t astride,
                     WideScene ws, const float *__restrict__ albedo, int spp, uint32_t seed_key, int tiles_x, int n_tiles, int remap,
                     const float *__restrict__ gimg, float *__restrict__ gtex, const float4 *__restrict__ nrec, const float4 *__restrict__ gn, DetK det) {
-  constexpr int NSUB = 4 / R;
   constexpr bool MAT = MATM != 0, TEX = MATM == 2;
   __shared__ uint2 s_wstack[WIDE ? FFX_WSTACK : 1];
   const int tile = __builtin_amdgcn_readfirstlane(xcd_remap(blockIdx.x, gridDim.x, remap) * (blockDim.x >> 6) + (threadIdx.x >> 6)); // wave-uniform: say so
@@ -3573,8 +3446,8 @@ __global__ void __launch_bounds__(PK_BLOCK) __attribute__((amdgpu_waves_per_eu(M
   const int W = c.cam.W, H = c.cam.H; // (the only direct use of the by-value copy; see kernarg_shade)
   const float inv_spp = RF ? 1.0f : 1.0f / (float)spp; // (RF: the normalisation is the weight inside G)
   const int passes = (spp + 63) >> 6;
-  static_assert(!RF || R == 1, "the filtered adjoint walks one pixel per wave");
-  for (int sub = 0; sub < NSUB; ++sub) {
+  static_assert(R == 1, "one ray per lane");
+  for (int sub = 0; sub < 4; ++sub) { // the tile's four pixels
     int px[R], py[R];
     packet_pixels<R>(tile, tiles_x, sub, px, py);
     bool live[R], any_live = false;
@@ -3611,7 +3484,7 @@ __global__ void __launch_bounds__(PK_BLOCK) __attribute__((amdgpu_waves_per_eu(M
         cam_ray(cam, ((float)px[r] + jx) * cam.inv_w, ((float)py[r] + jy) * cam.inv_h, o[r], d[r], nt[r], ft[r]);
       }
       SampleTerms st[R];
-      shade_sample_pk<R, WIDE, MATM>(nodes, recs, arecs, astride, ws, s_wstack, active, o, d, nt, ft, st, nrec, gn, px[0], py[0]);
+      shade_sample_pk<WIDE, MATM>(nodes, recs, arecs, astride, ws, s_wstack, active[0], o[0], d[0], nt[0], ft[0], st[0], nrec, gn, px[0], py[0]);
       const ShadeK &ct = kernarg_shade(); // phase: scatter into the texture gradient
       const int tc = ct.tc;
 #pragma unroll
@@ -5043,19 +4916,19 @@ __global__ void __launch_bounds__(PK_BLOCK) __attribute__((amdgpu_waves_per_eu(F
   for (int i = threadIdx.x & 63; i < (RF ? 4 * 64 : 8 * FFX_AOV_PITCH); i += 64) s_acc[i] = 0.f;
   __builtin_amdgcn_wave_barrier();
   for (int pass = 0; pass < passes; ++pass) {
-    Hit h[1];
+    Hit h;
     bool hit;
     {
       const AovK &a = kernarg_first<AovK>();
       const Sample q = sample_of(a, threadIdx.x & 63, pass);
-      const v3 o[1] = {q.o}, d[1] = {q.d};
-      const float nt[1] = {q.nt}, ft[1] = {q.ft};
-      const bool active[1] = {q.active};
-      bool fnd[1];
+      const v3 o = q.o, d = q.d;
+      const float nt = q.nt, ft = q.ft;
+      const bool active = q.active;
+      bool fnd;
       bool binned = false;
-      if (a.c.bins.g[0].on) binned = bins_block(a.c.bins, q.bx0, q.by0, 1 << a.bw_log2, 1 << a.bh_log2, a.arecs, d[0], nt[0], ft[0], wballot(active[0]), h[0]);
-      if (!binned) traverse_packet_any<false, 1, WIDE>(a.nodes, a.arecs, a.ws, s_wstack, o, d, nt, ft, active, h, fnd);
-      hit = active[0] && h[0].prim >= 0;
+      if (a.c.bins.g[0].on) binned = bins_block(a.c.bins, q.bx0, q.by0, 1 << a.bw_log2, 1 << a.bh_log2, a.arecs, d, nt, ft, wballot(active), h);
+      if (!binned) traverse_packet_any<false, WIDE>(a.nodes, a.arecs, a.ws, s_wstack, o, d, nt, ft, active, h, fnd);
+      hit = active && h.prim >= 0;
     }
     const AovK &a = kernarg_first<AovK>();
     const int lane = lane_again();
@@ -5063,7 +4936,7 @@ __global__ void __launch_bounds__(PK_BLOCK) __attribute__((amdgpu_waves_per_eu(F
     const int ppw_log2 = a.bw_log2 + a.bh_log2;
     if constexpr (RF) {
       float v[3] = {0.f, 0.f, 0.f};
-      if (hit) aov_group(a.c, a.group, a.recs, a.arecs, a.nrec, a.gn, h[0], q.nt, q.o, q.d, v);
+      if (hit) aov_group(a.c, a.group, a.recs, a.arecs, a.nrec, a.gn, h, q.nt, q.o, q.d, v);
       float gx[5], gy[5];
       rf_weights(a.c.rf, q.jx, gx);
       rf_weights(a.c.rf, q.jy, gy);
@@ -5085,7 +4958,7 @@ __global__ void __launch_bounds__(PK_BLOCK) __attribute__((amdgpu_waves_per_eu(F
 #pragma unroll 1
       for (int g = 0; g < FFX_AOV_GROUPS; ++g) {
         float v[3] = {0.f, 0.f, 0.f};
-        if (hit) aov_group(a.c, g, a.recs, a.arecs, a.nrec, a.gn, h[0], q.nt, q.o, q.d, v);
+        if (hit) aov_group(a.c, g, a.recs, a.arecs, a.nrec, a.gn, h, q.nt, q.o, q.d, v);
         for (int m = 1; m < spp_w; m <<= 1) {
           v[0] += __shfl_xor(v[0], m, 64);
           v[1] += __shfl_xor(v[1], m, 64);
