@@ -33,7 +33,7 @@ class BvhInfo(C.Structure):
         ("n_wide", C.c_int32),
         ("wide_depth", C.c_int32),
         ("wide_root", C.c_int32),
-        ("wide_pad", C.c_int32),
+        ("leaf_pad", C.c_float),
         ("off_wnodes", C.c_uint64),
         ("off_wsrc", C.c_uint64),
         ("off_tq", C.c_uint64),

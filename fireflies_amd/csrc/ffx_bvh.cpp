@@ -348,6 +348,17 @@ int ffx_bvh_build_host(const float *verts, int n_verts, const int32_t *tris, int
   info->n_tris = n_tris;
   info->n_nodes = n_nodes;
   info->max_depth = b.max_depth + 1;
+  {
+    // the absolute term of the leaf pad (ffx.h: leaf_pad): 2^-16 of the scene scale, the largest |coordinate| of the build
+    // vertices — a maximum and a multiplication by a power of two, the same bits as the oracle's.  The builder itself writes no box: every box
+    // of the blob, the first pose's included, comes from ffx_scene_update.
+    float scale = 0.f;
+    for (long i = 0; i < 3L * n_verts; ++i) {
+      const float a = fabsf(verts[i]);
+      if (a > scale && a <= 3.0e38f) scale = a;
+    }
+    info->leaf_pad = 0x1p-16f * scale;
+  }
   uint64_t off = 64;
   info->off_nodes = off;
   off += (uint64_t)n_nodes * sizeof(BvhNode);

@@ -158,8 +158,10 @@ __global__ void __launch_bounds__(UPD_BLOCK)
 }
 
 // conservative box of a leaf's triangles.  The intersection test works on (v0, e1, e2), whose
-// corners v0+e1, v0+e2 are re-rounded here, so the box is widened by a few ulps.
-__device__ __forceinline__ void leaf_box(const TriRec *__restrict__ recs, int32_t code, float lo[3], float hi[3]) {
+// corners v0+e1, v0+e2 are re-rounded here, so the box is widened by a few ulps of the coordinate — and by leaf_pad (ffx.h,
+// DESIGN.md 4.1), the term that does not vanish where the coordinate does: the exact test accepts rays that pass an edge on the
+// outside by a few ulp of their distance from the apex.  One fma, as in the oracle's refit_rec.
+__device__ __forceinline__ void leaf_box(const TriRec *__restrict__ recs, int32_t code, float leaf_pad, float lo[3], float hi[3]) {
   uint32_t lc = (uint32_t)~code;
   int first = (int)(lc >> 3), count = (int)(lc & 7u) + 1;
 #pragma unroll
@@ -170,19 +172,19 @@ __device__ __forceinline__ void leaf_box(const TriRec *__restrict__ recs, int32_
     for (int a = 0; a < 3; ++a) {
       float p0 = r.v0[a], p1 = r.v0[a] + r.e1[a], p2 = r.v0[a] + r.e2[a];
       float mn = fminf(p0, fminf(p1, p2)), mx = fmaxf(p0, fmaxf(p1, p2));
-      float pad = 4e-7f * fmaxf(fabsf(mn), fabsf(mx));
+      float pad = fmaf(4e-7f, fmaxf(fabsf(mn), fabsf(mx)), leaf_pad);
       lo[a] = fminf(lo[a], mn - pad);
       hi[a] = fmaxf(hi[a], mx + pad);
     }
   }
 }
 
-__device__ __forceinline__ void child_box(const BvhNode *nodes, const TriRec *__restrict__ recs, int32_t c, float lo[3], float hi[3]) {
+__device__ __forceinline__ void child_box(const BvhNode *nodes, const TriRec *__restrict__ recs, int32_t c, float leaf_pad, float lo[3], float hi[3]) {
   if (c == FFX_EMPTY_CHILD) {
 #pragma unroll
     for (int a = 0; a < 3; ++a) { lo[a] = INFINITY; hi[a] = -INFINITY; }
   } else if (c < 0) {
-    leaf_box(recs, c, lo, hi);
+    leaf_box(recs, c, leaf_pad, lo, hi);
   } else {
     const BvhNode &n = nodes[c];
 #pragma unroll
@@ -190,30 +192,30 @@ __device__ __forceinline__ void child_box(const BvhNode *nodes, const TriRec *__
   }
 }
 
-__device__ __forceinline__ void refit_node(BvhNode *nodes, const TriRec *__restrict__ recs, int id) {
+__device__ __forceinline__ void refit_node(BvhNode *nodes, const TriRec *__restrict__ recs, int id, float leaf_pad) {
   BvhNode &n = nodes[id];
   float lo[3], hi[3];
-  child_box(nodes, recs, n.c0, lo, hi);
+  child_box(nodes, recs, n.c0, leaf_pad, lo, hi);
 #pragma unroll
   for (int a = 0; a < 3; ++a) { n.lo0[a] = lo[a]; n.hi0[a] = hi[a]; }
-  child_box(nodes, recs, n.c1, lo, hi);
+  child_box(nodes, recs, n.c1, leaf_pad, lo, hi);
 #pragma unroll
   for (int a = 0; a < 3; ++a) { n.lo1[a] = lo[a]; n.hi1[a] = hi[a]; }
 }
 
 __global__ void __launch_bounds__(UPD_BLOCK)
-    k_refit_level(BvhNode *nodes, const TriRec *__restrict__ recs, const int32_t *__restrict__ refit, int begin, int end) {
+    k_refit_level(BvhNode *nodes, const TriRec *__restrict__ recs, const int32_t *__restrict__ refit, int begin, int end, float leaf_pad) {
   int i = begin + blockIdx.x * UPD_BLOCK + threadIdx.x;
   if (i >= end) return;
-  refit_node(nodes, recs, refit[i]);
+  refit_node(nodes, recs, refit[i], leaf_pad);
 }
 
 struct TailLevels { int n; int start[FFX_MAX_LEVELS + 1]; };
 
-__global__ void __launch_bounds__(TAIL_BLOCK) k_refit_tail(BvhNode *nodes, const TriRec *__restrict__ recs, const int32_t *__restrict__ refit, TailLevels lv) {
+__global__ void __launch_bounds__(TAIL_BLOCK) k_refit_tail(BvhNode *nodes, const TriRec *__restrict__ recs, const int32_t *__restrict__ refit, TailLevels lv, float leaf_pad) {
   for (int l = 0; l < lv.n; ++l) {
     int i = lv.start[l] + threadIdx.x;
-    if (i < lv.start[l + 1]) refit_node(nodes, recs, refit[i]);
+    if (i < lv.start[l + 1]) refit_node(nodes, recs, refit[i], leaf_pad);
     __threadfence_block();
     __syncthreads();
   }
@@ -229,7 +231,7 @@ __device__ __forceinline__ void wide_box(const float lo[3], const float hi[3], W
 }
 __global__ void __launch_bounds__(UPD_BLOCK)
     k_wide_quant(const BvhNode *__restrict__ nodes, const TriRec *__restrict__ recs, int n_tris, WideChild *__restrict__ tq, WideChild *__restrict__ wn,
-                 const int32_t *__restrict__ wsrc, int n_wchild, WideHdr *__restrict__ hdr) {
+                 const int32_t *__restrict__ wsrc, int n_wchild, WideHdr *__restrict__ hdr, float leaf_pad) {
   const int i = blockIdx.x * UPD_BLOCK + threadIdx.x;
   if (i == 0) {
 #pragma unroll
@@ -237,7 +239,7 @@ __global__ void __launch_bounds__(UPD_BLOCK)
   }
   if (i < n_tris) {
     float lo[3], hi[3];
-    leaf_box(recs, ~(int32_t)((uint32_t)i << 3), lo, hi); // the padded box of the single triangle in slot i
+    leaf_box(recs, ~(int32_t)((uint32_t)i << 3), leaf_pad, lo, hi); // the padded box of the single triangle in slot i
     WideChild c;
     wide_box(lo, hi, c);
     c.ref = 0;
@@ -262,14 +264,14 @@ __global__ void __launch_bounds__(UPD_BLOCK)
 #ifndef FUSED_BLOCK
 #define FUSED_BLOCK 64
 #endif
-__device__ __forceinline__ void tri_wide_box(const float (&p0)[3], const float (&e1)[3], const float (&e2)[3], WideChild &c) {
+__device__ __forceinline__ void tri_wide_box(const float (&p0)[3], const float (&e1)[3], const float (&e2)[3], float leaf_pad, WideChild &c) {
   // the padded box of ONE triangle exactly as leaf_box forms it from the record (corners re-rounded as v0 + e)
   float lo[3], hi[3];
 #pragma unroll
   for (int a = 0; a < 3; ++a) {
     const float q0 = p0[a], q1 = p0[a] + e1[a], q2 = p0[a] + e2[a];
     const float mn = fminf(q0, fminf(q1, q2)), mx = fmaxf(q0, fmaxf(q1, q2));
-    const float pad = 4e-7f * fmaxf(fabsf(mn), fabsf(mx));
+    const float pad = fmaf(4e-7f, fmaxf(fabsf(mn), fabsf(mx)), leaf_pad);
     lo[a] = mn - pad;
     hi[a] = mx + pad;
   }
@@ -279,11 +281,11 @@ __device__ __forceinline__ void tri_wide_box(const float (&p0)[3], const float (
   c.pad = 0;
 }
 
-__device__ __forceinline__ void plan_levels(BvhNode *nodes, const TriRec *recs, const int32_t *__restrict__ plan, const int32_t *__restrict__ h) {
+__device__ __forceinline__ void plan_levels(BvhNode *nodes, const TriRec *recs, const int32_t *__restrict__ plan, const int32_t *__restrict__ h, float leaf_pad) {
   const int lvl0 = h[2], n_l = h[3];
   for (int l = 0; l < n_l; ++l) {
     const int b = plan[lvl0 + l], e = plan[lvl0 + l + 1];
-    for (int i = b + (int)threadIdx.x; i < e; i += FUSED_BLOCK) refit_node(nodes, recs, plan[i]);
+    for (int i = b + (int)threadIdx.x; i < e; i += FUSED_BLOCK) refit_node(nodes, recs, plan[i], leaf_pad);
     __threadfence_block();
     __syncthreads();
   }
@@ -309,7 +311,7 @@ __global__ void __launch_bounds__(FUSED_BLOCK)
     k_scene_update_fused(BvhNode *nodes, TriRec *recs, const int32_t *__restrict__ order, WideChild *tq, WideChild *wn, const int32_t *__restrict__ wsrc,
                          int32_t *plan, int n_treelets, int counter_at, const float *__restrict__ src_verts, const int32_t *__restrict__ tris,
                          const int32_t *__restrict__ tri_shape, const int32_t *__restrict__ vert_off, const float *__restrict__ xform, int n_shapes, ShapeTabH tab,
-                         SmoothTab sm, int mode) {
+                         SmoothTab sm, int mode, float leaf_pad) {
   // mode 0: the whole update (the workgroup that arrives last re-fits the top); 1: the treelets only, 2: the top only — the same update as
   // two launches (FFX_REFIT=split).  Publishing needs an agent-scope release fence in every treelet's workgroup, and on this part that fence
   // writes back the workgroup's whole L2 — megabytes of fresh records; a kernel boundary does the same once.
@@ -317,7 +319,7 @@ __global__ void __launch_bounds__(FUSED_BLOCK)
   __shared__ int s_last;
   if (mode == 2) {
     const int32_t *ht = plan + 8 * n_treelets;
-    plan_levels(nodes, recs, plan, ht);
+    plan_levels(nodes, recs, plan, ht, leaf_pad);
     plan_wide_children(nodes, wn, wsrc, plan, ht);
     return;
   }
@@ -355,13 +357,13 @@ __global__ void __launch_bounds__(FUSED_BLOCK)
     if (sm.gn) sm.gn[k] = unit_normal_of(e1, e2, sh, sflag != 0.f);
     const float a0[3] = {p[0].x, p[0].y, p[0].z}, a1[3] = {e1.x, e1.y, e1.z}, a2[3] = {e2.x, e2.y, e2.z};
     WideChild c;
-    tri_wide_box(a0, a1, a2, c);
+    tri_wide_box(a0, a1, a2, leaf_pad, c);
     tq[k] = c;
   }
   __threadfence_block();
   __syncthreads();
   // ---- B, C: this treelet's nodes by height, then the wide children whose boxes live in them
-  plan_levels(nodes, recs, plan, h);
+  plan_levels(nodes, recs, plan, h, leaf_pad);
   plan_wide_children(nodes, wn, wsrc, plan, h);
   if (mode == 1) return;
   // ---- D: publish; the last workgroup to arrive re-fits the top of the tree
@@ -372,7 +374,7 @@ __global__ void __launch_bounds__(FUSED_BLOCK)
   if (!s_last) return;
   __threadfence();
   const int32_t *ht = plan + 8 * n_treelets;
-  plan_levels(nodes, recs, plan, ht);
+  plan_levels(nodes, recs, plan, ht, leaf_pad);
   plan_wide_children(nodes, wn, wsrc, plan, ht);
   if (threadIdx.x == 0) plan[counter_at] = 0; // ready for the next update of this blob (stream-ordered)
 }
@@ -401,7 +403,7 @@ static int scene_update_impl(void *bvh, const ffx_bvh_info *info, const float *s
       hipLaunchKernelGGL(k_scene_update_fused<true>, dim3(1), dim3(FUSED_BLOCK), 0, (hipStream_t)s, (BvhNode *)(b + info->off_nodes), (TriRec *)(b + info->off_recs),
                          (const int32_t *)(b + info->off_order), (WideChild *)(b + info->off_tq), (WideChild *)(b + info->off_wnodes), (const int32_t *)(b + info->off_wsrc),
                          (int32_t *)(b + info->off_plan), info->n_treelets, info->plan_ints - 1, (const float *)nullptr, (const int32_t *)nullptr, (const int32_t *)nullptr,
-                         (const int32_t *)nullptr, (const float *)nullptr, 1, tab0, sm0, 2);
+                         (const int32_t *)nullptr, (const float *)nullptr, 1, tab0, sm0, 2, info->leaf_pad);
       FFX_CHECK_LAUNCH("scene_refit_top");
     }
     return FFX_OK;
@@ -460,10 +462,10 @@ static int scene_update_impl(void *bvh, const ffx_bvh_info *info, const float *s
       const dim3 grid(mode == 2 ? 1 : info->n_treelets);
       if (host_tab)
         hipLaunchKernelGGL(k_scene_update_fused<true>, grid, dim3(FUSED_BLOCK), 0, st, nodes, recs, order, tq, wn, wsrc, plan, info->n_treelets,
-                           info->plan_ints - 1, src_verts, tris, tri_shape, (const int32_t *)nullptr, (const float *)nullptr, n_shapes, tab, sm, mode);
+                           info->plan_ints - 1, src_verts, tris, tri_shape, (const int32_t *)nullptr, (const float *)nullptr, n_shapes, tab, sm, mode, info->leaf_pad);
       else
         hipLaunchKernelGGL(k_scene_update_fused<false>, grid, dim3(FUSED_BLOCK), 0, st, nodes, recs, order, tq, wn, wsrc, plan, info->n_treelets,
-                           info->plan_ints - 1, src_verts, tris, tri_shape, vert_off, xform, n_shapes, tab, sm, mode);
+                           info->plan_ints - 1, src_verts, tris, tri_shape, vert_off, xform, n_shapes, tab, sm, mode, info->leaf_pad);
     }
     FFX_CHECK_LAUNCH("scene_update/fused");
     return FFX_OK;
@@ -486,21 +488,21 @@ static int scene_update_impl(void *bvh, const ffx_bvh_info *info, const float *s
       if (info->level_start[m + 1] - info->level_start[m] > TAIL_BLOCK) { tail_ok = false; break; }
     if (tail_ok) break;
     hipLaunchKernelGGL(k_refit_level, dim3(ffx_cdiv(cnt, UPD_BLOCK)), dim3(UPD_BLOCK), 0, st, nodes, recs, refit, info->level_start[l],
-                       info->level_start[l + 1]);
+                       info->level_start[l + 1], info->leaf_pad);
     FFX_CHECK_LAUNCH("scene_update/refit_level");
   }
   if (l < info->n_levels) {
     TailLevels lv;
     lv.n = info->n_levels - l;
     for (int m = 0; m <= lv.n; ++m) lv.start[m] = info->level_start[l + m];
-    hipLaunchKernelGGL(k_refit_tail, dim3(1), dim3(TAIL_BLOCK), 0, st, nodes, recs, refit, lv);
+    hipLaunchKernelGGL(k_refit_tail, dim3(1), dim3(TAIL_BLOCK), 0, st, nodes, recs, refit, lv, info->leaf_pad);
     FFX_CHECK_LAUNCH("scene_update/refit_tail");
   }
   if (info->off_tq != 0) { // the 64-wide overlay of the wave-packet kernels
     const int n_wchild = info->n_wide * FFX_WIDE;
     hipLaunchKernelGGL(k_wide_quant, dim3(ffx_cdiv((long)info->n_tris + n_wchild, UPD_BLOCK)), dim3(UPD_BLOCK), 0, st, nodes, recs, info->n_tris,
                        (WideChild *)(base + info->off_tq), (WideChild *)(base + info->off_wnodes), (const int32_t *)(base + info->off_wsrc), n_wchild,
-                       (WideHdr *)(base + info->off_whdr));
+                       (WideHdr *)(base + info->off_whdr), info->leaf_pad);
     FFX_CHECK_LAUNCH("scene_update/wide_quant");
   }
   return FFX_OK;

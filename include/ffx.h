@@ -455,7 +455,9 @@ typedef struct ffx_bvh_info {
   int32_t n_wide;     /* wide inner nodes (0: the whole scene is one cluster) */
   int32_t wide_depth; /* wide inner levels above the clusters */
   int32_t wide_root;  /* reference of the root: cluster << 31 | element << 6 | (count - 1), elements of 32 B from off_wnodes */
-  int32_t wide_pad;
+  float leaf_pad;     /* the absolute term of the leaf boxes' pad at re-fit: 2^-16 x the largest |coordinate| of the vertices given
+                         to ffx_bvh_build_host, written by it (both libraries; this word was padding and is 0 in an older blob's info: no
+                         absolute term).  ffx_scene_update pads a leaf box by fmaf(4e-7, max(|lo|, |hi|), leaf_pad) per axis. */
   uint64_t off_wnodes; /* n_wide x 64 x 32 B child records */
   uint64_t off_wsrc;   /* n_wide x 64 x int32: where each child's box lives in the binary tree */
   uint64_t off_tq;     /* n_tris (+ 64 of padding) x 32 B triangle boxes, leaf-slot order; = off_wnodes + n_wide * 2048 */

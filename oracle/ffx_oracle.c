@@ -785,6 +785,17 @@ static int build_rec(onode *nodes, int *n_nodes, int *order, int first, int coun
   return id;
 }
 
+/* the absolute term of the leaf pad (include/ffx.h ffx_bvh_info.leaf_pad): 2^-16 of the scene scale, the largest
+ * |coordinate| of the build vertices (a maximum and a multiplication by a power of two: the same bits in both libraries) */
+static float leaf_pad_of(const float *verts, int n_verts) {
+  float s = 0.f;
+  for (long i = 0; i < 3L * n_verts; ++i) {
+    const float a = fabsf(verts[i]);
+    if (a > s && a <= 3.0e38f) s = a;
+  }
+  return 0x1p-16f * s;
+}
+
 int ffx_bvh_build_host(const float *verts, int n_verts, const int32_t *tris, int n_tris, void *blob, size_t blob_bytes, ffx_bvh_info *info) {
   if (!verts || !tris || !blob || !info || n_tris < 1 || n_verts < 1) FAIL(FFX_ERR_ARG, "bvh_build_host: bad argument");
   if (blob_bytes < ffx_bvh_blob_bytes(n_tris)) FAIL(FFX_ERR_NOMEM, "bvh_build_host: blob too small");
@@ -814,10 +825,11 @@ int ffx_bvh_build_host(const float *verts, int n_verts, const int32_t *tris, int
   info->n_nodes = n_nodes;
   info->max_depth = max_depth + 1;
   info->n_levels = 1;
+  info->leaf_pad = leaf_pad_of(verts, n_verts);
   return FFX_OK;
 }
 
-static void refit_rec(onode *nodes, const orec *recs, int id) {
+static void refit_rec(onode *nodes, const orec *recs, int id, float leaf_pad) {
   onode *nd = &nodes[id];
   for (int a = 0; a < 3; ++a) { nd->lo[a] = INFINITY; nd->hi[a] = -INFINITY; }
   if (nd->left < 0) {
@@ -826,17 +838,19 @@ static void refit_rec(onode *nodes, const orec *recs, int id) {
       for (int a = 0; a < 3; ++a) {
         float p0 = r->v0[a], p1 = r->v0[a] + r->e1[a], p2 = r->v0[a] + r->e2[a];
         /* e1 = v1 - v0 is rounded, so pad by the exact corners is not available: use the
-           corners as reconstructed AND widen by one ulp-scale epsilon */
+           corners as reconstructed AND widen by one ulp-scale epsilon of the coordinate; plus leaf_pad, the term that does not
+           vanish where the coordinate does (a seam in a coordinate plane): the exact test accepts rays that pass an edge on the
+           outside by a few ulp of their distance from the apex */
         float mn = fminf(p0, fminf(p1, p2)), mx = fmaxf(p0, fmaxf(p1, p2));
-        float pad = 4e-7f * fmaxf(fabsf(mn), fabsf(mx));
+        float pad = fmaf(4e-7f, fmaxf(fabsf(mn), fabsf(mx)), leaf_pad);
         if (mn - pad < nd->lo[a]) nd->lo[a] = mn - pad;
         if (mx + pad > nd->hi[a]) nd->hi[a] = mx + pad;
       }
     }
     return;
   }
-  refit_rec(nodes, recs, nd->left);
-  refit_rec(nodes, recs, nd->right);
+  refit_rec(nodes, recs, nd->left, leaf_pad);
+  refit_rec(nodes, recs, nd->right, leaf_pad);
   for (int a = 0; a < 3; ++a) {
     nd->lo[a] = fminf(nodes[nd->left].lo[a], nodes[nd->right].lo[a]);
     nd->hi[a] = fmaxf(nodes[nd->left].hi[a], nodes[nd->right].hi[a]);
@@ -941,7 +955,7 @@ int ffx_scene_update(void *bvh, const ffx_bvh_info *info, const float *src_verts
       }
     }
   }
-  refit_rec(nodes, recs, 0);
+  refit_rec(nodes, recs, 0, info->leaf_pad);
   return FFX_OK;
 }
 
@@ -1001,7 +1015,19 @@ static inline int tri_hit_apex(const orec *r, v3 o, v3 d, float tmin, float *t_o
   return 1;
 }
 
+/* Tree-free mode (tests only; not part of include/ffx.h): while the switch is set, closest_hit and occluded enter EVERY box, so every
+ * leaf is visited and every triangle tested — triangle tests, acceptance rule and tie-break as they are.  What a walk returns with the
+ * switch set is what "the triangle test alone decides"  means; the tree may only ever make that cheaper.  Process-wide;
+ * set it before a call, never during one.  -> the previous value */
+static int g_tree_free;
+int ffx_oracle_tree_free(int on) {
+  const int was = g_tree_free;
+  g_tree_free = on != 0;
+  return was;
+}
+
 static inline int box_hit(const onode *nd, v3 o, v3 id, float tmin, float tmax) {
+  if (g_tree_free) return 1;
   float t0 = tmin, t1 = tmax;
   const float oo[3] = {o.x, o.y, o.z}, ii[3] = {id.x, id.y, id.z};
   for (int a = 0; a < 3; ++a) {
@@ -1027,7 +1053,7 @@ static void closest_hit(const onode *nodes, const orec *recs, v3 o, v3 d, float 
   while (sp) {
     const onode *nd = &nodes[stack[--sp]];
     /* boxes are culled against the hit distance WIDENED by 3 ulp: a box that ends exactly on the hit (a flat box in a coordinate plane, which
-     * refit_rec's relative pad leaves as it is) has the entry distance (plane - o) * (1/d), rounded up to three times where t = T/det is rounded
+     * refit_rec's relative pad leaves as it is when leaf_pad is 0) has the entry distance (plane - o) * (1/d), rounded up to three times where t = T/det is rounded
      * once, and may hold a triangle at the same t with a smaller id (tests/tie_scenes.py: sheets_far_from_their_plane) */
     if (!box_hit(nd, o, id, tmin, h->t * 1.0000004f)) continue;
     if (nd->left < 0) {

@@ -3,6 +3,7 @@
 TEST INFRASTRUCTURE ONLY — see the header of oracle/ffx_oracle.c.  Only tests/,
 __graft_entry__.smoke() and bench.py's cpu_baseline leg may import this module.
 """
+import contextlib
 import ctypes as C
 import os
 import subprocess
@@ -34,6 +35,21 @@ def api():
         _api = _abi.Api(C.CDLL(LIB_PATH))
         assert _api.backend == "cpu-oracle"
     return _api
+
+
+@contextlib.contextmanager
+def tree_free():
+    """Inside the block every closest-hit and any-hit walk of the oracle (trace_primary, trace_rays, the renders and their adjoints) skips
+    every box test and visits every leaf: the exact triangle test, its acceptance rule and the tie-break alone decide.  Slow (every ray
+    against every triangle); process-wide, so no oracle call of another thread may run meanwhile."""
+    lib = api().lib
+    lib.ffx_oracle_tree_free.restype = C.c_int
+    lib.ffx_oracle_tree_free.argtypes = [C.c_int]
+    was = lib.ffx_oracle_tree_free(1)
+    try:
+        yield
+    finally:
+        lib.ffx_oracle_tree_free(was)
 
 
 def _f32(a):

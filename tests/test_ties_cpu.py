@@ -16,6 +16,7 @@ def geom(oracle, sc, frame=0):
     pool, tris, shape, off, stride, nfr, alb = scenes.flatten(sc)
     g = oracle.Geometry(pool, tris, shape, off)
     g.update(np.tile(np.eye(4, dtype=np.float32), (len(sc.meshes), 1, 1)), (off + np.minimum(frame, nfr - 1) * stride).astype(np.int32))
+    ts.refit_with_marked_pad(sc, [g], np.tile(np.eye(4, dtype=np.float32), (len(sc.meshes), 1, 1)))
     return g, alb
 
 
@@ -27,7 +28,7 @@ def host_tex(sc, ch=1):
 
 
 @pytest.mark.parametrize("jitter", [0, 1])
-@pytest.mark.parametrize("make", [ts.sheets, ts.sheets_far_from_their_plane])
+@pytest.mark.parametrize("make", [ts.sheets, ts.sheets_far_from_their_plane, ts.sheets_far_unpadded])
 def test_stacked_sheets_tie_on_every_ray_and_the_first_shape_wins(oracle, make, jitter):
     out = []
     for fine_first in (False, True):
@@ -42,7 +43,7 @@ def test_stacked_sheets_tie_on_every_ray_and_the_first_shape_wins(oracle, make, 
 
 
 @pytest.mark.parametrize("shadows", [True, False])
-@pytest.mark.parametrize("make", [ts.sheets, ts.sheets_far_from_their_plane])
+@pytest.mark.parametrize("make", [ts.sheets, ts.sheets_far_from_their_plane, ts.sheets_far_unpadded])
 def test_a_coplanar_second_sheet_leaves_the_image_as_it_was(oracle, make, shadows):
     for fine_first in (False, True):
         sc = make(fine_first)

@@ -8,7 +8,8 @@ import torch
 from fireflies_amd import ops, scenes, scene_desc
 from tests import tie_scenes as ts
 from tests.conftest import assert_image_close
-from tests.test_hip_parity import _pair, _tex, dev, host
+from tests.test_hip_parity import _pair as _pair_as_built
+from tests.test_hip_parity import _tex, dev, host
 
 pytestmark = pytest.mark.gpu
 
@@ -28,6 +29,13 @@ def _need_gpu():
 def _no_knobs(monkeypatch):
     for k in KNOBS:
         monkeypatch.delenv(k, raising=False)
+
+
+def _pair(oracle, sc):
+    """the oracle's and the device's geometry of `sc`; a scene marked by tie_scenes.sheets_far_unpadded is re-fitted with leaf_pad = 0 on both"""
+    go, gd, alb = _pair_as_built(oracle, sc)
+    ts.refit_with_marked_pad(sc, [go, gd], np.tile(np.eye(4, dtype=np.float32), (len(sc.meshes), 1, 1)))
+    return go, gd, alb
 
 
 def bits(a):
@@ -74,6 +82,8 @@ K7_FIXTURES = {
     "sheets_fine_first": lambda: (ts.sheets(True), _shape0),
     "sheets_far": lambda: (ts.sheets_far_from_their_plane(False), _shape0),
     "sheets_far_fine_first": lambda: (ts.sheets_far_from_their_plane(True), _shape0),
+    "sheets_far_unpadded": lambda: (ts.sheets_far_unpadded(False), _shape0),
+    "sheets_far_unpadded_fine_first": lambda: (ts.sheets_far_unpadded(True), _shape0),
     "dup_colon": lambda: _dup("colon"),
     "dup_vocalfold": lambda: _dup("vocalfold"),
     "dup_hello": lambda: _dup("hello"),
@@ -238,7 +248,7 @@ def test_render_fwd_does_not_see_an_exact_copy_of_every_mesh(oracle, monkeypatch
 
 
 @pytest.mark.parametrize("walk", list(RENDER_WALKS))
-@pytest.mark.parametrize("make", [ts.sheets, ts.sheets_far_from_their_plane])
+@pytest.mark.parametrize("make", [ts.sheets, ts.sheets_far_from_their_plane, ts.sheets_far_unpadded])
 def test_renders_do_not_see_a_coplanar_second_sheet(oracle, monkeypatch, make, walk):
     """the stacked sheets under a spot light, in both orders: render_fwd at 5 and 70 spp, render_aov and a max_depth = 3 path render (primary rays on
     the per-lane walk) give, bit for bit, the image of the first sheet alone; the ids are the first sheet's"""

@@ -5,7 +5,8 @@ traversal order.  tests/test_ties_cpu.py proves on the oracle that every fixture
 to; tests/test_ties_gpu.py then holds every walk of the HIP library to the rule on them.
 
   sheets()        two coplanar planes at z = 2 (4x4 and 16x16 quads, two shapes): every ray ties between the shapes
-  sheets_far_from_their_plane()   the same in the plane z = 0 seen from z = -2.3: the boxes end exactly on the hit
+  sheets_far_from_their_plane()   the same in the plane z = 0 seen from z = -2.3: flat boxes, 2^-16 of the scene scale behind the hit
+  sheets_far_unpadded()           ... re-fitted with leaf_pad = 0: the boxes end exactly ON the hit (guards the cull's widening)
   duplicated(sc)  every mesh of `sc` appended once more as an extra shape: every hit ties with its copy
   reversed_tris / map_back   relabel a scene (triangle order reversed inside every mesh): a ray whose geometric pick
                   changes under the relabelling is one the id order decided — a natural tie of the stock scenes' seams
@@ -45,12 +46,33 @@ def first_sheet_only(sc):
 
 
 def sheets_far_from_their_plane(fine_first=False):
-    """the stacked sheets in the plane z = 0 seen from z = -2.3.  Every box of the scene is flat in z and ends exactly ON the hit:
-    the builders pad a box by 4e-7 of its own coordinates — nothing at z = 0 — and the eye's depth is no dyadic number, so
+    """the stacked sheets in the plane z = 0 seen from z = -2.3, with the builders' pad of today (4e-7 of a box's own
+    coordinates plus 2^-16 of the scene scale): every box of the scene is flat in z and ends 2^-16 x 2 BEHIND the hit.  This variant holds
+    the tie-break on boxes as every scene gets them; it no longer fails when a walk culls boxes against the bare hit distance —
+    sheets_far_unpadded does."""
+    return sheets(fine_first, z=0.0, eye_z=-2.3)
+
+
+def sheets_far_unpadded(fine_first=False):
+    """the same scene, marked (notes["leaf_pad"] = 0) for the tests to re-fit with ffx_bvh_info.leaf_pad set to 0 after the build — the
+    info of an older blob (include/ffx.h), and what a pose far larger than the build vertices comes to.  Then every box of the scene ends
+    exactly ON the hit: the relative pad is nothing at z = 0, and the eye's depth is no dyadic number, so
     the entry distance a box test computes, (0 - eye_z) * (1 / d_z), is rounded twice where the hit distance (0 - eye_z) / d_z is
     rounded once: on one ray in five it comes out one ulp BEHIND the hit.  A walk that culls boxes against the bare hit distance
-    then never looks at the other sheet."""
-    return sheets(fine_first, z=0.0, eye_z=-2.3)
+    then never looks at the other sheet.  This is the variant that guards the cull's widening (FFX_TIE_WIDEN, the octant and wide
+    walks' `sw`, the oracle's 1.0000004): with the widening removed it fails, the padded variant does not."""
+    sc = sheets_far_from_their_plane(fine_first)
+    return replace(sc, notes=dict(sc.notes, leaf_pad=0.0))
+
+
+def refit_with_marked_pad(sc, geometries, xforms):
+    """if `sc` is marked (notes["leaf_pad"]): set that value in the info of every geometry — the oracle's and the device's alike — and
+    re-fit, so that all boxes are rebuilt with it"""
+    pad = sc.notes.get("leaf_pad")
+    if pad is not None:
+        for g in geometries:
+            g.info.leaf_pad = float(pad)
+            g.update(xforms)
 
 
 # ----------------------------------------------------------------------------- exact duplicates
