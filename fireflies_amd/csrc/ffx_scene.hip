@@ -28,6 +28,8 @@
 // + 48*F (records out) + 64*N_nodes (nodes in/out).
 #include <stdlib.h>
 #include <string.h>
+#include <mutex>
+#include <unordered_map>
 
 #include "ffx_common.h"
 
@@ -391,6 +393,22 @@ static int refit_fused_enabled() {
 // top: 0 = the whole update; 1 = everything but the top of the tree (the treelets' records, boxes and nodes: all the pre-pass reads) — the caller owes
 // ffx_scene_refit_top before anything walks the tree; 2 = the top alone.  (1 and 2 only with the fused kernel's two-launch form, the default; every
 // other configuration does the whole update at 0 and 1 and nothing at 2: the top is then already in place.)
+// Which blobs hold no record flagged smooth: noted by every update that writes the records (the flags come from its `smooth` argument alone), asked
+// by the render launcher before it picks the instance that does not test the flag (ffx_trace.hip plain_scene).  1 flat, 0 smooth, -1 a blob no update
+// of this process has written (its records came from elsewhere: nothing is known).  Keyed by the blob's address: an update of a new blob at an
+// old address overwrites the entry.
+static std::mutex g_blob_flat_mu;
+static std::unordered_map<const void *, int> g_blob_flat;
+static void blob_note_flat(const void *bvh, int flat) {
+  std::lock_guard<std::mutex> lk(g_blob_flat_mu);
+  g_blob_flat[bvh] = flat;
+}
+int ffx_blob_flat(const void *bvh) {
+  std::lock_guard<std::mutex> lk(g_blob_flat_mu);
+  const auto it = g_blob_flat.find(bvh);
+  return it == g_blob_flat.end() ? -1 : it->second;
+}
+
 static int scene_update_impl(void *bvh, const ffx_bvh_info *info, const float *src_verts, const int32_t *tris, const int32_t *tri_shape,
                              const int32_t *vert_off, const float *xform, int n_shapes, const ffx_smooth *smooth, ffx_stream s, bool host_tab, int top = 0) {
   if (top == 2) {
@@ -431,6 +449,7 @@ static int scene_update_impl(void *bvh, const ffx_bvh_info *info, const float *s
   SmoothTab sm;
   memset(&sm, 0, sizeof sm);
   if (info->off_gn != 0 && info->off_gn + 16ull * (uint64_t)info->n_tris <= info->total_bytes) sm.gn = (float4 *)(base + info->off_gn);
+  blob_note_flat(bvh, -1); // (until this call's flags are known: a refusal below leaves the blob unknown)
   if (smooth) {
     if (!smooth->shape_smooth || !smooth->shape_vbase || !smooth->adj_start || !smooth->adj || !smooth->vnormals || smooth->n_vn < 1)
       FFX_FAIL(FFX_ERR_ARG, "scene_update: bad ffx_smooth");
@@ -450,6 +469,7 @@ static int scene_update_impl(void *bvh, const ffx_bvh_info *info, const float *s
       FFX_CHECK_LAUNCH("scene_update/vertex_normals");
     }
   }
+  blob_note_flat(bvh, sm.vn ? 0 : 1); // (sm.on[] is read by the record kernels only with sm.vn set: no shape flagged, or none given)
   if (info->off_plan != 0 && info->n_treelets > 0 && info->off_tq != 0 && refit_fused_enabled()) {
     if (info->plan_ints < 8 * (info->n_treelets + 1) + 1 || info->off_plan + 4ull * (uint64_t)info->plan_ints > info->total_bytes)
       FFX_FAIL(FFX_ERR_ARG, "scene_update: bad refit plan");

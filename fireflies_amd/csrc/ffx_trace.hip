@@ -680,6 +680,9 @@ __device__ __forceinline__ void material_terms_vjp(const float *__restrict__ m, 
 // ---- the same two functions on a row whose constants the host has derived once (ShadeK.mat_pre, FFX_PRE_FLOATS floats per row): no squares, clamps
 // and reciprocals of parameters per evaluation, one flag word instead of five parameter loads and compares.  The arithmetic of the lobes is
 // material_terms', with the host's IEEE values where that one forms hardware seeds (a last-bit difference, inside the parity tolerance).
+// PLAIN (k_render_fwd_pk's plain-scene instance): the host found no lobe flag set in any row — the flag word is the constant 0, the optional
+// lobes' tests and arms are not compiled; what remains is the arithmetic above, operation for operation
+template <bool PLAIN = false>
 __device__ __forceinline__ void material_geometry_p(const float *__restrict__ m, const float *__restrict__ p, v3 n, v3 wv, v3 wl, MatGeo &g) {
   g.cos_i = vdot(n, wv);
   g.cos_o = vdot(n, wl);
@@ -689,7 +692,7 @@ __device__ __forceinline__ void material_geometry_p(const float *__restrict__ m,
   g.ci_h = vdot(wv, wh);
   g.co_h = vdot(wl, wh);
   g.ch = vdot(n, wh);
-  if (__float_as_uint(p[9]) & FFX_PRE_ANISO) { // calc_dist_params + the shading frame coordinate_system(n): as material_geometry
+  if ((PLAIN ? 0u : __float_as_uint(p[9])) & FFX_PRE_ANISO) { // calc_dist_params + the shading frame coordinate_system(n): as material_geometry
     const float r2 = p[10], aniso = m[FFX_MAT_ANISOTROPIC];
     const float aspect = bsqrt(1.0f - 0.9f * aniso);
     const float ax = fmaxf(0.001f, bdiv(r2, aspect)), ay = fmaxf(0.001f, r2 * aspect);
@@ -711,7 +714,7 @@ __device__ __forceinline__ void material_geometry_p(const float *__restrict__ m,
     g.axay = a2;
   }
 }
-template <bool TEX = false>
+template <bool TEX = false, bool PLAIN = false>
 __device__ __forceinline__ void material_terms_p(const float *__restrict__ m, const float *__restrict__ p, const MatGeo &g, float &A, float &B, float b0 = 0.f, float b1 = 0.f,
                                                  float b2 = 0.f) {
   const float cos_i = g.cos_i, cos_o = g.cos_o, ch = g.ch, ci_h = g.ci_h, co_h = g.co_h;
@@ -720,7 +723,7 @@ __device__ __forceinline__ void material_terms_p(const float *__restrict__ m, co
   const bool facing = ci_h > 0.f && co_h > 0.f;
   float a = 0.f, b = 0.f;
   const float eta = p[0];
-  const uint32_t flags = __float_as_uint(p[9]);
+  const uint32_t flags = PLAIN ? 0u : __float_as_uint(p[9]);
   const float ct2 = 1.0f - (1.0f - ci_h * ci_h) * p[1];
   const float ct = ct2 > 0.f ? bsqrt(ct2) : 0.f;
   const float sw = schlick_weight(eta > 1.0f ? fabsf(ci_h) : ct);
@@ -2162,13 +2165,17 @@ __device__ __forceinline__ bool tex_footprint_lit(const float *__restrict__ tex,
 // MATM: 0 = [S,3] Lambert albedos, 1 = material rows, 2 = material rows some of which take their base colour from a texture
 // px, py (wave-uniform): the pixel the packet's primary rays belong to — the tile bins are tried first, the tree walks serve
 // what they cannot.  (The body's one-element arrays and single-trip loops: see as1.)
-template <bool WIDE, int MATM = 0>
+// PLAIN (k_render_fwd_pk<..., PLAIN>, MATM == 1): what the host proved about the scene before the launch (plain_scene) is a constant here — no record is
+// flagged smooth, the spot's frame is rigid, the projector's texture has one channel, every row is a principled row with a pre-row and no optional
+// lobe.  The tests and their arms are not compiled; the arithmetic that remains is the generic instance's, operation for operation.
+template <bool WIDE, int MATM = 0, bool PLAIN = false>
 __device__ __forceinline__ void shade_sample_pk(const BvhNode *__restrict__ nodes, const TriRec *__restrict__ recs, const TriApex *__restrict__ arecs,
                                                 uint32_t astride, const WideScene &ws, uint2 *__restrict__ stack, const bool &active_, const v3 &o_,
                                                 const v3 &d_, const float &nt_, const float &ft_, SampleTerms &st_,
                                                 const float4 *__restrict__ nrec, const float4 *__restrict__ gn, const int px, const int py,
                                                 const float *__restrict__ tex_probe = nullptr, const int blk_w = 1, const int blk_h = 1) {
   constexpr bool MAT = MATM != 0, TEX = MATM == 2;
+  static_assert(!PLAIN || MATM == 1, "the plain-scene instance renders principled rows without textured base colours");
   const bool (&active)[1] = as1(active_);
   const v3 (&o)[1] = as1(o_), (&d)[1] = as1(d_);
   const float (&nt)[1] = as1(nt_), (&ft)[1] = as1(ft_);
@@ -2238,15 +2245,15 @@ __device__ __forceinline__ void shade_sample_pk(const BvhNode *__restrict__ node
         float off = (1.0f + pmax) * RAY_EPS;
         q.Po = V3(fmaf(off, ng.x, q.P.x), fmaf(off, ng.y, q.P.y), fmaf(off, ng.z, q.P.z));
         ns = ng;
-        smooth = (gbits & FFX_GN_SMOOTH_BIT) != 0;
-        if (wballot(smooth) != 0ull) { // (wave-uniform: scenes without flagged records never enter)
+        if constexpr (!PLAIN) smooth = (gbits & FFX_GN_SMOOTH_BIT) != 0;
+        if (!PLAIN && wballot(smooth) != 0ull) { // (wave-uniform: scenes without flagged records never enter)
           const float4 ra = r4[0], rb = r4[1], rc = r4[2];
           const v3 ni = interpolated_normal<true>(nrec, smooth ? h[r].slot : 0, ra, rb, rc, o[r], d[r], ng);
           if (smooth) ns = ni;
         }
       }
     }
-    const bool any_smooth = wballot(smooth) != 0ull;
+    const bool any_smooth = !PLAIN && wballot(smooth) != 0ull;
     // ---- projector terms
     q.need_p = false;
     q.pfac = 0.f; q.u = 0.f; q.v = 0.f;
@@ -2278,7 +2285,7 @@ __device__ __forceinline__ void shade_sample_pk(const BvhNode *__restrict__ node
           if (any_smooth) lit = lit && (!smooth || vdot(q.ng, wi) > 0.f); // the emitter on the viewer's GEOMETRIC side too
           if constexpr (MAT) {
             // (material rows: the texture probe — see below — comes first, it saves the BSDF of a dark footprint too)
-            if (tex_probe && lit) lit = tex_footprint_lit(tex_probe, c.tw, c.th, c.tc, q.u, q.v);
+            if (tex_probe && lit) lit = tex_footprint_lit(tex_probe, c.tw, c.th, PLAIN ? 1 : c.tc, q.u, q.v);
           }
           if (lit) {
             q.need_p = true;
@@ -2305,7 +2312,7 @@ __device__ __forceinline__ void shade_sample_pk(const BvhNode *__restrict__ node
       if (any_smooth) front = front && (!smooth || vdot(q.ng, wi) > 0.f);
       if (front) {
         float cos_t;
-        if (c.s_rigid) { // (the spot's world-to-local is a rotation — the usual case: |ll| = |wi| = 1, and ll.z is one row of it)
+        if (PLAIN || c.s_rigid) { // (the spot's world-to-local is a rotation — the usual case: |ll| = |wi| = 1, and ll.z is one row of it)
           cos_t = -fmaf(c.s_w2l[8], wi.x, fmaf(c.s_w2l[9], wi.y, c.s_w2l[10] * wi.z));
         } else {
           v3 ll = xf_dir(c.s_w2l, V3(-wi.x, -wi.y, -wi.z));
@@ -2416,9 +2423,9 @@ __device__ __forceinline__ void shade_sample_pk(const BvhNode *__restrict__ node
       if constexpr (TEX) { st[r].base[0] = st[r].base[1] = st[r].base[2] = 0.f; }
       if (lit_p || lit_s) {
         const float *mrow = mat_table(c2) + (size_t)FFX_MAT_STRIDE * st[r].shape;
-        const bool mat_on = mrow[FFX_MAT_MODEL] != 0.f;
+        const bool mat_on = PLAIN || mrow[FFX_MAT_MODEL] != 0.f;
         // (wave-uniform: the rows travel with the call and the host derived their constants — other tables take the on-the-fly form)
-        const float *prow = c2.mat_pre_on ? c2.mat_pre + FFX_PRE_FLOATS * st[r].shape : nullptr;
+        const float *prow = (PLAIN || c2.mat_pre_on) ? c2.mat_pre + FFX_PRE_FLOATS * st[r].shape : nullptr;
         const v3 wv = V3(-d[r].x, -d[r].y, -d[r].z);
         if constexpr (TEX) { // base colour of this sample: the row's, or its texture at the hit (only lit samples need one)
           st[r].base[0] = mrow[0]; st[r].base[1] = mrow[1]; st[r].base[2] = mrow[2];
@@ -2438,7 +2445,7 @@ __device__ __forceinline__ void shade_sample_pk(const BvhNode *__restrict__ node
           float bA = vdot(q.ng, wi), bB = 0.f;
           if (mat_on) {
             MatGeo g;
-            if (prow) { material_geometry_p(mrow, prow, q.ng, wv, wi, g); material_terms_p<TEX>(mrow, prow, g, bA, bB, st[r].base[0], st[r].base[1], st[r].base[2]); }
+            if (PLAIN || prow) { material_geometry_p<PLAIN>(mrow, prow, q.ng, wv, wi, g); material_terms_p<TEX, PLAIN>(mrow, prow, g, bA, bB, st[r].base[0], st[r].base[1], st[r].base[2]); }
             else { material_geometry(mrow, q.ng, wv, wi, g); material_terms<TEX>(mrow, g, bA, bB, st[r].base[0], st[r].base[1], st[r].base[2]); }
           }
           q.pfac_b = q.pfac * bB;
@@ -2451,7 +2458,7 @@ __device__ __forceinline__ void shade_sample_pk(const BvhNode *__restrict__ node
           float bA = vdot(q.ng, wi), bB = 0.f;
           if (mat_on) {
             MatGeo g;
-            if (prow) { material_geometry_p(mrow, prow, q.ng, wv, wi, g); material_terms_p<TEX>(mrow, prow, g, bA, bB, st[r].base[0], st[r].base[1], st[r].base[2]); }
+            if (PLAIN || prow) { material_geometry_p<PLAIN>(mrow, prow, q.ng, wv, wi, g); material_terms_p<TEX, PLAIN>(mrow, prow, g, bA, bB, st[r].base[0], st[r].base[1], st[r].base[2]); }
             else { material_geometry(mrow, q.ng, wv, wi, g); material_terms<TEX>(mrow, g, bA, bB, st[r].base[0], st[r].base[1], st[r].base[2]); }
           }
           q.sfac_b = q.sfac * bB;
@@ -2851,7 +2858,11 @@ __device__ __forceinline__ float4 rf_window_g(const float4 *__restrict__ G, int 
 // its base travels in `adj_gtex`, the record areas' offsets (128-byte units) in cache_foot_off / cache_foot_b_off.
 // R (rays per lane) is 1 and stays in the template head: the benchmark and the committed profiles read ADJ and RF by their position
 // in the instance name as the profiler prints it, k_render_fwd_pk<1, true, 1, false, false, false>.  (Its [R] arrays and loops: see as1.)
-template <int R, bool WIDE, int MATM, bool ADJ = false, bool RF = false, bool RFC = false>
+// PLAIN (last, so the generic instances keep their printed names): the instance for a scene about which the host proved, before the launch, what the
+// generic one tests per sample (plain_scene below): principled rows that travel inline with their pre-rows, no optional lobe in any row, no smooth
+// record, a rigid spot, a one-channel projector texture, an f32 box film in one pass.  Same arithmetic, same order, same bits; FFX_K8_PLAIN=0 keeps
+// the generic instance.
+template <int R, bool WIDE, int MATM, bool ADJ = false, bool RF = false, bool RFC = false, bool PLAIN = false>
 __global__ void __launch_bounds__(PK_BLOCK) __attribute__((amdgpu_waves_per_eu(MATM ? FFX_PK_MAT_WAVES : FFX_PK1_WAVES, MATM ? FFX_PK_MAT_WAVES : FFX_PK1_WAVES)))
     k_render_fwd_pk(ShadeK c, const BvhNode *__restrict__ nodes, const TriRec *__restrict__ recs, const TriApex *__restrict__ arecs, uint32_t astride,
                     WideScene ws, const float *__restrict__ albedo, const float *__restrict__ tex, int spp, uint32_t seed_key, int tiles_x, int n_tiles, int remap,
@@ -2874,6 +2885,7 @@ __global__ void __launch_bounds__(PK_BLOCK) __attribute__((amdgpu_waves_per_eu(M
   __shared__ float s_foot_b[MAT ? 32 : 1]; // material rows: the footprint of the base_color-independent part
   static_assert(R == 1, "one ray per lane: the adjoint cache is written one pixel at a time");
   static_assert(!RFC || (RF && !ADJ), "RFC: the filtered forward that writes the per-sample adjoint records");
+  static_assert(!PLAIN || (MATM == 1 && !RF && !RFC), "PLAIN: principled rows, box film");
   FFX_TINIT();
   FFX_TSTART(twave);
   FFX_TSTART(tpro);
@@ -2888,7 +2900,7 @@ __global__ void __launch_bounds__(PK_BLOCK) __attribute__((amdgpu_waves_per_eu(M
   const int tile = wv >> wpt_log2, sub0 = (wv & ((1 << wpt_log2) - 1)) * ppw;
   const int lane = threadIdx.x & 63;
   const int W = c.cam.W, H = c.cam.H; // (the only direct use of the by-value copy)
-  const int passes = (spp + 63) >> 6;
+  const int passes = PLAIN ? 1 : (spp + 63) >> 6;
   // (wave-uniform, used once per pixel: kept in an SGPR — as a VGPR it was live across the whole kernel and spilled)
   const float inv_spp_u = inv_spp_arg; // 1 / spp from the host (a kernel argument is scalar by construction; the division here was ten vector instructions per wave)
   if (!ADJ && !RF && cache && wv == 0 && lane == 0) reinterpret_cast<CacheHdr *>(cache)->cap_stray = cap_stray; // (read back by K9 and ffx_render_cache_status; no wave of this launch reads it)
@@ -2935,7 +2947,7 @@ __global__ void __launch_bounds__(PK_BLOCK) __attribute__((amdgpu_waves_per_eu(M
       SampleTerms st[R];
       // (fp16 carries the call's flags: bit 0 fp16 film, bit 1 FFX_RENDER_SPARSE_ADJOINT — then the cache-writing forward may
       // skip dark footprints too: the caller only wants gradients of texels whose value is not zero)
-      shade_sample_pk<WIDE, MATM>(nodes, recs, arecs, astride, ws, s_wstack, active[0], o[0], d[0], nt[0], ft[0], st[0], nrec, gn, px[0], py[0], ((fold || RFC) && !(fp16 & 2)) ? nullptr : tex);
+      shade_sample_pk<WIDE, MATM, PLAIN>(nodes, recs, arecs, astride, ws, s_wstack, active[0], o[0], d[0], nt[0], ft[0], st[0], nrec, gn, px[0], py[0], ((fold || RFC) && !(fp16 & 2)) ? nullptr : tex);
       FFX_TSTOP(tk, 17);
       if constexpr (RFC) {
         // ---- the filtered film's adjoint cache: this pass's 64 records, if any of its samples is lit (one 1 KB store per wave)
@@ -3057,7 +3069,7 @@ __global__ void __launch_bounds__(PK_BLOCK) __attribute__((amdgpu_waves_per_eu(M
               const float *alb = mat_table(ca) + MS * st[0].shape;
               const float pf = st[0].proj_fac, pb = MAT ? st[0].proj_fac_b : 0.f;
               const float wx0 = st[0].wx0, wx1 = st[0].wx1, wy0 = st[0].wy0, wy1 = st[0].wy1;
-              if (ca.tc == 1) {
+              if (PLAIN || ca.tc == 1) {
                 float wsv = (g0 * alb[0] * ca.p_color[0] + g1 * alb[1] * ca.p_color[1] + g2 * alb[2] * ca.p_color[2]) * pf * inv_spp_u;
                 if (pb != 0.f) wsv += (g0 * ca.p_color[0] + g1 * ca.p_color[1] + g2 * ca.p_color[2]) * pb * inv_spp_u;
                 if (wsv != 0.f) {
@@ -3113,7 +3125,7 @@ __global__ void __launch_bounds__(PK_BLOCK) __attribute__((amdgpu_waves_per_eu(M
         float r0 = st[r].spot[0], r1 = st[r].spot[1], r2 = st[r].spot[2];
         float b0 = st[r].spot_b[0], b1 = st[r].spot_b[1], b2 = st[r].spot_b[2]; // (MAT only: dead otherwise)
         if (st[r].has_proj) {
-          const int tc = ct.tc;
+          const int tc = PLAIN ? 1 : ct.tc;
           size_t o00 = ((size_t)st[r].iy0 * ct.tw + st[r].ix0) * tc, o01 = ((size_t)st[r].iy0 * ct.tw + st[r].ix1) * tc;
           size_t o10 = ((size_t)st[r].iy1 * ct.tw + st[r].ix0) * tc, o11 = ((size_t)st[r].iy1 * ct.tw + st[r].ix1) * tc;
           const float wx0 = st[r].wx0, wx1 = st[r].wx1, wy0 = st[r].wy0, wy1 = st[r].wy1, pf = st[r].proj_fac, pb = st[r].proj_fac_b;
@@ -3181,7 +3193,7 @@ __global__ void __launch_bounds__(PK_BLOCK) __attribute__((amdgpu_waves_per_eu(M
           const float a2 = __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(c2), 63));
           if (lane == 0 && live[r]) {
             size_t o = (size_t)pix[r] * 3;
-            if (fp16 & 1) {
+            if (!PLAIN && (fp16 & 1)) {
               _Float16 *p = (_Float16 *)img;
               p[o] = (_Float16)vmul_s(a0, inv_spp_u);
               p[o + 1] = (_Float16)vmul_s(a1, inv_spp_u);
@@ -3194,9 +3206,10 @@ __global__ void __launch_bounds__(PK_BLOCK) __attribute__((amdgpu_waves_per_eu(M
             }
           }
           if (ADJ && adj_dot) { // (wave-uniform values: the same in every lane)
-            fin0 = (fp16 & 1) ? (float)(_Float16)vmul_s(a0, inv_spp_u) : vmul_s(a0, inv_spp_u);
-            fin1 = (fp16 & 1) ? (float)(_Float16)vmul_s(a1, inv_spp_u) : vmul_s(a1, inv_spp_u);
-            fin2 = (fp16 & 1) ? (float)(_Float16)vmul_s(a2, inv_spp_u) : vmul_s(a2, inv_spp_u);
+            const bool half_film = !PLAIN && (fp16 & 1);
+            fin0 = half_film ? (float)(_Float16)vmul_s(a0, inv_spp_u) : vmul_s(a0, inv_spp_u);
+            fin1 = half_film ? (float)(_Float16)vmul_s(a1, inv_spp_u) : vmul_s(a1, inv_spp_u);
+            fin2 = half_film ? (float)(_Float16)vmul_s(a2, inv_spp_u) : vmul_s(a2, inv_spp_u);
           }
         }
       }
@@ -3235,7 +3248,7 @@ __global__ void __launch_bounds__(PK_BLOCK) __attribute__((amdgpu_waves_per_eu(M
           const int ey = (lw * 13) >> 6, ex = lw - 5 * ey; // lw / 5, lw % 5 for lw < 25
           const int tx = fox + ex, ty = foy + ey;
           if (w != 0.f || wb != 0.f) {
-            if (ca.tc == 1) {
+            if (PLAIN || ca.tc == 1) {
               const float wsv = (g0 * alb[0] * ca.p_color[0] + g1 * alb[1] * ca.p_color[1] + g2 * alb[2] * ca.p_color[2]) * inv_spp_u;
               float val = wsv * w;
               if (wb != 0.f) val += (g0 * ca.p_color[0] + g1 * ca.p_color[1] + g2 * ca.p_color[2]) * inv_spp_u * wb;
@@ -5213,6 +5226,12 @@ static bool lowspp_blocks() {
   return !(e && strcmp(e, "0") == 0);
 }
 
+// k_render_fwd_pk's plain-scene instance for the scenes it covers (plain_scene); FFX_K8_PLAIN=0: the generic instance for every scene (A/B runs, tests)
+static bool k8_plain_enabled() {
+  const char *e = getenv("FFX_K8_PLAIN");
+  return !(e && strcmp(e, "0") == 0);
+}
+
 // ---- tile bins: the three grids of a scene description (ffx_common.h BinGrid).  A pure function of sd (and the environment), so that
 // ffx_apex_prepare and the render calls that follow it derive the same grids.  A grid is switched off (its packets walk the tree)
 // when its projection is not a central perspective, when a spot's cone is too wide for a perspective grid, or by FFX_BINS=0.
@@ -5577,8 +5596,27 @@ template <class F> static void dispatch_rf_mat(bool rf, bool mat, F &&f) {
   if (rf) by_mat(std::true_type());
   else by_mat(std::false_type());
 }
-// a k_render_fwd_pk launch's own arguments (the kernel's parameters: fp16, img, cache, cache_foot_off / cache_arena_off / cache_foot_b_off, ...)
-struct FwdPkArgs { int fp16; void *img; char *cache; uint32_t off[3], cap_stray; const float *adj_gimg; float *adj_gtex, *adj_dot; };
+// What k_render_fwd_pk<..., PLAIN> takes as constants, proved here from what the call carries (anything less: the generic instance).  The rows
+// travel inline and shade_prepare derived a pre-row for each (mat_pre_on), every row is a principled row (model != 0) with no optional lobe (its
+// flag word is 0), the blob's last update flagged no shape smooth (ffx_blob_flat: a blob this process has not updated is not known to be flat), a spot
+// is rigid, a projector texture has one channel, the film is f32 and takes one pass.  Box film, no adjoint cache: the route's own conditions.
+int ffx_blob_flat(const void *bvh); // (ffx_scene.hip; not part of the C ABI)
+static bool plain_scene(const RenderSetup &r, const ffx_scene_desc *sd, const void *bvh, int fp16) {
+  if (!k8_plain_enabled() || r.matm != 1 || !r.c.mat_inline || !r.c.mat_pre_on || (fp16 & FFX_RENDER_FP16) || r.spp > 64) return false;
+  if ((r.c.spot_on && !r.c.s_rigid) || (r.c.proj_on && r.c.tc != 1)) return false;
+  for (int k = 0; k < sd->n_shapes; ++k) { // (mat_pre_on: at most 8 rows, all inline)
+    uint32_t flags;
+    memcpy(&flags, &r.c.mat_pre[k * FFX_PRE_FLOATS + 9], 4);
+    if (flags != 0u || r.c.mat_h[k * FFX_MAT_STRIDE + FFX_MAT_MODEL] == 0.f) return false;
+  }
+  return ffx_blob_flat(bvh) == 1;
+}
+// launches of k_render_fwd_pk by instance: [0] plain-scene, [1] generic (a data symbol, not an entry point: fireflies_amd/ops.py
+// k8_launch_counters reads it in place — how mi.Scene.render_paths and the tests see which instance ran)
+extern "C" { unsigned long long ffx_k8_instance_launches[2] = {0ull, 0ull}; }
+// a k_render_fwd_pk launch's own arguments (the kernel's parameters: fp16, img, cache, cache_foot_off / cache_arena_off / cache_foot_b_off, ...);
+// plain: the scene passed plain_scene (the box film's route without an adjoint cache only)
+struct FwdPkArgs { int fp16; void *img; char *cache; uint32_t off[3], cap_stray; const float *adj_gimg; float *adj_gtex, *adj_dot; bool plain = false; };
 // ADJ: k_render_fwd_pk's ADJ (0 / 1), or 2 for the box film's route, which takes the fused adjoint iff a.adj_gtex
 template <int ADJ, bool RF = false, bool RFC = false>
 static void launch_fwd_pk(bool wide, const RenderSetup &r, const Packets &p, const float *tex, const FwdPkArgs &a, hipStream_t s) {
@@ -5586,10 +5624,19 @@ static void launch_fwd_pk(bool wide, const RenderSetup &r, const Packets &p, con
     auto launch = [&](auto adj) {
       constexpr bool WIDE = decltype(w)::value, A = decltype(adj)::value;
       constexpr int MATM = decltype(m)::value;
-      if constexpr ((WIDE || !RF) && (MATM < 2 || (!A && !RFC)))
-        hipLaunchKernelGGL((k_render_fwd_pk<1, WIDE, MATM, A, RF, RFC>), dim3(p.pgrid), dim3(64), 0, s, r.c, r.b.nodes, r.b.recs, p.arecs, p.astride, p.ws,
+      auto go = [&](auto plain) {
+        constexpr bool PLAIN = decltype(plain)::value;
+        __atomic_fetch_add(&ffx_k8_instance_launches[PLAIN ? 0 : 1], 1ull, __ATOMIC_RELAXED);
+        hipLaunchKernelGGL((k_render_fwd_pk<1, WIDE, MATM, A, RF, RFC, PLAIN>), dim3(p.pgrid), dim3(64), 0, s, r.c, r.b.nodes, r.b.recs, p.arecs, p.astride, p.ws,
                            r.c.mats, tex, r.spp, r.seed_key, p.ptx, p.pn, xcd_mode(r.n_pix), a.fp16, a.img, a.cache, p.ppw, 1.0f / (float)r.spp, a.off[0],
                            a.off[1], a.off[2], r.b.nrec, r.b.gn, a.cap_stray, a.adj_gimg, a.adj_gtex, a.adj_dot);
+      };
+      if constexpr ((WIDE || !RF) && (MATM < 2 || (!A && !RFC))) {
+        if constexpr (ADJ == 2 && MATM == 1) { // (the box film's route: the only one with a plain-scene instance)
+          if (a.plain) { go(std::true_type()); return; }
+        }
+        go(std::false_type());
+      }
     };
     if constexpr (ADJ != 2) launch(std::bool_constant<ADJ == 1>());
     else if (a.adj_gtex) launch(std::true_type());
@@ -5762,7 +5809,7 @@ static int render_fwd_impl(const void *bvh, const ffx_bvh_info *info, const ffx_
       FFX_CHECK_LAUNCH("render_fwd (pixel blocks)");
       return FFX_OK;
     }
-    launch_fwd_pk<2>(use_wide(info), r, p, tex, {img_fp16, img, (char *)cache, {foot_off, arena_off, foot_b_off}, cap_stray, adj_gimg, adj_gtex, adj_dot}, st);
+    launch_fwd_pk<2>(use_wide(info), r, p, tex, {img_fp16, img, (char *)cache, {foot_off, arena_off, foot_b_off}, cap_stray, adj_gimg, adj_gtex, adj_dot, !cache && plain_scene(r, sd, bvh, img_fp16)}, st);
     FFX_CHECK_LAUNCH("render_fwd");
     return FFX_OK;
   }

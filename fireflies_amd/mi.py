@@ -544,7 +544,8 @@ class Scene:
         # which path each mi.render of this scene took (bench.py prints it): "two_stream" = beside the previous render on the scene's
         # render streams, "caller_stream" = the plain forward on the caller's stream (a texture written in place since its assignment,
         # device material tables, base-colour textures, FFX_RENDER_STREAMS=1), "autograd" = through functional.render (tex.data requires grad)
-        self.render_paths = {"two_stream": 0, "caller_stream": 0, "autograd": 0}
+        # "k8_plain" = how many of them launched the packet kernel's plain-scene instance (ops.k8_instance_launches: the native launcher's choice)
+        self.render_paths = {"two_stream": 0, "caller_stream": 0, "autograd": 0, "k8_plain": 0}
         # which way each geometry push went: "native" = one ffx_scene_step_h call for the whole sample (step_native), "python" = params.update()
         self.update_paths = {"native": 0, "python": 0}
         self.update_fallbacks = {}  # why a sample of a compiled configuration took the Python path after all (reason -> count)
@@ -1294,22 +1295,27 @@ def render(scene: Scene, params: SceneParameters = None, spp: int = 16, seed: in
     # max_depth > 2: the path integrator, on the caller's stream (the live texture, the scene's material table)
     deep = integrator is not None and integrator.max_depth > 2
     md, rr = (integrator.max_depth, integrator.rr_depth) if deep else (2, 5)
-    if tex.requires_grad and torch.is_grad_enabled():
-        scene.render_paths["autograd"] += 1
-        img = Fn.render(tex, scene.geom, sd, scene.materials_arg(sd), spp, seed, fp16, md, rr)
-    else:  # nothing to differentiate: straight to the kernel (autograd.Function.apply costs ~80 us of host time per call)
-        mats = scene.materials_arg(sd)
-        slot = scene._render_stream(tex_in, mats) if tex_in is not None and not deep else None
-        if slot is not None:  # beside the previous render, on the scene's other render stream
-            rs, done, priv = slot
-            scene.render_paths["two_stream"] += 1
-            with torch.cuda.stream(rs):
-                img = scene.geom.render_fwd(sd, mats, Fn._tex3(priv), int(spp), int(seed), bool(fp16))
-                done.record(rs)
-            return _RenderedXf(img, done)
-        scene.render_paths["caller_stream"] += 1
-        img = scene.geom.render_fwd(sd, mats, Fn._tex3(tex), int(spp), int(seed), bool(fp16), max_depth=md, rr_depth=rr)
-    return TensorXf(img)
+    k8 = ops.k8_launch_counters()
+    k8_plain0 = k8[0]
+    try:
+        if tex.requires_grad and torch.is_grad_enabled():
+            scene.render_paths["autograd"] += 1
+            img = Fn.render(tex, scene.geom, sd, scene.materials_arg(sd), spp, seed, fp16, md, rr)
+        else:  # nothing to differentiate: straight to the kernel (autograd.Function.apply costs ~80 us of host time per call)
+            mats = scene.materials_arg(sd)
+            slot = scene._render_stream(tex_in, mats) if tex_in is not None and not deep else None
+            if slot is not None:  # beside the previous render, on the scene's other render stream
+                rs, done, priv = slot
+                scene.render_paths["two_stream"] += 1
+                with torch.cuda.stream(rs):
+                    img = scene.geom.render_fwd(sd, mats, Fn._tex3(priv), int(spp), int(seed), bool(fp16))
+                    done.record(rs)
+                return _RenderedXf(img, done)
+            scene.render_paths["caller_stream"] += 1
+            img = scene.geom.render_fwd(sd, mats, Fn._tex3(tex), int(spp), int(seed), bool(fp16), max_depth=md, rr_depth=rr)
+        return TensorXf(img)
+    finally:  # (the launcher counts its choice when it launches: two reads of a word of the library, no call into it)
+        scene.render_paths["k8_plain"] += k8[0] - k8_plain0
 
 
 def _render_aov(scene, params, spp, seed, fp16, integrator):

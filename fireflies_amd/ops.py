@@ -414,6 +414,28 @@ def render_cache_status(cache):
     return int(out[0]), int(out[1]), int(out[2])
 
 
+_K8_LAUNCHES = None
+
+
+def k8_launch_counters():
+    """The library's two launch counters of the packet render kernel k_render_fwd_pk, read in place: [0] launches of its plain-scene instance,
+    [1] of the generic one — which instance the native launcher picked (ffx_trace.hip plain_scene; FFX_K8_PLAIN=0 keeps the generic one).
+    Process-wide, never reset: callers take differences.  A build without the symbol (FFX_LIB) reads as zeros."""
+    global _K8_LAUNCHES
+    if _K8_LAUNCHES is None:
+        try:
+            _K8_LAUNCHES = (C.c_ulonglong * 2).in_dll(api().lib, "ffx_k8_instance_launches")
+        except ValueError:
+            _K8_LAUNCHES = (C.c_ulonglong * 2)()
+    return _K8_LAUNCHES
+
+
+def k8_instance_launches():
+    """-> (plain-scene, generic) launches so far"""
+    k = k8_launch_counters()
+    return int(k[0]), int(k[1])
+
+
 def _check_materials(sd, albedo):
     """-> the pointer argument for shape_albedo: None when the scene description carries the rows itself (sd.n_mat_h)"""
     if sd.n_mat_h > 0:

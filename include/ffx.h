@@ -37,6 +37,9 @@
  *       FFX_RENDER_BLOCKS=0      ffx_render_fwd / ffx_render_fwd_filtered below 33 samples per pixel: a pixel per wave whatever the count, as
  *                                at 64 (default: compact blocks of up to 8 pixels per wave, 16 at 1 spp, k_render_fwd_blk — the same image
  *                                bit for bit, 1.5 - 2.3x faster); the FFX_RENDER_AOV launches of such a call follow it
+ *       FFX_K8_PLAIN=0           ffx_render_fwd / ffx_render_fwd_adjoint at 33 .. 64 samples per pixel: the generic packet kernel for every scene
+ *                                (default: an instance without the per-sample feature tests for scenes the host proves plain — inline principled
+ *                                rows without optional lobes, no smooth shape, rigid spot, 1-channel texture, f32 box film; the same bits)
  *       FFX_BINS=0               the packet render kernels walk the tree for every packet (default: tile bins first, ffx_bvh_info.off_bins)
  *       FFX_BIN_TILE=4..32       side of a camera tile of the bins in pixels, a power of two (default 8)
  *       FFX_BIN_TILE_PROJ=4..64  side of a projector tile of the bins in texels, a power of two (default twice FFX_BIN_TILE)
