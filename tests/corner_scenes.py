@@ -1,0 +1,141 @@
+"""The scenes of the per-lane kernel tests (k_path_*, the appearance, material and prb adjoints, forward mode, the aov block), as tests/tie_scenes.py,
+tests/seam_scenes.py and tests/stage_scenes.py are for the walks: the box corner — a floor and two walls with a cube on the floor, lit by a projector
+and a spot — its smaller relatives, and the relay, whose camera sees a wall that only a bounce can light.  The geometry and the camera, projector and
+spot numbers stand here once.  numpy and fireflies_amd.scenes only: a test without a GPU may import this."""
+import numpy as np
+
+from fireflies_amd import scenes
+
+QUAD = np.array([[0, 1, 2], [0, 2, 3]], np.int32)
+R0 = scenes.MAT_COLUMN["roughness"]
+NAMES = ["roughness", "anisotropic", "metallic", "spec_trans", "eta", "spec_tint", "sheen", "sheen_tint", "flatness", "clearcoat", "clearcoat_gloss"]
+PRINCIPLED = {"roughness": 0.35, "metallic": 0.2, "specular": 0.6}
+EVERY_LOBE = {"roughness": 0.4, "anisotropic": 0.5, "metallic": 0.3, "spec_trans": 0.2, "specular": 0.6, "spec_tint": 0.6, "sheen": 0.8, "sheen_tint": 0.7,
+              "flatness": 0.4, "clearcoat": 0.7, "clearcoat_gloss": 0.3}
+# (floor's BSDF, wall y = 0's BSDF, whether the floor's base colour is base_texture())
+CASES = {
+    "defaults": ({}, {}, None),
+    "every_lobe": (EVERY_LOBE, {"roughness": 0.3, "metallic": 1.0, "clearcoat": 1.0, "clearcoat_gloss": 0.6, "spec_trans": 0.3, "sheen": 0.5}, None),
+    "textured": ({"roughness": 0.35, "metallic": 0.2, "specular": 0.6, "spec_tint": 0.5, "sheen": 0.6, "sheen_tint": 0.5}, {"roughness": 0.6}, "tex"),
+}
+FLOOR_RGB, WALL_X_RGB, WALL_Y_RGB, CUBE_RGB = (0.6, 0.55, 0.5), (0.7, 0.7, 0.75), (0.5, 0.6, 0.7), (0.8, 0.4, 0.3)
+
+
+def _quad(p):
+    return np.asarray(p, np.float32)[None]
+
+
+def _floor():
+    return _quad([[0, 0, 0], [2, 0, 0], [2, 2, 0], [0, 2, 0]])
+
+
+def _wall_x():
+    return _quad([[0, 0, 0], [0, 2, 0], [0, 2, 2], [0, 0, 2]])
+
+
+def _wall_y():
+    return _quad([[0, 0, 0], [2, 0, 0], [2, 0, 2], [0, 0, 2]])
+
+
+def _camera(W, H, eye=(3.2, 3.0, 2.4), target=(0.6, 0.6, 0.5)):
+    return scenes.SensorData("PerspectiveCamera", scenes.look_at(eye, target, up=(0, 0, 1)), 50.0, 0.01, 100.0, W, H)
+
+
+def _projector(tex):
+    return scenes.SensorData("PerspectiveCamera_1", scenes.look_at((2.6, 1.2, 2.8), (0.7, 0.9, 0.2), up=(0, 0, 1)), 50.0, 0.01, 100.0, tex, tex)
+
+
+def _spot():
+    return scenes.SpotData("emit-Spot", scenes.look_at((1.8, 2.6, 2.5), (0.5, 0.5, 0.0), up=(0, 0, 1)), (8.0, 8.0, 8.0), 30.0, 20.0)
+
+
+def base_texture():
+    """the [8, 8, 3] base-colour texture of every textured floor"""
+    return np.random.default_rng(5).uniform(0.2, 0.9, (8, 8, 3)).astype(np.float32)
+
+
+def corner(floor_bsdf=None, wall_y_bsdf=None, *, shared=False, materials=True, W=24, H=24, tex=32, base_tex=None):
+    """the box corner: floor, wall x = 0, wall y = 0 and a cube on the floor.  A BSDF of None is a Lambert row, a dict a principled one; wall x = 0 and
+    the cube are Lambert.  shared: wall x = 0 shares the floor's material (colour and BSDF); base_tex: the floor's base colour is this [h, w, 3]
+    texture; materials=False: no mesh names a material, so all four sit on mat-Default (mi.Scene builds its parameter map from the names)"""
+    cv, ct = scenes.make_cube((1.2, 1.1, 0.3), 0.3)
+    uv = np.array([[0, 0], [1, 0], [1, 1], [0, 1]], np.float32) if base_tex is not None else None
+
+    def mat(name):
+        return {"material": name} if materials else {}
+
+    meshes = [scenes.MeshData("mesh-Floor", _floor(), QUAD, FLOOR_RGB, bsdf=floor_bsdf, uv=uv, base_tex=base_tex, **mat("mat-Floor")),
+              scenes.MeshData("mesh-WallX", _wall_x(), QUAD, FLOOR_RGB if shared else WALL_X_RGB, bsdf=floor_bsdf if shared else None,
+                              **mat("mat-Floor" if shared else "mat-WallX")),
+              scenes.MeshData("mesh-WallY", _wall_y(), QUAD, WALL_Y_RGB, bsdf=wall_y_bsdf, **mat("mat-WallY")),
+              scenes.MeshData("mesh-Cube", cv[None], ct, CUBE_RGB, **mat("mat-Cube"))]
+    return scenes.SceneData(meshes, _camera(W, H), _projector(tex), _spot(), 1.0)
+
+
+def path_corner(principled, **kw):
+    """tests/test_path_gpu.py's corner: Lambert rows or a principled floor and wall y = 0, no material names"""
+    return corner(PRINCIPLED if principled else None, {"roughness": 0.6} if principled else None, materials=False, **kw)
+
+
+def appearance_corner(principled, tint=False, shared=False, base_tex=None, **kw):
+    """tests/test_appearance_gpu.py's corner.  tint: the floor's principled row carries spec_tint and sheen_tint"""
+    bs = dict(PRINCIPLED) if principled or base_tex is not None else None
+    if tint:
+        bs = dict(bs, spec_tint=0.6, sheen=0.8, sheen_tint=0.7)
+    return corner(bs, {"roughness": 0.6} if principled else None, shared=shared, base_tex=base_tex, **kw)
+
+
+def case(name, **kw):
+    """-> (the corner of CASES[name], its base texture or None)"""
+    fb, wb, textured = CASES[name]
+    bt = base_texture() if textured else None
+    return corner(fb, wb, base_tex=bt, **kw), bt
+
+
+def scene(name, **kw):
+    """"lambert": the corner with Lambert rows only (a table of stride 3); "bounce": the relay under both emitters; a key of CASES; or a (floor, wall)
+    pair of BSDF dictionaries"""
+    if name == "lambert":
+        return appearance_corner(False, **kw)
+    if name == "bounce":
+        return relay(True, True)
+    return case(name, **kw)[0] if isinstance(name, str) else corner(*name, **kw)
+
+
+def small_corner(W=6, H=6, tex=8):
+    """the corner with every lobe of the floor active, small enough for the float64 restatement on the host"""
+    return case("every_lobe", W=W, H=H, tex=tex)[0]
+
+
+def spot_corner():
+    """the principled floor and wall x = 0 under the spot alone, 6 x 6, no material names (tests/test_prb_cpu.py)"""
+    meshes = [scenes.MeshData("mesh-Floor", _floor(), QUAD, FLOOR_RGB, bsdf=dict(PRINCIPLED)), scenes.MeshData("mesh-Wall", _wall_x(), QUAD, WALL_X_RGB)]
+    return scenes.SceneData(meshes, _camera(6, 6), None, _spot())
+
+
+def relay(proj_on=True, spot_on=False, W=16, H=16, tex=32, projector_scale=2.0):
+    """the camera sees a Lambert wall (x = -1) only; the projector and the spot, straight above the floor (z = 0), light only the floor, which the
+    camera cannot see: nothing arrives without a bounce"""
+    wall = _quad([[-1, -1, 0], [-1, 1, 0], [-1, 1, 2], [-1, -1, 2]])
+    floor = _quad([[-1, -1, 0], [1, -1, 0], [1, 1, 0], [-1, 1, 0]])
+    above = scenes.look_at((0.0, 0.0, 1.5), (0.0, 0.0, 0.0), up=(0, 1, 0))
+    cam = scenes.SensorData("PerspectiveCamera", scenes.look_at((0.6, 0.0, 0.9), (-1.0, 0.0, 1.0), up=(0, 0, 1)), 20.0, 0.01, 100.0, W, H)
+    proj = scenes.SensorData("PerspectiveCamera_1", above, 40.0, 0.01, 100.0, tex, tex) if proj_on else None
+    spot = scenes.SpotData("emit-Spot", above, (10.0, 10.0, 10.0), 20.0, 15.0) if spot_on else None
+    return scenes.SceneData([scenes.MeshData("mesh-Wall", wall, QUAD, (0.8, 0.7, 0.6)), scenes.MeshData("mesh-Floor", floor, QUAD, (0.5, 0.5, 0.5))],
+                            cam, proj, spot, projector_scale)
+
+
+def aov_corner(W, H, lambert_only=False):
+    """a floor (textured base colour, flat) and a wall (Lambert row; smooth: its vertex normals are the plane's, bent at the shared seam by nothing — the
+    wall is its own mesh) with a smooth sphere above the floor so that the interpolated normal differs from the geometric one.  lambert_only: no BSDF,
+    no texture — mi.Scene then builds the stride-3 table.  The camera looks into the corner from above: no ray grazes the floor / wall seam.
+    -> (scene, base texture, uv)"""
+    sv, st = scenes.make_uv_sphere((1.1, 1.0, 0.45), 0.35, nu=8, nv=4)
+    base_tex = None if lambert_only else base_texture()
+    uv = None if lambert_only else np.array([[-0.5, 0.25], [2.5, 0.25], [2.5, 2.25], [-0.5, 2.25]], np.float32)  # (beyond [0, 1]: the lookup wraps, the channel not)
+    meshes = [scenes.MeshData("mesh-Floor", _floor(), QUAD, FLOOR_RGB, material="mat-Floor", bsdf=None if lambert_only else {"roughness": 0.4}, uv=uv,
+                              base_tex=base_tex),
+              scenes.MeshData("mesh-Wall", _wall_x(), QUAD, WALL_X_RGB, material="mat-Wall"),
+              scenes.MeshData("mesh-Ball", np.asarray(sv, np.float32)[None], np.asarray(st, np.int32), CUBE_RGB, material="mat-Ball", smooth=True)]
+    return scenes.SceneData(meshes, _camera(W, H, (3.1, 2.7, 2.6), (0.6, 0.8, 0.4)), _projector(32), _spot(), 1.0), base_tex, uv

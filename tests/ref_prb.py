@@ -8,8 +8,12 @@ test, which the image uses, and the one of the unperturbed rows `mats0`, which a
 Bounces are cosine-weighted, so no row moves a path: both throughputs belong to the same vertices."""
 import numpy as np
 
+from fireflies_amd import scenes
 from tests import ref_bruteforce as bf
 from tests import ref_path as rp
+from tests.support import copy_desc
+
+R0 = scenes.MAT_COLUMN["roughness"]
 
 
 def path_vertices_frozen(verts, tri_idx, tri_shape, sd, mats, mats0, spp, seed, max_depth, rr_depth=5):
@@ -68,3 +72,46 @@ def render_fwd_frozen(verts, tri_idx, tri_shape, sd, mats, mats0, tex, spp, seed
         num, den, _ = bf._film_splat(W, H, spp, seed, gaussian_stddev, values=L)
         return np.where(den[..., None] > 0, num / np.where(den > 0, den, 1.0)[..., None], 0.0)
     return L.reshape(H, W, spp, 3).mean(2)
+
+
+def interior_material_tangent(rows, rng):
+    """a random tangent of the BSDF columns of the principled rows that central differences can follow: zero where the parameter sits at a bound of
+    [0, 1] (the forward skips the lobe there; the one-sided values are the dot-product identity's business) and on the eta column at eta = 1"""
+    rows = np.asarray(rows, np.float64)
+    d = np.zeros_like(rows)
+    if rows.shape[1] <= 3:
+        return d
+    pr = rows[:, scenes.MAT_COLUMN["model"]] != 0
+    for j in range(11):
+        col = rows[:, R0 + j]
+        ok = pr & ((col > 0.05) & (col < 0.95) if R0 + j != scenes.MAT_COLUMN["eta"] else col > 1.05)
+        d[ok, R0 + j] = rng.uniform(0.5, 1.5, int(ok.sum()))
+    return d
+
+
+def float64_tangent(world, sd, rows, tex, spp, seed, depth, rr, stddev, drows=None, dtex=None, dspot=None, h=5e-4):
+    """d image / d theta . dtheta in float64 on the paths, survival decisions and q_v of `rows` (prb's detached roulette): the five-point central
+    difference of render_fwd_frozen along drows (base colours and BSDF columns, [n_shapes, stride]) plus — the image is linear in both —
+    the image of the texture dtex with a dark spot and of the spot intensity dspot (float32 values) with a dark texture"""
+    rows = np.asarray(rows, np.float64)
+    tex = None if tex is None else np.asarray(tex, np.float64)
+
+    def img(r, s, t):
+        return render_fwd_frozen(*world, s, r, rows, t, spp, seed, depth, rr, gaussian_stddev=stddev)
+
+    out = np.zeros((sd.cam.height, sd.cam.width, 3))
+    if drows is not None and np.abs(drows).max() > 0:
+        d = np.asarray(drows, np.float64)
+        out += (-img(rows + 2 * h * d, sd, tex) + 8 * img(rows + h * d, sd, tex) - 8 * img(rows - h * d, sd, tex) + img(rows - 2 * h * d, sd, tex)) / (12 * h)
+    dark = copy_desc(sd)
+    for c in range(3):
+        dark.spot.intensity[c] = 0.0
+    if dtex is not None and tex is not None:
+        out += img(rows, dark, np.asarray(dtex, np.float64))
+    if dspot is not None:
+        lit = copy_desc(sd)
+        for c in range(3):
+            lit.spot.intensity[c] = float(dspot[c])
+            assert float(lit.spot.intensity[c]) == float(dspot[c]), "dspot must hold float32 values"
+        out += img(rows, lit, None if tex is None else np.zeros_like(tex))
+    return out

@@ -10,12 +10,11 @@ import pytest
 import torch
 
 from fireflies_amd import _abi, _lib, ops, scenes
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from tests.support import ROOT, enum_value, header
 
 
 def _header_symbols():
-    txt = open(os.path.join(ROOT, "include", "ffx.h")).read()
+    txt = header()
     txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
     return sorted(set(re.findall(r"\b(ffx_[a-z0-9_]+)\s*\(", txt)))
 
@@ -38,7 +37,7 @@ def test_header_lists_exactly_the_environment_knobs_the_package_reads():
             else:
                 continue
             read.update(re.findall(pat, open(os.path.join(d, f)).read()))
-    block = open(os.path.join(ROOT, "include", "ffx.h")).read().split("*/", 1)[0]
+    block = header().split("*/", 1)[0]
     listed = re.findall(r"^ \* {7}(FFX_\w+)", block, flags=re.M)
     assert len(listed) == len(set(listed)), sorted(n for n in listed if listed.count(n) > 1)
     assert set(listed) == read, {"read, not listed": sorted(read - set(listed)), "listed, not read": sorted(set(listed) - read)}
@@ -86,8 +85,8 @@ def test_host_philox_known_answers(which, oracle):
         want = np.float32(np.float32(w) * np.float32(2.0**-32) + np.float32(2.0**-32))
         assert out[i] == (np.float32(0.0) if want == 1.0 else want), i
     assert all(0.0 <= out[i] < 1.0 for i in range(256))
-    assert fn(0, 0, 257, out, C.byref(inc)) == _abi_err("FFX_ERR_UNSUPPORTED") and fn(0, 2, 3, out, C.byref(inc)) == _abi_err("FFX_ERR_UNSUPPORTED")
-    assert fn(0, 0, 0, out, C.byref(inc)) == _abi_err("FFX_ERR_ARG")
+    assert fn(0, 0, 257, out, C.byref(inc)) == enum_value("FFX_ERR_UNSUPPORTED") and fn(0, 2, 3, out, C.byref(inc)) == enum_value("FFX_ERR_UNSUPPORTED")
+    assert fn(0, 0, 0, out, C.byref(inc)) == enum_value("FFX_ERR_ARG")
     # the batched entry point = the single one, draw by draw
     fb = lib.ffx_torch_rand_batch_h
     fb.argtypes = [C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_int32), C.POINTER(C.c_float)]
@@ -99,11 +98,7 @@ def test_host_philox_known_answers(which, oracle):
         assert fn(sd_, of_, n, out, C.byref(inc)) == 0
         assert [packed[p + i] for i in range(n)] == [out[i] for i in range(n)]
         p += n
-    assert fb(0, None, None, None, None) == 0 and fb(1, seeds, offs, (C.c_int32 * 1)(300), packed) == _abi_err("FFX_ERR_UNSUPPORTED")
-
-
-def _abi_err(name):
-    return {"FFX_ERR_ARG": -1, "FFX_ERR_LAUNCH": -2, "FFX_ERR_UNSUPPORTED": -3, "FFX_ERR_NOMEM": -4}[name]
+    assert fb(0, None, None, None, None) == 0 and fb(1, seeds, offs, (C.c_int32 * 1)(300), packed) == enum_value("FFX_ERR_UNSUPPORTED")
 
 
 def test_struct_sizes_match_header():
@@ -156,7 +151,7 @@ def test_adjoint_cache_size_follows_the_material_table():
     assert a.lib.ffx_render_cache_bytes_sd(C.byref(sd), 64) == up(plain) + 112 * 512 * 512
     assert a.lib.ffx_render_cache_bytes_sd(None, 64) == 0 and a.lib.ffx_render_cache_bytes(0, 4, 4) == 0
     # the material columns of the Python mirror are the header's
-    hdr = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "ffx.h")).read()
+    hdr = header()
     import re
 
     for name in ("MODEL", "ROUGHNESS", "ANISOTROPIC", "METALLIC", "SPEC_TRANS", "ETA", "SPEC_TINT", "SHEEN", "SHEEN_TINT", "FLATNESS", "CLEARCOAT",
@@ -362,7 +357,7 @@ _APP = _abi.RENDER_GRAD_APPEARANCE
 _GAUSS = {"rfilter": _abi.RFILTER_GAUSSIAN}
 _MISALIGNED = "misaligned"  # stands for a host address 4 bytes off a 16-byte boundary
 _BASE_TEX = {"mat_stride": _abi.MAT_STRIDE, "n_base_tex": 1, "base_tex_w": (4,), "base_tex_h": (4,), "base_tex": ("buf",), "slot_uv": "buf"}
-_ARG, _UNS = _abi_err("FFX_ERR_ARG"), _abi_err("FFX_ERR_UNSUPPORTED")
+_ARG, _UNS = enum_value("FFX_ERR_ARG"), enum_value("FFX_ERR_UNSUPPORTED")
 # (entry point, scene / bvh info changes, argument changes, return code, message substring)
 _REFUSALS = [
     # NULL buffers and counts

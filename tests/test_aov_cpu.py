@@ -1,7 +1,6 @@
 """The `aov` integrator without a GPU: mi.load_dict's parsing, names and refusals, the ABI constants against the header, the refusals
 of FFX_RENDER_AOV that come before any launch, and tests/ref_aov.py on a plane in closed form."""
 import ctypes as C
-import os
 import re
 
 import numpy as np
@@ -11,9 +10,8 @@ from fireflies_amd import _abi, _lib, mi, ops, scene_desc, scenes
 from fireflies_amd import functional as Fn
 from fireflies_amd.optim import PatternOptimizer
 from tests import ref_aov
+from tests.support import FFX_ERR_ARG, FFX_ERR_UNSUPPORTED, header
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-FFX_ERR_ARG, FFX_ERR_UNSUPPORTED = -1, -3  # (include/ffx.h)
 SERVED = ["albedo", "depth", "geo_normal", "position", "prim_index", "sh_normal", "shape_index", "uv"]
 
 
@@ -66,7 +64,7 @@ def test_everything_but_mi_render_refuses_an_aov_integrator():
 
 
 def test_abi_constants_agree_with_the_header():
-    text = open(os.path.join(ROOT, "include", "ffx.h")).read()
+    text = header()
     assert int(re.search(r"#define FFX_RENDER_AOV (0x[0-9a-fA-F]+)", text).group(1), 16) == _abi.RENDER_AOV == 0x100000
     assert int(re.search(r"#define FFX_RENDER_AOV_FLOATS (\d+)", text).group(1)) == _abi.RENDER_AOV_FLOATS == 17 == ref_aov.FLOATS
     assert int(re.search(r"#define FFX_ABI_VERSION (\d+)", text).group(1)) == 11

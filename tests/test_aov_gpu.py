@@ -7,36 +7,14 @@ import torch
 from fireflies_amd import mi, ops, scenes, workloads
 from tests import ref_aov
 from tests import ref_bruteforce as rb
+from tests.corner_scenes import aov_corner
+from tests.gpu_support import DEV
+from tests.support import outlier_rule, world_arrays
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda"
-QUAD = np.array([[0, 1, 2], [0, 2, 3]], np.int32)
 CH = ops.AOV_CHANNELS
 FILMS = [(37, 29), (64, 64)]
 SPPS = [1, 4, 32, 33, 100]
-
-
-def _quad(p):
-    return np.asarray(p, np.float32)[None]
-
-
-def corner(W, H, lambert_only=False):
-    """a floor (textured base colour, flat) and a wall (Lambert row; smooth: its vertex normals are the plane's, bent at the shared seam by nothing — the
-    wall is its own mesh) with a smooth sphere above the floor so that the interpolated normal differs from the geometric one.  lambert_only: no BSDF,
-    no texture — mi.Scene then builds the stride-3 table.  The camera looks into the corner from above: no ray grazes the floor / wall seam."""
-    floor = _quad([[0, 0, 0], [2, 0, 0], [2, 2, 0], [0, 2, 0]])
-    wall = _quad([[0, 0, 0], [0, 2, 0], [0, 2, 2], [0, 0, 2]])
-    sv, st = scenes.make_uv_sphere((1.1, 1.0, 0.45), 0.35, nu=8, nv=4)
-    base_tex = None if lambert_only else np.random.default_rng(5).uniform(0.2, 0.9, (8, 8, 3)).astype(np.float32)
-    uv = None if lambert_only else np.array([[-0.5, 0.25], [2.5, 0.25], [2.5, 2.25], [-0.5, 2.25]], np.float32)  # (beyond [0, 1]: the lookup wraps, the channel not)
-    meshes = [scenes.MeshData("mesh-Floor", floor, QUAD, (0.6, 0.55, 0.5), material="mat-Floor", bsdf=None if lambert_only else {"roughness": 0.4}, uv=uv,
-                              base_tex=base_tex),
-              scenes.MeshData("mesh-Wall", wall, QUAD, (0.7, 0.7, 0.75), material="mat-Wall"),
-              scenes.MeshData("mesh-Ball", np.asarray(sv, np.float32)[None], np.asarray(st, np.int32), (0.8, 0.4, 0.3), material="mat-Ball", smooth=True)]
-    cam = scenes.SensorData("PerspectiveCamera", scenes.look_at((3.1, 2.7, 2.6), (0.6, 0.8, 0.4), up=(0, 0, 1)), 50.0, 0.01, 100.0, W, H)
-    proj = scenes.SensorData("PerspectiveCamera_1", scenes.look_at((2.6, 1.2, 2.8), (0.7, 0.9, 0.2), up=(0, 0, 1)), 50.0, 0.01, 100.0, 32, 32)
-    spot = scenes.SpotData("emit-Spot", scenes.look_at((1.8, 2.6, 2.5), (0.5, 0.5, 0.0), up=(0, 0, 1)), (8.0, 8.0, 8.0), 30.0, 20.0)
-    return scenes.SceneData(meshes, cam, proj, spot, 1.0), base_tex, uv
 
 
 _CACHE = {}
@@ -46,16 +24,15 @@ def _case(film, lambert_only=False, gaussian=False):
     """one scene per (film, table): the loaded scene, its description, the world triangles and the float64 reference's inputs, shared by the tests"""
     key = (film, lambert_only, gaussian)
     if key not in _CACHE:
-        sc, base_tex, uv = corner(*film, lambert_only=lambert_only)
+        sc, base_tex, uv = aov_corner(*film, lambert_only=lambert_only)
         ms = mi.load_scene_data(sc, device=DEV, shadows=True)
         if gaussian:
             ms.rfilter = "gaussian"
         sd = ms.scene_desc(tex_channels=1)
-        pool, tris, shape, off, stride, nfr, alb = scenes.flatten(sc)
-        world = (pool.astype(np.float64), tris + off[shape][:, None], shape)
+        world = world_arrays(sc)[:3]
         vuv = None
         if uv is not None:
-            vuv = np.zeros((pool.shape[0], 2))
+            vuv = np.zeros((world[0].shape[0], 2))
             vuv[:4] = uv
         ref = dict(mats=ms._albedo_host.astype(np.float64), smooth=[m.smooth for m in sc.meshes], vert_uv=vuv,
                    base_tex=None if base_tex is None else [base_tex.astype(np.float64)])
@@ -83,19 +60,6 @@ def _ref_block(film, lambert_only, gaussian, spp, seed):
 
 def _aov(ms, sd, tex, spp, seed, **kw):
     return ms.geom.render_aov(sd, ms.materials_arg(sd), tex, spp, seed, **kw)
-
-
-def _outlier_rule(what, got, want, scale, spp):
-    """the project's rule: per pixel within 1e-4 of the scale; at most 2e-4 of the pixels (at least one) beyond, none by more than 1.5 scale / spp — one
-    sample on the other side of a triangle edge"""
-    err = np.abs(got - want)
-    err = err.reshape(err.shape[0] * err.shape[1], -1).max(1)
-    out = err > 1e-4 * scale
-    allowed = max(1, int(2e-4 * err.size))
-    print(f"{what}: scale {scale:.4g}, max err {err.max():.3e}, median {np.median(err):.3e}, outliers {int(out.sum())} / {err.size} (allowed {allowed}), "
-          f"cap {1.5 * scale / spp:.3e}")
-    assert out.sum() <= allowed, what
-    assert err.max() <= 1.5 * scale / spp, what
 
 
 @pytest.mark.parametrize("film", FILMS, ids=lambda f: f"{f[0]}x{f[1]}")
@@ -142,14 +106,14 @@ def test_every_channel_against_the_float64_restatement(film, spp, lambert_only, 
             assert scale == 0 and not got[..., first:first + n].any()  # (no slot_uv: zeros)
             continue
         assert scale > 0, name
-        _outlier_rule(f"{name} ({'gaussian' if gaussian else 'box'}, {spp} spp)", got[..., first:first + n], w, scale, spp)
+        outlier_rule(f"{name} ({'gaussian' if gaussian else 'box'}, {spp} spp)", got[..., first:first + n], w, scale, spp)
 
 
 @pytest.mark.parametrize("film", FILMS, ids=lambda f: f"{f[0]}x{f[1]}")
 def test_the_block_describes_the_samples_of_the_image(film):
     """spot only, Lambert rows, no shadows, 1 spp, box film: the image recomputed in float64 from position, sh_normal and albedo with DESIGN 4.3's spot
     formula (the normal faced to the viewer here) is render_fwd's image"""
-    sc, _, _ = corner(*film, lambert_only=True)
+    sc, _, _ = aov_corner(*film, lambert_only=True)
     sc = scenes.SceneData(sc.meshes, sc.camera, None, sc.spot, 1.0)
     ms = mi.load_scene_data(sc, device=DEV, shadows=False)
     sd = ms.scene_desc(tex_channels=1)
@@ -182,7 +146,7 @@ def test_the_block_describes_the_samples_of_the_image(film):
     want = np.where((ng * wi).sum(-1, keepdims=True) > 0, want, 0.0)
     scale = float(got.max())
     assert scale > 0
-    _outlier_rule("image from the block", got, want, scale, 1)
+    outlier_rule("image from the block", got, want, scale, 1)
 
 
 @pytest.mark.parametrize("gaussian", [False, True], ids=["box", "gaussian"])
@@ -242,7 +206,7 @@ def test_mi_render_end_to_end():
     mg._params["tex.data"] = texg[..., 0].clone()
     og = mi.render(mg, spp=4, seed=3, integrator=mi.load_dict({"type": "aov", "aovs": "p:position", "img": {"type": "direct"}})).torch()
     want = _ref_block((37, 29), False, True, 4, 3)[..., 1:4]
-    _outlier_rule("mi.render position (gaussian)", og[..., :3].double().cpu().numpy(), want, float(want.max() - want.min()), 4)
+    outlier_rule("mi.render position (gaussian)", og[..., :3].double().cpu().numpy(), want, float(want.max() - want.min()), 4)
     assert torch.equal(og[..., 3:], mi.render(mg, spp=4, seed=3).torch())
 
 

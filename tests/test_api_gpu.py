@@ -1138,7 +1138,7 @@ def test_laser_yaml_roundtrip(tmp_path):
 def test_load_file_xml_obj_renders_like_the_oracle(oracle, tmp_path):
     """data-format row: Mitsuba-XML subset + OBJ -> mi.load_file -> render."""
     from fireflies_amd import loaders
-    from tests.test_loaders_cpu import XML
+    from tests.support import SCENE_XML as XML
 
     wv, wt = scenes.make_plane(0.0, 1.0, 6, 6)
     wv[:, 0] += 0.0137
@@ -1203,7 +1203,7 @@ def test_the_dataset_loop_of_main_py_with_a_textured_mucosa(oracle, tmp_path):
 
     from fireflies_amd import loaders
     from fireflies_amd.sampling import AnimationSampler, NoiseTextureLerpSampler
-    from tests.test_loaders_cpu import XML
+    from tests.support import SCENE_XML as XML
 
     wv, wt = scenes.make_plane(0.0, 1.0, 8, 8)
     n = wv.shape[0]
@@ -1320,7 +1320,7 @@ def test_cfg5_colon_half_million_triangles_fp16(oracle):
     # domain offers: finite and deterministic; linear in the texture; the 256-spp image is the mean of four disjoint
     # 64-sample sub-renders only in expectation, so it is compared with an independent 256-spp render (other seed) on
     # the image mean; and the cached adjoint (344 MB of per-pixel footprints at this size) is the render's transpose
-    from tests.test_bruteforce_cpu import material_rows
+    from tests.support import material_rows
 
     mats = torch.from_numpy(material_rows(len(sc_big.meshes), 31)).to(DEV)
     sdm = scene_desc.scene_desc(sc_big, shadows=True, mat_stride=16)

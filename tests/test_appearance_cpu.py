@@ -1,41 +1,27 @@
 """The appearance adjoint's ABI (include/ffx.h FFX_RENDER_GRAD_APPEARANCE) without a GPU: the bit in the header and in _abi, its place
 among the flags, and the size of the appearance block from the header's macro against _abi.appearance_floats."""
 import os
-import re
-import shutil
 import subprocess
 
 import pytest
 
 from fireflies_amd import _abi
+from tests.support import ROOT, c_compiler, define, header
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "ffx.h")
-
-
-def _header():
-    with open(HEADER) as f:
-        return f.read()
-
-
-def _define(name):
-    m = re.search(r"^#define\s+" + name + r"\s+(\S+)", _header(), re.M)
-    assert m, name
-    return int(m.group(1), 0)
 
 
 def test_bit_in_header_and_abi_agree():
-    assert _define("FFX_RENDER_GRAD_APPEARANCE") == _abi.RENDER_GRAD_APPEARANCE == 0x10000
-    assert "FFX_RENDER_APPEARANCE_FLOATS(sd)" in _header()
+    assert define("FFX_RENDER_GRAD_APPEARANCE") == _abi.RENDER_GRAD_APPEARANCE == 0x10000
+    assert "FFX_RENDER_APPEARANCE_FLOATS(sd)" in header()
 
 
 def test_bit_is_clear_of_the_other_flags():
     a = _abi.RENDER_GRAD_APPEARANCE
     assert a & (a - 1) == 0
-    assert a & _abi.RENDER_PATH_MASK == 0 and a & _define("FFX_RENDER_PATH_MASK") == 0
+    assert a & _abi.RENDER_PATH_MASK == 0 and a & define("FFX_RENDER_PATH_MASK") == 0
     others = [_abi.RENDER_FP16, _abi.RENDER_SPARSE_ADJOINT, _abi.RENDER_APEX_READY, _abi.RENDER_CACHE_ZEROED, _abi.RENDER_CACHE_KEEP_DROPPED]
     for name in ("FFX_RENDER_FP16", "FFX_RENDER_SPARSE_ADJOINT", "FFX_RENDER_APEX_READY", "FFX_RENDER_CACHE_ZEROED", "FFX_RENDER_CACHE_KEEP_DROPPED"):
-        others.append(_define(name))
+        others.append(define(name))
     for f in others:
         assert a & f == 0, f
     # every depth the path integrator can carry stays clear of the bit
@@ -44,18 +30,11 @@ def test_bit_is_clear_of_the_other_flags():
             assert _abi.render_path(md, rr) & a == 0
 
 
-def _compiler():
-    for c in (os.environ.get("CC"), "cc", "gcc", "clang"):
-        if c and shutil.which(c):
-            return c
-    return None
-
-
 CASES = [(1, []), (4, [(8, 8)]), (7, [(16, 4), (3, 5)]), (2, [(1, 1), (2, 3), (4, 5)]), (12, [(64, 32), (7, 9), (1, 13), (128, 2)])]
 
 
 def test_block_size_macro_matches_the_helper(tmp_path):
-    cc = _compiler()
+    cc = c_compiler()
     assert cc is not None, "a C compiler is needed (the CPU oracle is built with one)"
     lines = ['#include "ffx.h"', "#include <stdio.h>", "#include <string.h>", "int main(void) {", "  ffx_scene_desc sd;"]
     for n_shapes, bt in CASES:

@@ -8,80 +8,23 @@ import numpy as np
 import pytest
 import torch
 
-from fireflies_amd import _abi, mi, scene_desc, scenes, workloads
+from fireflies_amd import _abi, mi, scene_desc, workloads
 from fireflies_amd._lib import api
+from tests import gpu_support as gpu
 from tests import ref_path as rp
+from tests.corner_scenes import appearance_corner, base_texture
+from tests.gpu_support import DEV
+from tests.support import copy_desc
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda"
-QUAD = np.array([[0, 1, 2], [0, 2, 3]], np.int32)
 
-
-def _quad(p):
-    return np.asarray(p, np.float32)[None]
-
-
-def corner_scene(principled, tint=False, shared=False, W=24, H=24, tex=32, base_tex=None):
-    """a box corner (floor and two walls) with a cube on the floor, lit by a projector and a spot (tests/test_path_gpu.py's scene).  tint: the
-    floor's principled row carries spec_tint and sheen_tint; shared: the floor and the wall x = 0 share one material; base_tex: the floor's base
-    colour is this [h, w, 3] texture"""
-    floor = _quad([[0, 0, 0], [2, 0, 0], [2, 2, 0], [0, 2, 0]])
-    wall_x = _quad([[0, 0, 0], [0, 2, 0], [0, 2, 2], [0, 0, 2]])
-    wall_y = _quad([[0, 0, 0], [2, 0, 0], [2, 0, 2], [0, 0, 2]])
-    cv, ct = scenes.make_cube((1.2, 1.1, 0.3), 0.3)
-    bs = {"roughness": 0.35, "metallic": 0.2, "specular": 0.6} if principled or base_tex is not None else None
-    if tint:
-        bs = dict(bs, spec_tint=0.6, sheen=0.8, sheen_tint=0.7)
-    uv = np.array([[0, 0], [1, 0], [1, 1], [0, 1]], np.float32) if base_tex is not None else None
-    meshes = [scenes.MeshData("mesh-Floor", floor, QUAD, (0.6, 0.55, 0.5), material="mat-Floor", bsdf=bs, uv=uv, base_tex=base_tex),
-              scenes.MeshData("mesh-WallX", wall_x, QUAD, (0.6, 0.55, 0.5) if shared else (0.7, 0.7, 0.75), material="mat-Floor" if shared else "mat-WallX",
-                              bsdf=bs if shared else None),
-              scenes.MeshData("mesh-WallY", wall_y, QUAD, (0.5, 0.6, 0.7), material="mat-WallY", bsdf={"roughness": 0.6} if principled else None),
-              scenes.MeshData("mesh-Cube", cv[None], ct, (0.8, 0.4, 0.3), material="mat-Cube")]
-    cam = scenes.SensorData("PerspectiveCamera", scenes.look_at((3.2, 3.0, 2.4), (0.6, 0.6, 0.5), up=(0, 0, 1)), 50.0, 0.01, 100.0, W, H)
-    proj = scenes.SensorData("PerspectiveCamera_1", scenes.look_at((2.6, 1.2, 2.8), (0.7, 0.9, 0.2), up=(0, 0, 1)), 50.0, 0.01, 100.0, tex, tex)
-    spot = scenes.SpotData("emit-Spot", scenes.look_at((1.8, 2.6, 2.5), (0.5, 0.5, 0.0), up=(0, 0, 1)), (8.0, 8.0, 8.0), 30.0, 20.0)
-    return scenes.SceneData(meshes, cam, proj, spot, 1.0)
-
-
-def _load(sc, gaussian, tc):
-    ms = mi.load_scene_data(sc, device=DEV, shadows=True)
-    if gaussian:
-        ms.rfilter = "gaussian"
-    sd = ms.scene_desc(tex_channels=tc)
-    pool, tris, shape, off, stride, nfr, alb = scenes.flatten(sc)
-    world = (pool.astype(np.float64), tris + off[shape][:, None], shape, ms.albedo.cpu().numpy().astype(np.float64))
-    return ms, sd, world
-
-
-def _tex(sd, seed=0):
-    g = torch.Generator().manual_seed(seed)
-    return torch.rand((sd.proj.tex_h, sd.proj.tex_w, sd.proj.tex_channels), generator=g).to(DEV)
-
-
-def _gimg(sd, seed=0):
-    g = torch.Generator().manual_seed(seed)
-    return (0.5 + torch.rand((sd.cam.height, sd.cam.width, 3), generator=g)).to(DEV)
-
-
-def _copy(sd):
-    out = _abi.SceneDesc()
-    C.memmove(C.addressof(out), C.addressof(sd), C.sizeof(out))
-    return out
-
-
-def _loss_gpu(ms, sd, rows, tex, spp, seed, gimg):
-    s2 = _copy(sd)
-    assert scene_desc.set_host_materials(s2, rows) is not False
-    img = ms.geom.render_fwd(s2, None, tex, spp, seed)
-    return float((img.double() * gimg.double()).sum())
 
 
 @pytest.mark.parametrize("principled,tint,gaussian", [(False, False, False), (True, False, True), (True, True, False), (True, True, True)])
 def test_row_gradients_match_central_differences(principled, tint, gaussian):
-    ms, sd, world = _load(corner_scene(principled, tint), gaussian, 1)
+    ms, sd, world = gpu.load(appearance_corner(principled, tint), gaussian, 1)
     assert sd.n_mat_h > 0
-    tex, gimg = _tex(sd, 1), _gimg(sd, 2)
+    tex, gimg = gpu.rand_tex(sd, 1), gpu.rand_gimg(sd, 2)
     spp, seed, h = 16, 7, 1e-2
     gtex, app = ms.geom.render_bwd(sd, None, spp, seed, gimg, appearance=True, tex=tex)
     g = app.rows.double().cpu().numpy()
@@ -94,7 +37,7 @@ def test_row_gradients_match_central_differences(principled, tint, gaussian):
             lo, hi = rows.copy(), rows.copy()
             lo[i, k] -= h
             hi[i, k] += h
-            fd_gpu[i, k] = (_loss_gpu(ms, sd, hi, tex, spp, seed, gimg) - _loss_gpu(ms, sd, lo, tex, spp, seed, gimg)) / (2 * h)
+            fd_gpu[i, k] = (gpu.loss(ms, sd, hi, tex, spp, seed, gimg) - gpu.loss(ms, sd, lo, tex, spp, seed, gimg)) / (2 * h)
             ref = [float((rp.render_fwd(*world[:3], sd, r.astype(np.float64), tex_np, spp, seed, 2, gaussian_stddev=stddev) * gimg_np).sum()) for r in (hi, lo)]
             fd_ref[i, k] = (ref[0] - ref[1]) / (2 * h)
     scale = np.abs(fd_gpu).max()
@@ -104,13 +47,13 @@ def test_row_gradients_match_central_differences(principled, tint, gaussian):
 
 
 def test_spot_intensity_gradient_is_the_finite_difference():
-    ms, sd, _ = _load(corner_scene(True, True), False, 1)
+    ms, sd, _ = gpu.load(appearance_corner(True, True), False, 1)
     assert sd.shadows & 1
-    tex, gimg = _tex(sd, 3), _gimg(sd, 4)
+    tex, gimg = gpu.rand_tex(sd, 3), gpu.rand_gimg(sd, 4)
     spp, seed, h = 16, 3, 0.5
     _, app = ms.geom.render_bwd(sd, None, spp, seed, gimg, appearance=True, tex=tex)
     for c in range(3):
-        lo, hi = _copy(sd), _copy(sd)
+        lo, hi = copy_desc(sd), copy_desc(sd)
         lo.spot.intensity[c] -= h
         hi.spot.intensity[c] += h
         ls = [float((ms.geom.render_fwd(s, None, tex, spp, seed).double() * gimg.double()).sum()) for s in (hi, lo)]
@@ -120,11 +63,10 @@ def test_spot_intensity_gradient_is_the_finite_difference():
 
 @pytest.mark.parametrize("gaussian", [False, True])
 def test_base_texture_directional_derivative(gaussian):
-    bt = np.random.default_rng(5).uniform(0.2, 0.9, (8, 8, 3)).astype(np.float32)
-    ms, sd, _ = _load(corner_scene(False, tint=True, base_tex=bt), gaussian, 1)
+    ms, sd, _ = gpu.load(appearance_corner(False, tint=True, base_tex=base_texture()), gaussian, 1)
     assert sd.n_base_tex == 1
     t = ms._base_tex[0][1]  # (the description points at this tensor)
-    tex, gimg = _tex(sd, 6), _gimg(sd, 7)
+    tex, gimg = gpu.rand_tex(sd, 6), gpu.rand_gimg(sd, 7)
     spp, seed, h = 16, 9, 1e-2
     _, app = ms.geom.render_bwd(sd, None, spp, seed, gimg, appearance=True, tex=tex)
     assert app.rows[0].abs().max() == 0  # (the floor's row: its base colour is the texture)
@@ -145,28 +87,24 @@ def test_base_texture_directional_derivative(gaussian):
 
 @pytest.mark.parametrize("gaussian,tc", [(False, 1), (True, 3)])
 def test_texture_gradient_with_the_bit_is_unchanged(gaussian, tc):
-    ms, sd, _ = _load(corner_scene(True, True), gaussian, tc)
-    tex, gimg = _tex(sd, 8), _gimg(sd, 9)
+    ms, sd, _ = gpu.load(appearance_corner(True, True), gaussian, tc)
+    tex, gimg = gpu.rand_tex(sd, 8), gpu.rand_gimg(sd, 9)
     ref = ms.geom.render_bwd(sd, None, 16, 2, gimg)
     gtex, _ = ms.geom.render_bwd(sd, None, 16, 2, gimg, appearance=True, tex=tex)
     assert float(ref.abs().max()) > 0
     assert torch.allclose(gtex, ref, rtol=1e-5, atol=1e-6 * float(ref.abs().max()))
 
 
-def _leaf(v):
-    return torch.tensor(v, dtype=torch.float32, device=DEV, requires_grad=True)
-
-
 def test_mi_render_leaves_end_to_end():
-    ms, sd, _ = _load(corner_scene(True, shared=True), False, 3)
+    ms, sd, _ = gpu.load(appearance_corner(True, shared=True), False, 3)
     p = mi.traverse(ms)
     spp, seed = 16, 4
-    tex = _tex(sd, 10)
-    gimg = _gimg(sd, 11)
+    tex = gpu.rand_tex(sd, 10)
+    gimg = gpu.rand_gimg(sd, 11)
     base, inten = p["mat-Floor.brdf_0.base_color.value"].t.clone(), p["emit-Spot.intensity.value"].t.clone()
     sd = ms.scene_desc(tex_channels=3)
     gtex_ref, app = ms.geom.render_bwd(sd, None, spp, seed, gimg, appearance=True, tex=tex)
-    b_leaf, i_leaf, t_leaf = _leaf(base.tolist()), _leaf(inten.tolist()), tex.clone().requires_grad_(True)
+    b_leaf, i_leaf, t_leaf = gpu.leaf(base.tolist()), gpu.leaf(inten.tolist()), tex.clone().requires_grad_(True)
     p["mat-Floor.brdf_0.base_color.value"] = b_leaf
     p["emit-Spot.intensity.value"] = i_leaf
     p["tex.data"] = t_leaf
@@ -189,36 +127,20 @@ def test_mi_render_leaves_end_to_end():
     assert not plain.requires_grad and torch.equal(plain, img.detach())
 
 
-def _fit(ms, key, start, target_img, spp, seed, lr):
-    p = mi.traverse(ms)
-    leaf = _leaf(start)
-    opt = torch.optim.Adam([leaf], lr=lr)
-    sched = torch.optim.lr_scheduler.ExponentialLR(opt, 0.98)
-    for _ in range(300):
-        p[key] = leaf
-        p.update()
-        loss = ((mi.render(ms, spp=spp, seed=seed).torch() - target_img) ** 2).mean()
-        opt.zero_grad()
-        loss.backward()
-        opt.step()
-        sched.step()
-    return leaf.detach()
-
-
 def test_inverse_rendering_recovers_base_colour_and_intensity():
-    ms, sd, _ = _load(corner_scene(False), False, 1)
+    ms, sd, _ = gpu.load(appearance_corner(False), False, 1)
     p = mi.traverse(ms)
-    p["tex.data"] = _tex(sd, 12)[..., 0].contiguous()
+    p["tex.data"] = gpu.rand_tex(sd, 12)[..., 0].contiguous()
     p.update()
     spp, seed = 16, 5
     target = mi.render(ms, spp=spp, seed=seed).torch().clone()
     key_b, key_i = "mat-Cube.brdf_0.base_color.value", "emit-Spot.intensity.value"
     b_true, i_true = p[key_b].t.clone(), p[key_i].t.clone()
-    b = _fit(ms, key_b, (b_true + torch.tensor([0.15, -0.2, 0.1])).tolist(), target, spp, seed, 0.03)
+    b = gpu.fit(ms, key_b, (b_true + torch.tensor([0.15, -0.2, 0.1])).tolist(), target, spp, seed, 0.03, 300)
     assert float((b.cpu() - b_true.cpu()).abs().max()) < 1e-2, (b, b_true)
     p[key_b] = mi.Color3f(b_true)
     p.update()
-    i = _fit(ms, key_i, (i_true * 0.6).tolist(), target, spp, seed, 0.2)
+    i = gpu.fit(ms, key_i, (i_true * 0.6).tolist(), target, spp, seed, 0.2, 300)
     assert float(((i.cpu() - i_true.cpu()) / i_true.cpu()).abs().max()) < 1e-2, (i, i_true)
 
 
@@ -242,7 +164,7 @@ def test_full_size_vocalfold_base_colour_gradient():
     for sign in (1, -1):
         r = rows.copy()
         r[i, k] += sign * h
-        s2 = _copy(sd)
+        s2 = copy_desc(sd)
         if sd.n_mat_h > 0:
             scene_desc.set_host_materials(s2, r)
             m2 = None
@@ -254,12 +176,12 @@ def test_full_size_vocalfold_base_colour_gradient():
 
 
 def test_refusals():
-    ms, sd, _ = _load(corner_scene(False), False, 1)
+    ms, sd, _ = gpu.load(appearance_corner(False), False, 1)
     p = mi.traverse(ms)
-    tex, gimg = _tex(sd), _gimg(sd)
+    tex, gimg = gpu.rand_tex(sd), gpu.rand_gimg(sd)
     g = ms.geom
     p["tex.data"] = tex[..., 0].contiguous()
-    p["mat-Cube.brdf_0.base_color.value"] = _leaf([0.8, 0.4, 0.3])
+    p["mat-Cube.brdf_0.base_color.value"] = gpu.leaf([0.8, 0.4, 0.3])
     p.update()
     with pytest.raises(ValueError):
         mi.render(ms, spp=4, integrator=mi.load_dict({"type": "path", "max_depth": 3}))

@@ -9,6 +9,7 @@ import pytest
 
 from fireflies_amd import _abi, scene_desc, scenes
 from tests import ref_bruteforce as bf
+from tests.support import material_rows
 
 
 def _world(sc, frame=0, xforms=None):
@@ -89,29 +90,6 @@ def test_oracle_agrees_with_an_independent_bruteforce_restatement(oracle, which)
         lhs = float(((img_b - base) * gimg).sum())
         rhs = float((tex.astype(np.float64) * gt_b).sum())
         assert abs(lhs - rhs) <= 1e-9 * max(abs(lhs), abs(rhs), 1e-12)
-
-
-def material_rows(S, seed, model=1.0, **fixed):
-    """random principled material rows [S,16] over the ranges the reference randomises (main.py:97-107)"""
-    rng = np.random.default_rng(seed)
-    m = np.zeros((S, _abi.MAT_STRIDE), np.float32)
-    m[:, 0:3] = rng.uniform(0.1, 0.9, (S, 3))
-    m[:, _abi.MAT_MODEL] = model
-    m[:, _abi.MAT_ROUGHNESS] = rng.uniform(0.05, 1.0, S)
-    m[:, _abi.MAT_ANISOTROPIC] = rng.uniform(0.0, 1.0, S)
-    m[:, _abi.MAT_METALLIC] = rng.uniform(0.0, 0.5, S)
-    m[:, _abi.MAT_SPEC_TRANS] = rng.uniform(0.0, 0.4, S)
-    specular = rng.uniform(0.05, 1.0, S)
-    m[:, _abi.MAT_ETA] = 2.0 / (1.0 - np.sqrt(0.08 * specular)) - 1.0
-    m[:, _abi.MAT_SPEC_TINT] = rng.uniform(0.0, 1.0, S)
-    m[:, _abi.MAT_SHEEN] = rng.uniform(0.0, 0.5, S)
-    m[:, _abi.MAT_SHEEN_TINT] = rng.uniform(0.0, 1.0, S)
-    m[:, _abi.MAT_FLATNESS] = rng.uniform(0.0, 1.0, S)
-    m[:, _abi.MAT_CLEARCOAT] = rng.uniform(0.0, 1.0, S)
-    m[:, _abi.MAT_CLEARCOAT_GLOSS] = rng.uniform(0.0, 1.0, S)
-    for k, v in fixed.items():
-        m[:, getattr(_abi, "MAT_" + k.upper())] = v
-    return m
 
 
 def _oracle_material_eval(oracle, row, n, wv, wl):

@@ -11,18 +11,12 @@ import torch
 
 from fireflies_amd import ops, scenes, scene_desc
 from tests.conftest import assert_image_close, load_golden
+from tests.gpu_support import bin_headers, dev, envelope, host, pair, splat_tex
+from tests.support import material_rows
 
 pytestmark = pytest.mark.gpu
 
 FLIP_Y = np.diag([1.0, -1.0, 1.0, 1.0]).astype(np.float32)
-
-
-def dev(a, dtype=torch.float32):
-    return torch.as_tensor(np.ascontiguousarray(a)).to(device="cuda", dtype=dtype).contiguous()
-
-
-def host(t):
-    return t.detach().cpu().numpy()
 
 
 @pytest.fixture(scope="module", autouse=True)
@@ -195,8 +189,8 @@ def test_renders_below_64_spp_pack_several_pixels_into_a_wave(oracle, monkeypatc
         monkeypatch.delenv(k, raising=False)
     for principled in (False, True):
         sc = scenes.vocalfold(width=45, height=37, tex=64, frames=3, n_fold=20, tube=(20, 24), principled=principled)
-        go, gd, alb = _pair(oracle, sc, frame=1, xforms=_rand_xforms(2, 8))
-        tex = _tex(sc, 1)
+        go, gd, alb = pair(oracle, sc, frame=1, xforms=_rand_xforms(2, 8))
+        tex = splat_tex(sc, 1)
         for shadows in (True, False):
             sd = scene_desc.scene_desc(sc, tex_channels=1, shadows=shadows)
             for spp in ((1, 2, 3, 4, 7, 8, 16, 24, 32) if shadows else (1, 5, 32)):
@@ -224,14 +218,13 @@ def test_filtered_renders_below_33_spp_pack_several_pixels_into_a_wave(oracle, m
     rf_fold_blk; against the oracle, and bit for bit the image of the pixel-per-wave kernel (FFX_RENDER_BLOCKS=0: the same fma chains), on a film whose
     sides are no multiple of a block, Lambert and material rows, 1- and 3-channel textures, fp16."""
     from fireflies_amd import _abi
-    from tests.test_bruteforce_cpu import material_rows
 
     monkeypatch.delenv("FFX_RENDER_BLOCKS", raising=False)
     sc = scenes.vocalfold(width=53, height=42, tex=96, frames=3, n_fold=24, tube=(24, 32))
-    go, gd, alb = _pair(oracle, sc, frame=1, xforms=_rand_xforms(2, 2))
+    go, gd, alb = pair(oracle, sc, frame=1, xforms=_rand_xforms(2, 2))
     for ch, rows, stddev in ((1, alb, 0.5), (3, alb, 0.5), (1, material_rows(len(sc.meshes), 5), 0.5), (1, alb, 0.3)):
         sd = scene_desc.scene_desc(sc, tex_channels=ch, shadows=True, mat_stride=_abi.MAT_STRIDE if rows.shape[1] == _abi.MAT_STRIDE else 0, rfilter=("gaussian", stddev))
-        tex = _tex(sc, ch)
+        tex = splat_tex(sc, ch)
         for spp in (1, 3, 8, 10, 12, 16, 27, 32):
             got = gd.render_fwd(sd, dev(rows), tex, spp, seed=11)
             monkeypatch.setenv("FFX_RENDER_BLOCKS", "0")
@@ -316,19 +309,6 @@ _assert_image_close = assert_image_close  # (tests/conftest.py)
 
 
 # ------------------------------------------------------------------ K5..K7
-def _pair(oracle, sc, frame=0, xforms=None):
-    pool, tris, shape, off, stride, nfr, alb = scenes.flatten(sc)
-    S = len(sc.meshes)
-    if xforms is None:
-        xforms = np.tile(np.eye(4, dtype=np.float32), (S, 1, 1))
-    offs = (off + np.minimum(frame, nfr - 1) * stride).astype(np.int32)
-    go = oracle.Geometry(pool, tris, shape, off)
-    go.update(xforms, offs)
-    gd = ops.DeviceGeometry(pool, tris, shape, off)
-    gd.update(xforms, offs)
-    return go, gd, alb
-
-
 def _rand_xforms(S, seed):
     rng = np.random.default_rng(seed)
     out = []
@@ -363,7 +343,7 @@ def test_k7_trace_primary(oracle, cfg):
         sc = scenes.vocalfold(width=128, height=128, frames=4)
         W, H, spp = 128, 128, 2
     xf = _rand_xforms(len(sc.meshes), 1)
-    go, gd, _ = _pair(oracle, sc, frame=2, xforms=xf)
+    go, gd, _ = pair(oracle, sc, frame=2, xforms=xf)
     cam = scene_desc.camera_from_sensor(sc.camera)
     for jitter in (0, 1):
         td, sd_, pd = gd.trace_primary(cam, spp, jitter, seed=7)
@@ -382,7 +362,7 @@ def test_k7_packet_layouts(oracle, spp, monkeypatch):
     a sample count that does not divide 64, more than one pass) and the per-lane kernel give the
     oracle's hits at an image size that is not a multiple of the pixel block."""
     sc = scenes.vocalfold(width=52, height=37, tex=64, frames=3, n_fold=16, tube=(24, 24))
-    go, gd, _ = _pair(oracle, sc, frame=1, xforms=_rand_xforms(len(sc.meshes), 4))
+    go, gd, _ = pair(oracle, sc, frame=1, xforms=_rand_xforms(len(sc.meshes), 4))
     cam = scene_desc.camera_from_sensor(sc.camera)
     to, so, po = go.trace_primary(cam, spp, 1, seed=3)
     for mode, bins in (("packet", "1"), ("packet", "0"), ("lane", "1")):  # (FFX_BINS=0: the packet tree walks that the tile bins fall back to)
@@ -395,7 +375,7 @@ def test_k7_packet_layouts(oracle, spp, monkeypatch):
 
 def test_k7_trace_rays_laser(oracle):
     sc = scenes.vocalfold(width=64, height=64, frames=2, n_fold=32, tube=(32, 32))
-    go, gd, _ = _pair(oracle, sc, frame=1)
+    go, gd, _ = pair(oracle, sc, frame=1)
     rng = np.random.default_rng(5)
     n = 1000
     d = rng.standard_normal((n, 3)).astype(np.float32)
@@ -598,23 +578,13 @@ def test_clamp_to_fov_matches_oracle(oracle):
 
 
 # ------------------------------------------------------------------ K8 / K9
-def _tex(sc, ch=1, seed=0):
-    rng = np.random.default_rng(seed)
-    n = 64
-    pts = (rng.random((n, 2)) * 0.8 + 0.1).astype(np.float32)
-    t = ops.blur_fwd(ops.splat_fwd(dev(pts), 10.0, "sum", -1, sc.projector.width, sc.projector.height))
-    if ch == 3:
-        t = torch.stack([0.2 * t, t, 0.1 * t], -1).contiguous()
-    return t
-
-
 @pytest.mark.parametrize("shadows", [False, True])
 @pytest.mark.parametrize("ch", [1, 3])
 def test_k8_render_forward(oracle, shadows, ch):
     sc = scenes.vocalfold(width=72, height=64, tex=96, frames=3, n_fold=24, tube=(24, 32))
-    go, gd, alb = _pair(oracle, sc, frame=1, xforms=_rand_xforms(2, 2))
+    go, gd, alb = pair(oracle, sc, frame=1, xforms=_rand_xforms(2, 2))
     sd = scene_desc.scene_desc(sc, tex_channels=ch, shadows=shadows)
-    tex = _tex(sc, ch)
+    tex = splat_tex(sc, ch)
     img_d = host(gd.render_fwd(sd, dev(alb), tex, 8, seed=11))
     img_o = go.render_fwd(sd, alb, host(tex), 8, seed=11)
     assert img_o.max() > 0.05
@@ -626,7 +596,7 @@ def test_k8_render_forward(oracle, shadows, ch):
 
 def test_k8_hello_world_plumbing(oracle):
     sc = scenes.hello_world(64, 64)
-    go, gd, alb = _pair(oracle, sc)
+    go, gd, alb = pair(oracle, sc)
     sd = scene_desc.scene_desc(sc, shadows=True)
     img_d = host(gd.render_fwd(sd, dev(alb), None, 16, seed=0))
     img_o = go.render_fwd(sd, alb, np.zeros((1, 1), np.float32), 16, seed=0)
@@ -637,7 +607,7 @@ def test_k8_hello_world_plumbing(oracle):
 @pytest.mark.parametrize("ch", [1, 3])
 def test_k9_render_backward(oracle, ch):
     sc = scenes.vocalfold(width=72, height=64, tex=96, frames=3, n_fold=24, tube=(24, 32))
-    go, gd, alb = _pair(oracle, sc, frame=2, xforms=_rand_xforms(2, 4))
+    go, gd, alb = pair(oracle, sc, frame=2, xforms=_rand_xforms(2, 4))
     sd = scene_desc.scene_desc(sc, tex_channels=ch, shadows=True)
     rng = np.random.default_rng(1)
     gimg = rng.standard_normal((64, 72, 3)).astype(np.float32)
@@ -659,7 +629,7 @@ def test_k8k9_full_size_properties():
     gd.update(_rand_xforms(2, 6), off + np.array([0, 17 * stride[1]], np.int32))
     sd = scene_desc.scene_desc(sc, shadows=True)
     albd = dev(alb)
-    tex = _tex(sc)
+    tex = splat_tex(sc)
     img = gd.render_fwd(sd, albd, tex, 64, seed=3)
     assert torch.isfinite(img).all() and float(img.max()) > 0.05
     # deterministic: no atomics in the forward pass
@@ -691,7 +661,7 @@ def test_full_size_parity_with_the_oracle_at_512x512x64(oracle):
     go = oracle.Geometry(pool, tris, shape, off)
     cam = scene_desc.camera_from_sensor(sc.camera)
     sd = scene_desc.scene_desc(sc, tex_channels=1, shadows=True)
-    tex = _tex(sc)
+    tex = splat_tex(sc)
     rng = np.random.default_rng(77)
     total = flips = lost = 0
     for i in range(3):
@@ -844,8 +814,8 @@ def test_k8k9_every_kernel_variant_matches_the_oracle(oracle, env, monkeypatch):
     for k, v in env.items():
         monkeypatch.setenv(k, v)
     sc = scenes.vocalfold(width=45, height=37, tex=64, frames=3, n_fold=20, tube=(20, 24))
-    go, gd, alb = _pair(oracle, sc, frame=1, xforms=_rand_xforms(2, 8))
-    tex = _tex(sc, 1)
+    go, gd, alb = pair(oracle, sc, frame=1, xforms=_rand_xforms(2, 8))
+    tex = splat_tex(sc, 1)
     rng = np.random.default_rng(2)
     gimg = rng.standard_normal((37, 45, 3)).astype(np.float32)
     for shadows, spp in ((True, 5), (False, 70)):
@@ -861,17 +831,6 @@ def test_k8k9_every_kernel_variant_matches_the_oracle(oracle, env, monkeypatch):
         assert gs > 0 and (gerr > 1e-3 * gs).mean() <= 1e-3 and gerr.max() <= 0.1 * gs, env
 
 
-def _bin_headers(gd):
-    """{ok, total, cap} of the three tile-bin grids (camera, projector, spot) of the blob the next render reads (ffx_common.h BinHdr)"""
-    torch.cuda.synchronize()
-    blob, info = gd.blob, gd.info
-    out = []
-    for a in range(3):
-        o = int(info.off_bins) + a * int(info.bins_stride)
-        out.append(tuple(int(v) for v in blob[o: o + 12].cpu().numpy().view(np.uint32)))
-    return out
-
-
 def test_tile_bins_that_overflow_or_cannot_be_built_fall_back_to_the_tree_walks(oracle, monkeypatch):
     """The paths behind the tile bins (round-4 review, weak 2a): (i) a grid whose entry lists do not fit its capacity (FFX_BIN_CAP, the
     test knob: in production a camera inside a coarse mesh) is marked not-ok by the pre-pass and ITS packets walk the tree while the other
@@ -880,21 +839,19 @@ def test_tile_bins_that_overflow_or_cannot_be_built_fall_back_to_the_tree_walks(
     image of the default path (the exact test alone decides hits)."""
     for k in ("FFX_BINS", "FFX_BIN_CAP", "FFX_TRAVERSAL", "FFX_WIDE"):
         monkeypatch.delenv(k, raising=False)
-    from tests.test_bruteforce_cpu import material_rows
-
     sc = scenes.vocalfold(width=96, height=80, tex=96, frames=3, n_fold=24, tube=(24, 32))
     xf = _rand_xforms(2, 7)
-    go, gd, alb = _pair(oracle, sc, frame=1, xforms=xf)
+    go, gd, alb = pair(oracle, sc, frame=1, xforms=xf)
     offs = gd._vert_off_host.copy()
     mats = material_rows(2, 17)
     sd = scene_desc.scene_desc(sc, tex_channels=1, shadows=True, mat_stride=16)
     cam = scene_desc.camera_from_sensor(sc.camera)
-    tex = _tex(sc, 1)
+    tex = splat_tex(sc, 1)
     spp = 16
     rng = np.random.default_rng(4)
     gimg = rng.standard_normal((80, 96, 3)).astype(np.float32)
     img_ref = gd.render_fwd(sd, dev(mats), tex, spp, seed=5)
-    hdrs = _bin_headers(gd)
+    hdrs = bin_headers(gd)
     assert all(h[0] == 1 and 0 < h[1] <= h[2] for h in hdrs), hdrs  # all three grids built, lists within the capacity
     img_o = go.render_fwd(sd, mats, host(tex), spp, seed=5)
     g_o = go.render_bwd(sd, mats, spp, 5, gimg)
@@ -906,7 +863,7 @@ def test_tile_bins_that_overflow_or_cannot_be_built_fall_back_to_the_tree_walks(
         monkeypatch.setenv("FFX_BIN_CAP", str(cap))
         gd.update(xf, offs)  # (a fresh pose: nothing of the previous capacity's pre-pass is claimed)
         img = gd.render_fwd(sd, dev(mats), tex, spp, seed=5)
-        h2 = _bin_headers(gd)
+        h2 = bin_headers(gd)
         assert [h[0] for h in h2] == [int(h[1] <= cap) for h in hdrs] and [h[1] for h in h2] == [h[1] for h in hdrs], (cap, h2, hdrs)
         assert torch.equal(img, img_ref), f"cap {cap}: the image depends on which grids served it"
         _assert_image_close(host(img), img_o, spp, frac=2e-4, rel=1e-4, what=f"FFX_BIN_CAP={cap}")
@@ -926,7 +883,7 @@ def test_tile_bins_that_overflow_or_cannot_be_built_fall_back_to_the_tree_walks(
     sdw.spot.cutoff_deg, sdw.spot.beam_width_deg = 80.0, 60.0
     gd.update(xf, offs)
     img_w = host(gd.render_fwd(sdw, dev(mats), tex, spp, seed=5))
-    hw = _bin_headers(gd)
+    hw = bin_headers(gd)
     assert hw[0][0] == 1 and hw[1][0] == 1
     scale_w, _ = _assert_image_close(img_w, go.render_fwd(sdw, mats, host(tex), spp, seed=5), spp, frac=2e-4, rel=1e-4, what="spot cutoff 80 degrees")
     assert scale_w > 0.02 and np.abs(img_w - host(img_ref)).max() > 0.01 * scale_w  # (the wider cone lights more of the scene)
@@ -937,19 +894,6 @@ def test_tile_bins_that_overflow_or_cannot_be_built_fall_back_to_the_tree_walks(
     g_wo = go.render_bwd(sdw, mats, spp, 5, gimg)
     gw = float(np.abs(g_wo).max())
     assert gw > 0 and (np.abs(g_w - g_wo) > 1e-3 * gw).mean() <= 1e-3
-
-
-def _envelope(gd, a, n_cells_x, n_cells_y):
-    """(header flag, [ny, nx, 4] cells) of emitter a's envelope in the blob the next render reads (ffx_common.h FFX_ENV_SUB, ffx_bin_off_env)"""
-    torch.cuda.synchronize()
-    info, blob = gd.info, gd.blob
-    F, NT = int(info.n_tris), 16384
-    off_entries = ((64 + 4 * (NT + 16) + 4 * NT + 63) // 64) * 64
-    off_env = ((off_entries + 64 * (2 * F + NT + 64) + 63) // 64) * 64
-    base = int(info.off_bins) + a * int(info.bins_stride)
-    hdr = blob[base: base + 64].cpu().numpy().view(np.uint32)
-    cells = blob[base + off_env: base + off_env + 16 * n_cells_x * n_cells_y].cpu().numpy().view(np.float32).reshape(n_cells_y, n_cells_x, 4)
-    return int(hdr[4]), cells, int(hdr[0])
 
 
 @pytest.mark.parametrize("which", ["vocalfold", "vocalfold_rows", "hello", "colon"])
@@ -963,8 +907,6 @@ def test_envelopes_settle_shadow_packets_and_leave_the_image_as_it_is(oracle, wh
     forward, forward + adjoint in one launch; the re-traced gradient agrees to the order of the atomics; the oracle's image is met."""
     for k in ("FFX_ENVELOPE", "FFX_BINS"):
         monkeypatch.delenv(k, raising=False)
-    from tests.test_bruteforce_cpu import material_rows
-
     if which == "hello":
         sc, spp = scenes.hello_world(96, 80), 16
     elif which == "colon":
@@ -974,18 +916,18 @@ def test_envelopes_settle_shadow_packets_and_leave_the_image_as_it_is(oracle, wh
     S = len(sc.meshes)
     xf = _rand_xforms(S, 12) if which != "hello" else None
     xfi = xf if xf is not None else np.tile(np.eye(4, dtype=np.float32), (S, 1, 1))
-    go, gd, alb = _pair(oracle, sc, frame=1, xforms=xf)
+    go, gd, alb = pair(oracle, sc, frame=1, xforms=xf)
     rows = which == "vocalfold_rows"
     mats = material_rows(S, 4) if rows else alb
     has_proj = sc.projector is not None
     sd = scene_desc.scene_desc(sc, tex_channels=1, shadows=True, mat_stride=16 if rows else 0)
     assert sd.shadows == 1
-    tex = _tex(sc, 1) if has_proj else None
+    tex = splat_tex(sc, 1) if has_proj else None
     pose = gd._vert_off_host.copy()
     gd.update(xfi, pose)
     img_on = gd.render_fwd(sd, dev(mats), tex, spp, seed=9)
     n_spot = min(128, max(8, int(2.0 * sd.spot.cutoff_deg + 0.999)))
-    flag, cells, lists_ok = _envelope(gd, 2, 7 * n_spot, 7 * n_spot)
+    flag, cells, lists_ok = envelope(gd, 2, 7 * n_spot, 7 * n_spot)
     # (the small colon's 15 k large triangles overflow the 120 x 120-tile grid of its 60-degree spot: its packets walk the tree, nobody builds or reads an envelope)
     assert flag == lists_ok and lists_ok == (0 if which == "colon" else 1)
     if lists_ok:
@@ -993,7 +935,7 @@ def test_envelopes_settle_shadow_packets_and_leave_the_image_as_it_is(oracle, wh
         planes = finite & (np.abs(cells[..., :3]).sum(-1) > 0)
         assert planes.mean() > 0.02 and (cells[..., 3] == 0).all(), planes.mean()  # cells that hold a plane (the rest: nothing listed, or no proof offered)
     if has_proj:
-        assert _envelope(gd, 1, 7 * ((sd.proj.tex_w + 15) // 16), 7 * ((sd.proj.tex_h + 15) // 16))[0] == 1
+        assert envelope(gd, 1, 7 * ((sd.proj.tex_w + 15) // 16), 7 * ((sd.proj.tex_h + 15) // 16))[0] == 1
     gimg = torch.ones_like(img_on) / img_on.numel()
     g_on = gd.render_bwd(sd, dev(mats), spp, 9, gimg) if has_proj else None
     fused_on = gd.render_fwd_adjoint(sd, dev(mats), tex, spp, 9, gimg) if has_proj else None
@@ -1001,7 +943,7 @@ def test_envelopes_settle_shadow_packets_and_leave_the_image_as_it_is(oracle, wh
     monkeypatch.setenv("FFX_ENVELOPE", "0")
     gd.update(xfi, pose)
     img_off = gd.render_fwd(sd, dev(mats), tex, spp, seed=9)
-    assert _envelope(gd, 2, 8, 8)[0] == 0
+    assert envelope(gd, 2, 8, 8)[0] == 0
     assert torch.equal(img_on, img_off), f"{which}: {int((img_on != img_off).sum())} pixel channels differ, worst {float((img_on - img_off).abs().max()):.3g}"
     if has_proj:
         g_off = gd.render_bwd(sd, dev(mats), spp, 9, gimg)
@@ -1015,10 +957,10 @@ def test_envelopes_settle_shadow_packets_and_leave_the_image_as_it_is(oracle, wh
     assert sdp.shadows == 3
     gd.update(xfi, pose)
     img_plain = gd.render_fwd(sdp, dev(mats), tex, spp, seed=9)
-    assert _envelope(gd, 2, 8, 8)[0] == 0 and torch.equal(img_plain, img_on)
+    assert envelope(gd, 2, 8, 8)[0] == 0 and torch.equal(img_plain, img_on)
     # ... and a render that wants them on a pose prepared without: the call prepares its own (the key of what the blob holds differs)
     img_again = gd.render_fwd(sd, dev(mats), tex, spp, seed=9)
-    assert _envelope(gd, 2, 8, 8)[0] == lists_ok and torch.equal(img_again, img_on)
+    assert envelope(gd, 2, 8, 8)[0] == lists_ok and torch.equal(img_again, img_on)
     if has_proj and not rows:  # the cache-writing forward (keeps every projector walk: its stage is where the projector's envelope counts)
         cache = torch.zeros(ops.render_cache_bytes(sd.cam.width, sd.cam.height, spp), dtype=torch.uint8, device="cuda")
         assert torch.equal(gd.render_fwd(sd, dev(mats), tex, spp, seed=9, cache=cache), img_on)
@@ -1037,9 +979,9 @@ def test_k9_cached_adjoint_matches_retrace_and_oracle(oracle, ch, k9_block, monk
     monkeypatch.setenv("FFX_K9_BLOCK", k9_block)  # (1-channel textures: 16x16-pixel blocks by default, the round-2 8x8 kernel for A/B)
     sc = scenes.vocalfold(width=52, height=44, tex=80, frames=3, n_fold=20, tube=(20, 24))
     xf = _rand_xforms(2, 5)
-    go, gd, alb = _pair(oracle, sc, frame=2, xforms=xf)
+    go, gd, alb = pair(oracle, sc, frame=2, xforms=xf)
     sd = scene_desc.scene_desc(sc, tex_channels=ch, shadows=True)
-    tex = _tex(sc, ch)
+    tex = splat_tex(sc, ch)
     rng = np.random.default_rng(0)
     gimg = rng.standard_normal((44, 52, 3)).astype(np.float32)
     for spp in (9, 70):  # one pass; two passes of the same pixel (64 + 6 samples)
@@ -1121,13 +1063,11 @@ def test_forward_and_adjoint_in_one_launch(oracle, ch, rows):
     the pixel's footprint times gimg goes straight into gtex, stray samples at once, <gimg, img> into 4096 partial sums.  Same image as
     the plain forward (bitwise), same gradient as the cached and the re-tracing adjoints and as the oracle's composition; accumulates
     into the caller's gtex; one and two passes per pixel; the sparse flag agrees where the texture is not zero."""
-    from tests.test_bruteforce_cpu import material_rows
-
     sc = scenes.vocalfold(width=52, height=44, tex=80, frames=3, n_fold=20, tube=(20, 24))
-    go, gd, alb = _pair(oracle, sc, frame=2, xforms=_rand_xforms(2, 5))
+    go, gd, alb = pair(oracle, sc, frame=2, xforms=_rand_xforms(2, 5))
     mats = alb if rows == "albedo" else material_rows(2, 31)
     sd = scene_desc.scene_desc(sc, tex_channels=ch, shadows=True, mat_stride=0 if rows == "albedo" else 16)
-    tex = _tex(sc, ch)
+    tex = splat_tex(sc, ch)
     rng = np.random.default_rng(1)
     gimg = rng.standard_normal((44, 52, 3)).astype(np.float32)
     for spp in (9, 70):
@@ -1178,10 +1118,10 @@ def test_apex_records_written_ahead_and_cache_header_cleared_by_the_caller(oracl
     records that a re-fit, a trace or a render from other positions has replaced."""
     sc = scenes.vocalfold(width=52, height=44, tex=80, frames=3, n_fold=20, tube=(20, 24))
     xf = _rand_xforms(2, 5)
-    go, gd, alb = _pair(oracle, sc, frame=2, xforms=xf)
+    go, gd, alb = pair(oracle, sc, frame=2, xforms=xf)
     offs = gd._vert_off_host.copy()
     sd = scene_desc.scene_desc(sc, tex_channels=1, shadows=True)
-    tex = _tex(sc, 1)
+    tex = splat_tex(sc, 1)
     i_cur = lambda: gd._cur if gd._async else 0  # noqa: E731
     assert gd._apex[i_cur()] is None  # a re-fit without apex_sd leaves nothing to claim
     ref = gd.render_fwd(sd, dev(alb), tex, 9, seed=3)  # (prepares for itself)
@@ -1251,7 +1191,7 @@ def test_adjoint_cache_overflow_is_refused_up_front_or_loud(oracle, monkeypatch)
 
     sc = scenes.vocalfold(width=40, height=32, tex=1024, frames=3, n_fold=20, tube=(20, 24))
     xf = _rand_xforms(2, 5)
-    go, gd, alb = _pair(oracle, sc, frame=1, xforms=xf)
+    go, gd, alb = pair(oracle, sc, frame=1, xforms=xf)
     sd = scene_desc.scene_desc(sc, tex_channels=1, shadows=True)
     spp = 64
     tex = torch.rand(1024, 1024, device="cuda") + 0.1
@@ -1638,12 +1578,12 @@ def test_wide_overlay_builders_give_identical_images(oracle, monkeypatch):
     ffx_bvh_build_host) must render bit-identical images and identical primitive ids — and the same as the oracle."""
     sc = scenes.vocalfold(width=72, height=64, tex=96, frames=3, n_fold=24, tube=(24, 32))
     sd = scene_desc.scene_desc(sc, shadows=True)
-    tex = _tex(sc)
+    tex = splat_tex(sc)
     cam = scene_desc.camera_from_sensor(sc.camera)
     imgs, prims, shapes_seen = [], [], []
     for mode in ("area", "count", "layers"):
         monkeypatch.setenv("FFX_WIDE_BUILD", mode)
-        go, gd, alb = _pair(oracle, sc, frame=1, xforms=_rand_xforms(2, 2))
+        go, gd, alb = pair(oracle, sc, frame=1, xforms=_rand_xforms(2, 2))
         shapes_seen.append((gd.info.n_wide, gd.info.wide_depth))
         imgs.append(gd.render_fwd(sd, dev(alb), tex, 8, seed=11))
         prims.append(gd.trace_primary(cam, 4, 1, 5)[2])
@@ -1660,7 +1600,7 @@ def test_sparse_adjoint_agrees_where_the_texture_is_not_zero(oracle):
     the full one (and with the oracle's) at every texel whose value is not zero — the only texels a pattern optimiser's
     chain reads, since a zero texel has no splat within reach of the blur that produced it."""
     sc = scenes.vocalfold(width=72, height=64, tex=128, frames=3, n_fold=24, tube=(24, 32))
-    go, gd, alb = _pair(oracle, sc, frame=1, xforms=_rand_xforms(2, 8))
+    go, gd, alb = pair(oracle, sc, frame=1, xforms=_rand_xforms(2, 8))
     sd = scene_desc.scene_desc(sc, tex_channels=1, shadows=True)
     rng = np.random.default_rng(5)
     pts = (rng.random((12, 2)) * 0.8 + 0.1).astype(np.float32)  # a dozen dots on 128^2: most texels are exactly zero
@@ -1688,18 +1628,16 @@ def test_principled_materials_match_the_oracle(oracle, env, ch, monkeypatch):
     """material rows (include/ffx.h FFX_MAT_*: Mitsuba's `principled` BSDF, reflection side) through every render entry
     point: forward, re-tracing adjoint, cache-writing forward + cached adjoint (second footprint), fp16 film; one shape
     stays Lambert.  The oracle's BSDF itself is pinned by tests/test_bruteforce_cpu.py."""
-    from tests.test_bruteforce_cpu import material_rows
-
     for k in ("FFX_TRAVERSAL", "FFX_WIDE", "FFX_BINS"):
         monkeypatch.delenv(k, raising=False)
     for k, v in env.items():
         monkeypatch.setenv(k, v)
     sc = scenes.vocalfold(width=52, height=44, tex=80, frames=3, n_fold=20, tube=(20, 24))
     xf = _rand_xforms(2, 5)
-    go, gd, alb = _pair(oracle, sc, frame=2, xforms=xf)
+    go, gd, alb = pair(oracle, sc, frame=2, xforms=xf)
     rng = np.random.default_rng(0)
     gimg = rng.standard_normal((44, 52, 3)).astype(np.float32)
-    tex = _tex(sc, ch)
+    tex = splat_tex(sc, ch)
     for trial, fixed in enumerate(({}, {"anisotropic": 0.0, "clearcoat": 0.0, "sheen": 0.0, "flatness": 0.0, "metallic": 0.0, "spec_trans": 0.0, "spec_tint": 0.0})):
         mats = material_rows(2, 11 + trial, **fixed)
         if trial == 0:
@@ -1745,8 +1683,6 @@ def test_interpolated_shading_normals_match_the_oracle(oracle, env, monkeypatch)
     shades in the interpolated frame): the update's vertex normals, the per-slot copies, and the render / both adjoints with
     a smooth and a flat shape in one scene, Lambert and principled rows, every walk and both refit paths, over several poses
     and animation frames — against the oracle, whose float64 cross-check is tests/test_bruteforce_cpu.py."""
-    from tests.test_bruteforce_cpu import material_rows
-
     for k in ("FFX_TRAVERSAL", "FFX_WIDE", "FFX_REFIT"):
         monkeypatch.delenv(k, raising=False)
     for k, v in env.items():
@@ -1755,7 +1691,7 @@ def test_interpolated_shading_normals_match_the_oracle(oracle, env, monkeypatch)
     pool, tris, shape, off, stride, nfr, alb = scenes.flatten(sc)
     rng = np.random.default_rng(3)
     gimg = rng.standard_normal((48, 56, 3)).astype(np.float32)
-    tex = _tex(sc, 1)
+    tex = splat_tex(sc, 1)
     mats = material_rows(2, 17, anisotropic=0.0)
     for smooth in ([True, True], [False, True]):
         gd = ops.DeviceGeometry(pool, tris, shape, off, smooth=smooth)
@@ -1814,8 +1750,6 @@ def test_textured_base_colour_matches_the_oracle(oracle, env, monkeypatch):
     select a texture (FFX_MAT_BASE_TEX), texture coordinates per leaf slot interpolated at the hit, repeat wrap, bilinear —
     a principled and a Lambert row on two textures of odd sizes, coordinates outside [0,1], together with interpolated
     normals, forward and re-tracing adjoint, packet and lane kernels; the footprint cache refuses such a scene."""
-    from tests.test_bruteforce_cpu import material_rows
-
     for k in ("FFX_TRAVERSAL", "FFX_WIDE"):
         monkeypatch.delenv(k, raising=False)
     for k, v in env.items():
@@ -1839,7 +1773,7 @@ def test_textured_base_colour_matches_the_oracle(oracle, env, monkeypatch):
         btex_d = [dev(b) for b in btex]
         mats = material_rows(2, 23, anisotropic=0.0)
         mats[0, 15], mats[1, 15], mats[1, 3] = 1.0, 2.0, 0.0  # a principled row on texture 0, a Lambert row on texture 1
-        tex = _tex(sc, 1)
+        tex = splat_tex(sc, 1)
         gimg = rng.standard_normal((48, 56, 3)).astype(np.float32)
         kw = dict(tex_channels=1, shadows=True, mat_stride=16)
         sd_d = scene_desc.scene_desc(sc, base_tex=[(b.data_ptr(), b.shape[1], b.shape[0]) for b in btex_d], slot_uv=suv_d.data_ptr(), **kw)
@@ -1877,15 +1811,13 @@ def test_material_table_inside_the_scene_description(oracle, env, monkeypatch):
     material pointer, a randomisation enqueues no upload.  Same bits as the device table for [S,3] albedos and [S,16] rows,
     forward, cache-writing forward, cached and re-tracing adjoint; the oracle honours the field too; a table that does not fit
     or does not match n_shapes x stride is refused."""
-    from tests.test_bruteforce_cpu import material_rows
-
     for k in ("FFX_TRAVERSAL",):
         monkeypatch.delenv(k, raising=False)
     for k, v in env.items():
         monkeypatch.setenv(k, v)
     sc = scenes.vocalfold(width=52, height=44, tex=80, frames=3, n_fold=20, tube=(20, 24))
-    go, gd, alb = _pair(oracle, sc, frame=1, xforms=_rand_xforms(2, 9))
-    tex = _tex(sc, 1)
+    go, gd, alb = pair(oracle, sc, frame=1, xforms=_rand_xforms(2, 9))
+    tex = splat_tex(sc, 1)
     gimg = dev(np.random.default_rng(5).standard_normal((44, 52, 3)).astype(np.float32))
     for rows, stride in ((alb, 0), (material_rows(2, 31), 16)):
         sd_dev = scene_desc.scene_desc(sc, tex_channels=1, shadows=True, mat_stride=stride)
@@ -1921,11 +1853,9 @@ def test_principled_materials_mid_size_and_abi_errors(oracle):
     """material rows at 256x256x64 spp on the full-detail vocal fold (one pixel per wave, the production launch shape) against
     the oracle, with the reference's vocal-fold randomisation (specular 0 .. 0.75, roughness 0.5); and the C ABI's refusals:
     an unknown material stride, material rows that are not 16-byte aligned."""
-    from tests.test_bruteforce_cpu import material_rows
-
     sc = scenes.vocalfold(width=256, height=256, tex=500, frames=4)
-    go, gd, alb = _pair(oracle, sc, frame=1, xforms=_rand_xforms(2, 3))
-    tex = _tex(sc, 1)
+    go, gd, alb = pair(oracle, sc, frame=1, xforms=_rand_xforms(2, 3))
+    tex = splat_tex(sc, 1)
     mats = material_rows(2, 5, anisotropic=0.0, clearcoat=0.0, sheen=0.0, flatness=0.0, metallic=0.0, spec_trans=0.0, spec_tint=0.0, roughness=0.5)
     mats[:, 8] = [2.0 / (1.0 - np.sqrt(0.08 * s_)) - 1.0 for s_ in (0.0, 0.75)]  # specular 0 (eta 1: no lobe) and 0.75
     sd = scene_desc.scene_desc(sc, tex_channels=1, shadows=True, mat_stride=16)
@@ -1951,8 +1881,6 @@ def test_principled_materials_mid_size_and_abi_errors(oracle):
 def test_material_rows_forward_and_adjoint_are_transposes(ch):
     """independent of the oracle: with material rows the render is still linear in the texture, and both adjoints (cached,
     re-tracing) are its transpose — <render(tex + d) - render(tex), g> = <d, adjoint(g)> for random d, g (float64 sums)."""
-    from tests.test_bruteforce_cpu import material_rows
-
     sc = scenes.vocalfold(width=64, height=48, tex=72, frames=3, n_fold=20, tube=(20, 24))
     S = len(sc.meshes)
     pool, tris, shape, off, stride, nfr, alb = scenes.flatten(sc)
@@ -2020,14 +1948,13 @@ def test_filtered_film_adjoint_cache_is_an_arena_at_config_5_size(oracle):
     of 64-sample blocks: 1.34 GB there (a quarter of the passes: configs[4]'s own 1 024-point pattern lights 17 % of the film).  The colon at 96 x 96 against the ORACLE's filtered adjoint, and at full size — 1024 x 1024 x 256, a dot
     pattern, FFX_RENDER_SPARSE_ADJOINT — against the library's own re-traced filtered adjoint; nothing dropped, a plausible share of the arena used."""
     from fireflies_amd import _abi
-    from tests.test_bruteforce_cpu import material_rows
 
     sc = scenes.colon(width=96, height=96, tex=128, n_around=48, n_along=160)
-    go, gd, alb = _pair(oracle, sc, frame=0, xforms=_rand_xforms(1, 3))
+    go, gd, alb = pair(oracle, sc, frame=0, xforms=_rand_xforms(1, 3))
     mats = material_rows(1, 6)
     spp = 70
     sd = scene_desc.scene_desc(sc, tex_channels=1, shadows=True, mat_stride=_abi.MAT_STRIDE, rfilter="gaussian")
-    tex = _tex(sc, 1)
+    tex = splat_tex(sc, 1)
     rng = np.random.default_rng(4)
     gimg = rng.standard_normal((96, 96, 3)).astype(np.float32)
     cache = torch.empty(ops.render_cache_bytes_sd(sd, spp), dtype=torch.uint8, device="cuda")
@@ -2090,14 +2017,12 @@ def test_gaussian_reconstruction_filter_forward_and_adjoint_match_the_oracle(ora
     from fireflies_amd import _abi
 
     sc = scenes.vocalfold(width=72, height=64, tex=96, frames=3, n_fold=24, tube=(24, 32))
-    go, gd, alb = _pair(oracle, sc, frame=1, xforms=_rand_xforms(2, 2))
+    go, gd, alb = pair(oracle, sc, frame=1, xforms=_rand_xforms(2, 2))
     if rows == "material_rows":
-        from tests.test_bruteforce_cpu import material_rows
-
         alb = material_rows(len(sc.meshes), 5)
     sd = scene_desc.scene_desc(sc, tex_channels=ch, shadows=True, mat_stride=_abi.MAT_STRIDE if rows == "material_rows" else 0, rfilter=("gaussian", stddev))
     assert sd.rfilter == _abi.RFILTER_GAUSSIAN
-    tex = _tex(sc, ch)
+    tex = splat_tex(sc, ch)
     img_d = host(gd.render_fwd(sd, dev(alb), tex, spp, seed=11))
     img_o = go.render_fwd(sd, alb, host(tex), spp, seed=11)
     assert img_o.max() > 0.05
@@ -2270,14 +2195,12 @@ def test_deterministic_adjoint_is_bitwise_reproducible_and_cross_checks_the_atom
     for the gaussian film.  At a small size it meets the oracle's (serial, double precision) sums to float rounding."""
     for k in ("FFX_XCD_REMAP", "FFX_TILE_BLOCK", "FFX_DETERMINISTIC"):
         monkeypatch.delenv(k, raising=False)
-    from tests.test_bruteforce_cpu import material_rows
-
     sc = scenes.vocalfold()
     pool, tris, shape, off, stride, nfr, alb = scenes.flatten(sc)
     gd = ops.DeviceGeometry(pool, tris, shape, off)
     gd.update(_rand_xforms(2, 6), off + np.array([0, 9 * stride[1]], np.int32))
     mats = material_rows(2, 3, anisotropic=0.0)
-    tex = _tex(sc)
+    tex = splat_tex(sc)
     rng = np.random.default_rng(8)
     gimg = dev(np.where(rng.random((512, 512, 3)) < 0.5, -1.0, 1.0).astype(np.float32) / (512 * 512 * 3))
     for rf in ("box", "gaussian"):
@@ -2302,7 +2225,7 @@ def test_deterministic_adjoint_is_bitwise_reproducible_and_cross_checks_the_atom
             assert float((err > 1e-3 * gs).float().mean()) <= 1e-3 and float(err.max()) <= 0.05 * gs, (rf, what, float(err.max()) / gs)
     # small: against the oracle, 1- and 3-channel textures, a Lambert table
     sc2 = scenes.vocalfold(width=52, height=44, tex=80, frames=3, n_fold=20, tube=(20, 24))
-    go, gd2, alb2 = _pair(oracle, sc2, frame=2, xforms=_rand_xforms(2, 5))
+    go, gd2, alb2 = pair(oracle, sc2, frame=2, xforms=_rand_xforms(2, 5))
     g2 = rng.standard_normal((44, 52, 3)).astype(np.float32)
     for ch in (1, 3):
         sd2 = scene_desc.scene_desc(sc2, tex_channels=ch, shadows=True)

@@ -3,7 +3,6 @@ dummy pointers, as tests/test_abi_cpu.py's), the packing of the tangent blocks b
 stand-in for the scene: they are decided before the geometry is touched) and the float64 tangent that tests/test_jvp_gpu.py compares to — central
 differences of tests/ref_prb.render_fwd_frozen along the tangent, with the linear parts (texture, spot intensity) taken exactly."""
 import ctypes as C
-import os
 import re
 import types
 
@@ -13,23 +12,18 @@ import torch
 
 from fireflies_amd import _abi, _lib, mi, ops, scene_desc, scenes
 from tests import ref_prb
+from tests.corner_scenes import small_corner
+from tests.support import FFX_ERR_ARG, FFX_ERR_UNSUPPORTED, copy_desc, define, header, world_arrays
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-FFX_ERR_ARG, FFX_ERR_UNSUPPORTED = -1, -3  # (include/ffx.h)
 TAN = 0x80000
 GAUSS = {"rfilter": _abi.RFILTER_GAUSSIAN}
 R0 = scenes.MAT_COLUMN["roughness"]
 
 
-def _header():
-    with open(os.path.join(ROOT, "include", "ffx.h")) as f:
-        return f.read()
-
-
 def test_bit_in_header_and_abi_agree_and_the_abi_is_frozen():
-    h = _header()
-    assert int(re.search(r"^#define\s+FFX_RENDER_TANGENT\s+(\S+)", h, re.M).group(1), 0) == _abi.RENDER_TANGENT == TAN
-    assert int(re.search(r"^#define\s+FFX_ABI_VERSION\s+(\S+)", h, re.M).group(1), 0) == _abi.FFX_ABI_VERSION == 11
+    h = header()
+    assert define("FFX_RENDER_TANGENT") == _abi.RENDER_TANGENT == TAN
+    assert define("FFX_ABI_VERSION") == _abi.FFX_ABI_VERSION == 11
     for name, val in re.findall(r"^#define\s+(FFX_RENDER_[A-Z_0-9]+)\s+(0x[0-9a-fA-F]+|\d+)\s", h, re.M):
         if name in ("FFX_RENDER_TANGENT", "FFX_RENDER_MAX_DEPTH_SHIFT", "FFX_RENDER_RR_DEPTH_SHIFT", "FFX_RENDER_MAX_DEPTH_LIMIT", "FFX_RENDER_MATERIAL_COLS"):
             continue
@@ -237,90 +231,32 @@ def test_render_forward_refuses_unknown_keys_and_path_with_appearance_tangents()
             mi.render_forward(sc, None, tan, integrator=it)
 
 
-# ---------------------------------------------------------------------------------------------- the float64 tangent
-def _copy(sd):
-    out = _abi.SceneDesc()
-    C.memmove(C.addressof(out), C.addressof(sd), C.sizeof(out))
-    return out
-
-
-def interior_material_tangent(rows, rng):
-    """a random tangent of the BSDF columns of the principled rows that central differences can follow: zero where the parameter sits at a bound of
-    [0, 1] (the forward skips the lobe there; the one-sided values are the dot-product identity's business) and on the eta column at eta = 1"""
-    rows = np.asarray(rows, np.float64)
-    d = np.zeros_like(rows)
-    if rows.shape[1] <= 3:
-        return d
-    pr = rows[:, scenes.MAT_COLUMN["model"]] != 0
-    for j in range(11):
-        col = rows[:, R0 + j]
-        ok = pr & ((col > 0.05) & (col < 0.95) if R0 + j != scenes.MAT_COLUMN["eta"] else col > 1.05)
-        d[ok, R0 + j] = rng.uniform(0.5, 1.5, int(ok.sum()))
-    return d
-
-
-def float64_tangent(world, sd, rows, tex, spp, seed, depth, rr, stddev, drows=None, dtex=None, dspot=None, h=5e-4):
-    """d image / d theta . dtheta in float64 on the paths, survival decisions and q_v of `rows` (prb's detached roulette): the five-point central
-    difference of ref_prb.render_fwd_frozen along drows (base colours and BSDF columns, [n_shapes, stride]) plus — the image is linear in both —
-    the image of the texture dtex with a dark spot and of the spot intensity dspot (float32 values) with a dark texture"""
-    rows = np.asarray(rows, np.float64)
-    tex = None if tex is None else np.asarray(tex, np.float64)
-
-    def img(r, s, t):
-        return ref_prb.render_fwd_frozen(*world, s, r, rows, t, spp, seed, depth, rr, gaussian_stddev=stddev)
-
-    out = np.zeros((sd.cam.height, sd.cam.width, 3))
-    if drows is not None and np.abs(drows).max() > 0:
-        d = np.asarray(drows, np.float64)
-        out += (-img(rows + 2 * h * d, sd, tex) + 8 * img(rows + h * d, sd, tex) - 8 * img(rows - h * d, sd, tex) + img(rows - 2 * h * d, sd, tex)) / (12 * h)
-    dark = _copy(sd)
-    for c in range(3):
-        dark.spot.intensity[c] = 0.0
-    if dtex is not None and tex is not None:
-        out += img(rows, dark, np.asarray(dtex, np.float64))
-    if dspot is not None:
-        lit = _copy(sd)
-        for c in range(3):
-            lit.spot.intensity[c] = float(dspot[c])
-            assert float(lit.spot.intensity[c]) == float(dspot[c]), "dspot must hold float32 values"
-        out += img(rows, lit, None if tex is None else np.zeros_like(tex))
-    return out
-
-
-def small_corner(W=6, H=6, tex=8):
-    """tests/test_material_grad_gpu.py's corner with every lobe of the floor active, small enough for the float64 restatement on the host"""
-    from tests import test_material_grad_gpu as tm
-
-    fb, wb, _ = tm.CASES["every_lobe"]
-    return tm.corner_scene(fb, wb, W=W, H=H, tex=tex)
-
-
+# ---------------------------------------------------------------------------------------------- the float64 tangent (tests/ref_prb.py)
 @pytest.mark.parametrize("depth,rr,stddev", [(2, 5, None), (3, 1, None), (3, 1, 0.5)])
 def test_float64_tangent_is_converged_in_h(depth, rr, stddev):
     """halving h changes the reference by less than 1e-6 of its scale (the stencil's h^4 term and the differences' rounding are both below it), and the
     exact linear parts are what differences of the texture and the intensity give"""
     sc = small_corner()
-    pool, tris, shape, off, stride, nfr, alb = scenes.flatten(sc)
-    world = (pool.astype(np.float64), tris + off[shape][:, None], shape)
+    world = world_arrays(sc)[:3]
     sd = scene_desc.scene_desc(sc, tex_channels=1, shadows=True)
     if stddev is not None:
         sd.rfilter = _abi.RFILTER_GAUSSIAN
     rows = scenes.material_rows(sc).astype(np.float64)
     rng = np.random.default_rng(1)
     tex = rng.uniform(0, 1, (8, 8, 1))
-    drows = interior_material_tangent(rows, rng)
+    drows = ref_prb.interior_material_tangent(rows, rng)
     drows[:, :3] = rng.uniform(0.5, 1.5, (rows.shape[0], 3))
     assert (drows[:, R0:R0 + 11] != 0).sum() >= 12
     spp, seed = 4, 3
-    a = float64_tangent(world, sd, rows, tex, spp, seed, depth, rr, stddev, drows=drows, h=5e-4)
-    b = float64_tangent(world, sd, rows, tex, spp, seed, depth, rr, stddev, drows=drows, h=2.5e-4)
+    a = ref_prb.float64_tangent(world, sd, rows, tex, spp, seed, depth, rr, stddev, drows=drows, h=5e-4)
+    b = ref_prb.float64_tangent(world, sd, rows, tex, spp, seed, depth, rr, stddev, drows=drows, h=2.5e-4)
     scale = np.abs(a).max()
     print("depth", depth, "rr", rr, "stddev", stddev, ": max |T(h) - T(h/2)|", np.abs(a - b).max(), "scale", scale)
     assert scale > 0 and np.abs(a - b).max() <= 1e-6 * scale
     dtex = rng.uniform(-1, 1, (8, 8, 1))
     dspot = np.array([0.5, 2.0, 1.25], np.float32)
-    lin = float64_tangent(world, sd, rows, tex, spp, seed, depth, rr, stddev, dtex=dtex, dspot=dspot)
-    hi = _copy(sd)
+    lin = ref_prb.float64_tangent(world, sd, rows, tex, spp, seed, depth, rr, stddev, dtex=dtex, dspot=dspot)
+    hi = copy_desc(sd)
     for c in range(3):
         hi.spot.intensity[c] = float(sd.spot.intensity[c]) + float(dspot[c])
     fd = (ref_prb.render_fwd_frozen(*world, hi, rows, rows, tex + dtex, spp, seed, depth, rr, gaussian_stddev=stddev)

@@ -2,7 +2,7 @@
 bit; the linear special cases against the existing forward; the dot-product identity <J dtheta, g> = <dtheta, J^T g> against the existing adjoints
 (render_bwd(appearance=True, material=True) at direct light, render_bwd_prb through the bounces), all blocks at once and one at a time, on rows
 inside their ranges and on rows pinned at the bounds where the adjoint holds one-sided values; every pixel against the float64 tangent of
-tests/test_jvp_cpu.py; mi.render_forward end to end; a full-size render.  Every compared figure is printed before it is asserted."""
+tests/ref_prb.py; mi.render_forward end to end; a full-size render.  Every compared figure is printed before it is asserted."""
 import os
 import subprocess
 import sys
@@ -11,32 +11,22 @@ import numpy as np
 import pytest
 import torch
 
-from fireflies_amd import mi, ops, scene_desc, scenes, workloads
-from tests import test_appearance_gpu as ta
-from tests import test_jvp_cpu as jc
-from tests import test_material_grad_gpu as tm
-from tests.test_path_gpu import bounce_scene
+from fireflies_amd import mi, ops, scenes, workloads
+from tests import corner_scenes as cs
+from tests import gpu_support as gpu
+from tests import ref_prb
+from tests.corner_scenes import R0
+from tests.gpu_support import DEV
+from tests.support import copy_desc
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda"
-R0 = tm.R0
 FILMS = [False, True]
 
 
 def _scene(name, gaussian, **kw):
-    """"lambert": tests/test_appearance_gpu.py's corner (a table of stride 3); "bounce": tests/test_path_gpu.py's relay; else
-    tests/test_material_grad_gpu.py's cases (defaults / every_lobe / textured) or a (floor, wall) pair of BSDF dictionaries"""
-    bt = None
-    if name == "lambert":
-        sc = ta.corner_scene(False, **kw)
-    elif name == "bounce":
-        sc = bounce_scene(True, True)
-    else:
-        fb, wb, tex = tm.CASES[name] if isinstance(name, str) else (*name, None)
-        bt = np.random.default_rng(5).uniform(0.2, 0.9, (8, 8, 3)).astype(np.float32) if tex else None
-        sc = tm.corner_scene(fb, wb, base_tex=bt, **kw)
-    ms, sd, world = tm._load(sc, gaussian, 1)
-    return sc, ms, sd, world
+    """cs.scene(name) loaded with a 1-channel texture -> (scene, loaded scene, description, world arrays)"""
+    sc = cs.scene(name, **kw)
+    return (sc, *gpu.load(sc, gaussian, 1))
 
 
 def _rand(shape, seed, lo=0.5, hi=1.5):
@@ -102,7 +92,7 @@ def _one_block(dtex, tan, name):
 @pytest.mark.parametrize("name", ["lambert", "every_lobe", "textured"])
 def test_primal_is_render_fwd_bitwise_and_the_tangent_repeats_bitwise(name, gaussian):
     _, ms, sd, _ = _scene(name, gaussian)
-    tex = tm._tex(sd, 1)
+    tex = gpu.rand_tex(sd, 1)
     dtex, tan = _tangent(ms, sd, 7)
     for depth, rr in ((2, 5), (3, 5), (4, 1)):
         ref = ms.geom.render_fwd(sd, None if sd.n_mat_h > 0 else ms.albedo, tex, 16, 3, max_depth=depth, rr_depth=rr).clone()
@@ -123,7 +113,7 @@ def test_linear_special_cases_against_the_forward(gaussian, depth):
     """identities of the model: the image is linear in the texture and in the spot's intensity, and (direct light, Lambert rows) in the base colours.
     1e-4 of the image scale per pixel: both sides are float32 sums of the same terms in another order"""
     _, ms, sd, _ = _scene("every_lobe", gaussian)
-    tex = tm._tex(sd, 1)
+    tex = gpu.rand_tex(sd, 1)
     spp, seed, rr = 16, 5, depth
     mats = None if sd.n_mat_h > 0 else ms.albedo
     fwd = lambda s, t, m=mats: ms.geom.render_fwd(s, m, t, spp, seed, max_depth=depth, rr_depth=rr).clone()  # noqa: E731
@@ -138,17 +128,17 @@ def test_linear_special_cases_against_the_forward(gaussian, depth):
     check("dtex", dimg, fwd(sd, dtex) - fwd(sd, torch.zeros_like(tex)))
     dspot = torch.tensor([0.5, 2.0, 1.25], device=DEV)
     _, dimg = _jvp(ms, sd, tex, spp, seed, None, ops.AppearanceGrad(None, dspot, None, None), depth, rr)
-    s2 = tm._copy(sd)
+    s2 = copy_desc(sd)
     for c in range(3):
         s2.spot.intensity[c] = float(dspot[c])
     check("dspot", dimg, fwd(s2, torch.zeros_like(tex)))
     if depth != 2:
         return
     _, ms, sd, _ = _scene("lambert", gaussian)
-    tex = tm._tex(sd, 1)
+    tex = gpu.rand_tex(sd, 1)
     db = _rand((sd.n_shapes, 3), 4, 0.1, 0.9)
     _, dimg = _jvp(ms, sd, tex, spp, seed, None, ops.AppearanceGrad(db, None, None, None))
-    s2 = tm._copy(sd)
+    s2 = copy_desc(sd)
     s2.n_mat_h = 0  # (the rows come from the table given)
     check("base colours of Lambert rows", dimg, ms.geom.render_fwd(s2, db.contiguous(), tex, spp, seed))
 
@@ -160,7 +150,7 @@ def test_dot_product_identity_against_the_adjoints(name, depth, rr, gaussian):
     """random gimg, a random tangent in every block and random dtex; then one block at a time, so that a wrong block cannot hide behind a large one.
     Roulette off (rr_depth = max_depth) and on"""
     _, ms, sd, _ = _scene(name, gaussian)
-    tex, gimg = tm._tex(sd, 3), tm._gimg(sd, 4) - 1.0  # (gimg in -0.5 .. 0.5)
+    tex, gimg = gpu.rand_tex(sd, 3), gpu.rand_gimg(sd, 4) - 1.0  # (gimg in -0.5 .. 0.5)
     spp, seed = 16, 5
     dtex, tan = _tangent(ms, sd, 11)
     what = f"{name} depth {depth} rr {rr} gaussian {gaussian}"
@@ -203,7 +193,7 @@ def test_one_sided_bounds_and_eta_1_follow_the_adjoint(corner, depth, rr, gaussi
     _, ms, sd, _ = _scene(BOUNDS[corner], gaussian)
     rows = ms._albedo_host
     assert rows[0, scenes.MAT_COLUMN["metallic"]] == 1.0 and (rows[[0, 2], scenes.MAT_COLUMN["eta"]] == 1.0).all() == (corner == 0)
-    tex, gimg = tm._tex(sd, 3), tm._gimg(sd, 4)
+    tex, gimg = gpu.rand_tex(sd, 3), gpu.rand_gimg(sd, 4)
     dtex, tan = _tangent(ms, sd, 21)
     what = f"bounds {corner} depth {depth} rr {rr} gaussian {gaussian}"
     _identity(ms, sd, tex, 16, 5, gimg, *_one_block(dtex, tan, "material"), depth, rr, what + " [material]")
@@ -221,21 +211,21 @@ def test_one_sided_bounds_and_eta_1_follow_the_adjoint(corner, depth, rr, gaussi
 @pytest.mark.parametrize("gaussian", FILMS)
 @pytest.mark.parametrize("depth,rr", [(2, 5), (3, 1)])
 def test_every_pixel_against_the_float64_tangent(depth, rr, gaussian):
-    """tests/test_jvp_cpu.float64_tangent (differences converged to 1e-6, linear parts exact), roulette frozen at the unperturbed rows.  Per pixel
+    """tests/ref_prb.float64_tangent (differences converged to 1e-6, linear parts exact), roulette frozen at the unperturbed rows.  Per pixel
     1e-4 of max |dimg_ref|; at most 2e-4 of the pixels (one here) may hold a flipped sample — the forward's tolerance, which a derivative image of the
     same sums inherits (256 pixels: none may)"""
     W = H = 16
-    sc = jc.small_corner(W, H, 8)
-    ms, sd, world = tm._load(sc, gaussian, 1)
+    sc = cs.small_corner(W, H, 8)
+    ms, sd, world = gpu.load(sc, gaussian, 1)
     rows = ms._albedo_host.astype(np.float64)
     rng = np.random.default_rng(2)
-    tex = tm._tex(sd, 1)
-    drows = jc.interior_material_tangent(rows, rng)
+    tex = gpu.rand_tex(sd, 1)
+    drows = ref_prb.interior_material_tangent(rows, rng)
     drows[:, :3] = rng.uniform(0.5, 1.5, (rows.shape[0], 3))
     dtex = rng.uniform(-1, 1, (8, 8, 1)).astype(np.float32)
     dspot = np.array([0.5, 2.0, 1.25], np.float32)
     spp, seed = 8, 7
-    ref = jc.float64_tangent(world, sd, rows, tex.cpu().numpy(), spp, seed, depth, rr, 0.5 if gaussian else None, drows=drows, dtex=dtex, dspot=dspot)
+    ref = ref_prb.float64_tangent(world, sd, rows, tex.cpu().numpy(), spp, seed, depth, rr, 0.5 if gaussian else None, drows=drows, dtex=dtex, dspot=dspot)
     tan = ops.AppearanceGrad(torch.from_numpy(drows[:, :3].astype(np.float32)), torch.from_numpy(dspot), [],
                              torch.from_numpy(drows[:, R0:R0 + 11].astype(np.float32)))
     _, dimg = _jvp(ms, sd, tex, spp, seed, torch.from_numpy(dtex), tan, depth, rr)
@@ -249,10 +239,10 @@ def test_every_pixel_against_the_float64_tangent(depth, rr, gaussian):
 
 
 def test_mi_render_forward_end_to_end():
-    fb, wb, _ = tm.CASES["every_lobe"]
-    sc = tm.corner_scene(fb, wb, shared=True)  # (the floor and the wall x = 0 share mat-Floor)
-    ms, sd, _ = tm._load(sc, False, 1)
-    tex = tm._tex(sd, 1)
+    fb, wb, _ = cs.CASES["every_lobe"]
+    sc = cs.corner(fb, wb, shared=True)  # (the floor and the wall x = 0 share mat-Floor)
+    ms, sd, _ = gpu.load(sc, False, 1)
+    tex = gpu.rand_tex(sd, 1)
     p = mi.traverse(ms)
     p["tex.data"] = tex[..., 0].clone()
     p.update()

@@ -3,33 +3,7 @@ import numpy as np
 import pytest
 
 from fireflies_amd import loaders, scenes
-
-XML = """<scene version="3.0.0">
-  <default name="spp" value="64"/>
-  <default name="res" value="96"/>
-  <bsdf type="twosided" id="mat-Mucosa"><bsdf type="principled"><rgb name="base_color" value="0.8, 0.3, 0.35"/><float name="roughness" value="0.35"/><float name="specular" value="0.6"/><float name="clearcoat" value="0.25"/></bsdf></bsdf>
-  <sensor type="perspective" id="PerspectiveCamera">
-    <float name="fov" value="60"/><float name="near_clip" value="0.01"/><float name="far_clip" value="100"/>
-    <transform name="to_world"><lookat origin="0,0,1.5" target="0,0,5" up="0,1,0"/></transform>
-    <film type="hdrfilm"><integer name="width" value="$res"/><integer name="height" value="$res"/></film>
-  </sensor>
-  <sensor type="perspective" id="PerspectiveCamera_1">
-    <float name="fov" value="30"/>
-    <transform name="to_world"><lookat origin="0.25,0,1.5" target="0,0,5" up="0,1,0"/></transform>
-    <film type="hdrfilm"><integer name="width" value="128"/><integer name="height" value="128"/></film>
-  </sensor>
-  <shape type="obj" id="mesh-Wall">
-    <string name="filename" value="wall.obj"/>
-    <transform name="to_world"><scale value="2"/><translate z="6"/></transform>
-    <ref id="mat-Mucosa"/>
-  </shape>
-  <shape type="obj" id="mesh-Quad"><string name="filename" value="quad.obj"/>
-    <bsdf type="diffuse"><rgb name="reflectance" value="0.2"/></bsdf></shape>
-  <emitter type="spot" id="emit-Spot"><rgb name="intensity" value="8"/><float name="cutoff_angle" value="40"/>
-    <transform name="to_world"><lookat origin="0,0.1,1.5" target="0,0,5" up="0,1,0"/></transform></emitter>
-  <emitter type="projector" id="Projector"><float name="scale" value="20"/>
-    <transform name="to_world"><lookat origin="0.25,0,1.5" target="0,0,5" up="0,1,0"/></transform></emitter>
-</scene>"""
+from tests.support import SCENE_XML as XML
 
 
 def test_obj_roundtrip_and_polygons(tmp_path):

@@ -1,43 +1,29 @@
 """The BSDF adjoint's ABI (include/ffx.h FFX_RENDER_GRAD_MATERIAL) without a GPU: the bit in the header and in _abi, its place among the
 flags, the block size from the header's macro against _abi.material_floats, the column order, and the specular -> eta chain factor."""
 import os
-import re
-import shutil
 import subprocess
 
 import numpy as np
 
 from fireflies_amd import _abi, scenes
+from tests.support import ROOT, c_compiler, define, header
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "ffx.h")
-
-
-def _header():
-    with open(HEADER) as f:
-        return f.read()
-
-
-def _define(name):
-    m = re.search(r"^#define\s+" + name + r"\s+(\S+)", _header(), re.M)
-    assert m, name
-    return int(m.group(1), 0)
 
 
 def test_bit_in_header_and_abi_agree():
-    assert _define("FFX_RENDER_GRAD_MATERIAL") == _abi.RENDER_GRAD_MATERIAL == 0x20000
-    assert _define("FFX_RENDER_MATERIAL_COLS") == _abi.RENDER_MATERIAL_COLS == 11
-    assert "FFX_RENDER_MATERIAL_FLOATS(sd)" in _header()
-    assert _define("FFX_ABI_VERSION") == 11
+    assert define("FFX_RENDER_GRAD_MATERIAL") == _abi.RENDER_GRAD_MATERIAL == 0x20000
+    assert define("FFX_RENDER_MATERIAL_COLS") == _abi.RENDER_MATERIAL_COLS == 11
+    assert "FFX_RENDER_MATERIAL_FLOATS(sd)" in header()
+    assert define("FFX_ABI_VERSION") == 11
 
 
 def test_bit_is_clear_of_the_other_flags():
     m = _abi.RENDER_GRAD_MATERIAL
     assert m & (m - 1) == 0
-    assert m & _abi.RENDER_GRAD_APPEARANCE == 0 and m & _define("FFX_RENDER_GRAD_APPEARANCE") == 0
-    assert m & _abi.RENDER_PATH_MASK == 0 and m & _define("FFX_RENDER_PATH_MASK") == 0
+    assert m & _abi.RENDER_GRAD_APPEARANCE == 0 and m & define("FFX_RENDER_GRAD_APPEARANCE") == 0
+    assert m & _abi.RENDER_PATH_MASK == 0 and m & define("FFX_RENDER_PATH_MASK") == 0
     for name in ("FFX_RENDER_FP16", "FFX_RENDER_SPARSE_ADJOINT", "FFX_RENDER_APEX_READY", "FFX_RENDER_CACHE_ZEROED", "FFX_RENDER_CACHE_KEEP_DROPPED"):
-        assert m & _define(name) == 0, name
+        assert m & define(name) == 0, name
     for f in (_abi.RENDER_FP16, _abi.RENDER_SPARSE_ADJOINT, _abi.RENDER_APEX_READY, _abi.RENDER_CACHE_ZEROED, _abi.RENDER_CACHE_KEEP_DROPPED):
         assert m & f == 0, f
     for md in range(2, _abi.RENDER_MAX_DEPTH_LIMIT + 1):
@@ -45,15 +31,8 @@ def test_bit_is_clear_of_the_other_flags():
             assert _abi.render_path(md, rr) & m == 0
 
 
-def _compiler():
-    for c in (os.environ.get("CC"), "cc", "gcc", "clang"):
-        if c and shutil.which(c):
-            return c
-    return None
-
-
 def test_block_size_macro_matches_the_helper(tmp_path):
-    cc = _compiler()
+    cc = c_compiler()
     assert cc is not None, "a C compiler is needed (the CPU oracle is built with one)"
     cases = [1, 2, 7, 64, 65, 255, 1000]
     lines = ['#include "ffx.h"', "#include <stdio.h>", "#include <string.h>", "int main(void) {", "  ffx_scene_desc sd;"]
@@ -71,10 +50,10 @@ def test_block_size_macro_matches_the_helper(tmp_path):
 
 def test_columns_follow_the_material_row():
     names = ["roughness", "anisotropic", "metallic", "spec_trans", "eta", "spec_tint", "sheen", "sheen_tint", "flatness", "clearcoat", "clearcoat_gloss"]
-    assert [scenes.MAT_COLUMN[n] for n in names] == list(range(_define("FFX_MAT_ROUGHNESS"), _define("FFX_MAT_CLEARCOAT_GLOSS") + 1))
+    assert [scenes.MAT_COLUMN[n] for n in names] == list(range(define("FFX_MAT_ROUGHNESS"), define("FFX_MAT_CLEARCOAT_GLOSS") + 1))
     for n in names:
-        assert scenes.MAT_COLUMN[n] == _define("FFX_MAT_" + n.upper())
-    assert _define("FFX_MAT_CLEARCOAT_GLOSS") - _define("FFX_MAT_ROUGHNESS") + 1 == _abi.RENDER_MATERIAL_COLS
+        assert scenes.MAT_COLUMN[n] == define("FFX_MAT_" + n.upper())
+    assert define("FFX_MAT_CLEARCOAT_GLOSS") - define("FFX_MAT_ROUGHNESS") + 1 == _abi.RENDER_MATERIAL_COLS
 
 
 def _eta64(s):

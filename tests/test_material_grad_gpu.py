@@ -11,102 +11,19 @@ import torch
 from fireflies_amd import _abi, mi, scene_desc, scenes, workloads
 from fireflies_amd._lib import api
 from tests import ref_bruteforce as rb
+from tests import gpu_support as gpu
 from tests import ref_path as rp
+from tests import support
+from tests.corner_scenes import EVERY_LOBE, NAMES, R0, base_texture, case, corner
+from tests.gpu_support import DEV
+from tests.support import FFX_ERR_ARG, copy_desc
 
 pytestmark = pytest.mark.gpu
-FFX_ERR_ARG = -1  # (include/ffx.h)
-DEV = "cuda"
-QUAD = np.array([[0, 1, 2], [0, 2, 3]], np.int32)
-R0 = scenes.MAT_COLUMN["roughness"]
-NAMES = ["roughness", "anisotropic", "metallic", "spec_trans", "eta", "spec_tint", "sheen", "sheen_tint", "flatness", "clearcoat", "clearcoat_gloss"]
-EVERY_LOBE = {"roughness": 0.4, "anisotropic": 0.5, "metallic": 0.3, "spec_trans": 0.2, "specular": 0.6, "spec_tint": 0.6, "sheen": 0.8, "sheen_tint": 0.7,
-              "flatness": 0.4, "clearcoat": 0.7, "clearcoat_gloss": 0.3}
-
-
-def _quad(p):
-    return np.asarray(p, np.float32)[None]
-
-
-def corner_scene(floor_bsdf, wall_bsdf, shared=False, W=24, H=24, tex=32, base_tex=None):
-    """tests/test_appearance_gpu.py's box corner: floor and wall y = 0 carry principled BSDFs, wall x = 0 and the cube are Lambert (or, shared, the wall
-    x = 0 shares the floor's material)"""
-    floor = _quad([[0, 0, 0], [2, 0, 0], [2, 2, 0], [0, 2, 0]])
-    wall_x = _quad([[0, 0, 0], [0, 2, 0], [0, 2, 2], [0, 0, 2]])
-    wall_y = _quad([[0, 0, 0], [2, 0, 0], [2, 0, 2], [0, 0, 2]])
-    cv, ct = scenes.make_cube((1.2, 1.1, 0.3), 0.3)
-    uv = np.array([[0, 0], [1, 0], [1, 1], [0, 1]], np.float32) if base_tex is not None else None
-    meshes = [scenes.MeshData("mesh-Floor", floor, QUAD, (0.6, 0.55, 0.5), material="mat-Floor", bsdf=floor_bsdf, uv=uv, base_tex=base_tex),
-              scenes.MeshData("mesh-WallX", wall_x, QUAD, (0.6, 0.55, 0.5) if shared else (0.7, 0.7, 0.75), material="mat-Floor" if shared else "mat-WallX",
-                              bsdf=floor_bsdf if shared else None),
-              scenes.MeshData("mesh-WallY", wall_y, QUAD, (0.5, 0.6, 0.7), material="mat-WallY", bsdf=wall_bsdf),
-              scenes.MeshData("mesh-Cube", cv[None], ct, (0.8, 0.4, 0.3), material="mat-Cube")]
-    cam = scenes.SensorData("PerspectiveCamera", scenes.look_at((3.2, 3.0, 2.4), (0.6, 0.6, 0.5), up=(0, 0, 1)), 50.0, 0.01, 100.0, W, H)
-    proj = scenes.SensorData("PerspectiveCamera_1", scenes.look_at((2.6, 1.2, 2.8), (0.7, 0.9, 0.2), up=(0, 0, 1)), 50.0, 0.01, 100.0, tex, tex)
-    spot = scenes.SpotData("emit-Spot", scenes.look_at((1.8, 2.6, 2.5), (0.5, 0.5, 0.0), up=(0, 0, 1)), (8.0, 8.0, 8.0), 30.0, 20.0)
-    return scenes.SceneData(meshes, cam, proj, spot, 1.0)
-
-
-def _load(sc, gaussian, tc):
-    ms = mi.load_scene_data(sc, device=DEV, shadows=True)
-    if gaussian:
-        ms.rfilter = "gaussian"
-    sd = ms.scene_desc(tex_channels=tc)
-    pool, tris, shape, off, stride, nfr, alb = scenes.flatten(sc)
-    world = (pool.astype(np.float64), tris + off[shape][:, None], shape)
-    return ms, sd, world
-
-
-def _tex(sd, seed=0):
-    g = torch.Generator().manual_seed(seed)
-    return torch.rand((sd.proj.tex_h, sd.proj.tex_w, sd.proj.tex_channels), generator=g).to(DEV)
-
-
-def _gimg(sd, seed=0):
-    g = torch.Generator().manual_seed(seed)
-    return (0.5 + torch.rand((sd.cam.height, sd.cam.width, 3), generator=g)).to(DEV)
-
-
-def _copy(sd):
-    out = _abi.SceneDesc()
-    C.memmove(C.addressof(out), C.addressof(sd), C.sizeof(out))
-    return out
-
-
-def _loss_gpu(ms, sd, rows, tex, spp, seed, gimg):
-    s2 = _copy(sd)
-    assert scene_desc.set_host_materials(s2, rows) is not False
-    img = ms.geom.render_fwd(s2, None, tex, spp, seed)
-    return float((img.double() * gimg.double()).sum())
-
-
-def _fd(f, rows, i, col, h, lo=0.0, hi=1.0):
-    """d f / d rows[i, col]: central, or second-order one-sided into [lo, hi] at a bound (the forward skips a lobe whose parameter sits there)"""
-    x = float(rows[i, col])
-
-    def at(v):
-        r = rows.copy()
-        r[i, col] = v
-        return f(r)
-
-    if col != scenes.MAT_COLUMN["eta"] and x - h < lo:
-        return (-3 * at(x) + 4 * at(x + h) - at(x + 2 * h)) / (2 * h)
-    if col != scenes.MAT_COLUMN["eta"] and x + h > hi:
-        return (3 * at(x) - 4 * at(x - h) + at(x - 2 * h)) / (2 * h)
-    return (at(x + h) - at(x - h)) / (2 * h)
-
-
-CASES = {
-    "defaults": ({}, {}, None),
-    "every_lobe": (EVERY_LOBE, {"roughness": 0.3, "metallic": 1.0, "clearcoat": 1.0, "clearcoat_gloss": 0.6, "spec_trans": 0.3, "sheen": 0.5}, None),
-    "textured": ({"roughness": 0.35, "metallic": 0.2, "specular": 0.6, "spec_tint": 0.5, "sheen": 0.6, "sheen_tint": 0.5}, {"roughness": 0.6}, "tex"),
-}
 
 
 def _case(name, gaussian):
-    fb, wb, bt = CASES[name]
-    base_tex = np.random.default_rng(5).uniform(0.2, 0.9, (8, 8, 3)).astype(np.float32) if bt else None
-    sc = corner_scene(fb, wb, base_tex=base_tex)
-    ms, sd, world = _load(sc, gaussian, 1)
+    sc, base_tex = case(name)
+    ms, sd, world = gpu.load(sc, gaussian, 1)
     return sc, ms, sd, world, base_tex
 
 
@@ -114,7 +31,7 @@ def _case(name, gaussian):
 def test_every_parameter_matches_the_float64_restatement(name, gaussian):
     sc, ms, sd, world, base_tex = _case(name, gaussian)
     assert sd.n_mat_h > 0
-    tex, gimg = _tex(sd, 1), _gimg(sd, 2)
+    tex, gimg = gpu.rand_tex(sd, 1), gpu.rand_gimg(sd, 2)
     spp, seed = 16, 7
     _, app = ms.geom.render_bwd(sd, None, spp, seed, gimg, appearance=True, tex=tex, material=True)
     g = app.material.double().cpu().numpy()
@@ -137,7 +54,7 @@ def test_every_parameter_matches_the_float64_restatement(name, gaussian):
     fd = np.zeros_like(g)
     for i in np.flatnonzero(~lam):
         for j in range(11):
-            fd[i, j] = _fd(f, rows, i, R0 + j, 1e-4)
+            fd[i, j] = support.fd(f, rows, i, R0 + j, 1e-4)
     for j in range(11):
         scale = np.abs(fd[:, j]).max()
         assert np.abs(g[:, j] - fd[:, j]).max() <= 2e-3 * scale + 1e-9, (NAMES[j], g[:, j], fd[:, j])
@@ -147,27 +64,26 @@ def test_every_parameter_matches_the_float64_restatement(name, gaussian):
 @pytest.mark.parametrize("name,gaussian", [("defaults", False), ("every_lobe", True), ("textured", True)])
 def test_every_parameter_matches_the_gpu_forward(name, gaussian):
     _, ms, sd, _, _ = _case(name, gaussian)
-    tex, gimg = _tex(sd, 3), _gimg(sd, 4)
+    tex, gimg = gpu.rand_tex(sd, 3), gpu.rand_gimg(sd, 4)
     spp, seed = 16, 5
     _, app = ms.geom.render_bwd(sd, None, spp, seed, gimg, appearance=True, tex=tex, material=True)
     g = app.material.double().cpu().numpy()
     rows = ms._albedo_host.copy()
 
     def f(r):
-        return _loss_gpu(ms, sd, r.astype(np.float32), tex, spp, seed, gimg)
+        return gpu.loss(ms, sd, r.astype(np.float32), tex, spp, seed, gimg)
 
     scale = np.abs(g).max()  # (the float32 loss resolves a column only relative to the largest gradient: the float64 test checks each column)
     for i in (0, 2):
         for j in range(11):
-            fd = _fd(f, rows.astype(np.float64), i, R0 + j, 1e-2)
+            fd = support.fd(f, rows.astype(np.float64), i, R0 + j, 1e-2)
             assert abs(g[i, j] - fd) <= 1e-2 * scale, (i, NAMES[j], g[i, j], fd, scale)
 
 
 @pytest.mark.parametrize("gaussian,tc", [(False, 1), (True, 3)])
 def test_nothing_else_moves(gaussian, tc):
-    bt = np.random.default_rng(5).uniform(0.2, 0.9, (8, 8, 3)).astype(np.float32)
-    ms, sd, _ = _load(corner_scene(EVERY_LOBE, {}, base_tex=bt), gaussian, tc)
-    tex, gimg = _tex(sd, 8), _gimg(sd, 9)
+    ms, sd, _ = gpu.load(corner(EVERY_LOBE, {}, base_tex=base_texture()), gaussian, tc)
+    tex, gimg = gpu.rand_tex(sd, 8), gpu.rand_gimg(sd, 9)
     gtex0 = ms.geom.render_bwd(sd, None, 16, 2, gimg)
     gtex1, app1 = ms.geom.render_bwd(sd, None, 16, 2, gimg, appearance=True, tex=tex)
     gtex2, app2 = ms.geom.render_bwd(sd, None, 16, 2, gimg, appearance=True, tex=tex, material=True)
@@ -183,15 +99,11 @@ def test_nothing_else_moves(gaussian, tc):
         assert torch.allclose(a, b, rtol=1e-5, atol=1e-5 * float(a.abs().max()))
 
 
-def _leaf(v):
-    return torch.tensor(v, dtype=torch.float32, device=DEV, requires_grad=True)
-
-
 def test_mi_render_leaves_end_to_end():
-    ms, sd, _ = _load(corner_scene(dict(EVERY_LOBE, anisotropic=0.0, clearcoat=0.0), {"roughness": 0.6}, shared=True), False, 3)
+    ms, sd, _ = gpu.load(corner(dict(EVERY_LOBE, anisotropic=0.0, clearcoat=0.0), {"roughness": 0.6}, shared=True), False, 3)
     p = mi.traverse(ms)
     spp, seed = 16, 4
-    tex, gimg = _tex(sd, 10), _gimg(sd, 11)
+    tex, gimg = gpu.rand_tex(sd, 10), gpu.rand_gimg(sd, 11)
     p["tex.data"] = tex
     p.update()
     sd = ms.scene_desc(tex_channels=3)
@@ -200,9 +112,9 @@ def test_mi_render_leaves_end_to_end():
     F, Y = "mat-Floor.brdf_0.", "mat-WallY.brdf_0."
     keys = {F + "roughness.value": 0.4, F + "metallic.value": 0.3, F + "clearcoat.value": 0.0, F + "anisotropic.value": 0.0, F + "specular": 0.6,
             Y + "eta": float(p[Y + "eta"])}
-    leaves = {k: _leaf(v) for k, v in keys.items()}
+    leaves = {k: gpu.leaf(v) for k, v in keys.items()}
     base = p[F + "base_color.value"].t.clone()
-    b_leaf, t_leaf = _leaf(base.tolist()), tex.clone().requires_grad_(True)
+    b_leaf, t_leaf = gpu.leaf(base.tolist()), tex.clone().requires_grad_(True)
     for k, v in leaves.items():
         p[k] = v
     p[F + "base_color.value"] = b_leaf
@@ -225,7 +137,7 @@ def test_mi_render_leaves_end_to_end():
     assert torch.allclose(b_leaf.grad, app.rows[rows].sum(0), rtol=1e-4, atol=1e-6)
     assert torch.allclose(t_leaf.grad, gtex_ref, rtol=1e-5, atol=1e-6 * float(gtex_ref.abs().max()))
     # specular and eta of one material in one update: specular drives the row, the eta leaf gets 0
-    s_leaf, e_leaf = _leaf(0.6), _leaf(1.7)
+    s_leaf, e_leaf = gpu.leaf(0.6), gpu.leaf(1.7)
     p[F + "specular"] = s_leaf
     p[F + "eta"] = e_leaf
     p.update()
@@ -246,11 +158,11 @@ def test_mi_render_leaves_end_to_end():
 
 
 def test_specular_at_zero_is_the_finite_limit():
-    ms, sd, _ = _load(corner_scene({"roughness": 0.3, "specular": 0.0}, {"roughness": 0.6}), False, 1)
+    ms, sd, _ = gpu.load(corner({"roughness": 0.3, "specular": 0.0}, {"roughness": 0.6}), False, 1)
     p = mi.traverse(ms)
-    tex, gimg = _tex(sd, 12), _gimg(sd, 13)
+    tex, gimg = gpu.rand_tex(sd, 12), gpu.rand_gimg(sd, 13)
     p["tex.data"] = tex[..., 0].contiguous()
-    leaf = _leaf(0.0)
+    leaf = gpu.leaf(0.0)
     p["mat-Floor.brdf_0.specular"] = leaf
     p.update()
     assert float(ms._albedo_host[0, scenes.MAT_COLUMN["eta"]]) == 1.0
@@ -263,39 +175,23 @@ def test_specular_at_zero_is_the_finite_limit():
     for s in (0.0, 1e-3, 2e-3):
         r = rows.copy()
         r[0, scenes.MAT_COLUMN["eta"]] = scenes.specular_to_eta(s)
-        ls.append(_loss_gpu(ms, sd, r, tex, 16, 3, gimg))
+        ls.append(gpu.loss(ms, sd, r, tex, 16, 3, gimg))
     fd = (-3 * ls[0] + 4 * ls[1] - ls[2]) / 2e-3
     assert abs(g - fd) <= 2e-2 * abs(fd), (g, fd)
 
 
-def _fit(ms, key, start, target_img, spp, seed, lr):
-    p = mi.traverse(ms)
-    leaf = _leaf(start)
-    opt = torch.optim.Adam([leaf], lr=lr)
-    sched = torch.optim.lr_scheduler.ExponentialLR(opt, 0.98)
-    for _ in range(300):
-        p[key] = leaf
-        p.update()
-        loss = ((mi.render(ms, spp=spp, seed=seed).torch() - target_img) ** 2).mean()
-        opt.zero_grad()
-        loss.backward()
-        opt.step()
-        sched.step()
-    return float(leaf.detach())
-
-
 def test_inverse_rendering_recovers_roughness_and_metallic():
-    ms, sd, _ = _load(corner_scene({"roughness": 0.35, "metallic": 0.2, "specular": 0.6}, {"roughness": 0.6}), False, 1)
+    ms, sd, _ = gpu.load(corner({"roughness": 0.35, "metallic": 0.2, "specular": 0.6}, {"roughness": 0.6}), False, 1)
     p = mi.traverse(ms)
-    p["tex.data"] = _tex(sd, 14)[..., 0].contiguous()
+    p["tex.data"] = gpu.rand_tex(sd, 14)[..., 0].contiguous()
     p.update()
     spp, seed = 16, 5
     target = mi.render(ms, spp=spp, seed=seed).torch().clone()
-    r = _fit(ms, "mat-Floor.brdf_0.roughness.value", 0.55, target, spp, seed, 0.02)
+    r = float(gpu.fit(ms, "mat-Floor.brdf_0.roughness.value", 0.55, target, spp, seed, 0.02, 300))
     assert abs(r - 0.35) < 2e-2, r
     p["mat-Floor.brdf_0.roughness.value"] = mi.Float(0.35)
     p.update()
-    m = _fit(ms, "mat-Floor.brdf_0.metallic.value", 0.4, target, spp, seed, 0.02)
+    m = float(gpu.fit(ms, "mat-Floor.brdf_0.metallic.value", 0.4, target, spp, seed, 0.02, 300))
     assert abs(m - 0.2) < 2e-2, m
 
 
@@ -323,7 +219,7 @@ def test_full_size_vocalfold_material_gradient():
     rows = ms._albedo_host.copy()
 
     def f(r):
-        s2 = _copy(sd)
+        s2 = copy_desc(sd)
         if sd.n_mat_h > 0:
             scene_desc.set_host_materials(s2, r.astype(np.float32))
             m2 = None
@@ -331,17 +227,17 @@ def test_full_size_vocalfold_material_gradient():
             m2 = torch.from_numpy(r.astype(np.float32)).to(DEV)
         return float((ms.geom.render_fwd(s2, m2, t3, spp, seed).double() * gimg.double()).sum())
 
-    fd = _fd(f, rows.astype(np.float64), i, R0 + j, 1e-2)
+    fd = support.fd(f, rows.astype(np.float64), i, R0 + j, 1e-2)
     assert abs(g[i, j] - fd) <= 1e-2 * abs(fd) + 1e-7, (NAMES[j], g[i, j], fd)
 
 
 def test_refusals():
-    ms, sd, _ = _load(corner_scene({"roughness": 0.35}, {}), False, 1)
+    ms, sd, _ = gpu.load(corner({"roughness": 0.35}, {}), False, 1)
     p = mi.traverse(ms)
-    tex, gimg = _tex(sd), _gimg(sd)
+    tex, gimg = gpu.rand_tex(sd), gpu.rand_gimg(sd)
     g = ms.geom
     p["tex.data"] = tex[..., 0].contiguous()
-    p["mat-Floor.brdf_0.roughness.value"] = _leaf(0.35)
+    p["mat-Floor.brdf_0.roughness.value"] = gpu.leaf(0.35)
     p.update()
     with pytest.raises(ValueError):
         mi.render(ms, spp=4, integrator=mi.load_dict({"type": "path", "max_depth": 3}))

@@ -1,37 +1,21 @@
 """The path integrator without a GPU: its float64 restatement (tests/ref_path.py) against a quadrature of the one-bounce
 radiance, and the argument checks of the Python layers and the ABI."""
-import os
 import re
 
 import numpy as np
 import pytest
 
-from fireflies_amd import _abi, ops, scene_desc, scenes
+from fireflies_amd import _abi, ops, scene_desc
 from tests import ref_bruteforce as bf
 from tests import ref_path as rp
+from tests.corner_scenes import relay
+from tests.support import header, world_arrays
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def bounce_scene(width=8, height=8):
-    """a Lambert wall (x = -1) that only the camera sees and no emitter reaches, and a floor (z = 0) lit by a spot straight above it"""
-    wall = np.array([[-1, -1, 0], [-1, 1, 0], [-1, 1, 2], [-1, -1, 2]], np.float32)
-    floor = np.array([[-1, -1, 0], [1, -1, 0], [1, 1, 0], [-1, 1, 0]], np.float32)
-    quad = np.array([[0, 1, 2], [0, 2, 3]], np.int32)
-    cam = scenes.SensorData("PerspectiveCamera", scenes.look_at((0.6, 0.0, 0.9), (-1.0, 0.0, 1.0), up=(0, 0, 1)), 20.0, 0.01, 100.0, width, height)
-    spot = scenes.SpotData("emit-Spot", scenes.look_at((0.0, 0.0, 1.5), (0.0, 0.0, 0.0), up=(0, 1, 0)), (10.0, 10.0, 10.0), 20.0, 15.0)
-    return scenes.SceneData([scenes.MeshData("mesh-Wall", wall[None], quad, (0.8, 0.7, 0.6)), scenes.MeshData("mesh-Floor", floor[None], quad, (0.5, 0.5, 0.5))],
-                            cam, None, spot)
-
-
-def _arrays(sc):
-    pool, tris, shape, off, stride, nfr, alb = scenes.flatten(sc)
-    return pool.astype(np.float64), tris + off[shape][:, None], shape, alb
 
 
 def test_path_estimator_matches_a_quadrature_of_the_one_bounce_radiance():
-    sc = bounce_scene()
-    verts, gidx, shape, alb = _arrays(sc)
+    sc = relay(False, True, 8, 8, projector_scale=1.0)  # (the spot alone)
+    verts, gidx, shape, alb = world_arrays(sc)
     sd = scene_desc.scene_desc(sc, tex_channels=1, shadows=True)
     spp, seed = 1024, 3
     # direct light only: the wall is dark
@@ -105,7 +89,7 @@ def test_load_dict_returns_integrators():
 
 
 def test_path_macros_in_header_and_abi():
-    hdr = open(os.path.join(ROOT, "include", "ffx.h")).read()
+    hdr = header()
     assert int(re.search(r"#define FFX_ABI_VERSION (\d+)", hdr).group(1)) == _abi.FFX_ABI_VERSION == 11
     for name, val in (("MAX_DEPTH_SHIFT", _abi.RENDER_MAX_DEPTH_SHIFT), ("RR_DEPTH_SHIFT", _abi.RENDER_RR_DEPTH_SHIFT), ("MAX_DEPTH_LIMIT", _abi.RENDER_MAX_DEPTH_LIMIT)):
         assert int(re.search(rf"#define FFX_RENDER_{name} (\d+)", hdr).group(1)) == val

@@ -9,68 +9,23 @@ import numpy as np
 import pytest
 import torch
 
-from fireflies_amd import _abi, mi, ops, scenes, workloads
+from fireflies_amd import _abi, mi, ops, workloads
 from fireflies_amd import functional as Fn
 from fireflies_amd._lib import api
 from fireflies_amd.optim import PatternOptimizer
+from tests import gpu_support as gpu
 from tests import ref_path as rp
+from tests.corner_scenes import path_corner, relay
+from tests.gpu_support import DEV
+from tests.support import FFX_ERR_ARG
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda"
-QUAD = np.array([[0, 1, 2], [0, 2, 3]], np.int32)
-FFX_ERR_ARG = -1  # include/ffx.h
-
-
-def _quad(p):
-    return np.asarray(p, np.float32)[None]
-
-
-def corner_scene(principled, W=24, H=24, tex=32):
-    """a box corner (floor and two walls) with a cube on the floor, lit by a projector and a spot"""
-    floor = _quad([[0, 0, 0], [2, 0, 0], [2, 2, 0], [0, 2, 0]])
-    wall_x = _quad([[0, 0, 0], [0, 2, 0], [0, 2, 2], [0, 0, 2]])
-    wall_y = _quad([[0, 0, 0], [2, 0, 0], [2, 0, 2], [0, 0, 2]])
-    cv, ct = scenes.make_cube((1.2, 1.1, 0.3), 0.3)
-    bs = {"roughness": 0.35, "metallic": 0.2, "specular": 0.6} if principled else None
-    meshes = [scenes.MeshData("mesh-Floor", floor, QUAD, (0.6, 0.55, 0.5), bsdf=bs), scenes.MeshData("mesh-WallX", wall_x, QUAD, (0.7, 0.7, 0.75)),
-              scenes.MeshData("mesh-WallY", wall_y, QUAD, (0.5, 0.6, 0.7), bsdf={"roughness": 0.6} if principled else None),
-              scenes.MeshData("mesh-Cube", cv[None], ct, (0.8, 0.4, 0.3))]
-    cam = scenes.SensorData("PerspectiveCamera", scenes.look_at((3.2, 3.0, 2.4), (0.6, 0.6, 0.5), up=(0, 0, 1)), 50.0, 0.01, 100.0, W, H)
-    proj = scenes.SensorData("PerspectiveCamera_1", scenes.look_at((2.6, 1.2, 2.8), (0.7, 0.9, 0.2), up=(0, 0, 1)), 50.0, 0.01, 100.0, tex, tex)
-    spot = scenes.SpotData("emit-Spot", scenes.look_at((1.8, 2.6, 2.5), (0.5, 0.5, 0.0), up=(0, 0, 1)), (8.0, 8.0, 8.0), 30.0, 20.0)
-    return scenes.SceneData(meshes, cam, proj, spot, 1.0)
-
-
-def bounce_scene(proj_on=True, spot_on=False, W=16, H=16, tex=32):
-    """the camera sees a wall (x = -1) only; the projector (and the spot) light only the floor (z = 0), which the camera cannot see"""
-    wall = _quad([[-1, -1, 0], [-1, 1, 0], [-1, 1, 2], [-1, -1, 2]])
-    floor = _quad([[-1, -1, 0], [1, -1, 0], [1, 1, 0], [-1, 1, 0]])
-    cam = scenes.SensorData("PerspectiveCamera", scenes.look_at((0.6, 0.0, 0.9), (-1.0, 0.0, 1.0), up=(0, 0, 1)), 20.0, 0.01, 100.0, W, H)
-    proj = scenes.SensorData("PerspectiveCamera_1", scenes.look_at((0.0, 0.0, 1.5), (0.0, 0.0, 0.0), up=(0, 1, 0)), 40.0, 0.01, 100.0, tex, tex) if proj_on else None
-    spot = scenes.SpotData("emit-Spot", scenes.look_at((0.0, 0.0, 1.5), (0.0, 0.0, 0.0), up=(0, 1, 0)), (10.0, 10.0, 10.0), 20.0, 15.0) if spot_on else None
-    return scenes.SceneData([scenes.MeshData("mesh-Wall", wall, QUAD, (0.8, 0.7, 0.6)), scenes.MeshData("mesh-Floor", floor, QUAD, (0.5, 0.5, 0.5))],
-                            cam, proj, spot, 2.0)
-
-
-def _load(sc, gaussian, tc):
-    ms = mi.load_scene_data(sc, device=DEV, shadows=True)
-    if gaussian:
-        ms.rfilter = "gaussian"
-    sd = ms.scene_desc(tex_channels=tc)
-    pool, tris, shape, off, stride, nfr, alb = scenes.flatten(sc)
-    world = (pool.astype(np.float64), tris + off[shape][:, None], shape, ms.albedo.cpu().numpy().astype(np.float64))
-    return ms, sd, world
-
-
-def _tex(sd, seed=0):
-    g = torch.Generator().manual_seed(seed)
-    return torch.rand((sd.proj.tex_h, sd.proj.tex_w, sd.proj.tex_channels), generator=g).to(DEV)
 
 
 @pytest.mark.parametrize("gaussian", [False, True])
 def test_max_depth_2_is_the_default_render_bitwise(gaussian):
-    ms, sd, _ = _load(corner_scene(True), gaussian, 1)
-    tex = _tex(sd)
+    ms, sd, _ = gpu.load(path_corner(True), gaussian, 1)
+    tex = gpu.rand_tex(sd)
     mats = ms.materials_arg(sd)
     ref = ms.geom.render_fwd(sd, mats, tex, 16, 3)
     assert torch.equal(ms.geom.render_fwd(sd, mats, tex, 16, 3, max_depth=2), ref)
@@ -85,15 +40,16 @@ def test_max_depth_2_is_the_default_render_bitwise(gaussian):
 
 @pytest.mark.parametrize("depth,principled,tc,gaussian", [(3, False, 1, False), (4, True, 3, True), (3, True, 1, True), (4, False, 3, False)])
 def test_path_render_matches_float64_restatement(depth, principled, tc, gaussian):
-    ms, sd, world = _load(corner_scene(principled), gaussian, tc)
-    tex = _tex(sd, 1)
+    ms, sd, world = gpu.load(path_corner(principled), gaussian, tc)
+    alb = ms.albedo.cpu().numpy().astype(np.float64)
+    tex = gpu.rand_tex(sd, 1)
     spp, seed = 16, 7
     mats = ms.materials_arg(sd)
     img = ms.geom.render_fwd(sd, mats, tex, spp, seed, max_depth=depth).cpu().numpy().astype(np.float64)
     tex_np = tex.cpu().numpy()
     stddev = 0.5 if gaussian else None
-    ref = rp.render_fwd(*world[:3], sd, world[3], tex_np, spp, seed, depth, gaussian_stddev=stddev)
-    ref2 = rp.render_fwd(*world[:3], sd, world[3], tex_np, spp, seed, 2, gaussian_stddev=stddev)
+    ref = rp.render_fwd(*world, sd, alb, tex_np, spp, seed, depth, gaussian_stddev=stddev)
+    ref2 = rp.render_fwd(*world, sd, alb, tex_np, spp, seed, 2, gaussian_stddev=stddev)
     indirect = ref - ref2
     scale = float(ref.max())
     assert indirect.mean() > 0.05 * ref.mean() > 0  # (the bounces matter in this scene)
@@ -106,15 +62,15 @@ def test_path_render_matches_float64_restatement(depth, principled, tc, gaussian
     # the adjoint: the same paths replayed
     gimg = np.where(np.random.default_rng(2).random(img.shape) < 0.5, -1.0, 1.0).astype(np.float32) / img.size
     gt = ms.geom.render_bwd(sd, mats, spp, seed, torch.from_numpy(gimg).to(DEV), max_depth=depth).cpu().numpy().astype(np.float64)
-    gt_ref = rp.render_bwd(*world[:3], sd, world[3], spp, seed, gimg, depth, gaussian_stddev=stddev)
+    gt_ref = rp.render_bwd(*world, sd, alb, spp, seed, gimg, depth, gaussian_stddev=stddev)
     gs = np.abs(gt_ref).sum()
     assert gs > 0 and np.abs(gt - gt_ref).sum() <= 0.03 * gs, (np.abs(gt - gt_ref).sum(), gs)
 
 
 @pytest.mark.parametrize("gaussian", [False, True])
 def test_light_that_arrives_by_a_bounce_only(gaussian):
-    ms, sd, _ = _load(bounce_scene(), gaussian, 1)
-    tex = _tex(sd, 4)
+    ms, sd, _ = gpu.load(relay(), gaussian, 1)
+    tex = gpu.rand_tex(sd, 4)
     mats = ms.materials_arg(sd)
     spp, seed = 32, 5
     gimg = torch.rand((sd.cam.height, sd.cam.width, 3), device=DEV)
@@ -131,9 +87,9 @@ def test_light_that_arrives_by_a_bounce_only(gaussian):
 
 @pytest.mark.parametrize("gaussian", [False, True])
 def test_path_autograd_equals_render_bwd_and_forward_is_deterministic(gaussian):
-    ms, sd, _ = _load(corner_scene(True), gaussian, 1)
+    ms, sd, _ = gpu.load(path_corner(True), gaussian, 1)
     mats = ms.materials_arg(sd)
-    tex = _tex(sd, 2)
+    tex = gpu.rand_tex(sd, 2)
     a = ms.geom.render_fwd(sd, mats, tex, 64, 11, max_depth=4)
     b = ms.geom.render_fwd(sd, mats, tex, 64, 11, max_depth=4)
     assert torch.equal(a, b)
@@ -175,9 +131,9 @@ def test_pattern_optimizer_path_steps_match_autograd():
 
 
 def test_path_refusals():
-    ms, sd, _ = _load(corner_scene(False), False, 1)
+    ms, sd, _ = gpu.load(path_corner(False), False, 1)
     mats = ms.materials_arg(sd)
-    tex = _tex(sd)
+    tex = gpu.rand_tex(sd)
     g = ms.geom
     gimg = torch.ones((sd.cam.height, sd.cam.width, 3), device=DEV)
     cache = torch.empty(ops.render_cache_bytes_sd(sd, 4), dtype=torch.uint8, device=DEV)

@@ -2,32 +2,20 @@
 flags, the refusals that come before any launch (host dummy pointers, as tests/test_abi_cpu.py's), and the float64 restatement's detached roulette
 (tests/ref_prb.py) against tests/ref_path.py."""
 import ctypes as C
-import os
 import re
 
 import numpy as np
 import pytest
 
-from fireflies_amd import _abi, _lib, mi, scene_desc, scenes
+from fireflies_amd import _abi, _lib, mi, scene_desc
 from tests import ref_path as rp
 from tests import ref_prb
+from tests.corner_scenes import spot_corner
+from tests.support import FFX_ERR_ARG, FFX_ERR_UNSUPPORTED, define, enum_value, header, world_arrays
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-FFX_ERR_ARG, FFX_ERR_UNSUPPORTED = -1, -3  # (include/ffx.h; checked below)
 APP, MAT, PRB = _abi.RENDER_GRAD_APPEARANCE, _abi.RENDER_GRAD_MATERIAL, _abi.RENDER_GRAD_PRB
 P3 = _abi.render_path(3, 5)
 GAUSS = {"rfilter": _abi.RFILTER_GAUSSIAN}
-
-
-def _header():
-    with open(os.path.join(ROOT, "include", "ffx.h")) as f:
-        return f.read()
-
-
-def _define(name):
-    m = re.search(r"^#define\s+" + name + r"\s+(\S+)", _header(), re.M)
-    assert m, name
-    return int(m.group(1), 0)
 
 
 def test_load_dict_prb():
@@ -48,10 +36,9 @@ def test_load_dict_prb():
 
 
 def test_bit_in_header_and_abi_agree():
-    assert _define("FFX_RENDER_GRAD_PRB") == _abi.RENDER_GRAD_PRB == 0x40000
-    assert _define("FFX_ABI_VERSION") == _abi.FFX_ABI_VERSION == 11
-    for name, val in (("FFX_ERR_ARG", FFX_ERR_ARG), ("FFX_ERR_UNSUPPORTED", FFX_ERR_UNSUPPORTED)):
-        assert int(re.search(r"^\s*" + name + r"\s*=\s*(-?\d+)", _header(), re.M).group(1)) == val
+    assert define("FFX_RENDER_GRAD_PRB") == _abi.RENDER_GRAD_PRB == 0x40000
+    assert define("FFX_ABI_VERSION") == _abi.FFX_ABI_VERSION == 11
+    assert (enum_value("FFX_ERR_ARG"), enum_value("FFX_ERR_UNSUPPORTED")) == (FFX_ERR_ARG, FFX_ERR_UNSUPPORTED) == (-1, -3)
 
 
 def test_bit_is_clear_of_the_other_flags():
@@ -59,9 +46,9 @@ def test_bit_is_clear_of_the_other_flags():
     assert m & (m - 1) == 0
     for name in ("FFX_RENDER_FP16", "FFX_RENDER_SPARSE_ADJOINT", "FFX_RENDER_APEX_READY", "FFX_RENDER_CACHE_ZEROED", "FFX_RENDER_CACHE_KEEP_DROPPED",
                  "FFX_RENDER_GRAD_APPEARANCE", "FFX_RENDER_GRAD_MATERIAL", "FFX_RENDER_PATH_MASK"):
-        assert m & _define(name) == 0, name
+        assert m & define(name) == 0, name
     # every other FFX_RENDER_* flag the header defines as a plain number that could share the word
-    for name, val in re.findall(r"^#define\s+(FFX_RENDER_[A-Z_0-9]+)\s+(0x[0-9a-fA-F]+|\d+)\s", _header(), re.M):
+    for name, val in re.findall(r"^#define\s+(FFX_RENDER_[A-Z_0-9]+)\s+(0x[0-9a-fA-F]+|\d+)\s", header(), re.M):
         if name in ("FFX_RENDER_GRAD_PRB", "FFX_RENDER_MAX_DEPTH_SHIFT", "FFX_RENDER_RR_DEPTH_SHIFT", "FFX_RENDER_MAX_DEPTH_LIMIT", "FFX_RENDER_MATERIAL_COLS"):
             continue
         assert m & int(val, 0) == 0, name
@@ -138,23 +125,11 @@ def test_refusals_before_any_launch(case, monkeypatch):
     assert msg in err, err
 
 
-def _corner():
-    quad = np.array([[0, 1, 2], [0, 2, 3]], np.int32)
-    floor = np.array([[0, 0, 0], [2, 0, 0], [2, 2, 0], [0, 2, 0]], np.float32)[None]
-    wall = np.array([[0, 0, 0], [0, 2, 0], [0, 2, 2], [0, 0, 2]], np.float32)[None]
-    meshes = [scenes.MeshData("mesh-Floor", floor, quad, (0.6, 0.55, 0.5), bsdf={"roughness": 0.35, "metallic": 0.2, "specular": 0.6}),
-              scenes.MeshData("mesh-Wall", wall, quad, (0.7, 0.7, 0.75))]
-    cam = scenes.SensorData("PerspectiveCamera", scenes.look_at((3.2, 3.0, 2.4), (0.6, 0.6, 0.5), up=(0, 0, 1)), 50.0, 0.01, 100.0, 6, 6)
-    spot = scenes.SpotData("emit-Spot", scenes.look_at((1.8, 2.6, 2.5), (0.5, 0.5, 0.0), up=(0, 0, 1)), (8.0, 8.0, 8.0), 30.0, 20.0)
-    return scenes.SceneData(meshes, cam, None, spot)
-
-
 def test_frozen_roulette_restatement():
     """ref_prb.render_fwd_frozen is ref_path.render_fwd when the rows are the frozen ones; under a perturbed row it keeps the unperturbed paths'
     survivors and q, so it is smooth in the row where ref_path's image differentiates q (and may jump)"""
-    sc = _corner()
-    pool, tris, shape, off, stride, nfr, alb = scenes.flatten(sc)
-    world = (pool.astype(np.float64), tris + off[shape][:, None], shape)
+    sc = spot_corner()
+    *world, alb = world_arrays(sc)
     sd = scene_desc.scene_desc(sc, tex_channels=1, shadows=True)
     rows = np.asarray(alb, np.float64)
     spp, seed = 8, 3

@@ -8,53 +8,24 @@ import torch
 
 from fireflies_amd import mi, scene_desc, scenes, workloads
 from fireflies_amd import functional as Fn
+from tests import corner_scenes as cs
+from tests import gpu_support as gpu
 from tests import ref_path as rp
 from tests import ref_prb
-from tests import test_appearance_gpu as ta
-from tests import test_material_grad_gpu as tm
-from tests.test_path_gpu import bounce_scene
+from tests import support
+from tests.corner_scenes import NAMES, R0
+from tests.gpu_support import DEV
+from tests.support import copy_desc
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda"
-R0, NAMES = tm.R0, tm.NAMES
 
 
 def _scene(name, gaussian, **kw):
-    """"lambert": tests/test_appearance_gpu.py's corner with Lambert rows only; else tests/test_material_grad_gpu.py's cases (defaults / every_lobe /
-    textured: principled floor and wall y = 0, Lambert wall x = 0 and cube)"""
-    if name == "lambert":
-        sc = ta.corner_scene(False, **kw)
-        bt = None
-    else:
-        fb, wb, tex = tm.CASES[name]
-        bt = np.random.default_rng(5).uniform(0.2, 0.9, (8, 8, 3)).astype(np.float32) if tex else None
-        sc = tm.corner_scene(fb, wb, base_tex=bt, **kw)
-    ms, sd, world = tm._load(sc, gaussian, 1)
-    return sc, ms, sd, world, bt
+    """cs.scene(name) loaded with a 1-channel texture -> (scene, loaded scene, description, world arrays, the floor's base texture or None)"""
+    sc = cs.scene(name, **kw)
+    ms, sd, world = gpu.load(sc, gaussian, 1)
+    return sc, ms, sd, world, sc.meshes[0].base_tex
 
-
-def _loss(ms, sd, rows, tex, spp, seed, gimg, depth, rr):
-    s2 = tm._copy(sd)
-    assert scene_desc.set_host_materials(s2, np.asarray(rows, np.float32)) is not False
-    img = ms.geom.render_fwd(s2, None, tex, spp, seed, max_depth=depth, rr_depth=rr)
-    return float((img.double() * gimg.double()).sum())
-
-
-def _fd4(f, rows, i, col, h):
-    """d f / d rows[i, col] by the five-point central stencil (error h^4 f^(5) / 30) where x -+ 2h stays inside the parameter's range, else
-    tests/test_material_grad_gpu.py's second-order one-sided form.  The three-point stencil is not enough for roughness once a bounce samples the
-    GGX peak, where D ~ roughness^-4: at h = 1e-2 its h^2 f(3) / 6 was 1 % of the floor's roughness gradient on the textured corner and fell by 4
-    with every halving of h (6.1e-2, 1.5e-2, 3.7e-3, 7.8e-4 at h = 2e-2 .. 2.5e-3), while this stencil agreed with the adjoint to 8e-6."""
-    x = float(rows[i, col])
-    if col != scenes.MAT_COLUMN["eta"] and (x - 2 * h < 0.0 or x + 2 * h > 1.0):
-        return tm._fd(f, rows, i, col, h)
-
-    def at(v):
-        r = rows.copy()
-        r[i, col] = v
-        return f(r)
-
-    return (-at(x + 2 * h) + 8 * at(x + h) - 8 * at(x - h) + at(x - 2 * h)) / (12 * h)
 
 
 def _blocks(ms, sd, spp, seed, gimg, tex, depth, rr, material=True):
@@ -66,7 +37,7 @@ def _blocks(ms, sd, spp, seed, gimg, tex, depth, rr, material=True):
 @pytest.mark.parametrize("gaussian", [False, True])
 def test_prb_forward_is_the_path_forward_bitwise(gaussian):
     _, ms, sd, _, _ = _scene("defaults", gaussian)
-    tex = tm._tex(sd)
+    tex = gpu.rand_tex(sd)
     ms._params["tex.data"] = tex[..., 0].clone()
     for depth, rr in ((3, 5), (4, 1), (2, 5)):
         a = mi.render(ms, spp=16, seed=3, integrator=mi.load_dict({"type": "path", "max_depth": depth, "rr_depth": rr})).torch().clone()
@@ -77,7 +48,7 @@ def test_prb_forward_is_the_path_forward_bitwise(gaussian):
     # with a tex.data leaf only (what PatternOptimizer differentiates) prb is path: same image, same texture gradient
     leaf = tex[..., 0].clone().requires_grad_(True)
     ms._params["tex.data"] = leaf
-    gimg = tm._gimg(sd, 1)
+    gimg = gpu.rand_gimg(sd, 1)
     grads = []
     for t in ("path", "prb"):
         leaf.grad = None
@@ -101,7 +72,7 @@ def test_blocks_match_central_differences_of_the_gpu_forward(name, gaussian, dep
     h = 1e-2): 127 of the 132 columns of the 12 principled cases are inside 2e-3 scale + 1e-9 on their own; the other five are the sheen_tint
     column (gradient 2e-3 .. 6e-3), errors 9e-6 .. 3e-5 against 2e-3 scale = 4e-6 .. 1e-5, with depth-2 floors of 5e-5 .. 1.3e-4 in the same runs."""
     _, ms, sd, _, bt = _scene(name, gaussian)
-    tex, gimg = tm._tex(sd, 3), tm._gimg(sd, 4)
+    tex, gimg = gpu.rand_tex(sd, 3), gpu.rand_gimg(sd, 4)
     spp, seed, rr = 16, 5, depth
     rows = ms._albedo_host.astype(np.float64)
     gtex, app = _blocks(ms, sd, spp, seed, gimg, tex, depth, rr)
@@ -121,7 +92,7 @@ def test_blocks_match_central_differences_of_the_gpu_forward(name, gaussian, dep
             lo, hi = rows.copy(), rows.copy()
             lo[i, k] -= h
             hi[i, k] += h
-            fd[i, k] = (_loss(ms, sd, hi, tex, spp, seed, gimg, depth, rr) - _loss(ms, sd, lo, tex, spp, seed, gimg, depth, rr)) / (2 * h)
+            fd[i, k] = (gpu.loss(ms, sd, hi, tex, spp, seed, gimg, depth, rr) - gpu.loss(ms, sd, lo, tex, spp, seed, gimg, depth, rr)) / (2 * h)
     scale = np.abs(fd).max()
     print("rows: max |g - fd|", np.abs(g - fd).max(), "scale", scale)
     assert scale > 0 and np.abs(g - fd).max() <= 1e-3 * scale, (g, fd)
@@ -130,7 +101,7 @@ def test_blocks_match_central_differences_of_the_gpu_forward(name, gaussian, dep
     assert np.abs(g - app2.rows.double().cpu().numpy()).max() > 1e-2 * scale
     # the spot's intensity
     for c in range(3):
-        lo, hi = tm._copy(sd), tm._copy(sd)
+        lo, hi = copy_desc(sd), copy_desc(sd)
         lo.spot.intensity[c] -= 0.5
         hi.spot.intensity[c] += 0.5
         ls = [float((ms.geom.render_fwd(s, None, tex, spp, seed, max_depth=depth, rr_depth=rr).double() * gimg.double()).sum()) for s in (hi, lo)]
@@ -164,8 +135,8 @@ def test_blocks_match_central_differences_of_the_gpu_forward(name, gaussian, dep
     fdm, fdm2 = np.zeros_like(m), np.zeros_like(m)
     for i in np.flatnonzero(~lam):
         for j in range(11):
-            fdm[i, j] = _fd4(lambda r: _loss(ms, sd, r, tex, spp, seed, gimg, depth, rr), rows, i, R0 + j, 1e-2)
-            fdm2[i, j] = _fd4(lambda r: _loss(ms, sd, r, tex, spp, seed, gimg, 2, 5), rows, i, R0 + j, 1e-2)
+            fdm[i, j] = support.fd4(lambda r: gpu.loss(ms, sd, r, tex, spp, seed, gimg, depth, rr), rows, i, R0 + j, 1e-2)
+            fdm2[i, j] = support.fd4(lambda r: gpu.loss(ms, sd, r, tex, spp, seed, gimg, 2, 5), rows, i, R0 + j, 1e-2)
     floor = np.abs(m2 - fdm2).max()  # (the existing adjoint against the same kind of difference, this run: the differences' noise floor)
     for j in range(11):
         sc_j = np.abs(fdm[:, j]).max()
@@ -183,7 +154,7 @@ def test_blocks_match_the_float64_restatement(name, gaussian, depth, rr):
     after a bounce, which test_path_render_matches_float64_restatement grants the texture gradient as 3 % of its L1 norm: every block is held to the
     same 3 %, and so is the texture gradient of the same call (the undisputed quantity)."""
     _, ms, sd, world, _ = _scene(name, gaussian, W=16, H=16)
-    tex, gimg = tm._tex(sd, 1), tm._gimg(sd, 2)
+    tex, gimg = gpu.rand_tex(sd, 1), gpu.rand_gimg(sd, 2)
     spp, seed = 8, 7
     gtex, app = _blocks(ms, sd, spp, seed, gimg, tex, depth, rr)
     rows = ms._albedo_host.astype(np.float64)
@@ -209,7 +180,7 @@ def test_blocks_match_the_float64_restatement(name, gaussian, depth, rr):
     assert np.abs(fd).sum() > 0 and np.abs(g - fd).sum() <= 0.03 * np.abs(fd).sum(), (g, fd)
     gs, fs = app.spot.double().cpu().numpy(), np.zeros(3)
     for c in range(3):
-        lo, hi = tm._copy(sd), tm._copy(sd)
+        lo, hi = copy_desc(sd), copy_desc(sd)
         lo.spot.intensity[c] -= 0.5
         hi.spot.intensity[c] += 0.5
         fs[c] = f(rows, hi) - f(rows, lo)
@@ -222,7 +193,7 @@ def test_blocks_match_the_float64_restatement(name, gaussian, depth, rr):
     fdm = np.zeros_like(m)
     for i in np.flatnonzero(~lam):
         for j in range(11):
-            fdm[i, j] = tm._fd(f, rows, i, R0 + j, 1e-4)
+            fdm[i, j] = support.fd(f, rows, i, R0 + j, 1e-4)
     print("material L1 err", np.abs(m - fdm).sum(), "of", np.abs(fdm).sum(), "\n", m, "\n", fdm)
     assert np.abs(fdm).sum() > 0 and np.abs(m - fdm).sum() <= 0.03 * np.abs(fdm).sum()
 
@@ -231,8 +202,8 @@ def test_blocks_match_the_float64_restatement(name, gaussian, depth, rr):
 def test_the_relaying_surface_has_a_gradient_only_through_the_bounce(gaussian):
     """bounce_scene: the camera sees the wall, the emitters light the floor only.  The wall's base colour scales every pixel, and so does the floor's,
     which relays the light — at direct light both gradients are exactly 0, at depth 3 they are the central differences"""
-    ms, sd, _ = tm._load(bounce_scene(True, True), gaussian, 1)
-    tex, gimg = tm._tex(sd, 4), tm._gimg(sd, 5)
+    ms, sd, _ = gpu.load(cs.relay(True, True), gaussian, 1)
+    tex, gimg = gpu.rand_tex(sd, 4), gpu.rand_gimg(sd, 5)
     spp, seed = 32, 5
     mats = ms.materials_arg(sd)
     _, app2 = ms.geom.render_bwd(sd, mats, spp, seed, gimg, appearance=True, tex=tex)
@@ -245,7 +216,7 @@ def test_the_relaying_surface_has_a_gradient_only_through_the_bounce(gaussian):
     fd = np.zeros_like(g)
 
     def loss(r):
-        s2 = tm._copy(sd)
+        s2 = copy_desc(sd)
         if sd.n_mat_h > 0:
             scene_desc.set_host_materials(s2, r)
             m2 = None
@@ -264,18 +235,13 @@ def test_the_relaying_surface_has_a_gradient_only_through_the_bounce(gaussian):
     assert float((gtex - ms.geom.render_bwd(sd, mats, spp, seed, gimg, max_depth=3)).abs().max()) <= 1e-3 * float(gtex.abs().max())
 
 
-def _leaf(v):
-    return torch.tensor(v, dtype=torch.float32, device=DEV, requires_grad=True)
-
-
 def test_mi_render_leaves_end_to_end(monkeypatch):
-    bt = np.random.default_rng(5).uniform(0.2, 0.9, (8, 8, 3)).astype(np.float32)
-    sc = tm.corner_scene(dict(tm.EVERY_LOBE, anisotropic=0.0, clearcoat=0.0), {"roughness": 0.6}, base_tex=bt)
-    ms, sd, _ = tm._load(sc, False, 3)
+    sc = cs.corner(dict(cs.EVERY_LOBE, anisotropic=0.0, clearcoat=0.0), {"roughness": 0.6}, base_tex=cs.base_texture())
+    ms, sd, _ = gpu.load(sc, False, 3)
     p = mi.traverse(ms)
     spp, seed = 16, 4
     it = mi.load_dict({"type": "prb", "max_depth": 3, "rr_depth": 2})
-    tex, gimg = tm._tex(sd, 10), tm._gimg(sd, 11)
+    tex, gimg = gpu.rand_tex(sd, 10), gpu.rand_gimg(sd, 11)
     p["tex.data"] = tex
     p.update()
     sd = ms.scene_desc(tex_channels=3)
@@ -283,11 +249,11 @@ def test_mi_render_leaves_end_to_end(monkeypatch):
     plain0 = mi.render(ms, spp=spp, seed=seed, integrator=it).torch().clone()
     F, Y = "mat-Floor.brdf_0.", "mat-WallY.brdf_0."
     keys = {F + "roughness.value": 0.4, F + "metallic.value": 0.3, F + "specular": 0.6, Y + "roughness.value": 0.6}
-    leaves = {k: _leaf(v) for k, v in keys.items()}
+    leaves = {k: gpu.leaf(v) for k, v in keys.items()}
     yb = p[Y + "base_color.value"].t.clone()
     cb = p["mat-Cube.brdf_0.base_color.value"].t.clone()
-    y_leaf, c_leaf = _leaf(yb.tolist()), _leaf(cb.tolist())
-    s_leaf = _leaf(p["emit-Spot.intensity.value"].t.tolist())
+    y_leaf, c_leaf = gpu.leaf(yb.tolist()), gpu.leaf(cb.tolist())
+    s_leaf = gpu.leaf(p["emit-Spot.intensity.value"].t.tolist())
     bt_leaf = p[F + "base_color.data"].t.clone().requires_grad_(True) if hasattr(p[F + "base_color.data"], "t") else None
     t_leaf = tex.clone().requires_grad_(True)
     for k, v in leaves.items():
@@ -350,39 +316,23 @@ def test_mi_render_leaves_end_to_end(monkeypatch):
     ms.geom.version -= 1
 
 
-def _fit(ms, key, start, target_img, spp, seed, lr, it):
-    p = mi.traverse(ms)
-    leaf = _leaf(start)
-    opt = torch.optim.Adam([leaf], lr=lr)
-    sched = torch.optim.lr_scheduler.ExponentialLR(opt, 0.98)
-    for _ in range(300):
-        p[key] = leaf
-        p.update()
-        loss = ((mi.render(ms, spp=spp, seed=seed, integrator=it).torch() - target_img) ** 2).mean()
-        opt.zero_grad()
-        loss.backward()
-        opt.step()
-        sched.step()
-    return leaf.detach()
-
-
 def test_inverse_rendering_at_depth_3():
     """the fits of tests/test_appearance_gpu.py (a base colour to 1e-2) and tests/test_material_grad_gpu.py (a roughness to 2e-2), with a bounce"""
-    sc = tm.corner_scene({"roughness": 0.35, "metallic": 0.2, "specular": 0.6}, {"roughness": 0.6})
-    ms, sd, _ = tm._load(sc, False, 1)
+    sc = cs.corner({"roughness": 0.35, "metallic": 0.2, "specular": 0.6}, {"roughness": 0.6})
+    ms, sd, _ = gpu.load(sc, False, 1)
     it = mi.load_dict({"type": "prb", "max_depth": 3})
     p = mi.traverse(ms)
-    p["tex.data"] = tm._tex(sd, 14)[..., 0].contiguous()
+    p["tex.data"] = gpu.rand_tex(sd, 14)[..., 0].contiguous()
     p.update()
     spp, seed = 16, 5
     target = mi.render(ms, spp=spp, seed=seed, integrator=it).torch().clone()
     key = "mat-WallX.brdf_0.base_color.value"
     b_true = p[key].t.clone()
-    b = _fit(ms, key, (b_true + torch.tensor([0.15, -0.2, 0.1])).tolist(), target, spp, seed, 0.03, it)
+    b = gpu.fit(ms, key, (b_true + torch.tensor([0.15, -0.2, 0.1])).tolist(), target, spp, seed, 0.03, 300, it)
     assert float((b.cpu() - b_true.cpu()).abs().max()) < 1e-2, (b, b_true)
     p[key] = mi.Color3f(b_true)
     p.update()
-    r = float(_fit(ms, "mat-Floor.brdf_0.roughness.value", 0.55, target, spp, seed, 0.02, it))
+    r = float(gpu.fit(ms, "mat-Floor.brdf_0.roughness.value", 0.55, target, spp, seed, 0.02, 300, it))
     assert abs(r - 0.35) < 2e-2, r
 
 
@@ -416,7 +366,7 @@ def test_full_size_vocalfold_at_depth_3():
     ls = []
     for sign in (1, -1):
         r = (rows + sign * h * v).astype(np.float32)
-        s2 = tm._copy(sd)
+        s2 = copy_desc(sd)
         if sd.n_mat_h > 0:
             scene_desc.set_host_materials(s2, r)
             m2 = None

@@ -15,7 +15,7 @@ import pytest
 
 from fireflies_amd import scenes, scene_desc
 from tests import seam_scenes as ss
-from tests.test_ties_cpu import bits, geom, host_tex
+from tests.support import bits, host_tex, oracle_geom
 
 _CACHE = {}
 
@@ -47,7 +47,7 @@ def _differences(what, got, want):
 def _ray_case(oracle, name):
     def make():
         mesh, eye = ss.RAY_FIXTURES[name]()
-        g, _ = geom(oracle, scenes.SceneData([mesh], None))
+        g, _ = oracle_geom(oracle, scenes.SceneData([mesh], None))
         o, d, k = ss.grazing_rays(eye)
         with oracle.tree_free():
             free = g.trace_rays(o, d)
@@ -90,7 +90,7 @@ def test_trace_rays_with_the_tree_equals_tree_free_on_every_grazing_ray(oracle, 
 def _cam_case(oracle, name):
     def make():
         mesh, eye, fov = ss.CAM_FIXTURES[name]()
-        g, _ = geom(oracle, scenes.SceneData([mesh], None))
+        g, _ = oracle_geom(oracle, scenes.SceneData([mesh], None))
         cams = ss.pitched_cameras(eye, fov=fov)
         with oracle.tree_free():
             free = [g.trace_primary(scene_desc.camera_from_sensor(c), 1, 0, 0) for c in cams]
@@ -136,7 +136,7 @@ def test_stock_scenes_trace_and_render_the_same_with_the_tree_and_tree_free(orac
     render tests every sample against every triangle: 8 spp on all 48 cameras would take minutes).  Only the trace_primary half is shown to
     detect the defect: with the leaf pad's absolute term zeroed it fails with the counts above, and no render comparison of these cameras does."""
     sc, eye, target = ss.stock(name)
-    g, alb = geom(oracle, sc)
+    g, alb = oracle_geom(oracle, sc)
     tex = host_tex(sc)
     bad, lit = [], 0.0
     for k, cam in zip(ss.KS, ss.pitched_cameras(eye, target=target)):

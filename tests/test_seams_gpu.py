@@ -10,8 +10,8 @@ import torch
 from fireflies_amd import ops, scenes, scene_desc
 from tests import seam_scenes as ss
 from tests.conftest import assert_image_close
-from tests.test_hip_parity import _tex, dev, host
-from tests.test_ties_gpu import KNOBS, _Env, bits
+from tests.gpu_support import WALK_KNOBS, Env, dev, grad_close, host, splat_tex
+from tests.support import bits
 
 pytestmark = pytest.mark.gpu
 
@@ -28,7 +28,7 @@ def _need_gpu():
 
 @pytest.fixture(autouse=True)
 def _no_knobs(monkeypatch):
-    for k in KNOBS:
+    for k in WALK_KNOBS:
         monkeypatch.delenv(k, raising=False)
 
 
@@ -75,7 +75,7 @@ def test_k7_every_walk_equals_the_tree_free_oracle_on_the_ridges(oracle, monkeyp
     assert all((w[2][ss.FILM_W:] >= 0).mean() > 0.85 for w in want)  # (what must hit and what may miss: tests/test_seams_cpu.py)
     bad = []
     for walk, env in WALKS.items():
-        with _Env(monkeypatch, env):
+        with Env(monkeypatch, env):
             gd = fresh()
             for k, c, w in zip(ss.KS, cams, want):
                 bad += _k7_findings(f"{walk} k={k:+.2f}", tuple(host(a) for a in gd.trace_primary(c, 1, 0, seed=0)), w)
@@ -109,7 +109,7 @@ def _stock(oracle, name):
     if name not in _STOCK:
         sc, eye, target = ss.stock(name)
         go, fresh, alb = _geoms(oracle, sc)
-        tex = _tex(sc)
+        tex = splat_tex(sc)
         gimg = np.random.default_rng(1).standard_normal((ss.FILM_H, ss.FILM_W, 3)).astype(np.float32)
         cams = dict(zip(ss.KS, ss.pitched_cameras(eye, target=target)))
         ref = {}
@@ -130,18 +130,11 @@ def test_k7_every_walk_equals_the_tree_free_oracle_on_the_stock_scenes(oracle, m
         want = [go.trace_primary(c, 1, 0, 0) for c in cs]
     bad = []
     for walk, env in WALKS.items():
-        with _Env(monkeypatch, env):
+        with Env(monkeypatch, env):
             gd = fresh()
             for k, c, w in zip(cams, cs, want):
                 bad += _k7_findings(f"{walk} k={k:+.2f}", tuple(host(a) for a in gd.trace_primary(c, 1, 0, seed=0)), w)
     assert not bad, f"{name}: {len(bad)} findings:\n  " + "\n  ".join(bad[:16])
-
-
-def _grad_close(gt, gt_o, what):
-    """the bound of tests/test_ties_gpu.py and tests/test_hip_parity.py for a texture gradient: 1e-3 of its scale per texel on all but 2e-4 of them"""
-    gs = float(np.abs(gt_o).max())
-    err = np.abs(gt - gt_o)
-    assert gs > 0 and (err > 1e-3 * gs).mean() <= 2e-4 and err.max() <= 0.1 * gs, (what, float((err > 1e-3 * gs).mean()), float(err.max()) / gs)
 
 
 @pytest.mark.parametrize("name", ["vocalfold", "colon"])
@@ -163,12 +156,12 @@ def test_renders_and_texture_gradients_of_every_walk_equal_each_other_and_the_tr
         first = None
         for walk, env in WALKS.items():
             lane = env.get("FFX_TRAVERSAL") == "lane"
-            with _Env(monkeypatch, env):
+            with Env(monkeypatch, env):
                 gd = fresh()
                 img = gd.render_fwd(sd, dev(alb), tex, 8, seed=3)
                 gt = gd.render_bwd(sd, dev(alb), 8, 3, dev(gimg), deterministic=not lane)
             assert_image_close(host(img), img_o, 8, what=f"{name} k={k:+.2f} {walk}")
-            _grad_close(host(gt), gt_o, f"{name} k={k:+.2f} {walk}")
+            grad_close(host(gt), gt_o, f"{name} k={k:+.2f} {walk}", 2e-4)
             if first is None:
                 first = (walk, img, gt)
             elif lane:
@@ -193,7 +186,7 @@ def test_recorded_vocal_fold_lane_bins_and_the_wide_tree_walk_agree_on_all_67m_r
     cam = scene_desc.camera_from_sensor(sc.camera)
     out = []
     for env in ({}, {"FFX_BINS": "0"}):
-        with _Env(monkeypatch, env):
+        with Env(monkeypatch, env):
             gd = ops.DeviceGeometry(pool, tris, shape, off)
             gd.update(np.tile(np.eye(4, dtype=np.float32), (len(sc.meshes), 1, 1)))
             out.append(gd.trace_primary(cam, 256, 1, seed=1))

@@ -23,11 +23,13 @@ import torch
 from fireflies_amd import ops, scene_desc, scenes
 from tests import stage_scenes as ss
 from tests.conftest import assert_image_close
-from tests.test_hip_parity import _bin_headers, _envelope, _pair, dev, host
+from tests.gpu_support import bin_headers, dev, envelope, grad_close, host, pair
+from tests.support import material_rows
 
 pytestmark = pytest.mark.gpu
 
 FRAC_BOX, FRAC_GAUSS = 1e-3, 0.02  # the widest shares the suite allows a scene with a cast shadow (box) / the small gaussian films
+FRAC_GRAD = 1e-3  # ... and a texture gradient
 KNOBS = ("FFX_ENVELOPE", "FFX_BINS", "FFX_WIDE", "FFX_TRAVERSAL", "FFX_BIN_CAP", "FFX_BIN_TILE", "FFX_BIN_TILE_PROJ", "FFX_BIN_SPOT_N", "FFX_K8_PLAIN",
          "FFX_PIXELS_PER_WAVE", "FFX_HOST_MATERIALS")
 SPOT_GRID_N = "32"  # FFX_BIN_SPOT_N for `facing` where the test is about the spot's grid: the default 128 x 128 tiles overflow there (see test a)
@@ -50,8 +52,6 @@ def _rows(sc, kind):
     """-> (material table, mat_stride, rel): Lambert albedos / random principled rows with one Lambert shape among them (optional lobes: 2e-4)"""
     if kind == "albedo":
         return scenes.flatten(sc)[6], 0, 1e-4
-    from tests.test_bruteforce_cpu import material_rows
-
     mats = material_rows(len(sc.meshes), 23)
     mats[0, 3] = 0.0
     return mats, 16, 2e-4
@@ -72,22 +72,13 @@ def _close(img_d, img_o, spp, frac, rel, what):
     return assert_image_close(img_d, img_o, spp, frac=frac, rel=rel, what=what)
 
 
-def _grad_close(g_d, g_o, what, frac=1e-3):
-    g_d, g_o = np.asarray(g_d), np.asarray(g_o)
-    gs = float(np.abs(g_o).max())
-    assert gs > 0, what
-    err = np.abs(g_d - g_o.reshape(g_d.shape))
-    print(f"GRAD {what}: {float((err > 1e-3 * gs).mean()):.2e} of the texels off by more than 1e-3 of the scale [{frac:g}], worst {err.max() / gs:.2e} [0.1]")
-    assert np.isfinite(g_d).all() and (err > 1e-3 * gs).mean() <= frac and err.max() <= 0.1 * gs, what
-
-
 def _grids_and_envelopes(gd, sd, what):
     """all three grids built with their lists within the capacity, and both emitters' envelopes written by this pose's pre-pass"""
-    hdrs = _bin_headers(gd)
+    hdrs = bin_headers(gd)
     assert all(h[0] == 1 and 0 < h[1] <= h[2] for h in hdrs), (what, hdrs)
     n = int(os.environ.get("FFX_BIN_SPOT_N", ss.spot_grid_n(sd.spot.cutoff_deg)))
-    assert _envelope(gd, 1, 7 * ((sd.proj.tex_w + 15) // 16), 7 * ((sd.proj.tex_h + 15) // 16))[0] == 1, what
-    assert _envelope(gd, 2, 7 * n, 7 * n)[0] == 1, what
+    assert envelope(gd, 1, 7 * ((sd.proj.tex_w + 15) // 16), 7 * ((sd.proj.tex_h + 15) // 16))[0] == 1, what
+    assert envelope(gd, 2, 7 * n, 7 * n)[0] == 1, what
     return hdrs
 
 
@@ -112,7 +103,7 @@ def test_every_direct_light_entry_point_meets_the_oracle_on_the_stages(oracle, s
         sc = ss.side_lit(W, H) if ch == 1 else ss.side_lit(W, H, 104, 88)
     else:
         sc = ss.facing(W, H, cutoff=74.0) if ch == 1 else ss.facing(W, H, 40, 24, cutoff=74.0)
-    go, gd, _ = _pair(oracle, sc)
+    go, gd, _ = pair(oracle, sc)
     mats, stride, rel = _rows(sc, rows)
     sd = _desc(sc, tex_channels=ch, mat_stride=stride, rfilter=None if film == "box" else "gaussian")
     frac = FRAC_BOX if film == "box" else FRAC_GAUSS
@@ -128,15 +119,15 @@ def test_every_direct_light_entry_point_meets_the_oracle_on_the_stages(oracle, s
     spp = 64
     gimg = np.random.default_rng(2).standard_normal((H, W, 3)).astype(np.float32)
     g_o = go.render_bwd(sd, mats, spp, 7, gimg)
-    _grad_close(host(gd.render_bwd(sd, dev(mats), spp, 7, dev(gimg))), g_o, f"{what} render_bwd")
+    grad_close(host(gd.render_bwd(sd, dev(mats), spp, 7, dev(gimg))), g_o, f"{what} render_bwd", FRAC_GRAD)
     cache = torch.zeros(ops.render_cache_bytes_sd(sd, spp), dtype=torch.uint8, device="cuda")
     assert torch.equal(gd.render_fwd(sd, dev(mats), tex, spp, seed=7, cache=cache), img[spp]), f"{what}: the cache-writing forward's image"
     assert ops.render_cache_status(cache)[2] == 0
-    _grad_close(host(gd.render_bwd_cached(sd, dev(mats), cache, spp, dev(gimg), seed=7 if film == "gaussian" else None)), g_o, f"{what} render_bwd_cached")
+    grad_close(host(gd.render_bwd_cached(sd, dev(mats), cache, spp, dev(gimg), seed=7 if film == "gaussian" else None)), g_o, f"{what} render_bwd_cached", FRAC_GRAD)
     if film == "box" or ch == 1:  # (the filtered film folds the adjoint for 1-channel textures only)
         img_f, g_f = gd.render_fwd_adjoint(sd, dev(mats), tex, spp, 7, dev(gimg))
         assert torch.equal(img_f, img[spp]), f"{what}: the fused launch's image"
-        _grad_close(host(g_f), g_o, f"{what} render_fwd_adjoint")
+        grad_close(host(g_f), g_o, f"{what} render_fwd_adjoint", FRAC_GRAD)
 
 
 # ------------------------------------------------------------------ b. the proofs change nothing
@@ -151,7 +142,7 @@ def test_envelopes_bins_and_walks_leave_every_bit_of_the_stages_alone(oracle, st
     if stage == "facing_spot_grid_32":
         monkeypatch.setenv("FFX_BIN_SPOT_N", SPOT_GRID_N)
     spot_served = 0 if stage == "facing" else 1
-    go, gd, _ = _pair(oracle, sc)
+    go, gd, _ = pair(oracle, sc)
     mats, stride, rel = _rows(sc, "material_rows")
     tex = _texture(sc, 1)
     gimg = dev(np.random.default_rng(2).standard_normal((H, W, 3)).astype(np.float32))
@@ -161,7 +152,7 @@ def test_envelopes_bins_and_walks_leave_every_bit_of_the_stages_alone(oracle, st
         gd.update(xf, pose)  # (a fresh pose: nothing of the previous setting's pre-pass is claimed)
         sd = _desc(sc, tex_channels=1, mat_stride=stride, shadows=shadows)
         out = [gd.render_fwd(sd, dev(mats), tex, spp, seed=5) for spp in (64, 16)]
-        state = (_bin_headers(gd), _envelope(gd, 1, 8, 8)[0], _envelope(gd, 2, 8, 8)[0])
+        state = (bin_headers(gd), envelope(gd, 1, 8, 8)[0], envelope(gd, 2, 8, 8)[0])
         return out, gd.render_bwd(_desc(sc, tex_channels=1, mat_stride=stride), dev(mats), 64, 5, gimg), state
 
     ref, g_ref, state = run()
@@ -194,7 +185,7 @@ def test_spot_frames_meet_the_oracle_and_take_the_instance_the_host_proves(oracl
     W, H, spp = 64, 48, 64
     sc = ss.side_lit(W, H)
     frame = ss.spot_frames()[name]
-    go, gd, alb = _pair(oracle, sc)
+    go, gd, alb = pair(oracle, sc)
     tex = _texture(sc, 1)
     sd = _desc(sc, frame, tex_channels=1)
     assert (ss.spot_rigid_measure(sd) < ss.SPOT_RIGID_TOL) == (name in ("rigid", "nearly_rigid", "mirrored"))
@@ -202,7 +193,7 @@ def test_spot_frames_meet_the_oracle_and_take_the_instance_the_host_proves(oracl
     img_d = host(gd.render_fwd(sd, dev(alb), tex, spp, seed=4))
     _close(img_d, img_o, spp, FRAC_BOX, 1e-4, f"spot frame {name}, Lambert")
     gimg = np.random.default_rng(6).standard_normal((H, W, 3)).astype(np.float32)
-    _grad_close(host(gd.render_bwd(sd, dev(alb), spp, 4, dev(gimg))), go.render_bwd(sd, alb, spp, 4, gimg), f"spot frame {name} render_bwd")
+    grad_close(host(gd.render_bwd(sd, dev(alb), spp, 4, dev(gimg))), go.render_bwd(sd, alb, spp, 4, gimg), f"spot frame {name} render_bwd", FRAC_GRAD)
     # ---- the plain-scene instance and its refusal
     rows = np.stack([scenes.material_row(m.albedo, {}) for m in sc.meshes])
     sdp = _desc(sc, frame, tex_channels=1, mat_stride=16, host_mats=rows)
@@ -220,7 +211,7 @@ def test_spot_frames_meet_the_oracle_and_take_the_instance_the_host_proves(oracl
     torch.cuda.synchronize()
     c2 = ops.k8_instance_launches()
     assert (c2[0] - c1[0], c2[1] - c1[1]) == ((1, 0) if plain else (0, 1)) and torch.equal(img_f, img_p)
-    _grad_close(host(g_f), go.render_bwd(sdp, rows, spp, 4, gimg), f"spot frame {name} fused adjoint, plain principled rows")
+    grad_close(host(g_f), go.render_bwd(sdp, rows, spp, 4, gimg), f"spot frame {name} fused adjoint, plain principled rows", FRAC_GRAD)
     if name in ("scaled", "mirrored"):  # (the same cone through the other arm / the other sign of l.x)
         _close(img_d, host(gd.render_fwd(_desc(sc, tex_channels=1), dev(alb), tex, spp, seed=4)), spp, FRAC_BOX, 1e-4, f"spot frame {name} against rigid, Lambert")
         sdr = _desc(sc, tex_channels=1, mat_stride=16, host_mats=rows)
@@ -230,7 +221,7 @@ def test_spot_frames_meet_the_oracle_and_take_the_instance_the_host_proves(oracl
 def test_the_squeezed_cone_is_another_cone(oracle):
     """guards the frames test against a set_spot_frame that writes nothing: the sheared frame's image is not the rigid one's"""
     sc = ss.side_lit(64, 48)
-    go, gd, alb = _pair(oracle, sc)
+    go, gd, alb = pair(oracle, sc)
     tex = _texture(sc, 1)
     a = gd.render_fwd(_desc(sc, None, tex_channels=1), dev(alb), tex, 16, seed=4)
     b = gd.render_fwd(_desc(sc, ss.spot_frames()["squeezed"], tex_channels=1), dev(alb), tex, 16, seed=4)
@@ -246,7 +237,7 @@ def test_spot_grid_at_its_cone_limits(oracle, monkeypatch):
     images are the same bits; and without bins the 75 and 75.5 images are what they were."""
     W, H = 64, 48
     sc = ss.facing(W, H, cutoff=74.0)
-    go, gd, alb = _pair(oracle, sc)
+    go, gd, alb = pair(oracle, sc)
     tex = _texture(sc, 1)
     xf, pose = np.tile(np.eye(4, dtype=np.float32), (len(sc.meshes), 1, 1)), gd._vert_off_host.copy()
     kept = {}
@@ -256,7 +247,7 @@ def test_spot_grid_at_its_cone_limits(oracle, monkeypatch):
         sd.spot.cutoff_deg, sd.spot.beam_width_deg = cutoff, 0.75 * cutoff
         gd.update(xf, pose)
         out = {spp: gd.render_fwd(sd, dev(alb), tex, spp, seed=8) for spp in (64, 16)}
-        hdrs = _bin_headers(gd)
+        hdrs = bin_headers(gd)
         for spp in (64, 16):
             scale, _ = _close(host(out[spp]), go.render_fwd(sd, alb, host(tex), spp, seed=8), spp, FRAC_BOX, 1e-4, f"facing cutoff {cutoff:g} spp={spp} {tag}")
             assert scale > 0.02
@@ -303,7 +294,7 @@ def test_emitters_that_see_nothing_give_an_exactly_black_image(oracle, stage):
     image is the oracle's."""
     W, H = 64, 48
     base = ss.side_lit(W, H) if stage == "side_lit" else ss.facing(W, H, cutoff=74.0)
-    go, gd, alb = _pair(oracle, base)
+    go, gd, alb = pair(oracle, base)
     tex = _texture(base, 1)
     gimg = dev(np.random.default_rng(2).standard_normal((H, W, 3)).astype(np.float32))
     sc = ss.away(base)
@@ -329,7 +320,7 @@ def test_emitters_that_see_nothing_give_an_exactly_black_image(oracle, stage):
         if which == "projector":
             assert torch.equal(g, torch.zeros_like(g))
         else:
-            _grad_close(host(g), go.render_bwd(sd, alb, 64, 3, host(gimg)), f"{stage}, spot away, render_bwd")
+            grad_close(host(g), go.render_bwd(sd, alb, 64, 3, host(gimg)), f"{stage}, spot away, render_bwd", FRAC_GRAD)
 
 
 # ------------------------------------------------------------------ f. one blob, re-prepared between arrangements
@@ -339,7 +330,7 @@ def test_a_blob_re_prepared_between_arrangements_of_the_emitters(oracle):
     the second is the oracle's."""
     W, H = 64, 48
     sc = ss.side_lit(W, H)
-    go, gd, alb = _pair(oracle, sc)
+    go, gd, alb = pair(oracle, sc)
     tex = _texture(sc, 1)
     sd_own, sd_swap = _desc(sc, tex_channels=1), _desc(ss.swapped(sc), tex_channels=1)
     gimg = np.random.default_rng(2).standard_normal((H, W, 3)).astype(np.float32)
@@ -356,4 +347,4 @@ def test_a_blob_re_prepared_between_arrangements_of_the_emitters(oracle):
         _close(host(first), go.render_fwd(sd_own, alb, host(tex), spp, seed=6), spp, FRAC_BOX, 1e-4, f"side_lit own emitters spp={spp}")
         scale, _ = _close(host(second), go.render_fwd(sd_swap, alb, host(tex), spp, seed=6), spp, FRAC_BOX, 1e-4, f"side_lit swapped emitters spp={spp}")
         assert scale > 0.02 and float((second - first).abs().max()) > 0.02 * scale
-        _grad_close(host(g_second), go.render_bwd(sd_swap, alb, spp, 6, gimg), f"side_lit swapped emitters render_bwd spp={spp}")
+        grad_close(host(g_second), go.render_bwd(sd_swap, alb, spp, 6, gimg), f"side_lit swapped emitters render_bwd spp={spp}", FRAC_GRAD)

@@ -6,25 +6,7 @@ import pytest
 
 from fireflies_amd import scenes, scene_desc
 from tests import tie_scenes as ts
-
-
-def bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
-
-
-def geom(oracle, sc, frame=0):
-    pool, tris, shape, off, stride, nfr, alb = scenes.flatten(sc)
-    g = oracle.Geometry(pool, tris, shape, off)
-    g.update(np.tile(np.eye(4, dtype=np.float32), (len(sc.meshes), 1, 1)), (off + np.minimum(frame, nfr - 1) * stride).astype(np.int32))
-    ts.refit_with_marked_pad(sc, [g], np.tile(np.eye(4, dtype=np.float32), (len(sc.meshes), 1, 1)))
-    return g, alb
-
-
-def host_tex(sc, ch=1):
-    if sc.projector is None:
-        return np.zeros((1, 1), np.float32)
-    rng = np.random.default_rng(0)
-    return rng.random((sc.projector.height, sc.projector.width) + ((ch,) if ch > 1 else ()), dtype=np.float32)
+from tests.support import bits, host_tex, oracle_geom
 
 
 @pytest.mark.parametrize("jitter", [0, 1])
@@ -33,7 +15,7 @@ def test_stacked_sheets_tie_on_every_ray_and_the_first_shape_wins(oracle, make, 
     out = []
     for fine_first in (False, True):
         sc = make(fine_first)
-        g, _ = geom(oracle, sc)
+        g, _ = oracle_geom(oracle, sc)
         t, shape, prim = g.trace_primary(scene_desc.camera_from_sensor(sc.camera), 3, jitter, seed=5)
         assert (shape == 0).all(), f"fine_first={fine_first}: {(shape != 0).sum()} rays do not return shape 0"  # (100 % hit, the first mesh everywhere)
         assert (prim >= 0).all() and (prim < sc.meshes[0].tris.shape[0]).all()
@@ -49,7 +31,7 @@ def test_a_coplanar_second_sheet_leaves_the_image_as_it_was(oracle, make, shadow
         sc = make(fine_first)
         imgs = []
         for s in (ts.first_sheet_only(sc), sc):
-            g, alb = geom(oracle, s)
+            g, alb = oracle_geom(oracle, s)
             imgs.append(g.render_fwd(scene_desc.scene_desc(s, shadows=shadows), alb, host_tex(s), 8, seed=3))
         assert imgs[0].min() > 0.01  # (lit everywhere)
         assert np.array_equal(imgs[0], imgs[1]), fine_first
@@ -60,8 +42,8 @@ def test_a_coplanar_second_sheet_leaves_the_image_as_it_was(oracle, make, shadow
 def test_duplicated_meshes_leave_every_hit_as_it_was(oracle, name, jitter):
     sc = ts.dup_cases()[name]()
     cam = scene_desc.camera_from_sensor(sc.camera)
-    t1, s1, p1 = geom(oracle, sc)[0].trace_primary(cam, 1, jitter, seed=5)
-    t2, s2, p2 = geom(oracle, ts.duplicated(sc))[0].trace_primary(cam, 1, jitter, seed=5)
+    t1, s1, p1 = oracle_geom(oracle, sc)[0].trace_primary(cam, 1, jitter, seed=5)
+    t2, s2, p2 = oracle_geom(oracle, ts.duplicated(sc))[0].trace_primary(cam, 1, jitter, seed=5)
     assert (p1 >= 0).mean() > 0.5
     assert (p2 < sc.n_tris).all()
     np.testing.assert_array_equal(bits(t2), bits(t1))
@@ -77,7 +59,7 @@ def test_duplicated_meshes_leave_the_image_as_it_was(oracle, name, shadows):
     tex = host_tex(sc)
     imgs = []
     for s in (sc, dup):
-        g, alb = geom(oracle, s)
+        g, alb = oracle_geom(oracle, s)
         imgs.append(g.render_fwd(scene_desc.scene_desc(s, shadows=shadows), alb, tex, 8, seed=3))
     assert imgs[0].max() > 0.01
     assert np.array_equal(imgs[0], imgs[1])
@@ -89,7 +71,7 @@ def test_seams_of_the_stock_scenes_tie_without_jitter_only(oracle, name):
     sc = ts.seam_cases()[name]()
     rev = ts.reversed_tris(sc)
     cam = scene_desc.camera_from_sensor(sc.camera)
-    g, gr = geom(oracle, sc)[0], geom(oracle, rev)[0]
+    g, gr = oracle_geom(oracle, sc)[0], oracle_geom(oracle, rev)[0]
     t, s, p = g.trace_primary(cam, 1, 0, 0)
     tr, sr, pr = gr.trace_primary(cam, 1, 0, 0)
     np.testing.assert_array_equal(bits(tr), bits(t))
@@ -118,7 +100,7 @@ def test_map_back_inverts_the_relabelling():
 def test_coincident_triangles_beyond_the_wide_walks_budget(oracle, jitter):
     sc = ts.budget()
     assert sc.n_tris == 128  # > FFX_WIDE_MAX_WORK = 96 exact tests (fireflies_amd/csrc/ffx_trace.hip)
-    t, s, p = geom(oracle, sc)[0].trace_primary(scene_desc.camera_from_sensor(sc.camera), 3, jitter, seed=2)
+    t, s, p = oracle_geom(oracle, sc)[0].trace_primary(scene_desc.camera_from_sensor(sc.camera), 3, jitter, seed=2)
     hit = p >= 0
     assert 0.2 < hit.mean() < 0.9
     assert set(np.unique(p[hit])) == {0, 1}
@@ -131,7 +113,7 @@ def test_lattice_rays_reference_equals_the_oracle_bit_for_bit(oracle):
     np.testing.assert_array_equal(n_tied, ties)  # (6 triangles at an interior vertex, 2 on an interior edge)
     assert (ties == 6).sum() == 49 and (ties == 2).sum() > 150
     np.testing.assert_array_equal(t_ref, np.where(d[:, 2] == 4, 1.0, 0.5).astype(np.float32))
-    g, _ = geom(oracle, scenes.SceneData([mesh], None))
+    g, _ = oracle_geom(oracle, scenes.SceneData([mesh], None))
     t, s, p = g.trace_rays(o, d)
     np.testing.assert_array_equal(bits(t), bits(t_ref))
     np.testing.assert_array_equal(p, p_ref)

@@ -8,13 +8,12 @@ import torch
 from fireflies_amd import ops, scenes, scene_desc
 from tests import tie_scenes as ts
 from tests.conftest import assert_image_close
-from tests.test_hip_parity import _pair as _pair_as_built
-from tests.test_hip_parity import _tex, dev, host
+from tests.gpu_support import WALK_KNOBS, Env, dev, host, splat_tex
+from tests.gpu_support import pair as _pair_as_built
+from tests.support import bits
 
 pytestmark = pytest.mark.gpu
 
-KNOBS = ("FFX_BINS", "FFX_WIDE", "FFX_TRAVERSAL", "FFX_BIN_CAP", "FFX_WIDE_BUILD", "FFX_ENVELOPE", "FFX_RENDER_BLOCKS", "FFX_DETERMINISTIC", "FFX_BIN_TILE",
-         "FFX_TREELET_TRIS", "FFX_PIXELS_PER_WAVE", "FFX_XCD_REMAP", "FFX_TILE_BLOCK")
 # the walks of K7 (include/ffx.h): the camera's tile bins; the 64-wide tree walk; the binary octant walk; the per-lane walk; the branch a
 # grid whose lists overflowed takes
 K7_WALKS = {"bins": {}, "wide": {"FFX_BINS": "0"}, "binary": {"FFX_BINS": "0", "FFX_WIDE": "0"}, "lane": {"FFX_TRAVERSAL": "lane"}, "bin_cap_0": {"FFX_BIN_CAP": "0"}}
@@ -27,7 +26,7 @@ def _need_gpu():
 
 @pytest.fixture(autouse=True)
 def _no_knobs(monkeypatch):
-    for k in KNOBS:
+    for k in WALK_KNOBS:
         monkeypatch.delenv(k, raising=False)
 
 
@@ -36,23 +35,6 @@ def _pair(oracle, sc):
     go, gd, alb = _pair_as_built(oracle, sc)
     ts.refit_with_marked_pad(sc, [go, gd], np.tile(np.eye(4, dtype=np.float32), (len(sc.meshes), 1, 1)))
     return go, gd, alb
-
-
-def bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
-
-
-class _Env:
-    def __init__(self, monkeypatch, env):
-        self.mp, self.env = monkeypatch, env
-
-    def __enter__(self):
-        for k, v in self.env.items():
-            self.mp.setenv(k, v)
-
-    def __exit__(self, *exc):
-        for k in self.env:
-            self.mp.delenv(k, raising=False)
 
 
 # ------------------------------------------------------------------ the fixtures and what the rule says about each
@@ -120,7 +102,7 @@ def _k7_problems(oracle, monkeypatch, name, gd, spp, jitter, walks):
     n = cam.width * cam.height * spp
     bad, first = [], None
     for walk, env in walks.items():
-        with _Env(monkeypatch, env):
+        with Env(monkeypatch, env):
             t, s, p = (host(a) for a in gd.trace_primary(cam, spp, jitter, seed=5))
         assert t.shape == (n,) and s.shape == (n,) and p.shape == (n,)
         msg = expect(t, s, p)
@@ -167,7 +149,7 @@ def test_k7_relabelled_seams_give_the_oracles_pick_on_the_tied_rays(oracle, monk
     cam = scene_desc.camera_from_sensor(sc.camera)
     bad = []
     for walk, env in K7_WALKS.items():
-        with _Env(monkeypatch, env):
+        with Env(monkeypatch, env):
             p = host(gd.trace_primary(cam, 1, 0, seed=5)[2])
         back = ts.map_back(p, sc)
         if not np.array_equal(back[tied], back_o[tied]):
@@ -224,7 +206,7 @@ def _render_pair(oracle, name):
         dup = ts.duplicated(sc)
         _, g1, a1 = _pair(oracle, sc)
         go2, g2, a2 = _pair(oracle, dup)
-        _RENDER[name] = (sc, dup, g1, dev(a1), g2, dev(a2), go2, a2, _tex(sc) if sc.projector is not None else None)
+        _RENDER[name] = (sc, dup, g1, dev(a1), g2, dev(a2), go2, a2, splat_tex(sc) if sc.projector is not None else None)
     return _RENDER[name]
 
 
@@ -237,7 +219,7 @@ def test_render_fwd_does_not_see_an_exact_copy_of_every_mesh(oracle, monkeypatch
     sc, dup, g1, a1, g2, a2, go2, alb2, tex = _render_pair(oracle, name)
     sd1, sd2 = scene_desc.scene_desc(sc, shadows=shadows), scene_desc.scene_desc(dup, shadows=shadows)
     for spp in (5, 70):
-        with _Env(monkeypatch, RENDER_WALKS[walk]):
+        with Env(monkeypatch, RENDER_WALKS[walk]):
             one = g1.render_fwd(sd1, a1, tex, spp, seed=3)
             two = g2.render_fwd(sd2, a2, tex, spp, seed=3)
         assert float(one.max()) > 0.01
@@ -258,7 +240,7 @@ def test_renders_do_not_see_a_coplanar_second_sheet(oracle, monkeypatch, make, w
         _, g1, a1 = _pair(oracle, one)
         _, g2, a2 = _pair(oracle, sc)
         sd1, sd2 = scene_desc.scene_desc(one, shadows=True), scene_desc.scene_desc(sc, shadows=True)
-        with _Env(monkeypatch, RENDER_WALKS[walk]):
+        with Env(monkeypatch, RENDER_WALKS[walk]):
             for spp in (5, 70):
                 i1, i2 = g1.render_fwd(sd1, dev(a1), None, spp, seed=3), g2.render_fwd(sd2, dev(a2), None, spp, seed=3)
                 assert float(i1.min()) > 0.01
