@@ -801,6 +801,102 @@ struct SampleTerms {
 
 __device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
+// ---- the projector texture at a sample and its adjoint: the pieces the render kernels and their adjoints below are built from ----
+// a sample's four bilinear taps: the float offsets of texels (x0, y0), (x1, y0), (x0, y1), (x1, y1) in a tw-wide, tc-channel texture, and their weights
+struct Taps { size_t o00, o01, o10, o11; float wx0, wx1, wy0, wy1; };
+__device__ __forceinline__ Taps make_taps(int x0, int x1, int y0, int y1, float wx0, float wx1, float wy0, float wy1, int tw, int tc) {
+  return {((size_t)y0 * tw + x0) * tc, ((size_t)y0 * tw + x1) * tc, ((size_t)y1 * tw + x0) * tc, ((size_t)y1 * tw + x1) * tc, wx0, wx1, wy0, wy1};
+}
+__device__ __forceinline__ Taps sample_taps(const SampleTerms &st, int tw, int tc) { return make_taps(st.ix0, st.ix1, st.iy0, st.iy1, st.wx0, st.wx1, st.wy0, st.wy1, tw, tc); }
+// (v * wy) * wx to each of the four texels: emit(texel offset, ch, value)
+template <class E>
+__device__ __forceinline__ void taps_scatter(const Taps &t, int ch, float v, E &&emit) {
+  emit(t.o00, ch, v * t.wy0 * t.wx0);
+  emit(t.o01, ch, v * t.wy0 * t.wx1);
+  emit(t.o10, ch, v * t.wy1 * t.wx0);
+  emit(t.o11, ch, v * t.wy1 * t.wx1);
+}
+struct AtomicInto { // the usual emitter: a float atomic into the gradient
+  float *g;
+  __device__ __forceinline__ void operator()(size_t o, int ch, float v) const { atomicAdd(g + o + ch, v); }
+};
+// the projector's texture value at a sample, per colour channel: wy0 * (wx0 * t00 + wx1 * t01) + wy1 * (wx0 * t10 + wx1 * t11), times the projector's
+// colour for one-channel textures (ONE_CH: the caller knows it is one)
+template <bool ONE_CH = false>
+__device__ __forceinline__ void proj_tex_value(const ShadeK &c, const SampleTerms &st, const float *__restrict__ tex, float (&tv)[3]) {
+  const int tc = ONE_CH ? 1 : c.tc;
+  const size_t o00 = ((size_t)st.iy0 * c.tw + st.ix0) * tc, o01 = ((size_t)st.iy0 * c.tw + st.ix1) * tc;
+  const size_t o10 = ((size_t)st.iy1 * c.tw + st.ix0) * tc, o11 = ((size_t)st.iy1 * c.tw + st.ix1) * tc;
+  const float v = st.wy0 * (st.wx0 * tex[o00] + st.wx1 * tex[o01]) + st.wy1 * (st.wx0 * tex[o10] + st.wx1 * tex[o11]);
+  if (tc == 1) {
+    tv[0] = v * c.p_color[0]; tv[1] = v * c.p_color[1]; tv[2] = v * c.p_color[2];
+  } else {
+    tv[0] = v;
+#pragma unroll
+    for (int ch = 1; ch < 3; ++ch) tv[ch] = st.wy0 * (st.wx0 * tex[o00 + ch] + st.wx1 * tex[o01 + ch]) + st.wy1 * (st.wx0 * tex[o10 + ch] + st.wx1 * tex[o11 + ch]);
+  }
+}
+// a sample's colour from its terms: alb * (spot + tv * proj_fac) + (spot_b + tv * proj_fac_b), the second bracket only where rows exist (`rows`)
+template <bool ONE_CH = false>
+__device__ __forceinline__ void sample_colour(const ShadeK &c, const SampleTerms &st, const float *__restrict__ tex, const float *alb, bool rows, float (&L)[3]) {
+  float r[3] = {st.spot[0], st.spot[1], st.spot[2]}, b[3] = {st.spot_b[0], st.spot_b[1], st.spot_b[2]};
+  if (st.has_proj) {
+    float tv[3];
+    proj_tex_value<ONE_CH>(c, st, tex, tv);
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) {
+      r[ch] += tv[ch] * st.proj_fac;
+      if (rows) b[ch] += tv[ch] * st.proj_fac_b;
+    }
+  }
+#pragma unroll
+  for (int ch = 0; ch < 3; ++ch) {
+    L[ch] = alb[ch] * r[ch];
+    if (rows) L[ch] += b[ch];
+  }
+}
+// what a one-channel texture's adjoint takes from a pixel's gradient g: sum over the channels of g * alb * colour, and of g * colour; left to right
+__device__ __forceinline__ float g_alb_colour(const float (&g)[3], const float *alb, const float (&col)[3]) {
+  return g[0] * alb[0] * col[0] + g[1] * alb[1] * col[1] + g[2] * alb[2] * col[2];
+}
+__device__ __forceinline__ float g_colour(const float (&g)[3], const float (&col)[3]) { return g[0] * col[0] + g[1] * col[1] + g[2] * col[2]; }
+// the value a sample sends to its taps.  One channel: g_alb_colour * fac * inv_spp, plus g_colour * fac_b * inv_spp where fac_b != 0
+__device__ __forceinline__ float tap_value_1ch(const float (&g)[3], const float *alb, const float (&col)[3], float fac, float fac_b, float inv_spp) {
+  float ws = g_alb_colour(g, alb, col) * fac * inv_spp;
+  if (fac_b != 0.f) ws += g_colour(g, col) * fac_b * inv_spp;
+  return ws;
+}
+// ... three channels, per channel: g * alb * fac * inv_spp, plus g * fac_b * inv_spp where fac_b != 0
+__device__ __forceinline__ float tap_value_3ch(float g, float alb, float fac, float fac_b, float inv_spp) {
+  float ws = g * alb * fac * inv_spp;
+  if (fac_b != 0.f) ws += g * fac_b * inv_spp;
+  return ws;
+}
+// a sample's gradient into its four texels through `emit`: one value for a one-channel texture, one per channel for three; skip_zero: no emit of a zero value
+template <class E>
+__device__ __forceinline__ void sample_scatter(const Taps &t, int tc, const float (&g)[3], const float *alb, const float (&col)[3], float fac, float fac_b,
+                                               float inv_spp, bool skip_zero, E &&emit) {
+  if (tc == 1) {
+    const float ws = tap_value_1ch(g, alb, col, fac, fac_b, inv_spp);
+    if (!skip_zero || ws != 0.f) taps_scatter(t, 0, ws, emit);
+  } else {
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) {
+      const float ws = tap_value_3ch(g[ch], alb[ch], fac, fac_b, inv_spp);
+      if (!skip_zero || ws != 0.f) taps_scatter(t, ch, ws, emit);
+    }
+  }
+}
+// the value a footprint element (weights w, and wb of the rows' base-colour-free part) sends to its texel.  One channel, with the pixel's factors
+// ws = g_alb_colour * inv_spp and wsb = g_colour * inv_spp: ws * w, plus wsb * wb where wb != 0
+__device__ __forceinline__ float foot_value_1ch(float ws, float wsb, float w, float wb) {
+  float val = ws * w;
+  if (wb != 0.f) val += wsb * wb;
+  return val;
+}
+// ... three channels, per channel: g * alb * inv_spp * w + g * inv_spp * wb
+__device__ __forceinline__ float foot_value_3ch(float g, float alb, float inv_spp, float w, float wb) { return g * alb * inv_spp * w + g * inv_spp * wb; }
+
 // what a path vertex needs beyond the emitters' terms: the lifted origin of its secondary ray, its normals, whether the row's base
 // colour came from a texture.  ok = 0: no vertex (a miss, a degenerate triangle)
 struct PathVtx { v3 Po, ng, ns; int textured, ok; };
@@ -1007,42 +1103,11 @@ __global__ void __launch_bounds__(TR_BLOCK)
       SampleTerms st;
       shade_sample(kernarg_shade(), nodes, recs, nrec, o, d, nt, ft, st, s_dyn + threadIdx.x, TR_BLOCK);
       if (!st.hit) continue;
-      float r0 = st.spot[0], r1 = st.spot[1], r2 = st.spot[2];
-      float b0 = st.spot_b[0], b1 = st.spot_b[1], b2 = st.spot_b[2];
-      if (st.has_proj) {
-        const int tc = c.tc;
-        size_t o00 = ((size_t)st.iy0 * c.tw + st.ix0) * tc, o01 = ((size_t)st.iy0 * c.tw + st.ix1) * tc;
-        size_t o10 = ((size_t)st.iy1 * c.tw + st.ix0) * tc, o11 = ((size_t)st.iy1 * c.tw + st.ix1) * tc;
-        if (tc == 1) {
-          float tv = st.wy0 * (st.wx0 * tex[o00] + st.wx1 * tex[o01]) + st.wy1 * (st.wx0 * tex[o10] + st.wx1 * tex[o11]);
-          r0 += tv * c.p_color[0] * st.proj_fac;
-          r1 += tv * c.p_color[1] * st.proj_fac;
-          r2 += tv * c.p_color[2] * st.proj_fac;
-          b0 += tv * c.p_color[0] * st.proj_fac_b;
-          b1 += tv * c.p_color[1] * st.proj_fac_b;
-          b2 += tv * c.p_color[2] * st.proj_fac_b;
-        } else {
-          float tv0 = st.wy0 * (st.wx0 * tex[o00] + st.wx1 * tex[o01]) + st.wy1 * (st.wx0 * tex[o10] + st.wx1 * tex[o11]);
-          float tv1 = st.wy0 * (st.wx0 * tex[o00 + 1] + st.wx1 * tex[o01 + 1]) + st.wy1 * (st.wx0 * tex[o10 + 1] + st.wx1 * tex[o11 + 1]);
-          float tv2 = st.wy0 * (st.wx0 * tex[o00 + 2] + st.wx1 * tex[o01 + 2]) + st.wy1 * (st.wx0 * tex[o10 + 2] + st.wx1 * tex[o11 + 2]);
-          r0 += tv0 * 1.0f * st.proj_fac;
-          r1 += tv1 * 1.0f * st.proj_fac;
-          r2 += tv2 * 1.0f * st.proj_fac;
-          b0 += tv0 * 1.0f * st.proj_fac_b;
-          b1 += tv1 * 1.0f * st.proj_fac_b;
-          b2 += tv2 * 1.0f * st.proj_fac_b;
-        }
-      }
-      const float *alb = st.base; // (the shape's row, or its base-colour texture at the hit)
-      if (c.mat_stride == 3) {
-        acc0 += alb[0] * r0;
-        acc1 += alb[1] * r1;
-        acc2 += alb[2] * r2;
-      } else {
-        acc0 += alb[0] * r0 + b0;
-        acc1 += alb[1] * r1 + b1;
-        acc2 += alb[2] * r2 + b2;
-      }
+      float L[3];
+      sample_colour(c, st, tex, st.base, c.mat_stride != 3, L); // (st.base: the shape's row, or its base-colour texture at the hit)
+      acc0 += L[0];
+      acc1 += L[1];
+      acc2 += L[2];
     }
   }
   if (wave > 0) {
@@ -1085,8 +1150,8 @@ __global__ void __launch_bounds__(TR_BLOCK)
   int px = (tile % tiles_x) * 8 + (lane & 7), py = (tile / tiles_x) * 8 + (lane >> 3);
   if (!(tile < n_tiles && px < W && py < H)) return;
   const uint32_t pix = (uint32_t)py * (uint32_t)W + (uint32_t)px;
-  const float g0 = gimg[(size_t)pix * 3], g1 = gimg[(size_t)pix * 3 + 1], g2 = gimg[(size_t)pix * 3 + 2];
-  if (g0 == 0.f && g1 == 0.f && g2 == 0.f) return;
+  const float g[3] = {gimg[(size_t)pix * 3], gimg[(size_t)pix * 3 + 1], gimg[(size_t)pix * 3 + 2]};
+  if (g[0] == 0.f && g[1] == 0.f && g[2] == 0.f) return;
   const float inv_spp = 1.0f / (float)spp;
   const int tc = c.tc;
   for (int s = wave; s < spp; s += TR_BLOCK / 64) {
@@ -1099,28 +1164,7 @@ __global__ void __launch_bounds__(TR_BLOCK)
     SampleTerms st;
     shade_sample(kernarg_shade(), nodes, recs, nrec, o, d, nt, ft, st, s_dyn + threadIdx.x, TR_BLOCK);
     if (!st.hit || !st.has_proj) continue;
-    const float *alb = st.base;
-    size_t o00 = ((size_t)st.iy0 * c.tw + st.ix0) * tc, o01 = ((size_t)st.iy0 * c.tw + st.ix1) * tc;
-    size_t o10 = ((size_t)st.iy1 * c.tw + st.ix0) * tc, o11 = ((size_t)st.iy1 * c.tw + st.ix1) * tc;
-    if (tc == 1) {
-      float ws = (g0 * alb[0] * c.p_color[0] + g1 * alb[1] * c.p_color[1] + g2 * alb[2] * c.p_color[2]) * st.proj_fac * inv_spp;
-      if (st.proj_fac_b != 0.f) ws += (g0 * c.p_color[0] + g1 * c.p_color[1] + g2 * c.p_color[2]) * st.proj_fac_b * inv_spp;
-      atomicAdd(gtex + o00, ws * st.wy0 * st.wx0);
-      atomicAdd(gtex + o01, ws * st.wy0 * st.wx1);
-      atomicAdd(gtex + o10, ws * st.wy1 * st.wx0);
-      atomicAdd(gtex + o11, ws * st.wy1 * st.wx1);
-    } else {
-      const float gg[3] = {g0, g1, g2};
-#pragma unroll
-      for (int ch = 0; ch < 3; ++ch) {
-        float ws = gg[ch] * alb[ch] * st.proj_fac * inv_spp;
-        if (st.proj_fac_b != 0.f) ws += gg[ch] * st.proj_fac_b * inv_spp;
-        atomicAdd(gtex + o00 + ch, ws * st.wy0 * st.wx0);
-        atomicAdd(gtex + o01 + ch, ws * st.wy0 * st.wx1);
-        atomicAdd(gtex + o10 + ch, ws * st.wy1 * st.wx0);
-        atomicAdd(gtex + o11 + ch, ws * st.wy1 * st.wx1);
-      }
-    }
+    sample_scatter(sample_taps(st, c.tw, tc), tc, g, st.base, c.p_color, st.proj_fac, st.proj_fac_b, inv_spp, false, AtomicInto{gtex});
   }
 }
 
@@ -2848,6 +2892,25 @@ __device__ __forceinline__ float4 rf_window_g(const float4 *__restrict__ G, int 
   if (!live || lane >= 25 || tx < 0 || tx >= W || ty < 0 || ty >= H) return make_float4(0.f, 0.f, 0.f, 0.f);
   return G[(size_t)ty * W + tx];
 }
+// the adjoint weight of a sample with jitter (jx, jy): box: g; RF: lanes 0..24 hold G of the pixel's window (rf_window_g) and q is the sum over the
+// window of filter weight x G — window order n = 0..24, w = gx[n % 5] * gy[n / 5], one fused multiply-add per channel and n
+template <bool RF>
+__device__ __forceinline__ void sample_adjoint(const RfC &rf, float jx, float jy, const float (&g)[3], float (&q)[3]) {
+  q[0] = g[0]; q[1] = g[1]; q[2] = g[2];
+  if (RF) { // (all lanes: the readlanes need the whole wave)
+    float gx[5], gy[5];
+    rf_weights(rf, jx, gx);
+    rf_weights(rf, jy, gy);
+    q[0] = q[1] = q[2] = 0.f;
+#pragma unroll
+    for (int n = 0; n < 25; ++n) {
+      const float w = gx[n % 5] * gy[n / 5];
+      q[0] = __builtin_fmaf(w, __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(g[0]), n)), q[0]);
+      q[1] = __builtin_fmaf(w, __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(g[1]), n)), q[1]);
+      q[2] = __builtin_fmaf(w, __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(g[2]), n)), q[2]);
+    }
+  }
+}
 
 #ifndef FFX_PK_MAT_WAVES
 #define FFX_PK_MAT_WAVES 7 // material rows: 75 VGPRs (72 at this setting without spills; 8 waves spill 4)
@@ -3015,25 +3078,11 @@ __global__ void __launch_bounds__(PK_BLOCK) __attribute__((amdgpu_waves_per_eu(M
           if constexpr (RF && ADJ) {
             const ShadeK &cr = kernarg_shade();
             const float4 gw = rf_window_g(reinterpret_cast<const float4 *>(adj_gimg), px[0], py[0], W, H, lane, live[0]);
-            float jx, jy, gx[5], gy[5];
+            const float gwin[3] = {gw.x, gw.y, gw.z};
+            float jx, jy, a[3];
             sample_jitter(seed_key, pix[0] * (uint32_t)spp + (uint32_t)s, jx, jy);
-            rf_weights(cr.rf, jx, gx);
-            rf_weights(cr.rf, jy, gy);
-            float a0 = 0.f, a1 = 0.f, a2 = 0.f;
-#pragma unroll
-            for (int n = 0; n < 25; ++n) {
-              const float w = gx[n % 5] * gy[n / 5];
-              a0 = __builtin_fmaf(w, __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(gw.x), n)), a0);
-              a1 = __builtin_fmaf(w, __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(gw.y), n)), a1);
-              a2 = __builtin_fmaf(w, __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(gw.z), n)), a2);
-            }
-            if (lit) { // (the arithmetic of k_render_bwd_pk's scatter, 1-channel texture)
-              const float *alb = mat_table(cr) + MS * st[0].shape;
-              rf_pf = (a0 * alb[0] * cr.p_color[0] + a1 * alb[1] * cr.p_color[1] + a2 * alb[2] * cr.p_color[2]) * st[0].proj_fac;
-              if constexpr (MAT) {
-                if (st[0].proj_fac_b != 0.f) rf_pf += (a0 * cr.p_color[0] + a1 * cr.p_color[1] + a2 * cr.p_color[2]) * st[0].proj_fac_b;
-              }
-            }
+            sample_adjoint<true>(cr.rf, jx, jy, gwin, a);
+            if (lit) rf_pf = tap_value_1ch(a, mat_table(cr) + MS * st[0].shape, cr.p_color, st[0].proj_fac, MAT ? st[0].proj_fac_b : 0.f, 1.0f); // (the weight inside G normalises)
           }
           if (in_win) {
             const float pf = (RF && ADJ) ? rf_pf : st[0].proj_fac;
@@ -3053,7 +3102,9 @@ __global__ void __launch_bounds__(PK_BLOCK) __attribute__((amdgpu_waves_per_eu(M
             }
           }
           const wmask straym = wballot(lit && !in_win);
-          if (ADJ && straym != 0ull) { // fused adjoint: the four taps of a sample that does not fit the footprint, at once (k9_stray's arithmetic)
+          // fused adjoint: the four taps of a sample that does not fit the footprint, at once.  sample_scatter's values (tap_value_1ch / tap_value_3ch, times
+          // wy, times wx, zero values skipped), written out: as a call, with the texel offsets scaled by a run-time tc, the ADJ instances spill other scalars
+          if (ADJ && straym != 0ull) {
             if constexpr (RF) {
               if (lit && !in_win && rf_pf != 0.f) {
                 const ShadeK &ca = kernarg_shade();
@@ -3120,51 +3171,10 @@ __global__ void __launch_bounds__(PK_BLOCK) __attribute__((amdgpu_waves_per_eu(M
       const ShadeK &ct = kernarg_shade(); // phase: texture gather and accumulation
 #pragma unroll
       for (int r = 0; r < R; ++r) {
-        float c0 = 0.f, c1 = 0.f, c2 = 0.f; // this pass's contribution of the lane's sample
-        if (st[r].hit) {
-        float r0 = st[r].spot[0], r1 = st[r].spot[1], r2 = st[r].spot[2];
-        float b0 = st[r].spot_b[0], b1 = st[r].spot_b[1], b2 = st[r].spot_b[2]; // (MAT only: dead otherwise)
-        if (st[r].has_proj) {
-          const int tc = PLAIN ? 1 : ct.tc;
-          size_t o00 = ((size_t)st[r].iy0 * ct.tw + st[r].ix0) * tc, o01 = ((size_t)st[r].iy0 * ct.tw + st[r].ix1) * tc;
-          size_t o10 = ((size_t)st[r].iy1 * ct.tw + st[r].ix0) * tc, o11 = ((size_t)st[r].iy1 * ct.tw + st[r].ix1) * tc;
-          const float wx0 = st[r].wx0, wx1 = st[r].wx1, wy0 = st[r].wy0, wy1 = st[r].wy1, pf = st[r].proj_fac, pb = st[r].proj_fac_b;
-          if (tc == 1) {
-            float tv = wy0 * (wx0 * tex[o00] + wx1 * tex[o01]) + wy1 * (wx0 * tex[o10] + wx1 * tex[o11]);
-            r0 += tv * ct.p_color[0] * pf;
-            r1 += tv * ct.p_color[1] * pf;
-            r2 += tv * ct.p_color[2] * pf;
-            if constexpr (MAT) {
-              b0 += tv * ct.p_color[0] * pb;
-              b1 += tv * ct.p_color[1] * pb;
-              b2 += tv * ct.p_color[2] * pb;
-            }
-          } else {
-            float tv0 = wy0 * (wx0 * tex[o00] + wx1 * tex[o01]) + wy1 * (wx0 * tex[o10] + wx1 * tex[o11]);
-            float tv1 = wy0 * (wx0 * tex[o00 + 1] + wx1 * tex[o01 + 1]) + wy1 * (wx0 * tex[o10 + 1] + wx1 * tex[o11 + 1]);
-            float tv2 = wy0 * (wx0 * tex[o00 + 2] + wx1 * tex[o01 + 2]) + wy1 * (wx0 * tex[o10 + 2] + wx1 * tex[o11 + 2]);
-            r0 += tv0 * 1.0f * pf;
-            r1 += tv1 * 1.0f * pf;
-            r2 += tv2 * 1.0f * pf;
-            if constexpr (MAT) {
-              b0 += tv0 * 1.0f * pb;
-              b1 += tv1 * 1.0f * pb;
-              b2 += tv2 * 1.0f * pb;
-            }
-          }
-        }
-        if constexpr (TEX) { // (a textured row: the sample's own base colour; zero where nothing lit it, and then r0..2 are zero too)
-          c0 = st[r].base[0] * r0;
-          c1 = st[r].base[1] * r1;
-          c2 = st[r].base[2] * r2;
-        } else {
-        const float *alb = mat_table(ct) + MS * st[r].shape;
-        c0 = alb[0] * r0;
-        c1 = alb[1] * r1;
-        c2 = alb[2] * r2;
-        }
-        if constexpr (MAT) { c0 += b0; c1 += b1; c2 += b2; }
-        }
+        float L[3] = {0.f, 0.f, 0.f}; // this pass's contribution of the lane's sample
+        // (a textured row: the sample's own base colour; zero where nothing lit it, and then its terms are zero too)
+        if (st[r].hit) sample_colour<PLAIN>(ct, st[r], tex, TEX ? st[r].base : mat_table(ct) + MS * st[r].shape, MAT, L);
+        float c0 = L[0], c1 = L[1], c2 = L[2];
         if constexpr (RF) {
           // the lane's sample -> its 25 window entries (weights from the jitter, re-derived: two hashes instead of two live registers)
           // (re-derived: two hashes instead of two live registers — parking the jitter in LDS instead was tried in round 5: the film's fold keeps
@@ -3233,10 +3243,10 @@ __global__ void __launch_bounds__(PK_BLOCK) __attribute__((amdgpu_waves_per_eu(M
         if (w != 0.f) atomicAdd(adj_gtex + (size_t)(foy + ey) * ca.tw + (fox + ex), w);
       }
     }
-    if (ADJ && !RF && live[0] && (fox >= 0 || adj_dot)) { // fused adjoint: the pixel's footprint x (gimg . albedo . colour) / spp goes straight into gtex (K9's arithmetic)
+    if (ADJ && !RF && live[0] && (fox >= 0 || adj_dot)) { // fused adjoint: the pixel's footprint x (gimg . albedo . colour) / spp goes straight into gtex
       __builtin_amdgcn_wave_barrier();
       const ShadeK &ca = kernarg_shade();
-      const float g0 = adj_gimg[(size_t)pix[0] * 3], g1 = adj_gimg[(size_t)pix[0] * 3 + 1], g2 = adj_gimg[(size_t)pix[0] * 3 + 2];
+      const float g[3] = {adj_gimg[(size_t)pix[0] * 3], adj_gimg[(size_t)pix[0] * 3 + 1], adj_gimg[(size_t)pix[0] * 3 + 2]};
       if (fox >= 0) {
         int lw = lane;
         asm volatile("" : "+v"(lw));
@@ -3249,21 +3259,19 @@ __global__ void __launch_bounds__(PK_BLOCK) __attribute__((amdgpu_waves_per_eu(M
           const int tx = fox + ex, ty = foy + ey;
           if (w != 0.f || wb != 0.f) {
             if (PLAIN || ca.tc == 1) {
-              const float wsv = (g0 * alb[0] * ca.p_color[0] + g1 * alb[1] * ca.p_color[1] + g2 * alb[2] * ca.p_color[2]) * inv_spp_u;
-              float val = wsv * w;
-              if (wb != 0.f) val += (g0 * ca.p_color[0] + g1 * ca.p_color[1] + g2 * ca.p_color[2]) * inv_spp_u * wb;
+              const float val = foot_value_1ch(g_alb_colour(g, alb, ca.p_color) * inv_spp_u, g_colour(g, ca.p_color) * inv_spp_u, w, wb);
               if (val != 0.f) atomicAdd(adj_gtex + (size_t)ty * ca.tw + tx, val);
             } else {
               float *t = adj_gtex + ((size_t)ty * ca.tw + tx) * 3;
-              if (g0 != 0.f) atomicAdd(t, g0 * alb[0] * inv_spp_u * w + g0 * inv_spp_u * wb);
-              if (g1 != 0.f) atomicAdd(t + 1, g1 * alb[1] * inv_spp_u * w + g1 * inv_spp_u * wb);
-              if (g2 != 0.f) atomicAdd(t + 2, g2 * alb[2] * inv_spp_u * w + g2 * inv_spp_u * wb);
+#pragma unroll
+              for (int ch = 0; ch < 3; ++ch)
+                if (g[ch] != 0.f) atomicAdd(t + ch, foot_value_3ch(g[ch], alb[ch], inv_spp_u, w, wb));
             }
           }
         }
       }
       if (adj_dot && lane == 0) { // <gimg, img> of this pixel into one of FFX_ADJOINT_DOT_SLOTS partial sums (256 cache lines: a quarter of a
-        const float dd = g0 * fin0 + g1 * fin1 + g2 * fin2; // million atomics over the launch meet ~1000 times per line, not on one address)
+        const float dd = g[0] * fin0 + g[1] * fin1 + g[2] * fin2; // million atomics over the launch meet ~1000 times per line, not on one address)
         if (dd != 0.f) atomicAdd(adj_dot + (pix[0] & (FFX_ADJOINT_DOT_SLOTS - 1)), dd);
       }
     }
@@ -3335,52 +3343,10 @@ __global__ void __launch_bounds__(PK_BLOCK) __attribute__((amdgpu_waves_per_eu(M
   }
   SampleTerms st;
   shade_sample_pk<WIDE, MATM>(nodes, recs, arecs, astride, ws, s_wstack, active, o, d, nt, ft, st, nrec, gn, bx0, by0, tex, 1 << bw_log2, 1 << bh_log2);
-  const ShadeK &ct = kernarg_shade(); // texture gather and the sample's colour: k_render_fwd_pk's arithmetic
-  float c0 = 0.f, c1 = 0.f, c2 = 0.f;
-  if (st.hit) {
-    float r0 = st.spot[0], r1 = st.spot[1], r2 = st.spot[2];
-    float b0 = st.spot_b[0], b1 = st.spot_b[1], b2 = st.spot_b[2]; // (MAT only: dead otherwise)
-    if (st.has_proj) {
-      const int tc = ct.tc;
-      const size_t o00 = ((size_t)st.iy0 * ct.tw + st.ix0) * tc, o01 = ((size_t)st.iy0 * ct.tw + st.ix1) * tc;
-      const size_t o10 = ((size_t)st.iy1 * ct.tw + st.ix0) * tc, o11 = ((size_t)st.iy1 * ct.tw + st.ix1) * tc;
-      const float wx0 = st.wx0, wx1 = st.wx1, wy0 = st.wy0, wy1 = st.wy1, pf = st.proj_fac, pb = st.proj_fac_b;
-      if (tc == 1) {
-        const float tv = wy0 * (wx0 * tex[o00] + wx1 * tex[o01]) + wy1 * (wx0 * tex[o10] + wx1 * tex[o11]);
-        r0 += tv * ct.p_color[0] * pf;
-        r1 += tv * ct.p_color[1] * pf;
-        r2 += tv * ct.p_color[2] * pf;
-        if constexpr (MAT) {
-          b0 += tv * ct.p_color[0] * pb;
-          b1 += tv * ct.p_color[1] * pb;
-          b2 += tv * ct.p_color[2] * pb;
-        }
-      } else {
-        const float tv0 = wy0 * (wx0 * tex[o00] + wx1 * tex[o01]) + wy1 * (wx0 * tex[o10] + wx1 * tex[o11]);
-        const float tv1 = wy0 * (wx0 * tex[o00 + 1] + wx1 * tex[o01 + 1]) + wy1 * (wx0 * tex[o10 + 1] + wx1 * tex[o11 + 1]);
-        const float tv2 = wy0 * (wx0 * tex[o00 + 2] + wx1 * tex[o01 + 2]) + wy1 * (wx0 * tex[o10 + 2] + wx1 * tex[o11 + 2]);
-        r0 += tv0 * 1.0f * pf;
-        r1 += tv1 * 1.0f * pf;
-        r2 += tv2 * 1.0f * pf;
-        if constexpr (MAT) {
-          b0 += tv0 * 1.0f * pb;
-          b1 += tv1 * 1.0f * pb;
-          b2 += tv2 * 1.0f * pb;
-        }
-      }
-    }
-    if constexpr (TEX) {
-      c0 = st.base[0] * r0;
-      c1 = st.base[1] * r1;
-      c2 = st.base[2] * r2;
-    } else {
-      const float *alb = mat_table(ct) + MS * st.shape;
-      c0 = alb[0] * r0;
-      c1 = alb[1] * r1;
-      c2 = alb[2] * r2;
-    }
-    if constexpr (MAT) { c0 += b0; c1 += b1; c2 += b2; }
-  }
+  const ShadeK &ct = kernarg_shade();
+  float L[3] = {0.f, 0.f, 0.f};
+  if (st.hit) sample_colour(ct, st, tex, TEX ? st.base : mat_table(ct) + MS * st.shape, MAT, L);
+  float c0 = L[0], c1 = L[1], c2 = L[2];
   if constexpr (RF) {
     float jx, jy, gx[5], gy[5];
     sample_jitter(seed_key, pix * (uint32_t)spp + (uint32_t)sl, jx, jy);
@@ -3506,47 +3472,15 @@ __global__ void __launch_bounds__(PK_BLOCK) __attribute__((amdgpu_waves_per_eu(M
           // every lane's sample gathers its own gradient through the filter's weights: window pixel n's G sits in lane n (re-read: cached),
           // broadcast with readlane and weighted per lane — window order, fused multiply-adds, as the oracle
           const float4 gw = rf_window_g(reinterpret_cast<const float4 *>(gimg), px[r], py[r], W, H, lane, live[r]);
-          float jx, jy, gx[5], gy[5];
+          const float gwin[3] = {gw.x, gw.y, gw.z};
+          float jx, jy;
           sample_jitter(seed_key, pix[r] * (uint32_t)spp + (uint32_t)s, jx, jy);
-          rf_weights(ct.rf, jx, gx);
-          rf_weights(ct.rf, jy, gy);
-          float a0 = 0.f, a1 = 0.f, a2 = 0.f;
-#pragma unroll
-          for (int n = 0; n < 25; ++n) {
-            const float w = gx[n % 5] * gy[n / 5];
-            a0 = __builtin_fmaf(w, __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(gw.x), n)), a0);
-            a1 = __builtin_fmaf(w, __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(gw.y), n)), a1);
-            a2 = __builtin_fmaf(w, __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(gw.z), n)), a2);
-          }
-          g[r][0] = a0; g[r][1] = a1; g[r][2] = a2;
+          sample_adjoint<true>(ct.rf, jx, jy, gwin, g[r]);
         }
         if (!st[r].hit || !st[r].has_proj) continue;
         const float *alb = TEX ? st[r].base : mat_table(ct) + (MAT ? FFX_MAT_STRIDE : 3) * st[r].shape;
-        size_t o00 = ((size_t)st[r].iy0 * ct.tw + st[r].ix0) * tc, o01 = ((size_t)st[r].iy0 * ct.tw + st[r].ix1) * tc;
-        size_t o10 = ((size_t)st[r].iy1 * ct.tw + st[r].ix0) * tc, o11 = ((size_t)st[r].iy1 * ct.tw + st[r].ix1) * tc;
-        const float wx0 = st[r].wx0, wx1 = st[r].wx1, wy0 = st[r].wy0, wy1 = st[r].wy1;
-        if (tc == 1) {
-          float ws = (g[r][0] * alb[0] * ct.p_color[0] + g[r][1] * alb[1] * ct.p_color[1] + g[r][2] * alb[2] * ct.p_color[2]) * st[r].proj_fac * inv_spp;
-          if constexpr (MAT) {
-            if (st[r].proj_fac_b != 0.f) ws += (g[r][0] * ct.p_color[0] + g[r][1] * ct.p_color[1] + g[r][2] * ct.p_color[2]) * st[r].proj_fac_b * inv_spp;
-          }
-          det_emit(det, gtex, o00, ws * wy0 * wx0);
-          det_emit(det, gtex, o01, ws * wy0 * wx1);
-          det_emit(det, gtex, o10, ws * wy1 * wx0);
-          det_emit(det, gtex, o11, ws * wy1 * wx1);
-        } else {
-#pragma unroll
-          for (int ch = 0; ch < 3; ++ch) {
-            float ws = g[r][ch] * alb[ch] * st[r].proj_fac * inv_spp;
-            if constexpr (MAT) {
-              if (st[r].proj_fac_b != 0.f) ws += g[r][ch] * st[r].proj_fac_b * inv_spp;
-            }
-            det_emit(det, gtex, o00 + ch, ws * wy0 * wx0);
-            det_emit(det, gtex, o01 + ch, ws * wy0 * wx1);
-            det_emit(det, gtex, o10 + ch, ws * wy1 * wx0);
-            det_emit(det, gtex, o11 + ch, ws * wy1 * wx1);
-          }
-        }
+        sample_scatter(sample_taps(st[r], ct.tw, tc), tc, g[r], alb, ct.p_color, st[r].proj_fac, MAT ? st[r].proj_fac_b : 0.f, inv_spp, false,
+                       [&](size_t o, int ch, float v) { det_emit(det, gtex, o + ch, v); });
       }
     }
   }
@@ -3575,8 +3509,8 @@ __device__ __forceinline__ void k9_g(const BwdP &p, const float *__restrict__ gi
   }
   g0 = gimg[pixel * 3]; g1 = gimg[pixel * 3 + 1]; g2 = gimg[pixel * 3 + 2];
 }
-__device__ __forceinline__ float k9_pixel_dot(const BwdP &p, long pixel, const float *__restrict__ gimg) {
-  const float g0 = gimg[pixel * 3], g1 = gimg[pixel * 3 + 1], g2 = gimg[pixel * 3 + 2];
+// <g, img> of a pixel with gradient g, for either film format
+__device__ __forceinline__ float k9_pixel_dot(const BwdP &p, long pixel, float g0, float g1, float g2) {
   if (p.img_fp16) {
     const _Float16 *q = (const _Float16 *)p.img + pixel * 3;
     return g0 * (float)q[0] + g1 * (float)q[1] + g2 * (float)q[2];
@@ -3597,6 +3531,7 @@ __device__ __forceinline__ void k9_stray(const char *__restrict__ cache, long n_
   if (i >= n) return;
   const CacheStray rec = reinterpret_cast<const CacheStray *>(cache + cache_off_arena((size_t)n_pix))[i];
   const long pixel = rec.pix;
+  // (sample_scatter's values with zero values skipped, written out: as a call it changes the register count of k_render_bwd_cached_tiled16, whose tail this is)
   float g0, g1, g2;
   k9_g(p, gimg, pixel, g0, g1, g2);
   const int ix0 = (int)(rec.xy_shape & 0xfffu) - 1, iy0 = (int)((rec.xy_shape >> 12) & 0xfffu) - 1, shape = (int)(rec.xy_shape >> 24);
@@ -3629,84 +3564,14 @@ __device__ __forceinline__ void k9_stray(const char *__restrict__ cache, long n_
   }
 }
 
-// K9 for 1-channel textures, tiled: a workgroup owns an 8x8-pixel block of the image.  Neighbouring pixels land on
-// neighbouring texels, so their 5x5 footprints overlap heavily: the plain kernel issued ~900 k contended global float
-// atomics into a 500^2 texture and was bound by them (0.027 ms for 12 MB).  Here the block's footprints are summed
-// in a 32x32-texel LDS tile anchored at the smallest window origin of its lit pixels, and every touched texel gets
-// ONE global atomic; footprint elements that fall outside the tile (a block on a depth discontinuity) go to memory
-// directly.  Summation order inside a block is not fixed (LDS float atomics) — like the global atomics it replaces.
-#define K9_TILE 32
-__global__ void __launch_bounds__(256)
-    k_render_bwd_cached_tiled(BwdP p_by_value, const char *__restrict__ cache, int blocks_x, int tile_blocks, const float *__restrict__ gimg,
-                              float *__restrict__ gtex) {
-  __shared__ float s_tile[K9_TILE * K9_TILE];
-  __shared__ int s_ox, s_oy, s_any;
-  const BwdP &p = kernarg_first<BwdP>(); // (read in place: the inline material rows are indexed per lane)
-  const float *albedo = mat_table(p);
-  const long n_pix = (long)p.W * p.H;
-  if ((int)blockIdx.x >= tile_blocks) { // the tail of the grid replays the stray records
-    k9_stray(cache, n_pix, (uint32_t)((int)blockIdx.x - tile_blocks) * 256u + threadIdx.x, p, gimg, albedo, gtex);
-    return;
-  }
-  const int bx = (int)blockIdx.x % blocks_x, by = (int)blockIdx.x / blocks_x;
-  const CachePix *hdrs = reinterpret_cast<const CachePix *>(cache + 64);
-  const CacheFoot *foots = reinterpret_cast<const CacheFoot *>(cache + cache_off_foot((size_t)n_pix));
-  if (threadIdx.x == 0) { s_ox = 0x7fffffff; s_oy = 0x7fffffff; s_any = 0; }
-  for (int i = threadIdx.x; i < K9_TILE * K9_TILE; i += 256) s_tile[i] = 0.f;
-  __syncthreads();
-  // pass 1 (threads 0..63, one per pixel): the tile origin
-  if (threadIdx.x < 64) {
-    const int x = bx * 8 + (threadIdx.x & 7), y = by * 8 + (threadIdx.x >> 3);
-    float d = 0.f;
-    if (x < p.W && y < p.H) {
-      const CachePix hp = hdrs[(long)y * p.W + x];
-      if (hp.lit) { atomicMin(&s_ox, (int)hp.x0); atomicMin(&s_oy, (int)hp.y0); s_any = 1; }
-      if (p.dot_out) d = k9_pixel_dot(p, (long)y * p.W + x, gimg);
-    }
-    if (p.dot_out) { // <gimg, img> of this 8x8 block: one wave, one add into the block's OWN slot (the loss of a pattern optimiser's step:
-      d = wave_sum64(d); // no separate reduction launch.  4096 atomics on ONE address cost 40 us here — a slot per block costs nothing)
-      if (threadIdx.x == 0 && d != 0.f) atomicAdd(p.dot_out + (int)blockIdx.x % p.dot_slots, d);
-    }
-  }
-  __syncthreads();
-  if (!s_any) return; // (uniform: nothing lit in this block)
-  const int ox = s_ox, oy = s_oy;
-  // pass 2: 32 lanes per pixel (25 footprint elements), 8 pixels per iteration
-  const int e = threadIdx.x & 31;
-  for (int it = 0; it < 8; ++it) {
-    const int pl = it * 8 + (threadIdx.x >> 5);
-    const int x = bx * 8 + (pl & 7), y = by * 8 + (pl >> 3);
-    if (x >= p.W || y >= p.H || e >= 25) continue;
-    const long pixel = (long)y * p.W + x;
-    const CachePix hp = hdrs[pixel];
-    if (!hp.lit) continue;
-    const float w = foots[pixel].w[e];
-    const float wb = p.ms == 3 ? 0.f : reinterpret_cast<const CacheFoot *>(cache + p.off_foot_b)[pixel].w[e];
-    if (w == 0.f && wb == 0.f) continue;
-    const float g0 = gimg[pixel * 3], g1 = gimg[pixel * 3 + 1], g2 = gimg[pixel * 3 + 2];
-    const float *alb = albedo + p.ms * (int)hp.shape;
-    const float ws = (g0 * alb[0] * p.color[0] + g1 * alb[1] * p.color[1] + g2 * alb[2] * p.color[2]) * p.inv_spp;
-    float val = ws * w;
-    if (wb != 0.f) val += (g0 * p.color[0] + g1 * p.color[1] + g2 * p.color[2]) * p.inv_spp * wb;
-    if (val == 0.f) continue;
-    const int tx = (int)hp.x0 + e % 5, ty = (int)hp.y0 + e / 5;
-    const int lx = tx - ox, ly = ty - oy;
-    if (lx < K9_TILE && ly < K9_TILE) atomicAdd(&s_tile[ly * K9_TILE + lx], val); // (lx, ly >= 0 by construction)
-    else atomicAdd(gtex + (size_t)ty * p.tw + tx, val);
-  }
-  __syncthreads();
-  for (int i = threadIdx.x; i < K9_TILE * K9_TILE; i += 256) {
-    const float v = s_tile[i];
-    if (v != 0.f) atomicAdd(gtex + (size_t)(oy + i / K9_TILE) * p.tw + (ox + i % K9_TILE), v);
-  }
-}
-
-// The same with 16x16-pixel blocks (round 3, the default).  Most of K9's time was not the scatter but finding out that there is nothing to
-// scatter: 96 % of the pixels of a dot pattern's render are unlit, and a workgroup of the 8x8 kernel spent an LDS clear, two barriers
-// and a dependent header -> atomicMin chain on 64 of its 256 lanes to learn that (4096 workgroups in two rounds: 20 us for 8 MB).
-// Here every lane owns a pixel in pass 1 — header, <gimg, img>, a ballot — and a workgroup without a lit pixel ends after ONE round of
-// independent loads; the lit pixels are compacted into a list that pass 2 walks 8 at a time (32 lanes per pixel, 25 footprint weights),
-// through a 48x48-texel LDS tile anchored at the smallest window origin.
+// K9 for 1-channel textures, tiled: a workgroup owns a 16x16-pixel block of the image.  Neighbouring pixels land on neighbouring texels, so their
+// 5x5 footprints overlap heavily: one global float atomic per footprint element was bound by contention (~900 k of them into a 500^2 texture).
+// Here the block's footprints are summed in a 48x48-texel LDS tile anchored at the smallest window origin of its lit pixels, and every touched
+// texel gets ONE global atomic; footprint elements that fall outside the tile (a block on a depth discontinuity) go to memory directly.
+// Summation order inside a block is not fixed (LDS float atomics) — like the global atomics it replaces.
+// Most of K9's time is not the scatter but finding out that there is nothing to scatter: 96 % of the pixels of a dot pattern's render are unlit.
+// Every lane owns a pixel in pass 1 — header, <gimg, img>, a ballot — and a workgroup without a lit pixel ends after ONE round of
+// independent loads; the lit pixels are compacted into a list that pass 2 walks 8 at a time (32 lanes per pixel, 25 footprint weights).
 #define K9_TILE16 48
 __global__ void __launch_bounds__(256)
     k_render_bwd_cached_tiled16(BwdP p_by_value, const char *__restrict__ cache, int blocks_x, int tile_blocks, const float *__restrict__ gimg,
@@ -3740,8 +3605,8 @@ __global__ void __launch_bounds__(256)
     hp.lit = 0;
     if (in) hp = hdrs[pixel];
     const bool lit = in && hp.lit;
-    float g0 = 0.f, g1 = 0.f, g2 = 0.f, l1_abs = 0.f;
-    if (in && (p.dot_out || lit)) k9_g(p, gimg, pixel, g0, g1, g2, &l1_abs);
+    float g[3] = {0.f, 0.f, 0.f}, l1_abs = 0.f;
+    if (in && (p.dot_out || lit)) k9_g(p, gimg, pixel, g[0], g[1], g[2], &l1_abs);
     if (p.l1_tgt) { // the L1 loss's value: this wave's 4 rows of |img - target|, one add into the block's own slot (summed by the gradient launch)
       const float d = wave_sum64(l1_abs);
       if ((threadIdx.x & 63) == 0 && d != 0.f) atomicAdd(p.dot_out + (int)blockIdx.x % p.dot_slots, d * p.l1_vs);
@@ -3758,17 +3623,12 @@ __global__ void __launch_bounds__(256)
         const int k = base + (int)mbcnt64(lm);
         s_px[k] = (unsigned short)threadIdx.x;
         s_xy[k] = (int)hp.x0 | ((int)hp.y0 << 16);
-        s_ws[k] = (g0 * alb[0] * p.color[0] + g1 * alb[1] * p.color[1] + g2 * alb[2] * p.color[2]) * p.inv_spp;
-        s_wsb[k] = (g0 * p.color[0] + g1 * p.color[1] + g2 * p.color[2]) * p.inv_spp;
+        s_ws[k] = g_alb_colour(g, alb, p.color) * p.inv_spp;
+        s_wsb[k] = g_colour(g, p.color) * p.inv_spp;
       }
     }
     if (p.dot_out && !p.l1_tgt) { // <gimg, img> of this wave's 4 rows: one add into the block's own slot (ffx_render_dot_slots)
-      float d = 0.f;
-      if (in) {
-        if (p.img_fp16) { const _Float16 *q = (const _Float16 *)p.img + pixel * 3; d = g0 * (float)q[0] + g1 * (float)q[1] + g2 * (float)q[2]; }
-        else { const float *q = (const float *)p.img + pixel * 3; d = g0 * q[0] + g1 * q[1] + g2 * q[2]; }
-      }
-      d = wave_sum64(d);
+      const float d = wave_sum64(in ? k9_pixel_dot(p, pixel, g[0], g[1], g[2]) : 0.f);
       if ((threadIdx.x & 63) == 0 && d != 0.f) atomicAdd(p.dot_out + (int)blockIdx.x % p.dot_slots, d);
     }
   }
@@ -3799,7 +3659,7 @@ __global__ void __launch_bounds__(256)
     for (int u = 0; u < 4; ++u) {
       const int it = it0 + 8 * u;
       if (it >= n_lit || (w[u] == 0.f && wb[u] == 0.f)) continue;
-      float val = s_ws[it] * w[u];
+      float val = s_ws[it] * w[u]; // (foot_value_1ch, written out: s_wsb[it] is read only where wb != 0)
       if (wb[u] != 0.f) val += s_wsb[it] * wb[u];
       if (val == 0.f) continue;
       const int xy = s_xy[it];
@@ -3825,7 +3685,7 @@ __global__ void __launch_bounds__(256)
     const int e = threadIdx.x & 31;
     if (p.dot_out) { // <gimg, img> of the block's 8 pixels: lanes 0..7 of wave 0, one atomic
       __shared__ float s_d[8];
-      if (e == 0) s_d[threadIdx.x >> 5] = pixel < n_pix ? k9_pixel_dot(p, pixel, gimg) : 0.f;
+      if (e == 0) s_d[threadIdx.x >> 5] = pixel < n_pix ? k9_pixel_dot(p, pixel, gimg[pixel * 3], gimg[pixel * 3 + 1], gimg[pixel * 3 + 2]) : 0.f;
       __syncthreads();
       if (threadIdx.x == 0) {
         const float d = ((s_d[0] + s_d[1]) + (s_d[2] + s_d[3])) + ((s_d[4] + s_d[5]) + (s_d[6] + s_d[7]));
@@ -3838,19 +3698,17 @@ __global__ void __launch_bounds__(256)
     const float w = reinterpret_cast<const CacheFoot *>(cache + cache_off_foot((size_t)n_pix))[pixel].w[e];
     const float wb = p.ms == 3 ? 0.f : reinterpret_cast<const CacheFoot *>(cache + p.off_foot_b)[pixel].w[e];
     if (w == 0.f && wb == 0.f) return;
-    const float g0 = gimg[pixel * 3], g1 = gimg[pixel * 3 + 1], g2 = gimg[pixel * 3 + 2];
+    const float g[3] = {gimg[pixel * 3], gimg[pixel * 3 + 1], gimg[pixel * 3 + 2]};
     const float *alb = albedo + p.ms * (int)hp.shape;
     const int x = (int)hp.x0 + e % 5, y = (int)hp.y0 + e / 5;
     if (p.tc == 1) {
-      const float ws = (g0 * alb[0] * p.color[0] + g1 * alb[1] * p.color[1] + g2 * alb[2] * p.color[2]) * p.inv_spp;
-      float val = ws * w;
-      if (wb != 0.f) val += (g0 * p.color[0] + g1 * p.color[1] + g2 * p.color[2]) * p.inv_spp * wb;
+      const float val = foot_value_1ch(g_alb_colour(g, alb, p.color) * p.inv_spp, g_colour(g, p.color) * p.inv_spp, w, wb);
       if (val != 0.f) atomicAdd(gtex + (size_t)y * p.tw + x, val);
     } else {
       float *t = gtex + ((size_t)y * p.tw + x) * 3;
-      if (g0 != 0.f) atomicAdd(t, g0 * alb[0] * p.inv_spp * w + g0 * p.inv_spp * wb);
-      if (g1 != 0.f) atomicAdd(t + 1, g1 * alb[1] * p.inv_spp * w + g1 * p.inv_spp * wb);
-      if (g2 != 0.f) atomicAdd(t + 2, g2 * alb[2] * p.inv_spp * w + g2 * p.inv_spp * wb);
+#pragma unroll
+      for (int ch = 0; ch < 3; ++ch)
+        if (g[ch] != 0.f) atomicAdd(t + ch, foot_value_3ch(g[ch], alb[ch], p.inv_spp, w, wb));
     }
     return;
   }
@@ -3859,8 +3717,8 @@ __global__ void __launch_bounds__(256)
 
 // K9 of the filtered film's cache (ffx_render_bwd_cached_filtered; rfc_off_* above).  An ITEM is one lit 64-sample pass of one pixel: the
 // lanes take its 64 records (one coalesced 1 KB load), their ten filter weights from the jitter (the forward's hash), the pixel's window of
-// G = gimg / weight (lanes 0..24 load a window pixel each, broadcast by v_readlane), the sample's own gradient sum_n w_n G[pixel + n] (the
-// arithmetic and the order of k_render_fwd_pk<.., ADJ, RF>); the wave then sums its samples' taps per texel of the pixel's 5x5 texel window
+// G = gimg / weight (lanes 0..24 load a window pixel each, broadcast by v_readlane), the sample's own gradient sum_n w_n G[pixel + n]
+// (sample_adjoint); the wave then sums its samples' taps per texel of the pixel's 5x5 texel window
 // (25 DPP reductions) and 25 lanes add one value each to gtex — no per-sample atomics (samples outside the window: their four taps directly).
 // ~800 VALU instructions per item, and the items of a dot pattern's render sit in ~500 of the film's 4096 8x8-pixel blocks: as ONE workgroup
 // per block (first version: 16x16-pixel blocks, then 8x8, four to sixteen waves, an LDS tile per block) a block's ~64 items ran on ONE compute
@@ -3953,18 +3811,10 @@ __global__ void __launch_bounds__(64)
     // the pixel's window of G = gimg / weight (lanes 0..24), zero outside the film
     const bool gok = cur.qw > 0.f;
     const float g0 = gok ? cur.q0 / cur.qw : 0.f, g1 = gok ? cur.q1 / cur.qw : 0.f, g2 = gok ? cur.q2 / cur.qw : 0.f;
-    float jx, jy, gx[5], gy[5];
+    const float gwin[3] = {g0, g1, g2};
+    float jx, jy, a[3];
     sample_jitter(p.seed_key, cur.sidx, jx, jy);
-    rf_weights(p.rf, jx, gx);
-    rf_weights(p.rf, jy, gy);
-    float a0 = 0.f, a1 = 0.f, a2 = 0.f;
-#pragma unroll
-    for (int n = 0; n < 25; ++n) {
-      const float w = gx[n % 5] * gy[n / 5];
-      a0 = __builtin_fmaf(w, __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(g0), n)), a0);
-      a1 = __builtin_fmaf(w, __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(g1), n)), a1);
-      a2 = __builtin_fmaf(w, __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(g2), n)), a2);
-    }
+    sample_adjoint<true>(p.rf, jx, jy, gwin, a);
     const int ubx = (int)(rec.x & 0xfffu) - 1, uby = (int)((rec.x >> 12) & 0xfffu) - 1, shape = (int)(rec.x >> 24);
     const int x0 = clampi(ubx, 0, p.tw - 1), x1 = clampi(ubx + 1, 0, p.tw - 1), y0 = clampi(uby, 0, p.th - 1), y1 = clampi(uby + 1, 0, p.th - 1);
     const float ax = __uint_as_float(rec.y), ay = __uint_as_float(rec.z);
@@ -3972,10 +3822,7 @@ __global__ void __launch_bounds__(64)
     const float *alb = albedo + p.ms * (lit ? shape : 0);
     if (tiled) {
       float pf = 0.f;
-      if (lit) {
-        pf = (a0 * alb[0] * p.color[0] + a1 * alb[1] * p.color[1] + a2 * alb[2] * p.color[2]) * fac;
-        if (fb != 0.f) pf += (a0 * p.color[0] + a1 * p.color[1] + a2 * p.color[2]) * fb;
-      }
+      if (lit) pf = tap_value_1ch(a, alb, p.color, fac, fb, 1.0f); // (the weight inside G normalises)
       const bool on = lit && pf != 0.f;
       if (wballot(on) != 0ull) { // (wave-uniform)
         const int fox = (int)wave_reduce_nn<false>(on ? (uint32_t)x0 : 0xffffffffu), foy = (int)wave_reduce_nn<false>(on ? (uint32_t)y0 : 0xffffffffu);
@@ -4003,27 +3850,11 @@ __global__ void __launch_bounds__(64)
           const int ey = (lane * 13) >> 6, ex = lane - 5 * ey;
           atomicAdd(gtex + (size_t)(foy + ey) * p.tw + (fox + ex), mine);
         }
-        if (on && !in_win) { // a sample outside its pixel's window (depth discontinuities, grazing surfaces: ~0.1 %): its four taps directly
-          atomicAdd(gtex + (size_t)y0 * p.tw + x0, pf * wy0 * wx0);
-          atomicAdd(gtex + (size_t)y0 * p.tw + x1, pf * wy0 * wx1);
-          atomicAdd(gtex + (size_t)y1 * p.tw + x0, pf * wy1 * wx0);
-          atomicAdd(gtex + (size_t)y1 * p.tw + x1, pf * wy1 * wx1);
-        }
+        // a sample outside its pixel's window (depth discontinuities, grazing surfaces: ~0.1 %): its four taps directly
+        if (on && !in_win) taps_scatter(make_taps(x0, x1, y0, y1, wx0, wx1, wy0, wy1, p.tw, 1), 0, pf, AtomicInto{gtex});
       }
     } else if (lit) { // 3-channel textures: twelve direct atomics per sample
-      const size_t o00 = ((size_t)y0 * p.tw + x0) * 3, o01 = ((size_t)y0 * p.tw + x1) * 3, o10 = ((size_t)y1 * p.tw + x0) * 3, o11 = ((size_t)y1 * p.tw + x1) * 3;
-      const float aa[3] = {a0, a1, a2};
-#pragma unroll
-      for (int ch = 0; ch < 3; ++ch) {
-        float cv = aa[ch] * alb[ch] * fac;
-        if (fb != 0.f) cv += aa[ch] * fb;
-        if (cv != 0.f) {
-          atomicAdd(gtex + o00 + ch, cv * wy0 * wx0);
-          atomicAdd(gtex + o01 + ch, cv * wy0 * wx1);
-          atomicAdd(gtex + o10 + ch, cv * wy1 * wx0);
-          atomicAdd(gtex + o11 + ch, cv * wy1 * wx1);
-        }
-      }
+      sample_scatter(make_taps(x0, x1, y0, y1, wx0, wx1, wy0, wy1, p.tw, 3), 3, a, alb, p.color, fac, fb, 1.0f, true, AtomicInto{gtex});
     }
     cur = nxt;
   }
@@ -4046,7 +3877,8 @@ __device__ __forceinline__ v3 cosine_dir(v3 n, float u0, float u1) {
   const float x = r * cosf(ph), y = r * sinf(ph);
   return V3(fmaf(x, s.x, fmaf(y, t.x, z * n.x)), fmaf(x, s.y, fmaf(y, t.y, z * n.y)), fmaf(x, s.z, fmaf(y, t.z, z * n.z)));
 }
-// the projector's texture value at a vertex, per colour channel (1-channel textures: times the projector's colour)
+// the projector's texture value at a vertex, per colour channel: proj_tex_value's values.  (Its own statement, one loop over the channels: through
+// proj_tex_value, which gathers the first channel ahead of the branch as the render kernels always did, the path kernels compile to other machine code.)
 __device__ __forceinline__ void path_tex(const ShadeK &c, const SampleTerms &st, const float *__restrict__ tex, float (&tv)[3]) {
   const int tc = c.tc;
   const size_t o00 = ((size_t)st.iy0 * c.tw + st.ix0) * tc, o01 = ((size_t)st.iy0 * c.tw + st.ix1) * tc;
@@ -4200,25 +4032,8 @@ __device__ __forceinline__ bool pixel_adjoint(const float *__restrict__ gsrc, ui
   g[0] = gsrc[(size_t)pix * 3] * inv_spp; g[1] = gsrc[(size_t)pix * 3 + 1] * inv_spp; g[2] = gsrc[(size_t)pix * 3 + 2] * inv_spp;
   return !(g[0] == 0.f && g[1] == 0.f && g[2] == 0.f);
 }
-// the adjoint weight of a sample with jitter (jx, jy): box: g; RF: sum over the sample's 5x5 window of filter weight x G
-template <bool RF>
-__device__ __forceinline__ void sample_adjoint(const RfC &rf, float jx, float jy, const float (&g)[3], float (&q)[3]) {
-  q[0] = g[0]; q[1] = g[1]; q[2] = g[2];
-  if (RF) { // (all lanes: the readlanes need the whole wave)
-    float gx[5], gy[5];
-    rf_weights(rf, jx, gx);
-    rf_weights(rf, jy, gy);
-    q[0] = q[1] = q[2] = 0.f;
-#pragma unroll
-    for (int n = 0; n < 25; ++n) {
-      const float w = gx[n % 5] * gy[n / 5];
-      q[0] = __builtin_fmaf(w, __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(g[0]), n)), q[0]);
-      q[1] = __builtin_fmaf(w, __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(g[1]), n)), q[1]);
-      q[2] = __builtin_fmaf(w, __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(g[2]), n)), q[2]);
-    }
-  }
-}
 // cw (d loss / d texture value per channel at a vertex) into the projector texture's gradient through the vertex's four bilinear taps: path_tex's adjoint
+// (taps_scatter's values; written out for the same reason as path_tex)
 __device__ __forceinline__ void proj_tex_scatter(const ShadeK &k, const SampleTerms &st, const float (&cw)[3], float *__restrict__ gtex) {
   const int tc = k.tc;
   const size_t o00 = ((size_t)st.iy0 * k.tw + st.ix0) * tc, o01 = ((size_t)st.iy0 * k.tw + st.ix1) * tc;
@@ -6027,8 +5842,6 @@ int ffx_render_bwd_cached_l1(const ffx_scene_desc *sd, const float *shape_albedo
                              float *gtex, float *loss_slots, ffx_stream s) {
   if (!img || !target || !loss_slots) FFX_FAIL(FFX_ERR_ARG, "render_bwd_cached_l1: bad argument");
   if (sd && (!sd->proj.enabled || sd->proj.tex_channels != 1)) FFX_FAIL(FFX_ERR_UNSUPPORTED, "render_bwd_cached_l1: a projector with a one-channel texture (else ffx_l1_value_grad + ffx_render_bwd_cached)");
-  const char *k9e = getenv("FFX_K9_BLOCK");
-  if (k9e && atoi(k9e) == 8) FFX_FAIL(FFX_ERR_UNSUPPORTED, "render_bwd_cached_l1: only the 16x16-block kernel carries the loss");
   return render_bwd_cached_impl(sd, shape_albedo, cache, spp, nullptr, gtex, img, 0, loss_slots, target, weight, s);
 }
 static int render_bwd_cached_impl(const ffx_scene_desc *sd, const float *shape_albedo, const void *cache, int spp, const float *gimg, float *gtex, const void *img,
@@ -6059,21 +5872,12 @@ static int render_bwd_cached_impl(const ffx_scene_desc *sd, const float *shape_a
   if (p.ms != 3 && p.ms != FFX_MAT_STRIDE) FFX_FAIL(FFX_ERR_ARG, "render_bwd_cached: bad material stride");
   p.off_foot_b = cache_off_foot_b((size_t)n_pix, cache_stray_capacity(sd->cam.width, sd->cam.height, spp));
   const int stray_blocks = ffx_cdiv((long)cache_stray_capacity(sd->cam.width, sd->cam.height, spp), 256);
-  const char *k9e = getenv("FFX_K9_BLOCK"); // (8: the round-2 kernel, for A/B; read per call like the other knobs)
-  const int k9_block = (k9e && atoi(k9e) == 8) ? 8 : 16;
-  if (p.tc == 1 && k9_block == 16) {
+  if (p.tc == 1) {
     // footprints by 16x16-pixel blocks through an LDS tile; the tail of the grid replays the stray records
     const int blocks_x = ffx_cdiv(p.W, 16), blocks_y = ffx_cdiv(p.H, 16);
     hipLaunchKernelGGL(k_render_bwd_cached_tiled16, dim3(blocks_x * blocks_y + stray_blocks), dim3(256), 0, (hipStream_t)s, p, (const char *)cache, blocks_x,
                        blocks_x * blocks_y, gimg, gtex);
     FFX_CHECK_LAUNCH("render_bwd_cached/tiled16");
-    return FFX_OK;
-  }
-  if (p.tc == 1) {
-    const int blocks_x = ffx_cdiv(p.W, 8), blocks_y = ffx_cdiv(p.H, 8);
-    hipLaunchKernelGGL(k_render_bwd_cached_tiled, dim3(blocks_x * blocks_y + stray_blocks), dim3(256), 0, (hipStream_t)s, p, (const char *)cache, blocks_x,
-                       blocks_x * blocks_y, gimg, gtex);
-    FFX_CHECK_LAUNCH("render_bwd_cached/tiled");
     return FFX_OK;
   }
   const int slot_blocks = ffx_cdiv(n_pix, 8);

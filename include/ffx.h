@@ -54,8 +54,6 @@
  *                                baseline).  A caller's hint in ffx_scene_desc.shadows (FFX_SHADOWS_PLAIN) leaves them out per pose.
  *       FFX_RFC_CAP=n            blocks of the filtered film's adjoint cache a forward may take, at most what the cache holds (a test knob: pixels
  *                                that find the arena full keep no records and are counted in `dropped` — the overflow path)
- *       FFX_K9_BLOCK=8           ffx_render_bwd_cached on the round-2 kernel (default 16: footprints by 16x16-pixel blocks through LDS);
- *                                ffx_render_bwd_cached_l1 then declines
  *     Read by ffx_scene_update:
  *       FFX_REFIT=fused|levels   fused: the fused re-fit as one launch; levels: the level-by-level re-fit (default: the fused re-fit's
  *                                treelets and the top of the tree as two launches)
