@@ -72,6 +72,89 @@ def corner(floor_bsdf=None, wall_y_bsdf=None, *, shared=False, materials=True, W
     return scenes.SceneData(meshes, _camera(W, H), _projector(tex), _spot(), 1.0)
 
 
+# the film (W, H), samples per pixel and projector texture size at which the GPU tests render mosaic: tests/test_leaf_arms_cpu.py shows that the rows of
+# high index receive samples there (a film too small for that is grown here, for both)
+MOSAIC_FILM, MOSAIC_SPP, MOSAIC_TEX = (32, 32), 16, 32
+MOSAIC_TEX_SIZES = ([8, 8], [3, 5], [4, 4], [2, 7])  # [h, w] of mosaic's base-colour textures
+# mosaic's camera is _camera from high above the floor: from corner()'s eye the cube hides a quarter of the floor's cells (its silhouette on z = 0 is
+# the hull of its footprint and that footprint shifted by (-0.77, -0.73)), whatever the film's size, and those rows would never take a primary hit
+MOSAIC_EYE, MOSAIC_TARGET = (2.0, 2.0, 5.5), (0.95, 0.95, 0.0)
+# where mosaic's textured cells lie: floor points beside the cube that the camera and both emitters see
+MOSAIC_TEX_POINTS = ((1.7, 0.45), (0.45, 1.7), (1.75, 1.15), (1.15, 1.75))
+
+
+def mosaic_order(m):
+    """the cell (iy * m + ix, x in 2 ix / m .. 2 (ix + 1) / m) of every floor mesh of mosaic: the cells of MOSAIC_TEX_POINTS first, the others in a
+    stride over the grid (neighbouring indices lie far apart, so low and high rows both cover the whole floor), the cells whose centre lies under
+    the cube last — no ray reaches them, and the last floor mesh takes what it can of them"""
+    n = m * m
+    first = []
+    for x, y in MOSAIC_TEX_POINTS:
+        c = int(y * m / 2) * m + int(x * m / 2)
+        assert c not in first
+        first.append(c)
+    step = next(s for s in range(int(0.38 * n) | 1, n + 2) if np.gcd(s, n) == 1)
+    rest = [c for c in (np.arange(n) * step) % n if c not in first]
+    cx, cy = (np.array([c % m for c in rest]) + 0.5) * 2 / m, (np.array([c // m for c in rest]) + 0.5) * 2 / m
+    under = (np.abs(cx - 1.2) < 0.3) & (np.abs(cy - 1.1) < 0.3)
+    return first + [c for c, u in zip(rest, under) if not u] + [c for c, u in zip(rest, under) if u]
+
+
+def mosaic(S, *, base_tex=0, lambert=False, hidden=False, W=None, H=None, tex=None, seed=17):
+    """the box corner with its floor cut into an m x m grid of quads, m = ceil(sqrt(S - 3)): S shapes — S - 3 floor meshes (mosaic_order names their
+    cells; the first S - 4 hold one cell, the last every remaining one), then wall x = 0, wall y = 0 and the cube.  Every floor mesh and wall y = 0
+    has its own material, colour and principled BSDF (roughness 0.2 .. 0.8, metallic 0 .. 0.5, specular 0.2 .. 0.8, on every third row sheen,
+    clearcoat and spec_tint in 0.1 .. 0.9) from a seeded generator whose draws depend on S and seed alone; wall x = 0 and the cube are Lambert rows
+    of a stride-16 table.  base_tex = k (0 .. 4): the first k floor meshes take a base-colour texture of MOSAIC_TEX_SIZES each, uv over the cell.
+    lambert: no mesh has a BSDF (without base_tex: a stride-3 table).  hidden: one more mesh behind every other index — a quad of side 0.02 under
+    the middle of the floor at z = -0.05 with a principled row; a segment from any point of the corner's surfaces to it crosses the floor, so no
+    camera, shadow or bounce ray reaches it"""
+    assert S >= 8 and 0 <= base_tex <= len(MOSAIC_TEX_SIZES)
+    W, H, tex = W or MOSAIC_FILM[0], H or MOSAIC_FILM[1], tex or MOSAIC_TEX
+    n_floor = S - 3
+    m = int(np.ceil(np.sqrt(n_floor)))
+    order = mosaic_order(m)
+    rng = np.random.default_rng(seed)
+    n_rows = n_floor + 2  # (the floor meshes, wall y = 0, the hidden quad)
+    rgb = rng.uniform(0.3, 0.8, (n_rows, 3))
+    par = {"roughness": rng.uniform(0.2, 0.8, n_rows), "metallic": rng.uniform(0.0, 0.5, n_rows), "specular": rng.uniform(0.2, 0.8, n_rows)}
+    extra = {k: rng.uniform(0.1, 0.9, n_rows) for k in ("sheen", "clearcoat", "spec_tint")}
+    trng = np.random.default_rng(seed + 1)
+    texs = [trng.uniform(0.2, 0.9, (h, w, 3)).astype(np.float32) for h, w in MOSAIC_TEX_SIZES]
+
+    def bsdf(i):
+        if lambert:
+            return None
+        b = {k: float(v[i]) for k, v in par.items()}
+        if i % 3 == 0:
+            b.update({k: float(v[i]) for k, v in extra.items()})
+        return b
+
+    def cells(cs_):
+        v = []
+        for c in cs_:
+            x0, y0, d = 2.0 * (c % m) / m, 2.0 * (c // m) / m, 2.0 / m
+            v += [[x0, y0, 0], [x0 + d, y0, 0], [x0 + d, y0 + d, 0], [x0, y0 + d, 0]]
+        t = np.concatenate([QUAD + 4 * j for j in range(len(cs_))]).astype(np.int32)
+        return np.asarray(v, np.float32)[None], t
+
+    uv = np.array([[0, 0], [1, 0], [1, 1], [0, 1]], np.float32)
+    meshes = []
+    for i in range(n_floor):
+        v, t = cells(order[i:i + 1] if i < n_floor - 1 else order[i:])
+        tx = texs[i] if i < base_tex else None
+        meshes.append(scenes.MeshData(f"mesh-Cell{i}", v, t, tuple(rgb[i]), material=f"mat-Cell{i}", bsdf=bsdf(i), uv=uv if tx is not None else None, base_tex=tx))
+    cv, ct = scenes.make_cube((1.2, 1.1, 0.3), 0.3)
+    meshes += [scenes.MeshData("mesh-WallX", _wall_x(), QUAD, WALL_X_RGB, material="mat-WallX"),
+               scenes.MeshData("mesh-WallY", _wall_y(), QUAD, tuple(rgb[n_floor]), material="mat-WallY", bsdf=bsdf(n_floor)),
+               scenes.MeshData("mesh-Cube", cv[None], ct, CUBE_RGB, material="mat-Cube")]
+    if hidden:
+        q = _quad([[0.99, 0.99, -0.05], [1.01, 0.99, -0.05], [1.01, 1.01, -0.05], [0.99, 1.01, -0.05]])
+        meshes.append(scenes.MeshData("mesh-Hidden", q, QUAD, tuple(rgb[n_floor + 1]), material="mat-Hidden",
+                                      bsdf=None if lambert else dict(bsdf(n_floor + 1), sheen=0.5, clearcoat=0.5)))
+    return scenes.SceneData(meshes, _camera(W, H, MOSAIC_EYE, MOSAIC_TARGET), _projector(tex), _spot(), 1.0)
+
+
 def path_corner(principled, **kw):
     """tests/test_path_gpu.py's corner: Lambert rows or a principled floor and wall y = 0, no material names"""
     return corner(PRINCIPLED if principled else None, {"roughness": 0.6} if principled else None, materials=False, **kw)

@@ -1,6 +1,6 @@
 """Helpers of the tests that need the device (tests/*_gpu.py and tests/test_hip_parity.py only): arrays to and from it, the oracle's and the device's
 geometry of one scene, what a blob's bin and envelope headers say, a loaded scene with its world arrays, seeded textures and gradient images, the loss
-of a material table, leaves and fits."""
+of a material table, leaves and fits, the rows' and the spot's central differences of the GPU forward, forward mode against the adjoints."""
 import numpy as np
 import torch
 
@@ -123,6 +123,37 @@ def loss(ms, sd, rows, tex, spp, seed, gimg, max_depth=2, rr_depth=5):
     return float((img.double() * gimg.double()).sum())
 
 
+def rows_central_differences(ms, sd, app, rows, tex, spp, seed, gimg, depth, rr, skip=(), h=1e-2):
+    """the rows block of `app` against central differences of render_fwd over every base colour (rows in `skip` excepted: their colour is a texture),
+    roulette off by the caller's rr: 1e-3 of the largest difference -> (the block, the differences' scale)"""
+    g = app.rows.double().cpu().numpy()
+    fd = np.zeros_like(g)
+    for i in range(rows.shape[0]):
+        if i in skip:
+            continue
+        for k in range(3):
+            lo, hi = rows.copy(), rows.copy()
+            lo[i, k] -= h
+            hi[i, k] += h
+            fd[i, k] = (loss(ms, sd, hi, tex, spp, seed, gimg, depth, rr) - loss(ms, sd, lo, tex, spp, seed, gimg, depth, rr)) / (2 * h)
+    scale = np.abs(fd).max()
+    print("rows: max |g - fd|", np.abs(g - fd).max(), "scale", scale)
+    assert scale > 0 and np.abs(g - fd).max() <= 1e-3 * scale, (g, fd)
+    return g, scale
+
+
+def spot_differences(ms, sd, app, mats, tex, spp, seed, gimg, depth, rr):
+    """the spot block of `app` against differences of render_fwd over the intensity (the image is linear in it): 1e-3 of each"""
+    for c in range(3):
+        lo, hi = copy_desc(sd), copy_desc(sd)
+        lo.spot.intensity[c] -= 0.5
+        hi.spot.intensity[c] += 0.5
+        ls = [float((ms.geom.render_fwd(s, mats, tex, spp, seed, max_depth=depth, rr_depth=rr).double() * gimg.double()).sum()) for s in (hi, lo)]
+        f = ls[0] - ls[1]
+        print("spot", c, float(app.spot[c]), f)
+        assert f > 0 and abs(float(app.spot[c]) - f) <= 1e-3 * f
+
+
 def leaf(v):
     return torch.tensor(v, dtype=torch.float32, device=DEV, requires_grad=True)
 
@@ -142,3 +173,63 @@ def fit(ms, key, start, target_img, spp, seed, lr, iters, integrator=None):
         opt.step()
         sched.step()
     return x.detach()
+
+
+# ------------------------------------------------------------------ forward mode against the adjoints: the dot-product identity
+def rand(shape, seed, lo=0.5, hi=1.5):
+    g = torch.Generator().manual_seed(seed)
+    return (lo + (hi - lo) * torch.rand(shape, generator=g)).to(DEV)
+
+
+def tangent(ms, sd, seed):
+    """a random tangent in every block: (dtex, AppearanceGrad)"""
+    S = sd.n_shapes
+    dtex = rand((sd.proj.tex_h, sd.proj.tex_w, sd.proj.tex_channels), seed, -1.0, 1.0) if sd.proj.enabled else None
+    bts = [rand(tuple(t.shape), seed + 10 + k, -1.0, 1.0) for k, (_, t) in enumerate(ms._base_tex)]
+    mat = rand((S, 11), seed + 3, -1.0, 1.0) if int(sd.mat_stride) == scenes.MAT_STRIDE else None
+    return dtex, ops.AppearanceGrad(rand((S, 3), seed + 1, -1.0, 1.0), rand((3,), seed + 2, -1.0, 1.0), bts, mat)
+
+
+def jvp(ms, sd, tex, spp, seed, dtex, tan, depth=2, rr=5):
+    return ms.geom.render_jvp(sd, ms.albedo, tex, spp, seed, dtex=dtex, tangent=tan, max_depth=depth, rr_depth=rr)
+
+
+def adjoint(ms, sd, spp, seed, gimg, tex, depth, rr):
+    material = int(sd.mat_stride) == scenes.MAT_STRIDE
+    if depth == 2:
+        return ms.geom.render_bwd(sd, None if sd.n_mat_h > 0 else ms.albedo, spp, seed, gimg, appearance=True, tex=tex, material=material)
+    return ms.geom.render_bwd_prb(sd, None if sd.n_mat_h > 0 else ms.albedo, spp, seed, gimg, tex, depth, rr, material=material)
+
+
+def pairs(dtex, tan, gtex, app):
+    """(name, tangent block, gradient block) for every block both sides hold"""
+    out = [("tex", dtex, gtex), ("rows", tan.rows, app.rows), ("spot", tan.spot, app.spot)]
+    out += [(f"base_tex[{k}]", t, g) for k, (t, g) in enumerate(zip(tan.base_tex or [], app.base_tex))]
+    if tan.material is not None:
+        out.append(("material", tan.material, app.material))
+    return [(n, t, g) for n, t, g in out if t is not None]
+
+
+def identity(ms, sd, tex, spp, seed, gimg, dtex, tan, depth, rr, what):
+    """|<dimg, gimg> - <tangent, gradient>| <= 1e-3 sum |terms|, the terms being the products the right side sums: the adjoint's entries are sums of
+    float atomics, each good to 1e-3 of its own size, and the inner product weighs entry i by the tangent's entry i.  float64 on the host"""
+    _, dimg = jvp(ms, sd, tex, spp, seed, dtex, tan, depth, rr)
+    gtex, app = adjoint(ms, sd, spp, seed, gimg, tex, depth, rr)
+    lhs = float((dimg.double() * gimg.double()).sum())
+    rhs = terms = 0.0
+    for _, t, g in pairs(dtex, tan, gtex, app):
+        p = t.double().reshape(-1) * g.double().reshape(-1)
+        rhs += float(p.sum())
+        terms += float(p.abs().sum())
+    print(f"{what}: <dimg, gimg> {lhs:.9e}  <tangent, gradient> {rhs:.9e}  |difference| {abs(lhs - rhs):.3e}  1e-3 sum |terms| {1e-3 * terms:.3e}")
+    assert np.isfinite(lhs) and terms > 0 and abs(lhs - rhs) <= 1e-3 * terms, (what, lhs, rhs, terms)
+    return lhs
+
+
+def one_block(dtex, tan, name):
+    """the tangent with every block but `name` zeroed"""
+    z = lambda t: None if t is None else torch.zeros_like(t)  # noqa: E731
+    bts = [t if name == f"base_tex[{k}]" else z(t) for k, t in enumerate(tan.base_tex or [])]
+    return (dtex if name == "tex" else z(dtex),
+            ops.AppearanceGrad(tan.rows if name == "rows" else z(tan.rows), tan.spot if name == "spot" else z(tan.spot), bts,
+                               tan.material if name == "material" else z(tan.material)))

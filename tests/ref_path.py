@@ -77,7 +77,7 @@ def _emitters(sd, tris, rows, P, n, Po, d):
 
 
 def path_vertices(verts, tri_idx, tri_shape, sd, mats, spp, seed, max_depth, rr_depth=5):
-    """every vertex of every sample's path: a list of (sample indices, throughput [n,3], _emitters' terms) in vertex order"""
+    """every vertex of every sample's path: a list of (sample indices, throughput [n,3], _emitters' terms and "shape": the hit shapes) in vertex order"""
     mats = np.asarray(mats, np.float64)
     tris = bf.world_triangles(verts, tri_idx)
     v0, e1, e2 = tris
@@ -98,7 +98,9 @@ def path_vertices(verts, tri_idx, tri_shape, sd, mats, spp, seed, max_depth, rr_
         n = np.where(((n * d).sum(1) > 0)[:, None], -n, n)
         Po = P + n * ((1.0 + np.abs(P).max(1)) * EPS)[:, None]
         rows = mats[np.asarray(tri_shape)[prim]]
-        out.append((idx, beta.copy(), _emitters(sd, tris, rows, P, n, Po, d)))
+        e = _emitters(sd, tris, rows, P, n, Po, d)
+        e["shape"] = np.asarray(tri_shape)[prim]  # (the shape every sample's vertex lies on)
+        out.append((idx, beta.copy(), e))
         if v + 1 >= max_depth:
             break
         wo = cosine_dir(n, path_u(key, idx, v, 0), path_u(key, idx, v, 1))

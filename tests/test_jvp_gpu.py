@@ -29,81 +29,22 @@ def _scene(name, gaussian, **kw):
     return (sc, *gpu.load(sc, gaussian, 1))
 
 
-def _rand(shape, seed, lo=0.5, hi=1.5):
-    g = torch.Generator().manual_seed(seed)
-    return (lo + (hi - lo) * torch.rand(shape, generator=g)).to(DEV)
-
-
-def _tangent(ms, sd, seed):
-    """a random tangent in every block: (dtex, AppearanceGrad)"""
-    S = sd.n_shapes
-    dtex = _rand((sd.proj.tex_h, sd.proj.tex_w, sd.proj.tex_channels), seed, -1.0, 1.0) if sd.proj.enabled else None
-    bts = [_rand(tuple(t.shape), seed + 10 + k, -1.0, 1.0) for k, (_, t) in enumerate(ms._base_tex)]
-    mat = _rand((S, 11), seed + 3, -1.0, 1.0) if int(sd.mat_stride) == scenes.MAT_STRIDE else None
-    return dtex, ops.AppearanceGrad(_rand((S, 3), seed + 1, -1.0, 1.0), _rand((3,), seed + 2, -1.0, 1.0), bts, mat)
-
-
-def _jvp(ms, sd, tex, spp, seed, dtex, tan, depth=2, rr=5):
-    return ms.geom.render_jvp(sd, ms.albedo, tex, spp, seed, dtex=dtex, tangent=tan, max_depth=depth, rr_depth=rr)
-
-
-def _adjoint(ms, sd, spp, seed, gimg, tex, depth, rr):
-    material = int(sd.mat_stride) == scenes.MAT_STRIDE
-    if depth == 2:
-        return ms.geom.render_bwd(sd, None if sd.n_mat_h > 0 else ms.albedo, spp, seed, gimg, appearance=True, tex=tex, material=material)
-    return ms.geom.render_bwd_prb(sd, None if sd.n_mat_h > 0 else ms.albedo, spp, seed, gimg, tex, depth, rr, material=material)
-
-
-def _pairs(dtex, tan, gtex, app):
-    """(name, tangent block, gradient block) for every block both sides hold"""
-    out = [("tex", dtex, gtex), ("rows", tan.rows, app.rows), ("spot", tan.spot, app.spot)]
-    out += [(f"base_tex[{k}]", t, g) for k, (t, g) in enumerate(zip(tan.base_tex or [], app.base_tex))]
-    if tan.material is not None:
-        out.append(("material", tan.material, app.material))
-    return [(n, t, g) for n, t, g in out if t is not None]
-
-
-def _identity(ms, sd, tex, spp, seed, gimg, dtex, tan, depth, rr, what):
-    """|<dimg, gimg> - <tangent, gradient>| <= 1e-3 sum |terms|, the terms being the products the right side sums: the adjoint's entries are sums of
-    float atomics, each good to 1e-3 of its own size, and the inner product weighs entry i by the tangent's entry i.  float64 on the host"""
-    _, dimg = _jvp(ms, sd, tex, spp, seed, dtex, tan, depth, rr)
-    gtex, app = _adjoint(ms, sd, spp, seed, gimg, tex, depth, rr)
-    lhs = float((dimg.double() * gimg.double()).sum())
-    rhs = terms = 0.0
-    for _, t, g in _pairs(dtex, tan, gtex, app):
-        p = t.double().reshape(-1) * g.double().reshape(-1)
-        rhs += float(p.sum())
-        terms += float(p.abs().sum())
-    print(f"{what}: <dimg, gimg> {lhs:.9e}  <tangent, gradient> {rhs:.9e}  |difference| {abs(lhs - rhs):.3e}  1e-3 sum |terms| {1e-3 * terms:.3e}")
-    assert np.isfinite(lhs) and terms > 0 and abs(lhs - rhs) <= 1e-3 * terms, (what, lhs, rhs, terms)
-    return lhs
-
-
-def _one_block(dtex, tan, name):
-    """the tangent with every block but `name` zeroed"""
-    z = lambda t: None if t is None else torch.zeros_like(t)  # noqa: E731
-    bts = [t if name == f"base_tex[{k}]" else z(t) for k, t in enumerate(tan.base_tex or [])]
-    return (dtex if name == "tex" else z(dtex),
-            ops.AppearanceGrad(tan.rows if name == "rows" else z(tan.rows), tan.spot if name == "spot" else z(tan.spot), bts,
-                               tan.material if name == "material" else z(tan.material)))
-
-
 @pytest.mark.parametrize("gaussian", FILMS)
 @pytest.mark.parametrize("name", ["lambert", "every_lobe", "textured"])
 def test_primal_is_render_fwd_bitwise_and_the_tangent_repeats_bitwise(name, gaussian):
     _, ms, sd, _ = _scene(name, gaussian)
     tex = gpu.rand_tex(sd, 1)
-    dtex, tan = _tangent(ms, sd, 7)
+    dtex, tan = gpu.tangent(ms, sd, 7)
     for depth, rr in ((2, 5), (3, 5), (4, 1)):
         ref = ms.geom.render_fwd(sd, None if sd.n_mat_h > 0 else ms.albedo, tex, 16, 3, max_depth=depth, rr_depth=rr).clone()
-        img, dimg = _jvp(ms, sd, tex, 16, 3, dtex, tan, depth, rr)
+        img, dimg = gpu.jvp(ms, sd, tex, 16, 3, dtex, tan, depth, rr)
         img, dimg = img.clone(), dimg.clone()
-        img2, dimg2 = _jvp(ms, sd, tex, 16, 3, dtex, tan, depth, rr)
+        img2, dimg2 = gpu.jvp(ms, sd, tex, 16, 3, dtex, tan, depth, rr)
         print(name, gaussian, depth, "max |img|", float(ref.abs().max()), "max |dimg|", float(dimg.abs().max()))
         assert float(ref.abs().max()) > 0 and torch.equal(img, ref) and torch.equal(img2, ref)
         assert torch.isfinite(dimg).all() and float(dimg.abs().max()) > 0 and torch.equal(dimg, dimg2)
         # a zero tangent gives a zero tangent image, exactly
-        _, d0 = _jvp(ms, sd, tex, 16, 3, None, None, depth, rr)
+        _, d0 = gpu.jvp(ms, sd, tex, 16, 3, None, None, depth, rr)
         assert float(d0.abs().max()) == 0.0
 
 
@@ -123,11 +64,11 @@ def test_linear_special_cases_against_the_forward(gaussian, depth):
         print(f"{what} (depth {depth}, gaussian {gaussian}): max |dimg - forward| {err:.3e}  1e-4 scale {1e-4 * scale:.3e}")
         assert scale > 0 and err <= 1e-4 * scale
 
-    dtex = _rand(tuple(tex.shape), 3, 0.0, 1.0)
-    _, dimg = _jvp(ms, sd, tex, spp, seed, dtex, None, depth, rr)
+    dtex = gpu.rand(tuple(tex.shape), 3, 0.0, 1.0)
+    _, dimg = gpu.jvp(ms, sd, tex, spp, seed, dtex, None, depth, rr)
     check("dtex", dimg, fwd(sd, dtex) - fwd(sd, torch.zeros_like(tex)))
     dspot = torch.tensor([0.5, 2.0, 1.25], device=DEV)
-    _, dimg = _jvp(ms, sd, tex, spp, seed, None, ops.AppearanceGrad(None, dspot, None, None), depth, rr)
+    _, dimg = gpu.jvp(ms, sd, tex, spp, seed, None, ops.AppearanceGrad(None, dspot, None, None), depth, rr)
     s2 = copy_desc(sd)
     for c in range(3):
         s2.spot.intensity[c] = float(dspot[c])
@@ -136,8 +77,8 @@ def test_linear_special_cases_against_the_forward(gaussian, depth):
         return
     _, ms, sd, _ = _scene("lambert", gaussian)
     tex = gpu.rand_tex(sd, 1)
-    db = _rand((sd.n_shapes, 3), 4, 0.1, 0.9)
-    _, dimg = _jvp(ms, sd, tex, spp, seed, None, ops.AppearanceGrad(db, None, None, None))
+    db = gpu.rand((sd.n_shapes, 3), 4, 0.1, 0.9)
+    _, dimg = gpu.jvp(ms, sd, tex, spp, seed, None, ops.AppearanceGrad(db, None, None, None))
     s2 = copy_desc(sd)
     s2.n_mat_h = 0  # (the rows come from the table given)
     check("base colours of Lambert rows", dimg, ms.geom.render_fwd(s2, db.contiguous(), tex, spp, seed))
@@ -152,23 +93,23 @@ def test_dot_product_identity_against_the_adjoints(name, depth, rr, gaussian):
     _, ms, sd, _ = _scene(name, gaussian)
     tex, gimg = gpu.rand_tex(sd, 3), gpu.rand_gimg(sd, 4) - 1.0  # (gimg in -0.5 .. 0.5)
     spp, seed = 16, 5
-    dtex, tan = _tangent(ms, sd, 11)
+    dtex, tan = gpu.tangent(ms, sd, 11)
     what = f"{name} depth {depth} rr {rr} gaussian {gaussian}"
     if name == "bounce" and depth == 2:  # (the emitters light the floor only and the camera sees the wall: nothing arrives without a bounce)
-        gtex, app = _adjoint(ms, sd, spp, seed, gimg, tex, depth, rr)
-        _, dimg = _jvp(ms, sd, tex, spp, seed, dtex, tan, depth, rr)
-        assert all(float(g.abs().max()) == 0.0 for _, _, g in _pairs(dtex, tan, gtex, app)) and float(dimg.abs().max()) == 0.0
+        gtex, app = gpu.adjoint(ms, sd, spp, seed, gimg, tex, depth, rr)
+        _, dimg = gpu.jvp(ms, sd, tex, spp, seed, dtex, tan, depth, rr)
+        assert all(float(g.abs().max()) == 0.0 for _, _, g in gpu.pairs(dtex, tan, gtex, app)) and float(dimg.abs().max()) == 0.0
         return
-    _identity(ms, sd, tex, spp, seed, gimg, dtex, tan, depth, rr, what + " [all blocks]")
-    gtex, app = _adjoint(ms, sd, spp, seed, gimg, tex, depth, rr)
+    gpu.identity(ms, sd, tex, spp, seed, gimg, dtex, tan, depth, rr, what + " [all blocks]")
+    gtex, app = gpu.adjoint(ms, sd, spp, seed, gimg, tex, depth, rr)
     live = 0
-    for n, _, g in _pairs(dtex, tan, gtex, app):
+    for n, _, g in gpu.pairs(dtex, tan, gtex, app):
         if float(g.abs().max()) == 0.0:
             print(f"{what} [{n}]: the adjoint's block is zero; the tangent image must be too")
-            _, dimg = _jvp(ms, sd, tex, spp, seed, *_one_block(dtex, tan, n), depth, rr)
+            _, dimg = gpu.jvp(ms, sd, tex, spp, seed, *gpu.one_block(dtex, tan, n), depth, rr)
             assert float((dimg.double() * gimg.double()).sum().abs()) <= 1e-12
             continue
-        _identity(ms, sd, tex, spp, seed, gimg, *_one_block(dtex, tan, n), depth, rr, f"{what} [{n}]")
+        gpu.identity(ms, sd, tex, spp, seed, gimg, *gpu.one_block(dtex, tan, n), depth, rr, f"{what} [{n}]")
         live += 1
     assert live >= 3
 
@@ -194,10 +135,10 @@ def test_one_sided_bounds_and_eta_1_follow_the_adjoint(corner, depth, rr, gaussi
     rows = ms._albedo_host
     assert rows[0, scenes.MAT_COLUMN["metallic"]] == 1.0 and (rows[[0, 2], scenes.MAT_COLUMN["eta"]] == 1.0).all() == (corner == 0)
     tex, gimg = gpu.rand_tex(sd, 3), gpu.rand_gimg(sd, 4)
-    dtex, tan = _tangent(ms, sd, 21)
+    dtex, tan = gpu.tangent(ms, sd, 21)
     what = f"bounds {corner} depth {depth} rr {rr} gaussian {gaussian}"
-    _identity(ms, sd, tex, 16, 5, gimg, *_one_block(dtex, tan, "material"), depth, rr, what + " [material]")
-    _, app = _adjoint(ms, sd, 16, 5, gimg, tex, depth, rr)
+    gpu.identity(ms, sd, tex, 16, 5, gimg, *gpu.one_block(dtex, tan, "material"), depth, rr, what + " [material]")
+    _, app = gpu.adjoint(ms, sd, 16, 5, gimg, tex, depth, rr)
     m = app.material.cpu().numpy()
     for col in BOUNDS_COLUMNS[corner]:
         j = scenes.MAT_COLUMN[col] - R0
@@ -205,7 +146,7 @@ def test_one_sided_bounds_and_eta_1_follow_the_adjoint(corner, depth, rr, gaussi
         assert np.abs(m[:, j]).max() > 0
         t = torch.zeros_like(tan.material)
         t[:, j] = tan.material[:, j]
-        _identity(ms, sd, tex, 16, 5, gimg, None, ops.AppearanceGrad(None, None, None, t), depth, rr, f"{what} [{col}]")
+        gpu.identity(ms, sd, tex, 16, 5, gimg, None, ops.AppearanceGrad(None, None, None, t), depth, rr, f"{what} [{col}]")
 
 
 @pytest.mark.parametrize("gaussian", FILMS)
@@ -228,7 +169,7 @@ def test_every_pixel_against_the_float64_tangent(depth, rr, gaussian):
     ref = ref_prb.float64_tangent(world, sd, rows, tex.cpu().numpy(), spp, seed, depth, rr, 0.5 if gaussian else None, drows=drows, dtex=dtex, dspot=dspot)
     tan = ops.AppearanceGrad(torch.from_numpy(drows[:, :3].astype(np.float32)), torch.from_numpy(dspot), [],
                              torch.from_numpy(drows[:, R0:R0 + 11].astype(np.float32)))
-    _, dimg = _jvp(ms, sd, tex, spp, seed, torch.from_numpy(dtex), tan, depth, rr)
+    _, dimg = gpu.jvp(ms, sd, tex, spp, seed, torch.from_numpy(dtex), tan, depth, rr)
     err = np.abs(dimg.double().cpu().numpy() - ref).max(-1)
     scale = np.abs(ref).max()
     bad = int((err > 1e-4 * scale).sum())
@@ -250,7 +191,7 @@ def test_mi_render_forward_end_to_end():
     rows_f = ms._material_meshes["mat-Floor"]
     assert len(rows_f) == 2
     spec = float(fb["specular"])
-    dt = _rand((sd.proj.tex_h, sd.proj.tex_w), 9, -1.0, 1.0)
+    dt = gpu.rand((sd.proj.tex_h, sd.proj.tex_w), 9, -1.0, 1.0)
     tangents = {"tex.data": dt, F + "base_color.value": torch.tensor([0.3, -0.2, 0.5]), F + "roughness.value": torch.tensor(0.7), F + "specular": 0.4,
                 F + "eta": 5.0, F + "clearcoat.value": -0.3, "mat-WallY.brdf_0.sheen.value": 1.0, spot: torch.tensor([1.0, 0.5, 2.0])}
     S = sd.n_shapes
@@ -265,7 +206,7 @@ def test_mi_render_forward_end_to_end():
     for it, depth, rr in ((None, 2, 5), (mi.load_dict({"type": "direct"}), 2, 5), (mi.load_dict({"type": "prb", "max_depth": 3, "rr_depth": 2}), 3, 2)):
         img, dimg = mi.render_forward(ms, p, tangents, spp=16, seed=3, integrator=it)
         sd_now = ms.scene_desc(tex_channels=1)
-        want_img, want = _jvp(ms, sd_now, tex, 16, 3, dt.unsqueeze(-1), want_tan, depth, rr)
+        want_img, want = gpu.jvp(ms, sd_now, tex, 16, 3, dt.unsqueeze(-1), want_tan, depth, rr)
         print("mi.render_forward", it, "max |dimg|", float(want.abs().max()), "max |difference|", float((dimg.torch() - want).abs().max()))
         assert float(want.abs().max()) > 0 and torch.equal(dimg.torch(), want) and torch.equal(img.torch(), want_img)
         assert torch.equal(img.torch(), mi.render(ms, spp=16, seed=3, integrator=it).torch())
@@ -288,7 +229,7 @@ def test_mi_render_forward_end_to_end():
     mat2 = torch.zeros((S, 11))
     mat2[rows_f, scenes.MAT_COLUMN["eta"] - R0] = 5.0
     got = mi.render_forward(ms, p, only, spp=16, seed=3)[1].torch()
-    want = _jvp(ms, sd_now, tex, 16, 3, None, ops.AppearanceGrad(None, None, [], mat2))[1]
+    want = gpu.jvp(ms, sd_now, tex, 16, 3, None, ops.AppearanceGrad(None, None, [], mat2))[1]
     print("eta drives the row: max |dimg|", float(want.abs().max()))
     assert float(want.abs().max()) > 0 and torch.equal(got, want)
     # ... and back
@@ -297,7 +238,7 @@ def test_mi_render_forward_end_to_end():
     sd_now = ms.scene_desc(tex_channels=1)
     mat2[rows_f, scenes.MAT_COLUMN["eta"] - R0] = chain(0.0)  # (the finite limit at 0)
     got = mi.render_forward(ms, p, only, spp=16, seed=3)[1].torch()
-    want = _jvp(ms, sd_now, tex, 16, 3, None, ops.AppearanceGrad(None, None, [], mat2))[1]
+    want = gpu.jvp(ms, sd_now, tex, 16, 3, None, ops.AppearanceGrad(None, None, [], mat2))[1]
     print("specular = 0 drives the row: max |dimg|", float(want.abs().max()))
     assert float(want.abs().max()) > 0 and torch.equal(got, want)
 
@@ -312,13 +253,13 @@ def _full_size(gaussian):
     tex = workloads.build_texture(wl).detach().unsqueeze(-1).contiguous()
     sd = ms.scene_desc(tex_channels=1)
     assert (sd.cam.width, sd.cam.height) == (512, 512)
-    gimg = _rand((512, 512, 3), 1, -1.0, 1.0) / (512 * 512)
-    dtex, tan = _tangent(ms, sd, 31)
+    gimg = gpu.rand((512, 512, 3), 1, -1.0, 1.0) / (512 * 512)
+    dtex, tan = gpu.tangent(ms, sd, 31)
     for depth in (2, 3):
         ref = ms.geom.render_fwd(sd, ms.materials_arg(sd), tex, 64, 1, max_depth=depth, rr_depth=depth).clone()
-        img, dimg = _jvp(ms, sd, tex, 64, 1, dtex, tan, depth, depth)
+        img, dimg = gpu.jvp(ms, sd, tex, 64, 1, dtex, tan, depth, depth)
         assert torch.equal(img, ref) and torch.isfinite(dimg).all() and float(dimg.abs().max()) > 0
-        _identity(ms, sd, tex, 64, 1, gimg, dtex, tan, depth, depth, f"vocal fold depth {depth} gaussian {gaussian}")
+        gpu.identity(ms, sd, tex, 64, 1, gimg, dtex, tan, depth, depth, f"vocal fold depth {depth} gaussian {gaussian}")
 
 
 @pytest.mark.parametrize("gaussian", FILMS)

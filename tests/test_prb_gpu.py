@@ -81,35 +81,17 @@ def test_blocks_match_central_differences_of_the_gpu_forward(name, gaussian, dep
     ts = float(gtex_ref.abs().max())
     print("gtex: max |prb - render_bwd|", float((gtex - gtex_ref).abs().max()), "scale", ts)
     assert ts > 0 and float((gtex - gtex_ref).abs().max()) <= 1e-3 * ts
-    # rows' colours (central differences are exact for the polynomial the image is in a colour up to h^2 f''' / 6 at depth 4)
-    g = app.rows.double().cpu().numpy()
-    fd = np.zeros_like(g)
-    h = 1e-2
-    for i in range(rows.shape[0]):
-        if bt is not None and i == 0:
-            continue  # (the floor's colour is its texture)
-        for k in range(3):
-            lo, hi = rows.copy(), rows.copy()
-            lo[i, k] -= h
-            hi[i, k] += h
-            fd[i, k] = (gpu.loss(ms, sd, hi, tex, spp, seed, gimg, depth, rr) - gpu.loss(ms, sd, lo, tex, spp, seed, gimg, depth, rr)) / (2 * h)
-    scale = np.abs(fd).max()
-    print("rows: max |g - fd|", np.abs(g - fd).max(), "scale", scale)
-    assert scale > 0 and np.abs(g - fd).max() <= 1e-3 * scale, (g, fd)
+    # rows' colours (central differences are exact for the polynomial the image is in a colour up to h^2 f''' / 6 at depth 4); the floor's colour may be
+    # its texture
+    g, scale = gpu.rows_central_differences(ms, sd, app, rows, tex, spp, seed, gimg, depth, rr, skip=(0,) if bt is not None else ())
     # the bounces matter: the direct-light adjoint's rows differ
     _, app2 = _blocks(ms, sd, spp, seed, gimg, tex, 2, 5)
     assert np.abs(g - app2.rows.double().cpu().numpy()).max() > 1e-2 * scale
     # the spot's intensity
-    for c in range(3):
-        lo, hi = copy_desc(sd), copy_desc(sd)
-        lo.spot.intensity[c] -= 0.5
-        hi.spot.intensity[c] += 0.5
-        ls = [float((ms.geom.render_fwd(s, None, tex, spp, seed, max_depth=depth, rr_depth=rr).double() * gimg.double()).sum()) for s in (hi, lo)]
-        f = ls[0] - ls[1]
-        print("spot", c, float(app.spot[c]), f)
-        assert f > 0 and abs(float(app.spot[c]) - f) <= 1e-3 * f
+    gpu.spot_differences(ms, sd, app, None, tex, spp, seed, gimg, depth, rr)
     # a base-colour texture: directional derivatives
     if bt is not None:
+        h = 1e-2
         t = ms._base_tex[0][1]
         gb = app.base_tex[0]
         assert float(app.rows[0].abs().max()) == 0 and float(gb.abs().sum()) > 0
