@@ -47,7 +47,11 @@ struct CamK {
 // the factor exp(2 alpha x0) stays inside float's range — narrower filters keep the five exponentials).  Every kernel that forms weights
 // calls rf_weights, so forward, adjoint and cache agree bit for bit; the oracle's five expf differ in the last bits (1e-6 of a weight).
 struct RfC { float alpha, bias, aL, aL2, k[4]; int rec; };
-#define FFX_PRE_FLOATS 12 // floats per pre-row: eta, 1/eta^2, a2, 1/a2, metallic, c_sw, c_fd, brdf, 2 roughness, lobe flags (bits), roughness^2, tint term
+// the columns of a pre-row (ShadeK.mat_pre; mat_pre_row fills them, RowPre reads them), m1 = 1 - metallic: eta, 1 / eta^2, a2 = max(0.001, roughness^2)^2, 1 / a2,
+// metallic, the Fresnel mix's coefficients of the Schlick weight (metallic + m1 spec_tint) and of the dielectric term (m1 (1 - spec_tint)), the diffuse weight
+// m1 (1 - spec_trans), 2 roughness, the lobe flags below (an integer's bits), roughness^2, the tint term m1 spec_tint ((eta - 1) / (eta + 1))^2
+enum { FFX_PRE_ETA, FFX_PRE_INV_ETA2, FFX_PRE_A2, FFX_PRE_INV_A2, FFX_PRE_METALLIC, FFX_PRE_C_SW, FFX_PRE_C_FD, FFX_PRE_BRDF, FFX_PRE_ROUGH2, FFX_PRE_FLAGS, FFX_PRE_R2,
+       FFX_PRE_TINT_TERM, FFX_PRE_FLOATS /* floats per pre-row */ };
 #define FFX_PRE_ANISO 1u
 #define FFX_PRE_TINT 2u
 #define FFX_PRE_CLEARCOAT 4u
@@ -428,7 +432,54 @@ struct MatGeo {
   float s2;                           // sin^2(theta_h) = hx^2 + hy^2 — NEVER as 1 - ch^2: near-mirror rows (alpha = 0.0025) and a glossy
                                       // clearcoat (alpha = 0.001) divide it by alpha^2, which turned the rounding of ch into 0.4 % of a highlight
 };
-__device__ __forceinline__ void material_geometry(const float *__restrict__ m, v3 n, v3 wv, v3 wl, MatGeo &g) {
+static __constant__ constexpr float FFX_LUM_W[3] = {0.212671f, 0.715160f, 0.072169f}; // the luminance weights w of the tint terms
+__device__ __forceinline__ float lum3(float r, float g, float b) { return FFX_LUM_W[0] * r + FFX_LUM_W[1] * g + FFX_LUM_W[2] * b; }
+// where the BSDF takes a row's constants from.  RowRaw: the material row m itself, derived per evaluation with the hardware seeds.  RowPre: the row
+// plus the constants the host has derived from it once (ShadeK.mat_pre, columns FFX_PRE_*): no squares, clamps and reciprocals of parameters per
+// evaluation, one flag word instead of five parameter loads and compares — with the host's IEEE values where RowRaw forms hardware seeds (a
+// last-bit difference in 1 / a2, 1 / eta^2 and the tint term, inside the parity tolerance).  PLAIN (k_render_fwd_pk's plain-scene instance): the
+// host found no lobe flag set in any row — the flag word is the constant 0, the optional lobes' tests and arms are not compiled
+struct RowRaw {
+  const float *__restrict__ m;
+  __device__ __forceinline__ float m1() const { return 1.0f - m[FFX_MAT_METALLIC]; }
+  __device__ __forceinline__ bool aniso() const { return m[FFX_MAT_ANISOTROPIC] != 0.f; }
+  __device__ __forceinline__ bool tint() const { return m[FFX_MAT_SPEC_TINT] != 0.f; }
+  __device__ __forceinline__ bool clearcoat() const { return m[FFX_MAT_CLEARCOAT] > 0.f; }
+  __device__ __forceinline__ bool flat() const { return m[FFX_MAT_FLATNESS] > 0.f; }
+  __device__ __forceinline__ bool sheen() const { return m[FFX_MAT_SHEEN] > 0.f && m1() > 0.f; }
+  __device__ __forceinline__ float r2() const { return sqrf(m[FFX_MAT_ROUGHNESS]); }
+  __device__ __forceinline__ float a2() const { return sqrf(fmaxf(0.001f, r2())); }
+  __device__ __forceinline__ float tmp_iso(float s2, float ch) const { return bdiv(s2, a2()) + sqrf(ch); }
+  __device__ __forceinline__ float rough2() const { return 2.0f * m[FFX_MAT_ROUGHNESS]; }
+  __device__ __forceinline__ float eta() const { return m[FFX_MAT_ETA]; }
+  __device__ __forceinline__ float inv_eta2() const { return sqrf(brcp(eta())); }
+  __device__ __forceinline__ float metallic() const { return m[FFX_MAT_METALLIC]; }
+  __device__ __forceinline__ float Fb(float sw, float F_d) const { return metallic() * sw + m1() * m[FFX_MAT_SPEC_TINT] * sw + m1() * (1.0f - m[FFX_MAT_SPEC_TINT]) * F_d; }
+  __device__ __forceinline__ float tint_term() const { return m1() * m[FFX_MAT_SPEC_TINT] * sqrf((eta() - 1.0f) * brcp(eta() + 1.0f)); }
+  __device__ __forceinline__ float brdf() const { return m1() * (1.0f - m[FFX_MAT_SPEC_TRANS]); }
+};
+template <bool PLAIN = false>
+struct RowPre {
+  const float *__restrict__ m, *__restrict__ p;
+  __device__ __forceinline__ uint32_t flags() const { return PLAIN ? 0u : __float_as_uint(p[FFX_PRE_FLAGS]); }
+  __device__ __forceinline__ bool aniso() const { return flags() & FFX_PRE_ANISO; }
+  __device__ __forceinline__ bool tint() const { return flags() & FFX_PRE_TINT; }
+  __device__ __forceinline__ bool clearcoat() const { return flags() & FFX_PRE_CLEARCOAT; }
+  __device__ __forceinline__ bool flat() const { return flags() & FFX_PRE_FLAT; }
+  __device__ __forceinline__ bool sheen() const { return flags() & FFX_PRE_SHEEN; }
+  __device__ __forceinline__ float r2() const { return p[FFX_PRE_R2]; }
+  __device__ __forceinline__ float a2() const { return p[FFX_PRE_A2]; }
+  __device__ __forceinline__ float tmp_iso(float s2, float ch) const { return fmaf(s2, p[FFX_PRE_INV_A2], sqrf(ch)); }
+  __device__ __forceinline__ float rough2() const { return p[FFX_PRE_ROUGH2]; }
+  __device__ __forceinline__ float eta() const { return p[FFX_PRE_ETA]; }
+  __device__ __forceinline__ float inv_eta2() const { return p[FFX_PRE_INV_ETA2]; }
+  __device__ __forceinline__ float metallic() const { return p[FFX_PRE_METALLIC]; }
+  __device__ __forceinline__ float Fb(float sw, float F_d) const { return fmaf(p[FFX_PRE_C_SW], sw, p[FFX_PRE_C_FD] * F_d); }
+  __device__ __forceinline__ float tint_term() const { return p[FFX_PRE_TINT_TERM]; }
+  __device__ __forceinline__ float brdf() const { return p[FFX_PRE_BRDF]; }
+};
+template <class Row>
+__device__ __forceinline__ void material_geometry(const Row &row, v3 n, v3 wv, v3 wl, MatGeo &g) {
   g.cos_i = vdot(n, wv);
   g.cos_o = vdot(n, wl);
   v3 wh = V3(wv.x + wl.x, wv.y + wl.y, wv.z + wl.z);
@@ -437,9 +488,8 @@ __device__ __forceinline__ void material_geometry(const float *__restrict__ m, v
   g.ci_h = vdot(wv, wh);
   g.co_h = vdot(wl, wh);
   g.ch = vdot(n, wh);
-  const float r2 = sqrf(m[FFX_MAT_ROUGHNESS]), aniso = m[FFX_MAT_ANISOTROPIC];
-  if (aniso != 0.f) { // calc_dist_params + the shading frame coordinate_system(n)
-    const float aspect = bsqrt(1.0f - 0.9f * aniso);
+  if (row.aniso()) { // calc_dist_params + the shading frame coordinate_system(n)
+    const float r2 = row.r2(), aspect = bsqrt(1.0f - 0.9f * row.m[FFX_MAT_ANISOTROPIC]);
     const float ax = fmaxf(0.001f, bdiv(r2, aspect)), ay = fmaxf(0.001f, r2 * aspect);
     const float sg = copysignf(1.0f, n.z), ca = -brcp(sg + n.z), cb = n.x * n.y * ca;
     const v3 fs = V3(sg * (sqrf(n.x) * ca) + 1.0f, sg * cb, -sg * n.x), ft = V3(cb, fmaf(n.y, n.y * ca, sg), -n.y);
@@ -450,10 +500,10 @@ __device__ __forceinline__ void material_geometry(const float *__restrict__ m, v
     g.xy_o = sqrf(ax * vdot(wl, fs)) + sqrf(ay * vdot(wl, ft));
     g.axay = ax * ay;
   } else {
-    const float a2 = sqrf(fmaxf(0.001f, r2));
+    const float a2 = row.a2();
     const v3 cx = vcross(n, wh); // |n x h|^2 = sin^2(theta_h), well conditioned at the peak (same order as the oracle's material_geometry)
     g.s2 = vdot(cx, cx);
-    g.tmp = bdiv(g.s2, a2) + sqrf(g.ch);
+    g.tmp = row.tmp_iso(g.s2, g.ch);
     g.xy_i = a2 * fmaxf(1.0f - sqrf(g.cos_i), 0.f);
     g.xy_o = a2 * fmaxf(1.0f - sqrf(g.cos_o), 0.f);
     g.axay = a2;
@@ -470,17 +520,17 @@ __device__ __forceinline__ float ggx1_cc(float c, float c_dot_h) { // smith_ggx1
 // TEX: the base colour is (b0, b1, b2) — the row's texture sampled at the hit — instead of the row's own m[0..2]
 // TAU (the appearance adjoint): *tau receives pi tau, the numerators of the tint terms that A divides by lum (A = A0 + pi tau / lum;
 // 0 when lum <= 0, where the tints went to B)
-template <bool TEX = false, bool TAU = false>
-__device__ __forceinline__ void material_terms(const float *__restrict__ m, const MatGeo &g, float &A, float &B, float b0 = 0.f, float b1 = 0.f, float b2 = 0.f,
-                                               float *tau = nullptr) {
+template <bool TEX = false, bool TAU = false, class Row>
+__device__ __forceinline__ void material_terms(const Row &row, const MatGeo &g, float &A, float &B, float b0 = 0.f, float b1 = 0.f, float b2 = 0.f, float *tau = nullptr) {
+  const float *__restrict__ m = row.m;
   const float cos_i = g.cos_i, cos_o = g.cos_o, ch = g.ch, ci_h = g.ci_h, co_h = g.co_h;
   A = 0.f; B = 0.f;
   if (TAU) *tau = 0.f;
   if (!(cos_i > 0.f && cos_o > 0.f)) return;
   const bool facing = ci_h > 0.f && co_h > 0.f; // (cos_i, cos_o > 0)
   float a = 0.f, b = 0.f, tu = 0.f;
-  const float eta = m[FFX_MAT_ETA];
-  const float ct2 = 1.0f - (1.0f - ci_h * ci_h) * sqrf(brcp(eta));
+  const float eta = row.eta();
+  const float ct2 = 1.0f - (1.0f - ci_h * ci_h) * row.inv_eta2();
   const float ct = ct2 > 0.f ? bsqrt(ct2) : 0.f; // cosine of the transmitted direction
   const float sw = schlick_weight(eta > 1.0f ? fabsf(ci_h) : ct);
   float F_d;
@@ -492,26 +542,25 @@ __device__ __forceinline__ void material_terms(const float *__restrict__ m, cons
     if (eta == 1.0f) F_d = 0.f;
     else if (c == 0.f) F_d = 1.f;
   }
-  const float metallic = m[FFX_MAT_METALLIC];
+  const float metallic = row.metallic();
   if (facing && F_d > 0.f) { // main specular reflection lobe: F D G / (4 cos_i)
     const float dden = FFX_PI_F * g.axay * sqrf(g.tmp);
     const float s_i = bsqrt(sqrf(cos_i) + g.xy_i), s_o = bsqrt(sqrf(cos_o) + g.xy_o);
     // D G / (4 cos_i) = cos_o / (dden (cos_i + s_i)(cos_o + s_o))
     float common = bdiv(cos_o, dden * ((cos_i + s_i) * (cos_o + s_o)));
     if (!(ch > 1e-20f * dden)) common = 0.f; // D * cos_h > 1e-20
-    const float spec_tint = m[FFX_MAT_SPEC_TINT], m1 = 1.0f - metallic;
-    float Fa = metallic * (1.0f - sw), Fb = metallic * sw + m1 * spec_tint * sw + m1 * (1.0f - spec_tint) * F_d;
-    if (spec_tint != 0.f) {
-      const float lum = TEX ? 0.212671f * b0 + 0.715160f * b1 + 0.072169f * b2 : 0.212671f * m[0] + 0.715160f * m[1] + 0.072169f * m[2];
-      const float t = m1 * spec_tint * sqrf((eta - 1.0f) * brcp(eta + 1.0f)) * (1.0f - sw);
+    float Fa = metallic * (1.0f - sw), Fb = row.Fb(sw, F_d); // Fb = (metallic + m1 spec_tint) sw + m1 (1 - spec_tint) F_d, m1 = 1 - metallic
+    if (row.tint()) {
+      const float lum = TEX ? lum3(b0, b1, b2) : lum3(m[0], m[1], m[2]);
+      const float t = row.tint_term() * (1.0f - sw); // m1 spec_tint R0 (1 - sw)
       if (lum > 0.f) { Fa += bdiv(t, lum); if (TAU) tu += t * common; }
       else Fb += t;
     }
     a += Fa * common;
     b += Fb * common;
   }
-  const float cc = m[FFX_MAT_CLEARCOAT];
-  if (cc > 0.f && facing) { // clearcoat
+  if (row.clearcoat() && facing) {
+    const float cc = m[FFX_MAT_CLEARCOAT];
     const float Fcc = sw + (1.0f - sw) * 0.04f;
     const float alpha = 0.1f + (0.001f - 0.1f) * m[FFX_MAT_CLEARCOAT_GLOSS], a2 = sqrf(alpha), c2 = sqrf(ch);
     float Dcc = bdiv(a2 - 1.0f, FFX_PI_F * logf(a2) * (g.s2 + a2 * c2)); // GTR1: 1 + (a2 - 1) cos^2 = sin^2 + a2 cos^2, without the cancellation
@@ -519,15 +568,15 @@ __device__ __forceinline__ void material_terms(const float *__restrict__ m, cons
     const float Gcc = ggx1_cc(cos_i, ci_h) * ggx1_cc(cos_o, co_h);
     b += cc * 0.25f * Fcc * Dcc * Gcc * cos_o;
   }
-  const float brdf = (1.0f - metallic) * (1.0f - m[FFX_MAT_SPEC_TRANS]);
+  const float brdf = row.brdf();
   if (brdf > 0.f) { // diffuse + retro-reflection (+ fake subsurface)
     const float Fo = schlick_weight(cos_o), Fi = schlick_weight(cos_i);
     const float f_diff = (1.0f - 0.5f * Fi) * (1.0f - 0.5f * Fo);
-    const float Rr = 2.0f * m[FFX_MAT_ROUGHNESS] * sqrf(co_h);
+    const float Rr = row.rough2() * sqrf(co_h);
     const float f_retro = Rr * (Fo + Fi + Fo * Fi * (Rr - 1.0f));
     float dterm = f_diff + f_retro;
-    const float flat = m[FFX_MAT_FLATNESS];
-    if (flat > 0.f) {
+    if (row.flat()) {
+      const float flat = m[FFX_MAT_FLATNESS];
       const float Fss90 = Rr * 0.5f;
       const float Fss = (1.0f + (Fss90 - 1.0f) * Fo) * (1.0f + (Fss90 - 1.0f) * Fi);
       const float f_ss = 1.25f * (Fss * (brcp(cos_o + cos_i) - 0.5f) + 0.5f);
@@ -535,10 +584,9 @@ __device__ __forceinline__ void material_terms(const float *__restrict__ m, cons
     }
     a += brdf * cos_o * 0.3183098861837907f * dterm;
   }
-  const float sheen = m[FFX_MAT_SHEEN];
-  if (sheen > 0.f && 1.0f - metallic > 0.f) {
-    const float sv = sheen * (1.0f - metallic) * schlick_weight(fabsf(co_h)) * cos_o;
-    const float lum = TEX ? 0.212671f * b0 + 0.715160f * b1 + 0.072169f * b2 : 0.212671f * m[0] + 0.715160f * m[1] + 0.072169f * m[2], sheen_tint = m[FFX_MAT_SHEEN_TINT];
+  if (row.sheen()) {
+    const float sv = m[FFX_MAT_SHEEN] * (1.0f - metallic) * schlick_weight(fabsf(co_h)) * cos_o;
+    const float lum = TEX ? lum3(b0, b1, b2) : lum3(m[0], m[1], m[2]), sheen_tint = m[FFX_MAT_SHEEN_TINT];
     if (lum > 0.f) { a += bdiv(sv * sheen_tint, lum); b += sv * (1.0f - sheen_tint); if (TAU) tu += sv * sheen_tint; }
     else b += sv;
   }
@@ -677,117 +725,6 @@ __device__ __forceinline__ void material_terms_vjp(const float *__restrict__ m, 
   gr[AN] += 0.45f * r2 * (bdiv(dx, aspect * aspect * aspect) - bdiv(dy, aspect));
 }
 
-// ---- the same two functions on a row whose constants the host has derived once (ShadeK.mat_pre, FFX_PRE_FLOATS floats per row): no squares, clamps
-// and reciprocals of parameters per evaluation, one flag word instead of five parameter loads and compares.  The arithmetic of the lobes is
-// material_terms', with the host's IEEE values where that one forms hardware seeds (a last-bit difference, inside the parity tolerance).
-// PLAIN (k_render_fwd_pk's plain-scene instance): the host found no lobe flag set in any row — the flag word is the constant 0, the optional
-// lobes' tests and arms are not compiled; what remains is the arithmetic above, operation for operation
-template <bool PLAIN = false>
-__device__ __forceinline__ void material_geometry_p(const float *__restrict__ m, const float *__restrict__ p, v3 n, v3 wv, v3 wl, MatGeo &g) {
-  g.cos_i = vdot(n, wv);
-  g.cos_o = vdot(n, wl);
-  v3 wh = V3(wv.x + wl.x, wv.y + wl.y, wv.z + wl.z);
-  const float ihl = __builtin_amdgcn_rsqf(vdot(wh, wh));
-  wh = V3(wh.x * ihl, wh.y * ihl, wh.z * ihl);
-  g.ci_h = vdot(wv, wh);
-  g.co_h = vdot(wl, wh);
-  g.ch = vdot(n, wh);
-  if ((PLAIN ? 0u : __float_as_uint(p[9])) & FFX_PRE_ANISO) { // calc_dist_params + the shading frame coordinate_system(n): as material_geometry
-    const float r2 = p[10], aniso = m[FFX_MAT_ANISOTROPIC];
-    const float aspect = bsqrt(1.0f - 0.9f * aniso);
-    const float ax = fmaxf(0.001f, bdiv(r2, aspect)), ay = fmaxf(0.001f, r2 * aspect);
-    const float sg = copysignf(1.0f, n.z), ca = -brcp(sg + n.z), cb = n.x * n.y * ca;
-    const v3 fs = V3(sg * (sqrf(n.x) * ca) + 1.0f, sg * cb, -sg * n.x), ft = V3(cb, fmaf(n.y, n.y * ca, sg), -n.y);
-    const float hx = vdot(wh, fs), hy = vdot(wh, ft);
-    g.s2 = sqrf(hx) + sqrf(hy);
-    g.tmp = sqrf(bdiv(hx, ax)) + sqrf(bdiv(hy, ay)) + sqrf(g.ch);
-    g.xy_i = sqrf(ax * vdot(wv, fs)) + sqrf(ay * vdot(wv, ft));
-    g.xy_o = sqrf(ax * vdot(wl, fs)) + sqrf(ay * vdot(wl, ft));
-    g.axay = ax * ay;
-  } else {
-    const float a2 = p[2];
-    const v3 cx = vcross(n, wh);
-    g.s2 = vdot(cx, cx);
-    g.tmp = fmaf(g.s2, p[3], sqrf(g.ch));
-    g.xy_i = a2 * fmaxf(1.0f - sqrf(g.cos_i), 0.f);
-    g.xy_o = a2 * fmaxf(1.0f - sqrf(g.cos_o), 0.f);
-    g.axay = a2;
-  }
-}
-template <bool TEX = false, bool PLAIN = false>
-__device__ __forceinline__ void material_terms_p(const float *__restrict__ m, const float *__restrict__ p, const MatGeo &g, float &A, float &B, float b0 = 0.f, float b1 = 0.f,
-                                                 float b2 = 0.f) {
-  const float cos_i = g.cos_i, cos_o = g.cos_o, ch = g.ch, ci_h = g.ci_h, co_h = g.co_h;
-  A = 0.f; B = 0.f;
-  if (!(cos_i > 0.f && cos_o > 0.f)) return;
-  const bool facing = ci_h > 0.f && co_h > 0.f;
-  float a = 0.f, b = 0.f;
-  const float eta = p[0];
-  const uint32_t flags = PLAIN ? 0u : __float_as_uint(p[9]);
-  const float ct2 = 1.0f - (1.0f - ci_h * ci_h) * p[1];
-  const float ct = ct2 > 0.f ? bsqrt(ct2) : 0.f;
-  const float sw = schlick_weight(eta > 1.0f ? fabsf(ci_h) : ct);
-  float F_d;
-  {
-    const float c = fabsf(ci_h);
-    const float ds = c + eta * ct, dp = ct + eta * c, ir = brcp(ds * dp);
-    const float a_s = (c - eta * ct) * dp * ir, a_p = (ct - eta * c) * ds * ir;
-    F_d = 0.5f * (a_s * a_s + a_p * a_p);
-    if (eta == 1.0f) F_d = 0.f;
-    else if (c == 0.f) F_d = 1.f;
-  }
-  const float metallic = p[4];
-  if (facing && F_d > 0.f) { // main specular reflection lobe
-    const float dden = FFX_PI_F * g.axay * sqrf(g.tmp);
-    const float s_i = bsqrt(sqrf(cos_i) + g.xy_i), s_o = bsqrt(sqrf(cos_o) + g.xy_o);
-    float common = bdiv(cos_o, dden * ((cos_i + s_i) * (cos_o + s_o)));
-    if (!(ch > 1e-20f * dden)) common = 0.f;
-    float Fa = metallic * (1.0f - sw), Fb = fmaf(p[5], sw, p[6] * F_d); // (metallic + m1 spec_tint) sw + m1 (1 - spec_tint) F_d
-    if (flags & FFX_PRE_TINT) {
-      const float lum = TEX ? 0.212671f * b0 + 0.715160f * b1 + 0.072169f * b2 : 0.212671f * m[0] + 0.715160f * m[1] + 0.072169f * m[2];
-      const float t = p[11] * (1.0f - sw);
-      if (lum > 0.f) Fa += bdiv(t, lum);
-      else Fb += t;
-    }
-    a += Fa * common;
-    b += Fb * common;
-  }
-  if ((flags & FFX_PRE_CLEARCOAT) && facing) {
-    const float cc = m[FFX_MAT_CLEARCOAT];
-    const float Fcc = sw + (1.0f - sw) * 0.04f;
-    const float alpha = 0.1f + (0.001f - 0.1f) * m[FFX_MAT_CLEARCOAT_GLOSS], a2 = sqrf(alpha), c2 = sqrf(ch);
-    float Dcc = bdiv(a2 - 1.0f, FFX_PI_F * logf(a2) * (g.s2 + a2 * c2));
-    if (!(Dcc * ch > 1e-20f)) Dcc = 0.f;
-    const float Gcc = ggx1_cc(cos_i, ci_h) * ggx1_cc(cos_o, co_h);
-    b += cc * 0.25f * Fcc * Dcc * Gcc * cos_o;
-  }
-  const float brdf = p[7];
-  if (brdf > 0.f) { // diffuse + retro-reflection (+ fake subsurface)
-    const float Fo = schlick_weight(cos_o), Fi = schlick_weight(cos_i);
-    const float f_diff = (1.0f - 0.5f * Fi) * (1.0f - 0.5f * Fo);
-    const float Rr = p[8] * sqrf(co_h);
-    const float f_retro = Rr * (Fo + Fi + Fo * Fi * (Rr - 1.0f));
-    float dterm = f_diff + f_retro;
-    if (flags & FFX_PRE_FLAT) {
-      const float flat = m[FFX_MAT_FLATNESS];
-      const float Fss90 = Rr * 0.5f;
-      const float Fss = (1.0f + (Fss90 - 1.0f) * Fo) * (1.0f + (Fss90 - 1.0f) * Fi);
-      const float f_ss = 1.25f * (Fss * (brcp(cos_o + cos_i) - 0.5f) + 0.5f);
-      dterm = dterm + (f_ss - dterm) * flat;
-    }
-    a += brdf * cos_o * 0.3183098861837907f * dterm;
-  }
-  if (flags & FFX_PRE_SHEEN) {
-    const float sheen = m[FFX_MAT_SHEEN];
-    const float sv = sheen * (1.0f - metallic) * schlick_weight(fabsf(co_h)) * cos_o;
-    const float lum = TEX ? 0.212671f * b0 + 0.715160f * b1 + 0.072169f * b2 : 0.212671f * m[0] + 0.715160f * m[1] + 0.072169f * m[2], sheen_tint = m[FFX_MAT_SHEEN_TINT];
-    if (lum > 0.f) { a += bdiv(sv * sheen_tint, lum); b += sv * (1.0f - sheen_tint); }
-    else b += sv;
-  }
-  A = a * FFX_PI_F;
-  B = b * FFX_PI_F;
-}
-
 struct SampleTerms {
   int hit, shape, has_proj;
   int ubx, uby; // unclamped bilinear base texel (for the per-sample cache)
@@ -800,6 +737,61 @@ struct SampleTerms {
 };
 
 __device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
+// the bilinear footprint of a projector sample at (u, v) in [0, 1]^2 of a tw x th texture: base texel, four clamped taps, their weights
+__device__ __forceinline__ void sample_footprint(SampleTerms &st, float u, float v, int tw, int th) {
+  float fx = fmaf(u, (float)tw, -0.5f), fy = fmaf(v, (float)th, -0.5f);
+  float x0 = floorf(fx), y0 = floorf(fy);
+  float ax = fx - x0, ay = fy - y0;
+  int ix0 = (int)x0, iy0 = (int)y0;
+  st.ubx = ix0; st.uby = iy0;
+  st.ix0 = clampi(ix0, 0, tw - 1);
+  st.ix1 = clampi(ix0 + 1, 0, tw - 1);
+  st.iy0 = clampi(iy0, 0, th - 1);
+  st.iy1 = clampi(iy0 + 1, 0, th - 1);
+  st.wx0 = 1.0f - ax; st.wx1 = ax;
+  st.wy0 = 1.0f - ay; st.wy1 = ay;
+  st.has_proj = 1;
+}
+// pi f cos = base * bA + bB of a principled row from either source, directions -> cosines (MatGeo) -> lobes
+template <bool TEX, class Row>
+__device__ __forceinline__ void row_lobes(const Row &row, v3 n, v3 wv, v3 wi, const float (&base)[3], float &bA, float &bB) {
+  MatGeo g;
+  material_geometry(row, n, wv, wi, g);
+  material_terms<TEX>(row, g, bA, bB, base[0], base[1], base[2]);
+}
+// the packet kernels' BSDF of one emitter at pos for the sample at P (normal n, viewer wv, base colour `base` with TEX): pi f cos = base * bA + bB,
+// bA = cos for a Lambert row (!mat_on); the emitter's factor fac becomes fac * bA and fac_b receives fac * bB.  The row source is chosen here, once:
+// prow, the row's pre-row (wave-uniform: the rows travel with the call and the host derived their constants), or null — the raw row mrow
+template <bool TEX, bool PLAIN>
+__device__ __forceinline__ void emitter_terms(const float *mrow, const float *prow, bool mat_on, v3 P, v3 n, v3 wv, const float (&base)[3], const float *pos, float &fac,
+                                              float &fac_b) {
+  v3 wi = vsub(V3(pos[0], pos[1], pos[2]), P);
+  const float idist = __builtin_amdgcn_rsqf(vdot(wi, wi));
+  wi = V3(wi.x * idist, wi.y * idist, wi.z * idist);
+  float bA = vdot(n, wi), bB = 0.f;
+  if (mat_on) {
+    if (PLAIN || prow) row_lobes<TEX>(RowPre<PLAIN>{mrow, prow}, n, wv, wi, base, bA, bB);
+    else row_lobes<TEX>(RowRaw{mrow}, n, wv, wi, base, bA, bB);
+  }
+  fac_b = fac * bB;
+  fac = fac * bA;
+}
+// is `shape`'s row of the material table mt a principled one (model != 0: it has a BSDF beyond base_color / pi)?
+__device__ __forceinline__ bool principled_row(const ShadeK &c, const float *mt, int shape) { return c.mat_stride == FFX_MAT_STRIDE && mt[(size_t)FFX_MAT_STRIDE * shape + FFX_MAT_MODEL] != 0.f; }
+// the BSDF of a shape's raw row for the lane kernels: pi f cos = base * A + B (and pi tau in T, TAU) at normal n, viewer wv, emitter wl; the base
+// colour is `base` where the row is textured.  false: a Lambert row — A, B, T and *cos_o are left as they are
+template <bool TAU>
+__device__ __forceinline__ bool row_terms(const ShadeK &c, const float *mt, int shape, bool textured, const float (&base)[3], v3 n, v3 wv, v3 wl, float &A, float &B,
+                                          float &T, float *cos_o = nullptr) {
+  if (!principled_row(c, mt, shape)) return false;
+  const RowRaw row{mt + (size_t)FFX_MAT_STRIDE * shape};
+  MatGeo mg;
+  material_geometry(row, n, wv, wl, mg);
+  if (textured) material_terms<true, TAU>(row, mg, A, B, base[0], base[1], base[2], &T);
+  else material_terms<false, TAU>(row, mg, A, B, 0.f, 0.f, 0.f, &T);
+  if (cos_o) *cos_o = mg.cos_o;
+  return true;
+}
 
 // ---- the projector texture at a sample and its adjoint: the pieces the render kernels and their adjoints below are built from ----
 // a sample's four bilinear taps: the float offsets of texels (x0, y0), (x1, y0), (x0, y1), (x1, y1) in a tw-wide, tc-channel texture, and their weights
@@ -983,29 +975,12 @@ __device__ __forceinline__ void shade_sample(const ShadeK &c, const BvhNode *__r
           }
           if (vis) {
             float bA = cos_s, bB = 0.f, bT = 0.f; // Lambert; material rows: pi f cos = base_color * bA + bB
-            if (c.mat_stride == FFX_MAT_STRIDE && mt[(size_t)FFX_MAT_STRIDE * h.shape + FFX_MAT_MODEL] != 0.f) {
-              const float *mrow = mt + (size_t)FFX_MAT_STRIDE * h.shape;
-              MatGeo mg;
-              material_geometry(mrow, ns, V3(-d.x, -d.y, -d.z), wi, mg);
-              if (textured) material_terms<true, APP>(mrow, mg, bA, bB, st.base[0], st.base[1], st.base[2], &bT);
-              else material_terms<false, APP>(mrow, mg, bA, bB, 0.f, 0.f, 0.f, &bT);
-            }
+            row_terms<APP>(c, mt, h.shape, textured, st.base, ns, V3(-d.x, -d.y, -d.z), wi, bA, bB, bT);
             st.proj_fac = (c.p_scale / (pl.z * pl.z * cos_p)) * bA;
             st.proj_fac_b = (c.p_scale / (pl.z * pl.z * cos_p)) * bB;
             if (APP) ap->proj_t = (c.p_scale / (pl.z * pl.z * cos_p)) * bT;
             if (MAT) { mv->kp = c.p_scale / (pl.z * pl.z * cos_p); mv->wp = wi; }
-            float fx = fmaf(u, (float)c.tw, -0.5f), fy = fmaf(v, (float)c.th, -0.5f);
-            float x0 = floorf(fx), y0 = floorf(fy);
-            float ax = fx - x0, ay = fy - y0;
-            int ix0 = (int)x0, iy0 = (int)y0;
-            st.ubx = ix0; st.uby = iy0;
-            st.ix0 = clampi(ix0, 0, c.tw - 1);
-            st.ix1 = clampi(ix0 + 1, 0, c.tw - 1);
-            st.iy0 = clampi(iy0, 0, c.th - 1);
-            st.iy1 = clampi(iy0 + 1, 0, c.th - 1);
-            st.wx0 = 1.0f - ax; st.wx1 = ax;
-            st.wy0 = 1.0f - ay; st.wy1 = ay;
-            st.has_proj = 1;
+            sample_footprint(st, u, v, c.tw, c.th);
           }
         }
       }
@@ -1033,13 +1008,7 @@ __device__ __forceinline__ void shade_sample(const ShadeK &c, const BvhNode *__r
         }
         if (vis) {
           float bA = cos_s, bB = 0.f, bT = 0.f;
-          if (c.mat_stride == FFX_MAT_STRIDE && mt[(size_t)FFX_MAT_STRIDE * h.shape + FFX_MAT_MODEL] != 0.f) {
-            const float *mrow = mt + (size_t)FFX_MAT_STRIDE * h.shape;
-            MatGeo mg;
-            material_geometry(mrow, ns, V3(-d.x, -d.y, -d.z), wi, mg);
-            if (textured) material_terms<true, APP>(mrow, mg, bA, bB, st.base[0], st.base[1], st.base[2], &bT);
-            else material_terms<false, APP>(mrow, mg, bA, bB, 0.f, 0.f, 0.f, &bT);
-          }
+          row_terms<APP>(c, mt, h.shape, textured, st.base, ns, V3(-d.x, -d.y, -d.z), wi, bA, bB, bT);
           float f = fall * bA / d2 * 0.3183098861837907f, fb = fall * bB / d2 * 0.3183098861837907f;
           if (APP) { ap->s_f = f; ap->s_fb = fb; ap->spot_t = fall * bT / d2 * 0.3183098861837907f; }
           if (MAT) { mv->ks = fall / d2 * 0.3183098861837907f; mv->ws = wi; }
@@ -2482,49 +2451,14 @@ __device__ __forceinline__ void shade_sample_pk(const BvhNode *__restrict__ node
           }
         }
         // one emitter after the other: directions -> cosines (MatGeo) -> lobes
-        if (lit_p) {
-          v3 wi = vsub(V3(c2.p_pos[0], c2.p_pos[1], c2.p_pos[2]), q.P);
-          const float idist = __builtin_amdgcn_rsqf(vdot(wi, wi));
-          wi = V3(wi.x * idist, wi.y * idist, wi.z * idist);
-          float bA = vdot(q.ng, wi), bB = 0.f;
-          if (mat_on) {
-            MatGeo g;
-            if (PLAIN || prow) { material_geometry_p<PLAIN>(mrow, prow, q.ng, wv, wi, g); material_terms_p<TEX, PLAIN>(mrow, prow, g, bA, bB, st[r].base[0], st[r].base[1], st[r].base[2]); }
-            else { material_geometry(mrow, q.ng, wv, wi, g); material_terms<TEX>(mrow, g, bA, bB, st[r].base[0], st[r].base[1], st[r].base[2]); }
-          }
-          q.pfac_b = q.pfac * bB;
-          q.pfac = q.pfac * bA;
-        }
-        if (lit_s) {
-          v3 wi = vsub(V3(c2.s_pos[0], c2.s_pos[1], c2.s_pos[2]), q.P);
-          const float idist = __builtin_amdgcn_rsqf(vdot(wi, wi));
-          wi = V3(wi.x * idist, wi.y * idist, wi.z * idist);
-          float bA = vdot(q.ng, wi), bB = 0.f;
-          if (mat_on) {
-            MatGeo g;
-            if (PLAIN || prow) { material_geometry_p<PLAIN>(mrow, prow, q.ng, wv, wi, g); material_terms_p<TEX, PLAIN>(mrow, prow, g, bA, bB, st[r].base[0], st[r].base[1], st[r].base[2]); }
-            else { material_geometry(mrow, q.ng, wv, wi, g); material_terms<TEX>(mrow, g, bA, bB, st[r].base[0], st[r].base[1], st[r].base[2]); }
-          }
-          q.sfac_b = q.sfac * bB;
-          q.sfac = q.sfac * bA;
-        }
+        if (lit_p) emitter_terms<TEX, PLAIN>(mrow, prow, mat_on, q.P, q.ng, wv, st[r].base, c2.p_pos, q.pfac, q.pfac_b);
+        if (lit_s) emitter_terms<TEX, PLAIN>(mrow, prow, mat_on, q.P, q.ng, wv, st[r].base, c2.s_pos, q.sfac, q.sfac_b);
       }
     }
     if (q.need_p && !occ_p[r]) {
       st[r].proj_fac = q.pfac;
       if constexpr (MAT) st[r].proj_fac_b = q.pfac_b;
-      float fx = fmaf(q.u, (float)c2.tw, -0.5f), fy = fmaf(q.v, (float)c2.th, -0.5f);
-      float x0 = floorf(fx), y0 = floorf(fy);
-      float ax = fx - x0, ay = fy - y0;
-      int ix0 = (int)x0, iy0 = (int)y0;
-      st[r].ubx = ix0; st[r].uby = iy0;
-      st[r].ix0 = clampi(ix0, 0, c2.tw - 1);
-      st[r].ix1 = clampi(ix0 + 1, 0, c2.tw - 1);
-      st[r].iy0 = clampi(iy0, 0, c2.th - 1);
-      st[r].iy1 = clampi(iy0 + 1, 0, c2.th - 1);
-      st[r].wx0 = 1.0f - ax; st[r].wx1 = ax;
-      st[r].wy0 = 1.0f - ay; st[r].wy1 = ay;
-      st[r].has_proj = 1;
+      sample_footprint(st[r], q.u, q.v, c2.tw, c2.th);
     }
     if (q.need_s && !occ_s[r]) {
       st[r].spot[0] = c2.s_int[0] * q.sfac;
@@ -3899,14 +3833,9 @@ __device__ __forceinline__ void path_bounce_weight(const ShadeK &c, const Sample
   const float *mt = mat_table(c);
   f[0] = st.base[0]; f[1] = st.base[1]; f[2] = st.base[2];
   pb.model = 0; pb.A = 1.f; pb.tau = 0.f; pb.ic = 1.f;
-  if (c.mat_stride == FFX_MAT_STRIDE && mt[(size_t)FFX_MAT_STRIDE * st.shape + FFX_MAT_MODEL] != 0.f) {
-    const float *mrow = mt + (size_t)FFX_MAT_STRIDE * st.shape;
-    MatGeo mg;
-    material_geometry(mrow, pv.ns, V3(-d.x, -d.y, -d.z), wo, mg);
-    float A, B, T = 0.f;
-    if (pv.textured) material_terms<true, TAU>(mrow, mg, A, B, st.base[0], st.base[1], st.base[2], &T);
-    else material_terms<false, TAU>(mrow, mg, A, B, 0.f, 0.f, 0.f, &T);
-    const float ic = mg.cos_o > 0.f ? 1.0f / mg.cos_o : 0.f;
+  float A, B, T = 0.f, cos_o;
+  if (row_terms<TAU>(c, mt, st.shape, pv.textured, st.base, pv.ns, V3(-d.x, -d.y, -d.z), wo, A, B, T, &cos_o)) {
+    const float ic = cos_o > 0.f ? 1.0f / cos_o : 0.f;
 #pragma unroll
     for (int ch = 0; ch < 3; ++ch) f[ch] = (st.base[ch] * A + B) * ic;
     pb.model = 1; pb.A = A; pb.tau = T; pb.ic = ic;
@@ -4122,8 +4051,7 @@ __device__ __forceinline__ void base_tex_taps(const ShadeK &c, int k, int slot, 
   o[0] = ((size_t)y0 * tw + x0) * 3; o[1] = ((size_t)y0 * tw + x1) * 3; o[2] = ((size_t)y1 * tw + x0) * 3; o[3] = ((size_t)y1 * tw + x1) * 3;
   w[0] = (1.0f - ay) * (1.0f - ax); w[1] = (1.0f - ay) * ax; w[2] = ay * (1.0f - ax); w[3] = ay * ax;
 }
-static __constant__ constexpr float FFX_LUM_W[3] = {0.212671f, 0.715160f, 0.072169f}; // the luminance weights w of the tint terms
-__device__ __forceinline__ float base_lum(const SampleTerms &st) { return FFX_LUM_W[0] * st.base[0] + FFX_LUM_W[1] * st.base[1] + FFX_LUM_W[2] * st.base[2]; }
+__device__ __forceinline__ float base_lum(const SampleTerms &st) { return lum3(st.base[0], st.base[1], st.base[2]); }
 // the appearance block at a vertex whose radiance carries the weight w (q at direct light, q beta in prb), tv = the projector's texture value there:
 // gs += d/d (spot intensity), gb = d/d (base colour) = w E - r w_lum
 __device__ __forceinline__ void base_colour_vjp(const ShadeK &k, const SampleTerms &st, const AppTerms &ap, const float (&tv)[3], const float (&w)[3], float (&gs)[3],
@@ -4146,7 +4074,7 @@ __device__ __forceinline__ void base_colour_vjp(const ShadeK &k, const SampleTer
 __device__ __forceinline__ bool emitters_material_vjp(const ShadeK &k, const SampleTerms &st, const MatVtx &mv, v3 wv, const float (&w)[3], const float (&tv)[3],
                                                       float (&gm)[FFX_MAT_GRAD_COLS]) {
   const float *mt = mat_table(k);
-  if (!(k.mat_stride == FFX_MAT_STRIDE && mt[(size_t)FFX_MAT_STRIDE * st.shape + FFX_MAT_MODEL] != 0.f && (mv.kp != 0.f || mv.ks != 0.f))) return false;
+  if (!(principled_row(k, mt, st.shape) && (mv.kp != 0.f || mv.ks != 0.f))) return false;
   const float *mrow = mt + (size_t)FFX_MAT_STRIDE * st.shape;
   const float lum = base_lum(st);
 #pragma unroll
@@ -4481,10 +4409,10 @@ __device__ __forceinline__ void vertex_tangent(const ShadeK &k, const JvpArgs &j
     for (int ch = 0; ch < 3; ++ch) vt.db[ch] = tw4[0] * dt[to[0] + ch] + tw4[1] * dt[to[1] + ch] + tw4[2] * dt[to[2] + ch] + tw4[3] * dt[to[3] + ch];
   }
   const float *mt = mat_table(k);
-  const bool model = k.mat_stride == FFX_MAT_STRIDE && mt[(size_t)FFX_MAT_STRIDE * st.shape + FFX_MAT_MODEL] != 0.f;
+  const bool model = principled_row(k, mt, st.shape);
   vt.md = MAT && model ? j.dmat + (size_t)st.shape * FFX_MAT_GRAD_COLS : nullptr;
   vt.lum = base_lum(st);
-  vt.wdb = FFX_LUM_W[0] * vt.db[0] + FFX_LUM_W[1] * vt.db[1] + FFX_LUM_W[2] * vt.db[2];
+  vt.wdb = lum3(vt.db[0], vt.db[1], vt.db[2]);
   N[0] = N[1] = N[2] = 0.f;
   dN[0] = dN[1] = dN[2] = 0.f;
   // no emitter lights the vertex.  (MAT: by the emitters' own factors — a row whose A and B both vanish, as at spec_trans = 1 with eta = 1, still has
@@ -4873,6 +4801,22 @@ template <class K> static int copy_mat_h(const ffx_scene_desc *sd, int ms, K &k)
   return 1;
 }
 
+// the pre-row p (columns FFX_PRE_*) of the material row m: what RowPre reads in place of RowRaw's per-evaluation forms
+static void mat_pre_row(const float *m, float *p) {
+  const float eta = m[FFX_MAT_ETA], r2 = m[FFX_MAT_ROUGHNESS] * m[FFX_MAT_ROUGHNESS], a = r2 > 0.001f ? r2 : 0.001f, a2 = a * a;
+  const float metallic = m[FFX_MAT_METALLIC], m1 = 1.0f - metallic, tint = m[FFX_MAT_SPEC_TINT];
+  const float r0 = (eta - 1.0f) / (eta + 1.0f);
+  uint32_t flags = 0;
+  if (m[FFX_MAT_ANISOTROPIC] != 0.f) flags |= FFX_PRE_ANISO;
+  if (tint != 0.f) flags |= FFX_PRE_TINT;
+  if (m[FFX_MAT_CLEARCOAT] > 0.f) flags |= FFX_PRE_CLEARCOAT;
+  if (m[FFX_MAT_FLATNESS] > 0.f) flags |= FFX_PRE_FLAT;
+  if (m[FFX_MAT_SHEEN] > 0.f && m1 > 0.f) flags |= FFX_PRE_SHEEN;
+  p[FFX_PRE_ETA] = eta; p[FFX_PRE_INV_ETA2] = 1.0f / (eta * eta); p[FFX_PRE_A2] = a2; p[FFX_PRE_INV_A2] = 1.0f / a2;
+  p[FFX_PRE_METALLIC] = metallic; p[FFX_PRE_C_SW] = metallic + m1 * tint; p[FFX_PRE_C_FD] = m1 * (1.0f - tint); p[FFX_PRE_BRDF] = m1 * (1.0f - m[FFX_MAT_SPEC_TRANS]);
+  p[FFX_PRE_ROUGH2] = 2.0f * m[FFX_MAT_ROUGHNESS]; memcpy(&p[FFX_PRE_FLAGS], &flags, 4); p[FFX_PRE_R2] = r2; p[FFX_PRE_TINT_TERM] = m1 * tint * r0 * r0;
+}
+
 static int shade_prepare(const ffx_scene_desc *sd, ShadeK &c) {
   memset(&c, 0, sizeof c);
   if (!cam_prepare(&sd->cam, c.cam)) return 0;
@@ -4884,22 +4828,7 @@ static int shade_prepare(const ffx_scene_desc *sd, ShadeK &c) {
   if (!copy_mat_h(sd, c.mat_stride, c)) return 0;
   if (c.mat_inline && c.mat_stride == FFX_MAT_STRIDE && sd->n_shapes <= 8) { // per-row constants of the principled rows (ShadeK.mat_pre)
     c.mat_pre_on = 1;
-    for (int k = 0; k < sd->n_shapes; ++k) {
-      const float *m = sd->mat_h + k * FFX_MAT_STRIDE;
-      float *p = c.mat_pre + k * FFX_PRE_FLOATS;
-      const float eta = m[FFX_MAT_ETA], r2 = m[FFX_MAT_ROUGHNESS] * m[FFX_MAT_ROUGHNESS], a = r2 > 0.001f ? r2 : 0.001f, a2 = a * a;
-      const float metallic = m[FFX_MAT_METALLIC], m1 = 1.0f - metallic, tint = m[FFX_MAT_SPEC_TINT];
-      const float r0 = (eta - 1.0f) / (eta + 1.0f);
-      uint32_t flags = 0;
-      if (m[FFX_MAT_ANISOTROPIC] != 0.f) flags |= FFX_PRE_ANISO;
-      if (tint != 0.f) flags |= FFX_PRE_TINT;
-      if (m[FFX_MAT_CLEARCOAT] > 0.f) flags |= FFX_PRE_CLEARCOAT;
-      if (m[FFX_MAT_FLATNESS] > 0.f) flags |= FFX_PRE_FLAT;
-      if (m[FFX_MAT_SHEEN] > 0.f && m1 > 0.f) flags |= FFX_PRE_SHEEN;
-      p[0] = eta; p[1] = 1.0f / (eta * eta); p[2] = a2; p[3] = 1.0f / a2;
-      p[4] = metallic; p[5] = metallic + m1 * tint; p[6] = m1 * (1.0f - tint); p[7] = m1 * (1.0f - m[FFX_MAT_SPEC_TRANS]);
-      p[8] = 2.0f * m[FFX_MAT_ROUGHNESS]; memcpy(&p[9], &flags, 4); p[10] = r2; p[11] = m1 * tint * r0 * r0;
-    }
+    for (int k = 0; k < sd->n_shapes; ++k) mat_pre_row(sd->mat_h + k * FFX_MAT_STRIDE, c.mat_pre + k * FFX_PRE_FLOATS);
   }
   if (sd->rfilter == FFX_RFILTER_GAUSSIAN) { // [EXT Mitsuba src/rfilters/gaussian.cpp] radius 4 stddev; the 5x5 window holds radius <= 2
     const float sdv = sd->rfilter_stddev > 0.f ? sd->rfilter_stddev : 0.5f;
@@ -5421,7 +5350,7 @@ static bool plain_scene(const RenderSetup &r, const ffx_scene_desc *sd, const vo
   if ((r.c.spot_on && !r.c.s_rigid) || (r.c.proj_on && r.c.tc != 1)) return false;
   for (int k = 0; k < sd->n_shapes; ++k) { // (mat_pre_on: at most 8 rows, all inline)
     uint32_t flags;
-    memcpy(&flags, &r.c.mat_pre[k * FFX_PRE_FLOATS + 9], 4);
+    memcpy(&flags, &r.c.mat_pre[k * FFX_PRE_FLOATS + FFX_PRE_FLAGS], 4);
     if (flags != 0u || r.c.mat_h[k * FFX_MAT_STRIDE + FFX_MAT_MODEL] == 0.f) return false;
   }
   return ffx_blob_flat(bvh) == 1;

@@ -1848,6 +1848,35 @@ def test_material_table_inside_the_scene_description(oracle, env, monkeypatch):
     assert scene_desc.set_host_materials(many, np.zeros((50, 3), np.float32)) is False and many.n_mat_h == 0  # 150 floats: stays a device table
 
 
+_OPTIONAL_LOBES = ("anisotropic", "spec_tint", "clearcoat", "flatness", "sheen")
+
+
+@pytest.mark.parametrize("lobes", [(k,) for k in _OPTIONAL_LOBES] + [_OPTIONAL_LOBES], ids=lambda l: "+".join(l))
+def test_inline_rows_with_optional_lobes_match_the_oracle(oracle, lobes):
+    """rows that travel with the call take the BSDF from constants the host derived once per row, with one flag bit per optional lobe
+    (anisotropic, spec_tint, clearcoat, flatness, sheen).  Each lobe switched on alone (the other four parameters 0) and all five
+    together: the inline render against the oracle, by the bound of the raw-row test, and against the device-table render of the
+    same rows by that bound too — the two forms differ by design in the last bit of 1 / a2, 1 / eta^2 and the tint term."""
+    from fireflies_amd import _abi
+
+    sc = scenes.vocalfold(width=52, height=44, tex=80, frames=3, n_fold=20, tube=(20, 24))
+    go, gd, alb = pair(oracle, sc, frame=2, xforms=_rand_xforms(2, 5))
+    tex = splat_tex(sc, 1)
+    mats = material_rows(2, 41, **{k: 0.0 for k in _OPTIONAL_LOBES if k not in lobes})
+    for k in _OPTIONAL_LOBES:
+        on = mats[:, getattr(_abi, "MAT_" + k.upper())] != 0.0
+        assert on.all() if k in lobes else not on.any()
+    sd_dev = scene_desc.scene_desc(sc, tex_channels=1, shadows=True, mat_stride=16)
+    sd_host = scene_desc.scene_desc(sc, tex_channels=1, shadows=True, mat_stride=16, host_mats=mats)
+    assert sd_host.n_mat_h == mats.size
+    img_o = go.render_fwd(sd_dev, mats, host(tex), 9, seed=3)
+    img_h = host(gd.render_fwd(sd_host, None, tex, 9, seed=3))
+    img_t = host(gd.render_fwd(sd_dev, dev(mats), tex, 9, seed=3))
+    scale, _ = _assert_image_close(img_h, img_o, 9, frac=2e-4, rel=1e-4, what=f"inline rows, {lobes}")
+    assert scale > 0.02
+    _assert_image_close(img_h, img_t, 9, frac=2e-4, rel=1e-4, what=f"inline rows against the device table, {lobes}")
+
+
 def test_principled_materials_mid_size_and_abi_errors(oracle):
     """material rows at 256x256x64 spp on the full-detail vocal fold (one pixel per wave, the production launch shape) against
     the oracle, with the reference's vocal-fold randomisation (specular 0 .. 0.75, roughness 0.5); and the C ABI's refusals:
