@@ -216,6 +216,15 @@ RENDER_TANGENT = 0x80000
 # back behind the image
 RENDER_AOV = 0x100000
 RENDER_AOV_FLOATS = 17
+# extra emitters (include/ffx.h FFX_RENDER_LIGHTS): n in bits 21..24 of the img_fp16 word of ffx_render_fwd[_filtered]; n records of LIGHT_FLOATS floats
+# follow the material table in the shape_albedo buffer (to_world 0..15, intensity 16..18, cutoff_deg 19, beam_width_deg 20, type 21, reserved 22..23)
+RENDER_MAX_LIGHTS, RENDER_LIGHTS_SHIFT, RENDER_LIGHTS_MASK = 8, 21, 0x1E00000
+LIGHT_FLOATS, LIGHT_POINT, LIGHT_SPOT = 24, 0, 1
+
+
+def render_lights(n):
+    """FFX_RENDER_LIGHTS(n): the flags bits of a forward with n extra emitters"""
+    return (int(n) & 15) << RENDER_LIGHTS_SHIFT
 
 
 MAX_BASE_TEX = 4

@@ -892,6 +892,7 @@ __device__ __forceinline__ float foot_value_3ch(float g, float alb, float inv_sp
 // what a path vertex needs beyond the emitters' terms: the lifted origin of its secondary ray, its normals, whether the row's base
 // colour came from a texture.  ok = 0: no vertex (a miss, a degenerate triangle)
 struct PathVtx { v3 Po, ng, ns; int textured, ok; };
+struct PathVtxP : PathVtx { v3 P; }; // ... with the hit itself, for the walk that evaluates further emitters there (shade_sample's !EMIT: pv points to one)
 // what the appearance adjoint needs beyond the emitters' terms: the tint parts pi tau of both emitters' factors (proj_t scales like
 // proj_fac, spot_t like s_f), the spot's factors at unit intensity (spot = s_int s_f, spot_b = s_int s_fb), and where a textured base colour was read
 struct AppTerms { float proj_t, spot_t, s_f, s_fb; int tix, slot; float bu, bv; };
@@ -901,8 +902,9 @@ struct MatVtx { v3 ns, wp, ws; float kp, ks; };
 
 // the sample's hit in (nt, ft] and next-event estimation there: projector and spot terms, shadow rays, base colour.  PATH (the path kernels):
 // the ray has an arbitrary origin (no apex form) and *pv receives the vertex.  APP (k_render_bwd_appearance): *ap receives AppTerms.  MAT
-// (k_render_bwd_material): *mv receives MatVtx
-template <bool PATH = false, bool APP = false, bool MAT = false>
+// (k_render_bwd_material): *mv receives MatVtx.  !EMIT (k_lights_fwd): the hit and the vertex only — neither of the two main emitters is
+// evaluated and none of their shadow rays is spent (the terms stay zero); pv->P receives the hit
+template <bool PATH = false, bool APP = false, bool MAT = false, bool EMIT = true>
 __device__ __forceinline__ void shade_sample(const ShadeK &c, const BvhNode *__restrict__ nodes, const TriRec *__restrict__ recs, const float4 *__restrict__ nrec, v3 o,
                                              v3 d, float nt, float ft, SampleTerms &st, int *stack, int stride, PathVtx *pv = nullptr, AppTerms *ap = nullptr,
                                              MatVtx *mv = nullptr) {
@@ -948,9 +950,10 @@ __device__ __forceinline__ void shade_sample(const ShadeK &c, const BvhNode *__r
     }
   }
   if (PATH) { pv->Po = Po; pv->ng = ng; pv->ns = ns; pv->textured = textured ? 1 : 0; pv->ok = 1; }
+  if (PATH && !EMIT) static_cast<PathVtxP *>(pv)->P = P;
   if (MAT) mv->ns = ns;
 
-  if (c.proj_on) {
+  if (EMIT && c.proj_on) {
     v3 pl = xf_point(c.p_w2l, P);
     if (pl.z > 0.f) {
       const float *m = c.p_c2s;
@@ -986,7 +989,7 @@ __device__ __forceinline__ void shade_sample(const ShadeK &c, const BvhNode *__r
       }
     }
   }
-  if (c.spot_on) {
+  if (EMIT && c.spot_on) {
     v3 spos = V3(c.s_pos[0], c.s_pos[1], c.s_pos[2]);
     v3 wi = vsub(spos, P);
     float d2 = vdot(wi, wi);
@@ -3849,18 +3852,19 @@ struct NoBounce {
 // visit(v, st, ap, mv, d, beta) sees the emitters' terms and the throughput (ap with APP, mv with MAT: shade_sample's); then the bounce (vertex
 // v < max_depth - 1), the roulette (v >= rr_depth: q and the survival test are constants of a replay) and, after a bounce that survived,
 // bounce(v, st, pv, ap, d, wo, beta, iq, f, pb) — beta is the throughput in front of the bounce, iq = 1 / q_v, pb.tau is formed with APP only —
-// and the secondary ray from the lifted point
-template <bool APP = false, bool MAT = false, typename V, typename B = NoBounce>
+// and the secondary ray from the lifted point.  !EMIT: shade_sample's — the main emitters are left out and the visitor is visit(v, st, pv, d, beta)
+template <bool APP = false, bool MAT = false, bool EMIT = true, typename V, typename B = NoBounce>
 __device__ __forceinline__ void path_walk(const PathArgs &a, uint32_t idx, v3 o, v3 d, float nt, float ft, int *stack, int stride, V &&visit, B &&bounce = B()) {
   const ShadeK &c = kernarg_shade();
   SampleTerms st;
-  PathVtx pv;
+  std::conditional_t<EMIT, PathVtx, PathVtxP> pv;
   AppTerms ap;
   MatVtx mv;
-  shade_sample<true, APP, MAT>(c, a.nodes, a.recs, a.nrec, o, d, nt, ft, st, stack, stride, &pv, &ap, &mv);
+  shade_sample<true, APP, MAT, EMIT>(c, a.nodes, a.recs, a.nrec, o, d, nt, ft, st, stack, stride, &pv, &ap, &mv);
   float beta[3] = {1.f, 1.f, 1.f};
   for (int v = 1; st.hit && pv.ok; ++v) {
-    visit(v, st, ap, mv, d, beta);
+    if constexpr (EMIT) visit(v, st, ap, mv, d, beta);
+    else visit(v, st, pv, d, beta);
     if (v + 1 >= a.max_depth) break;
     const v3 wo = cosine_dir(pv.ns, path_u(a.path_key, idx, v, 0), path_u(a.path_key, idx, v, 1));
     if (!(vdot(pv.ng, wo) > 0.f)) break;
@@ -3881,7 +3885,7 @@ __device__ __forceinline__ void path_walk(const PathArgs &a, uint32_t idx, v3 o,
     beta[0] = nb[0]; beta[1] = nb[1]; beta[2] = nb[2];
     o = pv.Po;
     d = wo;
-    shade_sample<true, APP, MAT>(c, a.nodes, a.recs, a.nrec, o, d, 0.f, 3.0e38f, st, stack, stride, &pv, &ap, &mv);
+    shade_sample<true, APP, MAT, EMIT>(c, a.nodes, a.recs, a.nrec, o, d, 0.f, 3.0e38f, st, stack, stride, &pv, &ap, &mv);
   }
 }
 __device__ __forceinline__ float wave_sum_tree(float v) { // (fixed order: the same bits on every run)
@@ -3947,6 +3951,160 @@ __global__ void __launch_bounds__(64)
     }
   }
 }
+// ------------------------------------------------------------------------------------------ extra emitters
+// FFX_RENDER_LIGHTS(n) (include/ffx.h): n further delta emitters — point lights and spots — in a pass of its own behind the launches of the main image.
+// k_path_fwd's shape (one wave = one pixel, lane l takes samples l, l + 64, ...) and its walk (path_walk<..., !EMIT>: the same hits, bounces and
+// roulette, the two main emitters left out); at every vertex the n lights by the formulas of shade_sample's spot.  The pixel's mean is ADDED to img
+// (box film: the pixel's own wave, lane 0; gaussian film: the sums through the scratch, k_lights_gather adds).  No atomics.
+// The table's records (FFX_LIGHT_FLOATS floats each, read with wave-uniform addresses) are turned into what a vertex needs once per wave, in LDS:
+#define FFX_LK_POS 0    // the light's position: to_world's translation
+#define FFX_LK_INV 3    // inverse of to_world's 3 x 3, row-major (spots)
+#define FFX_LK_INT 12   // intensity
+#define FFX_LK_CBEAM 15 // cos(beam_width), cos(cutoff), cutoff in radians, 1 / (cutoff - beam_width)
+#define FFX_LK_CCUT 16
+#define FFX_LK_CUT 17
+#define FFX_LK_ITRANS 18
+#define FFX_LK_TYPE 19
+#define FFX_LK_FLOATS 20
+__device__ __forceinline__ void lights_derive(const float *__restrict__ table, int n, int lane, float *__restrict__ s_l) {
+  for (int k = 0; k < n; ++k) { // (wave-uniform: every lane forms the same values, lane 0 parks them)
+    const float *m = table + (size_t)FFX_LIGHT_FLOATS * k;
+    const float a00 = m[0], a01 = m[1], a02 = m[2], a10 = m[4], a11 = m[5], a12 = m[6], a20 = m[8], a21 = m[9], a22 = m[10];
+    const float c00 = a11 * a22 - a12 * a21, c01 = a12 * a20 - a10 * a22, c02 = a10 * a21 - a11 * a20;
+    const float idet = 1.0f / (a00 * c00 + a01 * c01 + a02 * c02); // (a singular frame: no finite cosine below, the spot lights nothing)
+    const float deg = 0.017453292519943295f, cutoff = m[19] * deg, beam = m[20] * deg;
+    if (lane == 0) {
+      float *o = s_l + FFX_LK_FLOATS * k;
+      o[FFX_LK_POS] = m[3]; o[FFX_LK_POS + 1] = m[7]; o[FFX_LK_POS + 2] = m[11];
+      o[FFX_LK_INV + 0] = c00 * idet; o[FFX_LK_INV + 1] = (a02 * a21 - a01 * a22) * idet; o[FFX_LK_INV + 2] = (a01 * a12 - a02 * a11) * idet;
+      o[FFX_LK_INV + 3] = c01 * idet; o[FFX_LK_INV + 4] = (a00 * a22 - a02 * a20) * idet; o[FFX_LK_INV + 5] = (a02 * a10 - a00 * a12) * idet;
+      o[FFX_LK_INV + 6] = c02 * idet; o[FFX_LK_INV + 7] = (a01 * a20 - a00 * a21) * idet; o[FFX_LK_INV + 8] = (a00 * a11 - a01 * a10) * idet;
+      o[FFX_LK_INT] = m[16]; o[FFX_LK_INT + 1] = m[17]; o[FFX_LK_INT + 2] = m[18];
+      o[FFX_LK_CBEAM] = cosf(beam); o[FFX_LK_CCUT] = cosf(cutoff); o[FFX_LK_CUT] = cutoff; o[FFX_LK_ITRANS] = 1.0f / (cutoff - beam);
+      o[FFX_LK_TYPE] = m[21];
+    }
+  }
+  __syncthreads();
+}
+// the n lights at one vertex (st, pv: shade_sample<true, ..., !EMIT>'s; d: the ray that found it), weighted by the throughput beta, into L
+__device__ __forceinline__ void lights_at_vertex(const ShadeK &c, const PathArgs &a, const float *__restrict__ s_l, int n, const SampleTerms &st, const PathVtxP &pv, v3 d,
+                                                 const float (&beta)[3], int *stack, int stride, float (&L)[3]) {
+  const float *mt = mat_table(c);
+  for (int k = 0; k < n; ++k) {
+    const float *lk = s_l + FFX_LK_FLOATS * k;
+    const v3 lpos = V3(lk[FFX_LK_POS], lk[FFX_LK_POS + 1], lk[FFX_LK_POS + 2]);
+    v3 wi = vsub(lpos, pv.P);
+    const float d2 = vdot(wi, wi);
+    if (!(d2 > 0.f)) continue;
+    const float idist = 1.0f / sqrtf(d2);
+    wi = V3(wi.x * idist, wi.y * idist, wi.z * idist);
+    const float cos_s = vdot(pv.ns, wi);
+    if (!(cos_s > 0.f && vdot(pv.ng, wi) > 0.f)) continue;
+    float fall = 1.f;
+    if (lk[FFX_LK_TYPE] != 0.f) { // a spot: the falloff in the light's local frame (wave-uniform branch)
+      const float *iv = lk + FFX_LK_INV;
+      const v3 w = V3(-wi.x, -wi.y, -wi.z);
+      const v3 ll = V3(iv[0] * w.x + iv[1] * w.y + iv[2] * w.z, iv[3] * w.x + iv[4] * w.y + iv[5] * w.z, iv[6] * w.x + iv[7] * w.y + iv[8] * w.z);
+      const float cos_t = ll.z / sqrtf(vdot(ll, ll));
+      fall = 0.f;
+      if (cos_t >= lk[FFX_LK_CBEAM]) fall = 1.f;
+      else if (cos_t > lk[FFX_LK_CCUT]) fall = (lk[FFX_LK_CUT] - acosf(cos_t)) * lk[FFX_LK_ITRANS];
+      if (!(fall > 0.f)) continue;
+    }
+    if (c.shadows) { // shade_sample's ray: from the emitter to the lifted point, t in (0, 1 - eps)
+      Hit hs;
+      if (traverse<true, true>(a.nodes, a.recs, lpos, vsub(pv.Po, lpos), 0.f, 1.0f - SHADOW_EPS, hs, stack, stride)) continue;
+    }
+    float bA = cos_s, bB = 0.f, bT = 0.f;
+    row_terms<false>(c, mt, st.shape, pv.textured, st.base, pv.ns, V3(-d.x, -d.y, -d.z), wi, bA, bB, bT);
+    const float f = fall * bA / d2 * 0.3183098861837907f, fb = fall * bB / d2 * 0.3183098861837907f;
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) {
+      const float r = lk[FFX_LK_INT + ch] * f, b = lk[FFX_LK_INT + ch] * fb;
+      L[ch] += beta[ch] * (c.mat_stride == 3 ? st.base[ch] * r : st.base[ch] * r + b);
+    }
+  }
+}
+// RF: the gaussian film — the pixel's 25 x 4 outgoing sums of the lights' radiance into `part` (k_lights_gather adds them to the image); else img += the pixel's mean
+template <bool RF>
+__global__ void __launch_bounds__(64)
+    k_lights_fwd(ShadeK c, PathArgs a, const float *__restrict__ lights, int n_lights, float *__restrict__ img, float *__restrict__ part) {
+  extern __shared__ int s_dyn[];
+  __shared__ __attribute__((aligned(16))) float s_rf[RF ? FFX_RF_FLOATS : 4];
+  __shared__ float s_l[FFX_RENDER_MAX_LIGHTS * FFX_LK_FLOATS];
+  const int lane = threadIdx.x;
+  const uint32_t pix = blockIdx.x;
+  const int W = c.cam.W, px = (int)(pix % (uint32_t)W), py = (int)(pix / (uint32_t)W);
+  const int n = n_lights < FFX_RENDER_MAX_LIGHTS ? n_lights : FFX_RENDER_MAX_LIGHTS; // (the host refuses more: s_l holds this many)
+  lights_derive(lights, n, lane, s_l);
+  float acc[4] = {0.f, 0.f, 0.f, 0.f};
+  for (int pass = 0; pass < (a.spp + 63) >> 6; ++pass) {
+    const int s = pass * 64 + lane;
+    const uint32_t idx = pix * (uint32_t)a.spp + (uint32_t)s;
+    float jx, jy;
+    sample_jitter(a.seed_key, idx, jx, jy);
+    float L[3] = {0.f, 0.f, 0.f};
+    if (s < a.spp) {
+      v3 o, d;
+      float nt, ft;
+      cam_ray(c.cam, ((float)px + jx) * c.cam.inv_w, ((float)py + jy) * c.cam.inv_h, o, d, nt, ft);
+      path_walk<false, false, false>(a, idx, o, d, nt, ft, s_dyn + lane, 64, [&](int, const SampleTerms &st, const PathVtxP &pv, v3 dv, const float (&beta)[3]) {
+        lights_at_vertex(kernarg_shade(), a, s_l, n, st, pv, dv, beta, s_dyn + lane, 64, L);
+      });
+    }
+    if (RF) {
+      float gx[5], gy[5];
+      rf_weights(c.rf, jx, gx);
+      rf_weights(c.rf, jy, gy);
+      rf_fold(s_rf, lane, gx, gy, L[0], L[1], L[2], s < a.spp ? 1.f : 0.f, acc);
+    } else {
+      acc[0] += L[0]; acc[1] += L[1]; acc[2] += L[2];
+    }
+  }
+  if (RF) {
+    rf_store(part, pix, lane, acc);
+    return;
+  }
+  const float inv_spp = 1.0f / (float)a.spp;
+  const float m0 = wave_sum_tree(acc[0]) * inv_spp, m1 = wave_sum_tree(acc[1]) * inv_spp, m2 = wave_sum_tree(acc[2]) * inv_spp;
+  if (lane == 0) {
+    float *p = img + (size_t)pix * 3;
+    p[0] += m0; p[1] += m1; p[2] += m2;
+  }
+}
+// k_rf_gather's sums of the lights' pass, added to the image the main gather wrote: img += (r, g, b) / weight (the weight is the jitter's alone: the main image's)
+__global__ void __launch_bounds__(64) k_lights_gather(const float4 *__restrict__ part, int W, int H, float *__restrict__ img) {
+  __shared__ float4 s_seg[68 * 5];
+  const int lane = threadIdx.x;
+  const int x0 = blockIdx.x * 64, y = blockIdx.y;
+  if (y >= H) return;
+  float r = 0.f, g = 0.f, b = 0.f, w = 0.f;
+  for (int wb = 0; wb < 5; ++wb) {
+    const int qy = y - (wb - 2);
+    if (qy < 0 || qy >= H) continue; // (wave-uniform)
+    __builtin_amdgcn_wave_barrier();
+#pragma unroll
+    for (int k = 0; k < 6; ++k) {
+      const int e = lane + 64 * k;
+      if (e < 340) {
+        const int rec = e / 5, wa = e - 5 * rec;
+        const int qx = x0 - 2 + rec;
+        s_seg[e] = (qx >= 0 && qx < W) ? part[((size_t)qy * W + qx) * 25 + (wb * 5 + wa)] : make_float4(0.f, 0.f, 0.f, 0.f);
+      }
+    }
+    __builtin_amdgcn_wave_barrier();
+#pragma unroll
+    for (int wa = 0; wa < 5; ++wa) {
+      const float4 v = s_seg[(lane + 4 - wa) * 5 + wa];
+      r += v.x; g += v.y; b += v.z; w += v.w;
+    }
+  }
+  const int x = x0 + lane;
+  if (x >= W || !(w > 0.f)) return;
+  float *p = img + ((size_t)y * W + x) * 3;
+  p[0] += r / w; p[1] += g / w; p[2] += b / w;
+}
+
 // ---- the pieces of the per-lane replay adjoints (k_path_bwd, the direct-light leaves of 4.5 / 4.5.1, prb of 4.5.2): one wave = one pixel ----
 // the adjoint of a pixel.  Box film: g = gimg[pixel] / spp; RF: gsrc is G = gimg / weight as float4 per pixel (k_rf_gather) and lanes 0..24 hold G of
 // window pixel `lane`.  false: nothing flows into this pixel's samples (wave-uniform; box: block-uniform)
@@ -5680,12 +5838,63 @@ static int render_aov(const void *bvh, const ffx_bvh_info *info, const ffx_scene
   }
   return FFX_OK;
 }
+// the extra emitters' bits belong to ffx_render_fwd[_filtered] (and are ignored by ffx_render_bwd[_filtered]): every other render entry point refuses them
+#define FFX_NO_LIGHTS(flags_, what_) \
+  do { if ((flags_) & FFX_RENDER_LIGHTS_MASK) FFX_FAIL(FFX_ERR_UNSUPPORTED, "%s: FFX_RENDER_LIGHTS is served by ffx_render_fwd[_filtered] only", what_); } while (0)
+// FFX_RENDER_LIGHTS (include/ffx.h).  What a forward refuses about the bits before it launches anything: FFX_OK, or the error
+static int lights_check(int flags, const float *shape_albedo, const char *what) {
+  const int n = (flags & FFX_RENDER_LIGHTS_MASK) >> FFX_RENDER_LIGHTS_SHIFT;
+  if (n == 0) return FFX_OK;
+  if (n > FFX_RENDER_MAX_LIGHTS) FFX_FAIL(FFX_ERR_ARG, "%s: FFX_RENDER_LIGHTS(%d): at most %d extra emitters", what, n, FFX_RENDER_MAX_LIGHTS);
+  if (flags & FFX_RENDER_FP16) FFX_FAIL(FFX_ERR_UNSUPPORTED, "%s: FFX_RENDER_LIGHTS has no fp16 film", what);
+  if (flags & FFX_RENDER_TANGENT) FFX_FAIL(FFX_ERR_UNSUPPORTED, "%s: FFX_RENDER_LIGHTS is not served together with FFX_RENDER_TANGENT", what);
+  if (flags & (FFX_RENDER_GRAD_APPEARANCE | FFX_RENDER_GRAD_MATERIAL | FFX_RENDER_GRAD_PRB))
+    FFX_FAIL(FFX_ERR_UNSUPPORTED, "%s: FFX_RENDER_LIGHTS is not served together with a FFX_RENDER_GRAD_* bit (the extra emitters are not differentiated)", what);
+  if (!shape_albedo) FFX_FAIL(FFX_ERR_ARG, "%s: FFX_RENDER_LIGHTS needs the device buffer [material table | lights] (shape_albedo is NULL)", what);
+  return FFX_OK;
+}
+// ... and the pass, behind the launches of the main image on the same stream (the call without the bits has succeeded: its arguments are good):
+// k_lights_fwd adds to img; the gaussian film: into the scratch, which the image's (and an AOV block's) gathers have read by then, and k_lights_gather adds
+static int render_lights(const void *bvh, const ffx_bvh_info *info, const ffx_scene_desc *sd, const float *shape_albedo, int spp, uint32_t seed, int flags, void *img,
+                         ffx_stream s, void *rf_scratch) {
+  const int n = (flags & FFX_RENDER_LIGHTS_MASK) >> FFX_RENDER_LIGHTS_SHIFT;
+  RenderSetup r;
+  if (const int rc = render_setup("render_fwd", bvh, info, sd, shape_albedo, spp, seed, flags & FFX_RENDER_PATH_MASK, rf_scratch, r)) return rc;
+  if (r.n_pix >= (1L << 31)) FFX_FAIL(FFX_ERR_UNSUPPORTED, "render_fwd: FFX_RENDER_LIGHTS: more than 2^31 pixels");
+  if (sd->n_shapes < 0) FFX_FAIL(FFX_ERR_ARG, "render_fwd: n_shapes < 0");
+  const float *table = shape_albedo + (size_t)sd->n_shapes * (size_t)r.c.mat_stride; // (mat_stride: 3 or FFX_MAT_STRIDE — max(mat_stride, 3))
+  const PathArgs pa = path_args(r);
+  const hipStream_t st = (hipStream_t)s;
+  if (rf_scratch) {
+    hipLaunchKernelGGL(k_lights_fwd<true>, dim3((unsigned)r.n_pix), dim3(64), path_stack_bytes(info), st, r.c, pa, table, n, (float *)nullptr, (float *)rf_scratch);
+    FFX_CHECK_LAUNCH("render_fwd_filtered (lights)");
+    hipLaunchKernelGGL(k_lights_gather, dim3(ffx_cdiv(r.c.cam.W, 64), r.c.cam.H), dim3(64), 0, st, (const float4 *)rf_scratch, r.c.cam.W, r.c.cam.H, (float *)img);
+    FFX_CHECK_LAUNCH("render_fwd_filtered (lights)/gather");
+    return FFX_OK;
+  }
+  hipLaunchKernelGGL(k_lights_fwd<false>, dim3((unsigned)r.n_pix), dim3(64), path_stack_bytes(info), st, r.c, pa, table, n, (float *)img, (float *)nullptr);
+  FFX_CHECK_LAUNCH("render_fwd (lights)");
+  return FFX_OK;
+}
+// ffx_render_fwd[_filtered] (scratch: the filtered film's): the call without the lights' bits, then their pass
+static int render_fwd_entry(const void *bvh, const ffx_bvh_info *info, const ffx_scene_desc *sd, const float *shape_albedo, const float *tex, int spp, uint32_t seed,
+                            int img_fp16, void *img, ffx_stream s, void *scratch) {
+  const char *what = scratch ? "render_fwd_filtered" : "render_fwd";
+  if (const int rc = lights_check(img_fp16, shape_albedo, what)) return rc;
+  FFX_NO_APPEARANCE(img_fp16, what);
+  const int lights = img_fp16 & FFX_RENDER_LIGHTS_MASK;
+  img_fp16 &= ~FFX_RENDER_LIGHTS_MASK;
+  int rc;
+  if (img_fp16 & FFX_RENDER_AOV) rc = render_aov(bvh, info, sd, shape_albedo, tex, spp, seed, img_fp16, img, s, scratch);
+  else if (img_fp16 & FFX_RENDER_TANGENT) rc = render_jvp(bvh, info, sd, shape_albedo, tex, spp, seed, img_fp16, img, s, scratch);
+  else rc = render_fwd_impl(bvh, info, sd, shape_albedo, tex, spp, seed, img_fp16 & (FFX_RENDER_FP16 | FFX_RENDER_APEX_READY | FFX_RENDER_PATH_MASK), img, nullptr, s,
+                            nullptr, nullptr, nullptr, scratch);
+  if (rc != FFX_OK || !lights) return rc;
+  return render_lights(bvh, info, sd, shape_albedo, spp, seed, img_fp16 | lights, img, s, scratch);
+}
 int ffx_render_fwd(const void *bvh, const ffx_bvh_info *info, const ffx_scene_desc *sd, const float *shape_albedo, const float *tex, int spp,
                    uint32_t seed, int img_fp16, void *img, ffx_stream s) {
-  FFX_NO_APPEARANCE(img_fp16, "render_fwd");
-  if (img_fp16 & FFX_RENDER_AOV) return render_aov(bvh, info, sd, shape_albedo, tex, spp, seed, img_fp16, img, s, nullptr);
-  if (img_fp16 & FFX_RENDER_TANGENT) return render_jvp(bvh, info, sd, shape_albedo, tex, spp, seed, img_fp16, img, s, nullptr);
-  return render_fwd_impl(bvh, info, sd, shape_albedo, tex, spp, seed, img_fp16 & (FFX_RENDER_FP16 | FFX_RENDER_APEX_READY | FFX_RENDER_PATH_MASK), img, nullptr, s);
+  return render_fwd_entry(bvh, info, sd, shape_albedo, tex, spp, seed, img_fp16, img, s, nullptr);
 }
 // the entry points without the path integrator refuse its bits rather than render direct light only
 #define FFX_NO_PATH(flags_, what_) \
@@ -5712,6 +5921,7 @@ int ffx_render_fwd_cache(const void *bvh, const ffx_bvh_info *info, const ffx_sc
   FFX_NO_APPEARANCE(img_fp16, "render_fwd_cache");
   FFX_NO_TANGENT(img_fp16, "render_fwd_cache");
   FFX_NO_AOV(img_fp16, "render_fwd_cache");
+  FFX_NO_LIGHTS(img_fp16, "render_fwd_cache");
   return render_fwd_impl(bvh, info, sd, shape_albedo, tex, spp, seed, img_fp16 & 31, img, cache, s);
 }
 
@@ -5733,6 +5943,7 @@ int ffx_render_fwd_adjoint(const void *bvh, const ffx_bvh_info *info, const ffx_
   FFX_NO_APPEARANCE(img_fp16, "render_fwd_adjoint");
   FFX_NO_TANGENT(img_fp16, "render_fwd_adjoint");
   FFX_NO_AOV(img_fp16, "render_fwd_adjoint");
+  FFX_NO_LIGHTS(img_fp16, "render_fwd_adjoint");
   return render_fwd_impl(bvh, info, sd, shape_albedo, tex, spp, seed, img_fp16 & (FFX_RENDER_FP16 | FFX_RENDER_SPARSE_ADJOINT | FFX_RENDER_APEX_READY), img, nullptr, s, gimg,
                          gtex, dot_out);
 }
@@ -6031,6 +6242,9 @@ int ffx_render_bwd(const void *bvh, const ffx_bvh_info *info, const ffx_scene_de
   FFX_NO_TANGENT(flags, "render_bwd");
   FFX_NO_AOV(flags, "render_bwd");
   FFX_MATERIAL_NEEDS_APPEARANCE(flags, "render_bwd");
+  if ((flags & FFX_RENDER_LIGHTS_MASK) && (flags & (FFX_RENDER_GRAD_APPEARANCE | FFX_RENDER_GRAD_MATERIAL | FFX_RENDER_GRAD_PRB)))
+    FFX_FAIL(FFX_ERR_UNSUPPORTED, "render_bwd: FFX_RENDER_LIGHTS is not served together with a FFX_RENDER_GRAD_* bit (the extra emitters are not differentiated)");
+  flags &= ~FFX_RENDER_LIGHTS_MASK; // (the texture's adjoint does not see the extra emitters: the bits are ignored, the tail behind the table is not read)
   if (flags & FFX_RENDER_GRAD_APPEARANCE) return render_bwd_leaves(bvh, info, sd, shape_albedo, spp, seed, flags, gimg, gtex, s, nullptr);
   return render_bwd_impl(bvh, info, sd, shape_albedo, spp, seed, flags, gimg, gtex, s, nullptr);
 }
@@ -6048,6 +6262,7 @@ int ffx_render_bwd_det(const void *bvh, const ffx_bvh_info *info, const ffx_scen
   FFX_NO_APPEARANCE(flags, "render_bwd_det");
   FFX_NO_TANGENT(flags, "render_bwd_det");
   FFX_NO_AOV(flags, "render_bwd_det");
+  FFX_NO_LIGHTS(flags, "render_bwd_det");
   // workspace: [the filtered film's scratch (16-byte multiple)] [one 64-bit sum per texel and channel] [the largest tap]
   void *rf = sd->rfilter != FFX_RFILTER_BOX ? workspace : nullptr;
   void *det = (char *)workspace + (rf ? ffx_render_filter_bytes(sd) : 0);
@@ -6062,6 +6277,7 @@ int ffx_render_bwd_det_part(const void *bvh, const ffx_bvh_info *info, const ffx
   FFX_NO_APPEARANCE(flags, "render_bwd_det_part");
   FFX_NO_TANGENT(flags, "render_bwd_det_part");
   FFX_NO_AOV(flags, "render_bwd_det_part");
+  FFX_NO_LIGHTS(flags, "render_bwd_det_part");
   void *rf = nullptr;
   if (sd->rfilter != FFX_RFILTER_BOX) {
     if (!workspace || ((uintptr_t)workspace & 15) != 0) FFX_FAIL(FFX_ERR_ARG, "render_bwd_det_part: a filtered film needs its scratch (ffx_render_filter_bytes), 16-byte aligned");
@@ -6090,11 +6306,7 @@ size_t ffx_render_filter_bytes(const ffx_scene_desc *sd) {
 int ffx_render_fwd_filtered(const void *bvh, const ffx_bvh_info *info, const ffx_scene_desc *sd, const float *shape_albedo, const float *tex, int spp,
                             uint32_t seed, int img_fp16, void *img, void *scratch, ffx_stream s) {
   if (!scratch || ((uintptr_t)scratch & 15) != 0) FFX_FAIL(FFX_ERR_ARG, "render_fwd_filtered: scratch is NULL or not 16-byte aligned");
-  FFX_NO_APPEARANCE(img_fp16, "render_fwd_filtered");
-  if (img_fp16 & FFX_RENDER_AOV) return render_aov(bvh, info, sd, shape_albedo, tex, spp, seed, img_fp16, img, s, scratch);
-  if (img_fp16 & FFX_RENDER_TANGENT) return render_jvp(bvh, info, sd, shape_albedo, tex, spp, seed, img_fp16, img, s, scratch);
-  return render_fwd_impl(bvh, info, sd, shape_albedo, tex, spp, seed, img_fp16 & (FFX_RENDER_FP16 | FFX_RENDER_APEX_READY | FFX_RENDER_PATH_MASK), img, nullptr, s, nullptr,
-                         nullptr, nullptr, scratch);
+  return render_fwd_entry(bvh, info, sd, shape_albedo, tex, spp, seed, img_fp16, img, s, scratch);
 }
 
 int ffx_render_fwd_adjoint_filtered(const void *bvh, const ffx_bvh_info *info, const ffx_scene_desc *sd, const float *shape_albedo, const float *tex, int spp,
@@ -6106,6 +6318,7 @@ int ffx_render_fwd_adjoint_filtered(const void *bvh, const ffx_bvh_info *info, c
   FFX_NO_APPEARANCE(img_fp16, "render_fwd_adjoint_filtered");
   FFX_NO_TANGENT(img_fp16, "render_fwd_adjoint_filtered");
   FFX_NO_AOV(img_fp16, "render_fwd_adjoint_filtered");
+  FFX_NO_LIGHTS(img_fp16, "render_fwd_adjoint_filtered");
   return render_fwd_impl(bvh, info, sd, shape_albedo, tex, spp, seed, img_fp16 & (FFX_RENDER_FP16 | FFX_RENDER_SPARSE_ADJOINT | FFX_RENDER_APEX_READY), img, nullptr, s, gimg,
                          gtex, nullptr, scratch);
 }
@@ -6116,6 +6329,9 @@ int ffx_render_bwd_filtered(const void *bvh, const ffx_bvh_info *info, const ffx
   FFX_NO_TANGENT(flags, "render_bwd_filtered");
   FFX_NO_AOV(flags, "render_bwd_filtered");
   FFX_MATERIAL_NEEDS_APPEARANCE(flags, "render_bwd_filtered");
+  if ((flags & FFX_RENDER_LIGHTS_MASK) && (flags & (FFX_RENDER_GRAD_APPEARANCE | FFX_RENDER_GRAD_MATERIAL | FFX_RENDER_GRAD_PRB)))
+    FFX_FAIL(FFX_ERR_UNSUPPORTED, "render_bwd_filtered: FFX_RENDER_LIGHTS is not served together with a FFX_RENDER_GRAD_* bit (the extra emitters are not differentiated)");
+  flags &= ~FFX_RENDER_LIGHTS_MASK; // (the texture's adjoint does not see the extra emitters: the bits are ignored, the tail behind the table is not read)
   if (flags & FFX_RENDER_GRAD_APPEARANCE) return render_bwd_leaves(bvh, info, sd, shape_albedo, spp, seed, flags, gimg, gtex, s, scratch);
   return render_bwd_impl(bvh, info, sd, shape_albedo, spp, seed, flags, gimg, gtex, s, scratch);
 }
@@ -6128,6 +6344,7 @@ int ffx_render_fwd_cache_filtered(const void *bvh, const ffx_bvh_info *info, con
   FFX_NO_APPEARANCE(img_fp16, "render_fwd_cache_filtered");
   FFX_NO_TANGENT(img_fp16, "render_fwd_cache_filtered");
   FFX_NO_AOV(img_fp16, "render_fwd_cache_filtered");
+  FFX_NO_LIGHTS(img_fp16, "render_fwd_cache_filtered");
   return render_fwd_impl(bvh, info, sd, shape_albedo, tex, spp, seed,
                          img_fp16 & (FFX_RENDER_FP16 | FFX_RENDER_SPARSE_ADJOINT | FFX_RENDER_APEX_READY | FFX_RENDER_CACHE_ZEROED | FFX_RENDER_CACHE_KEEP_DROPPED), img, nullptr, s,
                          nullptr, nullptr, nullptr, scratch, cache);

@@ -8,7 +8,10 @@ module reads what those scene files contain so that `mi.load_file(path)` keeps w
   <sensor type="perspective">   fov, near_clip, far_clip, <transform name="to_world">, <film> width/height
   <shape type="obj"|"ply">       filename (Wavefront OBJ; Stanford PLY ascii / binary), optional to_world (baked into the vertices),
                                  nested or referenced <bsdf>: diffuse reflectance, or principled with its scalar parameters (scenes.PRINCIPLED_DEFAULTS)
-  <emitter type="spot">          intensity, cutoff_angle, beam_width, to_world
+  <emitter type="spot">          intensity, cutoff_angle, beam_width, to_world.  The first one is SceneData.spot (the packet kernels' emitter);
+                                 every further one goes to SceneData.lights in file order
+  <emitter type="point">         position (a <point>) or the translation of to_world, intensity (default 1): to SceneData.lights in file order.
+                                 Beyond scenes.MAX_EXTRA_LIGHTS entries the rest are reported once and dropped
   <emitter type="projector">     irradiance texture (id "tex"), scale, fov, to_world
   <transform>                    <matrix value="16 floats">, <lookat origin target up>, <translate>, <scale>,
                                  <rotate x|y|z angle>  (applied in document order, like Mitsuba)
@@ -373,6 +376,7 @@ def _albedo_of(bsdf, bsdfs):
     return tuple(col), bsdf.get("id") or "mat-Default", params
 
 
+_POINT_PROPS = {"intensity", "position"}
 _SENSOR_PROPS = {"fov", "fov_axis", "near_clip", "far_clip", "focus_distance", "principal_point_offset_x", "principal_point_offset_y"}
 _FILM_PROPS = {"width", "height", "pixel_format", "component_format", "file_format", "sample_border", "compensate", "crop_offset_x", "crop_offset_y", "crop_width", "crop_height"}
 _SHAPE_PROPS = {"filename", "face_normals", "flip_tex_coords", "flip_normals"}
@@ -453,7 +457,13 @@ def load_mitsuba_xml(path):
     root = ET.fromstring(text)
     base = os.path.dirname(os.path.abspath(path))
     bsdfs = {b.get("id"): b for b in root.iter("bsdf") if b.get("id")}
-    sensors, meshes, spot, projector, proj_scale = [], [], None, None, 1.0
+    sensors, meshes, spot, projector, proj_scale, lights = [], [], None, None, 1.0, []
+
+    def extra_light(light):
+        if len(lights) < scenes.MAX_EXTRA_LIGHTS:
+            lights.append(light)
+        else:
+            dropped("lights.max", f"more than {scenes.MAX_EXTRA_LIGHTS} emitters beyond the projector and the first spot: the rest are dropped (first: {light.name!r})")
     dropped = _Dropped(path)
     notes = {"source": path}
     have_integrator = False
@@ -545,7 +555,21 @@ def load_mitsuba_xml(path):
                 inten = p.get("intensity", (1.0, 1.0, 1.0))
                 inten = (inten,) * 3 if isinstance(inten, float) else inten
                 cutoff = float(p.get("cutoff_angle", 20.0))
-                spot = scenes.SpotData(node.get("id") or "emit-Spot", tw, tuple(inten), cutoff, float(p.get("beam_width", cutoff * 0.75)))
+                beam = float(p.get("beam_width", cutoff * 0.75))
+                if spot is None:
+                    spot = scenes.SpotData(node.get("id") or "emit-Spot", tw, tuple(inten), cutoff, beam)
+                else:  # (a later spot no longer replaces the first)
+                    extra_light(scenes.LightData(node.get("id") or f"emit-Spot-{len(lights) + 1}", "spot", tw, tuple(inten), cutoff, beam))
+            elif node.get("type") == "point":
+                dropped.props(node, _POINT_PROPS, "point emitter")
+                inten = p.get("intensity", (1.0, 1.0, 1.0))
+                inten = (inten,) * 3 if isinstance(inten, float) else inten
+                pos = _child(node, "point", "position")
+                if pos is not None:  # <point name="position" value="x y z"/> or x= y= z=
+                    xyz = _floats(pos.get("value")) if pos.get("value") is not None else [float(pos.get(a, 0.0)) for a in "xyz"]
+                    tw = np.eye(4)
+                    tw[:3, 3] = (xyz * 3)[:3] if len(xyz) == 1 else xyz[:3]
+                extra_light(scenes.LightData(node.get("id") or f"emit-Point-{len(lights) + 1}", "point", tw, tuple(inten)))
             elif node.get("type") == "projector":
                 dropped.props(node, _PROJ_PROPS, "projector emitter")
                 projector = (tw, float(p.get("fov", 45.0)), p.get("fov_axis"))
@@ -571,4 +595,4 @@ def load_mitsuba_xml(path):
         if m.bsdf is not None and float(m.bsdf.get("spec_trans", 0.0)) > 0.0:
             dropped("spec_trans", f"material {m.material!r}: spec_trans > 0 — the principled BSDF's transmission lobe is not evaluated; spec_trans only scales the "
                                   "diffuse lobe (DESIGN.md 4.3)")
-    return scenes.SceneData(meshes, sensors[0], proj, spot, proj_scale, notes=notes)
+    return scenes.SceneData(meshes, sensors[0], proj, spot, proj_scale, notes=notes, lights=lights)

@@ -626,6 +626,20 @@ class Scene:
             p._init(s.name + ".intensity.value", Color3f(torch.tensor(s.intensity, dtype=torch.float32)))
             p._init(s.name + ".cutoff_angle", Float(s.cutoff_angle))
             p._init(s.name + ".beam_width", Float(s.beam_width))
+        # extra emitters: a point light's `position` and intensity, a further spot's pose, intensity and cone; read when the table of a
+        # render is formed (lights_table)
+        if len(d.lights) > scenes.MAX_EXTRA_LIGHTS:
+            raise ValueError(f"at most {scenes.MAX_EXTRA_LIGHTS} emitters beyond the projector and the spot, got {len(d.lights)}")
+        for l in d.lights:
+            if l.kind == "point":
+                p._init(l.name + ".position", Color3f(torch.as_tensor(np.asarray(l.to_world, np.float32).reshape(4, 4)[:3, 3].copy())))
+            else:
+                p._init(l.name + ".to_world", Transform4f(l.to_world))
+                p._init(l.name + ".cutoff_angle", Float(l.cutoff_angle))
+                p._init(l.name + ".beam_width", Float(l.beam_width))
+            p._init(l.name + ".intensity.value", Color3f(torch.tensor(l.intensity, dtype=torch.float32)))
+        self._light_names = frozenset(l.name for l in d.lights)
+        self._lights_dev = None
         # (the BSDF parameters: every key a principled material exposes, and the `specular` / `roughness` that diffuse ones keep, whose gradient is 0)
         bsdf = [m + ".brdf_0.specular" for m in mats] + [m + ".brdf_0.roughness.value" for m in mats]
         bsdf += [m + f".brdf_0.{k}.value" for m, ms in mats.items() if ms[0].bsdf is not None for k in scenes.PRINCIPLED_DEFAULTS if k not in ("specular", "roughness")]
@@ -638,6 +652,32 @@ class Scene:
 
     def sensors(self):
         return self._sensors
+
+    def current_lights(self):
+        """the extra emitters (scenes.LightData) with the values the parameter map holds now"""
+        p, out = self._params, []
+
+        def vec3(v):
+            return tuple(float(x) for x in (v.t if isinstance(v, _ArrayBase) else torch.as_tensor(v, dtype=torch.float32)).detach().reshape(-1)[:3].cpu())
+
+        for l in self.data.lights:
+            inten = vec3(p[l.name + ".intensity.value"])
+            if l.kind == "point":
+                tw = np.eye(4, dtype=np.float32)
+                tw[:3, 3] = vec3(p[l.name + ".position"])
+                out.append(scenes.LightData(l.name, "point", tw, inten))
+            else:
+                out.append(scenes.LightData(l.name, "spot", self._mat(l.name + ".to_world"), inten, float(p[l.name + ".cutoff_angle"]), float(p[l.name + ".beam_width"])))
+        return out
+
+    def lights_table(self):
+        """the [n, 24] device table of the extra emitters for the render calls' `lights` (ops.pack_lights), None for a scene without; rebuilt after a
+        params.update() that touched one of their keys"""
+        if not self.data.lights:
+            return None
+        if self._lights_dev is None:
+            self._lights_dev = ops.pack_lights(self.current_lights()).to(self.device)
+        return self._lights_dev
 
     def ray_intersect(self, ray, active=True):
         """scene.ray_intersect(mi.Ray3f(o, d)) (depth.py:41,77,115,157): the closest hit of every ray against the current pose
@@ -784,6 +824,8 @@ class Scene:
                 else:
                     if not (rest.startswith("brdf_0.") or rest == "vertex_positions"):
                         plan[k] = _PLAIN_KEY  # (an emitter / sensor / texture parameter: read when the scene description is formed)
+        if self._light_names and any(k.partition(".")[0] in self._light_names for k in dirty):
+            self._lights_dev = None  # (the next render packs the table again)
         if albedo_dirty:
             if self._mats_in_sd:
                 self._albedo_stale = True  # the next scene_desc() carries the new rows; the device tensor is refreshed on demand
@@ -798,6 +840,7 @@ class Scene:
             dyn = kd.get(k)
             if dyn is None:
                 dyn = kd[k] = (k.endswith(".__pose__") or k.endswith(".to_world") or k.endswith(".intensity.value") or k.endswith(".vertex_positions") or k == "tex.data"
+                               or (k.endswith(".position") and k.partition(".")[0] in self._light_names)
                                or k.endswith(".cutoff_angle") or k.endswith(".beam_width") or (".brdf_0." in k and not k.endswith(".data")))
             if not dyn:
                 self._sd_templates = {}
@@ -828,6 +871,9 @@ class Scene:
         name)] — the writes of Scene._apply_native.  -> the compiled plan, or None (not compilable, or not yet: a key never pushed before)"""
         g = self.geom
         if not (g._async and g.n_shapes <= 32 and self.device.type == "cuda") or ops._lane_kernels():
+            return None
+        # (an extra emitter's values live in the lights' table, which the native push does not write: the key-by-key path serves them, DESIGN.md 4.7)
+        if any(key.partition(".")[0] in self._light_names for _, key in poses) or any(v[3].partition(".")[0] in self._light_names for v in values):
             return None
         d, stride = self.data, self._mat_stride
         sd_pose = {d.camera.name + ".to_world": _SD_CAM_TW}
@@ -1285,6 +1331,9 @@ def render(scene: Scene, params: SceneParameters = None, spp: int = 16, seed: in
         raise NotImplementedError("only sensor 0 renders; further sensors are projector proxies")
     if integrator is not None and not isinstance(integrator, Integrator):
         raise TypeError("render: integrator must come from mi.load_dict")
+    lights = scene.lights_table() if _has_lights(scene) else None
+    if lights is not None and fp16:
+        raise ValueError("mi.render: a scene with extra emitters (point lights, further spots) has no fp16 film")
     if integrator is not None and integrator.type == "aov":
         return _render_aov(scene, params, spp, seed, fp16, integrator)
     if scene._params._leaves and torch.is_grad_enabled():
@@ -1300,10 +1349,11 @@ def render(scene: Scene, params: SceneParameters = None, spp: int = 16, seed: in
     try:
         if tex.requires_grad and torch.is_grad_enabled():
             scene.render_paths["autograd"] += 1
-            img = Fn.render(tex, scene.geom, sd, scene.materials_arg(sd), spp, seed, fp16, md, rr)
+            img = Fn.render(tex, scene.geom, sd, scene.materials_arg(sd), spp, seed, fp16, md, rr, lights=lights)
         else:  # nothing to differentiate: straight to the kernel (autograd.Function.apply costs ~80 us of host time per call)
             mats = scene.materials_arg(sd)
-            slot = scene._render_stream(tex_in, mats) if tex_in is not None and not deep else None
+            # (extra emitters: a device table travels with the call — the caller's stream, like the device material tables)
+            slot = scene._render_stream(tex_in, mats) if tex_in is not None and not deep and lights is None else None
             if slot is not None:  # beside the previous render, on the scene's other render stream
                 rs, done, priv = slot
                 scene.render_paths["two_stream"] += 1
@@ -1312,10 +1362,15 @@ def render(scene: Scene, params: SceneParameters = None, spp: int = 16, seed: in
                     done.record(rs)
                 return _RenderedXf(img, done)
             scene.render_paths["caller_stream"] += 1
-            img = scene.geom.render_fwd(sd, mats, Fn._tex3(tex), int(spp), int(seed), bool(fp16), max_depth=md, rr_depth=rr)
+            img = scene.geom.render_fwd(sd, mats, Fn._tex3(tex), int(spp), int(seed), bool(fp16), max_depth=md, rr_depth=rr, lights=lights)
         return TensorXf(img)
     finally:  # (the launcher counts its choice when it launches: two reads of a word of the library, no call into it)
         scene.render_paths["k8_plain"] += k8[0] - k8_plain0
+
+
+def _has_lights(scene):
+    """does the scene hold emitters beyond the projector and the spot?"""
+    return bool(getattr(getattr(scene, "data", None), "lights", None))
 
 
 def _render_aov(scene, params, spp, seed, fp16, integrator):
@@ -1332,7 +1387,8 @@ def _render_aov(scene, params, spp, seed, fp16, integrator):
     grad = inner is not None and torch.is_grad_enabled() and (tex.requires_grad or bool(scene._params._leaves))
     rgb = render(scene, params, spp, seed, 0, False, inner).torch() if grad else None
     md, rr = (inner.max_depth, inner.rr_depth) if inner is not None and not grad else (2, 5)
-    img, block = scene.geom.render_aov(sd, scene.materials_arg(sd), Fn._tex3(tex.detach()), int(spp), int(seed), max_depth=md, rr_depth=rr)
+    img, block = scene.geom.render_aov(sd, scene.materials_arg(sd), Fn._tex3(tex.detach()), int(spp), int(seed), max_depth=md, rr_depth=rr,
+                                       lights=scene.lights_table() if _has_lights(scene) else None)
     parts = []
     for _, type_ in integrator.aovs:
         first, n = ops.AOV_CHANNELS[type_]
@@ -1418,6 +1474,9 @@ def render_forward(scene: Scene, params: SceneParameters = None, tangents: dict 
     if integrator is not None and not isinstance(integrator, Integrator):
         raise TypeError("render_forward: integrator must come from mi.load_dict")
     _no_aov(integrator, "render_forward")
+    if _has_lights(scene):
+        raise NotImplementedError("render_forward: the scene has extra emitters (point lights, further spots), which are not differentiated: no forward mode "
+                                  "is served for it (DESIGN.md 4.7)")
     if not isinstance(tangents, dict):
         raise TypeError("render_forward: tangents must be a dict of parameter key -> tensor")
     allowed = _forward_keys(scene)
@@ -1528,6 +1587,10 @@ class _AppearanceRender(torch.autograd.Function):
 
 def _render_appearance(scene, spp, seed, fp16, integrator):
     """mi.render while appearance leaves are assigned and grad is enabled: through _AppearanceRender on the caller's stream"""
+    if _has_lights(scene):
+        raise NotImplementedError("mi.render: the scene has extra emitters (point lights, further spots), which are not differentiated: the gradients of base "
+                                  "colours, spot intensity and BSDF parameters are not served for it (DESIGN.md 4.7).  The scene holds parameters that require "
+                                  "grad: " + ", ".join(sorted(scene._params._leaves)))
     if integrator is not None and integrator.max_depth > 2 and integrator.type != "prb":
         raise ValueError("mi.render: under the 'path' integrator the gradients of base colours, spot intensity and BSDF parameters are served for direct "
                          "light only (max_depth 2); use the 'prb' integrator (mi.load_dict({'type': 'prb', ...})) for max_depth > 2.  "

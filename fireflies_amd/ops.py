@@ -565,6 +565,23 @@ def _no_path(max_depth, what):
         raise ValueError(f"{what}: max_depth > 2 renders through render_fwd / render_bwd only (no adjoint cache, fused or deterministic adjoint)")
 
 
+def pack_lights(lights):
+    """the table of a render's extra emitters (include/ffx.h FFX_RENDER_LIGHTS): scenes.LightData entries -> [n, 24] float32 on the host
+    (to_world 0..15 row-major, intensity 16..18, cutoff_deg 19, beam_width_deg 20, type 21: 0 point / 1 spot, 22..23 zero)"""
+    lights = list(lights)
+    if len(lights) > _abi.RENDER_MAX_LIGHTS:
+        raise ValueError(f"at most {_abi.RENDER_MAX_LIGHTS} extra emitters, got {len(lights)}")
+    out = torch.zeros((len(lights), _abi.LIGHT_FLOATS), dtype=torch.float32)
+    for k, l in enumerate(lights):
+        if l.kind not in ("point", "spot"):
+            raise ValueError(f"light {l.name!r}: kind must be 'point' or 'spot', got {l.kind!r}")
+        out[k, :16] = torch.as_tensor(np.asarray(l.to_world, dtype=np.float32).reshape(16))
+        out[k, 16:19] = torch.as_tensor([float(v) for v in l.intensity], dtype=torch.float32)
+        out[k, 19], out[k, 20] = float(l.cutoff_angle), float(l.beam_width)
+        out[k, 21] = float(_abi.LIGHT_SPOT if l.kind == "spot" else _abi.LIGHT_POINT)
+    return out
+
+
 # the block of render_aov (include/ffx.h FFX_RENDER_AOV): channel -> (first float, floats), in the block's order
 AOV_CHANNELS = {"depth": (0, 1), "position": (1, 3), "geo_normal": (4, 3), "sh_normal": (7, 3), "uv": (10, 2), "albedo": (12, 3), "shape_index": (15, 1),
                 "prim_index": (16, 1)}
@@ -990,6 +1007,29 @@ class DeviceGeometry:
     def _timed(self, name):
         return _EventPair(self.timing, name)
 
+    def _with_lights(self, sd, albedo, mats_arg, lights, what):
+        """a call's extra emitters (include/ffx.h FFX_RENDER_LIGHTS): -> (the shape_albedo argument, the flags bits, the buffer to keep alive).  lights:
+        None / empty — the call as it was; else a [n, 24] float32 device tensor (pack_lights), which travels behind the material table in one buffer
+        [table | lights] (a scene description that carries its rows: their area is there but not read)"""
+        if lights is None or lights.numel() == 0:
+            return mats_arg, 0, None
+        if lights.dim() != 2 or lights.shape[1] != _abi.LIGHT_FLOATS or lights.dtype != torch.float32:
+            raise ValueError(f"{what}: lights must be a [n, {_abi.LIGHT_FLOATS}] float32 tensor (ops.pack_lights)")
+        n = int(lights.shape[0])
+        if n > _abi.RENDER_MAX_LIGHTS:
+            raise ValueError(f"{what}: at most {_abi.RENDER_MAX_LIGHTS} extra emitters, got {n}")
+        ms = max(int(sd.mat_stride), 3)
+        S = int(sd.n_shapes)
+        if albedo is not None:
+            _check_table(sd, albedo)
+            rows = albedo[:S].detach().to(device=self.device, dtype=torch.float32).reshape(-1)
+        else:
+            rows = torch.zeros(S * ms, dtype=torch.float32, device=self.device)
+        buf = torch.cat([rows, lights.detach().to(self.device).reshape(-1)]).contiguous()
+        if ms == _abi.MAT_STRIDE and buf.data_ptr() % 16:
+            raise ValueError(f"{what}: the [table | lights] buffer is not 16-byte aligned")
+        return _dev(buf, name="albedo"), _abi.render_lights(n), buf
+
     def _launch(self, timer, name, film, blob, sd, lead, spp, seed, flags, *rest):
         """every render call that reads a blob: `name`(blob, info, sd, *lead, spp, seed, flags, *rest, [scratch,] stream) inside the `timer` bracket, then
         the release.  lead: (materials,) for the adjoints, (materials, texture) for the forwards.  film: what `name` does about a film with a
@@ -1016,7 +1056,7 @@ class DeviceGeometry:
         self._launch("render_bwd", "ffx_render_bwd", _TWIN, blob, sd, (mats_arg,), spp, seed, flags, gimg_arg, gtex_arg)
 
     def render_fwd(self, sd, albedo, tex, spp, seed=0, fp16=False, cache=None, sparse_adjoint=False, cache_zeroed=False, keep_dropped=False, img_out=None,
-                   max_depth=2, rr_depth=5):
+                   max_depth=2, rr_depth=5, lights=None):
         """K8.  With `cache` (a uint8 tensor of render_cache_bytes(...) bytes) the kernel also stores one
         footprint of every pixel in the projector texture for render_bwd_cached (opaque layout, ffx.h).
         sparse_adjoint (with a cache): FFX_RENDER_SPARSE_ADJOINT — gradients are only wanted at texels whose value is
@@ -1024,10 +1064,14 @@ class DeviceGeometry:
         cleared the first 64 bytes of `cache` on this stream.  keep_dropped: FFX_RENDER_CACHE_KEEP_DROPPED — the header's count of dropped
         samples survives this call's reset (the later scene samples of a step that reuses one cache).
         A filtered film (sd.rfilter) with a cache: ffx_render_fwd_cache_filtered (per-sample records; render_bwd_cached needs the seed).
-        max_depth > 2: Mitsuba's `path` integrator — no cache; its adjoint is render_bwd with the same max_depth / rr_depth / seed."""
+        max_depth > 2: Mitsuba's `path` integrator — no cache; its adjoint is render_bwd with the same max_depth / rr_depth / seed.
+        lights: a [n, 24] float32 device tensor of extra emitters (pack_lights) — the image of the call without them plus each light's own
+        part, at direct light and under max_depth > 2, on either film; fp32 film, no cache."""
         path = path_flags(max_depth, rr_depth) if max_depth != 2 else 0
         if path and cache is not None:
             raise ValueError("render_fwd: max_depth > 2 has no adjoint cache (its adjoint is render_bwd with the same max_depth)")
+        if lights is not None and lights.numel() and (fp16 or cache is not None):
+            raise ValueError("render_fwd: extra emitters (lights=) are served on the fp32 film without an adjoint cache")
         H, W = sd.cam.height, sd.cam.width
         self._last_spp = spp
         mats_arg = _check_materials(sd, albedo)
@@ -1038,6 +1082,8 @@ class DeviceGeometry:
         # (the path integrator walks per lane and reads neither apex records nor tile bins: it claims nothing about the blob's apex areas, and rewrites none)
         flags = int(bool(fp16)) | (path if path else self._apex_flag(apex_key(sd)))
         if cache is None:
+            mats_arg, lbits, _keep = self._with_lights(sd, albedo, mats_arg, lights, "render_fwd")
+            flags |= lbits
             self._launch_fwd("render_fwd", blob, sd, mats_arg, _dev(tex, name="tex") if tex is not None else None, spp, seed, flags, _dev(img, img.dtype))
             return img
         # ... and the records of the adjoint: one footprint per pixel, under a filtered film every sample's (ABI 7)
@@ -1131,7 +1177,7 @@ class DeviceGeometry:
         self._launch("render_bwd", "ffx_render_bwd_det_part", _SLOT, blob, sd, (mats_arg,), spp, seed, flags,
                      _dev(gimg, name="gimg"), int(part), int(scale_log2), C.c_void_p(acc.data_ptr()))
 
-    def render_bwd(self, sd, albedo, spp, seed, gimg, deterministic=None, max_depth=2, rr_depth=5, appearance=False, tex=None, material=False):
+    def render_bwd(self, sd, albedo, spp, seed, gimg, deterministic=None, max_depth=2, rr_depth=5, appearance=False, tex=None, material=False, lights=None):
         """the re-tracing adjoint.  deterministic (default: FFX_DETERMINISTIC=1 in the environment): ffx_render_bwd_det — bitwise
         reproducible accumulation (64-bit fixed point instead of float atomics; two re-traces and one host synchronisation).
         max_depth > 2: the path integrator's adjoint — replays render_fwd's paths of the same max_depth, rr_depth, spp and seed (float atomics only).
@@ -1139,7 +1185,11 @@ class DeviceGeometry:
         d spot intensity and d loss / d base-colour texture; `tex` is the forward's projector texture (needed when the scene has a projector).
         Direct light (max_depth 2) and the float-atomic adjoint only.
         material=True (with appearance=True; FFX_RENDER_GRAD_MATERIAL): AppearanceGrad.material also holds d loss / d the principled BSDF's
-        parameters per material row [n_shapes, 11]."""
+        parameters per material row [n_shapes, 11].
+        lights: the forward's extra emitters.  They do not depend on the projector's texture: gtex is that of the call without them (the float-atomic
+        adjoint is handed the forward's bits and ignores them; the deterministic one is called without).  Not with appearance=True."""
+        if lights is not None and lights.numel() and appearance:
+            raise NotImplementedError("render_bwd(appearance=True): extra emitters (lights=) are not differentiated")
         if material and not appearance:
             raise ValueError("render_bwd(material=True) needs appearance=True (the material block extends the appearance adjoint)")
         if appearance:
@@ -1170,6 +1220,10 @@ class DeviceGeometry:
         # renders.  Before, they always re-ran the pre-pass — and rewrote the tile bins under the eyes of renders of the same pose on the scene's other
         # render stream)
         flags = path if path else self._apex_flag(apex_key(sd))
+        if lights is not None and lights.numel():  # (accepted and ignored: the table's tail is not read, so the table alone travels)
+            if lights.dim() != 2 or lights.shape[0] > _abi.RENDER_MAX_LIGHTS:
+                raise ValueError(f"render_bwd: lights must be [n <= {_abi.RENDER_MAX_LIGHTS}, {_abi.LIGHT_FLOATS}]")
+            flags |= _abi.render_lights(lights.shape[0])
         self._launch_bwd(blob, sd, mats_arg, spp, seed, flags, _dev(gimg, name="gimg"), _dev(gtex))
         return gtex
 
@@ -1204,18 +1258,20 @@ class DeviceGeometry:
         self._launch_fwd("render_jvp", blob, sd, _dev(albedo, name="albedo"), _dev(buf, name="tex"), spp, seed, flags, _dev(out))
         return out[0], out[1]
 
-    def render_aov(self, sd, albedo, tex, spp, seed=0, *, max_depth=2, rr_depth=5):
+    def render_aov(self, sd, albedo, tex, spp, seed=0, *, max_depth=2, rr_depth=5, lights=None):
         """the render and its ground truth (FFX_RENDER_AOV): -> (img [H, W, 3], aov [H, W, 17]), img the image of render_fwd with the
         same arguments bit for bit, aov the primary hit's depth, position, normals, uv, base colour and ids (AOV_CHANNELS names the offsets) through the
-        same film over the same samples.  max_depth > 2 chooses the image only.  fp32 film; two calls give the same bits."""
+        same film over the same samples.  max_depth > 2 chooses the image only.  fp32 film; two calls give the same bits.  lights (pack_lights, as
+        render_fwd): the image carries the extra emitters, the block is that of the call without them."""
         path = path_flags(max_depth, rr_depth) if max_depth != 2 else 0
         H, W = sd.cam.height, sd.cam.width
         mats_arg = _check_materials(sd, albedo)
+        mats_arg, lbits, _keep = self._with_lights(sd, albedo, mats_arg, lights, "render_aov")
         out = torch.empty(H * W * (3 + _abi.RENDER_AOV_FLOATS), dtype=torch.float32, device=self.device)
         blob = self.blob
         # (the block's launch reads the camera's apex records and bins: behind a path render, which writes none, the call runs the pre-pass itself unless
         # the blob already holds this pose's)
-        flags = path | self._apex_flag(apex_key(sd)) | _abi.RENDER_AOV
+        flags = path | self._apex_flag(apex_key(sd)) | _abi.RENDER_AOV | lbits
         self._launch_fwd("render_aov", blob, sd, mats_arg, _dev(tex, name="tex") if tex is not None else None, spp, seed, flags, _dev(out))
         return out[:H * W * 3].view(H, W, 3), out[H * W * 3:].view(H, W, _abi.RENDER_AOV_FLOATS)
 

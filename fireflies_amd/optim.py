@@ -157,7 +157,8 @@ class PatternOptimizer:
         self.ff_scene.randomize()
         leaf = tex_value.detach().clone().requires_grad_(True)
         sd = self.mi_scene.scene_desc(tex_channels=1)
-        img = Fn.render(leaf, self.mi_scene.geom, sd, self.mi_scene.materials_arg(sd), self.spp, seed, max_depth=self.max_depth, rr_depth=self.rr_depth)
+        img = Fn.render(leaf, self.mi_scene.geom, sd, self.mi_scene.materials_arg(sd), self.spp, seed, max_depth=self.max_depth, rr_depth=self.rr_depth,
+                        lights=self.mi_scene.lights_table() if getattr(self.mi_scene.data, "lights", None) else None)
         loss = self.loss_fn(img)
         (g,) = torch.autograd.grad(loss, leaf)
         return g, loss.detach()
@@ -203,6 +204,9 @@ class PatternOptimizer:
         launches — ffx_pattern_fwd (K1 + K2 sum + softor + the regulariser's partial sums), then _update_local or _update_exchanged.  As ~30 separate
         launches the pattern side cost 0.11 ms per step next to a 0.75 ms render; through torch.autograd the step was host-bound."""
         rays, KF, ms = self.laser._rays, self.laser._KF, self.mi_scene
+        if getattr(ms.data, "lights", None):
+            raise NotImplementedError("PatternOptimizer.step: the scene has extra emitters (point lights, further spots), which the explicit adjoint routes do not "
+                                      "render (DESIGN.md 4.7): use step_autograd")
         rd, (s0, s1), cam = rays.detach(), self.tex_size, ms.data.camera
         seeds = self._sample_seeds(self.step_index)
         sd0 = ms.scene_desc(tex_channels=1)  # (sizes only: the pose of the samples comes later)

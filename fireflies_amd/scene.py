@@ -228,6 +228,10 @@ class Scene:
                 if any(k.lower() in low for k in keys):
                     loader(root)
                     break
+        # the extra emitters are listed after the main spot, whatever their names sort to
+        main = getattr(getattr(getattr(mitsuba_params, "_scene", None), "data", None), "spot", None)
+        if main is not None and len(self._lights) > 1:
+            self._lights.sort(key=lambda l: l.name() != main.name)
 
     def _to_world_of(self, base_key):
         return self._mitsuba_params[base_key + ".to_world"].matrix.torch().squeeze().to(self._device)
@@ -668,6 +672,12 @@ class Scene:
         return plan.step
 
     def _push_native(self, plan, vals, mats, k, picks) -> bool:
+        ms = getattr(self._mitsuba_params, "_scene", None)
+        extra = getattr(ms, "_light_names", None)
+        if extra and any(l.randomizable() and l.name() in extra for l in self._lights):
+            # (an extra emitter's values go into the lights' table of the render, not into the description the native push writes: key by key)
+            ms.update_fallbacks["extra emitters"] = ms.update_fallbacks.get("extra emitters", 0) + 1
+            return False
         sp = self._step_plan(plan)
         if sp is None:
             return False

@@ -89,6 +89,24 @@ class SpotData:
     beam_width: float = 15.0
 
 
+MAX_EXTRA_LIGHTS = 8  # (include/ffx.h FFX_RENDER_MAX_LIGHTS)
+
+
+@dataclass
+class LightData:
+    """an emitter beyond the main spot: a point light (only to_world's translation counts) or a further spot"""
+    name: str
+    kind: str  # "point" | "spot"
+    to_world: np.ndarray
+    intensity: tuple = (1.0, 1.0, 1.0)
+    cutoff_angle: float = 20.0
+    beam_width: float = 15.0
+
+    def __post_init__(self):
+        if self.kind not in ("point", "spot"):
+            raise ValueError(f"LightData.kind must be 'point' or 'spot', got {self.kind!r}")
+
+
 @dataclass
 class SceneData:
     meshes: List[MeshData]
@@ -97,6 +115,7 @@ class SceneData:
     spot: Optional[SpotData] = None
     projector_scale: float = 1.0
     notes: dict = field(default_factory=dict)
+    lights: List[LightData] = field(default_factory=list)  # extra emitters, at most MAX_EXTRA_LIGHTS (last: the constructors above pass by position)
 
     @property
     def n_tris(self):

@@ -577,7 +577,8 @@ int ffx_trace_rays(const void *bvh /*[dev]*/, const ffx_bvh_info *info /*[host]*
  * Replaces mi.render(scene, spp=...) (examples/vocalfold_scene.py:102, main.py:156) and its
  * Dr.Jit backward w.r.t. `tex.data` (examples/vocalfold_scene.py:69).  Shading model
  * (DESIGN.md §4): direct illumination at the primary hit from two delta emitters
- * (projector with irradiance texture, spot light), Lambert or principled BSDF per shape, optional
+ * (projector with irradiance texture, spot light) and, with FFX_RENDER_LIGHTS, up to
+ * FFX_RENDER_MAX_LIGHTS further point lights and spots; Lambert or principled BSDF per shape, optional
  * shadow rays, box reconstruction filter, counter-based per-sample jitter.
  * The render is linear in the texture, so the adjoint needs no forward state: it replays
  * the same samples (same seed) and scatters d(loss)/d(img) through the bilinear weights.
@@ -849,6 +850,34 @@ int ffx_det_finish(const void *acc /*[dev] int64 [n]*/, int scale_log2, size_t n
  * other render entry point; FFX_ERR_ARG without a material table (shape_albedo NULL and no rows in sd->mat_h).  The oracle ignores the bit. */
 #define FFX_RENDER_AOV 0x100000
 #define FFX_RENDER_AOV_FLOATS 17
+/* Extra emitters: FFX_RENDER_LIGHTS(n), n = 1 .. FFX_RENDER_MAX_LIGHTS, in the img_fp16 word of ffx_render_fwd / ffx_render_fwd_filtered adds n
+ * further delta emitters — point lights and spots beyond ffx_scene_desc.spot — to the image.  An additive extension of ABI 11 (FFX_ABI_VERSION is unchanged;
+ * no struct changes, no new entry point).
+ *   input  — shape_albedo: the material table's n_shapes x max(mat_stride, 3) floats, followed in the same buffer by n records of FFX_LIGHT_FLOATS floats:
+ *              0..15   to_world, row-major, as ffx_spot.to_world (a point light: only the translation is read)
+ *              16..18  intensity RGB
+ *              19      cutoff_deg      (spots)
+ *              20      beam_width_deg  (spots)
+ *              21      type: FFX_LIGHT_POINT (0.0) or FFX_LIGHT_SPOT (1.0)
+ *              22..23  reserved, written 0
+ *            shape_albedo must be non-NULL even when sd->mat_h carries the rows (the rows' area is then skipped, not read): FFX_ERR_ARG otherwise, and
+ *            for n = 9 .. 15.
+ *   output — img: the image of the call without the bits (its launches, bit for bit) plus, per extra emitter, what that emitter alone adds — the path
+ *            sampling does not depend on the emitters, so the image is linear in them.  Evaluated where the projector and the spot are: the primary hit,
+ *            and every path vertex under FFX_RENDER_PATH; the spot's falloff, shadow ray and BSDF rows.  With FFX_RENDER_AOV the block is that of the call
+ *            without the bits.
+ * Written by further launches on the same stream behind those of the main image; no atomics (two calls give the same bits), no host synchronisation.
+ * FFX_ERR_UNSUPPORTED together with FFX_RENDER_FP16, FFX_RENDER_TANGENT or a FFX_RENDER_GRAD_* bit and on every other render entry point — except that
+ * ffx_render_bwd / ffx_render_bwd_filtered without a FFX_RENDER_GRAD_* bit accept and ignore the bits (the extra emitters do not depend on the projector's
+ * texture: gtex is that of the call without them, and the tail is not read), so a caller can hand the forward's flags to the adjoint.  The oracle does not
+ * know the bits: never pass them to it. */
+#define FFX_RENDER_MAX_LIGHTS 8
+#define FFX_RENDER_LIGHTS_SHIFT 21
+#define FFX_RENDER_LIGHTS_MASK 0x1e00000
+#define FFX_RENDER_LIGHTS(n) (((n) & 15) << FFX_RENDER_LIGHTS_SHIFT)
+#define FFX_LIGHT_FLOATS 24
+#define FFX_LIGHT_POINT 0
+#define FFX_LIGHT_SPOT 1
 /* Writes the apex records (the triangles as seen from a fixed ray origin) of sd's camera and enabled emitters into
  * the blob's apex areas — what every packet render does in front of its kernel unless told FFX_RENDER_APEX_READY.  Only
  * sd->cam.to_world, sd->proj.{enabled,to_world} and sd->spot.{enabled,to_world} are read.  No reference counterpart (Mitsuba
