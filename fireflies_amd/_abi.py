@@ -227,6 +227,12 @@ def render_lights(n):
     return (int(n) & 15) << RENDER_LIGHTS_SHIFT
 
 
+# the constant emitter (include/ffx.h FFX_RENDER_AMBIENT): bit 25 of the same word; one record of AMBIENT_FLOATS floats (radiance r, g, b, reserved 0)
+# follows the n light records (n may be 0) in the shape_albedo buffer
+RENDER_AMBIENT = 0x2000000
+AMBIENT_FLOATS = 4
+
+
 MAX_BASE_TEX = 4
 RFILTER_BOX, RFILTER_GAUSSIAN = 0, 1
 MAX_MAT_H = 128

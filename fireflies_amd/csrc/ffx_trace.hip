@@ -3852,9 +3852,13 @@ struct NoBounce {
 // visit(v, st, ap, mv, d, beta) sees the emitters' terms and the throughput (ap with APP, mv with MAT: shade_sample's); then the bounce (vertex
 // v < max_depth - 1), the roulette (v >= rr_depth: q and the survival test are constants of a replay) and, after a bounce that survived,
 // bounce(v, st, pv, ap, d, wo, beta, iq, f, pb) — beta is the throughput in front of the bounce, iq = 1 / q_v, pb.tau is formed with APP only —
-// and the secondary ray from the lifted point.  !EMIT: shade_sample's — the main emitters are left out and the visitor is visit(v, st, pv, d, beta)
-template <bool APP = false, bool MAT = false, bool EMIT = true, typename V, typename B = NoBounce>
-__device__ __forceinline__ void path_walk(const PathArgs &a, uint32_t idx, v3 o, v3 d, float nt, float ft, int *stack, int stride, V &&visit, B &&bounce = B()) {
+// and the secondary ray from the lifted point.  !EMIT: shade_sample's — the main emitters are left out and the visitor is visit(v, st, pv, d, beta).
+// AMB (the constant emitter): escaped(beta) is told of every ray of the walk that hit nothing — the camera ray (beta = 1), a bounce ray
+// (beta: the throughput behind that bounce) — and the last vertex, where the walk stops, makes its bounce all the same (direction, weight, roulette: the
+// numbers (v, 0..2) no other walk draws) as ONE any-hit ray from the lifted point: a bounce that ends in an occlusion test
+template <bool APP = false, bool MAT = false, bool EMIT = true, bool AMB = false, typename V, typename B = NoBounce, typename E = NoBounce>
+__device__ __forceinline__ void path_walk(const PathArgs &a, uint32_t idx, v3 o, v3 d, float nt, float ft, int *stack, int stride, V &&visit, B &&bounce = B(),
+                                          E &&escaped = E()) {
   const ShadeK &c = kernarg_shade();
   SampleTerms st;
   std::conditional_t<EMIT, PathVtx, PathVtxP> pv;
@@ -3862,10 +3866,14 @@ __device__ __forceinline__ void path_walk(const PathArgs &a, uint32_t idx, v3 o,
   MatVtx mv;
   shade_sample<true, APP, MAT, EMIT>(c, a.nodes, a.recs, a.nrec, o, d, nt, ft, st, stack, stride, &pv, &ap, &mv);
   float beta[3] = {1.f, 1.f, 1.f};
+  if constexpr (AMB) {
+    if (!st.hit) escaped(beta);
+  }
   for (int v = 1; st.hit && pv.ok; ++v) {
     if constexpr (EMIT) visit(v, st, ap, mv, d, beta);
     else visit(v, st, pv, d, beta);
-    if (v + 1 >= a.max_depth) break;
+    const bool last = v + 1 >= a.max_depth;
+    if (!AMB && last) break;
     const v3 wo = cosine_dir(pv.ns, path_u(a.path_key, idx, v, 0), path_u(a.path_key, idx, v, 1));
     if (!(vdot(pv.ng, wo) > 0.f)) break;
     float f[3], nb[3];
@@ -3881,11 +3889,21 @@ __device__ __forceinline__ void path_walk(const PathArgs &a, uint32_t idx, v3 o,
       iq = 1.0f / q;
       nb[0] *= iq; nb[1] *= iq; nb[2] *= iq;
     }
+    if constexpr (AMB) {
+      if (last) { // the closing ray (every lane that comes this far comes here in the same turn of the loop: max_depth is uniform)
+        Hit hc;
+        if (!traverse<true, false>(a.nodes, a.recs, pv.Po, wo, 0.f, 3.0e38f, hc, stack, stride)) escaped(nb);
+        break;
+      }
+    }
     bounce(v, st, pv, ap, d, wo, beta, iq, f, pb);
     beta[0] = nb[0]; beta[1] = nb[1]; beta[2] = nb[2];
     o = pv.Po;
     d = wo;
     shade_sample<true, APP, MAT, EMIT>(c, a.nodes, a.recs, a.nrec, o, d, 0.f, 3.0e38f, st, stack, stride, &pv, &ap, &mv);
+    if constexpr (AMB) {
+      if (!st.hit) escaped(beta);
+    }
   }
 }
 __device__ __forceinline__ float wave_sum_tree(float v) { // (fixed order: the same bits on every run)
@@ -4051,6 +4069,60 @@ __global__ void __launch_bounds__(64)
       path_walk<false, false, false>(a, idx, o, d, nt, ft, s_dyn + lane, 64, [&](int, const SampleTerms &st, const PathVtxP &pv, v3 dv, const float (&beta)[3]) {
         lights_at_vertex(kernarg_shade(), a, s_l, n, st, pv, dv, beta, s_dyn + lane, 64, L);
       });
+    }
+    if (RF) {
+      float gx[5], gy[5];
+      rf_weights(c.rf, jx, gx);
+      rf_weights(c.rf, jy, gy);
+      rf_fold(s_rf, lane, gx, gy, L[0], L[1], L[2], s < a.spp ? 1.f : 0.f, acc);
+    } else {
+      acc[0] += L[0]; acc[1] += L[1]; acc[2] += L[2];
+    }
+  }
+  if (RF) {
+    rf_store(part, pix, lane, acc);
+    return;
+  }
+  const float inv_spp = 1.0f / (float)a.spp;
+  const float m0 = wave_sum_tree(acc[0]) * inv_spp, m1 = wave_sum_tree(acc[1]) * inv_spp, m2 = wave_sum_tree(acc[2]) * inv_spp;
+  if (lane == 0) {
+    float *p = img + (size_t)pix * 3;
+    p[0] += m0; p[1] += m1; p[2] += m2;
+  }
+}
+// FFX_RENDER_AMBIENT (include/ffx.h): k_lights_fwd with the constant emitter in the same walk — its record (r, g, b, 0) stands behind the
+// n_lights records (n_lights may be 0); every ray of the walk that escapes, and the closing ray at its last vertex (path_walk's AMB), adds throughput x
+// radiance to the sample that the lights' terms go to.  A kernel of its own so that k_lights_fwd keeps its machine code (tools/isa_same.py)
+template <bool RF>
+__global__ void __launch_bounds__(64)
+    k_lights_ambient_fwd(ShadeK c, PathArgs a, const float *__restrict__ lights, int n_lights, float *__restrict__ img, float *__restrict__ part) {
+  extern __shared__ int s_dyn[];
+  __shared__ __attribute__((aligned(16))) float s_rf[RF ? FFX_RF_FLOATS : 4];
+  __shared__ float s_l[FFX_RENDER_MAX_LIGHTS * FFX_LK_FLOATS];
+  const int lane = threadIdx.x;
+  const uint32_t pix = blockIdx.x;
+  const int W = c.cam.W, px = (int)(pix % (uint32_t)W), py = (int)(pix / (uint32_t)W);
+  const int n = n_lights < FFX_RENDER_MAX_LIGHTS ? n_lights : FFX_RENDER_MAX_LIGHTS; // (the host refuses more: s_l holds this many)
+  lights_derive(lights, n, lane, s_l);
+  const float *la = lights + (size_t)FFX_LIGHT_FLOATS * n; // (the ambient record, at a wave-uniform address: scalar loads)
+  const float la0 = la[0], la1 = la[1], la2 = la[2];
+  float acc[4] = {0.f, 0.f, 0.f, 0.f};
+  for (int pass = 0; pass < (a.spp + 63) >> 6; ++pass) {
+    const int s = pass * 64 + lane;
+    const uint32_t idx = pix * (uint32_t)a.spp + (uint32_t)s;
+    float jx, jy;
+    sample_jitter(a.seed_key, idx, jx, jy);
+    float L[3] = {0.f, 0.f, 0.f};
+    if (s < a.spp) {
+      v3 o, d;
+      float nt, ft;
+      cam_ray(c.cam, ((float)px + jx) * c.cam.inv_w, ((float)py + jy) * c.cam.inv_h, o, d, nt, ft);
+      path_walk<false, false, false, true>(
+          a, idx, o, d, nt, ft, s_dyn + lane, 64,
+          [&](int, const SampleTerms &st, const PathVtxP &pv, v3 dv, const float (&beta)[3]) {
+            lights_at_vertex(kernarg_shade(), a, s_l, n, st, pv, dv, beta, s_dyn + lane, 64, L);
+          },
+          NoBounce(), [&](const float (&beta)[3]) { L[0] += beta[0] * la0; L[1] += beta[1] * la1; L[2] += beta[2] * la2; });
     }
     if (RF) {
       float gx[5], gy[5];
@@ -5840,10 +5912,20 @@ static int render_aov(const void *bvh, const ffx_bvh_info *info, const ffx_scene
 }
 // the extra emitters' bits belong to ffx_render_fwd[_filtered] (and are ignored by ffx_render_bwd[_filtered]): every other render entry point refuses them
 #define FFX_NO_LIGHTS(flags_, what_) \
-  do { if ((flags_) & FFX_RENDER_LIGHTS_MASK) FFX_FAIL(FFX_ERR_UNSUPPORTED, "%s: FFX_RENDER_LIGHTS is served by ffx_render_fwd[_filtered] only", what_); } while (0)
+  do { \
+    if ((flags_) & FFX_RENDER_LIGHTS_MASK) FFX_FAIL(FFX_ERR_UNSUPPORTED, "%s: FFX_RENDER_LIGHTS is served by ffx_render_fwd[_filtered] only", what_); \
+    if ((flags_) & FFX_RENDER_AMBIENT) FFX_FAIL(FFX_ERR_UNSUPPORTED, "%s: FFX_RENDER_AMBIENT is served by ffx_render_fwd[_filtered] only", what_); \
+  } while (0)
 // FFX_RENDER_LIGHTS (include/ffx.h).  What a forward refuses about the bits before it launches anything: FFX_OK, or the error
 static int lights_check(int flags, const float *shape_albedo, const char *what) {
   const int n = (flags & FFX_RENDER_LIGHTS_MASK) >> FFX_RENDER_LIGHTS_SHIFT;
+  if (flags & FFX_RENDER_AMBIENT) { // the constant emitter: the same refusals under its own name
+    if (flags & FFX_RENDER_FP16) FFX_FAIL(FFX_ERR_UNSUPPORTED, "%s: FFX_RENDER_AMBIENT has no fp16 film", what);
+    if (flags & FFX_RENDER_TANGENT) FFX_FAIL(FFX_ERR_UNSUPPORTED, "%s: FFX_RENDER_AMBIENT is not served together with FFX_RENDER_TANGENT", what);
+    if (flags & (FFX_RENDER_GRAD_APPEARANCE | FFX_RENDER_GRAD_MATERIAL | FFX_RENDER_GRAD_PRB))
+      FFX_FAIL(FFX_ERR_UNSUPPORTED, "%s: FFX_RENDER_AMBIENT is not served together with a FFX_RENDER_GRAD_* bit (the constant emitter is not differentiated)", what);
+    if (!shape_albedo) FFX_FAIL(FFX_ERR_ARG, "%s: FFX_RENDER_AMBIENT needs the device buffer [material table | lights | ambient] (shape_albedo is NULL)", what);
+  }
   if (n == 0) return FFX_OK;
   if (n > FFX_RENDER_MAX_LIGHTS) FFX_FAIL(FFX_ERR_ARG, "%s: FFX_RENDER_LIGHTS(%d): at most %d extra emitters", what, n, FFX_RENDER_MAX_LIGHTS);
   if (flags & FFX_RENDER_FP16) FFX_FAIL(FFX_ERR_UNSUPPORTED, "%s: FFX_RENDER_LIGHTS has no fp16 film", what);
@@ -5854,7 +5936,8 @@ static int lights_check(int flags, const float *shape_albedo, const char *what) 
   return FFX_OK;
 }
 // ... and the pass, behind the launches of the main image on the same stream (the call without the bits has succeeded: its arguments are good):
-// k_lights_fwd adds to img; the gaussian film: into the scratch, which the image's (and an AOV block's) gathers have read by then, and k_lights_gather adds
+// k_lights_fwd adds to img; the gaussian film: into the scratch, which the image's (and an AOV block's) gathers have read by then, and k_lights_gather adds.
+// With FFX_RENDER_AMBIENT the same launches are k_lights_ambient_fwd's: one walk per sample serves the n lights (n may be 0) and the constant emitter
 static int render_lights(const void *bvh, const ffx_bvh_info *info, const ffx_scene_desc *sd, const float *shape_albedo, int spp, uint32_t seed, int flags, void *img,
                          ffx_stream s, void *rf_scratch) {
   const int n = (flags & FFX_RENDER_LIGHTS_MASK) >> FFX_RENDER_LIGHTS_SHIFT;
@@ -5865,14 +5948,15 @@ static int render_lights(const void *bvh, const ffx_bvh_info *info, const ffx_sc
   const float *table = shape_albedo + (size_t)sd->n_shapes * (size_t)r.c.mat_stride; // (mat_stride: 3 or FFX_MAT_STRIDE — max(mat_stride, 3))
   const PathArgs pa = path_args(r);
   const hipStream_t st = (hipStream_t)s;
+  const bool amb = (flags & FFX_RENDER_AMBIENT) != 0;
   if (rf_scratch) {
-    hipLaunchKernelGGL(k_lights_fwd<true>, dim3((unsigned)r.n_pix), dim3(64), path_stack_bytes(info), st, r.c, pa, table, n, (float *)nullptr, (float *)rf_scratch);
+    hipLaunchKernelGGL(amb ? k_lights_ambient_fwd<true> : k_lights_fwd<true>, dim3((unsigned)r.n_pix), dim3(64), path_stack_bytes(info), st, r.c, pa, table, n, (float *)nullptr, (float *)rf_scratch);
     FFX_CHECK_LAUNCH("render_fwd_filtered (lights)");
     hipLaunchKernelGGL(k_lights_gather, dim3(ffx_cdiv(r.c.cam.W, 64), r.c.cam.H), dim3(64), 0, st, (const float4 *)rf_scratch, r.c.cam.W, r.c.cam.H, (float *)img);
     FFX_CHECK_LAUNCH("render_fwd_filtered (lights)/gather");
     return FFX_OK;
   }
-  hipLaunchKernelGGL(k_lights_fwd<false>, dim3((unsigned)r.n_pix), dim3(64), path_stack_bytes(info), st, r.c, pa, table, n, (float *)img, (float *)nullptr);
+  hipLaunchKernelGGL(amb ? k_lights_ambient_fwd<false> : k_lights_fwd<false>, dim3((unsigned)r.n_pix), dim3(64), path_stack_bytes(info), st, r.c, pa, table, n, (float *)img, (float *)nullptr);
   FFX_CHECK_LAUNCH("render_fwd (lights)");
   return FFX_OK;
 }
@@ -5882,8 +5966,8 @@ static int render_fwd_entry(const void *bvh, const ffx_bvh_info *info, const ffx
   const char *what = scratch ? "render_fwd_filtered" : "render_fwd";
   if (const int rc = lights_check(img_fp16, shape_albedo, what)) return rc;
   FFX_NO_APPEARANCE(img_fp16, what);
-  const int lights = img_fp16 & FFX_RENDER_LIGHTS_MASK;
-  img_fp16 &= ~FFX_RENDER_LIGHTS_MASK;
+  const int lights = img_fp16 & (FFX_RENDER_LIGHTS_MASK | FFX_RENDER_AMBIENT);
+  img_fp16 &= ~(FFX_RENDER_LIGHTS_MASK | FFX_RENDER_AMBIENT);
   int rc;
   if (img_fp16 & FFX_RENDER_AOV) rc = render_aov(bvh, info, sd, shape_albedo, tex, spp, seed, img_fp16, img, s, scratch);
   else if (img_fp16 & FFX_RENDER_TANGENT) rc = render_jvp(bvh, info, sd, shape_albedo, tex, spp, seed, img_fp16, img, s, scratch);
@@ -6244,7 +6328,9 @@ int ffx_render_bwd(const void *bvh, const ffx_bvh_info *info, const ffx_scene_de
   FFX_MATERIAL_NEEDS_APPEARANCE(flags, "render_bwd");
   if ((flags & FFX_RENDER_LIGHTS_MASK) && (flags & (FFX_RENDER_GRAD_APPEARANCE | FFX_RENDER_GRAD_MATERIAL | FFX_RENDER_GRAD_PRB)))
     FFX_FAIL(FFX_ERR_UNSUPPORTED, "render_bwd: FFX_RENDER_LIGHTS is not served together with a FFX_RENDER_GRAD_* bit (the extra emitters are not differentiated)");
-  flags &= ~FFX_RENDER_LIGHTS_MASK; // (the texture's adjoint does not see the extra emitters: the bits are ignored, the tail behind the table is not read)
+  if ((flags & FFX_RENDER_AMBIENT) && (flags & (FFX_RENDER_GRAD_APPEARANCE | FFX_RENDER_GRAD_MATERIAL | FFX_RENDER_GRAD_PRB)))
+    FFX_FAIL(FFX_ERR_UNSUPPORTED, "render_bwd: FFX_RENDER_AMBIENT is not served together with a FFX_RENDER_GRAD_* bit (the constant emitter is not differentiated)");
+  flags &= ~(FFX_RENDER_LIGHTS_MASK | FFX_RENDER_AMBIENT); // (the texture's adjoint sees neither the extra emitters nor the constant one: the bits are ignored, the tail behind the table is not read)
   if (flags & FFX_RENDER_GRAD_APPEARANCE) return render_bwd_leaves(bvh, info, sd, shape_albedo, spp, seed, flags, gimg, gtex, s, nullptr);
   return render_bwd_impl(bvh, info, sd, shape_albedo, spp, seed, flags, gimg, gtex, s, nullptr);
 }
@@ -6331,7 +6417,9 @@ int ffx_render_bwd_filtered(const void *bvh, const ffx_bvh_info *info, const ffx
   FFX_MATERIAL_NEEDS_APPEARANCE(flags, "render_bwd_filtered");
   if ((flags & FFX_RENDER_LIGHTS_MASK) && (flags & (FFX_RENDER_GRAD_APPEARANCE | FFX_RENDER_GRAD_MATERIAL | FFX_RENDER_GRAD_PRB)))
     FFX_FAIL(FFX_ERR_UNSUPPORTED, "render_bwd_filtered: FFX_RENDER_LIGHTS is not served together with a FFX_RENDER_GRAD_* bit (the extra emitters are not differentiated)");
-  flags &= ~FFX_RENDER_LIGHTS_MASK; // (the texture's adjoint does not see the extra emitters: the bits are ignored, the tail behind the table is not read)
+  if ((flags & FFX_RENDER_AMBIENT) && (flags & (FFX_RENDER_GRAD_APPEARANCE | FFX_RENDER_GRAD_MATERIAL | FFX_RENDER_GRAD_PRB)))
+    FFX_FAIL(FFX_ERR_UNSUPPORTED, "render_bwd_filtered: FFX_RENDER_AMBIENT is not served together with a FFX_RENDER_GRAD_* bit (the constant emitter is not differentiated)");
+  flags &= ~(FFX_RENDER_LIGHTS_MASK | FFX_RENDER_AMBIENT); // (the texture's adjoint sees neither the extra emitters nor the constant one: the bits are ignored, the tail behind the table is not read)
   if (flags & FFX_RENDER_GRAD_APPEARANCE) return render_bwd_leaves(bvh, info, sd, shape_albedo, spp, seed, flags, gimg, gtex, s, scratch);
   return render_bwd_impl(bvh, info, sd, shape_albedo, spp, seed, flags, gimg, gtex, s, scratch);
 }

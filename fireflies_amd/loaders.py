@@ -12,6 +12,8 @@ module reads what those scene files contain so that `mi.load_file(path)` keeps w
                                  every further one goes to SceneData.lights in file order
   <emitter type="point">         position (a <point>) or the translation of to_world, intensity (default 1): to SceneData.lights in file order.
                                  Beyond scenes.MAX_EXTRA_LIGHTS entries the rest are reported once and dropped
+  <emitter type="constant">      radiance (an <rgb> or a single float, default 1): SceneData.ambient — ambient light and the colour of rays that leave
+                                 the scene.  Mitsuba allows one environment: a second one is reported once and ignored
   <emitter type="projector">     irradiance texture (id "tex"), scale, fov, to_world
   <transform>                    <matrix value="16 floats">, <lookat origin target up>, <translate>, <scale>,
                                  <rotate x|y|z angle>  (applied in document order, like Mitsuba)
@@ -377,6 +379,7 @@ def _albedo_of(bsdf, bsdfs):
 
 
 _POINT_PROPS = {"intensity", "position"}
+_CONSTANT_PROPS = {"radiance"}
 _SENSOR_PROPS = {"fov", "fov_axis", "near_clip", "far_clip", "focus_distance", "principal_point_offset_x", "principal_point_offset_y"}
 _FILM_PROPS = {"width", "height", "pixel_format", "component_format", "file_format", "sample_border", "compensate", "crop_offset_x", "crop_offset_y", "crop_width", "crop_height"}
 _SHAPE_PROPS = {"filename", "face_normals", "flip_tex_coords", "flip_normals"}
@@ -457,7 +460,7 @@ def load_mitsuba_xml(path):
     root = ET.fromstring(text)
     base = os.path.dirname(os.path.abspath(path))
     bsdfs = {b.get("id"): b for b in root.iter("bsdf") if b.get("id")}
-    sensors, meshes, spot, projector, proj_scale, lights = [], [], None, None, 1.0, []
+    sensors, meshes, spot, projector, proj_scale, lights, ambient = [], [], None, None, 1.0, [], None
 
     def extra_light(light):
         if len(lights) < scenes.MAX_EXTRA_LIGHTS:
@@ -570,6 +573,15 @@ def load_mitsuba_xml(path):
                     tw = np.eye(4)
                     tw[:3, 3] = (xyz * 3)[:3] if len(xyz) == 1 else xyz[:3]
                 extra_light(scenes.LightData(node.get("id") or f"emit-Point-{len(lights) + 1}", "point", tw, tuple(inten)))
+            elif node.get("type") == "constant":
+                if ambient is not None:
+                    dropped("constant.second", f"a second constant emitter ({node.get('id') or 'without id'!r}) ignored: a scene has one environment "
+                                               f"({ambient.name!r} is rendered)")
+                    continue
+                dropped.props(node, _CONSTANT_PROPS, "constant emitter")
+                rad = p.get("radiance", (1.0, 1.0, 1.0))
+                rad = (float(rad),) * 3 if isinstance(rad, (int, float)) else tuple(float(v) for v in rad)
+                ambient = scenes.AmbientData(node.get("id") or "emit-Constant", rad)
             elif node.get("type") == "projector":
                 dropped.props(node, _PROJ_PROPS, "projector emitter")
                 projector = (tw, float(p.get("fov", 45.0)), p.get("fov_axis"))
@@ -595,4 +607,4 @@ def load_mitsuba_xml(path):
         if m.bsdf is not None and float(m.bsdf.get("spec_trans", 0.0)) > 0.0:
             dropped("spec_trans", f"material {m.material!r}: spec_trans > 0 — the principled BSDF's transmission lobe is not evaluated; spec_trans only scales the "
                                   "diffuse lobe (DESIGN.md 4.3)")
-    return scenes.SceneData(meshes, sensors[0], proj, spot, proj_scale, notes=notes, lights=lights)
+    return scenes.SceneData(meshes, sensors[0], proj, spot, proj_scale, notes=notes, lights=lights, ambient=ambient)

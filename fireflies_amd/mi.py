@@ -640,6 +640,12 @@ class Scene:
             p._init(l.name + ".intensity.value", Color3f(torch.tensor(l.intensity, dtype=torch.float32)))
         self._light_names = frozenset(l.name for l in d.lights)
         self._lights_dev = None
+        # the constant emitter: its radiance; read when the record of a render is formed (ambient_record)
+        amb = getattr(d, "ambient", None)
+        self._ambient_name = amb.name if amb is not None else None
+        self._ambient_dev = None
+        if amb is not None:
+            p._init(amb.name + ".radiance.value", Color3f(torch.tensor([float(v) for v in amb.radiance], dtype=torch.float32)))
         # (the BSDF parameters: every key a principled material exposes, and the `specular` / `roughness` that diffuse ones keep, whose gradient is 0)
         bsdf = [m + ".brdf_0.specular" for m in mats] + [m + ".brdf_0.roughness.value" for m in mats]
         bsdf += [m + f".brdf_0.{k}.value" for m, ms in mats.items() if ms[0].bsdf is not None for k in scenes.PRINCIPLED_DEFAULTS if k not in ("specular", "roughness")]
@@ -678,6 +684,19 @@ class Scene:
         if self._lights_dev is None:
             self._lights_dev = ops.pack_lights(self.current_lights()).to(self.device)
         return self._lights_dev
+
+    def ambient_record(self):
+        """the constant emitter's radiance as a [3] device tensor for the render calls' `ambient`, None for a scene without; rebuilt
+        after a params.update() that touched `<id>.radiance.value`"""
+        if self._ambient_name is None:
+            return None
+        if self._ambient_dev is None:
+            v = self._params[self._ambient_name + ".radiance.value"]
+            v = (v.t if isinstance(v, _ArrayBase) else torch.as_tensor(v, dtype=torch.float32)).detach().to(torch.float32).reshape(-1)
+            if v.numel() == 1:
+                v = v.repeat(3)
+            self._ambient_dev = v[:3].to(self.device)
+        return self._ambient_dev
 
     def ray_intersect(self, ray, active=True):
         """scene.ray_intersect(mi.Ray3f(o, d)) (depth.py:41,77,115,157): the closest hit of every ray against the current pose
@@ -826,6 +845,8 @@ class Scene:
                         plan[k] = _PLAIN_KEY  # (an emitter / sensor / texture parameter: read when the scene description is formed)
         if self._light_names and any(k.partition(".")[0] in self._light_names for k in dirty):
             self._lights_dev = None  # (the next render packs the table again)
+        if self._ambient_name is not None and any(k.partition(".")[0] == self._ambient_name for k in dirty):
+            self._ambient_dev = None  # (... and the ambient record)
         if albedo_dirty:
             if self._mats_in_sd:
                 self._albedo_stale = True  # the next scene_desc() carries the new rows; the device tensor is refreshed on demand
@@ -841,6 +862,7 @@ class Scene:
             if dyn is None:
                 dyn = kd[k] = (k.endswith(".__pose__") or k.endswith(".to_world") or k.endswith(".intensity.value") or k.endswith(".vertex_positions") or k == "tex.data"
                                or (k.endswith(".position") and k.partition(".")[0] in self._light_names)
+                               or (k.endswith(".radiance.value") and k.partition(".")[0] == self._ambient_name)
                                or k.endswith(".cutoff_angle") or k.endswith(".beam_width") or (".brdf_0." in k and not k.endswith(".data")))
             if not dyn:
                 self._sd_templates = {}
@@ -874,6 +896,9 @@ class Scene:
             return None
         # (an extra emitter's values live in the lights' table, which the native push does not write: the key-by-key path serves them)
         if any(key.partition(".")[0] in self._light_names for _, key in poses) or any(v[3].partition(".")[0] in self._light_names for v in values):
+            return None
+        # (... and the constant emitter's radiance in the ambient record)
+        if self._ambient_name is not None and any(v[3].partition(".")[0] == self._ambient_name for v in values):
             return None
         d, stride = self.data, self._mat_stride
         sd_pose = {d.camera.name + ".to_world": _SD_CAM_TW}
@@ -1334,6 +1359,9 @@ def render(scene: Scene, params: SceneParameters = None, spp: int = 16, seed: in
     lights = scene.lights_table() if _has_lights(scene) else None
     if lights is not None and fp16:
         raise ValueError("mi.render: a scene with extra emitters (point lights, further spots) has no fp16 film")
+    ambient = scene.ambient_record() if _has_ambient(scene) else None
+    if ambient is not None and fp16:
+        raise ValueError("mi.render: a scene with a constant emitter (ambient light) has no fp16 film")
     if integrator is not None and integrator.type == "aov":
         return _render_aov(scene, params, spp, seed, fp16, integrator)
     if scene._params._leaves and torch.is_grad_enabled():
@@ -1349,11 +1377,11 @@ def render(scene: Scene, params: SceneParameters = None, spp: int = 16, seed: in
     try:
         if tex.requires_grad and torch.is_grad_enabled():
             scene.render_paths["autograd"] += 1
-            img = Fn.render(tex, scene.geom, sd, scene.materials_arg(sd), spp, seed, fp16, md, rr, lights=lights)
+            img = Fn.render(tex, scene.geom, sd, scene.materials_arg(sd), spp, seed, fp16, md, rr, lights=lights, ambient=ambient)
         else:  # nothing to differentiate: straight to the kernel (autograd.Function.apply costs ~80 us of host time per call)
             mats = scene.materials_arg(sd)
             # (extra emitters: a device table travels with the call — the caller's stream, like the device material tables)
-            slot = scene._render_stream(tex_in, mats) if tex_in is not None and not deep and lights is None else None
+            slot = scene._render_stream(tex_in, mats) if tex_in is not None and not deep and lights is None and ambient is None else None
             if slot is not None:  # beside the previous render, on the scene's other render stream
                 rs, done, priv = slot
                 scene.render_paths["two_stream"] += 1
@@ -1362,7 +1390,7 @@ def render(scene: Scene, params: SceneParameters = None, spp: int = 16, seed: in
                     done.record(rs)
                 return _RenderedXf(img, done)
             scene.render_paths["caller_stream"] += 1
-            img = scene.geom.render_fwd(sd, mats, Fn._tex3(tex), int(spp), int(seed), bool(fp16), max_depth=md, rr_depth=rr, lights=lights)
+            img = scene.geom.render_fwd(sd, mats, Fn._tex3(tex), int(spp), int(seed), bool(fp16), max_depth=md, rr_depth=rr, lights=lights, ambient=ambient)
         return TensorXf(img)
     finally:  # (the launcher counts its choice when it launches: two reads of a word of the library, no call into it)
         scene.render_paths["k8_plain"] += k8[0] - k8_plain0
@@ -1371,6 +1399,11 @@ def render(scene: Scene, params: SceneParameters = None, spp: int = 16, seed: in
 def _has_lights(scene):
     """does the scene hold emitters beyond the projector and the spot?"""
     return bool(getattr(getattr(scene, "data", None), "lights", None))
+
+
+def _has_ambient(scene):
+    """does the scene hold a constant emitter?"""
+    return getattr(getattr(scene, "data", None), "ambient", None) is not None
 
 
 def _render_aov(scene, params, spp, seed, fp16, integrator):
@@ -1388,7 +1421,8 @@ def _render_aov(scene, params, spp, seed, fp16, integrator):
     rgb = render(scene, params, spp, seed, 0, False, inner).torch() if grad else None
     md, rr = (inner.max_depth, inner.rr_depth) if inner is not None and not grad else (2, 5)
     img, block = scene.geom.render_aov(sd, scene.materials_arg(sd), Fn._tex3(tex.detach()), int(spp), int(seed), max_depth=md, rr_depth=rr,
-                                       lights=scene.lights_table() if _has_lights(scene) else None)
+                                       lights=scene.lights_table() if _has_lights(scene) else None,
+                                       ambient=scene.ambient_record() if _has_ambient(scene) else None)
     parts = []
     for _, type_ in integrator.aovs:
         first, n = ops.AOV_CHANNELS[type_]
@@ -1477,6 +1511,9 @@ def render_forward(scene: Scene, params: SceneParameters = None, tangents: dict 
     if _has_lights(scene):
         raise NotImplementedError("render_forward: the scene has extra emitters (point lights, further spots), which are not differentiated: no forward mode "
                                   "is served for it (DESIGN.md 4.7)")
+    if _has_ambient(scene):
+        raise NotImplementedError("render_forward: the scene has a constant emitter (ambient light), which is not differentiated: no forward mode is served "
+                                  "for it (DESIGN.md 4.8)")
     if not isinstance(tangents, dict):
         raise TypeError("render_forward: tangents must be a dict of parameter key -> tensor")
     allowed = _forward_keys(scene)
@@ -1591,6 +1628,10 @@ def _render_appearance(scene, spp, seed, fp16, integrator):
         raise NotImplementedError("mi.render: the scene has extra emitters (point lights, further spots), which are not differentiated: the gradients of base "
                                   "colours, spot intensity and BSDF parameters are not served for it (DESIGN.md 4.7).  The scene holds parameters that require "
                                   "grad: " + ", ".join(sorted(scene._params._leaves)))
+    if _has_ambient(scene):
+        raise NotImplementedError("mi.render: the scene has a constant emitter (ambient light), which is not differentiated: the gradients of base colours, "
+                                  "spot intensity and BSDF parameters are not served for it (DESIGN.md 4.8).  The scene holds parameters that require grad: "
+                                  + ", ".join(sorted(scene._params._leaves)))
     if integrator is not None and integrator.max_depth > 2 and integrator.type != "prb":
         raise ValueError("mi.render: under the 'path' integrator the gradients of base colours, spot intensity and BSDF parameters are served for direct "
                          "light only (max_depth 2); use the 'prb' integrator (mi.load_dict({'type': 'prb', ...})) for max_depth > 2.  "

@@ -582,6 +582,18 @@ def pack_lights(lights):
     return out
 
 
+def pack_ambient(ambient):
+    """a render's ambient record (include/ffx.h FFX_RENDER_AMBIENT): three floats, a [3] tensor or a scenes.AmbientData -> [4] float32
+    (radiance r, g, b and a reserved 0) on the tensor's device (the host otherwise); None stays None"""
+    if ambient is None:
+        return None
+    rad = getattr(ambient, "radiance", ambient)
+    t = rad.detach().to(torch.float32).reshape(-1) if isinstance(rad, torch.Tensor) else torch.tensor([float(v) for v in rad], dtype=torch.float32)
+    if t.numel() != 3:
+        raise ValueError(f"ambient: a radiance of three floats, got {t.numel()}")
+    return torch.cat([t, t.new_zeros(_abi.AMBIENT_FLOATS - 3)])
+
+
 # the block of render_aov (include/ffx.h FFX_RENDER_AOV): channel -> (first float, floats), in the block's order
 AOV_CHANNELS = {"depth": (0, 1), "position": (1, 3), "geo_normal": (4, 3), "sh_normal": (7, 3), "uv": (10, 2), "albedo": (12, 3), "shape_index": (15, 1),
                 "prim_index": (16, 1)}
@@ -1007,12 +1019,18 @@ class DeviceGeometry:
     def _timed(self, name):
         return _EventPair(self.timing, name)
 
-    def _with_lights(self, sd, albedo, mats_arg, lights, what):
+    def _with_lights(self, sd, albedo, mats_arg, lights, what, ambient=None):
         """a call's extra emitters (include/ffx.h FFX_RENDER_LIGHTS): -> (the shape_albedo argument, the flags bits, the buffer to keep alive).  lights:
         None / empty — the call as it was; else a [n, 24] float32 device tensor (pack_lights), which travels behind the material table in one buffer
-        [table | lights] (a scene description that carries its rows: their area is there but not read)"""
-        if lights is None or lights.numel() == 0:
+        [table | lights] (a scene description that carries its rows: their area is there but not read).  ambient (FFX_RENDER_AMBIENT):
+        three floats or a [3] tensor — its record stands behind the lights, [table | lights | ambient], with or without lights"""
+        amb = pack_ambient(ambient)
+        if lights is not None and lights.numel() == 0:
+            lights = None
+        if lights is None and amb is None:
             return mats_arg, 0, None
+        if lights is None:
+            lights = torch.zeros((0, _abi.LIGHT_FLOATS), dtype=torch.float32, device=self.device)
         if lights.dim() != 2 or lights.shape[1] != _abi.LIGHT_FLOATS or lights.dtype != torch.float32:
             raise ValueError(f"{what}: lights must be a [n, {_abi.LIGHT_FLOATS}] float32 tensor (ops.pack_lights)")
         n = int(lights.shape[0])
@@ -1025,10 +1043,11 @@ class DeviceGeometry:
             rows = albedo[:S].detach().to(device=self.device, dtype=torch.float32).reshape(-1)
         else:
             rows = torch.zeros(S * ms, dtype=torch.float32, device=self.device)
-        buf = torch.cat([rows, lights.detach().to(self.device).reshape(-1)]).contiguous()
+        parts = [rows, lights.detach().to(self.device).reshape(-1)] + ([amb.to(self.device)] if amb is not None else [])
+        buf = torch.cat(parts).contiguous()
         if ms == _abi.MAT_STRIDE and buf.data_ptr() % 16:
             raise ValueError(f"{what}: the [table | lights] buffer is not 16-byte aligned")
-        return _dev(buf, name="albedo"), _abi.render_lights(n), buf
+        return _dev(buf, name="albedo"), _abi.render_lights(n) | (_abi.RENDER_AMBIENT if amb is not None else 0), buf
 
     def _launch(self, timer, name, film, blob, sd, lead, spp, seed, flags, *rest):
         """every render call that reads a blob: `name`(blob, info, sd, *lead, spp, seed, flags, *rest, [scratch,] stream) inside the `timer` bracket, then
@@ -1056,7 +1075,7 @@ class DeviceGeometry:
         self._launch("render_bwd", "ffx_render_bwd", _TWIN, blob, sd, (mats_arg,), spp, seed, flags, gimg_arg, gtex_arg)
 
     def render_fwd(self, sd, albedo, tex, spp, seed=0, fp16=False, cache=None, sparse_adjoint=False, cache_zeroed=False, keep_dropped=False, img_out=None,
-                   max_depth=2, rr_depth=5, lights=None):
+                   max_depth=2, rr_depth=5, lights=None, ambient=None):
         """K8.  With `cache` (a uint8 tensor of render_cache_bytes(...) bytes) the kernel also stores one
         footprint of every pixel in the projector texture for render_bwd_cached (opaque layout, ffx.h).
         sparse_adjoint (with a cache): FFX_RENDER_SPARSE_ADJOINT — gradients are only wanted at texels whose value is
@@ -1066,12 +1085,16 @@ class DeviceGeometry:
         A filtered film (sd.rfilter) with a cache: ffx_render_fwd_cache_filtered (per-sample records; render_bwd_cached needs the seed).
         max_depth > 2: Mitsuba's `path` integrator — no cache; its adjoint is render_bwd with the same max_depth / rr_depth / seed.
         lights: a [n, 24] float32 device tensor of extra emitters (pack_lights) — the image of the call without them plus each light's own
-        part, at direct light and under max_depth > 2, on either film; fp32 film, no cache."""
+        part, at direct light and under max_depth > 2, on either film; fp32 film, no cache.
+        ambient: the constant emitter's radiance (three floats or a [3] tensor) — as lights: added to the image by the same pass, fp32
+        film, no cache."""
         path = path_flags(max_depth, rr_depth) if max_depth != 2 else 0
         if path and cache is not None:
             raise ValueError("render_fwd: max_depth > 2 has no adjoint cache (its adjoint is render_bwd with the same max_depth)")
         if lights is not None and lights.numel() and (fp16 or cache is not None):
             raise ValueError("render_fwd: extra emitters (lights=) are served on the fp32 film without an adjoint cache")
+        if ambient is not None and (fp16 or cache is not None):
+            raise ValueError("render_fwd: the constant emitter (ambient=) is served on the fp32 film without an adjoint cache")
         H, W = sd.cam.height, sd.cam.width
         self._last_spp = spp
         mats_arg = _check_materials(sd, albedo)
@@ -1082,7 +1105,7 @@ class DeviceGeometry:
         # (the path integrator walks per lane and reads neither apex records nor tile bins: it claims nothing about the blob's apex areas, and rewrites none)
         flags = int(bool(fp16)) | (path if path else self._apex_flag(apex_key(sd)))
         if cache is None:
-            mats_arg, lbits, _keep = self._with_lights(sd, albedo, mats_arg, lights, "render_fwd")
+            mats_arg, lbits, _keep = self._with_lights(sd, albedo, mats_arg, lights, "render_fwd", ambient)
             flags |= lbits
             self._launch_fwd("render_fwd", blob, sd, mats_arg, _dev(tex, name="tex") if tex is not None else None, spp, seed, flags, _dev(img, img.dtype))
             return img
@@ -1177,7 +1200,8 @@ class DeviceGeometry:
         self._launch("render_bwd", "ffx_render_bwd_det_part", _SLOT, blob, sd, (mats_arg,), spp, seed, flags,
                      _dev(gimg, name="gimg"), int(part), int(scale_log2), C.c_void_p(acc.data_ptr()))
 
-    def render_bwd(self, sd, albedo, spp, seed, gimg, deterministic=None, max_depth=2, rr_depth=5, appearance=False, tex=None, material=False, lights=None):
+    def render_bwd(self, sd, albedo, spp, seed, gimg, deterministic=None, max_depth=2, rr_depth=5, appearance=False, tex=None, material=False, lights=None,
+                   ambient=None):
         """the re-tracing adjoint.  deterministic (default: FFX_DETERMINISTIC=1 in the environment): ffx_render_bwd_det — bitwise
         reproducible accumulation (64-bit fixed point instead of float atomics; two re-traces and one host synchronisation).
         max_depth > 2: the path integrator's adjoint — replays render_fwd's paths of the same max_depth, rr_depth, spp and seed (float atomics only).
@@ -1187,7 +1211,10 @@ class DeviceGeometry:
         material=True (with appearance=True; FFX_RENDER_GRAD_MATERIAL): AppearanceGrad.material also holds d loss / d the principled BSDF's
         parameters per material row [n_shapes, 11].
         lights: the forward's extra emitters.  They do not depend on the projector's texture: gtex is that of the call without them (the float-atomic
-        adjoint is handed the forward's bits and ignores them; the deterministic one is called without).  Not with appearance=True."""
+        adjoint is handed the forward's bits and ignores them; the deterministic one is called without).  Not with appearance=True.
+        ambient: the forward's constant emitter — as lights: its bit is handed on and ignored.  Not with appearance=True."""
+        if ambient is not None and appearance:
+            raise NotImplementedError("render_bwd(appearance=True): the constant emitter (ambient=) is not differentiated")
         if lights is not None and lights.numel() and appearance:
             raise NotImplementedError("render_bwd(appearance=True): extra emitters (lights=) are not differentiated")
         if material and not appearance:
@@ -1224,6 +1251,9 @@ class DeviceGeometry:
             if lights.dim() != 2 or lights.shape[0] > _abi.RENDER_MAX_LIGHTS:
                 raise ValueError(f"render_bwd: lights must be [n <= {_abi.RENDER_MAX_LIGHTS}, {_abi.LIGHT_FLOATS}]")
             flags |= _abi.render_lights(lights.shape[0])
+        if ambient is not None:  # (accepted and ignored likewise)
+            pack_ambient(ambient)
+            flags |= _abi.RENDER_AMBIENT
         self._launch_bwd(blob, sd, mats_arg, spp, seed, flags, _dev(gimg, name="gimg"), _dev(gtex))
         return gtex
 
@@ -1258,15 +1288,15 @@ class DeviceGeometry:
         self._launch_fwd("render_jvp", blob, sd, _dev(albedo, name="albedo"), _dev(buf, name="tex"), spp, seed, flags, _dev(out))
         return out[0], out[1]
 
-    def render_aov(self, sd, albedo, tex, spp, seed=0, *, max_depth=2, rr_depth=5, lights=None):
+    def render_aov(self, sd, albedo, tex, spp, seed=0, *, max_depth=2, rr_depth=5, lights=None, ambient=None):
         """the render and its ground truth (FFX_RENDER_AOV): -> (img [H, W, 3], aov [H, W, 17]), img the image of render_fwd with the
         same arguments bit for bit, aov the primary hit's depth, position, normals, uv, base colour and ids (AOV_CHANNELS names the offsets) through the
         same film over the same samples.  max_depth > 2 chooses the image only.  fp32 film; two calls give the same bits.  lights (pack_lights, as
-        render_fwd): the image carries the extra emitters, the block is that of the call without them."""
+        render_fwd): the image carries the extra emitters, the block is that of the call without them.  ambient: likewise."""
         path = path_flags(max_depth, rr_depth) if max_depth != 2 else 0
         H, W = sd.cam.height, sd.cam.width
         mats_arg = _check_materials(sd, albedo)
-        mats_arg, lbits, _keep = self._with_lights(sd, albedo, mats_arg, lights, "render_aov")
+        mats_arg, lbits, _keep = self._with_lights(sd, albedo, mats_arg, lights, "render_aov", ambient)
         out = torch.empty(H * W * (3 + _abi.RENDER_AOV_FLOATS), dtype=torch.float32, device=self.device)
         blob = self.blob
         # (the block's launch reads the camera's apex records and bins: behind a path render, which writes none, the call runs the pre-pass itself unless

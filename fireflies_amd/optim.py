@@ -158,7 +158,8 @@ class PatternOptimizer:
         leaf = tex_value.detach().clone().requires_grad_(True)
         sd = self.mi_scene.scene_desc(tex_channels=1)
         img = Fn.render(leaf, self.mi_scene.geom, sd, self.mi_scene.materials_arg(sd), self.spp, seed, max_depth=self.max_depth, rr_depth=self.rr_depth,
-                        lights=self.mi_scene.lights_table() if getattr(self.mi_scene.data, "lights", None) else None)
+                        lights=self.mi_scene.lights_table() if getattr(self.mi_scene.data, "lights", None) else None,
+                        ambient=self.mi_scene.ambient_record() if getattr(self.mi_scene.data, "ambient", None) is not None else None)
         loss = self.loss_fn(img)
         (g,) = torch.autograd.grad(loss, leaf)
         return g, loss.detach()
@@ -207,6 +208,9 @@ class PatternOptimizer:
         if getattr(ms.data, "lights", None):
             raise NotImplementedError("PatternOptimizer.step: the scene has extra emitters (point lights, further spots), which the explicit adjoint routes do not "
                                       "render (DESIGN.md 4.7): use step_autograd")
+        if getattr(ms.data, "ambient", None) is not None:
+            raise NotImplementedError("PatternOptimizer.step: the scene has a constant emitter (ambient light), which the explicit adjoint routes do not "
+                                      "render (DESIGN.md 4.8): use step_autograd")
         rd, (s0, s1), cam = rays.detach(), self.tex_size, ms.data.camera
         seeds = self._sample_seeds(self.step_index)
         sd0 = ms.scene_desc(tex_channels=1)  # (sizes only: the pose of the samples comes later)

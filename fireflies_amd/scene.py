@@ -222,8 +222,13 @@ class Scene:
         roots = sorted({key.split(".")[0] for key in mitsuba_params.keys()})
         table = [(self.MESH_KEYS, self.load_mesh), (self.CAM_KEYS, self.load_camera), (self.PROJ_KEYS, self.load_projector),
                  (self.LIGHT_KEYS, self.load_light), (self.MAT_KEYS, self.load_material)]
+        # (the constant emitter, DESIGN.md 4.8, is listed with the lights whatever its id says)
+        ambient = getattr(getattr(mitsuba_params, "_scene", None), "_ambient_name", None)
         for root in roots:
             low = root.lower()
+            if ambient is not None and root == ambient:
+                self.load_light(root)
+                continue
             for keys, loader in table:
                 if any(k.lower() in low for k in keys):
                     loader(root)
@@ -677,6 +682,11 @@ class Scene:
         if extra and any(l.randomizable() and l.name() in extra for l in self._lights):
             # (an extra emitter's values go into the lights' table of the render, not into the description the native push writes: key by key)
             ms.update_fallbacks["extra emitters"] = ms.update_fallbacks.get("extra emitters", 0) + 1
+            return False
+        amb = getattr(ms, "_ambient_name", None)
+        if amb is not None and any(l.randomizable() and l.name() == amb for l in self._lights):
+            # (the constant emitter's radiance goes into the ambient record of the render, DESIGN.md 4.8: key by key likewise)
+            ms.update_fallbacks["constant emitter"] = ms.update_fallbacks.get("constant emitter", 0) + 1
             return False
         sp = self._step_plan(plan)
         if sp is None:

@@ -108,6 +108,13 @@ class LightData:
 
 
 @dataclass
+class AmbientData:
+    """the constant emitter: Mitsuba's <emitter type="constant"> — ambient light, and the colour of rays that leave the scene"""
+    name: str
+    radiance: tuple = (1.0, 1.0, 1.0)
+
+
+@dataclass
 class SceneData:
     meshes: List[MeshData]
     camera: SensorData
@@ -115,7 +122,8 @@ class SceneData:
     spot: Optional[SpotData] = None
     projector_scale: float = 1.0
     notes: dict = field(default_factory=dict)
-    lights: List[LightData] = field(default_factory=list)  # extra emitters, at most MAX_EXTRA_LIGHTS (last: the constructors above pass by position)
+    lights: List[LightData] = field(default_factory=list)  # extra emitters, at most MAX_EXTRA_LIGHTS
+    ambient: Optional[AmbientData] = None  # the constant emitter (last: the constructors above pass by position)
 
     @property
     def n_tris(self):

@@ -578,7 +578,8 @@ int ffx_trace_rays(const void *bvh /*[dev]*/, const ffx_bvh_info *info /*[host]*
  * Dr.Jit backward w.r.t. `tex.data` (examples/vocalfold_scene.py:69).  Shading model
  * (DESIGN.md §4): direct illumination at the primary hit from two delta emitters
  * (projector with irradiance texture, spot light) and, with FFX_RENDER_LIGHTS, up to
- * FFX_RENDER_MAX_LIGHTS further point lights and spots; Lambert or principled BSDF per shape, optional
+ * FFX_RENDER_MAX_LIGHTS further point lights and spots and, with FFX_RENDER_AMBIENT, a constant
+ * emitter (ambient light); Lambert or principled BSDF per shape, optional
  * shadow rays, box reconstruction filter, counter-based per-sample jitter.
  * The render is linear in the texture, so the adjoint needs no forward state: it replays
  * the same samples (same seed) and scatters d(loss)/d(img) through the bilinear weights.
@@ -878,6 +879,23 @@ int ffx_det_finish(const void *acc /*[dev] int64 [n]*/, int scale_log2, size_t n
 #define FFX_LIGHT_FLOATS 24
 #define FFX_LIGHT_POINT 0
 #define FFX_LIGHT_SPOT 1
+/* The constant emitter — ambient light, Mitsuba's <emitter type="constant">: FFX_RENDER_AMBIENT in the img_fp16 word of ffx_render_fwd /
+ * ffx_render_fwd_filtered.  An additive extension of ABI 11 (FFX_ABI_VERSION is unchanged; no struct changes, no new entry point).
+ *   input  — shape_albedo: [material table | n light records | one ambient record] in one buffer: behind the table's n_shapes x max(mat_stride, 3) floats and
+ *            the n records of FFX_RENDER_LIGHTS(n) (n may be 0) stand FFX_AMBIENT_FLOATS floats: radiance r, g, b and a reserved 0.  shape_albedo must be
+ *            non-NULL (FFX_ERR_ARG otherwise).
+ *   output — img: the image of the call without the bit plus the emitter's part, which is linear in the radiance.  A camera ray that hits nothing gains the
+ *            radiance; so does, weighted by the throughput, every bounce ray of the path walk that hits nothing; and the walk's last vertex makes the
+ *            bounce it would make next — same direction, weight and roulette — as one any-hit ray, so that the part of a vertex does not depend on
+ *            max_depth (at max_depth 2: one such ray at the primary hit).  Bounces are cosine-weighted; there is no emitter sampling and no MIS.  Radiance 0
+ *            adds +0.0: the image of the call without the bit, bit for bit.  With FFX_RENDER_AOV the block is that of the call without the bit.
+ * Served by the extra emitters' pass (one walk per sample for the lights and the constant emitter together): the same stream, no atomics, no host
+ * synchronisation.  Accepted with FFX_RENDER_PATH, FFX_RENDER_LIGHTS(n) and FFX_RENDER_AOV.  FFX_ERR_UNSUPPORTED together with FFX_RENDER_FP16,
+ * FFX_RENDER_TANGENT or a FFX_RENDER_GRAD_* bit and on every other render entry point — except that ffx_render_bwd / ffx_render_bwd_filtered without a
+ * FFX_RENDER_GRAD_* bit accept and ignore the bit (the constant emitter does not depend on the projector's texture).  The oracle does not know the bit:
+ * never pass it to it. */
+#define FFX_RENDER_AMBIENT 0x2000000
+#define FFX_AMBIENT_FLOATS 4
 /* Writes the apex records (the triangles as seen from a fixed ray origin) of sd's camera and enabled emitters into
  * the blob's apex areas — what every packet render does in front of its kernel unless told FFX_RENDER_APEX_READY.  Only
  * sd->cam.to_world, sd->proj.{enabled,to_world} and sd->spot.{enabled,to_world} are read.  No reference counterpart (Mitsuba
