@@ -220,6 +220,10 @@ RENDER_AOV_FLOATS = 17
 # follow the material table in the shape_albedo buffer (to_world 0..15, intensity 16..18, cutoff_deg 19, beam_width_deg 20, type 21, reserved 22..23)
 RENDER_MAX_LIGHTS, RENDER_LIGHTS_SHIFT, RENDER_LIGHTS_MASK = 8, 21, 0x1E00000
 LIGHT_FLOATS, LIGHT_POINT, LIGHT_SPOT = 24, 0, 1
+# the directional emitter (include/ffx.h FFX_LIGHT_DIRECTIONAL): a third record type (to_world's 3 x 3 gives the direction of travel, its +Z;
+# floats 16..18 the irradiance; 19, 20, 22, 23 zero) and bit 26 of the same word — "the table may hold such records": it selects the kernels that know them
+LIGHT_DIRECTIONAL = 2
+RENDER_LIGHTS_DIRECTIONAL = 0x4000000
 
 
 def render_lights(n):

@@ -3984,9 +3984,28 @@ __global__ void __launch_bounds__(64)
 #define FFX_LK_ITRANS 18
 #define FFX_LK_TYPE 19
 #define FFX_LK_FLOATS 20
+// DIR (the directional emitter): a record of type FFX_LIGHT_DIRECTIONAL parks wi = -normalize(to_world's 3 x 3 . (0, 0, 1)) in the position's
+// three floats — (0, 0, 0) where that is no finite unit vector, which no vertex's cosine test passes — and its irradiance in the intensity's
+template <bool DIR = false>
 __device__ __forceinline__ void lights_derive(const float *__restrict__ table, int n, int lane, float *__restrict__ s_l) {
   for (int k = 0; k < n; ++k) { // (wave-uniform: every lane forms the same values, lane 0 parks them)
     const float *m = table + (size_t)FFX_LIGHT_FLOATS * k;
+    if constexpr (DIR) {
+      if (m[21] == (float)FFX_LIGHT_DIRECTIONAL) { // (wave-uniform)
+        const float zx = m[2], zy = m[6], zz = m[10];
+        const float il = 1.0f / sqrtf(zx * zx + zy * zy + zz * zz);
+        v3 wi = V3(-zx * il, -zy * il, -zz * il);
+        const float l2 = vdot(wi, wi);
+        if (!(l2 > 0.99f && l2 < 1.01f)) wi = V3(0.f, 0.f, 0.f); // (a zero, infinite or NaN axis: lights nothing)
+        if (lane == 0) {
+          float *o = s_l + FFX_LK_FLOATS * k;
+          o[FFX_LK_POS] = wi.x; o[FFX_LK_POS + 1] = wi.y; o[FFX_LK_POS + 2] = wi.z;
+          o[FFX_LK_INT] = m[16]; o[FFX_LK_INT + 1] = m[17]; o[FFX_LK_INT + 2] = m[18];
+          o[FFX_LK_TYPE] = m[21];
+        }
+        continue;
+      }
+    }
     const float a00 = m[0], a01 = m[1], a02 = m[2], a10 = m[4], a11 = m[5], a12 = m[6], a20 = m[8], a21 = m[9], a22 = m[10];
     const float c00 = a11 * a22 - a12 * a21, c01 = a12 * a20 - a10 * a22, c02 = a10 * a21 - a11 * a20;
     const float idet = 1.0f / (a00 * c00 + a01 * c01 + a02 * c02); // (a singular frame: no finite cosine below, the spot lights nothing)
@@ -4004,12 +4023,35 @@ __device__ __forceinline__ void lights_derive(const float *__restrict__ table, i
   }
   __syncthreads();
 }
-// the n lights at one vertex (st, pv: shade_sample<true, ..., !EMIT>'s; d: the ray that found it), weighted by the throughput beta, into L
+// the n lights at one vertex (st, pv: shade_sample<true, ..., !EMIT>'s; d: the ray that found it), weighted by the throughput beta, into L.
+// DIR: a directional record (lights_derive<true>'s) has no position, no falloff and no 1 / d^2; its shadow ray leaves the lifted point along wi, the closing
+// ray's form (path_walk's AMB), on the lane's own stack
+template <bool DIR = false>
 __device__ __forceinline__ void lights_at_vertex(const ShadeK &c, const PathArgs &a, const float *__restrict__ s_l, int n, const SampleTerms &st, const PathVtxP &pv, v3 d,
                                                  const float (&beta)[3], int *stack, int stride, float (&L)[3]) {
   const float *mt = mat_table(c);
   for (int k = 0; k < n; ++k) {
     const float *lk = s_l + FFX_LK_FLOATS * k;
+    if constexpr (DIR) {
+      if (lk[FFX_LK_TYPE] == (float)FFX_LIGHT_DIRECTIONAL) { // (wave-uniform branch: s_l is read at uniform addresses)
+        const v3 wi = V3(lk[FFX_LK_POS], lk[FFX_LK_POS + 1], lk[FFX_LK_POS + 2]);
+        const float cos_s = vdot(pv.ns, wi);
+        if (!(cos_s > 0.f && vdot(pv.ng, wi) > 0.f)) continue;
+        if (c.shadows) {
+          Hit hs;
+          if (traverse<true, false>(a.nodes, a.recs, pv.Po, wi, 0.f, 3.0e38f, hs, stack, stride)) continue;
+        }
+        float bA = cos_s, bB = 0.f, bT = 0.f;
+        row_terms<false>(c, mt, st.shape, pv.textured, st.base, pv.ns, V3(-d.x, -d.y, -d.z), wi, bA, bB, bT);
+        const float f = bA * 0.3183098861837907f, fb = bB * 0.3183098861837907f;
+#pragma unroll
+        for (int ch = 0; ch < 3; ++ch) {
+          const float r = lk[FFX_LK_INT + ch] * f, b = lk[FFX_LK_INT + ch] * fb;
+          L[ch] += beta[ch] * (c.mat_stride == 3 ? st.base[ch] * r : st.base[ch] * r + b);
+        }
+        continue;
+      }
+    }
     const v3 lpos = V3(lk[FFX_LK_POS], lk[FFX_LK_POS + 1], lk[FFX_LK_POS + 2]);
     v3 wi = vsub(lpos, pv.P);
     const float d2 = vdot(wi, wi);
@@ -4121,6 +4163,63 @@ __global__ void __launch_bounds__(64)
           a, idx, o, d, nt, ft, s_dyn + lane, 64,
           [&](int, const SampleTerms &st, const PathVtxP &pv, v3 dv, const float (&beta)[3]) {
             lights_at_vertex(kernarg_shade(), a, s_l, n, st, pv, dv, beta, s_dyn + lane, 64, L);
+          },
+          NoBounce(), [&](const float (&beta)[3]) { L[0] += beta[0] * la0; L[1] += beta[1] * la1; L[2] += beta[2] * la2; });
+    }
+    if (RF) {
+      float gx[5], gy[5];
+      rf_weights(c.rf, jx, gx);
+      rf_weights(c.rf, jy, gy);
+      rf_fold(s_rf, lane, gx, gy, L[0], L[1], L[2], s < a.spp ? 1.f : 0.f, acc);
+    } else {
+      acc[0] += L[0]; acc[1] += L[1]; acc[2] += L[2];
+    }
+  }
+  if (RF) {
+    rf_store(part, pix, lane, acc);
+    return;
+  }
+  const float inv_spp = 1.0f / (float)a.spp;
+  const float m0 = wave_sum_tree(acc[0]) * inv_spp, m1 = wave_sum_tree(acc[1]) * inv_spp, m2 = wave_sum_tree(acc[2]) * inv_spp;
+  if (lane == 0) {
+    float *p = img + (size_t)pix * 3;
+    p[0] += m0; p[1] += m1; p[2] += m2;
+  }
+}
+// FFX_RENDER_LIGHTS_DIRECTIONAL (include/ffx.h): the lights' pass for a table that may hold directional records — all three record types in one
+// walk per sample and, with AMB, the constant emitter in the same walk (k_lights_ambient_fwd's record behind the table).  Kernels of their own so that
+// k_lights_fwd and k_lights_ambient_fwd keep their machine code (tools/isa_same.py)
+template <bool RF, bool AMB>
+__global__ void __launch_bounds__(64)
+    k_lights_dir_fwd(ShadeK c, PathArgs a, const float *__restrict__ lights, int n_lights, float *__restrict__ img, float *__restrict__ part) {
+  extern __shared__ int s_dyn[];
+  __shared__ __attribute__((aligned(16))) float s_rf[RF ? FFX_RF_FLOATS : 4];
+  __shared__ float s_l[FFX_RENDER_MAX_LIGHTS * FFX_LK_FLOATS];
+  const int lane = threadIdx.x;
+  const uint32_t pix = blockIdx.x;
+  const int W = c.cam.W, px = (int)(pix % (uint32_t)W), py = (int)(pix / (uint32_t)W);
+  const int n = n_lights < FFX_RENDER_MAX_LIGHTS ? n_lights : FFX_RENDER_MAX_LIGHTS; // (the host refuses more: s_l holds this many)
+  lights_derive<true>(lights, n, lane, s_l);
+  float la0 = 0.f, la1 = 0.f, la2 = 0.f;
+  if constexpr (AMB) {
+    const float *la = lights + (size_t)FFX_LIGHT_FLOATS * n; // (the ambient record, at a wave-uniform address: scalar loads)
+    la0 = la[0]; la1 = la[1]; la2 = la[2];
+  }
+  float acc[4] = {0.f, 0.f, 0.f, 0.f};
+  for (int pass = 0; pass < (a.spp + 63) >> 6; ++pass) {
+    const int s = pass * 64 + lane;
+    const uint32_t idx = pix * (uint32_t)a.spp + (uint32_t)s;
+    float jx, jy;
+    sample_jitter(a.seed_key, idx, jx, jy);
+    float L[3] = {0.f, 0.f, 0.f};
+    if (s < a.spp) {
+      v3 o, d;
+      float nt, ft;
+      cam_ray(c.cam, ((float)px + jx) * c.cam.inv_w, ((float)py + jy) * c.cam.inv_h, o, d, nt, ft);
+      path_walk<false, false, false, AMB>(
+          a, idx, o, d, nt, ft, s_dyn + lane, 64,
+          [&](int, const SampleTerms &st, const PathVtxP &pv, v3 dv, const float (&beta)[3]) {
+            lights_at_vertex<true>(kernarg_shade(), a, s_l, n, st, pv, dv, beta, s_dyn + lane, 64, L);
           },
           NoBounce(), [&](const float (&beta)[3]) { L[0] += beta[0] * la0; L[1] += beta[1] * la1; L[2] += beta[2] * la2; });
     }
@@ -5915,6 +6014,8 @@ static int render_aov(const void *bvh, const ffx_bvh_info *info, const ffx_scene
   do { \
     if ((flags_) & FFX_RENDER_LIGHTS_MASK) FFX_FAIL(FFX_ERR_UNSUPPORTED, "%s: FFX_RENDER_LIGHTS is served by ffx_render_fwd[_filtered] only", what_); \
     if ((flags_) & FFX_RENDER_AMBIENT) FFX_FAIL(FFX_ERR_UNSUPPORTED, "%s: FFX_RENDER_AMBIENT is served by ffx_render_fwd[_filtered] only", what_); \
+    if ((flags_) & FFX_RENDER_LIGHTS_DIRECTIONAL) \
+      FFX_FAIL(FFX_ERR_UNSUPPORTED, "%s: FFX_RENDER_LIGHTS_DIRECTIONAL is served by ffx_render_fwd[_filtered] only", what_); \
   } while (0)
 // FFX_RENDER_LIGHTS (include/ffx.h).  What a forward refuses about the bits before it launches anything: FFX_OK, or the error
 static int lights_check(int flags, const float *shape_albedo, const char *what) {
@@ -5925,6 +6026,14 @@ static int lights_check(int flags, const float *shape_albedo, const char *what) 
     if (flags & (FFX_RENDER_GRAD_APPEARANCE | FFX_RENDER_GRAD_MATERIAL | FFX_RENDER_GRAD_PRB))
       FFX_FAIL(FFX_ERR_UNSUPPORTED, "%s: FFX_RENDER_AMBIENT is not served together with a FFX_RENDER_GRAD_* bit (the constant emitter is not differentiated)", what);
     if (!shape_albedo) FFX_FAIL(FFX_ERR_ARG, "%s: FFX_RENDER_AMBIENT needs the device buffer [material table | lights | ambient] (shape_albedo is NULL)", what);
+  }
+  if (flags & FFX_RENDER_LIGHTS_DIRECTIONAL) { // directional records in the table: the bit belongs to a table, and is refused where the table is
+    if (n == 0) FFX_FAIL(FFX_ERR_ARG, "%s: FFX_RENDER_LIGHTS_DIRECTIONAL needs FFX_RENDER_LIGHTS(n >= 1): the bit says what the table may hold", what);
+    if (flags & FFX_RENDER_FP16) FFX_FAIL(FFX_ERR_UNSUPPORTED, "%s: FFX_RENDER_LIGHTS_DIRECTIONAL has no fp16 film", what);
+    if (flags & FFX_RENDER_TANGENT) FFX_FAIL(FFX_ERR_UNSUPPORTED, "%s: FFX_RENDER_LIGHTS_DIRECTIONAL is not served together with FFX_RENDER_TANGENT", what);
+    if (flags & (FFX_RENDER_GRAD_APPEARANCE | FFX_RENDER_GRAD_MATERIAL | FFX_RENDER_GRAD_PRB))
+      FFX_FAIL(FFX_ERR_UNSUPPORTED, "%s: FFX_RENDER_LIGHTS_DIRECTIONAL is not served together with a FFX_RENDER_GRAD_* bit (the extra emitters are not differentiated)",
+               what);
   }
   if (n == 0) return FFX_OK;
   if (n > FFX_RENDER_MAX_LIGHTS) FFX_FAIL(FFX_ERR_ARG, "%s: FFX_RENDER_LIGHTS(%d): at most %d extra emitters", what, n, FFX_RENDER_MAX_LIGHTS);
@@ -5937,7 +6046,8 @@ static int lights_check(int flags, const float *shape_albedo, const char *what) 
 }
 // ... and the pass, behind the launches of the main image on the same stream (the call without the bits has succeeded: its arguments are good):
 // k_lights_fwd adds to img; the gaussian film: into the scratch, which the image's (and an AOV block's) gathers have read by then, and k_lights_gather adds.
-// With FFX_RENDER_AMBIENT the same launches are k_lights_ambient_fwd's: one walk per sample serves the n lights (n may be 0) and the constant emitter
+// With FFX_RENDER_AMBIENT the same launches are k_lights_ambient_fwd's: one walk per sample serves the n lights (n may be 0) and the constant emitter.
+// With FFX_RENDER_LIGHTS_DIRECTIONAL they are k_lights_dir_fwd's, with or without the constant emitter: still one walk per sample
 static int render_lights(const void *bvh, const ffx_bvh_info *info, const ffx_scene_desc *sd, const float *shape_albedo, int spp, uint32_t seed, int flags, void *img,
                          ffx_stream s, void *rf_scratch) {
   const int n = (flags & FFX_RENDER_LIGHTS_MASK) >> FFX_RENDER_LIGHTS_SHIFT;
@@ -5948,15 +6058,15 @@ static int render_lights(const void *bvh, const ffx_bvh_info *info, const ffx_sc
   const float *table = shape_albedo + (size_t)sd->n_shapes * (size_t)r.c.mat_stride; // (mat_stride: 3 or FFX_MAT_STRIDE — max(mat_stride, 3))
   const PathArgs pa = path_args(r);
   const hipStream_t st = (hipStream_t)s;
-  const bool amb = (flags & FFX_RENDER_AMBIENT) != 0;
+  const bool amb = (flags & FFX_RENDER_AMBIENT) != 0, dir = (flags & FFX_RENDER_LIGHTS_DIRECTIONAL) != 0;
   if (rf_scratch) {
-    hipLaunchKernelGGL(amb ? k_lights_ambient_fwd<true> : k_lights_fwd<true>, dim3((unsigned)r.n_pix), dim3(64), path_stack_bytes(info), st, r.c, pa, table, n, (float *)nullptr, (float *)rf_scratch);
+    hipLaunchKernelGGL(dir ? (amb ? k_lights_dir_fwd<true, true> : k_lights_dir_fwd<true, false>) : amb ? k_lights_ambient_fwd<true> : k_lights_fwd<true>, dim3((unsigned)r.n_pix), dim3(64), path_stack_bytes(info), st, r.c, pa, table, n, (float *)nullptr, (float *)rf_scratch);
     FFX_CHECK_LAUNCH("render_fwd_filtered (lights)");
     hipLaunchKernelGGL(k_lights_gather, dim3(ffx_cdiv(r.c.cam.W, 64), r.c.cam.H), dim3(64), 0, st, (const float4 *)rf_scratch, r.c.cam.W, r.c.cam.H, (float *)img);
     FFX_CHECK_LAUNCH("render_fwd_filtered (lights)/gather");
     return FFX_OK;
   }
-  hipLaunchKernelGGL(amb ? k_lights_ambient_fwd<false> : k_lights_fwd<false>, dim3((unsigned)r.n_pix), dim3(64), path_stack_bytes(info), st, r.c, pa, table, n, (float *)img, (float *)nullptr);
+  hipLaunchKernelGGL(dir ? (amb ? k_lights_dir_fwd<false, true> : k_lights_dir_fwd<false, false>) : amb ? k_lights_ambient_fwd<false> : k_lights_fwd<false>, dim3((unsigned)r.n_pix), dim3(64), path_stack_bytes(info), st, r.c, pa, table, n, (float *)img, (float *)nullptr);
   FFX_CHECK_LAUNCH("render_fwd (lights)");
   return FFX_OK;
 }
@@ -5966,8 +6076,8 @@ static int render_fwd_entry(const void *bvh, const ffx_bvh_info *info, const ffx
   const char *what = scratch ? "render_fwd_filtered" : "render_fwd";
   if (const int rc = lights_check(img_fp16, shape_albedo, what)) return rc;
   FFX_NO_APPEARANCE(img_fp16, what);
-  const int lights = img_fp16 & (FFX_RENDER_LIGHTS_MASK | FFX_RENDER_AMBIENT);
-  img_fp16 &= ~(FFX_RENDER_LIGHTS_MASK | FFX_RENDER_AMBIENT);
+  const int lights = img_fp16 & (FFX_RENDER_LIGHTS_MASK | FFX_RENDER_AMBIENT | FFX_RENDER_LIGHTS_DIRECTIONAL);
+  img_fp16 &= ~(FFX_RENDER_LIGHTS_MASK | FFX_RENDER_AMBIENT | FFX_RENDER_LIGHTS_DIRECTIONAL);
   int rc;
   if (img_fp16 & FFX_RENDER_AOV) rc = render_aov(bvh, info, sd, shape_albedo, tex, spp, seed, img_fp16, img, s, scratch);
   else if (img_fp16 & FFX_RENDER_TANGENT) rc = render_jvp(bvh, info, sd, shape_albedo, tex, spp, seed, img_fp16, img, s, scratch);
@@ -6330,7 +6440,9 @@ int ffx_render_bwd(const void *bvh, const ffx_bvh_info *info, const ffx_scene_de
     FFX_FAIL(FFX_ERR_UNSUPPORTED, "render_bwd: FFX_RENDER_LIGHTS is not served together with a FFX_RENDER_GRAD_* bit (the extra emitters are not differentiated)");
   if ((flags & FFX_RENDER_AMBIENT) && (flags & (FFX_RENDER_GRAD_APPEARANCE | FFX_RENDER_GRAD_MATERIAL | FFX_RENDER_GRAD_PRB)))
     FFX_FAIL(FFX_ERR_UNSUPPORTED, "render_bwd: FFX_RENDER_AMBIENT is not served together with a FFX_RENDER_GRAD_* bit (the constant emitter is not differentiated)");
-  flags &= ~(FFX_RENDER_LIGHTS_MASK | FFX_RENDER_AMBIENT); // (the texture's adjoint sees neither the extra emitters nor the constant one: the bits are ignored, the tail behind the table is not read)
+  if ((flags & FFX_RENDER_LIGHTS_DIRECTIONAL) && (flags & (FFX_RENDER_GRAD_APPEARANCE | FFX_RENDER_GRAD_MATERIAL | FFX_RENDER_GRAD_PRB)))
+    FFX_FAIL(FFX_ERR_UNSUPPORTED, "render_bwd: FFX_RENDER_LIGHTS_DIRECTIONAL is not served together with a FFX_RENDER_GRAD_* bit (the extra emitters are not differentiated)");
+  flags &= ~(FFX_RENDER_LIGHTS_MASK | FFX_RENDER_AMBIENT | FFX_RENDER_LIGHTS_DIRECTIONAL); // (the texture's adjoint sees neither the extra emitters nor the constant one: the bits are ignored, the tail behind the table is not read)
   if (flags & FFX_RENDER_GRAD_APPEARANCE) return render_bwd_leaves(bvh, info, sd, shape_albedo, spp, seed, flags, gimg, gtex, s, nullptr);
   return render_bwd_impl(bvh, info, sd, shape_albedo, spp, seed, flags, gimg, gtex, s, nullptr);
 }
@@ -6419,7 +6531,9 @@ int ffx_render_bwd_filtered(const void *bvh, const ffx_bvh_info *info, const ffx
     FFX_FAIL(FFX_ERR_UNSUPPORTED, "render_bwd_filtered: FFX_RENDER_LIGHTS is not served together with a FFX_RENDER_GRAD_* bit (the extra emitters are not differentiated)");
   if ((flags & FFX_RENDER_AMBIENT) && (flags & (FFX_RENDER_GRAD_APPEARANCE | FFX_RENDER_GRAD_MATERIAL | FFX_RENDER_GRAD_PRB)))
     FFX_FAIL(FFX_ERR_UNSUPPORTED, "render_bwd_filtered: FFX_RENDER_AMBIENT is not served together with a FFX_RENDER_GRAD_* bit (the constant emitter is not differentiated)");
-  flags &= ~(FFX_RENDER_LIGHTS_MASK | FFX_RENDER_AMBIENT); // (the texture's adjoint sees neither the extra emitters nor the constant one: the bits are ignored, the tail behind the table is not read)
+  if ((flags & FFX_RENDER_LIGHTS_DIRECTIONAL) && (flags & (FFX_RENDER_GRAD_APPEARANCE | FFX_RENDER_GRAD_MATERIAL | FFX_RENDER_GRAD_PRB)))
+    FFX_FAIL(FFX_ERR_UNSUPPORTED, "render_bwd_filtered: FFX_RENDER_LIGHTS_DIRECTIONAL is not served together with a FFX_RENDER_GRAD_* bit (the extra emitters are not differentiated)");
+  flags &= ~(FFX_RENDER_LIGHTS_MASK | FFX_RENDER_AMBIENT | FFX_RENDER_LIGHTS_DIRECTIONAL); // (the texture's adjoint sees neither the extra emitters nor the constant one: the bits are ignored, the tail behind the table is not read)
   if (flags & FFX_RENDER_GRAD_APPEARANCE) return render_bwd_leaves(bvh, info, sd, shape_albedo, spp, seed, flags, gimg, gtex, s, scratch);
   return render_bwd_impl(bvh, info, sd, shape_albedo, spp, seed, flags, gimg, gtex, s, scratch);
 }

@@ -169,7 +169,7 @@ class CacheOverflowError(RuntimeError):
 
 class _Render(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, tex, geom, sd, albedo, spp, seed, fp16, max_depth=2, rr_depth=5, lights=None, ambient=None):
+    def forward(ctx, tex, geom, sd, albedo, spp, seed, fp16, max_depth=2, rr_depth=5, lights=None, ambient=None, lights_directional=False):
         ctx.geom, ctx.sd, ctx.spp, ctx.seed = geom, sd, spp, seed
         ctx.depths = (max_depth, rr_depth)
         ctx.tex_shape = tex.shape
@@ -186,7 +186,8 @@ class _Render(torch.autograd.Function):
                 # store a texture footprint per pixel now instead of re-tracing the scene in backward
                 ctx.cache = torch.empty(ops.render_cache_bytes_sd(sd, spp), dtype=torch.uint8, device=t.device)
         ctx.pose_version = geom.version
-        return geom.render_fwd(sd, albedo, t, spp, seed, fp16, cache=ctx.cache, max_depth=max_depth, rr_depth=rr_depth, lights=lights, ambient=ambient)
+        return geom.render_fwd(sd, albedo, t, spp, seed, fp16, cache=ctx.cache, max_depth=max_depth, rr_depth=rr_depth, lights=lights, ambient=ambient,
+                               lights_directional=lights_directional)
 
     @staticmethod
     def backward(ctx, g):
@@ -211,10 +212,10 @@ class _Render(torch.autograd.Function):
                     "before the next randomisation"
                 )
             gtex = ctx.geom.render_bwd(ctx.sd, ctx.albedo, ctx.spp, ctx.seed, g, max_depth=ctx.depths[0], rr_depth=ctx.depths[1])
-        return gtex.reshape(ctx.tex_shape), None, None, None, None, None, None, None, None, None, None
+        return gtex.reshape(ctx.tex_shape), None, None, None, None, None, None, None, None, None, None, None
 
 
-def render(tex, geom, sd, albedo, spp, seed=0, fp16=False, max_depth=2, rr_depth=5, integrator=None, lights=None, ambient=None):
+def render(tex, geom, sd, albedo, spp, seed=0, fp16=False, max_depth=2, rr_depth=5, integrator=None, lights=None, ambient=None, lights_directional=False):
     """K8/K9: image [H,W,3], differentiable w.r.t. the projector texture ([h,w] or [h,w,c]).
     When the texture requires grad the forward kernel also stores each pixel's footprint in the texture
     (128 B per pixel + a small arena: 40 MB at 512x512x64; under a gaussian film an arena of per-sample records — 16 / 20 bytes per sample
@@ -226,7 +227,8 @@ def render(tex, geom, sd, albedo, spp, seed=0, fp16=False, max_depth=2, rr_depth
     lights: a [n, 24] device tensor of extra emitters (ops.pack_lights) for the forward — fp32 film, no adjoint cache; the texture's gradient
     does not depend on them, so the backward is that of the render without them (the re-tracing adjoint).
     ambient: the constant emitter's radiance (three floats or a [3] tensor) — as lights: fp32 film, no adjoint cache, a constant of the
-    texture's gradient."""
+    texture's gradient.
+    lights_directional: the table may hold directional emitters (ops.lights_directional) — handed to the forward."""
     if ambient is not None and fp16:
         raise ValueError("render: the constant emitter (ambient=) has no fp16 film")
     if lights is not None and lights.numel() == 0:
@@ -241,4 +243,4 @@ def render(tex, geom, sd, albedo, spp, seed=0, fp16=False, max_depth=2, rr_depth
         ops.path_flags(max_depth, rr_depth)  # (the range check before any launch)
         if ops.deterministic_mode() and tex.requires_grad:
             raise ValueError("render: max_depth > 2 has no deterministic adjoint (FFX_DETERMINISTIC=1)")
-    return _Render.apply(tex, geom, sd, albedo, int(spp), int(seed), bool(fp16), int(max_depth), int(rr_depth), lights, ambient)
+    return _Render.apply(tex, geom, sd, albedo, int(spp), int(seed), bool(fp16), int(max_depth), int(rr_depth), lights, ambient, bool(lights_directional))

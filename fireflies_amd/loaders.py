@@ -12,6 +12,8 @@ module reads what those scene files contain so that `mi.load_file(path)` keeps w
                                  every further one goes to SceneData.lights in file order
   <emitter type="point">         position (a <point>) or the translation of to_world, intensity (default 1): to SceneData.lights in file order.
                                  Beyond scenes.MAX_EXTRA_LIGHTS entries the rest are reported once and dropped
+  <emitter type="directional">   irradiance (an <rgb>, <spectrum> or a single float, default 1) and to_world or a <vector name="direction">: a sun,
+                                 to SceneData.lights in file order
   <emitter type="constant">      radiance (an <rgb> or a single float, default 1): SceneData.ambient — ambient light and the colour of rays that leave
                                  the scene.  Mitsuba allows one environment: a second one is reported once and ignored
   <emitter type="projector">     irradiance texture (id "tex"), scale, fov, to_world
@@ -380,6 +382,7 @@ def _albedo_of(bsdf, bsdfs):
 
 _POINT_PROPS = {"intensity", "position"}
 _CONSTANT_PROPS = {"radiance"}
+_DIRECTIONAL_PROPS = {"irradiance", "direction"}
 _SENSOR_PROPS = {"fov", "fov_axis", "near_clip", "far_clip", "focus_distance", "principal_point_offset_x", "principal_point_offset_y"}
 _FILM_PROPS = {"width", "height", "pixel_format", "component_format", "file_format", "sample_border", "compensate", "crop_offset_x", "crop_offset_y", "crop_width", "crop_height"}
 _SHAPE_PROPS = {"filename", "face_normals", "flip_tex_coords", "flip_normals"}
@@ -407,6 +410,20 @@ def _fov_x(fov, axis, width, height):
     else:
         raise ValueError(f"unknown fov_axis {axis!r}")
     return float(np.rad2deg(2.0 * np.arctan(tx)))
+
+
+def _frame_along(direction, what):
+    """a to_world whose +Z is the normalised direction (and whose X and Y complete a right-handed orthonormal frame)"""
+    z = np.asarray(direction, np.float64)
+    n = np.linalg.norm(z)
+    if not (np.isfinite(n) and n > 0.0):
+        raise ValueError(f"{what}: the direction {tuple(float(v) for v in z)} is not a direction (a zero or non-finite vector)")
+    z = z / n
+    x = np.cross((0.0, 0.0, 1.0) if abs(z[2]) < 0.9 else (1.0, 0.0, 0.0), z)
+    x = x / np.linalg.norm(x)
+    m = np.eye(4)
+    m[:3, 0], m[:3, 1], m[:3, 2] = x, np.cross(z, x), z
+    return m.astype(np.float32)
 
 
 class _Dropped:
@@ -573,6 +590,18 @@ def load_mitsuba_xml(path):
                     tw = np.eye(4)
                     tw[:3, 3] = (xyz * 3)[:3] if len(xyz) == 1 else xyz[:3]
                 extra_light(scenes.LightData(node.get("id") or f"emit-Point-{len(lights) + 1}", "point", tw, tuple(inten)))
+            elif node.get("type") == "directional":  # Mitsuba: the emitter radiates along its local +Z, or along `direction`
+                dropped.props(node, _DIRECTIONAL_PROPS, "directional emitter")
+                irr = p.get("irradiance", (1.0, 1.0, 1.0))
+                irr = (float(irr),) * 3 if isinstance(irr, (int, float)) else tuple(float(v) for v in irr)
+                vec = _child(node, "vector", "direction")
+                if vec is not None:
+                    if _child(node, "transform", "to_world") is not None:
+                        raise ValueError(f"{path}: directional emitter {node.get('id') or 'without id'!r}: only one of the parameters 'direction' and 'to_world' "
+                                         "can be specified")
+                    xyz = _floats(vec.get("value")) if vec.get("value") is not None else [float(vec.get(a, 0.0)) for a in "xyz"]
+                    tw = _frame_along((xyz * 3)[:3] if len(xyz) == 1 else xyz[:3], f"{path}: directional emitter {node.get('id') or 'without id'!r}")
+                extra_light(scenes.LightData(node.get("id") or f"emit-Directional-{len(lights) + 1}", "directional", tw, irr))
             elif node.get("type") == "constant":
                 if ambient is not None:
                     dropped("constant.second", f"a second constant emitter ({node.get('id') or 'without id'!r}) ignored: a scene has one environment "

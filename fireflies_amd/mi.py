@@ -626,13 +626,17 @@ class Scene:
             p._init(s.name + ".intensity.value", Color3f(torch.tensor(s.intensity, dtype=torch.float32)))
             p._init(s.name + ".cutoff_angle", Float(s.cutoff_angle))
             p._init(s.name + ".beam_width", Float(s.beam_width))
-        # extra emitters: a point light's `position` and intensity, a further spot's pose, intensity and cone; read when the table of a
-        # render is formed (lights_table)
+        # extra emitters: a point light's `position` and intensity, a further spot's pose, intensity and cone, a directional emitter's
+        # pose and irradiance; read when the table of a render is formed (lights_table)
         if len(d.lights) > scenes.MAX_EXTRA_LIGHTS:
             raise ValueError(f"at most {scenes.MAX_EXTRA_LIGHTS} emitters beyond the projector and the spot, got {len(d.lights)}")
         for l in d.lights:
             if l.kind == "point":
                 p._init(l.name + ".position", Color3f(torch.as_tensor(np.asarray(l.to_world, np.float32).reshape(4, 4)[:3, 3].copy())))
+            elif l.kind == "directional":
+                p._init(l.name + ".to_world", Transform4f(l.to_world))
+                p._init(l.name + ".irradiance.value", Color3f(torch.tensor(l.intensity, dtype=torch.float32)))
+                continue
             else:
                 p._init(l.name + ".to_world", Transform4f(l.to_world))
                 p._init(l.name + ".cutoff_angle", Float(l.cutoff_angle))
@@ -667,6 +671,9 @@ class Scene:
             return tuple(float(x) for x in (v.t if isinstance(v, _ArrayBase) else torch.as_tensor(v, dtype=torch.float32)).detach().reshape(-1)[:3].cpu())
 
         for l in self.data.lights:
+            if l.kind == "directional":
+                out.append(scenes.LightData(l.name, "directional", self._mat(l.name + ".to_world"), vec3(p[l.name + ".irradiance.value"])))
+                continue
             inten = vec3(p[l.name + ".intensity.value"])
             if l.kind == "point":
                 tw = np.eye(4, dtype=np.float32)
@@ -684,6 +691,10 @@ class Scene:
         if self._lights_dev is None:
             self._lights_dev = ops.pack_lights(self.current_lights()).to(self.device)
         return self._lights_dev
+
+    def lights_directional(self):
+        """whether the extra emitters hold a directional one: the render calls' `lights_directional`"""
+        return ops.lights_directional(self.data.lights)
 
     def ambient_record(self):
         """the constant emitter's radiance as a [3] device tensor for the render calls' `ambient`, None for a scene without; rebuilt
@@ -861,7 +872,7 @@ class Scene:
             dyn = kd.get(k)
             if dyn is None:
                 dyn = kd[k] = (k.endswith(".__pose__") or k.endswith(".to_world") or k.endswith(".intensity.value") or k.endswith(".vertex_positions") or k == "tex.data"
-                               or (k.endswith(".position") and k.partition(".")[0] in self._light_names)
+                               or ((k.endswith(".position") or k.endswith(".irradiance.value")) and k.partition(".")[0] in self._light_names)
                                or (k.endswith(".radiance.value") and k.partition(".")[0] == self._ambient_name)
                                or k.endswith(".cutoff_angle") or k.endswith(".beam_width") or (".brdf_0." in k and not k.endswith(".data")))
             if not dyn:
@@ -1359,6 +1370,7 @@ def render(scene: Scene, params: SceneParameters = None, spp: int = 16, seed: in
     lights = scene.lights_table() if _has_lights(scene) else None
     if lights is not None and fp16:
         raise ValueError("mi.render: a scene with extra emitters (point lights, further spots) has no fp16 film")
+    sun = lights is not None and scene.lights_directional()  # (a directional emitter among them, DESIGN.md 4.9: the table's bit)
     ambient = scene.ambient_record() if _has_ambient(scene) else None
     if ambient is not None and fp16:
         raise ValueError("mi.render: a scene with a constant emitter (ambient light) has no fp16 film")
@@ -1377,7 +1389,8 @@ def render(scene: Scene, params: SceneParameters = None, spp: int = 16, seed: in
     try:
         if tex.requires_grad and torch.is_grad_enabled():
             scene.render_paths["autograd"] += 1
-            img = Fn.render(tex, scene.geom, sd, scene.materials_arg(sd), spp, seed, fp16, md, rr, lights=lights, ambient=ambient)
+            img = Fn.render(tex, scene.geom, sd, scene.materials_arg(sd), spp, seed, fp16, md, rr, lights=lights, ambient=ambient,
+                            lights_directional=sun)
         else:  # nothing to differentiate: straight to the kernel (autograd.Function.apply costs ~80 us of host time per call)
             mats = scene.materials_arg(sd)
             # (extra emitters: a device table travels with the call — the caller's stream, like the device material tables)
@@ -1390,7 +1403,8 @@ def render(scene: Scene, params: SceneParameters = None, spp: int = 16, seed: in
                     done.record(rs)
                 return _RenderedXf(img, done)
             scene.render_paths["caller_stream"] += 1
-            img = scene.geom.render_fwd(sd, mats, Fn._tex3(tex), int(spp), int(seed), bool(fp16), max_depth=md, rr_depth=rr, lights=lights, ambient=ambient)
+            img = scene.geom.render_fwd(sd, mats, Fn._tex3(tex), int(spp), int(seed), bool(fp16), max_depth=md, rr_depth=rr, lights=lights, ambient=ambient,
+                                        lights_directional=sun)
         return TensorXf(img)
     finally:  # (the launcher counts its choice when it launches: two reads of a word of the library, no call into it)
         scene.render_paths["k8_plain"] += k8[0] - k8_plain0
@@ -1422,7 +1436,8 @@ def _render_aov(scene, params, spp, seed, fp16, integrator):
     md, rr = (inner.max_depth, inner.rr_depth) if inner is not None and not grad else (2, 5)
     img, block = scene.geom.render_aov(sd, scene.materials_arg(sd), Fn._tex3(tex.detach()), int(spp), int(seed), max_depth=md, rr_depth=rr,
                                        lights=scene.lights_table() if _has_lights(scene) else None,
-                                       ambient=scene.ambient_record() if _has_ambient(scene) else None)
+                                       ambient=scene.ambient_record() if _has_ambient(scene) else None,
+                                       lights_directional=_has_lights(scene) and scene.lights_directional())
     parts = []
     for _, type_ in integrator.aovs:
         first, n = ops.AOV_CHANNELS[type_]

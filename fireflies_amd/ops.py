@@ -567,19 +567,28 @@ def _no_path(max_depth, what):
 
 def pack_lights(lights):
     """the table of a render's extra emitters (include/ffx.h FFX_RENDER_LIGHTS): scenes.LightData entries -> [n, 24] float32 on the host
-    (to_world 0..15 row-major, intensity 16..18, cutoff_deg 19, beam_width_deg 20, type 21: 0 point / 1 spot, 22..23 zero)"""
+    (to_world 0..15 row-major, intensity 16..18, cutoff_deg 19, beam_width_deg 20, type 21: 0 point / 1 spot, 22..23 zero; a directional emitter,
+    DESIGN.md 4.9: to_world, its irradiance in 16..18, type 2, zeros elsewhere — such a table is rendered with lights_directional=True)"""
     lights = list(lights)
     if len(lights) > _abi.RENDER_MAX_LIGHTS:
         raise ValueError(f"at most {_abi.RENDER_MAX_LIGHTS} extra emitters, got {len(lights)}")
     out = torch.zeros((len(lights), _abi.LIGHT_FLOATS), dtype=torch.float32)
     for k, l in enumerate(lights):
-        if l.kind not in ("point", "spot"):
-            raise ValueError(f"light {l.name!r}: kind must be 'point' or 'spot', got {l.kind!r}")
+        if l.kind not in ("point", "spot", "directional"):
+            raise ValueError(f"light {l.name!r}: kind must be 'point', 'spot' or 'directional', got {l.kind!r}")
         out[k, :16] = torch.as_tensor(np.asarray(l.to_world, dtype=np.float32).reshape(16))
         out[k, 16:19] = torch.as_tensor([float(v) for v in l.intensity], dtype=torch.float32)
+        if l.kind == "directional":
+            out[k, 21] = float(_abi.LIGHT_DIRECTIONAL)
+            continue
         out[k, 19], out[k, 20] = float(l.cutoff_angle), float(l.beam_width)
         out[k, 21] = float(_abi.LIGHT_SPOT if l.kind == "spot" else _abi.LIGHT_POINT)
     return out
+
+
+def lights_directional(lights):
+    """whether a list of scenes.LightData holds a directional emitter: the lights_directional= of the render that takes pack_lights(lights)"""
+    return any(l.kind == "directional" for l in lights)
 
 
 def pack_ambient(ambient):
@@ -1019,11 +1028,12 @@ class DeviceGeometry:
     def _timed(self, name):
         return _EventPair(self.timing, name)
 
-    def _with_lights(self, sd, albedo, mats_arg, lights, what, ambient=None):
+    def _with_lights(self, sd, albedo, mats_arg, lights, what, ambient=None, lights_directional=False):
         """a call's extra emitters (include/ffx.h FFX_RENDER_LIGHTS): -> (the shape_albedo argument, the flags bits, the buffer to keep alive).  lights:
         None / empty — the call as it was; else a [n, 24] float32 device tensor (pack_lights), which travels behind the material table in one buffer
         [table | lights] (a scene description that carries its rows: their area is there but not read).  ambient (FFX_RENDER_AMBIENT):
-        three floats or a [3] tensor — its record stands behind the lights, [table | lights | ambient], with or without lights"""
+        three floats or a [3] tensor — its record stands behind the lights, [table | lights | ambient], with or without lights.  lights_directional
+        (FFX_RENDER_LIGHTS_DIRECTIONAL): the table may hold directional records; without a table the bit is not set"""
         amb = pack_ambient(ambient)
         if lights is not None and lights.numel() == 0:
             lights = None
@@ -1047,7 +1057,8 @@ class DeviceGeometry:
         buf = torch.cat(parts).contiguous()
         if ms == _abi.MAT_STRIDE and buf.data_ptr() % 16:
             raise ValueError(f"{what}: the [table | lights] buffer is not 16-byte aligned")
-        return _dev(buf, name="albedo"), _abi.render_lights(n) | (_abi.RENDER_AMBIENT if amb is not None else 0), buf
+        bits = _abi.render_lights(n) | (_abi.RENDER_AMBIENT if amb is not None else 0) | (_abi.RENDER_LIGHTS_DIRECTIONAL if lights_directional and n else 0)
+        return _dev(buf, name="albedo"), bits, buf
 
     def _launch(self, timer, name, film, blob, sd, lead, spp, seed, flags, *rest):
         """every render call that reads a blob: `name`(blob, info, sd, *lead, spp, seed, flags, *rest, [scratch,] stream) inside the `timer` bracket, then
@@ -1075,7 +1086,7 @@ class DeviceGeometry:
         self._launch("render_bwd", "ffx_render_bwd", _TWIN, blob, sd, (mats_arg,), spp, seed, flags, gimg_arg, gtex_arg)
 
     def render_fwd(self, sd, albedo, tex, spp, seed=0, fp16=False, cache=None, sparse_adjoint=False, cache_zeroed=False, keep_dropped=False, img_out=None,
-                   max_depth=2, rr_depth=5, lights=None, ambient=None):
+                   max_depth=2, rr_depth=5, lights=None, ambient=None, lights_directional=False):
         """K8.  With `cache` (a uint8 tensor of render_cache_bytes(...) bytes) the kernel also stores one
         footprint of every pixel in the projector texture for render_bwd_cached (opaque layout, ffx.h).
         sparse_adjoint (with a cache): FFX_RENDER_SPARSE_ADJOINT — gradients are only wanted at texels whose value is
@@ -1087,7 +1098,9 @@ class DeviceGeometry:
         lights: a [n, 24] float32 device tensor of extra emitters (pack_lights) — the image of the call without them plus each light's own
         part, at direct light and under max_depth > 2, on either film; fp32 film, no cache.
         ambient: the constant emitter's radiance (three floats or a [3] tensor) — as lights: added to the image by the same pass, fp32
-        film, no cache."""
+        film, no cache.
+        lights_directional: the table may hold directional emitters (ops.lights_directional(the list) tells) — the pass's kernels that
+        know all three record types; a table without such a record renders the same image either way."""
         path = path_flags(max_depth, rr_depth) if max_depth != 2 else 0
         if path and cache is not None:
             raise ValueError("render_fwd: max_depth > 2 has no adjoint cache (its adjoint is render_bwd with the same max_depth)")
@@ -1105,7 +1118,7 @@ class DeviceGeometry:
         # (the path integrator walks per lane and reads neither apex records nor tile bins: it claims nothing about the blob's apex areas, and rewrites none)
         flags = int(bool(fp16)) | (path if path else self._apex_flag(apex_key(sd)))
         if cache is None:
-            mats_arg, lbits, _keep = self._with_lights(sd, albedo, mats_arg, lights, "render_fwd", ambient)
+            mats_arg, lbits, _keep = self._with_lights(sd, albedo, mats_arg, lights, "render_fwd", ambient, lights_directional=lights_directional)
             flags |= lbits
             self._launch_fwd("render_fwd", blob, sd, mats_arg, _dev(tex, name="tex") if tex is not None else None, spp, seed, flags, _dev(img, img.dtype))
             return img
@@ -1201,7 +1214,7 @@ class DeviceGeometry:
                      _dev(gimg, name="gimg"), int(part), int(scale_log2), C.c_void_p(acc.data_ptr()))
 
     def render_bwd(self, sd, albedo, spp, seed, gimg, deterministic=None, max_depth=2, rr_depth=5, appearance=False, tex=None, material=False, lights=None,
-                   ambient=None):
+                   ambient=None, lights_directional=False):
         """the re-tracing adjoint.  deterministic (default: FFX_DETERMINISTIC=1 in the environment): ffx_render_bwd_det — bitwise
         reproducible accumulation (64-bit fixed point instead of float atomics; two re-traces and one host synchronisation).
         max_depth > 2: the path integrator's adjoint — replays render_fwd's paths of the same max_depth, rr_depth, spp and seed (float atomics only).
@@ -1212,7 +1225,8 @@ class DeviceGeometry:
         parameters per material row [n_shapes, 11].
         lights: the forward's extra emitters.  They do not depend on the projector's texture: gtex is that of the call without them (the float-atomic
         adjoint is handed the forward's bits and ignores them; the deterministic one is called without).  Not with appearance=True.
-        ambient: the forward's constant emitter — as lights: its bit is handed on and ignored.  Not with appearance=True."""
+        ambient: the forward's constant emitter — as lights: its bit is handed on and ignored.  Not with appearance=True.
+        lights_directional: the forward's — handed on with the lights' bits and ignored."""
         if ambient is not None and appearance:
             raise NotImplementedError("render_bwd(appearance=True): the constant emitter (ambient=) is not differentiated")
         if lights is not None and lights.numel() and appearance:
@@ -1250,7 +1264,7 @@ class DeviceGeometry:
         if lights is not None and lights.numel():  # (accepted and ignored: the table's tail is not read, so the table alone travels)
             if lights.dim() != 2 or lights.shape[0] > _abi.RENDER_MAX_LIGHTS:
                 raise ValueError(f"render_bwd: lights must be [n <= {_abi.RENDER_MAX_LIGHTS}, {_abi.LIGHT_FLOATS}]")
-            flags |= _abi.render_lights(lights.shape[0])
+            flags |= _abi.render_lights(lights.shape[0]) | (_abi.RENDER_LIGHTS_DIRECTIONAL if lights_directional else 0)
         if ambient is not None:  # (accepted and ignored likewise)
             pack_ambient(ambient)
             flags |= _abi.RENDER_AMBIENT
@@ -1288,15 +1302,15 @@ class DeviceGeometry:
         self._launch_fwd("render_jvp", blob, sd, _dev(albedo, name="albedo"), _dev(buf, name="tex"), spp, seed, flags, _dev(out))
         return out[0], out[1]
 
-    def render_aov(self, sd, albedo, tex, spp, seed=0, *, max_depth=2, rr_depth=5, lights=None, ambient=None):
+    def render_aov(self, sd, albedo, tex, spp, seed=0, *, max_depth=2, rr_depth=5, lights=None, ambient=None, lights_directional=False):
         """the render and its ground truth (FFX_RENDER_AOV): -> (img [H, W, 3], aov [H, W, 17]), img the image of render_fwd with the
         same arguments bit for bit, aov the primary hit's depth, position, normals, uv, base colour and ids (AOV_CHANNELS names the offsets) through the
         same film over the same samples.  max_depth > 2 chooses the image only.  fp32 film; two calls give the same bits.  lights (pack_lights, as
-        render_fwd): the image carries the extra emitters, the block is that of the call without them.  ambient: likewise."""
+        render_fwd): the image carries the extra emitters, the block is that of the call without them.  ambient, lights_directional: likewise."""
         path = path_flags(max_depth, rr_depth) if max_depth != 2 else 0
         H, W = sd.cam.height, sd.cam.width
         mats_arg = _check_materials(sd, albedo)
-        mats_arg, lbits, _keep = self._with_lights(sd, albedo, mats_arg, lights, "render_aov", ambient)
+        mats_arg, lbits, _keep = self._with_lights(sd, albedo, mats_arg, lights, "render_aov", ambient, lights_directional=lights_directional)
         out = torch.empty(H * W * (3 + _abi.RENDER_AOV_FLOATS), dtype=torch.float32, device=self.device)
         blob = self.blob
         # (the block's launch reads the camera's apex records and bins: behind a path render, which writes none, the call runs the pre-pass itself unless

@@ -224,9 +224,11 @@ class Scene:
                  (self.LIGHT_KEYS, self.load_light), (self.MAT_KEYS, self.load_material)]
         # (the constant emitter, DESIGN.md 4.8, is listed with the lights whatever its id says)
         ambient = getattr(getattr(mitsuba_params, "_scene", None), "_ambient_name", None)
+        # (... and so is a directional emitter)
+        suns = {l.name for l in getattr(getattr(getattr(mitsuba_params, "_scene", None), "data", None), "lights", None) or [] if l.kind == "directional"}
         for root in roots:
             low = root.lower()
-            if ambient is not None and root == ambient:
+            if (ambient is not None and root == ambient) or root in suns:
                 self.load_light(root)
                 continue
             for keys, loader in table:

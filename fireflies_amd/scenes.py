@@ -94,17 +94,18 @@ MAX_EXTRA_LIGHTS = 8  # (include/ffx.h FFX_RENDER_MAX_LIGHTS)
 
 @dataclass
 class LightData:
-    """an emitter beyond the main spot: a point light (only to_world's translation counts) or a further spot"""
+    """an emitter beyond the main spot: a point light (only to_world's translation counts) or a further spot; or a directional emitter
+    (a sun) — it travels along the +Z of to_world's 3 x 3, and `intensity` carries its irradiance"""
     name: str
-    kind: str  # "point" | "spot"
+    kind: str  # "point" | "spot" | "directional"
     to_world: np.ndarray
     intensity: tuple = (1.0, 1.0, 1.0)
     cutoff_angle: float = 20.0
     beam_width: float = 15.0
 
     def __post_init__(self):
-        if self.kind not in ("point", "spot"):
-            raise ValueError(f"LightData.kind must be 'point' or 'spot', got {self.kind!r}")
+        if self.kind not in ("point", "spot", "directional"):
+            raise ValueError(f"LightData.kind must be 'point', 'spot' or 'directional', got {self.kind!r}")
 
 
 @dataclass

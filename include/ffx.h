@@ -578,7 +578,8 @@ int ffx_trace_rays(const void *bvh /*[dev]*/, const ffx_bvh_info *info /*[host]*
  * Dr.Jit backward w.r.t. `tex.data` (examples/vocalfold_scene.py:69).  Shading model
  * (DESIGN.md §4): direct illumination at the primary hit from two delta emitters
  * (projector with irradiance texture, spot light) and, with FFX_RENDER_LIGHTS, up to
- * FFX_RENDER_MAX_LIGHTS further point lights and spots and, with FFX_RENDER_AMBIENT, a constant
+ * FFX_RENDER_MAX_LIGHTS further point lights, spots and (FFX_RENDER_LIGHTS_DIRECTIONAL)
+ * directional emitters and, with FFX_RENDER_AMBIENT, a constant
  * emitter (ambient light); Lambert or principled BSDF per shape, optional
  * shadow rays, box reconstruction filter, counter-based per-sample jitter.
  * The render is linear in the texture, so the adjoint needs no forward state: it replays
@@ -879,6 +880,24 @@ int ffx_det_finish(const void *acc /*[dev] int64 [n]*/, int scale_log2, size_t n
 #define FFX_LIGHT_FLOATS 24
 #define FFX_LIGHT_POINT 0
 #define FFX_LIGHT_SPOT 1
+/* The directional emitter — a sun, Mitsuba's <emitter type="directional">: a third type of light record, FFX_LIGHT_DIRECTIONAL (2.0) in
+ * float 21.  An additive extension of ABI 11 (FFX_ABI_VERSION is unchanged; no struct changes, no new entry point).  Such a record is
+ *              0..15   to_world, row-major; only its 3 x 3 is read: the light travels along normalize(3 x 3 . (0, 0, 1)), the frame's +Z
+ *              16..18  irradiance RGB: the power per unit area on a surface perpendicular to the light
+ *              19, 20  written 0
+ *              21      FFX_LIGHT_DIRECTIONAL
+ *              22..23  reserved, written 0
+ * and counts among the FFX_RENDER_MAX_LIGHTS.  A delta light at infinity: wi = -direction at every vertex, no falloff and no 1 / d^2; with bit 0 of
+ * sd->shadows one any-hit ray from the lifted point along wi over (0, 3e38).  A direction that does not normalise to a finite unit vector lights nothing.
+ * Irradiance 0 adds +0.0.
+ * FFX_RENDER_LIGHTS_DIRECTIONAL in the img_fp16 word of ffx_render_fwd / ffx_render_fwd_filtered says that the table may hold such records (the host does
+ * not read the device table) and selects the kernels that know them; they serve all three types, and the constant emitter of FFX_RENDER_AMBIENT, in one
+ * walk per sample.  Without the bit nothing changes: a record of type 2 is then the caller's error.  FFX_ERR_ARG without FFX_RENDER_LIGHTS(n >= 1).
+ * Refused and accepted where FFX_RENDER_LIGHTS is: FFX_ERR_UNSUPPORTED together with FFX_RENDER_FP16, FFX_RENDER_TANGENT or a FFX_RENDER_GRAD_* bit and on
+ * every other render entry point; accepted with FFX_RENDER_PATH, FFX_RENDER_AOV and FFX_RENDER_AMBIENT; accepted and ignored by ffx_render_bwd /
+ * ffx_render_bwd_filtered without a FFX_RENDER_GRAD_* bit.  The oracle does not know the bit: never pass it to it. */
+#define FFX_LIGHT_DIRECTIONAL 2
+#define FFX_RENDER_LIGHTS_DIRECTIONAL 0x4000000
 /* The constant emitter — ambient light, Mitsuba's <emitter type="constant">: FFX_RENDER_AMBIENT in the img_fp16 word of ffx_render_fwd /
  * ffx_render_fwd_filtered.  An additive extension of ABI 11 (FFX_ABI_VERSION is unchanged; no struct changes, no new entry point).
  *   input  — shape_albedo: [material table | n light records | one ambient record] in one buffer: behind the table's n_shapes x max(mat_stride, 3) floats and
