@@ -209,6 +209,32 @@ def relay(proj_on=True, spot_on=False, W=16, H=16, tex=32, projector_scale=2.0):
                             cam, proj, spot, projector_scale)
 
 
+SMOOTH_BALL = ((0.9, 0.9, 0.65), 0.6)  # (centre, radius) of smooth_corner's ball
+SMOOTH_UV = np.array([[-0.5, 0.25], [2.5, 0.25], [2.5, 2.25], [-0.5, 2.25]], np.float32)  # (aov_corner's: beyond [0, 1], the lookup wraps)
+
+
+def smooth_corner(W, H, lambert_only=False, every_lobe=False, smooth=True, tex=32):
+    """the scene of tests/test_shading_walk_*.py, where the shading normal differs from the geometric one at every vertex of a walk: the floor
+    z = 0 (a base-colour texture as aov_corner's, uv beyond [0, 1], a principled row), wall x = 0 (a Lambert row), wall y = 0 (a principled row) and,
+    above the floor between them, a smooth ball of 8 x 4 facets — coarse on purpose: its interpolated normals stand tens of degrees off its
+    facets', so that bounces drawn about n_s leave below a facet and shading normals face the other way than their facet.  lambert_only: no BSDF and
+    no texture (a stride-3 table); every_lobe: EVERY_LOBE on the ball; smooth=False: the same geometry flat.
+    -> (scene, base texture or None, the floor's uv or None)"""
+    sv, st = scenes.make_uv_sphere(*SMOOTH_BALL, nu=8, nv=4)
+    base_tex = None if lambert_only else base_texture()
+    uv = None if lambert_only else SMOOTH_UV
+
+    def bsdf(b):
+        return None if lambert_only else b
+
+    meshes = [scenes.MeshData("mesh-Floor", _floor(), QUAD, FLOOR_RGB, material="mat-Floor", bsdf=bsdf({"roughness": 0.4}), uv=uv, base_tex=base_tex),
+              scenes.MeshData("mesh-WallX", _wall_x(), QUAD, WALL_X_RGB, material="mat-WallX"),
+              scenes.MeshData("mesh-WallY", _wall_y(), QUAD, WALL_Y_RGB, material="mat-WallY", bsdf=bsdf({"roughness": 0.6})),
+              scenes.MeshData("mesh-Ball", np.asarray(sv, np.float32)[None], np.asarray(st, np.int32), CUBE_RGB, material="mat-Ball",
+                              bsdf=bsdf(dict(EVERY_LOBE)) if every_lobe else None, smooth=smooth)]
+    return scenes.SceneData(meshes, _camera(W, H, (3.1, 2.7, 2.6), SMOOTH_BALL[0]), _projector(tex), _spot(), 1.0), base_tex, uv
+
+
 def aov_corner(W, H, lambert_only=False):
     """a floor (textured base colour, flat) and a wall (Lambert row; smooth: its vertex normals are the plane's, bent at the shared seam by nothing — the
     wall is its own mesh) with a smooth sphere above the floor so that the interpolated normal differs from the geometric one.  lambert_only: no BSDF,

@@ -5,7 +5,9 @@ cosine-weighted bounces, roulette) with its escapes reported, and the closing ra
   - when its camera ray hits nothing in (nt, ft]                                                     (vertex 0: the background),
   - times the throughput behind the bounce at vertex v when that bounce's ray hits nothing in (0, inf) (vertex v; v + 1 < max_depth: the walk's own
     secondary ray, v + 1 = max_depth: the closing ray, an occlusion test along the bounce the walk would make).
-Flat-shaded scenes without base-colour textures (ng = ns).  The image it returns is the emitter's part alone: the render is linear in the emitters.
+Both normals and the base-colour textures are ref_path.Surface's (`shading`: ref_path.walk's smooth, vert_uv, base_tex and swap): the bounce — the
+closing one included — is drawn about n_s, ends where n_g . wo <= 0 and weighs by pi f / (n_s . wo).  The image it returns is the emitter's part
+alone: the render is linear in the emitters.
 
 round32: every quantity the walk hands from one step to the next (ray origins and directions, lifted points, bounce weights, throughputs) is rounded
 to float32 — a model of evaluating the same statement in single precision, for the test that the caps of the GPU comparison leave room for that.
@@ -22,13 +24,14 @@ def _r(x, round32):
     return np.asarray(x, np.float32).astype(np.float64) if round32 else x
 
 
-def sample_radiance(verts, tri_idx, tri_shape, sd, mats, radiance, spp, seed, max_depth=2, rr_depth=5, use_jitter=True, parts=None, round32=False):
+def sample_radiance(verts, tri_idx, tri_shape, sd, mats, radiance, spp, seed, max_depth=2, rr_depth=5, use_jitter=True, parts=None, round32=False, *,
+                    smooth=None, vert_uv=None, base_tex=None, swap=None):
     """[W*H*spp, 3]: what the constant emitter of radiance (r, g, b) adds to every sample.  parts (a dict): vertex -> that vertex's share of the result
     (0: the background), and under "closing" the number of closing rays cast, under "escaped" the number of rays of any kind that hit nothing"""
     La = np.asarray(radiance, np.float64).reshape(3)
     mats = np.asarray(mats, np.float64)
-    tris = bf.world_triangles(verts, tri_idx)
-    _, e1, e2 = tris
+    surf = rp.Surface(verts, tri_idx, tri_shape, smooth, vert_uv, base_tex, swap)
+    tris = surf.tris
     key = rp.path_key(seed)
     o, d, nt, ft = bf.camera_rays(sd.cam, spp, use_jitter, seed)
     o, d = _r(o, round32), _r(d, round32)
@@ -53,17 +56,15 @@ def sample_radiance(verts, tri_idx, tri_shape, sd, mats, radiance, spp, seed, ma
         if len(idx) == 0:
             break
         P = _r(o + t[:, None] * d, round32)
-        n = np.cross(e1[prim], e2[prim])
-        n = n / np.linalg.norm(n, axis=1, keepdims=True)
-        n = np.where(((n * d).sum(1) > 0)[:, None], -n, n)
-        Po = _r(P + n * ((1.0 + np.abs(P).max(1)) * EPS)[:, None], round32)
-        rows = mats[np.asarray(tri_shape)[prim]]
-        # the bounce the walk makes, or would make, at this vertex
-        wo = _r(rp.cosine_dir(n, rp.path_u(key, idx, v, 0), rp.path_u(key, idx, v, 1)), round32)
-        cos_o = (n * wo).sum(1)
+        ng, ns, Po = surf.frame(P, d, prim)
+        Po = _r(Po, round32)
+        rows = surf.rows(mats, P, prim, v)
+        # the bounce the walk makes, or would make, at this vertex: about n_s, alive on the geometric side
+        wo = _r(rp.cosine_dir(ng if swap == "bounce_about_ng" else ns, rp.path_u(key, idx, v, 0), rp.path_u(key, idx, v, 1)), round32)
+        cos_o = (ns * wo).sum(1)
         with np.errstate(divide="ignore", invalid="ignore"):
-            f = _r(np.pi * bf.bsdf_cos(rows, n, -d, wo) / cos_o[:, None], round32)
-        keep = cos_o > 0
+            f = _r(np.pi * bf.bsdf_cos(rows, ns, -d, wo) / cos_o[:, None], round32)
+        keep = (ng * wo).sum(1) > 0 if swap != "no_ng_wo_test" else np.ones(len(idx), bool)
         nb = np.where(keep[:, None], beta * f, 0.0)
         bmax = nb.max(1)
         keep &= bmax > 0
@@ -90,7 +91,7 @@ def film(sd, L, spp, seed, gaussian_stddev=None):
 
 
 def render_ambient(verts, tri_idx, tri_shape, sd, mats, radiance, spp, seed, max_depth=2, rr_depth=5, gaussian_stddev=None, use_jitter=True, parts=None,
-                   round32=False):
+                   round32=False, **shading):
     """[H, W, 3]: the constant emitter's part of the image — image(main, lights, ambient) - image(main, lights)"""
-    L = sample_radiance(verts, tri_idx, tri_shape, sd, mats, radiance, spp, seed, max_depth, rr_depth, use_jitter, parts, round32)
+    L = sample_radiance(verts, tri_idx, tri_shape, sd, mats, radiance, spp, seed, max_depth, rr_depth, use_jitter, parts, round32, **shading)
     return film(sd, L, spp, seed, gaussian_stddev)

@@ -3,7 +3,9 @@
 Written from DESIGN.md 4.7, not from the kernels: every ray against every triangle (no tree), the walk of DESIGN.md 4.4 (ref_path's random numbers,
 cosine-weighted bounces, roulette), and at every vertex the n lights of a [n, 24] table (include/ffx.h FFX_RENDER_LIGHTS): direction and lit test,
 the spot's falloff in the light's local frame, the shadow ray from the light to the lifted point, radiance beta I fall / d^2 (base A + B) / pi.
-Flat-shaded scenes without base-colour textures (ng = ns).  The image it returns is the lights' part alone: the render is linear in the emitters.
+The walk is ref_path.walk: shading normals and base-colour textures as it states them (`shading`: its smooth, vert_uv, base_tex and swap); a light
+must lie on the geometric side (n_g . wi > 0) and its cosine and the BSDF's frame are the shading normal's.  The image it returns is the lights'
+part alone: the render is linear in the emitters.
 """
 import numpy as np
 
@@ -23,17 +25,20 @@ def table_row(kind, to_world, intensity, cutoff_deg=20.0, beam_width_deg=15.0):
     return r
 
 
-def light_terms(row, tris, rows, P, n, Po, d, shadows):
-    """one light at the points P (normal n — geometric and shading — faced to the incoming direction d, lifted points Po, material rows `rows`):
-    -> (radiance per channel [N,3] at throughput 1, {"faces": the lit test passed, "fall": the falloff, "occluded": the shadow ray hit})"""
+def light_terms(row, tris, rows, P, ng, ns, Po, d, shadows, swap=None):
+    """one light at the points P (geometric normal ng and shading normal ns as ref_path.Surface.frame faces them, lifted points Po, material rows
+    `rows`): -> (radiance per channel [N,3] at throughput 1, {"faces": the lit test passed, "fall": the falloff, "occluded": the shadow ray hit})"""
     row = np.asarray(row, np.float64)
+    n = ng if swap == "emitter_cosine_from_ng" else ns  # (the normal of the cosine and of the BSDF's frame)
     tw = row[:16].reshape(4, 4)
     Lk = tw[:3, 3]
     wi = Lk - P
     d2 = (wi * wi).sum(1)
     with np.errstate(divide="ignore", invalid="ignore"):
         wi = wi / np.sqrt(d2)[:, None]
-    faces = (d2 > 0) & ((n * wi).sum(1) > 0)  # (ns = ng here: both tests are this one)
+    faces = (d2 > 0) & ((n * wi).sum(1) > 0)
+    if swap != "no_geometric_side":
+        faces &= (ng * wi).sum(1) > 0
     fall = np.ones(len(P))
     if row[21] != TYPE_POINT:
         local = (-wi) @ np.linalg.inv(tw[:3, :3]).T
@@ -52,45 +57,14 @@ def light_terms(row, tris, rows, P, n, Po, d, shadows):
     return rad, {"faces": faces, "fall": fall, "occluded": occluded}
 
 
-def vertices(verts, tri_idx, tri_shape, sd, mats, spp, seed, max_depth=2, rr_depth=5, use_jitter=True):
-    """the walk of DESIGN.md 4.4 without any emitter: yields (v, sample indices, throughput [n,3], P, n, Po, d, rows) per vertex v = 1 .. max_depth - 1"""
-    mats = np.asarray(mats, np.float64)
-    tris = bf.world_triangles(verts, tri_idx)
-    _, e1, e2 = tris
-    key = rp.path_key(seed)
-    o, d, nt, ft = bf.camera_rays(sd.cam, spp, use_jitter, seed)
-    idx = np.arange(len(d), dtype=np.uint64)
-    beta = np.ones((len(d), 3))
-    for v in range(1, max_depth):
-        t, prim = bf.intersect(o, d, tris, nt, ft)
-        hit = prim >= 0
-        idx, o, d, beta, t, prim = idx[hit], o[hit], d[hit], beta[hit], t[hit], prim[hit]
-        if len(idx) == 0:
-            return
-        P = o + t[:, None] * d
-        n = np.cross(e1[prim], e2[prim])
-        n = n / np.linalg.norm(n, axis=1, keepdims=True)
-        n = np.where(((n * d).sum(1) > 0)[:, None], -n, n)
-        Po = P + n * ((1.0 + np.abs(P).max(1)) * EPS)[:, None]
-        rows = mats[np.asarray(tri_shape)[prim]]
-        yield v, idx, beta.copy(), P, n, Po, d, rows
-        if v + 1 >= max_depth:
-            return
-        wo = rp.cosine_dir(n, rp.path_u(key, idx, v, 0), rp.path_u(key, idx, v, 1))
-        with np.errstate(divide="ignore", invalid="ignore"):
-            f = np.pi * bf.bsdf_cos(rows, n, -d, wo) / (n * wo).sum(1)[:, None]
-        beta = beta * f
-        bmax = beta.max(1)
-        keep = bmax > 0
-        if v >= rr_depth:
-            q = np.minimum(bmax, 0.95)
-            keep &= rp.path_u(key, idx, v, 2) < q
-            beta = beta / np.where(keep, q, 1.0)[:, None]
-        idx, o, d, beta = idx[keep], Po[keep], wo[keep], beta[keep]
-        nt, ft = np.zeros(len(idx)), np.full(len(idx), np.inf)
+def vertices(verts, tri_idx, tri_shape, sd, mats, spp, seed, max_depth=2, rr_depth=5, use_jitter=True, **shading):
+    """ref_path.walk, the walk of DESIGN.md 4.4 without any emitter: yields (v, sample indices, throughput [n,3], P, ng, ns, Po, d, rows) per vertex
+    v = 1 .. max_depth - 1"""
+    for x in rp.walk(verts, tri_idx, tri_shape, sd, mats, spp, seed, max_depth, rr_depth, use_jitter, **shading):
+        yield x.v, x.idx, x.beta, x.P, x.ng, x.ns, x.Po, x.d, x.rows
 
 
-def sample_radiance(verts, tri_idx, tri_shape, sd, mats, lights, spp, seed, max_depth=2, rr_depth=5, use_jitter=True, stats=None):
+def sample_radiance(verts, tri_idx, tri_shape, sd, mats, lights, spp, seed, max_depth=2, rr_depth=5, use_jitter=True, stats=None, **shading):
     """[W*H*spp, 3]: what the lights of the [n, 24] table add to every sample.  stats (a dict): per light k the counts over all vertices of the
     samples that face it ("faces"), of those with a positive falloff ("lit") and of those whose shadow ray hit ("occluded"), and "min_fall"; under
     "direct" the part of L that comes from vertex 1"""
@@ -100,9 +74,9 @@ def sample_radiance(verts, tri_idx, tri_shape, sd, mats, lights, spp, seed, max_
     direct = np.zeros_like(L)
     if stats is not None:
         stats.update({k: {"faces": 0, "lit": 0, "occluded": 0, "min_fall": np.inf} for k in range(len(lights))})
-    for v, idx, beta, P, n, Po, d, rows in vertices(verts, tri_idx, tri_shape, sd, mats, spp, seed, max_depth, rr_depth, use_jitter):
+    for v, idx, beta, P, ng, ns, Po, d, rows in vertices(verts, tri_idx, tri_shape, sd, mats, spp, seed, max_depth, rr_depth, use_jitter, **shading):
         for k, row in enumerate(lights):
-            rad, info = light_terms(row, tris, rows, P, n, Po, d, bool(sd.shadows & 1))
+            rad, info = light_terms(row, tris, rows, P, ng, ns, Po, d, bool(sd.shadows & 1), shading.get("swap"))
             L[idx.astype(np.int64)] += beta * rad
             if v == 1:
                 direct[idx.astype(np.int64)] += beta * rad
@@ -126,7 +100,7 @@ def film(sd, L, spp, seed, gaussian_stddev=None):
     return L.reshape(H, W, spp, 3).mean(2)
 
 
-def render_lights(verts, tri_idx, tri_shape, sd, mats, lights, spp, seed, max_depth=2, rr_depth=5, gaussian_stddev=None, use_jitter=True, stats=None):
+def render_lights(verts, tri_idx, tri_shape, sd, mats, lights, spp, seed, max_depth=2, rr_depth=5, gaussian_stddev=None, use_jitter=True, stats=None, **shading):
     """[H, W, 3]: the lights' part of the image — image(proj, spot, lights) - image(proj, spot)"""
-    L = sample_radiance(verts, tri_idx, tri_shape, sd, mats, lights, spp, seed, max_depth, rr_depth, use_jitter, stats)
+    L = sample_radiance(verts, tri_idx, tri_shape, sd, mats, lights, spp, seed, max_depth, rr_depth, use_jitter, stats, **shading)
     return film(sd, L, spp, seed, gaussian_stddev)

@@ -5,7 +5,9 @@ central differences of it over a row differentiate q_v too (and meet a jump wher
 "max beta = 0 ends the path" test as constants of the replay.  render_fwd_frozen walks the same paths with two throughputs: the one of the rows under
 test, which the image uses, and the one of the unperturbed rows `mats0`, which alone decides survival and supplies q_v.  Central differences of it over
 `mats` (and over the spot's intensity in `sd`) are the detached gradient; with the roulette off it equals ref_path.render_fwd.
-Bounces are cosine-weighted, so no row moves a path: both throughputs belong to the same vertices."""
+Bounces are cosine-weighted, so no row moves a path: both throughputs belong to the same vertices.  The walk is ref_path.walk (its mats0): shading
+normals and base-colour textures as it states them; a texture under test (base_tex) is frozen at base_tex0 in the same way, and float64_tangent
+takes a tangent of the textures beside those of the rows, the projector's texture and the spot."""
 import numpy as np
 
 from fireflies_amd import scenes
@@ -16,54 +18,17 @@ from tests.support import copy_desc
 R0 = scenes.MAT_COLUMN["roughness"]
 
 
-def path_vertices_frozen(verts, tri_idx, tri_shape, sd, mats, mats0, spp, seed, max_depth, rr_depth=5):
-    """ref_path.path_vertices with survival and q_v from mats0: a list of (sample indices, throughput under mats [n, 3], emitters' terms under mats)"""
-    mats, mats0 = np.asarray(mats, np.float64), np.asarray(mats0, np.float64)
-    tris = bf.world_triangles(verts, tri_idx)
-    v0, e1, e2 = tris
-    key = rp.path_key(seed)
-    o, d, nt, ft = bf.camera_rays(sd.cam, spp, True, seed)
-    idx = np.arange(len(d), dtype=np.uint64)
-    beta, beta0 = np.ones((len(d), 3)), np.ones((len(d), 3))
-    out = []
-    for v in range(1, max_depth):
-        t, prim = bf.intersect(o, d, tris, nt, ft)
-        hit = prim >= 0
-        idx, o, d, beta, beta0, t, prim = idx[hit], o[hit], d[hit], beta[hit], beta0[hit], t[hit], prim[hit]
-        if len(idx) == 0:
-            break
-        P = o + t[:, None] * d
-        n = np.cross(e1[prim], e2[prim])
-        n = n / np.linalg.norm(n, axis=1, keepdims=True)
-        n = np.where(((n * d).sum(1) > 0)[:, None], -n, n)
-        Po = P + n * ((1.0 + np.abs(P).max(1)) * rp.EPS)[:, None]
-        shape = np.asarray(tri_shape)[prim]
-        out.append((idx, beta.copy(), rp._emitters(sd, tris, mats[shape], P, n, Po, d)))
-        if v + 1 >= max_depth:
-            break
-        wo = rp.cosine_dir(n, rp.path_u(key, idx, v, 0), rp.path_u(key, idx, v, 1))
-        with np.errstate(divide="ignore", invalid="ignore"):
-            cos_o = (n * wo).sum(1)[:, None]
-            f = np.pi * bf.bsdf_cos(mats[shape], n, -d, wo) / cos_o
-            f0 = np.pi * bf.bsdf_cos(mats0[shape], n, -d, wo) / cos_o
-        beta, beta0 = beta * f, beta0 * f0
-        bmax0 = beta0.max(1)
-        keep = bmax0 > 0
-        if v >= rr_depth:
-            q = np.minimum(bmax0, 0.95)
-            keep &= rp.path_u(key, idx, v, 2) < q
-            qs = np.where(keep, q, 1.0)[:, None]
-            beta, beta0 = beta / qs, beta0 / qs
-        idx, o, d, beta, beta0 = idx[keep], Po[keep], wo[keep], beta[keep], beta0[keep]
-        nt, ft = np.zeros(len(idx)), np.full(len(idx), np.inf)
-    return out
+def path_vertices_frozen(verts, tri_idx, tri_shape, sd, mats, mats0, spp, seed, max_depth, rr_depth=5, **shading):
+    """ref_path.path_vertices with survival and q_v from mats0: a list of (sample indices, throughput under mats [n, 3], emitters' terms under mats).
+    shading: ref_path.walk's smooth, vert_uv, base_tex, base_tex0 (the textures of the frozen roulette where base_tex is the one under test) and swap"""
+    return rp.path_vertices(verts, tri_idx, tri_shape, sd, mats, spp, seed, max_depth, rr_depth, mats0=mats0, **shading)
 
 
-def render_fwd_frozen(verts, tri_idx, tri_shape, sd, mats, mats0, tex, spp, seed, max_depth, rr_depth=5, gaussian_stddev=None):
+def render_fwd_frozen(verts, tri_idx, tri_shape, sd, mats, mats0, tex, spp, seed, max_depth, rr_depth=5, gaussian_stddev=None, **shading):
     """ref_path.render_fwd of `mats` on the paths, survival decisions and q_v of `mats0`"""
     W, H = sd.cam.width, sd.cam.height
     L = np.zeros((W * H * spp, 3))
-    for idx, beta, e in path_vertices_frozen(verts, tri_idx, tri_shape, sd, mats, mats0, spp, seed, max_depth, rr_depth):
+    for idx, beta, e in path_vertices_frozen(verts, tri_idx, tri_shape, sd, mats, mats0, spp, seed, max_depth, rr_depth, **shading):
         rad = e["spot"].copy()
         if sd.proj.enabled:
             rad += rp._tex_value(sd, tex, e) * e["pfac"]
@@ -72,6 +37,27 @@ def render_fwd_frozen(verts, tri_idx, tri_shape, sd, mats, mats0, tex, spp, seed
         num, den, _ = bf._film_splat(W, H, spp, seed, gaussian_stddev, values=L)
         return np.where(den[..., None] > 0, num / np.where(den > 0, den, 1.0)[..., None], 0.0)
     return L.reshape(H, W, spp, 3).mean(2)
+
+
+class SameRays:
+    """with SameRays(): ref_bruteforce.intersect answers a question it has been asked before from memory.  Bounces are cosine-weighted and the
+    roulette is frozen, so the renders of a difference over rows, intensities or textures ask the same rays of the same triangles again and again;
+    more than half of a small render's time is those answers.  The key is every argument's bytes: nothing is assumed about the callers"""
+
+    def __enter__(self):
+        self.inner, self.seen = bf.intersect, {}
+
+        def intersect(o, d, tris, tmin, tmax, chunk=4096):
+            key = tuple(np.ascontiguousarray(a).tobytes() for a in (o, d, *tris, np.asarray(tmin, np.float64), np.asarray(tmax, np.float64)))
+            if key not in self.seen:
+                self.seen[key] = self.inner(o, d, tris, tmin, tmax, chunk)
+            return tuple(a.copy() for a in self.seen[key])
+
+        bf.intersect = intersect
+        return self
+
+    def __exit__(self, *exc):
+        bf.intersect = self.inner
 
 
 def interior_material_tangent(rows, rng):
@@ -89,20 +75,27 @@ def interior_material_tangent(rows, rng):
     return d
 
 
-def float64_tangent(world, sd, rows, tex, spp, seed, depth, rr, stddev, drows=None, dtex=None, dspot=None, h=5e-4):
+def float64_tangent(world, sd, rows, tex, spp, seed, depth, rr, stddev, drows=None, dtex=None, dspot=None, h=5e-4, dbase_tex=None, **shading):
     """d image / d theta . dtheta in float64 on the paths, survival decisions and q_v of `rows` (prb's detached roulette): the five-point central
     difference of render_fwd_frozen along drows (base colours and BSDF columns, [n_shapes, stride]) plus — the image is linear in both —
-    the image of the texture dtex with a dark spot and of the spot intensity dspot (float32 values) with a dark texture"""
+    the image of the texture dtex with a dark spot and of the spot intensity dspot (float32 values) with a dark texture.  shading: ref_path.walk's smooth,
+    vert_uv and base_tex; dbase_tex (one [h, w, 3] per base-colour texture): the same five-point difference along it, the roulette frozen at base_tex —
+    up to one bounce the image is affine in a texture and the difference exact, beyond it the image is a polynomial in it as in a row's colour"""
     rows = np.asarray(rows, np.float64)
     tex = None if tex is None else np.asarray(tex, np.float64)
 
-    def img(r, s, t):
-        return render_fwd_frozen(*world, s, r, rows, t, spp, seed, depth, rr, gaussian_stddev=stddev)
+    bt0 = shading.pop("base_tex", None)
+
+    def img(r, s, t, bt=bt0):
+        return render_fwd_frozen(*world, s, r, rows, t, spp, seed, depth, rr, gaussian_stddev=stddev, base_tex=bt, base_tex0=bt0, **shading)
 
     out = np.zeros((sd.cam.height, sd.cam.width, 3))
     if drows is not None and np.abs(drows).max() > 0:
         d = np.asarray(drows, np.float64)
         out += (-img(rows + 2 * h * d, sd, tex) + 8 * img(rows + h * d, sd, tex) - 8 * img(rows - h * d, sd, tex) + img(rows - 2 * h * d, sd, tex)) / (12 * h)
+    if dbase_tex is not None and bt0 is not None:
+        at = lambda k: img(rows, sd, tex, [np.asarray(b, np.float64) + k * h * np.asarray(db, np.float64) for b, db in zip(bt0, dbase_tex)])  # noqa: E731
+        out += (-at(2) + 8 * at(1) - 8 * at(-1) + at(-2)) / (12 * h)
     dark = copy_desc(sd)
     for c in range(3):
         dark.spot.intensity[c] = 0.0

@@ -162,6 +162,22 @@ def fd4(f, rows, i, col, h):
 
 
 # ------------------------------------------------------------------ comparisons
+def independent_figures(got, ref, scale, part_sum):
+    """the figures of the three conditions of tests/test_lights_gpu.py's `independent`, each as a fraction of its bound: the share of the pixels off by
+    more than 2e-3 of the scale over 0.04, the median error over 1e-4 of the scale, the sums' difference over 1 % of the part under test"""
+    err = np.abs(got - ref)
+    return float((err > 2e-3 * scale).mean()) / 0.04, float(np.median(err)) / (1e-4 * scale), float(abs(got.sum() - ref.sum())) / (0.01 * part_sum)
+
+
+def independent(what, got, ref, scale, part_sum):
+    """tests/test_lights_gpu.py's three conditions on `independent_figures`; the figures are printed before they are asserted -> the figures"""
+    f = independent_figures(got, ref, scale, part_sum)
+    print(f"{what}: scale {scale:.4g}; as fractions of the bounds: pixels off by > 2e-3 scale {f[0]:.2e}, median {f[1]:.2e}, sums {f[2]:.2e}")
+    assert np.isfinite(got).all() and part_sum > 0
+    assert f[0] <= 1.0 and f[1] <= 1.0 and f[2] <= 1.0, (what, f)
+    return f
+
+
 def outlier_rule(what, got, want, scale, spp):
     """the project's rule: per pixel within 1e-4 of the scale; at most 2e-4 of the pixels (at least one) beyond, none by more than 1.5 scale / spp — one
     sample on the other side of a triangle edge"""
