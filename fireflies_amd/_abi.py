@@ -235,6 +235,16 @@ def render_lights(n):
 # follows the n light records (n may be 0) in the shape_albedo buffer
 RENDER_AMBIENT = 0x2000000
 AMBIENT_FLOATS = 4
+# the extra emitters' adjoint (include/ffx.h FFX_RENDER_EMITTER_GRAD): bit 27 of the flags word of ffx_render_bwd[_filtered], beside the forward's
+# lights / ambient bits; behind gtex the result block [RENDER_MAX_LIGHTS + 1][3] (row k: d loss / d record k's power, the last row: d loss / d radiance),
+# then one slot of the block's size per pixel (the workspace)
+RENDER_EMITTER_GRAD = 0x8000000
+RENDER_EMITTER_GRAD_BLOCK_FLOATS = 3 * (RENDER_MAX_LIGHTS + 1)
+
+
+def emitter_grad_floats(width, height):
+    """FFX_RENDER_EMITTER_GRAD_FLOATS: the floats behind gtex of a call with RENDER_EMITTER_GRAD — the result block and the workspace"""
+    return RENDER_EMITTER_GRAD_BLOCK_FLOATS * (int(width) * int(height) + 1)
 
 
 MAX_BASE_TEX = 4

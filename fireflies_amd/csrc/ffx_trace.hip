@@ -4025,10 +4025,12 @@ __device__ __forceinline__ void lights_derive(const float *__restrict__ table, i
 }
 // the n lights at one vertex (st, pv: shade_sample<true, ..., !EMIT>'s; d: the ray that found it), weighted by the throughput beta, into L.
 // DIR: a directional record (lights_derive<true>'s) has no position, no falloff and no 1 / d^2; its shadow ray leaves the lifted point along wi, the closing
-// ray's form (path_walk's AMB), on the lane's own stack
-template <bool DIR = false>
+// ray's form (path_walk's AMB), on the lane's own stack.
+// ADJ (k_lights_bwd): the same geometry, falloff, shadow ray and row_terms, but record k's term WITHOUT its intensity, times the sample's
+// adjoint weight q, is added to the record's three sums sums[(3 k + ch) * stride]; L is not touched
+template <bool DIR = false, bool ADJ = false>
 __device__ __forceinline__ void lights_at_vertex(const ShadeK &c, const PathArgs &a, const float *__restrict__ s_l, int n, const SampleTerms &st, const PathVtxP &pv, v3 d,
-                                                 const float (&beta)[3], int *stack, int stride, float (&L)[3]) {
+                                                 const float (&beta)[3], int *stack, int stride, float (&L)[3], const float *q = nullptr, float *sums = nullptr) {
   const float *mt = mat_table(c);
   for (int k = 0; k < n; ++k) {
     const float *lk = s_l + FFX_LK_FLOATS * k;
@@ -4046,8 +4048,12 @@ __device__ __forceinline__ void lights_at_vertex(const ShadeK &c, const PathArgs
         const float f = bA * 0.3183098861837907f, fb = bB * 0.3183098861837907f;
 #pragma unroll
         for (int ch = 0; ch < 3; ++ch) {
-          const float r = lk[FFX_LK_INT + ch] * f, b = lk[FFX_LK_INT + ch] * fb;
-          L[ch] += beta[ch] * (c.mat_stride == 3 ? st.base[ch] * r : st.base[ch] * r + b);
+          if constexpr (ADJ) {
+            sums[(3 * k + ch) * stride] += q[ch] * (beta[ch] * (c.mat_stride == 3 ? st.base[ch] * f : st.base[ch] * f + fb));
+          } else {
+            const float r = lk[FFX_LK_INT + ch] * f, b = lk[FFX_LK_INT + ch] * fb;
+            L[ch] += beta[ch] * (c.mat_stride == 3 ? st.base[ch] * r : st.base[ch] * r + b);
+          }
         }
         continue;
       }
@@ -4080,8 +4086,12 @@ __device__ __forceinline__ void lights_at_vertex(const ShadeK &c, const PathArgs
     const float f = fall * bA / d2 * 0.3183098861837907f, fb = fall * bB / d2 * 0.3183098861837907f;
 #pragma unroll
     for (int ch = 0; ch < 3; ++ch) {
-      const float r = lk[FFX_LK_INT + ch] * f, b = lk[FFX_LK_INT + ch] * fb;
-      L[ch] += beta[ch] * (c.mat_stride == 3 ? st.base[ch] * r : st.base[ch] * r + b);
+      if constexpr (ADJ) {
+        sums[(3 * k + ch) * stride] += q[ch] * (beta[ch] * (c.mat_stride == 3 ? st.base[ch] * f : st.base[ch] * f + fb));
+      } else {
+        const float r = lk[FFX_LK_INT + ch] * f, b = lk[FFX_LK_INT + ch] * fb;
+        L[ch] += beta[ch] * (c.mat_stride == 3 ? st.base[ch] * r : st.base[ch] * r + b);
+      }
     }
   }
 }
@@ -4341,6 +4351,94 @@ __global__ void __launch_bounds__(64)
       proj_tex_scatter(kernarg_shade(), st, cw, gtex);
     });
   }
+}
+// ------------------------------------------------------------------------------------------ extra emitters' adjoint
+// FFX_RENDER_EMITTER_GRAD (include/ffx.h): d loss / d (the RGB power of every light record, the constant emitter's radiance).  The walk does not depend on the
+// emitters, so the image is linear in those powers and the derivative is the adjoint-weighted image at unit power: k_lights_dir_fwd's walk once more
+// (lights_derive<true>, path_walk<..., AMB>, the same jitter and path keys: the forward's paths by construction), where lights_at_vertex<true, ADJ> adds record k's
+// q[ch] beta[ch] (base[ch] f + fb) to the record's sum and every escaped ray q[ch] beta[ch] to the ambient's.  One wave = one pixel, lane l takes samples
+// l, l + 64, ...; a lane's 3 n record sums live in LDS, one column per lane (stride 64: conflict-free; a run-time record number never indexes registers)
+// behind the traversal stack in the dynamic area (stack_ints ints, then 3 n x 64 floats: a table of one record does not pay LDS, and with it occupancy,
+// for eight), the ambient's three in registers.  No atomics: the wave's sums go to the pixel's slot of the workspace [FFX_RENDER_EMITTER_GRAD_BLOCK_FLOATS]
+// [pixels] — zeros from a pixel nothing flows into, so that every slot is written by every call — and k_lights_grad_reduce adds the slots in a fixed order
+template <bool RF, bool AMB>
+__global__ void __launch_bounds__(64)
+    k_lights_bwd(ShadeK c, PathArgs a, const float *__restrict__ lights, int n_lights, const float *__restrict__ gsrc, float *__restrict__ slots, int stack_ints) {
+  extern __shared__ int s_dyn[];
+  __shared__ float s_l[FFX_RENDER_MAX_LIGHTS * FFX_LK_FLOATS];
+  float *s_sum = reinterpret_cast<float *>(s_dyn + stack_ints);
+  const int lane = threadIdx.x;
+  const uint32_t pix = blockIdx.x;
+  const int W = c.cam.W, H = c.cam.H, px = (int)(pix % (uint32_t)W), py = (int)(pix / (uint32_t)W);
+  const int n = n_lights < FFX_RENDER_MAX_LIGHTS ? n_lights : FFX_RENDER_MAX_LIGHTS; // (the host refuses more: s_l holds this many)
+  float *slot = slots + (size_t)lane * ((size_t)W * (size_t)H) + pix; // (lanes < FFX_RENDER_EMITTER_GRAD_BLOCK_FLOATS: entry `lane` of the pixel's slot)
+  float g[3];
+  bool flows; // pixel_adjoint<RF>'s values.  (The gaussian film's window is fetched by a statement of this kernel's own: one more caller of rf_window_g, and the
+              // packet kernels that inline it compile to other machine code — commuted operands of the window's bounds tests, tools/isa_same.py.)
+  if constexpr (RF) {
+    const int wb = (lane * 13) >> 6, wa = lane - 5 * wb, tx = px + wa - 2, ty = py + wb - 2;
+    float4 gw = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (lane < 25 && tx >= 0 && tx < W && ty >= 0 && ty < H) gw = reinterpret_cast<const float4 *>(gsrc)[(size_t)ty * W + tx];
+    g[0] = gw.x; g[1] = gw.y; g[2] = gw.z;
+    flows = wballot(g[0] != 0.f || g[1] != 0.f || g[2] != 0.f) != 0ull;
+  } else {
+    flows = pixel_adjoint<false>(gsrc, pix, px, py, W, H, lane, a.spp, g);
+  }
+  if (!flows) { // (wave-uniform, and the wave is the workgroup)
+    if (lane < FFX_RENDER_EMITTER_GRAD_BLOCK_FLOATS) *slot = 0.f;
+    return;
+  }
+  lights_derive<true>(lights, n, lane, s_l);
+  for (int j = 0; j < 3 * n; ++j) s_sum[j * 64 + lane] = 0.f;
+  float amb[3] = {0.f, 0.f, 0.f};
+  for (int pass = 0; pass < (a.spp + 63) >> 6; ++pass) {
+    const int s = pass * 64 + lane;
+    const uint32_t idx = pix * (uint32_t)a.spp + (uint32_t)s;
+    float jx, jy, q[3];
+    sample_jitter(a.seed_key, idx, jx, jy);
+    sample_adjoint<RF>(c.rf, jx, jy, g, q);
+    if (s >= a.spp || (q[0] == 0.f && q[1] == 0.f && q[2] == 0.f)) continue;
+    v3 o, d;
+    float nt, ft;
+    cam_ray(c.cam, ((float)px + jx) * c.cam.inv_w, ((float)py + jy) * c.cam.inv_h, o, d, nt, ft);
+    path_walk<false, false, false, AMB>(
+        a, idx, o, d, nt, ft, s_dyn + lane, 64,
+        [&](int, const SampleTerms &st, const PathVtxP &pv, v3 dv, const float (&beta)[3]) {
+          lights_at_vertex<true, true>(kernarg_shade(), a, s_l, n, st, pv, dv, beta, s_dyn + lane, 64, amb, q, s_sum + lane);
+        },
+        NoBounce(), [&](const float (&beta)[3]) { amb[0] += q[0] * beta[0]; amb[1] += q[1] * beta[1]; amb[2] += q[2] * beta[2]; });
+  }
+  float mine = 0.f; // (lane j: the wave's sum j; rows of absent records and of an absent constant emitter stay 0)
+  for (int j = 0; j < 3 * n; ++j) {
+    const float v = wave_sum_tree(s_sum[j * 64 + lane]);
+    if (lane == j) mine = v;
+  }
+  if constexpr (AMB) {
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) {
+      const float v = wave_sum_tree(amb[ch]);
+      if (lane == 3 * FFX_RENDER_MAX_LIGHTS + ch) mine = v;
+    }
+  }
+  if (lane < FFX_RENDER_EMITTER_GRAD_BLOCK_FLOATS) *slot = mine;
+}
+// the result block from the pixels' slots: workgroup j adds entry j of every slot (contiguous: slots[j][pixels]) — a thread its pixels in ascending order, then a tree over the threads
+// (a fixed order: the same bits on every run) — and WRITES block[j]; 0 for the row of an absent record or of an absent constant emitter
+#define FFX_EG_REDUCE_THREADS 1024
+__global__ void __launch_bounds__(FFX_EG_REDUCE_THREADS) k_lights_grad_reduce(const float *__restrict__ slots, int n_pix, int n, int amb, float *__restrict__ block) {
+  __shared__ float s_p[FFX_EG_REDUCE_THREADS];
+  const int j = blockIdx.x, row = j / 3, t = threadIdx.x;
+  const bool live = row < n || (row == FFX_RENDER_MAX_LIGHTS && amb); // (workgroup-uniform)
+  float v = 0.f;
+  if (live)
+    for (int p = t; p < n_pix; p += FFX_EG_REDUCE_THREADS) v += slots[(size_t)j * (size_t)n_pix + p];
+  s_p[t] = v;
+  __syncthreads();
+  for (int off = FFX_EG_REDUCE_THREADS / 2; off > 0; off >>= 1) {
+    if (t < off) s_p[t] += s_p[t + off];
+    __syncthreads();
+  }
+  if (t == 0) block[j] = s_p[0];
 }
 
 // ------------------------------------------------------------------------------------------ appearance adjoint
@@ -6009,13 +6107,18 @@ static int render_aov(const void *bvh, const ffx_bvh_info *info, const ffx_scene
   }
   return FFX_OK;
 }
-// the extra emitters' bits belong to ffx_render_fwd[_filtered] (and are ignored by ffx_render_bwd[_filtered]): every other render entry point refuses them
+// the extra emitters' adjoint (FFX_RENDER_EMITTER_GRAD) belongs to ffx_render_bwd[_filtered]: every other render entry point refuses the bit
+#define FFX_NO_EMITTER_GRAD(flags_, what_) \
+  do { if ((flags_) & FFX_RENDER_EMITTER_GRAD) FFX_FAIL(FFX_ERR_UNSUPPORTED, "%s: FFX_RENDER_EMITTER_GRAD is served by ffx_render_bwd[_filtered] only", what_); } while (0)
+// the extra emitters' bits belong to ffx_render_fwd[_filtered] (and are ignored by ffx_render_bwd[_filtered] without FFX_RENDER_EMITTER_GRAD): every other render
+// entry point refuses them
 #define FFX_NO_LIGHTS(flags_, what_) \
   do { \
     if ((flags_) & FFX_RENDER_LIGHTS_MASK) FFX_FAIL(FFX_ERR_UNSUPPORTED, "%s: FFX_RENDER_LIGHTS is served by ffx_render_fwd[_filtered] only", what_); \
     if ((flags_) & FFX_RENDER_AMBIENT) FFX_FAIL(FFX_ERR_UNSUPPORTED, "%s: FFX_RENDER_AMBIENT is served by ffx_render_fwd[_filtered] only", what_); \
     if ((flags_) & FFX_RENDER_LIGHTS_DIRECTIONAL) \
       FFX_FAIL(FFX_ERR_UNSUPPORTED, "%s: FFX_RENDER_LIGHTS_DIRECTIONAL is served by ffx_render_fwd[_filtered] only", what_); \
+    FFX_NO_EMITTER_GRAD(flags_, what_); \
   } while (0)
 // FFX_RENDER_LIGHTS (include/ffx.h).  What a forward refuses about the bits before it launches anything: FFX_OK, or the error
 static int lights_check(int flags, const float *shape_albedo, const char *what) {
@@ -6074,6 +6177,7 @@ static int render_lights(const void *bvh, const ffx_bvh_info *info, const ffx_sc
 static int render_fwd_entry(const void *bvh, const ffx_bvh_info *info, const ffx_scene_desc *sd, const float *shape_albedo, const float *tex, int spp, uint32_t seed,
                             int img_fp16, void *img, ffx_stream s, void *scratch) {
   const char *what = scratch ? "render_fwd_filtered" : "render_fwd";
+  FFX_NO_EMITTER_GRAD(img_fp16, what);
   if (const int rc = lights_check(img_fp16, shape_albedo, what)) return rc;
   FFX_NO_APPEARANCE(img_fp16, what);
   const int lights = img_fp16 & (FFX_RENDER_LIGHTS_MASK | FFX_RENDER_AMBIENT | FFX_RENDER_LIGHTS_DIRECTIONAL);
@@ -6169,6 +6273,7 @@ int ffx_render_bwd_cached(const ffx_scene_desc *sd, const float *shape_albedo, c
   FFX_NO_APPEARANCE(img_fp16, "render_bwd_cached");
   FFX_NO_TANGENT(img_fp16, "render_bwd_cached");
   FFX_NO_AOV(img_fp16, "render_bwd_cached");
+  FFX_NO_EMITTER_GRAD(img_fp16, "render_bwd_cached");
   return render_bwd_cached_impl(sd, shape_albedo, cache, spp, gimg, gtex, img, img_fp16, dot_out, nullptr, 0.f, s);
 }
 // K9 under an L1 loss against a target image (include/ffx.h): the loss launch (ffx_l1_value_grad) and its gradient image are folded into the scatter
@@ -6430,6 +6535,49 @@ static int render_bwd_leaves(const void *bvh, const ffx_bvh_info *info, const ff
   }
   return render_bwd_appearance(bvh, info, sd, shape_albedo, spp, seed, flags, gimg, gtex, s, rf_scratch);
 }
+// FFX_RENDER_EMITTER_GRAD (include/ffx.h), behind the entry points' own refusals (the lights' bits beside a GRAD bit among them): the texture
+// part — the launches of the call without the bit, which ignore the lights' bits and leave G = gimg / weight in the filtered film's scratch when the scene has
+// a projector — then k_lights_bwd into the workspace behind the result block and k_lights_grad_reduce into the block.  `what`: the entry point's name
+static int render_bwd_emitters(const void *bvh, const ffx_bvh_info *info, const ffx_scene_desc *sd, const float *shape_albedo, int spp, uint32_t seed, int flags,
+                               const float *gimg, float *gtex, ffx_stream s, void *rf_scratch) {
+  const char *what = rf_scratch ? "render_bwd_filtered" : "render_bwd";
+  if (flags & (FFX_RENDER_GRAD_APPEARANCE | FFX_RENDER_GRAD_MATERIAL | FFX_RENDER_GRAD_PRB))
+    FFX_FAIL(FFX_ERR_UNSUPPORTED, "%s: FFX_RENDER_EMITTER_GRAD is not served together with FFX_RENDER_GRAD_APPEARANCE, FFX_RENDER_GRAD_MATERIAL or FFX_RENDER_GRAD_PRB", what);
+  const int n = (flags & FFX_RENDER_LIGHTS_MASK) >> FFX_RENDER_LIGHTS_SHIFT;
+  const bool amb = (flags & FFX_RENDER_AMBIENT) != 0;
+  if (n == 0 && !amb) FFX_FAIL(FFX_ERR_ARG, "%s: FFX_RENDER_EMITTER_GRAD needs FFX_RENDER_LIGHTS(n >= 1) or FFX_RENDER_AMBIENT: there is nothing to differentiate", what);
+  if (n == 0 && (flags & FFX_RENDER_LIGHTS_DIRECTIONAL))
+    FFX_FAIL(FFX_ERR_ARG, "%s: FFX_RENDER_LIGHTS_DIRECTIONAL needs FFX_RENDER_LIGHTS(n >= 1): the bit says what the table may hold", what);
+  if (n > FFX_RENDER_MAX_LIGHTS) FFX_FAIL(FFX_ERR_ARG, "%s: FFX_RENDER_LIGHTS(%d): at most %d extra emitters", what, n, FFX_RENDER_MAX_LIGHTS);
+  if (!shape_albedo) FFX_FAIL(FFX_ERR_ARG, "%s: FFX_RENDER_EMITTER_GRAD needs the device buffer [material table | lights | ambient] (shape_albedo is NULL)", what);
+  const int plain = flags & ~(FFX_RENDER_EMITTER_GRAD | FFX_RENDER_LIGHTS_MASK | FFX_RENDER_AMBIENT | FFX_RENDER_LIGHTS_DIRECTIONAL); // (the call without the bits)
+  if (const int rc = render_bwd_impl(bvh, info, sd, shape_albedo, spp, seed, plain, gimg, gtex, s, rf_scratch)) return rc;
+  RenderSetup r;
+  if (const int rc = render_setup("render_bwd", bvh, info, sd, shape_albedo, spp, seed, flags & FFX_RENDER_PATH_MASK, rf_scratch, r)) return rc;
+  if (r.n_pix >= (1L << 31)) FFX_FAIL(FFX_ERR_UNSUPPORTED, "%s: FFX_RENDER_EMITTER_GRAD: more than 2^31 pixels", what);
+  if (sd->n_shapes < 0) FFX_FAIL(FFX_ERR_ARG, "%s: n_shapes < 0", what);
+  const long n_tex = (long)sd->proj.tex_w * sd->proj.tex_h * sd->proj.tex_channels;
+  if (n_tex < 0) FFX_FAIL(FFX_ERR_ARG, "%s: bad projector texture size", what);
+  const float *table = shape_albedo + (size_t)sd->n_shapes * (size_t)r.c.mat_stride; // (render_lights')
+  float *block = gtex + n_tex, *slots = block + FFX_RENDER_EMITTER_GRAD_BLOCK_FLOATS;
+  const PathArgs pa = path_args(r);
+  const hipStream_t st = (hipStream_t)s;
+  const float *gsrc = gimg;
+  if (rf_scratch) { // G = gimg / weight: the texture part left it in the scratch, or (no projector) launched nothing and it is formed here
+    gsrc = (const float *)(sd->proj.enabled ? rf_G_area(rf_scratch, r.n_pix)
+                                            : rf_G(r, gimg, rf_scratch, st, "render_bwd_filtered (emitters)/weights", "render_bwd_filtered (emitters)/gather"));
+    if (!gsrc) return FFX_ERR_LAUNCH;
+  }
+  const size_t stack = path_stack_bytes(info); // (dynamic LDS: the lanes' traversal stacks, then their 3 n record sums)
+  dispatch_rf_mat(rf_scratch != nullptr, amb, [&](auto rf, auto am) {
+    hipLaunchKernelGGL((k_lights_bwd<decltype(rf)::value, decltype(am)::value>), dim3((unsigned)r.n_pix), dim3(64), stack + (size_t)3 * n * 64 * sizeof(float), st, r.c, pa,
+                       table, n, gsrc, slots, (int)(stack / sizeof(int)));
+  });
+  FFX_CHECK_LAUNCH(rf_scratch ? "render_bwd_filtered (emitters)" : "render_bwd (emitters)");
+  hipLaunchKernelGGL(k_lights_grad_reduce, dim3(FFX_RENDER_EMITTER_GRAD_BLOCK_FLOATS), dim3(FFX_EG_REDUCE_THREADS), 0, st, (const float *)slots, (int)r.n_pix, n, (int)amb, block);
+  FFX_CHECK_LAUNCH(rf_scratch ? "render_bwd_filtered (emitters)/reduce" : "render_bwd (emitters)/reduce");
+  return FFX_OK;
+}
 
 int ffx_render_bwd(const void *bvh, const ffx_bvh_info *info, const ffx_scene_desc *sd, const float *shape_albedo, int spp, uint32_t seed, int flags,
                    const float *gimg, float *gtex, ffx_stream s) {
@@ -6442,6 +6590,7 @@ int ffx_render_bwd(const void *bvh, const ffx_bvh_info *info, const ffx_scene_de
     FFX_FAIL(FFX_ERR_UNSUPPORTED, "render_bwd: FFX_RENDER_AMBIENT is not served together with a FFX_RENDER_GRAD_* bit (the constant emitter is not differentiated)");
   if ((flags & FFX_RENDER_LIGHTS_DIRECTIONAL) && (flags & (FFX_RENDER_GRAD_APPEARANCE | FFX_RENDER_GRAD_MATERIAL | FFX_RENDER_GRAD_PRB)))
     FFX_FAIL(FFX_ERR_UNSUPPORTED, "render_bwd: FFX_RENDER_LIGHTS_DIRECTIONAL is not served together with a FFX_RENDER_GRAD_* bit (the extra emitters are not differentiated)");
+  if (flags & FFX_RENDER_EMITTER_GRAD) return render_bwd_emitters(bvh, info, sd, shape_albedo, spp, seed, flags, gimg, gtex, s, nullptr);
   flags &= ~(FFX_RENDER_LIGHTS_MASK | FFX_RENDER_AMBIENT | FFX_RENDER_LIGHTS_DIRECTIONAL); // (the texture's adjoint sees neither the extra emitters nor the constant one: the bits are ignored, the tail behind the table is not read)
   if (flags & FFX_RENDER_GRAD_APPEARANCE) return render_bwd_leaves(bvh, info, sd, shape_albedo, spp, seed, flags, gimg, gtex, s, nullptr);
   return render_bwd_impl(bvh, info, sd, shape_albedo, spp, seed, flags, gimg, gtex, s, nullptr);
@@ -6533,6 +6682,7 @@ int ffx_render_bwd_filtered(const void *bvh, const ffx_bvh_info *info, const ffx
     FFX_FAIL(FFX_ERR_UNSUPPORTED, "render_bwd_filtered: FFX_RENDER_AMBIENT is not served together with a FFX_RENDER_GRAD_* bit (the constant emitter is not differentiated)");
   if ((flags & FFX_RENDER_LIGHTS_DIRECTIONAL) && (flags & (FFX_RENDER_GRAD_APPEARANCE | FFX_RENDER_GRAD_MATERIAL | FFX_RENDER_GRAD_PRB)))
     FFX_FAIL(FFX_ERR_UNSUPPORTED, "render_bwd_filtered: FFX_RENDER_LIGHTS_DIRECTIONAL is not served together with a FFX_RENDER_GRAD_* bit (the extra emitters are not differentiated)");
+  if (flags & FFX_RENDER_EMITTER_GRAD) return render_bwd_emitters(bvh, info, sd, shape_albedo, spp, seed, flags, gimg, gtex, s, scratch);
   flags &= ~(FFX_RENDER_LIGHTS_MASK | FFX_RENDER_AMBIENT | FFX_RENDER_LIGHTS_DIRECTIONAL); // (the texture's adjoint sees neither the extra emitters nor the constant one: the bits are ignored, the tail behind the table is not read)
   if (flags & FFX_RENDER_GRAD_APPEARANCE) return render_bwd_leaves(bvh, info, sd, shape_albedo, spp, seed, flags, gimg, gtex, s, scratch);
   return render_bwd_impl(bvh, info, sd, shape_albedo, spp, seed, flags, gimg, gtex, s, scratch);

@@ -432,6 +432,11 @@ class SceneParameters:
         # to these leaves until the key is assigned again
         self._leaf_keys = frozenset()
         self._leaves = {}
+        # the extra emitters' powers — `<id>.intensity.value` of every extra point light or spot, `<id>.irradiance.value` of every directional
+        # emitter, `<id>.radiance.value` of the constant emitter — and those of them assigned a tensor that requires grad: a registry of its own, so that
+        # everything keyed off the appearance leaves above (mi.render's appearance route, mi.render_forward's keys and refusals) stays what it was
+        self._emitter_leaf_keys = frozenset()
+        self._emitter_leaves = {}
 
     def keys(self):
         return self._d.keys()
@@ -464,12 +469,13 @@ class SceneParameters:
         self._dirty.add(k)
         if k == "tex.data":
             self._scene._note_texture(v)
-        elif k in self._leaf_keys:
+        elif k in self._leaf_keys or k in self._emitter_leaf_keys:
+            leaves = self._leaves if k in self._leaf_keys else self._emitter_leaves
             t = v.t if isinstance(v, _ArrayBase) else v
             if isinstance(t, torch.Tensor) and t.requires_grad:
-                self._leaves[k] = t
+                leaves[k] = t
             else:
-                self._leaves.pop(k, None)
+                leaves.pop(k, None)
 
     def _init(self, k, v):
         self._d[k] = v
@@ -656,6 +662,8 @@ class Scene:
         bsdf += [m + ".brdf_0.eta" for m, ms in mats.items() if ms[0].bsdf is not None]
         p._leaf_keys = frozenset([m + ".brdf_0.base_color.value" for m in mats] + [n + ".brdf_0.base_color.data" for n, _ in self._base_tex]
                                  + ([d.spot.name + ".intensity.value"] if d.spot is not None else []) + bsdf)
+        p._emitter_leaf_keys = frozenset([l.name + (".irradiance.value" if l.kind == "directional" else ".intensity.value") for l in d.lights]
+                                         + ([amb.name + ".radiance.value"] if amb is not None else []))
         # which key last wrote each principled material's eta (`<mat>.brdf_0.eta` -> its own key or the material's `specular`): a specular leaf and an
         # eta leaf get d loss / d eta only while the row's eta is theirs (specular wins within one update, as _apply orders it)
         self._eta_src = {}
@@ -1034,6 +1042,9 @@ class Scene:
                 if values[drow, 0] > 0.0:
                     self._warn_spec_trans(key)
         p._dirty = set()
+        if p._emitter_leaves:
+            for k in sp.keys:
+                p._emitter_leaves.pop(k, None)
         if p._leaves:
             for k in sp.keys:
                 p._leaves.pop(k, None)
@@ -1362,6 +1373,10 @@ def render(scene: Scene, params: SceneParameters = None, spp: int = 16, seed: in
     spec_trans, spec_tint, sheen, sheen_tint, flatness, clearcoat, clearcoat_gloss}.value`, `.specular`, `.eta`) when such a tensor was assigned to
     them (each BSDF leaf's gradient is summed over the material's shapes).  Those leaves need direct light (max_depth 2) or the `prb`
     integrator, which carries them through the bounces; `path` with max_depth > 2 refuses them.
+    Differentiable, too, w.r.t. the extra emitters' powers: `<id>.intensity.value` of a further point light or spot, `<id>.irradiance.value`
+    of a directional emitter and `<id>.radiance.value` of the constant emitter, when a tensor that requires grad was assigned to them — at direct light,
+    under `path` and under `prb` (the image is exactly linear in them: the gradient is the derivative of the fixed-seed image, roulette included), on
+    either film, together with `tex.data`.  Not together with the appearance and BSDF leaves above, which stay refused on a scene with extra emitters.
     integrator (mi.load_dict): None or max_depth 2 renders direct light at the primary hit, as always; deeper paths run on the caller's stream."""
     if sensor != 0:
         raise NotImplementedError("only sensor 0 renders; further sensors are projector proxies")
@@ -1378,6 +1393,8 @@ def render(scene: Scene, params: SceneParameters = None, spp: int = 16, seed: in
         return _render_aov(scene, params, spp, seed, fp16, integrator)
     if scene._params._leaves and torch.is_grad_enabled():
         return _render_appearance(scene, spp, seed, fp16, integrator)
+    if scene._params._emitter_leaves and torch.is_grad_enabled():
+        return _render_emitters(scene, spp, seed, integrator)
     sd, tex_in, tex = _scene_texture(scene, spp)
     if tex is None:
         tex = torch.zeros((1, 1, 1), device=scene.device)
@@ -1431,7 +1448,7 @@ def _render_aov(scene, params, spp, seed, fp16, integrator):
     sd, _, tex = _scene_texture(scene, spp)
     if tex is None:
         tex = torch.zeros((1, 1, 1), device=scene.device)
-    grad = inner is not None and torch.is_grad_enabled() and (tex.requires_grad or bool(scene._params._leaves))
+    grad = inner is not None and torch.is_grad_enabled() and (tex.requires_grad or bool(scene._params._leaves) or bool(scene._params._emitter_leaves))
     rgb = render(scene, params, spp, seed, 0, False, inner).torch() if grad else None
     md, rr = (inner.max_depth, inner.rr_depth) if inner is not None and not grad else (2, 5)
     img, block = scene.geom.render_aov(sd, scene.materials_arg(sd), Fn._tex3(tex.detach()), int(spp), int(seed), max_depth=md, rr_depth=rr,
@@ -1671,3 +1688,70 @@ def _render_appearance(scene, spp, seed, fp16, integrator):
         leaves.append(leaf)
     depths = (2, 5) if integrator is None else (int(integrator.max_depth), int(integrator.rr_depth))
     return TensorXf(_AppearanceRender.apply(tex, scene, sd, scene.materials_arg(sd), int(spp), int(seed), bool(fp16), kinds, depths, *leaves))
+
+
+class _EmitterRender(torch.autograd.Function):
+    """mi.render with emitter leaves: the plain forward with the packed table; the backward is ONE ffx_render_bwd[_filtered] call with
+    FFX_RENDER_EMITTER_GRAD, which yields the texture gradient and the emitters' block together.  rows: per leaf the record of the table it drives, None
+    for the constant emitter's radiance"""
+
+    @staticmethod
+    def forward(ctx, tex, scene, sd, mats, spp, seed, lights, ambient, sun, rows, depths, *leaves):
+        geom = scene.geom
+        t = Fn._tex3(tex.detach())
+        ctx.geom, ctx.sd, ctx.spp, ctx.seed, ctx.rows, ctx.depths = geom, sd, spp, seed, rows, depths
+        ctx.tex_shape = tex.shape
+        ctx.mats = mats.clone() if mats is not None else None  # (the scene's table is rewritten in place by the next randomisation)
+        ctx.keep = [bt for _, bt in scene._base_tex]  # (the description points at them)
+        ctx.lights, ctx.ambient, ctx.sun = lights, ambient, sun
+        ctx.leaf_meta = [(x.shape, x.dtype, x.device) for x in leaves]
+        ctx.pose_version = geom.version
+        return geom.render_fwd(sd, mats, t, spp, seed, False, max_depth=depths[0], rr_depth=depths[1], lights=lights, ambient=ambient, lights_directional=sun)
+
+    @staticmethod
+    def backward(ctx, g):
+        if ctx.geom.version != ctx.pose_version:
+            raise RuntimeError("mi.render: the scene was updated between the render and its backward — the appearance adjoint re-traces the render's pose: "
+                               "call backward before the next params.update()")
+        gtex, eg = ctx.geom.render_bwd(ctx.sd, ctx.mats, ctx.spp, ctx.seed, g.float().contiguous(), max_depth=ctx.depths[0], rr_depth=ctx.depths[1],
+                                       lights=ctx.lights, ambient=ctx.ambient, lights_directional=ctx.sun, emitters=True)
+        grads = []
+        for row, (shape, dtype, device) in zip(ctx.rows, ctx.leaf_meta):
+            v = eg.ambient if row is None else eg.lights[row]
+            n = 1
+            for e in shape:
+                n *= int(e)
+            v = v.sum().reshape(shape) if n == 1 else v.reshape(shape)  # (a scalar assigned to a colour is broadcast to its three channels)
+            grads.append(v.to(device=device, dtype=dtype))
+        gt = gtex.reshape(ctx.tex_shape) if ctx.needs_input_grad[0] else None
+        return (gt, None, None, None, None, None, None, None, None, None, None, *grads)
+
+
+def _render_emitters(scene, spp, seed, integrator):
+    """mi.render while emitter leaves are assigned and grad is enabled (no appearance leaf: that route's refusal comes first): through _EmitterRender on
+    the caller's stream.  The table and the ambient record take the leaves' values as they are now"""
+    if ops.deterministic_mode():
+        raise ValueError("mi.render: the gradients of the extra emitters' powers have no deterministic adjoint (FFX_DETERMINISTIC=1).  The scene holds "
+                         "parameters that require grad: " + ", ".join(sorted(scene._params._emitter_leaves)))
+    sd, _, tex = _scene_texture(scene, spp)
+    if tex is None:
+        tex = torch.zeros((1, 1, 1), device=scene.device)
+    lights = scene.lights_table().clone() if _has_lights(scene) else None
+    ambient = scene.ambient_record().clone() if _has_ambient(scene) else None
+    index = {l.name: k for k, l in enumerate(scene.data.lights)}
+    rows, leaves = [], []
+    for k, leaf in scene._params._emitter_leaves.items():
+        name = k.rsplit(".", 2)[0]
+        value = leaf.detach().to(device=scene.device, dtype=torch.float32).reshape(-1)
+        if value.numel() not in (1, 3):
+            raise ValueError(f"mi.render: {k} must hold one or three floats, got {value.numel()}")
+        if name == scene._ambient_name and k.endswith(".radiance.value"):
+            ambient[:] = value
+            rows.append(None)
+        else:
+            lights[index[name], 16:19] = value
+            rows.append(index[name])
+        leaves.append(leaf)
+    depths = (2, 5) if integrator is None else (max(int(integrator.max_depth), 2), int(integrator.rr_depth))
+    sun = lights is not None and scene.lights_directional()
+    return TensorXf(_EmitterRender.apply(tex, scene, sd, scene.materials_arg(sd), int(spp), int(seed), lights, ambient, sun, rows, depths, *leaves))

@@ -568,7 +568,8 @@ def _no_path(max_depth, what):
 def pack_lights(lights):
     """the table of a render's extra emitters (include/ffx.h FFX_RENDER_LIGHTS): scenes.LightData entries -> [n, 24] float32 on the host
     (to_world 0..15 row-major, intensity 16..18, cutoff_deg 19, beam_width_deg 20, type 21: 0 point / 1 spot, 22..23 zero; a directional emitter,
-    DESIGN.md 4.9: to_world, its irradiance in 16..18, type 2, zeros elsewhere — such a table is rendered with lights_directional=True)"""
+    DESIGN.md 4.9: to_world, its irradiance in 16..18, type 2, zeros elsewhere — such a table is rendered with lights_directional=True).  Floats 16..18 are
+    what render_bwd(emitters=True) differentiates with respect to: row k of EmitterGrad.lights belongs to record k"""
     lights = list(lights)
     if len(lights) > _abi.RENDER_MAX_LIGHTS:
         raise ValueError(f"at most {_abi.RENDER_MAX_LIGHTS} extra emitters, got {len(lights)}")
@@ -633,6 +634,14 @@ def appearance_blocks(sd, material, buf, start):
         o += n
     mat = views.pop() if material else None
     return AppearanceGrad(views[0], views[1], views[2:], mat), o - int(start)
+
+
+class EmitterGrad(NamedTuple):
+    """what render_bwd(..., emitters=True) adds to the texture gradient (FFX_RENDER_EMITTER_GRAD): lights [n, 3] — d loss / d (the RGB power
+    of record k of the `lights` table: floats 16..18, a point light's or spot's intensity, a directional emitter's irradiance) — and ambient [3], d loss /
+    d (the constant emitter's radiance), None for a call without `ambient`"""
+    lights: torch.Tensor
+    ambient: torch.Tensor = None
 
 
 # what a render entry point does about a film with a reconstruction filter (sd.rfilter): DeviceGeometry._launch
@@ -1214,7 +1223,7 @@ class DeviceGeometry:
                      _dev(gimg, name="gimg"), int(part), int(scale_log2), C.c_void_p(acc.data_ptr()))
 
     def render_bwd(self, sd, albedo, spp, seed, gimg, deterministic=None, max_depth=2, rr_depth=5, appearance=False, tex=None, material=False, lights=None,
-                   ambient=None, lights_directional=False):
+                   ambient=None, lights_directional=False, emitters=False):
         """the re-tracing adjoint.  deterministic (default: FFX_DETERMINISTIC=1 in the environment): ffx_render_bwd_det — bitwise
         reproducible accumulation (64-bit fixed point instead of float atomics; two re-traces and one host synchronisation).
         max_depth > 2: the path integrator's adjoint — replays render_fwd's paths of the same max_depth, rr_depth, spp and seed (float atomics only).
@@ -1226,13 +1235,21 @@ class DeviceGeometry:
         lights: the forward's extra emitters.  They do not depend on the projector's texture: gtex is that of the call without them (the float-atomic
         adjoint is handed the forward's bits and ignores them; the deterministic one is called without).  Not with appearance=True.
         ambient: the forward's constant emitter — as lights: its bit is handed on and ignored.  Not with appearance=True.
-        lights_directional: the forward's — handed on with the lights' bits and ignored."""
+        lights_directional: the forward's — handed on with the lights' bits and ignored.
+        emitters=True (FFX_RENDER_EMITTER_GRAD): -> (gtex, EmitterGrad) — also d loss / d (the RGB power of every record of `lights`) and
+        d loss / d (the radiance of `ambient`): the exact derivative of the fixed-seed image of render_fwd with the same lights, ambient, max_depth,
+        rr_depth, spp and seed.  Needs lights= and / or ambient=; the table then travels and is read.  No atomics: two calls give the same EmitterGrad.
+        Direct light and max_depth > 2, both films; not with appearance=True, no deterministic adjoint."""
         if ambient is not None and appearance:
             raise NotImplementedError("render_bwd(appearance=True): the constant emitter (ambient=) is not differentiated")
         if lights is not None and lights.numel() and appearance:
             raise NotImplementedError("render_bwd(appearance=True): extra emitters (lights=) are not differentiated")
         if material and not appearance:
             raise ValueError("render_bwd(material=True) needs appearance=True (the material block extends the appearance adjoint)")
+        if emitters and appearance:
+            raise NotImplementedError("render_bwd(emitters=True): not served together with appearance=True")
+        if emitters:
+            return self._render_bwd_emitters(sd, albedo, spp, seed, gimg, deterministic, max_depth, rr_depth, lights, ambient, lights_directional)
         if appearance:
             if max_depth != 2:
                 path_flags(max_depth)  # (the range check's message first)
@@ -1270,6 +1287,37 @@ class DeviceGeometry:
             flags |= _abi.RENDER_AMBIENT
         self._launch_bwd(blob, sd, mats_arg, spp, seed, flags, _dev(gimg, name="gimg"), _dev(gtex))
         return gtex
+
+    def _render_bwd_emitters(self, sd, albedo, spp, seed, gimg, deterministic, max_depth, rr_depth, lights, ambient, lights_directional, out=None):
+        """the call behind render_bwd(emitters=True): [table | lights | ambient] travels as in the forward; gtex, the result block and the workspace in one
+        buffer (include/ffx.h FFX_RENDER_EMITTER_GRAD).  out: that buffer, the caller's (float32, on the device; its gtex part is zeroed here)"""
+        if (lights is None or lights.numel() == 0) and ambient is None:
+            raise ValueError("render_bwd(emitters=True) needs lights= and / or ambient=: there is nothing to differentiate")
+        path = path_flags(max_depth, rr_depth) if max_depth != 2 else 0
+        if deterministic is None:
+            deterministic = deterministic_mode()
+        if deterministic:
+            raise ValueError("render_bwd(emitters=True) has no deterministic adjoint (FFX_DETERMINISTIC / deterministic=True)")
+        H, W = sd.cam.height, sd.cam.width
+        if gimg.numel() < H * W * 3:
+            raise ValueError("gimg must hold [H, W, 3] floats")
+        n_tex = sd.proj.tex_h * sd.proj.tex_w * sd.proj.tex_channels
+        mats_arg = _check_materials(sd, albedo)
+        mats_arg, lbits, _keep = self._with_lights(sd, albedo, mats_arg, lights, "render_bwd(emitters=True)", ambient, lights_directional=lights_directional)
+        n = (lbits & _abi.RENDER_LIGHTS_MASK) >> _abi.RENDER_LIGHTS_SHIFT
+        # (gtex is accumulated into: zeros; the block and the workspace are written by the call)
+        n_out = n_tex + _abi.emitter_grad_floats(W, H)
+        if out is None:
+            out = torch.empty(n_out, dtype=torch.float32, device=self.device)
+        elif out.dtype != torch.float32 or out.dim() != 1 or out.numel() < n_out or not out.is_contiguous():
+            raise ValueError(f"render_bwd(emitters=True): out must be a contiguous float32 vector of at least {n_out} floats")
+        out[:n_tex].zero_()
+        blob = self.blob
+        flags = (path if path else self._apex_flag(apex_key(sd))) | lbits | _abi.RENDER_EMITTER_GRAD
+        self._launch_bwd(blob, sd, mats_arg, spp, seed, flags, _dev(gimg, name="gimg"), _dev(out))
+        block = out[n_tex:n_tex + _abi.RENDER_EMITTER_GRAD_BLOCK_FLOATS].view(_abi.RENDER_MAX_LIGHTS + 1, 3)
+        return (out[:n_tex].view(sd.proj.tex_h, sd.proj.tex_w, sd.proj.tex_channels),
+                EmitterGrad(block[:n].clone(), block[_abi.RENDER_MAX_LIGHTS].clone() if ambient is not None else None))
 
     def render_bwd_prb(self, sd, albedo, spp, seed, gimg, tex, max_depth, rr_depth=5, material=False, deterministic=None):
         """path replay backpropagation (Mitsuba's `prb`, FFX_RENDER_GRAD_PRB): -> (gtex, AppearanceGrad) of a render_fwd with the same

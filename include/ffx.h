@@ -848,8 +848,8 @@ int ffx_det_finish(const void *acc /*[dev] int64 [n]*/, int scale_log2, size_t n
  *            averaged like the rest [EXT Mitsuba's aov does the same]; they are exact at 1 spp.  The path bits choose the image only: the block always
  *            describes the primary hit.
  * Written by further launches on the same stream (the gaussian film: one pass over its scratch per three channels, the scratch keeps its size).  No
- * atomics: two calls give the same bits.  FFX_ERR_UNSUPPORTED together with FFX_RENDER_FP16, FFX_RENDER_TANGENT or a FFX_RENDER_GRAD_* bit and on every
- * other render entry point; FFX_ERR_ARG without a material table (shape_albedo NULL and no rows in sd->mat_h).  The oracle ignores the bit. */
+ * atomics: two calls give the same bits.  FFX_ERR_UNSUPPORTED together with FFX_RENDER_FP16, FFX_RENDER_TANGENT, FFX_RENDER_GRAD_APPEARANCE,
+ * FFX_RENDER_GRAD_MATERIAL or FFX_RENDER_GRAD_PRB and on every other render entry point; FFX_ERR_ARG without a material table (shape_albedo NULL and no rows in sd->mat_h).  The oracle ignores the bit. */
 #define FFX_RENDER_AOV 0x100000
 #define FFX_RENDER_AOV_FLOATS 17
 /* Extra emitters: FFX_RENDER_LIGHTS(n), n = 1 .. FFX_RENDER_MAX_LIGHTS, in the img_fp16 word of ffx_render_fwd / ffx_render_fwd_filtered adds n
@@ -869,9 +869,10 @@ int ffx_det_finish(const void *acc /*[dev] int64 [n]*/, int scale_log2, size_t n
  *            and every path vertex under FFX_RENDER_PATH; the spot's falloff, shadow ray and BSDF rows.  With FFX_RENDER_AOV the block is that of the call
  *            without the bits.
  * Written by further launches on the same stream behind those of the main image; no atomics (two calls give the same bits), no host synchronisation.
- * FFX_ERR_UNSUPPORTED together with FFX_RENDER_FP16, FFX_RENDER_TANGENT or a FFX_RENDER_GRAD_* bit and on every other render entry point — except that
- * ffx_render_bwd / ffx_render_bwd_filtered without a FFX_RENDER_GRAD_* bit accept and ignore the bits (the extra emitters do not depend on the projector's
- * texture: gtex is that of the call without them, and the tail is not read), so a caller can hand the forward's flags to the adjoint.  The oracle does not
+ * FFX_ERR_UNSUPPORTED together with FFX_RENDER_FP16, FFX_RENDER_TANGENT, FFX_RENDER_GRAD_APPEARANCE, FFX_RENDER_GRAD_MATERIAL or FFX_RENDER_GRAD_PRB and on
+ * every other render entry point — except that ffx_render_bwd / ffx_render_bwd_filtered without one of those three GRAD bits accept the bits: without
+ * FFX_RENDER_EMITTER_GRAD they ignore them (the extra emitters do not depend on the projector's texture: gtex is that of the call without them, and the tail
+ * is not read), so a caller can hand the forward's flags to the adjoint; with it they differentiate with respect to the records' powers (below).  The oracle does not
  * know the bits: never pass them to it. */
 #define FFX_RENDER_MAX_LIGHTS 8
 #define FFX_RENDER_LIGHTS_SHIFT 21
@@ -893,9 +894,9 @@ int ffx_det_finish(const void *acc /*[dev] int64 [n]*/, int scale_log2, size_t n
  * FFX_RENDER_LIGHTS_DIRECTIONAL in the img_fp16 word of ffx_render_fwd / ffx_render_fwd_filtered says that the table may hold such records (the host does
  * not read the device table) and selects the kernels that know them; they serve all three types, and the constant emitter of FFX_RENDER_AMBIENT, in one
  * walk per sample.  Without the bit nothing changes: a record of type 2 is then the caller's error.  FFX_ERR_ARG without FFX_RENDER_LIGHTS(n >= 1).
- * Refused and accepted where FFX_RENDER_LIGHTS is: FFX_ERR_UNSUPPORTED together with FFX_RENDER_FP16, FFX_RENDER_TANGENT or a FFX_RENDER_GRAD_* bit and on
- * every other render entry point; accepted with FFX_RENDER_PATH, FFX_RENDER_AOV and FFX_RENDER_AMBIENT; accepted and ignored by ffx_render_bwd /
- * ffx_render_bwd_filtered without a FFX_RENDER_GRAD_* bit.  The oracle does not know the bit: never pass it to it. */
+ * Refused and accepted where FFX_RENDER_LIGHTS is: FFX_ERR_UNSUPPORTED together with FFX_RENDER_FP16, FFX_RENDER_TANGENT, FFX_RENDER_GRAD_APPEARANCE,
+ * FFX_RENDER_GRAD_MATERIAL or FFX_RENDER_GRAD_PRB and on every other render entry point; accepted with FFX_RENDER_PATH, FFX_RENDER_AOV and FFX_RENDER_AMBIENT;
+ * accepted by ffx_render_bwd / ffx_render_bwd_filtered without one of those three GRAD bits (ignored without FFX_RENDER_EMITTER_GRAD, read with it).  The oracle does not know the bit: never pass it to it. */
 #define FFX_LIGHT_DIRECTIONAL 2
 #define FFX_RENDER_LIGHTS_DIRECTIONAL 0x4000000
 /* The constant emitter — ambient light, Mitsuba's <emitter type="constant">: FFX_RENDER_AMBIENT in the img_fp16 word of ffx_render_fwd /
@@ -910,11 +911,34 @@ int ffx_det_finish(const void *acc /*[dev] int64 [n]*/, int scale_log2, size_t n
  *            adds +0.0: the image of the call without the bit, bit for bit.  With FFX_RENDER_AOV the block is that of the call without the bit.
  * Served by the extra emitters' pass (one walk per sample for the lights and the constant emitter together): the same stream, no atomics, no host
  * synchronisation.  Accepted with FFX_RENDER_PATH, FFX_RENDER_LIGHTS(n) and FFX_RENDER_AOV.  FFX_ERR_UNSUPPORTED together with FFX_RENDER_FP16,
- * FFX_RENDER_TANGENT or a FFX_RENDER_GRAD_* bit and on every other render entry point — except that ffx_render_bwd / ffx_render_bwd_filtered without a
- * FFX_RENDER_GRAD_* bit accept and ignore the bit (the constant emitter does not depend on the projector's texture).  The oracle does not know the bit:
+ * FFX_RENDER_TANGENT, FFX_RENDER_GRAD_APPEARANCE, FFX_RENDER_GRAD_MATERIAL or FFX_RENDER_GRAD_PRB and on every other render entry point — except that
+ * ffx_render_bwd / ffx_render_bwd_filtered without one of those three GRAD bits accept the bit: ignored without FFX_RENDER_EMITTER_GRAD (the constant emitter
+ * does not depend on the projector's texture), differentiated with it (below).  The oracle does not know the bit:
  * never pass it to it. */
 #define FFX_RENDER_AMBIENT 0x2000000
 #define FFX_AMBIENT_FLOATS 4
+/* The extra emitters' adjoint: FFX_RENDER_EMITTER_GRAD in the flags word of ffx_render_bwd / ffx_render_bwd_filtered adds d loss / d (the RGB
+ * power of every record of FFX_RENDER_LIGHTS(n) and the radiance of FFX_RENDER_AMBIENT).  An additive extension of ABI 11 (FFX_ABI_VERSION is unchanged; no
+ * struct changes, no new entry point).  The walk, its roulette and its throughput do not depend on any emitter, so the image is exactly linear in these
+ * powers: the block is the exact derivative of the fixed-seed image of ffx_render_fwd[_filtered] with the same bits, spp and seed, roulette included.
+ *   input  — shape_albedo: [material table | n light records | ambient record] exactly as the forward takes it, with FFX_RENDER_LIGHTS(n), optionally
+ *            FFX_RENDER_LIGHTS_DIRECTIONAL, and FFX_RENDER_AMBIENT: with this bit the adjoint no longer ignores those bits, the tail behind the table is
+ *            read (the records' geometry; the powers themselves do not enter).  FFX_ERR_ARG without FFX_RENDER_LIGHTS(n >= 1) or FFX_RENDER_AMBIENT, for
+ *            n > FFX_RENDER_MAX_LIGHTS, for FFX_RENDER_LIGHTS_DIRECTIONAL without a table, and with a NULL shape_albedo.
+ *   output — gtex [tex_h][tex_w][tex_channels] is followed in the same buffer by FFX_RENDER_EMITTER_GRAD_FLOATS(sd) floats: the result block
+ *            [FFX_RENDER_MAX_LIGHTS + 1][3] — row k < n: d loss / d (record k's floats 16..18), the last row: d loss / d radiance; the rows of absent
+ *            records and of an absent FFX_RENDER_AMBIENT are written 0 — and behind it a workspace of [FFX_RENDER_MAX_LIGHTS + 1][3][H x W] floats (one
+ *            slot of partial sums per pixel, every slot written by every call).  The block is WRITTEN, not accumulated into.
+ * gtex is that of the call without the bit, from the same launches; two launches follow them on the same stream (the replay of the lights' pass, one wave per
+ * pixel, and the sum of the slots in a fixed order).  No atomics: two calls give the same block, bit for bit.  No host synchronisation.  Served at direct
+ * light and with FFX_RENDER_PATH(3 .. FFX_RENDER_MAX_DEPTH_LIMIT, rr), on both films.  FFX_ERR_UNSUPPORTED together with FFX_RENDER_GRAD_APPEARANCE,
+ * FFX_RENDER_GRAD_MATERIAL or FFX_RENDER_GRAD_PRB (the refusals of the lights' bits beside those three fire first) and on every other render entry point.
+ * The oracle does not know the bit: never pass it to it. */
+#define FFX_RENDER_EMITTER_GRAD 0x8000000
+#define FFX_RENDER_EMITTER_GRAD_ROWS (FFX_RENDER_MAX_LIGHTS + 1)
+#define FFX_RENDER_EMITTER_GRAD_BLOCK_FLOATS (3 * FFX_RENDER_EMITTER_GRAD_ROWS)
+#define FFX_RENDER_EMITTER_GRAD_FLOATS(sd) \
+  ((size_t)FFX_RENDER_EMITTER_GRAD_BLOCK_FLOATS * ((size_t)(sd)->cam.width * (size_t)(sd)->cam.height + 1))
 /* Writes the apex records (the triangles as seen from a fixed ray origin) of sd's camera and enabled emitters into
  * the blob's apex areas — what every packet render does in front of its kernel unless told FFX_RENDER_APEX_READY.  Only
  * sd->cam.to_world, sd->proj.{enabled,to_world} and sd->spot.{enabled,to_world} are read.  No reference counterpart (Mitsuba
