@@ -2775,6 +2775,32 @@ __global__ void __launch_bounds__(64) k_rf_weights(RfC rfc, int n_pix, int spp, 
 // neighbours': 0.061 ms for 105 MB, the vector L1 thrashing.)
 #define FFX_RFG_WAVES 1 // (one-wave workgroups: the gather of one render runs beside the next render's kernel on the other stream — with four waves and 22 KB of LDS
                         //  per workgroup it waited for room on one compute unit: 1 742 -> 1 913 filtered renders/s; the waves never cooperated anyway)
+// k_rf_gather's staging and 25 additions for the two gathers beside it (k_lights_gather, k_aov_gather): pixel (x0 + lane, y)'s sums into r, g, b, w;
+// seg: the wave's 68 x 5 segment table in LDS
+__device__ __forceinline__ void rf_window_sums(const float4 *__restrict__ part, int W, int H, int x0, int y, int lane, float4 *seg, float &r, float &g, float &b,
+                                               float &w) {
+  r = g = b = w = 0.f;
+  for (int wb = 0; wb < 5; ++wb) {
+    const int qy = y - (wb - 2);
+    if (qy < 0 || qy >= H) continue; // (wave-uniform)
+    __builtin_amdgcn_wave_barrier();
+#pragma unroll
+    for (int k = 0; k < 6; ++k) {
+      const int e = lane + 64 * k; // element (record e / 5, entry e % 5) of the 68 x 5 segment table
+      if (e < 340) {
+        const int rec = e / 5, wa = e - 5 * rec;
+        const int qx = x0 - 2 + rec;
+        seg[e] = (qx >= 0 && qx < W) ? part[((size_t)qy * W + qx) * 25 + (wb * 5 + wa)] : make_float4(0.f, 0.f, 0.f, 0.f);
+      }
+    }
+    __builtin_amdgcn_wave_barrier();
+#pragma unroll
+    for (int wa = 0; wa < 5; ++wa) {
+      const float4 v = seg[(lane + 4 - wa) * 5 + wa];
+      r += v.x; g += v.y; b += v.z; w += v.w;
+    }
+  }
+}
 __global__ void __launch_bounds__(64 * FFX_RFG_WAVES) k_rf_gather(const float4 *__restrict__ part, int W, int H, int fp16, void *__restrict__ img,
                                                                    const float *__restrict__ gimg, float4 *__restrict__ G, float *__restrict__ wsum_out = nullptr) {
   __shared__ float4 s_seg[FFX_RFG_WAVES][68 * 5];
@@ -2782,6 +2808,7 @@ __global__ void __launch_bounds__(64 * FFX_RFG_WAVES) k_rf_gather(const float4 *
   const int x0 = blockIdx.x * 64, y = blockIdx.y * FFX_RFG_WAVES + wv;
   if (y >= H) return; // (wave-uniform; the waves of a workgroup never synchronise)
   float4 *seg = s_seg[wv];
+  // (rf_window_sums, stated here: through the shared piece the benchmark's gaussian gradient steps measured 0.35 % slower, outside the parent's spread)
   float r = 0.f, g = 0.f, b = 0.f, w = 0.f;
   for (int wb = 0; wb < 5; ++wb) {
     const int qy = y - (wb - 2);
@@ -4023,6 +4050,18 @@ __device__ __forceinline__ void lights_derive(const float *__restrict__ table, i
   }
   __syncthreads();
 }
+// lights_at_vertex's last statement, for its directional and its positional arm: record k's term from the arm's factors f, fb without the intensity.  (A
+// macro: stated as a lambda or as a function, one addition of every k_lights_bwd instance comes out with its operands commuted — tools/isa_same.py.)
+// It reads, by these names, lights_at_vertex's ADJ, c, st, beta, L, q, sums, stride, the loop's k and lk and the arm's f and fb
+#define FFX_LIGHT_ADD()                                                                                                     \
+  _Pragma("unroll") for (int ch = 0; ch < 3; ++ch) {                                                                        \
+    if constexpr (ADJ) {                                                                                                    \
+      sums[(3 * k + ch) * stride] += q[ch] * (beta[ch] * (c.mat_stride == 3 ? st.base[ch] * f : st.base[ch] * f + fb));     \
+    } else {                                                                                                                \
+      const float r = lk[FFX_LK_INT + ch] * f, b = lk[FFX_LK_INT + ch] * fb;                                                \
+      L[ch] += beta[ch] * (c.mat_stride == 3 ? st.base[ch] * r : st.base[ch] * r + b);                                      \
+    }                                                                                                                       \
+  }
 // the n lights at one vertex (st, pv: shade_sample<true, ..., !EMIT>'s; d: the ray that found it), weighted by the throughput beta, into L.
 // DIR: a directional record (lights_derive<true>'s) has no position, no falloff and no 1 / d^2; its shadow ray leaves the lifted point along wi, the closing
 // ray's form (path_walk's AMB), on the lane's own stack.
@@ -4046,15 +4085,7 @@ __device__ __forceinline__ void lights_at_vertex(const ShadeK &c, const PathArgs
         float bA = cos_s, bB = 0.f, bT = 0.f;
         row_terms<false>(c, mt, st.shape, pv.textured, st.base, pv.ns, V3(-d.x, -d.y, -d.z), wi, bA, bB, bT);
         const float f = bA * 0.3183098861837907f, fb = bB * 0.3183098861837907f;
-#pragma unroll
-        for (int ch = 0; ch < 3; ++ch) {
-          if constexpr (ADJ) {
-            sums[(3 * k + ch) * stride] += q[ch] * (beta[ch] * (c.mat_stride == 3 ? st.base[ch] * f : st.base[ch] * f + fb));
-          } else {
-            const float r = lk[FFX_LK_INT + ch] * f, b = lk[FFX_LK_INT + ch] * fb;
-            L[ch] += beta[ch] * (c.mat_stride == 3 ? st.base[ch] * r : st.base[ch] * r + b);
-          }
-        }
+        FFX_LIGHT_ADD();
         continue;
       }
     }
@@ -4084,19 +4115,16 @@ __device__ __forceinline__ void lights_at_vertex(const ShadeK &c, const PathArgs
     float bA = cos_s, bB = 0.f, bT = 0.f;
     row_terms<false>(c, mt, st.shape, pv.textured, st.base, pv.ns, V3(-d.x, -d.y, -d.z), wi, bA, bB, bT);
     const float f = fall * bA / d2 * 0.3183098861837907f, fb = fall * bB / d2 * 0.3183098861837907f;
-#pragma unroll
-    for (int ch = 0; ch < 3; ++ch) {
-      if constexpr (ADJ) {
-        sums[(3 * k + ch) * stride] += q[ch] * (beta[ch] * (c.mat_stride == 3 ? st.base[ch] * f : st.base[ch] * f + fb));
-      } else {
-        const float r = lk[FFX_LK_INT + ch] * f, b = lk[FFX_LK_INT + ch] * fb;
-        L[ch] += beta[ch] * (c.mat_stride == 3 ? st.base[ch] * r : st.base[ch] * r + b);
-      }
-    }
+    FFX_LIGHT_ADD();
   }
 }
-// RF: the gaussian film — the pixel's 25 x 4 outgoing sums of the lights' radiance into `part` (k_lights_gather adds them to the image); else img += the pixel's mean
-template <bool RF>
+#undef FFX_LIGHT_ADD
+// The pass's one kernel.  RF: the gaussian film — the sums of the lights' radiance into `part` (k_lights_gather adds them to the image); else img += the pixel's mean.
+// DIR (FFX_RENDER_LIGHTS_DIRECTIONAL, include/ffx.h): the table may hold directional records — all three record types in one walk per sample.
+// AMB (FFX_RENDER_AMBIENT, include/ffx.h): the constant emitter in the same walk — its record (r, g, b, 0) stands behind the n_lights records
+// (n_lights may be 0); every ray of the walk that escapes, and the closing ray at its last vertex (path_walk's AMB), adds throughput x radiance to the
+// sample that the lights' terms go to
+template <bool RF, bool DIR, bool AMB>
 __global__ void __launch_bounds__(64)
     k_lights_fwd(ShadeK c, PathArgs a, const float *__restrict__ lights, int n_lights, float *__restrict__ img, float *__restrict__ part) {
   extern __shared__ int s_dyn[];
@@ -4106,110 +4134,7 @@ __global__ void __launch_bounds__(64)
   const uint32_t pix = blockIdx.x;
   const int W = c.cam.W, px = (int)(pix % (uint32_t)W), py = (int)(pix / (uint32_t)W);
   const int n = n_lights < FFX_RENDER_MAX_LIGHTS ? n_lights : FFX_RENDER_MAX_LIGHTS; // (the host refuses more: s_l holds this many)
-  lights_derive(lights, n, lane, s_l);
-  float acc[4] = {0.f, 0.f, 0.f, 0.f};
-  for (int pass = 0; pass < (a.spp + 63) >> 6; ++pass) {
-    const int s = pass * 64 + lane;
-    const uint32_t idx = pix * (uint32_t)a.spp + (uint32_t)s;
-    float jx, jy;
-    sample_jitter(a.seed_key, idx, jx, jy);
-    float L[3] = {0.f, 0.f, 0.f};
-    if (s < a.spp) {
-      v3 o, d;
-      float nt, ft;
-      cam_ray(c.cam, ((float)px + jx) * c.cam.inv_w, ((float)py + jy) * c.cam.inv_h, o, d, nt, ft);
-      path_walk<false, false, false>(a, idx, o, d, nt, ft, s_dyn + lane, 64, [&](int, const SampleTerms &st, const PathVtxP &pv, v3 dv, const float (&beta)[3]) {
-        lights_at_vertex(kernarg_shade(), a, s_l, n, st, pv, dv, beta, s_dyn + lane, 64, L);
-      });
-    }
-    if (RF) {
-      float gx[5], gy[5];
-      rf_weights(c.rf, jx, gx);
-      rf_weights(c.rf, jy, gy);
-      rf_fold(s_rf, lane, gx, gy, L[0], L[1], L[2], s < a.spp ? 1.f : 0.f, acc);
-    } else {
-      acc[0] += L[0]; acc[1] += L[1]; acc[2] += L[2];
-    }
-  }
-  if (RF) {
-    rf_store(part, pix, lane, acc);
-    return;
-  }
-  const float inv_spp = 1.0f / (float)a.spp;
-  const float m0 = wave_sum_tree(acc[0]) * inv_spp, m1 = wave_sum_tree(acc[1]) * inv_spp, m2 = wave_sum_tree(acc[2]) * inv_spp;
-  if (lane == 0) {
-    float *p = img + (size_t)pix * 3;
-    p[0] += m0; p[1] += m1; p[2] += m2;
-  }
-}
-// FFX_RENDER_AMBIENT (include/ffx.h): k_lights_fwd with the constant emitter in the same walk — its record (r, g, b, 0) stands behind the
-// n_lights records (n_lights may be 0); every ray of the walk that escapes, and the closing ray at its last vertex (path_walk's AMB), adds throughput x
-// radiance to the sample that the lights' terms go to.  A kernel of its own so that k_lights_fwd keeps its machine code (tools/isa_same.py)
-template <bool RF>
-__global__ void __launch_bounds__(64)
-    k_lights_ambient_fwd(ShadeK c, PathArgs a, const float *__restrict__ lights, int n_lights, float *__restrict__ img, float *__restrict__ part) {
-  extern __shared__ int s_dyn[];
-  __shared__ __attribute__((aligned(16))) float s_rf[RF ? FFX_RF_FLOATS : 4];
-  __shared__ float s_l[FFX_RENDER_MAX_LIGHTS * FFX_LK_FLOATS];
-  const int lane = threadIdx.x;
-  const uint32_t pix = blockIdx.x;
-  const int W = c.cam.W, px = (int)(pix % (uint32_t)W), py = (int)(pix / (uint32_t)W);
-  const int n = n_lights < FFX_RENDER_MAX_LIGHTS ? n_lights : FFX_RENDER_MAX_LIGHTS; // (the host refuses more: s_l holds this many)
-  lights_derive(lights, n, lane, s_l);
-  const float *la = lights + (size_t)FFX_LIGHT_FLOATS * n; // (the ambient record, at a wave-uniform address: scalar loads)
-  const float la0 = la[0], la1 = la[1], la2 = la[2];
-  float acc[4] = {0.f, 0.f, 0.f, 0.f};
-  for (int pass = 0; pass < (a.spp + 63) >> 6; ++pass) {
-    const int s = pass * 64 + lane;
-    const uint32_t idx = pix * (uint32_t)a.spp + (uint32_t)s;
-    float jx, jy;
-    sample_jitter(a.seed_key, idx, jx, jy);
-    float L[3] = {0.f, 0.f, 0.f};
-    if (s < a.spp) {
-      v3 o, d;
-      float nt, ft;
-      cam_ray(c.cam, ((float)px + jx) * c.cam.inv_w, ((float)py + jy) * c.cam.inv_h, o, d, nt, ft);
-      path_walk<false, false, false, true>(
-          a, idx, o, d, nt, ft, s_dyn + lane, 64,
-          [&](int, const SampleTerms &st, const PathVtxP &pv, v3 dv, const float (&beta)[3]) {
-            lights_at_vertex(kernarg_shade(), a, s_l, n, st, pv, dv, beta, s_dyn + lane, 64, L);
-          },
-          NoBounce(), [&](const float (&beta)[3]) { L[0] += beta[0] * la0; L[1] += beta[1] * la1; L[2] += beta[2] * la2; });
-    }
-    if (RF) {
-      float gx[5], gy[5];
-      rf_weights(c.rf, jx, gx);
-      rf_weights(c.rf, jy, gy);
-      rf_fold(s_rf, lane, gx, gy, L[0], L[1], L[2], s < a.spp ? 1.f : 0.f, acc);
-    } else {
-      acc[0] += L[0]; acc[1] += L[1]; acc[2] += L[2];
-    }
-  }
-  if (RF) {
-    rf_store(part, pix, lane, acc);
-    return;
-  }
-  const float inv_spp = 1.0f / (float)a.spp;
-  const float m0 = wave_sum_tree(acc[0]) * inv_spp, m1 = wave_sum_tree(acc[1]) * inv_spp, m2 = wave_sum_tree(acc[2]) * inv_spp;
-  if (lane == 0) {
-    float *p = img + (size_t)pix * 3;
-    p[0] += m0; p[1] += m1; p[2] += m2;
-  }
-}
-// FFX_RENDER_LIGHTS_DIRECTIONAL (include/ffx.h): the lights' pass for a table that may hold directional records — all three record types in one
-// walk per sample and, with AMB, the constant emitter in the same walk (k_lights_ambient_fwd's record behind the table).  Kernels of their own so that
-// k_lights_fwd and k_lights_ambient_fwd keep their machine code (tools/isa_same.py)
-template <bool RF, bool AMB>
-__global__ void __launch_bounds__(64)
-    k_lights_dir_fwd(ShadeK c, PathArgs a, const float *__restrict__ lights, int n_lights, float *__restrict__ img, float *__restrict__ part) {
-  extern __shared__ int s_dyn[];
-  __shared__ __attribute__((aligned(16))) float s_rf[RF ? FFX_RF_FLOATS : 4];
-  __shared__ float s_l[FFX_RENDER_MAX_LIGHTS * FFX_LK_FLOATS];
-  const int lane = threadIdx.x;
-  const uint32_t pix = blockIdx.x;
-  const int W = c.cam.W, px = (int)(pix % (uint32_t)W), py = (int)(pix / (uint32_t)W);
-  const int n = n_lights < FFX_RENDER_MAX_LIGHTS ? n_lights : FFX_RENDER_MAX_LIGHTS; // (the host refuses more: s_l holds this many)
-  lights_derive<true>(lights, n, lane, s_l);
+  lights_derive<DIR>(lights, n, lane, s_l);
   float la0 = 0.f, la1 = 0.f, la2 = 0.f;
   if constexpr (AMB) {
     const float *la = lights + (size_t)FFX_LIGHT_FLOATS * n; // (the ambient record, at a wave-uniform address: scalar loads)
@@ -4226,12 +4151,14 @@ __global__ void __launch_bounds__(64)
       v3 o, d;
       float nt, ft;
       cam_ray(c.cam, ((float)px + jx) * c.cam.inv_w, ((float)py + jy) * c.cam.inv_h, o, d, nt, ft);
-      path_walk<false, false, false, AMB>(
-          a, idx, o, d, nt, ft, s_dyn + lane, 64,
-          [&](int, const SampleTerms &st, const PathVtxP &pv, v3 dv, const float (&beta)[3]) {
-            lights_at_vertex<true>(kernarg_shade(), a, s_l, n, st, pv, dv, beta, s_dyn + lane, 64, L);
-          },
-          NoBounce(), [&](const float (&beta)[3]) { L[0] += beta[0] * la0; L[1] += beta[1] * la1; L[2] += beta[2] * la2; });
+      const auto at_vertex = [&](int, const SampleTerms &st, const PathVtxP &pv, v3 dv, const float (&beta)[3]) {
+        lights_at_vertex<DIR>(kernarg_shade(), a, s_l, n, st, pv, dv, beta, s_dyn + lane, 64, L);
+      };
+      if constexpr (DIR || AMB)
+        path_walk<false, false, false, AMB>(a, idx, o, d, nt, ft, s_dyn + lane, 64, at_vertex, NoBounce(),
+                                            [&](const float (&beta)[3]) { L[0] += beta[0] * la0; L[1] += beta[1] * la1; L[2] += beta[2] * la2; });
+      else // (the plain instances without the hooks, as they were written: with them the three sums of L change registers — tools/isa_same.py)
+        path_walk<false, false, false>(a, idx, o, d, nt, ft, s_dyn + lane, 64, at_vertex);
     }
     if (RF) {
       float gx[5], gy[5];
@@ -4259,27 +4186,8 @@ __global__ void __launch_bounds__(64) k_lights_gather(const float4 *__restrict__
   const int lane = threadIdx.x;
   const int x0 = blockIdx.x * 64, y = blockIdx.y;
   if (y >= H) return;
-  float r = 0.f, g = 0.f, b = 0.f, w = 0.f;
-  for (int wb = 0; wb < 5; ++wb) {
-    const int qy = y - (wb - 2);
-    if (qy < 0 || qy >= H) continue; // (wave-uniform)
-    __builtin_amdgcn_wave_barrier();
-#pragma unroll
-    for (int k = 0; k < 6; ++k) {
-      const int e = lane + 64 * k;
-      if (e < 340) {
-        const int rec = e / 5, wa = e - 5 * rec;
-        const int qx = x0 - 2 + rec;
-        s_seg[e] = (qx >= 0 && qx < W) ? part[((size_t)qy * W + qx) * 25 + (wb * 5 + wa)] : make_float4(0.f, 0.f, 0.f, 0.f);
-      }
-    }
-    __builtin_amdgcn_wave_barrier();
-#pragma unroll
-    for (int wa = 0; wa < 5; ++wa) {
-      const float4 v = s_seg[(lane + 4 - wa) * 5 + wa];
-      r += v.x; g += v.y; b += v.z; w += v.w;
-    }
-  }
+  float r, g, b, w;
+  rf_window_sums(part, W, H, x0, y, lane, s_seg, r, g, b, w);
   const int x = x0 + lane;
   if (x >= W || !(w > 0.f)) return;
   float *p = img + ((size_t)y * W + x) * 3;
@@ -4354,7 +4262,7 @@ __global__ void __launch_bounds__(64)
 }
 // ------------------------------------------------------------------------------------------ extra emitters' adjoint
 // FFX_RENDER_EMITTER_GRAD (include/ffx.h): d loss / d (the RGB power of every light record, the constant emitter's radiance).  The walk does not depend on the
-// emitters, so the image is linear in those powers and the derivative is the adjoint-weighted image at unit power: k_lights_dir_fwd's walk once more
+// emitters, so the image is linear in those powers and the derivative is the adjoint-weighted image at unit power: k_lights_fwd<RF, true, AMB>'s walk once more
 // (lights_derive<true>, path_walk<..., AMB>, the same jitter and path keys: the forward's paths by construction), where lights_at_vertex<true, ADJ> adds record k's
 // q[ch] beta[ch] (base[ch] f + fb) to the record's sum and every escaped ray q[ch] beta[ch] to the ambient's.  One wave = one pixel, lane l takes samples
 // l, l + 64, ...; a lane's 3 n record sums live in LDS, one column per lane (stride 64: conflict-free; a run-time record number never indexes registers)
@@ -5173,27 +5081,8 @@ __global__ void __launch_bounds__(64) k_aov_gather(const float4 *__restrict__ pa
   __shared__ float4 seg[68 * 5];
   const int lane = threadIdx.x;
   const int x0 = blockIdx.x * 64, y = blockIdx.y;
-  float r = 0.f, g = 0.f, b = 0.f, w = 0.f;
-  for (int wb = 0; wb < 5; ++wb) {
-    const int qy = y - (wb - 2);
-    if (qy < 0 || qy >= H) continue; // (wave-uniform)
-    __builtin_amdgcn_wave_barrier();
-#pragma unroll
-    for (int kk = 0; kk < 6; ++kk) {
-      const int e = lane + 64 * kk; // element (record e / 5, entry e % 5) of the 68 x 5 segment table
-      if (e < 340) {
-        const int rec = e / 5, wa = e - 5 * rec;
-        const int qx = x0 - 2 + rec;
-        seg[e] = (qx >= 0 && qx < W) ? part[((size_t)qy * W + qx) * 25 + (wb * 5 + wa)] : make_float4(0.f, 0.f, 0.f, 0.f);
-      }
-    }
-    __builtin_amdgcn_wave_barrier();
-#pragma unroll
-    for (int wa = 0; wa < 5; ++wa) {
-      const float4 v = seg[(lane + 4 - wa) * 5 + wa];
-      r += v.x; g += v.y; b += v.z; w += v.w;
-    }
-  }
+  float r, g, b, w;
+  rf_window_sums(part, W, H, x0, y, lane, seg, r, g, b, w);
   const int x = x0 + lane;
   if (x >= W) return;
   float *p = aov + ((size_t)y * W + x) * FFX_RENDER_AOV_FLOATS + ch0;
@@ -5767,6 +5656,13 @@ template <class F> static void dispatch_rf_mat(bool rf, bool mat, F &&f) {
   if (rf) by_mat(std::true_type());
   else by_mat(std::false_type());
 }
+// ... with the lights' pass's third (filtered film, directional records, constant emitter), for k_lights_fwd: f(std::bool_constant<RF>, <DIR>, <AMB>)
+template <class F> static void dispatch_rf_dir_amb(bool rf, bool dir, bool amb, F &&f) {
+  dispatch_rf_mat(rf, dir, [&](auto r, auto d) {
+    if (amb) f(r, d, std::true_type());
+    else f(r, d, std::false_type());
+  });
+}
 // What k_render_fwd_pk<..., PLAIN> takes as constants, proved here from what the call carries (anything less: the generic instance).  The rows
 // travel inline and shade_prepare derived a pre-row for each (mat_pre_on), every row is a principled row (model != 0) with no optional lobe (its
 // flag word is 0), the blob's last update flagged no shape smooth (ffx_blob_flat: a blob this process has not updated is not known to be flat), a spot
@@ -6120,37 +6016,46 @@ static int render_aov(const void *bvh, const ffx_bvh_info *info, const ffx_scene
       FFX_FAIL(FFX_ERR_UNSUPPORTED, "%s: FFX_RENDER_LIGHTS_DIRECTIONAL is served by ffx_render_fwd[_filtered] only", what_); \
     FFX_NO_EMITTER_GRAD(flags_, what_); \
   } while (0)
-// FFX_RENDER_LIGHTS (include/ffx.h).  What a forward refuses about the bits before it launches anything: FFX_OK, or the error
+// FFX_RENDER_LIGHTS (include/ffx.h).  The three bits of the extra emitters: what each is called, who it stands for and the device buffer it reads (NULL: the table's bit reads nothing of its own)
+struct EmitterBit { int mask; const char *name, *who, *buffer; };
+static const EmitterBit kLightsBit = {FFX_RENDER_LIGHTS_MASK, "FFX_RENDER_LIGHTS", "the extra emitters are", "material table | lights"};
+static const EmitterBit kAmbientBit = {FFX_RENDER_AMBIENT, "FFX_RENDER_AMBIENT", "the constant emitter is", "material table | lights | ambient"};
+static const EmitterBit kDirectionalBit = {FFX_RENDER_LIGHTS_DIRECTIONAL, "FFX_RENDER_LIGHTS_DIRECTIONAL", "the extra emitters are", nullptr};
+// a bit of the extra emitters beside a FFX_RENDER_GRAD_* bit: refused by the forwards and by ffx_render_bwd[_filtered] alike
+static int emitter_bit_no_grad(int flags, const char *what, const EmitterBit &b) {
+  if (flags & (FFX_RENDER_GRAD_APPEARANCE | FFX_RENDER_GRAD_MATERIAL | FFX_RENDER_GRAD_PRB))
+    FFX_FAIL(FFX_ERR_UNSUPPORTED, "%s: %s is not served together with a FFX_RENDER_GRAD_* bit (%s not differentiated)", what, b.name, b.who);
+  return FFX_OK;
+}
+// what a forward refuses about a set bit, the same for the three under each one's name
+static int emitter_bit_check(int flags, const float *shape_albedo, const char *what, const EmitterBit &b) {
+  if (flags & FFX_RENDER_FP16) FFX_FAIL(FFX_ERR_UNSUPPORTED, "%s: %s has no fp16 film", what, b.name);
+  if (flags & FFX_RENDER_TANGENT) FFX_FAIL(FFX_ERR_UNSUPPORTED, "%s: %s is not served together with FFX_RENDER_TANGENT", what, b.name);
+  if (const int rc = emitter_bit_no_grad(flags, what, b)) return rc;
+  if (b.buffer && !shape_albedo) FFX_FAIL(FFX_ERR_ARG, "%s: %s needs the device buffer [%s] (shape_albedo is NULL)", what, b.name, b.buffer);
+  return FFX_OK;
+}
+// what a forward refuses about the bits before it launches anything: FFX_OK, or the error
 static int lights_check(int flags, const float *shape_albedo, const char *what) {
   const int n = (flags & FFX_RENDER_LIGHTS_MASK) >> FFX_RENDER_LIGHTS_SHIFT;
-  if (flags & FFX_RENDER_AMBIENT) { // the constant emitter: the same refusals under its own name
-    if (flags & FFX_RENDER_FP16) FFX_FAIL(FFX_ERR_UNSUPPORTED, "%s: FFX_RENDER_AMBIENT has no fp16 film", what);
-    if (flags & FFX_RENDER_TANGENT) FFX_FAIL(FFX_ERR_UNSUPPORTED, "%s: FFX_RENDER_AMBIENT is not served together with FFX_RENDER_TANGENT", what);
-    if (flags & (FFX_RENDER_GRAD_APPEARANCE | FFX_RENDER_GRAD_MATERIAL | FFX_RENDER_GRAD_PRB))
-      FFX_FAIL(FFX_ERR_UNSUPPORTED, "%s: FFX_RENDER_AMBIENT is not served together with a FFX_RENDER_GRAD_* bit (the constant emitter is not differentiated)", what);
-    if (!shape_albedo) FFX_FAIL(FFX_ERR_ARG, "%s: FFX_RENDER_AMBIENT needs the device buffer [material table | lights | ambient] (shape_albedo is NULL)", what);
+  if (flags & FFX_RENDER_AMBIENT) { // the constant emitter
+    if (const int rc = emitter_bit_check(flags, shape_albedo, what, kAmbientBit)) return rc;
   }
   if (flags & FFX_RENDER_LIGHTS_DIRECTIONAL) { // directional records in the table: the bit belongs to a table, and is refused where the table is
     if (n == 0) FFX_FAIL(FFX_ERR_ARG, "%s: FFX_RENDER_LIGHTS_DIRECTIONAL needs FFX_RENDER_LIGHTS(n >= 1): the bit says what the table may hold", what);
-    if (flags & FFX_RENDER_FP16) FFX_FAIL(FFX_ERR_UNSUPPORTED, "%s: FFX_RENDER_LIGHTS_DIRECTIONAL has no fp16 film", what);
-    if (flags & FFX_RENDER_TANGENT) FFX_FAIL(FFX_ERR_UNSUPPORTED, "%s: FFX_RENDER_LIGHTS_DIRECTIONAL is not served together with FFX_RENDER_TANGENT", what);
-    if (flags & (FFX_RENDER_GRAD_APPEARANCE | FFX_RENDER_GRAD_MATERIAL | FFX_RENDER_GRAD_PRB))
-      FFX_FAIL(FFX_ERR_UNSUPPORTED, "%s: FFX_RENDER_LIGHTS_DIRECTIONAL is not served together with a FFX_RENDER_GRAD_* bit (the extra emitters are not differentiated)",
-               what);
+    if (const int rc = emitter_bit_check(flags, shape_albedo, what, kDirectionalBit)) return rc;
   }
   if (n == 0) return FFX_OK;
   if (n > FFX_RENDER_MAX_LIGHTS) FFX_FAIL(FFX_ERR_ARG, "%s: FFX_RENDER_LIGHTS(%d): at most %d extra emitters", what, n, FFX_RENDER_MAX_LIGHTS);
-  if (flags & FFX_RENDER_FP16) FFX_FAIL(FFX_ERR_UNSUPPORTED, "%s: FFX_RENDER_LIGHTS has no fp16 film", what);
-  if (flags & FFX_RENDER_TANGENT) FFX_FAIL(FFX_ERR_UNSUPPORTED, "%s: FFX_RENDER_LIGHTS is not served together with FFX_RENDER_TANGENT", what);
-  if (flags & (FFX_RENDER_GRAD_APPEARANCE | FFX_RENDER_GRAD_MATERIAL | FFX_RENDER_GRAD_PRB))
-    FFX_FAIL(FFX_ERR_UNSUPPORTED, "%s: FFX_RENDER_LIGHTS is not served together with a FFX_RENDER_GRAD_* bit (the extra emitters are not differentiated)", what);
-  if (!shape_albedo) FFX_FAIL(FFX_ERR_ARG, "%s: FFX_RENDER_LIGHTS needs the device buffer [material table | lights] (shape_albedo is NULL)", what);
-  return FFX_OK;
+  return emitter_bit_check(flags, shape_albedo, what, kLightsBit);
+}
+// the emitters' records in the caller's device buffer [material table | lights | ambient]: behind the rows (mat_stride: 3 or FFX_MAT_STRIDE — max(mat_stride, 3))
+static const float *lights_table(const float *shape_albedo, const ffx_scene_desc *sd, const RenderSetup &r) {
+  return shape_albedo + (size_t)sd->n_shapes * (size_t)r.c.mat_stride;
 }
 // ... and the pass, behind the launches of the main image on the same stream (the call without the bits has succeeded: its arguments are good):
 // k_lights_fwd adds to img; the gaussian film: into the scratch, which the image's (and an AOV block's) gathers have read by then, and k_lights_gather adds.
-// With FFX_RENDER_AMBIENT the same launches are k_lights_ambient_fwd's: one walk per sample serves the n lights (n may be 0) and the constant emitter.
-// With FFX_RENDER_LIGHTS_DIRECTIONAL they are k_lights_dir_fwd's, with or without the constant emitter: still one walk per sample
+// One walk per sample serves the n lights (with FFX_RENDER_AMBIENT n may be 0), whatever their types, and the constant emitter
 static int render_lights(const void *bvh, const ffx_bvh_info *info, const ffx_scene_desc *sd, const float *shape_albedo, int spp, uint32_t seed, int flags, void *img,
                          ffx_stream s, void *rf_scratch) {
   const int n = (flags & FFX_RENDER_LIGHTS_MASK) >> FFX_RENDER_LIGHTS_SHIFT;
@@ -6158,19 +6063,17 @@ static int render_lights(const void *bvh, const ffx_bvh_info *info, const ffx_sc
   if (const int rc = render_setup("render_fwd", bvh, info, sd, shape_albedo, spp, seed, flags & FFX_RENDER_PATH_MASK, rf_scratch, r)) return rc;
   if (r.n_pix >= (1L << 31)) FFX_FAIL(FFX_ERR_UNSUPPORTED, "render_fwd: FFX_RENDER_LIGHTS: more than 2^31 pixels");
   if (sd->n_shapes < 0) FFX_FAIL(FFX_ERR_ARG, "render_fwd: n_shapes < 0");
-  const float *table = shape_albedo + (size_t)sd->n_shapes * (size_t)r.c.mat_stride; // (mat_stride: 3 or FFX_MAT_STRIDE — max(mat_stride, 3))
+  const float *table = lights_table(shape_albedo, sd, r);
   const PathArgs pa = path_args(r);
   const hipStream_t st = (hipStream_t)s;
-  const bool amb = (flags & FFX_RENDER_AMBIENT) != 0, dir = (flags & FFX_RENDER_LIGHTS_DIRECTIONAL) != 0;
-  if (rf_scratch) {
-    hipLaunchKernelGGL(dir ? (amb ? k_lights_dir_fwd<true, true> : k_lights_dir_fwd<true, false>) : amb ? k_lights_ambient_fwd<true> : k_lights_fwd<true>, dim3((unsigned)r.n_pix), dim3(64), path_stack_bytes(info), st, r.c, pa, table, n, (float *)nullptr, (float *)rf_scratch);
-    FFX_CHECK_LAUNCH("render_fwd_filtered (lights)");
-    hipLaunchKernelGGL(k_lights_gather, dim3(ffx_cdiv(r.c.cam.W, 64), r.c.cam.H), dim3(64), 0, st, (const float4 *)rf_scratch, r.c.cam.W, r.c.cam.H, (float *)img);
-    FFX_CHECK_LAUNCH("render_fwd_filtered (lights)/gather");
-    return FFX_OK;
-  }
-  hipLaunchKernelGGL(dir ? (amb ? k_lights_dir_fwd<false, true> : k_lights_dir_fwd<false, false>) : amb ? k_lights_ambient_fwd<false> : k_lights_fwd<false>, dim3((unsigned)r.n_pix), dim3(64), path_stack_bytes(info), st, r.c, pa, table, n, (float *)img, (float *)nullptr);
-  FFX_CHECK_LAUNCH("render_fwd (lights)");
+  dispatch_rf_dir_amb(rf_scratch != nullptr, (flags & FFX_RENDER_LIGHTS_DIRECTIONAL) != 0, (flags & FFX_RENDER_AMBIENT) != 0, [&](auto rf, auto dir, auto amb) {
+    hipLaunchKernelGGL((k_lights_fwd<decltype(rf)::value, decltype(dir)::value, decltype(amb)::value>), dim3((unsigned)r.n_pix), dim3(64), path_stack_bytes(info), st, r.c,
+                       pa, table, n, rf_scratch ? (float *)nullptr : (float *)img, (float *)rf_scratch);
+  });
+  FFX_CHECK_LAUNCH(rf_scratch ? "render_fwd_filtered (lights)" : "render_fwd (lights)");
+  if (!rf_scratch) return FFX_OK;
+  hipLaunchKernelGGL(k_lights_gather, dim3(ffx_cdiv(r.c.cam.W, 64), r.c.cam.H), dim3(64), 0, st, (const float4 *)rf_scratch, r.c.cam.W, r.c.cam.H, (float *)img);
+  FFX_CHECK_LAUNCH("render_fwd_filtered (lights)/gather");
   return FFX_OK;
 }
 // ffx_render_fwd[_filtered] (scratch: the filtered film's): the call without the lights' bits, then their pass
@@ -6558,7 +6461,7 @@ static int render_bwd_emitters(const void *bvh, const ffx_bvh_info *info, const 
   if (sd->n_shapes < 0) FFX_FAIL(FFX_ERR_ARG, "%s: n_shapes < 0", what);
   const long n_tex = (long)sd->proj.tex_w * sd->proj.tex_h * sd->proj.tex_channels;
   if (n_tex < 0) FFX_FAIL(FFX_ERR_ARG, "%s: bad projector texture size", what);
-  const float *table = shape_albedo + (size_t)sd->n_shapes * (size_t)r.c.mat_stride; // (render_lights')
+  const float *table = lights_table(shape_albedo, sd, r);
   float *block = gtex + n_tex, *slots = block + FFX_RENDER_EMITTER_GRAD_BLOCK_FLOATS;
   const PathArgs pa = path_args(r);
   const hipStream_t st = (hipStream_t)s;
@@ -6579,21 +6482,26 @@ static int render_bwd_emitters(const void *bvh, const ffx_bvh_info *info, const 
   return FFX_OK;
 }
 
+// ffx_render_bwd[_filtered] (scratch: the filtered film's): what both refuse about the flags, then the adjoint the flags name
+static int render_bwd_entry(const void *bvh, const ffx_bvh_info *info, const ffx_scene_desc *sd, const float *shape_albedo, int spp, uint32_t seed, int flags,
+                            const float *gimg, float *gtex, ffx_stream s, void *scratch) {
+  const char *what = scratch ? "render_bwd_filtered" : "render_bwd";
+  FFX_NO_TANGENT(flags, what);
+  FFX_NO_AOV(flags, what);
+  FFX_MATERIAL_NEEDS_APPEARANCE(flags, what);
+  for (const EmitterBit *b : {&kLightsBit, &kAmbientBit, &kDirectionalBit}) {
+    if (flags & b->mask) {
+      if (const int rc = emitter_bit_no_grad(flags, what, *b)) return rc;
+    }
+  }
+  if (flags & FFX_RENDER_EMITTER_GRAD) return render_bwd_emitters(bvh, info, sd, shape_albedo, spp, seed, flags, gimg, gtex, s, scratch);
+  flags &= ~(FFX_RENDER_LIGHTS_MASK | FFX_RENDER_AMBIENT | FFX_RENDER_LIGHTS_DIRECTIONAL); // (the texture's adjoint sees neither the extra emitters nor the constant one: the bits are ignored, the tail behind the table is not read)
+  if (flags & FFX_RENDER_GRAD_APPEARANCE) return render_bwd_leaves(bvh, info, sd, shape_albedo, spp, seed, flags, gimg, gtex, s, scratch);
+  return render_bwd_impl(bvh, info, sd, shape_albedo, spp, seed, flags, gimg, gtex, s, scratch);
+}
 int ffx_render_bwd(const void *bvh, const ffx_bvh_info *info, const ffx_scene_desc *sd, const float *shape_albedo, int spp, uint32_t seed, int flags,
                    const float *gimg, float *gtex, ffx_stream s) {
-  FFX_NO_TANGENT(flags, "render_bwd");
-  FFX_NO_AOV(flags, "render_bwd");
-  FFX_MATERIAL_NEEDS_APPEARANCE(flags, "render_bwd");
-  if ((flags & FFX_RENDER_LIGHTS_MASK) && (flags & (FFX_RENDER_GRAD_APPEARANCE | FFX_RENDER_GRAD_MATERIAL | FFX_RENDER_GRAD_PRB)))
-    FFX_FAIL(FFX_ERR_UNSUPPORTED, "render_bwd: FFX_RENDER_LIGHTS is not served together with a FFX_RENDER_GRAD_* bit (the extra emitters are not differentiated)");
-  if ((flags & FFX_RENDER_AMBIENT) && (flags & (FFX_RENDER_GRAD_APPEARANCE | FFX_RENDER_GRAD_MATERIAL | FFX_RENDER_GRAD_PRB)))
-    FFX_FAIL(FFX_ERR_UNSUPPORTED, "render_bwd: FFX_RENDER_AMBIENT is not served together with a FFX_RENDER_GRAD_* bit (the constant emitter is not differentiated)");
-  if ((flags & FFX_RENDER_LIGHTS_DIRECTIONAL) && (flags & (FFX_RENDER_GRAD_APPEARANCE | FFX_RENDER_GRAD_MATERIAL | FFX_RENDER_GRAD_PRB)))
-    FFX_FAIL(FFX_ERR_UNSUPPORTED, "render_bwd: FFX_RENDER_LIGHTS_DIRECTIONAL is not served together with a FFX_RENDER_GRAD_* bit (the extra emitters are not differentiated)");
-  if (flags & FFX_RENDER_EMITTER_GRAD) return render_bwd_emitters(bvh, info, sd, shape_albedo, spp, seed, flags, gimg, gtex, s, nullptr);
-  flags &= ~(FFX_RENDER_LIGHTS_MASK | FFX_RENDER_AMBIENT | FFX_RENDER_LIGHTS_DIRECTIONAL); // (the texture's adjoint sees neither the extra emitters nor the constant one: the bits are ignored, the tail behind the table is not read)
-  if (flags & FFX_RENDER_GRAD_APPEARANCE) return render_bwd_leaves(bvh, info, sd, shape_albedo, spp, seed, flags, gimg, gtex, s, nullptr);
-  return render_bwd_impl(bvh, info, sd, shape_albedo, spp, seed, flags, gimg, gtex, s, nullptr);
+  return render_bwd_entry(bvh, info, sd, shape_albedo, spp, seed, flags, gimg, gtex, s, nullptr);
 }
 
 size_t ffx_render_bwd_det_bytes(const ffx_scene_desc *sd) {
@@ -6673,19 +6581,7 @@ int ffx_render_fwd_adjoint_filtered(const void *bvh, const ffx_bvh_info *info, c
 int ffx_render_bwd_filtered(const void *bvh, const ffx_bvh_info *info, const ffx_scene_desc *sd, const float *shape_albedo, int spp, uint32_t seed, int flags,
                             const float *gimg, float *gtex, void *scratch, ffx_stream s) {
   if (!scratch || ((uintptr_t)scratch & 15) != 0) FFX_FAIL(FFX_ERR_ARG, "render_bwd_filtered: scratch is NULL or not 16-byte aligned");
-  FFX_NO_TANGENT(flags, "render_bwd_filtered");
-  FFX_NO_AOV(flags, "render_bwd_filtered");
-  FFX_MATERIAL_NEEDS_APPEARANCE(flags, "render_bwd_filtered");
-  if ((flags & FFX_RENDER_LIGHTS_MASK) && (flags & (FFX_RENDER_GRAD_APPEARANCE | FFX_RENDER_GRAD_MATERIAL | FFX_RENDER_GRAD_PRB)))
-    FFX_FAIL(FFX_ERR_UNSUPPORTED, "render_bwd_filtered: FFX_RENDER_LIGHTS is not served together with a FFX_RENDER_GRAD_* bit (the extra emitters are not differentiated)");
-  if ((flags & FFX_RENDER_AMBIENT) && (flags & (FFX_RENDER_GRAD_APPEARANCE | FFX_RENDER_GRAD_MATERIAL | FFX_RENDER_GRAD_PRB)))
-    FFX_FAIL(FFX_ERR_UNSUPPORTED, "render_bwd_filtered: FFX_RENDER_AMBIENT is not served together with a FFX_RENDER_GRAD_* bit (the constant emitter is not differentiated)");
-  if ((flags & FFX_RENDER_LIGHTS_DIRECTIONAL) && (flags & (FFX_RENDER_GRAD_APPEARANCE | FFX_RENDER_GRAD_MATERIAL | FFX_RENDER_GRAD_PRB)))
-    FFX_FAIL(FFX_ERR_UNSUPPORTED, "render_bwd_filtered: FFX_RENDER_LIGHTS_DIRECTIONAL is not served together with a FFX_RENDER_GRAD_* bit (the extra emitters are not differentiated)");
-  if (flags & FFX_RENDER_EMITTER_GRAD) return render_bwd_emitters(bvh, info, sd, shape_albedo, spp, seed, flags, gimg, gtex, s, scratch);
-  flags &= ~(FFX_RENDER_LIGHTS_MASK | FFX_RENDER_AMBIENT | FFX_RENDER_LIGHTS_DIRECTIONAL); // (the texture's adjoint sees neither the extra emitters nor the constant one: the bits are ignored, the tail behind the table is not read)
-  if (flags & FFX_RENDER_GRAD_APPEARANCE) return render_bwd_leaves(bvh, info, sd, shape_albedo, spp, seed, flags, gimg, gtex, s, scratch);
-  return render_bwd_impl(bvh, info, sd, shape_albedo, spp, seed, flags, gimg, gtex, s, scratch);
+  return render_bwd_entry(bvh, info, sd, shape_albedo, spp, seed, flags, gimg, gtex, s, scratch);
 }
 
 int ffx_render_fwd_cache_filtered(const void *bvh, const ffx_bvh_info *info, const ffx_scene_desc *sd, const float *shape_albedo, const float *tex, int spp,

@@ -704,6 +704,10 @@ class Scene:
         """whether the extra emitters hold a directional one: the render calls' `lights_directional`"""
         return ops.lights_directional(self.data.lights)
 
+    def emitter_args(self):
+        """the render calls' `lights`, `ambient` and `lights_directional` keywords for this scene's extra emitters"""
+        return _emitter_args(self)
+
     def ambient_record(self):
         """the constant emitter's radiance as a [3] device tensor for the render calls' `ambient`, None for a scene without; rebuilt
         after a params.update() that touched `<id>.radiance.value`"""
@@ -1382,12 +1386,10 @@ def render(scene: Scene, params: SceneParameters = None, spp: int = 16, seed: in
         raise NotImplementedError("only sensor 0 renders; further sensors are projector proxies")
     if integrator is not None and not isinstance(integrator, Integrator):
         raise TypeError("render: integrator must come from mi.load_dict")
-    lights = scene.lights_table() if _has_lights(scene) else None
-    if lights is not None and fp16:
+    emitters = _emitter_args(scene)
+    if emitters["lights"] is not None and fp16:
         raise ValueError("mi.render: a scene with extra emitters (point lights, further spots) has no fp16 film")
-    sun = lights is not None and scene.lights_directional()  # (a directional emitter among them, DESIGN.md 4.9: the table's bit)
-    ambient = scene.ambient_record() if _has_ambient(scene) else None
-    if ambient is not None and fp16:
+    if emitters["ambient"] is not None and fp16:
         raise ValueError("mi.render: a scene with a constant emitter (ambient light) has no fp16 film")
     if integrator is not None and integrator.type == "aov":
         return _render_aov(scene, params, spp, seed, fp16, integrator)
@@ -1406,12 +1408,11 @@ def render(scene: Scene, params: SceneParameters = None, spp: int = 16, seed: in
     try:
         if tex.requires_grad and torch.is_grad_enabled():
             scene.render_paths["autograd"] += 1
-            img = Fn.render(tex, scene.geom, sd, scene.materials_arg(sd), spp, seed, fp16, md, rr, lights=lights, ambient=ambient,
-                            lights_directional=sun)
+            img = Fn.render(tex, scene.geom, sd, scene.materials_arg(sd), spp, seed, fp16, md, rr, **emitters)
         else:  # nothing to differentiate: straight to the kernel (autograd.Function.apply costs ~80 us of host time per call)
             mats = scene.materials_arg(sd)
             # (extra emitters: a device table travels with the call — the caller's stream, like the device material tables)
-            slot = scene._render_stream(tex_in, mats) if tex_in is not None and not deep and lights is None and ambient is None else None
+            slot = scene._render_stream(tex_in, mats) if tex_in is not None and not deep and emitters["lights"] is None and emitters["ambient"] is None else None
             if slot is not None:  # beside the previous render, on the scene's other render stream
                 rs, done, priv = slot
                 scene.render_paths["two_stream"] += 1
@@ -1420,8 +1421,7 @@ def render(scene: Scene, params: SceneParameters = None, spp: int = 16, seed: in
                     done.record(rs)
                 return _RenderedXf(img, done)
             scene.render_paths["caller_stream"] += 1
-            img = scene.geom.render_fwd(sd, mats, Fn._tex3(tex), int(spp), int(seed), bool(fp16), max_depth=md, rr_depth=rr, lights=lights, ambient=ambient,
-                                        lights_directional=sun)
+            img = scene.geom.render_fwd(sd, mats, Fn._tex3(tex), int(spp), int(seed), bool(fp16), max_depth=md, rr_depth=rr, **emitters)
         return TensorXf(img)
     finally:  # (the launcher counts its choice when it launches: two reads of a word of the library, no call into it)
         scene.render_paths["k8_plain"] += k8[0] - k8_plain0
@@ -1435,6 +1435,12 @@ def _has_lights(scene):
 def _has_ambient(scene):
     """does the scene hold a constant emitter?"""
     return getattr(getattr(scene, "data", None), "ambient", None) is not None
+
+
+def _emitter_args(scene):
+    """Scene.emitter_args for anything _has_lights / _has_ambient accept (the refusals of `render` are reached with stand-ins for a scene)"""
+    lights = scene.lights_table() if _has_lights(scene) else None
+    return dict(lights=lights, ambient=scene.ambient_record() if _has_ambient(scene) else None, lights_directional=lights is not None and scene.lights_directional())
 
 
 def _render_aov(scene, params, spp, seed, fp16, integrator):
@@ -1451,10 +1457,7 @@ def _render_aov(scene, params, spp, seed, fp16, integrator):
     grad = inner is not None and torch.is_grad_enabled() and (tex.requires_grad or bool(scene._params._leaves) or bool(scene._params._emitter_leaves))
     rgb = render(scene, params, spp, seed, 0, False, inner).torch() if grad else None
     md, rr = (inner.max_depth, inner.rr_depth) if inner is not None and not grad else (2, 5)
-    img, block = scene.geom.render_aov(sd, scene.materials_arg(sd), Fn._tex3(tex.detach()), int(spp), int(seed), max_depth=md, rr_depth=rr,
-                                       lights=scene.lights_table() if _has_lights(scene) else None,
-                                       ambient=scene.ambient_record() if _has_ambient(scene) else None,
-                                       lights_directional=_has_lights(scene) and scene.lights_directional())
+    img, block = scene.geom.render_aov(sd, scene.materials_arg(sd), Fn._tex3(tex.detach()), int(spp), int(seed), max_depth=md, rr_depth=rr, **scene.emitter_args())
     parts = []
     for _, type_ in integrator.aovs:
         first, n = ops.AOV_CHANNELS[type_]
@@ -1605,6 +1608,35 @@ def render_forward(scene: Scene, params: SceneParameters = None, tangents: dict 
     return TensorXf(img), TensorXf(dimg)
 
 
+def _replay_setup(ctx, tex, scene, sd, mats, spp, seed, depths, leaves):
+    """what the two autograd Functions below keep for a backward that re-traces the render's pose -> the texture as the kernels take it"""
+    ctx.geom, ctx.sd, ctx.spp, ctx.seed, ctx.depths = scene.geom, sd, spp, seed, depths
+    ctx.tex, ctx.tex_shape = Fn._tex3(tex.detach()), tex.shape
+    ctx.mats = mats.clone() if mats is not None else None  # (the scene's table is rewritten in place by the next randomisation)
+    ctx.keep = [bt for _, bt in scene._base_tex]  # (the description points at them)
+    ctx.leaf_meta = [(x.shape, x.dtype, x.device) for x in leaves]
+    ctx.pose_version = scene.geom.version
+    return ctx.tex
+
+
+def _replay_gimg(ctx, g):
+    """the image gradient for the backward's call; refuses a pose other than the render's"""
+    if ctx.geom.version != ctx.pose_version:
+        raise RuntimeError("mi.render: the scene was updated between the render and its backward — the appearance adjoint re-traces the render's pose: "
+                           "call backward before the next params.update()")
+    return g.float().contiguous()
+
+
+def _replay_grads(ctx, gtex, values, n_args):
+    """backward's result: the texture's gradient, None for the n_args constants, then each leaf's value in the leaf's shape, dtype and device"""
+    grads = []
+    for v, (shape, dtype, device) in zip(values, ctx.leaf_meta):
+        v = v.sum().reshape(shape) if int(np.prod(shape)) == 1 else v.reshape(shape)  # (a scalar assigned to a colour is broadcast to its three channels)
+        grads.append(v.to(device=device, dtype=dtype))
+    gt = gtex.reshape(ctx.tex_shape) if ctx.needs_input_grad[0] else None
+    return (gt, *[None] * n_args, *grads)
+
+
 class _AppearanceRender(torch.autograd.Function):
     """mi.render with appearance leaves: the plain forward; the backward is ONE ffx_render_bwd[_filtered] call with
     FFX_RENDER_GRAD_APPEARANCE, which yields the texture gradient and the appearance block together (and, with BSDF leaves, FFX_RENDER_GRAD_MATERIAL's
@@ -1612,46 +1644,32 @@ class _AppearanceRender(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, tex, scene, sd, mats, spp, seed, fp16, kinds, depths, *leaves):
-        geom = scene.geom
-        t = Fn._tex3(tex.detach())
-        ctx.geom, ctx.sd, ctx.spp, ctx.seed, ctx.kinds, ctx.depths = geom, sd, spp, seed, kinds, depths
-        ctx.tex, ctx.tex_shape = t, tex.shape
-        ctx.mats = mats.clone() if mats is not None else None  # (the scene's table is rewritten in place by the next randomisation)
-        ctx.keep = [bt for _, bt in scene._base_tex]  # (the description points at them)
-        ctx.leaf_meta = [(x.shape, x.dtype, x.device) for x in leaves]
-        ctx.pose_version = geom.version
+        t = _replay_setup(ctx, tex, scene, sd, mats, spp, seed, depths, leaves)
+        ctx.kinds = kinds
         if depths[0] > 2:  # (`prb`: the path integrator's image)
-            return geom.render_fwd(sd, mats, t, spp, seed, fp16, max_depth=depths[0], rr_depth=depths[1])
-        return geom.render_fwd(sd, mats, t, spp, seed, fp16)
+            return scene.geom.render_fwd(sd, mats, t, spp, seed, fp16, max_depth=depths[0], rr_depth=depths[1])
+        return scene.geom.render_fwd(sd, mats, t, spp, seed, fp16)
 
     @staticmethod
     def backward(ctx, g):
-        if ctx.geom.version != ctx.pose_version:
-            raise RuntimeError("mi.render: the scene was updated between the render and its backward — the appearance adjoint re-traces the render's pose: "
-                               "call backward before the next params.update()")
+        g = _replay_gimg(ctx, g)
         material = any(kind == "bsdf" for kind, _ in ctx.kinds)
         if ctx.depths[0] > 2:  # (`prb`: FFX_RENDER_GRAD_PRB's replay of the paths yields the same blocks)
-            gtex, app = ctx.geom.render_bwd_prb(ctx.sd, ctx.mats, ctx.spp, ctx.seed, g.float().contiguous(), ctx.tex, ctx.depths[0], ctx.depths[1], material=material)
+            gtex, app = ctx.geom.render_bwd_prb(ctx.sd, ctx.mats, ctx.spp, ctx.seed, g, ctx.tex, ctx.depths[0], ctx.depths[1], material=material)
         else:
-            gtex, app = ctx.geom.render_bwd(ctx.sd, ctx.mats, ctx.spp, ctx.seed, g.float().contiguous(), appearance=True, tex=ctx.tex, material=material)
-        grads = []
-        for (kind, arg), (shape, dtype, device) in zip(ctx.kinds, ctx.leaf_meta):
+            gtex, app = ctx.geom.render_bwd(ctx.sd, ctx.mats, ctx.spp, ctx.seed, g, appearance=True, tex=ctx.tex, material=material)
+        values = []
+        for kind, arg in ctx.kinds:
             if kind == "mat":
-                v = app.rows[list(arg)].sum(0)
+                values.append(app.rows[list(arg)].sum(0))
             elif kind == "spot":
-                v = app.spot
+                values.append(app.spot)
             elif kind == "bsdf":
                 rows, col, fac = arg
-                v = app.material[list(rows), col].sum() * fac
+                values.append(app.material[list(rows), col].sum() * fac)
             else:
-                v = app.base_tex[arg]
-            n = 1
-            for e in shape:
-                n *= int(e)
-            v = v.sum().reshape(shape) if n == 1 else v.reshape(shape)  # (a scalar assigned to a colour is broadcast to its three channels)
-            grads.append(v.to(device=device, dtype=dtype))
-        gt = gtex.reshape(ctx.tex_shape) if ctx.needs_input_grad[0] else None
-        return (gt, None, None, None, None, None, None, None, None, *grads)
+                values.append(app.base_tex[arg])
+        return _replay_grads(ctx, gtex, values, 8)
 
 
 def _render_appearance(scene, spp, seed, fp16, integrator):
@@ -1696,35 +1714,16 @@ class _EmitterRender(torch.autograd.Function):
     for the constant emitter's radiance"""
 
     @staticmethod
-    def forward(ctx, tex, scene, sd, mats, spp, seed, lights, ambient, sun, rows, depths, *leaves):
-        geom = scene.geom
-        t = Fn._tex3(tex.detach())
-        ctx.geom, ctx.sd, ctx.spp, ctx.seed, ctx.rows, ctx.depths = geom, sd, spp, seed, rows, depths
-        ctx.tex_shape = tex.shape
-        ctx.mats = mats.clone() if mats is not None else None  # (the scene's table is rewritten in place by the next randomisation)
-        ctx.keep = [bt for _, bt in scene._base_tex]  # (the description points at them)
-        ctx.lights, ctx.ambient, ctx.sun = lights, ambient, sun
-        ctx.leaf_meta = [(x.shape, x.dtype, x.device) for x in leaves]
-        ctx.pose_version = geom.version
-        return geom.render_fwd(sd, mats, t, spp, seed, False, max_depth=depths[0], rr_depth=depths[1], lights=lights, ambient=ambient, lights_directional=sun)
+    def forward(ctx, tex, scene, sd, mats, spp, seed, emitters, rows, depths, *leaves):
+        t = _replay_setup(ctx, tex, scene, sd, mats, spp, seed, depths, leaves)
+        ctx.emitters, ctx.rows = emitters, rows
+        return scene.geom.render_fwd(sd, mats, t, spp, seed, False, max_depth=depths[0], rr_depth=depths[1], **emitters)
 
     @staticmethod
     def backward(ctx, g):
-        if ctx.geom.version != ctx.pose_version:
-            raise RuntimeError("mi.render: the scene was updated between the render and its backward — the appearance adjoint re-traces the render's pose: "
-                               "call backward before the next params.update()")
-        gtex, eg = ctx.geom.render_bwd(ctx.sd, ctx.mats, ctx.spp, ctx.seed, g.float().contiguous(), max_depth=ctx.depths[0], rr_depth=ctx.depths[1],
-                                       lights=ctx.lights, ambient=ctx.ambient, lights_directional=ctx.sun, emitters=True)
-        grads = []
-        for row, (shape, dtype, device) in zip(ctx.rows, ctx.leaf_meta):
-            v = eg.ambient if row is None else eg.lights[row]
-            n = 1
-            for e in shape:
-                n *= int(e)
-            v = v.sum().reshape(shape) if n == 1 else v.reshape(shape)  # (a scalar assigned to a colour is broadcast to its three channels)
-            grads.append(v.to(device=device, dtype=dtype))
-        gt = gtex.reshape(ctx.tex_shape) if ctx.needs_input_grad[0] else None
-        return (gt, None, None, None, None, None, None, None, None, None, None, *grads)
+        g = _replay_gimg(ctx, g)
+        gtex, eg = ctx.geom.render_bwd(ctx.sd, ctx.mats, ctx.spp, ctx.seed, g, max_depth=ctx.depths[0], rr_depth=ctx.depths[1], emitters=True, **ctx.emitters)
+        return _replay_grads(ctx, gtex, [eg.ambient if row is None else eg.lights[row] for row in ctx.rows], 8)
 
 
 def _render_emitters(scene, spp, seed, integrator):
@@ -1736,8 +1735,8 @@ def _render_emitters(scene, spp, seed, integrator):
     sd, _, tex = _scene_texture(scene, spp)
     if tex is None:
         tex = torch.zeros((1, 1, 1), device=scene.device)
-    lights = scene.lights_table().clone() if _has_lights(scene) else None
-    ambient = scene.ambient_record().clone() if _has_ambient(scene) else None
+    emitters = {k: v.clone() if torch.is_tensor(v) else v for k, v in scene.emitter_args().items()}  # (the leaves' values go into copies)
+    lights, ambient = emitters["lights"], emitters["ambient"]
     index = {l.name: k for k, l in enumerate(scene.data.lights)}
     rows, leaves = [], []
     for k, leaf in scene._params._emitter_leaves.items():
@@ -1753,5 +1752,4 @@ def _render_emitters(scene, spp, seed, integrator):
             rows.append(index[name])
         leaves.append(leaf)
     depths = (2, 5) if integrator is None else (max(int(integrator.max_depth), 2), int(integrator.rr_depth))
-    sun = lights is not None and scene.lights_directional()
-    return TensorXf(_EmitterRender.apply(tex, scene, sd, scene.materials_arg(sd), int(spp), int(seed), lights, ambient, sun, rows, depths, *leaves))
+    return TensorXf(_EmitterRender.apply(tex, scene, sd, scene.materials_arg(sd), int(spp), int(seed), emitters, rows, depths, *leaves))

@@ -158,9 +158,7 @@ class PatternOptimizer:
         leaf = tex_value.detach().clone().requires_grad_(True)
         sd = self.mi_scene.scene_desc(tex_channels=1)
         img = Fn.render(leaf, self.mi_scene.geom, sd, self.mi_scene.materials_arg(sd), self.spp, seed, max_depth=self.max_depth, rr_depth=self.rr_depth,
-                        lights=self.mi_scene.lights_table() if getattr(self.mi_scene.data, "lights", None) else None,
-                        ambient=self.mi_scene.ambient_record() if getattr(self.mi_scene.data, "ambient", None) is not None else None,
-                        lights_directional=bool(getattr(self.mi_scene.data, "lights", None)) and self.mi_scene.lights_directional())
+                        **self.mi_scene.emitter_args())
         loss = self.loss_fn(img)
         (g,) = torch.autograd.grad(loss, leaf)
         return g, loss.detach()

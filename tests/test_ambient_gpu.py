@@ -1,4 +1,4 @@
-"""The constant emitter on the GPU: k_lights_ambient_fwd in closed form, against the float64 restatement (tests/ref_ambient.py) on both
+"""The constant emitter on the GPU: k_lights_fwd<RF, DIR, AMB> in closed form, against the float64 restatement (tests/ref_ambient.py) on both
 films, film sizes and row kinds at max_depth 2, 3 and 4, the identities, the arms a small case misses, the adjoint, and the public interface.
 Independent evaluations are held to the three conditions of the path and lights tests, the same computation by another route to rtol 1e-5, atol 1e-7."""
 import numpy as np

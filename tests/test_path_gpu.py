@@ -38,6 +38,18 @@ def test_max_depth_2_is_the_default_render_bitwise(gaussian):
     assert torch.allclose(ms.geom.render_bwd(sd, mats, 16, 3, gimg, max_depth=2), ms.geom.render_bwd(sd, mats, 16, 3, gimg), rtol=1e-5, atol=1e-7)
 
 
+@pytest.mark.parametrize("gaussian", [False, True])
+def test_the_fp16_film_of_a_path_render_is_the_fp32_image_rounded(gaussian):
+    """k_path_fwd's fp16 store (box film) and k_rf_gather's behind it (gaussian film): the pixel's fp32 value converted with round-to-nearest-even, as
+    Tensor.half() converts — the fp32 render's image bit for bit.  24 x 24, 16 spp, max_depth 3"""
+    ms, sd, _ = gpu.load(path_corner(False), gaussian, 1)
+    tex = gpu.rand_tex(sd, 1)
+    mats = ms.materials_arg(sd)
+    half = ms.geom.render_fwd(sd, mats, tex, 16, 7, fp16=True, max_depth=3)
+    assert half.dtype == torch.float16 and float(half.float().max()) > 0
+    assert torch.equal(half, ms.geom.render_fwd(sd, mats, tex, 16, 7, max_depth=3).half())
+
+
 @pytest.mark.parametrize("depth,principled,tc,gaussian", [(3, False, 1, False), (4, True, 3, True), (3, True, 1, True), (4, False, 3, False)])
 def test_path_render_matches_float64_restatement(depth, principled, tc, gaussian):
     ms, sd, world = gpu.load(path_corner(principled), gaussian, tc)

@@ -1,5 +1,5 @@
 """Every per-lane walk on shading normals and base-colour textures against the float64 walk of tests/ref_path.py, on
-corner_scenes.smooth_corner: k_path_fwd / k_path_bwd, the three kernels of the extra emitters, prb's blocks, forward mode and the direct-light lane
+corner_scenes.smooth_corner: k_path_fwd / k_path_bwd, the kernel of the extra emitters in its instances, prb's blocks, forward mode and the direct-light lane
 adjoints, and the bit rules that must survive.  tests/test_shading_walk_cpu.py shows that on these films and seeds the walk meets the places where
 n_s differs from n_g and that each rule of the walk, swapped, misses a bound held here.  The bounds are those of the flat-scene test of the same
 kernel, named at each test; every figure is printed, as a fraction of its bound, before it is asserted.  46 cases in 10 .. 14 s on an MI355X, the
@@ -124,9 +124,8 @@ def test_path_render_and_its_texture_adjoint_match_the_float64_walk(depth, tc, g
 @pytest.mark.parametrize("gaussian", [False, True], ids=["box", "gaussian"])
 @pytest.mark.parametrize("film,shadows", [("12x12", True), ("13x11", True), ("12x12", False)], ids=["12x12", "13x11", "12x12-unshadowed"])
 def test_what_every_extra_emitter_adds_matches_the_float64_walk(film, shadows, gaussian, depth):
-    """k_lights_fwd (point, spot), k_lights_dir_fwd (sun), k_lights_ambient_fwd (the constant emitter, closing ray included) and k_lights_dir_fwd with
-    the ambient term (all at once): image minus unlit image against the restatement of that part, under tests/test_lights_gpu.py's three conditions
-    with the sums the flat tests of each kernel use — the part itself at direct light and for the constant emitter, the part's indirect share
+    """k_lights_fwd's instances — plain (point, spot), DIR (sun), AMB (the constant emitter, closing ray included) and DIR with AMB (all at
+    once): image minus unlit image against the restatement of that part, under tests/test_lights_gpu.py's three conditions with the sums the flat tests of each kernel use — the part itself at direct light and for the constant emitter, the part's indirect share
     through the bounces of the lights and the sun"""
     c = case(film, gaussian, 1, shadows)
     plain, main_ref = gpu_image(c, "main", depth), ref_image(c, "main", depth)

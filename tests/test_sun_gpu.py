@@ -1,4 +1,4 @@
-"""The directional emitter on the GPU: k_lights_dir_fwd against the float64 restatement (tests/ref_sun.py) on both films, film sizes and
+"""The directional emitter on the GPU: k_lights_fwd<RF, DIR> against the float64 restatement (tests/ref_sun.py) on both films, film sizes and
 row kinds, the closed forms on the quad that fills the film (with the roof that pins the shadow ray), the sun as the limit of a point light through the
 kernel that exists, the bit identities, linearity, paths and the adjoint, a ragged second pass, and the public interface.  Independent evaluations are
 held to tests/test_lights_gpu.py's three conditions, the same computation by another kernel to rtol 1e-5."""

@@ -2,7 +2,11 @@
 """Whether two builds of a HIP unit are the same machine code, kernel by kernel (no GPU needed).
 
     hipcc <the library's flags> -S --cuda-device-only ffx_trace.hip -o parent.s     (once per tree)
-    python tools/isa_same.py parent.s new.s
+    python tools/isa_same.py parent.s new.s [--map 'OLD=NEW' ...]
+
+--map (repeatable) compares a renamed kernel against its predecessor: OLD and NEW are demangled kernel names without return type and
+argument list, e.g. --map 'k_old<true>=k_new<true, false>'.  For that, every kernel's own symbol is masked in its instruction text, with
+or without --map: without it both sides hold the same symbol there, so the verdicts are what they were.
 
 Per kernel symbol it compares the instruction text (labels and directives included; comments, blank lines, .file / .loc / .ident
 dropped, the function's ordinal in local labels — .LBB<n>_<m>, .Lfunc_end<n> — taken out, since it shifts when a kernel is
@@ -36,7 +40,7 @@ def parse(path):
         if s.startswith(".Lfunc_end"):
             cur = None
             continue
-        body[cur].append(re.sub(r"\.LBB\d+_", ".LBB_", re.sub(r"\s+", " ", s)))
+        body[cur].append(re.sub(r"\.LBB\d+_", ".LBB_", re.sub(r"\s+", " ", s)).replace(cur, "<kernel>"))  # (its own symbol masked: --map)
     meta, name, fields = {}, None, {}
     for raw in lines:  # the metadata note: one "- .args: ... .name: sym ..." entry per kernel, keys sorted, the fields flat
         m = re.match(r"^\s+(?:- )?\.(\w+):\s*(\S*)\s*$", raw)
@@ -55,20 +59,42 @@ def parse(path):
     return {k: (body.get(k, []), meta[k]) for k in meta}
 
 
+def short(name):
+    """a demangled kernel name as --map spells it: no return type, no argument list, no blanks"""
+    return re.sub(r"\(.*", "", name).removeprefix("void ").replace(" ", "")
+
+
 def main():
-    if len(sys.argv) != 3:
+    argv, renames = sys.argv[1:], {}
+    while "--map" in argv:  # --map OLD=NEW (repeatable): parent kernel OLD is compared against the new build's kernel NEW
+        i = argv.index("--map")
+        old, eq, new = (argv[i + 1] if i + 1 < len(argv) else "").partition("=")
+        if not eq or not old or not new:
+            raise SystemExit(__doc__)
+        renames[short(old)] = short(new)
+        del argv[i:i + 2]
+    if len(argv) != 2:
         raise SystemExit(__doc__)
-    a, b = parse(sys.argv[1]), parse(sys.argv[2])
+    path_a, path_b = argv
+    a, b = parse(path_a), parse(path_b)
     if not a or not b:
-        raise SystemExit("no kernels found in " + (sys.argv[1] if not a else sys.argv[2]))
+        raise SystemExit("no kernels found in " + (path_a if not a else path_b))
     syms = sorted(set(a) | set(b))
     names = dict(zip(syms, subprocess.run(["c++filt"], input="\n".join(syms), capture_output=True, text=True).stdout.split("\n")))
+    for old, new in renames.items():  # the parent's kernel takes the new kernel's symbol, and is then compared like any other
+        src = [k for k in a if short(names.get(k) or k) == old]
+        dst = [k for k in b if short(names.get(k) or k) == new]
+        if len(src) != 1 or len(dst) != 1 or (dst[0] in a and dst[0] != src[0]):
+            raise SystemExit(f"--map {old}={new}: {len(src)} such kernels in {path_a}, {len(dst)} in {path_b} (need one each, and no {new} in the former)")
+        a[dst[0]] = a.pop(src[0])
+        names[dst[0]] = f"{old} -> {new}"
+    syms = sorted(set(a) | set(b))
     n_diff = 0
     for k in syms:
         label = re.sub(r"\(.*", "", names.get(k) or k)[:110]
         if k not in a or k not in b:
             n_diff += 1
-            print(f"DIFF  {label}: only in {sys.argv[2] if k in b else sys.argv[1]}")
+            print(f"DIFF  {label}: only in {path_b if k in b else path_a}")
             continue
         (ia, fa), (ib, fb) = a[k], b[k]
         what = [f"{f} {fa.get(f)} -> {fb.get(f)}" for f in FIELDS if fa.get(f) != fb.get(f)]
