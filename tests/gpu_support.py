@@ -1,6 +1,6 @@
 """Helpers of the tests that need the device (tests/*_gpu.py and tests/test_hip_parity.py only): arrays to and from it, the oracle's and the device's
-geometry of one scene, what a blob's bin and envelope headers say, a loaded scene with its world arrays, seeded textures and gradient images, the loss
-of a material table, leaves and fits, the rows' and the spot's central differences of the GPU forward, forward mode against the adjoints."""
+geometry of one scene, what a blob's bin and envelope headers say, its tile lists, apex records and triangle records, a loaded scene with its world
+arrays, seeded textures and gradient images, the loss of a material table, leaves and fits, the rows' and the spot's central differences of the GPU forward, forward mode against the adjoints."""
 import numpy as np
 import torch
 
@@ -83,6 +83,47 @@ def envelope(gd, a, n_cells_x, n_cells_y):
     hdr = blob[base: base + 64].cpu().numpy().view(np.uint32)
     cells = blob[base + off_env: base + off_env + 16 * n_cells_x * n_cells_y].cpu().numpy().view(np.float32).reshape(n_cells_y, n_cells_x, 4)
     return int(hdr[4]), cells, int(hdr[0])
+
+
+BIN_MAX_TILES, LEAF_MAX = 16384, 4  # ffx_common.h FFX_BIN_MAX_TILES, FFX_LEAF_MAX
+BIN_ENTRY = np.dtype([("bb", "<f4", 4), ("e", "<f4", 9), ("slot", "<i4"), ("pad", "<u4", 2)])  # ffx_common.h BinEntry
+TRI_APEX = np.dtype([("A", "<f4", 3), ("B", "<f4", 3), ("C", "<f4", 3), ("T", "<f4"), ("prim", "<i4"), ("shape", "<i4")])  # ffx_common.h TriApex
+
+
+def _bytes(blob, off, n):
+    return blob[off: off + n].cpu().numpy()
+
+
+def bin_lists(gd, a, nx, ny, n_entries=None):
+    """(hdr [16] uint32, starts [nt + 1], cursors [nt], entries [total] as BIN_ENTRY) of grid a (0 camera, 1 projector, 2 spot) of nx x ny tiles in the
+    blob the next render reads (ffx_common.h BinHdr, ffx_bin_off_starts / _cursors / _entries).  n_entries: read that many entries whatever the header
+    says (lists that did not fit: what the entries area holds)"""
+    torch.cuda.synchronize()
+    blob, nt = gd.blob, nx * ny
+    base = int(gd.info.off_bins) + a * int(gd.info.bins_stride)
+    off_cursors = 64 + 4 * (BIN_MAX_TILES + 16)
+    off_entries = (off_cursors + 4 * BIN_MAX_TILES + 63) // 64 * 64
+    hdr = _bytes(blob, base, 64).view(np.uint32)
+    starts = _bytes(blob, base + 64, 4 * (nt + 1)).view(np.uint32)
+    cursors = _bytes(blob, base + off_cursors, 4 * nt).view(np.uint32)
+    n = int(hdr[1]) if n_entries is None else int(n_entries)
+    assert 0 <= n <= 2 * int(gd.info.n_tris) + BIN_MAX_TILES + 64, (n, hdr[:5])  # (the entries area: cap + 64)
+    return hdr, starts, cursors, _bytes(blob, base + off_entries, 64 * n).view(BIN_ENTRY)
+
+
+def apex_records(gd, a):
+    """[F] TRI_APEX: the triangles as apex a sees them (A = e2 x e1, T = e2 . ((o - v0) x e1)), in leaf-slot order, from the blob the next render reads"""
+    torch.cuda.synchronize()
+    F = int(gd.info.n_tris)
+    stride = ((F + LEAF_MAX) * 48 + 63) // 64 * 64
+    return _bytes(gd.blob, int(gd.info.total_bytes) - (3 - a) * stride, 48 * F).view(TRI_APEX)
+
+
+def tri_records(gd):
+    """[F, 3, 3] float64: the posed triangles in leaf-slot order as the blob's own records hold them (float32 v0, v0 + e1, v0 + e2, widened)"""
+    torch.cuda.synchronize()
+    r = _bytes(gd.blob, int(gd.info.off_recs), 48 * int(gd.info.n_tris)).view(np.float32).reshape(-1, 12).astype(np.float64)
+    return np.stack([r[:, 0:3], r[:, 0:3] + r[:, 3:6], r[:, 0:3] + r[:, 6:9]], 1)
 
 
 def grad_close(got, want, what, frac):
