@@ -1,10 +1,11 @@
 """Helpers of the tests that need the device (tests/*_gpu.py and tests/test_hip_parity.py only): arrays to and from it, the oracle's and the device's
 geometry of one scene, what a blob's bin and envelope headers say, its tile lists, apex records and triangle records, a loaded scene with its world
-arrays, seeded textures and gradient images, the loss of a material table, leaves and fits, the rows' and the spot's central differences of the GPU forward, forward mode against the adjoints."""
+arrays, seeded textures and gradient images, the lights' table and the emitter suites' corner cases, the loss of a material table, leaves and fits, the rows' and the spot's central differences of the GPU forward, forward mode against the adjoints."""
 import numpy as np
 import torch
 
 from fireflies_amd import mi, ops, scene_desc, scenes
+from tests import ref_path
 from tests.support import copy_desc, world_arrays
 
 DEV = "cuda"
@@ -154,6 +155,32 @@ def rand_tex(sd, seed=0):
 def rand_gimg(sd, seed=0):
     g = torch.Generator().manual_seed(seed)
     return (0.5 + torch.rand((sd.cam.height, sd.cam.width, 3), generator=g)).to(DEV)
+
+
+def table(*lights):
+    """the lights' [n, 24] table of ops.pack_lights on the device"""
+    return ops.pack_lights(lights).to(DEV)
+
+
+_CORNERS = {}
+
+
+def corner_case(corner, film, principled, gaussian, spp, seed, direct=True):
+    """the scene `corner(film, principled)` of one of the emitter suites' builders, loaded once per builder and arguments: (scene, description, world
+    arrays, rows in float64, texture — None without a projector —, materials argument, the image without extra emitters at direct light and its float64
+    restatement — None, None unless `direct`)"""
+    key = (corner, film, principled, gaussian, spp, seed, direct)
+    if key not in _CORNERS:
+        ms, sd, world = load(corner(film, principled), gaussian, 1)
+        rows = ms.albedo.cpu().numpy().astype(np.float64)
+        tex = rand_tex(sd, 1) if sd.proj.enabled else None
+        mats = ms.materials_arg(sd)
+        unlit = main_ref = None
+        if direct:
+            unlit = ms.geom.render_fwd(sd, mats, tex, spp, seed)
+            main_ref = ref_path.render_fwd(*world, sd, rows, tex.cpu().numpy(), spp, seed, 2, gaussian_stddev=0.5 if gaussian else None)
+        _CORNERS[key] = (ms, sd, world, rows, tex, mats, unlit, main_ref)
+    return _CORNERS[key]
 
 
 def loss(ms, sd, rows, tex, spp, seed, gimg, max_depth=2, rr_depth=5):

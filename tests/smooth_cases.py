@@ -35,7 +35,7 @@ def host_rows(sc):
     return (world_arrays(sc)[3] if rows is None else rows).astype(np.float64)
 
 
-def table(*lights):
+def host_table(*lights):
     """the [n, 24] table of ops.pack_lights in float64, stated here so that a test without the package's device side can build it"""
     from fireflies_amd import ops
 

@@ -1,14 +1,16 @@
-"""Helpers that tests with and without a GPU share: a scene's world arrays, copies of a scene description, finite-difference stencils, the outlier rule,
+"""Helpers that tests with and without a GPU share: a scene's world arrays, copies of a scene description, a loaded scene file, finite-difference stencils, the outlier rule and the
+three conditions of an independent evaluation,
 what include/ffx.h says, a C compiler, the oracle's geometry of a scene.  numpy, ctypes and the standard library beside the package's host-side
 modules: nothing here needs a device (tests/gpu_support.py holds what does)."""
 import ctypes as C
 import os
 import re
 import shutil
+import warnings
 
 import numpy as np
 
-from fireflies_amd import _abi, scenes
+from fireflies_amd import _abi, loaders, scene_desc, scenes
 from tests import tie_scenes
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -47,6 +49,22 @@ def world_arrays(sc):
     """-> (vertex pool in float64, triangles in pool indices, shape of every triangle, albedo rows): what the float64 restatements take"""
     pool, tris, shape, off, stride, nfr, alb = scenes.flatten(sc)
     return pool.astype(np.float64), tris + off[shape][:, None], shape, alb
+
+
+def arrays(sc, principled=False):
+    """-> (the description with shadows, (vertex pool, triangles, shape of every triangle), the material rows or the albedos): what the float64
+    restatements of the emitter suites take"""
+    sd = scene_desc.scene_desc(sc, shadows=True, mat_stride=16 if principled else 0)
+    verts, tri_idx, tri_shape, alb = world_arrays(sc)
+    return sd, (verts, tri_idx, tri_shape), scenes.material_rows(sc) if principled else alb
+
+
+def load_xml(path):
+    """-> (the scene of a Mitsuba-XML file, the loader's reports as strings)"""
+    with warnings.catch_warnings(record=True) as w:
+        warnings.simplefilter("always")
+        sc = loaders.load_mitsuba_xml(path)
+    return sc, [str(x.message) for x in w]
 
 
 def copy_desc(sd):
@@ -162,19 +180,34 @@ def fd4(f, rows, i, col, h):
 
 
 # ------------------------------------------------------------------ comparisons
-def independent_figures(got, ref, scale, part_sum):
-    """the figures of the three conditions of tests/test_lights_gpu.py's `independent`, each as a fraction of its bound: the share of the pixels off by
-    more than 2e-3 of the scale over 0.04, the median error over 1e-4 of the scale, the sums' difference over 1 % of the part under test"""
+def _independent(got, ref, scale, part_sum):
+    """-> (the three figures, their bounds): the share of the pixels off by more than 2e-3 of the scale [0.04], the median error [1e-4 of the scale], the
+    sums' difference [1 % of the part under test]"""
     err = np.abs(got - ref)
-    return float((err > 2e-3 * scale).mean()) / 0.04, float(np.median(err)) / (1e-4 * scale), float(abs(got.sum() - ref.sum())) / (0.01 * part_sum)
+    return (float((err > 2e-3 * scale).mean()), np.median(err), abs(got.sum() - ref.sum())), (0.04, 1e-4 * scale, 0.01 * part_sum)
+
+
+def _fractions(figures, bounds):
+    return tuple(float(v) / b for v, b in zip(figures, bounds))
+
+
+def independent_figures(got, ref, scale, part_sum):
+    """the figures of `independent`, each as a fraction of its bound"""
+    return _fractions(*_independent(got, ref, scale, part_sum))
 
 
 def independent(what, got, ref, scale, part_sum):
-    """tests/test_lights_gpu.py's three conditions on `independent_figures`; the figures are printed before they are asserted -> the figures"""
-    f = independent_figures(got, ref, scale, part_sum)
-    print(f"{what}: scale {scale:.4g}; as fractions of the bounds: pixels off by > 2e-3 scale {f[0]:.2e}, median {f[1]:.2e}, sums {f[2]:.2e}")
+    """the three conditions that an evaluation independent of its reference is held to: at most 0.04 of the pixels off by more than 2e-3 of the image's
+    scale, the median error within 1e-4 of it, the sums within 1 % of the part under test — the figures themselves against their bounds, no quotient
+    in between; they are printed before they are asserted -> the figures as fractions of the bounds"""
+    (off, median, dsum), bounds = _independent(got, ref, scale, part_sum)
+    f = _fractions((off, median, dsum), bounds)
+    print(f"{what}: scale {scale:.4g}, off by > 2e-3 scale {off:.4f} [0.04], median {median / scale:.2e} [1e-4], |sum - ref sum| {dsum:.4g} "
+          f"[{bounds[2]:.4g}]; as fractions of the bounds: pixels off by > 2e-3 scale {f[0]:.2e}, median {f[1]:.2e}, sums {f[2]:.2e}")
     assert np.isfinite(got).all() and part_sum > 0
-    assert f[0] <= 1.0 and f[1] <= 1.0 and f[2] <= 1.0, (what, f)
+    assert off <= bounds[0], what
+    assert median <= bounds[1], what
+    assert dsum <= bounds[2], what
     return f
 
 

@@ -10,6 +10,7 @@ import pytest
 import torch
 
 from fireflies_amd import _abi, _lib, ops, scenes
+from tests import refusals
 from tests.support import ROOT, enum_value, header
 
 
@@ -335,27 +336,9 @@ def test_ctypes_mirrors_have_the_compilers_layout(tmp_path):
             assert int(got[f"{cname}.{fname}"]) == getattr(cls, fname).offset, f"{cname}.{fname}"
 
 
-# the parameters of every render entry point, in order (include/ffx.h); `s` is the stream
-_RENDER_PARAMS = {
-    "ffx_render_fwd": "bvh info sd mats tex spp seed flags img s",
-    "ffx_render_fwd_cache": "bvh info sd mats tex spp seed flags img cache s",
-    "ffx_render_fwd_adjoint": "bvh info sd mats tex spp seed flags img gimg gtex dot s",
-    "ffx_render_fwd_filtered": "bvh info sd mats tex spp seed flags img scratch s",
-    "ffx_render_fwd_adjoint_filtered": "bvh info sd mats tex spp seed flags img gimg gtex scratch s",
-    "ffx_render_fwd_cache_filtered": "bvh info sd mats tex spp seed flags img cache scratch s",
-    "ffx_render_bwd": "bvh info sd mats spp seed flags gimg gtex s",
-    "ffx_render_bwd_filtered": "bvh info sd mats spp seed flags gimg gtex scratch s",
-    "ffx_render_bwd_det": "bvh info sd mats spp seed flags gimg gtex workspace s",
-    "ffx_render_bwd_det_part": "bvh info sd mats spp seed flags gimg part scale_log2 acc workspace s",
-    "ffx_render_bwd_cached": "sd mats cache spp gimg gtex img flags dot s",
-    "ffx_render_bwd_cached_l1": "sd mats cache spp img target weight gtex dot s",
-    "ffx_render_bwd_cached_filtered": "sd mats cache spp seed gimg gtex s",
-    "ffx_trace_primary": "bvh info cam spp flags seed t_out shape_out prim_out s",
-}
 _P3 = _abi.render_path(3, 5)
 _APP = _abi.RENDER_GRAD_APPEARANCE
-_GAUSS = {"rfilter": _abi.RFILTER_GAUSSIAN}
-_MISALIGNED = "misaligned"  # stands for a host address 4 bytes off a 16-byte boundary
+_GAUSS, _MISALIGNED = refusals.GAUSS, refusals.MISALIGNED
 _BASE_TEX = {"mat_stride": _abi.MAT_STRIDE, "n_base_tex": 1, "base_tex_w": (4,), "base_tex_h": (4,), "base_tex": ("buf",), "slot_uv": "buf"}
 _ARG, _UNS = enum_value("FFX_ERR_ARG"), enum_value("FFX_ERR_UNSUPPORTED")
 # (entry point, scene / bvh info changes, argument changes, return code, message substring)
@@ -465,33 +448,7 @@ def test_render_entry_points_refuse_before_any_launch(case, monkeypatch):
     """every render entry point's refusals that come before its first launch, in the order the host code checks them: host dummy
     pointers that the library never dereferences, a one-triangle bvh info without normals or apex areas (so that nothing can launch)"""
     name, sd_changes, arg_changes, rc, msg = case
-    for knob in ("FFX_TRAVERSAL", "FFX_WIDE"):
-        monkeypatch.delenv(knob, raising=False)
-    lib = _lib.api().lib
-    buf = np.zeros(64, np.float32)
-    addr = (buf.ctypes.data + 15) & ~15
-    eye = _abi.mat16(np.eye(4))
-    sd = _abi.SceneDesc()
-    sd.cam.to_world, sd.cam.camera_to_sample, sd.cam.width, sd.cam.height = eye, eye, 4, 4
-    sd.proj.to_world, sd.proj.camera_to_sample, sd.proj.tex_w, sd.proj.tex_h, sd.proj.tex_channels, sd.proj.enabled = eye, eye, 4, 4, 1, 1
-    sd.n_shapes = 1
-    info = _abi.BvhInfo(n_tris=1, n_nodes=1, max_depth=1, off_tq=64)
-    val = lambda v: addr if v == "buf" else (addr + 4 if v == _MISALIGNED else v)  # noqa: E731
-    for key, v in sd_changes.items():
-        obj, attr = (info, key[5:]) if key.startswith("info.") else (sd, key)
-        while "." in attr:
-            head, attr = attr.split(".", 1)
-            obj = getattr(obj, head)
-        if isinstance(v, tuple):
-            getattr(obj, attr)[: len(v)] = [val(x) for x in v]
-        else:
-            setattr(obj, attr, val(v))
-    args = dict(bvh=addr, info=C.byref(info), sd=C.byref(sd), cam=C.byref(sd.cam), mats=addr, tex=addr, spp=4, seed=1, flags=0, img=addr, cache=addr,
-                scratch=addr, gimg=addr, gtex=addr, dot=addr, target=addr, weight=1.0, workspace=addr, part=1, scale_log2=0, acc=addr, t_out=addr,
-                shape_out=addr, prim_out=addr, s=None)
-    args.update({k: val(v) for k, v in arg_changes.items()})
-    got = getattr(lib, name)(*[args[p] for p in _RENDER_PARAMS[name].split()])
-    err = (lib.ffx_last_error() or b"").decode()
+    got, err = refusals.call(name, sd_changes, arg_changes, monkeypatch=monkeypatch)
     assert got == rc, (got, err)
     if msg:
         assert msg in err, err

@@ -1,19 +1,18 @@
 """The constant emitter without a GPU: the header's macros against _abi, the [table | lights | ambient] buffer, the refusals of
 FFX_RENDER_AMBIENT that come before any launch, the loader, the record mi.Scene forms from its parameter map, tests/ref_ambient.py's own identities, and
 — on ref_ambient alone — the preconditions of the comparisons tests/test_ambient_gpu.py makes."""
-import ctypes as C
 import types
-import warnings
 
 import numpy as np
 import pytest
 import torch
 
-from fireflies_amd import _abi, _lib, loaders, mi, ops, scene_desc, scenes
+from fireflies_amd import _abi, mi, ops, scenes
 from tests import ambient_scenes as am
 from tests import ref_ambient as ra
 from tests import ref_path as rp
-from tests.support import FFX_ERR_ARG, FFX_ERR_UNSUPPORTED, define, header, host_tex, world_arrays
+from tests import refusals
+from tests.support import FFX_ERR_ARG, FFX_ERR_UNSUPPORTED, arrays, define, header, host_tex, independent, load_xml
 
 
 # ------------------------------------------------------------------ header and ABI
@@ -66,19 +65,7 @@ def test_pack_ambient_and_the_buffer_behind_the_lights():
         ops._dev = orig
 
 
-# ------------------------------------------------------------------ refusals (tests/test_lights_cpu.py's set-up)
-_PARAMS = {
-    "ffx_render_fwd": "bvh info sd mats tex spp seed flags img s",
-    "ffx_render_fwd_filtered": "bvh info sd mats tex spp seed flags img scratch s",
-    "ffx_render_fwd_cache": "bvh info sd mats tex spp seed flags img cache s",
-    "ffx_render_fwd_cache_filtered": "bvh info sd mats tex spp seed flags img cache scratch s",
-    "ffx_render_fwd_adjoint": "bvh info sd mats tex spp seed flags img gimg gtex dot s",
-    "ffx_render_fwd_adjoint_filtered": "bvh info sd mats tex spp seed flags img gimg gtex scratch s",
-    "ffx_render_bwd": "bvh info sd mats spp seed flags gimg gtex s",
-    "ffx_render_bwd_filtered": "bvh info sd mats spp seed flags gimg gtex scratch s",
-    "ffx_render_bwd_det": "bvh info sd mats spp seed flags gimg gtex scratch s",
-    "ffx_render_bwd_det_part": "bvh info sd mats spp seed flags gimg part scale acc scratch s",
-}
+# ------------------------------------------------------------------ refusals (tests/refusals.py's set-up)
 _A, _L1 = _abi.RENDER_AMBIENT, _abi.render_lights(1)
 _ONLY = "FFX_RENDER_AMBIENT is served by ffx_render_fwd[_filtered] only"
 _GRAD = "FFX_RENDER_AMBIENT is not served together with a FFX_RENDER_GRAD_* bit"
@@ -113,28 +100,9 @@ _REFUSALS = [
 
 @pytest.mark.parametrize("case", _REFUSALS, ids=lambda c: f"{c[0][4:]}-{c[1]:#x}-{'nomats' if c[2] else 'mats'}")
 def test_the_bit_is_refused_before_any_launch(case, monkeypatch):
-    """host dummy pointers that the library never dereferences, a one-triangle bvh info without normals, apex areas or a wide tree (so that nothing can
-    launch)"""
+    """tests/refusals.py's set-up (nothing can launch), with this suite's own default: no dot_out / loss_slots buffer"""
     name, flags, arg_changes, rc, msg = case
-    for knob in ("FFX_TRAVERSAL", "FFX_WIDE"):
-        monkeypatch.delenv(knob, raising=False)
-    lib = _lib.api().lib
-    buf = np.zeros(64, np.float32)
-    addr = (buf.ctypes.data + 15) & ~15
-    eye = _abi.mat16(np.eye(4))
-    sd = _abi.SceneDesc()
-    sd.cam.to_world, sd.cam.camera_to_sample, sd.cam.width, sd.cam.height = eye, eye, 4, 4
-    sd.proj.to_world, sd.proj.camera_to_sample, sd.proj.tex_w, sd.proj.tex_h, sd.proj.tex_channels, sd.proj.enabled = eye, eye, 4, 4, 1, 1
-    sd.n_shapes = 1
-    if "filtered" in name:
-        sd.rfilter = _abi.RFILTER_GAUSSIAN
-    info = _abi.BvhInfo(n_tris=1, n_nodes=1, max_depth=1, off_tq=64)
-    args = dict(bvh=addr, info=C.byref(info), sd=C.byref(sd), mats=addr, tex=addr, spp=4, seed=1, flags=flags, img=addr, cache=addr, scratch=addr, gimg=addr,
-                gtex=addr, dot=None, part=1, scale=0, acc=addr, s=None)
-    args.update(arg_changes)
-    got = getattr(lib, name)(*[args[p] for p in _PARAMS[name].split()])
-    err = (lib.ffx_last_error() or b"").decode()
-    print(name, hex(flags), got, err)
+    got, err = refusals.call(name, refusals.GAUSS if "filtered" in name else {}, {"flags": flags, "dot": None, **arg_changes}, monkeypatch=monkeypatch)
     assert got == rc, (got, err)
     assert msg in err, err
 
@@ -155,33 +123,26 @@ def test_the_python_layers_refuse_what_the_library_would():
 
 
 # ------------------------------------------------------------------ the loader
-def _load(path):
-    with warnings.catch_warnings(record=True) as w:
-        warnings.simplefilter("always")
-        sc = loaders.load_mitsuba_xml(path)
-    return sc, [str(x.message) for x in w]
-
-
 def test_the_loader_reads_the_constant_emitter(tmp_path):
-    sc, reports = _load(am.write_scene(tmp_path))
+    sc, reports = load_xml(am.write_scene(tmp_path))
     print(reports)
     assert isinstance(sc.ambient, scenes.AmbientData) and sc.ambient.name == "emit-World" and sc.ambient.radiance == (0.8, 1.0, 1.3)
     assert sc.spot is not None and sc.projector is not None and sc.lights == []
     assert not any("constant" in r for r in reports), reports
     # a single float; an emitter without id or radiance: Mitsuba's default radiance 1
-    sc1, r1 = _load(am.write_scene(tmp_path, am.XML.replace(am.WORLD, '<emitter type="constant" id="sky"><float name="radiance" value="0.25"/></emitter>'), "f.xml"))
+    sc1, r1 = load_xml(am.write_scene(tmp_path, am.XML.replace(am.WORLD, '<emitter type="constant" id="sky"><float name="radiance" value="0.25"/></emitter>'), "f.xml"))
     assert sc1.ambient.name == "sky" and sc1.ambient.radiance == (0.25, 0.25, 0.25) and not any("constant" in r for r in r1)
-    sc2, _ = _load(am.write_scene(tmp_path, am.XML.replace(am.WORLD, '<emitter type="constant"/>'), "d.xml"))
+    sc2, _ = load_xml(am.write_scene(tmp_path, am.XML.replace(am.WORLD, '<emitter type="constant"/>'), "d.xml"))
     assert sc2.ambient.name == "emit-Constant" and sc2.ambient.radiance == (1.0, 1.0, 1.0)
     # an unknown property is reported as for the other emitters
-    _, r3 = _load(am.write_scene(tmp_path, am.XML.replace(am.WORLD, '<emitter type="constant" id="w"><rgb name="radiance" value="1"/><float name="scale" value="2"/></emitter>'),
+    _, r3 = load_xml(am.write_scene(tmp_path, am.XML.replace(am.WORLD, '<emitter type="constant" id="w"><rgb name="radiance" value="1"/><float name="scale" value="2"/></emitter>'),
                                  "p.xml"))
     assert any("constant emitter property 'scale' is ignored" in r for r in r3), r3
 
 
 def test_a_second_constant_emitter_is_reported_once_and_ignored(tmp_path):
     more = "".join(f'<emitter type="constant" id="second-{k}"><rgb name="radiance" value="9"/></emitter>' for k in range(2))
-    sc, reports = _load(am.write_scene(tmp_path, am.XML.replace("</scene>", more + "</scene>"), "two.xml"))
+    sc, reports = load_xml(am.write_scene(tmp_path, am.XML.replace("</scene>", more + "</scene>"), "two.xml"))
     assert sc.ambient.name == "emit-World" and sc.ambient.radiance == (0.8, 1.0, 1.3)
     told = [r for r in reports if "second constant emitter" in r]
     assert len(told) == 1 and "second-0" in told[0], reports
@@ -190,12 +151,12 @@ def test_a_second_constant_emitter_is_reported_once_and_ignored(tmp_path):
 def test_envmap_and_area_emitters_stay_reported_and_a_file_without_the_emitter_is_unchanged(tmp_path):
     xml = am.XML.replace(am.WORLD, '<emitter type="envmap" id="sky"><string name="filename" value="e.exr"/></emitter>')
     xml = xml.replace('</bsdf></shape>', '</bsdf><emitter type="area"><rgb name="radiance" value="1"/></emitter></shape>', 1)
-    sc, reports = _load(am.write_scene(tmp_path, xml, "env.xml"))
+    sc, reports = load_xml(am.write_scene(tmp_path, xml, "env.xml"))
     assert sc.ambient is None
     assert any("emitter type 'envmap' ignored" in r for r in reports), reports
     assert any("area emitter on a shape ignored" in r for r in reports), reports
-    plain, r0 = _load(am.write_scene(tmp_path, am.XML.replace(am.WORLD, ""), "plain.xml"))
-    with_w, r1 = _load(am.write_scene(tmp_path))
+    plain, r0 = load_xml(am.write_scene(tmp_path, am.XML.replace(am.WORLD, ""), "plain.xml"))
+    with_w, r1 = load_xml(am.write_scene(tmp_path))
     assert plain.ambient is None and with_w.ambient is not None and r0 == [r.replace("ambient.xml", "plain.xml") for r in r1]
     assert np.array_equal(plain.spot.to_world, with_w.spot.to_world) and plain.spot.intensity == with_w.spot.intensity
     assert (plain.projector_scale, plain.lights, len(plain.meshes)) == (with_w.projector_scale, with_w.lights, len(with_w.meshes))
@@ -219,23 +180,17 @@ def test_the_ambient_record_follows_the_parameter_map():
 
 
 # ------------------------------------------------------------------ ref_ambient's own identities
-def _arrays(sc, principled=False):
-    sd = scene_desc.scene_desc(sc, shadows=True, mat_stride=16 if principled else 0)
-    verts, tri_idx, tri_shape, alb = world_arrays(sc)
-    return sd, (verts, tri_idx, tri_shape), scenes.material_rows(sc) if principled else alb
-
-
 @pytest.mark.parametrize("gaussian", [False, True])
 def test_the_closed_forms(gaussian):
     """one Lambert quad that fills the film at max_depth 2: every closing ray escapes and f is the base colour — every pixel base x L_a; the camera turned
     away: every pixel L_a"""
     La, std = np.array([0.8, 1.0, 1.3]), 0.5 if gaussian else None
-    sd, world, alb = _arrays(am.quad())
+    sd, world, alb = arrays(am.quad())
     parts = {}
     img = ra.render_ambient(*world, sd, alb, La, 4, 3, gaussian_stddev=std, parts=parts)
     np.testing.assert_allclose(img, np.broadcast_to(np.asarray(am.QUAD_RGB, np.float32).astype(np.float64) * La, img.shape), rtol=1e-12)
     assert parts["closing"] == parts["escaped"] == 24 * 24 * 4 and parts[0].sum() == 0.0
-    sd, world, alb = _arrays(am.quad(away=True))
+    sd, world, alb = arrays(am.quad(away=True))
     parts = {}
     img = ra.render_ambient(*world, sd, alb, La, 4, 3, gaussian_stddev=std, parts=parts)
     np.testing.assert_allclose(img, np.broadcast_to(La, img.shape), rtol=1e-12)
@@ -243,7 +198,7 @@ def test_the_closed_forms(gaussian):
 
 
 def test_the_term_of_a_vertex_does_not_depend_on_max_depth_and_the_part_is_linear():
-    sd, world, alb = _arrays(am.corner("21x19"))
+    sd, world, alb = arrays(am.corner("21x19"))
     p2, p3, p4 = {}, {}, {}
     L2 = ra.sample_radiance(*world, sd, alb, am.RADIANCE, 4, 3, max_depth=2, rr_depth=99, parts=p2)
     L3 = ra.sample_radiance(*world, sd, alb, am.RADIANCE, 4, 3, max_depth=3, rr_depth=99, parts=p3)
@@ -261,7 +216,7 @@ def test_the_term_of_a_vertex_does_not_depend_on_max_depth_and_the_part_is_linea
 def test_the_roulette_on_the_closing_ray_keeps_the_mean():
     """rr_depth 1: every bounce — the closing one too — survives with q = min(max beta f, 0.95) and is divided by q; over many samples the part's sum
     is that without roulette (an unbiased estimator: 3 % at 21 x 19 x 64 samples), and the kept samples are fewer"""
-    sd, world, alb = _arrays(am.corner("21x19"))
+    sd, world, alb = arrays(am.corner("21x19"))
     on, off = {}, {}
     a = ra.sample_radiance(*world, sd, alb, am.RADIANCE, 64, 5, max_depth=2, rr_depth=1, parts=on)
     b = ra.sample_radiance(*world, sd, alb, am.RADIANCE, 64, 5, max_depth=2, rr_depth=99, parts=off)
@@ -271,21 +226,13 @@ def test_the_roulette_on_the_closing_ray_keeps_the_mean():
 
 
 # ------------------------------------------------------------------ the preconditions of tests/test_ambient_gpu.py's comparisons
-def _caps(what, got, ref, scale, part_sum):
-    err = np.abs(got - ref)
-    off = float((err > 2e-3 * scale).mean())
-    print(f"{what}: scale {scale:.4g}, off by > 2e-3 scale {off:.4f} [0.04], median {np.median(err) / scale:.2e} [1e-4], "
-          f"|sum - ref sum| {abs(got.sum() - ref.sum()):.4g} [{0.01 * part_sum:.4g}]")
-    assert off <= 0.04 and np.median(err) <= 1e-4 * scale and abs(got.sum() - ref.sum()) <= 0.01 * part_sum
-
-
 @pytest.mark.parametrize("film", sorted(am.FILMS))
 @pytest.mark.parametrize("principled", [False, True])
 def test_the_ambient_part_matters_and_single_precision_stays_inside_the_caps(film, principled):
     """the part under test is well above zero in the scenes of the GPU tests, at every depth they use, on both films; and the same statement with every
     ray, point and weight rounded to float32 stays inside the three caps the GPU comparison is held to"""
     sc = am.corner(film, principled)
-    sd, world, mats = _arrays(sc, principled)
+    sd, world, mats = arrays(sc, principled)
     spp, seed = 16, 7
     for depth, rr in ((2, 5), (3, 5), (4, 5), (4, 1)):
         main = rp.render_fwd(*world, sd, mats, host_tex(sc), spp, seed, depth, rr)
@@ -296,5 +243,5 @@ def test_the_ambient_part_matters_and_single_precision_stays_inside_the_caps(fil
             print(film, principled, depth, rr, std, "share of the image's mean", share, "closing", parts["closing"], "escaped", parts["escaped"])
             assert share > 0.05 and 0 < parts["escaped"] and parts["closing"] > 0
             single = ra.render_ambient(*world, sd, mats, am.RADIANCE, spp, seed, depth, rr, gaussian_stddev=std, round32=True)
-            _caps(f"{film} principled={principled} depth {depth} rr {rr} gaussian={std is not None}: float32-rounded against float64", single, part,
-                  float((main + part).max()), float(part.sum()))
+            independent(f"{film} principled={principled} depth {depth} rr {rr} gaussian={std is not None}: float32-rounded against float64", single, part,
+                        float((main + part).max()), float(part.sum()))

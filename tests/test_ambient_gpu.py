@@ -1,6 +1,6 @@
 """The constant emitter on the GPU: k_lights_fwd<RF, DIR, AMB> in closed form, against the float64 restatement (tests/ref_ambient.py) on both
 films, film sizes and row kinds at max_depth 2, 3 and 4, the identities, the arms a small case misses, the adjoint, and the public interface.
-Independent evaluations are held to the three conditions of the path and lights tests, the same computation by another route to rtol 1e-5, atol 1e-7."""
+Independent evaluations are held to the three conditions of tests/support.py's `independent`, the same computation by another route to rtol 1e-5, atol 1e-7."""
 import numpy as np
 import pytest
 import torch
@@ -13,39 +13,20 @@ from tests import light_scenes as ls
 from tests import ref_ambient as ra
 from tests import ref_path as rp
 from tests.gpu_support import DEV
+from tests.support import independent
 
 pytestmark = pytest.mark.gpu
 
 SPP, SEED = 16, 7
 LA = am.RADIANCE
-
-
-def independent(what, got, ref, scale, part_sum):
-    """the three conditions: at most 0.04 of the pixels off by more than 2e-3 of the image's scale, the median error within 1e-4 of it, the sums within
-    1 % of the part under test; the figures are printed before they are asserted"""
-    err = np.abs(got - ref)
-    off = float((err > 2e-3 * scale).mean())
-    print(f"{what}: scale {scale:.4g}, off by > 2e-3 scale {off:.4f} [0.04], median {np.median(err) / scale:.2e} [1e-4], "
-          f"|sum - ref sum| {abs(got.sum() - ref.sum()):.4g} [{0.01 * part_sum:.4g}]")
-    assert np.isfinite(got).all() and part_sum > 0
-    assert off <= 0.04
-    assert np.median(err) <= 1e-4 * scale
-    assert abs(got.sum() - ref.sum()) <= 0.01 * part_sum
-
-
-_CASES = {}
+_RENDERED = {}
 
 
 def case(film, principled, gaussian, dark=False):
-    """a corner of ambient_scenes, loaded once: (scene, description, world arrays, rows in float64, texture, materials argument, {depth: the image
-    without the bit}, {depth: the float64 restatement of that image})"""
-    key = (film, principled, gaussian, dark)
-    if key not in _CASES:
-        ms, sd, world = gpu.load(am.dark_corner(film, principled) if dark else am.corner(film, principled), gaussian, 1)
-        rows = ms.albedo.cpu().numpy().astype(np.float64)
-        tex = None if dark else gpu.rand_tex(sd, 1)
-        _CASES[key] = (ms, sd, world, rows, tex, ms.materials_arg(sd), {}, {})
-    return _CASES[key]
+    """gpu.corner_case without its direct-light images; in their place {(depth, rr, spp): the image without the bit} and {(depth, rr, spp): the float64
+    restatement of that image}, filled by plain_of and main_ref_of"""
+    c = gpu.corner_case(am.dark_corner if dark else am.corner, film, principled, gaussian, SPP, SEED, direct=False)
+    return (*c[:6], *_RENDERED.setdefault((film, principled, gaussian, dark), ({}, {})))
 
 
 def plain_of(c, depth, rr=5, spp=SPP):

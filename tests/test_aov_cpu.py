@@ -1,16 +1,15 @@
 """The `aov` integrator without a GPU: mi.load_dict's parsing, names and refusals, the ABI constants against the header, the refusals
 of FFX_RENDER_AOV that come before any launch, and tests/ref_aov.py on a plane in closed form."""
-import ctypes as C
 import re
 
 import numpy as np
 import pytest
 
-from fireflies_amd import _abi, _lib, mi, ops, scene_desc, scenes
+from fireflies_amd import _abi, mi, ops, scene_desc, scenes
 from fireflies_amd import functional as Fn
 from fireflies_amd.optim import PatternOptimizer
-from tests import ref_aov
-from tests.support import FFX_ERR_ARG, FFX_ERR_UNSUPPORTED, header
+from tests import ref_aov, refusals
+from tests.support import FFX_ERR_ARG, FFX_ERR_UNSUPPORTED, define, header
 
 SERVED = ["albedo", "depth", "geo_normal", "position", "prim_index", "sh_normal", "shape_index", "uv"]
 
@@ -67,19 +66,13 @@ def test_abi_constants_agree_with_the_header():
     text = header()
     assert int(re.search(r"#define FFX_RENDER_AOV (0x[0-9a-fA-F]+)", text).group(1), 16) == _abi.RENDER_AOV == 0x100000
     assert int(re.search(r"#define FFX_RENDER_AOV_FLOATS (\d+)", text).group(1)) == _abi.RENDER_AOV_FLOATS == 17 == ref_aov.FLOATS
-    assert int(re.search(r"#define FFX_ABI_VERSION (\d+)", text).group(1)) == 11
+    assert define("FFX_ABI_VERSION") == 11
     assert ops.AOV_CHANNELS == ref_aov.CHANNELS
     taken = (_abi.RENDER_FP16 | _abi.RENDER_SPARSE_ADJOINT | _abi.RENDER_APEX_READY | _abi.RENDER_CACHE_ZEROED | _abi.RENDER_CACHE_KEEP_DROPPED
              | _abi.RENDER_PATH_MASK | _abi.RENDER_GRAD_APPEARANCE | _abi.RENDER_GRAD_MATERIAL | _abi.RENDER_GRAD_PRB | _abi.RENDER_TANGENT)
     assert _abi.RENDER_AOV & taken == 0
 
 
-_PARAMS = {
-    "ffx_render_fwd": "bvh info sd mats tex spp seed flags img s",
-    "ffx_render_fwd_filtered": "bvh info sd mats tex spp seed flags img scratch s",
-    "ffx_render_fwd_cache": "bvh info sd mats tex spp seed flags img cache s",
-    "ffx_render_bwd": "bvh info sd mats spp seed flags gimg gtex s",
-}
 _AOV = _abi.RENDER_AOV
 _REFUSALS = [
     ("ffx_render_fwd", _AOV | _abi.RENDER_FP16, {}, FFX_ERR_UNSUPPORTED, "render_fwd: FFX_RENDER_AOV has no fp16 film"),
@@ -98,28 +91,9 @@ _REFUSALS = [
 
 @pytest.mark.parametrize("case", _REFUSALS, ids=lambda c: f"{c[0][4:]}-{c[1]:#x}-{'nomats' if c[2] else 'mats'}")
 def test_the_bit_is_refused_before_any_launch(case, monkeypatch):
-    """tests/test_abi_cpu.py's set-up: host dummy pointers that the library never dereferences, a one-triangle bvh info without normals or apex
-    areas (so that nothing can launch)"""
+    """tests/refusals.py's set-up: nothing can launch"""
     name, flags, arg_changes, rc, msg = case
-    for knob in ("FFX_TRAVERSAL", "FFX_WIDE"):
-        monkeypatch.delenv(knob, raising=False)
-    lib = _lib.api().lib
-    buf = np.zeros(64, np.float32)
-    addr = (buf.ctypes.data + 15) & ~15
-    eye = _abi.mat16(np.eye(4))
-    sd = _abi.SceneDesc()
-    sd.cam.to_world, sd.cam.camera_to_sample, sd.cam.width, sd.cam.height = eye, eye, 4, 4
-    sd.proj.to_world, sd.proj.camera_to_sample, sd.proj.tex_w, sd.proj.tex_h, sd.proj.tex_channels, sd.proj.enabled = eye, eye, 4, 4, 1, 1
-    sd.n_shapes = 1
-    if "filtered" in name:
-        sd.rfilter = _abi.RFILTER_GAUSSIAN
-    info = _abi.BvhInfo(n_tris=1, n_nodes=1, max_depth=1, off_tq=64)
-    args = dict(bvh=addr, info=C.byref(info), sd=C.byref(sd), mats=addr, tex=addr, spp=4, seed=1, flags=flags, img=addr, cache=addr, scratch=addr, gimg=addr,
-                gtex=addr, s=None)
-    args.update(arg_changes)
-    got = getattr(lib, name)(*[args[p] for p in _PARAMS[name].split()])
-    err = (lib.ffx_last_error() or b"").decode()
-    print(name, hex(flags), got, err)
+    got, err = refusals.call(name, refusals.GAUSS if "filtered" in name else {}, {"flags": flags, **arg_changes}, monkeypatch=monkeypatch)
     assert got == rc, (got, err)
     assert msg in err, err
 

@@ -1,15 +1,14 @@
-"""The extra emitters' adjoint without a GPU: the bit in the header and the ABI module, its refusals before any launch (the
-dummy-pointer set-up of tests/test_sun_cpu.py: nothing can launch), ops.render_bwd's argument checks, and mi.Scene's two leaf registries."""
-import ctypes as C
+"""The extra emitters' adjoint without a GPU: the bit in the header and the ABI module, its refusals before any launch
+(tests/refusals.py's set-up: nothing can launch), ops.render_bwd's argument checks, and mi.Scene's two leaf registries."""
 import re
 import types
 
-import numpy as np
 import pytest
 import torch
 
-from fireflies_amd import _abi, _lib, mi, ops, scenes
+from fireflies_amd import _abi, mi, ops, scenes
 from tests import light_scenes as ls
+from tests import refusals
 from tests import sun_scenes as ss
 from tests.support import FFX_ERR_ARG, FFX_ERR_UNSUPPORTED, define, header
 
@@ -33,19 +32,6 @@ def test_the_headers_bit_equals_abis_and_overlaps_no_other_flag():
 
 
 # ------------------------------------------------------------------ 2. refusals before any launch
-_PARAMS = {
-    "ffx_render_fwd": "bvh info sd mats tex spp seed flags img s",
-    "ffx_render_fwd_filtered": "bvh info sd mats tex spp seed flags img scratch s",
-    "ffx_render_fwd_cache": "bvh info sd mats tex spp seed flags img cache s",
-    "ffx_render_fwd_cache_filtered": "bvh info sd mats tex spp seed flags img cache scratch s",
-    "ffx_render_fwd_adjoint": "bvh info sd mats tex spp seed flags img gimg gtex dot s",
-    "ffx_render_fwd_adjoint_filtered": "bvh info sd mats tex spp seed flags img gimg gtex scratch s",
-    "ffx_render_bwd": "bvh info sd mats spp seed flags gimg gtex s",
-    "ffx_render_bwd_filtered": "bvh info sd mats spp seed flags gimg gtex scratch s",
-    "ffx_render_bwd_det": "bvh info sd mats spp seed flags gimg gtex scratch s",
-    "ffx_render_bwd_det_part": "bvh info sd mats spp seed flags gimg part scale acc scratch s",
-    "ffx_render_bwd_cached": "sd mats cache spp gimg gtex img flags dot s",
-}
 _E, _D, _L1, _A = _abi.RENDER_EMITTER_GRAD, _abi.RENDER_LIGHTS_DIRECTIONAL, _abi.render_lights(1), _abi.RENDER_AMBIENT
 _GRAD = "is not served together with a FFX_RENDER_GRAD_* bit"
 _ONLY = "FFX_RENDER_EMITTER_GRAD is served by ffx_render_bwd[_filtered] only"
@@ -93,28 +79,9 @@ _REFUSALS = [
 
 @pytest.mark.parametrize("case", _REFUSALS, ids=lambda c: f"{c[0][4:]}-{c[1]:#x}-{'nomats' if c[2] else 'mats'}")
 def test_the_bit_is_refused_before_any_launch(case, monkeypatch):
-    """host dummy pointers that the library never dereferences, a one-triangle bvh info without normals, apex areas or a wide tree (so that nothing can
-    launch)"""
+    """tests/refusals.py's set-up (nothing can launch), with this suite's own default: no dot_out / loss_slots buffer"""
     name, flags, arg_changes, rc, msg = case
-    for knob in ("FFX_TRAVERSAL", "FFX_WIDE"):
-        monkeypatch.delenv(knob, raising=False)
-    lib = _lib.api().lib
-    buf = np.zeros(64, np.float32)
-    addr = (buf.ctypes.data + 15) & ~15
-    eye = _abi.mat16(np.eye(4))
-    sd = _abi.SceneDesc()
-    sd.cam.to_world, sd.cam.camera_to_sample, sd.cam.width, sd.cam.height = eye, eye, 4, 4
-    sd.proj.to_world, sd.proj.camera_to_sample, sd.proj.tex_w, sd.proj.tex_h, sd.proj.tex_channels, sd.proj.enabled = eye, eye, 4, 4, 1, 1
-    sd.n_shapes = 1
-    if "filtered" in name:
-        sd.rfilter = _abi.RFILTER_GAUSSIAN
-    info = _abi.BvhInfo(n_tris=1, n_nodes=1, max_depth=1, off_tq=64)
-    args = dict(bvh=addr, info=C.byref(info), sd=C.byref(sd), mats=addr, tex=addr, spp=4, seed=1, flags=flags, img=addr, cache=addr, scratch=addr, gimg=addr,
-                gtex=addr, dot=None, part=1, scale=0, acc=addr, s=None)
-    args.update(arg_changes)
-    got = getattr(lib, name)(*[args[p] for p in _PARAMS[name].split()])
-    err = (lib.ffx_last_error() or b"").decode()
-    print(name, hex(flags), got, err)
+    got, err = refusals.call(name, refusals.GAUSS if "filtered" in name else {}, {"flags": flags, "dot": None, **arg_changes}, monkeypatch=monkeypatch)
     assert got == rc, (got, err)
     assert msg in err, err
 

@@ -12,7 +12,7 @@ from tests import ref_ambient as ra
 from tests import ref_path as rp
 from tests import ref_sun as rs
 from tests import sun_scenes as ss
-from tests.gpu_support import DEV
+from tests.gpu_support import DEV, table
 
 pytestmark = pytest.mark.gpu
 
@@ -25,21 +25,10 @@ LA = (0.2, 0.25, 0.3)
 RTOL = 6e-7
 
 
-def table(*lights):
-    return ops.pack_lights(lights).to(DEV)
-
-
-_CASES = {}
-
-
 def case(film, principled, gaussian):
-    """a corner of sun_scenes, loaded once: (scene, description, world arrays, rows in float64, texture, materials argument, image gradient)"""
-    key = (film, principled, gaussian)
-    if key not in _CASES:
-        ms, sd, world = gpu.load(ss.corner(film, principled), gaussian, 1)
-        rows = ms.albedo.cpu().numpy().astype(np.float64)
-        _CASES[key] = (ms, sd, world, rows, gpu.rand_tex(sd, 1), ms.materials_arg(sd), gpu.rand_gimg(sd, 3))
-    return _CASES[key]
+    """gpu.corner_case on sun_scenes without its direct-light images; in their place the image gradient"""
+    c = gpu.corner_case(ss.corner, film, principled, gaussian, SPP, SEED, direct=False)
+    return (*c[:6], gpu.rand_gimg(c[1], 3))
 
 
 def fwd(ms, sd, mats, tex, t=None, amb=None, depth=2, spp=SPP):
@@ -113,7 +102,7 @@ def test_the_block_is_the_forwards_inner_product(principled, gaussian, film, dep
 # ------------------------------------------------------------------ 2. against float64, every ray against every triangle
 @pytest.mark.parametrize("depth,principled,gaussian,film", [(2, False, False, "21x19"), (2, True, True, "24x24"), (3, True, False, "24x24"), (3, False, True, "21x19")])
 def test_the_block_matches_the_float64_restatement(depth, principled, gaussian, film):
-    """the inner product is a weighted image sum: held to 1 % of the sum, the third of tests/test_lights_gpu.py's conditions for independent evaluations"""
+    """the inner product is a weighted image sum: held to 1 % of the sum, the third of the conditions of tests/support.py's `independent`"""
     ms, sd, world, rows, tex, mats, gimg = case(film, principled, gaussian)
     lights = [ls.POINT, ls.SPOT_B, ss.SUN_A]
     t = table(*lights)

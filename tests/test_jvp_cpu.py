@@ -1,8 +1,7 @@
-"""Forward mode (FFX_RENDER_TANGENT) without a GPU: the bit in the header and in _abi, the refusals that come before any launch (host
-dummy pointers, as tests/test_abi_cpu.py's), the packing of the tangent blocks behind the texture, mi.render_forward's key and integrator rules (on a
+"""Forward mode (FFX_RENDER_TANGENT) without a GPU: the bit in the header and in _abi, the refusals that come before any launch
+(tests/refusals.py's set-up), the packing of the tangent blocks behind the texture, mi.render_forward's key and integrator rules (on a
 stand-in for the scene: they are decided before the geometry is touched) and the float64 tangent that tests/test_jvp_gpu.py compares to — central
 differences of tests/ref_prb.render_fwd_frozen along the tangent, with the linear parts (texture, spot intensity) taken exactly."""
-import ctypes as C
 import re
 import types
 
@@ -10,13 +9,13 @@ import numpy as np
 import pytest
 import torch
 
-from fireflies_amd import _abi, _lib, mi, ops, scene_desc, scenes
-from tests import ref_prb
+from fireflies_amd import _abi, mi, ops, scene_desc, scenes
+from tests import ref_prb, refusals
 from tests.corner_scenes import small_corner
 from tests.support import FFX_ERR_ARG, FFX_ERR_UNSUPPORTED, copy_desc, define, header, world_arrays
 
 TAN = 0x80000
-GAUSS = {"rfilter": _abi.RFILTER_GAUSSIAN}
+GAUSS = refusals.GAUSS
 R0 = scenes.MAT_COLUMN["roughness"]
 
 
@@ -31,19 +30,6 @@ def test_bit_in_header_and_abi_agree_and_the_abi_is_frozen():
     assert "render_jvp" not in h and "ffx_render_forward" not in h  # (no new entry point: the bit rides on ffx_render_fwd[_filtered])
 
 
-_PARAMS = {
-    "ffx_render_fwd": "bvh info sd mats tex spp seed flags img s",
-    "ffx_render_fwd_cache": "bvh info sd mats tex spp seed flags img cache s",
-    "ffx_render_fwd_adjoint": "bvh info sd mats tex spp seed flags img gimg gtex dot s",
-    "ffx_render_fwd_filtered": "bvh info sd mats tex spp seed flags img scratch s",
-    "ffx_render_fwd_adjoint_filtered": "bvh info sd mats tex spp seed flags img gimg gtex scratch s",
-    "ffx_render_fwd_cache_filtered": "bvh info sd mats tex spp seed flags img cache scratch s",
-    "ffx_render_bwd": "bvh info sd mats spp seed flags gimg gtex s",
-    "ffx_render_bwd_filtered": "bvh info sd mats spp seed flags gimg gtex scratch s",
-    "ffx_render_bwd_det": "bvh info sd mats spp seed flags gimg gtex workspace s",
-    "ffx_render_bwd_det_part": "bvh info sd mats spp seed flags gimg part scale_log2 acc workspace s",
-    "ffx_render_bwd_cached": "sd mats cache spp gimg gtex img flags dot s",
-}
 _OTHERS = ("ffx_render_fwd_cache", "ffx_render_fwd_adjoint", "ffx_render_fwd_adjoint_filtered", "ffx_render_fwd_cache_filtered", "ffx_render_bwd",
            "ffx_render_bwd_filtered", "ffx_render_bwd_det", "ffx_render_bwd_det_part", "ffx_render_bwd_cached")
 _P3 = _abi.render_path(3, 5)
@@ -80,28 +66,7 @@ _CASES = [
 @pytest.mark.parametrize("case", _CASES, ids=lambda c: f"{c[0][4:]}-{c[3]}-{c[4][:48]}")
 def test_refusals_before_any_launch(case, monkeypatch):
     name, changes, arg_changes, rc, msg = case
-    for knob in ("FFX_TRAVERSAL", "FFX_WIDE"):
-        monkeypatch.delenv(knob, raising=False)
-    lib = _lib.api().lib
-    buf = np.zeros(64, np.float32)
-    addr = (buf.ctypes.data + 15) & ~15
-    eye = _abi.mat16(np.eye(4))
-    sd = _abi.SceneDesc()
-    sd.cam.to_world, sd.cam.camera_to_sample, sd.cam.width, sd.cam.height = eye, eye, 4, 4
-    sd.proj.to_world, sd.proj.camera_to_sample, sd.proj.tex_w, sd.proj.tex_h, sd.proj.tex_channels, sd.proj.enabled = eye, eye, 4, 4, 1, 1
-    sd.n_shapes = 1
-    info = _abi.BvhInfo(n_tris=1, n_nodes=1, max_depth=1, off_tq=64)
-    for key, v in changes.items():
-        obj, attr = (info, key[5:]) if key.startswith("info.") else (sd, key)
-        while "." in attr:
-            head, attr = attr.split(".", 1)
-            obj = getattr(obj, head)
-        setattr(obj, attr, v)
-    args = dict(bvh=addr, info=C.byref(info), sd=C.byref(sd), mats=addr, tex=addr, spp=4, seed=1, flags=0, img=addr, cache=addr, scratch=addr, gimg=addr,
-                gtex=addr, dot=addr, workspace=addr, part=1, scale_log2=0, acc=addr, s=None)
-    args.update(arg_changes)
-    got = getattr(lib, name)(*[args[p] for p in _PARAMS[name].split()])
-    err = (lib.ffx_last_error() or b"").decode()
+    got, err = refusals.call(name, changes, arg_changes, monkeypatch=monkeypatch)
     assert got == rc, (got, err)
     assert msg in err, err
 

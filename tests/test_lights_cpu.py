@@ -1,18 +1,17 @@
 """Extra emitters without a GPU: the header's macros against _abi, the loader's point lights and further spots, ops.pack_lights' layout,
 the refusals of FFX_RENDER_LIGHTS that come before any launch, tests/ref_lights.py against closed forms, and — on ref_lights alone — the preconditions of
 the comparisons tests/test_lights_gpu.py makes."""
-import ctypes as C
 import re
-import warnings
 
 import numpy as np
 import pytest
 
-from fireflies_amd import _abi, _lib, loaders, ops, scene_desc, scenes
+from fireflies_amd import _abi, ops, scene_desc, scenes
 from tests import light_scenes as ls
 from tests import ref_lights as rl
 from tests import ref_path as rp
-from tests.support import FFX_ERR_ARG, FFX_ERR_UNSUPPORTED, define, header, host_tex, world_arrays
+from tests import refusals
+from tests.support import FFX_ERR_ARG, FFX_ERR_UNSUPPORTED, define, header, host_tex, load_xml, world_arrays
 
 
 # ------------------------------------------------------------------ header and ABI
@@ -38,15 +37,8 @@ def test_the_header_declares_no_function_that_the_prototypes_lack():
 
 
 # ------------------------------------------------------------------ the loader
-def _load(path):
-    with warnings.catch_warnings(record=True) as w:
-        warnings.simplefilter("always")
-        sc = loaders.load_mitsuba_xml(path)
-    return sc, [str(x.message) for x in w]
-
-
 def test_point_lights_and_further_spots_are_kept_in_file_order(tmp_path):
-    sc, reports = _load(ls.write_scene(tmp_path))
+    sc, reports = load_xml(ls.write_scene(tmp_path))
     assert sc.spot is not None and sc.spot.name == "emit-Spot" and sc.spot.intensity == (8.0, 8.0, 8.0) and sc.spot.cutoff_angle == 30.0
     assert [(l.name, l.kind) for l in sc.lights] == [("emit-Light", "point"), ("emit-PointLight", "point"), ("emit-SecondSpot", "spot")]
     a, b, s2 = sc.lights
@@ -58,12 +50,12 @@ def test_point_lights_and_further_spots_are_kept_in_file_order(tmp_path):
     print(reports)
     assert not any("point" in r for r in reports), reports
     # the default intensity of a point light is 1
-    sc1, _ = _load(ls.write_scene(tmp_path, ls.with_extra_points(1), "one.xml"))
+    sc1, _ = load_xml(ls.write_scene(tmp_path, ls.with_extra_points(1), "one.xml"))
     assert sc1.lights[-1].intensity == (1.0, 1.0, 1.0) and np.allclose(np.asarray(sc1.lights[-1].to_world)[:3, 3], (0.0, 1.0, 2.0))
 
 
 def test_beyond_eight_extra_lights_the_rest_are_reported_once_and_dropped(tmp_path):
-    sc, reports = _load(ls.write_scene(tmp_path, ls.with_extra_points(7), "ten.xml"))  # 3 + 7 = 10 extra emitters
+    sc, reports = load_xml(ls.write_scene(tmp_path, ls.with_extra_points(7), "ten.xml"))  # 3 + 7 = 10 extra emitters
     assert len(sc.lights) == 8 and [l.name for l in sc.lights[:3]] == ["emit-Light", "emit-PointLight", "emit-SecondSpot"] and sc.lights[-1].name == "emit-More4"
     told = [r for r in reports if "dropped" in r and "emitters" in r]
     assert len(told) == 1, reports
@@ -71,7 +63,7 @@ def test_beyond_eight_extra_lights_the_rest_are_reported_once_and_dropped(tmp_pa
 
 def test_the_pinned_reports_keep_their_wording(tmp_path):
     xml = ls.XML.replace("</scene>", '<emitter type="envmap" id="env"/></scene>')
-    _, reports = _load(ls.write_scene(tmp_path, xml, "env.xml"))
+    _, reports = load_xml(ls.write_scene(tmp_path, xml, "env.xml"))
     assert any("emitter type 'envmap' ignored" in r for r in reports), reports
 
 
@@ -92,19 +84,7 @@ def test_pack_lights_matches_the_layout_word_for_word():
     np.testing.assert_array_equal(rl.table_row("spot", ls.SPOT_B.to_world, ls.SPOT_B.intensity, 35.0, 22.0).astype(np.float32), t[1])
 
 
-# ------------------------------------------------------------------ refusals (tests/test_aov_cpu.py's set-up)
-_PARAMS = {
-    "ffx_render_fwd": "bvh info sd mats tex spp seed flags img s",
-    "ffx_render_fwd_filtered": "bvh info sd mats tex spp seed flags img scratch s",
-    "ffx_render_fwd_cache": "bvh info sd mats tex spp seed flags img cache s",
-    "ffx_render_fwd_cache_filtered": "bvh info sd mats tex spp seed flags img cache scratch s",
-    "ffx_render_fwd_adjoint": "bvh info sd mats tex spp seed flags img gimg gtex dot s",
-    "ffx_render_fwd_adjoint_filtered": "bvh info sd mats tex spp seed flags img gimg gtex scratch s",
-    "ffx_render_bwd": "bvh info sd mats spp seed flags gimg gtex s",
-    "ffx_render_bwd_filtered": "bvh info sd mats spp seed flags gimg gtex scratch s",
-    "ffx_render_bwd_det": "bvh info sd mats spp seed flags gimg gtex scratch s",
-    "ffx_render_bwd_det_part": "bvh info sd mats spp seed flags gimg part scale acc scratch s",
-}
+# ------------------------------------------------------------------ refusals (tests/refusals.py's set-up)
 _L1, _L8, _L9 = _abi.render_lights(1), _abi.render_lights(8), _abi.render_lights(9)
 _ONLY = "FFX_RENDER_LIGHTS is served by ffx_render_fwd[_filtered] only"
 _GRAD = "FFX_RENDER_LIGHTS is not served together with a FFX_RENDER_GRAD_* bit"
@@ -139,28 +119,9 @@ _REFUSALS = [
 
 @pytest.mark.parametrize("case", _REFUSALS, ids=lambda c: f"{c[0][4:]}-{c[1]:#x}-{'nomats' if c[2] else 'mats'}")
 def test_the_bits_are_refused_before_any_launch(case, monkeypatch):
-    """host dummy pointers that the library never dereferences, a one-triangle bvh info without normals, apex areas or a wide tree (so that nothing can
-    launch)"""
+    """tests/refusals.py's set-up (nothing can launch), with this suite's own default: no dot_out / loss_slots buffer"""
     name, flags, arg_changes, rc, msg = case
-    for knob in ("FFX_TRAVERSAL", "FFX_WIDE"):
-        monkeypatch.delenv(knob, raising=False)
-    lib = _lib.api().lib
-    buf = np.zeros(64, np.float32)
-    addr = (buf.ctypes.data + 15) & ~15
-    eye = _abi.mat16(np.eye(4))
-    sd = _abi.SceneDesc()
-    sd.cam.to_world, sd.cam.camera_to_sample, sd.cam.width, sd.cam.height = eye, eye, 4, 4
-    sd.proj.to_world, sd.proj.camera_to_sample, sd.proj.tex_w, sd.proj.tex_h, sd.proj.tex_channels, sd.proj.enabled = eye, eye, 4, 4, 1, 1
-    sd.n_shapes = 1
-    if "filtered" in name:
-        sd.rfilter = _abi.RFILTER_GAUSSIAN
-    info = _abi.BvhInfo(n_tris=1, n_nodes=1, max_depth=1, off_tq=64)
-    args = dict(bvh=addr, info=C.byref(info), sd=C.byref(sd), mats=addr, tex=addr, spp=4, seed=1, flags=flags, img=addr, cache=addr, scratch=addr, gimg=addr,
-                gtex=addr, dot=None, part=1, scale=0, acc=addr, s=None)
-    args.update(arg_changes)
-    got = getattr(lib, name)(*[args[p] for p in _PARAMS[name].split()])
-    err = (lib.ffx_last_error() or b"").decode()
-    print(name, hex(flags), got, err)
+    got, err = refusals.call(name, refusals.GAUSS if "filtered" in name else {}, {"flags": flags, "dot": None, **arg_changes}, monkeypatch=monkeypatch)
     assert got == rc, (got, err)
     assert msg in err, err
 

@@ -9,7 +9,7 @@ from fireflies_amd import _abi, ops, scene_desc
 from tests import ref_bruteforce as bf
 from tests import ref_path as rp
 from tests.corner_scenes import relay
-from tests.support import header, world_arrays
+from tests.support import define, header, world_arrays
 
 
 
@@ -90,7 +90,7 @@ def test_load_dict_returns_integrators():
 
 def test_path_macros_in_header_and_abi():
     hdr = header()
-    assert int(re.search(r"#define FFX_ABI_VERSION (\d+)", hdr).group(1)) == _abi.FFX_ABI_VERSION == 11
+    assert define("FFX_ABI_VERSION") == _abi.FFX_ABI_VERSION == 11
     for name, val in (("MAX_DEPTH_SHIFT", _abi.RENDER_MAX_DEPTH_SHIFT), ("RR_DEPTH_SHIFT", _abi.RENDER_RR_DEPTH_SHIFT), ("MAX_DEPTH_LIMIT", _abi.RENDER_MAX_DEPTH_LIMIT)):
         assert int(re.search(rf"#define FFX_RENDER_{name} (\d+)", hdr).group(1)) == val
     assert int(re.search(r"#define FFX_RENDER_PATH_MASK (0x[0-9a-fA-F]+)", hdr).group(1), 16) == _abi.RENDER_PATH_MASK

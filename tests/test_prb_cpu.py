@@ -1,21 +1,20 @@
 """The `prb` integrator without a GPU: mi.load_dict, the FFX_RENDER_GRAD_PRB bit in the header and in _abi and its place among the
-flags, the refusals that come before any launch (host dummy pointers, as tests/test_abi_cpu.py's), and the float64 restatement's detached roulette
+flags, the refusals that come before any launch (tests/refusals.py's set-up), and the float64 restatement's detached roulette
 (tests/ref_prb.py) against tests/ref_path.py."""
-import ctypes as C
 import re
 
 import numpy as np
 import pytest
 
-from fireflies_amd import _abi, _lib, mi, scene_desc
+from fireflies_amd import _abi, mi, scene_desc
 from tests import ref_path as rp
-from tests import ref_prb
+from tests import ref_prb, refusals
 from tests.corner_scenes import spot_corner
 from tests.support import FFX_ERR_ARG, FFX_ERR_UNSUPPORTED, define, enum_value, header, world_arrays
 
 APP, MAT, PRB = _abi.RENDER_GRAD_APPEARANCE, _abi.RENDER_GRAD_MATERIAL, _abi.RENDER_GRAD_PRB
 P3 = _abi.render_path(3, 5)
-GAUSS = {"rfilter": _abi.RFILTER_GAUSSIAN}
+GAUSS = refusals.GAUSS
 
 
 def test_load_dict_prb():
@@ -60,20 +59,6 @@ def test_bit_is_clear_of_the_other_flags():
             assert _abi.render_path(md, rr) & m == 0
 
 
-# the parameters of the render entry points, in order (include/ffx.h); `s` is the stream
-_PARAMS = {
-    "ffx_render_fwd": "bvh info sd mats tex spp seed flags img s",
-    "ffx_render_fwd_cache": "bvh info sd mats tex spp seed flags img cache s",
-    "ffx_render_fwd_adjoint": "bvh info sd mats tex spp seed flags img gimg gtex dot s",
-    "ffx_render_fwd_filtered": "bvh info sd mats tex spp seed flags img scratch s",
-    "ffx_render_fwd_adjoint_filtered": "bvh info sd mats tex spp seed flags img gimg gtex scratch s",
-    "ffx_render_fwd_cache_filtered": "bvh info sd mats tex spp seed flags img cache scratch s",
-    "ffx_render_bwd": "bvh info sd mats spp seed flags gimg gtex s",
-    "ffx_render_bwd_filtered": "bvh info sd mats spp seed flags gimg gtex scratch s",
-    "ffx_render_bwd_det": "bvh info sd mats spp seed flags gimg gtex workspace s",
-    "ffx_render_bwd_det_part": "bvh info sd mats spp seed flags gimg part scale_log2 acc workspace s",
-    "ffx_render_bwd_cached": "sd mats cache spp gimg gtex img flags dot s",
-}
 # the entry points that refuse FFX_RENDER_GRAD_APPEARANCE (tests/test_abi_cpu.py _REFUSALS) refuse FFX_RENDER_GRAD_PRB the same way
 _OTHERS = ("ffx_render_fwd", "ffx_render_fwd_cache", "ffx_render_fwd_adjoint", "ffx_render_fwd_filtered", "ffx_render_fwd_adjoint_filtered",
            "ffx_render_fwd_cache_filtered", "ffx_render_bwd_cached", "ffx_render_bwd_det", "ffx_render_bwd_det_part")
@@ -100,27 +85,7 @@ _CASES = [
 @pytest.mark.parametrize("case", _CASES, ids=lambda c: f"{c[0][4:]}-{c[2]:#x}-{c[3]}")
 def test_refusals_before_any_launch(case, monkeypatch):
     name, changes, flags, rc, msg = case
-    for knob in ("FFX_TRAVERSAL", "FFX_WIDE"):
-        monkeypatch.delenv(knob, raising=False)
-    lib = _lib.api().lib
-    buf = np.zeros(64, np.float32)
-    addr = (buf.ctypes.data + 15) & ~15
-    eye = _abi.mat16(np.eye(4))
-    sd = _abi.SceneDesc()
-    sd.cam.to_world, sd.cam.camera_to_sample, sd.cam.width, sd.cam.height = eye, eye, 4, 4
-    sd.proj.to_world, sd.proj.camera_to_sample, sd.proj.tex_w, sd.proj.tex_h, sd.proj.tex_channels, sd.proj.enabled = eye, eye, 4, 4, 1, 1
-    sd.n_shapes = 1
-    info = _abi.BvhInfo(n_tris=1, n_nodes=1, max_depth=1, off_tq=64)
-    for key, v in changes.items():
-        obj, attr = (info, key[5:]) if key.startswith("info.") else (sd, key)
-        while "." in attr:
-            head, attr = attr.split(".", 1)
-            obj = getattr(obj, head)
-        setattr(obj, attr, v)
-    args = dict(bvh=addr, info=C.byref(info), sd=C.byref(sd), mats=addr, tex=addr, spp=4, seed=1, flags=flags, img=addr, cache=addr, scratch=addr, gimg=addr,
-                gtex=addr, dot=addr, workspace=addr, part=1, scale_log2=0, acc=addr, s=None)
-    got = getattr(lib, name)(*[args[p] for p in _PARAMS[name].split()])
-    err = (lib.ffx_last_error() or b"").decode()
+    got, err = refusals.call(name, changes, {"flags": flags}, monkeypatch=monkeypatch)
     assert got == rc, (got, err)
     assert msg in err, err
 

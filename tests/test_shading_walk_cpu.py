@@ -56,12 +56,12 @@ def walk_values():
     seen = list(rl.vertices(*world, sd, rows, 2, 7, 4, 2))
     _cat(out, "lights", [(idx, [v] * len(idx), beta, P, ng, Po, d, r) for v, idx, beta, P, ng, ns, Po, d, r in seen])
     _cat(out, "lights_ns", [(idx, ns) for v, idx, beta, P, ng, ns, Po, d, r in seen])
-    out["lights/image"] = rl.render_lights(*world, sd, rows, sm.table(ls.POINT, ls.SPOT_B), 2, 7, 4, 2, gaussian_stddev=0.5)
+    out["lights/image"] = rl.render_lights(*world, sd, rows, sm.host_table(ls.POINT, ls.SPOT_B), 2, 7, 4, 2, gaussian_stddev=0.5)
     world, sd, rows = _host(am.corner("21x19", False))
     out["ambient/image"] = ra.render_ambient(*world, sd, rows, am.RADIANCE, 2, 7, 3, 1)
     out["ambient/image32"] = ra.render_ambient(*world, sd, rows, am.RADIANCE, 2, 7, 3, 1, round32=True)
     world, sd, rows = _host(ss.corner("21x19", True))
-    out["sun/image"] = rs.render_sun(*world, sd, rows, sm.table(ss.SUN_A, ls.POINT), 2, 7, 3, 1, gaussian_stddev=0.5)
+    out["sun/image"] = rs.render_sun(*world, sd, rows, sm.host_table(ss.SUN_A, ls.POINT), 2, 7, 3, 1, gaussian_stddev=0.5)
     return out
 
 
@@ -167,9 +167,9 @@ def parts(film, depth, stddev, shadows, swap):
     a = (*world, sd, rows)
     b = (sm.SPP, sm.SEED, depth)
     p = {"main": rp.render_fwd(*a, tex, *b, gaussian_stddev=stddev, **k),
-         "point": rl.render_lights(*a, sm.table(sm.POINT), *b, gaussian_stddev=stddev, **k),
-         "spot": rl.render_lights(*a, sm.table(sm.SPOT), *b, gaussian_stddev=stddev, **k),
-         "sun": rs.render_sun(*a, sm.table(sm.SUN), *b, gaussian_stddev=stddev, **k),
+         "point": rl.render_lights(*a, sm.host_table(sm.POINT), *b, gaussian_stddev=stddev, **k),
+         "spot": rl.render_lights(*a, sm.host_table(sm.SPOT), *b, gaussian_stddev=stddev, **k),
+         "sun": rs.render_sun(*a, sm.host_table(sm.SUN), *b, gaussian_stddev=stddev, **k),
          "ambient": ra.render_ambient(*a, sm.RADIANCE, *b, gaussian_stddev=stddev, **k)}
     if swap is None:
         direct = rp.render_fwd(*a, tex, sm.SPP, sm.SEED, 2, gaussian_stddev=stddev, **k)

@@ -82,9 +82,9 @@ def ref_image(c, part, depth):
         if part == "main":
             r = rp.render_fwd(*a, c.tex_np, *b, gaussian_stddev=c.std, **c.sh)
         elif part in ("point", "spot"):
-            r = rl.render_lights(*a, sm.table(*EXTRA[part]["lights"]), *b, gaussian_stddev=c.std, **c.sh)
+            r = rl.render_lights(*a, sm.host_table(*EXTRA[part]["lights"]), *b, gaussian_stddev=c.std, **c.sh)
         elif part == "sun":
-            r = rs.render_sun(*a, sm.table(sm.SUN), *b, gaussian_stddev=c.std, **c.sh)
+            r = rs.render_sun(*a, sm.host_table(sm.SUN), *b, gaussian_stddev=c.std, **c.sh)
         elif part == "ambient":
             r = ra.render_ambient(*a, sm.RADIANCE, *b, gaussian_stddev=c.std, **c.sh)
         else:  # (the render is linear in the emitters)
@@ -125,7 +125,7 @@ def test_path_render_and_its_texture_adjoint_match_the_float64_walk(depth, tc, g
 @pytest.mark.parametrize("film,shadows", [("12x12", True), ("13x11", True), ("12x12", False)], ids=["12x12", "13x11", "12x12-unshadowed"])
 def test_what_every_extra_emitter_adds_matches_the_float64_walk(film, shadows, gaussian, depth):
     """k_lights_fwd's instances — plain (point, spot), DIR (sun), AMB (the constant emitter, closing ray included) and DIR with AMB (all at
-    once): image minus unlit image against the restatement of that part, under tests/test_lights_gpu.py's three conditions with the sums the flat tests of each kernel use — the part itself at direct light and for the constant emitter, the part's indirect share
+    once): image minus unlit image against the restatement of that part, under the three conditions of tests/support.py's `independent` with the sums the flat tests of each kernel use — the part itself at direct light and for the constant emitter, the part's indirect share
     through the bounces of the lights and the sun"""
     c = case(film, gaussian, 1, shadows)
     plain, main_ref = gpu_image(c, "main", depth), ref_image(c, "main", depth)

@@ -1,22 +1,21 @@
 """The directional emitter without a GPU: the header's macros against _abi, ops.pack_lights' record and the bit _with_lights sets, the
 refusals of FFX_RENDER_LIGHTS_DIRECTIONAL that come before any launch, the loader, mi.Scene's parameter map (over a stand-in for the device geometry),
 tests/ref_sun.py's own identities in float64 and — on ref_sun alone — the preconditions of the comparisons tests/test_sun_gpu.py makes."""
-import ctypes as C
 import re
 import types
-import warnings
 
 import numpy as np
 import pytest
 import torch
 
-from fireflies_amd import _abi, _lib, loaders, mi, ops, scene_desc, scenes
+from fireflies_amd import _abi, loaders, mi, ops, scenes
 from tests import light_scenes as ls
 from tests import ref_lights as rl
 from tests import ref_path as rp
 from tests import ref_sun as rs
+from tests import refusals
 from tests import sun_scenes as ss
-from tests.support import FFX_ERR_ARG, FFX_ERR_UNSUPPORTED, define, header, host_tex, world_arrays
+from tests.support import FFX_ERR_ARG, FFX_ERR_UNSUPPORTED, arrays, define, header, host_tex, load_xml
 
 
 # ------------------------------------------------------------------ 1. header and ABI
@@ -84,19 +83,7 @@ def test_with_lights_ors_the_bit_and_defaults_to_todays_bits():
         ops._dev = orig
 
 
-# ------------------------------------------------------------------ 3. refusals before any launch (tests/test_lights_cpu.py's set-up)
-_PARAMS = {
-    "ffx_render_fwd": "bvh info sd mats tex spp seed flags img s",
-    "ffx_render_fwd_filtered": "bvh info sd mats tex spp seed flags img scratch s",
-    "ffx_render_fwd_cache": "bvh info sd mats tex spp seed flags img cache s",
-    "ffx_render_fwd_cache_filtered": "bvh info sd mats tex spp seed flags img cache scratch s",
-    "ffx_render_fwd_adjoint": "bvh info sd mats tex spp seed flags img gimg gtex dot s",
-    "ffx_render_fwd_adjoint_filtered": "bvh info sd mats tex spp seed flags img gimg gtex scratch s",
-    "ffx_render_bwd": "bvh info sd mats spp seed flags gimg gtex s",
-    "ffx_render_bwd_filtered": "bvh info sd mats spp seed flags gimg gtex scratch s",
-    "ffx_render_bwd_det": "bvh info sd mats spp seed flags gimg gtex scratch s",
-    "ffx_render_bwd_det_part": "bvh info sd mats spp seed flags gimg part scale acc scratch s",
-}
+# ------------------------------------------------------------------ 3. refusals before any launch (tests/refusals.py's set-up)
 _D, _L1, _A = _abi.RENDER_LIGHTS_DIRECTIONAL, _abi.render_lights(1), _abi.RENDER_AMBIENT
 _DL = _D | _L1
 _ONLY = "FFX_RENDER_LIGHTS is served by ffx_render_fwd[_filtered] only"  # (the count's refusal comes first: its wording stays)
@@ -143,47 +130,21 @@ _REFUSALS = [
 
 @pytest.mark.parametrize("case", _REFUSALS, ids=lambda c: f"{c[0][4:]}-{c[1]:#x}-{'nomats' if c[2] else 'mats'}")
 def test_the_bit_is_refused_before_any_launch(case, monkeypatch):
-    """host dummy pointers that the library never dereferences, a one-triangle bvh info without normals, apex areas or a wide tree (so that nothing can
-    launch)"""
+    """tests/refusals.py's set-up (nothing can launch), with this suite's own default: no dot_out / loss_slots buffer"""
     name, flags, arg_changes, rc, msg = case
-    for knob in ("FFX_TRAVERSAL", "FFX_WIDE"):
-        monkeypatch.delenv(knob, raising=False)
-    lib = _lib.api().lib
-    buf = np.zeros(64, np.float32)
-    addr = (buf.ctypes.data + 15) & ~15
-    eye = _abi.mat16(np.eye(4))
-    sd = _abi.SceneDesc()
-    sd.cam.to_world, sd.cam.camera_to_sample, sd.cam.width, sd.cam.height = eye, eye, 4, 4
-    sd.proj.to_world, sd.proj.camera_to_sample, sd.proj.tex_w, sd.proj.tex_h, sd.proj.tex_channels, sd.proj.enabled = eye, eye, 4, 4, 1, 1
-    sd.n_shapes = 1
-    if "filtered" in name:
-        sd.rfilter = _abi.RFILTER_GAUSSIAN
-    info = _abi.BvhInfo(n_tris=1, n_nodes=1, max_depth=1, off_tq=64)
-    args = dict(bvh=addr, info=C.byref(info), sd=C.byref(sd), mats=addr, tex=addr, spp=4, seed=1, flags=flags, img=addr, cache=addr, scratch=addr, gimg=addr,
-                gtex=addr, dot=None, part=1, scale=0, acc=addr, s=None)
-    args.update(arg_changes)
-    got = getattr(lib, name)(*[args[p] for p in _PARAMS[name].split()])
-    err = (lib.ffx_last_error() or b"").decode()
-    print(name, hex(flags), got, err)
+    got, err = refusals.call(name, refusals.GAUSS if "filtered" in name else {}, {"flags": flags, "dot": None, **arg_changes}, monkeypatch=monkeypatch)
     assert got == rc, (got, err)
     assert msg in err, err
 
 
 # ------------------------------------------------------------------ 4. the loader
-def _load(path):
-    with warnings.catch_warnings(record=True) as w:
-        warnings.simplefilter("always")
-        sc = loaders.load_mitsuba_xml(path)
-    return sc, [str(x.message) for x in w]
-
-
 def _sun_dir(light):
     z = np.asarray(light.to_world, np.float64)[:3, 2]
     return z / np.linalg.norm(z)
 
 
 def test_the_loader_reads_the_directional_emitter(tmp_path):
-    sc, reports = _load(ss.write_scene(tmp_path))
+    sc, reports = load_xml(ss.write_scene(tmp_path))
     print(reports)
     assert [(l.name, l.kind) for l in sc.lights] == [("emit-Light", "point"), ("emit-Sun", "directional")]  # (file order)
     sun = sc.lights[1]
@@ -195,19 +156,19 @@ def test_the_loader_reads_the_directional_emitter(tmp_path):
     assert sc.spot is not None and sc.projector is not None and sc.ambient is not None and sc.ambient.radiance == ss.WORLD_RADIANCE
     assert not any("directional" in r for r in reports), reports
     # the other spelling of the vector, a single float, a spectrum
-    sc1, r1 = _load(ss.write_scene(tmp_path, ss.with_sun('<emitter type="directional" id="sun"><float name="irradiance" value="0.25"/>'
+    sc1, r1 = load_xml(ss.write_scene(tmp_path, ss.with_sun('<emitter type="directional" id="sun"><float name="irradiance" value="0.25"/>'
                                                          '<vector name="direction" x="0" y="3" z="-4"/></emitter>'), "f.xml"))
     assert sc1.lights[1].name == "sun" and sc1.lights[1].intensity == (0.25, 0.25, 0.25) and not any("directional" in r for r in r1)
     np.testing.assert_allclose(_sun_dir(sc1.lights[1]), (0.0, 0.6, -0.8), atol=1e-6)
-    sc2, _ = _load(ss.write_scene(tmp_path, ss.with_sun('<emitter type="directional" id="sun"><spectrum name="irradiance" value="3"/></emitter>'), "s.xml"))
+    sc2, _ = load_xml(ss.write_scene(tmp_path, ss.with_sun('<emitter type="directional" id="sun"><spectrum name="irradiance" value="3"/></emitter>'), "s.xml"))
     assert sc2.lights[1].intensity == (3.0, 3.0, 3.0)
     # no id, no irradiance, no pose: Mitsuba's defaults — irradiance 1 along the local +Z of the identity
-    sc3, _ = _load(ss.write_scene(tmp_path, ss.with_sun('<emitter type="directional"/>'), "d.xml"))
+    sc3, _ = load_xml(ss.write_scene(tmp_path, ss.with_sun('<emitter type="directional"/>'), "d.xml"))
     assert sc3.lights[1].kind == "directional" and sc3.lights[1].intensity == (1.0, 1.0, 1.0)
     np.testing.assert_array_equal(np.asarray(sc3.lights[1].to_world), np.eye(4, dtype=np.float32))
     # to_world: the whole transform is kept, its +Z is the direction
     look = '<transform name="to_world"><lookat origin="4,3,5" target="1,1,0" up="0,0,1"/></transform>'
-    sc4, _ = _load(ss.write_scene(tmp_path, ss.with_sun(f'<emitter type="directional" id="sun"><rgb name="irradiance" value="1,2,3"/>{look}</emitter>'), "t.xml"))
+    sc4, _ = load_xml(ss.write_scene(tmp_path, ss.with_sun(f'<emitter type="directional" id="sun"><rgb name="irradiance" value="1,2,3"/>{look}</emitter>'), "t.xml"))
     np.testing.assert_allclose(np.asarray(sc4.lights[1].to_world), scenes.look_at((4, 3, 5), (1, 1, 0), up=(0, 0, 1)), atol=1e-6)
     np.testing.assert_allclose(_sun_dir(sc4.lights[1]), ss.unit((-3, -2, -5)), atol=1e-6)
     assert sc4.lights[1].intensity == (1.0, 2.0, 3.0)
@@ -224,31 +185,31 @@ def test_both_poses_and_a_zero_direction_raise(tmp_path):
 
 
 def test_the_slots_are_eight_in_file_order_and_unknown_properties_are_reported_once(tmp_path):
-    sc, reports = _load(ss.write_scene(tmp_path, ss.with_extra_suns(8), "ten.xml"))  # 2 + 8 = 10 extra emitters
+    sc, reports = load_xml(ss.write_scene(tmp_path, ss.with_extra_suns(8), "ten.xml"))  # 2 + 8 = 10 extra emitters
     assert len(sc.lights) == 8 and [l.name for l in sc.lights] == ["emit-Light", "emit-Sun"] + [f"emit-More{k}" for k in range(6)]
     assert all(l.kind == "directional" for l in sc.lights[1:])
     told = [r for r in reports if "dropped" in r and "emitters" in r]
     assert len(told) == 1 and "emit-More6" in told[0], reports
     extra = '<float name="scale" value="2"/>'
     xml = ss.with_sun(f'<emitter type="directional" id="a">{extra}</emitter><emitter type="directional" id="b">{extra}</emitter>')
-    sc, reports = _load(ss.write_scene(tmp_path, xml, "p.xml"))
+    sc, reports = load_xml(ss.write_scene(tmp_path, xml, "p.xml"))
     assert [l.name for l in sc.lights] == ["emit-Light", "a", "b"]
     assert [r for r in reports if "directional emitter property 'scale' is ignored" in r] and len([r for r in reports if "'scale'" in r]) == 1, reports
 
 
 def test_a_file_without_the_emitter_loads_as_before_and_the_pinned_reports_keep_their_wording(tmp_path):
-    plain, r0 = _load(ss.write_scene(tmp_path, ss.with_sun(""), "plain.xml"))
-    with_s, r1 = _load(ss.write_scene(tmp_path))
+    plain, r0 = load_xml(ss.write_scene(tmp_path, ss.with_sun(""), "plain.xml"))
+    with_s, r1 = load_xml(ss.write_scene(tmp_path))
     assert [l.name for l in plain.lights] == ["emit-Light"] and r0 == [r.replace("sun.xml", "plain.xml") for r in r1]
     assert np.array_equal(plain.spot.to_world, with_s.spot.to_world) and plain.spot.intensity == with_s.spot.intensity and plain.ambient == with_s.ambient
     assert np.array_equal(plain.lights[0].to_world, with_s.lights[0].to_world) and plain.lights[0].intensity == with_s.lights[0].intensity
     xml = ss.with_sun('<emitter type="envmap" id="sky"><string name="filename" value="e.exr"/></emitter>')
     xml = xml.replace('</bsdf></shape>', '</bsdf><emitter type="area"><rgb name="radiance" value="1"/></emitter></shape>', 1)
-    _, reports = _load(ss.write_scene(tmp_path, xml, "env.xml"))
+    _, reports = load_xml(ss.write_scene(tmp_path, xml, "env.xml"))
     assert any("emitter type 'envmap' ignored: only `projector` and `spot` emitters illuminate the scene" in r for r in reports), reports
     assert any("area emitter on a shape ignored" in r for r in reports), reports
     # light_scenes' file (no sun): what it loaded before
-    sc, reports = _load(ls.write_scene(tmp_path))
+    sc, reports = load_xml(ls.write_scene(tmp_path))
     assert [(l.name, l.kind) for l in sc.lights] == [("emit-Light", "point"), ("emit-PointLight", "point"), ("emit-SecondSpot", "spot")]
     assert not any("directional" in r for r in reports)
 
@@ -295,12 +256,6 @@ def test_the_parameter_map_holds_the_sun_and_the_table_follows_it(monkeypatch):
 
 
 # ------------------------------------------------------------------ 6. ref_sun's own identities in float64
-def _arrays(sc, principled=False):
-    sd = scene_desc.scene_desc(sc, shadows=True, mat_stride=16 if principled else 0)
-    verts, tri_idx, tri_shape, alb = world_arrays(sc)
-    return sd, (verts, tri_idx, tri_shape), scenes.material_rows(sc) if principled else alb
-
-
 def _row(sun):
     return rs.table_row(sun.to_world, sun.intensity)
 
@@ -309,13 +264,13 @@ def _row(sun):
 def test_the_closed_form_on_the_quad_that_fills_the_film(gaussian):
     want = ss.quad_closed_form()
     stddev = 0.5 if gaussian else None
-    sd, world, alb = _arrays(ss.quad())
+    sd, world, alb = arrays(ss.quad())
     img = rs.render_sun(*world, sd, alb, [_row(ss.SUN_Q)], 4, 3, gaussian_stddev=stddev)
     rel = np.abs(img - want) / want
     print("quad, gaussian", gaussian, ": max relative error", rel.max())
     assert img.shape == (24, 24, 3) and rel.max() <= 1e-6
     # under a roof the camera does not see: every shadow ray hits it; with bit 0 of `shadows` cleared the closed form is back
-    sd, world, alb = _arrays(ss.quad(roof=True))
+    sd, world, alb = arrays(ss.quad(roof=True))
     st = {}
     dark = rs.render_sun(*world, sd, alb, [_row(ss.SUN_Q)], 4, 3, gaussian_stddev=stddev, stats=st)
     assert (dark == 0.0).all() and st[0]["occluded"] == st[0]["faces"] == 24 * 24 * 4
@@ -336,7 +291,7 @@ def test_the_sun_is_the_limit_of_a_point_light(sun):
     """shadows off, D = 1e6 r: the point light of intensity E D^2 at c - D dir against the sun, to 4 r / D of the part's maximum — the direction and the
     cosine each move by at most r / D, and D^2 / d^2 by 2 r / D (|d - D| <= r).  Lambert rows: the derivation takes the radiance to depend on the
     direction through the cosine alone (a specular lobe's slope in the direction is a multiple of its value)"""
-    sd, world, mats = _arrays(ss.corner("21x19"))
+    sd, world, mats = arrays(ss.corner("21x19"))
     sd.shadows &= ~1
     D = 1.0e6 * ss.RADIUS
     tw = np.eye(4)
@@ -349,7 +304,7 @@ def test_the_sun_is_the_limit_of_a_point_light(sun):
 
 
 def test_linearity_in_float64():
-    sd, world, alb = _arrays(ss.corner("21x19"))
+    sd, world, alb = arrays(ss.corner("21x19"))
     t = ops.pack_lights([ls.POINT, ls.SPOT_B, ss.SUN_A]).numpy().astype(np.float64)
     all3 = rs.render_sun(*world, sd, alb, t, 4, 3, max_depth=3)
     parts = [rs.render_sun(*world, sd, alb, t[k:k + 1], 4, 3, max_depth=3) for k in range(3)]
@@ -366,7 +321,7 @@ def test_linearity_in_float64():
 @pytest.mark.parametrize("principled", [False, True])
 def test_the_suns_matter_in_the_scenes_of_the_gpu_tests(film, principled):
     sc = ss.corner(film, principled)
-    sd, world, mats = _arrays(sc, principled)
+    sd, world, mats = arrays(sc, principled)
     spp, seed = 16, 7
     main = rp.render_fwd(*world, sd, mats, host_tex(sc), spp, seed, 2)
     for sun in (ss.SUN_A, ss.SUN_B):
@@ -382,7 +337,7 @@ def test_the_suns_matter_in_the_scenes_of_the_gpu_tests(film, principled):
 
 def test_sun_b_leaves_the_walls_dark_and_its_shadow_strip_holds_lit_and_unlit_floor():
     sc = ss.corner("24x24")
-    sd, world, alb = _arrays(sc)
+    sd, world, alb = arrays(sc)
     verts, tri_idx, tri_shape = world
     L = rs.sample_radiance(*world, sd, alb, [_row(ss.SUN_B)], 1, 7, use_jitter=False)
     from tests import ref_bruteforce as bf
@@ -404,7 +359,7 @@ def test_sun_b_leaves_the_walls_dark_and_its_shadow_strip_holds_lit_and_unlit_fl
 
 
 def test_bounces_carry_the_suns_light():
-    sd, world, alb = _arrays(ss.corner("24x24"))
+    sd, world, alb = arrays(ss.corner("24x24"))
     st = {}
     L = rs.sample_radiance(*world, sd, alb, [_row(ss.SUN_A)], 16, 7, max_depth=3, stats=st)
     direct = st["direct"].sum()

@@ -1,7 +1,7 @@
 """The directional emitter on the GPU: k_lights_fwd<RF, DIR> against the float64 restatement (tests/ref_sun.py) on both films, film sizes and
 row kinds, the closed forms on the quad that fills the film (with the roof that pins the shadow ray), the sun as the limit of a point light through the
 kernel that exists, the bit identities, linearity, paths and the adjoint, a ragged second pass, and the public interface.  Independent evaluations are
-held to tests/test_lights_gpu.py's three conditions, the same computation by another kernel to rtol 1e-5."""
+held to the three conditions of tests/support.py's `independent`, the same computation by another kernel to rtol 1e-5."""
 import numpy as np
 import pytest
 import torch
@@ -13,8 +13,8 @@ from tests import light_scenes as ls
 from tests import ref_path as rp
 from tests import ref_sun as rs
 from tests import sun_scenes as ss
-from tests.gpu_support import DEV
-from tests.support import copy_desc
+from tests.gpu_support import DEV, table
+from tests.support import copy_desc, independent
 
 pytestmark = pytest.mark.gpu
 
@@ -22,39 +22,8 @@ SPP, SEED = 16, 7
 LA = (0.2, 0.25, 0.3)
 
 
-def table(*lights):
-    return ops.pack_lights(lights).to(DEV)
-
-
-def independent(what, got, ref, scale, part_sum):
-    """the three conditions: at most 0.04 of the pixels off by more than 2e-3 of the image's scale, the median error within 1e-4 of it, the sums within
-    1 % of the part under test; the figures are printed before they are asserted"""
-    err = np.abs(got - ref)
-    off = float((err > 2e-3 * scale).mean())
-    print(f"{what}: scale {scale:.4g}, off by > 2e-3 scale {off:.4f} [0.04], median {np.median(err) / scale:.2e} [1e-4], "
-          f"|sum - ref sum| {abs(got.sum() - ref.sum()):.4g} [{0.01 * part_sum:.4g}]")
-    assert np.isfinite(got).all() and part_sum > 0
-    assert off <= 0.04
-    assert np.median(err) <= 1e-4 * scale
-    assert abs(got.sum() - ref.sum()) <= 0.01 * part_sum
-
-
-_CASES = {}
-
-
 def case(film, principled, gaussian):
-    """a corner of sun_scenes, loaded once: (scene, description, world arrays, rows in float64, texture, materials argument, the image without extra
-    emitters at direct light and its float64 restatement)"""
-    key = (film, principled, gaussian)
-    if key not in _CASES:
-        ms, sd, world = gpu.load(ss.corner(film, principled), gaussian, 1)
-        rows = ms.albedo.cpu().numpy().astype(np.float64)
-        tex = gpu.rand_tex(sd, 1)
-        mats = ms.materials_arg(sd)
-        unlit = ms.geom.render_fwd(sd, mats, tex, SPP, SEED)
-        main_ref = rp.render_fwd(*world, sd, rows, tex.cpu().numpy(), SPP, SEED, 2, gaussian_stddev=0.5 if gaussian else None)
-        _CASES[key] = (ms, sd, world, rows, tex, mats, unlit, main_ref)
-    return _CASES[key]
+    return gpu.corner_case(ss.corner, film, principled, gaussian, SPP, SEED)
 
 
 def sun_fwd(ms, sd, mats, tex, lights, spp=SPP, **kw):

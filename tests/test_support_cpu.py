@@ -1,5 +1,5 @@
-"""The rule of the test support: helpers live in tests/support.py (no device), tests/gpu_support.py (device) and the *_scenes.py modules, and no
-test module is another one's library."""
+"""The rule of the test support: helpers live in tests/support.py (no device), tests/gpu_support.py (device), tests/refusals.py (the library's
+refusals before any launch) and the *_scenes.py modules, and no test module is another one's library."""
 import ast
 import glob
 import os
