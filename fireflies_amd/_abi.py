@@ -325,6 +325,20 @@ PROTOTYPES = {
 }
 
 
+# name -> (restype, argtypes); every symbol include/ffx_labels.h declares: the entry points of libffx_hip.so without an oracle restatement
+# (a library that lacks them — the oracle — binds PROTOTYPES alone)
+PROTOTYPES_NO_ORACLE = {
+    # img, elem_size, h, w, background, connectivity, labels, n_labels, stats, centroids, max_labels, workspace, stream
+    "ffx_connected_components": (c_i, [c_p, c_i, c_i, c_i, C.c_int64, c_i, c_p, c_p, c_p, c_p, c_i, c_p, c_p]),
+}
+
+
+def components_workspace_bytes(h, w, max_labels):
+    """FFX_COMPONENTS_WORKSPACE_BYTES(h, w, max_labels) of include/ffx_labels.h"""
+    n = int(h) * int(w)
+    return 8 * n + 16 * ((n + 4095) // 4096) + 40 * max(int(max_labels), 0)
+
+
 class FFXError(RuntimeError):
     pass
 
@@ -351,6 +365,11 @@ class Api:
         if ver != FFX_ABI_VERSION:
             raise FFXError(f"ABI version mismatch: library {ver}, python {FFX_ABI_VERSION}")
         self.backend = cdll.ffx_backend().decode()
+        if self.backend != "cpu-oracle":  # the product: a missing symbol is an error here too
+            for name, (res, args) in PROTOTYPES_NO_ORACLE.items():
+                fn = getattr(cdll, name)
+                fn.restype = res
+                fn.argtypes = args
 
     def check(self, rc, what):
         if rc != 0:

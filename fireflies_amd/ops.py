@@ -380,6 +380,52 @@ def rgb_to_gray(img, weights=(0.299, 0.587, 0.114)):
     return out
 
 
+class Components(NamedTuple):
+    """what connected_components returns, laid out as cv2.connectedComponentsWithStats returns it (include/ffx_labels.h): n_labels — a 0-d
+    int32 tensor, components + 1; reading it is the caller's synchronisation —, labels [H, W] int32, stats [max_labels, 5] int32 (left, top, width,
+    height, area; row 0 the background), centroids [max_labels, 2] float64 (x, y).  labels / stats and centroids are None where they were not asked for"""
+    n_labels: torch.Tensor
+    labels: torch.Tensor = None
+    stats: torch.Tensor = None
+    centroids: torch.Tensor = None
+
+
+_COMPONENT_DTYPES = {torch.bool: 1, torch.uint8: 1, torch.int32: 4, torch.int64: 8}
+
+
+def connected_components(img, connectivity=8, background=0, max_labels=256, labels=True, stats=True, workspace=None):
+    """The 4- or 8-connected components of the pixels of `img` that differ from `background`, numbered 1..C in raster order of their first pixel, with
+    cv2's statistics of the first max_labels labels (ffx_connected_components; main.py:168-180) -> Components.  img: [H, W] bool / uint8 / int32 / int64 on
+    a HIP device, contiguous.  labels=False / stats=False skip those outputs and the launches that only serve them.  workspace: a uint8 tensor of at least
+    _abi.components_workspace_bytes(H, W, max_labels) bytes to use instead of a fresh one (its contents do not matter)."""
+    if not isinstance(img, torch.Tensor):
+        raise TypeError("img: expected a torch.Tensor")
+    if img.dtype not in _COMPONENT_DTYPES:
+        raise TypeError(f"img: expected bool, uint8, int32 or int64, got {img.dtype}")
+    if img.dim() != 2:
+        raise ValueError(f"img: expected a 2-D image [H, W], got {tuple(img.shape)}")
+    if not img.is_contiguous():
+        raise ValueError("img: must be contiguous")
+    if stats and int(max_labels) < 1:
+        raise ValueError(f"max_labels: {max_labels} with stats (at least 1)")
+    p_img = _dev(img, img.dtype, "img")
+    h, w = int(img.shape[0]), int(img.shape[1])
+    need = _abi.components_workspace_bytes(h, w, max_labels if stats else 0)
+    if workspace is None:
+        workspace = torch.empty(need, dtype=torch.uint8, device=img.device)
+    elif workspace.numel() < need:
+        raise ValueError(f"workspace: {workspace.numel()} bytes, the call needs {need}")
+    p_ws = _dev(workspace, torch.uint8, "workspace")
+    n = torch.empty((), dtype=torch.int32, device=img.device)
+    lab = torch.empty((h, w), dtype=torch.int32, device=img.device) if labels else None
+    st = torch.empty((int(max_labels), 5), dtype=torch.int32, device=img.device) if stats else None
+    cen = torch.empty((int(max_labels), 2), dtype=torch.float64, device=img.device) if stats else None
+    api().call("ffx_connected_components", p_img, _COMPONENT_DTYPES[img.dtype], h, w, int(background), int(connectivity),
+               _dev(lab, torch.int32, "labels") if labels else None, _dev(n, torch.int32, "n_labels"), _dev(st, torch.int32, "stats") if stats else None,
+               _dev(cen, torch.float64, "centroids") if stats else None, int(max_labels), p_ws, _stream(img.device))
+    return Components(n, lab, st, cen)
+
+
 def blur_bwd(g, ksize=5, sigma=3.0):
     out = torch.empty_like(g)
     api().call("ffx_blur_bwd", _dev(g, name="g"), g.shape[0], g.shape[1], ksize, float(sigma), _dev(out), _stream())

@@ -1,0 +1,50 @@
+/* ffx_labels.h — the entry points of libffx_hip.so that have no restatement in the CPU oracle.
+ *
+ * include/ffx.h is the header BOTH shared libraries implement, symbol for symbol.  What is declared here is implemented by
+ * fireflies_amd/csrc/libffx_hip.so alone and is held to numpy / scipy references by its own tests (tests/ref_components.py).  The
+ * conventions are ffx.h's: FFX_OK or a negative code with a message in ffx_last_error(), the caller owns every buffer, every call is
+ * asynchronous on `stream`, arrays are dense and row-major.  FFX_ABI_VERSION is ffx.h's; additions here do not change it.
+ */
+#ifndef FFX_LABELS_H
+#define FFX_LABELS_H
+
+#include "ffx.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+/* ------------------------------------------------------------------------------------------
+ * Dataset path, the acceptance step: connected components of an integer image with statistics.
+ * Replaces cv2.connectedComponentsWithStats(seg_test.astype(np.uint8)) at main.py:168-180 (and :217-229), where the reference drops
+ * a sample whose mask "everything but the glottis" falls into more than two pieces (n_labels > 3).  DESIGN.md 4.11 is the definition;
+ * in short:
+ *   a pixel is foreground when img[y][x] != background (a 1-byte pixel is zero-extended, 4- and 8-byte pixels are signed);
+ *   a component is a maximal set of foreground pixels joined by 4- or 8-neighbour steps; components are numbered 1..C in raster
+ *   order of their first pixel (scipy.ndimage.label's numbering; cv2's is not promised);
+ *   n_labels[0]   = C + 1 (the background is label 0 whether or not a pixel has it);
+ *   labels[y][x]  = 0 on the background, else the component's number — complete whatever max_labels is;
+ *   stats[k]      = left, top, width, height, area of label k for k < min(n_labels, max_labels) (row 0: the background pixels); a row
+ *                   of area 0 and every later row: zeros;
+ *   centroids[k]  = (sum x / area, sum y / area): exact 64-bit integer sums, each converted to float64, one IEEE division; NaN where
+ *                   stats[k] is zeros.
+ * labels, stats and centroids may each be NULL (the launches that only serve them are skipped); centroids without stats is refused.
+ * Everything is written, nothing accumulated; integer atomics only: two calls give the same bytes.  No host synchronisation and no
+ * host read of device memory: the call can be captured into a graph.
+ * Limits: 1 <= h, w <= 32768, h * w <= 2^30, elem_size 1 / 4 / 8, connectivity 4 / 8, max_labels >= 1 with stats; workspace 8-byte
+ * aligned.  Outside them, or with a NULL img / n_labels / workspace: FFX_ERR_ARG before any launch, the parameter named in the message.
+ * ---------------------------------------------------------------------------------------- */
+/* bytes of `workspace`: two int32 per pixel (the union-find's parents; tile-local slots, then ranks), one int32 per 1024 pixels
+ * (root counts, then their prefix sums) padded to 16 bytes, and 40 bytes per statistics row */
+#define FFX_COMPONENTS_WORKSPACE_BYTES(h, w, max_labels) \
+  ((size_t)8 * (size_t)(h) * (size_t)(w) + (size_t)16 * (((size_t)(h) * (size_t)(w) + 4095) / 4096) + (size_t)40 * (size_t)((max_labels) > 0 ? (max_labels) : 0))
+
+int ffx_connected_components(const void *img /*[dev][h,w] integers of elem_size bytes*/, int elem_size, int h, int w, int64_t background,
+                             int connectivity, int32_t *labels /*[dev][h,w] or NULL*/, int32_t *n_labels /*[dev][1]*/,
+                             int32_t *stats /*[dev][max_labels,5] or NULL*/, double *centroids /*[dev][max_labels,2] or NULL*/,
+                             int max_labels, void *workspace /*[dev] FFX_COMPONENTS_WORKSPACE_BYTES(h, w, max_labels)*/, ffx_stream stream);
+
+#ifdef __cplusplus
+}
+#endif
+#endif
