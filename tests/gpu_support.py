@@ -1,5 +1,5 @@
 """Helpers of the tests that need the device (tests/*_gpu.py and tests/test_hip_parity.py only): arrays to and from it, the oracle's and the device's
-geometry of one scene, what a blob's bin and envelope headers say, its tile lists, apex records and triangle records, a loaded scene with its world
+geometry of one scene, what a blob's bin and envelope headers say, its tile lists, apex records and triangle records, a host copy of all the update writes, a loaded scene with its world
 arrays, seeded textures and gradient images, the lights' table and the emitter suites' corner cases, the loss of a material table, leaves and fits, the rows' and the spot's central differences of the GPU forward, forward mode against the adjoints."""
 import numpy as np
 import torch
@@ -125,6 +125,14 @@ def tri_records(gd):
     torch.cuda.synchronize()
     r = _bytes(gd.blob, int(gd.info.off_recs), 48 * int(gd.info.n_tris)).view(np.float32).reshape(-1, 12).astype(np.float64)
     return np.stack([r[:, 0:3], r[:, 0:3] + r[:, 3:6], r[:, 0:3] + r[:, 6:9]], 1)
+
+
+def blob_host(gd, copy=None):
+    """the first off_bins bytes — everything the builder and the geometry update write — of the blob the next render reads (or of blob copy `copy`),
+    on the host.  Taking the blob orders the caller's stream behind its re-fit (and launches a deferred top): what a render would find"""
+    b = gd.blob if copy is None else gd._blobs[copy]
+    torch.cuda.synchronize()
+    return _bytes(b, 0, int(gd.info.off_bins)).copy()
 
 
 def grad_close(got, want, what, frac):
