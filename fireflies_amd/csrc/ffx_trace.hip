@@ -24,6 +24,7 @@
 #include <limits.h>
 
 #include "ffx_common.h"
+#include "ffx_band.h"
 
 #define TR_BLOCK 256
 #define RAY_EPS 8.940696716308594e-05f
@@ -264,6 +265,21 @@ __device__ __forceinline__ void sample_jitter(uint32_t seed_key, uint32_t idx, f
   jy = (float)(b >> 8) * (1.0f / 16777216.0f);
 }
 
+// The plain-scene instance's two launch-proven diets, each with a build switch for single-item A/B libraries (tools/build_variant_lib.sh -D...; not
+// run-time knobs): -DFFX_K8_NO_BAND keeps cam_ray's IEEE forms, -DFFX_K8_NO_OFF32 keeps the 64-bit texel and record addresses.
+#ifdef FFX_K8_NO_BAND
+#define FFX_K8_BAND false
+#else
+#define FFX_K8_BAND true
+#endif
+#ifdef FFX_K8_NO_OFF32
+#define FFX_K8_OFF32 false
+#else
+#define FFX_K8_OFF32 true
+#endif
+// (rcp_band, sqrt_band: ffx_band.h — the IEEE expansions of 1.0f / d and sqrtf(x) without the steps that do nothing inside the camera's band)
+// BAND (k_render_fwd_pk's plain-scene instance only): the launch proved w_uniform and the band of |np|^2, |np| and dl.z
+template <bool BAND = false>
 __device__ __forceinline__ void cam_ray(const CamK &k, float sx, float sy, v3 &o, v3 &d, float &near_t, float &far_t) {
   const float *m = k.s2c;
   float qx = fmaf(m[0], sx, fmaf(m[1], sy, m[3]));
@@ -271,14 +287,14 @@ __device__ __forceinline__ void cam_ray(const CamK &k, float sx, float sy, v3 &o
   float qz = fmaf(m[8], sx, fmaf(m[9], sy, m[11]));
   // one IEEE reciprocal + multiplies instead of a division per component (same order as the oracle)
   float iw;
-  if (k.w_uniform) iw = k.iw_u; // (wave-uniform branch)
+  if (BAND || k.w_uniform) iw = k.iw_u; // (wave-uniform branch)
   else iw = 1.0f / fmaf(m[12], sx, fmaf(m[13], sy, m[15]));
   v3 np = V3(qx * iw, qy * iw, qz * iw);
-  const float il = 1.0f / sqrtf(vdot(np, np));
+  const float il = BAND ? rcp_band(sqrt_band(vdot(np, np))) : 1.0f / sqrtf(vdot(np, np));
   v3 dl = V3(np.x * il, np.y * il, np.z * il);
   d = xf_dir(k.tw, dl);
   o = V3(k.tw[3], k.tw[7], k.tw[11]);
-  const float idz = 1.0f / dl.z;
+  const float idz = BAND ? rcp_band(dl.z) : 1.0f / dl.z;
   near_t = k.near_clip * idz;
   far_t = k.far_clip * idz;
 }
@@ -814,8 +830,21 @@ struct AtomicInto { // the usual emitter: a float atomic into the gradient
 };
 // the projector's texture value at a sample, per colour channel: wy0 * (wx0 * t00 + wx1 * t01) + wy1 * (wx0 * t10 + wx1 * t11), times the projector's
 // colour for one-channel textures (ONE_CH: the caller knows it is one)
-template <bool ONE_CH = false>
+// OFF32 (k_render_fwd_pk's plain-scene instance; the launch proved every buffer named in plain_scene below 2^32 bytes, texture sides below 2^24):
+// a T at a 32-bit byte offset from a wave-uniform base — the load takes its scalar base and a 32-bit vector offset, no 64-bit address arithmetic
+template <class T>
+__device__ __forceinline__ const T &at32(const void *base, uint32_t byte_off) { return *reinterpret_cast<const T *>(reinterpret_cast<const char *>(base) + byte_off); }
+template <bool ONE_CH = false, bool OFF32 = false>
 __device__ __forceinline__ void proj_tex_value(const ShadeK &c, const SampleTerms &st, const float *__restrict__ tex, float (&tv)[3]) {
+  static_assert(!OFF32 || ONE_CH, "32-bit texel offsets: the plain-scene instance's one-channel texture");
+  if constexpr (OFF32) {
+    const uint32_t r0 = __umul24((uint32_t)st.iy0, (uint32_t)c.tw), r1 = __umul24((uint32_t)st.iy1, (uint32_t)c.tw);
+    const float t00 = at32<float>(tex, (r0 + (uint32_t)st.ix0) << 2), t01 = at32<float>(tex, (r0 + (uint32_t)st.ix1) << 2);
+    const float t10 = at32<float>(tex, (r1 + (uint32_t)st.ix0) << 2), t11 = at32<float>(tex, (r1 + (uint32_t)st.ix1) << 2);
+    const float v = st.wy0 * (st.wx0 * t00 + st.wx1 * t01) + st.wy1 * (st.wx0 * t10 + st.wx1 * t11);
+    tv[0] = v * c.p_color[0]; tv[1] = v * c.p_color[1]; tv[2] = v * c.p_color[2];
+    return;
+  }
   const int tc = ONE_CH ? 1 : c.tc;
   const size_t o00 = ((size_t)st.iy0 * c.tw + st.ix0) * tc, o01 = ((size_t)st.iy0 * c.tw + st.ix1) * tc;
   const size_t o10 = ((size_t)st.iy1 * c.tw + st.ix0) * tc, o11 = ((size_t)st.iy1 * c.tw + st.ix1) * tc;
@@ -829,12 +858,12 @@ __device__ __forceinline__ void proj_tex_value(const ShadeK &c, const SampleTerm
   }
 }
 // a sample's colour from its terms: alb * (spot + tv * proj_fac) + (spot_b + tv * proj_fac_b), the second bracket only where rows exist (`rows`)
-template <bool ONE_CH = false>
+template <bool ONE_CH = false, bool OFF32 = false>
 __device__ __forceinline__ void sample_colour(const ShadeK &c, const SampleTerms &st, const float *__restrict__ tex, const float *alb, bool rows, float (&L)[3]) {
   float r[3] = {st.spot[0], st.spot[1], st.spot[2]}, b[3] = {st.spot_b[0], st.spot_b[1], st.spot_b[2]};
   if (st.has_proj) {
     float tv[3];
-    proj_tex_value<ONE_CH>(c, st, tex, tv);
+    proj_tex_value<ONE_CH, OFF32>(c, st, tex, tv);
 #pragma unroll
     for (int ch = 0; ch < 3; ++ch) {
       r[ch] += tv[ch] * st.proj_fac;
@@ -1951,7 +1980,7 @@ __device__ __forceinline__ void traverse_packet_any(const BvhNode *__restrict__ 
 // with the primitive-id tie-break: the result does not depend on the order, and is the tree walk's bit for bit).
 // No stack, no descent, no packet constants: where the 64-wide walk took 4.2 dependent steps and 100 VALU of set-up per pixel
 // this is ~1.3 steps.  tx0..ty1: the tiles the rectangle touches (at most four: the caller falls back to the tree otherwise).
-template <bool ANY>
+template <bool ANY, bool OFF32 = false>
 __device__ __forceinline__ void traverse_bins(const char *__restrict__ bbase, const int nx, const int tx0, const int ty0, const int tx1, const int ty1, const float rcx,
                                               const float rcy, const float rhx, const float rhy, const TriApex *__restrict__ recs, const v3 d, const float tmin,
                                               const float tmax, const wmask active, Hit &h, wmask &occluded) {
@@ -1979,7 +2008,7 @@ __device__ __forceinline__ void traverse_bins(const char *__restrict__ bbase, co
         FFX_STAT(ANY ? 41 : 33);
         const uint32_t idx = b0 + lane;
         const uint32_t idc = idx < end ? idx : end - 1u; // lanes beyond the list re-read its last entry and are masked out
-        const float4 *e4 = reinterpret_cast<const float4 *>(ents + ((size_t)idc << 6));
+        const float4 *e4 = OFF32 ? &at32<float4>(ents, idc << 6) : reinterpret_cast<const float4 *>(ents + ((size_t)idc << 6));
         const float4 A = e4[0], B = e4[1], C = e4[2], D = e4[3];
         wmask m = m_ult(idx, end) & m_le(A.x, rx1) & m_ge(A.z, rx0) & m_le(A.y, ry1) & m_ge(A.w, ry0);
         m &= m_ge(fmaf(B.x, rcx, fmaf(fabsf(B.x), rhx, fmaf(B.y, rcy, fmaf(fabsf(B.y), rhy, B.z)))), 0.f);
@@ -2050,6 +2079,7 @@ __device__ __forceinline__ bool bins_ready(const BinsK &bk, const int a) {
 // primary rays of pixel (px, py): its own tile, its own square of the image plane.  The square is taken a half pad short at the far
 // side: a sample position of exactly px + 1 (rounding of px + jitter) still lies within the entries' padding, and the pixels of a
 // tile's last column do not drag the next tile's list in.
+template <bool OFF32 = false>
 __device__ __forceinline__ bool bins_primary(const BinsK &bk, const int px, const int py, const TriApex *__restrict__ recs, const v3 d, const float tmin, const float tmax,
                                              const wmask active, Hit &h) {
   if (!bins_ready(bk, 0)) return false;
@@ -2065,7 +2095,7 @@ __device__ __forceinline__ bool bins_primary(const BinsK &bk, const int px, cons
   const float shx = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(hx))), shy = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(hy)));
   if (stx >= bk.g[0].nx || sty >= bk.g[0].ny) return false;
   wmask occ;
-  traverse_bins<false>(bk.base[0], bk.g[0].nx, stx, sty, stx, sty, scx, scy, shx, shy, recs, d, tmin, tmax, active, h, occ);
+  traverse_bins<false, OFF32>(bk.base[0], bk.g[0].nx, stx, sty, stx, sty, scx, scy, shx, shy, recs, d, tmin, tmax, active, h, occ);
   return true;
 }
 
@@ -2112,6 +2142,7 @@ __device__ __forceinline__ void wave_reduce_minmax4(uint32_t &mn0, uint32_t &mn1
 // points on the emitter's grid are (M sdir).xy / (M sdir).z; the packet's rectangle is their bounding box (the samples of one pixel:
 // a pixel's footprint as the emitter sees it).  A packet that leaves the grid or spreads over more than four tiles (the two sides of
 // a depth discontinuity, far apart as seen from the emitter) takes the tree walk.
+template <bool OFF32 = false>
 __device__ __forceinline__ bool bins_shadow(const BinsK &bk, const int a, const TriApex *__restrict__ recs, const v3 sdir, const wmask active, wmask &occluded) {
   if (!bins_ready(bk, a)) return false;
   const float *M = bk.g[a].M;
@@ -2131,7 +2162,7 @@ __device__ __forceinline__ bool bins_shadow(const BinsK &bk, const int a, const 
     const int nxf = bk.g[a].nx * FFX_ENV_SUB;
     const uint32_t last = (uint32_t)(nxf * bk.g[a].ny * FFX_ENV_SUB) - 1u;
     const uint32_t ci = (uint32_t)((int)(fy * (float)FFX_ENV_SUB) * nxf + (int)(fx * (float)FFX_ENV_SUB));
-    const float4 Nc = reinterpret_cast<const float4 *>(bk.base[a] + bk.env_off)[ci < last ? ci : last]; // (lanes that are not active may hold anything)
+    const float4 Nc = OFF32 ? at32<float4>(bk.base[a] + bk.env_off, (ci < last ? ci : last) << 4) : reinterpret_cast<const float4 *>(bk.base[a] + bk.env_off)[ci < last ? ci : last]; // (lanes that are not active may hold anything)
     const float v = fmaf(Nc.x, sdir.x, fmaf(Nc.y, sdir.y, Nc.z * sdir.z));
     if ((active & ~m_le(v, 1.0f)) == 0ull) { occluded = 0ull; FFX_STAT(a == 1 ? 37 : 47); return true; }
   }
@@ -2147,7 +2178,7 @@ __device__ __forceinline__ bool bins_shadow(const BinsK &bk, const int a, const 
   const float scx = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(cx))), scy = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(cy)));
   const float shx = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(hx))), shy = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(hy)));
   Hit hs;
-  traverse_bins<true>(bk.base[a], bk.g[a].nx, stx0, sty0, stx1, sty1, scx, scy, shx, shy, recs, sdir, 0.f, 1.0f - SHADOW_EPS, active, hs, occluded);
+  traverse_bins<true, OFF32>(bk.base[a], bk.g[a].nx, stx0, sty0, stx1, sty1, scx, scy, shx, shy, recs, sdir, 0.f, 1.0f - SHADOW_EPS, active, hs, occluded);
   return true;
 }
 
@@ -2167,11 +2198,19 @@ struct ShadePre {
 // each phase re-reads what it needs with scalar loads from the kernarg segment (no VALU work at all).
 
 // whether any of the four texels of the bilinear footprint at (u, v) is non-zero (same texel arithmetic as the footprint phase)
+// (OFF32: one channel, the four texels at 32-bit offsets — at32)
+template <bool OFF32 = false>
 __device__ __forceinline__ bool tex_footprint_lit(const float *__restrict__ tex, int tw, int th, int tc, float u, float v) {
   const float fx = fmaf(u, (float)tw, -0.5f), fy = fmaf(v, (float)th, -0.5f);
   const int ix0 = (int)floorf(fx), iy0 = (int)floorf(fy);
   const int x0 = clampi(ix0, 0, tw - 1), x1 = clampi(ix0 + 1, 0, tw - 1), y0 = clampi(iy0, 0, th - 1), y1 = clampi(iy0 + 1, 0, th - 1);
   float m = 0.f;
+  if constexpr (OFF32) {
+    const uint32_t r0 = __umul24((uint32_t)y0, (uint32_t)tw), r1 = __umul24((uint32_t)y1, (uint32_t)tw);
+    m = fmaxf(m, fmaxf(fmaxf(fabsf(at32<float>(tex, (r0 + (uint32_t)x0) << 2)), fabsf(at32<float>(tex, (r0 + (uint32_t)x1) << 2))),
+                       fmaxf(fabsf(at32<float>(tex, (r1 + (uint32_t)x0) << 2)), fabsf(at32<float>(tex, (r1 + (uint32_t)x1) << 2)))));
+    return m > 0.f;
+  }
   for (int ch = 0; ch < tc; ++ch)
     m = fmaxf(m, fmaxf(fmaxf(fabsf(tex[((size_t)y0 * tw + x0) * tc + ch]), fabsf(tex[((size_t)y0 * tw + x1) * tc + ch])),
                        fmaxf(fabsf(tex[((size_t)y1 * tw + x0) * tc + ch]), fabsf(tex[((size_t)y1 * tw + x1) * tc + ch]))));
@@ -2202,7 +2241,7 @@ __device__ __forceinline__ void shade_sample_pk(const BvhNode *__restrict__ node
   bool binned = false;
   // (blk_w x blk_h > 1: the packet's primary rays belong to a compact block of pixels whose first is (px, py) — k_render_fwd_blk, renders at
   // fewer than 64 samples per pixel; the default arguments are constants of every other caller)
-  if (blk_w * blk_h == 1) binned = bins_primary(kernarg_shade().bins, px, py, arecs, d[0], nt[0], ft[0], wballot(active[0]), h[0]);
+  if (blk_w * blk_h == 1) binned = bins_primary<PLAIN && FFX_K8_OFF32>(kernarg_shade().bins, px, py, arecs, d[0], nt[0], ft[0], wballot(active[0]), h[0]);
   else binned = bins_block(kernarg_shade().bins, px, py, blk_w, blk_h, arecs, d[0], nt[0], ft[0], wballot(active[0]), h[0]);
   if (!binned) {
     FFX_STAT(36);
@@ -2247,7 +2286,7 @@ __device__ __forceinline__ void shade_sample_pk(const BvhNode *__restrict__ node
       // the unit geometric normal comes from the update (ffx_bvh_info.off_gn: IEEE, the oracle's bits) — re-deriving it from the
       // record cost 22 VALU per sample (cross, dot, sqrt, reciprocal, scale) — with the shape id and the smooth flag in its fourth
       // word: the record itself is only touched by samples that interpolate normals or look up a base-colour texture
-      const float4 gq = gn[h[r].slot];
+      const float4 gq = (PLAIN && FFX_K8_OFF32) ? at32<float4>(gn, (uint32_t)h[r].slot << 4) : gn[h[r].slot];
       const int gbits = __float_as_int(gq.w); // 0: degenerate triangle; else (shape + 1) | smooth << 30
       st[r].shape = (gbits & FFX_GN_SHAPE_MASK) - 1;
       q.P = V3(fmaf(h[r].t, d[r].x, o[r].x), fmaf(h[r].t, d[r].y, o[r].y), fmaf(h[r].t, d[r].z, o[r].z));
@@ -2301,7 +2340,7 @@ __device__ __forceinline__ void shade_sample_pk(const BvhNode *__restrict__ node
           if (any_smooth) lit = lit && (!smooth || vdot(q.ng, wi) > 0.f); // the emitter on the viewer's GEOMETRIC side too
           if constexpr (MAT) {
             // (material rows: the texture probe — see below — comes first, it saves the BSDF of a dark footprint too)
-            if (tex_probe && lit) lit = tex_footprint_lit(tex_probe, c.tw, c.th, PLAIN ? 1 : c.tc, q.u, q.v);
+            if (tex_probe && lit) lit = tex_footprint_lit<PLAIN && FFX_K8_OFF32>(tex_probe, c.tw, c.th, PLAIN ? 1 : c.tc, q.u, q.v);
           }
           if (lit) {
             q.need_p = true;
@@ -2378,7 +2417,7 @@ __device__ __forceinline__ void shade_sample_pk(const BvhNode *__restrict__ node
     const TriApex *arecs_p = reinterpret_cast<const TriApex *>(reinterpret_cast<const char *>(arecs) + astride);
     bool binned_p = false;
     wmask occm;
-    binned_p = bins_shadow(kernarg_shade().bins, 1, arecs_p, sdir[0], wballot(act[0]), occm);
+    binned_p = bins_shadow<PLAIN && FFX_K8_OFF32>(kernarg_shade().bins, 1, arecs_p, sdir[0], wballot(act[0]), occm);
     if (binned_p) occ_p[0] = __builtin_amdgcn_inverse_ballot_w64(occm);
     if (!binned_p) {
       FFX_STAT(44);
@@ -2409,7 +2448,7 @@ __device__ __forceinline__ void shade_sample_pk(const BvhNode *__restrict__ node
     const TriApex *arecs_s = reinterpret_cast<const TriApex *>(reinterpret_cast<const char *>(arecs) + 2u * astride);
     bool binned_s = false;
     wmask occm;
-    binned_s = bins_shadow(kernarg_shade().bins, 2, arecs_s, sdir[0], wballot(act[0]), occm);
+    binned_s = bins_shadow<PLAIN && FFX_K8_OFF32>(kernarg_shade().bins, 2, arecs_s, sdir[0], wballot(act[0]), occm);
     if (binned_s) occ_s[0] = __builtin_amdgcn_inverse_ballot_w64(occm);
     if (!binned_s) {
       FFX_STAT(45);
@@ -2438,10 +2477,11 @@ __device__ __forceinline__ void shade_sample_pk(const BvhNode *__restrict__ node
       const bool lit_p = q.need_p && !occ_p[r], lit_s = q.need_s && !occ_s[r];
       if constexpr (TEX) { st[r].base[0] = st[r].base[1] = st[r].base[2] = 0.f; }
       if (lit_p || lit_s) {
-        const float *mrow = mat_table(c2) + (size_t)FFX_MAT_STRIDE * st[r].shape;
+        const float *mrow = (PLAIN && FFX_K8_OFF32) ? &at32<float>(c2.mat_h, __umul24((uint32_t)st[r].shape, FFX_MAT_STRIDE * 4u)) : mat_table(c2) + (size_t)FFX_MAT_STRIDE * st[r].shape;
         const bool mat_on = PLAIN || mrow[FFX_MAT_MODEL] != 0.f;
         // (wave-uniform: the rows travel with the call and the host derived their constants — other tables take the on-the-fly form)
-        const float *prow = (PLAIN || c2.mat_pre_on) ? c2.mat_pre + FFX_PRE_FLOATS * st[r].shape : nullptr;
+        const float *prow = (PLAIN && FFX_K8_OFF32) ? &at32<float>(c2.mat_pre, __umul24((uint32_t)st[r].shape, FFX_PRE_FLOATS * 4u))
+                            : (PLAIN || c2.mat_pre_on) ? c2.mat_pre + FFX_PRE_FLOATS * st[r].shape : nullptr;
         const v3 wv = V3(-d[r].x, -d[r].y, -d[r].z);
         if constexpr (TEX) { // base colour of this sample: the row's, or its texture at the hit (only lit samples need one)
           st[r].base[0] = mrow[0]; st[r].base[1] = mrow[1]; st[r].base[2] = mrow[2];
@@ -2968,7 +3008,7 @@ __global__ void __launch_bounds__(PK_BLOCK) __attribute__((amdgpu_waves_per_eu(M
         uint32_t idx = pix[r] * (uint32_t)spp + (uint32_t)s;
         float jx, jy;
         sample_jitter(seed_key, idx, jx, jy);
-        cam_ray(cam, ((float)px[r] + jx) * cam.inv_w, ((float)py[r] + jy) * cam.inv_h, o[r], d[r], nt[r], ft[r]);
+        cam_ray<PLAIN && FFX_K8_BAND>(cam, ((float)px[r] + jx) * cam.inv_w, ((float)py[r] + jy) * cam.inv_h, o[r], d[r], nt[r], ft[r]);
       }
       FFX_TSTOP(tk, 16);
       SampleTerms st[R];
@@ -3087,6 +3127,15 @@ __global__ void __launch_bounds__(PK_BLOCK) __attribute__((amdgpu_waves_per_eu(M
               if (PLAIN || ca.tc == 1) {
                 float wsv = (g0 * alb[0] * ca.p_color[0] + g1 * alb[1] * ca.p_color[1] + g2 * alb[2] * ca.p_color[2]) * pf * inv_spp_u;
                 if (pb != 0.f) wsv += (g0 * ca.p_color[0] + g1 * ca.p_color[1] + g2 * ca.p_color[2]) * pb * inv_spp_u;
+                if constexpr (PLAIN && FFX_K8_OFF32) { // (gtex has the texture's shape: the same 32-bit texel offsets)
+                  if (wsv != 0.f) {
+                    const uint32_t r0 = __umul24((uint32_t)st[0].iy0, (uint32_t)ca.tw), r1 = __umul24((uint32_t)st[0].iy1, (uint32_t)ca.tw);
+                    atomicAdd(const_cast<float *>(&at32<float>(adj_gtex, (r0 + (uint32_t)st[0].ix0) << 2)), wsv * wy0 * wx0);
+                    atomicAdd(const_cast<float *>(&at32<float>(adj_gtex, (r0 + (uint32_t)st[0].ix1) << 2)), wsv * wy0 * wx1);
+                    atomicAdd(const_cast<float *>(&at32<float>(adj_gtex, (r1 + (uint32_t)st[0].ix0) << 2)), wsv * wy1 * wx0);
+                    atomicAdd(const_cast<float *>(&at32<float>(adj_gtex, (r1 + (uint32_t)st[0].ix1) << 2)), wsv * wy1 * wx1);
+                  }
+                } else
                 if (wsv != 0.f) {
                   atomicAdd(adj_gtex + (size_t)st[0].iy0 * ca.tw + st[0].ix0, wsv * wy0 * wx0);
                   atomicAdd(adj_gtex + (size_t)st[0].iy0 * ca.tw + st[0].ix1, wsv * wy0 * wx1);
@@ -3137,6 +3186,9 @@ __global__ void __launch_bounds__(PK_BLOCK) __attribute__((amdgpu_waves_per_eu(M
       for (int r = 0; r < R; ++r) {
         float L[3] = {0.f, 0.f, 0.f}; // this pass's contribution of the lane's sample
         // (a textured row: the sample's own base colour; zero where nothing lit it, and then its terms are zero too)
+        if constexpr (PLAIN && FFX_K8_OFF32) {
+          if (st[r].hit) sample_colour<true, true>(ct, st[r], tex, &at32<float>(ct.mat_h, __umul24((uint32_t)st[r].shape, MS * 4u)), MAT, L);
+        } else
         if (st[r].hit) sample_colour<PLAIN>(ct, st[r], tex, TEX ? st[r].base : mat_table(ct) + MS * st[r].shape, MAT, L);
         float c0 = L[0], c1 = L[1], c2 = L[2];
         if constexpr (RF) {
@@ -3215,7 +3267,7 @@ __global__ void __launch_bounds__(PK_BLOCK) __attribute__((amdgpu_waves_per_eu(M
         int lw = lane;
         asm volatile("" : "+v"(lw));
         if (lw < 25) {
-          const float *alb = mat_table(ca) + MS * fshape;
+          const float *alb = (PLAIN && FFX_K8_OFF32) ? ca.mat_h + MS * fshape : mat_table(ca) + MS * fshape; // (fshape: wave-uniform)
           const float w = s_foot[lw];
           float wb = 0.f;
           if constexpr (MAT) wb = s_foot_b[lw];
@@ -3224,6 +3276,9 @@ __global__ void __launch_bounds__(PK_BLOCK) __attribute__((amdgpu_waves_per_eu(M
           if (w != 0.f || wb != 0.f) {
             if (PLAIN || ca.tc == 1) {
               const float val = foot_value_1ch(g_alb_colour(g, alb, ca.p_color) * inv_spp_u, g_colour(g, ca.p_color) * inv_spp_u, w, wb);
+              if constexpr (PLAIN && FFX_K8_OFF32) {
+                if (val != 0.f) atomicAdd(const_cast<float *>(&at32<float>(adj_gtex, (__umul24((uint32_t)ty, (uint32_t)ca.tw) + (uint32_t)tx) << 2)), val);
+              } else
               if (val != 0.f) atomicAdd(adj_gtex + (size_t)ty * ca.tw + tx, val);
             } else {
               float *t = adj_gtex + ((size_t)ty * ca.tw + tx) * 3;
@@ -5667,10 +5722,17 @@ template <class F> static void dispatch_rf_dir_amb(bool rf, bool dir, bool amb, 
 // travel inline and shade_prepare derived a pre-row for each (mat_pre_on), every row is a principled row (model != 0) with no optional lobe (its
 // flag word is 0), the blob's last update flagged no shape smooth (ffx_blob_flat: a blob this process has not updated is not known to be flat), a spot
 // is rigid, a projector texture has one channel, the film is f32 and takes one pass.  Box film, no adjoint cache: the route's own conditions.
+// The camera is in band (ffx_band.h: w_uniform, qz one-signed over the film, |np|^2 and |dl.z| within [2^-40, 2^40], bounded in double from the
+// film's corners with the float roundings covered) — cam_ray<BAND> then takes its root and its two reciprocals as seed + fma chain, without the
+// IEEE expansions' scaling, fix-up and class steps, which do nothing there.  The blob (tile bins with their envelopes, gn, apex records) and the
+// projector's texture are below 2^32 bytes, the texture's sides below 2^24; the rows are kernel arguments: the instance addresses all of them by
+// 32-bit offsets from their scalar bases (at32).
 int ffx_blob_flat(const void *bvh); // (ffx_scene.hip; not part of the C ABI)
-static bool plain_scene(const RenderSetup &r, const ffx_scene_desc *sd, const void *bvh, int fp16) {
+static bool plain_scene(const RenderSetup &r, const ffx_scene_desc *sd, const void *bvh, const ffx_bvh_info *info, int fp16) {
   if (!k8_plain_enabled() || r.matm != 1 || !r.c.mat_inline || !r.c.mat_pre_on || (fp16 & FFX_RENDER_FP16) || r.spp > 64) return false;
   if ((r.c.spot_on && !r.c.s_rigid) || (r.c.proj_on && r.c.tc != 1)) return false;
+  if (FFX_K8_BAND && !ffx_cam_in_band(r.c.cam.s2c, r.c.cam.w_uniform, r.c.cam.iw_u)) return false;
+  if (FFX_K8_OFF32 && (info->total_bytes >= (1ull << 32) || (r.c.proj_on && (r.c.tw >= (1 << 24) || r.c.th >= (1 << 24) || 4ull * (uint64_t)r.c.tw * (uint64_t)r.c.th >= (1ull << 32))))) return false;
   for (int k = 0; k < sd->n_shapes; ++k) { // (mat_pre_on: at most 8 rows, all inline)
     uint32_t flags;
     memcpy(&flags, &r.c.mat_pre[k * FFX_PRE_FLOATS + FFX_PRE_FLAGS], 4);
@@ -5876,7 +5938,7 @@ static int render_fwd_impl(const void *bvh, const ffx_bvh_info *info, const ffx_
       FFX_CHECK_LAUNCH("render_fwd (pixel blocks)");
       return FFX_OK;
     }
-    launch_fwd_pk<2>(use_wide(info), r, p, tex, {img_fp16, img, (char *)cache, {foot_off, arena_off, foot_b_off}, cap_stray, adj_gimg, adj_gtex, adj_dot, !cache && plain_scene(r, sd, bvh, img_fp16)}, st);
+    launch_fwd_pk<2>(use_wide(info), r, p, tex, {img_fp16, img, (char *)cache, {foot_off, arena_off, foot_b_off}, cap_stray, adj_gimg, adj_gtex, adj_dot, !cache && plain_scene(r, sd, bvh, info, img_fp16)}, st);
     FFX_CHECK_LAUNCH("render_fwd");
     return FFX_OK;
   }

@@ -4,7 +4,8 @@ principled material), each rendered `reps` times back to back with nothing else 
 of the per-pose median of ffx_render_fwd's duration (apex pre-pass + K8, HIP events on the launch stream).  Resolves ~0.3 %,
 which the bench loop (random poses, refits sharing the GPU) does not.
 
-    python tools/k8ab.py [name=path/to/libffx_hip_variant.so ...]        (the in-tree library is always measured as "tree")
+    python tools/k8ab.py [name=path/to/libffx_hip_variant.so ...]        (the in-tree library is always measured as "tree": first, or where a
+                                                                          bare `tree` stands among the arms — reversed orders)
     FFX_K8AB_ARGS="--workload colon --res 1024 --spp 256" ...             (workload of the child processes)
 Child mode (one library per process, FFX_LIB decides which):  python tools/k8ab.py --child
 """
@@ -63,10 +64,13 @@ def child():
 def main():
     if "--child" in sys.argv:
         return child()
-    builds = [("tree", os.path.join(ROOT, "fireflies_amd", "csrc", "libffx_hip.so"))]
+    tree = os.path.join(ROOT, "fireflies_amd", "csrc", "libffx_hip.so")
+    builds = []
     for spec in sys.argv[1:]:
-        name, path = spec.split("=", 1)
-        builds.append((name, os.path.abspath(path)))
+        name, _, path = spec.partition("=")
+        builds.append((name, os.path.abspath(path) if path else tree))  # (a bare "tree": the in-tree library at this place in the order)
+    if not any(n == "tree" for n, _ in builds):
+        builds.insert(0, ("tree", tree))
     extra = os.environ.get("FFX_K8AB_ARGS", "").split()
     base = None
     for rnd in range(2):  # two interleaved rounds: drift of the clocks shows up as a difference between them
@@ -76,12 +80,12 @@ def main():
             try:
                 d = json.loads(r.stdout.strip().splitlines()[-1])
             except Exception:
-                print(f"{name:24s} FAILED\n{r.stderr[-1500:]}")
-                continue
+                print(f"{name:24s} FAILED (exit status {r.returncode})\n{r.stderr[-1500:]}")
+                return 1  # (nothing more is started on a GPU on which a child has just failed)
             if base is None:
                 base = d["ms"]
             print(f"round {rnd} {name:24s} {d['ms']:.4f} ms  ({100.0 * (d['ms'] / base - 1.0):+.2f} % vs the first)   poses: " + " ".join(f"{v:.3f}" for v in d["per_pose"]), flush=True)
 
 
 if __name__ == "__main__":
-    main()
+    sys.exit(main())

@@ -194,6 +194,22 @@
 #define K_BR_NT(i) "s_cbranch_scc1 1f\n"
 #define K_CMPBR(i) "s_cmp_lg_u32 s36, 0\n s_cbranch_scc0 1f\n"
 
+// integer multiplies, the 64-bit address forms and the IEEE division's range steps (64-bit destinations P, 64-bit sources Q, carry-outs into S)
+#define K_MUL_LO_U32(i) "v_mul_lo_u32 " D(i) ", " A(i) ", " B(i) "\n"
+#define K_MAD_U32_U24(i) "v_mad_u32_u24 " D(i) ", " A(i) ", " B(i) ", " A(i) "\n"
+#define K_MAD_I64_I32(i) "v_mad_i64_i32 " P(i) ", " S(i) ", " A(i) ", " B(i) ", " Q(i) "\n"
+#define K_MAD_U64_U32(i) "v_mad_u64_u32 " P(i) ", " S(i) ", " A(i) ", " B(i) ", " Q(i) "\n"
+#define K_LSHL_ADD_U64(i) "v_lshl_add_u64 " P(i) ", " Q(i) ", 2, " Q(i) "\n"
+#define K_LSHLREV_B64(i) "v_lshlrev_b64 " P(i) ", 2, " Q(i) "\n"
+#define K_DIV_SCALE(i) "v_div_scale_f32 " D(i) ", " S(i) ", " A(i) ", " A(i) ", " B(i) "\n"
+#define K_DIV_SCALE_VCC(i) "v_div_scale_f32 " D(i) ", vcc, " B(i) ", " A(i) ", " B(i) "\n"
+#define K_DIV_FMAS(i) "v_div_fmas_f32 " D(i) ", " A(i) ", " B(i) ", " A(i) "\n"
+#define K_DIV_FIXUP(i) "v_div_fixup_f32 " D(i) ", " A(i) ", " B(i) ", " A(i) "\n"
+// the select of the compiler's range arms: v_cmp into VCC, the two wait states the hardware wants before a VALU reads a mask a VALU wrote, the VOP2 select
+#define K_CMP_CND_VCC(i) "v_cmp_le_f32 vcc, " A(i) ", " B(i) "\n s_nop 1\n v_cndmask_b32 " D(i) ", " A(i) ", " B(i) ", vcc\n"
+// ... and the same through an SGPR pair (VOP3 compare, VOP3 select)
+#define K_CMP_CND_S(i) "v_cmp_le_f32 s[40:41], " A(i) ", " B(i) "\n s_nop 1\n v_cndmask_b32 " D(i) ", " A(i) ", " B(i) ", s[40:41]\n"
+
 #define CLOB "v32", "v33", "v34", "v35", "v36", "v37", "v38", "v39", "v40", "v41", "v42", "v43", "v44", "v45", "v46", "v47", "v48", "v49", "v50", "v51", \
              "v52", "v53", "v54", "v55", "v56", "v57", "v58", "v59", "v60", "v61", "v62", "v63", "s40", "s41", "s42", "s43", "s44", "s45", "s46", "s47",   \
              "s48", "s49", "s50", "s51", "s52", "s53", "s54", "s55", "s56", "s57", "s58", "s59", "s60", "s61", "s62", "s63", "s64", "s65", "s66", "s67",   \
@@ -269,6 +285,19 @@ KERNEL(k_snop1, X4(K_SNOP1))
 KERNEL(k_dpp_chain, X4(K_DPP_CHAIN))
 KERNEL(k_rl_smin, X4(K_RL_SMIN))
 KERNEL(k_cmp_br, X4(K_CMP_BR))
+
+KERNEL(k_mul_lo_u32, X4(K_MUL_LO_U32))
+KERNEL(k_mad_u32_u24, X4(K_MAD_U32_U24))
+KERNEL(k_mad_i64_i32, X4(K_MAD_I64_I32))
+KERNEL(k_mad_u64_u32, X4(K_MAD_U64_U32))
+KERNEL(k_lshl_add_u64, X4(K_LSHL_ADD_U64))
+KERNEL(k_lshlrev_b64, X4(K_LSHLREV_B64))
+KERNEL(k_div_scale, X4(K_DIV_SCALE))
+KERNEL(k_div_scale_vcc, X4(K_DIV_SCALE_VCC))
+KERNEL(k_div_fmas, X4(K_DIV_FMAS))
+KERNEL(k_div_fixup, X4(K_DIV_FIXUP))
+KERNEL(k_cmp_cnd_vcc, X4(K_CMP_CND_VCC))
+KERNEL(k_cmp_cnd_s, X4(K_CMP_CND_S))
 
 // scalar loads from a 4 KB table (scalar-cache hits): 16 x s_load_dwordx16 per iteration, drained once per iteration
 __global__ void __launch_bounds__(64) k_sload16(float *out, Stamp *st, int iters, const int *tab) {
@@ -402,6 +431,20 @@ int main(int argc, char **argv) {
   RUN(k_dpp_chain, "s_nop 1 + dependent v_min_u32_dpp (pair)", 64)
   RUN(k_rl_smin, "v_readlane -> s_min_u32 (pair)", 64)
   RUN(k_cmp_br, "v_cmp->s_and->s_cmp->branch (4 instr)", 64)
+  // (round 9: what the plain-scene instance's launch-proven diets take out — `issue_rates r9:` runs these alone)
+  RUN(k_mul_lo_u32, "r9: v_mul_lo_u32", 64)
+  RUN(k_mad_u32_u24, "r9: v_mad_u32_u24", 64)
+  RUN(k_mad_i64_i32, "r9: v_mad_i64_i32", 64)
+  RUN(k_mad_u64_u32, "r9: v_mad_u64_u32", 64)
+  RUN(k_lshl_add_u64, "r9: v_lshl_add_u64", 64)
+  RUN(k_lshlrev_b64, "r9: v_lshlrev_b64", 64)
+  RUN(k_div_scale, "r9: v_div_scale_f32 -> SGPR pair", 64)
+  RUN(k_div_scale_vcc, "r9: v_div_scale_f32 -> vcc", 64)
+  RUN(k_div_fmas, "r9: v_div_fmas_f32", 64)
+  RUN(k_div_fixup, "r9: v_div_fixup_f32", 64)
+  RUN(k_cmp_cnd_vcc, "r9: v_cmp->vcc, s_nop 1, v_cndmask vcc (per triple)", 64)
+  RUN(k_cmp_cnd_s, "r9: v_cmp->SGPR, s_nop 1, v_cndmask SGPR (per triple)", 64)
+  if (g_filter && !strcmp(g_filter, "r9:")) return 0;
   for (int w : {1, 2, 4, 7, 8})
     time_one("s_load_dwordx16 (scalar-cache hits)", 16, w,
              [&](int blocks, size_t lds, int iters) { hipLaunchKernelGGL(k_sload16, dim3(blocks), dim3(64), lds, 0, d_out, d_st, iters, d_tab); });
