@@ -330,13 +330,22 @@ PROTOTYPES = {
 PROTOTYPES_NO_ORACLE = {
     # img, elem_size, h, w, background, connectivity, labels, n_labels, stats, centroids, max_labels, workspace, stream
     "ffx_connected_components": (c_i, [c_p, c_i, c_i, c_i, C.c_int64, c_i, c_p, c_p, c_p, c_p, c_i, c_p, c_p]),
+    # angles, pos, octaves, r0, r1, persistence, h, w, color_a, color_b, layout, out, workspace, stream
+    "ffx_perlin_texture": (c_i, [c_p, c_p, c_i, c_i, c_i, C.c_double, c_i, c_i, c_p, c_p, c_i, c_p, c_p, c_p]),
 }
+PERLIN_MAX_OCTAVES = 8
+PERLIN_LAYOUT_CHW, PERLIN_LAYOUT_HWC = 0, 1  # the `layout` argument of ffx_perlin_texture: [3, h, w] / [h, w, 3]
 
 
 def components_workspace_bytes(h, w, max_labels):
     """FFX_COMPONENTS_WORKSPACE_BYTES(h, w, max_labels) of include/ffx_labels.h"""
     n = int(h) * int(w)
     return 8 * n + 16 * ((n + 4095) // 4096) + 40 * max(int(max_labels), 0)
+
+
+def perlin_workspace_bytes(h, w):
+    """FFX_PERLIN_WORKSPACE_BYTES(h, w) of include/ffx_labels.h"""
+    return 16 + 8 * (((int(h) + 15) // 16) * ((int(w) + 63) // 64))
 
 
 class FFXError(RuntimeError):

@@ -426,6 +426,55 @@ def connected_components(img, connectivity=8, background=0, max_labels=256, labe
     return Components(n, lab, st, cen)
 
 
+_PERLIN_LAYOUTS = {"chw": _abi.PERLIN_LAYOUT_CHW, "hwc": _abi.PERLIN_LAYOUT_HWC}
+
+
+def perlin_angle_count(res, octaves):
+    """floats of the packed lattice angles of ffx_perlin_texture: (R0 + 1) * (R1 + 1) per octave, R = res * 2^octave"""
+    return sum(((int(res[0]) << o) + 1) * ((int(res[1]) << o) + 1) for o in range(int(octaves)))
+
+
+def perlin_texture(angles, pos, octaves, res, persistence, shape, color_a, color_b, layout="hwc", workspace=None):
+    """color_a .. color_b blended by the normalised multi-octave Perlin noise of DESIGN.md 4.12 (ffx_perlin_texture; main.py:148-153) -> a fresh
+    [H, W, 3] (layout "hwc", the renderer's) or [3, H, W] ("chw") float32 tensor.  angles: the octaves' lattice angles packed one after the other,
+    perlin_angle_count(res, octaves) floats; pos: per octave the H row positions then the W column positions inside their cells, octaves * (H + W)
+    floats; color_a, color_b: [3]; all float32 on one HIP device, contiguous.  workspace: a uint8 tensor of at least _abi.perlin_workspace_bytes(H, W)
+    bytes to use instead of a fresh one (its contents do not matter)."""
+    for name, t in (("angles", angles), ("pos", pos), ("color_a", color_a), ("color_b", color_b)):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{name}: expected a torch.Tensor")
+        if t.dtype != torch.float32:
+            raise TypeError(f"{name}: expected float32, got {t.dtype}")
+    if layout not in _PERLIN_LAYOUTS:
+        raise ValueError(f"layout: {layout!r} ('hwc' or 'chw')")
+    octaves, h, w, r0, r1 = int(octaves), int(shape[0]), int(shape[1]), int(res[0]), int(res[1])
+    if not 1 <= octaves <= _abi.PERLIN_MAX_OCTAVES:
+        raise ValueError(f"octaves: {octaves} outside 1..{_abi.PERLIN_MAX_OCTAVES}")
+    if min(h, w, r0, r1) < 1 or max(h, w) > 32768:
+        raise ValueError(f"shape / res: {h} x {w} texels (1..32768), a {r0} x {r1} lattice (at least 1 x 1)")
+    if (r0 << (octaves - 1)) > h or (r1 << (octaves - 1)) > w:
+        raise ValueError(f"res: octave {octaves - 1}'s {r0 << (octaves - 1)} x {r1 << (octaves - 1)} lattice needs at least as many texels per axis (got {h} x {w})")
+    if angles.dim() != 1 or angles.numel() != perlin_angle_count((r0, r1), octaves):
+        raise ValueError(f"angles: expected {perlin_angle_count((r0, r1), octaves)} packed floats, got {tuple(angles.shape)}")
+    if pos.dim() != 1 or pos.numel() != octaves * (h + w):
+        raise ValueError(f"pos: expected {octaves * (h + w)} packed floats, got {tuple(pos.shape)}")
+    for name, t in (("color_a", color_a), ("color_b", color_b)):
+        if tuple(t.shape) != (3,):
+            raise ValueError(f"{name}: expected [3], got {tuple(t.shape)}")
+    p_ang, p_pos, p_a, p_b = _dev(angles, name="angles"), _dev(pos, name="pos"), _dev(color_a, name="color_a"), _dev(color_b, name="color_b")
+    if not angles.device == pos.device == color_a.device == color_b.device:
+        raise ValueError("angles, pos, color_a and color_b must live on one device")
+    need = _abi.perlin_workspace_bytes(h, w)
+    if workspace is None:
+        workspace = torch.empty(need, dtype=torch.uint8, device=angles.device)
+    elif workspace.numel() < need:
+        raise ValueError(f"workspace: {workspace.numel()} bytes, the call needs {need}")
+    out = torch.empty((h, w, 3) if layout == "hwc" else (3, h, w), dtype=torch.float32, device=angles.device)
+    api().call("ffx_perlin_texture", p_ang, p_pos, octaves, r0, r1, float(persistence), h, w, p_a, p_b, _PERLIN_LAYOUTS[layout], _dev(out, name="out"),
+               _dev(workspace, torch.uint8, "workspace"), _stream(angles.device))
+    return out
+
+
 def blur_bwd(g, ksize=5, sigma=3.0):
     out = torch.empty_like(g)
     api().call("ffx_blur_bwd", _dev(g, name="g"), g.shape[0], g.shape[1], ksize, float(sigma), _dev(out), _stream())

@@ -224,12 +224,20 @@ def _fold_lip(side, phase, n=96, R=1.25, z0=5.0, half_len=1.15, g0=0.28):
     return verts, tris
 
 
-def vocalfold(width=512, height=512, tex=500, frames=50, n_fold=96, tube=(64, 128), principled=True):
+def vocalfold(width=512, height=512, tex=500, frames=50, n_fold=96, tube=(64, 128), principled=True, textured=False):
     """cfg2-4: F = 2*tube[0]*tube[1] + 2 * 2*n_fold^2 = 16384 + 36864 = 53248 triangles.
     The material is a principled BSDF with the plugin's defaults, like the reference's "mat-Default OBJ" whose
-    `brdf_0.specular` examples/vocalfold_scene.py:93 randomises (principled=False: diffuse)."""
+    `brdf_0.specular` examples/vocalfold_scene.py:93 randomises (principled=False: diffuse).
+    textured: the larynx gets a material of its own, "mat-Mucosa", whose base colour is a texture (a grey 1 x 1 stand-in for what the dataset loop
+    of main.py:147-153 assigns to `mat-Mucosa.brdf_0.base_color.data`); u runs around the tube and back (no seam), v along it."""
     bsdf = {} if principled else None
     lar_v, lar_t = _tube(tube[0], tube[1], 0.8, 7.5, lambda t, z: 1.25 + 0.08 * np.sin(3 * t) * np.sin(1.3 * z) + 0.05 * np.cos(2.1 * z))
+    larynx = MeshData("mesh-Larynx", lar_v[None], lar_t, (0.80, 0.32, 0.34), "mat-Default OBJ", bsdf)
+    if textured:
+        if not principled:
+            raise ValueError("vocalfold: a textured base colour is a parameter of the principled BSDF")
+        uv = np.stack([np.abs(np.arctan2(lar_v[:, 1], lar_v[:, 0])) / np.pi, (lar_v[:, 2] - 0.8) / (7.5 - 0.8)], -1).astype(np.float32)
+        larynx = MeshData("mesh-Larynx", lar_v[None], lar_t, (0.80, 0.32, 0.34), "mat-Mucosa", bsdf, uv=uv, base_tex=np.full((1, 1, 3), 0.5, np.float32))
     fold_frames = []
     for k in range(frames):
         ph = 2 * np.pi * k / frames
@@ -242,7 +250,7 @@ def vocalfold(width=512, height=512, tex=500, frames=50, n_fold=96, tube=(64, 12
     spot = SpotData("emit-Spot", look_at((0.0, 0.1, 1.5), (0.0, 0.0, 5.0)), (8.0, 8.0, 8.0), 40.0, 30.0)
     return SceneData(
         [
-            MeshData("mesh-Larynx", lar_v[None], lar_t, (0.80, 0.32, 0.34), "mat-Default OBJ", bsdf),
+            larynx,
             MeshData("mesh-VocalFold", np.stack(fold_frames).astype(np.float32), fold_t, (0.85, 0.62, 0.60), "mat-Default OBJ", bsdf),
         ],
         cam, proj, spot, projector_scale=20.0, notes={"config": "vocalfold", "frames": frames},

@@ -23,7 +23,7 @@ class Workload:
 
 
 def vocalfold(device="cuda", width=512, height=512, tex=500, grid=16, frames=50, n_fold=96, tube=(64, 128), shadows=True, randomize=True,
-              entity_device=None, principled=True, lights=None, ambient=None):
+              entity_device=None, principled=True, lights=None, ambient=None, textured=False):
     """configs[1]/[2] of BASELINE.json: animated vocal-fold scene (53,248 triangles at the default
     detail), `grid` x `grid` point laser, camera width x height, projector texture tex x tex.
     Randomisation ranges are those of examples/vocalfold_scene.py:73-92.
@@ -31,9 +31,11 @@ def vocalfold(device="cuda", width=512, height=512, tex=500, grid=16, frames=50,
     default is the GPU; "cpu" draws from torch's CPU generator and avoids one device sync per draw.
     `principled`: the material is Mitsuba's principled BSDF, whose `specular` the reference randomises (False: diffuse).
     `lights`: scenes.LightData entries — emitters beyond the projector and the spot.
-    `ambient`: the radiance (r, g, b) of a constant emitter "emit-World" (DESIGN.md 4.8)."""
+    `ambient`: the radiance (r, g, b) of a constant emitter "emit-World" (DESIGN.md 4.8).
+    `textured`: the larynx's material is "mat-Mucosa" with a texture-valued base colour (scenes.vocalfold): what the dataset loop's Perlin textures
+    are assigned to."""
     edev = device if entity_device is None else entity_device
-    data = scenes.vocalfold(width=width, height=height, tex=tex, frames=frames, n_fold=n_fold, tube=tube, principled=principled)
+    data = scenes.vocalfold(width=width, height=height, tex=tex, frames=frames, n_fold=n_fold, tube=tube, principled=principled, textured=textured)
     data.lights = list(lights or [])
     data.ambient = scenes.AmbientData("emit-World", tuple(float(v) for v in ambient)) if ambient is not None else None
     mi_scene = mi.load_scene_data(data, device=device, shadows=shadows)

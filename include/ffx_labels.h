@@ -1,7 +1,8 @@
 /* ffx_labels.h — the entry points of libffx_hip.so that have no restatement in the CPU oracle.
  *
  * include/ffx.h is the header BOTH shared libraries implement, symbol for symbol.  What is declared here is implemented by
- * fireflies_amd/csrc/libffx_hip.so alone and is held to numpy / scipy references by its own tests (tests/ref_components.py).  The
+ * fireflies_amd/csrc/libffx_hip.so alone and is held to numpy / scipy references by its own tests (tests/ref_components.py,
+ * tests/ref_perlin.py).  The
  * conventions are ffx.h's: FFX_OK or a negative code with a message in ffx_last_error(), the caller owns every buffer, every call is
  * asynchronous on `stream`, arrays are dense and row-major.  FFX_ABI_VERSION is ffx.h's; additions here do not change it.
  */
@@ -43,6 +44,32 @@ int ffx_connected_components(const void *img /*[dev][h,w] integers of elem_size 
                              int connectivity, int32_t *labels /*[dev][h,w] or NULL*/, int32_t *n_labels /*[dev][1]*/,
                              int32_t *stats /*[dev][max_labels,5] or NULL*/, double *centroids /*[dev][max_labels,2] or NULL*/,
                              int max_labels, void *workspace /*[dev] FFX_COMPONENTS_WORKSPACE_BYTES(h, w, max_labels)*/, ffx_stream stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Dataset path, the first step: a multi-octave Perlin base-colour texture.
+ * Replaces the per-texel arithmetic of lerp_sampler.sample() at main.py:148-153 (fireflies/sampling/noise_texture_lerp.py); the lattice
+ * angles stay host draws.  DESIGN.md 4.12 is the definition; in short, per octave o = 0..octaves-1 with R0 = r0 << o, R1 = r1 << o,
+ * c0 = h / R0, c1 = w / R1 (integer divisions):
+ *   angles: [R0+1][R1+1] binary32 lattice angles (2 pi torch.rand), the octaves packed one after the other;
+ *   pos:    fy[h] then fx[w], the binary32 positions of every row / column inside its lattice cell AS THE HOST COMPUTED THEM
+ *           ((torch.arange(0, R0, R0 / h) % 1)[:h]; they are inputs, not recomputed), the octaves packed one after the other;
+ *   texel (i, j): cell cy = min(i / c0, R0-1), cx = min(j / c1, R1-1); py = fy[i], px = fx[j];
+ *           n(dy,dx) = (py-dy) cos(ang[cy+dy][cx+dx]) + (px-dx) sin(ang[cy+dy][cx+dx]); fade(t) = 6t^5 - 15t^4 + 10t^3;
+ *           octave = sqrt(2) lerp(lerp(n00, n10, fade(py)), lerp(n01, n11, fade(py)), fade(px));
+ *   noise = sum_o float(persistence^o) octave_o;  t = (noise - min) / (max - min) over the whole plane (max == min is not special: the
+ *   same IEEE division, a NaN texture);  out[c] = lerp(color_a[c], color_b[c], t).
+ * layout 0 writes [3][h][w], layout 1 writes [h][w][3] (the renderer's).  Three launches (tile extremes, their reduction, the write
+ * pass, which recomputes the noise with the same device function: the extremes come out as exactly color_a and color_b); no atomics,
+ * no workgroup waits for another: two calls give the same bits.  No host synchronisation and no host read of device memory.
+ * Limits: octaves 1..8, 1 <= h, w <= 32768, r0, r1 >= 1, every octave's cell at least one texel (c0, c1 >= 1), layout 0 / 1, workspace
+ * 8-byte aligned.  Outside them, or with a NULL pointer: FFX_ERR_ARG before any launch, the parameter named in the message.
+ * ---------------------------------------------------------------------------------------- */
+/* bytes of `workspace`: the extremes of the plane (two floats, padded to 16 bytes) and two floats per 64 x 16 tile */
+#define FFX_PERLIN_WORKSPACE_BYTES(h, w) ((size_t)16 + (size_t)8 * ((((size_t)(h) + 15) / 16) * (((size_t)(w) + 63) / 64)))
+
+int ffx_perlin_texture(const float *angles /*[dev] packed per octave*/, const float *pos /*[dev] packed per octave: fy[h], fx[w]*/, int octaves, int r0,
+                       int r1, double persistence, int h, int w, const float *color_a /*[dev][3]*/, const float *color_b /*[dev][3]*/, int layout,
+                       float *out /*[dev][3,h,w] or [h,w,3]*/, void *workspace /*[dev] FFX_PERLIN_WORKSPACE_BYTES(h, w)*/, ffx_stream stream);
 
 #ifdef __cplusplus
 }

@@ -6,7 +6,11 @@ With `accept` the loop also covers main.py:168-180: per sample the flag "the seg
 falls into at most two pieces" (graphics.accept_segmentation: connected components on the device, no host read), the loop is timed
 without and with it in turn, all flags are read once behind the loop, and the host's route to the same flag — seg.cpu() plus
 scipy.ndimage.label where scipy is importable, the numpy restatement tests/ref_components.py otherwise — is timed beside it.
-    python tools/datasetbench.py [n_samples] [spp | mix] [accept]"""
+With `perlin` the loop also covers main.py:147-153, its first lines: per sample two colour draws, a 1024 x 1024 NoiseTextureLerpSampler texture and its
+assignment to `mat-Mucosa.brdf_0.base_color.data` of the workload with a textured larynx.  The loop is timed with the sampler's torch engine and with
+its device engine (one call into the library) in turn, both under the same seeds, and one sample() with a synchronise behind it is
+timed beside them for each engine.
+    python tools/datasetbench.py [n_samples] [spp | mix] [accept | perlin]"""
 import os
 import random
 import sys
@@ -24,7 +28,8 @@ spp = sys.argv[2] if len(sys.argv) > 2 else "64"
 MIX = spp == "mix"  # main.py:145 draws every sample's spp: fireflies.sampling.AnimationSampler(1, 100, 1, 100) — here uniform in 1..100 from python's `random`
 spp = 64 if MIX else int(spp)
 ACCEPT = len(sys.argv) > 3 and sys.argv[3] == "accept"
-wl = workloads.vocalfold(device="cuda")
+PERLIN = len(sys.argv) > 3 and sys.argv[3] == "perlin"
+wl = workloads.vocalfold(device="cuda", textured=PERLIN)
 with torch.no_grad():
     wl.params["tex.data"] = workloads.build_texture(wl).contiguous()
 chain = pp.PostProcessor([pp.GaussianBlur((3, 3), (5, 5), 0.5), pp.ApplySilhouette(), pp.WhiteNoise(0.0, 0.05, 0.5, rng="device")])
@@ -32,7 +37,11 @@ torch.manual_seed(0)
 random.seed(0)
 
 
-def sample(i, flags=None):
+def sample(i, flags=None, lerp=None):
+    if lerp is not None:  # main.py:147-153
+        lerp._color_a = torch.rand(3, device="cuda")
+        lerp._color_b = torch.rand(3, device="cuda")
+        wl.params["mat-Mucosa.brdf_0.base_color.data"] = mi.TensorXf(lerp.sample().moveaxis(0, -1))
     wl.ff_scene.randomize()
     img = mi.render(wl.mi_scene, spp=random.randint(1, 100) if MIX else spp, seed=i).torch()
     grey = pp.rgb_to_gray(img)  # cv2.COLOR_RGB2GRAY's weights, one launch (as a torch expression: five)
@@ -112,6 +121,49 @@ if ACCEPT:
     assert bool(flag_d) is flag_h
     print(f"one flag on a {tuple(seg.shape)} label image, median of 7: host route (seg.cpu() + {how}) {1e6 * statistics.median(host_t):.0f} us, "
           f"device call with a synchronise behind it {1e6 * statistics.median(dev_t):.0f} us")
+
+if PERLIN:
+    import statistics
+
+    from fireflies_amd.sampling import NoiseTextureLerpSampler
+
+    SHAPE = (1024, 1024)
+    lerps = {e: NoiseTextureLerpSampler(torch.zeros(3), torch.ones(3), SHAPE, device="cuda", engine=e) for e in ("torch", "device")}
+
+    def loop(lerp, seed):
+        torch.manual_seed(seed)  # (both engines draw the same lattices in a round)
+        random.seed(seed)
+        torch.cuda.synchronize()
+        t = time.perf_counter()
+        for j in range(n):
+            sample(10 + j, lerp=lerp)
+        torch.cuda.synchronize()
+        return time.perf_counter() - t
+
+    times = {e: [] for e in lerps}
+    for e in lerps:
+        loop(lerps[e], 0)  # warm-up: the position tables, the pinned buffers, torch's allocations
+    for k in range(7):  # in turn, so that both see the same drift
+        for e in lerps:
+            times[e].append(loop(lerps[e], 1 + k))
+    med = {e: statistics.median(v) for e, v in times.items()}
+    print(f"textured dataset path (main.py:147-153 in front of each sample, {SHAPE[0]} x {SHAPE[1]} texture), median of 7 loops of {n}: "
+          f"{n / med['torch']:.1f} samples/s with engine='torch', {n / med['device']:.1f} with engine='device' "
+          f"({1e6 * (med['device'] - med['torch']) / n:+.1f} us per sample)")
+    one = {}
+    for e in lerps:
+        torch.manual_seed(100)
+        random.seed(100)
+        ts = []
+        for _ in range(3 + 21):
+            torch.cuda.synchronize()
+            t = time.perf_counter()
+            tex = lerps[e].sample()
+            torch.cuda.synchronize()
+            ts.append(time.perf_counter() - t)
+        one[e] = statistics.median(ts[3:])
+    print(f"one sample() of {SHAPE[0]} x {SHAPE[1]} with a synchronise behind it, median of 21 under the same seeds: engine='torch' {1e6 * one['torch']:.0f} us, "
+          f"engine='device' {1e6 * one['device']:.0f} us")
 
 if os.environ.get("FFX_DS_PROFILE") == "1":  # where the host's time per sample goes (cProfile, 200 samples at 1 spp so that the device is not the limit)
     import cProfile
