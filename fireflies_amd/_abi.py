@@ -332,6 +332,14 @@ PROTOTYPES_NO_ORACLE = {
     "ffx_connected_components": (c_i, [c_p, c_i, c_i, c_i, C.c_int64, c_i, c_p, c_p, c_p, c_p, c_i, c_p, c_p]),
     # angles, pos, octaves, r0, r1, persistence, h, w, color_a, color_b, layout, out, workspace, stream
     "ffx_perlin_texture": (c_i, [c_p, c_p, c_i, c_i, c_i, C.c_double, c_i, c_i, c_p, c_p, c_i, c_p, c_p, c_p]),
+    # pts, depth, n, sigma, size0, size1, gout, gpts, gdepth, stream
+    "ffx_splat_depth_bwd": (c_i, [c_p, c_p, c_i, c_f, c_i, c_i, c_p, c_p, c_p, c_p]),
+    # pts, depth, n, sigma, size0, size1, out, stream
+    "ffx_splat_depth_softor_fwd": (c_i, [c_p, c_p, c_i, c_f, c_i, c_i, c_p, c_p]),
+    # pts, depth, n, sigma, size0, size1, gout, gpts, gdepth, stream
+    "ffx_splat_depth_softor_bwd": (c_i, [c_p, c_p, c_i, c_f, c_i, c_i, c_p, c_p, c_p, c_p]),
+    # bvh, info, origins, dirs, n, t, prim, gt, gorig, gdir, stream
+    "ffx_trace_rays_bwd": (c_i, [c_p, C.POINTER(BvhInfo), c_p, c_p, c_i, c_p, c_p, c_p, c_p, c_p, c_p]),
 }
 PERLIN_MAX_OCTAVES = 8
 PERLIN_LAYOUT_CHW, PERLIN_LAYOUT_HWC = 0, 1  # the `layout` argument of ffx_perlin_texture: [3, h, w] / [h, w, 3]

@@ -5,31 +5,10 @@
 // All arithmetic follows the operation order of the reference's torch code (separate multiplies
 // and adds; the file is compiled with -ffp-contract=off), so results agree with the reference to
 // the last few ulps of expf.
-#include "ffx_common.h"
+#include "ffx_splat_shared.h" // tile / list sizes, FFX_QCUT, splat_val, splat_gcoef, wave_sum: shared with ffx_depth.hip
 #include <cstring>
 
-#define SPLAT_BLOCK 256
-#define TILE_W 32
-#define TILE_H 8
-#define CAND_MAX 512   // candidates staged per chunk in the fused forward kernel
-#define NEIGH_MAX 2048 // neighbour list capacity of the gradient kernel
-// exp(-q^2) is exactly 0 in binary32 for q^2 > 103.98; 10.3^2 = 106.1 leaves a margin, so culling
-// on q > FFX_QCUT never drops a non-zero term.
-#define FFX_QCUT 10.3f
-
 // ------------------------------------------------------------------------------- helpers
-// value of one splat at texel (fj, fi); rasterization.py:29-35
-__device__ __forceinline__ float splat_val(float fj, float fi, float p0s, float p1s, float sigma, float inv_sigma, float &d, float &yd, float &xd) {
-  yd = fj - p0s;
-  xd = fi - p1s;
-  d = yd * yd + xd * xd;
-  if (d * inv_sigma > FFX_QCUT) return 0.f;
-  float q = d / sigma;
-  return expf(-(q * q));
-}
-// dv/d(p0*size0) = v*4*d*yd/sigma^2 (and xd for the other axis)
-__device__ __forceinline__ float splat_gcoef(float v, float d, float sigma) { return v * 4.0f * d / (sigma * sigma); }
-
 // window of baked_sum/baked_softor along one axis (rasterization.py:180-235); mirrors
 // window_axis() of the oracle.  Returns false if the point contributes nothing on this axis.
 struct Win1 { int lo, hi, off; float pm; };
@@ -52,12 +31,6 @@ __device__ __forceinline__ float baked_val(int A, int B, const Win1 &w0, const W
   d = yd * yd + xd * xd;
   float q = d / sigma;
   return expf(-(q * q));
-}
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-  return v;
 }
 
 // =================================================================================== K1

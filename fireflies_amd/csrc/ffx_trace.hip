@@ -25,6 +25,7 @@
 
 #include "ffx_common.h"
 #include "ffx_band.h"
+#include "../../include/ffx_labels.h" // ffx_trace_rays_bwd
 
 #define TR_BLOCK 256
 #define RAY_EPS 8.940696716308594e-05f
@@ -332,6 +333,40 @@ __global__ void __launch_bounds__(TR_BLOCK)
   t_out[i] = hit ? h.t : 0.f;
   if (shape_out) shape_out[i] = h.shape;
   if (prim_out) prim_out[i] = h.prim;
+}
+
+// Adjoint of k_trace_rays's t with respect to the rays (ffx_trace_rays_bwd): the hit stays on the plane of its triangle,
+// t = N . (v0 - o) / (N . d) with N = e1 x e2, so dt/do = -N / (N . d) and dt/dd = -t N / (N . d).  A lane per ray.  The forward returns the
+// primitive's id, the records lie in leaf order: the lane walks the tree again with the forward's t as the far end — the boxes are culled
+// against the hit from the first step, the walk visits a handful of nodes — and takes the record of the hit it finds, which is the forward's
+// (same tests, same tie-break).  A miss, or a walk that ends on another primitive than the forward named (the pose changed in between):
+// zeros.  The quotients are formed in binary64 from the record's binary32 edges.
+__global__ void __launch_bounds__(TR_BLOCK)
+    k_trace_rays_bwd(const BvhNode *__restrict__ nodes, const TriRec *__restrict__ recs, const float *__restrict__ org, const float *__restrict__ dir, int n,
+                     const float *__restrict__ t_in, const int32_t *__restrict__ prim_in, const float *__restrict__ gt, float *__restrict__ gorig,
+                     float *__restrict__ gdir) {
+  extern __shared__ int s_stack[];
+  const int i = blockIdx.x * TR_BLOCK + threadIdx.x;
+  if (i >= n) return;
+  double go[3] = {0.0, 0.0, 0.0}, gd[3] = {0.0, 0.0, 0.0};
+  const int prim = prim_in[i];
+  const float t = t_in[i];
+  if (prim >= 0 && t > 0.f) {
+    const v3 o = V3(org[3 * i], org[3 * i + 1], org[3 * i + 2]), d = V3(dir[3 * i], dir[3 * i + 1], dir[3 * i + 2]);
+    Hit h;
+    if (traverse<false, false>(nodes, recs, o, d, 0.f, t, h, s_stack + threadIdx.x, TR_BLOCK) && h.prim == prim) {
+      const float4 *r4 = reinterpret_cast<const float4 *>(recs + h.slot);
+      const float4 a = r4[0], b = r4[1], c = r4[2];
+      const double e1[3] = {a.w, b.x, b.y}, e2[3] = {b.z, b.w, c.x};
+      const double N[3] = {e1[1] * e2[2] - e1[2] * e2[1], e1[2] * e2[0] - e1[0] * e2[2], e1[0] * e2[1] - e1[1] * e2[0]};
+      const double nd = N[0] * (double)d.x + N[1] * (double)d.y + N[2] * (double)d.z;
+      const double s = -(double)gt[i] / nd;
+#pragma unroll
+      for (int c3 = 0; c3 < 3; ++c3) { go[c3] = s * N[c3]; gd[c3] = s * (double)t * N[c3]; }
+    }
+  }
+#pragma unroll
+  for (int c3 = 0; c3 < 3; ++c3) { gorig[3 * i + c3] = (float)go[c3]; gdir[3 * i + c3] = (float)gd[c3]; }
 }
 
 // ------------------------------------------------------------------------------------------ shading
@@ -5853,6 +5888,23 @@ int ffx_trace_rays(const void *bvh, const ffx_bvh_info *info, const float *origi
   hipLaunchKernelGGL(k_trace_rays, dim3(ffx_cdiv(n, TR_BLOCK)), dim3(TR_BLOCK), stack_bytes(info), (hipStream_t)s, b.nodes, b.recs, origins, dirs, n, tmax,
                      t_out, shape_out, prim_out);
   FFX_CHECK_LAUNCH("trace_rays");
+  return FFX_OK;
+}
+
+int ffx_trace_rays_bwd(const void *bvh, const ffx_bvh_info *info, const float *origins, const float *dirs, int n, const float *t, const int32_t *prim,
+                       const float *gt, float *gorig, float *gdir, ffx_stream s) {
+  if (n < 0) FFX_FAIL(FFX_ERR_ARG, "trace_rays_bwd: n = %d is negative", n);
+  if (!bvh) FFX_FAIL(FFX_ERR_ARG, "trace_rays_bwd: bvh is NULL");
+  if (!info) FFX_FAIL(FFX_ERR_ARG, "trace_rays_bwd: info is NULL");
+  if (!check_info(info, "trace_rays_bwd")) return FFX_ERR_ARG;
+  if (n == 0) return FFX_OK;
+  const struct { const void *p; const char *name; } ptrs[] = {{origins, "origins"}, {dirs, "dirs"}, {t, "t"}, {prim, "prim"}, {gt, "gt"}, {gorig, "gorig"}, {gdir, "gdir"}};
+  for (const auto &a : ptrs)
+    if (!a.p) FFX_FAIL(FFX_ERR_ARG, "trace_rays_bwd: %s is NULL", a.name);
+  const BlobView b = blob_view(bvh, info);
+  hipLaunchKernelGGL(k_trace_rays_bwd, dim3(ffx_cdiv(n, TR_BLOCK)), dim3(TR_BLOCK), stack_bytes(info), (hipStream_t)s, b.nodes, b.recs, origins, dirs, n, t, prim,
+                     gt, gorig, gdir);
+  FFX_CHECK_LAUNCH("trace_rays_bwd");
   return FFX_OK;
 }
 

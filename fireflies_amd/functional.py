@@ -104,6 +104,75 @@ def splat(pts, sigma, size0, size1, reduce="sum", half_window=-1):
     return _Splat.apply(pts, float(sigma), reduce, int(half_window), int(size0), int(size1))
 
 
+class _RasterizeDepth(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, pts, depth, sigma, size0, size1):
+        pts, depth = _c(pts), _c(depth.reshape(-1))
+        ctx.save_for_backward(pts, depth)
+        ctx.args = (sigma, size0, size1)
+        return ops.splat_depth_fwd(pts, depth, sigma, size0, size1)
+
+    @staticmethod
+    def backward(ctx, g):
+        pts, depth = ctx.saved_tensors
+        gpts, gdepth = ops.splat_depth_bwd(pts, depth, *ctx.args, _c(g))
+        return gpts, gdepth, None, None, None
+
+
+def rasterize_depth_dense(pts, depth, sigma, size0, size1):
+    """depth layers [N,size1,size0] of graphics/rasterization.py:66-104 — each layer over its own maximum, times its depth —,
+    differentiable in pts [N,2] and depth [N] by one launch each way."""
+    return _RasterizeDepth.apply(pts, depth.reshape(-1), float(sigma), int(size0), int(size1))
+
+
+class _SplatDepthSoftor(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, pts, depth, sigma, size0, size1):
+        pts, depth = _c(pts), _c(depth.reshape(-1))
+        ctx.save_for_backward(pts, depth)
+        ctx.args = (sigma, size0, size1)
+        return ops.splat_depth_softor_fwd(pts, depth, sigma, size0, size1)
+
+    @staticmethod
+    def backward(ctx, g):
+        pts, depth = ctx.saved_tensors
+        gpts, gdepth = ops.splat_depth_softor_bwd(pts, depth, *ctx.args, _c(g))
+        return gpts, gdepth, None, None, None
+
+
+def splat_depth_softor(pts, depth, sigma, size0, size1):
+    """softor over the depth layers -> [size1,size0] in one kernel each way; the [N,size1,size0] stack never exists."""
+    return _SplatDepthSoftor.apply(pts, depth.reshape(-1), float(sigma), int(size0), int(size1))
+
+
+class _TraceRays(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, origins, dirs, geom):
+        origins, dirs = _c(origins), _c(dirs)
+        t, shape, prim = geom.trace_rays(origins, dirs)
+        ctx.save_for_backward(origins, dirs, t, prim)
+        ctx.geom, ctx.pose_version = geom, geom.version
+        ctx.mark_non_differentiable(shape, prim)
+        return t, shape, prim
+
+    @staticmethod
+    def backward(ctx, gt, _gshape, _gprim):
+        origins, dirs, t, prim = ctx.saved_tensors
+        if ctx.geom.version != ctx.pose_version:  # replays the geometry: it must still be in the pose of the forward pass
+            raise RuntimeError(
+                "trace_rays backward: the scene was re-fitted (randomize()/update()) between forward and backward and the adjoint reads the "
+                "hit triangles of the forward's pose: call backward before the next randomisation"
+            )
+        gorig, gdir = ctx.geom.trace_rays_bwd(origins, dirs, t, prim, _c(gt.float()))
+        return gorig, gdir, None
+
+
+def trace_rays(geom, origins, dirs):
+    """K7 for arbitrary rays -> (t, shape, prim); t (in units of the given directions, 0 on a miss) is differentiable in origins and
+    dirs through the plane of the hit triangle, the ids are not."""
+    return _TraceRays.apply(origins, dirs, geom)
+
+
 class _Blur(torch.autograd.Function):
     @staticmethod
     def forward(ctx, img, ksize, sigma):

@@ -9,7 +9,7 @@ with the same names, argument order, output shapes and orientation, executed by 
 
 `texture_size` is (size0, size1) as a tensor or sequence; `device` arguments are accepted for
 source compatibility — the tensors must already live on the HIP device.
-The fused forms `splat_sum` / `splat_softor` never build the [N,H,W] stack; on the reference this
+The fused forms `splat_sum` / `splat_softor` (and `subsampled_point_raster`) never build the [N,H,W] stack; on the reference this
 stack plus ~12 temporaries is the dominant cost of the pattern side.
 """
 import math
@@ -101,14 +101,12 @@ def rasterize_points_baked_sum(points, sigma: float, texture_size, device=None):
 
 
 def rasterize_depth(points, depth_vals, sigma: float, texture_size, device=None):
-    """layers normalised by their own maximum and scaled by depth (:66-104).  Without autograd this
-    is one fused kernel; under autograd it is composed from the differentiable dense splat."""
+    """layers normalised by their own maximum and scaled by depth (:66-104): one kernel, and under autograd one more for the adjoint
+    with respect to the points and the depths — the forward is the same kernel either way."""
     s0, s1 = _size(texture_size)
     pts = points[:, 0:2].contiguous()
     if torch.is_grad_enabled() and (pts.requires_grad or depth_vals.requires_grad):
-        d = Fn.rasterize_points_dense(pts, float(sigma), s0, s1)
-        d = d / d.amax(dim=2, keepdim=True).amax(dim=1, keepdim=True)
-        return d * depth_vals.reshape(-1, 1).unsqueeze(-1)
+        return Fn.rasterize_depth_dense(pts, depth_vals, float(sigma), s0, s1)
     return ops.splat_depth_fwd(pts, depth_vals.reshape(-1).contiguous(), float(sigma), s0, s1)
 
 
@@ -121,9 +119,15 @@ def rasterize_lines(lines, sigma: float, texture_size, device=None):
 
 
 def subsampled_point_raster(ndc_points, num_subsamples, sigma, sensor_size):
-    """multi-resolution pyramid of softor(rasterize_depth) (:538-549)."""
+    """multi-resolution pyramid of softor(rasterize_depth) (:538-549): level i is [1, size1 // 2^i, size0 // 2^i].  One fused kernel per
+    level — the [N,h,w] layers never exist — and one more per level for the adjoint with respect to the points [N,3] = (x, y, depth)
+    (DESIGN.md 4.13)."""
+    s0, s1 = _size(sensor_size)
+    pts, depth = ndc_points[:, 0:2].contiguous(), ndc_points[:, 2].contiguous()
     out = []
     for i in range(num_subsamples):
-        r = rasterize_depth(ndc_points[:, 0:2], ndc_points[:, 2:3], sigma, sensor_size // 2**i)
-        out.append(softor(r, keepdim=True))
+        l0, l1 = s0 // 2**i, s1 // 2**i
+        if l0 < 1 or l1 < 1:
+            raise ValueError(f"subsampled_point_raster: level {i} of a {s0} x {s1} sensor has no texels ({l0} x {l1})")
+        out.append(Fn.splat_depth_softor(pts, depth, float(sigma), l0, l1).unsqueeze(0))
     return out

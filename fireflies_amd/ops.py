@@ -329,6 +329,44 @@ def splat_depth_fwd(pts, depth, sigma, size0, size1):
     return out
 
 
+def _depth_pair(pts, depth):
+    _check_pts(pts)
+    depth = depth.reshape(-1)
+    if depth.shape[0] != pts.shape[0]:
+        raise ValueError(f"depth must hold one value per point: {pts.shape[0]} points, {depth.shape[0]} depths")
+    return depth
+
+
+def splat_depth_bwd(pts, depth, sigma, size0, size1, gout):
+    """adjoint of splat_depth_fwd -> (gpts [n,2], gdepth [n])"""
+    depth = _depth_pair(pts, depth)
+    if tuple(gout.shape) != (pts.shape[0], size1, size0):
+        raise ValueError("gout shape mismatch")
+    gpts, gdepth = torch.empty_like(pts), torch.empty_like(depth)
+    api().call("ffx_splat_depth_bwd", _dev(pts, name="pts"), _dev(depth, name="depth"), pts.shape[0], float(sigma), size0, size1, _dev(gout, name="gout"),
+               _dev(gpts), _dev(gdepth), _stream())
+    return gpts, gdepth
+
+
+def splat_depth_softor_fwd(pts, depth, sigma, size0, size1):
+    """softor over splat_depth_fwd's layers -> [size1,size0], without the layers"""
+    depth = _depth_pair(pts, depth)
+    out = torch.empty((size1, size0), dtype=torch.float32, device=pts.device)
+    api().call("ffx_splat_depth_softor_fwd", _dev(pts, name="pts"), _dev(depth, name="depth"), pts.shape[0], float(sigma), size0, size1, _dev(out), _stream())
+    return out
+
+
+def splat_depth_softor_bwd(pts, depth, sigma, size0, size1, gout):
+    """adjoint of splat_depth_softor_fwd -> (gpts [n,2], gdepth [n])"""
+    depth = _depth_pair(pts, depth)
+    if tuple(gout.shape) != (size1, size0):
+        raise ValueError("gout shape mismatch")
+    gpts, gdepth = torch.empty_like(pts), torch.empty_like(depth)
+    api().call("ffx_splat_depth_softor_bwd", _dev(pts, name="pts"), _dev(depth, name="depth"), pts.shape[0], float(sigma), size0, size1,
+               _dev(gout, name="gout"), _dev(gpts), _dev(gdepth), _stream())
+    return gpts, gdepth
+
+
 def splat_lines_fwd(lines, sigma, size0, size1):
     if lines.dim() != 3 or tuple(lines.shape[1:]) != (2, 2):
         raise ValueError("lines must be [N,2,2]")
@@ -1128,6 +1166,17 @@ class DeviceGeometry:
         )
         self._release()
         return t, shape, prim
+
+    def trace_rays_bwd(self, origins, dirs, t, prim, gt):
+        """adjoint of trace_rays's t with respect to the rays on the pose the forward traced -> (gorig [n,3], gdir [n,3])"""
+        n = origins.shape[0]
+        gorig, gdir = torch.empty_like(origins), torch.empty_like(dirs)
+        self._call(
+            "ffx_trace_rays_bwd", _dev(self.blob, torch.uint8), C.byref(self.info), _dev(origins, name="origins"), _dev(dirs, name="dirs"), n,
+            _dev(t, name="t"), _dev(prim, torch.int32, "prim"), _dev(gt, name="gt"), _dev(gorig), _dev(gdir), _stream(self._didx),
+        )
+        self._release()
+        return gorig, gdir
 
     def _timed(self, name):
         return _EventPair(self.timing, name)

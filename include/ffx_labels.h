@@ -2,7 +2,7 @@
  *
  * include/ffx.h is the header BOTH shared libraries implement, symbol for symbol.  What is declared here is implemented by
  * fireflies_amd/csrc/libffx_hip.so alone and is held to numpy / scipy references by its own tests (tests/ref_components.py,
- * tests/ref_perlin.py).  The
+ * tests/ref_perlin.py, tests/ref_sparse_depth.py).  The
  * conventions are ffx.h's: FFX_OK or a negative code with a message in ffx_last_error(), the caller owns every buffer, every call is
  * asynchronous on `stream`, arrays are dense and row-major.  FFX_ABI_VERSION is ffx.h's; additions here do not change it.
  */
@@ -70,6 +70,45 @@ int ffx_connected_components(const void *img /*[dev][h,w] integers of elem_size 
 int ffx_perlin_texture(const float *angles /*[dev] packed per octave*/, const float *pos /*[dev] packed per octave: fy[h], fx[w]*/, int octaves, int r0,
                        int r1, double persistence, int h, int w, const float *color_a /*[dev][3]*/, const float *color_b /*[dev][3]*/, int layout,
                        float *out /*[dev][3,h,w] or [h,w,3]*/, void *workspace /*[dev] FFX_PERLIN_WORKSPACE_BYTES(h, w)*/, ffx_stream stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Sparse-depth route: the laser's hits as a differentiable sparse depth image.
+ * Replaces the autograd graphs of rasterize_depth (fireflies/graphics/rasterization.py:66-104), of softor(rasterize_depth) in
+ * subsampled_point_raster (:538-549) and of dr.wrap_ad around ray_intersect in cast_laser (fireflies/graphics/depth.py:16).
+ * With p = (pts[n][0] size0, pts[n][1] size1) and the texel x = (j, i):
+ *   e_n(x)     = exp(-(|x - p|^2 / sigma)^2), exactly 0 beyond the footprint ffx_splat_fwd cuts at;
+ *   m_n        = e_n(x*), x* = rintf(p) clamped into the texture (ffx_splat_depth_fwd's statement of the layer maximum);
+ *   layer_n(x) = (e_n(x) / m_n) depth[n]: the float ffx_splat_depth_fwd writes.
+ * ffx_splat_depth_bwd         adjoint of ffx_splat_depth_fwd:  gdepth[n] = sum_x gout[n](x) e_n / m_n,
+ *                             gpts[n] = (depth[n] / m_n) sum_x gout[n](x) (de_n/dp - (e_n / m_n) dm_n/dp), chained through the scaling by the
+ *                             size; dm_n/dp at the FIXED x*.  At a rintf tie the layer is not differentiable: the value is that of the x* rintf picks.
+ * ffx_splat_depth_softor_fwd  out = 1 - prod_n (1 - layer_n), the product in ascending point order in binary32: bit for bit what the host
+ *                             forms from ffx_splat_depth_fwd's layers; the [n,size1,size0] stack never exists.  n = 0: a zero plane.
+ * ffx_splat_depth_softor_bwd  its adjoint: the sums above with gout(x) prod_{k != n} (1 - layer_k(x)) for gout[n](x); the product is formed from
+ *                             the other points' factors, never by dividing by the point's own.
+ * A point whose m_n underflows to 0 (far outside the texture) has a NaN layer: the fused forward gives the NaN plane the layers give; the
+ * adjoints on such input are unspecified.  depth is taken finite.
+ * Per-texel terms binary32, their sums binary64; no atomics: two calls give the same bits.  Everything is written, nothing accumulated
+ * (n = 0: the adjoints have nothing to write).  No host synchronisation.
+ * Refused with FFX_ERR_ARG before any launch, the parameter named: n < 0, size0 / size1 < 1, sigma <= 0 (or NaN), a NULL pointer that
+ * would be read or written.
+ * ---------------------------------------------------------------------------------------- */
+int ffx_splat_depth_bwd(const float *pts /*[dev][n,2]*/, const float *depth /*[dev][n]*/, int n, float sigma, int size0, int size1,
+                        const float *gout /*[dev][n,size1,size0]*/, float *gpts /*[dev][n,2]*/, float *gdepth /*[dev][n]*/, ffx_stream stream);
+int ffx_splat_depth_softor_fwd(const float *pts /*[dev][n,2]*/, const float *depth /*[dev][n]*/, int n, float sigma, int size0, int size1,
+                               float *out /*[dev][size1,size0]*/, ffx_stream stream);
+int ffx_splat_depth_softor_bwd(const float *pts /*[dev][n,2]*/, const float *depth /*[dev][n]*/, int n, float sigma, int size0, int size1,
+                               const float *gout /*[dev][size1,size0]*/, float *gpts /*[dev][n,2]*/, float *gdepth /*[dev][n]*/, ffx_stream stream);
+
+/* Adjoint of ffx_trace_rays's t with respect to the rays.  A hit stays on the plane of its triangle (current world vertices v0, v1, v2,
+ * N = (v1 - v0) x (v2 - v0)):  t = N . (v0 - o) / (N . d) in units of the given d, so
+ *   gorig[r] = -gt[r] N / (N . d),   gdir[r] = -gt[r] t[r] N / (N . d);   a miss (prim[r] < 0): zeros.
+ * t and prim are the forward's outputs for the same rays on the same pose of the blob.  No term for a ray that crosses an edge or a
+ * silhouette (Mitsuba's interior derivative has none), no gradient to the vertices.
+ * Refused with FFX_ERR_ARG before any launch, the parameter named: n < 0, a NULL pointer, a bvh info ffx_trace_rays refuses. */
+int ffx_trace_rays_bwd(const void *bvh /*[dev]*/, const ffx_bvh_info *info /*[host]*/, const float *origins /*[dev][n,3]*/,
+                       const float *dirs /*[dev][n,3]*/, int n, const float *t /*[dev][n]*/, const int32_t *prim /*[dev][n]*/,
+                       const float *gt /*[dev][n]*/, float *gorig /*[dev][n,3]*/, float *gdir /*[dev][n,3]*/, ffx_stream stream);
 
 #ifdef __cplusplus
 }
