@@ -2964,7 +2964,11 @@ __device__ __forceinline__ void sample_adjoint(const RfC &rf, float jx, float jy
 // generic one tests per sample (plain_scene below): principled rows that travel inline with their pre-rows, no optional lobe in any row, no smooth
 // record, a rigid spot, a one-channel projector texture, an f32 box film in one pass.  Same arithmetic, same order, same bits; FFX_K8_PLAIN=0 keeps
 // the generic instance.
-template <int R, bool WIDE, int MATM, bool ADJ = false, bool RF = false, bool RFC = false, bool PLAIN = false>
+// CACHE (behind PLAIN for the same reason; PLAIN only): whether the launch writes the adjoint cache is a fact of the instance too — the launcher knows
+// it when it picks.  The plain forward (!ADJ, !CACHE) holds no footprint fold, no stray-record allocation, no header write and no footprint store
+// (as a run-time `cache != nullptr` that dead arm kept scalars live through the whole kernel: 12 SGPR spills, 4 without it); the cache-writing plain
+// forward (!ADJ, CACHE) is the L1-loss step's render.  The generic instances keep the run-time test.
+template <int R, bool WIDE, int MATM, bool ADJ = false, bool RF = false, bool RFC = false, bool PLAIN = false, bool CACHE = false>
 __global__ void __launch_bounds__(PK_BLOCK) __attribute__((amdgpu_waves_per_eu(MATM ? FFX_PK_MAT_WAVES : FFX_PK1_WAVES, MATM ? FFX_PK_MAT_WAVES : FFX_PK1_WAVES)))
     k_render_fwd_pk(ShadeK c, const BvhNode *__restrict__ nodes, const TriRec *__restrict__ recs, const TriApex *__restrict__ arecs, uint32_t astride,
                     WideScene ws, const float *__restrict__ albedo, const float *__restrict__ tex, int spp, uint32_t seed_key, int tiles_x, int n_tiles, int remap,
@@ -2980,7 +2984,10 @@ __global__ void __launch_bounds__(PK_BLOCK) __attribute__((amdgpu_waves_per_eu(M
   // RF && ADJ (ffx_render_fwd_adjoint_filtered): adj_gimg is then G = gimg / weight as float4 per pixel (k_rf_gather) and every lit sample
   // enters the pixel's footprint with ITS OWN gradient — sum over its window of w_n G[pixel + n], times albedo and colour — already applied;
   // the epilogue scatters the footprint as it is.  1-channel textures only (the host refuses the other).
-  const bool fold = RF ? ADJ : (ADJ || cache != nullptr);
+  // CACHE_ARM: the instance can write the box film's adjoint cache; has_cache: this launch does (PLAIN: a constant of the instance)
+  constexpr bool CACHE_ARM = !ADJ && !RF && (!PLAIN || CACHE), FOLD_CT = RF ? ADJ : (ADJ || CACHE);
+  const bool has_cache = PLAIN ? CACHE : cache != nullptr;
+  const bool fold = (RF || PLAIN) ? FOLD_CT : (ADJ || has_cache);
   constexpr int WSTACK_N = WIDE ? FFX_WSTACK : 1, RF_N = (FFX_RF_FLOATS * 4 + 7) / 8;
   __shared__ __attribute__((aligned(16))) uint2 s_wstack[RF ? (WSTACK_N > RF_N ? WSTACK_N : RF_N) : WSTACK_N]; // (RF: the filter's rows alias the walk's stack and are read in 16-byte units)
   __shared__ float s_foot[32]; // the pixel's 5x5 texture footprint (adjoint cache)
@@ -2988,6 +2995,7 @@ __global__ void __launch_bounds__(PK_BLOCK) __attribute__((amdgpu_waves_per_eu(M
   static_assert(R == 1, "one ray per lane: the adjoint cache is written one pixel at a time");
   static_assert(!RFC || (RF && !ADJ), "RFC: the filtered forward that writes the per-sample adjoint records");
   static_assert(!PLAIN || (MATM == 1 && !RF && !RFC), "PLAIN: principled rows, box film");
+  static_assert(!CACHE || (PLAIN && !ADJ), "CACHE: the plain-scene forward that writes the adjoint cache");
   FFX_TINIT();
   FFX_TSTART(twave);
   FFX_TSTART(tpro);
@@ -3005,7 +3013,9 @@ __global__ void __launch_bounds__(PK_BLOCK) __attribute__((amdgpu_waves_per_eu(M
   const int passes = PLAIN ? 1 : (spp + 63) >> 6;
   // (wave-uniform, used once per pixel: kept in an SGPR — as a VGPR it was live across the whole kernel and spilled)
   const float inv_spp_u = inv_spp_arg; // 1 / spp from the host (a kernel argument is scalar by construction; the division here was ten vector instructions per wave)
-  if (!ADJ && !RF && cache && wv == 0 && lane == 0) reinterpret_cast<CacheHdr *>(cache)->cap_stray = cap_stray; // (read back by K9 and ffx_render_cache_status; no wave of this launch reads it)
+  if constexpr (CACHE_ARM) {
+    if (has_cache && wv == 0 && lane == 0) reinterpret_cast<CacheHdr *>(cache)->cap_stray = cap_stray; // (read back by K9 and ffx_render_cache_status; no wave of this launch reads it)
+  }
   if constexpr (RFC) { // (the arena's counters were cleared in front of this launch — launch_apex / FFX_RENDER_CACHE_ZEROED; nobody here reads the capacity word)
     if (wv == 0 && lane == 0) reinterpret_cast<CacheHdr *>(adj_gtex)->cap_stray = cap_stray;
   }
@@ -3193,25 +3203,27 @@ __global__ void __launch_bounds__(PK_BLOCK) __attribute__((amdgpu_waves_per_eu(M
                 }
               }
             }
-          } else if (!ADJ && straym != 0ull) { // single samples that do not fit the footprint: one allocation per wave
-            CacheHdr *hdr = reinterpret_cast<CacheHdr *>(cache);
-            const uint32_t n = (uint32_t)wpop(straym);
-            uint32_t base = 0;
-            if (lane == 0) base = atomicAdd(&hdr->n_stray, n);
-            base = (uint32_t)__builtin_amdgcn_readfirstlane((int)base);
-            const uint32_t cap = cap_stray; // (a kernel argument: the header may have been cleared as a whole by the caller, FFX_RENDER_CACHE_ZEROED)
-            if (base + n <= cap) {
-              if (lit && !in_win) {
-                CacheStray *rec = reinterpret_cast<CacheStray *>(cache + ((size_t)cache_arena_off << 7)) + base + mbcnt64(straym);
-                rec->pix = pix[0];
-                rec->xy_shape = (uint32_t)(st[0].ubx + 1) | ((uint32_t)(st[0].uby + 1) << 12) | ((uint32_t)st[0].shape << 24);
-                rec->ax = st[0].wx1;
-                rec->ay = st[0].wy1;
-                rec->fac = st[0].proj_fac;
-                if constexpr (MAT) rec->fac_b = st[0].proj_fac_b;
+          } else if constexpr (CACHE_ARM) {
+            if (straym != 0ull) { // single samples that do not fit the footprint: one allocation per wave
+              CacheHdr *hdr = reinterpret_cast<CacheHdr *>(cache);
+              const uint32_t n = (uint32_t)wpop(straym);
+              uint32_t base = 0;
+              if (lane == 0) base = atomicAdd(&hdr->n_stray, n);
+              base = (uint32_t)__builtin_amdgcn_readfirstlane((int)base);
+              const uint32_t cap = cap_stray; // (a kernel argument: the header may have been cleared as a whole by the caller, FFX_RENDER_CACHE_ZEROED)
+              if (base + n <= cap) {
+                if (lit && !in_win) {
+                  CacheStray *rec = reinterpret_cast<CacheStray *>(cache + ((size_t)cache_arena_off << 7)) + base + mbcnt64(straym);
+                  rec->pix = pix[0];
+                  rec->xy_shape = (uint32_t)(st[0].ubx + 1) | ((uint32_t)(st[0].uby + 1) << 12) | ((uint32_t)st[0].shape << 24);
+                  rec->ax = st[0].wx1;
+                  rec->ay = st[0].wy1;
+                  rec->fac = st[0].proj_fac;
+                  if constexpr (MAT) rec->fac_b = st[0].proj_fac_b;
+                }
+              } else if (lane == 0) {
+                atomicAdd(&hdr->dropped, n); // arena exhausted (never seen: it holds 1/64 of all samples, strays are ~0.1 %)
               }
-            } else if (lane == 0) {
-              atomicAdd(&hdr->dropped, n); // arena exhausted (never seen: it holds 1/64 of all samples, strays are ~0.1 %)
             }
           }
         }
@@ -3329,20 +3341,22 @@ __global__ void __launch_bounds__(PK_BLOCK) __attribute__((amdgpu_waves_per_eu(M
         if (dd != 0.f) atomicAdd(adj_dot + (pix[0] & (FFX_ADJOINT_DOT_SLOTS - 1)), dd);
       }
     }
-    if (!ADJ && !RF && cache && live[0]) { // the pixel's slot: header always, the footprint only if something was lit
-      __builtin_amdgcn_wave_barrier();
-      if (lane == 0) {
-        CachePix hp;
-        hp.x0 = (int16_t)fox; hp.y0 = (int16_t)foy;
-        hp.shape = (uint16_t)(fshape < 0 ? 0 : fshape);
-        hp.lit = fox >= 0 ? 1 : 0;
-        reinterpret_cast<CachePix *>(cache + 64)[pix[0]] = hp; // one 8-byte store
-      }
-      int lw = lane;
-      asm volatile("" : "+v"(lw));
-      if (fox >= 0 && lw < 25) reinterpret_cast<CacheFoot *>(cache + ((size_t)cache_foot_off << 7))[pix[0]].w[lw] = s_foot[lw];
-      if constexpr (MAT) {
-        if (fox >= 0 && lw < 25) reinterpret_cast<CacheFoot *>(cache + ((size_t)cache_foot_b_off << 7))[pix[0]].w[lw] = s_foot_b[lw];
+    if constexpr (CACHE_ARM) {
+      if (has_cache && live[0]) { // the pixel's slot: header always, the footprint only if something was lit
+        __builtin_amdgcn_wave_barrier();
+        if (lane == 0) {
+          CachePix hp;
+          hp.x0 = (int16_t)fox; hp.y0 = (int16_t)foy;
+          hp.shape = (uint16_t)(fshape < 0 ? 0 : fshape);
+          hp.lit = fox >= 0 ? 1 : 0;
+          reinterpret_cast<CachePix *>(cache + 64)[pix[0]] = hp; // one 8-byte store
+        }
+        int lw = lane;
+        asm volatile("" : "+v"(lw));
+        if (fox >= 0 && lw < 25) reinterpret_cast<CacheFoot *>(cache + ((size_t)cache_foot_off << 7))[pix[0]].w[lw] = s_foot[lw];
+        if constexpr (MAT) {
+          if (fox >= 0 && lw < 25) reinterpret_cast<CacheFoot *>(cache + ((size_t)cache_foot_b_off << 7))[pix[0]].w[lw] = s_foot_b[lw];
+        }
       }
     }
   }
@@ -5756,7 +5770,8 @@ template <class F> static void dispatch_rf_dir_amb(bool rf, bool dir, bool amb, 
 // What k_render_fwd_pk<..., PLAIN> takes as constants, proved here from what the call carries (anything less: the generic instance).  The rows
 // travel inline and shade_prepare derived a pre-row for each (mat_pre_on), every row is a principled row (model != 0) with no optional lobe (its
 // flag word is 0), the blob's last update flagged no shape smooth (ffx_blob_flat: a blob this process has not updated is not known to be flat), a spot
-// is rigid, a projector texture has one channel, the film is f32 and takes one pass.  Box film, no adjoint cache: the route's own conditions.
+// is rigid, a projector texture has one channel, the film is f32 and takes one pass.  Box film: the route's own condition; with or without an adjoint cache
+// (whose buffer keeps its 64-bit addressing: it is not among the areas proved below 2^32 bytes).
 // The camera is in band (ffx_band.h: w_uniform, qz one-signed over the film, |np|^2 and |dl.z| within [2^-40, 2^40], bounded in double from the
 // film's corners with the float roundings covered) — cam_ray<BAND> then takes its root and its two reciprocals as seed + fma chain, without the
 // IEEE expansions' scaling, fix-up and class steps, which do nothing there.  The blob (tile bins with their envelopes, gn, apex records) and the
@@ -5779,7 +5794,7 @@ static bool plain_scene(const RenderSetup &r, const ffx_scene_desc *sd, const vo
 // k8_launch_counters reads it in place — how mi.Scene.render_paths and the tests see which instance ran)
 extern "C" { unsigned long long ffx_k8_instance_launches[2] = {0ull, 0ull}; }
 // a k_render_fwd_pk launch's own arguments (the kernel's parameters: fp16, img, cache, cache_foot_off / cache_arena_off / cache_foot_b_off, ...);
-// plain: the scene passed plain_scene (the box film's route without an adjoint cache only)
+// plain: the scene passed plain_scene (the box film's route only: its forward, its forward + adjoint and its cache-writing forward)
 struct FwdPkArgs { int fp16; void *img; char *cache; uint32_t off[3], cap_stray; const float *adj_gimg; float *adj_gtex, *adj_dot; bool plain = false; };
 // ADJ: k_render_fwd_pk's ADJ (0 / 1), or 2 for the box film's route, which takes the fused adjoint iff a.adj_gtex
 template <int ADJ, bool RF = false, bool RFC = false>
@@ -5788,18 +5803,24 @@ static void launch_fwd_pk(bool wide, const RenderSetup &r, const Packets &p, con
     auto launch = [&](auto adj) {
       constexpr bool WIDE = decltype(w)::value, A = decltype(adj)::value;
       constexpr int MATM = decltype(m)::value;
-      auto go = [&](auto plain) {
-        constexpr bool PLAIN = decltype(plain)::value;
+      auto go = [&](auto plain, auto with_cache) {
+        constexpr bool PLAIN = decltype(plain)::value, CACHE = decltype(with_cache)::value;
         __atomic_fetch_add(&ffx_k8_instance_launches[PLAIN ? 0 : 1], 1ull, __ATOMIC_RELAXED);
-        hipLaunchKernelGGL((k_render_fwd_pk<1, WIDE, MATM, A, RF, RFC, PLAIN>), dim3(p.pgrid), dim3(64), 0, s, r.c, r.b.nodes, r.b.recs, p.arecs, p.astride, p.ws,
+        hipLaunchKernelGGL((k_render_fwd_pk<1, WIDE, MATM, A, RF, RFC, PLAIN, CACHE>), dim3(p.pgrid), dim3(64), 0, s, r.c, r.b.nodes, r.b.recs, p.arecs, p.astride, p.ws,
                            r.c.mats, tex, r.spp, r.seed_key, p.ptx, p.pn, xcd_mode(r.n_pix), a.fp16, a.img, a.cache, p.ppw, 1.0f / (float)r.spp, a.off[0],
                            a.off[1], a.off[2], r.b.nrec, r.b.gn, a.cap_stray, a.adj_gimg, a.adj_gtex, a.adj_dot);
       };
       if constexpr ((WIDE || !RF) && (MATM < 2 || (!A && !RFC))) {
-        if constexpr (ADJ == 2 && MATM == 1) { // (the box film's route: the only one with a plain-scene instance)
-          if (a.plain) { go(std::true_type()); return; }
+        if constexpr (ADJ == 2 && MATM == 1) { // (the box film's route: the only one with plain-scene instances — forward, forward + adjoint, cache-writing forward)
+          if (a.plain) {
+            if constexpr (!A) {
+              if (a.cache) { go(std::true_type(), std::true_type()); return; }
+            }
+            go(std::true_type(), std::false_type());
+            return;
+          }
         }
-        go(std::false_type());
+        go(std::false_type(), std::false_type());
       }
     };
     if constexpr (ADJ != 2) launch(std::bool_constant<ADJ == 1>());
@@ -5990,7 +6011,7 @@ static int render_fwd_impl(const void *bvh, const ffx_bvh_info *info, const ffx_
       FFX_CHECK_LAUNCH("render_fwd (pixel blocks)");
       return FFX_OK;
     }
-    launch_fwd_pk<2>(use_wide(info), r, p, tex, {img_fp16, img, (char *)cache, {foot_off, arena_off, foot_b_off}, cap_stray, adj_gimg, adj_gtex, adj_dot, !cache && plain_scene(r, sd, bvh, info, img_fp16)}, st);
+    launch_fwd_pk<2>(use_wide(info), r, p, tex, {img_fp16, img, (char *)cache, {foot_off, arena_off, foot_b_off}, cap_stray, adj_gimg, adj_gtex, adj_dot, plain_scene(r, sd, bvh, info, img_fp16)}, st);
     FFX_CHECK_LAUNCH("render_fwd");
     return FFX_OK;
   }

@@ -37,7 +37,7 @@
  *       FFX_RENDER_BLOCKS=0      ffx_render_fwd / ffx_render_fwd_filtered below 33 samples per pixel: a pixel per wave whatever the count, as
  *                                at 64 (default: compact blocks of up to 8 pixels per wave, 16 at 1 spp, k_render_fwd_blk — the same image
  *                                bit for bit, 1.5 - 2.3x faster); the FFX_RENDER_AOV launches of such a call follow it
- *       FFX_K8_PLAIN=0           ffx_render_fwd / ffx_render_fwd_adjoint at 33 .. 64 samples per pixel: the generic packet kernel for every scene
+ *       FFX_K8_PLAIN=0           ffx_render_fwd / ffx_render_fwd_adjoint at 33 .. 64 samples per pixel, ffx_render_fwd_cache up to 64: the generic packet kernel for every scene
  *                                (default: an instance without the per-sample feature tests for scenes the host proves plain — inline principled
  *                                rows without optional lobes, no smooth shape, rigid spot, 1-channel texture, f32 box film; the same bits)
  *       FFX_BINS=0               the packet render kernels walk the tree for every packet (default: tile bins first, ffx_bvh_info.off_bins)
