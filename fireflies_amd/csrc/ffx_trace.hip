@@ -22,9 +22,11 @@
 #include <string.h>
 
 #include <limits.h>
+#include <mutex>
 
 #include "ffx_common.h"
 #include "ffx_band.h"
+#include "ffx_rect.h"
 #include "../../include/ffx_labels.h" // ffx_trace_rays_bwd
 
 #define TR_BLOCK 256
@@ -102,6 +104,12 @@ __device__ __forceinline__ const T &kernarg_first() {
   return *(const T *)p;
 }
 __device__ __forceinline__ const ShadeK &kernarg_shade() { return kernarg_first<ShadeK>(); }
+// What the plain-scene instances of k_render_fwd_pk read instead of forming it per pixel or per walk (rect_tables): the film's pixel-rectangle
+// tables (ffx_rect.h: W column entries, then H row entries from entry `row0`) with their two half extents, and the grids' sizes as the floats
+// bins_shadow compares against.  It is k_render_fwd_pk's LAST argument — behind every other one, so no existing kernarg offset moves and no other
+// kernel's code does — and is read in place like the first (kernarg_rect, defined behind the kernel).
+struct RectK { const void *tab; float hx, hy; uint32_t row0, pad; float gxf[FFX_N_APEX], gyf[FFX_N_APEX]; };
+__device__ __forceinline__ const RectK &kernarg_rect();
 // the material table of a launch: its own kernel arguments, or the caller's device array
 __device__ __forceinline__ const float *mat_table(const ShadeK &k) { return k.mat_inline ? k.mat_h : k.mats; }
 
@@ -277,6 +285,31 @@ __device__ __forceinline__ void sample_jitter(uint32_t seed_key, uint32_t idx, f
 #define FFX_K8_OFF32 false
 #else
 #define FFX_K8_OFF32 true
+#endif
+// ... and a third: -DFFX_K8_NO_RECTTAB keeps the per-pixel arithmetic of the bin rectangle (and the uniform work next to it) that the plain-scene
+// instances otherwise take from the film's tables (ffx_rect.h, rect_tables below).
+#ifdef FFX_K8_NO_RECTTAB
+#define FFX_K8_RECTTAB false
+#else
+#define FFX_K8_RECTTAB true
+#endif
+// (its parts beside the tables, for single-item A/B libraries as well: -DFFX_K8_NO_RECT_UNI keeps the tile origin per pixel and the vector form of the
+// `live` test, -DFFX_K8_NO_RECT_GF the conversion of the grids' sizes per shadow walk, -DFFX_K8_NO_RECT_SL the vector loads of the bins' header words
+// and list bounds)
+#ifdef FFX_K8_NO_RECT_UNI
+#define FFX_K8_RECT_UNI false
+#else
+#define FFX_K8_RECT_UNI true
+#endif
+#ifdef FFX_K8_NO_RECT_GF
+#define FFX_K8_RECT_GF false
+#else
+#define FFX_K8_RECT_GF true
+#endif
+#ifdef FFX_K8_NO_RECT_SL
+#define FFX_K8_RECT_SL false
+#else
+#define FFX_K8_RECT_SL true
 #endif
 // (rcp_band, sqrt_band: ffx_band.h — the IEEE expansions of 1.0f / d and sqrtf(x) without the steps that do nothing inside the camera's band)
 // BAND (k_render_fwd_pk's plain-scene instance only): the launch proved w_uniform and the band of |np|^2, |np| and dl.z
@@ -2015,10 +2048,16 @@ __device__ __forceinline__ void traverse_packet_any(const BvhNode *__restrict__ 
 // with the primitive-id tie-break: the result does not depend on the order, and is the tree walk's bit for bit).
 // No stack, no descent, no packet constants: where the 64-wide walk took 4.2 dependent steps and 100 VALU of set-up per pixel
 // this is ~1.3 steps.  tx0..ty1: the tiles the rectangle touches (at most four: the caller falls back to the tree otherwise).
-template <bool ANY, bool OFF32 = false>
+// BOX (bins_primary<..., RECT>): the caller hands the box bounds over — bx0..by1, the values rcx -+ rhx, rcy -+ rhy it read from the film's tables,
+// already scalar — instead of having them formed and made uniform here.
+// SL (the table-fed plain instances): a tile's two list bounds are read through the constant address space — the bins are the pre-pass's, no wave of
+// a render writes them — so that their uniform address makes them scalar loads, not two vector loads and a wait for the vector memory counter.
+#define FFX_CONST_AS __attribute__((address_space(4)))
+template <bool ANY, bool OFF32 = false, bool BOX = false, bool SL = false>
 __device__ __forceinline__ void traverse_bins(const char *__restrict__ bbase, const int nx, const int tx0, const int ty0, const int tx1, const int ty1, const float rcx,
                                               const float rcy, const float rhx, const float rhy, const TriApex *__restrict__ recs, const v3 d, const float tmin,
-                                              const float tmax, const wmask active, Hit &h, wmask &occluded) {
+                                              const float tmax, const wmask active, Hit &h, wmask &occluded, const float bx0 = 0.f, const float bx1 = 0.f,
+                                              const float by0 = 0.f, const float by1 = 0.f) {
   h.t = msel(active, tmax, -INFINITY);
   h.prim = -1;
   h.shape = -1;
@@ -2031,14 +2070,20 @@ __device__ __forceinline__ void traverse_bins(const char *__restrict__ bbase, co
   // the rectangle's bounds for the box test — wave-uniform like centre and half extents: kept in SGPRs (they feed the step as scalar
   // operands; as VGPRs they would be eight more registers live across the exact tests)
   auto uni = [](float v) { return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v))); };
-  const float rx0 = uni(rcx - rhx), rx1 = uni(rcx + rhx), ry0 = uni(rcy - rhy), ry1 = uni(rcy + rhy);
+  const float rx0 = BOX ? bx0 : uni(rcx - rhx), rx1 = BOX ? bx1 : uni(rcx + rhx), ry0 = BOX ? by0 : uni(rcy - rhy), ry1 = BOX ? by1 : uni(rcy + rhy);
   FFX_STAT(ANY ? 40 : 32);
   const float tmax_up = tmax * 1.0000038f; // tmax (1 + 2^-18)
   bool go = true;
   for (int ty = ty0; ty <= ty1 && go; ++ty) {
     for (int tx = tx0; tx <= tx1 && go; ++tx) {
       const uint32_t tile = (uint32_t)(ty * nx + tx);
-      const uint32_t beg = starts[tile], end = starts[tile + 1]; // (uniform address: scalar loads)
+      uint32_t beg, end;
+      if constexpr (SL) {
+        const FFX_CONST_AS uint32_t *sc = (const FFX_CONST_AS uint32_t *)(uintptr_t)starts;
+        beg = sc[tile]; end = sc[tile + 1];
+      } else {
+        beg = starts[tile]; end = starts[tile + 1]; // (uniform address: scalar loads)
+      }
       for (uint32_t b0 = beg; b0 < end && go; b0 += 64u) {
         FFX_STAT(ANY ? 41 : 33);
         const uint32_t idx = b0 + lane;
@@ -2106,19 +2151,39 @@ __device__ __forceinline__ void traverse_bins(const char *__restrict__ bbase, co
 }
 
 // the bins of apex `a` are usable for this launch and this pose?  (grid enabled by the host; lists complete: written by k_bin_scan)
+// (SL: the header word through the constant address space, as traverse_bins<..., SL> reads the list bounds)
+template <bool SL = false>
 __device__ __forceinline__ bool bins_ready(const BinsK &bk, const int a) {
   if (!bk.g[a].on) return false;
-  return reinterpret_cast<const BinHdr *>(bk.base[a])->ok != 0u; // (uniform address: a scalar load)
+  if constexpr (SL) return ((const FFX_CONST_AS BinHdr *)(uintptr_t)bk.base[a])->ok != 0u;
+  else return reinterpret_cast<const BinHdr *>(bk.base[a])->ok != 0u; // (uniform address: a scalar load)
 }
 
 // primary rays of pixel (px, py): its own tile, its own square of the image plane.  The square is taken a half pad short at the far
 // side: a sample position of exactly px + 1 (rounding of px + jitter) still lies within the entries' padding, and the pixels of a
 // tile's last column do not drag the next tile's list in.
-template <bool OFF32 = false>
+// RECT (the plain-scene instances; the launch made the film's tables, rect_tables): centre, box bounds and tile of the pixel's column and row are
+// two 16-byte scalar loads from the tables (ffx_rect.h: the values the arithmetic below gives, bit for bit — they depend on the column or row, the
+// film and the tile side alone), the half extents two kernel arguments; nothing is formed on the vector ALU and carried back.
+typedef float v4f __attribute__((ext_vector_type(4)));
+template <bool OFF32 = false, bool RECT = false, bool SL = false>
 __device__ __forceinline__ bool bins_primary(const BinsK &bk, const int px, const int py, const TriApex *__restrict__ recs, const v3 d, const float tmin, const float tmax,
                                              const wmask active, Hit &h) {
-  if (!bins_ready(bk, 0)) return false;
+  if (!bins_ready<SL>(bk, 0)) return false;
   if (active == 0ull) { h.t = -INFINITY; h.prim = -1; h.shape = -1; h.slot = -1; return true; } // nothing to trace
+  if constexpr (RECT) {
+    // (px < W, py < H: the kernel walks live pixels only.  Constant address space: written once, by the host, before the launch — a uniform index
+    // is then a scalar load whatever the kernel itself stores elsewhere)
+    typedef const __attribute__((address_space(4))) v4f *ctab;
+    const RectK &rk = kernarg_rect();
+    const ctab tab = (ctab)(uintptr_t)rk.tab;
+    const v4f ex = tab[(uint32_t)px], ey = tab[rk.row0 + (uint32_t)py];
+    const int stx = __float_as_int(ex.w), sty = __float_as_int(ey.w);
+    if (stx >= bk.g[0].nx || sty >= bk.g[0].ny) return false;
+    wmask occ;
+    traverse_bins<false, OFF32, true, SL>(bk.base[0], bk.g[0].nx, stx, sty, stx, sty, ex.x, ey.x, rk.hx, rk.hy, recs, d, tmin, tmax, active, h, occ, ex.y, ex.z, ey.y, ey.z);
+    return true;
+  }
   const float its_x = bk.cam_inv_ts_x, its_y = bk.cam_inv_ts_y; // 1 / tile side: a power of two
   const float x0 = (float)px * its_x, y0 = (float)py * its_y;
   const int tx = (int)x0, ty = (int)y0;
@@ -2130,7 +2195,7 @@ __device__ __forceinline__ bool bins_primary(const BinsK &bk, const int px, cons
   const float shx = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(hx))), shy = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(hy)));
   if (stx >= bk.g[0].nx || sty >= bk.g[0].ny) return false;
   wmask occ;
-  traverse_bins<false, OFF32>(bk.base[0], bk.g[0].nx, stx, sty, stx, sty, scx, scy, shx, shy, recs, d, tmin, tmax, active, h, occ);
+  traverse_bins<false, OFF32, false, SL>(bk.base[0], bk.g[0].nx, stx, sty, stx, sty, scx, scy, shx, shy, recs, d, tmin, tmax, active, h, occ);
   return true;
 }
 
@@ -2177,14 +2242,17 @@ __device__ __forceinline__ void wave_reduce_minmax4(uint32_t &mn0, uint32_t &mn1
 // points on the emitter's grid are (M sdir).xy / (M sdir).z; the packet's rectangle is their bounding box (the samples of one pixel:
 // a pixel's footprint as the emitter sees it).  A packet that leaves the grid or spreads over more than four tiles (the two sides of
 // a depth discontinuity, far apart as seen from the emitter) takes the tree walk.
-template <bool OFF32 = false>
+// GF (the table-fed plain instances): the grid's size as the floats the host converted once (RectK.gxf / gyf, read through kernarg_rect), not a conversion per call
+template <bool OFF32 = false, bool GF = false, bool SL = false>
 __device__ __forceinline__ bool bins_shadow(const BinsK &bk, const int a, const TriApex *__restrict__ recs, const v3 sdir, const wmask active, wmask &occluded) {
-  if (!bins_ready(bk, a)) return false;
+  if (!bins_ready<SL>(bk, a)) return false;
   const float *M = bk.g[a].M;
   const float Z = fmaf(M[6], sdir.x, fmaf(M[7], sdir.y, M[8] * sdir.z));
   const float iz = __builtin_amdgcn_rcpf(Z);
   const float fx = fmaf(M[0], sdir.x, fmaf(M[1], sdir.y, M[2] * sdir.z)) * iz, fy = fmaf(M[3], sdir.x, fmaf(M[4], sdir.y, M[5] * sdir.z)) * iz;
-  const float gx = (float)bk.g[a].nx, gy = (float)bk.g[a].ny;
+  float gx, gy;
+  if constexpr (GF) { gx = kernarg_rect().gxf[a]; gy = kernarg_rect().gyf[a]; }
+  else { gx = (float)bk.g[a].nx; gy = (float)bk.g[a].ny; }
   // inside the grid (NaN fails): everything else is the tree's business.  0 <= f < g as ONE unsigned comparison of the floats' bits: non-negative floats
   // order like their bits, negative ones (and NaN) have larger bits than any grid size (-0.0 counts as outside: the tree gives the same answer)
   const wmask inside = m_gt(Z, 0.f) & m_ult(__float_as_uint(fx), __float_as_uint(gx)) & m_ult(__float_as_uint(fy), __float_as_uint(gy));
@@ -2193,7 +2261,11 @@ __device__ __forceinline__ bool bins_shadow(const BinsK &bk, const int a, const 
   // front of every triangle the tile lists over that cell, pulled forward past the ignored tail of a shadow ray.  N . sdir <= 1: the segment
   // ends in front of it, no listed triangle can be hit within the counted part — and only listed triangles can be hit at all.  A packet all of
   // whose samples pass skips the stage (most do: the emitter stands next to the camera); NaN cells (no proof offered) fail the comparison.
-  if (((bk.env_on >> (a - 1)) & 1) && reinterpret_cast<const BinHdr *>(bk.base[a])->env != 0u) { // (the header: THIS pose's pre-pass built it)
+  auto env_built = [&]() { // (SL: the header word as a scalar load, as bins_ready<SL> reads its neighbour)
+    if constexpr (SL) return ((const FFX_CONST_AS BinHdr *)(uintptr_t)bk.base[a])->env != 0u;
+    else return reinterpret_cast<const BinHdr *>(bk.base[a])->env != 0u;
+  };
+  if (((bk.env_on >> (a - 1)) & 1) && env_built()) { // (the header: THIS pose's pre-pass built it)
     const int nxf = bk.g[a].nx * FFX_ENV_SUB;
     const uint32_t last = (uint32_t)(nxf * bk.g[a].ny * FFX_ENV_SUB) - 1u;
     const uint32_t ci = (uint32_t)((int)(fy * (float)FFX_ENV_SUB) * nxf + (int)(fx * (float)FFX_ENV_SUB));
@@ -2213,7 +2285,7 @@ __device__ __forceinline__ bool bins_shadow(const BinsK &bk, const int a, const 
   const float scx = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(cx))), scy = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(cy)));
   const float shx = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(hx))), shy = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(hy)));
   Hit hs;
-  traverse_bins<true, OFF32>(bk.base[a], bk.g[a].nx, stx0, sty0, stx1, sty1, scx, scy, shx, shy, recs, sdir, 0.f, 1.0f - SHADOW_EPS, active, hs, occluded);
+  traverse_bins<true, OFF32, false, SL>(bk.base[a], bk.g[a].nx, stx0, sty0, stx1, sty1, scx, scy, shx, shy, recs, sdir, 0.f, 1.0f - SHADOW_EPS, active, hs, occluded);
   return true;
 }
 
@@ -2258,7 +2330,9 @@ __device__ __forceinline__ bool tex_footprint_lit(const float *__restrict__ tex,
 // PLAIN (k_render_fwd_pk<..., PLAIN>, MATM == 1): what the host proved about the scene before the launch (plain_scene) is a constant here — no record is
 // flagged smooth, the spot's frame is rigid, the projector's texture has one channel, every row is a principled row with a pre-row and no optional
 // lobe.  The tests and their arms are not compiled; the arithmetic that remains is the generic instance's, operation for operation.
-template <bool WIDE, int MATM = 0, bool PLAIN = false>
+// RECT (the plain forward and the plain forward + adjoint): the film's rectangle tables are at hand (rect_tables); the cache-writing plain forward keeps
+// the per-pixel arithmetic and the parent's machine code (not measured with the tables; left for a change of its own).
+template <bool WIDE, int MATM = 0, bool PLAIN = false, bool RECT = false>
 __device__ __forceinline__ void shade_sample_pk(const BvhNode *__restrict__ nodes, const TriRec *__restrict__ recs, const TriApex *__restrict__ arecs,
                                                 uint32_t astride, const WideScene &ws, uint2 *__restrict__ stack, const bool &active_, const v3 &o_,
                                                 const v3 &d_, const float &nt_, const float &ft_, SampleTerms &st_,
@@ -2276,7 +2350,7 @@ __device__ __forceinline__ void shade_sample_pk(const BvhNode *__restrict__ node
   bool binned = false;
   // (blk_w x blk_h > 1: the packet's primary rays belong to a compact block of pixels whose first is (px, py) — k_render_fwd_blk, renders at
   // fewer than 64 samples per pixel; the default arguments are constants of every other caller)
-  if (blk_w * blk_h == 1) binned = bins_primary<PLAIN && FFX_K8_OFF32>(kernarg_shade().bins, px, py, arecs, d[0], nt[0], ft[0], wballot(active[0]), h[0]);
+  if (blk_w * blk_h == 1) binned = bins_primary<PLAIN && FFX_K8_OFF32, RECT, RECT && FFX_K8_RECT_SL>(kernarg_shade().bins, px, py, arecs, d[0], nt[0], ft[0], wballot(active[0]), h[0]);
   else binned = bins_block(kernarg_shade().bins, px, py, blk_w, blk_h, arecs, d[0], nt[0], ft[0], wballot(active[0]), h[0]);
   if (!binned) {
     FFX_STAT(36);
@@ -2452,7 +2526,7 @@ __device__ __forceinline__ void shade_sample_pk(const BvhNode *__restrict__ node
     const TriApex *arecs_p = reinterpret_cast<const TriApex *>(reinterpret_cast<const char *>(arecs) + astride);
     bool binned_p = false;
     wmask occm;
-    binned_p = bins_shadow<PLAIN && FFX_K8_OFF32>(kernarg_shade().bins, 1, arecs_p, sdir[0], wballot(act[0]), occm);
+    binned_p = bins_shadow<PLAIN && FFX_K8_OFF32, RECT && FFX_K8_RECT_GF, RECT && FFX_K8_RECT_SL>(kernarg_shade().bins, 1, arecs_p, sdir[0], wballot(act[0]), occm);
     if (binned_p) occ_p[0] = __builtin_amdgcn_inverse_ballot_w64(occm);
     if (!binned_p) {
       FFX_STAT(44);
@@ -2483,7 +2557,7 @@ __device__ __forceinline__ void shade_sample_pk(const BvhNode *__restrict__ node
     const TriApex *arecs_s = reinterpret_cast<const TriApex *>(reinterpret_cast<const char *>(arecs) + 2u * astride);
     bool binned_s = false;
     wmask occm;
-    binned_s = bins_shadow<PLAIN && FFX_K8_OFF32>(kernarg_shade().bins, 2, arecs_s, sdir[0], wballot(act[0]), occm);
+    binned_s = bins_shadow<PLAIN && FFX_K8_OFF32, RECT && FFX_K8_RECT_GF, RECT && FFX_K8_RECT_SL>(kernarg_shade().bins, 2, arecs_s, sdir[0], wballot(act[0]), occm);
     if (binned_s) occ_s[0] = __builtin_amdgcn_inverse_ballot_w64(occm);
     if (!binned_s) {
       FFX_STAT(45);
@@ -2968,13 +3042,14 @@ __device__ __forceinline__ void sample_adjoint(const RfC &rf, float jx, float jy
 // it when it picks.  The plain forward (!ADJ, !CACHE) holds no footprint fold, no stray-record allocation, no header write and no footprint store
 // (as a run-time `cache != nullptr` that dead arm kept scalars live through the whole kernel: 12 SGPR spills, 4 without it); the cache-writing plain
 // forward (!ADJ, CACHE) is the L1-loss step's render.  The generic instances keep the run-time test.
+// (rk, the last parameter: read in place through kernarg_rect, which is defined behind the kernel from the kernel's own parameter types)
 template <int R, bool WIDE, int MATM, bool ADJ = false, bool RF = false, bool RFC = false, bool PLAIN = false, bool CACHE = false>
 __global__ void __launch_bounds__(PK_BLOCK) __attribute__((amdgpu_waves_per_eu(MATM ? FFX_PK_MAT_WAVES : FFX_PK1_WAVES, MATM ? FFX_PK_MAT_WAVES : FFX_PK1_WAVES)))
     k_render_fwd_pk(ShadeK c, const BvhNode *__restrict__ nodes, const TriRec *__restrict__ recs, const TriApex *__restrict__ arecs, uint32_t astride,
                     WideScene ws, const float *__restrict__ albedo, const float *__restrict__ tex, int spp, uint32_t seed_key, int tiles_x, int n_tiles, int remap,
                     int fp16, void *__restrict__ img, char *__restrict__ cache, int ppw, float inv_spp_arg, uint32_t cache_foot_off, uint32_t cache_arena_off,
                     uint32_t cache_foot_b_off, const float4 *__restrict__ nrec, const float4 *__restrict__ gn, uint32_t cap_stray,
-                    const float *__restrict__ adj_gimg, float *__restrict__ adj_gtex, float *__restrict__ adj_dot) {
+                    const float *__restrict__ adj_gimg, float *__restrict__ adj_gtex, float *__restrict__ adj_dot, RectK rk) {
   constexpr bool MAT = MATM != 0, TEX = MATM == 2;
   constexpr int MS = MAT ? FFX_MAT_STRIDE : 3; // floats per material row
   // adj_gtex (ffx_render_fwd_adjoint): the adjoint of a loss whose gradient gimg does not depend on the image (a loss linear in it) needs
@@ -3020,9 +3095,15 @@ __global__ void __launch_bounds__(PK_BLOCK) __attribute__((amdgpu_waves_per_eu(M
     if (wv == 0 && lane == 0) reinterpret_cast<CacheHdr *>(adj_gtex)->cap_stray = cap_stray;
   }
   FFX_TSTOP(tpro, 25);
+  // UNI (the plain-scene instances, next to their rectangle tables): the tile's origin — a division through a float reciprocal and its way back into
+  // scalar registers — is found once per wave instead of once per pixel, and the wave-uniform `live` is branched on as the scalar it is
+  constexpr bool RECT_I = PLAIN && !CACHE && FFX_K8_RECTTAB, UNI = RECT_I && FFX_K8_RECT_UNI; // (RECT_I: the instance reads the film's tables)
+  int bx0[R], by0[R];
+  if constexpr (UNI) packet_pixels<R>(tile, tiles_x, 0, bx0, by0); // (sub 0: the tile's first pixel)
   for (int sub = sub0; sub < sub0 + ppw; ++sub) {
     int px[R], py[R];
-    packet_pixels<R>(tile, tiles_x, sub, px, py);
+    if constexpr (UNI) { px[0] = bx0[0] + (sub & 1); py[0] = by0[0] + (sub >> 1); }
+    else packet_pixels<R>(tile, tiles_x, sub, px, py);
     bool live[R], any_live = false;
     uint32_t pix[R];
 #pragma unroll
@@ -3031,7 +3112,11 @@ __global__ void __launch_bounds__(PK_BLOCK) __attribute__((amdgpu_waves_per_eu(M
       any_live |= live[r];
       pix[r] = (uint32_t)py[r] * (uint32_t)W + (uint32_t)px[r];
     }
-    if (wballot(any_live) == 0ull) continue;
+    if constexpr (UNI) {
+      if (!any_live) continue;
+    } else {
+      if (wballot(any_live) == 0ull) continue;
+    }
     // adjoint cache: window origin (wave-uniform) and shape of this pixel's footprint, -1 until a sample is lit
     int fox = -1, foy = -1, fshape = -1;
     float fin0 = 0.f, fin1 = 0.f, fin2 = 0.f; // the pixel's value as stored (ffx_render_fwd_adjoint: <gimg, img>)
@@ -3059,7 +3144,7 @@ __global__ void __launch_bounds__(PK_BLOCK) __attribute__((amdgpu_waves_per_eu(M
       SampleTerms st[R];
       // (fp16 carries the call's flags: bit 0 fp16 film, bit 1 FFX_RENDER_SPARSE_ADJOINT — then the cache-writing forward may
       // skip dark footprints too: the caller only wants gradients of texels whose value is not zero)
-      shade_sample_pk<WIDE, MATM, PLAIN>(nodes, recs, arecs, astride, ws, s_wstack, active[0], o[0], d[0], nt[0], ft[0], st[0], nrec, gn, px[0], py[0], ((fold || RFC) && !(fp16 & 2)) ? nullptr : tex);
+      shade_sample_pk<WIDE, MATM, PLAIN, RECT_I>(nodes, recs, arecs, astride, ws, s_wstack, active[0], o[0], d[0], nt[0], ft[0], st[0], nrec, gn, px[0], py[0], ((fold || RFC) && !(fp16 & 2)) ? nullptr : tex);
       FFX_TSTOP(tk, 17);
       if constexpr (RFC) {
         // ---- the filtered film's adjoint cache: this pass's 64 records, if any of its samples is lit (one 1 KB store per wave)
@@ -5790,12 +5875,85 @@ static bool plain_scene(const RenderSetup &r, const ffx_scene_desc *sd, const vo
   }
   return ffx_blob_flat(bvh) == 1;
 }
+// ---- the table-fed plain instances' pixel-rectangle tables (ffx_rect.h; read by bins_primary<..., RECT>).  A table depends on the film's size and the
+// camera grid's tile side alone — not on the pose, the seed, the texture or the materials —, so the library keeps it on the device per (device, W, H,
+// its_x, its_y): built and uploaded at a key's first launch, found again by every later one (a run renders one film; another film or another
+// FFX_BIN_TILE is another key).  A table, once made, is NEVER freed or moved: a launch that is queued, in flight or recorded for replay keeps a valid
+// pointer whatever other threads or later calls do, and the mutex needs to cover the lookup only.  FFX_RECT_KEYS keys (at most FFX_RECT_KEYS x 128 KB,
+// which stay with the process's device context: the library's unload makes no HIP call, which at process exit would come after the runtime's own
+// teardown); a process that has used them all renders further films through the generic instance
+// and says so once on stderr (the issue asked for a handful of keys freed at unload: DESIGN 5.1, round 11, gives the reasons for this form).  The upload is a copy on the render's own stream
+// followed by a wait for that stream: ordered before the launch that follows, complete before any later launch on any stream, and the host vector
+// outlives it.  Constraint: a key's FIRST launch allocates and waits, so it must not be made while its stream is being captured (render the film once
+// before capturing; later launches of the key make no HIP call here).
+// -> false: no table for this launch (a film beyond FFX_RECT_MAX_SIDE, every key in use, no device memory) — the launch takes the generic instance.
+static_assert(FFX_RECT_BIN_PAD == FFX_BIN_PAD, "ffx_rect.h restates the bins' pad");
+#define FFX_RECT_KEYS 32
+struct RectTab { int dev, W, H; float its_x, its_y, hx, hy; void *d; };
+static RectTab g_rect_tab[FFX_RECT_KEYS];
+static std::mutex g_rect_mu;
+static bool rect_tables(const ShadeK &c, RectK &rk, hipStream_t s) {
+  const BinsK &bk = c.bins;
+  memset(&rk, 0, sizeof rk);
+  for (int a = 0; a < FFX_N_APEX; ++a) { rk.gxf[a] = (float)bk.g[a].nx; rk.gyf[a] = (float)bk.g[a].ny; } // (bins_shadow<..., GF>: the conversion it made per call)
+  if (!bk.g[0].on) return true; // (no camera grid: bins_primary leaves before it looks at a table)
+  const int W = c.cam.W, H = c.cam.H;
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess) return false;
+  std::lock_guard<std::mutex> lock(g_rect_mu);
+  RectTab *e = nullptr, *free_slot = nullptr;
+  for (RectTab &t : g_rect_tab) {
+    if (t.d && t.dev == dev && t.W == W && t.H == H && t.its_x == bk.cam_inv_ts_x && t.its_y == bk.cam_inv_ts_y) { e = &t; break; }
+    if (!t.d && !free_slot) free_slot = &t;
+  }
+  if (!e) {
+    if (!free_slot) { // every key in use: said once, since from here on this process renders new films through the generic instance
+      static bool told = false;
+      if (!told) fprintf(stderr, "libffx_hip: all %d pixel-rectangle tables are in use; further film sizes render through the generic K8 instance\n", FFX_RECT_KEYS);
+      told = true;
+      return false;
+    }
+    std::vector<FfxRectEntry> tab;
+    float hx, hy;
+    if (!ffx_rect_fill(W, H, bk.cam_inv_ts_x, bk.cam_inv_ts_y, tab, hx, hy)) return false;
+    void *d = nullptr;
+    if (hipMalloc(&d, tab.size() * sizeof(FfxRectEntry)) != hipSuccess) { (void)hipGetLastError(); return false; }
+    if (hipMemcpyAsync(d, tab.data(), tab.size() * sizeof(FfxRectEntry), hipMemcpyHostToDevice, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) {
+      (void)hipGetLastError();
+      (void)hipFree(d); // (never handed out)
+      return false;
+    }
+    *free_slot = {dev, W, H, bk.cam_inv_ts_x, bk.cam_inv_ts_y, hx, hy, d};
+    e = free_slot;
+  }
+  rk.tab = e->d;
+  rk.hx = e->hx;
+  rk.hy = e->hy;
+  rk.row0 = (uint32_t)W;
+  return true;
+}
 // launches of k_render_fwd_pk by instance: [0] plain-scene, [1] generic (a data symbol, not an entry point: fireflies_amd/ops.py
 // k8_launch_counters reads it in place — how mi.Scene.render_paths and the tests see which instance ran)
 extern "C" { unsigned long long ffx_k8_instance_launches[2] = {0ull, 0ull}; }
 // a k_render_fwd_pk launch's own arguments (the kernel's parameters: fp16, img, cache, cache_foot_off / cache_arena_off / cache_foot_b_off, ...);
 // plain: the scene passed plain_scene (the box film's route only: its forward, its forward + adjoint and its cache-writing forward)
-struct FwdPkArgs { int fp16; void *img; char *cache; uint32_t off[3], cap_stray; const float *adj_gimg; float *adj_gtex, *adj_dot; bool plain = false; };
+// kernarg_rect: k_render_fwd_pk's last argument, read in place.  The kernarg segment lays the arguments out in order, each at its own alignment, so
+// the last one's offset follows from the kernel's parameter types — taken from the kernel's own type here, nothing restates the list (the code
+// object's metadata says the same: .offset of the last .args entry, 1856).
+template <class F> struct KernargLast;
+template <class... A> struct KernargLast<void (*)(A...)> {
+  static constexpr size_t offset() {
+    size_t off = 0, last = 0;
+    ((off = (off + alignof(A) - 1) / alignof(A) * alignof(A), last = off, off += sizeof(A)), ...);
+    return last;
+  }
+};
+__device__ __forceinline__ const RectK &kernarg_rect() {
+  const __attribute__((address_space(4))) char *p = (const __attribute__((address_space(4))) char *)__builtin_amdgcn_kernarg_segment_ptr();
+  asm volatile("" : "+s"(p));
+  return *(const RectK *)(p + KernargLast<decltype(&k_render_fwd_pk<1, true, 1>)>::offset());
+}
+struct FwdPkArgs { int fp16; void *img; char *cache; uint32_t off[3], cap_stray; const float *adj_gimg; float *adj_gtex, *adj_dot; bool plain = false; RectK rk = {}; };
 // ADJ: k_render_fwd_pk's ADJ (0 / 1), or 2 for the box film's route, which takes the fused adjoint iff a.adj_gtex
 template <int ADJ, bool RF = false, bool RFC = false>
 static void launch_fwd_pk(bool wide, const RenderSetup &r, const Packets &p, const float *tex, const FwdPkArgs &a, hipStream_t s) {
@@ -5808,7 +5966,7 @@ static void launch_fwd_pk(bool wide, const RenderSetup &r, const Packets &p, con
         __atomic_fetch_add(&ffx_k8_instance_launches[PLAIN ? 0 : 1], 1ull, __ATOMIC_RELAXED);
         hipLaunchKernelGGL((k_render_fwd_pk<1, WIDE, MATM, A, RF, RFC, PLAIN, CACHE>), dim3(p.pgrid), dim3(64), 0, s, r.c, r.b.nodes, r.b.recs, p.arecs, p.astride, p.ws,
                            r.c.mats, tex, r.spp, r.seed_key, p.ptx, p.pn, xcd_mode(r.n_pix), a.fp16, a.img, a.cache, p.ppw, 1.0f / (float)r.spp, a.off[0],
-                           a.off[1], a.off[2], r.b.nrec, r.b.gn, a.cap_stray, a.adj_gimg, a.adj_gtex, a.adj_dot);
+                           a.off[1], a.off[2], r.b.nrec, r.b.gn, a.cap_stray, a.adj_gimg, a.adj_gtex, a.adj_dot, a.rk);
       };
       if constexpr ((WIDE || !RF) && (MATM < 2 || (!A && !RFC))) {
         if constexpr (ADJ == 2 && MATM == 1) { // (the box film's route: the only one with plain-scene instances — forward, forward + adjoint, cache-writing forward)
@@ -6011,7 +6169,12 @@ static int render_fwd_impl(const void *bvh, const ffx_bvh_info *info, const ffx_
       FFX_CHECK_LAUNCH("render_fwd (pixel blocks)");
       return FFX_OK;
     }
-    launch_fwd_pk<2>(use_wide(info), r, p, tex, {img_fp16, img, (char *)cache, {foot_off, arena_off, foot_b_off}, cap_stray, adj_gimg, adj_gtex, adj_dot, plain_scene(r, sd, bvh, info, img_fp16)}, st);
+    // (a plain scene AND the film's rectangle tables at hand, which the plain instances read: rect_tables)
+    RectK rk = {};
+    // (the cache-writing plain forward — a cache and no fused adjoint — reads no table: launch_fwd_pk's choice of instance)
+    const bool reads_tables = FFX_K8_RECTTAB && (adj_gtex || !cache);
+    const bool plain = plain_scene(r, sd, bvh, info, img_fp16) && (!reads_tables || rect_tables(r.c, rk, st));
+    launch_fwd_pk<2>(use_wide(info), r, p, tex, {img_fp16, img, (char *)cache, {foot_off, arena_off, foot_b_off}, cap_stray, adj_gimg, adj_gtex, adj_dot, plain, rk}, st);
     FFX_CHECK_LAUNCH("render_fwd");
     return FFX_OK;
   }
